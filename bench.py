@@ -20,6 +20,15 @@ excluded).
 
 Contract: python bench.py --gpus N --steps K --warmup W ; for N > 1 the driver launches it under
 torch.distributed.run (one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the line (`value`, `ms_per_step`, the
+per-stage HIP-event times of the timed steps and the rooflines derived from them).  Everything else it can measure or check runs
+only with --full: the CPU baseline, the PCIe-inclusive end_to_end object, the HBM streaming probe, the sustained loop,
+first_encode, the weak-scaling figure and the halo self-check of N > 1.
+
+--dump-outputs DIR: after the timed steps, every rank writes what its last step computed (the buffers svc_clip_output hands a
+caller) as DIR/<name>.npy in float32, at most 64 MB in all: the per-block results whole while they fit, the coefficient planes
+(records with --wire) as a fixed, seeded sample of their elements.  Same arguments, same inputs, same files.
 """
 from __future__ import annotations
 
@@ -405,14 +414,52 @@ def _checksum(x: torch.Tensor) -> int:
     return int((x.to(torch.int64) * w).sum().item())
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: the payload of all files of all ranks (under 64 MB with the .npy headers)
+DUMP_SEED = 0x5EED0D0
+
+
+def _seeded_sample(flat: torch.Tensor, k: int) -> torch.Tensor:
+    """k elements of `flat` at sorted indices drawn from a fixed seed (the same indices for the same length, run after run)."""
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(0, flat.numel(), (k,), generator=g, dtype=torch.int64).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(enc, out_dir: str, wire: bool, budget_bytes: int, prefix: str = "") -> None:
+    """What the newest finished step computed, as out_dir/<prefix><name>.npy (float32), `budget_bytes` in all: the coefficient planes
+    (records with --wire) as a seeded sample of an eighth of the budget, the per-block results (MVs, min-MADs, global motion, RMSE,
+    inlier masks and counts, region ids) whole while they fit in the rest.  An array larger than its share of what is left is sampled
+    the same way."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    arrays = enc.outputs(device=dev)
+    big = "records" if wire else "coeffs"
+    arrays[big] = enc.read(big, device=dev)
+    coeff_sample = budget_bytes // 4 // 8
+    budget = budget_bytes // 4 - min(arrays[big].numel(), coeff_sample)
+    small = sorted((n for n in arrays if n != big), key=lambda n: arrays[n].numel())
+    for j, name in enumerate(small):  # smallest first: each takes all of itself or its fair share of what is left
+        a = arrays[name]
+        share = budget // (len(small) - j)
+        arrays[name] = a if a.numel() <= share else _seeded_sample(a.reshape(-1), share)
+        budget -= arrays[name].numel()
+    a = arrays[big]
+    arrays[big] = a if a.numel() <= coeff_sample else _seeded_sample(a.reshape(-1), coeff_sample)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a.to(torch.float32).cpu().numpy())
+    del arrays
+
+
 def hbma_flags_of(args) -> int:
     return {"auto": native.HBMA_AUTO, "tiled": native.HBMA_FORCE_TILED, "lane": native.HBMA_FORCE_LANE,
             "wave": native.HBMA_FORCE_WAVE_PER_BLOCK}[args.hbma_kernel]
 
 
-def run_mode(args, cfg, mode: str, rank: int, world: int, dev, backend: str, comm):
+def run_mode(args, cfg, mode: str, rank: int, world: int, dev, backend: str, comm, dump: bool = False):
     """Builds this rank's shard for `mode` ("strong": cfg.frames cut over the ranks; "weak": cfg.frames per rank),
-    runs W warm-up and exactly K timed steps between barriers, returns the measurements of this rank."""
+    runs W warm-up and exactly K timed steps between barriers, returns the measurements of this rank (`dump`: and writes
+    what the last timed step computed to --dump-outputs)."""
     n_cfg = args.frames or cfg.frames
     clip_frames = n_cfg if mode == "strong" else n_cfg * world
     schedule = clipmod.SERIAL if args.schedule == "serial" else clipmod.PIPELINED
@@ -457,7 +504,7 @@ def run_mode(args, cfg, mode: str, rank: int, world: int, dev, backend: str, com
     for _ in range(max(args.warmup, 1 if world > 1 else 0)):
         enc.step()
     enc.sync()
-    if world > 1:
+    if world > 1 and args.full:
         # the halo that arrived must be the predecessor's last pyramid: checked once, outside the timed region
         pyr = enc.read("pyramids", device=dev)
         stride = info.pyramid_stride
@@ -491,6 +538,8 @@ def run_mode(args, cfg, mode: str, rank: int, world: int, dev, backend: str, com
     enc.sync()
     barrier()
     elapsed = time.perf_counter() - t0
+    if dump and args.dump_outputs:
+        dump_outputs(enc, args.dump_outputs, args.wire, DUMP_BYTES // world, f"rank{rank}_" if world > 1 else "")
     pol1 = enc.policy_info()
     chunks = enc.info.chunks_per_step
     policy = {"chunk_launches": args.steps * chunks, "had_the_choice": pol1["chunks_decided"] - pol0["chunks_decided"],
@@ -677,8 +726,8 @@ def main() -> None:
     ap.add_argument("--schedule", choices=("pipelined", "serial"), default="pipelined",
                     help="pipelined: software pipeline over consecutive steps (HBM-bound kernels back to back on one stream, RANSAC + "
                          "segmentation of the previous step beside them, halo in flight meanwhile); serial: one stream, stages back to back")
-    ap.add_argument("--scaling", choices=("both", "strong", "weak"), default="both",
-                    help="N > 1: which shardings to measure (default: strong = the BASELINE config 4/5 workload, then weak)")
+    ap.add_argument("--scaling", choices=("both", "strong", "weak"), default=None,
+                    help="N > 1: which shardings to measure (default: strong = the BASELINE config 4/5 workload; with --full, then weak)")
     ap.add_argument("--no-segmentation", action="store_true",
                     help="region ids from the in-repo part only (foreground = one region) instead of the full segmentation glue")
     ap.add_argument("--wire", action="store_true", help="emit the serialised records of libs/encoder.cpp:222-269 (fused into the DCT kernel) instead of coefficient planes")
@@ -701,7 +750,7 @@ def main() -> None:
     ap.add_argument("--chunk-pairs", type=int, default=0,
                     help="pipelined, one rank: frame pairs per chunk of EVERY step (0 = whole-shard launches, with the idle-pipeline rule for a step "
                          "that finds the pipeline empty)")
-    ap.add_argument("--first-encode-reps", type=int, default=8, help="N = 1: repetitions of {load the clip, ONE step, sync} behind first_encode (0 = skip)")
+    ap.add_argument("--first-encode-reps", type=int, default=8, help="N = 1, --full: repetitions of {load the clip, ONE step, sync} behind first_encode (0 = skip)")
     ap.add_argument("--time-every", type=int, default=4, help="record the per-stage HIP events on every n-th timed step (every step when --steps < 8)")
     # A/B switches (svc_clip_config tuning fields): kernel choice and launch shapes only, results never change.  The
     # environment variables of the round-2 scripts under tools/ are honoured HERE as defaults, not inside the library.
@@ -715,20 +764,31 @@ def main() -> None:
     ap.add_argument("--segment-fork", action="store_true", default=os.environ.get("SVC_LAUNCH_NO_FORK", "1") == "0",
                     help="pipelined: let the segmentation fork its heavy attempts to a side stream")
     ap.add_argument("--sustain-seconds", type=float, default=3.0,
-                    help="N = 1: after the timed steps, run back-to-back steps for this long and report sustained_ms_per_step (0 = skip)")
+                    help="N = 1, --full: after the timed steps, run back-to-back steps for this long and report sustained_ms_per_step (0 = skip)")
     ap.add_argument("--inline-rmse", action="store_true",
                     help="pipelined: RANSAC keeps its in-order RMSE sum inside its kernel (A/B of the deferred form)")
     ap.add_argument("--narrow-attempts", action="store_true",
                     help="segmentation: one workgroup per (frame, k-means attempt) even on small shards of large fields (A/B of the multi-launch form)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, end_to_end, the HBM streaming probe, the sustained loop, first_encode, "
+                         "and for N > 1 the weak-scaling figure and the halo self-check (the --no-* switches below refine such a run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32, at most 64 MB in all; "
+                         "the coefficient planes as a fixed, seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-hbm-probe", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="N = 1: skip the PCIe-inclusive end_to_end object (measured outside the timed region)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="N = 1, --full: skip the PCIe-inclusive end_to_end object (measured outside the timed region)")
     ap.add_argument("--end-to-end", action="store_true",
-                    help="N = 1: measure end_to_end also on a shortened clip (--frames): by default only the full-length run does (it writes "
+                    help="N = 1, --full: measure end_to_end also on a shortened clip (--frames): by default only the full-length run does (it writes "
                          "~1.2 GB of clips to /dev/shm and starts four child processes on the GPU)")
     args = ap.parse_args()
     if args.frames and not args.end_to_end:
         args.no_end_to_end = True
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the line -- nothing beside the headline
+        args.no_cpu_baseline = args.no_end_to_end = args.no_hbm_probe = True
+        args.sustain_seconds, args.first_encode_reps = 0.0, 0
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "strong"
 
     if args.gpus < 1:
         raise SystemExit(f"--gpus {args.gpus}: need at least one")
@@ -801,7 +861,7 @@ def main() -> None:
 
     cfg = configs.ALL[args.config]
     modes = ["strong"] if world == 1 else (["strong", "weak"] if args.scaling == "both" else [args.scaling])
-    results = {m: run_mode(args, cfg, m, rank, world, dev, backend, comm) for m in modes}
+    results = {m: run_mode(args, cfg, m, rank, world, dev, backend, comm, dump=m == modes[0]) for m in modes}
 
     rccl_mismatch = False
     if rank == 0:

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def _run(*args):
 
 
 def test_bench_line_contract():
-    d = _run("--frames", "12", "--steps", "2", "--warmup", "1", "--end-to-end")
+    d = _run("--frames", "12", "--steps", "2", "--warmup", "1", "--end-to-end", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -103,6 +104,26 @@ def test_bench_line_contract():
     assert abs(s["value"] - d["config"]["encoded_frames_per_step"] / (s["ms_per_step"] * 1e-3)) <= 1e-6 * s["value"]
 
 
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes what the last timed step
+    computed, float32, under 64 MB, the same files for the same arguments (the coefficient planes as a fixed sample)."""
+    args = ("--frames", "12", "--steps", "3", "--warmup", "1")
+    a = _run(*args, "--dump-outputs", str(tmp_path / "a"))
+    b = _run(*args, "--dump-outputs", str(tmp_path / "b"))
+    for d in (a, b):
+        assert d["steps"] == 3 and d["value"] > 0 and abs(d["ms_per_step"] * 1e-3 * d["value"] - d["config"]["encoded_frames_per_step"]) <= 1e-6 * d["value"]
+        assert not {"cpu_baseline", "end_to_end", "hbm_streaming_measured", "sustained", "first_encode", "weak"} & set(d), sorted(d)
+    names = {"mv", "min_mad", "global_motion", "rmse", "inlier_mask", "inlier_count", "block_types", "coeffs"}
+    assert {p.name for p in (tmp_path / "a").iterdir()} == {n + ".npy" for n in names}
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 * 10 ** 6
+    pairs = a["config"]["encoded_frames_per_step"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+    assert np.load(tmp_path / "a" / "mv.npy").shape[:1] == np.load(tmp_path / "a" / "block_types.npy").shape[:1] == (pairs,)
+    assert np.load(tmp_path / "a" / "coeffs.npy").ndim == 1 and np.abs(np.load(tmp_path / "a" / "coeffs.npy")).max() > 0
+
+
 def test_single_rank_under_the_launcher_is_the_plain_run():
     """The scaling driver launches N = 1 through torch.distributed.run like every other N: same code path, same line
     (world size 1: no process group, no halo, `scaling` weak) -- so SCALE's N = 1 agrees with BENCH by construction."""
@@ -137,7 +158,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     env = dict(os.environ, SVC_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29513", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "9", "--steps", "3",
-                        "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--warmup", "2", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -173,7 +194,7 @@ def test_bench_halo_check_failure_is_collective():
     # bench.py itself carries no fault hook: tests/helpers/bench_corrupt_halo.py wraps its halo transport and runs its main()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29519", os.path.join(ROOT, "tests", "helpers", "bench_corrupt_halo.py"), "--gpus", "2", "--frames", "9", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+                        "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode != 0
     assert "halo self-check failed on rank(s) [1]" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
 

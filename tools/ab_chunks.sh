@@ -3,7 +3,7 @@
 # rounds 2-5).  Per setting: the steady-state figure (`value`: K back-to-back steps) and what a clip encoded once costs (first_encode).
 set -eu
 cd "$GRAFT_REPO_ROOT"
-run() { python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-probe --no-end-to-end --sustain-seconds 0 "$@" 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-probe --no-end-to-end --sustain-seconds 0 "$@" 2>/dev/null | python3 -c "
 import json,sys; d=json.load(sys.stdin); k=d['kernel_ms_per_step']; f=d['first_encode']
 print(' ', d['config']['workload'][:16], 'chunks', d['config']['chunks_per_step'], 'steady ms', round(d['ms_per_step'],3), 'kernels', round(sum(k.values()),3),
       '| once-through ms', round(f['once_through']['ms_median'],3), '(min', round(f['once_through']['ms_min'],3), ') with prior', round(f['with_prior']['ms_median'],3),

@@ -11,7 +11,7 @@ for r in $(seq 1 ${1:-3}); do
 for c in C3-1080p-3L-dct8-quant C3b-1080p-4L-dct8-quant C5-4k-4L-dct16; do
   for f in "--mixed-steps" "" "--whole-shard-steps"; do
     echo "== $c ${f:-as built (two-pass halves)}"
-    python3 bench.py --config $c $f --no-cpu-baseline --no-end-to-end --sustain-seconds 0 --no-hbm-probe 2>/dev/null | python3 -c "$pick"
+    python3 bench.py --full --config $c $f --no-cpu-baseline --no-end-to-end --sustain-seconds 0 --no-hbm-probe 2>/dev/null | python3 -c "$pick"
   done
 done
 done

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Performance expectations of a bench.py line -- a REPORT, never a gate.
 
-    python3 bench.py > line.json && python3 tools/perf_expectations.py line.json
+    python3 bench.py --full > line.json && python3 tools/perf_expectations.py line.json
 
 Every inequality on a measured time or rate that used to sit in tests/test_gpu_bench_contract.py lives here instead (round 4:
 one of them, evaluated on a 12-frame 2-step cold run, stopped the driver's `pytest -x` before any parity test).  The exit code
