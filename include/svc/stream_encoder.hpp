@@ -46,6 +46,9 @@ struct StreamEncoderConfig {
   uint64_t seed = 0;
   svc_ransac_params ransac{1, 7.5f, 0.99f, 0.5f};
   svc_segment_params segment{3, 3, 10, 3, 10, 1.0f, 4};
+  bool compact = false;            // the quantised planes leave as the compact stream of include/svc_hip.h ("SVCQ": masks + int16
+                                   // levels, ~1 MB instead of 25 MB per 1080p frame): packed on the device, drained by a kernel;
+                                   // EncodedBatch::compact instead of coeffs.  Not with `wire`
 };
 
 // One finished batch; the pointers are pinned host memory owned by the encoder and stay valid
@@ -63,6 +66,9 @@ struct EncodedBatch {
   uint64_t record_bytes = 0;
   const svc_wire_header* header = nullptr;  // wire == true, first batch of a clip only: the 32 bytes that
                                             // open the reference's stream (libs/codec.hpp:8-17, encoder.cpp:360-381)
+  const uint8_t* compact = nullptr;           // compact == true: `count` frames of the compact stream back to back (coeffs is null)
+  const uint64_t* compact_offsets = nullptr;  // [count + 1]: frame i in [offsets[i], offsets[i + 1])
+  uint64_t compact_bytes = 0;                 // = compact_offsets[count]
 };
 
 // Where the time of one Encode() went (round 6: the PCIe-inclusive rate explains itself).  Host clocks are wall time of the CALLING thread;
@@ -78,7 +84,7 @@ struct EncodeStats {
   double deliver_wait_ms = 0;  // host: waiting for a batch's results before handing it to the sink
   double sink_ms = 0;          // host: inside the caller's sink
   double h2d_ms = 0, kernels_ms = 0, d2h_ms = 0;  // device, per stream
-  uint64_t h2d_bytes = 0, d2h_bytes = 0;
+  uint64_t h2d_bytes = 0, d2h_bytes = 0;  // bytes actually moved (compact: the used bytes of the stream)
 };
 
 class StreamEncoder {

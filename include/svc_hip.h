@@ -395,6 +395,76 @@ int svc_hip_sse_frames(const uint8_t* d_src_bgr, uint64_t src_frame_stride_bytes
                        void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Compact quantised-coefficient stream ("SVCQ", format version 1; the ABI version does not
+ * change).  Quantised planes are almost all zeros; a frame goes out as a significance mask per
+ * tile plus the non-zero levels as int16.  Little-endian; every frame starts on a 16-byte
+ * boundary and frames sit back to back:
+ *   header  64 B = 16 x u32: 0x51435653 ("SVCQ"), 1, frame_w, frame_h, block_w, block_h,
+ *           mv_block_w, mv_block_h, fg_step, bg_step, level_count (non-zero levels),
+ *           inexact (coefficients != level * step; 0 for quantised planes), frame_bytes
+ *           (padding included), 0, 0, 0
+ *   types   [mv_field_h][mv_field_w] u32, the region ids the planes were quantised with
+ *   masks   [3 planes B,G,R][tiles_y][tiles_x][ceil(block_w * block_h / 64)] u64; bit i of word w
+ *           = coefficient w * 64 + i of the tile in row-major order (r * block_w + c), set when
+ *           the level is non-zero; bits past block_w * block_h are 0
+ *   levels  level_count x i16, by plane, then tile (raster order), then coefficient
+ *   pad     zero bytes up to a multiple of 16
+ * level = std::round(c / step) clamped to int16, step = the type of the MV block holding the
+ * tile origin == 0 ? bg_step : fg_step (the rule of svc_hip_dct_quant_frames); a coefficient
+ * decodes to (float)level * (float)step.  Quantised planes round-trip as numbers (-0.0 comes
+ * back as +0.0).  Geometry as svc_hip_dct_quant_frames takes it, tiles up to 4096
+ * coefficients.  The three device entry points only enqueue work.
+ * ------------------------------------------------------------------------- */
+
+/* Worst case of a batch: n_frames x (64 + 4 * mv blocks + masks + 2 * 3 * W * H), each frame
+ * rounded up to 16.  0 (svc_hip_last_error() says why) for a geometry the pack refuses. */
+uint64_t svc_hip_levels_max_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                  uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                  uint32_t mv_block_h);
+
+/* Scratch of svc_hip_pack_levels_frames and svc_hip_unpack_levels_frames; 0 for a geometry they refuse.
+ * The three calls below check geometry, steps, limits and sizes before anything else, for any
+ * n_frames (n_frames == 0 then returns SVC_OK), and only then their pointers. */
+uint64_t svc_hip_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w,
+                                             uint32_t frame_h, uint32_t block_w,
+                                             uint32_t block_h);
+
+/* d_planes [n_frames][3][H][W] f32 + d_block_types [n_frames][mv blocks] -> frames back to back
+ * at d_out (out_capacity >= svc_hip_levels_max_bytes) and d_frame_offsets [n_frames + 1] u64
+ * (offsets[n_frames] = bytes used).  SVC_ERR_INVALID_ARG for a step of 0,
+ * SVC_ERR_UNSUPPORTED when 255 * sqrt(block_w * block_h) / min(fg_step, bg_step) > 32767
+ * (Parseval's bound on a coefficient: a level could leave int16). */
+int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_types,
+                               uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                               uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                               uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                               uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
+                               uint64_t out_capacity, uint64_t* d_frame_offsets, void* stream);
+
+/* The inverse: stream_bytes of frames at d_frames, frame f at d_frame_offsets[f] -> planes
+ * [n_frames][3][H][W] f32 (0 wherever a mask bit is 0) and d_block_types.  Each header is
+ * checked against the geometry passed here and against the offsets; d_status [n_frames] u32:
+ * 0 ok, 1 offsets out of range, 2 magic, 3 version, 4 geometry or a step of 0, 5 frame size,
+ * 6 level count != the masks' popcount, 7 mask bits set past block_w * block_h.  A frame that
+ * fails is written as zeros. */
+int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                 const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                 uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                 uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                 uint8_t* d_workspace, uint64_t workspace_bytes, float* d_planes,
+                                 uint32_t* d_block_types, uint32_t* d_status, void* stream);
+
+/* Copies exactly d_frame_offsets[n_frames] bytes (read on the device: no host sync) from
+ * d_frames to host_dst by a kernel.  host_dst must be pinned (hipHostMalloc) or registered
+ * (hipHostRegister) host memory, 16-byte aligned, of capacity >= svc_hip_levels_max_bytes for
+ * this geometry, and all `capacity` bytes must lie in that one allocation; anything else is
+ * SVC_ERR_INVALID_ARG before any launch. */
+int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offsets,
+                         uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                         uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                         uint32_t mv_block_h, void* host_dst, uint64_t capacity, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Pre-step: luma + pyramid on the device, so the pyramid never
  * crosses PCIe.  Stands in for cv::cvtColor(BGR2YUV) + cv::extractChannel +
  * cv::buildPyramid (libs/encoder.cpp:468-470) with this repo's fixed-point

@@ -55,7 +55,10 @@ template <typename T> struct PinBuf {
 };
 
 struct Slot {
-  DevBuf<uint8_t> bgr, pyr, mask, seg_ws, records;
+  DevBuf<uint8_t> bgr, pyr, mask, seg_ws, records, packed, pack_ws;
+  DevBuf<uint64_t> offsets;
+  PinBuf<uint8_t> pin_packed;
+  PinBuf<uint64_t> pin_offsets;
   DevBuf<float> mv, mad, gm, rmse, coeffs;
   DevBuf<uint32_t> count, types, samples;
   PinBuf<uint32_t> pin_samples;
@@ -81,6 +84,7 @@ struct StreamEncoder::Impl {
   uint32_t pw = 0, ph = 0, mfw = 0, mfh = 0, blocks = 0, iters = 0;
   uint32_t bw = 0, bh = 0, tw = 0, th = 0;  // MV block and transform block sides
   uint64_t pyr_stride = 0, frame_bytes = 0, plane_elems = 0, record_bytes = 0, seg_ws_bytes = 0;
+  uint64_t packed_bytes = 0, pack_ws_bytes = 0;  // compact: worst case of a batch, pack workspace
   std::vector<std::unique_ptr<Slot>> slots;
   hipStream_t s_in = nullptr, s_compute = nullptr, s_out = nullptr;
   bool fused_records = false;  // wire: the transform kernel emits the records itself
@@ -103,6 +107,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   m.bw = c.mv_block; m.bh = c.mv_block_h ? c.mv_block_h : c.mv_block;
   m.tw = c.dct_block; m.th = c.dct_block_h ? c.dct_block_h : c.dct_block;
   if (!m.tw || !m.th) throw std::runtime_error("svc::StreamEncoder: invalid configuration");
+  if (c.compact && c.wire) throw std::runtime_error("svc::StreamEncoder: compact is a form of the quantised planes, not of the wire records");
   m.pw = ClosestLargerDivisible(c.width, m.bw, f);   // libs/encoder.cpp:164-168
   m.ph = ClosestLargerDivisible(c.height, m.bh, f);
   m.mfw = m.pw / m.bw; m.mfh = m.ph / m.bh; m.blocks = m.mfw * m.mfh;
@@ -117,6 +122,11 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   m.fused_records = c.wire && m.tw == m.th && (!c.reference_stream || m.pw == c.width);
   m.iters = svc_hip_ransac_iter_count(c.ransac);
   m.seg_ws_bytes = svc_hip_segment_workspace_bytes(m.mfw, m.mfh, c.batch, c.segment.attempt_count);
+  if (c.compact) {
+    m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
+    m.pack_ws_bytes = svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
+    if (!m.packed_bytes || !m.pack_ws_bytes) throw std::runtime_error("svc::StreamEncoder: no compact stream for this geometry");
+  }
   m.crew.reset(new CopyCrew(std::min<uint32_t>(c.copy_threads ? c.copy_threads - 1 : 0, 15)));
   Hip(hipStreamCreateWithFlags(&m.s_in, hipStreamNonBlocking), "hipStreamCreate");
   Hip(hipStreamCreateWithFlags(&m.s_compute, hipStreamNonBlocking), "hipStreamCreate");
@@ -138,7 +148,11 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     Hip(hipMemset(s->samples.p, 0, std::max<size_t>(B * m.iters * c.ransac.subset_sz, 1) * sizeof(uint32_t)), "hipMemset");
     if (c.wire) { s->records.Alloc(B * m.record_bytes); s->pin_records.Alloc(B * m.record_bytes); }
     if (!c.wire || !m.fused_records) s->coeffs.Alloc(B * 3 * m.plane_elems);
-    if (!c.wire) s->pin_coeffs.Alloc(B * 3 * m.plane_elems);
+    if (!c.wire && !c.compact) s->pin_coeffs.Alloc(B * 3 * m.plane_elems);
+    if (c.compact) {
+      s->packed.Alloc(m.packed_bytes); s->pack_ws.Alloc(m.pack_ws_bytes); s->offsets.Alloc(B + 1);
+      s->pin_packed.Alloc(m.packed_bytes); s->pin_offsets.Alloc(B + 1);
+    }
     Hip(hipEventCreateWithFlags(&s->h2d_done, hipEventDisableTiming), "hipEventCreate");
     Hip(hipEventCreateWithFlags(&s->compute_done, hipEventDisableTiming), "hipEventCreate");
     Hip(hipEventCreateWithFlags(&s->d2h_done, hipEventDisableTiming), "hipEventCreate");
@@ -189,6 +203,7 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     Hip(hipEventElapsedTime(&ms, s.t_k[0], s.t_k[1]), "hipEventElapsedTime"); st.kernels_ms += ms;
     Hip(hipEventElapsedTime(&ms, s.t_out[0], s.t_out[1]), "hipEventElapsedTime"); st.d2h_ms += ms;
     st.h2d_bytes += s.h2d_bytes; st.d2h_bytes += s.d2h_bytes;
+    if (c.compact) st.d2h_bytes += s.pin_offsets.p[s.encoded];  // the drain moved exactly the used bytes
     ++st.batches; st.encoded_frames += s.encoded;
     t0 = Clock::now();
     EncodedBatch b;
@@ -196,7 +211,10 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     b.first_frame = s.first; b.count = s.encoded;
     b.padded_w = m.pw; b.padded_h = m.ph; b.mv_field_w = m.mfw; b.mv_field_h = m.mfh;
     b.mv_xy = s.pin_mv.p; b.global_motion = s.pin_gm.p; b.block_types = s.pin_types.p;
-    b.coeffs = c.wire ? nullptr : s.pin_coeffs.p;
+    b.coeffs = c.wire || c.compact ? nullptr : s.pin_coeffs.p;
+    if (c.compact) {
+      b.compact = s.pin_packed.p; b.compact_offsets = s.pin_offsets.p; b.compact_bytes = s.pin_offsets.p[s.encoded];
+    }
     b.records = c.wire ? s.pin_records.p : nullptr;
     b.record_bytes = m.record_bytes;
     sink(b);
@@ -283,19 +301,29 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     } else {
       Abi(svc_hip_dct_quant_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.types.p, m.bw,
                                    m.bh, c.fg_step, c.bg_step, s.coeffs.p, m.s_compute), "svc_hip_dct_quant_frames");
+      if (c.compact)
+        Abi(svc_hip_pack_levels_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step,
+                                       s.pack_ws.p, m.pack_ws_bytes, s.packed.p, m.packed_bytes, s.offsets.p, m.s_compute),
+            "svc_hip_pack_levels_frames");
     }
     Hip(hipEventRecord(s.t_k[1], m.s_compute), "hipEventRecord");
     Hip(hipEventRecord(s.compute_done, m.s_compute), "hipEventRecord");
 
     Hip(hipStreamWaitEvent(m.s_out, s.compute_done, 0), "hipStreamWaitEvent");
     Hip(hipEventRecord(s.t_out[0], m.s_out), "hipEventRecord");
-    s.d2h_bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : 3 * m.plane_elems * sizeof(float)));
+    s.d2h_bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : c.compact ? 0 : 3 * m.plane_elems * sizeof(float)));
+    if (c.compact) s.d2h_bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t);  // + the stream's used bytes, known at delivery
     Hip(hipMemcpyAsync(s.pin_mv.p, s.mv.p, (size_t)encoded * m.blocks * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H mv");
     Hip(hipMemcpyAsync(s.pin_types.p, s.types.p, (size_t)encoded * m.blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "D2H types");
     Hip(hipMemcpyAsync(s.pin_gm.p, s.gm.p, (size_t)encoded * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H gm");
     if (c.wire)
       Hip(hipMemcpyAsync(s.pin_records.p, s.records.p, (size_t)encoded * m.record_bytes, hipMemcpyDeviceToHost, m.s_out), "D2H records");
-    else
+    else if (c.compact) {  // the used bytes only: the count is on the device, the drain kernel reads it there
+      Abi(svc_hip_levels_drain(s.packed.p, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_packed.p, m.packed_bytes,
+                               m.s_out), "svc_hip_levels_drain");
+      Hip(hipMemcpyAsync(s.pin_offsets.p, s.offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, m.s_out),
+          "D2H offsets");
+    } else
       Hip(hipMemcpyAsync(s.pin_coeffs.p, s.coeffs.p, (size_t)encoded * 3 * m.plane_elems * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H coeffs");
     Hip(hipEventRecord(s.t_out[1], m.s_out), "hipEventRecord");
     Hip(hipEventRecord(s.d2h_done, m.s_out), "hipEventRecord");

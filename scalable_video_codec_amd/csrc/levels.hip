@@ -1,0 +1,590 @@
+// levels.hip -- the compact quantised-coefficient stream ("SVCQ", version 1): pack, unpack, drain.
+//
+// Quantised planes are almost all zeros (a C3 background tile-channel holds about one non-zero level), so a frame is sent as
+// a significance mask per tile plus the non-zero levels as int16 -- about 1 MB instead of the 25 MB of f32 planes at 1080p.
+// Layout of one frame (little-endian, 16-byte aligned, frames back to back; include/svc_hip.h has the table):
+//   header 16 x u32 | types [mv blocks] u32 | masks [3][tiles_y][tiles_x][words] u64 | levels [level_count] i16 | zero pad to 16
+//
+// Work split, pack and unpack alike: a workgroup owns a GROUP = one plane, one tile row, up to `tpg` adjacent tiles (about 2048
+// coefficients).  It stages the group's rows in LDS with 16-byte loads (the planes are row-major: one 8x8 tile per wave would
+// read 32-byte pieces), then one wave per 64-coefficient mask word: the word is a __ballot, a lane's rank among the non-zero
+// levels is mbcnt + the popcounts of the earlier words.  The only variable-size section is the levels, so each direction is
+//   count   (per group: non-zero levels)  ->  scan (per frame: exclusive scan of the group sums, frame size)  ->  scatter.
+// The frame offsets are not scanned by a kernel of their own: the scatter's workgroup sums the frame sizes before its own
+// frame (a batch is a few dozen frames).  Group order = (plane, tile row, group in the row) = the order of the levels.
+#include "svc_common.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace svc {
+namespace {
+
+constexpr uint32_t kMagic = 0x51435653u;  // "SVCQ"
+constexpr uint32_t kVersion = 1;
+constexpr uint32_t kHeaderBytes = 64;
+constexpr uint32_t kMaxTileCoeffs = 4096;  // a tile fits one group's LDS; the Dct's largest tile is 64 x 64
+constexpr uint32_t kGroupCoeffs = 2048;    // coefficients a workgroup stages
+constexpr uint32_t kMaxJobs = 256;         // mask words per group
+constexpr uint32_t kThreads = 256;
+
+// unpack's per-frame status word
+enum : uint32_t { kStOk = 0, kStRange = 1, kStMagic = 2, kStVersion = 3, kStGeometry = 4, kStSize = 5, kStLevels = 6, kStStrayBits = 7 };
+
+struct Geom {
+  uint32_t w, h, bw, bh, mvbw, mvbh, mfw, mvb;
+  uint32_t tiles_x, tiles_y, words, tpg, gx, groups;  // words per tile, tiles per group, groups per tile row, groups per frame
+  uint32_t pitch_pad;                                // LDS row pitch = cols + ((pitch_pad - cols) & 63): conflict-free word reads
+  uint64_t masks_off, levels_off;                    // byte offsets inside a frame
+  bool vec;                                          // rows may be moved as float4
+};
+
+__host__ __device__ inline uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
+
+Geom make_geom(uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  Geom g{};
+  g.w = w; g.h = h; g.bw = bw; g.bh = bh; g.mvbw = mvbw; g.mvbh = mvbh;
+  g.mfw = w / mvbw; g.mvb = g.mfw * (h / mvbh);
+  g.tiles_x = w / bw; g.tiles_y = h / bh;
+  const uint32_t area = bw * bh;
+  g.words = (area + 63) / 64;
+  uint32_t tpg = std::max<uint32_t>(1, kGroupCoeffs / area);
+  tpg = std::max<uint32_t>(1, std::min<uint32_t>(tpg, kMaxJobs / g.words));  // (tiles above kMaxTileCoeffs are refused)
+  if (tpg > 1) tpg &= ~1u;  // even: a group's first column (tile side even) is then a multiple of 4 floats
+  g.tpg = std::min(tpg, g.tiles_x);
+  g.gx = div_up(g.tiles_x, g.tpg);
+  g.groups = 3 * g.tiles_y * g.gx;
+  g.pitch_pad = bw & 63;
+  g.masks_off = kHeaderBytes + 4ull * g.mvb;
+  g.levels_off = g.masks_off + 8ull * 3 * g.tiles_x * g.tiles_y * g.words;
+  g.vec = w % 4 == 0 && (g.tpg * bw) % 4 == 0;  // then every group's first column and every plane are 16-byte aligned
+  return g;
+}
+
+uint64_t frame_max_bytes(const Geom& g) { return up16(g.levels_off + 2ull * 3 * g.w * g.h); }
+
+uint32_t lds_bytes(const Geom& g) {
+  const uint32_t cols = g.tpg * g.bw;
+  return g.bh * (cols + ((g.pitch_pad - cols) & 63)) * 4;
+}
+
+// the workspace: per group a count (then its exclusive prefix) and an inexact count (unpack: mask bits set past the tile area);
+// per frame its size, level count, inexact count and unpack status
+struct Ws {
+  uint32_t *cnt, *inexact, *frame_bytes, *frame_levels, *frame_inexact, *status;
+};
+uint64_t ws_bytes(uint32_t n, uint32_t groups) {
+  return 2 * up16(4ull * n * groups) + 4 * up16(4ull * n);
+}
+Ws carve(uint8_t* p, uint32_t n, uint32_t groups) {
+  Ws s;
+  const uint64_t a = up16(4ull * n * groups), b = up16(4ull * n);
+  s.cnt = reinterpret_cast<uint32_t*>(p);
+  s.inexact = reinterpret_cast<uint32_t*>(p + a);
+  s.frame_bytes = reinterpret_cast<uint32_t*>(p + 2 * a);
+  s.frame_levels = reinterpret_cast<uint32_t*>(p + 2 * a + b);
+  s.frame_inexact = reinterpret_cast<uint32_t*>(p + 2 * a + 2 * b);
+  s.status = reinterpret_cast<uint32_t*>(p + 2 * a + 3 * b);
+  return s;
+}
+
+// ---- device helpers ---------------------------------------------------------------------------------------------------------
+
+struct Group {
+  uint32_t plane, ty, t0, nt, x0, y0, cols, pitch;
+};
+
+__device__ __forceinline__ Group group_of(const Geom& g, uint32_t gi) {
+  Group r;
+  const uint32_t per_plane = g.tiles_y * g.gx;
+  r.plane = gi / per_plane;
+  const uint32_t rem = gi - r.plane * per_plane;
+  r.ty = rem / g.gx;
+  r.t0 = (rem - r.ty * g.gx) * g.tpg;
+  r.nt = min(g.tpg, g.tiles_x - r.t0);
+  r.x0 = r.t0 * g.bw;
+  r.y0 = r.ty * g.bh;
+  r.cols = r.nt * g.bw;
+  r.pitch = r.cols + ((g.pitch_pad - r.cols) & 63u);
+  return r;
+}
+
+// the group's bh rows x cols floats of plane p -> LDS (row pitch gr.pitch)
+__device__ __forceinline__ void stage_rows(const Geom& g, const Group& gr, const float* __restrict__ plane, float* lds) {
+  if (g.vec && gr.cols % 4 == 0) {
+    const uint32_t q = gr.cols / 4, n = q * g.bh;
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+      const uint32_t r = i / q, c = (i - r * q) * 4;
+      const float4 v = *reinterpret_cast<const float4*>(plane + (size_t)(gr.y0 + r) * g.w + gr.x0 + c);
+      float* d = lds + r * gr.pitch + c;
+      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    }
+  } else {
+    const uint32_t n = gr.cols * g.bh;
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+      const uint32_t r = i / gr.cols, c = i - r * gr.cols;
+      lds[r * gr.pitch + c] = plane[(size_t)(gr.y0 + r) * g.w + gr.x0 + c];
+    }
+  }
+}
+
+// LDS -> the group's rows of plane p
+__device__ __forceinline__ void store_rows(const Geom& g, const Group& gr, const float* lds, float* __restrict__ plane) {
+  if (g.vec && gr.cols % 4 == 0) {
+    const uint32_t q = gr.cols / 4, n = q * g.bh;
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+      const uint32_t r = i / q, c = (i - r * q) * 4;
+      const float* s = lds + r * gr.pitch + c;
+      *reinterpret_cast<float4*>(plane + (size_t)(gr.y0 + r) * g.w + gr.x0 + c) = make_float4(s[0], s[1], s[2], s[3]);
+    }
+  } else {
+    const uint32_t n = gr.cols * g.bh;
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+      const uint32_t r = i / gr.cols, c = i - r * gr.cols;
+      plane[(size_t)(gr.y0 + r) * g.w + gr.x0 + c] = lds[r * gr.pitch + c];
+    }
+  }
+}
+
+// LDS slot of coefficient k of the group's tile t
+__device__ __forceinline__ uint32_t lds_index(const Geom& g, const Group& gr, uint32_t t, uint32_t k) {
+  const uint32_t r = k / g.bw, c = k - r * g.bw;
+  return r * gr.pitch + t * g.bw + c;
+}
+
+// region id of the MV block holding the tile origin (the rule of svc_hip_dct_quant_frames)
+__device__ __forceinline__ uint32_t tile_type(const Geom& g, const uint32_t* __restrict__ types, const Group& gr, uint32_t t) {
+  return types[(gr.y0 / g.mvbh) * g.mfw + (gr.x0 + t * g.bw) / g.mvbw];
+}
+
+// std::round(c / step) (the quantiser's level), clamped to int16
+__device__ __forceinline__ int32_t level_of(float c, float step) {
+  const float q = roundf(c / step);
+  return (int32_t)fminf(fmaxf(q, -32768.f), 32767.f);
+}
+
+__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// exclusive scan of v over the workgroup's 256 threads; *total gets the sum
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds4, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t x = v;
+  for (uint32_t off = 1; off < 64; off <<= 1) {
+    const uint32_t y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  if (lane == 63) lds4[wave] = x;
+  __syncthreads();
+  uint32_t base = 0, sum = 0;
+  for (uint32_t i = 0; i < kThreads / 64; ++i) {
+    const uint32_t s = lds4[i];
+    if (i < wave) base += s;
+    sum += s;
+  }
+  __syncthreads();
+  *total = sum;
+  return base + x - v;
+}
+
+// unpack: is frame f well formed for geometry g inside a stream of stream_bytes?  Returns a status, fills *off / *hdr
+__device__ uint32_t check_frame(const Geom& g, const uint8_t* __restrict__ in, uint64_t stream_bytes,
+                                const uint64_t* __restrict__ offsets, uint32_t f, uint64_t* off, const uint32_t** hdr) {
+  const uint64_t o = offsets[f], e = offsets[f + 1];
+  *off = o;
+  if (o % 16 != 0 || o > e || e > stream_bytes || e - o < kHeaderBytes) return kStRange;
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(in + o);
+  *hdr = h;
+  if (h[0] != kMagic) return kStMagic;
+  if (h[1] != kVersion) return kStVersion;
+  if (h[2] != g.w || h[3] != g.h || h[4] != g.bw || h[5] != g.bh || h[6] != g.mvbw || h[7] != g.mvbh || h[8] == 0 || h[9] == 0)
+    return kStGeometry;
+  if (h[12] != e - o || g.levels_off + 2ull * h[10] > h[12]) return kStSize;
+  return kStOk;
+}
+
+// ---- pack --------------------------------------------------------------------------------------------------------------------
+
+struct PackArgs {
+  Geom g;
+  const float* planes;   // [n][3][h][w]
+  const uint32_t* types; // [n][mvb]
+  uint8_t* out;
+  uint64_t* offsets;     // [n + 1]
+  Ws ws;
+  uint32_t n, fg, bg;
+};
+
+// SCATTER = false: the group's non-zero count and inexact count.  SCATTER = true: masks and levels at their final place (plus,
+// from group 0 of each frame, the header, the types, the zero pad and offsets[f + 1]).
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
+  extern __shared__ float lds[];
+  __shared__ uint64_t job_mask[kMaxJobs];
+  __shared__ uint32_t job_base[kMaxJobs];
+  __shared__ uint32_t red[kThreads / 64];
+  __shared__ uint64_t frame_off;
+  const Geom& g = a.g;
+  const uint32_t gi = blockIdx.x, f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const Group gr = group_of(g, gi);
+  const uint32_t* types = a.types + (size_t)f * g.mvb;
+  stage_rows(g, gr, a.planes + ((size_t)f * 3 + gr.plane) * g.h * g.w, lds);
+  if (SCATTER && wave == 0) {  // this frame's offset: the sizes of the frames before it
+    uint64_t s = 0;
+    for (uint32_t i = lane; i < f; i += 64) s += a.ws.frame_bytes[i];
+    for (uint32_t off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) frame_off = s;
+  }
+  __syncthreads();
+
+  const uint32_t area = g.bw * g.bh, jobs = gr.nt * g.words;
+  uint32_t nz_count = 0, inexact = 0;
+  for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
+    const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
+    const float step = tile_type(g, types, gr, t) == 0 ? (float)a.bg : (float)a.fg;
+    int32_t lv = 0;
+    if (k < area) {
+      const float c = lds[lds_index(g, gr, t, k)];
+      lv = level_of(c, step);
+      if (!SCATTER) inexact += c != (float)lv * step;
+    }
+    const uint64_t mask = __ballot(lv != 0);
+    if (!SCATTER) nz_count += __popcll(mask);
+    else if (lane == 0) job_mask[j] = mask;
+  }
+  if (!SCATTER) {
+    for (uint32_t off = 32; off >= 1; off >>= 1) inexact += __shfl_xor(inexact, off, 64);
+    if (lane == 0) red[wave] = inexact;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t s = 0;
+      for (uint32_t i = 0; i < kThreads / 64; ++i) s += red[i];
+      a.ws.inexact[(size_t)f * g.groups + gi] = s;
+    }
+    __syncthreads();
+    if (lane == 0) red[wave] = nz_count;
+    __syncthreads();
+    if (threadIdx.x == 0) a.ws.cnt[(size_t)f * g.groups + gi] = red[0] + red[1] + red[2] + red[3];
+    return;
+  }
+
+  // scatter: exclusive scan of the words' popcounts, in word order
+  __syncthreads();
+  uint32_t total;
+  const uint32_t pc = threadIdx.x < jobs ? (uint32_t)__popcll(job_mask[threadIdx.x]) : 0u;
+  const uint32_t ex = block_exclusive_scan(pc, red, &total);
+  if (threadIdx.x < jobs) job_base[threadIdx.x] = ex;
+  __syncthreads();
+  uint8_t* frame = a.out + frame_off;
+  int16_t* levels = reinterpret_cast<int16_t*>(frame + g.levels_off) + a.ws.cnt[(size_t)f * g.groups + gi];
+  // the mask words of the group are contiguous: [plane][ty][t0 .. t0 + nt)[words]
+  uint32_t* masks = reinterpret_cast<uint32_t*>(frame + g.masks_off) +
+                    2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+  for (uint32_t j = threadIdx.x; j < jobs; j += kThreads) {  // two u32 stores: the masks are 4-byte aligned when mvb is odd
+    masks[2 * j] = (uint32_t)job_mask[j];
+    masks[2 * j + 1] = (uint32_t)(job_mask[j] >> 32);
+  }
+  for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
+    const uint64_t mask = job_mask[j];
+    if (!((mask >> lane) & 1u)) continue;
+    const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
+    const float step = tile_type(g, types, gr, t) == 0 ? (float)a.bg : (float)a.fg;
+    levels[job_base[j] + lane_rank(mask)] = (int16_t)level_of(lds[lds_index(g, gr, t, k)], step);
+  }
+  if (gi != 0) return;
+  // group 0: header, types, pad, offsets
+  const uint32_t level_count = a.ws.frame_levels[f], fbytes = a.ws.frame_bytes[f];
+  uint32_t* hdr = reinterpret_cast<uint32_t*>(frame);
+  if (threadIdx.x < 16) {
+    const uint32_t v[16] = {kMagic, kVersion, g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh, a.fg, a.bg, level_count, a.ws.frame_inexact[f],
+                            fbytes, 0, 0, 0};
+    hdr[threadIdx.x] = v[threadIdx.x];
+  }
+  uint32_t* tdst = reinterpret_cast<uint32_t*>(frame + kHeaderBytes);
+  for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) tdst[i] = types[i];
+  const uint64_t used = g.levels_off + 2ull * level_count;
+  for (uint64_t i = used + threadIdx.x; i < fbytes; i += kThreads) frame[i] = 0;
+  if (threadIdx.x == 0) {
+    a.offsets[f + 1] = frame_off + fbytes;
+    if (f == 0) a.offsets[0] = 0;
+  }
+}
+
+// one workgroup per frame: group counts -> exclusive prefixes (in place), the frame's level count, inexact count and size.
+// UNPACK: also the frame's status (header vs geometry, level count vs masks), to ws and d_status.
+template <bool UNPACK>
+__global__ __launch_bounds__(256) void scan_kernel(Geom g, Ws ws, const uint8_t* in, uint64_t stream_bytes, const uint64_t* offsets,
+                                                   uint32_t* d_status) {
+  __shared__ uint32_t red[kThreads / 64];
+  const uint32_t f = blockIdx.x;
+  uint32_t* cnt = ws.cnt + (size_t)f * g.groups;
+  uint32_t carry = 0, inexact = 0;
+  for (uint32_t base = 0; base < g.groups; base += kThreads) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t v = i < g.groups ? cnt[i] : 0u;
+    if (i < g.groups) inexact += ws.inexact[(size_t)f * g.groups + i];
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(v, red, &total);
+    if (i < g.groups) cnt[i] = carry + ex;
+    carry += total;
+  }
+  uint32_t t;
+  (void)block_exclusive_scan(inexact, red, &t);  // pack: inexact coefficients; unpack: mask bits past the tile area
+  if (!UNPACK) {
+    if (threadIdx.x == 0) {
+      ws.frame_levels[f] = carry;
+      ws.frame_inexact[f] = t;
+      ws.frame_bytes[f] = (uint32_t)up16(g.levels_off + 2ull * carry);
+    }
+    return;
+  }
+  if (threadIdx.x == 0) {
+    uint64_t off = 0;
+    const uint32_t* hdr = nullptr;
+    uint32_t st = check_frame(g, in, stream_bytes, offsets, f, &off, &hdr);
+    if (st == kStOk && t != 0) st = kStStrayBits;
+    if (st == kStOk && hdr[10] != carry) st = kStLevels;
+    ws.status[f] = st;
+    d_status[f] = st;
+  }
+}
+
+// ---- unpack ------------------------------------------------------------------------------------------------------------------
+
+struct UnpackArgs {
+  Geom g;
+  const uint8_t* in;
+  uint64_t stream_bytes;
+  const uint64_t* offsets;
+  float* planes;
+  uint32_t* types;
+  Ws ws;
+};
+
+// SCATTER = false: the group's popcount over its mask words (0 for a frame that fails its checks).  SCATTER = true: the group's
+// rows of the planes (zeros where the mask is 0, everywhere for a bad frame) and, from group 0, the types.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void unpack_kernel(UnpackArgs a) {
+  extern __shared__ float lds[];
+  __shared__ uint32_t red[kThreads / 64];
+  __shared__ uint32_t job_base[kMaxJobs];
+  __shared__ uint64_t job_mask[kMaxJobs];
+  const Geom& g = a.g;
+  const uint32_t gi = blockIdx.x, f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const Group gr = group_of(g, gi);
+  uint64_t off = 0;
+  const uint32_t* hdr = nullptr;
+  const uint32_t st = SCATTER ? a.ws.status[f] : check_frame(g, a.in, a.stream_bytes, a.offsets, f, &off, &hdr);
+  if (SCATTER) off = a.offsets[f], hdr = reinterpret_cast<const uint32_t*>(a.in + off);
+  const uint8_t* frame = a.in + off;
+  const uint32_t jobs = gr.nt * g.words;
+  const uint32_t* masks = st != kStOk ? nullptr :
+      reinterpret_cast<const uint32_t*>(frame + g.masks_off) + 2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+  const uint32_t j = threadIdx.x;
+  const uint64_t m = (masks && j < jobs) ? ((uint64_t)masks[2 * j + 1] << 32 | masks[2 * j]) : 0ull;
+  const uint32_t area = g.bw * g.bh;
+  uint32_t total;
+  const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
+  if (!SCATTER) {
+    // the format keeps the bits past the tile area 0: a frame with such bits is refused (status kStStrayBits), not half read
+    const uint32_t valid = j < jobs ? area - (j % g.words) * 64 : 64u;
+    uint32_t stray;
+    (void)block_exclusive_scan(valid < 64 ? (uint32_t)__popcll(m >> valid) : 0u, red, &stray);
+    if (threadIdx.x == 0) {
+      a.ws.cnt[(size_t)f * g.groups + gi] = total;
+      a.ws.inexact[(size_t)f * g.groups + gi] = stray;
+    }
+    return;
+  }
+  if (j < jobs) { job_mask[j] = m; job_base[j] = ex; }
+  __syncthreads();
+  const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) + a.ws.cnt[(size_t)f * g.groups + gi];
+  const uint32_t* types = reinterpret_cast<const uint32_t*>(frame + kHeaderBytes);
+  const float fg = st == kStOk ? (float)hdr[8] : 0.f, bg = st == kStOk ? (float)hdr[9] : 0.f;
+  for (uint32_t jj = wave; jj < jobs; jj += kThreads / 64) {
+    const uint64_t mask = job_mask[jj];
+    const uint32_t t = jj / g.words, k = (jj - t * g.words) * 64 + lane;
+    if (k >= area) continue;
+    float v = 0.f;
+    if ((mask >> lane) & 1u) {
+      const float step = tile_type(g, types, gr, t) == 0 ? bg : fg;
+      v = (float)levels[job_base[jj] + lane_rank(mask)] * step;
+    }
+    lds[lds_index(g, gr, t, k)] = v;
+  }
+  __syncthreads();
+  store_rows(g, gr, lds, a.planes + ((size_t)f * 3 + gr.plane) * g.h * g.w);
+  if (gi == 0) {
+    uint32_t* tdst = a.types + (size_t)f * g.mvb;
+    for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) tdst[i] = st == kStOk ? types[i] : 0u;
+  }
+}
+
+// ---- drain -------------------------------------------------------------------------------------------------------------------
+
+// offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
+__global__ __launch_bounds__(256) void drain_kernel(const uint4* __restrict__ src, const uint64_t* __restrict__ offsets, uint32_t n,
+                                                    uint4* dst, uint64_t capacity) {
+  const uint64_t bytes = min(offsets[n], capacity);
+  const uint64_t n16 = bytes / 16;
+  const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
+}
+
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int validate_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  SVC_REQUIRE(w > 0 && h > 0 && bw > 0 && bh > 0, "%s: frame and tile sides must be positive", what);
+  SVC_REQUIRE(w % bw == 0 && h % bh == 0, "%s: frame %ux%u not divisible by tile %ux%u", what, w, h, bw, bh);
+  SVC_REQUIRE(mvbw > 0 && mvbh > 0 && mvbw % bw == 0 && mvbh % bh == 0 && w % mvbw == 0 && h % mvbh == 0,
+              "%s: MV block %ux%u must be a multiple of the tile %ux%u and divide the frame", what, mvbw, mvbh, bw, bh);
+  return SVC_OK;
+}
+
+// what this build's kernels and the format's fields hold
+int validate_limits(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  if ((uint64_t)bw * bh > kMaxTileCoeffs) return fail(SVC_ERR_UNSUPPORTED, "%s: tiles above %u coefficients", what, kMaxTileCoeffs);
+  if (n > 65535) return fail(SVC_ERR_UNSUPPORTED, "%s: more than 65535 frames in one call", what);
+  if (frame_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)) > 0xFFFFFFFFull)
+    return fail(SVC_ERR_UNSUPPORTED, "%s: a frame of %ux%u could exceed the u32 frame_bytes field", what, w, h);
+  return SVC_OK;
+}
+
+}  // namespace
+}  // namespace svc
+
+using namespace svc;
+
+extern "C" {
+
+uint64_t svc_hip_levels_max_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                  uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("levels_max_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("levels_max_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  return n_frames * frame_max_bytes(make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
+}
+
+uint64_t svc_hip_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                             uint32_t block_h) {
+  // the MV block does not enter the group split: the whole frame stands in for it
+  if (validate_geom("pack_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
+      validate_limits("pack_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
+    return 0;
+  return ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
+}
+
+// Every argument is checked in this order, whatever n_frames: geometry, steps, limits, sizes, then pointers (null, alignment,
+// and for the drain what memory the destination is).  n_frames == 0 returns SVC_OK after the checks that need no pointer.
+int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_types, uint32_t n_frames, uint32_t frame_w,
+                               uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                               uint32_t fg_step, uint32_t bg_step, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
+                               uint64_t out_capacity, uint64_t* d_frame_offsets, void* stream) {
+  int rc = validate_geom("pack_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "pack_levels: quant steps must be positive");
+  // Parseval: no coefficient of an orthonormal DCT of u8 samples exceeds 255 * sqrt(tile area) in magnitude
+  if (255.0 * std::sqrt((double)block_w * block_h) / std::min(fg_step, bg_step) > 32767.0)
+    return fail(SVC_ERR_UNSUPPORTED, "pack_levels: levels of a %ux%u tile at step %u could exceed int16", block_w, block_h,
+                std::min(fg_step, bg_step));
+  if ((rc = validate_limits("pack_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "pack_levels: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
+  const uint64_t need = n_frames * frame_max_bytes(g);
+  SVC_REQUIRE(out_capacity >= need, "pack_levels: output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)out_capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_planes && d_block_types && d_workspace && d_out && d_frame_offsets, "pack_levels: null pointer");
+  SVC_REQUIRE(aligned(d_planes, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_block_types, 4),
+              "pack_levels: planes, output and workspace must be 16-byte aligned, offsets 8-byte");
+  PackArgs a;
+  a.g = g;
+  a.planes = d_planes; a.types = d_block_types; a.out = d_out; a.offsets = d_frame_offsets;
+  a.ws = carve(d_workspace, n_frames, g.groups);
+  a.n = n_frames; a.fg = fg_step; a.bg = bg_step;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(g.groups, n_frames);
+  hipLaunchKernelGGL(pack_kernel<false>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  if ((rc = check_launch("pack_levels count"))) return rc;
+  hipLaunchKernelGGL(scan_kernel<false>, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws, nullptr, 0, nullptr, nullptr);
+  if ((rc = check_launch("pack_levels scan"))) return rc;
+  hipLaunchKernelGGL(pack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  return check_launch("pack_levels scatter");
+}
+
+int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                 uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                 uint32_t mv_block_h, uint8_t* d_workspace, uint64_t workspace_bytes, float* d_planes,
+                                 uint32_t* d_block_types, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("unpack_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (!rc) rc = validate_limits("unpack_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "unpack_levels: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_planes && d_block_types && d_status, "unpack_levels: null pointer");
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_planes, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_block_types, 4) && aligned(d_status, 4),
+              "unpack_levels: frames, planes and workspace must be 16-byte aligned, offsets 8-byte");
+  UnpackArgs a;
+  a.g = g;
+  a.in = d_frames; a.stream_bytes = stream_bytes; a.offsets = d_frame_offsets;
+  a.planes = d_planes; a.types = d_block_types;
+  a.ws = carve(d_workspace, n_frames, g.groups);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(g.groups, n_frames);
+  hipLaunchKernelGGL(unpack_kernel<false>, grid, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("unpack_levels count"))) return rc;
+  hipLaunchKernelGGL(scan_kernel<true>, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws, d_frames, stream_bytes, d_frame_offsets, d_status);
+  if ((rc = check_launch("unpack_levels scan"))) return rc;
+  hipLaunchKernelGGL(unpack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  return check_launch("unpack_levels scatter");
+}
+
+int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t frame_w,
+                         uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                         void* host_dst, uint64_t capacity, void* stream) {
+  int rc = validate_geom("levels_drain", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (!rc) rc = validate_limits("levels_drain", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  const uint64_t need = svc_hip_levels_max_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  SVC_REQUIRE(capacity >= need, "levels_drain: destination of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && host_dst, "levels_drain: null pointer");
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(host_dst, 16) && aligned(d_frame_offsets, 8),
+              "levels_drain: frames and destination must be 16-byte aligned, offsets 8-byte");
+  // A kernel that stores to pageable memory faults the GPU: the destination must be pinned / registered host memory, and the
+  // WHOLE of [host_dst, host_dst + capacity) must lie inside that one allocation (not run on into a neighbour or a gap).
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, host_dst) != hipSuccess || attr.type != hipMemoryTypeHost) {
+    (void)hipGetLastError();
+    return fail(SVC_ERR_INVALID_ARG, "levels_drain: the destination is not pinned or registered host memory");
+  }
+  hipDeviceptr_t start = nullptr;
+  size_t size = 0;
+  if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, host_dst) != hipSuccess ||
+      hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, host_dst) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SVC_ERR_INVALID_ARG, "levels_drain: the destination's allocation cannot be resolved");
+  }
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(start), dst = reinterpret_cast<uintptr_t>(host_dst);
+  if (dst < lo || dst - lo > size || capacity > size - (dst - lo))
+    return fail(SVC_ERR_INVALID_ARG, "levels_drain: %llu B from the destination run past its pinned allocation (%llu B from %p)",
+                (unsigned long long)capacity, (unsigned long long)size, reinterpret_cast<void*>(lo));
+  void* d_dst = nullptr;
+  if (hipHostGetDevicePointer(&d_dst, host_dst, 0) != hipSuccess || !d_dst) {
+    (void)hipGetLastError();
+    return fail(SVC_ERR_INVALID_ARG, "levels_drain: the destination has no device mapping");
+  }
+  SVC_REQUIRE(aligned(d_dst, 16), "levels_drain: the destination's device mapping is not 16-byte aligned");
+  hipLaunchKernelGGL(drain_kernel, dim3(64), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const uint4*>(d_frames), d_frame_offsets, n_frames, static_cast<uint4*>(d_dst), capacity);
+  return check_launch("levels_drain");
+}
+
+}  // extern "C"

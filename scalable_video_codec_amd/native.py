@@ -113,6 +113,12 @@ SIGNATURES = {
     "svc_hip_kmeans_host": (C.c_int, [_vp, _u32, _u32, _u32, _u32, _u32, C.c_float, _u64, _vp, C.POINTER(C.c_double)]),
     "svc_hip_connected_components_host": (C.c_int, [_vp, _u32, _u32, _u32, _vp, C.POINTER(_u32)]),
     "svc_hip_dct_tiles_host": (C.c_int, [_vp, _u32, _u32, _u32, _u32, _vp, _u32]),
+    # the compact quantised-coefficient stream (csrc/levels.hip)
+    "svc_hip_levels_max_bytes": (_u64, [_u32] * 7),
+    "svc_hip_pack_levels_workspace_bytes": (_u64, [_u32] * 5),
+    "svc_hip_pack_levels_frames": (C.c_int, [_vp, _vp] + [_u32] * 9 + [_vp, _u64, _vp, _u64, _vp, _vp]),
+    "svc_hip_unpack_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _vp, _vp, _vp]),
+    "svc_hip_levels_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -664,3 +670,67 @@ def dct_planes_host(bgr, bw: int, bh: int):
     ptrs = (_vp * 3)(*[p.ctypes.data for p in planes])
     _check(load().svc_hip_dct_planes_host(src.ctypes.data, w, h, bw, bh, ptrs))
     return np.stack(planes)
+
+
+# ---- the compact quantised-coefficient stream (include/svc_hip.h, "SVCQ" v1; host reader: levels.py) ----
+
+def levels_max_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    """Worst-case bytes of n packed frames (what the output and a drain destination must hold)."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_levels_max_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def pack_levels_workspace_bytes(n: int, w: int, h: int, block) -> int:
+    bw, bh = _bwbh(block)
+    return int(load().svc_hip_pack_levels_workspace_bytes(n, w, h, bw, bh))
+
+
+def pack_levels_frames(planes: torch.Tensor, block_types: torch.Tensor, block, mv_block, fg_step: int, bg_step: int,
+                       out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Quantised planes (frames, 3, H, W) f32 + region ids (frames, blocks) i32 -> (stream u8 of the worst-case size, offsets
+    (frames + 1,) i64 on the device; offsets[-1] = bytes used)."""
+    n, _, h, w = planes.shape
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=planes.device)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=planes.device)
+    if workspace is None:
+        workspace = torch.empty(max(pack_levels_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=planes.device)
+    _check(load().svc_hip_pack_levels_frames(_dev(planes, torch.float32), _dev(block_types, torch.int32), n, w, h, bw, bh, mbw, mbh,
+                                             fg_step, bg_step, _dev(workspace, torch.uint8), workspace.numel(),
+                                             _dev(out, torch.uint8), out.numel(), _dev(offsets, torch.int64), _stream()))
+    return out, offsets
+
+
+def unpack_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block,
+                         planes: Optional[torch.Tensor] = None, block_types: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A packed stream (u8 on the device) + its offsets -> (planes (frames, 3, H, W) f32, region ids (frames, blocks) i32,
+    status (frames,) i32: 0 = the frame's header matched this geometry)."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    if planes is None:
+        planes = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+    if block_types is None:
+        block_types = torch.empty((n, (w // mbw) * (h // mbh)), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(pack_levels_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_unpack_levels_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, w, h, bw, bh,
+                                               mbw, mbh, _dev(workspace, torch.uint8), workspace.numel(),
+                                               _dev(planes, torch.float32), _dev(block_types, torch.int32), _dev(status, torch.int32),
+                                               _stream()))
+    return planes, block_types, status
+
+
+def levels_drain(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, dst: torch.Tensor) -> None:
+    """Copies offsets[-1] bytes of a packed stream into dst, a PINNED host u8 tensor of at least the worst-case size, by a kernel
+    on the current stream (the byte count stays on the device)."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    assert not dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous()
+    _check(load().svc_hip_levels_drain(_dev(frames, torch.uint8), _dev(offsets, torch.int64), n, w, h, bw, bh, mbw, mbh,
+                                       dst.data_ptr(), dst.numel(), _stream()))

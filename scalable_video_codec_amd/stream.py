@@ -25,7 +25,7 @@ from .pipeline import ClipEncoder, ransac_samples
 
 
 class _Slot:
-    def __init__(self, cfg: CodecConfig, batch: int, device, wire: bool, segmentation: bool):
+    def __init__(self, cfg: CodecConfig, batch: int, device, wire: bool, segmentation: bool, compact: bool = False):
         self.enc = ClipEncoder(cfg, batch + 1, device, segmentation=segmentation, wire=wire)
         pw, ph = cfg.padded
         self.pin_in = torch.zeros((batch + 1, ph, pw, 3), dtype=torch.uint8).pin_memory()  # padding stays zero
@@ -34,7 +34,16 @@ class _Slot:
         self.pin_types = torch.empty(e.types.shape, dtype=torch.int32).pin_memory()
         self.pin_gm = torch.empty(e.gm.shape, dtype=torch.float32).pin_memory()
         big = e.records if e.wire else e.coeffs
-        self.pin_big = torch.empty(big.shape, dtype=big.dtype).pin_memory() if big is not None else None
+        self.pin_big = torch.empty(big.shape, dtype=big.dtype).pin_memory() if big is not None and not compact else None
+        self.compact = compact
+        if compact:  # the quantised planes leave as the compact stream (levels.py): packed on the device, drained by a kernel
+            cap = native.levels_max_bytes(batch, pw, ph, cfg.dct_block, cfg.mv_block)
+            self.packed = torch.empty(cap, dtype=torch.uint8, device=device)
+            self.offsets = torch.empty(batch + 1, dtype=torch.int64, device=device)
+            self.pack_ws = torch.empty(max(native.pack_levels_workspace_bytes(batch, pw, ph, cfg.dct_block), 16), dtype=torch.uint8,
+                                       device=device)
+            self.pin_packed = torch.empty(cap, dtype=torch.uint8).pin_memory()
+            self.pin_offsets = torch.empty(batch + 1, dtype=torch.int64).pin_memory()
         self.h2d_done = torch.cuda.Event()
         self.compute_done = torch.cuda.Event()
         self.d2h_done = torch.cuda.Event()
@@ -49,14 +58,18 @@ class HostStreamEncoder:
     libs/encoder.cpp:361-367), mv (n, blocks, 2) f32, types (n, blocks) i32, gm (n, 2) f32 and
     coeffs (n, 3, H, W) f32 (quantised) or records (n, bytes) u8 -- the serialised RAW coefficients over the
     PADDED tile grid, what the reference's decoder parses (libs/decoder.cpp:185-186); the first batch of a wire
-    stream also carries "header", the 32 bytes of libs/codec.hpp:8-17.  A view is valid until depth - 2 more
+    stream also carries "header", the 32 bytes of libs/codec.hpp:8-17.  compact=True replaces coeffs by "compact",
+    the used bytes of the compact quantised-coefficient stream (u8; levels.iter_frames reads it), and
+    "compact_offsets" (n + 1,) i64.  A view is valid until depth - 2 more
     batches have been yielded (its slot is re-staged one iteration before its turn to be yielded comes again)."""
 
     def __init__(self, cfg: CodecConfig, batch: int = 32, device=None, wire: bool = False,
-                 segmentation: bool = True, depth: int = 3):
+                 segmentation: bool = True, depth: int = 3, compact: bool = False):
+        if compact and (wire or not cfg.dct_block):
+            raise ValueError("compact output is a form of the quantised planes: not with wire records, nor without a transform")
         self.cfg, self.batch, self.depth = cfg, batch, max(3, depth)  # 2 would leave nothing overlapped
         self.dev = device or torch.device("cuda")
-        self.slots = [_Slot(cfg, batch, self.dev, wire, segmentation) for _ in range(self.depth)]
+        self.slots = [_Slot(cfg, batch, self.dev, wire, segmentation, compact) for _ in range(self.depth)]
         self.copy_in = torch.cuda.Stream(device=self.dev)
         self.copy_out = torch.cuda.Stream(device=self.dev)
         self.compute = torch.cuda.Stream(device=self.dev)
@@ -113,6 +126,10 @@ class HostStreamEncoder:
                     torch.cat([samples[g0:], samples[:e.pairs_per_step - (n_total - 1 - g0)]])
                 self.compute.wait_event(slot.h2d_done)
                 e.step()
+                if slot.compact:
+                    c_ = self.cfg
+                    native.pack_levels_frames(e.coeffs[:cnt], e.types[:cnt], c_.dct_block, c_.mv_block, c_.fg_step, c_.bg_step,
+                                              out=slot.packed, offsets=slot.offsets[:cnt + 1], workspace=slot.pack_ws)
                 slot.compute_done.record(self.compute)
             with torch.cuda.stream(self.copy_out):
                 self.copy_out.wait_event(slot.compute_done)
@@ -122,6 +139,11 @@ class HostStreamEncoder:
                 if slot.pin_big is not None:
                     big = e.records if e.wire else e.coeffs
                     slot.pin_big[:cnt].copy_(big[:cnt], non_blocking=True)
+                if slot.compact:
+                    c_ = self.cfg
+                    pw, ph = c_.padded
+                    native.levels_drain(slot.packed, slot.offsets[:cnt + 1], pw, ph, c_.dct_block, c_.mv_block, slot.pin_packed)
+                    slot.pin_offsets[:cnt + 1].copy_(slot.offsets[:cnt + 1], non_blocking=True)
                 slot.d2h_done.record(self.copy_out)
             slot.busy, slot.count, slot.first = True, cnt, first
             pending.append(slot)
@@ -138,6 +160,9 @@ class HostStreamEncoder:
                "gm": slot.pin_gm.numpy()[:c]}
         if slot.pin_big is not None:
             out["records" if slot.enc.wire else "coeffs"] = slot.pin_big.numpy()[:c]
+        if slot.compact:
+            offs = slot.pin_offsets.numpy()[:c + 1]
+            out["compact"], out["compact_offsets"] = slot.pin_packed.numpy()[:int(offs[-1])], offs
         if slot.enc.wire and slot.first == 1:
             c_ = self.cfg
             out["header"] = native.wire_header(self._n_total, c_.width, c_.height, c_.mv_block, c_.levels, c_.dct_block)
