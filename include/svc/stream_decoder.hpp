@@ -1,0 +1,73 @@
+// stream_decoder.hpp -- the decoder-side mirror of stream_encoder.hpp: a compact quantised-coefficient stream ("SVCQ", include/svc_hip.h)
+// in HOST memory -> the display frames the reference's decoder shows (libs/decoder.cpp:168-210, headless: no window, the gaze centre
+// comes from a callback instead of the mouse).
+//
+// Per frame: the gaze rectangle of svc_hip_gaze_rect around the callback's centre, then svc_hip_decode_levels_frames (DecodeBlock
+// over every tile, / 255, bilinear resize, u8).  Batches are staged into pinned memory and copied H2D while the previous batch is
+// in the kernels and the one before it is on its way back as u8 display frames.
+#ifndef SVC_STREAM_DECODER_HPP
+#define SVC_STREAM_DECODER_HPP
+
+#include <cstdint>
+#include <functional>
+#include <memory>
+
+#include "svc_hip.h"
+
+namespace svc {
+
+struct StreamDecoderConfig {
+  uint32_t display_w = 0, display_h = 0;  // the source size the picture is shown at; 0 = the padded size
+  uint32_t fg_step = 1, bg_step = 640;    // the decoder's steps (apps/decoder.cpp:21-26)
+  uint32_t max_gaze_w = 64, max_gaze_h = 64;
+  uint32_t batch = 16;                    // frames per batch
+  uint32_t depth = 3;                     // batches in flight, >= 3 (H2D, kernels and D2H of three batches overlap)
+};
+
+// One finished batch; the pointers are pinned host memory owned by the decoder and stay valid until depth - 2 more batches have
+// been delivered (as for EncodedBatch): with the default depth of 3, until the NEXT delivery returns.
+struct DecodedBatch {
+  uint32_t first_frame = 0;        // stream index of the batch's first frame
+  uint32_t count = 0;
+  uint32_t width = 0, height = 0;  // of a display frame
+  const uint8_t* bgr = nullptr;    // [count][height][width][3] u8 B,G,R
+  const uint32_t* status = nullptr;  // [count]: 0, or svc_hip_unpack_levels_frames's code (the frame is then all zeros)
+};
+
+// Where the time of one Decode() went: wall time of the calling thread; per-stream device times summed over the batches (the
+// streams overlap); the bytes actually moved each way.
+struct DecodeStats {
+  uint32_t batches = 0, frames = 0;
+  double wall_ms = 0;
+  double h2d_ms = 0, kernels_ms = 0, d2h_ms = 0;
+  uint64_t h2d_bytes = 0, d2h_bytes = 0;
+};
+
+class StreamDecoder {
+ public:
+  using Sink = std::function<void(const DecodedBatch&)>;
+  // Frame index -> gaze centre in display-frame coordinates (where the reference reads the mouse); false = no gaze for that frame.
+  using Gaze = std::function<bool(uint32_t frame, uint32_t* x, uint32_t* y)>;
+
+  // Creates the streams; buffers are sized by the first Decode().  Throws std::runtime_error on an invalid configuration.
+  explicit StreamDecoder(const StreamDecoderConfig& config);
+  ~StreamDecoder();
+  StreamDecoder(const StreamDecoder&) = delete;
+  StreamDecoder& operator=(const StreamDecoder&) = delete;
+
+  // stream: n_frames SVCQ frames anywhere in host memory, frame i in [offsets[i], offsets[i + 1]) (offsets: n_frames + 1 values,
+  // the shape of EncodedBatch::compact / compact_offsets).  The geometry comes from the first frame's header, which must parse
+  // (else std::runtime_error); any later frame that does not match is reported in DecodedBatch::status, not thrown.  gaze may be
+  // empty (no gaze).  sink is called once per batch, in stream order, from this thread.
+  void Decode(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const Gaze& gaze, const Sink& sink);
+
+  const DecodeStats& last_stats() const;  // of the last Decode() that returned
+
+ private:
+  struct Impl;
+  std::unique_ptr<Impl> p_;
+};
+
+}  // namespace svc
+
+#endif  // SVC_STREAM_DECODER_HPP

@@ -465,6 +465,62 @@ int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offset
                          uint32_t mv_block_h, void* host_dst, uint64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Headless decoder of the compact stream: DecodeBlock over every tile with a gaze rectangle per
+ * frame (libs/decoder.cpp:128-149, :168-207), then the picture the reference shows.
+ *
+ * Per tile: c = (float)level * (float)enc_step, enc_step = the frame header's bg_step for a tile
+ * whose MV block (the one holding the tile origin) has type 0, else its fg_step; then the
+ * decoder's step = gazed ? 1 : (type == 0 ? bg_step : fg_step), with gazed = the frame's
+ * rectangle contains the tile origin (x <= tx < x + w && y <= ty < y + h; w or h == 0 holds
+ * nothing); requantise, f64 inverse DCT.  d_rec [n][H][W][3] f32 B,G,R at the padded size is
+ * bit-identical to svc_hip_unpack_levels_frames followed by svc_hip_decode_frames with that
+ * frame's rectangle.  Gaze can only keep what the encoder's steps kept: a stream encoded with
+ * bg_step 640 has already lost the background detail, and decoding at step 1 inside the
+ * rectangle cannot restore it.  Gaze-scalable streams are encoded with small steps and
+ * quantised by the decoder, as the reference's are (its wire records are raw coefficients).
+ *
+ * Display (d_display != NULL, display size not 0 x 0): the reference's upscaled_frame /= 255,
+ * cv::resize(INTER_LINEAR) to the source size and imshow's float -> u8, stated here (parity with
+ * OpenCV unpinned): v = rec / 255.0f; bilinear from W x H to display_w x display_h with half-pixel
+ * centres, fx = (dx + 0.5) * (W / display_w) - 0.5 (computed exactly from integers, the weight
+ * rounded once to f32), sx = floor(fx), a = fx - sx; sx < 0 -> sx = 0, a = 0; sx >= W - 1 ->
+ * sx = W - 1, a = 0; the same vertically; horizontal then vertical, (1 - a) * v0 + a * v1 in f32;
+ * out = saturate_u8(rint(255 * v)).  A display of the padded size gives saturate_u8(rint(rec)).
+ * Like the reference this SQUEEZES the padded picture (padding included) into the display size,
+ * it does not crop it.  1 <= display_w <= W and 1 <= display_h <= H, else SVC_ERR_INVALID_ARG.
+ *
+ * Geometry: square 8x8 or 16x16 transform blocks, frame_w a multiple of 16 (as
+ * svc_hip_decode_frames), any MV block the format accepts; else SVC_ERR_UNSUPPORTED.  Checked in
+ * the order of the SVCQ entry points above, for any n_frames: geometry, steps (0 is
+ * SVC_ERR_INVALID_ARG, libs/decoder.cpp:35-47), display size, limits, workspace, then pointers.
+ * d_status [n_frames] u32 with the codes of svc_hip_unpack_levels_frames; a frame that fails is
+ * zeros in d_rec and d_display and leaves its neighbours as they would be.  Only enqueues work.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_decode_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w,
+                                               uint32_t frame_h, uint32_t block_w,
+                                               uint32_t block_h);
+int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                 const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                 uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                 uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                 uint32_t fg_step, uint32_t bg_step,
+                                 const uint32_t* d_gaze /* [n_frames][4] x, y, w, h (padded); NULL = none */,
+                                 uint8_t* d_workspace, uint64_t workspace_bytes,
+                                 float* d_rec /* [n][H][W][3] f32 B,G,R, padded */,
+                                 uint8_t* d_display /* [n][display_h][display_w][3] u8 B,G,R, or NULL */,
+                                 uint32_t display_w, uint32_t display_h, uint32_t* d_status,
+                                 void* stream);
+
+/* The reference's gaze rectangle from a point, on the host (no device needed):
+ * CalcWithinFrameRectFromCenter (libs/decoder.cpp:65-100: halves (max + 1) / 2, clipped at the
+ * frame's edges) in the source frame, then scaled by (float)padded / frame with
+ * round-half-away-from-zero (:163-164, :179-183) -> out_xywh = x, y, w, h in padded coordinates.
+ * A centre outside the frame is SVC_ERR_INVALID_ARG (the reference asserts). */
+int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w,
+                      uint32_t frame_h, uint32_t padded_w, uint32_t padded_h,
+                      uint32_t out_xywh[4]);
+
+/* ------------------------------------------------------------------------- *
  * Pre-step: luma + pyramid on the device, so the pyramid never
  * crosses PCIe.  Stands in for cv::cvtColor(BGR2YUV) + cv::extractChannel +
  * cv::buildPyramid (libs/encoder.cpp:468-470) with this repo's fixed-point

@@ -63,7 +63,7 @@ def _run(cmd: List[str]) -> None:
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "svc_common.hpp"), os.path.join(CSRC, "union_find.hpp"), os.path.join(CSRC, "hbma_search.hpp"), os.path.join(CSRC, "hbma_fused_kernel.hpp"), os.path.join(CSRC, "dct_tables.inc"), os.path.join(CSRC, "luma16.hpp"),
+    headers = [os.path.join(CSRC, "svc_common.hpp"), os.path.join(CSRC, "union_find.hpp"), os.path.join(CSRC, "hbma_search.hpp"), os.path.join(CSRC, "hbma_fused_kernel.hpp"), os.path.join(CSRC, "dct_tables.inc"), os.path.join(CSRC, "idct_core.hpp"), os.path.join(CSRC, "luma16.hpp"),
                os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h")]
     jobs, objs = [], []
     for s in HIP_SOURCES:
@@ -82,6 +82,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
 
 
 STREAM_SRC = os.path.join(CSRC, "host", "stream_encoder.cpp")
+DECODER_SRC = os.path.join(CSRC, "host", "stream_decoder.cpp")
 CLIP_SRC = os.path.join(CSRC, "host", "clip_encoder.cpp")
 
 
@@ -89,18 +90,20 @@ def build_motion(force: bool = False) -> str:
     """The C++ layer above the C ABI: the reference's motion.hpp entry points (plain C++, g++) and the
     batched host-memory encoder (uses the HIP runtime for buffers, streams and events: hipcc, host only)."""
     srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
-    deps = srcs + [STREAM_SRC, CLIP_SRC, os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h"), os.path.join(INCLUDE, "svc_clip.h")] + \
+    deps = srcs + [STREAM_SRC, DECODER_SRC, CLIP_SRC, os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h"), os.path.join(INCLUDE, "svc_clip.h")] + \
         [os.path.join(INCLUDE, "svc", h) for h in ("motion.hpp", "math.hpp", "types.hpp", "stream_encoder.hpp",
-                                                    "clip_encoder.hpp")]
+                                                    "stream_decoder.hpp", "clip_encoder.hpp")]
     if force or not _newer(LIB_MOTION, deps + [LIB_HIP]):
         cxx = shutil.which("g++") or "g++"
         stream_obj = os.path.join(OBJ, "stream_encoder.o")
         clip_obj = os.path.join(OBJ, "clip_encoder.o")
+        decoder_obj = os.path.join(OBJ, "stream_decoder.o")
         _run([_hipcc(), "-std=c++17", "-O2", "-fPIC", "-Wall", f"-I{INCLUDE}", "-c", STREAM_SRC, "-o", stream_obj])
+        _run([_hipcc(), "-std=c++17", "-O2", "-fPIC", "-Wall", f"-I{INCLUDE}", "-c", DECODER_SRC, "-o", decoder_obj])
         _run([_hipcc(), "-std=c++17", "-O2", "-fPIC", "-Wall", f"-I{INCLUDE}", "-c", CLIP_SRC, "-o", clip_obj])
         rocm_lib = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(_hipcc()))), "lib")
         _run([cxx, "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", f"-I{INCLUDE}", f"-I{os.path.join(INCLUDE, 'svc')}",
-              "-o", LIB_MOTION, *srcs, stream_obj, clip_obj, f"-L{PKG}", "-lsvc_hip", f"-L{rocm_lib}", "-lamdhip64",
+              "-o", LIB_MOTION, *srcs, stream_obj, decoder_obj, clip_obj, f"-L{PKG}", "-lsvc_hip", f"-L{rocm_lib}", "-lamdhip64",
               "-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{rocm_lib}"])
     return LIB_MOTION
 
@@ -136,6 +139,13 @@ def build_dropin(force: bool = False) -> List[str]:
     exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_levels_main")
     src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_levels_main.cpp")
     if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp")]):
+        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
+    out.append(exe)
+    # the decoder's host application (svc::StreamDecoder): stream_levels_main's output -> display frames, tests/test_gpu_decode_levels.py
+    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_decode_main")
+    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_decode_main.cpp")
+    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_decoder.hpp")]):
         _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
               f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
     out.append(exe)

@@ -12,7 +12,10 @@
 //   count   (per group: non-zero levels)  ->  scan (per frame: exclusive scan of the group sums, frame size)  ->  scatter.
 // The frame offsets are not scanned by a kernel of their own: the scatter's workgroup sums the frame sizes before its own
 // frame (a batch is a few dozen frames).  Group order = (plane, tile row, group in the row) = the order of the levels.
-#include "svc_common.hpp"
+//
+// decode: unpack's count and scan, then one kernel from the stream straight to the decoder's reconstruction (DecodeBlock with a
+// gaze rectangle per frame, the arithmetic of idct_core.hpp), and optionally the display pass (/ 255, bilinear resize, to u8).
+#include "idct_core.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -421,6 +424,132 @@ __global__ __launch_bounds__(256) void unpack_kernel(UnpackArgs a) {
   }
 }
 
+// ---- decode ------------------------------------------------------------------------------------------------------------------
+
+struct DecodeArgs {
+  Geom g;
+  const uint8_t* in;
+  const uint64_t* offsets;
+  const uint32_t* gaze;  // [n][4] x, y, w, h in padded coordinates, or null
+  float* rec;            // [n][h][w][3]
+  Ws ws;
+  float fg, bg;          // the decoder's steps
+};
+
+// One workgroup per (tile row, group in the row) of a frame: the same tiles in all three planes.  Thread (t, j) owns row j of the
+// group's tile t: it gathers that coefficient row by rank (the group's level prefix + the popcounts of the earlier mask words + the
+// set bits below it in its own word), dequantises with the encoder's step, requantises with the decoder's and inverts the row; the
+// same thread then inverts column j of tile t from LDS and, after the third plane, stores that column's interleaved B,G,R pixels.
+// Rows and columns go through idct1d exactly as in idct_kernel, so d_rec has the bits of unpack + svc_hip_decode_frames.
+template <int N>
+__global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
+  constexpr uint32_t kRows = kGroupCoeffs / N;  // coefficient rows of a group: tpg * N <= 2048 / N
+  __shared__ uint64_t job_mask[kMaxJobs];
+  __shared__ uint32_t job_base[kMaxJobs];
+  __shared__ uint32_t red[kThreads / 64];
+  __shared__ double rows[kRows * (N + 1)];  // pitch N + 1: the column reads of a wave spread over the banks
+  const Geom& g = a.g;
+  const uint32_t gi0 = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t st = a.ws.status[f];
+  const uint8_t* frame = a.in + a.offsets[f];  // dereferenced only for a frame that passed its checks
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t t = tid / N, j = tid - t * N;
+  const bool active = t < gr.nt;
+  float enc = 0.f, dec = 1.f;
+  if (st == kStOk && active) {
+    const uint32_t type = tile_type(g, reinterpret_cast<const uint32_t*>(frame + kHeaderBytes), gr, t);
+    const uint32_t tx = gr.x0 + t * N, ty = gr.y0;
+    bool gazed = false;
+    if (a.gaze) {  // x <= tx < x + w && y <= ty < y + h, without overflow
+      const uint32_t* r = a.gaze + 4ull * f;
+      gazed = tx >= r[0] && tx - r[0] < r[2] && ty >= r[1] && ty - r[1] < r[3];
+    }
+    enc = (float)(type == 0 ? hdr[9] : hdr[8]);
+    dec = gazed ? 1.f : (type == 0 ? a.bg : a.fg);
+  }
+  const uint32_t jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
+  float out[3][N];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint32_t* masks = st != kStOk ? nullptr :
+        reinterpret_cast<const uint32_t*>(frame + g.masks_off) + 2 * ((((size_t)c * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+    const uint64_t m = (masks && tid < jobs) ? ((uint64_t)masks[2 * tid + 1] << 32 | masks[2 * tid]) : 0ull;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
+    if (tid < jobs) { job_mask[tid] = m; job_base[tid] = ex; }
+    __syncthreads();
+    if (active) {
+      const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) +
+                              (st == kStOk ? a.ws.cnt[(size_t)f * g.groups + c * per_plane + gi0] : 0u);
+      double y[N], r[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const uint32_t k = j * N + i, w = t * g.words + (k >> 6), b = k & 63u;
+        const uint64_t mask = job_mask[w];  // 0 for a frame that failed: no level is read
+        float v = 0.f;
+        if ((mask >> b) & 1u) v = (float)levels[job_base[w] + (uint32_t)__popcll(mask & ((1ull << b) - 1))] * enc;
+        y[i] = (double)requant(v, dec);
+      }
+      idct1d<N>(y, r);
+      double* row = rows + (t * N + j) * (N + 1);
+#pragma unroll
+      for (int i = 0; i < N; ++i) row[i] = r[i];
+    }
+    __syncthreads();
+    if (active) {
+      double cc[N], xx[N];
+#pragma unroll
+      for (int v = 0; v < N; ++v) cc[v] = rows[(t * N + v) * (N + 1) + j];
+      idct1d<N>(cc, xx);
+#pragma unroll
+      for (int y = 0; y < N; ++y) out[c][y] = (float)xx[y];
+    }
+    __syncthreads();  // the next plane reuses rows and the job arrays
+  }
+  if (!active) return;
+  float* dst = a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3;  // a wave stores 64 adjacent pixels per row
+#pragma unroll
+  for (int y = 0; y < N; ++y) {
+    float* p = dst + (size_t)y * g.w * 3;
+    p[0] = out[0][y]; p[1] = out[1][y]; p[2] = out[2][y];
+  }
+}
+
+// source index s and weight a of s + 1 for destination index d (half-pixel centres): fx = (d + 0.5) * n_src / n_dst - 0.5
+// = ((2d + 1) n_src - n_dst) / (2 n_dst), >= 0 since n_src >= n_dst; from integers, the weight rounded once to f32
+__device__ __forceinline__ void src_coord(uint32_t d, uint32_t n_src, uint32_t n_dst, uint32_t* s, float* a) {
+  const uint32_t num = (2 * d + 1) * n_src - n_dst, den = 2 * n_dst;  // < 2^32: sides are at most 32768
+  const uint32_t q = num / den;
+  if (q >= n_src - 1) { *s = n_src - 1; *a = 0.f; return; }
+  *s = q;
+  *a = (float)((double)(num - q * den) / (double)den);
+}
+
+// display pass: v = rec / 255, bilinear (horizontal, then vertical, f32), saturate_u8(rint(255 v)).  A frame that failed its checks
+// is zeros in rec and so zeros here.  Grid (row blocks of 256 pixels, display rows, frames).
+__global__ __launch_bounds__(256) void display_kernel(const float* __restrict__ rec, uint8_t* __restrict__ out, uint32_t w, uint32_t h,
+                                                      uint32_t dw, uint32_t dh) {
+  const uint32_t dx = blockIdx.x * kThreads + threadIdx.x, dy = blockIdx.y, f = blockIdx.z;
+  if (dx >= dw) return;
+  uint32_t sx, sy;
+  float ax, ay;
+  src_coord(dx, w, dw, &sx, &ax);
+  src_coord(dy, h, dh, &sy, &ay);
+  const uint32_t sx1 = min(sx + 1, w - 1), sy1 = min(sy + 1, h - 1);
+  const float* r0 = rec + ((size_t)f * h + sy) * w * 3;
+  const float* r1 = rec + ((size_t)f * h + sy1) * w * 3;
+  uint8_t* p = out + (((size_t)f * dh + dy) * dw + dx) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v00 = r0[sx * 3 + c] / 255.f, v01 = r0[sx1 * 3 + c] / 255.f;
+    const float v10 = r1[sx * 3 + c] / 255.f, v11 = r1[sx1 * 3 + c] / 255.f;
+    const float top = v00 * (1.f - ax) + v01 * ax, bot = v10 * (1.f - ax) + v11 * ax;
+    const float q = rintf(255.f * (top * (1.f - ay) + bot * ay));
+    p[c] = (uint8_t)(q < 0.f ? 0.f : (q > 255.f ? 255.f : q));
+  }
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -448,6 +577,18 @@ int validate_limits(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32
   if (n > 65535) return fail(SVC_ERR_UNSUPPORTED, "%s: more than 65535 frames in one call", what);
   if (frame_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)) > 0xFFFFFFFFull)
     return fail(SVC_ERR_UNSUPPORTED, "%s: a frame of %ux%u could exceed the u32 frame_bytes field", what, w, h);
+  return SVC_OK;
+}
+
+// decode: what the reconstruction kernels take (square 8x8 or 16x16 transform blocks and a width of whole 16-pixel segments, as
+// svc_hip_decode_frames; sides up to 32768 for the display pass's u32 coordinates), after the format's own geometry
+int validate_decode_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  if (bw != bh || (bw != 8 && bw != 16))
+    return fail(SVC_ERR_UNSUPPORTED, "%s: transform block %ux%u (supported: 8x8, 16x16)", what, bw, bh);
+  if (w % 16 != 0) return fail(SVC_ERR_UNSUPPORTED, "%s: frame width %u is not a multiple of 16", what, w);
+  if (w > 32768 || h > 32768) return fail(SVC_ERR_UNSUPPORTED, "%s: frame %ux%u above 32768 on a side", what, w, h);
   return SVC_OK;
 }
 
@@ -585,6 +726,81 @@ int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offset
   hipLaunchKernelGGL(drain_kernel, dim3(64), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const uint4*>(d_frames), d_frame_offsets, n_frames, static_cast<uint4*>(d_dst), capacity);
   return check_launch("levels_drain");
+}
+
+uint64_t svc_hip_decode_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                               uint32_t block_h) {
+  if (validate_decode_geom("decode_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
+      validate_limits("decode_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
+    return 0;
+  return ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
+}
+
+int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                 uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                 uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint32_t* d_gaze, uint8_t* d_workspace,
+                                 uint64_t workspace_bytes, float* d_rec, uint8_t* d_display, uint32_t display_w, uint32_t display_h,
+                                 uint32_t* d_status, void* stream) {
+  int rc = validate_decode_geom("decode_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_levels: quant steps must be positive (libs/decoder.cpp:35-47)");
+  const bool display = display_w != 0 || display_h != 0;
+  SVC_REQUIRE(!display || (display_w >= 1 && display_w <= frame_w && display_h >= 1 && display_h <= frame_h),
+              "decode_levels: display %ux%u must lie within 1x1 .. %ux%u (the padded frame)", display_w, display_h, frame_w, frame_h);
+  if ((rc = validate_limits("decode_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "decode_levels: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_rec && d_status, "decode_levels: null pointer");
+  SVC_REQUIRE(display == (d_display != nullptr), "decode_levels: a display buffer goes with a display size, and only with one");
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_rec, 4) &&
+                  aligned(d_status, 4) && aligned(d_gaze, 4),
+              "decode_levels: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
+  UnpackArgs u;
+  u.g = g;
+  u.in = d_frames; u.stream_bytes = stream_bytes; u.offsets = d_frame_offsets;
+  u.planes = nullptr; u.types = nullptr;  // the count pass writes neither
+  u.ws = carve(d_workspace, n_frames, g.groups);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(unpack_kernel<false>, dim3(g.groups, n_frames), dim3(kThreads), 0, s, u);
+  if ((rc = check_launch("decode_levels count"))) return rc;
+  hipLaunchKernelGGL(scan_kernel<true>, dim3(n_frames), dim3(kThreads), 0, s, g, u.ws, d_frames, stream_bytes, d_frame_offsets, d_status);
+  if ((rc = check_launch("decode_levels scan"))) return rc;
+  DecodeArgs a;
+  a.g = g;
+  a.in = d_frames; a.offsets = d_frame_offsets; a.gaze = d_gaze; a.rec = d_rec; a.ws = u.ws;
+  a.fg = (float)fg_step; a.bg = (float)bg_step;
+  const dim3 grid(g.tiles_y * g.gx, n_frames);
+  if (block_w == 8) hipLaunchKernelGGL(decode_levels_kernel<8>, grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL(decode_levels_kernel<16>, grid, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("decode_levels reconstruction")) || !display) return rc;
+  hipLaunchKernelGGL(display_kernel, dim3(div_up(display_w, kThreads), display_h, n_frames), dim3(kThreads), 0, s, d_rec, d_display,
+                     frame_w, frame_h, display_w, display_h);
+  return check_launch("decode_levels display");
+}
+
+int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w, uint32_t frame_h, uint32_t padded_w,
+                      uint32_t padded_h, uint32_t out_xywh[4]) {
+  SVC_REQUIRE(frame_w > 0 && frame_h > 0 && padded_w > 0 && padded_h > 0, "gaze_rect: frame sides must be positive");
+  SVC_REQUIRE(cx < frame_w && cy < frame_h, "gaze_rect: centre (%u, %u) outside the %ux%u frame (libs/decoder.cpp:71-75 asserts)", cx,
+              cy, frame_w, frame_h);
+  SVC_REQUIRE(out_xywh, "gaze_rect: null pointer");
+  // CalcWithinFrameRectFromCenter, libs/decoder.cpp:65-100 (unsigned arithmetic, as there)
+  uint32_t half_w = (max_w + 1) / 2;
+  if (cx + half_w >= frame_w) half_w = frame_w - cx - 1;
+  if (cx < half_w) half_w = cx;
+  uint32_t half_h = (max_h + 1) / 2;
+  if (cy + half_h >= frame_h) half_h = frame_h - cy - 1;
+  if (cy < half_h) half_h = cy;
+  const uint32_t tl_x = cx - half_w, tl_y = cy - half_h, br_x = cx + half_w, br_y = cy + half_h;
+  // to the padded frame: f32 ratios, RoundFloatToInt (libs/decoder.cpp:163-164, :179-183; libs/math.hpp:15-18)
+  const float w_ratio = (float)padded_w / (float)frame_w, h_ratio = (float)padded_h / (float)frame_h;
+  out_xywh[0] = (uint32_t)(int)std::round((float)tl_x * w_ratio);
+  out_xywh[1] = (uint32_t)(int)std::round((float)tl_y * h_ratio);
+  out_xywh[2] = (uint32_t)(int)std::round((float)(br_x - tl_x) * w_ratio);
+  out_xywh[3] = (uint32_t)(int)std::round((float)(br_y - tl_y) * h_ratio);
+  return SVC_OK;
 }
 
 }  // extern "C"

@@ -119,6 +119,10 @@ SIGNATURES = {
     "svc_hip_pack_levels_frames": (C.c_int, [_vp, _vp] + [_u32] * 9 + [_vp, _u64, _vp, _u64, _vp, _vp]),
     "svc_hip_unpack_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _vp, _vp, _vp]),
     "svc_hip_levels_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
+    # its decoder (csrc/levels.hip) and the gaze rule
+    "svc_hip_decode_levels_workspace_bytes": (_u64, [_u32] * 5),
+    "svc_hip_decode_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "svc_hip_gaze_rect": (C.c_int, [_u32] * 8 + [C.POINTER(_u32)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -734,3 +738,45 @@ def levels_drain(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, bl
     assert not dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous()
     _check(load().svc_hip_levels_drain(_dev(frames, torch.uint8), _dev(offsets, torch.int64), n, w, h, bw, bh, mbw, mbh,
                                        dst.data_ptr(), dst.numel(), _stream()))
+
+
+def decode_levels_workspace_bytes(n: int, w: int, h: int, block) -> int:
+    bw, bh = _bwbh(block)
+    return int(load().svc_hip_decode_levels_workspace_bytes(n, w, h, bw, bh))
+
+
+def decode_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, fg_step: int = 1,
+                         bg_step: int = 640, gaze=None, display: Optional[Tuple[int, int]] = None,
+                         rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """A packed stream (u8 on the device) + its offsets -> (rec (frames, H, W, 3) f32 B,G,R at the padded size, display
+    (frames, display_h, display_w, 3) u8 or None, status (frames,) i32 with unpack's codes).  fg_step / bg_step are the DECODER's
+    steps; gaze: None, or per frame x, y, w, h in padded coordinates ((frames, 4) ints, a tensor or a list); display: (w, h)."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    if rec is None:
+        rec = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    dw, dh = display if display is not None else (0, 0)
+    if display is not None and out_display is None:
+        out_display = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(decode_levels_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=dev)
+    g = None
+    if gaze is not None:
+        g = torch.as_tensor(gaze, dtype=torch.int32).reshape(n, 4).to(dev).contiguous()
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_decode_levels_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, w, h, bw, bh,
+                                               mbw, mbh, fg_step, bg_step, None if g is None else _dev(g, torch.int32),
+                                               _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
+                                               None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
+                                               _dev(status, torch.int32), _stream()))
+    return rec, out_display, status
+
+
+def gaze_rect(cx: int, cy: int, max_w: int, max_h: int, frame_w: int, frame_h: int, padded_w: int, padded_h: int
+              ) -> Tuple[int, int, int, int]:
+    """The reference decoder's gaze rectangle around a centre in the source frame, scaled to the padded frame: (x, y, w, h)."""
+    out = (_u32 * 4)()
+    _check(load().svc_hip_gaze_rect(cx, cy, max_w, max_h, frame_w, frame_h, padded_w, padded_h, out))
+    return tuple(int(v) for v in out)
