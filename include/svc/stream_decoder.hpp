@@ -5,6 +5,9 @@
 // Per frame: the gaze rectangle of svc_hip_gaze_rect around the callback's centre, then svc_hip_decode_levels_frames (DecodeBlock
 // over every tile, / 255, bilinear resize, u8).  Batches are staged into pinned memory and copied H2D while the previous batch is
 // in the kernels and the one before it is on its way back as u8 display frames.
+//
+// DecodeWire does the same for the reference's own wire stream (Header + raw-coefficient records, what apps/encoder.cpp writes),
+// with svc_hip_wire_layout deciding how the stream is read and svc_hip_decode_records_frames in place of the compact decoder.
 #ifndef SVC_STREAM_DECODER_HPP
 #define SVC_STREAM_DECODER_HPP
 
@@ -17,10 +20,18 @@
 namespace svc {
 
 struct StreamDecoderConfig {
-  uint32_t display_w = 0, display_h = 0;  // the source size the picture is shown at; 0 = the padded size
+  // The size the picture is shown at.  0 x 0 = a default that depends on the stream: Decode (SVCQ) shows the PADDED size, the only
+  // size its header holds; DecodeWire shows the header's SOURCE size frame_w x frame_h, what the reference's decoder shows
+  // (libs/decoder.cpp:161, :210-211).  Gaze centres are given in display coordinates either way.
+  uint32_t display_w = 0, display_h = 0;
   uint32_t fg_step = 1, bg_step = 640;    // the decoder's steps (apps/decoder.cpp:21-26)
   uint32_t max_gaze_w = 64, max_gaze_h = 64;
-  uint32_t batch = 16;                    // frames per batch
+  uint32_t batch = 16;                    // frames per batch of Decode (a 1080p SVCQ frame is about 1.1 MB)
+  // Frames per batch of DecodeWire.  A 1080p wire frame is 25.07 MB of records (23 x the SVCQ frame), and every slot holds a batch of
+  // them in pinned AND in device memory: depth x wire_batch x 25 MB = 602 MB pinned at the defaults (1.2 GB at 16).  8 frames are
+  // 200 MB per H2D copy, about 4 ms on the link: long enough that the per-batch costs do not show, short enough to keep three
+  // batches in flight without pinning a GB.
+  uint32_t wire_batch = 8;
   uint32_t depth = 3;                     // batches in flight, >= 3 (H2D, kernels and D2H of three batches overlap)
 };
 
@@ -31,10 +42,10 @@ struct DecodedBatch {
   uint32_t count = 0;
   uint32_t width = 0, height = 0;  // of a display frame
   const uint8_t* bgr = nullptr;    // [count][height][width][3] u8 B,G,R
-  const uint32_t* status = nullptr;  // [count]: 0, or svc_hip_unpack_levels_frames's code (the frame is then all zeros)
+  const uint32_t* status = nullptr;  // [count]: 0, or svc_hip_unpack_levels_frames's code (the frame is then all zeros); DecodeWire: 0
 };
 
-// Where the time of one Decode() went: wall time of the calling thread; per-stream device times summed over the batches (the
+// Where the time of one Decode() / DecodeWire() went: wall time of the calling thread; per-stream device times summed over the batches (the
 // streams overlap); the bytes actually moved each way.
 struct DecodeStats {
   uint32_t batches = 0, frames = 0;
@@ -60,6 +71,12 @@ class StreamDecoder {
   // (else std::runtime_error); any later frame that does not match is reported in DecodedBatch::status, not thrown.  gaze may be
   // empty (no gaze).  sink is called once per batch, in stream order, from this thread.
   void Decode(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const Gaze& gaze, const Sink& sink);
+
+  // stream: a whole wire stream of `bytes` bytes in host memory, the 32-byte Header (libs/codec.hpp:8-17) first, then frame_count
+  // frames of records.  svc_hip_wire_layout decides how it is read (the decoder's padded tile grid, or the reference encoder's
+  // unpadded loops); a stream it refuses throws std::runtime_error with its message.  Batches of config.wire_batch frames, the
+  // schedule of Decode; every DecodedBatch::status is 0.  last_stats() is filled as for Decode.
+  void DecodeWire(const uint8_t* stream, uint64_t bytes, const Gaze& gaze, const Sink& sink);
 
   const DecodeStats& last_stats() const;  // of the last Decode() that returned
 

@@ -521,6 +521,53 @@ int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, 
                       uint32_t out_xywh[4]);
 
 /* ------------------------------------------------------------------------- *
+ * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes
+ * of svc_hip_serialize_frames / svc_hip_dct_records_frames and of the reference's encoder): the
+ * reference's Decoder::operator() (libs/decoder.cpp:168-210) without the GUI.  Its records hold
+ * RAW coefficients and the decoder quantises, so this is the stream gaze really scales.
+ *
+ * Per tile: step = gazed ? 1 : (type_word == 0 ? bg_step : fg_step), type_word = the record's
+ * own first u32 (any non-zero value is foreground, libs/decoder.cpp:130-135), gazed = the
+ * frame's rectangle contains the tile origin (x <= tx < x + w && y <= ty < y + h; w or h == 0
+ * holds nothing); requantise, f64 inverse DCT.  d_rec [n][frame_h][frame_w][3] f32 B,G,R at the
+ * padded size is bit-identical to parsing the records into planes + per-tile types and calling
+ * svc_hip_decode_frames(mv_block = block) with that frame's rectangle.  The display pass (d_display,
+ * display_w x display_h) is the one of svc_hip_decode_levels_frames, stated there.
+ *
+ * Geometry: frame_w x frame_h is the PADDED size; the stream's tile grid is frame_w / block
+ * columns by ceil(emit_frame_h / block) rows, frame f at d_records + f * records_stride_bytes
+ * (the inverse of svc_hip_dct_records_frames for every emit_frame_h it accepts).  Tile rows the
+ * stream does not hold (emit_frame_h < frame_h) come out as zeros in d_rec.  Checked in this
+ * order, for any n_frames, before any pointer and without a device: geometry (block 8 or 16 and
+ * frame_w a multiple of 16, else SVC_ERR_UNSUPPORTED as svc_hip_decode_frames; frame_h a multiple
+ * of block; 1 <= emit_frame_h <= frame_h), steps (0 is SVC_ERR_INVALID_ARG, libs/decoder.cpp:35-47),
+ * display size, stride (a multiple of 4, at least svc_hip_serialized_frame_bytes(frame_w,
+ * emit_frame_h, block, block)), then pointers (records, rec and gaze 4-byte aligned).  Only
+ * enqueues work.
+ * ------------------------------------------------------------------------- */
+int svc_hip_decode_records_frames(const uint8_t* d_records, uint64_t records_stride_bytes, uint32_t n_frames,
+                                  uint32_t frame_w, uint32_t frame_h /* padded */, uint32_t block,
+                                  uint32_t emit_frame_h, uint32_t fg_step, uint32_t bg_step,
+                                  const uint32_t* d_gaze /* [n][4] x,y,w,h padded, or NULL */,
+                                  float* d_rec, uint8_t* d_display, uint32_t display_w, uint32_t display_h,
+                                  void* stream);
+
+/* How a whole wire stream of stream_bytes bytes (the 32-byte header first) is read; host-only.
+ * Two readings exist: the DECODER's, the padded grid (frame_w + excess_w) / bw x (frame_h +
+ * excess_h) / bh tiles per frame (libs/decoder.cpp:185-186), and the reference ENCODER's, what
+ * apps/encoder.cpp writes: tile loops over the UNPADDED size (libs/encoder.cpp:647-650; at 1080p
+ * with 8x8 tiles 135 tile rows where its own decoder expects 136).  The length picks the reading:
+ * 32 + frame_count * frame_bytes must match one of them; where both match, the decoder's wins.
+ * The encoder's reading is accepted only with frame_excess_w == 0: otherwise its unpadded row
+ * stride (:258) has scrambled the coefficients.  Refused with a message (SVC_ERR_INVALID_ARG): a
+ * truncated or overlong stream, channel_count != 3, the scrambled reading; SVC_ERR_UNSUPPORTED:
+ * non-square or other than 8x8 / 16x16 tiles, a padded width that is not a multiple of 16.  Out:
+ * *emit_frame_h (the padded height, or frame_h for the encoder's reading) and *frame_bytes, the
+ * arguments of svc_hip_decode_records_frames with frame_w + excess_w x frame_h + excess_h. */
+int svc_hip_wire_layout(const svc_wire_header* hdr, uint64_t stream_bytes, uint32_t* emit_frame_h,
+                        uint64_t* frame_bytes);
+
+/* ------------------------------------------------------------------------- *
  * Pre-step: luma + pyramid on the device, so the pyramid never
  * crosses PCIe.  Stands in for cv::cvtColor(BGR2YUV) + cv::extractChannel +
  * cv::buildPyramid (libs/encoder.cpp:468-470) with this repo's fixed-point

@@ -73,6 +73,8 @@ struct StreamDecoder::Impl {
   // geometry the buffers are sized for (0 = none yet)
   uint32_t pw = 0, ph = 0, bw = 0, bh = 0, mbw = 0, mbh = 0, dw = 0, dh = 0;
   uint64_t disp_bytes = 0, ws_bytes = 0;
+  bool wire = false;        // the buffers are sized for DecodeWire
+  uint64_t frame_bytes = 0; // DecodeWire: bytes of one frame's records
   DevBuf<float> rec;        // the kernels' stream only: one for all slots
   DevBuf<uint8_t> ws;
   std::vector<std::unique_ptr<Slot>> slots;
@@ -88,11 +90,13 @@ struct StreamDecoder::Impl {
   void Size(const uint32_t* hdr) {
     const uint32_t w = hdr[2], h = hdr[3];
     const uint32_t want_dw = c.display_w ? c.display_w : w, want_dh = c.display_h ? c.display_h : h;
-    if (w == pw && h == ph && hdr[4] == bw && hdr[5] == bh && hdr[6] == mbw && hdr[7] == mbh && want_dw == dw && want_dh == dh) return;
+    if (!wire && w == pw && h == ph && hdr[4] == bw && hdr[5] == bh && hdr[6] == mbw && hdr[7] == mbh && want_dw == dw && want_dh == dh)
+      return;
     for (hipStream_t s : {s_in, s_compute, s_out}) Hip(hipStreamSynchronize(s), "hipStreamSynchronize");
     const uint64_t need_ws = svc_hip_decode_levels_workspace_bytes(c.batch, w, h, hdr[4], hdr[5]);
     if (!need_ws) Abi(SVC_ERR_UNSUPPORTED, "no decoder for the first frame's geometry");
     if (want_dw > w || want_dh > h) throw std::runtime_error("svc::StreamDecoder: the display size exceeds the padded frame");
+    wire = false;
     pw = w; ph = h; bw = hdr[4]; bh = hdr[5]; mbw = hdr[6]; mbh = hdr[7]; dw = want_dw; dh = want_dh;
     disp_bytes = (uint64_t)dw * dh * 3;
     ws_bytes = need_ws;
@@ -103,18 +107,35 @@ struct StreamDecoder::Impl {
       s->disp.Alloc(B * disp_bytes); s->pin_disp.Alloc(B * disp_bytes);
     }
   }
+
+  // DecodeWire: a padded w x h frame of `fbytes` bytes of b x b records, shown at want_dw x want_dh
+  void SizeWire(uint32_t w, uint32_t h, uint32_t b, uint64_t fbytes, uint32_t want_dw, uint32_t want_dh) {
+    if (wire && w == pw && h == ph && b == bw && fbytes == frame_bytes && want_dw == dw && want_dh == dh) return;
+    for (hipStream_t s : {s_in, s_compute, s_out}) Hip(hipStreamSynchronize(s), "hipStreamSynchronize");
+    if (want_dw > w || want_dh > h) throw std::runtime_error("svc::StreamDecoder: the display size exceeds the padded frame");
+    wire = true;
+    pw = w; ph = h; bw = bh = b; mbw = mbh = 0; dw = want_dw; dh = want_dh; frame_bytes = fbytes;
+    disp_bytes = (uint64_t)dw * dh * 3;
+    const size_t B = c.wire_batch;
+    rec.Alloc(B * pw * ph * 3);
+    for (auto& s : slots) {
+      s->disp.Alloc(B * disp_bytes); s->pin_disp.Alloc(B * disp_bytes);
+      s->in.Alloc(B * frame_bytes); s->pin_in.Alloc(B * frame_bytes);
+      std::memset(s->pin_status.p, 0, s->pin_status.n * sizeof(uint32_t));  // the records carry no per-frame status
+    }
+  }
 };
 
 StreamDecoder::StreamDecoder(const StreamDecoderConfig& config) : p_(new Impl) {
   Impl& m = *p_;
   m.c = config;
   const StreamDecoderConfig& c = m.c;
-  if (c.batch == 0 || c.depth < 3 || !c.fg_step || !c.bg_step || (c.display_w == 0) != (c.display_h == 0))
+  if (c.batch == 0 || c.wire_batch == 0 || c.depth < 3 || !c.fg_step || !c.bg_step || (c.display_w == 0) != (c.display_h == 0))
     throw std::runtime_error("svc::StreamDecoder: invalid configuration");
   Hip(hipStreamCreateWithFlags(&m.s_in, hipStreamNonBlocking), "hipStreamCreate");
   Hip(hipStreamCreateWithFlags(&m.s_compute, hipStreamNonBlocking), "hipStreamCreate");
   Hip(hipStreamCreateWithFlags(&m.s_out, hipStreamNonBlocking), "hipStreamCreate");
-  const size_t B = c.batch;
+  const size_t B = std::max(c.batch, c.wire_batch);  // per-frame arrays serve both paths
   for (uint32_t i = 0; i < c.depth; ++i) {
     std::unique_ptr<Slot> s(new Slot);
     s->pin_off.Alloc(B + 1); s->off.Alloc(B + 1);
@@ -216,6 +237,87 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
     Hip(hipEventRecord(s.t_out[1], m.s_out), "hipEventRecord");
     Hip(hipEventRecord(s.d2h_done, m.s_out), "hipEventRecord");
     s.d2h_bytes = cnt * (m.disp_bytes + sizeof(uint32_t));
+
+    s.busy = true; s.first = first; s.count = cnt;
+    pending.push_back(&s);
+    first += cnt;
+    if (pending.size() >= c.depth - 1) { deliver(*pending.front()); pending.erase(pending.begin()); }
+  }
+  for (Slot* s : pending) deliver(*s);
+  for (auto& s : m.slots) s->busy = false;  // everything delivered and synchronised
+  st.wall_ms = std::chrono::duration<double, std::milli>(Clock::now() - t_start).count();
+  m.stats = st;
+}
+
+void StreamDecoder::DecodeWire(const uint8_t* stream, uint64_t bytes, const Gaze& gaze, const Sink& sink) {
+  Impl& m = *p_;
+  const StreamDecoderConfig& c = m.c;
+  if (!stream || bytes < sizeof(svc_wire_header)) throw std::runtime_error("svc::StreamDecoder: a wire stream opens with a 32-byte header");
+  svc_wire_header hdr;
+  std::memcpy(&hdr, stream, sizeof(hdr));
+  uint32_t emit_h = 0;
+  uint64_t fbytes = 0;
+  Abi(svc_hip_wire_layout(&hdr, bytes, &emit_h, &fbytes), "svc_hip_wire_layout");
+  const uint32_t n_frames = hdr.frame_count;
+  if (n_frames == 0) { m.stats = DecodeStats{}; return; }
+  m.SizeWire(hdr.frame_w + hdr.frame_excess_w, hdr.frame_h + hdr.frame_excess_h, hdr.transform_block_w, fbytes,
+             c.display_w ? c.display_w : hdr.frame_w, c.display_h ? c.display_h : hdr.frame_h);
+  const uint8_t* records = stream + sizeof(hdr);
+  const uint32_t B = c.wire_batch;
+
+  using Clock = std::chrono::steady_clock;
+  DecodeStats st;
+  const Clock::time_point t_start = Clock::now();
+
+  auto deliver = [&](Slot& s) {
+    Hip(hipEventSynchronize(s.d2h_done), "hipEventSynchronize");
+    float ms = 0;
+    Hip(hipEventElapsedTime(&ms, s.t_in[0], s.t_in[1]), "hipEventElapsedTime"); st.h2d_ms += ms;
+    Hip(hipEventElapsedTime(&ms, s.t_k[0], s.t_k[1]), "hipEventElapsedTime"); st.kernels_ms += ms;
+    Hip(hipEventElapsedTime(&ms, s.t_out[0], s.t_out[1]), "hipEventElapsedTime"); st.d2h_ms += ms;
+    st.h2d_bytes += s.h2d_bytes; st.d2h_bytes += s.d2h_bytes;
+    ++st.batches; st.frames += s.count;
+    DecodedBatch b;
+    b.first_frame = s.first; b.count = s.count; b.width = m.dw; b.height = m.dh;
+    b.bgr = s.pin_disp.p; b.status = s.pin_status.p;
+    sink(b);
+  };
+
+  std::vector<Slot*> pending;
+  for (uint32_t first = 0, k = 0; first < n_frames; ++k) {
+    const uint32_t cnt = std::min(B, n_frames - first);
+    Slot& s = *m.slots[k % c.depth];
+    if (s.busy) { Hip(hipEventSynchronize(s.d2h_done), "hipEventSynchronize"); s.busy = false; }
+    const uint64_t batch_bytes = (uint64_t)cnt * fbytes;  // whole frames: the stream's length was checked by svc_hip_wire_layout
+    m.crew.Copy(s.pin_in.p, records + (uint64_t)first * fbytes, batch_bytes);
+    for (uint32_t i = 0; i < cnt; ++i) {
+      uint32_t x = 0, y = 0, *r = s.pin_gaze.p + 4 * i;
+      if (gaze && gaze(first + i, &x, &y))
+        Abi(svc_hip_gaze_rect(x, y, c.max_gaze_w, c.max_gaze_h, m.dw, m.dh, m.pw, m.ph, r), "svc_hip_gaze_rect");
+      else
+        r[0] = r[1] = r[2] = r[3] = 0;
+    }
+    Hip(hipEventRecord(s.t_in[0], m.s_in), "hipEventRecord");
+    Hip(hipMemcpyAsync(s.in.p, s.pin_in.p, batch_bytes, hipMemcpyHostToDevice, m.s_in), "hipMemcpyAsync H2D");
+    Hip(hipMemcpyAsync(s.gaze.p, s.pin_gaze.p, 4 * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, m.s_in), "hipMemcpyAsync H2D gaze");
+    Hip(hipEventRecord(s.t_in[1], m.s_in), "hipEventRecord");
+    Hip(hipEventRecord(s.h2d_done, m.s_in), "hipEventRecord");
+    s.h2d_bytes = batch_bytes + 4 * cnt * sizeof(uint32_t);
+
+    Hip(hipStreamWaitEvent(m.s_compute, s.h2d_done, 0), "hipStreamWaitEvent");
+    Hip(hipEventRecord(s.t_k[0], m.s_compute), "hipEventRecord");
+    Abi(svc_hip_decode_records_frames(s.in.p, fbytes, cnt, m.pw, m.ph, m.bw, emit_h, c.fg_step, c.bg_step, s.gaze.p, m.rec.p, s.disp.p,
+                                      m.dw, m.dh, m.s_compute),
+        "svc_hip_decode_records_frames");
+    Hip(hipEventRecord(s.t_k[1], m.s_compute), "hipEventRecord");
+    Hip(hipEventRecord(s.compute_done, m.s_compute), "hipEventRecord");
+
+    Hip(hipStreamWaitEvent(m.s_out, s.compute_done, 0), "hipStreamWaitEvent");
+    Hip(hipEventRecord(s.t_out[0], m.s_out), "hipEventRecord");
+    Hip(hipMemcpyAsync(s.pin_disp.p, s.disp.p, cnt * m.disp_bytes, hipMemcpyDeviceToHost, m.s_out), "hipMemcpyAsync D2H display");
+    Hip(hipEventRecord(s.t_out[1], m.s_out), "hipEventRecord");
+    Hip(hipEventRecord(s.d2h_done, m.s_out), "hipEventRecord");
+    s.d2h_bytes = cnt * m.disp_bytes;
 
     s.busy = true; s.first = first; s.count = cnt;
     pending.push_back(&s);

@@ -14,7 +14,9 @@
 // frame (a batch is a few dozen frames).  Group order = (plane, tile row, group in the row) = the order of the levels.
 //
 // decode: unpack's count and scan, then one kernel from the stream straight to the decoder's reconstruction (DecodeBlock with a
-// gaze rectangle per frame, the arithmetic of idct_core.hpp), and optionally the display pass (/ 255, bilinear resize, to u8).
+// gaze rectangle per frame, the arithmetic of idct_core.hpp), and optionally the display pass of display_core.hpp (/ 255, bilinear
+// resize, to u8).
+#include "display_core.hpp"
 #include "idct_core.hpp"
 
 #include <algorithm>
@@ -516,40 +518,6 @@ __global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
   }
 }
 
-// source index s and weight a of s + 1 for destination index d (half-pixel centres): fx = (d + 0.5) * n_src / n_dst - 0.5
-// = ((2d + 1) n_src - n_dst) / (2 n_dst), >= 0 since n_src >= n_dst; from integers, the weight rounded once to f32
-__device__ __forceinline__ void src_coord(uint32_t d, uint32_t n_src, uint32_t n_dst, uint32_t* s, float* a) {
-  const uint32_t num = (2 * d + 1) * n_src - n_dst, den = 2 * n_dst;  // < 2^32: sides are at most 32768
-  const uint32_t q = num / den;
-  if (q >= n_src - 1) { *s = n_src - 1; *a = 0.f; return; }
-  *s = q;
-  *a = (float)((double)(num - q * den) / (double)den);
-}
-
-// display pass: v = rec / 255, bilinear (horizontal, then vertical, f32), saturate_u8(rint(255 v)).  A frame that failed its checks
-// is zeros in rec and so zeros here.  Grid (row blocks of 256 pixels, display rows, frames).
-__global__ __launch_bounds__(256) void display_kernel(const float* __restrict__ rec, uint8_t* __restrict__ out, uint32_t w, uint32_t h,
-                                                      uint32_t dw, uint32_t dh) {
-  const uint32_t dx = blockIdx.x * kThreads + threadIdx.x, dy = blockIdx.y, f = blockIdx.z;
-  if (dx >= dw) return;
-  uint32_t sx, sy;
-  float ax, ay;
-  src_coord(dx, w, dw, &sx, &ax);
-  src_coord(dy, h, dh, &sy, &ay);
-  const uint32_t sx1 = min(sx + 1, w - 1), sy1 = min(sy + 1, h - 1);
-  const float* r0 = rec + ((size_t)f * h + sy) * w * 3;
-  const float* r1 = rec + ((size_t)f * h + sy1) * w * 3;
-  uint8_t* p = out + (((size_t)f * dh + dy) * dw + dx) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float v00 = r0[sx * 3 + c] / 255.f, v01 = r0[sx1 * 3 + c] / 255.f;
-    const float v10 = r1[sx * 3 + c] / 255.f, v11 = r1[sx1 * 3 + c] / 255.f;
-    const float top = v00 * (1.f - ax) + v01 * ax, bot = v10 * (1.f - ax) + v11 * ax;
-    const float q = rintf(255.f * (top * (1.f - ay) + bot * ay));
-    p[c] = (uint8_t)(q < 0.f ? 0.f : (q > 255.f ? 255.f : q));
-  }
-}
-
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -775,7 +743,7 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   if (block_w == 8) hipLaunchKernelGGL(decode_levels_kernel<8>, grid, dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(decode_levels_kernel<16>, grid, dim3(kThreads), 0, s, a);
   if ((rc = check_launch("decode_levels reconstruction")) || !display) return rc;
-  hipLaunchKernelGGL(display_kernel, dim3(div_up(display_w, kThreads), display_h, n_frames), dim3(kThreads), 0, s, d_rec, d_display,
+  hipLaunchKernelGGL(display_kernel, dim3(div_up(display_w, kDisplayThreads), display_h, n_frames), dim3(kDisplayThreads), 0, s, d_rec, d_display,
                      frame_w, frame_h, display_w, display_h);
   return check_launch("decode_levels display");
 }

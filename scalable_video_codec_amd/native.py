@@ -123,6 +123,9 @@ SIGNATURES = {
     "svc_hip_decode_levels_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_decode_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     "svc_hip_gaze_rect": (C.c_int, [_u32] * 8 + [C.POINTER(_u32)]),
+    # the wire stream's decoder (csrc/records.hip) and its reading of a whole stream
+    "svc_hip_decode_records_frames": (C.c_int, [_vp, _u64] + [_u32] * 7 + [_vp, _vp, _vp, _u32, _u32, _vp]),
+    "svc_hip_wire_layout": (C.c_int, [C.POINTER(WireHeader), _u64, C.POINTER(_u32), C.POINTER(_u64)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -780,3 +783,37 @@ def gaze_rect(cx: int, cy: int, max_w: int, max_h: int, frame_w: int, frame_h: i
     out = (_u32 * 4)()
     _check(load().svc_hip_gaze_rect(cx, cy, max_w, max_h, frame_w, frame_h, padded_w, padded_h, out))
     return tuple(int(v) for v in out)
+
+
+def decode_records_frames(records: torch.Tensor, w: int, h: int, block: int, fg_step: int = 1, bg_step: int = 640, gaze=None,
+                          display: Optional[Tuple[int, int]] = None, emit_h: Optional[int] = None,
+                          rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None
+                          ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Wire records (frames, bytes) u8 on the device, frame f's records in row f -> (rec (frames, H, W, 3) f32 B,G,R at the padded
+    size w x h, display (frames, display_h, display_w, 3) u8 or None).  fg_step / bg_step are the DECODER's steps; gaze: None, or per
+    frame x, y, w, h in padded coordinates; display: (w, h); emit_h: the height the records were emitted for (default h; tile rows
+    past it come out as zeros)."""
+    n = records.shape[0]
+    emit_h = h if emit_h is None else emit_h
+    dev = records.device
+    if rec is None:
+        rec = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    dw, dh = display if display is not None else (0, 0)
+    if display is not None and out_display is None:
+        out_display = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=dev)
+    g = None
+    if gaze is not None:
+        g = torch.as_tensor(gaze, dtype=torch.int32).reshape(n, 4).to(dev).contiguous()
+    _check(load().svc_hip_decode_records_frames(_dev(records, torch.uint8), records.stride(0) if n else 4 * (1 + 3 * block * block),
+                                                n, w, h, block, emit_h, fg_step, bg_step, None if g is None else _dev(g, torch.int32),
+                                                _dev(rec, torch.float32), None if out_display is None else _dev(out_display, torch.uint8),
+                                                dw, dh, _stream()))
+    return rec, out_display
+
+
+def wire_layout(header: bytes, stream_bytes: int) -> Tuple[int, int]:
+    """How a whole wire stream of stream_bytes bytes with this 32-byte header is read -> (emit_frame_h, frame_bytes)."""
+    hdr = WireHeader.from_buffer_copy(bytes(header[:C.sizeof(WireHeader)]))
+    emit, per = _u32(), _u64()
+    _check(load().svc_hip_wire_layout(C.byref(hdr), stream_bytes, C.byref(emit), C.byref(per)))
+    return int(emit.value), int(per.value)
