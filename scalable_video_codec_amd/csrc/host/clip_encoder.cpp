@@ -311,10 +311,7 @@ struct ClipEncoder::Impl {
     // have written (or, drained by GrowCoeffSets, will write) set 0, and a step's planes must not end up in two sets.  So the first
     // speculation of a shard waits for a step's first chunk (found by tests/helpers/driver_fuzz.py: chunked steps, the foreground count of
     // the previous step landing between the decisions of two chunks of one step).
-#ifndef SVC_CLIP_ALLOW_MIDSTEP_ROTATION  // 1: the behaviour before the fix, to show that test_the_policy_may_flip_at_every_chunk sees it
-#define SVC_CLIP_ALLOW_MIDSTEP_ROTATION 0
-#endif
-    if (decided && coeff_sets != rec_sets && ((!At(m).first && !SVC_CLIP_ALLOW_MIDSTEP_ROTATION) || !GrowCoeffSets())) {
+    if (decided && coeff_sets != rec_sets && (!At(m).first || !GrowCoeffSets())) {
       decided = false;
       --n_spec;
     }

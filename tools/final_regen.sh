@@ -35,10 +35,6 @@ pmc)
   PMC_GROUPS="6 7" bash tools/pmc_passes.sh $F/pmc_C5 --config C5-4k-4L-dct16 > $F/pmc_C5.log 2>&1; cp $F/pmc_C5/summary.csv $F/${tag}_pmc_C5_traffic_summary.csv; cp $F/pmc_C5/summary.csv.meta.json $F/${tag}_pmc_C5_traffic_summary.csv.meta.json
   PMC_GROUPS="6 7" bash tools/pmc_passes.sh $F/pmc_C2 --config C2-720p-3L-dct8 > $F/pmc_C2.log 2>&1; cp $F/pmc_C2/summary.csv $F/${tag}_pmc_C2_traffic_summary.csv; cp $F/pmc_C2/summary.csv.meta.json $F/${tag}_pmc_C2_traffic_summary.csv.meta.json
   echo pmc done ;;
-pmcpyr)
-  # round 6: SQ / TCP counters of the plane-to-plane pyramid pass before (LDS-tiled, variant library pyr_tiled) and after (pyr_strip_kernel)
-  PMC_KERNEL_FILTER="pyr_strip\|luma_pyr1_kernel<false" bash tools/pmc_variants.sh $F/pmc_pyr "3 4 9" pyr_tiled asbuilt -- --always-speculate > $F/pmc_pyr.txt 2>&1
-  cp $F/pmc_pyr/pyr_tiled_summary.csv $F/${tag}_pmc_pyr_tiled_summary.csv; cp $F/pmc_pyr/asbuilt_summary.csv $F/${tag}_pmc_pyr_strip_summary.csv; echo pmcpyr done ;;
 shards)
   bash tools/shard_sizes.sh > $F/${tag}_shard_rows.jsonl 2>>$F/bench.err; echo shard sizes done ;;
 esac; done

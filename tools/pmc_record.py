@@ -76,7 +76,7 @@ elif a.wire:
         sys.exit("the plane-form figure of this config was collected on other dct sources: re-collect it first")
 else:
     hb = pick(lambda k: "hbma_" in k)
-    lus = [k for k in rows if "luma_pyr1_kernel<true" in k]
+    lus = [k for k in rows if "luma_pyr1_kernel" in k]
     spec = dct.rstrip(">").rstrip().endswith(", true, 1")  # the front-of-step kernel (also stores the luma plane): a figure of its own
     for k in ("dct_bytes_per_launch", "dct_note", "dct_luma_bytes_per_launch", "dct_luma_note"):
         rec.pop(k, None)
