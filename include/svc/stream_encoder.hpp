@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <vector>
 
 #include "svc_hip.h"
 
@@ -49,6 +50,10 @@ struct StreamEncoderConfig {
   bool compact = false;            // the quantised planes leave as the compact stream of include/svc_hip.h ("SVCQ": masks + int16
                                    // levels, ~1 MB instead of 25 MB per 1080p frame): packed on the device, drained by a kernel;
                                    // EncodedBatch::compact instead of coeffs.  Not with `wire`
+  uint32_t compact_budget = 0;     // with `compact`: bytes per frame.  Each frame is packed with the finest entry of compact_ladder whose
+                                   // frame fits (svc_hip_pack_levels_budget_frames; the transform then leaves RAW planes).  0 = the
+                                   // fixed fg_step / bg_step.  SetCompactBudget changes it for a live stream
+  std::vector<svc_step_pair> compact_ladder;  // required with a budget: 1 .. 64 (fg_step, bg_step), finest first, non-decreasing
 };
 
 // One finished batch; the pointers are pinned host memory owned by the encoder and stay valid
@@ -69,6 +74,8 @@ struct EncodedBatch {
   const uint8_t* compact = nullptr;           // compact == true: `count` frames of the compact stream back to back (coeffs is null)
   const uint64_t* compact_offsets = nullptr;  // [count + 1]: frame i in [offsets[i], offsets[i + 1])
   uint64_t compact_bytes = 0;                 // = compact_offsets[count]
+  const uint32_t* compact_choice = nullptr;   // compact_budget != 0: [count] the ladder entry each frame was packed with, bit 31 set
+                                              // when even the last entry is over that frame's budget
 };
 
 // Where the time of one Encode() went (round 6: the PCIe-inclusive rate explains itself).  Host clocks are wall time of the CALLING thread;
@@ -85,6 +92,7 @@ struct EncodeStats {
   double sink_ms = 0;          // host: inside the caller's sink
   double h2d_ms = 0, kernels_ms = 0, d2h_ms = 0;  // device, per stream
   uint64_t h2d_bytes = 0, d2h_bytes = 0;  // bytes actually moved (compact: the used bytes of the stream)
+  uint32_t over_budget_frames = 0;        // compact_budget != 0: frames that no ladder entry fit into (compact_choice bit 31)
 };
 
 class StreamEncoder {
@@ -108,6 +116,13 @@ class StreamEncoder {
   // apps/encoder.cpp:125-148): frames are pulled from `next` as the batches need them.  header_frame_count is what the
   // stream's header announces (the reference takes it from the container, libs/encoder.cpp:361-367), not a limit.
   void Encode(const Source& next, uint32_t header_frame_count, const Sink& sink);
+
+  // The byte budget of every frame of each batch STAGED after this returns; a batch already staged keeps the budget it was staged
+  // with.  Batches are staged in clip order and batch j + depth - 2 is staged before the sink receives batch j, so a call from inside
+  // the sink for batch j applies from batch j + depth - 1 on (with the default depth of 3: j + 2), and a call between Encode() calls
+  // applies to the whole next clip.  Safe from any thread.  Throws std::logic_error on an encoder built without a budget, and
+  // std::invalid_argument for 0.
+  void SetCompactBudget(uint32_t bytes);
 
   uint32_t padded_width() const;
   uint32_t padded_height() const;

@@ -465,6 +465,44 @@ int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offset
                          uint32_t mv_block_h, void* host_dst, uint64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Rate control of the compact stream: per frame the finest steps whose frame fits a byte budget.
+ *
+ * Input: RAW coefficient planes (svc_hip_dct_frames) + region ids, a ladder of ladder_len
+ * (1 .. 64) step pairs on the HOST, finest first: every step > 0, fg_step and bg_step each
+ * non-decreasing along it (so the non-zero level count nz_k is non-increasing in k), and
+ * d_budget [n_frames] u32 bytes.  For frame f and entry k let
+ *   bytes_k = up16(64 + 4 * mv blocks + 8 * 3 * tiles * words + 2 * nz_k),
+ * the frame_bytes svc_hip_pack_levels_frames writes for that frame with entry k's pair.
+ * d_choice[f] = the smallest k with bytes_k <= d_budget[f]; when none fits, ladder_len - 1 with
+ * bit 31 set (over budget: the masks alone, one bit per coefficient, are the floor).  Frame f is
+ * then written BYTE FOR BYTE as svc_hip_pack_levels_frames writes it with pair choice[f] (header
+ * steps, level_count, inexact and frame_bytes included), offsets as there.  A one-entry ladder is
+ * the fixed-step pack.
+ *
+ * Checked in the order of the SVCQ entry points, for any n_frames and before any launch:
+ * geometry; the ladder (its length, a zero step, a decreasing fg_step or bg_step:
+ * SVC_ERR_INVALID_ARG); the int16 bound of svc_hip_pack_levels_frames on entry 0
+ * (SVC_ERR_UNSUPPORTED); limits; workspace and output sizes; then pointers and alignment
+ * (budget and choice 4-byte).  n_frames == 0 returns SVC_OK once the pointer-free checks pass.
+ * Only enqueues work: a count per ladder entry in one pass over the planes, a per-frame
+ * selection, then the pack's count, scan and scatter with each frame's chosen steps.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  uint32_t fg_step, bg_step;
+} svc_step_pair;
+
+/* Scratch of svc_hip_pack_levels_budget_frames; 0 for a geometry or a ladder length it refuses. */
+uint64_t svc_hip_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                    uint32_t block_w, uint32_t block_h, uint32_t ladder_len);
+int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_block_types, uint32_t n_frames,
+                                      uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                      uint32_t mv_block_w, uint32_t mv_block_h,
+                                      const svc_step_pair* ladder /* host, ladder_len entries */, uint32_t ladder_len,
+                                      const uint32_t* d_budget /* [n_frames] bytes */,
+                                      uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                      uint64_t* d_frame_offsets, uint32_t* d_choice /* [n_frames] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Headless decoder of the compact stream: DecodeBlock over every tile with a gaze rectangle per
  * frame (libs/decoder.cpp:128-149, :168-207), then the picture the reference shows.
  *

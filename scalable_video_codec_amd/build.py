@@ -138,6 +138,13 @@ def build_dropin(force: bool = False) -> List[str]:
         _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
               f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
     out.append(exe)
+    # ... and with rate control (StreamEncoderConfig::compact_budget, SetCompactBudget): tests/test_gpu_levels_budget.py
+    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_budget_main")
+    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_budget_main.cpp")
+    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp")]):
+        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
+    out.append(exe)
     # the decoder's host application (svc::StreamDecoder): stream_levels_main's output -> display frames, tests/test_gpu_decode_levels.py
     exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_decode_main")
     src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_decode_main.cpp")

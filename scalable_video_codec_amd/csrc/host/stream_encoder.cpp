@@ -60,8 +60,8 @@ struct Slot {
   PinBuf<uint8_t> pin_packed;
   PinBuf<uint64_t> pin_offsets;
   DevBuf<float> mv, mad, gm, rmse, coeffs;
-  DevBuf<uint32_t> count, types, samples;
-  PinBuf<uint32_t> pin_samples;
+  DevBuf<uint32_t> count, types, samples, budget, choice;
+  PinBuf<uint32_t> pin_samples, pin_budget, pin_choice;
   PinBuf<uint8_t> pin_in, pin_records;
   PinBuf<float> pin_mv, pin_gm, pin_coeffs;
   PinBuf<uint32_t> pin_types;
@@ -85,6 +85,8 @@ struct StreamEncoder::Impl {
   uint32_t bw = 0, bh = 0, tw = 0, th = 0;  // MV block and transform block sides
   uint64_t pyr_stride = 0, frame_bytes = 0, plane_elems = 0, record_bytes = 0, seg_ws_bytes = 0;
   uint64_t packed_bytes = 0, pack_ws_bytes = 0;  // compact: worst case of a batch, pack workspace
+  bool budgeted = false;                          // compact_budget != 0: rate control
+  std::atomic<uint32_t> budget{0};                // bytes per frame of the next batch staged (SetCompactBudget)
   std::vector<std::unique_ptr<Slot>> slots;
   hipStream_t s_in = nullptr, s_compute = nullptr, s_out = nullptr;
   bool fused_records = false;  // wire: the transform kernel emits the records itself
@@ -122,9 +124,17 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   m.fused_records = c.wire && m.tw == m.th && (!c.reference_stream || m.pw == c.width);
   m.iters = svc_hip_ransac_iter_count(c.ransac);
   m.seg_ws_bytes = svc_hip_segment_workspace_bytes(m.mfw, m.mfh, c.batch, c.segment.attempt_count);
+  if (c.compact_budget && !c.compact) throw std::runtime_error("svc::StreamEncoder: a byte budget is a setting of the compact stream");
+  m.budgeted = c.compact_budget != 0;
+  m.budget.store(c.compact_budget);
+  if (m.budgeted)  // the budgeted pack's checks that need neither a device pointer nor a size: geometry, the ladder, the int16 bound
+    Abi(svc_hip_pack_levels_budget_frames(nullptr, nullptr, 0, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.compact_ladder.data(),
+                                          (uint32_t)c.compact_ladder.size(), nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr, nullptr,
+                                          nullptr), "compact_ladder");
   if (c.compact) {
     m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
-    m.pack_ws_bytes = svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
+    m.pack_ws_bytes = m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
+                                 : svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
     if (!m.packed_bytes || !m.pack_ws_bytes) throw std::runtime_error("svc::StreamEncoder: no compact stream for this geometry");
   }
   m.crew.reset(new CopyCrew(std::min<uint32_t>(c.copy_threads ? c.copy_threads - 1 : 0, 15)));
@@ -153,6 +163,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
       s->packed.Alloc(m.packed_bytes); s->pack_ws.Alloc(m.pack_ws_bytes); s->offsets.Alloc(B + 1);
       s->pin_packed.Alloc(m.packed_bytes); s->pin_offsets.Alloc(B + 1);
     }
+    if (m.budgeted) { s->budget.Alloc(B); s->choice.Alloc(B); s->pin_budget.Alloc(B); s->pin_choice.Alloc(B); }
     Hip(hipEventCreateWithFlags(&s->h2d_done, hipEventDisableTiming), "hipEventCreate");
     Hip(hipEventCreateWithFlags(&s->compute_done, hipEventDisableTiming), "hipEventCreate");
     Hip(hipEventCreateWithFlags(&s->d2h_done, hipEventDisableTiming), "hipEventCreate");
@@ -165,6 +176,12 @@ StreamEncoder::~StreamEncoder() = default;
 uint32_t StreamEncoder::padded_width() const { return p_->pw; }
 uint32_t StreamEncoder::padded_height() const { return p_->ph; }
 const EncodeStats& StreamEncoder::last_stats() const { return p_->stats; }
+
+void StreamEncoder::SetCompactBudget(uint32_t bytes) {
+  if (!p_->budgeted) throw std::logic_error("svc::StreamEncoder: SetCompactBudget on an encoder built without compact_budget");
+  if (bytes == 0) throw std::invalid_argument("svc::StreamEncoder: a byte budget of 0");
+  p_->budget.store(bytes);
+}
 
 void StreamEncoder::Encode(const uint8_t* bgr, uint32_t n_frames, const Sink& sink) {
   if (!bgr || n_frames < 2) throw std::runtime_error("svc::StreamEncoder: a clip needs at least two frames");
@@ -204,6 +221,8 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     Hip(hipEventElapsedTime(&ms, s.t_out[0], s.t_out[1]), "hipEventElapsedTime"); st.d2h_ms += ms;
     st.h2d_bytes += s.h2d_bytes; st.d2h_bytes += s.d2h_bytes;
     if (c.compact) st.d2h_bytes += s.pin_offsets.p[s.encoded];  // the drain moved exactly the used bytes
+    if (m.budgeted)
+      for (uint32_t i = 0; i < s.encoded; ++i) st.over_budget_frames += s.pin_choice.p[i] >> 31;
     ++st.batches; st.encoded_frames += s.encoded;
     t0 = Clock::now();
     EncodedBatch b;
@@ -214,6 +233,7 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     b.coeffs = c.wire || c.compact ? nullptr : s.pin_coeffs.p;
     if (c.compact) {
       b.compact = s.pin_packed.p; b.compact_offsets = s.pin_offsets.p; b.compact_bytes = s.pin_offsets.p[s.encoded];
+      b.compact_choice = m.budgeted ? s.pin_choice.p : nullptr;
     }
     b.records = c.wire ? s.pin_records.p : nullptr;
     b.record_bytes = m.record_bytes;
@@ -270,6 +290,12 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       Hip(hipMemcpyAsync(s.samples.p, s.pin_samples.p, (size_t)encoded * m.iters * c.ransac.subset_sz * sizeof(uint32_t),
                          hipMemcpyHostToDevice, m.s_in), "hipMemcpyAsync samples");
     }
+    if (m.budgeted) {  // the budget as it stands now, for every frame of this batch (SetCompactBudget's rule)
+      const uint32_t bytes = m.budget.load();
+      std::fill(s.pin_budget.p, s.pin_budget.p + encoded, bytes);
+      Hip(hipMemcpyAsync(s.budget.p, s.pin_budget.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyHostToDevice, m.s_in),
+          "hipMemcpyAsync budget");
+    }
     Hip(hipEventRecord(s.t_in[1], m.s_in), "hipEventRecord");
     Hip(hipEventRecord(s.h2d_done, m.s_in), "hipEventRecord");
     s.frames = off + n_new;
@@ -298,6 +324,12 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       const uint32_t sw = c.reference_stream ? c.width : m.pw, sh = c.reference_stream ? c.height : m.ph;
       Abi(svc_hip_serialize_frames(s.coeffs.p, m.plane_elems, B, s.types.p, sw, sh, m.tw, m.th, m.mfw, m.mfh,
                                    m.bw, m.bh, s.records.p, m.record_bytes, m.s_compute), "svc_hip_serialize_frames");
+    } else if (m.budgeted) {  // raw planes; the pack picks each frame's steps from its budget
+      Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, m.s_compute), "svc_hip_dct_frames");
+      Abi(svc_hip_pack_levels_budget_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.compact_ladder.data(),
+                                            (uint32_t)c.compact_ladder.size(), s.budget.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
+                                            m.packed_bytes, s.offsets.p, s.choice.p, m.s_compute),
+          "svc_hip_pack_levels_budget_frames");
     } else {
       Abi(svc_hip_dct_quant_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.types.p, m.bw,
                                    m.bh, c.fg_step, c.bg_step, s.coeffs.p, m.s_compute), "svc_hip_dct_quant_frames");
@@ -313,6 +345,7 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     Hip(hipEventRecord(s.t_out[0], m.s_out), "hipEventRecord");
     s.d2h_bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : c.compact ? 0 : 3 * m.plane_elems * sizeof(float)));
     if (c.compact) s.d2h_bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t);  // + the stream's used bytes, known at delivery
+    if (m.budgeted) s.d2h_bytes += (uint64_t)encoded * sizeof(uint32_t);
     Hip(hipMemcpyAsync(s.pin_mv.p, s.mv.p, (size_t)encoded * m.blocks * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H mv");
     Hip(hipMemcpyAsync(s.pin_types.p, s.types.p, (size_t)encoded * m.blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "D2H types");
     Hip(hipMemcpyAsync(s.pin_gm.p, s.gm.p, (size_t)encoded * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H gm");
@@ -323,6 +356,8 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
                                m.s_out), "svc_hip_levels_drain");
       Hip(hipMemcpyAsync(s.pin_offsets.p, s.offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, m.s_out),
           "D2H offsets");
+      if (m.budgeted)
+        Hip(hipMemcpyAsync(s.pin_choice.p, s.choice.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "D2H choice");
     } else
       Hip(hipMemcpyAsync(s.pin_coeffs.p, s.coeffs.p, (size_t)encoded * 3 * m.plane_elems * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H coeffs");
     Hip(hipEventRecord(s.t_out[1], m.s_out), "hipEventRecord");

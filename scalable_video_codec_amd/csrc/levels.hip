@@ -13,6 +13,9 @@
 // The frame offsets are not scanned by a kernel of their own: the scatter's workgroup sums the frame sizes before its own
 // frame (a batch is a few dozen frames).  Group order = (plane, tile row, group in the row) = the order of the levels.
 //
+// budgeted pack (rate control): a count per ladder entry, a per-frame choice of steps from a byte budget, then the pack's count,
+// scan and scatter with each frame's chosen steps.
+//
 // decode: unpack's count and scan, then one kernel from the stream straight to the decoder's reconstruction (DecodeBlock with a
 // gaze rectangle per frame, the arithmetic of idct_core.hpp), and optionally the display pass of display_core.hpp (/ 255, bilinear
 // resize, to u8).
@@ -219,6 +222,7 @@ struct PackArgs {
   uint64_t* offsets;     // [n + 1]
   Ws ws;
   uint32_t n, fg, bg;
+  const uint32_t* steps; // [n][2] fg, bg per frame (the budgeted pack's choice), or null: fg / bg for every frame
 };
 
 // SCATTER = false: the group's non-zero count and inexact count.  SCATTER = true: masks and levels at their final place (plus,
@@ -234,6 +238,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   const uint32_t gi = blockIdx.x, f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const Group gr = group_of(g, gi);
   const uint32_t* types = a.types + (size_t)f * g.mvb;
+  const uint32_t fg = a.steps ? a.steps[2 * f] : a.fg, bg = a.steps ? a.steps[2 * f + 1] : a.bg;
   stage_rows(g, gr, a.planes + ((size_t)f * 3 + gr.plane) * g.h * g.w, lds);
   if (SCATTER && wave == 0) {  // this frame's offset: the sizes of the frames before it
     uint64_t s = 0;
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   uint32_t nz_count = 0, inexact = 0;
   for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
     const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
-    const float step = tile_type(g, types, gr, t) == 0 ? (float)a.bg : (float)a.fg;
+    const float step = tile_type(g, types, gr, t) == 0 ? (float)bg : (float)fg;
     int32_t lv = 0;
     if (k < area) {
       const float c = lds[lds_index(g, gr, t, k)];
@@ -294,7 +299,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
     const uint64_t mask = job_mask[j];
     if (!((mask >> lane) & 1u)) continue;
     const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
-    const float step = tile_type(g, types, gr, t) == 0 ? (float)a.bg : (float)a.fg;
+    const float step = tile_type(g, types, gr, t) == 0 ? (float)bg : (float)fg;
     levels[job_base[j] + lane_rank(mask)] = (int16_t)level_of(lds[lds_index(g, gr, t, k)], step);
   }
   if (gi != 0) return;
@@ -302,7 +307,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   const uint32_t level_count = a.ws.frame_levels[f], fbytes = a.ws.frame_bytes[f];
   uint32_t* hdr = reinterpret_cast<uint32_t*>(frame);
   if (threadIdx.x < 16) {
-    const uint32_t v[16] = {kMagic, kVersion, g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh, a.fg, a.bg, level_count, a.ws.frame_inexact[f],
+    const uint32_t v[16] = {kMagic, kVersion, g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh, fg, bg, level_count, a.ws.frame_inexact[f],
                             fbytes, 0, 0, 0};
     hdr[threadIdx.x] = v[threadIdx.x];
   }
@@ -353,6 +358,118 @@ __global__ __launch_bounds__(256) void scan_kernel(Geom g, Ws ws, const uint8_t*
     ws.status[f] = st;
     d_status[f] = st;
   }
+}
+
+// ---- budgeted pack: per frame the finest ladder entry whose frame fits its byte budget ------------------------------------------
+
+constexpr uint32_t kMaxLadder = 64;  // one entry per lane of a wave
+
+// The ladder as the kernels take it (by value: 1 KB of kernel arguments, no copy to the device).  tau[c][k] = the smallest f32
+// >= step * (0.5 - 2^-26), class c = 0 background, 1 foreground: with a correctly rounded division, level_of(x, step) != 0
+// exactly when |x| >= tau (fl(|x| / step) >= 0.5 under round-to-nearest-even, and std::round sends 0.5 away from zero).
+struct Ladder {
+  uint32_t len;
+  uint32_t step[2][kMaxLadder];
+  float tau[2][kMaxLadder];
+};
+
+// workspace of the budgeted pack: the pack's own, then per (frame, entry, group) the non-zero levels, per (frame, entry) the frame's
+// size, per frame its steps
+struct BudgetWs {
+  Ws pack;
+  uint32_t *nz, *steps;
+  uint64_t* bytes;
+};
+uint64_t budget_ws_bytes(uint32_t n, uint32_t groups, uint32_t len) {
+  return ws_bytes(n, groups) + up16(4ull * n * len * groups) + up16(8ull * n * len) + up16(8ull * n);
+}
+BudgetWs carve_budget(uint8_t* p, uint32_t n, uint32_t groups, uint32_t len) {
+  BudgetWs s;
+  s.pack = carve(p, n, groups);
+  uint8_t* q = p + ws_bytes(n, groups);
+  s.nz = reinterpret_cast<uint32_t*>(q);
+  q += up16(4ull * n * len * groups);
+  s.bytes = reinterpret_cast<uint64_t*>(q);
+  q += up16(8ull * n * len);
+  s.steps = reinterpret_cast<uint32_t*>(q);
+  return s;
+}
+
+// the smallest f32 >= step * (0.5 - 2^-26) = N / 2^26 with N = step * (2^25 - 1) < 2^57, exactly: every candidate is >= 0.25, so
+// candidate * 2^26 is an integer below 2^64 and compares with N without rounding
+float zero_threshold(uint32_t step) {
+  const uint64_t n = (uint64_t)step * ((1u << 25) - 1);
+  auto ge = [n](float f) { return (uint64_t)((double)f * 67108864.0) >= n; };
+  float f = (float)std::ldexp((double)n, -26);
+  while (!ge(f)) f = std::nextafter(f, INFINITY);
+  while (ge(std::nextafter(f, 0.f))) f = std::nextafter(f, 0.f);
+  return f;
+}
+
+// One group as pack_kernel splits it.  Per 64-coefficient word (the tile, hence the step class, is the same in every lane):
+// entry k keeps a coefficient when |c| >= tau[k]; tau is non-decreasing along the ladder, so the words' ballots for k = 0, 1, ...
+// shrink and the loop stops at the first empty one -- a background word at a coarse step costs one ballot.  Lane k holds tau[k] of
+// both classes in registers and the loop reads the one it needs with readlane (no memory access in the loop); lane k of each wave
+// also sums entry k's popcounts, the four waves add up through LDS and thread k stores nz[f][k][group].
+__global__ __launch_bounds__(256) void budget_count_kernel(Geom g, const float* __restrict__ planes, const uint32_t* __restrict__ types_all,
+                                                           Ladder lad, uint32_t* __restrict__ nz) {
+  extern __shared__ float lds[];
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  const uint32_t gi = blockIdx.x, f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const Group gr = group_of(g, gi);
+  const uint32_t* types = types_all + (size_t)f * g.mvb;
+  const float tau_bg = lane < lad.len ? lad.tau[0][lane] : INFINITY, tau_fg = lane < lad.len ? lad.tau[1][lane] : INFINITY;
+  stage_rows(g, gr, planes + ((size_t)f * 3 + gr.plane) * g.h * g.w, lds);
+  __syncthreads();
+  const uint32_t area = g.bw * g.bh, jobs = gr.nt * g.words;
+  uint32_t acc = 0;  // lane k: this wave's non-zero levels at entry k
+  for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
+    const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
+    const int tau = __float_as_int(tile_type(g, types, gr, t) == 0 ? tau_bg : tau_fg);
+    // a NaN quantises to -32768 (fmaxf drops it): kept at every entry, as the pack keeps it
+    const float c = k < area ? lds[lds_index(g, gr, t, k)] : 0.f;
+    const float m = c != c ? INFINITY : fabsf(c);
+    for (uint32_t e = 0; e < lad.len; ++e) {
+      const uint64_t mask = __ballot(m >= __int_as_float(__builtin_amdgcn_readlane(tau, e)));
+      if (mask == 0) break;
+      acc += lane == e ? (uint32_t)__popcll(mask) : 0u;
+    }
+  }
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (threadIdx.x < lad.len)
+    nz[((size_t)f * lad.len + threadIdx.x) * g.groups + gi] =
+        part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+// One workgroup per (entry, frame): nz_k of the frame = the sum over its groups, as bytes_k = up16(levels_off + 2 nz_k).
+__global__ __launch_bounds__(256) void budget_sum_kernel(Geom g, uint32_t len, const uint32_t* __restrict__ nz, uint64_t* __restrict__ bytes) {
+  __shared__ uint64_t red[kThreads / 64];
+  const uint32_t k = blockIdx.x, f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t* p = nz + ((size_t)f * len + k) * g.groups;
+  uint64_t s = 0;
+  for (uint32_t i = threadIdx.x; i < g.groups; i += kThreads) s += p[i];
+  for (uint32_t off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) bytes[(size_t)f * len + k] = up16(g.levels_off + 2 * (red[0] + red[1] + red[2] + red[3]));
+}
+
+// One thread per frame: choice = the smallest k with bytes_k <= budget, else the last entry with bit 31 set; that entry's steps go to
+// the pack.
+__global__ __launch_bounds__(256) void budget_select_kernel(uint32_t n, Ladder lad, const uint64_t* __restrict__ bytes,
+                                                            const uint32_t* __restrict__ budget, uint32_t* __restrict__ steps,
+                                                            uint32_t* __restrict__ choice) {
+  const uint32_t f = blockIdx.x * kThreads + threadIdx.x;
+  if (f >= n) return;
+  const uint64_t b = budget[f];
+  const uint64_t* fb = bytes + (size_t)f * lad.len;
+  uint32_t k = 0;
+  while (k < lad.len && fb[k] > b) ++k;
+  const uint32_t pick = k < lad.len ? k : lad.len - 1;
+  choice[f] = k < lad.len ? k : (pick | 0x80000000u);
+  steps[2 * f] = lad.step[1][pick];
+  steps[2 * f + 1] = lad.step[0][pick];
 }
 
 // ---- unpack ------------------------------------------------------------------------------------------------------------------
@@ -613,7 +730,7 @@ int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_ty
   a.g = g;
   a.planes = d_planes; a.types = d_block_types; a.out = d_out; a.offsets = d_frame_offsets;
   a.ws = carve(d_workspace, n_frames, g.groups);
-  a.n = n_frames; a.fg = fg_step; a.bg = bg_step;
+  a.n = n_frames; a.fg = fg_step; a.bg = bg_step; a.steps = nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(g.groups, n_frames);
   hipLaunchKernelGGL(pack_kernel<false>, grid, dim3(kThreads), lds_bytes(g), s, a);
@@ -622,6 +739,81 @@ int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_ty
   if ((rc = check_launch("pack_levels scan"))) return rc;
   hipLaunchKernelGGL(pack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
   return check_launch("pack_levels scatter");
+}
+
+uint64_t svc_hip_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                    uint32_t block_h, uint32_t ladder_len) {
+  if (validate_geom("pack_levels_budget_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
+      validate_limits("pack_levels_budget_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
+    return 0;
+  if (ladder_len == 0 || ladder_len > kMaxLadder) {
+    (void)fail(SVC_ERR_INVALID_ARG, "pack_levels_budget_workspace_bytes: a ladder of %u entries (1 .. %u)", ladder_len, kMaxLadder);
+    return 0;
+  }
+  return budget_ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups, ladder_len);
+}
+
+// Checked in the order of svc_hip_pack_levels_frames, the ladder in place of the steps: geometry, ladder, int16 bound on entry 0,
+// limits, sizes, then pointers; n_frames == 0 returns SVC_OK after the checks that need no device pointer.
+int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_block_types, uint32_t n_frames, uint32_t frame_w,
+                                      uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                      const svc_step_pair* ladder, uint32_t ladder_len, const uint32_t* d_budget, uint8_t* d_workspace,
+                                      uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets,
+                                      uint32_t* d_choice, void* stream) {
+  int rc = validate_geom("pack_levels_budget", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(ladder_len >= 1 && ladder_len <= kMaxLadder, "pack_levels_budget: a ladder of %u entries (1 .. %u)", ladder_len, kMaxLadder);
+  SVC_REQUIRE(ladder != nullptr, "pack_levels_budget: null ladder");
+  for (uint32_t k = 0; k < ladder_len; ++k) {
+    SVC_REQUIRE(ladder[k].fg_step > 0 && ladder[k].bg_step > 0, "pack_levels_budget: ladder entry %u: quant steps must be positive", k);
+    SVC_REQUIRE(k == 0 || (ladder[k].fg_step >= ladder[k - 1].fg_step && ladder[k].bg_step >= ladder[k - 1].bg_step),
+                "pack_levels_budget: ladder entry %u (%u, %u) is below entry %u (%u, %u): the ladder must be non-decreasing", k,
+                ladder[k].fg_step, ladder[k].bg_step, k - 1, ladder[k - 1].fg_step, ladder[k - 1].bg_step);
+  }
+  // entry 0 holds the smallest steps: the bound of svc_hip_pack_levels_frames there covers the whole ladder
+  const uint32_t smin = std::min(ladder[0].fg_step, ladder[0].bg_step);
+  if (255.0 * std::sqrt((double)block_w * block_h) / smin > 32767.0)
+    return fail(SVC_ERR_UNSUPPORTED, "pack_levels_budget: levels of a %ux%u tile at step %u could exceed int16", block_w, block_h, smin);
+  if ((rc = validate_limits("pack_levels_budget", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  const uint64_t ws_need = budget_ws_bytes(n_frames, g.groups, ladder_len);
+  SVC_REQUIRE(workspace_bytes >= ws_need, "pack_levels_budget: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
+  const uint64_t need = n_frames * frame_max_bytes(g);
+  SVC_REQUIRE(out_capacity >= need, "pack_levels_budget: output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)out_capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_planes && d_block_types && d_budget && d_workspace && d_out && d_frame_offsets && d_choice, "pack_levels_budget: null pointer");
+  SVC_REQUIRE(aligned(d_planes, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_block_types, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
+              "pack_levels_budget: planes, output and workspace must be 16-byte aligned, offsets 8-byte, types, budget and choice 4-byte");
+  Ladder lad{};
+  lad.len = ladder_len;
+  for (uint32_t k = 0; k < ladder_len; ++k) {
+    lad.step[0][k] = ladder[k].bg_step; lad.step[1][k] = ladder[k].fg_step;
+    lad.tau[0][k] = zero_threshold(ladder[k].bg_step); lad.tau[1][k] = zero_threshold(ladder[k].fg_step);
+  }
+  const BudgetWs bws = carve_budget(d_workspace, n_frames, g.groups, ladder_len);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(g.groups, n_frames);
+  hipLaunchKernelGGL(budget_count_kernel, grid, dim3(kThreads), lds_bytes(g), s, g, d_planes, d_block_types, lad, bws.nz);
+  if ((rc = check_launch("pack_levels_budget count per entry"))) return rc;
+  hipLaunchKernelGGL(budget_sum_kernel, dim3(ladder_len, n_frames), dim3(kThreads), 0, s, g, ladder_len, bws.nz, bws.bytes);
+  if ((rc = check_launch("pack_levels_budget sum"))) return rc;
+  hipLaunchKernelGGL(budget_select_kernel, dim3(div_up(n_frames, kThreads)), dim3(kThreads), 0, s, n_frames, lad, bws.bytes, d_budget,
+                     bws.steps, d_choice);
+  if ((rc = check_launch("pack_levels_budget select"))) return rc;
+  PackArgs a;
+  a.g = g;
+  a.planes = d_planes; a.types = d_block_types; a.out = d_out; a.offsets = d_frame_offsets;
+  a.ws = bws.pack;
+  a.n = n_frames; a.fg = 0; a.bg = 0; a.steps = bws.steps;
+  hipLaunchKernelGGL(pack_kernel<false>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  if ((rc = check_launch("pack_levels_budget count"))) return rc;
+  hipLaunchKernelGGL(scan_kernel<false>, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws, nullptr, 0, nullptr, nullptr);
+  if ((rc = check_launch("pack_levels_budget scan"))) return rc;
+  hipLaunchKernelGGL(pack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  return check_launch("pack_levels_budget scatter");
 }
 
 int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,

@@ -1,5 +1,6 @@
 """Host reader of the compact quantised-coefficient stream ("SVCQ", format version 1; layout in include/svc_hip.h, written by
-svc_hip_pack_levels_frames).  Pure numpy: a consumer of the stream needs neither a GPU nor the native library."""
+svc_hip_pack_levels_frames), and the step ladders its rate control (svc_hip_pack_levels_budget_frames) picks from.  Pure numpy: a
+consumer of the stream needs neither a GPU nor the native library."""
 from __future__ import annotations
 
 from typing import Dict, Iterator, Tuple
@@ -72,3 +73,34 @@ def iter_frames(buf, offsets) -> Iterator[Tuple[Dict[str, int], np.ndarray, np.n
         if hdr["frame_bytes"] != hi - lo:
             raise ValueError(f"SVCQ frame at {lo} has frame_bytes {hdr['frame_bytes']}, its offsets {hi - lo}")
         yield hdr, types, planes
+
+
+def step_ladder(fg_lo: int, fg_hi: int, bg_lo: int, bg_hi: int, n_bg: int, n_fg: int) -> np.ndarray:
+    """A rate-control ladder, finest first: (K, 2) u32 rows (fg_step, bg_step), both columns non-decreasing.
+
+    The background degrades before the foreground (the codec's content scalability): first
+      (fg_lo, round(bg_lo * (bg_hi / bg_lo) ** (i / n_bg)))  for i = 0 .. n_bg,
+    then
+      (round(fg_lo * (fg_hi / fg_lo) ** (j / n_fg)), bg_hi)  for j = 1 .. n_fg,
+    with round(x) = floor(x + 0.5) and exact end points; a pair equal to the one before it is dropped.  n_bg = 0 starts at
+    (fg_lo, bg_hi); n_fg = 0 ends there.  At most n_bg + n_fg + 1 entries (the C ABI takes up to 64)."""
+    for v in (fg_lo, fg_hi, bg_lo, bg_hi):
+        if int(v) != v or v < 1:
+            raise ValueError("steps are positive integers")
+    if fg_lo > fg_hi or bg_lo > bg_hi:
+        raise ValueError("a ladder runs from the finest step to the coarsest")
+    if n_bg < 0 or n_fg < 0:
+        raise ValueError("the numbers of steps are not negative")
+
+    def geometric(lo: int, hi: int, i: int, n: int) -> int:
+        if n == 0 or i == n:
+            return int(hi)
+        return int(min(hi, max(lo, np.floor(lo * (hi / lo) ** (i / n) + 0.5))))
+
+    pairs = [(int(fg_lo), geometric(bg_lo, bg_hi, i, n_bg)) for i in range(n_bg + 1)]
+    pairs += [(geometric(fg_lo, fg_hi, j, n_fg), int(bg_hi)) for j in range(1, n_fg + 1)]
+    out = [pairs[0]]
+    for p in pairs[1:]:
+        if p != out[-1]:
+            out.append(p)
+    return np.array(out, np.uint32).reshape(-1, 2)

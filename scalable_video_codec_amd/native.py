@@ -37,6 +37,10 @@ class SegmentParams(C.Structure):
                 ("connectivity", C.c_uint32)]
 
 
+class StepPair(C.Structure):  # svc_step_pair: one entry of a rate-control ladder
+    _fields_ = [("fg_step", C.c_uint32), ("bg_step", C.c_uint32)]
+
+
 class WireHeader(C.Structure):  # libs/codec.hpp:8-17
     _fields_ = [(n, C.c_uint32) for n in ("frame_count", "frame_w", "frame_h", "frame_excess_w", "frame_excess_h",
                                           "transform_block_w", "transform_block_h", "channel_count")]
@@ -119,6 +123,10 @@ SIGNATURES = {
     "svc_hip_pack_levels_frames": (C.c_int, [_vp, _vp] + [_u32] * 9 + [_vp, _u64, _vp, _u64, _vp, _vp]),
     "svc_hip_unpack_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _vp, _vp, _vp]),
     "svc_hip_levels_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
+    # its rate control: per-frame steps from a byte budget (csrc/levels.hip)
+    "svc_hip_pack_levels_budget_workspace_bytes": (_u64, [_u32] * 6),
+    "svc_hip_pack_levels_budget_frames": (C.c_int, [_vp, _vp] + [_u32] * 7 + [C.POINTER(StepPair), _u32, _vp, _vp, _u64, _vp, _u64, _vp,
+                                                                             _vp, _vp]),
     # its decoder (csrc/levels.hip) and the gaze rule
     "svc_hip_decode_levels_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_decode_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
@@ -709,6 +717,56 @@ def pack_levels_frames(planes: torch.Tensor, block_types: torch.Tensor, block, m
                                              fg_step, bg_step, _dev(workspace, torch.uint8), workspace.numel(),
                                              _dev(out, torch.uint8), out.numel(), _dev(offsets, torch.int64), _stream()))
     return out, offsets
+
+
+def _ladder(ladder) -> Tuple[C.Array, int]:
+    """[(fg_step, bg_step), ...] -> a svc_step_pair array for the C ABI (the library checks it)."""
+    pairs = [(int(fg), int(bg)) for fg, bg in ladder]
+    arr = (StepPair * max(1, len(pairs)))(*[StepPair(fg, bg) for fg, bg in pairs])
+    return arr, len(pairs)
+
+
+def pack_levels_budget_workspace_bytes(n: int, w: int, h: int, block, ladder_len: int) -> int:
+    bw, bh = _bwbh(block)
+    return int(load().svc_hip_pack_levels_budget_workspace_bytes(n, w, h, bw, bh, ladder_len))
+
+
+def budget_tensor(budget, n: int, device) -> torch.Tensor:
+    """A byte budget (one int for every frame, or one per frame) -> (n,) i32 on the device holding the u32 values."""
+    import numpy as np
+    b = np.broadcast_to(np.asarray(budget, np.int64), (n,))
+    if (b < 0).any() or (b > 0xFFFFFFFF).any():
+        raise ValueError("a budget is a u32 byte count")
+    return torch.from_numpy(b.astype(np.uint32).view(np.int32).copy()).to(device)
+
+
+def pack_levels_budget_frames(planes: torch.Tensor, block_types: torch.Tensor, block, mv_block, ladder, budget,
+                              out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                              workspace: Optional[torch.Tensor] = None, choice: Optional[torch.Tensor] = None
+                              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """RAW coefficient planes (frames, 3, H, W) f32 + region ids -> each frame packed with the finest ladder entry (fg_step, bg_step)
+    whose frame fits its byte budget (include/svc_hip.h).  budget: an int, one value per frame, or an (frames,) i32 device tensor
+    of u32 bytes.  -> (stream u8, offsets (frames + 1,) i64, choice (frames,) i32 on the device: the entry's index, with bit 31
+    set (a negative int32) when even the last entry is over budget)."""
+    n, _, h, w = planes.shape
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    arr, k = _ladder(ladder)
+    dev = planes.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(pack_levels_budget_workspace_bytes(n, w, h, block, k), 16), dtype=torch.uint8, device=dev)
+    if choice is None:
+        choice = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    if not (isinstance(budget, torch.Tensor) and budget.is_cuda):
+        budget = budget_tensor(budget, n, dev)
+    _check(load().svc_hip_pack_levels_budget_frames(_dev(planes, torch.float32), _dev(block_types, torch.int32), n, w, h, bw, bh,
+                                                    mbw, mbh, arr, k, _dev(budget, torch.int32), _dev(workspace, torch.uint8),
+                                                    workspace.numel(), _dev(out, torch.uint8), out.numel(),
+                                                    _dev(offsets, torch.int64), _dev(choice, torch.int32), _stream()))
+    return out, offsets, choice
 
 
 def unpack_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block,

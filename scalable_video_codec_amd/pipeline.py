@@ -146,7 +146,7 @@ class ClipEncoder:
 
     def __init__(self, cfg: CodecConfig, n_frames: int, device, rank: int = 0, world: int = 1,
                  ransac: Optional[dict] = None, segment: Optional[dict] = None, segmentation: bool = True,
-                 wire: bool = False):
+                 wire: bool = False, quantise: bool = True):
         self.cfg, self.n, self.dev, self.rank, self.world = cfg, n_frames, device, rank, world
         self.pw, self.ph = cfg.padded
         self.levels = cfg.levels
@@ -173,6 +173,8 @@ class ClipEncoder:
         # wire=True: the transform emits the serialised records of libs/encoder.cpp:222-269 directly
         # (padded tile counts: the layout the reference's decoder parses) instead of planes
         self.wire = wire and bool(cfg.dct_block)
+        # quantise=False: the planes hold RAW coefficients (svc_hip_dct_frames), what the compact stream's rate control takes
+        self.quantise = quantise
         self.coeffs = (torch.empty((p, 3, self.ph, self.pw), dtype=torch.float32, device=device)
                        if cfg.dct_block and not self.wire else None)
         self.records = (torch.empty((p, native.serialized_frame_bytes(self.pw, self.ph, cfg.dct_block, cfg.dct_block)),
@@ -267,7 +269,9 @@ class ClipEncoder:
                     # (libs/encoder.cpp:638-650; the decoder picks the step per tile, libs/decoder.cpp:130-135)
                     native.dct_records_frames(self.bgr[f0:f0 + p], c.dct_block, self.types, c.mv_block,
                                               0, 0, out=self.records)
-                else:
+                elif self.quantise:
                     native.dct_quant_frames(self.bgr[f0:f0 + p], c.dct_block, self.types, c.mv_block,
                                             c.fg_step, c.bg_step, out=self.coeffs)
+                else:
+                    native.dct_frames(self.bgr[f0:f0 + p], c.dct_block, out=self.coeffs)
         self._steps_timed += 1 if timed else 0

@@ -25,8 +25,10 @@ from .pipeline import ClipEncoder, ransac_samples
 
 
 class _Slot:
-    def __init__(self, cfg: CodecConfig, batch: int, device, wire: bool, segmentation: bool, compact: bool = False):
-        self.enc = ClipEncoder(cfg, batch + 1, device, segmentation=segmentation, wire=wire)
+    def __init__(self, cfg: CodecConfig, batch: int, device, wire: bool, segmentation: bool, compact: bool = False,
+                 budget: Optional[int] = None, ladder=None):
+        # with a budget the transform leaves RAW planes and the pack picks each frame's steps
+        self.enc = ClipEncoder(cfg, batch + 1, device, segmentation=segmentation, wire=wire, quantise=budget is None)
         pw, ph = cfg.padded
         self.pin_in = torch.zeros((batch + 1, ph, pw, 3), dtype=torch.uint8).pin_memory()  # padding stays zero
         e = self.enc
@@ -40,10 +42,16 @@ class _Slot:
             cap = native.levels_max_bytes(batch, pw, ph, cfg.dct_block, cfg.mv_block)
             self.packed = torch.empty(cap, dtype=torch.uint8, device=device)
             self.offsets = torch.empty(batch + 1, dtype=torch.int64, device=device)
-            self.pack_ws = torch.empty(max(native.pack_levels_workspace_bytes(batch, pw, ph, cfg.dct_block), 16), dtype=torch.uint8,
-                                       device=device)
+            ws = (native.pack_levels_workspace_bytes(batch, pw, ph, cfg.dct_block) if budget is None else
+                  native.pack_levels_budget_workspace_bytes(batch, pw, ph, cfg.dct_block, len(ladder)))
+            self.pack_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
             self.pin_packed = torch.empty(cap, dtype=torch.uint8).pin_memory()
             self.pin_offsets = torch.empty(batch + 1, dtype=torch.int64).pin_memory()
+        self.budget = native.budget_tensor(budget, batch, device) if budget is not None else None
+        self.ladder = ladder
+        if budget is not None:
+            self.choice = torch.empty(batch, dtype=torch.int32, device=device)
+            self.pin_choice = torch.empty(batch, dtype=torch.int32).pin_memory()
         self.h2d_done = torch.cuda.Event()
         self.compute_done = torch.cuda.Event()
         self.d2h_done = torch.cuda.Event()
@@ -60,16 +68,23 @@ class HostStreamEncoder:
     PADDED tile grid, what the reference's decoder parses (libs/decoder.cpp:185-186); the first batch of a wire
     stream also carries "header", the 32 bytes of libs/codec.hpp:8-17.  compact=True replaces coeffs by "compact",
     the used bytes of the compact quantised-coefficient stream (u8; levels.iter_frames reads it), and
-    "compact_offsets" (n + 1,) i64.  A view is valid until depth - 2 more
+    "compact_offsets" (n + 1,) i64.  compact_budget (bytes per frame, with compact and compact_ladder, a sequence of (fg_step,
+    bg_step) pairs finest first, e.g. levels.step_ladder) packs each frame with the finest pair whose frame fits the budget
+    (svc_hip_pack_levels_budget_frames) and adds "compact_choice" (n,) u32: the pair's index, bit 31 set where none fits.
+    A view is valid until depth - 2 more
     batches have been yielded (its slot is re-staged one iteration before its turn to be yielded comes again)."""
 
     def __init__(self, cfg: CodecConfig, batch: int = 32, device=None, wire: bool = False,
-                 segmentation: bool = True, depth: int = 3, compact: bool = False):
+                 segmentation: bool = True, depth: int = 3, compact: bool = False, compact_budget: Optional[int] = None,
+                 compact_ladder=None):
         if compact and (wire or not cfg.dct_block):
             raise ValueError("compact output is a form of the quantised planes: not with wire records, nor without a transform")
+        if compact_budget is not None and (not compact or compact_ladder is None or len(compact_ladder) == 0):
+            raise ValueError("a byte budget needs compact output and a ladder of steps")
+        ladder = None if compact_budget is None else [(int(fg), int(bg)) for fg, bg in compact_ladder]
         self.cfg, self.batch, self.depth = cfg, batch, max(3, depth)  # 2 would leave nothing overlapped
         self.dev = device or torch.device("cuda")
-        self.slots = [_Slot(cfg, batch, self.dev, wire, segmentation, compact) for _ in range(self.depth)]
+        self.slots = [_Slot(cfg, batch, self.dev, wire, segmentation, compact, compact_budget, ladder) for _ in range(self.depth)]
         self.copy_in = torch.cuda.Stream(device=self.dev)
         self.copy_out = torch.cuda.Stream(device=self.dev)
         self.compute = torch.cuda.Stream(device=self.dev)
@@ -126,7 +141,12 @@ class HostStreamEncoder:
                     torch.cat([samples[g0:], samples[:e.pairs_per_step - (n_total - 1 - g0)]])
                 self.compute.wait_event(slot.h2d_done)
                 e.step()
-                if slot.compact:
+                if slot.budget is not None:
+                    c_ = self.cfg
+                    native.pack_levels_budget_frames(e.coeffs[:cnt], e.types[:cnt], c_.dct_block, c_.mv_block, slot.ladder,
+                                                     slot.budget[:cnt], out=slot.packed, offsets=slot.offsets[:cnt + 1],
+                                                     workspace=slot.pack_ws, choice=slot.choice[:cnt])
+                elif slot.compact:
                     c_ = self.cfg
                     native.pack_levels_frames(e.coeffs[:cnt], e.types[:cnt], c_.dct_block, c_.mv_block, c_.fg_step, c_.bg_step,
                                               out=slot.packed, offsets=slot.offsets[:cnt + 1], workspace=slot.pack_ws)
@@ -144,6 +164,8 @@ class HostStreamEncoder:
                     pw, ph = c_.padded
                     native.levels_drain(slot.packed, slot.offsets[:cnt + 1], pw, ph, c_.dct_block, c_.mv_block, slot.pin_packed)
                     slot.pin_offsets[:cnt + 1].copy_(slot.offsets[:cnt + 1], non_blocking=True)
+                if slot.budget is not None:
+                    slot.pin_choice[:cnt].copy_(slot.choice[:cnt], non_blocking=True)
                 slot.d2h_done.record(self.copy_out)
             slot.busy, slot.count, slot.first = True, cnt, first
             pending.append(slot)
@@ -163,6 +185,8 @@ class HostStreamEncoder:
         if slot.compact:
             offs = slot.pin_offsets.numpy()[:c + 1]
             out["compact"], out["compact_offsets"] = slot.pin_packed.numpy()[:int(offs[-1])], offs
+        if slot.budget is not None:
+            out["compact_choice"] = slot.pin_choice.numpy()[:c].view(np.uint32)
         if slot.enc.wire and slot.first == 1:
             c_ = self.cfg
             out["header"] = native.wire_header(self._n_total, c_.width, c_.height, c_.mv_block, c_.levels, c_.dct_block)
