@@ -42,7 +42,8 @@ struct DecodedBatch {
   uint32_t count = 0;
   uint32_t width = 0, height = 0;  // of a display frame
   const uint8_t* bgr = nullptr;    // [count][height][width][3] u8 B,G,R
-  const uint32_t* status = nullptr;  // [count]: 0, or svc_hip_unpack_levels_frames's code (the frame is then all zeros); DecodeWire: 0
+  const uint32_t* status = nullptr;  // [count]: 0, or svc_hip_unpack_levels_frames's code (the frame is then all zeros); an SVCE
+                                    // frame the entropy decoder refuses: svc_hip_entropy_decode_frames's code; DecodeWire: 0
 };
 
 // Where the time of one Decode() / DecodeWire() went: wall time of the calling thread; per-stream device times summed over the batches (the
@@ -66,7 +67,8 @@ class StreamDecoder {
   StreamDecoder(const StreamDecoder&) = delete;
   StreamDecoder& operator=(const StreamDecoder&) = delete;
 
-  // stream: n_frames SVCQ frames anywhere in host memory, frame i in [offsets[i], offsets[i + 1]) (offsets: n_frames + 1 values,
+  // stream: n_frames SVCQ frames, or SVCE frames (chosen by the first frame's magic: decoded to SVCQ on the device by
+  // svc_hip_entropy_decode_frames, then as SVCQ), anywhere in host memory, frame i in [offsets[i], offsets[i + 1]) (offsets: n_frames + 1 values,
   // the shape of EncodedBatch::compact / compact_offsets).  The geometry comes from the first frame's header, which must parse
   // (else std::runtime_error); any later frame that does not match is reported in DecodedBatch::status, not thrown.  gaze may be
   // empty (no gaze).  sink is called once per batch, in stream order, from this thread.

@@ -54,6 +54,9 @@ struct StreamEncoderConfig {
                                    // frame fits (svc_hip_pack_levels_budget_frames; the transform then leaves RAW planes).  0 = the
                                    // fixed fg_step / bg_step.  SetCompactBudget changes it for a live stream
   std::vector<svc_step_pair> compact_ladder;  // required with a budget: 1 .. 64 (fg_step, bg_step), finest first, non-decreasing
+  bool entropy = false;            // with `compact`, not with a budget: every packed frame is coded losslessly on the device ("SVCE",
+                                   // svc_hip_entropy_encode_frames) and EncodedBatch::compact carries the SVCE frames; d2h_bytes counts
+                                   // the coded bytes.  A budget counts SVCQ bytes, so entropy with compact_budget throws at construction
 };
 
 // One finished batch; the pointers are pinned host memory owned by the encoder and stay valid
@@ -71,7 +74,8 @@ struct EncodedBatch {
   uint64_t record_bytes = 0;
   const svc_wire_header* header = nullptr;  // wire == true, first batch of a clip only: the 32 bytes that
                                             // open the reference's stream (libs/codec.hpp:8-17, encoder.cpp:360-381)
-  const uint8_t* compact = nullptr;           // compact == true: `count` frames of the compact stream back to back (coeffs is null)
+  const uint8_t* compact = nullptr;           // compact == true: `count` frames of the compact stream back to back (coeffs is null);
+                                              // with entropy, its SVCE frames (svc_hip_entropy_decode_frames gives back the SVCQ ones)
   const uint64_t* compact_offsets = nullptr;  // [count + 1]: frame i in [offsets[i], offsets[i + 1])
   uint64_t compact_bytes = 0;                 // = compact_offsets[count]
   const uint32_t* compact_choice = nullptr;   // compact_budget != 0: [count] the ladder entry each frame was packed with, bit 31 set

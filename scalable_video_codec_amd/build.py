@@ -25,7 +25,7 @@ OBJ = os.path.join(PKG, "_obj")
 LIB_HIP = os.path.join(PKG, "libsvc_hip.so")
 LIB_MOTION = os.path.join(PKG, "libsvc_motion.so")
 
-HIP_SOURCES = ["capi.hip", "hbma_wave.hip", "hbma_fused.hip", "hbma_fused8.hip", "hbma_fused32.hip", "hbma_tiled.hip", "dct.hip", "ransac.hip", "luma_pyramid.hip", "segment.hip", "wire.hip", "idct.hip", "probe.hip", "comm.hip", "global_motion.hip", "imageops.hip", "levels.hip", "records.hip"]
+HIP_SOURCES = ["capi.hip", "hbma_wave.hip", "hbma_fused.hip", "hbma_fused8.hip", "hbma_fused32.hip", "hbma_tiled.hip", "dct.hip", "ransac.hip", "luma_pyramid.hip", "segment.hip", "wire.hip", "idct.hip", "probe.hip", "comm.hip", "global_motion.hip", "imageops.hip", "levels.hip", "records.hip", "entropy.hip"]
 HOST_SOURCES = [os.path.join("host", "motion_hip.cpp")]
 
 # -ffp-contract=off: the reference's float expressions (RANSAC inlier test, quant) are
@@ -142,6 +142,14 @@ def build_dropin(force: bool = False) -> List[str]:
     exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_budget_main")
     src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_budget_main.cpp")
     if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp")]):
+        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
+    out.append(exe)
+    # ... and with the entropy-coded output (StreamEncoderConfig::entropy), decoded again by svc::StreamDecoder: tests/test_gpu_entropy.py
+    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_entropy_main")
+    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_entropy_main.cpp")
+    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp"),
+                                 os.path.join(INCLUDE, "svc", "stream_decoder.hpp")]):
         _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
               f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
     out.append(exe)

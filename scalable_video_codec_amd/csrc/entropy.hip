@@ -1,0 +1,1020 @@
+// entropy.hip -- lossless coding of the compact stream: "SVCQ" frames <-> "SVCE" frames (format version 1).
+//
+// include/svc_hip.h states the format; scalable_video_codec_amd/entropy.py is its executable statement and writes the same bytes.
+// A frame's levels are cut into CHUNKS (one plane, one tile row, up to chunk_tiles adjacent tiles, in the order of SVCQ's levels);
+// each chunk is coded on its own, with Exp-Golomb codes whose parameters the encoder picks per chunk, or copied raw when that is
+// smaller.  An index of (bytes, levels) per chunk makes every chunk independently decodable.
+//
+// encode, following the count / scan / scatter of levels.hip:
+//   count    one wave per chunk: the popcount of its masks (and mask bits past the tile)
+//   scan     one workgroup per frame: the SVCQ frame's checks -> status; chunk level offsets; the types section's size
+//   lengths  one wave per chunk, one lane per tile: the code lengths for every k, the choice of k and of raw
+//   layout   one workgroup per frame: chunk byte offsets, the frame's size; then one workgroup for the frame offsets
+//   scatter  one wave per chunk: codewords ORed into LDS words, then written out bytewise (coalesced); raw chunks copied
+//   frame    one workgroup per frame: header, types section, index, padding (a failed frame: 64 zero bytes)
+// decode:
+//   check    one workgroup per frame: header and index against each other -> status; chunk byte and level offsets
+//   offsets  one workgroup: SVCQ frame offsets
+//   chunks   one lane per chunk: serial Exp-Golomb decoding (a chunk is serial by design), every read clamped to the frame
+//   frame    one workgroup per frame: SVCQ header, types, padding, or zeros for a frame that failed
+#include "svc_common.hpp"
+
+#include <algorithm>
+
+namespace svc {
+namespace {
+
+constexpr uint32_t kMagicQ = 0x51435653u;  // "SVCQ"
+constexpr uint32_t kMagicE = 0x45435653u;  // "SVCE"
+constexpr uint32_t kVersion = 1;
+constexpr uint32_t kHeaderBytes = 64;
+constexpr uint32_t kMaxTileCoeffs = 4096;
+constexpr uint32_t kChunkCoeffs = 2048;  // the encoder's chunk: about this many coefficients ...
+constexpr uint32_t kMaxChunkTiles = 64;  // ... and at most one tile per lane of a wave
+constexpr uint32_t kMaxPrefix = 24;      // a longer Exp-Golomb prefix is malformed (valid values need at most 17)
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kWaves = kThreads / 64;
+
+// statuses: the unpack's 1 .. 7, then SVCE's own
+enum : uint32_t {
+  kStOk = 0, kStRange = 1, kStMagic = 2, kStVersion = 3, kStGeometry = 4, kStSize = 5, kStLevels = 6, kStStrayBits = 7,
+  kStIndex = 8, kStChunk = 9, kStSvcqBytes = 10
+};
+
+__host__ __device__ inline uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
+__host__ __device__ inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+
+struct Geom {
+  uint32_t w, h, bw, bh, mvbw, mvbh, mvb, tx, ty, area, nw;
+  uint32_t ct, cx, chunks;  // the encoder's chunk_tiles, chunks per tile row, chunks per frame
+  uint32_t max_chunks;      // chunks per frame at chunk_tiles 1 (what the decoder's workspace holds)
+  uint32_t max_chunk_bytes; // the largest chunk the encoder writes (its raw size)
+  uint64_t masks_off, levels_off;
+};
+
+Geom make_geom(uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  Geom g{};
+  g.w = w; g.h = h; g.bw = bw; g.bh = bh; g.mvbw = mvbw; g.mvbh = mvbh;
+  g.mvb = (w / mvbw) * (h / mvbh);
+  g.tx = w / bw; g.ty = h / bh; g.area = bw * bh; g.nw = (g.area + 63) / 64;
+  g.ct = std::min(kMaxChunkTiles, std::max(1u, kChunkCoeffs / g.area));
+  g.cx = div_up(g.tx, g.ct);
+  g.chunks = 3 * g.ty * g.cx;
+  g.max_chunks = 3 * g.ty * g.tx;
+  const uint32_t nt = std::min(g.ct, g.tx);
+  g.max_chunk_bytes = 1 + 8 * g.nw * nt + 2 * nt * g.area;
+  g.masks_off = kHeaderBytes + 4ull * g.mvb;
+  g.levels_off = g.masks_off + 8ull * 3 * g.tx * g.ty * g.nw;
+  return g;
+}
+
+uint64_t svcq_max_bytes(const Geom& g) { return up16(g.levels_off + 6ull * g.w * g.h); }
+// the worst SVCE frame: SVCQ's worst case, the types section's mode word, and per chunk its index entry and mode byte
+uint64_t svce_max_bytes(const Geom& g) { return up16(g.levels_off + 6ull * g.w * g.h + 4 + 5ull * g.chunks); }
+
+// ---- workspaces ---------------------------------------------------------------------------------------------------------------
+
+struct EncWs {
+  uint32_t* cnt;    // [n][chunks] levels (bit 31: mask bits past the tile), then their exclusive prefix
+  uint32_t* info;   // [n][chunks] bytes | k_dc << 16 | k_ac << 19 | raw << 22
+  uint32_t* coff;   // [n][chunks] byte offset of the chunk's payload inside the frame
+  uint32_t* status; // [n]
+  uint32_t* types;  // [n][2] types section: bytes, width | raw << 8
+  uint32_t* fbytes; // [n] SVCE frame bytes
+  uint64_t* foff;   // [n + 1] frame offsets
+};
+uint64_t enc_ws_bytes(uint32_t n, const Geom& g) { return 3 * up16(4ull * n * g.chunks) + 4 * up16(4ull * n) + up16(8ull * (n + 1)); }
+EncWs carve_enc(uint8_t* p, uint32_t n, const Geom& g) {
+  EncWs s;
+  const uint64_t a = up16(4ull * n * g.chunks), b = up16(4ull * n);
+  s.cnt = reinterpret_cast<uint32_t*>(p);
+  s.info = reinterpret_cast<uint32_t*>(p + a);
+  s.coff = reinterpret_cast<uint32_t*>(p + 2 * a);
+  s.status = reinterpret_cast<uint32_t*>(p + 3 * a);
+  s.types = reinterpret_cast<uint32_t*>(p + 3 * a + b);
+  s.fbytes = reinterpret_cast<uint32_t*>(p + 3 * a + 3 * b);
+  s.foff = reinterpret_cast<uint64_t*>(p + 3 * a + 4 * b);
+  return s;
+}
+
+struct DecWs {
+  uint32_t* coff;   // [n][max_chunks] byte offset of the chunk's payload inside the frame
+  uint32_t* loff;   // [n][max_chunks] its first level
+  uint32_t* status; // [n]
+  uint32_t* fail;   // [n] set by a chunk that fails
+  uint32_t* chunks; // [n] chunk_tiles of the frame's header (0 for a frame that failed its checks)
+  uint32_t* qbytes; // [n] SVCQ frame bytes written (the header's, or 64 for a frame that failed its checks)
+  uint64_t* qoff;   // [n + 1]
+};
+uint64_t dec_ws_bytes(uint32_t n, const Geom& g) { return 2 * up16(4ull * n * g.max_chunks) + 4 * up16(4ull * n) + up16(8ull * (n + 1)); }
+DecWs carve_dec(uint8_t* p, uint32_t n, const Geom& g) {
+  DecWs s;
+  const uint64_t a = up16(4ull * n * g.max_chunks), b = up16(4ull * n);
+  s.coff = reinterpret_cast<uint32_t*>(p);
+  s.loff = reinterpret_cast<uint32_t*>(p + a);
+  s.status = reinterpret_cast<uint32_t*>(p + 2 * a);
+  s.fail = reinterpret_cast<uint32_t*>(p + 2 * a + b);
+  s.chunks = reinterpret_cast<uint32_t*>(p + 2 * a + 2 * b);
+  s.qbytes = reinterpret_cast<uint32_t*>(p + 2 * a + 3 * b);
+  s.qoff = reinterpret_cast<uint64_t*>(p + 2 * a + 4 * b);
+  return s;
+}
+
+// ---- device helpers -----------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+  for (uint32_t off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint32_t wave_exclusive_scan(uint32_t v) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t x = v;
+  for (uint32_t off = 1; off < 64; off <<= 1) {
+    const uint32_t y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  return x - v;
+}
+
+// exclusive scan of v over the workgroup's 256 threads; *total gets the sum
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds4, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t ex = wave_exclusive_scan(v);
+  if (lane == 63) lds4[wave] = ex + v;
+  __syncthreads();
+  uint32_t base = 0, sum = 0;
+  for (uint32_t i = 0; i < kWaves; ++i) {
+    const uint32_t s = lds4[i];
+    if (i < wave) base += s;
+    sum += s;
+  }
+  __syncthreads();
+  *total = sum;
+  return base + ex;
+}
+
+__device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t* lds4) {
+  for (uint32_t off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor(v, off, 64));
+  if ((threadIdx.x & 63u) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint32_t m = 0;
+  for (uint32_t i = 0; i < kWaves; ++i) m = max(m, lds4[i]);
+  __syncthreads();
+  return m;
+}
+
+__device__ __forceinline__ uint32_t bitlen32(uint32_t x) { return x ? 32u - __clz(x) : 0u; }
+__device__ __forceinline__ uint32_t sgn(int32_t v) { return v > 0 ? 2u * (uint32_t)v - 1u : 2u * (uint32_t)(-v); }
+__device__ __forceinline__ int32_t unsgn(uint32_t u) { return (u & 1u) ? (int32_t)((u + 1u) >> 1) : -(int32_t)(u >> 1); }
+// Exp-Golomb-k code length of u: 2 * floor(log2((u >> k) + 1)) + 1 + k
+__device__ __forceinline__ uint32_t eg_len(uint32_t u, uint32_t k) { return 2u * (bitlen32((u >> k) + 1u) - 1u) + 1u + k; }
+
+// the mask word j of a tile (u64 from two u32: the masks are only 4-byte aligned when the MV block count is odd)
+__device__ __forceinline__ uint64_t load_mask(const uint8_t* p) {
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+  return (uint64_t)q[0] | ((uint64_t)q[1] << 32);
+}
+__device__ __forceinline__ void store_mask(uint8_t* p, uint64_t m) {
+  uint32_t* q = reinterpret_cast<uint32_t*>(p);
+  q[0] = (uint32_t)m;
+  q[1] = (uint32_t)(m >> 32);
+}
+
+// the SVCQ frame f of an encode's input: offsets, header against the geometry, size and padding (what the unpack checks before
+// its masks, plus the exact size and zero padding a lossless coding needs).  Reads nothing outside [o, e).
+__device__ uint32_t check_svcq(const Geom& g, const uint8_t* __restrict__ in, uint64_t stream_bytes, const uint64_t* __restrict__ offsets,
+                               uint32_t f, const uint32_t** hdr_out) {
+  const uint64_t o = offsets[f], e = offsets[f + 1];
+  if (o % 16 != 0 || o > e || e > stream_bytes || e - o < kHeaderBytes) return kStRange;
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(in + o);
+  *hdr_out = h;
+  if (h[0] != kMagicQ) return kStMagic;
+  if (h[1] != kVersion) return kStVersion;
+  if (h[2] != g.w || h[3] != g.h || h[4] != g.bw || h[5] != g.bh || h[6] != g.mvbw || h[7] != g.mvbh || h[8] == 0 || h[9] == 0 ||
+      h[13] != 0 || h[14] != 0 || h[15] != 0)
+    return kStGeometry;
+  const uint64_t used = g.levels_off + 2ull * h[10];
+  if (h[12] != e - o || h[12] != up16(used)) return kStSize;
+  for (uint64_t i = used; i < h[12]; ++i)
+    if (in[o + i] != 0) return kStSize;
+  return kStOk;
+}
+
+// ---- encode -------------------------------------------------------------------------------------------------------------------
+
+struct EncArgs {
+  Geom g;
+  const uint8_t* in;
+  uint64_t in_bytes;
+  const uint64_t* in_off;
+  uint8_t* out;
+  uint64_t* out_off;
+  uint32_t* d_status;
+  EncWs ws;
+  uint32_t n;
+};
+
+// chunk c of a frame -> its first tile row (plane * ty + tile row), first tile and tile count
+__device__ __forceinline__ void chunk_tiles(const Geom& g, uint32_t ct, uint32_t cx, uint32_t c, uint32_t* row, uint32_t* t0, uint32_t* nt) {
+  *row = c / cx;
+  *t0 = (c - *row * cx) * ct;
+  *nt = min(ct, g.tx - *t0);
+}
+
+// count: one wave per chunk, a lane per tile
+__global__ __launch_bounds__(256) void enc_count_kernel(EncArgs a) {
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.y, c = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (c >= g.chunks) return;
+  const uint32_t* hdr = nullptr;
+  uint32_t cnt = 0, stray = 0;
+  if (check_svcq(g, a.in, a.in_bytes, a.in_off, f, &hdr) == kStOk) {
+    uint32_t row, t0, nt;
+    chunk_tiles(g, g.ct, g.cx, c, &row, &t0, &nt);
+    if (lane < nt) {
+      const uint8_t* m = a.in + a.in_off[f] + g.masks_off + 8ull * (((uint64_t)row * g.tx + t0 + lane) * g.nw);
+      for (uint32_t j = 0; j < g.nw; ++j) {
+        const uint64_t w = load_mask(m + 8 * j);
+        const uint32_t valid = min(64u, g.area - 64 * j);
+        const uint64_t keep = valid == 64 ? ~0ull : ((1ull << valid) - 1);
+        cnt += __popcll(w & keep);
+        stray |= (w & ~keep) != 0;
+      }
+    }
+  }
+  cnt = wave_sum(cnt);
+  stray = wave_sum(stray);
+  if (lane == 0) a.ws.cnt[(size_t)f * g.chunks + c] = cnt | (stray ? 0x80000000u : 0u);
+}
+
+// scan: one workgroup per frame
+__global__ __launch_bounds__(256) void enc_scan_kernel(EncArgs a) {
+  __shared__ uint32_t red[kWaves];
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.x;
+  uint32_t* cnt = a.ws.cnt + (size_t)f * g.chunks;
+  uint32_t carry = 0, stray = 0;
+  for (uint32_t base = 0; base < g.chunks; base += kThreads) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t v = i < g.chunks ? cnt[i] : 0u;
+    stray |= v >> 31;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(v & 0x7FFFFFFFu, red, &total);
+    if (i < g.chunks) cnt[i] = carry + ex;
+    carry += total;
+  }
+  uint32_t any_stray;
+  (void)block_exclusive_scan(stray, red, &any_stray);
+  const uint32_t* hdr = nullptr;
+  uint32_t st = check_svcq(g, a.in, a.in_bytes, a.in_off, f, &hdr);
+  if (st == kStOk && any_stray) st = kStStrayBits;
+  if (st == kStOk && hdr[10] != carry) st = kStLevels;
+  // the types section: a bitmap and fixed-width values, or raw when strictly smaller
+  uint32_t nnz = 0, vmax = 0;
+  if (st == kStOk) {
+    const uint32_t* types = hdr + kHeaderBytes / 4;
+    for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) {
+      const uint32_t t = types[i];
+      nnz += t != 0;
+      vmax = max(vmax, t);
+    }
+  }
+  uint32_t total_nnz;
+  (void)block_exclusive_scan(nnz, red, &total_nnz);
+  vmax = block_max(vmax, red);
+  if (threadIdx.x == 0) {
+    const uint32_t width = total_nnz ? bitlen32(vmax - 1) : 0;
+    const uint64_t coded = 4ull * (1 + cdiv(g.mvb, 32) + (uint32_t)(((uint64_t)total_nnz * width + 31) / 32));
+    const uint64_t raw = 4ull + 4ull * g.mvb;
+    a.ws.types[2 * f] = (uint32_t)(raw < coded ? raw : coded);
+    a.ws.types[2 * f + 1] = raw < coded ? 1u << 8 : width;
+    a.ws.status[f] = st;
+    a.d_status[f] = st;
+  }
+}
+
+// per tile of a chunk (lane = tile): walk its set mask bits in coefficient order; fn(pos, level) for each
+template <typename Fn>
+__device__ __forceinline__ void for_each_level(const Geom& g, const uint8_t* masks, const int16_t* lev, Fn fn) {
+  uint32_t i = 0;
+  for (uint32_t j = 0; j < g.nw; ++j) {
+    uint64_t w = load_mask(masks + 8 * j);
+    while (w) {
+      const uint32_t b = __ffsll((unsigned long long)w) - 1;
+      w &= w - 1;
+      fn(64 * j + b, (int32_t)lev[i++]);
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t tile_levels(const Geom& g, const uint8_t* masks) {
+  uint32_t n = 0;
+  for (uint32_t j = 0; j < g.nw; ++j) n += __popcll(load_mask(masks + 8 * j));
+  return n;
+}
+
+struct TileCtx {
+  const uint8_t* masks;
+  const int16_t* lev;
+  uint32_t nt, row, t0;
+};
+
+// the chunk's tile `lane`: its masks and its first level (wave-wide: every lane takes part in the scan)
+__device__ __forceinline__ TileCtx tile_ctx(const EncArgs& a, uint32_t f, uint32_t c, uint32_t lane) {
+  const Geom& g = a.g;
+  TileCtx t;
+  chunk_tiles(g, g.ct, g.cx, c, &t.row, &t.t0, &t.nt);
+  const uint8_t* frame = a.in + a.in_off[f];
+  t.masks = frame + g.masks_off + 8ull * (((uint64_t)t.row * g.tx + t.t0 + min(lane, t.nt - 1)) * g.nw);
+  const uint32_t mine = lane < t.nt ? tile_levels(g, t.masks) : 0u;
+  const uint32_t first = a.ws.cnt[(size_t)f * g.chunks + c] + wave_exclusive_scan(mine);
+  t.lev = reinterpret_cast<const int16_t*>(frame + g.levels_off) + first;
+  return t;
+}
+
+// lengths: one wave per chunk, a lane per tile -> bytes, k_dc, k_ac, raw
+__global__ __launch_bounds__(256) void enc_lengths_kernel(EncArgs a) {
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.y, c = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (c >= g.chunks || a.ws.status[f] != kStOk) return;
+  const TileCtx t = tile_ctx(a, f, c, lane);
+  uint32_t dc_bits[8] = {}, ac_bits[8] = {};
+  uint32_t fixed = 0, forced = 0, n_lev = 0;
+  int32_t dc = 0;
+  if (lane < t.nt) {
+    uint32_t prev = 0, nac = 0;
+    for_each_level(g, t.masks, t.lev, [&](uint32_t pos, int32_t v) {
+      ++n_lev;
+      forced |= v == 0;
+      if (pos == 0) { dc = v; return; }
+      ++nac;
+      fixed += eg_len(pos - prev - 1, 0);
+      prev = pos;
+      const uint32_t u = sgn(v);
+      for (uint32_t k = 0; k < 8; ++k) ac_bits[k] += eg_len(u, k);
+    });
+    fixed += eg_len(nac, 0);
+  }
+  const int32_t left = __shfl_up(dc, 1, 64);
+  if (lane < t.nt) {
+    const uint32_t u = sgn(dc - (lane == 0 ? 0 : left));
+    for (uint32_t k = 0; k < 8; ++k) dc_bits[k] = eg_len(u, k);
+  }
+  fixed = wave_sum(fixed);
+  forced = wave_sum(forced);
+  n_lev = wave_sum(n_lev);
+  uint32_t best_dc = 0, best_ac = 0, kd = 0, ka = 0;
+  for (uint32_t k = 0; k < 8; ++k) {
+    const uint32_t d = wave_sum(dc_bits[k]), s = wave_sum(ac_bits[k]);
+    if (k == 0 || d < best_dc) { best_dc = d; kd = k; }
+    if (k == 0 || s < best_ac) { best_ac = s; ka = k; }
+  }
+  if (lane == 0) {
+    const uint32_t coded = (7 + fixed + best_dc + best_ac + 7) / 8;
+    const uint32_t raw = 1 + 8 * g.nw * t.nt + 2 * n_lev;
+    const bool use_raw = forced || raw < coded;
+    a.ws.info[(size_t)f * g.chunks + c] = (use_raw ? raw : coded) | (kd << 16) | (ka << 19) | ((use_raw ? 1u : 0u) << 22);
+  }
+}
+
+// layout: one workgroup per frame -> chunk byte offsets, frame bytes
+__global__ __launch_bounds__(256) void enc_layout_kernel(EncArgs a) {
+  __shared__ uint32_t red[kWaves];
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.x;
+  if (a.ws.status[f] != kStOk) {
+    if (threadIdx.x == 0) a.ws.fbytes[f] = kHeaderBytes;
+    return;
+  }
+  const uint32_t payload = kHeaderBytes + a.ws.types[2 * f] + 4 * g.chunks;
+  uint32_t carry = payload;
+  for (uint32_t base = 0; base < g.chunks; base += kThreads) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t v = i < g.chunks ? a.ws.info[(size_t)f * g.chunks + i] & 0xFFFFu : 0u;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(v, red, &total);
+    if (i < g.chunks) a.ws.coff[(size_t)f * g.chunks + i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) a.ws.fbytes[f] = (uint32_t)up16(carry);
+}
+
+// frame offsets of a batch: one workgroup
+__global__ __launch_bounds__(256) void frame_offsets_kernel(const uint32_t* __restrict__ bytes, uint32_t n, uint64_t* __restrict__ ws_off,
+                                                            uint64_t* __restrict__ out_off) {
+  __shared__ uint64_t red[kWaves];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint64_t carry = 0;
+  for (uint32_t base = 0; base < n; base += kThreads) {
+    const uint32_t i = base + threadIdx.x;
+    const uint64_t v = i < n ? bytes[i] : 0u;
+    uint64_t x = v;
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+      const uint64_t y = __shfl_up(x, off, 64);
+      if (lane >= off) x += y;
+    }
+    if (lane == 63) red[wave] = x;
+    __syncthreads();
+    uint64_t before = 0, sum = 0;
+    for (uint32_t w = 0; w < kWaves; ++w) {
+      if (w < wave) before += red[w];
+      sum += red[w];
+    }
+    __syncthreads();
+    if (i < n) {
+      ws_off[i + 1] = carry + before + x;
+      out_off[i + 1] = carry + before + x;
+    }
+    carry += sum;
+  }
+  if (threadIdx.x == 0) {
+    ws_off[0] = 0;
+    out_off[0] = 0;
+  }
+}
+
+// LDS bit writer: the field's `bits` low bits of v at bit `pos` of the chunk's words (fields never overlap: OR)
+__device__ __forceinline__ void put_bits(uint32_t* words, uint32_t pos, uint64_t v) {
+  const uint64_t s = v << (pos & 31u);
+  const uint32_t w = pos >> 5;
+  if ((uint32_t)s) atomicOr(&words[w], (uint32_t)s);
+  if ((uint32_t)(s >> 32)) atomicOr(&words[w + 1], (uint32_t)(s >> 32));
+}
+// Exp-Golomb-k code of u at bit pos (z zeros, a 1, the low n bits of w = u + 2^k); returns its length
+__device__ __forceinline__ uint32_t put_eg(uint32_t* words, uint32_t pos, uint32_t u, uint32_t k) {
+  const uint32_t w = u + (1u << k);
+  const uint32_t n = bitlen32(w) - 1, z = n - k;
+  put_bits(words, pos + z, 1ull | ((uint64_t)(w & ((1u << n) - 1u)) << 1));
+  return z + 1 + n;
+}
+
+// scatter: one wave per chunk; coded chunks are assembled in LDS (the wave's words), then stored bytewise
+__global__ __launch_bounds__(256) void enc_scatter_kernel(EncArgs a, uint32_t lds_words) {
+  extern __shared__ uint32_t lds[];
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.y, c = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (c >= g.chunks || a.ws.status[f] != kStOk) return;
+  const uint32_t info = a.ws.info[(size_t)f * g.chunks + c];
+  const uint32_t size = info & 0xFFFFu, kd = (info >> 16) & 7u, ka = (info >> 19) & 7u;
+  uint8_t* dst = a.out + a.ws.foff[f] + a.ws.coff[(size_t)f * g.chunks + c];
+  const TileCtx t = tile_ctx(a, f, c, lane);
+  if (info >> 22) {  // raw: the mode byte, then the chunk's mask words and levels as they are (both contiguous in SVCQ)
+    const uint32_t mbytes = 8 * g.nw * t.nt;
+    const uint8_t* m = a.in + a.in_off[f] + g.masks_off + 8ull * ((uint64_t)t.row * g.tx + t.t0) * g.nw;
+    const uint8_t* l = reinterpret_cast<const uint8_t*>(__shfl(reinterpret_cast<uintptr_t>(t.lev), 0, 64));
+    for (uint32_t i = lane; i < size; i += 64) dst[i] = i == 0 ? 1 : (i <= mbytes ? m[i - 1] : l[i - 1 - mbytes]);
+    return;
+  }
+  uint32_t* words = lds + (threadIdx.x >> 6) * lds_words;
+  for (uint32_t i = lane; i < lds_words; i += 64) words[i] = 0;
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  // this tile's DC and code length, then its bit offset in the chunk
+  int32_t dc = 0;
+  uint32_t len = 0;
+  if (lane < t.nt) {
+    uint32_t prev = 0, nac = 0;
+    for_each_level(g, t.masks, t.lev, [&](uint32_t pos, int32_t v) {
+      if (pos == 0) { dc = v; return; }
+      ++nac;
+      len += eg_len(pos - prev - 1, 0) + eg_len(sgn(v), ka);
+      prev = pos;
+    });
+    len += eg_len(nac, 0);
+  }
+  const int32_t left = __shfl_up(dc, 1, 64);
+  const uint32_t udc = sgn(dc - (lane == 0 ? 0 : left));
+  if (lane < t.nt) len += eg_len(udc, kd);
+  uint32_t pos = 7 + wave_exclusive_scan(lane < t.nt ? len : 0u);
+  if (lane == 0) put_bits(words, 0, (kd << 1) | (ka << 4));
+  if (lane < t.nt) {
+    pos += put_eg(words, pos, udc, kd);
+    uint32_t nac = 0;
+    for (uint32_t j = 0; j < g.nw; ++j) nac += __popcll(load_mask(t.masks + 8 * j));
+    nac -= (uint32_t)(load_mask(t.masks) & 1u);
+    pos += put_eg(words, pos, nac, 0);
+    uint32_t prev = 0;
+    for_each_level(g, t.masks, t.lev, [&](uint32_t p, int32_t v) {
+      if (p == 0) return;
+      pos += put_eg(words, pos, p - prev - 1, 0);
+      pos += put_eg(words, pos, sgn(v), ka);
+      prev = p;
+    });
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(words);
+  for (uint32_t i = lane; i < size; i += 64) dst[i] = bytes[i];
+}
+
+// frame: one workgroup per frame -> header, types section, index, padding, or 64 zero bytes for a frame that failed
+__global__ __launch_bounds__(256) void enc_frame_kernel(EncArgs a) {
+  __shared__ uint32_t red[kWaves];
+  __shared__ uint32_t win[kThreads + 2];
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.x;
+  uint8_t* frame = a.out + a.ws.foff[f];
+  uint32_t* fw = reinterpret_cast<uint32_t*>(frame);
+  const uint32_t st = a.ws.status[f];
+  if (st != kStOk) {
+    if (threadIdx.x < 16) fw[threadIdx.x] = 0;
+    return;
+  }
+  const uint32_t* in = reinterpret_cast<const uint32_t*>(a.in + a.in_off[f]);
+  const uint32_t tbytes = a.ws.types[2 * f], width = a.ws.types[2 * f + 1] & 0xFFu, raw = a.ws.types[2 * f + 1] >> 8;
+  const uint32_t fbytes = a.ws.fbytes[f];
+  if (threadIdx.x < 16) {
+    uint32_t v = in[threadIdx.x];
+    if (threadIdx.x == 0) v = kMagicE;
+    if (threadIdx.x == 12) v = fbytes;
+    if (threadIdx.x == 13) v = in[12];
+    if (threadIdx.x == 14) v = g.ct;
+    if (threadIdx.x == 15) v = tbytes;
+    fw[threadIdx.x] = v;
+  }
+  const uint32_t* types = in + kHeaderBytes / 4;
+  uint32_t* sec = fw + kHeaderBytes / 4;
+  if (raw) {
+    if (threadIdx.x == 0) sec[0] = 1;
+    for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) sec[1 + i] = types[i];
+  } else {
+    if (threadIdx.x == 0) sec[0] = width << 8;
+    const uint32_t bm = cdiv(g.mvb, 32);
+    uint32_t* vals = sec + 1 + bm;
+    // 256 types at a time: the bitmap word of every 32, and the values (type - 1) in `width` bits at rank * width, ORed into an
+    // LDS window of words; complete words go out, the partial last one carries into the next window
+    uint32_t rank0 = 0, carry = 0;
+    for (uint32_t base = 0; base < g.mvb; base += kThreads) {
+      const uint32_t i = base + threadIdx.x;
+      const uint32_t t = i < g.mvb ? types[i] : 0u;
+      const uint64_t b = __ballot(t != 0);
+      if ((threadIdx.x & 31u) == 0 && i < g.mvb) sec[1 + (i >> 5)] = (uint32_t)(b >> (threadIdx.x & 32u));
+      uint32_t total;
+      const uint32_t ex = block_exclusive_scan(t != 0 ? 1u : 0u, red, &total);
+      if (width) {
+        const uint64_t w0 = ((uint64_t)rank0 * width) >> 5;
+        for (uint32_t j = threadIdx.x; j < kThreads + 2; j += kThreads) win[j] = j == 0 ? carry : 0u;
+        __syncthreads();
+        if (t != 0) {
+          const uint32_t bit = (uint32_t)((uint64_t)(rank0 + ex) * width - 32 * w0);
+          const uint64_t v = (uint64_t)(t - 1u) << (bit & 31u);
+          if ((uint32_t)v) atomicOr(&win[bit >> 5], (uint32_t)v);
+          if ((uint32_t)(v >> 32)) atomicOr(&win[(bit >> 5) + 1], (uint32_t)(v >> 32));
+        }
+        __syncthreads();
+        const uint32_t full = (uint32_t)((((uint64_t)(rank0 + total) * width) >> 5) - w0);
+        for (uint32_t j = threadIdx.x; j < full; j += kThreads) vals[w0 + j] = win[j];
+        carry = win[full];
+        __syncthreads();
+      }
+      rank0 += total;
+    }
+    const uint64_t end_bit = (uint64_t)rank0 * width;
+    if (threadIdx.x == 0 && (end_bit & 31u)) vals[end_bit >> 5] = carry;
+  }
+  // the index: bytes | levels << 16 per chunk
+  const uint32_t level_count = in[10];
+  uint32_t* index = fw + (kHeaderBytes + tbytes) / 4;
+  for (uint32_t i = threadIdx.x; i < g.chunks; i += kThreads) {
+    const uint32_t lo = a.ws.cnt[(size_t)f * g.chunks + i];
+    const uint32_t hi = i + 1 < g.chunks ? a.ws.cnt[(size_t)f * g.chunks + i + 1] : level_count;
+    index[i] = (a.ws.info[(size_t)f * g.chunks + i] & 0xFFFFu) | ((hi - lo) << 16);
+  }
+  // padding: after the last chunk's payload
+  const uint32_t last = g.chunks - 1;
+  const uint32_t used = a.ws.coff[(size_t)f * g.chunks + last] + (a.ws.info[(size_t)f * g.chunks + last] & 0xFFFFu);
+  for (uint32_t i = used + threadIdx.x; i < fbytes; i += kThreads) frame[i] = 0;
+}
+
+// ---- decode -------------------------------------------------------------------------------------------------------------------
+
+struct DecArgs {
+  Geom g;
+  const uint8_t* in;
+  uint64_t in_bytes;
+  const uint64_t* in_off;
+  uint8_t* out;
+  uint64_t* out_off;
+  uint32_t* d_status;
+  DecWs ws;
+  uint32_t n;
+};
+
+// frame check and index scan: one workgroup per frame
+__global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
+  __shared__ uint32_t red[kWaves];
+  __shared__ uint32_t s_st;
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.x;
+  const uint64_t o = a.in_off[f], e = a.in_off[f + 1];
+  uint32_t st = kStOk, ct = 0, cx = 0, chunks = 0;
+  const uint32_t* h = nullptr;
+  uint64_t payload = 0;
+  if (o % 16 != 0 || o > e || e > a.in_bytes || e - o < kHeaderBytes) st = kStRange;
+  if (st == kStOk) {
+    h = reinterpret_cast<const uint32_t*>(a.in + o);
+    if (h[0] != kMagicE) st = kStMagic;
+    else if (h[1] != kVersion) st = kStVersion;
+    else if (h[2] != g.w || h[3] != g.h || h[4] != g.bw || h[5] != g.bh || h[6] != g.mvbw || h[7] != g.mvbh || h[8] == 0 || h[9] == 0 ||
+             h[14] == 0)
+      st = kStGeometry;
+    else if (h[12] % 16 != 0 || h[12] != e - o) st = kStSize;
+    else if (h[10] > 3ull * g.w * g.h || h[13] != up16(g.levels_off + 2ull * h[10])) st = kStSvcqBytes;
+    else {
+      ct = h[14];
+      cx = ct >= g.tx ? 1u : (g.tx + ct - 1) / ct;  // ct may exceed tx (up to 2^32 - 1): then a chunk per tile row
+      chunks = 3 * g.ty * cx;
+      payload = kHeaderBytes + (uint64_t)h[15] + 4ull * chunks;
+      if (h[15] % 4 != 0 || payload > h[12]) st = kStIndex;
+    }
+  }
+  // the index: chunk byte and level offsets
+  uint32_t bytes_total = 0, lev_total = 0;
+  if (st == kStOk) {
+    const uint32_t* index = h + (kHeaderBytes + h[15]) / 4;
+    uint32_t bcarry = 0, lcarry = 0;
+    for (uint32_t base = 0; base < chunks; base += kThreads) {
+      const uint32_t i = base + threadIdx.x;
+      const uint32_t v = i < chunks ? index[i] : 0u;
+      uint32_t tb, tl;
+      const uint32_t eb = block_exclusive_scan(v & 0xFFFFu, red, &tb);
+      const uint32_t el = block_exclusive_scan(v >> 16, red, &tl);
+      if (i < chunks) {
+        a.ws.coff[(size_t)f * g.max_chunks + i] = (uint32_t)payload + bcarry + eb;
+        a.ws.loff[(size_t)f * g.max_chunks + i] = lcarry + el;
+      }
+      bcarry += tb;
+      lcarry += tl;
+    }
+    bytes_total = bcarry;
+    lev_total = lcarry;
+    if (up16(payload + bytes_total) != h[12] || lev_total != h[10]) st = kStIndex;
+  }
+  // the types section: its mode word and its size against the bitmap's popcount
+  if (st == kStOk) {
+    const uint32_t* sec = h + kHeaderBytes / 4;
+    const uint32_t tbytes = h[15];
+    const uint32_t head = tbytes >= 4 ? sec[0] : 0xFFFFFFFFu;
+    const uint32_t mode = head & 0xFFu, width = head >> 8;
+    const uint32_t bm = cdiv(g.mvb, 32);
+    uint32_t bad = 0, nnz = 0;
+    if (tbytes < 4) bad = 1;
+    else if (mode == 1 && width == 0) bad = (uint64_t)tbytes != 4ull + 4ull * g.mvb;
+    else if (mode != 0 || width > 32 || (uint64_t)tbytes < 4ull * (1 + bm)) bad = 1;
+    else {
+      for (uint32_t j = threadIdx.x; j < bm; j += kThreads) {
+        uint32_t w = sec[1 + j];
+        if (j == bm - 1 && g.mvb % 32) {
+          if (w >> (g.mvb % 32)) bad = 1;  // bitmap bits past the MV blocks
+          w &= (1u << (g.mvb % 32)) - 1u;
+        }
+        nnz += __popc(w);
+      }
+    }
+    uint32_t any_bad, total_nnz;
+    (void)block_exclusive_scan(bad, red, &any_bad);
+    (void)block_exclusive_scan(nnz, red, &total_nnz);
+    if (!any_bad && mode == 0 && (uint64_t)tbytes != 4ull * (1 + bm + ((uint64_t)total_nnz * width + 31) / 32)) any_bad = 1;
+    if (!any_bad && mode == 0 && width == 32) {  // a stored id - 1 of 2^32 - 1 would decode to the id 2^32, which u32 cannot hold
+      uint32_t over = 0;
+      for (uint32_t i = threadIdx.x; i < total_nnz; i += kThreads) over |= sec[1 + bm + i] == 0xFFFFFFFFu;
+      uint32_t any_over;
+      (void)block_exclusive_scan(over, red, &any_over);
+      any_bad = any_over;
+    }
+    if (any_bad) st = kStIndex;
+  }
+  if (threadIdx.x == 0) s_st = st;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.ws.status[f] = s_st;
+    a.ws.fail[f] = 0;
+    a.ws.chunks[f] = s_st == kStOk ? ct : 0u;
+    a.ws.qbytes[f] = s_st == kStOk ? h[13] : kHeaderBytes;
+  }
+}
+
+// a bit reader over one frame: aligned u32 loads, nothing read at or past the frame's end (zeros there).  The bits from the read
+// position sit in a 64-bit buffer (33 .. 64 of them after a refill) and the next word is loaded one refill ahead, so a codeword
+// usually costs no load of its own; a codeword longer than the buffer holds is read from memory directly.
+struct BitReader {
+  const uint32_t* w;
+  uint32_t nwords;
+  uint64_t buf;   // bits [pos, pos + nb) of the frame, the rest zero
+  uint32_t nb;
+  uint64_t wi;    // the word that follows them
+  uint32_t ahead; // word(wi), loaded in advance
+  __device__ __forceinline__ uint32_t word(uint64_t i) const { return i < nwords ? w[i] : 0u; }
+  __device__ __forceinline__ uint64_t peek(uint64_t pos) const {
+    const uint64_t i = pos >> 5;
+    const uint32_t s = (uint32_t)(pos & 31u);
+    const uint64_t lo = (uint64_t)word(i) | ((uint64_t)word(i + 1) << 32);
+    return s ? (lo >> s) | ((uint64_t)word(i + 2) << (64 - s)) : lo;
+  }
+  __device__ __forceinline__ void seek(uint64_t pos) {
+    wi = pos >> 5;
+    const uint32_t s = (uint32_t)(pos & 31u);
+    buf = (uint64_t)(word(wi) >> s);
+    nb = 32 - s;
+    ++wi;
+    ahead = word(wi);
+  }
+  __device__ __forceinline__ void refill() {
+    while (nb <= 32) {
+      buf |= (uint64_t)ahead << nb;
+      nb += 32;
+      ++wi;
+      ahead = word(wi);
+    }
+  }
+};
+
+// one Exp-Golomb-k codeword at *pos (bounded by end): false when malformed
+__device__ __forceinline__ bool get_eg(BitReader& r, uint64_t* pos, uint64_t end, uint32_t k, uint32_t* u) {
+  r.refill();
+  uint64_t v = r.buf;
+  uint32_t z = v ? (uint32_t)__builtin_ctzll(v) : 64u;
+  const bool slow = z >= r.nb || 2 * z + k + 1 > r.nb;  // the codeword runs past the buffered bits
+  if (slow) {
+    v = r.peek(*pos);
+    z = v ? (uint32_t)__builtin_ctzll(v) : 64u;
+  }
+  if (z > kMaxPrefix) return false;
+  const uint32_t n = z + k, len = z + 1 + n;
+  if (*pos + len > end) return false;
+  const uint64_t w = (1ull << n) | ((v >> (z + 1)) & ((1ull << n) - 1));
+  *u = (uint32_t)(w - (1ull << k));
+  *pos += len;
+  if (slow) {
+    r.seek(*pos);
+  } else {
+    r.buf >>= len;
+    r.nb -= len;
+  }
+  return true;
+}
+
+// chunks: one lane per chunk; decodes the masks and levels of its tiles into the SVCQ frame
+__global__ __launch_bounds__(256) void dec_chunks_kernel(DecArgs a) {
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.y, c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= g.max_chunks || a.ws.status[f] != kStOk) return;
+  const uint32_t ct = a.ws.chunks[f], cx = ct >= g.tx ? 1u : (g.tx + ct - 1) / ct;
+  if (c >= 3 * g.ty * cx) return;
+  const uint8_t* frame = a.in + a.in_off[f];
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t fbytes = hdr[12];
+  const uint32_t* index = hdr + (kHeaderBytes + hdr[15]) / 4;
+  const uint32_t entry = index[c], size = entry & 0xFFFFu, count = entry >> 16;
+  const uint32_t start = a.ws.coff[(size_t)f * g.max_chunks + c], lev0 = a.ws.loff[(size_t)f * g.max_chunks + c];
+  uint32_t row, t0, nt;
+  chunk_tiles(g, ct, cx, c, &row, &t0, &nt);
+  uint8_t* q = a.out + a.ws.qoff[f];
+  uint8_t* masks = q + g.masks_off + 8ull * ((uint64_t)row * g.tx + t0) * g.nw;
+  int16_t* lev = reinterpret_cast<int16_t*>(q + g.levels_off) + lev0;
+  bool ok = size != 0;
+  if (ok && (frame[start] & 1u)) {  // raw: mask words and levels verbatim
+    const uint32_t mbytes = 8 * g.nw * nt;
+    ok = (uint64_t)size == 1ull + mbytes + 2ull * count;
+    uint32_t got = 0;
+    for (uint32_t i = 0; ok && i < nt * g.nw; ++i) {
+      const uint8_t* s = frame + start + 1 + 8 * i;
+      uint64_t m = 0;
+      for (uint32_t b = 0; b < 8; ++b) m |= (uint64_t)s[b] << (8 * b);
+      const uint32_t j = i % g.nw;
+      const uint32_t valid = min(64u, g.area - 64 * j);
+      if (valid < 64 && (m >> valid)) ok = false;
+      got += __popcll(m);
+      store_mask(masks + 8 * i, m);
+    }
+    ok = ok && got == count;
+    const uint8_t* s = frame + start + 1 + mbytes;
+    for (uint32_t i = 0; ok && i < count; ++i) lev[i] = (int16_t)((uint32_t)s[2 * i] | ((uint32_t)s[2 * i + 1] << 8));
+  } else if (ok) {
+    BitReader r{reinterpret_cast<const uint32_t*>(frame), fbytes / 4, 0, 0, 0, 0};
+    const uint64_t end = 8ull * (start + size);
+    uint64_t pos = 8ull * start;
+    const uint32_t head = (uint32_t)r.peek(pos);
+    const uint32_t kd = (head >> 1) & 7u, ka = (head >> 4) & 7u;
+    pos += 7;
+    r.seek(pos);
+    uint32_t written = 0;
+    int32_t dcp = 0;
+    for (uint32_t t = 0; ok && t < nt; ++t) {
+      uint8_t* tm = masks + 8ull * t * g.nw;
+      uint32_t u;
+      ok = get_eg(r, &pos, end, kd, &u);
+      if (!ok) break;
+      const int32_t dc = dcp + unsgn(u);
+      dcp = dc;
+      ok = dc >= -32768 && dc <= 32767;
+      uint64_t cur = 0;  // the mask word being filled, word cj of the tile
+      uint32_t cj = 0;
+      if (ok && dc != 0) {
+        ok = written < count;
+        if (ok) lev[written++] = (int16_t)dc;
+        cur = 1;
+      }
+      uint32_t nac = 0;
+      ok = ok && get_eg(r, &pos, end, 0, &nac) && nac <= g.area - 1;
+      uint32_t p = 0;
+      for (uint32_t i = 0; ok && i < nac; ++i) {
+        uint32_t run, lu;
+        ok = get_eg(r, &pos, end, 0, &run) && (uint64_t)p + run + 1 <= g.area - 1;
+        if (!ok) break;
+        p += run + 1;
+        ok = get_eg(r, &pos, end, ka, &lu);
+        if (!ok) break;
+        const int32_t v = unsgn(lu);
+        ok = v >= -32768 && v <= 32767 && written < count;
+        if (!ok) break;
+        lev[written++] = (int16_t)v;
+        for (; cj < (p >> 6); ++cj) {
+          store_mask(tm + 8 * cj, cur);
+          cur = 0;
+        }
+        cur |= 1ull << (p & 63u);
+      }
+      if (!ok) break;
+      for (; cj < g.nw; ++cj) {
+        store_mask(tm + 8 * cj, cur);
+        cur = 0;
+      }
+    }
+    ok = ok && written == count && (pos + 7) / 8 == start + size;
+  }
+  if (!ok) atomicOr(&a.ws.fail[f], 1u);
+}
+
+// frame: SVCQ header, types, padding; a frame that failed is zeros (64 B after a failed check, its svcq_frame_bytes after a chunk)
+__global__ __launch_bounds__(256) void dec_frame_kernel(DecArgs a) {
+  __shared__ uint32_t red[kWaves];
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.x;
+  uint8_t* q = a.out + a.ws.qoff[f];
+  uint32_t* qw = reinterpret_cast<uint32_t*>(q);
+  const uint32_t qbytes = a.ws.qbytes[f];
+  uint32_t st = a.ws.status[f];
+  if (st == kStOk && a.ws.fail[f]) st = kStChunk;
+  if (threadIdx.x == 0) a.d_status[f] = st;
+  if (st != kStOk) {
+    for (uint32_t i = threadIdx.x; i < qbytes / 4; i += kThreads) qw[i] = 0;
+    return;
+  }
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(a.in + a.in_off[f]);
+  if (threadIdx.x < 16) {
+    uint32_t v = threadIdx.x < 12 ? h[threadIdx.x] : 0u;
+    if (threadIdx.x == 0) v = kMagicQ;
+    if (threadIdx.x == 12) v = h[13];
+    qw[threadIdx.x] = v;
+  }
+  const uint32_t* sec = h + kHeaderBytes / 4;
+  uint32_t* types = qw + kHeaderBytes / 4;
+  const uint32_t head = sec[0], width = head >> 8;
+  if (head == 1) {
+    for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) types[i] = sec[1 + i];
+  } else {
+    const uint32_t bm = cdiv(g.mvb, 32);
+    const uint32_t* bitmap = sec + 1;
+    const uint32_t* vals = sec + 1 + bm;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < g.mvb; base += kThreads) {
+      const uint32_t i = base + threadIdx.x;
+      const uint32_t nz = i < g.mvb ? (bitmap[i >> 5] >> (i & 31u)) & 1u : 0u;
+      uint32_t total;
+      const uint32_t rank = carry + block_exclusive_scan(nz, red, &total);
+      carry += total;
+      if (i >= g.mvb) continue;
+      uint32_t t = 0;
+      if (nz) {
+        uint64_t v = 0;
+        if (width) {
+          const uint64_t bit = (uint64_t)rank * width;
+          const uint64_t wi = bit >> 5;
+          const uint64_t two = (uint64_t)vals[wi] | (wi + 1 < (uint64_t)(h[15] / 4 - 1 - bm) ? (uint64_t)vals[wi + 1] << 32 : 0ull);
+          v = (two >> (bit & 31u)) & ((1ull << width) - 1ull);
+        }
+        t = (uint32_t)(v + 1);
+      }
+      types[i] = t;
+    }
+  }
+  const uint64_t used = g.levels_off + 2ull * h[10];
+  for (uint64_t i = used + threadIdx.x; i < qbytes; i += kThreads) q[i] = 0;
+}
+
+inline bool aligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) == 0; }
+
+int validate_geom(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  SVC_REQUIRE(w > 0 && h > 0 && bw > 0 && bh > 0, "%s: frame and tile sides must be positive", what);
+  SVC_REQUIRE(w % bw == 0 && h % bh == 0, "%s: frame %ux%u not divisible by tile %ux%u", what, w, h, bw, bh);
+  SVC_REQUIRE(mvbw > 0 && mvbh > 0 && mvbw % bw == 0 && mvbh % bh == 0 && w % mvbw == 0 && h % mvbh == 0,
+              "%s: MV block %ux%u must be a multiple of the tile %ux%u and divide the frame", what, mvbw, mvbh, bw, bh);
+  if ((uint64_t)bw * bh > kMaxTileCoeffs) return fail(SVC_ERR_UNSUPPORTED, "%s: tiles above %u coefficients", what, kMaxTileCoeffs);
+  if (n > 65535) return fail(SVC_ERR_UNSUPPORTED, "%s: more than 65535 frames in one call", what);
+  const Geom g = make_geom(w, h, bw, bh, mvbw, mvbh);
+  if (svce_max_bytes(g) > 0xFFFFFFFFull)
+    return fail(SVC_ERR_UNSUPPORTED, "%s: a frame of %ux%u could exceed the u32 frame_bytes field", what, w, h);
+  return SVC_OK;
+}
+
+uint64_t ws_bytes(uint32_t n, const Geom& g) { return n ? std::max(enc_ws_bytes(n, g), dec_ws_bytes(n, g)) : 0; }
+
+}  // namespace
+}  // namespace svc
+
+using namespace svc;
+
+extern "C" {
+
+uint64_t svc_hip_entropy_max_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                   uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("entropy_max_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
+  return n_frames * svce_max_bytes(make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
+}
+
+uint64_t svc_hip_entropy_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                         uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("entropy_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
+  return ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
+}
+
+// Checked in the order of the SVCQ entry points, for any n_frames: geometry, limits, sizes, then pointers.
+int svc_hip_entropy_encode_frames(const uint8_t* d_svcq, uint64_t svcq_bytes, const uint64_t* d_svcq_offsets, uint32_t n_frames,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                  uint32_t mv_block_h, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
+                                  uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("entropy_encode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g), "entropy_encode: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g));
+  const uint64_t need = n_frames * svce_max_bytes(g);
+  SVC_REQUIRE(out_capacity >= need, "entropy_encode: output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)out_capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_svcq && d_svcq_offsets && d_workspace && d_out && d_out_offsets && d_status, "entropy_encode: null pointer");
+  SVC_REQUIRE(aligned(d_svcq, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_svcq_offsets, 8) &&
+                  aligned(d_out_offsets, 8) && aligned(d_status, 4),
+              "entropy_encode: frames, output and workspace must be 16-byte aligned, offsets 8-byte, status 4-byte");
+  EncArgs a;
+  a.g = g;
+  a.in = d_svcq; a.in_bytes = svcq_bytes; a.in_off = d_svcq_offsets;
+  a.out = d_out; a.out_off = d_out_offsets; a.d_status = d_status;
+  a.ws = carve_enc(d_workspace, n_frames, g);
+  a.n = n_frames;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 chunk_grid(div_up(g.chunks, kWaves), n_frames);
+  hipLaunchKernelGGL(enc_count_kernel, chunk_grid, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("entropy_encode count"))) return rc;
+  hipLaunchKernelGGL(enc_scan_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("entropy_encode scan"))) return rc;
+  hipLaunchKernelGGL(enc_lengths_kernel, chunk_grid, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("entropy_encode lengths"))) return rc;
+  hipLaunchKernelGGL(enc_layout_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("entropy_encode layout"))) return rc;
+  hipLaunchKernelGGL(frame_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.fbytes, n_frames, a.ws.foff, d_out_offsets);
+  if ((rc = check_launch("entropy_encode offsets"))) return rc;
+  const uint32_t lds_words = div_up(g.max_chunk_bytes, 4) + 2;
+  hipLaunchKernelGGL(enc_scatter_kernel, chunk_grid, dim3(kThreads), kWaves * lds_words * 4, s, a, lds_words);
+  if ((rc = check_launch("entropy_encode scatter"))) return rc;
+  hipLaunchKernelGGL(enc_frame_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
+  return check_launch("entropy_encode frame");
+}
+
+int svc_hip_entropy_decode_frames(const uint8_t* d_svce, uint64_t svce_bytes, const uint64_t* d_offsets, uint32_t n_frames,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                  uint32_t mv_block_h, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_svcq_out,
+                                  uint64_t capacity, uint64_t* d_svcq_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("entropy_decode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g), "entropy_decode: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g));
+  const uint64_t need = n_frames * svcq_max_bytes(g);
+  SVC_REQUIRE(capacity >= need, "entropy_decode: output of %llu B is below the batch's SVCQ worst case of %llu B",
+              (unsigned long long)capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_svce && d_offsets && d_workspace && d_svcq_out && d_svcq_offsets && d_status, "entropy_decode: null pointer");
+  SVC_REQUIRE(aligned(d_svce, 16) && aligned(d_svcq_out, 16) && aligned(d_workspace, 16) && aligned(d_offsets, 8) &&
+                  aligned(d_svcq_offsets, 8) && aligned(d_status, 4),
+              "entropy_decode: frames, output and workspace must be 16-byte aligned, offsets 8-byte, status 4-byte");
+  DecArgs a;
+  a.g = g;
+  a.in = d_svce; a.in_bytes = svce_bytes; a.in_off = d_offsets;
+  a.out = d_svcq_out; a.out_off = d_svcq_offsets; a.d_status = d_status;
+  a.ws = carve_dec(d_workspace, n_frames, g);
+  a.n = n_frames;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(dec_check_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("entropy_decode check"))) return rc;
+  hipLaunchKernelGGL(frame_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.qbytes, n_frames, a.ws.qoff, d_svcq_offsets);
+  if ((rc = check_launch("entropy_decode offsets"))) return rc;
+  hipLaunchKernelGGL(dec_chunks_kernel, dim3(div_up(g.max_chunks, kThreads), n_frames), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("entropy_decode chunks"))) return rc;
+  hipLaunchKernelGGL(dec_frame_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
+  return check_launch("entropy_decode frame");
+}
+
+}  // extern "C"

@@ -52,7 +52,8 @@ struct Slot {
   PinBuf<uint32_t> pin_gaze, pin_status;
   DevBuf<uint8_t> in, disp;
   DevBuf<uint64_t> off;
-  DevBuf<uint32_t> gaze, status;
+  DevBuf<uint32_t> gaze, status, estatus;  // estatus: svc_hip_entropy_decode_frames's codes (SVCE)
+  PinBuf<uint32_t> pin_estatus;
   hipEvent_t h2d_done = nullptr, compute_done = nullptr, d2h_done = nullptr;
   hipEvent_t t_in[2] = {}, t_k[2] = {}, t_out[2] = {};
   uint64_t h2d_bytes = 0, d2h_bytes = 0;
@@ -64,7 +65,7 @@ struct Slot {
   }
 };
 
-constexpr uint32_t kMagic = 0x51435653u, kVersion = 1;  // include/svc_hip.h, the SVCQ header
+constexpr uint32_t kMagic = 0x51435653u, kMagicE = 0x45435653u, kVersion = 1;  // include/svc_hip.h, the SVCQ and SVCE headers
 
 }  // namespace
 
@@ -74,6 +75,10 @@ struct StreamDecoder::Impl {
   uint32_t pw = 0, ph = 0, bw = 0, bh = 0, mbw = 0, mbh = 0, dw = 0, dh = 0;
   uint64_t disp_bytes = 0, ws_bytes = 0;
   bool wire = false;        // the buffers are sized for DecodeWire
+  bool svce = false;        // Decode: the stream is SVCE, decoded to SVCQ in q first
+  DevBuf<uint8_t> q, ews;   // SVCE: the batch's SVCQ frames and the coder's workspace (the kernels' stream only)
+  DevBuf<uint64_t> qoff;
+  uint64_t q_bytes = 0, ews_bytes = 0;
   uint64_t frame_bytes = 0; // DecodeWire: bytes of one frame's records
   DevBuf<float> rec;        // the kernels' stream only: one for all slots
   DevBuf<uint8_t> ws;
@@ -87,15 +92,23 @@ struct StreamDecoder::Impl {
       if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
   }
 
-  void Size(const uint32_t* hdr) {
+  void Size(const uint32_t* hdr, bool entropy) {
     const uint32_t w = hdr[2], h = hdr[3];
     const uint32_t want_dw = c.display_w ? c.display_w : w, want_dh = c.display_h ? c.display_h : h;
-    if (!wire && w == pw && h == ph && hdr[4] == bw && hdr[5] == bh && hdr[6] == mbw && hdr[7] == mbh && want_dw == dw && want_dh == dh)
+    if (!wire && entropy == svce && w == pw && h == ph && hdr[4] == bw && hdr[5] == bh && hdr[6] == mbw && hdr[7] == mbh && want_dw == dw &&
+        want_dh == dh)
       return;
     for (hipStream_t s : {s_in, s_compute, s_out}) Hip(hipStreamSynchronize(s), "hipStreamSynchronize");
     const uint64_t need_ws = svc_hip_decode_levels_workspace_bytes(c.batch, w, h, hdr[4], hdr[5]);
     if (!need_ws) Abi(SVC_ERR_UNSUPPORTED, "no decoder for the first frame's geometry");
     if (want_dw > w || want_dh > h) throw std::runtime_error("svc::StreamDecoder: the display size exceeds the padded frame");
+    if (entropy) {
+      q_bytes = svc_hip_levels_max_bytes(c.batch, w, h, hdr[4], hdr[5], hdr[6], hdr[7]);
+      ews_bytes = svc_hip_entropy_workspace_bytes(c.batch, w, h, hdr[4], hdr[5], hdr[6], hdr[7]);
+      if (!q_bytes || !ews_bytes) Abi(SVC_ERR_UNSUPPORTED, "no entropy decoder for the first frame's geometry");
+      q.Alloc(q_bytes); ews.Alloc(ews_bytes); qoff.Alloc(c.batch + 1);
+    }
+    svce = entropy;
     wire = false;
     pw = w; ph = h; bw = hdr[4]; bh = hdr[5]; mbw = hdr[6]; mbh = hdr[7]; dw = want_dw; dh = want_dh;
     disp_bytes = (uint64_t)dw * dh * 3;
@@ -141,6 +154,7 @@ StreamDecoder::StreamDecoder(const StreamDecoderConfig& config) : p_(new Impl) {
     s->pin_off.Alloc(B + 1); s->off.Alloc(B + 1);
     s->pin_gaze.Alloc(4 * B); s->gaze.Alloc(4 * B);
     s->pin_status.Alloc(B); s->status.Alloc(B);
+    s->pin_estatus.Alloc(B); s->estatus.Alloc(B);
     Hip(hipEventCreateWithFlags(&s->h2d_done, hipEventDisableTiming), "hipEventCreate");
     Hip(hipEventCreateWithFlags(&s->compute_done, hipEventDisableTiming), "hipEventCreate");
     Hip(hipEventCreateWithFlags(&s->d2h_done, hipEventDisableTiming), "hipEventCreate");
@@ -162,8 +176,9 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
     throw std::runtime_error("svc::StreamDecoder: the first frame's header is out of range");
   uint32_t hdr[16];
   std::memcpy(hdr, stream + offsets[0], sizeof(hdr));
-  if (hdr[0] != kMagic || hdr[1] != kVersion) throw std::runtime_error("svc::StreamDecoder: the stream does not open with an SVCQ v1 header");
-  m.Size(hdr);
+  if ((hdr[0] != kMagic && hdr[0] != kMagicE) || hdr[1] != kVersion)
+    throw std::runtime_error("svc::StreamDecoder: the stream does not open with an SVCQ v1 or SVCE v1 header");
+  m.Size(hdr, hdr[0] == kMagicE);
   const uint32_t B = c.batch;
 
   using Clock = std::chrono::steady_clock;
@@ -178,6 +193,9 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
     Hip(hipEventElapsedTime(&ms, s.t_out[0], s.t_out[1]), "hipEventElapsedTime"); st.d2h_ms += ms;
     st.h2d_bytes += s.h2d_bytes; st.d2h_bytes += s.d2h_bytes;
     ++st.batches; st.frames += s.count;
+    if (m.svce)  // a frame the entropy decoder refused is zeros to the SVCQ decoder (status 2): report the entropy decoder's code
+      for (uint32_t i = 0; i < s.count; ++i)
+        if (s.pin_estatus.p[i]) s.pin_status.p[i] = s.pin_estatus.p[i];
     DecodedBatch b;
     b.first_frame = s.first; b.count = s.count; b.width = m.dw; b.height = m.dh;
     b.bgr = s.pin_disp.p; b.status = s.pin_status.p;
@@ -224,7 +242,16 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
 
     Hip(hipStreamWaitEvent(m.s_compute, s.h2d_done, 0), "hipStreamWaitEvent");
     Hip(hipEventRecord(s.t_k[0], m.s_compute), "hipEventRecord");
-    Abi(svc_hip_decode_levels_frames(s.in.p, bytes, s.off.p, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step, c.bg_step, s.gaze.p,
+    const uint8_t* qin = s.in.p;
+    const uint64_t* qoff = s.off.p;
+    uint64_t qbytes = bytes;
+    if (m.svce) {  // SVCE -> SVCQ in device scratch, then the SVCQ decoder unchanged
+      Abi(svc_hip_entropy_decode_frames(s.in.p, bytes, s.off.p, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, m.ews.p, m.ews_bytes, m.q.p,
+                                        m.q_bytes, m.qoff.p, s.estatus.p, m.s_compute),
+          "svc_hip_entropy_decode_frames");
+      qin = m.q.p; qoff = m.qoff.p; qbytes = m.q_bytes;
+    }
+    Abi(svc_hip_decode_levels_frames(qin, qbytes, qoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step, c.bg_step, s.gaze.p,
                                      m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh, s.status.p, m.s_compute),
         "svc_hip_decode_levels_frames");
     Hip(hipEventRecord(s.t_k[1], m.s_compute), "hipEventRecord");
@@ -234,9 +261,11 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
     Hip(hipEventRecord(s.t_out[0], m.s_out), "hipEventRecord");
     Hip(hipMemcpyAsync(s.pin_disp.p, s.disp.p, cnt * m.disp_bytes, hipMemcpyDeviceToHost, m.s_out), "hipMemcpyAsync D2H display");
     Hip(hipMemcpyAsync(s.pin_status.p, s.status.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "hipMemcpyAsync D2H status");
+    if (m.svce)
+      Hip(hipMemcpyAsync(s.pin_estatus.p, s.estatus.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "hipMemcpyAsync D2H status");
     Hip(hipEventRecord(s.t_out[1], m.s_out), "hipEventRecord");
     Hip(hipEventRecord(s.d2h_done, m.s_out), "hipEventRecord");
-    s.d2h_bytes = cnt * (m.disp_bytes + sizeof(uint32_t));
+    s.d2h_bytes = cnt * (m.disp_bytes + (m.svce ? 2 : 1) * sizeof(uint32_t));
 
     s.busy = true; s.first = first; s.count = cnt;
     pending.push_back(&s);

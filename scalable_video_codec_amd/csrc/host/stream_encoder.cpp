@@ -55,8 +55,10 @@ template <typename T> struct PinBuf {
 };
 
 struct Slot {
-  DevBuf<uint8_t> bgr, pyr, mask, seg_ws, records, packed, pack_ws;
-  DevBuf<uint64_t> offsets;
+  DevBuf<uint8_t> bgr, pyr, mask, seg_ws, records, packed, pack_ws, coded, entropy_ws;
+  DevBuf<uint64_t> offsets, coded_offsets;
+  DevBuf<uint32_t> entropy_status;
+  PinBuf<uint32_t> pin_entropy_status;
   PinBuf<uint8_t> pin_packed;
   PinBuf<uint64_t> pin_offsets;
   DevBuf<float> mv, mad, gm, rmse, coeffs;
@@ -85,6 +87,7 @@ struct StreamEncoder::Impl {
   uint32_t bw = 0, bh = 0, tw = 0, th = 0;  // MV block and transform block sides
   uint64_t pyr_stride = 0, frame_bytes = 0, plane_elems = 0, record_bytes = 0, seg_ws_bytes = 0;
   uint64_t packed_bytes = 0, pack_ws_bytes = 0;  // compact: worst case of a batch, pack workspace
+  uint64_t coded_bytes = 0, entropy_ws_bytes = 0; // entropy: worst case of a coded batch, coder workspace
   bool budgeted = false;                          // compact_budget != 0: rate control
   std::atomic<uint32_t> budget{0};                // bytes per frame of the next batch staged (SetCompactBudget)
   std::vector<std::unique_ptr<Slot>> slots;
@@ -131,6 +134,14 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     Abi(svc_hip_pack_levels_budget_frames(nullptr, nullptr, 0, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.compact_ladder.data(),
                                           (uint32_t)c.compact_ladder.size(), nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr, nullptr,
                                           nullptr), "compact_ladder");
+  if (c.entropy && !c.compact) throw std::runtime_error("svc::StreamEncoder: entropy coding is a form of the compact stream");
+  if (c.entropy && c.compact_budget)
+    throw std::runtime_error("svc::StreamEncoder: a byte budget counts uncoded compact bytes: not with entropy");
+  if (c.entropy) {
+    m.coded_bytes = svc_hip_entropy_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
+    m.entropy_ws_bytes = svc_hip_entropy_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
+    if (!m.coded_bytes || !m.entropy_ws_bytes) throw std::runtime_error("svc::StreamEncoder: no entropy-coded stream for this geometry");
+  }
   if (c.compact) {
     m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
     m.pack_ws_bytes = m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
@@ -161,7 +172,11 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     if (!c.wire && !c.compact) s->pin_coeffs.Alloc(B * 3 * m.plane_elems);
     if (c.compact) {
       s->packed.Alloc(m.packed_bytes); s->pack_ws.Alloc(m.pack_ws_bytes); s->offsets.Alloc(B + 1);
-      s->pin_packed.Alloc(m.packed_bytes); s->pin_offsets.Alloc(B + 1);
+      s->pin_packed.Alloc(c.entropy ? m.coded_bytes : m.packed_bytes); s->pin_offsets.Alloc(B + 1);
+      if (c.entropy) {
+        s->coded.Alloc(m.coded_bytes); s->entropy_ws.Alloc(m.entropy_ws_bytes); s->coded_offsets.Alloc(B + 1);
+        s->entropy_status.Alloc(B); s->pin_entropy_status.Alloc(B);
+      }
     }
     if (m.budgeted) { s->budget.Alloc(B); s->choice.Alloc(B); s->pin_budget.Alloc(B); s->pin_choice.Alloc(B); }
     Hip(hipEventCreateWithFlags(&s->h2d_done, hipEventDisableTiming), "hipEventCreate");
@@ -221,6 +236,11 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     Hip(hipEventElapsedTime(&ms, s.t_out[0], s.t_out[1]), "hipEventElapsedTime"); st.d2h_ms += ms;
     st.h2d_bytes += s.h2d_bytes; st.d2h_bytes += s.d2h_bytes;
     if (c.compact) st.d2h_bytes += s.pin_offsets.p[s.encoded];  // the drain moved exactly the used bytes
+    if (c.entropy)  // the input is the pack's own output: a flagged frame is a bug, not a stream to pass on
+      for (uint32_t i = 0; i < s.encoded; ++i)
+        if (s.pin_entropy_status.p[i])
+          throw std::runtime_error("svc::StreamEncoder: svc_hip_entropy_encode_frames flagged frame " + std::to_string(s.first + i) +
+                                   " with status " + std::to_string(s.pin_entropy_status.p[i]));
     if (m.budgeted)
       for (uint32_t i = 0; i < s.encoded; ++i) st.over_budget_frames += s.pin_choice.p[i] >> 31;
     ++st.batches; st.encoded_frames += s.encoded;
@@ -337,6 +357,11 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         Abi(svc_hip_pack_levels_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step,
                                        s.pack_ws.p, m.pack_ws_bytes, s.packed.p, m.packed_bytes, s.offsets.p, m.s_compute),
             "svc_hip_pack_levels_frames");
+      if (c.entropy)
+        Abi(svc_hip_entropy_encode_frames(s.packed.p, m.packed_bytes, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
+                                          s.entropy_ws.p, m.entropy_ws_bytes, s.coded.p, m.coded_bytes, s.coded_offsets.p,
+                                          s.entropy_status.p, m.s_compute),
+            "svc_hip_entropy_encode_frames");
     }
     Hip(hipEventRecord(s.t_k[1], m.s_compute), "hipEventRecord");
     Hip(hipEventRecord(s.compute_done, m.s_compute), "hipEventRecord");
@@ -345,13 +370,20 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     Hip(hipEventRecord(s.t_out[0], m.s_out), "hipEventRecord");
     s.d2h_bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : c.compact ? 0 : 3 * m.plane_elems * sizeof(float)));
     if (c.compact) s.d2h_bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t);  // + the stream's used bytes, known at delivery
-    if (m.budgeted) s.d2h_bytes += (uint64_t)encoded * sizeof(uint32_t);
+    if (m.budgeted || c.entropy) s.d2h_bytes += (uint64_t)encoded * sizeof(uint32_t);  // the choices, or the coder's statuses
     Hip(hipMemcpyAsync(s.pin_mv.p, s.mv.p, (size_t)encoded * m.blocks * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H mv");
     Hip(hipMemcpyAsync(s.pin_types.p, s.types.p, (size_t)encoded * m.blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "D2H types");
     Hip(hipMemcpyAsync(s.pin_gm.p, s.gm.p, (size_t)encoded * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H gm");
     if (c.wire)
       Hip(hipMemcpyAsync(s.pin_records.p, s.records.p, (size_t)encoded * m.record_bytes, hipMemcpyDeviceToHost, m.s_out), "D2H records");
-    else if (c.compact) {  // the used bytes only: the count is on the device, the drain kernel reads it there
+    else if (c.entropy) {  // the coded frames, drained the same way, their offsets and the coder's statuses
+      Abi(svc_hip_entropy_drain(s.coded.p, s.coded_offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_packed.p, m.coded_bytes,
+                                m.s_out), "svc_hip_entropy_drain");
+      Hip(hipMemcpyAsync(s.pin_offsets.p, s.coded_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, m.s_out),
+          "D2H offsets");
+      Hip(hipMemcpyAsync(s.pin_entropy_status.p, s.entropy_status.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out),
+          "D2H entropy status");
+    } else if (c.compact) {  // the used bytes only: the count is on the device, the drain kernel reads it there
       Abi(svc_hip_levels_drain(s.packed.p, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_packed.p, m.packed_bytes,
                                m.s_out), "svc_hip_levels_drain");
       Hip(hipMemcpyAsync(s.pin_offsets.p, s.offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, m.s_out),

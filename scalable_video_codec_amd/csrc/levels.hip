@@ -648,6 +648,44 @@ __global__ __launch_bounds__(256) void drain_kernel(const uint4* __restrict__ sr
 
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// the drain after its geometry checks: capacity against `need`, then pointers, the destination's memory, and the launch
+int drain_to_host(const char* what, const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, void* host_dst,
+                  uint64_t capacity, uint64_t need, void* stream) {
+  SVC_REQUIRE(capacity >= need, "%s: destination of %llu B is below the batch's worst case of %llu B", what,
+              (unsigned long long)capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && host_dst, "%s: null pointer", what);
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(host_dst, 16) && aligned(d_frame_offsets, 8),
+              "%s: frames and destination must be 16-byte aligned, offsets 8-byte", what);
+  // A kernel that stores to pageable memory faults the GPU: the destination must be pinned / registered host memory, and the
+  // WHOLE of [host_dst, host_dst + capacity) must lie inside that one allocation (not run on into a neighbour or a gap).
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, host_dst) != hipSuccess || attr.type != hipMemoryTypeHost) {
+    (void)hipGetLastError();
+    return fail(SVC_ERR_INVALID_ARG, "%s: the destination is not pinned or registered host memory", what);
+  }
+  hipDeviceptr_t start = nullptr;
+  size_t size = 0;
+  if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, host_dst) != hipSuccess ||
+      hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, host_dst) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SVC_ERR_INVALID_ARG, "%s: the destination's allocation cannot be resolved", what);
+  }
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(start), dst = reinterpret_cast<uintptr_t>(host_dst);
+  if (dst < lo || dst - lo > size || capacity > size - (dst - lo))
+    return fail(SVC_ERR_INVALID_ARG, "%s: %llu B from the destination run past its pinned allocation (%llu B from %p)", what,
+                (unsigned long long)capacity, (unsigned long long)size, reinterpret_cast<void*>(lo));
+  void* d_dst = nullptr;
+  if (hipHostGetDevicePointer(&d_dst, host_dst, 0) != hipSuccess || !d_dst) {
+    (void)hipGetLastError();
+    return fail(SVC_ERR_INVALID_ARG, "%s: the destination has no device mapping", what);
+  }
+  SVC_REQUIRE(aligned(d_dst, 16), "%s: the destination's device mapping is not 16-byte aligned", what);
+  hipLaunchKernelGGL(drain_kernel, dim3(64), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const uint4*>(d_frames), d_frame_offsets, n_frames, static_cast<uint4*>(d_dst), capacity);
+  return check_launch(what);
+}
+
 int validate_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
   SVC_REQUIRE(w > 0 && h > 0 && bw > 0 && bh > 0, "%s: frame and tile sides must be positive", what);
   SVC_REQUIRE(w % bw == 0 && h % bh == 0, "%s: frame %ux%u not divisible by tile %ux%u", what, w, h, bw, bh);
@@ -853,39 +891,19 @@ int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offset
   if (!rc) rc = validate_limits("levels_drain", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
   const uint64_t need = svc_hip_levels_max_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  SVC_REQUIRE(capacity >= need, "levels_drain: destination of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)capacity, (unsigned long long)need);
-  if (n_frames == 0) return SVC_OK;
-  SVC_REQUIRE(d_frames && d_frame_offsets && host_dst, "levels_drain: null pointer");
-  SVC_REQUIRE(aligned(d_frames, 16) && aligned(host_dst, 16) && aligned(d_frame_offsets, 8),
-              "levels_drain: frames and destination must be 16-byte aligned, offsets 8-byte");
-  // A kernel that stores to pageable memory faults the GPU: the destination must be pinned / registered host memory, and the
-  // WHOLE of [host_dst, host_dst + capacity) must lie inside that one allocation (not run on into a neighbour or a gap).
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, host_dst) != hipSuccess || attr.type != hipMemoryTypeHost) {
-    (void)hipGetLastError();
-    return fail(SVC_ERR_INVALID_ARG, "levels_drain: the destination is not pinned or registered host memory");
-  }
-  hipDeviceptr_t start = nullptr;
-  size_t size = 0;
-  if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, host_dst) != hipSuccess ||
-      hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, host_dst) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SVC_ERR_INVALID_ARG, "levels_drain: the destination's allocation cannot be resolved");
-  }
-  const uintptr_t lo = reinterpret_cast<uintptr_t>(start), dst = reinterpret_cast<uintptr_t>(host_dst);
-  if (dst < lo || dst - lo > size || capacity > size - (dst - lo))
-    return fail(SVC_ERR_INVALID_ARG, "levels_drain: %llu B from the destination run past its pinned allocation (%llu B from %p)",
-                (unsigned long long)capacity, (unsigned long long)size, reinterpret_cast<void*>(lo));
-  void* d_dst = nullptr;
-  if (hipHostGetDevicePointer(&d_dst, host_dst, 0) != hipSuccess || !d_dst) {
-    (void)hipGetLastError();
-    return fail(SVC_ERR_INVALID_ARG, "levels_drain: the destination has no device mapping");
-  }
-  SVC_REQUIRE(aligned(d_dst, 16), "levels_drain: the destination's device mapping is not 16-byte aligned");
-  hipLaunchKernelGGL(drain_kernel, dim3(64), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
-                     reinterpret_cast<const uint4*>(d_frames), d_frame_offsets, n_frames, static_cast<uint4*>(d_dst), capacity);
-  return check_launch("levels_drain");
+  return drain_to_host("levels_drain", d_frames, d_frame_offsets, n_frames, host_dst, capacity, need, stream);
+}
+
+// The same drain for SVCE frames (csrc/entropy.hip), with their worst case as the capacity rule.
+int svc_hip_entropy_drain(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t frame_w,
+                          uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                          void* host_dst, uint64_t capacity, void* stream) {
+  int rc = validate_geom("entropy_drain", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (!rc) rc = validate_limits("entropy_drain", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  const uint64_t need = svc_hip_entropy_max_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (need == 0 && n_frames != 0) return SVC_ERR_UNSUPPORTED;  // svc_hip_last_error() says why
+  return drain_to_host("entropy_drain", d_frames, d_frame_offsets, n_frames, host_dst, capacity, need, stream);
 }
 
 uint64_t svc_hip_decode_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,

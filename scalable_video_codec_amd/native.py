@@ -123,6 +123,12 @@ SIGNATURES = {
     "svc_hip_pack_levels_frames": (C.c_int, [_vp, _vp] + [_u32] * 9 + [_vp, _u64, _vp, _u64, _vp, _vp]),
     "svc_hip_unpack_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _vp, _vp, _vp]),
     "svc_hip_levels_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
+    # its lossless entropy coding, "SVCE" (csrc/entropy.hip; the drain in csrc/levels.hip)
+    "svc_hip_entropy_max_bytes": (_u64, [_u32] * 7),
+    "svc_hip_entropy_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_entropy_encode_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "svc_hip_entropy_decode_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "svc_hip_entropy_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
     # its rate control: per-frame steps from a byte budget (csrc/levels.hip)
     "svc_hip_pack_levels_budget_workspace_bytes": (_u64, [_u32] * 6),
     "svc_hip_pack_levels_budget_frames": (C.c_int, [_vp, _vp] + [_u32] * 7 + [C.POINTER(StepPair), _u32, _vp, _vp, _u64, _vp, _u64, _vp,
@@ -799,6 +805,72 @@ def levels_drain(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, bl
     assert not dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous()
     _check(load().svc_hip_levels_drain(_dev(frames, torch.uint8), _dev(offsets, torch.int64), n, w, h, bw, bh, mbw, mbh,
                                        dst.data_ptr(), dst.numel(), _stream()))
+
+
+# ---- its lossless entropy coding ("SVCE" v1, include/svc_hip.h; host coder: entropy.py) ----
+
+def entropy_max_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    """Worst-case bytes of n SVCE frames (what the encoder's output and an SVCE drain destination must hold)."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_entropy_max_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def entropy_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_entropy_workspace_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def entropy_encode_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block,
+                          out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """SVCQ frames (u8 on the device) + their offsets -> (SVCE stream u8 of the worst-case size, offsets (frames + 1,) i64,
+    status (frames,) i32: 0, or the unpack's code for a malformed input frame, written as 64 zero bytes)."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    if out is None:
+        out = torch.empty(max(entropy_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(entropy_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    _check(load().svc_hip_entropy_encode_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, w, h, bw, bh,
+                                                mbw, mbh, _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8),
+                                                out.numel(), _dev(out_offsets, torch.int64), _dev(status, torch.int32), _stream()))
+    return out, out_offsets, status
+
+
+def entropy_decode_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block,
+                          out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """SVCE frames (u8 on the device) + their offsets -> (SVCQ stream u8 of SVCQ's worst-case size, offsets (frames + 1,) i64,
+    status (frames,) i32 with the codes of include/svc_hip.h; a frame that fails is zeros)."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(entropy_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    _check(load().svc_hip_entropy_decode_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, w, h, bw, bh,
+                                                mbw, mbh, _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8),
+                                                out.numel(), _dev(out_offsets, torch.int64), _dev(status, torch.int32), _stream()))
+    return out, out_offsets, status
+
+
+def entropy_drain(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, dst: torch.Tensor) -> None:
+    """levels_drain for SVCE frames: dst is a PINNED host u8 tensor of at least entropy_max_bytes."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    assert not dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous()
+    _check(load().svc_hip_entropy_drain(_dev(frames, torch.uint8), _dev(offsets, torch.int64), n, w, h, bw, bh, mbw, mbh,
+                                        dst.data_ptr(), dst.numel(), _stream()))
 
 
 def decode_levels_workspace_bytes(n: int, w: int, h: int, block) -> int:

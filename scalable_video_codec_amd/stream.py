@@ -26,7 +26,7 @@ from .pipeline import ClipEncoder, ransac_samples
 
 class _Slot:
     def __init__(self, cfg: CodecConfig, batch: int, device, wire: bool, segmentation: bool, compact: bool = False,
-                 budget: Optional[int] = None, ladder=None):
+                 budget: Optional[int] = None, ladder=None, entropy: bool = False):
         # with a budget the transform leaves RAW planes and the pack picks each frame's steps
         self.enc = ClipEncoder(cfg, batch + 1, device, segmentation=segmentation, wire=wire, quantise=budget is None)
         pw, ph = cfg.padded
@@ -45,8 +45,17 @@ class _Slot:
             ws = (native.pack_levels_workspace_bytes(batch, pw, ph, cfg.dct_block) if budget is None else
                   native.pack_levels_budget_workspace_bytes(batch, pw, ph, cfg.dct_block, len(ladder)))
             self.pack_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
-            self.pin_packed = torch.empty(cap, dtype=torch.uint8).pin_memory()
             self.pin_offsets = torch.empty(batch + 1, dtype=torch.int64).pin_memory()
+            if entropy:  # the packed frames are then coded losslessly on the device ("SVCE", entropy.py) and only those drain
+                cap = native.entropy_max_bytes(batch, pw, ph, cfg.dct_block, cfg.mv_block)
+                self.coded = torch.empty(cap, dtype=torch.uint8, device=device)
+                self.coded_offsets = torch.empty(batch + 1, dtype=torch.int64, device=device)
+                ews = native.entropy_workspace_bytes(batch, pw, ph, cfg.dct_block, cfg.mv_block)
+                self.entropy_ws = torch.empty(max(ews, 16), dtype=torch.uint8, device=device)
+                self.entropy_status = torch.empty(batch, dtype=torch.int32, device=device)
+                self.pin_entropy_status = torch.empty(batch, dtype=torch.int32).pin_memory()
+            self.pin_packed = torch.empty(cap, dtype=torch.uint8).pin_memory()
+        self.entropy = entropy
         self.budget = native.budget_tensor(budget, batch, device) if budget is not None else None
         self.ladder = ladder
         if budget is not None:
@@ -71,20 +80,26 @@ class HostStreamEncoder:
     "compact_offsets" (n + 1,) i64.  compact_budget (bytes per frame, with compact and compact_ladder, a sequence of (fg_step,
     bg_step) pairs finest first, e.g. levels.step_ladder) packs each frame with the finest pair whose frame fits the budget
     (svc_hip_pack_levels_budget_frames) and adds "compact_choice" (n,) u32: the pair's index, bit 31 set where none fits.
+    entropy=True (with compact, without a budget) codes every packed frame losslessly on the device, and "compact" /
+    "compact_offsets" carry the "SVCE" frames (entropy.iter_frames decodes them to the SVCQ frames compact=True yields).
     A view is valid until depth - 2 more
     batches have been yielded (its slot is re-staged one iteration before its turn to be yielded comes again)."""
 
     def __init__(self, cfg: CodecConfig, batch: int = 32, device=None, wire: bool = False,
                  segmentation: bool = True, depth: int = 3, compact: bool = False, compact_budget: Optional[int] = None,
-                 compact_ladder=None):
+                 compact_ladder=None, entropy: bool = False):
         if compact and (wire or not cfg.dct_block):
             raise ValueError("compact output is a form of the quantised planes: not with wire records, nor without a transform")
         if compact_budget is not None and (not compact or compact_ladder is None or len(compact_ladder) == 0):
             raise ValueError("a byte budget needs compact output and a ladder of steps")
+        if entropy and (not compact or compact_budget is not None):
+            raise ValueError("entropy coding codes the compact stream (compact=True), and a budget counts uncoded bytes: "
+                             "not with compact_budget")
         ladder = None if compact_budget is None else [(int(fg), int(bg)) for fg, bg in compact_ladder]
         self.cfg, self.batch, self.depth = cfg, batch, max(3, depth)  # 2 would leave nothing overlapped
         self.dev = device or torch.device("cuda")
-        self.slots = [_Slot(cfg, batch, self.dev, wire, segmentation, compact, compact_budget, ladder) for _ in range(self.depth)]
+        self.slots = [_Slot(cfg, batch, self.dev, wire, segmentation, compact, compact_budget, ladder, entropy)
+                      for _ in range(self.depth)]
         self.copy_in = torch.cuda.Stream(device=self.dev)
         self.copy_out = torch.cuda.Stream(device=self.dev)
         self.compute = torch.cuda.Stream(device=self.dev)
@@ -150,6 +165,11 @@ class HostStreamEncoder:
                     c_ = self.cfg
                     native.pack_levels_frames(e.coeffs[:cnt], e.types[:cnt], c_.dct_block, c_.mv_block, c_.fg_step, c_.bg_step,
                                               out=slot.packed, offsets=slot.offsets[:cnt + 1], workspace=slot.pack_ws)
+                    if slot.entropy:
+                        pw, ph = c_.padded
+                        native.entropy_encode_frames(slot.packed, slot.offsets[:cnt + 1], pw, ph, c_.dct_block, c_.mv_block,
+                                                     out=slot.coded, out_offsets=slot.coded_offsets[:cnt + 1],
+                                                     workspace=slot.entropy_ws, status=slot.entropy_status[:cnt])
                 slot.compute_done.record(self.compute)
             with torch.cuda.stream(self.copy_out):
                 self.copy_out.wait_event(slot.compute_done)
@@ -162,8 +182,14 @@ class HostStreamEncoder:
                 if slot.compact:
                     c_ = self.cfg
                     pw, ph = c_.padded
-                    native.levels_drain(slot.packed, slot.offsets[:cnt + 1], pw, ph, c_.dct_block, c_.mv_block, slot.pin_packed)
-                    slot.pin_offsets[:cnt + 1].copy_(slot.offsets[:cnt + 1], non_blocking=True)
+                    if slot.entropy:
+                        native.entropy_drain(slot.coded, slot.coded_offsets[:cnt + 1], pw, ph, c_.dct_block, c_.mv_block,
+                                             slot.pin_packed)
+                        slot.pin_offsets[:cnt + 1].copy_(slot.coded_offsets[:cnt + 1], non_blocking=True)
+                        slot.pin_entropy_status[:cnt].copy_(slot.entropy_status[:cnt], non_blocking=True)
+                    else:
+                        native.levels_drain(slot.packed, slot.offsets[:cnt + 1], pw, ph, c_.dct_block, c_.mv_block, slot.pin_packed)
+                        slot.pin_offsets[:cnt + 1].copy_(slot.offsets[:cnt + 1], non_blocking=True)
                 if slot.budget is not None:
                     slot.pin_choice[:cnt].copy_(slot.choice[:cnt], non_blocking=True)
                 slot.d2h_done.record(self.copy_out)
@@ -182,6 +208,11 @@ class HostStreamEncoder:
                "gm": slot.pin_gm.numpy()[:c]}
         if slot.pin_big is not None:
             out["records" if slot.enc.wire else "coeffs"] = slot.pin_big.numpy()[:c]
+        if slot.entropy:  # the coder's input is the pack's own output: a flagged frame is a bug, not a frame to pass on
+            bad = np.flatnonzero(slot.pin_entropy_status.numpy()[:c])
+            if bad.size:
+                raise RuntimeError(f"svc_hip_entropy_encode_frames flagged frame {slot.first + int(bad[0])} with status "
+                                   f"{int(slot.pin_entropy_status.numpy()[bad[0]])}")
         if slot.compact:
             offs = slot.pin_offsets.numpy()[:c + 1]
             out["compact"], out["compact_offsets"] = slot.pin_packed.numpy()[:int(offs[-1])], offs
