@@ -59,7 +59,7 @@ def _run(cmd: List[str]) -> None:
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "svc_common.hpp"), os.path.join(CSRC, "union_find.hpp"), os.path.join(CSRC, "hbma_search.hpp"), os.path.join(CSRC, "hbma_fused_kernel.hpp"), os.path.join(CSRC, "dct_tables.inc"), os.path.join(CSRC, "idct_core.hpp"), os.path.join(CSRC, "display_core.hpp"), os.path.join(CSRC, "luma16.hpp"),
+    headers = [os.path.join(CSRC, "svc_common.hpp"), os.path.join(CSRC, "union_find.hpp"), os.path.join(CSRC, "hbma_search.hpp"), os.path.join(CSRC, "hbma_fused_kernel.hpp"), os.path.join(CSRC, "dct_tables.inc"), os.path.join(CSRC, "idct_core.hpp"), os.path.join(CSRC, "display_core.hpp"), os.path.join(CSRC, "stream_format.hpp"), os.path.join(CSRC, "luma16.hpp"),
                os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h")]
     jobs, objs = [], []
     for s in HIP_SOURCES:
@@ -86,7 +86,7 @@ def build_motion(force: bool = False) -> str:
     """The C++ layer above the C ABI: the reference's motion.hpp entry points (plain C++, g++) and the
     batched host-memory encoder (uses the HIP runtime for buffers, streams and events: hipcc, host only)."""
     srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
-    deps = srcs + [STREAM_SRC, DECODER_SRC, CLIP_SRC, os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h"), os.path.join(INCLUDE, "svc_clip.h")] + \
+    deps = srcs + [STREAM_SRC, DECODER_SRC, CLIP_SRC, os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(CSRC, "stream_format.hpp"), os.path.join(INCLUDE, "svc_hip.h"), os.path.join(INCLUDE, "svc_clip.h")] + \
         [os.path.join(INCLUDE, "svc", h) for h in ("motion.hpp", "math.hpp", "types.hpp", "stream_encoder.hpp",
                                                     "stream_decoder.hpp", "clip_encoder.hpp")]
     if force or not _newer(LIB_MOTION, deps + [LIB_HIP]):

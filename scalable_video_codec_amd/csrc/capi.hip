@@ -29,8 +29,6 @@ int launch_hbma_fused(const uint8_t*, const uint8_t*, uint64_t, uint32_t, uint32
 int launch_hbma_wave(const uint8_t*, const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t,
                      uint32_t, uint32_t, uint32_t, float*, float*, hipStream_t);
 
-static inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // The reference's asserts (libs/motion.cpp:417-433) as a status, plus what a
 // pyramid needs to be well formed (every level an exact halving).
 static int validate_hbma(uint32_t levels, uint32_t w, uint32_t h, uint32_t range, uint32_t bw, uint32_t bh) {

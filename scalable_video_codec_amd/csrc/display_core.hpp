@@ -45,5 +45,19 @@ __global__ __launch_bounds__(256) void display_kernel(const float* __restrict__ 
   }
 }
 
+// a decoder's display size: 0 x 0 = no display pass, else within the padded frame (the pass only shrinks)
+inline int validate_display(const char* what, uint32_t dw, uint32_t dh, uint32_t w, uint32_t h) {
+  SVC_REQUIRE((dw == 0 && dh == 0) || (dw >= 1 && dw <= w && dh >= 1 && dh <= h),
+              "%s: display %ux%u must lie within 1x1 .. %ux%u (the padded frame)", what, dw, dh, w, h);
+  return SVC_OK;
+}
+
+inline int launch_display(const char* what, const float* d_rec, uint8_t* d_display, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t dw,
+                          uint32_t dh, hipStream_t s) {
+  hipLaunchKernelGGL(display_kernel, dim3(div_up(dw, kDisplayThreads), dh, n_frames), dim3(kDisplayThreads), 0, s, d_rec, d_display, w, h,
+                     dw, dh);
+  return check_launch(what, "display");
+}
+
 }  // namespace
 }  // namespace svc

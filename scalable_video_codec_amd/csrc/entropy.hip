@@ -1,6 +1,7 @@
 // entropy.hip -- lossless coding of the compact stream: "SVCQ" frames <-> "SVCE" frames (format version 1).
 //
-// include/svc_hip.h states the format; scalable_video_codec_amd/entropy.py is its executable statement and writes the same bytes.
+// include/svc_hip.h states the format and stream_format.hpp its header words, its statuses and the SVCQ side (layout, frame check);
+// scalable_video_codec_amd/entropy.py is its executable statement and writes the same bytes.
 // A frame's levels are cut into CHUNKS (one plane, one tile row, up to chunk_tiles adjacent tiles, in the order of SVCQ's levels);
 // each chunk is coded on its own, with Exp-Golomb codes whose parameters the encoder picks per chunk, or copied raw when that is
 // smaller.  An index of (bytes, levels) per chunk makes every chunk independently decodable.
@@ -18,31 +19,17 @@
 //   chunks   one lane per chunk: serial Exp-Golomb decoding (a chunk is serial by design), every read clamped to the frame
 //   frame    one workgroup per frame: SVCQ header, types, padding, or zeros for a frame that failed
 #include "svc_common.hpp"
+#include "stream_format.hpp"
 
 #include <algorithm>
 
 namespace svc {
 namespace {
 
-constexpr uint32_t kMagicQ = 0x51435653u;  // "SVCQ"
-constexpr uint32_t kMagicE = 0x45435653u;  // "SVCE"
-constexpr uint32_t kVersion = 1;
-constexpr uint32_t kHeaderBytes = 64;
-constexpr uint32_t kMaxTileCoeffs = 4096;
 constexpr uint32_t kChunkCoeffs = 2048;  // the encoder's chunk: about this many coefficients ...
 constexpr uint32_t kMaxChunkTiles = 64;  // ... and at most one tile per lane of a wave
 constexpr uint32_t kMaxPrefix = 24;      // a longer Exp-Golomb prefix is malformed (valid values need at most 17)
-constexpr uint32_t kThreads = 256;
 constexpr uint32_t kWaves = kThreads / 64;
-
-// statuses: the unpack's 1 .. 7, then SVCE's own
-enum : uint32_t {
-  kStOk = 0, kStRange = 1, kStMagic = 2, kStVersion = 3, kStGeometry = 4, kStSize = 5, kStLevels = 6, kStStrayBits = 7,
-  kStIndex = 8, kStChunk = 9, kStSvcqBytes = 10
-};
-
-__host__ __device__ inline uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
-__host__ __device__ inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 struct Geom {
   uint32_t w, h, bw, bh, mvbw, mvbh, mvb, tx, ty, area, nw;
@@ -52,23 +39,23 @@ struct Geom {
   uint64_t masks_off, levels_off;
 };
 
+// the SVCQ frame's layout and this file's chunk split
 Geom make_geom(uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const FrameLayout l = frame_layout(w, h, bw, bh, mvbw, mvbh);
   Geom g{};
   g.w = w; g.h = h; g.bw = bw; g.bh = bh; g.mvbw = mvbw; g.mvbh = mvbh;
-  g.mvb = (w / mvbw) * (h / mvbh);
-  g.tx = w / bw; g.ty = h / bh; g.area = bw * bh; g.nw = (g.area + 63) / 64;
+  g.mvb = l.mvb;
+  g.tx = l.tiles_x; g.ty = l.tiles_y; g.area = bw * bh; g.nw = l.words;
+  g.masks_off = l.masks_off; g.levels_off = l.levels_off;
   g.ct = std::min(kMaxChunkTiles, std::max(1u, kChunkCoeffs / g.area));
   g.cx = div_up(g.tx, g.ct);
   g.chunks = 3 * g.ty * g.cx;
   g.max_chunks = 3 * g.ty * g.tx;
   const uint32_t nt = std::min(g.ct, g.tx);
   g.max_chunk_bytes = 1 + 8 * g.nw * nt + 2 * nt * g.area;
-  g.masks_off = kHeaderBytes + 4ull * g.mvb;
-  g.levels_off = g.masks_off + 8ull * 3 * g.tx * g.ty * g.nw;
   return g;
 }
 
-uint64_t svcq_max_bytes(const Geom& g) { return up16(g.levels_off + 6ull * g.w * g.h); }
 // the worst SVCE frame: SVCQ's worst case, the types section's mode word, and per chunk its index entry and mode byte
 uint64_t svce_max_bytes(const Geom& g) { return up16(g.levels_off + 6ull * g.w * g.h + 4 + 5ull * g.chunks); }
 
@@ -122,38 +109,6 @@ DecWs carve_dec(uint8_t* p, uint32_t n, const Geom& g) {
 
 // ---- device helpers -----------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (uint32_t off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_exclusive_scan(uint32_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t x = v;
-  for (uint32_t off = 1; off < 64; off <<= 1) {
-    const uint32_t y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  return x - v;
-}
-
-// exclusive scan of v over the workgroup's 256 threads; *total gets the sum
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds4, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t ex = wave_exclusive_scan(v);
-  if (lane == 63) lds4[wave] = ex + v;
-  __syncthreads();
-  uint32_t base = 0, sum = 0;
-  for (uint32_t i = 0; i < kWaves; ++i) {
-    const uint32_t s = lds4[i];
-    if (i < wave) base += s;
-    sum += s;
-  }
-  __syncthreads();
-  *total = sum;
-  return base + ex;
-}
-
 __device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t* lds4) {
   for (uint32_t off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor(v, off, 64));
   if ((threadIdx.x & 63u) == 0) lds4[threadIdx.x >> 6] = v;
@@ -169,37 +124,6 @@ __device__ __forceinline__ uint32_t sgn(int32_t v) { return v > 0 ? 2u * (uint32
 __device__ __forceinline__ int32_t unsgn(uint32_t u) { return (u & 1u) ? (int32_t)((u + 1u) >> 1) : -(int32_t)(u >> 1); }
 // Exp-Golomb-k code length of u: 2 * floor(log2((u >> k) + 1)) + 1 + k
 __device__ __forceinline__ uint32_t eg_len(uint32_t u, uint32_t k) { return 2u * (bitlen32((u >> k) + 1u) - 1u) + 1u + k; }
-
-// the mask word j of a tile (u64 from two u32: the masks are only 4-byte aligned when the MV block count is odd)
-__device__ __forceinline__ uint64_t load_mask(const uint8_t* p) {
-  const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-  return (uint64_t)q[0] | ((uint64_t)q[1] << 32);
-}
-__device__ __forceinline__ void store_mask(uint8_t* p, uint64_t m) {
-  uint32_t* q = reinterpret_cast<uint32_t*>(p);
-  q[0] = (uint32_t)m;
-  q[1] = (uint32_t)(m >> 32);
-}
-
-// the SVCQ frame f of an encode's input: offsets, header against the geometry, size and padding (what the unpack checks before
-// its masks, plus the exact size and zero padding a lossless coding needs).  Reads nothing outside [o, e).
-__device__ uint32_t check_svcq(const Geom& g, const uint8_t* __restrict__ in, uint64_t stream_bytes, const uint64_t* __restrict__ offsets,
-                               uint32_t f, const uint32_t** hdr_out) {
-  const uint64_t o = offsets[f], e = offsets[f + 1];
-  if (o % 16 != 0 || o > e || e > stream_bytes || e - o < kHeaderBytes) return kStRange;
-  const uint32_t* h = reinterpret_cast<const uint32_t*>(in + o);
-  *hdr_out = h;
-  if (h[0] != kMagicQ) return kStMagic;
-  if (h[1] != kVersion) return kStVersion;
-  if (h[2] != g.w || h[3] != g.h || h[4] != g.bw || h[5] != g.bh || h[6] != g.mvbw || h[7] != g.mvbh || h[8] == 0 || h[9] == 0 ||
-      h[13] != 0 || h[14] != 0 || h[15] != 0)
-    return kStGeometry;
-  const uint64_t used = g.levels_off + 2ull * h[10];
-  if (h[12] != e - o || h[12] != up16(used)) return kStSize;
-  for (uint64_t i = used; i < h[12]; ++i)
-    if (in[o + i] != 0) return kStSize;
-  return kStOk;
-}
 
 // ---- encode -------------------------------------------------------------------------------------------------------------------
 
@@ -227,9 +151,10 @@ __global__ __launch_bounds__(256) void enc_count_kernel(EncArgs a) {
   const Geom& g = a.g;
   const uint32_t f = blockIdx.y, c = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (c >= g.chunks) return;
+  uint64_t off = 0;
   const uint32_t* hdr = nullptr;
   uint32_t cnt = 0, stray = 0;
-  if (check_svcq(g, a.in, a.in_bytes, a.in_off, f, &hdr) == kStOk) {
+  if (check_svcq<true>(g, a.in, a.in_bytes, a.in_off, f, &off, &hdr) == kStOk) {
     uint32_t row, t0, nt;
     chunk_tiles(g, g.ct, g.cx, c, &row, &t0, &nt);
     if (lane < nt) {
@@ -266,10 +191,11 @@ __global__ __launch_bounds__(256) void enc_scan_kernel(EncArgs a) {
   }
   uint32_t any_stray;
   (void)block_exclusive_scan(stray, red, &any_stray);
+  uint64_t off = 0;
   const uint32_t* hdr = nullptr;
-  uint32_t st = check_svcq(g, a.in, a.in_bytes, a.in_off, f, &hdr);
+  uint32_t st = check_svcq<true>(g, a.in, a.in_bytes, a.in_off, f, &off, &hdr);
   if (st == kStOk && any_stray) st = kStStrayBits;
-  if (st == kStOk && hdr[10] != carry) st = kStLevels;
+  if (st == kStOk && hdr[kHLevels] != carry) st = kStLevels;
   // the types section: a bitmap and fixed-width values, or raw when strictly smaller
   uint32_t nnz = 0, vmax = 0;
   if (st == kStOk) {
@@ -285,7 +211,7 @@ __global__ __launch_bounds__(256) void enc_scan_kernel(EncArgs a) {
   vmax = block_max(vmax, red);
   if (threadIdx.x == 0) {
     const uint32_t width = total_nnz ? bitlen32(vmax - 1) : 0;
-    const uint64_t coded = 4ull * (1 + cdiv(g.mvb, 32) + (uint32_t)(((uint64_t)total_nnz * width + 31) / 32));
+    const uint64_t coded = 4ull * (1 + div_up(g.mvb, 32) + (uint32_t)(((uint64_t)total_nnz * width + 31) / 32));
     const uint64_t raw = 4ull + 4ull * g.mvb;
     a.ws.types[2 * f] = (uint32_t)(raw < coded ? raw : coded);
     a.ws.types[2 * f + 1] = raw < coded ? 1u << 8 : width;
@@ -527,10 +453,10 @@ __global__ __launch_bounds__(256) void enc_frame_kernel(EncArgs a) {
   if (threadIdx.x < 16) {
     uint32_t v = in[threadIdx.x];
     if (threadIdx.x == 0) v = kMagicE;
-    if (threadIdx.x == 12) v = fbytes;
-    if (threadIdx.x == 13) v = in[12];
-    if (threadIdx.x == 14) v = g.ct;
-    if (threadIdx.x == 15) v = tbytes;
+    if (threadIdx.x == kHBytes) v = fbytes;
+    if (threadIdx.x == kESvcqBytes) v = in[kHBytes];
+    if (threadIdx.x == kEChunkTiles) v = g.ct;
+    if (threadIdx.x == kETypesBytes) v = tbytes;
     fw[threadIdx.x] = v;
   }
   const uint32_t* types = in + kHeaderBytes / 4;
@@ -540,7 +466,7 @@ __global__ __launch_bounds__(256) void enc_frame_kernel(EncArgs a) {
     for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) sec[1 + i] = types[i];
   } else {
     if (threadIdx.x == 0) sec[0] = width << 8;
-    const uint32_t bm = cdiv(g.mvb, 32);
+    const uint32_t bm = div_up(g.mvb, 32);
     uint32_t* vals = sec + 1 + bm;
     // 256 types at a time: the bitmap word of every 32, and the values (type - 1) in `width` bits at rank * width, ORed into an
     // LDS window of words; complete words go out, the partial last one carries into the next window
@@ -574,7 +500,7 @@ __global__ __launch_bounds__(256) void enc_frame_kernel(EncArgs a) {
     if (threadIdx.x == 0 && (end_bit & 31u)) vals[end_bit >> 5] = carry;
   }
   // the index: bytes | levels << 16 per chunk
-  const uint32_t level_count = in[10];
+  const uint32_t level_count = in[kHLevels];
   uint32_t* index = fw + (kHeaderBytes + tbytes) / 4;
   for (uint32_t i = threadIdx.x; i < g.chunks; i += kThreads) {
     const uint32_t lo = a.ws.cnt[(size_t)f * g.chunks + i];
@@ -614,25 +540,25 @@ __global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
   if (o % 16 != 0 || o > e || e > a.in_bytes || e - o < kHeaderBytes) st = kStRange;
   if (st == kStOk) {
     h = reinterpret_cast<const uint32_t*>(a.in + o);
-    if (h[0] != kMagicE) st = kStMagic;
-    else if (h[1] != kVersion) st = kStVersion;
-    else if (h[2] != g.w || h[3] != g.h || h[4] != g.bw || h[5] != g.bh || h[6] != g.mvbw || h[7] != g.mvbh || h[8] == 0 || h[9] == 0 ||
-             h[14] == 0)
+    if (h[kHMagic] != kMagicE) st = kStMagic;
+    else if (h[kHVersion] != kVersion) st = kStVersion;
+    else if (h[kHWidth] != g.w || h[kHHeight] != g.h || h[kHTileW] != g.bw || h[kHTileH] != g.bh || h[kHMvW] != g.mvbw ||
+             h[kHMvH] != g.mvbh || h[kHFgStep] == 0 || h[kHBgStep] == 0 || h[kEChunkTiles] == 0)
       st = kStGeometry;
-    else if (h[12] % 16 != 0 || h[12] != e - o) st = kStSize;
-    else if (h[10] > 3ull * g.w * g.h || h[13] != up16(g.levels_off + 2ull * h[10])) st = kStSvcqBytes;
+    else if (h[kHBytes] % 16 != 0 || h[kHBytes] != e - o) st = kStSize;
+    else if (h[kHLevels] > 3ull * g.w * g.h || h[kESvcqBytes] != up16(g.levels_off + 2ull * h[kHLevels])) st = kStSvcqBytes;
     else {
-      ct = h[14];
+      ct = h[kEChunkTiles];
       cx = ct >= g.tx ? 1u : (g.tx + ct - 1) / ct;  // ct may exceed tx (up to 2^32 - 1): then a chunk per tile row
       chunks = 3 * g.ty * cx;
-      payload = kHeaderBytes + (uint64_t)h[15] + 4ull * chunks;
-      if (h[15] % 4 != 0 || payload > h[12]) st = kStIndex;
+      payload = kHeaderBytes + (uint64_t)h[kETypesBytes] + 4ull * chunks;
+      if (h[kETypesBytes] % 4 != 0 || payload > h[kHBytes]) st = kStIndex;
     }
   }
   // the index: chunk byte and level offsets
   uint32_t bytes_total = 0, lev_total = 0;
   if (st == kStOk) {
-    const uint32_t* index = h + (kHeaderBytes + h[15]) / 4;
+    const uint32_t* index = h + (kHeaderBytes + h[kETypesBytes]) / 4;
     uint32_t bcarry = 0, lcarry = 0;
     for (uint32_t base = 0; base < chunks; base += kThreads) {
       const uint32_t i = base + threadIdx.x;
@@ -649,15 +575,15 @@ __global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
     }
     bytes_total = bcarry;
     lev_total = lcarry;
-    if (up16(payload + bytes_total) != h[12] || lev_total != h[10]) st = kStIndex;
+    if (up16(payload + bytes_total) != h[kHBytes] || lev_total != h[kHLevels]) st = kStIndex;
   }
   // the types section: its mode word and its size against the bitmap's popcount
   if (st == kStOk) {
     const uint32_t* sec = h + kHeaderBytes / 4;
-    const uint32_t tbytes = h[15];
+    const uint32_t tbytes = h[kETypesBytes];
     const uint32_t head = tbytes >= 4 ? sec[0] : 0xFFFFFFFFu;
     const uint32_t mode = head & 0xFFu, width = head >> 8;
-    const uint32_t bm = cdiv(g.mvb, 32);
+    const uint32_t bm = div_up(g.mvb, 32);
     uint32_t bad = 0, nnz = 0;
     if (tbytes < 4) bad = 1;
     else if (mode == 1 && width == 0) bad = (uint64_t)tbytes != 4ull + 4ull * g.mvb;
@@ -691,7 +617,7 @@ __global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
     a.ws.status[f] = s_st;
     a.ws.fail[f] = 0;
     a.ws.chunks[f] = s_st == kStOk ? ct : 0u;
-    a.ws.qbytes[f] = s_st == kStOk ? h[13] : kHeaderBytes;
+    a.ws.qbytes[f] = s_st == kStOk ? h[kESvcqBytes] : kHeaderBytes;
   }
 }
 
@@ -764,8 +690,8 @@ __global__ __launch_bounds__(256) void dec_chunks_kernel(DecArgs a) {
   if (c >= 3 * g.ty * cx) return;
   const uint8_t* frame = a.in + a.in_off[f];
   const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
-  const uint32_t fbytes = hdr[12];
-  const uint32_t* index = hdr + (kHeaderBytes + hdr[15]) / 4;
+  const uint32_t fbytes = hdr[kHBytes];
+  const uint32_t* index = hdr + (kHeaderBytes + hdr[kETypesBytes]) / 4;
   const uint32_t entry = index[c], size = entry & 0xFFFFu, count = entry >> 16;
   const uint32_t start = a.ws.coff[(size_t)f * g.max_chunks + c], lev0 = a.ws.loff[(size_t)f * g.max_chunks + c];
   uint32_t row, t0, nt;
@@ -866,7 +792,7 @@ __global__ __launch_bounds__(256) void dec_frame_kernel(DecArgs a) {
   if (threadIdx.x < 16) {
     uint32_t v = threadIdx.x < 12 ? h[threadIdx.x] : 0u;
     if (threadIdx.x == 0) v = kMagicQ;
-    if (threadIdx.x == 12) v = h[13];
+    if (threadIdx.x == kHBytes) v = h[kESvcqBytes];
     qw[threadIdx.x] = v;
   }
   const uint32_t* sec = h + kHeaderBytes / 4;
@@ -875,7 +801,7 @@ __global__ __launch_bounds__(256) void dec_frame_kernel(DecArgs a) {
   if (head == 1) {
     for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) types[i] = sec[1 + i];
   } else {
-    const uint32_t bm = cdiv(g.mvb, 32);
+    const uint32_t bm = div_up(g.mvb, 32);
     const uint32_t* bitmap = sec + 1;
     const uint32_t* vals = sec + 1 + bm;
     uint32_t carry = 0;
@@ -892,7 +818,7 @@ __global__ __launch_bounds__(256) void dec_frame_kernel(DecArgs a) {
         if (width) {
           const uint64_t bit = (uint64_t)rank * width;
           const uint64_t wi = bit >> 5;
-          const uint64_t two = (uint64_t)vals[wi] | (wi + 1 < (uint64_t)(h[15] / 4 - 1 - bm) ? (uint64_t)vals[wi + 1] << 32 : 0ull);
+          const uint64_t two = (uint64_t)vals[wi] | (wi + 1 < (uint64_t)(h[kETypesBytes] / 4 - 1 - bm) ? (uint64_t)vals[wi + 1] << 32 : 0ull);
           v = (two >> (bit & 31u)) & ((1ull << width) - 1ull);
         }
         t = (uint32_t)(v + 1);
@@ -900,23 +826,16 @@ __global__ __launch_bounds__(256) void dec_frame_kernel(DecArgs a) {
       types[i] = t;
     }
   }
-  const uint64_t used = g.levels_off + 2ull * h[10];
+  const uint64_t used = g.levels_off + 2ull * h[kHLevels];
   for (uint64_t i = used + threadIdx.x; i < qbytes; i += kThreads) q[i] = 0;
 }
 
-inline bool aligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) == 0; }
-
-int validate_geom(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
-  SVC_REQUIRE(w > 0 && h > 0 && bw > 0 && bh > 0, "%s: frame and tile sides must be positive", what);
-  SVC_REQUIRE(w % bw == 0 && h % bh == 0, "%s: frame %ux%u not divisible by tile %ux%u", what, w, h, bw, bh);
-  SVC_REQUIRE(mvbw > 0 && mvbh > 0 && mvbw % bw == 0 && mvbh % bh == 0 && w % mvbw == 0 && h % mvbh == 0,
-              "%s: MV block %ux%u must be a multiple of the tile %ux%u and divide the frame", what, mvbw, mvbh, bw, bh);
-  if ((uint64_t)bw * bh > kMaxTileCoeffs) return fail(SVC_ERR_UNSUPPORTED, "%s: tiles above %u coefficients", what, kMaxTileCoeffs);
-  if (n > 65535) return fail(SVC_ERR_UNSUPPORTED, "%s: more than 65535 frames in one call", what);
-  const Geom g = make_geom(w, h, bw, bh, mvbw, mvbh);
-  if (svce_max_bytes(g) > 0xFFFFFFFFull)
-    return fail(SVC_ERR_UNSUPPORTED, "%s: a frame of %ux%u could exceed the u32 frame_bytes field", what, w, h);
-  return SVC_OK;
+// geometry, then the limits with SVCE's worst case (make_geom divides by the tile area: only for a tile within the limit)
+int validate(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  const bool tile_ok = (uint64_t)bw * bh <= kMaxTileCoeffs;
+  return validate_limits(what, n, w, h, bw, bh, tile_ok ? svce_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)) : 0);
 }
 
 uint64_t ws_bytes(uint32_t n, const Geom& g) { return n ? std::max(enc_ws_bytes(n, g), dec_ws_bytes(n, g)) : 0; }
@@ -930,13 +849,13 @@ extern "C" {
 
 uint64_t svc_hip_entropy_max_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
                                    uint32_t mv_block_w, uint32_t mv_block_h) {
-  if (validate_geom("entropy_max_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
+  if (validate("entropy_max_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
   return n_frames * svce_max_bytes(make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
 }
 
 uint64_t svc_hip_entropy_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
                                          uint32_t mv_block_w, uint32_t mv_block_h) {
-  if (validate_geom("entropy_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
+  if (validate("entropy_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
   return ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
 }
 
@@ -945,7 +864,7 @@ int svc_hip_entropy_encode_frames(const uint8_t* d_svcq, uint64_t svcq_bytes, co
                                   uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
                                   uint32_t mv_block_h, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
                                   uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
-  int rc = validate_geom("entropy_encode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  int rc = validate("entropy_encode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g), "entropy_encode: workspace of %llu B is smaller than the %llu B needed",
@@ -958,12 +877,7 @@ int svc_hip_entropy_encode_frames(const uint8_t* d_svcq, uint64_t svcq_bytes, co
   SVC_REQUIRE(aligned(d_svcq, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_svcq_offsets, 8) &&
                   aligned(d_out_offsets, 8) && aligned(d_status, 4),
               "entropy_encode: frames, output and workspace must be 16-byte aligned, offsets 8-byte, status 4-byte");
-  EncArgs a;
-  a.g = g;
-  a.in = d_svcq; a.in_bytes = svcq_bytes; a.in_off = d_svcq_offsets;
-  a.out = d_out; a.out_off = d_out_offsets; a.d_status = d_status;
-  a.ws = carve_enc(d_workspace, n_frames, g);
-  a.n = n_frames;
+  const EncArgs a{g, d_svcq, svcq_bytes, d_svcq_offsets, d_out, d_out_offsets, d_status, carve_enc(d_workspace, n_frames, g), n_frames};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 chunk_grid(div_up(g.chunks, kWaves), n_frames);
   hipLaunchKernelGGL(enc_count_kernel, chunk_grid, dim3(kThreads), 0, s, a);
@@ -987,12 +901,12 @@ int svc_hip_entropy_decode_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
                                   uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
                                   uint32_t mv_block_h, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_svcq_out,
                                   uint64_t capacity, uint64_t* d_svcq_offsets, uint32_t* d_status, void* stream) {
-  int rc = validate_geom("entropy_decode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  int rc = validate("entropy_decode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g), "entropy_decode: workspace of %llu B is smaller than the %llu B needed",
               (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g));
-  const uint64_t need = n_frames * svcq_max_bytes(g);
+  const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
   SVC_REQUIRE(capacity >= need, "entropy_decode: output of %llu B is below the batch's SVCQ worst case of %llu B",
               (unsigned long long)capacity, (unsigned long long)need);
   if (n_frames == 0) return SVC_OK;
@@ -1000,12 +914,7 @@ int svc_hip_entropy_decode_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
   SVC_REQUIRE(aligned(d_svce, 16) && aligned(d_svcq_out, 16) && aligned(d_workspace, 16) && aligned(d_offsets, 8) &&
                   aligned(d_svcq_offsets, 8) && aligned(d_status, 4),
               "entropy_decode: frames, output and workspace must be 16-byte aligned, offsets 8-byte, status 4-byte");
-  DecArgs a;
-  a.g = g;
-  a.in = d_svce; a.in_bytes = svce_bytes; a.in_off = d_offsets;
-  a.out = d_svcq_out; a.out_off = d_svcq_offsets; a.d_status = d_status;
-  a.ws = carve_dec(d_workspace, n_frames, g);
-  a.n = n_frames;
+  const DecArgs a{g, d_svce, svce_bytes, d_offsets, d_svcq_out, d_svcq_offsets, d_status, carve_dec(d_workspace, n_frames, g), n_frames};
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(dec_check_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
   if ((rc = check_launch("entropy_decode check"))) return rc;
@@ -1015,6 +924,20 @@ int svc_hip_entropy_decode_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
   if ((rc = check_launch("entropy_decode chunks"))) return rc;
   hipLaunchKernelGGL(dec_frame_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
   return check_launch("entropy_decode frame");
+}
+
+// The drain of levels.hip for SVCE frames, with their worst case as the capacity rule.  Checked as an SVCQ geometry first; SVCE's own
+// limit is then reported as svc_hip_entropy_max_bytes reports it (an empty batch needs no room and is not refused for it).
+int svc_hip_entropy_drain(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t frame_w,
+                          uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                          void* host_dst, uint64_t capacity, void* stream) {
+  int rc = validate_geom("entropy_drain", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (!rc) rc = validate_limits("entropy_drain", n_frames, frame_w, frame_h, block_w, block_h,
+                                frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes);
+  if (rc) return rc;
+  const uint64_t worst = svce_max_bytes(make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
+  if ((rc = validate_limits("entropy_max_bytes", n_frames, frame_w, frame_h, block_w, block_h, worst)) && n_frames != 0) return rc;
+  return drain_to_host("entropy_drain", d_frames, d_frame_offsets, n_frames, host_dst, capacity, n_frames * worst, stream);
 }
 
 }  // extern "C"

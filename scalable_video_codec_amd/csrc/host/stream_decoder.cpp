@@ -2,6 +2,7 @@
 // other way.  No arithmetic of the hot path lives here; the gaze rule and the decode are calls into the C ABI.
 #include "svc/stream_decoder.hpp"
 
+#include "../stream_format.hpp"
 #include "copy_crew.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -65,8 +66,6 @@ struct Slot {
   }
 };
 
-constexpr uint32_t kMagic = 0x51435653u, kMagicE = 0x45435653u, kVersion = 1;  // include/svc_hip.h, the SVCQ and SVCE headers
-
 }  // namespace
 
 struct StreamDecoder::Impl {
@@ -93,24 +92,23 @@ struct StreamDecoder::Impl {
   }
 
   void Size(const uint32_t* hdr, bool entropy) {
-    const uint32_t w = hdr[2], h = hdr[3];
+    const uint32_t w = hdr[kHWidth], h = hdr[kHHeight], tw = hdr[kHTileW], th = hdr[kHTileH], mw = hdr[kHMvW], mh = hdr[kHMvH];
     const uint32_t want_dw = c.display_w ? c.display_w : w, want_dh = c.display_h ? c.display_h : h;
-    if (!wire && entropy == svce && w == pw && h == ph && hdr[4] == bw && hdr[5] == bh && hdr[6] == mbw && hdr[7] == mbh && want_dw == dw &&
-        want_dh == dh)
+    if (!wire && entropy == svce && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
       return;
     for (hipStream_t s : {s_in, s_compute, s_out}) Hip(hipStreamSynchronize(s), "hipStreamSynchronize");
-    const uint64_t need_ws = svc_hip_decode_levels_workspace_bytes(c.batch, w, h, hdr[4], hdr[5]);
+    const uint64_t need_ws = svc_hip_decode_levels_workspace_bytes(c.batch, w, h, tw, th);
     if (!need_ws) Abi(SVC_ERR_UNSUPPORTED, "no decoder for the first frame's geometry");
     if (want_dw > w || want_dh > h) throw std::runtime_error("svc::StreamDecoder: the display size exceeds the padded frame");
     if (entropy) {
-      q_bytes = svc_hip_levels_max_bytes(c.batch, w, h, hdr[4], hdr[5], hdr[6], hdr[7]);
-      ews_bytes = svc_hip_entropy_workspace_bytes(c.batch, w, h, hdr[4], hdr[5], hdr[6], hdr[7]);
+      q_bytes = svc_hip_levels_max_bytes(c.batch, w, h, tw, th, mw, mh);
+      ews_bytes = svc_hip_entropy_workspace_bytes(c.batch, w, h, tw, th, mw, mh);
       if (!q_bytes || !ews_bytes) Abi(SVC_ERR_UNSUPPORTED, "no entropy decoder for the first frame's geometry");
       q.Alloc(q_bytes); ews.Alloc(ews_bytes); qoff.Alloc(c.batch + 1);
     }
     svce = entropy;
     wire = false;
-    pw = w; ph = h; bw = hdr[4]; bh = hdr[5]; mbw = hdr[6]; mbh = hdr[7]; dw = want_dw; dh = want_dh;
+    pw = w; ph = h; bw = tw; bh = th; mbw = mw; mbh = mh; dw = want_dw; dh = want_dh;
     disp_bytes = (uint64_t)dw * dh * 3;
     ws_bytes = need_ws;
     const size_t B = c.batch;
@@ -172,13 +170,13 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
   if (n_frames == 0) { m.stats = DecodeStats{}; return; }
   if (!stream || !offsets) throw std::runtime_error("svc::StreamDecoder: null stream");
   const uint64_t total = offsets[n_frames];  // the stream's bytes, from offsets[0] on
-  if (offsets[0] % 16 || offsets[0] > total || total - offsets[0] < 64 || offsets[1] < offsets[0] + 64)
+  if (offsets[0] % 16 || offsets[0] > total || total - offsets[0] < kHeaderBytes || offsets[1] < offsets[0] + kHeaderBytes)
     throw std::runtime_error("svc::StreamDecoder: the first frame's header is out of range");
-  uint32_t hdr[16];
+  uint32_t hdr[kHeaderWords];
   std::memcpy(hdr, stream + offsets[0], sizeof(hdr));
-  if ((hdr[0] != kMagic && hdr[0] != kMagicE) || hdr[1] != kVersion)
+  if ((hdr[kHMagic] != kMagicQ && hdr[kHMagic] != kMagicE) || hdr[kHVersion] != kVersion)
     throw std::runtime_error("svc::StreamDecoder: the stream does not open with an SVCQ v1 or SVCE v1 header");
-  m.Size(hdr, hdr[0] == kMagicE);
+  m.Size(hdr, hdr[kHMagic] == kMagicE);
   const uint32_t B = c.batch;
 
   using Clock = std::chrono::steady_clock;

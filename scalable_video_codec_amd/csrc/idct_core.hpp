@@ -1,6 +1,7 @@
 // idct_core.hpp -- the decoder's per-coefficient arithmetic, shared by every kernel that reconstructs tiles (idct.hip from f32
-// planes, levels.hip straight from the compact stream): the f64 inverse DCT basis, the 1-D inverse transform and the
-// quantise-round-dequantise of DecodeBlock.  One definition, so that both paths produce the same bits.
+// planes, levels.hip straight from the compact stream, records.hip from the wire records): the f64 inverse DCT basis, the 1-D
+// inverse transform and the quantise-round-dequantise of DecodeBlock; and the edges the two stream decoders share, the gaze test
+// of a tile and the store of a thread's pixel column.  One definition, so that all paths produce the same bits.
 #pragma once
 
 #include "svc_common.hpp"
@@ -41,6 +42,24 @@ __device__ __forceinline__ float requant(float c, float step) {  // libs/decoder
   float q = c / step;
   q = roundf(q);
   return q * step;
+}
+
+// is the tile at (tx, ty) inside frame f's gaze rectangle?  gaze = [n][4] x, y, w, h in padded coordinates, or null (no gaze):
+// x <= tx < x + w && y <= ty < y + h, without overflow
+__device__ __forceinline__ bool gazed(const uint32_t* gaze, uint32_t f, uint32_t tx, uint32_t ty) {
+  if (!gaze) return false;
+  const uint32_t* r = gaze + 4ull * f;
+  return tx >= r[0] && tx - r[0] < r[2] && ty >= r[1] && ty - r[1] < r[3];
+}
+
+// a thread's column of N interleaved B,G,R pixels, from dst down rows of w pixels (the lanes of a wave hold adjacent columns)
+template <int N>
+__device__ __forceinline__ void store_bgr_column(float* dst, uint32_t w, const float (&out)[3][N]) {
+#pragma unroll
+  for (int y = 0; y < N; ++y) {
+    float* p = dst + (size_t)y * w * 3;
+    p[0] = out[0][y]; p[1] = out[1][y]; p[2] = out[2][y];
+  }
 }
 
 }  // namespace svc

@@ -2,8 +2,7 @@
 //
 // Quantised planes are almost all zeros (a C3 background tile-channel holds about one non-zero level), so a frame is sent as
 // a significance mask per tile plus the non-zero levels as int16 -- about 1 MB instead of the 25 MB of f32 planes at 1080p.
-// Layout of one frame (little-endian, 16-byte aligned, frames back to back; include/svc_hip.h has the table):
-//   header 16 x u32 | types [mv blocks] u32 | masks [3][tiles_y][tiles_x][words] u64 | levels [level_count] i16 | zero pad to 16
+// stream_format.hpp states the frame's layout, its header and the check of a frame; include/svc_hip.h has the table.
 //
 // Work split, pack and unpack alike: a workgroup owns a GROUP = one plane, one tile row, up to `tpg` adjacent tiles (about 2048
 // coefficients).  It stages the group's rows in LDS with 16-byte loads (the planes are row-major: one 8x8 tile per wave would
@@ -21,6 +20,7 @@
 // resize, to u8).
 #include "display_core.hpp"
 #include "idct_core.hpp"
+#include "stream_format.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,16 +28,8 @@
 namespace svc {
 namespace {
 
-constexpr uint32_t kMagic = 0x51435653u;  // "SVCQ"
-constexpr uint32_t kVersion = 1;
-constexpr uint32_t kHeaderBytes = 64;
-constexpr uint32_t kMaxTileCoeffs = 4096;  // a tile fits one group's LDS; the Dct's largest tile is 64 x 64
 constexpr uint32_t kGroupCoeffs = 2048;    // coefficients a workgroup stages
 constexpr uint32_t kMaxJobs = 256;         // mask words per group
-constexpr uint32_t kThreads = 256;
-
-// unpack's per-frame status word
-enum : uint32_t { kStOk = 0, kStRange = 1, kStMagic = 2, kStVersion = 3, kStGeometry = 4, kStSize = 5, kStLevels = 6, kStStrayBits = 7 };
 
 struct Geom {
   uint32_t w, h, bw, bh, mvbw, mvbh, mfw, mvb;
@@ -47,29 +39,24 @@ struct Geom {
   bool vec;                                          // rows may be moved as float4
 };
 
-__host__ __device__ inline uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
-
+// the frame's layout and this file's work split
 Geom make_geom(uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const FrameLayout l = frame_layout(w, h, bw, bh, mvbw, mvbh);
   Geom g{};
   g.w = w; g.h = h; g.bw = bw; g.bh = bh; g.mvbw = mvbw; g.mvbh = mvbh;
-  g.mfw = w / mvbw; g.mvb = g.mfw * (h / mvbh);
-  g.tiles_x = w / bw; g.tiles_y = h / bh;
-  const uint32_t area = bw * bh;
-  g.words = (area + 63) / 64;
-  uint32_t tpg = std::max<uint32_t>(1, kGroupCoeffs / area);
+  g.mfw = l.mfw; g.mvb = l.mvb;
+  g.tiles_x = l.tiles_x; g.tiles_y = l.tiles_y; g.words = l.words;
+  g.masks_off = l.masks_off; g.levels_off = l.levels_off;
+  uint32_t tpg = std::max<uint32_t>(1, kGroupCoeffs / (bw * bh));
   tpg = std::max<uint32_t>(1, std::min<uint32_t>(tpg, kMaxJobs / g.words));  // (tiles above kMaxTileCoeffs are refused)
   if (tpg > 1) tpg &= ~1u;  // even: a group's first column (tile side even) is then a multiple of 4 floats
   g.tpg = std::min(tpg, g.tiles_x);
   g.gx = div_up(g.tiles_x, g.tpg);
   g.groups = 3 * g.tiles_y * g.gx;
   g.pitch_pad = bw & 63;
-  g.masks_off = kHeaderBytes + 4ull * g.mvb;
-  g.levels_off = g.masks_off + 8ull * 3 * g.tiles_x * g.tiles_y * g.words;
   g.vec = w % 4 == 0 && (g.tpg * bw) % 4 == 0;  // then every group's first column and every plane are 16-byte aligned
   return g;
 }
-
-uint64_t frame_max_bytes(const Geom& g) { return up16(g.levels_off + 2ull * 3 * g.w * g.h); }
 
 uint32_t lds_bytes(const Geom& g) {
   const uint32_t cols = g.tpg * g.bw;
@@ -175,43 +162,6 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// exclusive scan of v over the workgroup's 256 threads; *total gets the sum
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds4, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t x = v;
-  for (uint32_t off = 1; off < 64; off <<= 1) {
-    const uint32_t y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) lds4[wave] = x;
-  __syncthreads();
-  uint32_t base = 0, sum = 0;
-  for (uint32_t i = 0; i < kThreads / 64; ++i) {
-    const uint32_t s = lds4[i];
-    if (i < wave) base += s;
-    sum += s;
-  }
-  __syncthreads();
-  *total = sum;
-  return base + x - v;
-}
-
-// unpack: is frame f well formed for geometry g inside a stream of stream_bytes?  Returns a status, fills *off / *hdr
-__device__ uint32_t check_frame(const Geom& g, const uint8_t* __restrict__ in, uint64_t stream_bytes,
-                                const uint64_t* __restrict__ offsets, uint32_t f, uint64_t* off, const uint32_t** hdr) {
-  const uint64_t o = offsets[f], e = offsets[f + 1];
-  *off = o;
-  if (o % 16 != 0 || o > e || e > stream_bytes || e - o < kHeaderBytes) return kStRange;
-  const uint32_t* h = reinterpret_cast<const uint32_t*>(in + o);
-  *hdr = h;
-  if (h[0] != kMagic) return kStMagic;
-  if (h[1] != kVersion) return kStVersion;
-  if (h[2] != g.w || h[3] != g.h || h[4] != g.bw || h[5] != g.bh || h[6] != g.mvbw || h[7] != g.mvbh || h[8] == 0 || h[9] == 0)
-    return kStGeometry;
-  if (h[12] != e - o || g.levels_off + 2ull * h[10] > h[12]) return kStSize;
-  return kStOk;
-}
-
 // ---- pack --------------------------------------------------------------------------------------------------------------------
 
 struct PackArgs {
@@ -307,7 +257,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   const uint32_t level_count = a.ws.frame_levels[f], fbytes = a.ws.frame_bytes[f];
   uint32_t* hdr = reinterpret_cast<uint32_t*>(frame);
   if (threadIdx.x < 16) {
-    const uint32_t v[16] = {kMagic, kVersion, g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh, fg, bg, level_count, a.ws.frame_inexact[f],
+    const uint32_t v[kHeaderWords] = {kMagicQ, kVersion, g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh, fg, bg, level_count, a.ws.frame_inexact[f],
                             fbytes, 0, 0, 0};
     hdr[threadIdx.x] = v[threadIdx.x];
   }
@@ -352,9 +302,9 @@ __global__ __launch_bounds__(256) void scan_kernel(Geom g, Ws ws, const uint8_t*
   if (threadIdx.x == 0) {
     uint64_t off = 0;
     const uint32_t* hdr = nullptr;
-    uint32_t st = check_frame(g, in, stream_bytes, offsets, f, &off, &hdr);
+    uint32_t st = check_svcq<false>(g, in, stream_bytes, offsets, f, &off, &hdr);
     if (st == kStOk && t != 0) st = kStStrayBits;
-    if (st == kStOk && hdr[10] != carry) st = kStLevels;
+    if (st == kStOk && hdr[kHLevels] != carry) st = kStLevels;
     ws.status[f] = st;
     d_status[f] = st;
   }
@@ -497,14 +447,14 @@ __global__ __launch_bounds__(256) void unpack_kernel(UnpackArgs a) {
   const Group gr = group_of(g, gi);
   uint64_t off = 0;
   const uint32_t* hdr = nullptr;
-  const uint32_t st = SCATTER ? a.ws.status[f] : check_frame(g, a.in, a.stream_bytes, a.offsets, f, &off, &hdr);
+  const uint32_t st = SCATTER ? a.ws.status[f] : check_svcq<false>(g, a.in, a.stream_bytes, a.offsets, f, &off, &hdr);
   if (SCATTER) off = a.offsets[f], hdr = reinterpret_cast<const uint32_t*>(a.in + off);
   const uint8_t* frame = a.in + off;
   const uint32_t jobs = gr.nt * g.words;
   const uint32_t* masks = st != kStOk ? nullptr :
       reinterpret_cast<const uint32_t*>(frame + g.masks_off) + 2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
   const uint32_t j = threadIdx.x;
-  const uint64_t m = (masks && j < jobs) ? ((uint64_t)masks[2 * j + 1] << 32 | masks[2 * j]) : 0ull;
+  const uint64_t m = (masks && j < jobs) ? load_mask(masks + 2 * j) : 0ull;
   const uint32_t area = g.bw * g.bh;
   uint32_t total;
   const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
@@ -523,7 +473,7 @@ __global__ __launch_bounds__(256) void unpack_kernel(UnpackArgs a) {
   __syncthreads();
   const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) + a.ws.cnt[(size_t)f * g.groups + gi];
   const uint32_t* types = reinterpret_cast<const uint32_t*>(frame + kHeaderBytes);
-  const float fg = st == kStOk ? (float)hdr[8] : 0.f, bg = st == kStOk ? (float)hdr[9] : 0.f;
+  const float fg = st == kStOk ? (float)hdr[kHFgStep] : 0.f, bg = st == kStOk ? (float)hdr[kHBgStep] : 0.f;
   for (uint32_t jj = wave; jj < jobs; jj += kThreads / 64) {
     const uint64_t mask = job_mask[jj];
     const uint32_t t = jj / g.words, k = (jj - t * g.words) * 64 + lane;
@@ -578,14 +528,9 @@ __global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
   float enc = 0.f, dec = 1.f;
   if (st == kStOk && active) {
     const uint32_t type = tile_type(g, reinterpret_cast<const uint32_t*>(frame + kHeaderBytes), gr, t);
-    const uint32_t tx = gr.x0 + t * N, ty = gr.y0;
-    bool gazed = false;
-    if (a.gaze) {  // x <= tx < x + w && y <= ty < y + h, without overflow
-      const uint32_t* r = a.gaze + 4ull * f;
-      gazed = tx >= r[0] && tx - r[0] < r[2] && ty >= r[1] && ty - r[1] < r[3];
-    }
-    enc = (float)(type == 0 ? hdr[9] : hdr[8]);
-    dec = gazed ? 1.f : (type == 0 ? a.bg : a.fg);
+    const bool in_gaze = gazed(a.gaze, f, gr.x0 + t * N, gr.y0);  // ahead of the header's steps: in this order the code is the measured one
+    enc = (float)(type == 0 ? hdr[kHBgStep] : hdr[kHFgStep]);
+    dec = in_gaze ? 1.f : (type == 0 ? a.bg : a.fg);
   }
   const uint32_t jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
   float out[3][N];
@@ -593,7 +538,7 @@ __global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
   for (int c = 0; c < 3; ++c) {
     const uint32_t* masks = st != kStOk ? nullptr :
         reinterpret_cast<const uint32_t*>(frame + g.masks_off) + 2 * ((((size_t)c * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
-    const uint64_t m = (masks && tid < jobs) ? ((uint64_t)masks[2 * tid + 1] << 32 | masks[2 * tid]) : 0ull;
+    const uint64_t m = (masks && tid < jobs) ? load_mask(masks + 2 * tid) : 0ull;
     uint32_t total;
     const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
     if (tid < jobs) { job_mask[tid] = m; job_base[tid] = ex; }
@@ -627,12 +572,8 @@ __global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
     __syncthreads();  // the next plane reuses rows and the job arrays
   }
   if (!active) return;
-  float* dst = a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3;  // a wave stores 64 adjacent pixels per row
-#pragma unroll
-  for (int y = 0; y < N; ++y) {
-    float* p = dst + (size_t)y * g.w * 3;
-    p[0] = out[0][y]; p[1] = out[1][y]; p[2] = out[2][y];
-  }
+  // a wave stores 64 adjacent pixels per row
+  store_bgr_column<N>(a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3, g.w, out);
 }
 
 // ---- drain -------------------------------------------------------------------------------------------------------------------
@@ -646,9 +587,49 @@ __global__ __launch_bounds__(256) void drain_kernel(const uint4* __restrict__ sr
   for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// ---- the entry points' checks and launch sequences -----------------------------------------------------------------------------------
 
-// the drain after its geometry checks: capacity against `need`, then pointers, the destination's memory, and the launch
+// the limits with SVCQ's worst case
+int validate_limits(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  return svc::validate_limits(what, n, w, h, bw, bh, frame_layout(w, h, bw, bh, mvbw, mvbh).max_bytes);
+}
+
+// decode: what the reconstruction kernels take (square 8x8 or 16x16 transform blocks and a width of whole 16-pixel segments, as
+// svc_hip_decode_frames; sides up to 32768 for the display pass's u32 coordinates), after the format's own geometry
+int validate_decode_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  if (bw != bh || (bw != 8 && bw != 16))
+    return fail(SVC_ERR_UNSUPPORTED, "%s: transform block %ux%u (supported: 8x8, 16x16)", what, bw, bh);
+  if (w % 16 != 0) return fail(SVC_ERR_UNSUPPORTED, "%s: frame width %u is not a multiple of 16", what, w);
+  if (w > 32768 || h > 32768) return fail(SVC_ERR_UNSUPPORTED, "%s: frame %ux%u above 32768 on a side", what, w, h);
+  return SVC_OK;
+}
+
+// the pack's launches, with a.fg / a.bg or the budgeted pack's per-frame steps
+int enqueue_pack(const char* what, const PackArgs& a, hipStream_t s) {
+  const Geom& g = a.g;
+  const dim3 grid(g.groups, a.n);
+  int rc;
+  hipLaunchKernelGGL(pack_kernel<false>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  if ((rc = check_launch(what, "count"))) return rc;
+  hipLaunchKernelGGL(scan_kernel<false>, dim3(a.n), dim3(kThreads), 0, s, g, a.ws, nullptr, 0, nullptr, nullptr);
+  if ((rc = check_launch(what, "scan"))) return rc;
+  hipLaunchKernelGGL(pack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  return check_launch(what, "scatter");
+}
+
+// what the unpack and the decode begin with: the groups' level counts, then their prefixes and every frame's status
+int enqueue_unpack_scan(const char* what, const UnpackArgs& u, uint32_t n, uint32_t* d_status, hipStream_t s) {
+  hipLaunchKernelGGL(unpack_kernel<false>, dim3(u.g.groups, n), dim3(kThreads), 0, s, u);
+  const int rc = check_launch(what, "count");
+  if (rc) return rc;
+  hipLaunchKernelGGL(scan_kernel<true>, dim3(n), dim3(kThreads), 0, s, u.g, u.ws, u.in, u.stream_bytes, u.offsets, d_status);
+  return check_launch(what, "scan");
+}
+
+}  // namespace
+
 int drain_to_host(const char* what, const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, void* host_dst,
                   uint64_t capacity, uint64_t need, void* stream) {
   SVC_REQUIRE(capacity >= need, "%s: destination of %llu B is below the batch's worst case of %llu B", what,
@@ -686,36 +667,6 @@ int drain_to_host(const char* what, const uint8_t* d_frames, const uint64_t* d_f
   return check_launch(what);
 }
 
-int validate_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
-  SVC_REQUIRE(w > 0 && h > 0 && bw > 0 && bh > 0, "%s: frame and tile sides must be positive", what);
-  SVC_REQUIRE(w % bw == 0 && h % bh == 0, "%s: frame %ux%u not divisible by tile %ux%u", what, w, h, bw, bh);
-  SVC_REQUIRE(mvbw > 0 && mvbh > 0 && mvbw % bw == 0 && mvbh % bh == 0 && w % mvbw == 0 && h % mvbh == 0,
-              "%s: MV block %ux%u must be a multiple of the tile %ux%u and divide the frame", what, mvbw, mvbh, bw, bh);
-  return SVC_OK;
-}
-
-// what this build's kernels and the format's fields hold
-int validate_limits(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
-  if ((uint64_t)bw * bh > kMaxTileCoeffs) return fail(SVC_ERR_UNSUPPORTED, "%s: tiles above %u coefficients", what, kMaxTileCoeffs);
-  if (n > 65535) return fail(SVC_ERR_UNSUPPORTED, "%s: more than 65535 frames in one call", what);
-  if (frame_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)) > 0xFFFFFFFFull)
-    return fail(SVC_ERR_UNSUPPORTED, "%s: a frame of %ux%u could exceed the u32 frame_bytes field", what, w, h);
-  return SVC_OK;
-}
-
-// decode: what the reconstruction kernels take (square 8x8 or 16x16 transform blocks and a width of whole 16-pixel segments, as
-// svc_hip_decode_frames; sides up to 32768 for the display pass's u32 coordinates), after the format's own geometry
-int validate_decode_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
-  const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
-  if (rc) return rc;
-  if (bw != bh || (bw != 8 && bw != 16))
-    return fail(SVC_ERR_UNSUPPORTED, "%s: transform block %ux%u (supported: 8x8, 16x16)", what, bw, bh);
-  if (w % 16 != 0) return fail(SVC_ERR_UNSUPPORTED, "%s: frame width %u is not a multiple of 16", what, w);
-  if (w > 32768 || h > 32768) return fail(SVC_ERR_UNSUPPORTED, "%s: frame %ux%u above 32768 on a side", what, w, h);
-  return SVC_OK;
-}
-
-}  // namespace
 }  // namespace svc
 
 using namespace svc;
@@ -727,7 +678,7 @@ uint64_t svc_hip_levels_max_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t 
   if (validate_geom("levels_max_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
       validate_limits("levels_max_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
     return 0;
-  return n_frames * frame_max_bytes(make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
+  return n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
 }
 
 uint64_t svc_hip_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
@@ -756,7 +707,7 @@ int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_ty
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "pack_levels: workspace of %llu B is smaller than the %llu B needed",
               (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
-  const uint64_t need = n_frames * frame_max_bytes(g);
+  const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
   SVC_REQUIRE(out_capacity >= need, "pack_levels: output of %llu B is below the batch's worst case of %llu B",
               (unsigned long long)out_capacity, (unsigned long long)need);
   if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
@@ -764,19 +715,9 @@ int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_ty
   SVC_REQUIRE(aligned(d_planes, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4),
               "pack_levels: planes, output and workspace must be 16-byte aligned, offsets 8-byte");
-  PackArgs a;
-  a.g = g;
-  a.planes = d_planes; a.types = d_block_types; a.out = d_out; a.offsets = d_frame_offsets;
-  a.ws = carve(d_workspace, n_frames, g.groups);
-  a.n = n_frames; a.fg = fg_step; a.bg = bg_step; a.steps = nullptr;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(g.groups, n_frames);
-  hipLaunchKernelGGL(pack_kernel<false>, grid, dim3(kThreads), lds_bytes(g), s, a);
-  if ((rc = check_launch("pack_levels count"))) return rc;
-  hipLaunchKernelGGL(scan_kernel<false>, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws, nullptr, 0, nullptr, nullptr);
-  if ((rc = check_launch("pack_levels scan"))) return rc;
-  hipLaunchKernelGGL(pack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
-  return check_launch("pack_levels scatter");
+  const PackArgs a{g, d_planes, d_block_types, d_out, d_frame_offsets, carve(d_workspace, n_frames, g.groups), n_frames, fg_step, bg_step,
+                   nullptr};
+  return enqueue_pack("pack_levels", a, static_cast<hipStream_t>(stream));
 }
 
 uint64_t svc_hip_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
@@ -817,7 +758,7 @@ int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_b
   const uint64_t ws_need = budget_ws_bytes(n_frames, g.groups, ladder_len);
   SVC_REQUIRE(workspace_bytes >= ws_need, "pack_levels_budget: workspace of %llu B is smaller than the %llu B needed",
               (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
-  const uint64_t need = n_frames * frame_max_bytes(g);
+  const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
   SVC_REQUIRE(out_capacity >= need, "pack_levels_budget: output of %llu B is below the batch's worst case of %llu B",
               (unsigned long long)out_capacity, (unsigned long long)need);
   if (n_frames == 0) return SVC_OK;
@@ -841,17 +782,8 @@ int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_b
   hipLaunchKernelGGL(budget_select_kernel, dim3(div_up(n_frames, kThreads)), dim3(kThreads), 0, s, n_frames, lad, bws.bytes, d_budget,
                      bws.steps, d_choice);
   if ((rc = check_launch("pack_levels_budget select"))) return rc;
-  PackArgs a;
-  a.g = g;
-  a.planes = d_planes; a.types = d_block_types; a.out = d_out; a.offsets = d_frame_offsets;
-  a.ws = bws.pack;
-  a.n = n_frames; a.fg = 0; a.bg = 0; a.steps = bws.steps;
-  hipLaunchKernelGGL(pack_kernel<false>, grid, dim3(kThreads), lds_bytes(g), s, a);
-  if ((rc = check_launch("pack_levels_budget count"))) return rc;
-  hipLaunchKernelGGL(scan_kernel<false>, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws, nullptr, 0, nullptr, nullptr);
-  if ((rc = check_launch("pack_levels_budget scan"))) return rc;
-  hipLaunchKernelGGL(pack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
-  return check_launch("pack_levels_budget scatter");
+  const PackArgs a{g, d_planes, d_block_types, d_out, d_frame_offsets, bws.pack, n_frames, 0, 0, bws.steps};
+  return enqueue_pack("pack_levels_budget", a, s);
 }
 
 int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
@@ -869,18 +801,10 @@ int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_planes, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4) && aligned(d_status, 4),
               "unpack_levels: frames, planes and workspace must be 16-byte aligned, offsets 8-byte");
-  UnpackArgs a;
-  a.g = g;
-  a.in = d_frames; a.stream_bytes = stream_bytes; a.offsets = d_frame_offsets;
-  a.planes = d_planes; a.types = d_block_types;
-  a.ws = carve(d_workspace, n_frames, g.groups);
+  const UnpackArgs a{g, d_frames, stream_bytes, d_frame_offsets, d_planes, d_block_types, carve(d_workspace, n_frames, g.groups)};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(g.groups, n_frames);
-  hipLaunchKernelGGL(unpack_kernel<false>, grid, dim3(kThreads), 0, s, a);
-  if ((rc = check_launch("unpack_levels count"))) return rc;
-  hipLaunchKernelGGL(scan_kernel<true>, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws, d_frames, stream_bytes, d_frame_offsets, d_status);
-  if ((rc = check_launch("unpack_levels scan"))) return rc;
-  hipLaunchKernelGGL(unpack_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  if ((rc = enqueue_unpack_scan("unpack_levels", a, n_frames, d_status, s))) return rc;
+  hipLaunchKernelGGL(unpack_kernel<true>, dim3(g.groups, n_frames), dim3(kThreads), lds_bytes(g), s, a);
   return check_launch("unpack_levels scatter");
 }
 
@@ -890,20 +814,8 @@ int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offset
   int rc = validate_geom("levels_drain", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (!rc) rc = validate_limits("levels_drain", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
-  const uint64_t need = svc_hip_levels_max_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  return drain_to_host("levels_drain", d_frames, d_frame_offsets, n_frames, host_dst, capacity, need, stream);
-}
-
-// The same drain for SVCE frames (csrc/entropy.hip), with their worst case as the capacity rule.
-int svc_hip_entropy_drain(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t frame_w,
-                          uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
-                          void* host_dst, uint64_t capacity, void* stream) {
-  int rc = validate_geom("entropy_drain", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  if (!rc) rc = validate_limits("entropy_drain", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  if (rc) return rc;
-  const uint64_t need = svc_hip_entropy_max_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  if (need == 0 && n_frames != 0) return SVC_ERR_UNSUPPORTED;  // svc_hip_last_error() says why
-  return drain_to_host("entropy_drain", d_frames, d_frame_offsets, n_frames, host_dst, capacity, need, stream);
+  return drain_to_host("levels_drain", d_frames, d_frame_offsets, n_frames, host_dst, capacity,
+                       n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes, stream);
 }
 
 uint64_t svc_hip_decode_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
@@ -923,8 +835,7 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   if (rc) return rc;
   SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_levels: quant steps must be positive (libs/decoder.cpp:35-47)");
   const bool display = display_w != 0 || display_h != 0;
-  SVC_REQUIRE(!display || (display_w >= 1 && display_w <= frame_w && display_h >= 1 && display_h <= frame_h),
-              "decode_levels: display %ux%u must lie within 1x1 .. %ux%u (the padded frame)", display_w, display_h, frame_w, frame_h);
+  if ((rc = validate_display("decode_levels", display_w, display_h, frame_w, frame_h))) return rc;
   if ((rc = validate_limits("decode_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "decode_levels: workspace of %llu B is smaller than the %llu B needed",
@@ -935,27 +846,16 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_rec, 4) &&
                   aligned(d_status, 4) && aligned(d_gaze, 4),
               "decode_levels: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
-  UnpackArgs u;
-  u.g = g;
-  u.in = d_frames; u.stream_bytes = stream_bytes; u.offsets = d_frame_offsets;
-  u.planes = nullptr; u.types = nullptr;  // the count pass writes neither
-  u.ws = carve(d_workspace, n_frames, g.groups);
+  // planes and types null: the count pass writes neither
+  const UnpackArgs u{g, d_frames, stream_bytes, d_frame_offsets, nullptr, nullptr, carve(d_workspace, n_frames, g.groups)};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(unpack_kernel<false>, dim3(g.groups, n_frames), dim3(kThreads), 0, s, u);
-  if ((rc = check_launch("decode_levels count"))) return rc;
-  hipLaunchKernelGGL(scan_kernel<true>, dim3(n_frames), dim3(kThreads), 0, s, g, u.ws, d_frames, stream_bytes, d_frame_offsets, d_status);
-  if ((rc = check_launch("decode_levels scan"))) return rc;
-  DecodeArgs a;
-  a.g = g;
-  a.in = d_frames; a.offsets = d_frame_offsets; a.gaze = d_gaze; a.rec = d_rec; a.ws = u.ws;
-  a.fg = (float)fg_step; a.bg = (float)bg_step;
+  if ((rc = enqueue_unpack_scan("decode_levels", u, n_frames, d_status, s))) return rc;
+  const DecodeArgs a{g, d_frames, d_frame_offsets, d_gaze, d_rec, u.ws, (float)fg_step, (float)bg_step};
   const dim3 grid(g.tiles_y * g.gx, n_frames);
   if (block_w == 8) hipLaunchKernelGGL(decode_levels_kernel<8>, grid, dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(decode_levels_kernel<16>, grid, dim3(kThreads), 0, s, a);
   if ((rc = check_launch("decode_levels reconstruction")) || !display) return rc;
-  hipLaunchKernelGGL(display_kernel, dim3(div_up(display_w, kDisplayThreads), display_h, n_frames), dim3(kDisplayThreads), 0, s, d_rec, d_display,
-                     frame_w, frame_h, display_w, display_h);
-  return check_launch("decode_levels display");
+  return launch_display("decode_levels", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w, uint32_t frame_h, uint32_t padded_w,

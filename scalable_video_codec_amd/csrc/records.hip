@@ -49,12 +49,8 @@ __global__ __launch_bounds__(RecGeom<N>::kThreads) void decode_records_kernel(Re
   const bool active = t < nt;
   float* dst = a.rec + (((size_t)f * a.h + ty * N) * a.w + (t0 + t) * N + j) * 3;  // a wave stores 64 adjacent pixels per row
   if (ty >= a.emit_rows) {  // uniform over the workgroup
-    if (!active) return;
-#pragma unroll
-    for (int y = 0; y < N; ++y) {
-      float* p = dst + (size_t)y * a.w * 3;
-      p[0] = 0.f; p[1] = 0.f; p[2] = 0.f;
-    }
+    const float zeros[3][N] = {};
+    if (active) store_bgr_column<N>(dst, a.w, zeros);
     return;
   }
   // the stretch: nt whole records, contiguous, 4-byte aligned
@@ -65,13 +61,7 @@ __global__ __launch_bounds__(RecGeom<N>::kThreads) void decode_records_kernel(Re
   float dec = 1.f;
   if (active) {
     const uint32_t type = stage[t * G::kRecDw];  // any non-zero word is foreground (libs/decoder.cpp:130-135, codec.hpp:6)
-    const uint32_t tx = (t0 + t) * N, typ = ty * N;
-    bool gazed = false;
-    if (a.gaze) {  // x <= tx < x + w && y <= ty < y + h, without overflow
-      const uint32_t* r = a.gaze + 4ull * f;
-      gazed = tx >= r[0] && tx - r[0] < r[2] && typ >= r[1] && typ - r[1] < r[3];
-    }
-    dec = gazed ? 1.f : (type == 0 ? a.bg : a.fg);
+    dec = gazed(a.gaze, f, (t0 + t) * N, ty * N) ? 1.f : (type == 0 ? a.bg : a.fg);
   }
   float out[3][N];
 #pragma unroll
@@ -98,14 +88,8 @@ __global__ __launch_bounds__(RecGeom<N>::kThreads) void decode_records_kernel(Re
     __syncthreads();  // the next plane reuses rows
   }
   if (!active) return;
-#pragma unroll
-  for (int y = 0; y < N; ++y) {
-    float* p = dst + (size_t)y * a.w * 3;
-    p[0] = out[0][y]; p[1] = out[1][y]; p[2] = out[2][y];
-  }
+  store_bgr_column<N>(dst, a.w, out);
 }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // what the reconstruction kernel takes, as svc_hip_decode_frames (square 8x8 or 16x16 tiles, whole 16-pixel segments), sides up to
 // 32768 for the display pass's u32 coordinates, and the rows of the padded frame the stream holds
@@ -141,8 +125,7 @@ int svc_hip_decode_records_frames(const uint8_t* d_records, uint64_t records_str
   if (rc) return rc;
   SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_records: quant steps must be positive (libs/decoder.cpp:35-47)");
   const bool display = display_w != 0 || display_h != 0;
-  SVC_REQUIRE(!display || (display_w >= 1 && display_w <= frame_w && display_h >= 1 && display_h <= frame_h),
-              "decode_records: display %ux%u must lie within 1x1 .. %ux%u (the padded frame)", display_w, display_h, frame_w, frame_h);
+  if ((rc = validate_display("decode_records", display_w, display_h, frame_w, frame_h))) return rc;
   const uint64_t per = svc_hip_serialized_frame_bytes(frame_w, emit_frame_h, block, block);
   SVC_REQUIRE(records_stride_bytes % 4 == 0 && records_stride_bytes >= per,
               "decode_records: records stride %llu must be a multiple of 4 and at least one frame's %llu B",
@@ -165,9 +148,7 @@ int svc_hip_decode_records_frames(const uint8_t* d_records, uint64_t records_str
     hipLaunchKernelGGL(decode_records_kernel<16>, dim3(a.gx * (frame_h / 16), n_frames), dim3(RecGeom<16>::kThreads), 0, s, a);
   }
   if ((rc = check_launch("decode_records reconstruction")) || !display) return rc;
-  hipLaunchKernelGGL(display_kernel, dim3(div_up(display_w, kDisplayThreads), display_h, n_frames), dim3(kDisplayThreads), 0, s, d_rec,
-                     d_display, frame_w, frame_h, display_w, display_h);
-  return check_launch("decode_records display");
+  return launch_display("decode_records", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 int svc_hip_wire_layout(const svc_wire_header* hdr, uint64_t stream_bytes, uint32_t* emit_frame_h, uint64_t* frame_bytes) {

@@ -36,10 +36,11 @@ inline int fail(int code, const char* fmt, ...) {
     if (!(cond)) return ::svc::fail(SVC_ERR_INVALID_ARG, __VA_ARGS__);          \
   } while (0)
 
-inline int check_launch(const char* what) {
+// `pass` names one launch of an entry point `what` that enqueues several ("pack_levels", "count" -> "pack_levels count")
+inline int check_launch(const char* what, const char* pass = nullptr) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess)
-    return fail(SVC_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
+    return fail(SVC_ERR_HIP, "launch of %s%s%s failed: %s", what, pass ? " " : "", pass ? pass : "", hipGetErrorString(e));
   return SVC_OK;
 }
 
@@ -49,7 +50,8 @@ inline uint64_t pyramid_bytes(uint32_t w, uint32_t h, uint32_t levels) {
   return n;
 }
 
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+__host__ __device__ inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // Per-thread staging of the host-pointer entry points (*_host): one internal stream, one device buffer and one
 // pinned bounce buffer, grown on demand and kept (capi.hip owns the thread_local instance).
