@@ -59,7 +59,7 @@ def _run(cmd: List[str]) -> None:
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "svc_common.hpp"), os.path.join(CSRC, "union_find.hpp"), os.path.join(CSRC, "hbma_search.hpp"), os.path.join(CSRC, "hbma_fused_kernel.hpp"), os.path.join(CSRC, "dct_tables.inc"), os.path.join(CSRC, "idct_core.hpp"), os.path.join(CSRC, "display_core.hpp"), os.path.join(CSRC, "stream_format.hpp"), os.path.join(CSRC, "luma16.hpp"),
+    headers = [os.path.join(CSRC, "svc_common.hpp"), os.path.join(CSRC, "union_find.hpp"), os.path.join(CSRC, "hbma_search.hpp"), os.path.join(CSRC, "hbma_fused_kernel.hpp"), os.path.join(CSRC, "dct_tables.inc"), os.path.join(CSRC, "idct_core.hpp"), os.path.join(CSRC, "quant_core.hpp"), os.path.join(CSRC, "display_core.hpp"), os.path.join(CSRC, "stream_format.hpp"), os.path.join(CSRC, "luma16.hpp"),
                os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h")]
     jobs, objs = [], []
     for s in HIP_SOURCES:
@@ -75,6 +75,19 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     if jobs or not os.path.exists(LIB_HIP):
         _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_HIP, *objs])
     return LIB_HIP
+
+
+QUANT_PROBE_SRC = os.path.join(ROOT, "tests", "quant_probe", "quant_probe.hip")
+LIB_QUANT_PROBE = os.path.join(os.path.dirname(QUANT_PROBE_SRC), "libsvc_quant_probe.so")
+
+
+def build_quant_probe(force: bool = False) -> str:
+    """TEST ONLY: csrc/quant_core.hpp's fused-kernel quantiser on a plain array (tests/test_gpu_transform_exact.py), a small library
+    of its own with the product's flags -- libsvc_hip.so gains no symbol for it."""
+    deps = [QUANT_PROBE_SRC, os.path.join(CSRC, "quant_core.hpp"), os.path.join(CSRC, "svc_common.hpp"), os.path.join(INCLUDE, "svc_hip.h")]
+    if force or not _newer(LIB_QUANT_PROBE, deps):
+        _run([_hipcc(), *HIPCC_FLAGS, "-shared", "-o", LIB_QUANT_PROBE, QUANT_PROBE_SRC])
+    return LIB_QUANT_PROBE
 
 
 STREAM_SRC = os.path.join(CSRC, "host", "stream_encoder.cpp")
@@ -260,6 +273,7 @@ def build_reference_encoder(force: bool = False) -> List[str]:
 
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_hip(force, verbose)
+    build_quant_probe(force)
     build_motion(force)
     build_compat(force)
     build_dropin(force)

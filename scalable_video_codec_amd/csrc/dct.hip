@@ -32,6 +32,7 @@
 #include <algorithm>
 
 #include "luma16.hpp"
+#include "quant_core.hpp"
 #include "svc_common.hpp"
 
 namespace svc {
@@ -121,41 +122,7 @@ __device__ __forceinline__ void dct1d(const T* __restrict__ x, double* __restric
   dct_level<N, N, 0, T>(x, y);
 }
 
-// libs/decoder.cpp:141-143: c /= step; c = std::round(c); c *= step  (all f32)
-__device__ __forceinline__ float quant1(float c, float step) {
-  float q = c / step;  // correctly rounded (hipcc default), as the CPU's divss
-  q = roundf(q);
-  return q * step;
-}
-
-// The same three lines at a fraction of the cost (the IEEE divide expansion + roundf are
-// ~60 issue cycles per coefficient on gfx950 and made the fused kernel VALU-bound):
-//  - division: q0 = c * inv, r = fma(-q0, step, c), q = fma(r, inv, q0) with inv = RN(1/step)
-//    from the host is the correctly rounded quotient (Markstein's correction step) as long
-//    as nothing under/overflows -- coefficients here are 0 or 1e-16 < |c| < 4100;
-//  - std::round (half away from zero) == trunc(q + copysign(0.5 - 2^-25, q)) for every float.
-// Both identities are checked bit-for-bit against the oracle by tests/test_gpu_dct_quant.py.
-__device__ __forceinline__ float quant1_fast(float c, float step, float inv) {
-  const float q0 = c * inv;
-  const float r = __builtin_fmaf(-q0, step, c);
-  float q = __builtin_fmaf(r, inv, q0);
-  q = __builtin_truncf(q + __builtin_copysignf(0.49999997f, q));
-  return q * step;
-}
-
-// Two coefficients of one tile at a time: the same five steps as v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32, which issue
-// like one f32 instruction on gfx950 (copysign and trunc have no packed form) -- 9 instructions per pair instead of 14.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 quant2_fast(f32x2 c, float step, float inv) {
-  const f32x2 s2 = {step, step}, i2 = {inv, inv};
-  const f32x2 q0 = c * i2;
-  const f32x2 r = __builtin_elementwise_fma(-q0, s2, c);
-  f32x2 q = __builtin_elementwise_fma(r, i2, q0);
-  const f32x2 h = {__builtin_copysignf(0.49999997f, q.x), __builtin_copysignf(0.49999997f, q.y)};
-  q = q + h;
-  q = f32x2{__builtin_truncf(q.x), __builtin_truncf(q.y)};
-  return q * s2;
-}
+// the quantiser (quant1, quant1_fast, quant2_fast): quant_core.hpp
 
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
