@@ -11,6 +11,7 @@ Both land next to this file; they are git-ignored but travel to the GPU box.
 from __future__ import annotations
 
 import concurrent.futures as cf
+import glob
 import os
 import shutil
 import subprocess
@@ -50,6 +51,12 @@ def _newer(target: str, deps: List[str]) -> bool:
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
+def _headers() -> List[str]:
+    """Every header a native source may include: listed by directory, so a new one cannot be left out and keep a stale library."""
+    pats = [(CSRC, "*.hpp"), (CSRC, "*.inc"), (os.path.join(CSRC, "host"), "*.hpp"), (INCLUDE, "*.h"), (os.path.join(INCLUDE, "svc"), "*.hpp")]
+    return sorted(f for d, pat in pats for f in glob.glob(os.path.join(d, pat)))
+
+
 def _run(cmd: List[str]) -> None:
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -59,8 +66,7 @@ def _run(cmd: List[str]) -> None:
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "svc_common.hpp"), os.path.join(CSRC, "union_find.hpp"), os.path.join(CSRC, "hbma_search.hpp"), os.path.join(CSRC, "hbma_fused_kernel.hpp"), os.path.join(CSRC, "dct_tables.inc"), os.path.join(CSRC, "idct_core.hpp"), os.path.join(CSRC, "quant_core.hpp"), os.path.join(CSRC, "display_core.hpp"), os.path.join(CSRC, "stream_format.hpp"), os.path.join(CSRC, "luma16.hpp"),
-               os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h")]
+    headers = _headers()
     jobs, objs = [], []
     for s in HIP_SOURCES:
         src, obj = os.path.join(CSRC, s), os.path.join(OBJ, s.replace(".hip", ".o"))
@@ -84,41 +90,46 @@ LIB_QUANT_PROBE = os.path.join(os.path.dirname(QUANT_PROBE_SRC), "libsvc_quant_p
 def build_quant_probe(force: bool = False) -> str:
     """TEST ONLY: csrc/quant_core.hpp's fused-kernel quantiser on a plain array (tests/test_gpu_transform_exact.py), a small library
     of its own with the product's flags -- libsvc_hip.so gains no symbol for it."""
-    deps = [QUANT_PROBE_SRC, os.path.join(CSRC, "quant_core.hpp"), os.path.join(CSRC, "svc_common.hpp"), os.path.join(INCLUDE, "svc_hip.h")]
+    deps = [QUANT_PROBE_SRC] + _headers()
     if force or not _newer(LIB_QUANT_PROBE, deps):
         _run([_hipcc(), *HIPCC_FLAGS, "-shared", "-o", LIB_QUANT_PROBE, QUANT_PROBE_SRC])
     return LIB_QUANT_PROBE
 
 
-STREAM_SRC = os.path.join(CSRC, "host", "stream_encoder.cpp")
-DECODER_SRC = os.path.join(CSRC, "host", "stream_decoder.cpp")
-CLIP_SRC = os.path.join(CSRC, "host", "clip_encoder.cpp")
+HIPCC_HOST_SOURCES = [os.path.join("host", f) for f in ("stream_encoder.cpp", "stream_decoder.cpp", "clip_encoder.cpp")]
 
 
 def build_motion(force: bool = False) -> str:
     """The C++ layer above the C ABI: the reference's motion.hpp entry points (plain C++, g++) and the
     batched host-memory encoder (uses the HIP runtime for buffers, streams and events: hipcc, host only)."""
     srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
-    deps = srcs + [STREAM_SRC, DECODER_SRC, CLIP_SRC, os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(CSRC, "stream_format.hpp"), os.path.join(INCLUDE, "svc_hip.h"), os.path.join(INCLUDE, "svc_clip.h")] + \
-        [os.path.join(INCLUDE, "svc", h) for h in ("motion.hpp", "math.hpp", "types.hpp", "stream_encoder.hpp",
-                                                    "stream_decoder.hpp", "clip_encoder.hpp")]
-    if force or not _newer(LIB_MOTION, deps + [LIB_HIP]):
+    hip_srcs = [os.path.join(CSRC, s) for s in HIPCC_HOST_SOURCES]
+    if force or not _newer(LIB_MOTION, srcs + hip_srcs + _headers() + [LIB_HIP]):
         cxx = shutil.which("g++") or "g++"
-        stream_obj = os.path.join(OBJ, "stream_encoder.o")
-        clip_obj = os.path.join(OBJ, "clip_encoder.o")
-        decoder_obj = os.path.join(OBJ, "stream_decoder.o")
-        _run([_hipcc(), "-std=c++17", "-O2", "-fPIC", "-Wall", f"-I{INCLUDE}", "-c", STREAM_SRC, "-o", stream_obj])
-        _run([_hipcc(), "-std=c++17", "-O2", "-fPIC", "-Wall", f"-I{INCLUDE}", "-c", DECODER_SRC, "-o", decoder_obj])
-        _run([_hipcc(), "-std=c++17", "-O2", "-fPIC", "-Wall", f"-I{INCLUDE}", "-c", CLIP_SRC, "-o", clip_obj])
+        objs = [os.path.join(OBJ, os.path.basename(src).replace(".cpp", ".o")) for src in hip_srcs]
+        for src, obj in zip(hip_srcs, objs):
+            _run([_hipcc(), "-std=c++17", "-O2", "-fPIC", "-Wall", f"-I{INCLUDE}", "-c", src, "-o", obj])
         rocm_lib = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(_hipcc()))), "lib")
         _run([cxx, "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", f"-I{INCLUDE}", f"-I{os.path.join(INCLUDE, 'svc')}",
-              "-o", LIB_MOTION, *srcs, stream_obj, decoder_obj, clip_obj, f"-L{PKG}", "-lsvc_hip", f"-L{rocm_lib}", "-lamdhip64",
+              "-o", LIB_MOTION, *srcs, *objs, f"-L{PKG}", "-lsvc_hip", f"-L{rocm_lib}", "-lamdhip64",
               "-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{rocm_lib}"])
     return LIB_MOTION
 
 
 DROPIN_SRC = os.path.join(ROOT, "tests", "dropin", "dropin_main.cpp")
 REFERENCE_LIBS = os.environ.get("SVC_REFERENCE_DIR", "/root/reference") + "/libs"
+
+
+# Host applications written against the public C++ headers only, one source each, all built by the same line:
+DROPIN_APPS = [
+    "stream_main",          # include/svc/stream_encoder.hpp
+    "stream_levels_main",   # ... with the compact quantised-coefficient output (StreamEncoderConfig::compact): tests/test_gpu_levels.py
+    "stream_budget_main",   # ... and with rate control (compact_budget, SetCompactBudget): tests/test_gpu_levels_budget.py
+    "stream_entropy_main",  # ... and with the entropy-coded output, decoded again by svc::StreamDecoder: tests/test_gpu_entropy.py
+    "stream_decode_main",   # svc::StreamDecoder: stream_levels_main's output -> display frames, tests/test_gpu_decode_levels.py
+    "wire_decode_main",     # svc::StreamDecoder::DecodeWire: a reference stream on stdin -> display frames, tests/test_gpu_decode_records.py
+    "stream_fuzz",          # the encoder at random against itself (batch sizes, depths, entry points, reuse): tests/test_gpu_stream.py
+]
 
 
 def build_dropin(force: bool = False) -> List[str]:
@@ -137,57 +148,13 @@ def build_dropin(force: bool = False) -> List[str]:
             _run([cxx, "-std=c++17", "-O2", "-msse2", f"-I{inc}", *extra, "-o", exe, DROPIN_SRC, f"-L{PKG}",
                   "-lsvc_motion", "-lsvc_hip", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd"])
         out.append(exe)
-    # a host application written against include/svc/stream_encoder.hpp only
-    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_main")
-    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_main.cpp")
-    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp")]):
-        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
-              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
-    out.append(exe)
-    # the same application with the compact quantised-coefficient output (StreamEncoderConfig::compact): tests/test_gpu_levels.py
-    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_levels_main")
-    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_levels_main.cpp")
-    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp")]):
-        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
-              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
-    out.append(exe)
-    # ... and with rate control (StreamEncoderConfig::compact_budget, SetCompactBudget): tests/test_gpu_levels_budget.py
-    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_budget_main")
-    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_budget_main.cpp")
-    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp")]):
-        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
-              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
-    out.append(exe)
-    # ... and with the entropy-coded output (StreamEncoderConfig::entropy), decoded again by svc::StreamDecoder: tests/test_gpu_entropy.py
-    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_entropy_main")
-    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_entropy_main.cpp")
-    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp"),
-                                 os.path.join(INCLUDE, "svc", "stream_decoder.hpp")]):
-        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
-              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
-    out.append(exe)
-    # the decoder's host application (svc::StreamDecoder): stream_levels_main's output -> display frames, tests/test_gpu_decode_levels.py
-    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_decode_main")
-    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_decode_main.cpp")
-    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_decoder.hpp")]):
-        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
-              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
-    out.append(exe)
-    # the wire stream's decoder application (svc::StreamDecoder::DecodeWire): a reference stream on stdin -> display frames,
-    # tests/test_gpu_decode_records.py
-    exe = os.path.join(os.path.dirname(DROPIN_SRC), "wire_decode_main")
-    src = os.path.join(os.path.dirname(DROPIN_SRC), "wire_decode_main.cpp")
-    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_decoder.hpp")]):
-        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
-              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
-    out.append(exe)
-    # ... and one that uses it at random against itself (batch sizes, depths, entry points, reuse): tests/test_gpu_stream.py
-    exe = os.path.join(os.path.dirname(DROPIN_SRC), "stream_fuzz")
-    src = os.path.join(os.path.dirname(DROPIN_SRC), "stream_fuzz.cpp")
-    if force or not _newer(exe, [src, LIB_MOTION, os.path.join(INCLUDE, "svc", "stream_encoder.hpp")]):
-        _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
-              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
-    out.append(exe)
+    for name in DROPIN_APPS:
+        exe = os.path.join(os.path.dirname(DROPIN_SRC), name)
+        src = exe + ".cpp"
+        if force or not _newer(exe, [src, LIB_MOTION]):  # (the library is newer than every header)
+            _run([cxx, "-std=c++17", "-O2", f"-I{INCLUDE}", "-o", exe, src, f"-L{PKG}", "-lsvc_motion", "-lsvc_hip",
+                  f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../scalable_video_codec_amd", "-Wl,--allow-shlib-undefined"])
+        out.append(exe)
     return out
 
 
@@ -199,7 +166,7 @@ def build_compat(force: bool = False) -> str:
     """compat/opencv2: the slice of the OpenCV API the reference's encoder uses, every arithmetic call forwarding to
     include/svc_hip.h (a product-side adapter -- never an oracle).  Plain C++ on top of the C ABI."""
     srcs = [os.path.join(COMPAT, "src", f) for f in ("core.cpp", "imgproc.cpp", "videoio.cpp")]
-    hdrs = [os.path.join(COMPAT, "src", "internal.hpp"), os.path.join(CSRC, "host", "copy_crew.hpp"), os.path.join(INCLUDE, "svc_hip.h")] + \
+    hdrs = [os.path.join(COMPAT, "src", "internal.hpp")] + _headers() + \
         [os.path.join(COMPAT, "opencv2", f) for f in ("core.hpp", "imgproc.hpp", "videoio.hpp", os.path.join("core", "mat.hpp"))]
     if force or not _newer(LIB_COMPAT, srcs + hdrs + [LIB_HIP]):
         cxx = shutil.which("g++") or "g++"

@@ -3,8 +3,6 @@
 // every stage is a call into the C ABI (include/svc_hip.h).
 #include "svc/clip_encoder.hpp"
 
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -12,50 +10,19 @@
 #include <utility>
 #include <vector>
 
+#include "encode_geometry.hpp"
+#include "hip_raii.hpp"
 #include "svc_clip.h"
 
 namespace svc {
 namespace {
 
-void Hip(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("svc::ClipEncoder: ") + what + ": " + hipGetErrorString(e));
-}
-// an event that has not completed yet is "not ready"; any other status is an error of an earlier launch and is reported HERE, where it
-// is first seen, not swallowed as "no news yet"
-bool Ready(hipEvent_t e) {
-  const hipError_t q = hipEventQuery(e);
-  if (q == hipErrorNotReady) return false;
-  Hip(q, "hipEventQuery");
-  return true;
-}
-void Abi(int rc, const char* what) {
-  if (rc) throw std::runtime_error(std::string("svc::ClipEncoder: ") + what + ": " + svc_hip_last_error());
-}
+using namespace host;
 
-// libs/math.hpp:276-283 (ClosestLargerDivisible)
-uint32_t ClosestLargerDivisible(uint32_t dim, uint32_t a, uint32_t b) {
-  while (dim % a != 0 || dim % b != 0) ++dim;
-  return dim;
-}
-
-uint32_t Hash32(uint64_t x) {  // the harness's stateless mixer (synth.py:hash32, stream_encoder.cpp)
-  uint32_t v = (uint32_t)x;
-  v ^= v >> 16; v *= 0x7FEB352Du;
-  v ^= v >> 15; v *= 0x846CA68Bu;
-  v ^= v >> 16;
-  return v;
-}
-
-template <typename T> struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  void Alloc(size_t count) {
-    n = count;
-    Hip(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)), "hipMalloc");
-  }
-  uint64_t bytes() const { return (uint64_t)n * sizeof(T); }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
+constexpr Who kWho{"svc::ClipEncoder"};
+void Hip(hipError_t e, const char* what) { kWho.Hip(e, what); }
+void Abi(int rc, const char* what) { kWho.Abi(rc, what); }
+bool Ready(hipEvent_t e) { return kWho.Ready(e); }
 
 constexpr uint32_t kStages = (uint32_t)Stage::kCount;
 
@@ -73,11 +40,11 @@ Shard PlanShard(uint32_t clip_frames, uint32_t world, uint32_t rank) {
   return s;
 }
 
-struct ClipEncoder::Impl {
+struct ClipEncoder::Impl : EncodeGeometry {
   ClipEncoderConfig c;
   Shard sh;
-  uint32_t pw = 0, ph = 0, mfw = 0, mfh = 0, blocks = 0, iters = 0;
-  uint64_t pyr_stride = 0, frame_bytes = 0, plane_elems = 0, record_bytes = 0, seg_ws_bytes = 0;
+  uint32_t iters = 0;
+  uint64_t record_bytes = 0, seg_ws_bytes = 0;
   // Pipelined schedule: RANSAC + segmentation of a step get `depth` iterations to finish, on `depth` streams (step l on
   // stream l % depth), and the small per-step buffers exist in depth + 2 sets (step s uses set s % nsets).
   static constexpr int kMaxDepth = 3, kSets = kMaxDepth + 2;
@@ -101,7 +68,7 @@ struct ClipEncoder::Impl {
   const uint8_t* step_frames = nullptr;   // frames of the step being submitted (Step: the resident buffer; StepFrames: the caller's)
   // "the frames of step s are no longer read": an event on the main stream behind the step's last transform (which has joined the step's
   // RANSAC + segmentation + redo by then); kRing of them, by step -- a slot reused by a later step stands for the earlier one too (stream order)
-  hipEvent_t e_step[kRing] = {};
+  Event e_step[kRing];
   uint64_t step_last_micro[kRing] = {};  // the micro-step whose transform is the step's last reader
   void MarkStepDone(uint64_t d) {        // called where the transform of micro-step d has just been enqueued
     const uint32_t s = StepOf(d);
@@ -112,12 +79,11 @@ struct ClipEncoder::Impl {
   uint32_t P0(uint64_t m) const { return At(m).p0; }  // first pair of the micro-step's chunk
   uint32_t Pn(uint64_t m) const { return At(m).pn; }  // its pairs
   int Slot(uint64_t m) const { return (int)(m % (uint64_t)nsets); }
-  hipStream_t sM = nullptr, sL[kMaxDepth] = {nullptr, nullptr, nullptr}, sC = nullptr;
   DevBuf<uint8_t> bgr, pyr[2], mask[kSets], seg_ws[kMaxDepth], records[kSets + 1];
   DevBuf<float> mv[kSets], mad[kSets], gm[kSets], rmse[kSets], coeffs[kSets + 1];
   DevBuf<uint8_t> redo_ws[kMaxDepth];  // spec_quant: the foreground list of the step being finished, one per latency stream (as seg_ws)
   DevBuf<uint32_t> count[kSets], types[kSets], samples;
-  hipEvent_t e_pyr[2] = {nullptr, nullptr}, e_halo[2] = {nullptr, nullptr}, e_fork = nullptr, e_join[kSets] = {}, e_rfork = nullptr, e_rmse[kSets] = {};
+  Event e_pyr[2], e_halo[2], e_fork, e_join[kSets], e_rfork, e_rmse[kSets];
   bool halo_recorded[2] = {false, false}, join_pending[kSets] = {}, rmse_pending[kSets] = {};
   bool defer_rmse = false;  // pipelined, large fields: RANSAC leaves its in-order RMSE sum to a later kernel (nothing downstream
                             // needs it): on sC beside the segmentation at world 1, on the latency stream behind it on a multi-rank run
@@ -153,16 +119,12 @@ struct ClipEncoder::Impl {
   bool GrowCoeffSets() {
     if (coeff_sets == rec_sets) return true;
     while (n_dct < n_luma) Iterate(false, last_timed);
-    for (int b = 1; b < rec_sets; ++b) {
-      float* q = nullptr;
-      if (hipMalloc(reinterpret_cast<void**>(&q), std::max<size_t>(coeffs[0].n, 1) * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();  // not sticky: clear it
-        for (int k = 1; k < b; ++k) { (void)hipFree(coeffs[k].p); coeffs[k].p = nullptr; coeffs[k].n = 0; }
-        spec_quant = false;       // two passes from here on
+    for (int b = 1; b < rec_sets; ++b)
+      if (!coeffs[b].TryAlloc(coeffs[0].n)) {
+        for (int k = 1; k < b; ++k) coeffs[k].Free();
+        spec_quant = false;  // two passes from here on
         return false;
       }
-      coeffs[b].p = q; coeffs[b].n = coeffs[0].n;
-    }
     coeff_sets = rec_sets;
     return true;
   }
@@ -186,8 +148,8 @@ struct ClipEncoder::Impl {
   static constexpr uint64_t kIdleRuleMinPixels = 400000000ull;
   static constexpr uint32_t kMaxAutoChunks = 1;              // chunks of a step that follows another one
   DevBuf<uint32_t> fg_dev;
-  uint32_t* fg_host = nullptr;
-  hipEvent_t e_fg[kFgSlots] = {};
+  PinBuf<uint32_t> fg_host;
+  Event e_fg[kFgSlots];
   bool fg_pending[kFgSlots] = {};
   uint64_t fg_blocks[kFgSlots] = {};  // MV blocks the slot's count was taken over (a chunk's)
   uint64_t n_fg = 0;
@@ -198,7 +160,7 @@ struct ClipEncoder::Impl {
     const int slot = (int)(n_fg % kFgSlots);
     if (fg_pending[slot] && !Ready(e_fg[slot])) return;  // eight measurements in flight: skip this one
     Abi(svc_hip_count_foreground(types[Set(m)].p + (uint64_t)P0(m) * blocks, (uint64_t)Pn(m) * blocks, fg_dev.p + slot, st), "svc_hip_count_foreground");
-    Hip(hipMemcpyAsync(fg_host + slot, fg_dev.p + slot, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    Hip(hipMemcpyAsync(fg_host.p + slot, fg_dev.p + slot, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
     Hip(hipEventRecord(e_fg[slot], st), "hipEventRecord");
     fg_pending[slot] = true;
     fg_blocks[slot] = (uint64_t)Pn(m) * blocks;
@@ -209,7 +171,7 @@ struct ClipEncoder::Impl {
       const int slot = (int)((k - 1) % kFgSlots);
       if (!fg_pending[slot]) continue;
       if (!Ready(e_fg[slot])) continue;
-      fg_share = (double)fg_host[slot] / (double)fg_blocks[slot];
+      fg_share = (double)fg_host.p[slot] / (double)fg_blocks[slot];
       break;
     }
   }
@@ -222,7 +184,7 @@ struct ClipEncoder::Impl {
       // allocates the extra coefficient sets and starts their rotation -- then falls INSIDE a step whose set is not set 0), later steps by
       // a fixed pseudo-random sequence over the chunk launches (a strict alternation would lock onto the number of chunks per step)
       const uint32_t s = StepOf(m);
-      yes = s == 0 ? false : s == 1 ? !At(m).first : (Hash32(n_decided * 0x9E3779B1ull) & 1u) != 0;
+      yes = s == 0 ? false : s == 1 ? !At(m).first : (Hash32(n_decided * kHashStride) & 1u) != 0;
     } else if (!yes) {
       PollForeground();
       yes = fg_share >= 0.0 && fg_share <= kSpecMaxShare;
@@ -245,31 +207,13 @@ struct ClipEncoder::Impl {
   }
   bool last_timed = false;  // Flush() times the rest of a step that was submitted timed
   // timing
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> timed[kStages];
-  std::vector<hipEvent_t> event_pool;
+  std::vector<std::pair<Event, Event>> timed[kStages];
+  std::vector<Event> event_pool;
 
-  ~Impl() {
-    for (hipStream_t s : {sM, sL[0], sL[1], sL[2], sC})
-      if (s) (void)hipStreamSynchronize(s);
-    for (auto& v : timed)
-      for (auto& pr : v) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {e_pyr[0], e_pyr[1], e_halo[0], e_halo[1], e_fork, e_rfork, e_join[0], e_join[1], e_join[2], e_join[3], e_join[4],
-                         e_rmse[0], e_rmse[1], e_rmse[2], e_rmse[3], e_rmse[4]})
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : e_fg)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : e_step)
-      if (e) (void)hipEventDestroy(e);
-    if (fg_host) (void)hipHostFree(fg_host);
-    for (hipStream_t s : {sM, sL[0], sL[1], sL[2], sC})
-      if (s) (void)hipStreamDestroy(s);
-  }
-
-  hipEvent_t TimingEvent() {
-    if (!event_pool.empty()) { hipEvent_t e = event_pool.back(); event_pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    Hip(hipEventCreate(&e), "hipEventCreate");
+  Event TimingEvent() {
+    if (event_pool.empty()) return Event(kWho, true);
+    Event e = std::move(event_pool.back());
+    event_pool.pop_back();
     return e;
   }
 
@@ -279,11 +223,11 @@ struct ClipEncoder::Impl {
   template <typename F> void Run(Stage st, hipStream_t stream, bool timing, F&& fn) {
     if (!timing) { fn(); return; }
     timed_pairs[(uint32_t)st] += cur_pairs;
-    hipEvent_t a = TimingEvent(), b = TimingEvent();
+    Event a = TimingEvent(), b = TimingEvent();
     Hip(hipEventRecord(a, stream), "hipEventRecord");
     fn();
     Hip(hipEventRecord(b, stream), "hipEventRecord");
-    timed[(uint32_t)st].emplace_back(a, b);
+    timed[(uint32_t)st].emplace_back(std::move(a), std::move(b));
   }
 
   // pyramid set of micro-step m's step: the pipelined schedule alternates two, the serial one has one
@@ -594,6 +538,10 @@ struct ClipEncoder::Impl {
     MarkStepDone(s);
     ++n_luma; ++n_hbma; ++n_lat; ++n_dct;
   }
+
+  // main, latency (RANSAC + segmentation, one per step in flight) and communication.  Declared LAST: they synchronise and go first, so
+  // every buffer and event above outlives the work that uses it.
+  Stream sM, sL[kMaxDepth], sC;
 };
 
 ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
@@ -613,13 +561,7 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
   }
   if (c.narrow_attempts) m.lat_flags |= SVC_LAUNCH_NO_WIDE;
   if (c.lat_depth > (uint32_t)Impl::kMaxDepth) throw std::runtime_error("svc::ClipEncoder: lat_depth must be 0..3");
-  const uint32_t f = 1u << (c.levels - 1);
-  m.pw = ClosestLargerDivisible(c.width, c.mv_block, f);   // libs/encoder.cpp:164-168
-  m.ph = ClosestLargerDivisible(c.height, c.mv_block, f);
-  m.mfw = m.pw / c.mv_block; m.mfh = m.ph / c.mv_block; m.blocks = m.mfw * m.mfh;
-  m.pyr_stride = (svc_hip_pyramid_bytes(m.pw, m.ph, c.levels) + 255) / 256 * 256;
-  m.frame_bytes = (uint64_t)m.pw * m.ph * 3;
-  m.plane_elems = (uint64_t)m.pw * m.ph;
+  static_cast<EncodeGeometry&>(m) = EncodeGeometry(c.width, c.height, c.levels, c.mv_block, c.mv_block);
   const bool transform = c.dct_block_w != 0;
   m.record_bytes = (c.wire && transform) ? svc_hip_serialized_frame_bytes(m.pw, m.ph, c.dct_block_w, c.dct_block_h) : 0;
   m.iters = svc_hip_ransac_iter_count(c.ransac);
@@ -654,29 +596,28 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
   // only where the chain is long enough to matter: 0.13 ms at 4K against 0.03 ms at 1080p, where it measures neutral
   // (profiles/r03_ab_defer_rmse.txt)
   m.defer_rmse = pipelined && !c.inline_rmse && m.blocks > 8192;
-  Hip(hipStreamCreateWithFlags(&m.sM, hipStreamNonBlocking), "hipStreamCreate");
-  Hip(hipStreamCreateWithFlags(&m.sC, hipStreamNonBlocking), "hipStreamCreate");
+  m.sM = Stream(kWho);
+  m.sC = Stream(kWho);
   if (m.defer_rmse) {
-    Hip(hipEventCreateWithFlags(&m.e_rfork, hipEventDisableTiming), "hipEventCreate");
-    for (int b = 0; b < m.nsets; ++b) Hip(hipEventCreateWithFlags(&m.e_rmse[b], hipEventDisableTiming), "hipEventCreate");
+    m.e_rfork = Event(kWho);
+    for (int b = 0; b < m.nsets; ++b) m.e_rmse[b] = Event(kWho);
   }
-  for (int k = 0; k < m.depth; ++k) Hip(hipStreamCreateWithFlags(&m.sL[k], hipStreamNonBlocking), "hipStreamCreate");
-  for (hipEvent_t* e : {&m.e_pyr[0], &m.e_pyr[1], &m.e_halo[0], &m.e_halo[1], &m.e_fork})
-    Hip(hipEventCreateWithFlags(e, hipEventDisableTiming), "hipEventCreate");
-  for (int b = 0; b < m.nsets; ++b) Hip(hipEventCreateWithFlags(&m.e_join[b], hipEventDisableTiming), "hipEventCreate");
-  for (hipEvent_t& e : m.e_step) Hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-  m.bgr.Alloc((size_t)N * m.frame_bytes);
+  for (int k = 0; k < m.depth; ++k) m.sL[k] = Stream(kWho);
+  for (Event* e : {&m.e_pyr[0], &m.e_pyr[1], &m.e_halo[0], &m.e_halo[1], &m.e_fork}) *e = Event(kWho);
+  for (int b = 0; b < m.nsets; ++b) m.e_join[b] = Event(kWho);
+  for (Event& e : m.e_step) e = Event(kWho);
+  m.bgr.Alloc(kWho, (size_t)N * m.frame_bytes);
   for (int b = 0; b < (pipelined ? 2 : 1); ++b) {
-    m.pyr[b].Alloc((size_t)(N + 1) * m.pyr_stride);  // slot 0 = halo, slots 1..N = own frames
+    m.pyr[b].Alloc(kWho, (size_t)(N + 1) * m.pyr_stride);  // slot 0 = halo, slots 1..N = own frames
     Hip(hipMemset(m.pyr[b].p, 0, (size_t)(N + 1) * m.pyr_stride), "hipMemset");
   }
   for (int b = 0; b < m.nsets; ++b) {
-    m.mv[b].Alloc((size_t)P * m.blocks * 2); m.mad[b].Alloc((size_t)P * m.blocks);
-    m.gm[b].Alloc((size_t)P * 2); m.rmse[b].Alloc(P);
-    m.mask[b].Alloc((size_t)P * m.blocks); m.count[b].Alloc(P); m.types[b].Alloc((size_t)P * m.blocks);
+    m.mv[b].Alloc(kWho, (size_t)P * m.blocks * 2); m.mad[b].Alloc(kWho, (size_t)P * m.blocks);
+    m.gm[b].Alloc(kWho, (size_t)P * 2); m.rmse[b].Alloc(kWho, P);
+    m.mask[b].Alloc(kWho, (size_t)P * m.blocks); m.count[b].Alloc(kWho, P); m.types[b].Alloc(kWho, (size_t)P * m.blocks);
   }
   m.seg_ws_bytes = c.segmentation ? svc_hip_segment_workspace_bytes(m.mfw, m.mfh, std::max(m.cp, 1u), c.segment.attempt_count) : 0;
-  for (int k = 0; k < m.depth; ++k) m.seg_ws[k].Alloc(m.seg_ws_bytes);
+  for (int k = 0; k < m.depth; ++k) m.seg_ws[k].Alloc(kWho, m.seg_ws_bytes);
   m.fused_records = c.wire && c.dct_block_w == c.dct_block_h && c.dct_block_w <= 64 && c.dct_block_w % 2 == 0;
   // one pass over the BGR clip: the tuned record emitter (8x8 / 16x16 on widths that are whole 16-pixel segments) also leaves the luma plane
   m.one_bgr_pass = m.fused_records && !c.two_bgr_passes && transform && (c.dct_block_w == 8 || c.dct_block_w == 16) && m.pw % 16 == 0 &&
@@ -691,31 +632,22 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
   m.rec_sets = (m.one_bgr_pass || m.spec_quant) && pipelined ? (m.nsets + 1 + (int)m.nch - 1) / (int)m.nch : 1;
   if (transform) {
     if (c.wire)
-      for (int b = 0; b < m.rec_sets; ++b) m.records[b].Alloc((size_t)P * m.record_bytes);
+      for (int b = 0; b < m.rec_sets; ++b) m.records[b].Alloc(kWho, (size_t)P * m.record_bytes);
     if (!c.wire || !m.fused_records)
-      m.coeffs[0].Alloc((size_t)P * 3 * m.plane_elems);  // the other rec_sets - 1 sets: Impl::GrowCoeffSets, on the first speculation
+      m.coeffs[0].Alloc(kWho, (size_t)P * 3 * m.plane_elems);  // the other rec_sets - 1 sets: Impl::GrowCoeffSets, on the first speculation
     if (m.spec_quant) {
-      for (int k = 0; k < m.depth; ++k) m.redo_ws[k].Alloc(svc_hip_dct_redo_workspace_bytes(m.cp, m.pw, m.ph, c.mv_block, c.mv_block));
-      m.fg_dev.Alloc(Impl::kFgSlots);
-      Hip(hipHostMalloc(reinterpret_cast<void**>(&m.fg_host), Impl::kFgSlots * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
-      for (hipEvent_t& e : m.e_fg) Hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+      for (int k = 0; k < m.depth; ++k) m.redo_ws[k].Alloc(kWho, svc_hip_dct_redo_workspace_bytes(m.cp, m.pw, m.ph, c.mv_block, c.mv_block));
+      m.fg_dev.Alloc(kWho, Impl::kFgSlots);
+      m.fg_host.Alloc(kWho, Impl::kFgSlots);
+      for (Event& e : m.e_fg) e = Event(kWho);
     }
   }
-  // RANSAC draws: distinct within an iteration, a function of (seed, clip frame, iteration) only --
-  // the generator of stream_encoder.cpp / pipeline.ransac_samples, indexed by the CLIP-wide pair
+  // RANSAC draws, indexed by the CLIP-wide pair
   {
-    const uint64_t g0 = m.sh.first_encoded - 1;
     const size_t n = (size_t)P * m.iters * c.ransac.subset_sz;
     std::vector<uint32_t> h(std::max<size_t>(n, 1));
-    const uint32_t div = std::max<uint32_t>(1, (m.blocks - 1) / std::max<uint32_t>(1, c.ransac.subset_sz));
-    for (size_t i = 0; i < (size_t)P * m.iters; ++i) {
-      const uint64_t idx = g0 * m.iters + i;
-      const uint32_t first = Hash32(idx * 0x9E3779B1ull + c.seed) % m.blocks;
-      const uint32_t step = 1 + Hash32(idx * 0x85EBCA6Bull + c.seed + 1) % div;
-      for (uint32_t k = 0; k < c.ransac.subset_sz; ++k)
-        h[i * c.ransac.subset_sz + k] = (uint32_t)(((uint64_t)first + (uint64_t)step * k) % m.blocks);
-    }
-    m.samples.Alloc(n);
+    FillRansacDraws(h.data(), m.sh.first_encoded - 1, P, m.iters, c.ransac.subset_sz, m.blocks, c.seed);
+    m.samples.Alloc(kWho, n);
     if (n) Hip(hipMemcpy(m.samples.p, h.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy");
   }
   Hip(hipDeviceSynchronize(), "hipDeviceSynchronize");
@@ -827,8 +759,8 @@ void ClipEncoder::Flush() {
 
 void ClipEncoder::Sync() {
   Flush();
-  for (hipStream_t s : {p_->sC, p_->sL[0], p_->sL[1], p_->sL[2], p_->sM})
-    if (s) Hip(hipStreamSynchronize(s), "hipStreamSynchronize");
+  for (const Stream* s : {&p_->sC, &p_->sL[0], &p_->sL[1], &p_->sL[2], &p_->sM})
+    if (*s) Hip(hipStreamSynchronize(*s), "hipStreamSynchronize");
 }
 
 uint64_t ClipEncoder::StagePairs(Stage s) {
@@ -851,7 +783,7 @@ void ClipEncoder::StageTime(Stage s, double* total_ms, uint32_t* launches) {
 void ClipEncoder::ResetTimers() {
   Sync();
   for (auto& v : p_->timed) {
-    for (auto& pr : v) { p_->event_pool.push_back(pr.first); p_->event_pool.push_back(pr.second); }
+    for (auto& pr : v) { p_->event_pool.push_back(std::move(pr.first)); p_->event_pool.push_back(std::move(pr.second)); }
     v.clear();
   }
   for (uint64_t& n : p_->timed_pairs) n = 0;

@@ -1,58 +1,30 @@
-// stream_encoder.cpp -- include/svc/stream_encoder.hpp: buffers, streams and the batch schedule.
+// stream_encoder.cpp -- include/svc/stream_encoder.hpp: buffers and what a batch does on each stream of batch_pipe.hpp's schedule.
 // No arithmetic of the hot path lives here; every stage is a call into the C ABI.
 #include "svc/stream_encoder.hpp"
 
+#include "batch_pipe.hpp"
 #include "copy_crew.hpp"
-
-#include <hip/hip_runtime_api.h>
+#include "encode_geometry.hpp"
 
 #include <sched.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstring>
-#include <mutex>
+#include <memory>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 namespace svc {
 namespace {
 
-void Hip(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("svc::StreamEncoder: ") + what + ": " + hipGetErrorString(e));
-}
-void Abi(int rc, const char* what) {
-  if (rc) throw std::runtime_error(std::string("svc::StreamEncoder: ") + what + ": " + svc_hip_last_error());
-}
+using namespace host;
 
-// libs/math.hpp:276-283 (ClosestLargerDivisible): smallest value >= dim divisible by both
-uint32_t ClosestLargerDivisible(uint32_t dim, uint32_t a, uint32_t b) {
-  while (dim % a != 0 || dim % b != 0) ++dim;
-  return dim;
-}
-
-uint32_t Hash32(uint64_t x) {  // the harness's stateless mixer (scalable_video_codec_amd/synth.py:hash32)
-  uint32_t v = (uint32_t)x;
-  v ^= v >> 16; v *= 0x7FEB352Du;
-  v ^= v >> 15; v *= 0x846CA68Bu;
-  v ^= v >> 16;
-  return v;
-}
-
-template <typename T> struct DevBuf {
-  T* p = nullptr;
-  void Alloc(size_t n) { Hip(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)), "hipMalloc"); }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-template <typename T> struct PinBuf {
-  T* p = nullptr;
-  void Alloc(size_t n) { Hip(hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault), "hipHostMalloc"); }
-  ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
+constexpr Who kWho{"svc::StreamEncoder"};
+void Hip(hipError_t e, const char* what) { kWho.Hip(e, what); }
+void Abi(int rc, const char* what) { kWho.Abi(rc, what); }
 
 struct Slot {
   DevBuf<uint8_t> bgr, pyr, mask, seg_ws, records, packed, pack_ws, coded, entropy_ws;
@@ -67,39 +39,26 @@ struct Slot {
   PinBuf<uint8_t> pin_in, pin_records;
   PinBuf<float> pin_mv, pin_gm, pin_coeffs;
   PinBuf<uint32_t> pin_types;
-  hipEvent_t h2d_done = nullptr, compute_done = nullptr, d2h_done = nullptr;
-  hipEvent_t t_in[2] = {}, t_k[2] = {}, t_out[2] = {};  // EncodeStats: start / end of the batch's work on each stream
-  uint64_t h2d_bytes = 0, d2h_bytes = 0;
-  bool busy = false;
   uint32_t frames = 0;  // source frames resident in bgr (the last one carries into the next batch)
   uint32_t encoded = 0, first = 0;
-  ~Slot() {
-    for (hipEvent_t e : {h2d_done, compute_done, d2h_done, t_in[0], t_in[1], t_k[0], t_k[1], t_out[0], t_out[1]})
-      if (e) (void)hipEventDestroy(e);
-  }
 };
 
 }  // namespace
 
-struct StreamEncoder::Impl {
+struct StreamEncoder::Impl : EncodeGeometry {
   StreamEncoderConfig c;
-  uint32_t pw = 0, ph = 0, mfw = 0, mfh = 0, blocks = 0, iters = 0;
+  uint32_t iters = 0;
   uint32_t bw = 0, bh = 0, tw = 0, th = 0;  // MV block and transform block sides
-  uint64_t pyr_stride = 0, frame_bytes = 0, plane_elems = 0, record_bytes = 0, seg_ws_bytes = 0;
+  uint64_t record_bytes = 0, seg_ws_bytes = 0;
   uint64_t packed_bytes = 0, pack_ws_bytes = 0;  // compact: worst case of a batch, pack workspace
   uint64_t coded_bytes = 0, entropy_ws_bytes = 0; // entropy: worst case of a coded batch, coder workspace
   bool budgeted = false;                          // compact_budget != 0: rate control
   std::atomic<uint32_t> budget{0};                // bytes per frame of the next batch staged (SetCompactBudget)
-  std::vector<std::unique_ptr<Slot>> slots;
-  hipStream_t s_in = nullptr, s_compute = nullptr, s_out = nullptr;
+  std::vector<std::unique_ptr<Slot>> slots;       // the buffers of the pipe's slots
   bool fused_records = false;  // wire: the transform kernel emits the records itself
   std::unique_ptr<CopyCrew> crew;
+  std::unique_ptr<BatchPipe> pipe;  // (after the buffers: its streams synchronise before those go)
   EncodeStats stats;
-
-  ~Impl() {
-    for (hipStream_t s : {s_in, s_compute, s_out})
-      if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-  }
 };
 
 StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
@@ -108,17 +67,11 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   const StreamEncoderConfig& c = m.c;
   if (!c.width || !c.height || !c.levels || !c.mv_block || c.batch == 0 || c.depth < 3)
     throw std::runtime_error("svc::StreamEncoder: invalid configuration");
-  const uint32_t f = 1u << (c.levels - 1);
   m.bw = c.mv_block; m.bh = c.mv_block_h ? c.mv_block_h : c.mv_block;
   m.tw = c.dct_block; m.th = c.dct_block_h ? c.dct_block_h : c.dct_block;
   if (!m.tw || !m.th) throw std::runtime_error("svc::StreamEncoder: invalid configuration");
   if (c.compact && c.wire) throw std::runtime_error("svc::StreamEncoder: compact is a form of the quantised planes, not of the wire records");
-  m.pw = ClosestLargerDivisible(c.width, m.bw, f);   // libs/encoder.cpp:164-168
-  m.ph = ClosestLargerDivisible(c.height, m.bh, f);
-  m.mfw = m.pw / m.bw; m.mfh = m.ph / m.bh; m.blocks = m.mfw * m.mfh;
-  m.pyr_stride = (svc_hip_pyramid_bytes(m.pw, m.ph, c.levels) + 255) / 256 * 256;  // the kernels ask for 16-byte aligned pyramids
-  m.frame_bytes = (uint64_t)m.pw * m.ph * 3;
-  m.plane_elems = (uint64_t)m.pw * m.ph;
+  static_cast<EncodeGeometry&>(m) = EncodeGeometry(c.width, c.height, c.levels, m.bw, m.bh);
   // reference_stream: SerializeEncodedFrame over the UNPADDED size (libs/encoder.cpp:647-650); the transform kernel emits that
   // directly when the padded width IS the frame's width (emit height = the unpadded one); with a padded width the row
   // stride quirk needs the planes first and svc_hip_serialize_frames behind them
@@ -149,40 +102,34 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     if (!m.packed_bytes || !m.pack_ws_bytes) throw std::runtime_error("svc::StreamEncoder: no compact stream for this geometry");
   }
   m.crew.reset(new CopyCrew(std::min<uint32_t>(c.copy_threads ? c.copy_threads - 1 : 0, 15)));
-  Hip(hipStreamCreateWithFlags(&m.s_in, hipStreamNonBlocking), "hipStreamCreate");
-  Hip(hipStreamCreateWithFlags(&m.s_compute, hipStreamNonBlocking), "hipStreamCreate");
-  Hip(hipStreamCreateWithFlags(&m.s_out, hipStreamNonBlocking), "hipStreamCreate");
+  m.pipe.reset(new BatchPipe(kWho, c.depth));
   const size_t B = c.batch;
   for (uint32_t i = 0; i < c.depth; ++i) {
     std::unique_ptr<Slot> s(new Slot);
-    s->bgr.Alloc((B + 1) * m.frame_bytes);
+    s->bgr.Alloc(kWho, (B + 1) * m.frame_bytes);
     Hip(hipMemset(s->bgr.p, 0, (B + 1) * m.frame_bytes), "hipMemset");  // a short last batch runs the kernels over the whole slot
-    s->pyr.Alloc((B + 1) * m.pyr_stride);
-    s->mv.Alloc(B * m.blocks * 2); s->mad.Alloc(B * m.blocks);
-    s->gm.Alloc(B * 2); s->rmse.Alloc(B);
-    s->mask.Alloc(B * m.blocks); s->count.Alloc(B); s->types.Alloc(B * m.blocks);
-    s->seg_ws.Alloc(m.seg_ws_bytes);
-    s->pin_in.Alloc((B + 1) * m.frame_bytes);
+    s->pyr.Alloc(kWho, (B + 1) * m.pyr_stride);
+    s->mv.Alloc(kWho, B * m.blocks * 2); s->mad.Alloc(kWho, B * m.blocks);
+    s->gm.Alloc(kWho, B * 2); s->rmse.Alloc(kWho, B);
+    s->mask.Alloc(kWho, B * m.blocks); s->count.Alloc(kWho, B); s->types.Alloc(kWho, B * m.blocks);
+    s->seg_ws.Alloc(kWho, m.seg_ws_bytes);
+    s->pin_in.Alloc(kWho, (B + 1) * m.frame_bytes);
     std::memset(s->pin_in.p, 0, (B + 1) * m.frame_bytes);  // the padding border stays zero (encoder.cpp:459-461)
-    s->pin_mv.Alloc(B * m.blocks * 2); s->pin_gm.Alloc(B * 2); s->pin_types.Alloc(B * m.blocks);
-    s->samples.Alloc(B * m.iters * c.ransac.subset_sz); s->pin_samples.Alloc(B * m.iters * c.ransac.subset_sz);
+    s->pin_mv.Alloc(kWho, B * m.blocks * 2); s->pin_gm.Alloc(kWho, B * 2); s->pin_types.Alloc(kWho, B * m.blocks);
+    s->samples.Alloc(kWho, B * m.iters * c.ransac.subset_sz); s->pin_samples.Alloc(kWho, B * m.iters * c.ransac.subset_sz);
     Hip(hipMemset(s->samples.p, 0, std::max<size_t>(B * m.iters * c.ransac.subset_sz, 1) * sizeof(uint32_t)), "hipMemset");
-    if (c.wire) { s->records.Alloc(B * m.record_bytes); s->pin_records.Alloc(B * m.record_bytes); }
-    if (!c.wire || !m.fused_records) s->coeffs.Alloc(B * 3 * m.plane_elems);
-    if (!c.wire && !c.compact) s->pin_coeffs.Alloc(B * 3 * m.plane_elems);
+    if (c.wire) { s->records.Alloc(kWho, B * m.record_bytes); s->pin_records.Alloc(kWho, B * m.record_bytes); }
+    if (!c.wire || !m.fused_records) s->coeffs.Alloc(kWho, B * 3 * m.plane_elems);
+    if (!c.wire && !c.compact) s->pin_coeffs.Alloc(kWho, B * 3 * m.plane_elems);
     if (c.compact) {
-      s->packed.Alloc(m.packed_bytes); s->pack_ws.Alloc(m.pack_ws_bytes); s->offsets.Alloc(B + 1);
-      s->pin_packed.Alloc(c.entropy ? m.coded_bytes : m.packed_bytes); s->pin_offsets.Alloc(B + 1);
+      s->packed.Alloc(kWho, m.packed_bytes); s->pack_ws.Alloc(kWho, m.pack_ws_bytes); s->offsets.Alloc(kWho, B + 1);
+      s->pin_packed.Alloc(kWho, c.entropy ? m.coded_bytes : m.packed_bytes); s->pin_offsets.Alloc(kWho, B + 1);
       if (c.entropy) {
-        s->coded.Alloc(m.coded_bytes); s->entropy_ws.Alloc(m.entropy_ws_bytes); s->coded_offsets.Alloc(B + 1);
-        s->entropy_status.Alloc(B); s->pin_entropy_status.Alloc(B);
+        s->coded.Alloc(kWho, m.coded_bytes); s->entropy_ws.Alloc(kWho, m.entropy_ws_bytes); s->coded_offsets.Alloc(kWho, B + 1);
+        s->entropy_status.Alloc(kWho, B); s->pin_entropy_status.Alloc(kWho, B);
       }
     }
-    if (m.budgeted) { s->budget.Alloc(B); s->choice.Alloc(B); s->pin_budget.Alloc(B); s->pin_choice.Alloc(B); }
-    Hip(hipEventCreateWithFlags(&s->h2d_done, hipEventDisableTiming), "hipEventCreate");
-    Hip(hipEventCreateWithFlags(&s->compute_done, hipEventDisableTiming), "hipEventCreate");
-    Hip(hipEventCreateWithFlags(&s->d2h_done, hipEventDisableTiming), "hipEventCreate");
-    for (hipEvent_t* e : {&s->t_in[0], &s->t_in[1], &s->t_k[0], &s->t_k[1], &s->t_out[0], &s->t_out[1]}) Hip(hipEventCreate(e), "hipEventCreate");
+    if (m.budgeted) { s->budget.Alloc(kWho, B); s->choice.Alloc(kWho, B); s->pin_budget.Alloc(kWho, B); s->pin_choice.Alloc(kWho, B); }
     m.slots.push_back(std::move(s));
   }
 }
@@ -224,17 +171,9 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     cpu_set_t set;
     st.host_cores = sched_getaffinity(0, sizeof(set), &set) == 0 ? (uint32_t)CPU_COUNT(&set) : 0;
   }
-  const Clock::time_point t_start = Clock::now();
 
-  auto deliver = [&](Slot& s) {
-    Clock::time_point t0 = Clock::now();
-    Hip(hipEventSynchronize(s.d2h_done), "hipEventSynchronize");
-    st.deliver_wait_ms += ms_since(t0);
-    float ms = 0;
-    Hip(hipEventElapsedTime(&ms, s.t_in[0], s.t_in[1]), "hipEventElapsedTime"); st.h2d_ms += ms;
-    Hip(hipEventElapsedTime(&ms, s.t_k[0], s.t_k[1]), "hipEventElapsedTime"); st.kernels_ms += ms;
-    Hip(hipEventElapsedTime(&ms, s.t_out[0], s.t_out[1]), "hipEventElapsedTime"); st.d2h_ms += ms;
-    st.h2d_bytes += s.h2d_bytes; st.d2h_bytes += s.d2h_bytes;
+  m.pipe->Begin([&](uint32_t slot) {
+    Slot& s = *m.slots[slot];
     if (c.compact) st.d2h_bytes += s.pin_offsets.p[s.encoded];  // the drain moved exactly the used bytes
     if (c.entropy)  // the input is the pack's own output: a flagged frame is a bug, not a stream to pass on
       for (uint32_t i = 0; i < s.encoded; ++i)
@@ -243,8 +182,8 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
                                    " with status " + std::to_string(s.pin_entropy_status.p[i]));
     if (m.budgeted)
       for (uint32_t i = 0; i < s.encoded; ++i) st.over_budget_frames += s.pin_choice.p[i] >> 31;
-    ++st.batches; st.encoded_frames += s.encoded;
-    t0 = Clock::now();
+    st.encoded_frames += s.encoded;
+    const Clock::time_point t0 = Clock::now();
     EncodedBatch b;
     b.header = (c.wire && s.first == 1) ? &header : nullptr;
     b.first_frame = s.first; b.count = s.encoded;
@@ -259,20 +198,14 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     b.record_bytes = m.record_bytes;
     sink(b);
     st.sink_ms += ms_since(t0);
-  };
+  });
 
-  std::vector<Slot*> pending;
-  Slot* prev = nullptr;
-  uint32_t first = 1, k = 0;
+  const Slot* prev = nullptr;
+  uint32_t first = 1;
   bool ended = false;
   while (!ended) {
-    Slot& s = *m.slots[k % c.depth];
-    if (s.busy) {
-      const Clock::time_point t0 = Clock::now();
-      Hip(hipEventSynchronize(s.d2h_done), "hipEventSynchronize");
-      st.slot_wait_ms += ms_since(t0);
-      s.busy = false;
-    }
+    const uint32_t slot = m.pipe->Acquire();
+    Slot& s = *m.slots[slot];
     const Clock::time_point t_stage = Clock::now();
     const bool carry = prev != nullptr;
     const uint32_t want = carry ? B : B + 1, off = carry ? 1 : 0;
@@ -286,123 +219,104 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     }
     const uint32_t encoded = carry ? n_new : (n_new ? n_new - 1 : 0);
     if (encoded == 0) break;  // the clip ended on a batch boundary (or had a single frame): nothing left to encode
-    Hip(hipEventRecord(s.t_in[0], m.s_in), "hipEventRecord");
-    s.h2d_bytes = (uint64_t)n_new * m.frame_bytes;
-    Hip(hipMemcpyAsync(s.bgr.p + (size_t)off * m.frame_bytes, s.pin_in.p + (size_t)off * m.frame_bytes,
-                       (size_t)n_new * m.frame_bytes, hipMemcpyHostToDevice, m.s_in), "hipMemcpyAsync H2D");
-    if (carry) {
-      Hip(hipStreamWaitEvent(m.s_in, prev->h2d_done, 0), "hipStreamWaitEvent");
-      Hip(hipMemcpyAsync(s.bgr.p, prev->bgr.p + (size_t)(prev->frames - 1) * m.frame_bytes, m.frame_bytes,
-                         hipMemcpyDeviceToDevice, m.s_in), "hipMemcpyAsync D2D");
-    }
-    // RANSAC draws of the batch's pairs: distinct within an iteration, a function of (seed, clip-wide pair, iteration) only
-    // (same generator as the harness: pipeline.ransac_samples), so the clip encodes the same whatever the batch size
     const uint32_t g0 = first - 1;  // clip-wide index of the batch's first pair
-    {
-      const uint32_t div = std::max<uint32_t>(1, (m.blocks - 1) / std::max<uint32_t>(1, c.ransac.subset_sz));
-      for (size_t q = 0; q < (size_t)encoded * m.iters; ++q) {
-        const uint64_t idx = (uint64_t)g0 * m.iters + q;
-        const uint32_t f0 = Hash32(idx * 0x9E3779B1ull + c.seed) % m.blocks;
-        const uint32_t step = 1 + Hash32(idx * 0x85EBCA6Bull + c.seed + 1) % div;
-        for (uint32_t j = 0; j < c.ransac.subset_sz; ++j)
-          s.pin_samples.p[q * c.ransac.subset_sz + j] = (uint32_t)(((uint64_t)f0 + (uint64_t)step * j) % m.blocks);
-      }
+
+    auto h2d = [&](hipStream_t si) -> uint64_t {
+      Hip(hipMemcpyAsync(s.bgr.p + (size_t)off * m.frame_bytes, s.pin_in.p + (size_t)off * m.frame_bytes,
+                         (size_t)n_new * m.frame_bytes, hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D");
+      if (carry)  // the previous batch's last frame is this one's first: behind that batch's H2D, which this stream carried too
+        Hip(hipMemcpyAsync(s.bgr.p, prev->bgr.p + (size_t)(prev->frames - 1) * m.frame_bytes, m.frame_bytes,
+                           hipMemcpyDeviceToDevice, si), "hipMemcpyAsync D2D");
+      FillRansacDraws(s.pin_samples.p, g0, encoded, m.iters, c.ransac.subset_sz, m.blocks, c.seed);
       Hip(hipMemcpyAsync(s.samples.p, s.pin_samples.p, (size_t)encoded * m.iters * c.ransac.subset_sz * sizeof(uint32_t),
-                         hipMemcpyHostToDevice, m.s_in), "hipMemcpyAsync samples");
-    }
-    if (m.budgeted) {  // the budget as it stands now, for every frame of this batch (SetCompactBudget's rule)
-      const uint32_t bytes = m.budget.load();
-      std::fill(s.pin_budget.p, s.pin_budget.p + encoded, bytes);
-      Hip(hipMemcpyAsync(s.budget.p, s.pin_budget.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyHostToDevice, m.s_in),
-          "hipMemcpyAsync budget");
-    }
-    Hip(hipEventRecord(s.t_in[1], m.s_in), "hipEventRecord");
-    Hip(hipEventRecord(s.h2d_done, m.s_in), "hipEventRecord");
-    s.frames = off + n_new;
-    st.staging_ms += ms_since(t_stage);
-
-    // the kernels: always B pairs (a short last batch re-encodes stale frames past its end and drops them)
-    Hip(hipStreamWaitEvent(m.s_compute, s.h2d_done, 0), "hipStreamWaitEvent");
-    Hip(hipEventRecord(s.t_k[0], m.s_compute), "hipEventRecord");
-    Abi(svc_hip_luma_pyramid_frames(s.bgr.p, m.frame_bytes, B + 1, m.pw, m.ph, c.levels, s.pyr.p, m.pyr_stride, m.s_compute),
-        "svc_hip_luma_pyramid_frames");
-    Abi(svc_hip_hbma_pairs(s.pyr.p, s.pyr.p + m.pyr_stride, m.pyr_stride, B, c.levels, m.pw, m.ph, c.search_range,
-                           m.bw, m.bh, s.mv.p, s.mad.p, SVC_HBMA_AUTO, m.s_compute), "svc_hip_hbma_pairs");
-    Hip(hipMemsetAsync(s.gm.p, 0, (size_t)B * 2 * sizeof(float), m.s_compute), "hipMemsetAsync");
-    Abi(svc_hip_ransac_frames(s.mv.p, m.blocks, B, c.ransac, s.samples.p, m.iters,
-                              s.gm.p, s.rmse.p, s.mask.p, s.count.p, m.s_compute), "svc_hip_ransac_frames");
-    Abi(svc_hip_segment_frames(s.mask.p, s.mv.p, m.mfw, m.mfh, B, m.bw, m.bh, c.segment,
-                               c.seed * 1000003ull + g0, s.seg_ws.p, m.seg_ws_bytes, s.types.p, m.s_compute),
-        "svc_hip_segment_frames");
-    const uint8_t* enc_bgr = s.bgr.p + m.frame_bytes;  // encoded frame of pair p is source frame p + 1
-    if (c.wire && m.fused_records) {
-      Abi(svc_hip_dct_records_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh,
-                                     0, 0, c.reference_stream ? c.height : m.ph, s.records.p, m.record_bytes, m.s_compute),  // raw: see the header
-          "svc_hip_dct_records_frames");
-    } else if (c.wire) {  // the reference encoder's stream on a padded width, or non-square tiles: planes, then the serialiser with the reference's own arguments
-      Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, m.s_compute), "svc_hip_dct_frames");
-      const uint32_t sw = c.reference_stream ? c.width : m.pw, sh = c.reference_stream ? c.height : m.ph;
-      Abi(svc_hip_serialize_frames(s.coeffs.p, m.plane_elems, B, s.types.p, sw, sh, m.tw, m.th, m.mfw, m.mfh,
-                                   m.bw, m.bh, s.records.p, m.record_bytes, m.s_compute), "svc_hip_serialize_frames");
-    } else if (m.budgeted) {  // raw planes; the pack picks each frame's steps from its budget
-      Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, m.s_compute), "svc_hip_dct_frames");
-      Abi(svc_hip_pack_levels_budget_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.compact_ladder.data(),
-                                            (uint32_t)c.compact_ladder.size(), s.budget.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
-                                            m.packed_bytes, s.offsets.p, s.choice.p, m.s_compute),
-          "svc_hip_pack_levels_budget_frames");
-    } else {
-      Abi(svc_hip_dct_quant_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.types.p, m.bw,
-                                   m.bh, c.fg_step, c.bg_step, s.coeffs.p, m.s_compute), "svc_hip_dct_quant_frames");
-      if (c.compact)
-        Abi(svc_hip_pack_levels_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step,
-                                       s.pack_ws.p, m.pack_ws_bytes, s.packed.p, m.packed_bytes, s.offsets.p, m.s_compute),
-            "svc_hip_pack_levels_frames");
-      if (c.entropy)
-        Abi(svc_hip_entropy_encode_frames(s.packed.p, m.packed_bytes, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
-                                          s.entropy_ws.p, m.entropy_ws_bytes, s.coded.p, m.coded_bytes, s.coded_offsets.p,
-                                          s.entropy_status.p, m.s_compute),
-            "svc_hip_entropy_encode_frames");
-    }
-    Hip(hipEventRecord(s.t_k[1], m.s_compute), "hipEventRecord");
-    Hip(hipEventRecord(s.compute_done, m.s_compute), "hipEventRecord");
-
-    Hip(hipStreamWaitEvent(m.s_out, s.compute_done, 0), "hipStreamWaitEvent");
-    Hip(hipEventRecord(s.t_out[0], m.s_out), "hipEventRecord");
-    s.d2h_bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : c.compact ? 0 : 3 * m.plane_elems * sizeof(float)));
-    if (c.compact) s.d2h_bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t);  // + the stream's used bytes, known at delivery
-    if (m.budgeted || c.entropy) s.d2h_bytes += (uint64_t)encoded * sizeof(uint32_t);  // the choices, or the coder's statuses
-    Hip(hipMemcpyAsync(s.pin_mv.p, s.mv.p, (size_t)encoded * m.blocks * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H mv");
-    Hip(hipMemcpyAsync(s.pin_types.p, s.types.p, (size_t)encoded * m.blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "D2H types");
-    Hip(hipMemcpyAsync(s.pin_gm.p, s.gm.p, (size_t)encoded * 2 * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H gm");
-    if (c.wire)
-      Hip(hipMemcpyAsync(s.pin_records.p, s.records.p, (size_t)encoded * m.record_bytes, hipMemcpyDeviceToHost, m.s_out), "D2H records");
-    else if (c.entropy) {  // the coded frames, drained the same way, their offsets and the coder's statuses
-      Abi(svc_hip_entropy_drain(s.coded.p, s.coded_offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_packed.p, m.coded_bytes,
-                                m.s_out), "svc_hip_entropy_drain");
-      Hip(hipMemcpyAsync(s.pin_offsets.p, s.coded_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, m.s_out),
-          "D2H offsets");
-      Hip(hipMemcpyAsync(s.pin_entropy_status.p, s.entropy_status.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out),
-          "D2H entropy status");
-    } else if (c.compact) {  // the used bytes only: the count is on the device, the drain kernel reads it there
-      Abi(svc_hip_levels_drain(s.packed.p, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_packed.p, m.packed_bytes,
-                               m.s_out), "svc_hip_levels_drain");
-      Hip(hipMemcpyAsync(s.pin_offsets.p, s.offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, m.s_out),
-          "D2H offsets");
-      if (m.budgeted)
-        Hip(hipMemcpyAsync(s.pin_choice.p, s.choice.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, m.s_out), "D2H choice");
-    } else
-      Hip(hipMemcpyAsync(s.pin_coeffs.p, s.coeffs.p, (size_t)encoded * 3 * m.plane_elems * sizeof(float), hipMemcpyDeviceToHost, m.s_out), "D2H coeffs");
-    Hip(hipEventRecord(s.t_out[1], m.s_out), "hipEventRecord");
-    Hip(hipEventRecord(s.d2h_done, m.s_out), "hipEventRecord");
-
-    s.busy = true; s.encoded = encoded; s.first = first;
-    pending.push_back(&s);
-    prev = &s; first += encoded; ++k;
-    if (pending.size() >= c.depth - 1) { deliver(*pending.front()); pending.erase(pending.begin()); }
+                         hipMemcpyHostToDevice, si), "hipMemcpyAsync samples");
+      if (m.budgeted) {  // the budget as it stands now, for every frame of this batch (SetCompactBudget's rule)
+        const uint32_t bytes = m.budget.load();
+        std::fill(s.pin_budget.p, s.pin_budget.p + encoded, bytes);
+        Hip(hipMemcpyAsync(s.budget.p, s.pin_budget.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyHostToDevice, si),
+            "hipMemcpyAsync budget");
+      }
+      st.staging_ms += ms_since(t_stage);
+      return (uint64_t)n_new * m.frame_bytes;
+    };
+    // always B pairs (a short last batch re-encodes stale frames past its end and drops them)
+    auto kernels = [&](hipStream_t sk) {
+      Abi(svc_hip_luma_pyramid_frames(s.bgr.p, m.frame_bytes, B + 1, m.pw, m.ph, c.levels, s.pyr.p, m.pyr_stride, sk),
+          "svc_hip_luma_pyramid_frames");
+      Abi(svc_hip_hbma_pairs(s.pyr.p, s.pyr.p + m.pyr_stride, m.pyr_stride, B, c.levels, m.pw, m.ph, c.search_range,
+                             m.bw, m.bh, s.mv.p, s.mad.p, SVC_HBMA_AUTO, sk), "svc_hip_hbma_pairs");
+      Hip(hipMemsetAsync(s.gm.p, 0, (size_t)B * 2 * sizeof(float), sk), "hipMemsetAsync");
+      Abi(svc_hip_ransac_frames(s.mv.p, m.blocks, B, c.ransac, s.samples.p, m.iters,
+                                s.gm.p, s.rmse.p, s.mask.p, s.count.p, sk), "svc_hip_ransac_frames");
+      Abi(svc_hip_segment_frames(s.mask.p, s.mv.p, m.mfw, m.mfh, B, m.bw, m.bh, c.segment,
+                                 c.seed * 1000003ull + g0, s.seg_ws.p, m.seg_ws_bytes, s.types.p, sk),
+          "svc_hip_segment_frames");
+      const uint8_t* enc_bgr = s.bgr.p + m.frame_bytes;  // encoded frame of pair p is source frame p + 1
+      if (c.wire && m.fused_records) {
+        Abi(svc_hip_dct_records_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh,
+                                       0, 0, c.reference_stream ? c.height : m.ph, s.records.p, m.record_bytes, sk),  // raw: see the header
+            "svc_hip_dct_records_frames");
+      } else if (c.wire) {  // the reference encoder's stream on a padded width, or non-square tiles: planes, then the serialiser with the reference's own arguments
+        Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, sk), "svc_hip_dct_frames");
+        const uint32_t sw = c.reference_stream ? c.width : m.pw, sh = c.reference_stream ? c.height : m.ph;
+        Abi(svc_hip_serialize_frames(s.coeffs.p, m.plane_elems, B, s.types.p, sw, sh, m.tw, m.th, m.mfw, m.mfh,
+                                     m.bw, m.bh, s.records.p, m.record_bytes, sk), "svc_hip_serialize_frames");
+      } else if (m.budgeted) {  // raw planes; the pack picks each frame's steps from its budget
+        Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, sk), "svc_hip_dct_frames");
+        Abi(svc_hip_pack_levels_budget_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.compact_ladder.data(),
+                                              (uint32_t)c.compact_ladder.size(), s.budget.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
+                                              m.packed_bytes, s.offsets.p, s.choice.p, sk),
+            "svc_hip_pack_levels_budget_frames");
+      } else {
+        Abi(svc_hip_dct_quant_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.types.p, m.bw,
+                                     m.bh, c.fg_step, c.bg_step, s.coeffs.p, sk), "svc_hip_dct_quant_frames");
+        if (c.compact)
+          Abi(svc_hip_pack_levels_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step,
+                                         s.pack_ws.p, m.pack_ws_bytes, s.packed.p, m.packed_bytes, s.offsets.p, sk),
+              "svc_hip_pack_levels_frames");
+        if (c.entropy)
+          Abi(svc_hip_entropy_encode_frames(s.packed.p, m.packed_bytes, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
+                                            s.entropy_ws.p, m.entropy_ws_bytes, s.coded.p, m.coded_bytes, s.coded_offsets.p,
+                                            s.entropy_status.p, sk),
+              "svc_hip_entropy_encode_frames");
+      }
+    };
+    auto d2h = [&](hipStream_t so) -> uint64_t {
+      uint64_t bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : c.compact ? 0 : 3 * m.plane_elems * sizeof(float)));
+      if (c.compact) bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t);  // + the stream's used bytes, known at delivery
+      if (m.budgeted || c.entropy) bytes += (uint64_t)encoded * sizeof(uint32_t);  // the choices, or the coder's statuses
+      Hip(hipMemcpyAsync(s.pin_mv.p, s.mv.p, (size_t)encoded * m.blocks * 2 * sizeof(float), hipMemcpyDeviceToHost, so), "D2H mv");
+      Hip(hipMemcpyAsync(s.pin_types.p, s.types.p, (size_t)encoded * m.blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "D2H types");
+      Hip(hipMemcpyAsync(s.pin_gm.p, s.gm.p, (size_t)encoded * 2 * sizeof(float), hipMemcpyDeviceToHost, so), "D2H gm");
+      if (c.wire)
+        Hip(hipMemcpyAsync(s.pin_records.p, s.records.p, (size_t)encoded * m.record_bytes, hipMemcpyDeviceToHost, so), "D2H records");
+      else if (c.entropy) {  // the coded frames, drained the same way, their offsets and the coder's statuses
+        Abi(svc_hip_entropy_drain(s.coded.p, s.coded_offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_packed.p, m.coded_bytes,
+                                  so), "svc_hip_entropy_drain");
+        Hip(hipMemcpyAsync(s.pin_offsets.p, s.coded_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, so),
+            "D2H offsets");
+        Hip(hipMemcpyAsync(s.pin_entropy_status.p, s.entropy_status.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, so),
+            "D2H entropy status");
+      } else if (c.compact) {  // the used bytes only: the count is on the device, the drain kernel reads it there
+        Abi(svc_hip_levels_drain(s.packed.p, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_packed.p, m.packed_bytes,
+                                 so), "svc_hip_levels_drain");
+        Hip(hipMemcpyAsync(s.pin_offsets.p, s.offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, so),
+            "D2H offsets");
+        if (m.budgeted)
+          Hip(hipMemcpyAsync(s.pin_choice.p, s.choice.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "D2H choice");
+      } else
+        Hip(hipMemcpyAsync(s.pin_coeffs.p, s.coeffs.p, (size_t)encoded * 3 * m.plane_elems * sizeof(float), hipMemcpyDeviceToHost, so), "D2H coeffs");
+      return bytes;
+    };
+    s.frames = off + n_new; s.encoded = encoded; s.first = first;
+    m.pipe->Submit(slot, h2d, kernels, d2h);
+    prev = &s; first += encoded;
   }
-  for (Slot* s : pending) deliver(*s);
-  for (auto& s : m.slots) s->busy = false;  // everything delivered and synchronised
-  st.wall_ms = ms_since(t_start);
+  const BatchPipe::Totals& t = m.pipe->Finish();
+  st.batches = t.batches; st.wall_ms = t.wall_ms;
+  st.slot_wait_ms = t.slot_wait_ms; st.deliver_wait_ms = t.deliver_wait_ms;
+  st.h2d_ms = t.h2d_ms; st.kernels_ms = t.kernels_ms; st.d2h_ms = t.d2h_ms;
+  st.h2d_bytes = t.h2d_bytes; st.d2h_bytes += t.d2h_bytes;
   m.stats = st;
 }
 

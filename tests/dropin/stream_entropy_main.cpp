@@ -7,17 +7,121 @@
 // gaze_file: one line per frame, "x y" or "-", as stream_decode_main.  out_prefix "-": no files; the clip is encoded, then its SVCE
 // stream decoded, again and again for a second each, and both PCIe-inclusive rates printed.  compact_budget (default 0): a byte
 // budget, which svc::StreamEncoder refuses together with entropy (the process then fails with its message).
+//   stream_entropy_main reuse <clip.raw> <seed> <out_prefix>
+// The slot ring at a depth of 4 and ONE decoder across stream kinds (tests/test_gpu_entropy.py): 11 frames of 96 x 64 are encoded
+// three ways (compact, compact + entropy, wire; batch 3, depth 4: a short last batch), then one svc::StreamDecoder (depth 4, batch 2,
+// wire_batch 3: more batches than slots) decodes SVCQ, wire, SVCE, SVCQ, a gaze on every other frame, and a fresh default-configured
+// decoder decodes each stream once.  Writes <prefix>.{q,e,w}.mv / .types and <prefix>.{reuse,fresh}{0..3}.display / .status.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "svc/stream_decoder.hpp"
 #include "svc/stream_encoder.hpp"
 
+namespace {
+
+void Dump(const std::string& path, const void* p, size_t bytes) {
+  FILE* o = std::fopen(path.c_str(), "wb");
+  if (!o || std::fwrite(p, 1, bytes, o) != bytes) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); std::exit(1); }
+  std::fclose(o);
+}
+
+struct Coded {  // a clip's stream in host memory, whichever kind
+  std::vector<uint8_t> bytes;       // SVCQ / SVCE frames back to back, or the wire header and its records
+  std::vector<uint64_t> offsets{0};  // compact kinds only
+  std::vector<float> mv;
+  std::vector<uint32_t> types;
+};
+
+Coded EncodeClip(const std::vector<uint8_t>& clip, uint32_t w, uint32_t h, uint32_t n, uint64_t seed, bool entropy, bool wire) {
+  svc::StreamEncoderConfig cfg;
+  cfg.width = w; cfg.height = h; cfg.levels = 3; cfg.mv_block = 16; cfg.dct_block = 8;
+  cfg.batch = 3; cfg.depth = 4; cfg.seed = seed;
+  cfg.wire = wire; cfg.compact = !wire; cfg.entropy = entropy;
+  svc::StreamEncoder enc(cfg);
+  Coded out;
+  uint32_t next = 1;
+  enc.Encode(clip.data(), n, [&](const svc::EncodedBatch& b) {
+    if (b.first_frame != next) { std::fprintf(stderr, "batch out of order: %u, expected %u\n", b.first_frame, next); std::exit(1); }
+    next += b.count;
+    const size_t blocks = (size_t)b.mv_field_w * b.mv_field_h;
+    out.mv.insert(out.mv.end(), b.mv_xy, b.mv_xy + b.count * blocks * 2);
+    out.types.insert(out.types.end(), b.block_types, b.block_types + b.count * blocks);
+    if (wire) {
+      if (b.header) out.bytes.insert(out.bytes.end(), (const uint8_t*)b.header, (const uint8_t*)b.header + sizeof(*b.header));
+      out.bytes.insert(out.bytes.end(), b.records, b.records + b.count * b.record_bytes);
+    } else {
+      const uint64_t base = out.bytes.size();
+      out.bytes.insert(out.bytes.end(), b.compact, b.compact + b.compact_bytes);
+      for (uint32_t k = 1; k <= b.count; ++k) out.offsets.push_back(base + b.compact_offsets[k]);
+    }
+  });
+  if (next != n) { std::fprintf(stderr, "%u encoded frames, expected %u\n", next - 1, n - 1); std::exit(1); }
+  return out;
+}
+
+int Reuse(const char* clip_path, uint64_t seed, const std::string& prefix) {
+  const uint32_t w = 96, h = 64, n = 11;
+  std::vector<uint8_t> clip((size_t)w * h * 3 * n);
+  FILE* f = std::fopen(clip_path, "rb");
+  if (!f || std::fread(clip.data(), 1, clip.size(), f) != clip.size()) { std::fprintf(stderr, "cannot read %s\n", clip_path); return 1; }
+  std::fclose(f);
+  const Coded q = EncodeClip(clip, w, h, n, seed, false, false), e = EncodeClip(clip, w, h, n, seed, true, false),
+              wr = EncodeClip(clip, w, h, n, seed, false, true);
+  for (const auto& kv : {std::make_pair(".q", &q), std::make_pair(".e", &e), std::make_pair(".w", &wr)}) {
+    Dump(prefix + kv.first + ".mv", kv.second->mv.data(), kv.second->mv.size() * sizeof(float));
+    Dump(prefix + kv.first + ".types", kv.second->types.data(), kv.second->types.size() * sizeof(uint32_t));
+  }
+  const svc::StreamDecoder::Gaze gaze = [&](uint32_t i, uint32_t* x, uint32_t* y) {
+    if (i % 2) return false;
+    *x = (37 * i + 5) % w; *y = (23 * i + 3) % h;
+    return true;
+  };
+  const Coded* order[4] = {&q, &wr, &e, &q};
+  auto decode = [&](svc::StreamDecoder& dec, int k, const std::string& name) {
+    std::vector<uint8_t> display;
+    std::vector<uint32_t> status;
+    uint32_t dnext = 0;
+    auto sink = [&](const svc::DecodedBatch& b) {
+      if (b.first_frame != dnext) { std::fprintf(stderr, "decoded batch out of order: %u, expected %u\n", b.first_frame, dnext); std::exit(1); }
+      dnext += b.count;
+      display.insert(display.end(), b.bgr, b.bgr + (size_t)b.count * b.width * b.height * 3);
+      status.insert(status.end(), b.status, b.status + b.count);
+    };
+    if (order[k] == &wr) dec.DecodeWire(wr.bytes.data(), wr.bytes.size(), gaze, sink);
+    else dec.Decode(order[k]->bytes.data(), order[k]->offsets.data(), n - 1, gaze, sink);
+    if (dnext != n - 1) { std::fprintf(stderr, "%u decoded frames, expected %u\n", dnext, n - 1); std::exit(1); }
+    Dump(prefix + name + std::to_string(k) + ".display", display.data(), display.size());
+    Dump(prefix + name + std::to_string(k) + ".status", status.data(), status.size() * sizeof(uint32_t));
+  };
+  svc::StreamDecoderConfig dcfg;
+  dcfg.depth = 4; dcfg.batch = 2; dcfg.wire_batch = 3;
+  svc::StreamDecoder reused(dcfg);
+  for (int k = 0; k < 4; ++k) {
+    decode(reused, k, ".reuse");
+    svc::StreamDecoder fresh{svc::StreamDecoderConfig{}};
+    decode(fresh, k, ".fresh");
+  }
+  std::printf("%u frames encoded three ways, decoded by one decoder and by fresh ones\n", n - 1);
+  return 0;
+}
+
+}  // namespace
+
 int main(int argc, char** argv) {
+  if (argc == 5 && std::string(argv[1]) == "reuse") {
+    try {
+      return Reuse(argv[2], std::strtoull(argv[3], nullptr, 10), argv[4]);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "%s\n", e.what());
+      return 1;
+    }
+  }
   if (argc != 11 && argc != 12) { std::fprintf(stderr, "usage: see the header comment\n"); return 2; }
   const uint32_t w = std::atoi(argv[2]), h = std::atoi(argv[3]), n = std::atoi(argv[4]);
   svc::StreamEncoderConfig cfg;

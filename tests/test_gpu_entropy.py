@@ -328,3 +328,33 @@ def test_cpp_stream_entropy_main_equals_the_compact_stream_and_its_decode(native
     r = subprocess.run([_exe("stream_entropy_main"), *common, "8", str(cfg.seed), "-", "-", "200000"], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 1 and "budget" in r.stderr, r.stdout + r.stderr
+
+
+def test_cpp_one_decoder_at_depth_4_across_svcq_wire_and_svce(native, tmp_path):
+    """svc::StreamDecoder's slot ring beyond the default depth, its regrow path and the switch between Decode's and DecodeWire's
+    buffers: one decoder (depth 4, batch 2, wire_batch 3) decodes the SVCQ, the wire, the SVCE and again the SVCQ stream of a clip
+    (stream_entropy_main reuse: 10 encoded frames of 96 x 64 from an encoder at batch 3, depth 4), and gives every time, display
+    bytes and frame statuses, what a fresh default decoder gives for that stream -- which test_cpp_stream_decode_main_equals_python
+    and tests/test_gpu_decode_records.py pin to the Python statement."""
+    import subprocess
+    w, h, n = 96, 64, 11
+    clip = synth.SynthClip(w, h, n, 7, device="cuda")
+    raw = tmp_path / "clip.raw"
+    torch.stack([clip.frame_bgr(t) for t in range(n)]).cpu().numpy().tofile(raw)
+    prefix = str(tmp_path / "reuse")
+    r = subprocess.run([_exe("stream_entropy_main"), "reuse", str(raw), "7", prefix], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+    def out(name, k):
+        return (np.fromfile(f"{prefix}.{name}{k}.display", np.uint8), np.fromfile(f"{prefix}.{name}{k}.status", np.uint32))
+
+    for k, kind in enumerate(["SVCQ", "wire", "SVCE", "SVCQ again"]):  # the order the one decoder saw them in
+        (disp, status), (fresh_disp, fresh_status) = out("reuse", k), out("fresh", k)
+        assert disp.size == (n - 1) * w * h * 3 and status.size == n - 1, kind
+        assert np.array_equal(disp, fresh_disp) and np.array_equal(status, fresh_status), kind
+        assert not status.any(), kind
+    for a, b in ((0, 3), (0, 2)):  # the same stream twice; and the coding is lossless
+        assert np.array_equal(out("reuse", a)[0], out("reuse", b)[0]) and np.array_equal(out("reuse", a)[1], out("reuse", b)[1])
+    for ext in (".mv", ".types"):  # one clip, one seed: the three encodings tracked and segmented it alike
+        q = open(f"{prefix}.q{ext}", "rb").read()
+        assert len(q) > 0 and q == open(f"{prefix}.e{ext}", "rb").read() == open(f"{prefix}.w{ext}", "rb").read(), ext
