@@ -82,6 +82,13 @@ struct ClipEncoderConfig {
   uint32_t fg_step = 1, bg_step = 640;        // apps/decoder.cpp:22-23
   bool wire = false;          // serialised records (libs/encoder.cpp:222-269) of the RAW coefficients, as the
                               // reference's encoder emits them, instead of quantised planes
+  bool compact = false;       // the compact stream (SVCQ, include/svc_hip.h) of the quantised coefficients instead of the planes, straight
+                              // from the transform kernel (svc_hip_dct_pack_levels_frames): Buffer::kCompact / kCompactOffsets.  Not with
+                              // `wire`; needs an 8x8 or 16x16 transform, a padded width of whole 16-pixel segments, an MV block that is a
+                              // multiple of the tile, steps > 0 and whole-shard launches (chunk_pairs = 0) -- anything else throws.  A
+                              // compact step is the two-pass order (the region ids exist when the transform runs: nothing to speculate
+                              // on); one launch per step makes a shard's frames one back-to-back stream.  No coefficient planes are
+                              // allocated: the stream (at its worst case), its offsets and the call's workspace exist once
   bool segmentation = true;   // false: region ids from the in-repo part only (foreground = one region)
   uint64_t seed = 0;
   svc_ransac_params ransac{1, 7.5f, 0.99f, 0.5f};
@@ -115,7 +122,8 @@ struct ClipEncoderConfig {
 
 enum class Stage : uint32_t { kLumaPyramid = 0, kHalo, kHbma, kRansac, kSegment, kTransform, kTypePatch, kCount };
 enum class Buffer : uint32_t { kMv = 0, kMinMad, kGlobalMotion, kRmse, kInlierMask, kInlierCount, kBlockTypes,
-                               kCoeffs, kRecords, kPyramids, kBgr, kCount };
+                               kCoeffs, kRecords, kPyramids, kBgr,
+                               kCompact /* offsets[pairs] bytes of SVCQ frames, back to back */, kCompactOffsets /* [pairs + 1] u64 */, kCount };
 
 class ClipEncoder {
  public:

@@ -39,6 +39,12 @@ typedef struct svc_clip svc_clip;
  * stream, so the foreground share measured on the last piece stays the speculation policy's prior for the next (default: a load voids it and
  * the first step over new frames runs the plain two-pass order).  Safe at any share: a stale prior costs one slow step, never a byte. */
 #define SVC_CLIP_KEEP_FOREGROUND_PRIOR 64u
+/* Not a tuning switch either but a statement about the OUTPUT (same field; svc_clip_create refused the bit before it had this meaning): the
+ * step leaves the compact stream (SVCQ, svc_hip.h) of the quantised coefficients, straight from the transform kernel
+ * (svc_hip_dct_pack_levels_frames), instead of the f32 planes: SVC_BUF_COMPACT holds the shard's frames back to back, SVC_BUF_COMPACT_OFFSETS
+ * their pairs + 1 u64 offsets; no plane buffer exists.  Not with `wire`; needs an 8x8 or 16x16 transform, a padded width of whole 16-pixel
+ * segments, an MV block that is a multiple of the tile, steps > 0 and chunk_pairs = 0 (svc_clip_create fails with a message otherwise). */
+#define SVC_CLIP_OUTPUT_COMPACT 8192u
 #define SVC_CLIP_TUNE_IDLE_RULE_ANY_SIZE 512u /* the idle-pipeline rule whatever the shard's size (tests; default: from 400 M pixels x frames) */
 #define SVC_CLIP_TUNE_FORK_BEHIND_FRONT 4096u /* one rank, A/B: RANSAC + segmentation of the previous micro-step fork behind the front-of-step transform */
 #define SVC_CLIP_TUNE_RANDOM_POLICY 2048u /* tests: the speculation policy answers yes / no by a fixed pseudo-random sequence over the chunk launches */
@@ -91,7 +97,7 @@ enum { SVC_STAGE_LUMA_PYRAMID = 0, SVC_STAGE_HALO, SVC_STAGE_HBMA, SVC_STAGE_RAN
 /* buffer ids for svc_clip_output / svc_clip_read */
 enum { SVC_BUF_MV = 0, SVC_BUF_MIN_MAD, SVC_BUF_GLOBAL_MOTION, SVC_BUF_RMSE, SVC_BUF_INLIER_MASK,
        SVC_BUF_INLIER_COUNT, SVC_BUF_BLOCK_TYPES, SVC_BUF_COEFFS, SVC_BUF_RECORDS, SVC_BUF_PYRAMIDS,
-       SVC_BUF_BGR, SVC_BUF_COUNT };
+       SVC_BUF_BGR, SVC_BUF_COMPACT /* bytes = offsets[pairs] of the newest step */, SVC_BUF_COMPACT_OFFSETS, SVC_BUF_COUNT };
 
 /* Halo transport override: must enqueue on `stream` the send of `bytes` from d_send to rank + 1
  * (if any) and the receive into d_recv from rank - 1 (if any). */

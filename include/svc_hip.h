@@ -464,6 +464,31 @@ int svc_hip_levels_drain(const uint8_t* d_frames, const uint64_t* d_frame_offset
                          uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
                          uint32_t mv_block_h, void* host_dst, uint64_t capacity, void* stream);
 
+/* The compact stream straight from the transform: d_out and d_frame_offsets receive, byte for
+ * byte, what svc_hip_dct_quant_frames followed by svc_hip_pack_levels_frames leave for the same
+ * arguments (header with inexact = 0, types, masks, levels, padding, offsets) -- from one pass
+ * over the B,G,R bytes that quantises and packs in the transform kernel, a per-frame scan and an
+ * assemble pass; the f32 planes (12 bytes per pixel written once and read twice by the two
+ * calls) are never made.  For the tuned transform only: block = 8 or 16 (square) and frame_w a
+ * multiple of 16; anything else is SVC_ERR_UNSUPPORTED and the caller uses the two calls.
+ * d_bgr 16-byte aligned, frame_stride_bytes >= 3 * W * H and a multiple of 16 (else
+ * SVC_ERR_INVALID_ARG).  The workspace holds every piece of a frame at its worst case: about
+ * 6 * W * H bytes per frame plus the masks; the query returns 0 for a geometry the call refuses.
+ * Checked in the order of the SVCQ entry points, for any n_frames and before any pointer:
+ * geometry, steps (0 is SVC_ERR_INVALID_ARG), limits, workspace, out_capacity against
+ * svc_hip_levels_max_bytes; n_frames == 0 then returns SVC_OK; then pointers.  Only enqueues. */
+uint64_t svc_hip_dct_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w,
+                                                 uint32_t frame_h, uint32_t block,
+                                                 uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_dct_pack_levels_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes,
+                                   uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                   uint32_t block, const uint32_t* d_block_types,
+                                   uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                   uint32_t bg_step, uint8_t* d_workspace,
+                                   uint64_t workspace_bytes, uint8_t* d_out,
+                                   uint64_t out_capacity, uint64_t* d_frame_offsets,
+                                   void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Entropy-coded compact stream ("SVCE", format version 1): a LOSSLESS coding of SVCQ frames;
  * decoding an SVCE frame gives back its SVCQ frame byte for byte (header words, padding and

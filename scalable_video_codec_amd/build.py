@@ -26,7 +26,7 @@ OBJ = os.path.join(PKG, "_obj")
 LIB_HIP = os.path.join(PKG, "libsvc_hip.so")
 LIB_MOTION = os.path.join(PKG, "libsvc_motion.so")
 
-HIP_SOURCES = ["capi.hip", "hbma_wave.hip", "hbma_fused.hip", "hbma_fused8.hip", "hbma_fused32.hip", "hbma_tiled.hip", "dct.hip", "ransac.hip", "luma_pyramid.hip", "segment.hip", "wire.hip", "idct.hip", "probe.hip", "comm.hip", "global_motion.hip", "imageops.hip", "levels.hip", "records.hip", "entropy.hip"]
+HIP_SOURCES = ["capi.hip", "hbma_wave.hip", "hbma_fused.hip", "hbma_fused8.hip", "hbma_fused32.hip", "hbma_tiled.hip", "dct.hip", "dct_pack.hip", "ransac.hip", "luma_pyramid.hip", "segment.hip", "wire.hip", "idct.hip", "probe.hip", "comm.hip", "global_motion.hip", "imageops.hip", "levels.hip", "records.hip", "entropy.hip"]
 HOST_SOURCES = [os.path.join("host", "motion_hip.cpp")]
 
 # -ffp-contract=off: the reference's float expressions (RANSAC inlier test, quant) are

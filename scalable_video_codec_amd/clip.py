@@ -26,12 +26,13 @@ TUNE_RANDOM_POLICY = 2048  # tests: the speculation policy answers yes / no by a
 TUNE_MIXED_STEPS = 1024  # a step into an empty pipeline that knows nothing about the clip takes the mixed form (A/B, off by default)
 TUNE_SEARCH_AFTER_TRANSFORM = 256  # one rank: the motion search right behind the transform kernel (A/B)
 TUNE_WHOLE_SHARD_STEPS = 128  # never the idle-pipeline rule (A/B)
+OUTPUT_COMPACT = 8192  # same field, a statement about the output: the compact stream (SVCQ) straight from the transform instead of planes
 KEEP_FOREGROUND_PRIOR = 64  # same field: the clips loaded are consecutive pieces of one stream (the policy keeps its prior across load_frames)
 STAGES = ("luma_pyramid", "halo_exchange", "hbma", "ransac", "segment", "dct_quant", "type_patch")
 BUFFERS = {"mv": (0, torch.float32), "min_mad": (1, torch.float32), "global_motion": (2, torch.float32),
            "rmse": (3, torch.float32), "inlier_mask": (4, torch.uint8), "inlier_count": (5, torch.int32),
            "block_types": (6, torch.int32), "coeffs": (7, torch.float32), "records": (8, torch.uint8),
-           "pyramids": (9, torch.uint8), "bgr": (10, torch.uint8)}
+           "pyramids": (9, torch.uint8), "bgr": (10, torch.uint8), "compact": (11, torch.uint8), "compact_offsets": (12, torch.int64)}
 COMM_ID_BYTES = 128
 
 
@@ -155,7 +156,7 @@ class Clip:
     def __init__(self, cfg: CodecConfig, clip_frames: int, rank: int = 0, world: int = 1, schedule: int = PIPELINED,
                  segmentation: bool = True, wire: bool = False, seed: Optional[int] = None,
                  ransac: Optional[dict] = None, segment: Optional[dict] = None, dct_block: Optional[Tuple[int, int]] = None,
-                 hbma_flags: int = 0, lat_depth: int = 0, tuning: int = 0, chunk_pairs: int = 0):
+                 hbma_flags: int = 0, lat_depth: int = 0, tuning: int = 0, chunk_pairs: int = 0, compact: bool = False):
         self.cfg = cfg
         r = dict(subset_sz=1, inlier_thresh=7.5, success_prob=0.99, inlier_ratio=0.5)
         r.update(ransac or {})
@@ -165,7 +166,8 @@ class Clip:
         self.config = ClipConfig(C.sizeof(ClipConfig), cfg.width, cfg.height, cfg.levels, cfg.mv_block, cfg.search_range, bw, bh,
                                  cfg.fg_step, cfg.bg_step, int(wire), int(segmentation),
                                  cfg.seed if seed is None else seed, RansacParams(**r), SegmentParams(**s),
-                                 clip_frames, rank, world, schedule, chunk_pairs, hbma_flags, lat_depth, tuning)
+                                 clip_frames, rank, world, schedule, chunk_pairs, hbma_flags, lat_depth,
+                                 tuning | (OUTPUT_COMPACT if compact else 0))
         self._h = _vp()
         self._cb = None  # keeps the ctypes callback alive
         _check(load().svc_clip_create(C.byref(self.config), C.byref(self._h)))
@@ -292,6 +294,11 @@ class Clip:
         if n:
             _check(load().svc_clip_read(self._h, idx, 0, _vp(out.data_ptr()), nbytes.value, int(out.is_cuda)))
         return out
+
+    def read_compact(self, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The newest finished step's compact stream (a clip made with compact=True): (the offsets[pairs] bytes of the shard's SVCQ
+        frames, back to back; their pairs + 1 offsets as i64)."""
+        return self.read("compact", device), self.read("compact_offsets", device)
 
     def outputs(self, device=None) -> Dict[str, torch.Tensor]:
         i = self.info

@@ -31,13 +31,12 @@
 // 600 f64 instructions per lane and segment row (420 FMA + 90 MUL + 90 ADD) against 348 at N = 8, see DESIGN.md 4.2.
 #include <algorithm>
 
+#include "dct_core.hpp"
 #include "luma16.hpp"
 #include "quant_core.hpp"
 #include "svc_common.hpp"
 
 namespace svc {
-
-#include "dct_tables.inc"
 
 struct DctArgs {
   const uint8_t* bgr;
@@ -65,73 +64,9 @@ struct DctArgs {
   uint32_t segs_per_block_x, segs_per_block;  // segment columns of one MV block: (mv_bw / 16) x (mv_bh / N)
 };
 
-template <int N> struct Basis;
-template <> struct Basis<8> {
-  static __device__ __forceinline__ double even(int k, int i) { return kDctEven8[k][i]; }
-  static __device__ __forceinline__ double odd(int k, int i) { return kDctOdd8[k][i]; }
-};
-template <> struct Basis<16> {
-  static __device__ __forceinline__ double even(int k, int i) { return kDctEven16[k][i]; }
-  static __device__ __forceinline__ double odd(int k, int i) { return kDctOdd16[k][i]; }
-};
-
-template <int N, int L> struct RecTab;
-#define SVC_RECTAB(N_, L_) \
-  template <> struct RecTab<N_, L_> { \
-    static __device__ __forceinline__ double at(int r, int i) { return kDctRec##N_##_L##L_[r][i]; } \
-  }
-SVC_RECTAB(8, 0); SVC_RECTAB(8, 1); SVC_RECTAB(8, 2);
-SVC_RECTAB(16, 0); SVC_RECTAB(16, 1); SVC_RECTAB(16, 2); SVC_RECTAB(16, 3);
-#undef SVC_RECTAB
-template <int N> struct RecDc;
-template <> struct RecDc<8> { static constexpr double v = kDctRec8_Dc; };
-template <> struct RecDc<16> { static constexpr double v = kDctRec16_Dc; };
-
-// N-point orthonormal DCT-II by the even/odd split of the basis, applied recursively: the odd rows
-// of a level act on the differences x[i] - x[M-1-i], the even rows are a scaled M/2-point DCT of the
-// sums (86 multiplies for 16 points instead of 128, 22 instead of 32 for 8).  x holds the M inputs
-// of level L, y the N outputs: level L produces the rows k = 2^L * odd.
-// T = int for the row pass: the inputs are bytes, so the sums and differences of every level are integers <= 4080 (byte
-// extraction folds into the adds as SDWA operands); each operand of a multiply is widened once (v_cvt_f64_i32).
-template <int N, int M, int L, typename T>
-__device__ __forceinline__ void dct_level(const T* __restrict__ x, double* __restrict__ y) {
-  if constexpr (M == 1) {
-    y[0] = RecDc<N>::v * (double)x[0];
-  } else {
-    constexpr int H = M / 2;
-    T s[H];
-    double d[H];
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-      s[i] = x[i] + x[M - 1 - i];
-      d[i] = (double)(x[i] - x[M - 1 - i]);
-    }
-#pragma unroll
-    for (int r = 0; r < H; ++r) {
-      double o = RecTab<N, L>::at(r, 0) * d[0];
-#pragma unroll
-      for (int i = 1; i < H; ++i) o = __builtin_fma(RecTab<N, L>::at(r, i), d[i], o);
-      y[(1 << L) * (2 * r + 1)] = o;
-    }
-    dct_level<N, H, L + 1, T>(s, y);
-  }
-}
-
-template <int N, typename T>
-__device__ __forceinline__ void dct1d(const T* __restrict__ x, double* __restrict__ y) {
-  dct_level<N, N, 0, T>(x, y);
-}
 
 // the quantiser (quant1, quant1_fast, quant2_fast): quant_core.hpp
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-constexpr int kRowPitch = 144;                  // 16 f64 + 16 B pad
-constexpr int kSlab8 = 8 * kRowPitch;           // 1152 B  (= 128 mod 256)
-constexpr int kSlab16 = 16 * kRowPitch + 128;   // 2432 B  (= 128 mod 256)
 // WIRE: once the last channel has left it, a wave's slabs (adjacent in LDS) become ONE linear staging buffer for the
 // records of the wave's 64 / N segment columns (8 x 2 x 772 = 12 352 B for N = 8, 4 x 3076 = 12 304 B for N = 16) plus up
 // to 12 bytes of alignment slack -- so the slab pitch grows to cover its share of that, still = 128 mod 256

@@ -1,0 +1,398 @@
+// dct_pack.hip -- the compact stream ("SVCQ", stream_format.hpp) straight from the transform: B,G,R frames + region ids in, packed
+// frames out, byte for byte what svc_hip_dct_quant_frames followed by svc_hip_pack_levels_frames leaves -- without the 12 bytes per
+// pixel of f32 planes that route writes once and reads twice.
+//
+// dct_pack_kernel<N> is the front half of dct_kernel<N, QUANT> (dct.hip; the arithmetic is dct_core.hpp and quant_core.hpp, shared):
+// segment columns of 16 pixels x N rows x 3 channels, N lanes per column, 48-byte row loads, integer butterflies, f64 even/odd chains, a
+// wave-private LDS slab per column and no workgroup barrier.  Where that kernel stores f32, this one packs:
+//   staging  once the column pass of a channel has read the slabs, every lane writes its integer levels (quant2_level: the quantiser's q
+//            before the * step) as int16 into TILE IMAGES inside its column's slab -- 128 B per 8x8 tile, 512 B per 16x16 tile,
+//            coefficients in the format's row-major order;
+//   packing  the wave walks its tiles' 64-coefficient words in the format's order, one 16-bit LDS read per lane: the word's mask is a
+//            __ballot, a lane's rank mbcnt, and the base of the word a running popcount sum -- the wave takes its words in order, so the
+//            sum is wave-uniform: no scan, no atomics.
+// Geometry: a wave's 64 / N segment columns lie in ONE tile row of ONE frame (the last wave of a row may be partly idle), so its tiles are
+// consecutive in the format's tile order and a wave's output of one channel is one PIECE = (frame, plane, tile row, wave in the row).
+//
+// Levels are ordered plane-major within a frame, so a wave cannot know where its levels end up.  The workspace holds, per piece, a slot
+// of the worst-case capacity (1024 levels) with the compacted levels and their count -- only the lines touched cost traffic -- and per
+// frame the mask words in the format's own order.  Then
+//   dct_pack_scan_kernel      one workgroup per frame: piece counts -> exclusive prefixes, the frame's level count and size;
+//   dct_pack_assemble_kernel  the frame's offset (the sizes of the frames before it, as the pack's scatter sums them), header, types,
+//                             masks, every piece's levels to levels_off + 2 * prefix, the zero pad, offsets[f + 1].
+#include <algorithm>
+
+#include "dct_core.hpp"
+#include "quant_core.hpp"
+#include "stream_format.hpp"
+#include "svc_common.hpp"
+
+namespace svc {
+namespace {
+
+constexpr uint32_t kPieceLevels = 1024;  // 64 / N segment columns x 16 x N coefficients, N = 8 and 16 alike
+
+struct DctPackWs {
+  int16_t* slots;        // [n][pieces][kPieceLevels]
+  uint32_t* masks;       // [n][mask_dwords] the frame's mask section
+  uint32_t* counts;      // [n][pieces] levels of a piece, then (scan) their exclusive prefix
+  uint32_t* frame_bytes; // [n]
+  uint32_t* frame_levels;// [n]
+};
+
+struct PackGeom {
+  FrameLayout l;
+  uint32_t w, h, n_block, mvbw, mvbh;
+  uint32_t segs_per_band;   // w / 16
+  uint32_t waves_per_row;   // ceil(segs_per_band / (64 / N))
+  uint32_t pieces;          // 3 * tiles_y * waves_per_row, in the order of the levels: plane, tile row, wave
+  uint32_t mask_dwords;     // of one frame
+};
+
+PackGeom make_pack_geom(uint32_t w, uint32_t h, uint32_t block, uint32_t mvbw, uint32_t mvbh) {
+  PackGeom g{};
+  g.l = frame_layout(w, h, block, block, mvbw, mvbh);
+  g.w = w; g.h = h; g.n_block = block; g.mvbw = mvbw; g.mvbh = mvbh;
+  g.segs_per_band = w / 16;
+  g.waves_per_row = div_up(g.segs_per_band, 64 / block);
+  g.pieces = 3 * g.l.tiles_y * g.waves_per_row;
+  g.mask_dwords = (uint32_t)((g.l.levels_off - g.l.masks_off) / 4);
+  return g;
+}
+
+uint64_t pack_ws_bytes(uint32_t n, const PackGeom& g) {
+  return 2ull * kPieceLevels * n * g.pieces + (uint64_t)n * up16(4ull * g.mask_dwords) + up16(4ull * n * g.pieces) + 2 * up16(4ull * n);
+}
+
+DctPackWs carve(uint8_t* p, uint32_t n, const PackGeom& g) {
+  DctPackWs s;
+  s.slots = reinterpret_cast<int16_t*>(p);
+  p += 2ull * kPieceLevels * n * g.pieces;
+  s.masks = reinterpret_cast<uint32_t*>(p);
+  p += (uint64_t)n * up16(4ull * g.mask_dwords);
+  s.counts = reinterpret_cast<uint32_t*>(p);
+  p += up16(4ull * n * g.pieces);
+  s.frame_bytes = reinterpret_cast<uint32_t*>(p);
+  p += up16(4ull * n);
+  s.frame_levels = reinterpret_cast<uint32_t*>(p);
+  return s;
+}
+
+struct DctPackArgs {
+  const uint8_t* bgr;
+  uint64_t frame_stride;
+  PackGeom g;
+  uint32_t total_waves;       // frames * tile rows * waves per row
+  const uint32_t* types;
+  float fg_step, bg_step, fg_inv, bg_inv;  // inv = RN(1 / step), computed on the host
+  DctPackWs ws;
+};
+
+__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+__device__ __forceinline__ uint32_t pack2(f32x2 q) {  // two levels as int16, the first in the low half
+  return ((uint32_t)(int32_t)q.x & 0xFFFFu) | ((uint32_t)(int32_t)q.y << 16);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
+  constexpr uint32_t kCols = 64 / N;        // segment columns of a wave
+  constexpr uint32_t kColWords = N / 4;     // mask words of a segment column: two 8x8 tiles of one word, or one 16x16 tile of four
+  constexpr int kSlab = N == 8 ? kSlab8 : kSlab16;
+  // Where word k of the wave's column g starts inside the column's slab.  The slabs are a multiple of 128 B apart, so images at the same
+  // place in every slab would put the staging stores of a half-wave's columns on the same banks (8-way at N = 8): each image is skewed
+  // by its column -- N = 8: 16 B per tile, the 32 lanes of a half-wave then store to 32 different banks; N = 16: 64 B per odd column.
+  // A word's 64 levels stay 128 contiguous bytes, so the walk's reads have no conflicts either way.
+  auto image_at = [](uint32_t col, uint32_t k) { return N == 8 ? k * 144 + col * 32 : (col & 1u) * 64 + k * 128; };
+  static_assert((N == 8 ? 144 + 7 * 32 + 128 : 64 + 512) <= kSlab, "a column's tile images fit its slab");
+  __shared__ __attribute__((aligned(16))) uint8_t lds[(256 / N) * kSlab];
+
+  const PackGeom& gm = a.g;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, sc_local = tid / N, j = tid % N, g = lane / N;
+  // the wave's place: (frame, tile row, wave in the row), the same in every lane
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(xcd_contiguous_block(blockIdx.x, gridDim.x) * 4u + (tid >> 6));
+  if (wv >= a.total_waves) return;
+  const uint32_t row_g = wv / gm.waves_per_row, wr = wv - row_g * gm.waves_per_row;
+  const uint32_t frame = row_g / gm.l.tiles_y, band = row_g - frame * gm.l.tiles_y;
+  const uint32_t seg0 = wr * kCols, seg = seg0 + g;
+  const uint32_t ncols = min(kCols, gm.segs_per_band - seg0);  // the last wave of a row may hold fewer
+  const bool active = g < ncols;  // an idle column runs on zeros and is not packed
+  const uint32_t y_pix = band * N, x_pix = seg * 16;
+
+  // 16 BGR pixels of row j of this segment column
+  uint32_t wds[12] = {};
+  uint32_t t = 0;
+  if (active) {
+    const uint4* p = reinterpret_cast<const uint4*>(a.bgr + (size_t)frame * a.frame_stride + ((size_t)(y_pix + j) * gm.w + x_pix) * 3);
+    const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
+    wds[0] = v0.x; wds[1] = v0.y; wds[2] = v0.z; wds[3] = v0.w;
+    wds[4] = v1.x; wds[5] = v1.y; wds[6] = v1.z; wds[7] = v1.w;
+    wds[8] = v2.x; wds[9] = v2.y; wds[10] = v2.z; wds[11] = v2.w;
+    // tile type = type of the MV block that holds it; background (0) takes bg_step: the rule of dct_kernel
+    const uint32_t col = N == 8 ? x_pix + 2 * j : x_pix + j;
+    t = a.types[(size_t)frame * gm.l.mvb + (y_pix / gm.mvbh) * gm.l.mfw + col / gm.mvbw];
+  }
+  const float step = t == 0 ? a.bg_step : a.fg_step, inv_step = t == 0 ? a.bg_inv : a.fg_inv;
+
+  uint8_t* slab = lds + sc_local * kSlab;
+  const uint8_t* wave_slabs = lds + (sc_local - g) * kSlab;
+  const uint32_t nwords = ncols * kColWords;                           // mask words of the piece, in the format's order
+  const uint32_t word0 = (seg0 * (16 / N)) * gm.l.words;               // the piece's first word within its tile row
+
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    int x[16];
+    double r[16];
+#pragma unroll
+    for (int p = 0; p < 16; ++p) x[p] = (int)((wds[(3 * p + c) >> 2] >> (8 * ((3 * p + c) & 3))) & 0xFFu);
+    if (N == 8) {
+      dct1d<8, int>(x, r);
+      dct1d<8, int>(x + 8, r + 8);
+    } else {
+      dct1d<16, int>(x, r);
+    }
+    double2* row = reinterpret_cast<double2*>(slab + j * kRowPitch);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) row[i] = make_double2(r[2 * i], r[2 * i + 1]);
+    wave_lds_sync();
+
+    uint32_t lv[8];  // this lane's levels of the channel, two int16 each
+    if (N == 8) {
+      // lane j takes columns 2j, 2j+1 of the 16-wide slab (tile j >> 2): lv[v] = row v
+      double ca[8], cb[8], ya[8], yb[8];
+#pragma unroll
+      for (int y = 0; y < 8; ++y) {
+        double2 v = *reinterpret_cast<const double2*>(slab + y * kRowPitch + j * 16);
+        ca[y] = v.x;
+        cb[y] = v.y;
+      }
+      dct1d<8, double>(ca, ya);
+      dct1d<8, double>(cb, yb);
+#pragma unroll
+      for (int v = 0; v < 8; ++v) lv[v] = pack2(quant2_level(f32x2{(float)ya[v], (float)yb[v]}, step, inv_step));
+    } else {
+      // lane j takes column j: lv[v / 2] = rows v, v + 1
+      double cc[16], yy[16];
+#pragma unroll
+      for (int y = 0; y < 16; ++y) cc[y] = *reinterpret_cast<const double*>(slab + y * kRowPitch + j * 8);
+      dct1d<16, double>(cc, yy);
+#pragma unroll
+      for (int v = 0; v < 16; v += 2) lv[v / 2] = pack2(quant2_level(f32x2{(float)yy[v], (float)yy[v + 1]}, step, inv_step));
+    }
+    wave_lds_sync();  // every lane of the column has read the slab: it becomes the column's tile images
+
+    if (N == 8) {
+      uint8_t* img = slab + image_at(g, j >> 2) + (j & 3u) * 4;  // coefficient (v, 2 (j & 3)) of tile j >> 2: 2 * (v * 8 + 2 (j & 3)) bytes in
+#pragma unroll
+      for (int v = 0; v < 8; ++v) *reinterpret_cast<uint32_t*>(img + v * 16) = lv[v];
+    } else {
+      uint8_t* img = slab + image_at(g, 0) + j * 2;  // coefficient (v, j): 2 * (v * 16 + j) bytes in
+#pragma unroll
+      for (int v = 0; v < 16; v += 2) {
+        *reinterpret_cast<uint16_t*>(img + v * 32) = (uint16_t)lv[v / 2];
+        *reinterpret_cast<uint16_t*>(img + (v + 1) * 32) = (uint16_t)(lv[v / 2] >> 16);
+      }
+    }
+    wave_lds_sync();
+
+    // the piece of this channel
+    const size_t piece = ((size_t)frame * 3 + c) * gm.l.tiles_y * gm.waves_per_row + (size_t)band * gm.waves_per_row + wr;
+    int16_t* slot = a.ws.slots + piece * kPieceLevels;
+    // all 16 words of the wave, idle columns included (their images hold the levels of zero pixels: zeros, so their masks are 0 and
+    // nothing of them is stored): no trip count, so the reads go out together and the walk is straight-line code
+    constexpr uint32_t kWaveWords = kCols * kColWords;
+    int16_t l16[kWaveWords];
+#pragma unroll
+    for (uint32_t w = 0; w < kWaveWords; ++w)
+      l16[w] = *reinterpret_cast<const int16_t*>(wave_slabs + (w / kColWords) * kSlab + image_at(w / kColWords, w % kColWords) + lane * 2);
+    uint32_t base = 0;  // levels of the words before this one: wave-uniform
+    uint64_t mine = 0;  // lane w keeps word w's mask: one store of the piece's masks at the end
+#pragma unroll
+    for (uint32_t w = 0; w < kWaveWords; ++w) {
+      const uint64_t mask = __ballot(l16[w] != 0);
+      if (l16[w] != 0) slot[base + lane_rank(mask)] = l16[w];
+      if (lane == w) mine = mask;
+      base += (uint32_t)__popcll(mask);
+    }
+    uint32_t* masks = a.ws.masks + (size_t)frame * (up16(4ull * gm.mask_dwords) / 4) +
+                      2 * ((((size_t)c * gm.l.tiles_y + band) * gm.l.tiles_x) * gm.l.words + word0);
+    if (lane < nwords) store_mask(masks + 2 * lane, mine);
+    if (lane == 0) a.ws.counts[piece] = base;
+    wave_lds_sync();  // the slabs are rewritten by the next channel
+  }
+}
+
+// one workgroup per frame: piece counts -> exclusive prefixes (in place), the frame's level count and size
+__global__ __launch_bounds__(256) void dct_pack_scan_kernel(uint32_t pieces, uint64_t levels_off, DctPackWs ws) {
+  __shared__ uint32_t red[kThreads / 64];
+  const uint32_t f = blockIdx.x;
+  uint32_t* cnt = ws.counts + (size_t)f * pieces;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < pieces; base += kThreads) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t v = i < pieces ? cnt[i] : 0u;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(v, red, &total);
+    if (i < pieces) cnt[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    ws.frame_levels[f] = carry;
+    ws.frame_bytes[f] = (uint32_t)up16(levels_off + 2ull * carry);
+  }
+}
+
+struct AssembleArgs {
+  PackGeom g;
+  uint32_t fg, bg;
+  const uint32_t* types;  // [n][mvb]
+  DctPackWs ws;
+  uint8_t* out;
+  uint64_t* offsets;      // [n + 1]
+};
+
+// grid (workgroups per frame, frames): the frame's sections to their final place.  Masks and pieces are dealt over the frame's
+// workgroups; workgroup 0 also writes the header, the types, the pad and offsets[f + 1].
+__global__ __launch_bounds__(256) void dct_pack_assemble_kernel(AssembleArgs a) {
+  __shared__ uint64_t frame_off;
+  const PackGeom& g = a.g;
+  const uint32_t f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (wave == 0) {  // this frame's offset: the sizes of the frames before it
+    uint64_t s = 0;
+    for (uint32_t i = lane; i < f; i += 64) s += a.ws.frame_bytes[i];
+    for (uint32_t off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) frame_off = s;
+  }
+  __syncthreads();
+  uint8_t* frame = a.out + frame_off;
+  const uint32_t level_count = a.ws.frame_levels[f], fbytes = a.ws.frame_bytes[f];
+
+  // masks: u32 copies (the section is only 4-byte aligned when the MV block count is odd)
+  const uint32_t* msrc = a.ws.masks + (size_t)f * (up16(4ull * g.mask_dwords) / 4);
+  uint32_t* mdst = reinterpret_cast<uint32_t*>(frame + g.l.masks_off);
+  for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < g.mask_dwords; i += gridDim.x * kThreads) mdst[i] = msrc[i];
+
+  // levels: a wave per piece.  The destination is 2-byte aligned (the prefix is any number), so the copy goes by the DESTINATION's
+  // dwords; a dword that two pieces share is written as halves, each piece its own
+  const uint32_t* cnt = a.ws.counts + (size_t)f * g.pieces;
+  uint16_t* ldst = reinterpret_cast<uint16_t*>(frame + g.l.levels_off);
+  for (uint32_t p = blockIdx.x * (kThreads / 64) + wave; p < g.pieces; p += gridDim.x * (kThreads / 64)) {
+    const uint32_t prefix = cnt[p], end = p + 1 < g.pieces ? cnt[p + 1] : level_count;
+    if (end == prefix) continue;
+    const uint16_t* src = reinterpret_cast<const uint16_t*>(a.ws.slots + ((size_t)f * g.pieces + p) * kPieceLevels);
+    for (uint32_t d = prefix / 2 + lane; 2 * d < end; d += 64) {
+      const uint32_t e0 = 2 * d, e1 = e0 + 1;  // the dword's two levels, as indices into the frame's levels
+      const bool has0 = e0 >= prefix, has1 = e1 < end;
+      if (has0 && has1) *reinterpret_cast<uint32_t*>(ldst + e0) = (uint32_t)src[e0 - prefix] | ((uint32_t)src[e1 - prefix] << 16);
+      else if (has0) ldst[e0] = src[e0 - prefix];
+      else if (has1) ldst[e1] = src[e1 - prefix];
+    }
+  }
+
+  if (blockIdx.x != 0) return;
+  // header (inexact = 0: every level reproduces its quantised coefficient), types, pad, offsets
+  uint32_t* hdr = reinterpret_cast<uint32_t*>(frame);
+  if (threadIdx.x < kHeaderWords) {
+    const uint32_t v[kHeaderWords] = {kMagicQ, kVersion, g.w, g.h, g.n_block, g.n_block, g.mvbw, g.mvbh, a.fg, a.bg, level_count, 0,
+                                      fbytes, 0, 0, 0};
+    hdr[threadIdx.x] = v[threadIdx.x];
+  }
+  const uint32_t* types = a.types + (size_t)f * g.l.mvb;
+  uint32_t* tdst = reinterpret_cast<uint32_t*>(frame + kHeaderBytes);
+  for (uint32_t i = threadIdx.x; i < g.l.mvb; i += kThreads) tdst[i] = types[i];
+  const uint64_t used = g.l.levels_off + 2ull * level_count;
+  for (uint64_t i = used + threadIdx.x; i < fbytes; i += kThreads) frame[i] = 0;
+  if (threadIdx.x == 0) {
+    a.offsets[f + 1] = frame_off + fbytes;
+    if (f == 0) a.offsets[0] = 0;
+  }
+}
+
+// the format's geometry, then what the fused kernels take: the tuned transform's blocks on whole 16-pixel segments
+int validate_pack_geom(const char* what, uint32_t w, uint32_t h, uint32_t block, uint32_t mvbw, uint32_t mvbh) {
+  const int rc = validate_geom(what, w, h, block, block, mvbw, mvbh);
+  if (rc) return rc;
+  if (block != 8 && block != 16)
+    return fail(SVC_ERR_UNSUPPORTED, "%s: transform block %ux%u (supported: 8x8, 16x16; for any other call svc_hip_dct_quant_frames, then "
+                                     "svc_hip_pack_levels_frames)", what, block, block);
+  if (w % 16 != 0)
+    return fail(SVC_ERR_UNSUPPORTED, "%s: frame width %u is not a multiple of 16 (call svc_hip_dct_quant_frames, then svc_hip_pack_levels_frames)",
+                what, w);
+  return SVC_OK;
+}
+
+// the formats' limits with SVCQ's worst case, and one launch's worth of waves
+int validate_pack_limits(const char* what, uint32_t n, const PackGeom& g) {
+  const int rc = validate_limits(what, n, g.w, g.h, g.n_block, g.n_block, g.l.max_bytes);
+  if (rc) return rc;
+  if ((uint64_t)n * g.l.tiles_y * g.waves_per_row > 0x7FFFFFFFull) return fail(SVC_ERR_UNSUPPORTED, "%s: too many segment columns for one launch", what);
+  return SVC_OK;
+}
+
+}  // namespace
+}  // namespace svc
+
+using namespace svc;
+
+extern "C" {
+
+uint64_t svc_hip_dct_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,
+                                                 uint32_t mv_block_h) {
+  if (validate_pack_geom("dct_pack_levels_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits("dct_pack_levels_workspace_bytes", n_frames, g)) return 0;
+  return pack_ws_bytes(n_frames, g);
+}
+
+// Checked in the order of the SVCQ entry points, whatever n_frames: geometry, steps, limits, sizes, then pointers.
+int svc_hip_dct_pack_levels_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                   uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                   uint32_t bg_step, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                   uint64_t* d_frame_offsets, void* stream) {
+  int rc = validate_pack_geom("dct_pack_levels", frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "dct_pack_levels: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", (unsigned long long)frame_stride_bytes,
+              3ull * frame_w * frame_h);
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "dct_pack_levels: quant steps must be positive");
+  // (the pack's int16 bound, 255 * sqrt(tile area) / step <= 32767, holds for every step at 8x8 and 16x16: at most 4080)
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits("dct_pack_levels", n_frames, g))) return rc;
+  const uint64_t ws_need = pack_ws_bytes(n_frames, g);
+  SVC_REQUIRE(workspace_bytes >= ws_need, "dct_pack_levels: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
+  const uint64_t need = n_frames * g.l.max_bytes;
+  SVC_REQUIRE(out_capacity >= need, "dct_pack_levels: output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)out_capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets, "dct_pack_levels: null pointer");
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_block_types, 4),
+              "dct_pack_levels: frames, output and workspace must be 16-byte aligned, offsets 8-byte");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.total_waves = n_frames * g.l.tiles_y * g.waves_per_row;
+  a.types = d_block_types;
+  a.fg_step = (float)fg_step;  // libs/decoder.cpp:141 divides a float by an unsigned
+  a.bg_step = (float)bg_step;
+  a.fg_inv = 1.0f / a.fg_step;
+  a.bg_inv = 1.0f / a.bg_step;
+  a.ws = carve(d_workspace, n_frames, g);
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (block == 8) hipLaunchKernelGGL(dct_pack_kernel<8>, grid, blk, 0, s, a);
+  else hipLaunchKernelGGL(dct_pack_kernel<16>, grid, blk, 0, s, a);
+  if ((rc = check_launch("dct_pack_levels", "transform"))) return rc;
+  hipLaunchKernelGGL(dct_pack_scan_kernel, dim3(n_frames), blk, 0, s, g.pieces, g.l.levels_off, a.ws);
+  if ((rc = check_launch("dct_pack_levels", "scan"))) return rc;
+  const AssembleArgs as{g, fg_step, bg_step, d_block_types, a.ws, d_out, d_frame_offsets};
+  // a wave per piece and trip; enough workgroups per frame to keep a single 4K frame busy, few enough that a batch is not all launch
+  const uint32_t per_frame = std::min<uint32_t>(std::max<uint32_t>(div_up(g.pieces, 32), 1), 256);
+  hipLaunchKernelGGL(dct_pack_assemble_kernel, dim3(per_frame, n_frames), blk, 0, s, as);
+  return check_launch("dct_pack_levels", "assemble");
+}
+
+}  // extern "C"

@@ -83,6 +83,10 @@ struct ClipEncoder::Impl : EncodeGeometry {
   DevBuf<float> mv[kSets], mad[kSets], gm[kSets], rmse[kSets], coeffs[kSets + 1];
   DevBuf<uint8_t> redo_ws[kMaxDepth];  // spec_quant: the foreground list of the step being finished, one per latency stream (as seg_ws)
   DevBuf<uint32_t> count[kSets], types[kSets], samples;
+  // compact: the shard's SVCQ frames back to back (at their worst case), their offsets and the workspace of the one launch per step -- one
+  // set, as the planes of the two-pass order: the transforms of consecutive steps follow each other on the main stream
+  DevBuf<uint8_t> compact, compact_ws;
+  DevBuf<uint64_t> compact_off;
   Event e_pyr[2], e_halo[2], e_fork, e_join[kSets], e_rfork, e_rmse[kSets];
   bool halo_recorded[2] = {false, false}, join_pending[kSets] = {}, rmse_pending[kSets] = {};
   bool defer_rmse = false;  // pipelined, large fields: RANSAC leaves its in-order RMSE sum to a later kernel (nothing downstream
@@ -412,7 +416,11 @@ struct ClipEncoder::Impl : EncodeGeometry {
     Run(Stage::kTransform, st, timing, [&] {
       // records carry RAW coefficients, as the reference's encoder serialises them (libs/encoder.cpp:638-650:
       // the decoder picks the step per tile, libs/decoder.cpp:130-135); planes carry the quantised ones
-      if (c.wire && fused_records)
+      if (c.compact)  // the quantised coefficients as the compact stream, straight from the transform (whole-shard launches: p0 = 0)
+        Abi(svc_hip_dct_pack_levels_frames(enc, frame_bytes, pn, pw, ph, c.dct_block_w, types_c, c.mv_block, c.mv_block, c.fg_step, c.bg_step,
+                                           compact_ws.p, compact_ws.bytes(), compact.p, compact.bytes(), compact_off.p, st),
+            "svc_hip_dct_pack_levels_frames");
+      else if (c.wire && fused_records)
         Abi(svc_hip_dct_records_frames(enc, frame_bytes, pn, pw, ph, c.dct_block_w, types_c, c.mv_block, c.mv_block,
                                        0, 0, ph, Records(m).p + (uint64_t)p0 * record_bytes, record_bytes, st), "svc_hip_dct_records_frames");
       else if (c.wire) {  // any other transform block: Dct, then SerializeEncodedFrame
@@ -554,6 +562,14 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
     throw std::runtime_error("svc::ClipEncoder: a clip needs at least two frames and one frame per rank");
   if ((c.dct_block_w == 0) != (c.dct_block_h == 0))
     throw std::runtime_error("svc::ClipEncoder: transform block needs both sides");
+  if (c.compact) {
+    if (c.wire) throw std::runtime_error("svc::ClipEncoder: compact and wire are two different outputs: choose one");
+    if (c.chunk_pairs) throw std::runtime_error("svc::ClipEncoder: compact needs whole-shard launches (chunk_pairs = 0): one launch per step makes the shard's frames one stream");
+    if (c.dct_block_w != c.dct_block_h || (c.dct_block_w != 8 && c.dct_block_w != 16))
+      throw std::runtime_error("svc::ClipEncoder: compact needs an 8x8 or 16x16 transform block");
+    if (c.mv_block % c.dct_block_w != 0) throw std::runtime_error("svc::ClipEncoder: compact needs an MV block that is a multiple of the transform block");
+    if (c.fg_step == 0 || c.bg_step == 0) throw std::runtime_error("svc::ClipEncoder: compact needs quant steps > 0");
+  }
   m.sh = PlanShard(c.clip_frames, c.world, c.rank);
   if (c.schedule == Schedule::kPipelined) {
     if (!c.standalone_shapes) m.lat_flags |= SVC_LAUNCH_BESIDE;
@@ -563,6 +579,7 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
   if (c.lat_depth > (uint32_t)Impl::kMaxDepth) throw std::runtime_error("svc::ClipEncoder: lat_depth must be 0..3");
   static_cast<EncodeGeometry&>(m) = EncodeGeometry(c.width, c.height, c.levels, c.mv_block, c.mv_block);
   const bool transform = c.dct_block_w != 0;
+  if (c.compact && m.pw % 16 != 0) throw std::runtime_error("svc::ClipEncoder: compact needs a padded width of whole 16-pixel segments");
   m.record_bytes = (c.wire && transform) ? svc_hip_serialized_frame_bytes(m.pw, m.ph, c.dct_block_w, c.dct_block_h) : 0;
   m.iters = svc_hip_ransac_iter_count(c.ransac);
   const uint32_t P = m.sh.pairs, N = m.sh.frames;
@@ -624,7 +641,7 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
                    c.mv_block % c.dct_block_w == 0 && P > 0;
   // can this shard ever speculate?  (not when told never to; not -- unless told always to -- when it is too small to pay: then it keeps
   // one set of coefficients and measures nothing)
-  m.spec_quant = !c.wire && !c.two_bgr_passes && transform && c.dct_block_w == c.dct_block_h && (c.dct_block_w == 8 || c.dct_block_w == 16) &&
+  m.spec_quant = !c.wire && !c.compact && !c.two_bgr_passes && transform && c.dct_block_w == c.dct_block_h && (c.dct_block_w == 8 || c.dct_block_w == 16) &&
                  m.pw % 16 == 0 && c.mv_block % 16 == 0 && c.mv_block % c.dct_block_w == 0 && c.fg_step > 0 && c.bg_step > 0 && P > 0 &&
                  (c.always_speculate || c.idle_rule_any_size || (uint64_t)P * m.pw * m.ph >= Impl::kSpecMinPixels);
   // a micro-step's output is written at its front and completed up to depth + 2 iterations later; the same chunk of the NEXT step that uses
@@ -633,7 +650,11 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
   if (transform) {
     if (c.wire)
       for (int b = 0; b < m.rec_sets; ++b) m.records[b].Alloc(kWho, (size_t)P * m.record_bytes);
-    if (!c.wire || !m.fused_records)
+    if (c.compact) {
+      m.compact.Alloc(kWho, svc_hip_levels_max_bytes(P, m.pw, m.ph, c.dct_block_w, c.dct_block_h, c.mv_block, c.mv_block));
+      m.compact_off.Alloc(kWho, (size_t)P + 1);
+      m.compact_ws.Alloc(kWho, svc_hip_dct_pack_levels_workspace_bytes(P, m.pw, m.ph, c.dct_block_w, c.mv_block, c.mv_block));
+    } else if (!c.wire || !m.fused_records)
       m.coeffs[0].Alloc(kWho, (size_t)P * 3 * m.plane_elems);  // the other rec_sets - 1 sets: Impl::GrowCoeffSets, on the first speculation
     if (m.spec_quant) {
       for (int k = 0; k < m.depth; ++k) m.redo_ws[k].Alloc(kWho, svc_hip_dct_redo_workspace_bytes(m.cp, m.pw, m.ph, c.mv_block, c.mv_block));
@@ -737,7 +758,7 @@ void ClipEncoder::StepOn(const uint8_t* frames, bool timed) {
   const uint32_t P = m.sh.pairs;
   uint32_t n = m.nch, cp = m.cp;
   uint8_t order[2] = {0, 0};
-  const bool idle = !m.c.chunk_pairs && m.c.world == 1 && !m.c.whole_shard_steps && m.n_dct == m.n_luma && P >= 2 &&
+  const bool idle = !m.c.chunk_pairs && !m.c.compact && m.c.world == 1 && !m.c.whole_shard_steps && m.n_dct == m.n_luma && P >= 2 &&
                     (m.c.idle_rule_any_size || (uint64_t)P * m.pw * m.ph >= Impl::kIdleRuleMinPixels);
   if (idle && !m.WouldReadOnce()) {  // (polls the newest foreground measurement)
     n = 2; cp = (P + 1) / 2;
@@ -807,6 +828,12 @@ void* ClipEncoder::Output(Buffer b, uint64_t* bytes) {
     case Buffer::kRecords: { auto& r = m.n_dct ? m.Records(m.n_dct - 1) : m.records[0]; ptr = r.p; n = r.bytes(); break; }
     case Buffer::kPyramids: ptr = m.pyr[ppar].p; n = m.pyr[ppar].bytes(); break;
     case Buffer::kBgr: ptr = m.bgr.p; n = m.bgr.bytes(); break;
+    case Buffer::kCompact:  // the bytes the newest step used: offsets[pairs] (everything is synchronised by now)
+      ptr = m.compact.p;
+      if (m.compact.p && m.n_dct && m.sh.pairs)
+        Hip(hipMemcpy(&n, m.compact_off.p + m.sh.pairs, sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+      break;
+    case Buffer::kCompactOffsets: ptr = m.compact_off.p; n = m.compact_off.bytes(); break;
     default: throw std::runtime_error("svc::ClipEncoder: unknown buffer");
   }
   if (bytes) *bytes = n;
@@ -865,7 +892,7 @@ int svc_clip_create(const svc_clip_config* k, svc_clip** out) {
     constexpr uint32_t kTuneBits = SVC_CLIP_TUNE_STANDALONE_SHAPES | SVC_CLIP_TUNE_SEGMENT_FORK | SVC_CLIP_TUNE_NARROW_ATTEMPTS | SVC_CLIP_TUNE_INLINE_RMSE |
                                    SVC_CLIP_TUNE_TWO_BGR_PASSES | SVC_CLIP_TUNE_ALWAYS_SPECULATE | SVC_CLIP_KEEP_FOREGROUND_PRIOR |
                                    SVC_CLIP_TUNE_WHOLE_SHARD_STEPS | SVC_CLIP_TUNE_SEARCH_AFTER_TRANSFORM | SVC_CLIP_TUNE_IDLE_RULE_ANY_SIZE |
-                                   SVC_CLIP_TUNE_MIXED_STEPS | SVC_CLIP_TUNE_RANDOM_POLICY | SVC_CLIP_TUNE_FORK_BEHIND_FRONT;
+                                   SVC_CLIP_TUNE_MIXED_STEPS | SVC_CLIP_TUNE_RANDOM_POLICY | SVC_CLIP_TUNE_FORK_BEHIND_FRONT | SVC_CLIP_OUTPUT_COMPACT;
     if (k->hbma_flags & ~kHbmaBits) throw std::runtime_error("svc_clip_create: unknown hbma_flags bits");
     if (k->tuning & ~kTuneBits) throw std::runtime_error("svc_clip_create: unknown tuning bits");
     if (k->lat_depth > 3) throw std::runtime_error("svc_clip_create: lat_depth must be 0..3");
@@ -891,6 +918,7 @@ int svc_clip_create(const svc_clip_config* k, svc_clip** out) {
     c.mixed_steps = (k->tuning & SVC_CLIP_TUNE_MIXED_STEPS) != 0;
     c.random_policy = (k->tuning & SVC_CLIP_TUNE_RANDOM_POLICY) != 0;
     c.fork_behind_front = (k->tuning & SVC_CLIP_TUNE_FORK_BEHIND_FRONT) != 0;
+    c.compact = (k->tuning & SVC_CLIP_OUTPUT_COMPACT) != 0;
     c.chunk_pairs = k->chunk_pairs;
     std::unique_ptr<svc_clip> h(new svc_clip);
     h->cfg = c;

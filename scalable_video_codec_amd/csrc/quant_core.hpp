@@ -46,4 +46,17 @@ __device__ __forceinline__ f32x2 quant2_fast(f32x2 c, float step, float inv) {
   return q * s2;
 }
 
+// quant2_fast up to its last line: the integer level q itself (an f32 holding an integer, possibly -0.0), for the kernel that
+// packs levels instead of storing q * step (dct_pack.hip).  Every level a coefficient can reach here has q * step exact in f32
+// (|q * step| <= |c| + step / 2 < 2^24), so std::round((q * step) / step) -- what the pack reads back from the planes -- is q.
+__device__ __forceinline__ f32x2 quant2_level(f32x2 c, float step, float inv) {
+  const f32x2 s2 = {step, step}, i2 = {inv, inv};
+  const f32x2 q0 = c * i2;
+  const f32x2 r = __builtin_elementwise_fma(-q0, s2, c);
+  f32x2 q = __builtin_elementwise_fma(r, i2, q0);
+  const f32x2 h = {__builtin_copysignf(0.49999997f, q0.x), __builtin_copysignf(0.49999997f, q0.y)};
+  q = q + h;
+  return f32x2{__builtin_truncf(q.x), __builtin_truncf(q.y)};
+}
+
 }  // namespace svc

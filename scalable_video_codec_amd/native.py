@@ -122,6 +122,8 @@ SIGNATURES = {
     "svc_hip_pack_levels_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_pack_levels_frames": (C.c_int, [_vp, _vp] + [_u32] * 9 + [_vp, _u64, _vp, _u64, _vp, _vp]),
     "svc_hip_unpack_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _vp, _vp, _vp]),
+    "svc_hip_dct_pack_levels_workspace_bytes": (_u64, [_u32] * 6),
+    "svc_hip_dct_pack_levels_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 + [_vp, _u64, _vp, _u64, _vp, _vp]),
     "svc_hip_levels_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
     # its lossless entropy coding, "SVCE" (csrc/entropy.hip; the drain in csrc/levels.hip)
     "svc_hip_entropy_max_bytes": (_u64, [_u32] * 7),
@@ -722,6 +724,34 @@ def pack_levels_frames(planes: torch.Tensor, block_types: torch.Tensor, block, m
     _check(load().svc_hip_pack_levels_frames(_dev(planes, torch.float32), _dev(block_types, torch.int32), n, w, h, bw, bh, mbw, mbh,
                                              fg_step, bg_step, _dev(workspace, torch.uint8), workspace.numel(),
                                              _dev(out, torch.uint8), out.numel(), _dev(offsets, torch.int64), _stream()))
+    return out, offsets
+
+
+def dct_pack_levels_workspace_bytes(n: int, w: int, h: int, block: int, mv_block) -> int:
+    """Scratch of dct_pack_levels_frames; 0 for a geometry it refuses (then: dct_quant_frames + pack_levels_frames)."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_levels_workspace_bytes(n, w, h, block, mbw, mbh))
+
+
+def dct_pack_levels_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, fg_step: int, bg_step: int,
+                           out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """B,G,R frames (frames, H, W, 3) u8 + region ids (frames, blocks) i32 -> the compact stream of dct_quant_frames +
+    pack_levels_frames, byte for byte, without the planes: (stream u8 of the worst-case size, offsets (frames + 1,) i64 on the
+    device).  8x8 / 16x16 blocks on widths that are multiples of 16; anything else raises (use the two calls)."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    dev = bgr.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_levels_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    _check(load().svc_hip_dct_pack_levels_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                 _dev(block_types, torch.int32), mbw, mbh, fg_step, bg_step,
+                                                 _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
+                                                 _dev(offsets, torch.int64), _stream()))
     return out, offsets
 
 

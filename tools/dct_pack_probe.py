@@ -1,0 +1,127 @@
+"""The compact stream straight from the transform kernel (csrc/dct_pack.hip) against the two-call route it replaces, at C3 (1080p,
+8x8 tiles, steps 1 / 640) or C5 (4K, 16x16 tiles).
+
+  python tools/dct_pack_probe.py kernels [C3|C5]   one batch of 16 encoded frames, region ids from the pipeline; the two-call route
+                                                   (svc_hip_dct_quant_frames + svc_hip_pack_levels_frames) 5 times, then the fused
+                                                   route (svc_hip_dct_pack_levels_frames) 5 times; the bytes are compared.  Run under
+                                                   `rocprofv3 --kernel-trace --stats -- python ...` (a kernel trace only)
+  python tools/dct_pack_probe.py fused [C3|C5]     the fused route alone, 5 times (for a counter run of its own: `rocprofv3 --pmc ...`)
+  python tools/dct_pack_probe.py step [C3|C5] [frames]
+                                                   svc::ClipEncoder over a resident clip (default 300 frames = 299 pairs), serial and
+                                                   pipelined: the compact step against the two-pass planes step plus the pack of its
+                                                   output; wall time per step over back-to-back steps
+"""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from scalable_video_codec_amd import clip as clipmod  # noqa: E402
+from scalable_video_codec_amd import configs, native, pipeline, synth  # noqa: E402
+
+
+def _cfg(argv, k):
+    return {"C3": configs.C3, "C5": configs.C5}[argv[k] if len(argv) > k else "C3"]
+
+
+def _batch(cfg, n):
+    """n + 1 padded frames on the device and the pipeline's region ids for the n encoded ones."""
+    dev = torch.device("cuda")
+    clip = synth.SynthClip(cfg.width, cfg.height, n + 1, cfg.seed, device=dev)
+    pw, ph = cfg.padded
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(n + 1)]).contiguous()
+    enc = pipeline.ClipEncoder(cfg, n + 1, dev)
+    enc.load_frames(list(frames))
+    enc.step()
+    torch.cuda.synchronize()
+    return frames[1:].contiguous(), enc.types.clone()
+
+
+def kernels(cfg, fused_only=False) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, cfg.dct_block, cfg.mv_block)
+    offs, offs2 = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    out2 = torch.empty(cap, dtype=torch.uint8, device=dev)
+    ws2 = torch.empty(native.dct_pack_levels_workspace_bytes(n, pw, ph, cfg.dct_block, cfg.mv_block), dtype=torch.uint8, device=dev)
+    if not fused_only:
+        planes = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=dev)
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        ws = torch.empty(native.pack_levels_workspace_bytes(n, pw, ph, cfg.dct_block), dtype=torch.uint8, device=dev)
+        for _ in range(5):
+            native.dct_quant_frames(bgr, cfg.dct_block, types, cfg.mv_block, cfg.fg_step, cfg.bg_step, out=planes)
+            native.pack_levels_frames(planes, types, cfg.dct_block, cfg.mv_block, cfg.fg_step, cfg.bg_step, out=out, offsets=offs, workspace=ws)
+    for _ in range(5):
+        native.dct_pack_levels_frames(bgr, cfg.dct_block, types, cfg.mv_block, cfg.fg_step, cfg.bg_step, out=out2, offsets=offs2, workspace=ws2)
+    torch.cuda.synchronize()
+    total = int(offs2[-1].item())
+    if not fused_only:
+        assert torch.equal(offs, offs2) and torch.equal(out[:total], out2[:total]), "the fused route's bytes differ from the two calls'"
+    print(f"{cfg.name} batch of {n}: {total} B compact ({total / n / 1e6:.3f} MB per frame), planes {3 * pw * ph * 4 / 1e6:.2f} MB per frame, "
+          f"fused workspace {ws2.numel() / n / 1e6:.2f} MB per frame" + ("" if fused_only else "; fused bytes == two-call bytes"), flush=True)
+
+
+def _per_step(fn, sync, warm=2, reps=3, steps=4):
+    """Wall ms per call of fn over `steps` back-to-back calls and one sync; the best and the worst of `reps` such runs."""
+    for _ in range(warm):
+        fn()
+    sync()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        sync()
+        ts.append((time.perf_counter() - t0) * 1e3 / steps)
+    return min(ts), max(ts)
+
+
+def step(cfg, frames_n) -> None:
+    dev = torch.device("cuda")
+    clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=dev)
+    pw, ph = cfg.padded
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(frames_n)]).contiguous()
+    for schedule, name in ((clipmod.SERIAL, "serial"), (clipmod.PIPELINED, "pipelined")):
+        # the planes step in the two-pass order, and the pack of its output
+        enc = clipmod.Clip(cfg, frames_n, schedule=schedule, tuning=clipmod.TUNE_TWO_BGR_PASSES | clipmod.TUNE_WHOLE_SHARD_STEPS)
+        enc.load_frames(frames)
+        planes_ms = _per_step(enc.step, enc.sync)
+        i = enc.info
+        coeffs = enc.read("coeffs", device=dev).view(i.pairs, 3, ph, pw)
+        types = enc.read("block_types", device=dev).view(i.pairs, i.blocks)
+        enc.close()
+        del enc
+        out = torch.empty(native.levels_max_bytes(i.pairs, pw, ph, cfg.dct_block, cfg.mv_block), dtype=torch.uint8, device=dev)
+        offs = torch.empty(i.pairs + 1, dtype=torch.int64, device=dev)
+        ws = torch.empty(native.pack_levels_workspace_bytes(i.pairs, pw, ph, cfg.dct_block), dtype=torch.uint8, device=dev)
+        pack_ms = _per_step(lambda: native.pack_levels_frames(coeffs, types, cfg.dct_block, cfg.mv_block, cfg.fg_step, cfg.bg_step, out=out,
+                                                              offsets=offs, workspace=ws), torch.cuda.synchronize)
+        want, want_offs = out[:int(offs[-1].item())].cpu(), offs.cpu()
+        del coeffs, out, ws
+        torch.cuda.empty_cache()
+        enc = clipmod.Clip(cfg, frames_n, schedule=schedule, compact=True)
+        enc.load_frames(frames)
+        compact_ms = _per_step(enc.step, enc.sync)
+        got, got_offs = enc.read_compact()
+        assert torch.equal(got_offs, want_offs) and torch.equal(got, want), "the compact step's bytes differ from the pack of the planes"
+        enc.close()
+        del enc
+        torch.cuda.empty_cache()
+        print(f"{cfg.name} {name}, {i.pairs} pairs, ms per step (best .. worst of 3 runs of 4 back-to-back steps): planes step "
+              f"{planes_ms[0]:.3f} .. {planes_ms[1]:.3f} + pack {pack_ms[0]:.3f} .. {pack_ms[1]:.3f} = {planes_ms[0] + pack_ms[0]:.3f} .. "
+              f"{planes_ms[1] + pack_ms[1]:.3f}; compact step {compact_ms[0]:.3f} .. {compact_ms[1]:.3f} "
+              f"({(planes_ms[0] + pack_ms[0]) / compact_ms[0]:.2f}x); {got.numel() / i.pairs / 1e6:.3f} MB per frame, same bytes", flush=True)
+
+
+if __name__ == "__main__":
+    mode = sys.argv[1] if len(sys.argv) > 1 else "kernels"
+    if mode == "step":
+        step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
+    else:
+        kernels(_cfg(sys.argv, 2), fused_only=mode == "fused")
