@@ -123,7 +123,8 @@ struct ClipEncoderConfig {
 enum class Stage : uint32_t { kLumaPyramid = 0, kHalo, kHbma, kRansac, kSegment, kTransform, kTypePatch, kCount };
 enum class Buffer : uint32_t { kMv = 0, kMinMad, kGlobalMotion, kRmse, kInlierMask, kInlierCount, kBlockTypes,
                                kCoeffs, kRecords, kPyramids, kBgr,
-                               kCompact /* offsets[pairs] bytes of SVCQ frames, back to back */, kCompactOffsets /* [pairs + 1] u64 */, kCount };
+                               kCompact /* offsets[pairs] bytes of SVCQ frames, back to back */, kCompactOffsets /* [pairs + 1] u64 */,
+                               kCompactChoice /* SetCompactBudget: [pairs] u32, the ladder entry of each frame; empty without a budget */, kCount };
 
 class ClipEncoder {
  public:
@@ -166,6 +167,13 @@ class ClipEncoder {
   // newest finished step's; a step's small outputs live for depth + 2 steps, its planes / records for output_sets() steps.
   uint32_t StepFrames(const uint8_t* device_frames, bool timed = false);
   void WaitStep(uint32_t step);  // returns once nothing reads that step's frames any more
+  // Rate control of the compact stream (ClipEncoderConfig::compact; throws otherwise): every step submitted after this call packs each frame
+  // with the finest pair of `ladder` (1 .. 64 pairs, finest first, every step > 0, fg_step and bg_step each non-decreasing) whose frame fits
+  // bytes_per_frame SVCQ bytes -- svc_hip_dct_pack_levels_budget_frames in place of svc_hip_dct_pack_levels_frames, still without planes.
+  // Buffer::kCompactChoice then holds each frame's ladder entry, bit 31 set where even the last one is over budget.  Sync()s first;
+  // the ladder is checked by the C ABI's pointer-free checks (std::runtime_error with its message).  ladder_len == 0 returns to the fixed
+  // fg_step / bg_step.  The first call allocates the larger workspace, a budget and a choice per pair.
+  void SetCompactBudget(const svc_step_pair* ladder, uint32_t ladder_len, uint32_t bytes_per_frame);
   void Flush();  // pipelined schedule: enqueues what is left of the steps in flight
   void Sync();   // Flush() + waits for every stream
 

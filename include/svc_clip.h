@@ -97,7 +97,8 @@ enum { SVC_STAGE_LUMA_PYRAMID = 0, SVC_STAGE_HALO, SVC_STAGE_HBMA, SVC_STAGE_RAN
 /* buffer ids for svc_clip_output / svc_clip_read */
 enum { SVC_BUF_MV = 0, SVC_BUF_MIN_MAD, SVC_BUF_GLOBAL_MOTION, SVC_BUF_RMSE, SVC_BUF_INLIER_MASK,
        SVC_BUF_INLIER_COUNT, SVC_BUF_BLOCK_TYPES, SVC_BUF_COEFFS, SVC_BUF_RECORDS, SVC_BUF_PYRAMIDS,
-       SVC_BUF_BGR, SVC_BUF_COMPACT /* bytes = offsets[pairs] of the newest step */, SVC_BUF_COMPACT_OFFSETS, SVC_BUF_COUNT };
+       SVC_BUF_BGR, SVC_BUF_COMPACT /* bytes = offsets[pairs] of the newest step */, SVC_BUF_COMPACT_OFFSETS,
+       SVC_BUF_COMPACT_CHOICE /* svc_clip_set_compact_budget: pairs x u32, each frame's ladder entry; empty without a budget */, SVC_BUF_COUNT };
 
 /* Halo transport override: must enqueue on `stream` the send of `bytes` from d_send to rank + 1
  * (if any) and the receive into d_recv from rank - 1 (if any). */
@@ -129,6 +130,11 @@ int svc_clip_step(svc_clip* clip, int timed); /* enqueue one pass over the shard
    *step (optional) receives the step's number; the frames must stay untouched until svc_clip_wait_step(clip, that number) or svc_clip_sync. */
 int svc_clip_step_frames(svc_clip* clip, const uint8_t* device_frames, int timed, uint32_t* step);
 int svc_clip_wait_step(svc_clip* clip, uint32_t step); /* returns once nothing reads that step's frames any more */
+/* Rate control of the compact stream (a handle made with SVC_CLIP_OUTPUT_COMPACT; 1 otherwise): syncs, then every later step packs each frame with
+   the finest of `ladder`'s ladder_len pairs (1 .. 64, finest first, rules of svc_hip_dct_pack_levels_budget_frames, whose message a bad ladder
+   gives) whose frame fits bytes_per_frame SVCQ bytes, and SVC_BUF_COMPACT_CHOICE holds the entries chosen (bit 31: over budget).
+   ladder_len == 0 returns to the fixed fg_step / bg_step.  A call and not a config field: svc_clip_config keeps its layout. */
+int svc_clip_set_compact_budget(svc_clip* clip, const svc_step_pair* ladder, uint32_t ladder_len, uint32_t bytes_per_frame);
 int svc_clip_flush(svc_clip* clip);           /* enqueue what the pipeline still holds */
 int svc_clip_sync(svc_clip* clip);            /* flush + wait for the GPU */
 

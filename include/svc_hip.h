@@ -603,6 +603,34 @@ int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_b
                                       uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
                                       uint64_t* d_frame_offsets, uint32_t* d_choice /* [n_frames] */, void* stream);
 
+/* The same rate control straight from the transform: d_out, d_frame_offsets (all n + 1) and
+ * d_choice receive, byte for byte, what svc_hip_dct_frames followed by
+ * svc_hip_pack_levels_budget_frames leave for the same frames, region ids, ladder and budgets
+ * (header steps, level_count, inexact = 0, frame_bytes, padding, bit 31 of choice for a frame over
+ * budget) -- equivalently, frame f is what svc_hip_dct_pack_levels_frames writes with pair
+ * choice[f] & 0x7FFFFFFF -- and nothing is written past offsets[n].  No f32 plane is made: a first
+ * pass of the transform counts, per wave, the coefficients each ladder entry keeps (|c| >= the
+ * threshold below which entry k's step quantises to zero), a sum and a per-frame selection pick
+ * the pair, and the fused call's three passes run with each frame's own steps.
+ * Geometry as svc_hip_dct_pack_levels_frames (block = 8 or 16, frame_w a multiple of 16: anything
+ * else is SVC_ERR_UNSUPPORTED and a workspace of 0); ladder rules as
+ * svc_hip_pack_levels_budget_frames (a workspace of 0 for ladder_len outside 1 .. 64).  The
+ * workspace is the fused call's plus 256 bytes per wave of the transform and 8 KB per frame.
+ * Checked for any n_frames and before any launch: geometry, stride, ladder, limits, workspace,
+ * out_capacity against svc_hip_levels_max_bytes; n_frames == 0 then returns SVC_OK; then pointers
+ * and alignment (frames, output, workspace 16-byte, offsets 8-byte, types, budget, choice 4-byte).
+ * Only enqueues work. */
+uint64_t svc_hip_dct_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                        uint32_t block, uint32_t mv_block_w, uint32_t mv_block_h,
+                                                        uint32_t ladder_len);
+int svc_hip_dct_pack_levels_budget_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames,
+                                          uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                          const uint32_t* d_block_types, uint32_t mv_block_w, uint32_t mv_block_h,
+                                          const svc_step_pair* ladder /* host, ladder_len entries */, uint32_t ladder_len,
+                                          const uint32_t* d_budget /* [n_frames] bytes */,
+                                          uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                          uint64_t* d_frame_offsets, uint32_t* d_choice /* [n_frames] */, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Headless decoder of the compact stream: DecodeBlock over every tile with a gaze rectangle per
  * frame (libs/decoder.cpp:128-149, :168-207), then the picture the reference shows.

@@ -32,7 +32,8 @@ STAGES = ("luma_pyramid", "halo_exchange", "hbma", "ransac", "segment", "dct_qua
 BUFFERS = {"mv": (0, torch.float32), "min_mad": (1, torch.float32), "global_motion": (2, torch.float32),
            "rmse": (3, torch.float32), "inlier_mask": (4, torch.uint8), "inlier_count": (5, torch.int32),
            "block_types": (6, torch.int32), "coeffs": (7, torch.float32), "records": (8, torch.uint8),
-           "pyramids": (9, torch.uint8), "bgr": (10, torch.uint8), "compact": (11, torch.uint8), "compact_offsets": (12, torch.int64)}
+           "pyramids": (9, torch.uint8), "bgr": (10, torch.uint8), "compact": (11, torch.uint8), "compact_offsets": (12, torch.int64),
+           "compact_choice": (13, torch.int32)}
 COMM_ID_BYTES = 128
 
 
@@ -65,6 +66,7 @@ SIGNATURES = {
     "svc_clip_step": (C.c_int, [_vp, C.c_int]),
     "svc_clip_step_frames": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_u32)]),
     "svc_clip_wait_step": (C.c_int, [_vp, _u32]),
+    "svc_clip_set_compact_budget": (C.c_int, [_vp, C.POINTER(native.StepPair), _u32, _u32]),
     "svc_clip_flush": (C.c_int, [_vp]),
     "svc_clip_sync": (C.c_int, [_vp]),
     "svc_clip_stage_time": (C.c_int, [_vp, _u32, C.POINTER(C.c_double), C.POINTER(_u32)]),
@@ -238,6 +240,14 @@ class Clip:
 
     def wait_step(self, step: int) -> None:
         _check(load().svc_clip_wait_step(self._h, step))
+
+    def set_compact_budget(self, ladder, bytes_per_frame: int) -> None:
+        """Rate control of a clip made with compact=True: every later step packs each frame with the finest (fg_step, bg_step) of `ladder`
+        whose frame fits bytes_per_frame SVCQ bytes (svc_hip_dct_pack_levels_budget_frames); read("compact_choice") then gives each frame's
+        entry (bit 31 set: a negative int32 where even the last one is over budget).  An empty ladder returns to the configuration's steps.
+        Syncs first."""
+        arr, k = native._ladder(ladder)
+        _check(load().svc_clip_set_compact_budget(self._h, arr, k, bytes_per_frame))
 
     def flush(self) -> None:
         _check(load().svc_clip_flush(self._h))

@@ -20,8 +20,21 @@
 //   dct_pack_scan_kernel      one workgroup per frame: piece counts -> exclusive prefixes, the frame's level count and size;
 //   dct_pack_assemble_kernel  the frame's offset (the sizes of the frames before it, as the pack's scatter sums them), header, types,
 //                             masks, every piece's levels to levels_off + 2 * prefix, the zero pad, offsets[f + 1].
+//
+// Rate control (svc_hip_dct_pack_levels_budget_frames): the rule of the budgeted pack of levels.hip -- per frame the finest pair of a
+// ladder whose frame fits a byte budget -- without its planes.  Two launches in front of the three above:
+//   dct_count_kernel<N>       the transform up to the column pass's f32 coefficients (the SAME body as dct_pack_kernel<N>: one template,
+//                             a flag), then per coefficient e = the number of ladder entries that keep it, |c| >= tau[class][k] (tau is
+//                             non-decreasing in k: a binary search over a table in LDS), a histogram of e per wave in LDS, and the
+//                             wave's row of it to the workspace;
+//   dct_count_sum_kernel      the frame's rows summed in kSumParts interleaved parts (one workgroup per frame took 142 us for the
+//                             planes route's counts: profiles/levels_budget_c3.txt);
+//   dct_pack_select_kernel    one workgroup per frame: the sum of the parts, nz_k as its suffix sum, bytes_k, the choice
+//                             (budget_core.hpp) and the frame's steps, which dct_pack_kernel and the assemble pass then read per frame.
 #include <algorithm>
+#include <type_traits>
 
+#include "budget_core.hpp"
 #include "dct_core.hpp"
 #include "quant_core.hpp"
 #include "stream_format.hpp"
@@ -38,6 +51,20 @@ struct DctPackWs {
   uint32_t* counts;      // [n][pieces] levels of a piece, then (scan) their exclusive prefix
   uint32_t* frame_bytes; // [n]
   uint32_t* frame_levels;// [n]
+};
+
+// a frame's steps as the budgeted call's selection leaves them: the pair, and RN(1 / step) of each as the host computes it
+struct FrameSteps {
+  uint32_t fg, bg;
+  float fg_inv, bg_inv;
+};
+
+// the budgeted call's part of the workspace, behind the pack's own
+constexpr uint32_t kSumParts = 32;  // workgroups that share the sum of a frame's rows
+struct BudgetWs {
+  uint32_t* rows;     // [n][waves of a frame][kMaxLadder]: a wave's coefficients that exactly k + 1 entries keep (the last entry: all)
+  uint32_t* parts;    // [n][kSumParts][kMaxLadder]: the rows of a frame summed part by part
+  FrameSteps* steps;  // [n]
 };
 
 struct PackGeom {
@@ -64,6 +91,21 @@ uint64_t pack_ws_bytes(uint32_t n, const PackGeom& g) {
   return 2ull * kPieceLevels * n * g.pieces + (uint64_t)n * up16(4ull * g.mask_dwords) + up16(4ull * n * g.pieces) + 2 * up16(4ull * n);
 }
 
+uint64_t budget_ws_bytes(uint32_t n, const PackGeom& g) {
+  return pack_ws_bytes(n, g) + 4ull * kMaxLadder * n * (g.l.tiles_y * g.waves_per_row + kSumParts) + up16(sizeof(FrameSteps) * (uint64_t)n);
+}
+
+BudgetWs carve_budget(uint8_t* p, uint32_t n, const PackGeom& g) {
+  BudgetWs s;
+  p += pack_ws_bytes(n, g);
+  s.rows = reinterpret_cast<uint32_t*>(p);
+  p += 4ull * kMaxLadder * n * g.l.tiles_y * g.waves_per_row;
+  s.parts = reinterpret_cast<uint32_t*>(p);
+  p += 4ull * kMaxLadder * n * kSumParts;
+  s.steps = reinterpret_cast<FrameSteps*>(p);
+  return s;
+}
+
 DctPackWs carve(uint8_t* p, uint32_t n, const PackGeom& g) {
   DctPackWs s;
   s.slots = reinterpret_cast<int16_t*>(p);
@@ -85,8 +127,18 @@ struct DctPackArgs {
   uint32_t total_waves;       // frames * tile rows * waves per row
   const uint32_t* types;
   float fg_step, bg_step, fg_inv, bg_inv;  // inv = RN(1 / step), computed on the host
+  const FrameSteps* steps;    // [n] each frame's own steps (the budgeted call), or null: the four above for every frame
   DctPackWs ws;
 };
+
+// what the counting form takes besides: the ladder, its search depth and where the waves' rows go
+struct CountArgs {
+  Ladder lad;
+  uint32_t probes;  // bit length of lad.len: the probes that find e in 0 .. lad.len
+  uint32_t* rows;
+};
+struct NoCountArgs {};
+constexpr uint32_t kTauTable = 2 * kMaxLadder;  // a class's thresholds, padded with +inf to what 7 probes can reach
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -96,8 +148,12 @@ __device__ __forceinline__ uint32_t pack2(f32x2 q) {  // two levels as int16, th
   return ((uint32_t)(int32_t)q.x & 0xFFFFu) | ((uint32_t)(int32_t)q.y << 16);
 }
 
-template <int N>
-__global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
+// COUNT = false: the fused pack.  COUNT = true: the same transform, stopped at the column pass's f32 coefficients, which are counted per
+// ladder entry instead of quantised: k, and the counting kernel's LDS -- both classes' thresholds, tau_tab[c][i] = tau[c][i] (+inf from
+// the ladder's end on), and a histogram per wave (null for the pack).
+template <int N, bool COUNT>
+__device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::conditional_t<COUNT, CountArgs, NoCountArgs>& k,
+                                              float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
   constexpr uint32_t kCols = 64 / N;        // segment columns of a wave
   constexpr uint32_t kColWords = N / 4;     // mask words of a segment column: two 8x8 tiles of one word, or one 16x16 tile of four
   constexpr int kSlab = N == 8 ? kSlab8 : kSlab16;
@@ -113,6 +169,12 @@ __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, sc_local = tid / N, j = tid % N, g = lane / N;
   // the wave's place: (frame, tile row, wave in the row), the same in every lane
   const uint32_t wv = __builtin_amdgcn_readfirstlane(xcd_contiguous_block(blockIdx.x, gridDim.x) * 4u + (tid >> 6));
+  if constexpr (COUNT) {
+    const uint32_t c = tid / kTauTable, i = tid % kTauTable;  // 256 threads = 2 classes x 128 entries
+    tau_tab[c][i] = i < k.lad.len ? k.lad.tau[c][i] : INFINITY;
+    hist_all[tid >> 6][lane] = 0;
+    __syncthreads();  // the only workgroup barrier, in front of the first exit
+  }
   if (wv >= a.total_waves) return;
   const uint32_t row_g = wv / gm.waves_per_row, wr = wv - row_g * gm.waves_per_row;
   const uint32_t frame = row_g / gm.l.tiles_y, band = row_g - frame * gm.l.tiles_y;
@@ -134,7 +196,13 @@ __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
     const uint32_t col = N == 8 ? x_pix + 2 * j : x_pix + j;
     t = a.types[(size_t)frame * gm.l.mvb + (y_pix / gm.mvbh) * gm.l.mfw + col / gm.mvbw];
   }
-  const float step = t == 0 ? a.bg_step : a.fg_step, inv_step = t == 0 ? a.bg_inv : a.fg_inv;
+  float step = t == 0 ? a.bg_step : a.fg_step, inv_step = t == 0 ? a.bg_inv : a.fg_inv;
+  if (!COUNT && a.steps) {  // the wave's own frame's pair: one workgroup's four waves can belong to four frames
+    const FrameSteps fs = a.steps[frame];
+    step = (float)(t == 0 ? fs.bg : fs.fg);  // libs/decoder.cpp:141 divides a float by an unsigned
+    inv_step = t == 0 ? fs.bg_inv : fs.fg_inv;
+  }
+  uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
 
   uint8_t* slab = lds + sc_local * kSlab;
   const uint8_t* wave_slabs = lds + (sc_local - g) * kSlab;
@@ -159,6 +227,7 @@ __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
     wave_lds_sync();
 
     uint32_t lv[8];  // this lane's levels of the channel, two int16 each
+    float m[16];     // COUNT: |c| of its 16 coefficients instead
     if (N == 8) {
       // lane j takes columns 2j, 2j+1 of the 16-wide slab (tile j >> 2): lv[v] = row v
       double ca[8], cb[8], ya[8], yb[8];
@@ -171,7 +240,14 @@ __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
       dct1d<8, double>(ca, ya);
       dct1d<8, double>(cb, yb);
 #pragma unroll
-      for (int v = 0; v < 8; ++v) lv[v] = pack2(quant2_level(f32x2{(float)ya[v], (float)yb[v]}, step, inv_step));
+      for (int v = 0; v < 8; ++v) {
+        if constexpr (COUNT) {
+          m[2 * v] = fabsf((float)ya[v]);
+          m[2 * v + 1] = fabsf((float)yb[v]);
+        } else {
+          lv[v] = pack2(quant2_level(f32x2{(float)ya[v], (float)yb[v]}, step, inv_step));
+        }
+      }
     } else {
       // lane j takes column j: lv[v / 2] = rows v, v + 1
       double cc[16], yy[16];
@@ -179,9 +255,39 @@ __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
       for (int y = 0; y < 16; ++y) cc[y] = *reinterpret_cast<const double*>(slab + y * kRowPitch + j * 8);
       dct1d<16, double>(cc, yy);
 #pragma unroll
-      for (int v = 0; v < 16; v += 2) lv[v / 2] = pack2(quant2_level(f32x2{(float)yy[v], (float)yy[v + 1]}, step, inv_step));
+      for (int v = 0; v < 16; v += 2) {
+        if constexpr (COUNT) {
+          m[v] = fabsf((float)yy[v]);
+          m[v + 1] = fabsf((float)yy[v + 1]);
+        } else {
+          lv[v / 2] = pack2(quant2_level(f32x2{(float)yy[v], (float)yy[v + 1]}, step, inv_step));
+        }
+      }
     }
     wave_lds_sync();  // every lane of the column has read the slab: it becomes the column's tile images
+
+    if constexpr (COUNT) {
+      // e = the entries that keep a coefficient = the thresholds of its class (the lane's: a lane's coefficients lie in one tile) that
+      // are <= |c|.  tau is non-decreasing and the table ends in +inf, so e is found bit by bit, highest first: with e' of the earlier
+      // probes, bit b is set exactly when tab[e' + 2^b - 1] <= |c|.  Sixteen independent searches per probe keep the LDS reads in flight.
+      const float* tab = tau_tab[t == 0 ? 0 : 1];
+      uint32_t e[16] = {};
+#pragma unroll
+      for (int b = 6; b >= 0; --b) {
+        if ((uint32_t)b >= k.probes) continue;  // the same in every lane
+#pragma unroll
+        for (int i = 0; i < 16; ++i) e[i] += m[i] >= tab[e[i] + ((1u << b) - 1u)] ? (1u << b) : 0u;
+      }
+      // bin e - 1 of the wave's histogram; e = 0 is nobody's level and e = len (every tile's DC, a flat frame's every level) is counted
+      // in a register: neither serialises the wave's adds on one bin
+      uint32_t* hist = hist_all[tid >> 6];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        full += e[i] == k.lad.len ? 1u : 0u;
+        if (e[i] != 0 && e[i] != k.lad.len) atomicAdd(&hist[e[i] - 1], 1u);
+      }
+      continue;  // (the slabs are free for the next channel: the sync above)
+    }
 
     if (N == 8) {
       uint8_t* img = slab + image_at(g, j >> 2) + (j & 3u) * 4;  // coefficient (v, 2 (j & 3)) of tile j >> 2: 2 * (v * 8 + 2 (j & 3)) bytes in
@@ -222,6 +328,76 @@ __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
     if (lane == 0) a.ws.counts[piece] = base;
     wave_lds_sync();  // the slabs are rewritten by the next channel
   }
+  if constexpr (COUNT) {  // the wave's row: bins 0 .. len - 2 as they are, bin len - 1 = the lanes' full counts
+    uint32_t* hist = hist_all[tid >> 6];
+    if (full) atomicAdd(&hist[k.lad.len - 1], full);
+    wave_lds_sync();
+    k.rows[(size_t)wv * kMaxLadder + lane] = hist[lane];
+  }
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
+  dct_pack_body<N, false>(a, NoCountArgs{}, nullptr, nullptr);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void dct_count_kernel(DctPackArgs a, CountArgs k) {
+  __shared__ float tau_tab[2][kTauTable];
+  __shared__ uint32_t hist_all[kThreads / 64][kMaxLadder];
+  dct_pack_body<N, true>(a, k, tau_tab, hist_all);
+}
+
+// Column `lane` of rows first, first + step, ... below count, summed over the workgroup's four waves: every thread gets its column's sum
+// (unsigned sums: any order gives the same bytes).
+__device__ __forceinline__ uint32_t sum_rows(const uint32_t* __restrict__ rows, uint32_t first, uint32_t step, uint32_t count,
+                                             uint32_t (*part)[kMaxLadder]) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t s = 0;
+#pragma unroll 4
+  for (uint32_t r = first + wave * step; r < count; r += (kThreads / 64) * step) s += rows[(size_t)r * kMaxLadder + lane];
+  part[wave][lane] = s;
+  __syncthreads();
+  return part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+}
+
+// grid (kSumParts, frames): part p of frame f = the sum of its waves' rows p, p + kSumParts, ...
+__global__ __launch_bounds__(256) void dct_count_sum_kernel(uint32_t rows_per_frame, const uint32_t* __restrict__ rows, uint32_t* __restrict__ parts) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  const uint32_t f = blockIdx.y;
+  const uint32_t v = sum_rows(rows + (size_t)f * rows_per_frame * kMaxLadder, blockIdx.x, kSumParts, rows_per_frame, part);
+  if (threadIdx.x < kMaxLadder) parts[((size_t)f * kSumParts + blockIdx.x) * kMaxLadder + threadIdx.x] = v;
+}
+
+// One workgroup per frame: bin k of the summed rows = the coefficients that exactly k + 1 entries keep (the last entry: all of them), so
+// nz_k = the suffix sum from bin k; bytes_k = up16(levels_off + 2 nz_k); the choice, and the chosen pair's steps.
+struct SelectArgs {
+  uint64_t levels_off;
+  const uint32_t* parts;
+  const uint32_t* budget;
+  FrameSteps* steps;
+  uint32_t* choice;
+};
+struct LadderInv {
+  float inv[2][kMaxLadder];  // RN(1 / step), computed on the host as the fixed call computes it
+};
+
+__global__ __launch_bounds__(256) void dct_pack_select_kernel(Ladder lad, LadderInv li, SelectArgs a) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  __shared__ uint64_t bytes[kMaxLadder];
+  const uint32_t f = blockIdx.x, lane = threadIdx.x & 63u;
+  uint32_t nz = sum_rows(a.parts + (size_t)f * kSumParts * kMaxLadder, 0, 1, kSumParts, part);
+  if (threadIdx.x >= 64) return;
+  for (uint32_t off = 1; off < 64; off <<= 1) {  // inclusive suffix sum over the lanes
+    const uint32_t up = __shfl_down(nz, off, 64);
+    if (lane + off < 64) nz += up;
+  }
+  bytes[lane] = up16(a.levels_off + 2ull * nz);
+  wave_lds_sync();
+  if (lane != 0) return;
+  const uint32_t ch = budget_choice(bytes, lad.len, a.budget[f]), pick = ch & 0x7FFFFFFFu;
+  a.choice[f] = ch;
+  a.steps[f] = FrameSteps{lad.step[1][pick], lad.step[0][pick], li.inv[1][pick], li.inv[0][pick]};
 }
 
 // one workgroup per frame: piece counts -> exclusive prefixes (in place), the frame's level count and size
@@ -247,6 +423,7 @@ __global__ __launch_bounds__(256) void dct_pack_scan_kernel(uint32_t pieces, uin
 struct AssembleArgs {
   PackGeom g;
   uint32_t fg, bg;
+  const FrameSteps* steps;  // [n] each frame's own pair for its header (the budgeted call), or null: fg / bg
   const uint32_t* types;  // [n][mvb]
   DctPackWs ws;
   uint8_t* out;
@@ -295,7 +472,8 @@ __global__ __launch_bounds__(256) void dct_pack_assemble_kernel(AssembleArgs a) 
   // header (inexact = 0: every level reproduces its quantised coefficient), types, pad, offsets
   uint32_t* hdr = reinterpret_cast<uint32_t*>(frame);
   if (threadIdx.x < kHeaderWords) {
-    const uint32_t v[kHeaderWords] = {kMagicQ, kVersion, g.w, g.h, g.n_block, g.n_block, g.mvbw, g.mvbh, a.fg, a.bg, level_count, 0,
+    const uint32_t fg = a.steps ? a.steps[f].fg : a.fg, bg = a.steps ? a.steps[f].bg : a.bg;
+    const uint32_t v[kHeaderWords] = {kMagicQ, kVersion, g.w, g.h, g.n_block, g.n_block, g.mvbw, g.mvbh, fg, bg, level_count, 0,
                                       fbytes, 0, 0, 0};
     hdr[threadIdx.x] = v[threadIdx.x];
   }
@@ -329,6 +507,24 @@ int validate_pack_limits(const char* what, uint32_t n, const PackGeom& g) {
   if (rc) return rc;
   if ((uint64_t)n * g.l.tiles_y * g.waves_per_row > 0x7FFFFFFFull) return fail(SVC_ERR_UNSUPPORTED, "%s: too many segment columns for one launch", what);
   return SVC_OK;
+}
+
+// the fused pack's three launches, with a.fg_step / a.bg_step (fg, bg in the headers) or each frame's own steps
+int enqueue_dct_pack(const char* what, DctPackArgs& a, uint32_t n_frames, uint32_t fg, uint32_t bg, uint8_t* d_out, uint64_t* d_frame_offsets,
+                     hipStream_t s) {
+  const PackGeom& g = a.g;
+  int rc;
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (g.n_block == 8) hipLaunchKernelGGL(dct_pack_kernel<8>, grid, blk, 0, s, a);
+  else hipLaunchKernelGGL(dct_pack_kernel<16>, grid, blk, 0, s, a);
+  if ((rc = check_launch(what, "transform"))) return rc;
+  hipLaunchKernelGGL(dct_pack_scan_kernel, dim3(n_frames), blk, 0, s, g.pieces, g.l.levels_off, a.ws);
+  if ((rc = check_launch(what, "scan"))) return rc;
+  const AssembleArgs as{g, fg, bg, a.steps, a.types, a.ws, d_out, d_frame_offsets};
+  // a wave per piece and trip; enough workgroups per frame to keep a single 4K frame busy, few enough that a batch is not all launch
+  const uint32_t per_frame = std::min<uint32_t>(std::max<uint32_t>(div_up(g.pieces, 32), 1), 256);
+  hipLaunchKernelGGL(dct_pack_assemble_kernel, dim3(per_frame, n_frames), blk, 0, s, as);
+  return check_launch(what, "assemble");
 }
 
 }  // namespace
@@ -382,17 +578,77 @@ int svc_hip_dct_pack_levels_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
   a.fg_inv = 1.0f / a.fg_step;
   a.bg_inv = 1.0f / a.bg_step;
   a.ws = carve(d_workspace, n_frames, g);
+  return enqueue_dct_pack("dct_pack_levels", a, n_frames, fg_step, bg_step, d_out, d_frame_offsets, s);
+}
+
+uint64_t svc_hip_dct_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                                        uint32_t mv_block_w, uint32_t mv_block_h, uint32_t ladder_len) {
+  const char* what = "dct_pack_levels_budget_workspace_bytes";
+  if (validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  if (ladder_len == 0 || ladder_len > kMaxLadder) {
+    (void)fail(SVC_ERR_INVALID_ARG, "%s: a ladder of %u entries (1 .. %u)", what, ladder_len, kMaxLadder);
+    return 0;
+  }
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits(what, n_frames, g)) return 0;
+  return budget_ws_bytes(n_frames, g);
+}
+
+// Checked in the order of svc_hip_dct_pack_levels_frames, the ladder in place of the steps: geometry, stride, ladder, limits, sizes;
+// n_frames == 0 then returns SVC_OK; then pointers.
+int svc_hip_dct_pack_levels_budget_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                          uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                          uint32_t mv_block_h, const svc_step_pair* ladder, uint32_t ladder_len, const uint32_t* d_budget,
+                                          uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                          uint64_t* d_frame_offsets, uint32_t* d_choice, void* stream) {
+  int rc = validate_pack_geom("dct_pack_levels_budget", frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "dct_pack_levels_budget: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)",
+              (unsigned long long)frame_stride_bytes, 3ull * frame_w * frame_h);
+  if ((rc = validate_ladder("dct_pack_levels_budget", ladder, ladder_len))) return rc;
+  // (the pack's int16 bound holds for every step at 8x8 and 16x16, as in svc_hip_dct_pack_levels_frames)
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits("dct_pack_levels_budget", n_frames, g))) return rc;
+  const uint64_t ws_need = budget_ws_bytes(n_frames, g);
+  SVC_REQUIRE(workspace_bytes >= ws_need, "dct_pack_levels_budget: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
+  const uint64_t need = n_frames * g.l.max_bytes;
+  SVC_REQUIRE(out_capacity >= need, "dct_pack_levels_budget: output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)out_capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_budget && d_workspace && d_out && d_frame_offsets && d_choice,
+              "dct_pack_levels_budget: null pointer");
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_block_types, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
+              "dct_pack_levels_budget: frames, output and workspace must be 16-byte aligned, offsets 8-byte, types, budget and choice 4-byte");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const BudgetWs bws = carve_budget(d_workspace, n_frames, g);
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.total_waves = n_frames * g.l.tiles_y * g.waves_per_row;
+  a.types = d_block_types;
+  a.steps = bws.steps;
+  a.ws = carve(d_workspace, n_frames, g);
+  CountArgs k{make_ladder(ladder, ladder_len), 0, bws.rows};
+  while ((ladder_len >> k.probes) != 0) ++k.probes;
+  LadderInv li{};
+  for (uint32_t i = 0; i < ladder_len; ++i) {
+    li.inv[0][i] = 1.0f / (float)ladder[i].bg_step;
+    li.inv[1][i] = 1.0f / (float)ladder[i].fg_step;
+  }
   const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
-  if (block == 8) hipLaunchKernelGGL(dct_pack_kernel<8>, grid, blk, 0, s, a);
-  else hipLaunchKernelGGL(dct_pack_kernel<16>, grid, blk, 0, s, a);
-  if ((rc = check_launch("dct_pack_levels", "transform"))) return rc;
-  hipLaunchKernelGGL(dct_pack_scan_kernel, dim3(n_frames), blk, 0, s, g.pieces, g.l.levels_off, a.ws);
-  if ((rc = check_launch("dct_pack_levels", "scan"))) return rc;
-  const AssembleArgs as{g, fg_step, bg_step, d_block_types, a.ws, d_out, d_frame_offsets};
-  // a wave per piece and trip; enough workgroups per frame to keep a single 4K frame busy, few enough that a batch is not all launch
-  const uint32_t per_frame = std::min<uint32_t>(std::max<uint32_t>(div_up(g.pieces, 32), 1), 256);
-  hipLaunchKernelGGL(dct_pack_assemble_kernel, dim3(per_frame, n_frames), blk, 0, s, as);
-  return check_launch("dct_pack_levels", "assemble");
+  if (block == 8) hipLaunchKernelGGL(dct_count_kernel<8>, grid, blk, 0, s, a, k);
+  else hipLaunchKernelGGL(dct_count_kernel<16>, grid, blk, 0, s, a, k);
+  if ((rc = check_launch("dct_pack_levels_budget", "count"))) return rc;
+  hipLaunchKernelGGL(dct_count_sum_kernel, dim3(kSumParts, n_frames), blk, 0, s, g.l.tiles_y * g.waves_per_row, bws.rows, bws.parts);
+  if ((rc = check_launch("dct_pack_levels_budget", "sum"))) return rc;
+  const SelectArgs sel{g.l.levels_off, bws.parts, d_budget, bws.steps, d_choice};
+  hipLaunchKernelGGL(dct_pack_select_kernel, dim3(n_frames), blk, 0, s, k.lad, li, sel);
+  if ((rc = check_launch("dct_pack_levels_budget", "select"))) return rc;
+  return enqueue_dct_pack("dct_pack_levels_budget", a, n_frames, 0, 0, d_out, d_frame_offsets, s);
 }
 
 }  // extern "C"

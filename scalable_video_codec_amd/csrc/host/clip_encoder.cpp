@@ -87,6 +87,10 @@ struct ClipEncoder::Impl : EncodeGeometry {
   // set, as the planes of the two-pass order: the transforms of consecutive steps follow each other on the main stream
   DevBuf<uint8_t> compact, compact_ws;
   DevBuf<uint64_t> compact_off;
+  // SetCompactBudget: the ladder (empty: the fixed fg_step / bg_step), every frame's budget and the newest step's choices; compact_ws is
+  // then the budgeted call's workspace, which holds the fixed call's
+  std::vector<svc_step_pair> budget_ladder;
+  DevBuf<uint32_t> compact_budget, compact_choice;
   Event e_pyr[2], e_halo[2], e_fork, e_join[kSets], e_rfork, e_rmse[kSets];
   bool halo_recorded[2] = {false, false}, join_pending[kSets] = {}, rmse_pending[kSets] = {};
   bool defer_rmse = false;  // pipelined, large fields: RANSAC leaves its in-order RMSE sum to a later kernel (nothing downstream
@@ -416,7 +420,12 @@ struct ClipEncoder::Impl : EncodeGeometry {
     Run(Stage::kTransform, st, timing, [&] {
       // records carry RAW coefficients, as the reference's encoder serialises them (libs/encoder.cpp:638-650:
       // the decoder picks the step per tile, libs/decoder.cpp:130-135); planes carry the quantised ones
-      if (c.compact)  // the quantised coefficients as the compact stream, straight from the transform (whole-shard launches: p0 = 0)
+      if (c.compact && !budget_ladder.empty())  // ... with each frame's steps from its byte budget (SetCompactBudget)
+        Abi(svc_hip_dct_pack_levels_budget_frames(enc, frame_bytes, pn, pw, ph, c.dct_block_w, types_c, c.mv_block, c.mv_block,
+                                                  budget_ladder.data(), (uint32_t)budget_ladder.size(), compact_budget.p, compact_ws.p,
+                                                  compact_ws.bytes(), compact.p, compact.bytes(), compact_off.p, compact_choice.p, st),
+            "svc_hip_dct_pack_levels_budget_frames");
+      else if (c.compact)  // the quantised coefficients as the compact stream, straight from the transform (whole-shard launches: p0 = 0)
         Abi(svc_hip_dct_pack_levels_frames(enc, frame_bytes, pn, pw, ph, c.dct_block_w, types_c, c.mv_block, c.mv_block, c.fg_step, c.bg_step,
                                            compact_ws.p, compact_ws.bytes(), compact.p, compact.bytes(), compact_off.p, st),
             "svc_hip_dct_pack_levels_frames");
@@ -773,6 +782,28 @@ void ClipEncoder::StepOn(const uint8_t* frames, bool timed) {
   ++m.n_steps;
 }
 
+void ClipEncoder::SetCompactBudget(const svc_step_pair* ladder, uint32_t ladder_len, uint32_t bytes_per_frame) {
+  Sync();  // the steps in flight keep the steps they were submitted with
+  Impl& m = *p_;
+  const ClipEncoderConfig& c = m.c;
+  if (!c.compact) throw std::runtime_error("svc::ClipEncoder: a byte budget is a setting of the compact stream (compact)");
+  if (ladder_len == 0) { m.budget_ladder.clear(); return; }
+  const uint32_t P = m.sh.pairs;
+  // the budgeted call's checks that need neither a device pointer nor a size: geometry, stride, the ladder, limits
+  Abi(svc_hip_dct_pack_levels_budget_frames(nullptr, m.frame_bytes, 0, m.pw, m.ph, c.dct_block_w, nullptr, c.mv_block, c.mv_block, ladder, ladder_len,
+                                            nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr, nullptr, nullptr),
+      "svc_hip_dct_pack_levels_budget_frames");
+  if (!m.compact_budget.p) {  // once: the larger workspace, a budget and a choice per pair
+    m.compact_ws.Alloc(kWho, svc_hip_dct_pack_levels_budget_workspace_bytes(P, m.pw, m.ph, c.dct_block_w, c.mv_block, c.mv_block, 64));
+    m.compact_budget.Alloc(kWho, std::max(P, 1u));
+    m.compact_choice.Alloc(kWho, std::max(P, 1u));
+    Hip(hipMemset(m.compact_choice.p, 0, m.compact_choice.bytes()), "hipMemset");
+  }
+  const std::vector<uint32_t> b(std::max(P, 1u), bytes_per_frame);
+  Hip(hipMemcpy(m.compact_budget.p, b.data(), b.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy");
+  m.budget_ladder.assign(ladder, ladder + ladder_len);
+}
+
 void ClipEncoder::Flush() {
   Impl& m = *p_;
   while (m.n_dct < m.n_luma) m.Iterate(false, m.last_timed);
@@ -834,6 +865,10 @@ void* ClipEncoder::Output(Buffer b, uint64_t* bytes) {
         Hip(hipMemcpy(&n, m.compact_off.p + m.sh.pairs, sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
       break;
     case Buffer::kCompactOffsets: ptr = m.compact_off.p; n = m.compact_off.bytes(); break;
+    case Buffer::kCompactChoice:  // nothing while the steps are the fixed ones
+      ptr = m.compact_choice.p;
+      n = m.budget_ladder.empty() ? 0 : (uint64_t)m.sh.pairs * sizeof(uint32_t);
+      break;
     default: throw std::runtime_error("svc::ClipEncoder: unknown buffer");
   }
   if (bytes) *bytes = n;
@@ -972,6 +1007,9 @@ int svc_clip_step_frames(svc_clip* clip, const uint8_t* device_frames, int timed
   });
 }
 int svc_clip_wait_step(svc_clip* clip, uint32_t step) { return Guard([&] { clip->enc->WaitStep(step); }); }
+int svc_clip_set_compact_budget(svc_clip* clip, const svc_step_pair* ladder, uint32_t ladder_len, uint32_t bytes_per_frame) {
+  return Guard([&] { clip->enc->SetCompactBudget(ladder, ladder_len, bytes_per_frame); });
+}
 int svc_clip_flush(svc_clip* clip) { return Guard([&] { clip->enc->Flush(); }); }
 int svc_clip_sync(svc_clip* clip) { return Guard([&] { clip->enc->Sync(); }); }
 

@@ -18,6 +18,7 @@
 // decode: unpack's count and scan, then one kernel from the stream straight to the decoder's reconstruction (DecodeBlock with a
 // gaze rectangle per frame, the arithmetic of idct_core.hpp), and optionally the display pass of display_core.hpp (/ 255, bilinear
 // resize, to u8).
+#include "budget_core.hpp"
 #include "display_core.hpp"
 #include "idct_core.hpp"
 #include "stream_format.hpp"
@@ -312,16 +313,7 @@ __global__ __launch_bounds__(256) void scan_kernel(Geom g, Ws ws, const uint8_t*
 
 // ---- budgeted pack: per frame the finest ladder entry whose frame fits its byte budget ------------------------------------------
 
-constexpr uint32_t kMaxLadder = 64;  // one entry per lane of a wave
-
-// The ladder as the kernels take it (by value: 1 KB of kernel arguments, no copy to the device).  tau[c][k] = the smallest f32
-// >= step * (0.5 - 2^-26), class c = 0 background, 1 foreground: with a correctly rounded division, level_of(x, step) != 0
-// exactly when |x| >= tau (fl(|x| / step) >= 0.5 under round-to-nearest-even, and std::round sends 0.5 away from zero).
-struct Ladder {
-  uint32_t len;
-  uint32_t step[2][kMaxLadder];
-  float tau[2][kMaxLadder];
-};
+// (the ladder as the kernels take it, its thresholds, its checks and the choice: budget_core.hpp, shared with dct_pack.hip)
 
 // workspace of the budgeted pack: the pack's own, then per (frame, entry, group) the non-zero levels, per (frame, entry) the frame's
 // size, per frame its steps
@@ -343,17 +335,6 @@ BudgetWs carve_budget(uint8_t* p, uint32_t n, uint32_t groups, uint32_t len) {
   q += up16(8ull * n * len);
   s.steps = reinterpret_cast<uint32_t*>(q);
   return s;
-}
-
-// the smallest f32 >= step * (0.5 - 2^-26) = N / 2^26 with N = step * (2^25 - 1) < 2^57, exactly: every candidate is >= 0.25, so
-// candidate * 2^26 is an integer below 2^64 and compares with N without rounding
-float zero_threshold(uint32_t step) {
-  const uint64_t n = (uint64_t)step * ((1u << 25) - 1);
-  auto ge = [n](float f) { return (uint64_t)((double)f * 67108864.0) >= n; };
-  float f = (float)std::ldexp((double)n, -26);
-  while (!ge(f)) f = std::nextafter(f, INFINITY);
-  while (ge(std::nextafter(f, 0.f))) f = std::nextafter(f, 0.f);
-  return f;
 }
 
 // One group as pack_kernel splits it.  Per 64-coefficient word (the tile, hence the step class, is the same in every lane):
@@ -414,10 +395,8 @@ __global__ __launch_bounds__(256) void budget_select_kernel(uint32_t n, Ladder l
   if (f >= n) return;
   const uint64_t b = budget[f];
   const uint64_t* fb = bytes + (size_t)f * lad.len;
-  uint32_t k = 0;
-  while (k < lad.len && fb[k] > b) ++k;
-  const uint32_t pick = k < lad.len ? k : lad.len - 1;
-  choice[f] = k < lad.len ? k : (pick | 0x80000000u);
+  const uint32_t ch = budget_choice(fb, lad.len, b), pick = ch & 0x7FFFFFFFu;
+  choice[f] = ch;
   steps[2 * f] = lad.step[1][pick];
   steps[2 * f + 1] = lad.step[0][pick];
 }
@@ -741,14 +720,7 @@ int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_b
                                       uint32_t* d_choice, void* stream) {
   int rc = validate_geom("pack_levels_budget", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
-  SVC_REQUIRE(ladder_len >= 1 && ladder_len <= kMaxLadder, "pack_levels_budget: a ladder of %u entries (1 .. %u)", ladder_len, kMaxLadder);
-  SVC_REQUIRE(ladder != nullptr, "pack_levels_budget: null ladder");
-  for (uint32_t k = 0; k < ladder_len; ++k) {
-    SVC_REQUIRE(ladder[k].fg_step > 0 && ladder[k].bg_step > 0, "pack_levels_budget: ladder entry %u: quant steps must be positive", k);
-    SVC_REQUIRE(k == 0 || (ladder[k].fg_step >= ladder[k - 1].fg_step && ladder[k].bg_step >= ladder[k - 1].bg_step),
-                "pack_levels_budget: ladder entry %u (%u, %u) is below entry %u (%u, %u): the ladder must be non-decreasing", k,
-                ladder[k].fg_step, ladder[k].bg_step, k - 1, ladder[k - 1].fg_step, ladder[k - 1].bg_step);
-  }
+  if ((rc = validate_ladder("pack_levels_budget", ladder, ladder_len))) return rc;
   // entry 0 holds the smallest steps: the bound of svc_hip_pack_levels_frames there covers the whole ladder
   const uint32_t smin = std::min(ladder[0].fg_step, ladder[0].bg_step);
   if (255.0 * std::sqrt((double)block_w * block_h) / smin > 32767.0)
@@ -766,12 +738,7 @@ int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_b
   SVC_REQUIRE(aligned(d_planes, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
               "pack_levels_budget: planes, output and workspace must be 16-byte aligned, offsets 8-byte, types, budget and choice 4-byte");
-  Ladder lad{};
-  lad.len = ladder_len;
-  for (uint32_t k = 0; k < ladder_len; ++k) {
-    lad.step[0][k] = ladder[k].bg_step; lad.step[1][k] = ladder[k].fg_step;
-    lad.tau[0][k] = zero_threshold(ladder[k].bg_step); lad.tau[1][k] = zero_threshold(ladder[k].fg_step);
-  }
+  const Ladder lad = make_ladder(ladder, ladder_len);
   const BudgetWs bws = carve_budget(d_workspace, n_frames, g.groups, ladder_len);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(g.groups, n_frames);

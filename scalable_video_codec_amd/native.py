@@ -131,6 +131,10 @@ SIGNATURES = {
     "svc_hip_entropy_encode_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "svc_hip_entropy_decode_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "svc_hip_entropy_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
+    # the same with rate control, still without planes (csrc/dct_pack.hip)
+    "svc_hip_dct_pack_levels_budget_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_dct_pack_levels_budget_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 2 + [C.POINTER(StepPair), _u32, _vp, _vp, _u64,
+                                                        _vp, _u64, _vp, _vp, _vp]),
     # its rate control: per-frame steps from a byte budget (csrc/levels.hip)
     "svc_hip_pack_levels_budget_workspace_bytes": (_u64, [_u32] * 6),
     "svc_hip_pack_levels_budget_frames": (C.c_int, [_vp, _vp] + [_u32] * 7 + [C.POINTER(StepPair), _u32, _vp, _vp, _u64, _vp, _u64, _vp,
@@ -802,6 +806,38 @@ def pack_levels_budget_frames(planes: torch.Tensor, block_types: torch.Tensor, b
                                                     mbw, mbh, arr, k, _dev(budget, torch.int32), _dev(workspace, torch.uint8),
                                                     workspace.numel(), _dev(out, torch.uint8), out.numel(),
                                                     _dev(offsets, torch.int64), _dev(choice, torch.int32), _stream()))
+    return out, offsets, choice
+
+
+def dct_pack_levels_budget_workspace_bytes(n: int, w: int, h: int, block: int, mv_block, ladder_len: int) -> int:
+    """Scratch of dct_pack_levels_budget_frames; 0 for a geometry or a ladder length it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_levels_budget_workspace_bytes(n, w, h, block, mbw, mbh, ladder_len))
+
+
+def dct_pack_levels_budget_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, ladder, budget,
+                                  out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
+                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """B,G,R frames (frames, H, W, 3) u8 + region ids -> each frame packed with the finest ladder entry whose frame fits its byte
+    budget, byte for byte what dct_frames + pack_levels_budget_frames leave, without the planes (include/svc_hip.h).  ladder and
+    budget as pack_levels_budget_frames takes them.  -> (stream u8 of the worst-case size, offsets (frames + 1,) i64, choice
+    (frames,) i32 on the device)."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    arr, k = _ladder(ladder)
+    dev = bgr.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_levels_budget_workspace_bytes(n, w, h, block, mv_block, k), 16), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    choice = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    if not (isinstance(budget, torch.Tensor) and budget.is_cuda):
+        budget = budget_tensor(budget, n, dev)
+    _check(load().svc_hip_dct_pack_levels_budget_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                        _dev(block_types, torch.int32), mbw, mbh, arr, k, _dev(budget, torch.int32),
+                                                        _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8),
+                                                        out.numel(), _dev(offsets, torch.int64), _dev(choice, torch.int32), _stream()))
     return out, offsets, choice
 
 

@@ -10,6 +10,13 @@
                                                    svc::ClipEncoder over a resident clip (default 300 frames = 299 pairs), serial and
                                                    pipelined: the compact step against the two-pass planes step plus the pack of its
                                                    output; wall time per step over back-to-back steps
+  python tools/dct_pack_probe.py budget [C3|C5]    rate control: the same batch, levels.step_ladder(1, 256, 4, 640, 10, 24) (32 entries) and
+                                                   1.1 MB per 1080p frame (scaled by the pixels at C5); the planes route (svc_hip_dct_frames +
+                                                   svc_hip_pack_levels_budget_frames) 5 times, then svc_hip_dct_pack_levels_budget_frames 5
+                                                   times; stream, offsets and choices are compared.  Run under rocprofv3 as `kernels`
+  python tools/dct_pack_probe.py budget_step [C3|C5] [frames]
+                                                   svc::ClipEncoder with compact: the step at the fixed steps against the step under that
+                                                   budget (SetCompactBudget), serial and pipelined; wall time per step
 """
 import os
 import sys
@@ -21,7 +28,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from scalable_video_codec_amd import clip as clipmod  # noqa: E402
-from scalable_video_codec_amd import configs, native, pipeline, synth  # noqa: E402
+from scalable_video_codec_amd import configs, levels, native, pipeline, synth  # noqa: E402
 
 
 def _cfg(argv, k):
@@ -65,6 +72,68 @@ def kernels(cfg, fused_only=False) -> None:
         assert torch.equal(offs, offs2) and torch.equal(out[:total], out2[:total]), "the fused route's bytes differ from the two calls'"
     print(f"{cfg.name} batch of {n}: {total} B compact ({total / n / 1e6:.3f} MB per frame), planes {3 * pw * ph * 4 / 1e6:.2f} MB per frame, "
           f"fused workspace {ws2.numel() / n / 1e6:.2f} MB per frame" + ("" if fused_only else "; fused bytes == two-call bytes"), flush=True)
+
+
+def _budget(cfg):
+    """The ladder and the bytes per frame of profiles/levels_budget_c3.txt (1.1 MB per 1080p frame, by the pixels elsewhere)."""
+    pw, ph = cfg.padded
+    return levels.step_ladder(1, 256, 4, 640, 10, 24), int(1_100_000 * (pw * ph) / (1920 * 1088)) // 16 * 16
+
+
+def budget(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    bgr, types = _batch(cfg, n)
+    lad, per_frame = _budget(cfg)
+    b = native.budget_tensor(per_frame, n, dev)
+    cap = native.levels_max_bytes(n, pw, ph, cfg.dct_block, cfg.mv_block)
+    out2 = torch.empty(cap, dtype=torch.uint8, device=dev)
+    ws2 = torch.empty(native.dct_pack_levels_budget_workspace_bytes(n, pw, ph, cfg.dct_block, cfg.mv_block, len(lad)), dtype=torch.uint8, device=dev)
+    planes = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=dev)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(native.pack_levels_budget_workspace_bytes(n, pw, ph, cfg.dct_block, len(lad)), dtype=torch.uint8, device=dev)
+    for _ in range(5):
+        native.dct_frames(bgr, cfg.dct_block, out=planes)
+        _, _, choice = native.pack_levels_budget_frames(planes, types, cfg.dct_block, cfg.mv_block, lad, b, out=out, offsets=offs, workspace=ws)
+    for _ in range(5):
+        _, offs2, choice2 = native.dct_pack_levels_budget_frames(bgr, cfg.dct_block, types, cfg.mv_block, lad, b, out=out2, workspace=ws2)
+    torch.cuda.synchronize()
+    total = int(offs2[-1].item())
+    out.view(torch.int32)[offs[:-1] // 4 + 11] = 0  # `inexact`: the planes route counts its raw planes' coefficients, the fused calls write 0
+    assert torch.equal(offs, offs2) and torch.equal(choice, choice2) and torch.equal(out[:total], out2[:total]), \
+        "the budgeted fused call's bytes differ from the planes route's"
+    sizes = (offs2[1:] - offs2[:-1]).cpu().tolist()
+    ch = choice2.cpu().numpy().view("uint32")
+    print(f"{cfg.name} batch of {n}: {len(lad)} entries, budget {per_frame} B per frame: choices {[int(c) & 0x7FFFFFFF for c in ch]}, over budget "
+          f"{int((ch >> 31).sum())}, {min(sizes) / 1e6:.3f} .. {max(sizes) / 1e6:.3f} MB per frame, workspace {ws2.numel() / n / 1e6:.2f} MB per frame; "
+          f"bytes, offsets and choices == the planes route's", flush=True)
+
+
+def budget_step(cfg, frames_n) -> None:
+    dev = torch.device("cuda")
+    clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=dev)
+    pw, ph = cfg.padded
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(frames_n)]).contiguous()
+    lad, per_frame = _budget(cfg)
+    for schedule, name in ((clipmod.SERIAL, "serial"), (clipmod.PIPELINED, "pipelined")):
+        enc = clipmod.Clip(cfg, frames_n, schedule=schedule, compact=True)
+        enc.load_frames(frames)
+        fixed_ms = _per_step(enc.step, enc.sync)
+        enc.set_compact_budget(lad, per_frame)
+        budget_ms = _per_step(enc.step, enc.sync)
+        ch = enc.read("compact_choice").numpy().view("uint32")
+        enc.set_compact_budget([], 0)
+        again_ms = _per_step(enc.step, enc.sync)
+        i = enc.info
+        enc.close()
+        del enc
+        torch.cuda.empty_cache()
+        print(f"{cfg.name} {name}, {i.pairs} pairs, ms per step (best .. worst of 3 runs of 4 back-to-back steps): fixed compact step "
+              f"{fixed_ms[0]:.3f} .. {fixed_ms[1]:.3f}; under a budget of {per_frame} B per frame {budget_ms[0]:.3f} .. {budget_ms[1]:.3f} "
+              f"({budget_ms[0] / fixed_ms[0]:.2f}x; entries {int((ch & 0x7FFFFFFF).min())} .. {int((ch & 0x7FFFFFFF).max())}, over budget "
+              f"{int((ch >> 31).sum())}); fixed again {again_ms[0]:.3f} .. {again_ms[1]:.3f}", flush=True)
 
 
 def _per_step(fn, sync, warm=2, reps=3, steps=4):
@@ -123,5 +192,9 @@ if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "kernels"
     if mode == "step":
         step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
+    elif mode == "budget_step":
+        budget_step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
+    elif mode == "budget":
+        budget(_cfg(sys.argv, 2))
     else:
         kernels(_cfg(sys.argv, 2), fused_only=mode == "fused")
