@@ -678,6 +678,31 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                                  uint32_t display_w, uint32_t display_h, uint32_t* d_status,
                                  void* stream);
 
+/* The same decoder straight from SVCE frames, without the SVCQ frames in between: d_rec and
+ * d_display are bit-identical to svc_hip_entropy_decode_frames followed by
+ * svc_hip_decode_levels_frames with the same arguments and gaze.  d_status [n_frames] u32 with the
+ * codes of svc_hip_entropy_decode_frames (0 .. 5, 8, 9, 10); a frame that fails is zeros in d_rec
+ * and d_display and leaves its neighbours as they would be.  Every read is clamped to the frame's
+ * bytes; any chunk_tiles >= 1 is honoured.  A workgroup decodes the chunks that cover its group of
+ * tiles (the encoder's chunk is that group) into LDS and reconstructs from there.  Geometry as
+ * svc_hip_decode_levels_frames (else SVC_ERR_UNSUPPORTED and a workspace of 0).  Checked in its
+ * order, for any n_frames: geometry, steps, display size, limits (SVCE's), workspace, then
+ * pointers (n_frames == 0 returns SVC_OK before the pointers; frames and workspace 16-byte
+ * aligned, offsets 8-byte, output, gaze and status 4-byte).  Only enqueues work. */
+uint64_t svc_hip_decode_entropy_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                                uint32_t mv_block_h);
+int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, const uint64_t* d_offsets,
+                                  uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                  uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                  uint32_t fg_step, uint32_t bg_step,
+                                  const uint32_t* d_gaze /* [n_frames][4] x, y, w, h (padded); NULL = none */,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes,
+                                  float* d_rec /* [n][H][W][3] f32 B,G,R, padded */,
+                                  uint8_t* d_display /* [n][display_h][display_w][3] u8 B,G,R, or NULL */,
+                                  uint32_t display_w, uint32_t display_h, uint32_t* d_status,
+                                  void* stream);
+
 /* The reference's gaze rectangle from a point, on the host (no device needed):
  * CalcWithinFrameRectFromCenter (libs/decoder.cpp:65-100: halves (max + 1) / 2, clipped at the
  * frame's edges) in the source frame, then scaled by (float)padded / frame with

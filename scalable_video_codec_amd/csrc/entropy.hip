@@ -18,7 +18,12 @@
 //   offsets  one workgroup: SVCQ frame offsets
 //   chunks   one lane per chunk: serial Exp-Golomb decoding (a chunk is serial by design), every read clamped to the frame
 //   frame    one workgroup per frame: SVCQ header, types, padding, or zeros for a frame that failed
-#include "svc_common.hpp"
+// fused decode (svc_hip_decode_entropy_frames), without the SVCQ frames:
+//   check    as above
+//   decode   one workgroup per group of tiles of levels.hip's decoder: its chunks into LDS, one lane per chunk, then the reconstruction
+//   finish   status; zeros for a frame that failed
+#include "display_core.hpp"
+#include "idct_core.hpp"
 #include "stream_format.hpp"
 
 #include <algorithm>
@@ -830,6 +835,228 @@ __global__ __launch_bounds__(256) void dec_frame_kernel(DecArgs a) {
   for (uint64_t i = used + threadIdx.x; i < qbytes; i += kThreads) q[i] = 0;
 }
 
+// ---- fused decode: SVCE frames straight to the decoder's reconstruction ---------------------------------------------------------
+//
+// The encoder's chunk (g.ct tiles) is the group of tiles one workgroup of levels.hip's decode_levels_kernel reconstructs, so a
+// workgroup decodes the chunks that cover its group (one per plane in the encoder's layout) into dense int16 coefficients in LDS and
+// inverts them from there: the SVCQ masks and levels never exist.  Any other chunk_tiles is honoured: a chunk that overlaps the group
+// is walked from its first tile to the group's last one, and the group that holds a chunk's last tile walks it to its end and makes
+// the end checks, so every chunk is checked exactly once in full.
+
+constexpr uint32_t kCoefBytes = 3 * kChunkCoeffs * 2;  // the group's dense int16 coefficients, three planes
+constexpr uint32_t kStageSlots = 3;                    // payloads walked from LDS: the first three walkers (the encoder's layout has three)
+// a slot holds the largest chunk the encoder writes for a group (raw: mode byte, 8 B per mask word, 2 B per coefficient) from the
+// 4-byte boundary below its first byte
+constexpr uint32_t kStageWords = (uint32_t)up16(3 + 1 + 8 * (kChunkCoeffs / 64) + 2 * kChunkCoeffs) / 4;
+
+struct FusedArgs {
+  Geom g;
+  const uint8_t* in;
+  const uint64_t* in_off;
+  const uint32_t* gaze;  // [n][4] x, y, w, h in padded coordinates, or null
+  float* rec;            // [n][h][w][3]
+  uint32_t* d_status;
+  DecWs ws;
+  float fg, bg;          // the decoder's steps
+};
+
+// a coded chunk of `size` bytes from byte sb of the reader's words: its tiles [0, t_end); chunk tile t is the group's tile t + d
+// (outside the group while that is negative).  to_end: t_end is the chunk's last tile, and the chunk must end where its index says.
+__device__ __forceinline__ bool walk_coded(BitReader r, uint32_t sb, uint32_t size, uint32_t count, uint32_t t_end, bool to_end, int32_t d,
+                                           uint32_t area, int16_t* coef) {
+  const uint64_t end = 8ull * (sb + size);
+  uint64_t pos = 8ull * sb;
+  const uint32_t head = (uint32_t)r.peek(pos);
+  const uint32_t kd = (head >> 1) & 7u, ka = (head >> 4) & 7u;
+  pos += 7;
+  r.seek(pos);
+  uint32_t written = 0;
+  int32_t dcp = 0;
+  bool ok = true;
+  for (uint32_t t = 0; ok && t < t_end; ++t) {
+    const int32_t lt = (int32_t)t + d;
+    int16_t* tile = coef + lt * (int32_t)area;  // written only for lt >= 0
+    uint32_t u;
+    ok = get_eg(r, &pos, end, kd, &u);
+    if (!ok) break;
+    const int32_t dc = dcp + unsgn(u);
+    dcp = dc;
+    ok = dc >= -32768 && dc <= 32767;
+    if (ok && dc != 0) {
+      ok = written < count;
+      if (ok) {
+        ++written;
+        if (lt >= 0) tile[0] = (int16_t)dc;
+      }
+    }
+    uint32_t nac = 0;
+    ok = ok && get_eg(r, &pos, end, 0, &nac) && nac <= area - 1;
+    uint32_t p = 0;
+    for (uint32_t i = 0; ok && i < nac; ++i) {
+      uint32_t run, lu;
+      ok = get_eg(r, &pos, end, 0, &run) && (uint64_t)p + run + 1 <= area - 1;
+      if (!ok) break;
+      p += run + 1;
+      ok = get_eg(r, &pos, end, ka, &lu);
+      if (!ok) break;
+      const int32_t v = unsgn(lu);
+      ok = v >= -32768 && v <= 32767 && written < count;
+      if (!ok) break;
+      ++written;
+      if (lt >= 0) tile[p] = (int16_t)v;
+    }
+  }
+  if (to_end) ok = ok && written == count && (pos + 7) / 8 == sb + size;
+  return ok;
+}
+
+// a raw chunk of nt tiles at s (its mode byte): the same walk over its mask words, the levels from behind them
+__device__ __forceinline__ bool walk_raw(const uint8_t* s, uint32_t size, uint32_t count, uint32_t nt, uint32_t t_end, bool to_end, int32_t d,
+                                         const Geom& g, int16_t* coef) {
+  const uint32_t mbytes = 8 * g.nw * nt;
+  if ((uint64_t)size != 1ull + mbytes + 2ull * count) return false;
+  const uint8_t* lv = s + 1 + mbytes;
+  uint32_t got = 0;
+  for (uint32_t i = 0; i < t_end * g.nw; ++i) {
+    const uint8_t* q = s + 1 + 8 * i;
+    uint64_t m = 0;
+    for (uint32_t b = 0; b < 8; ++b) m |= (uint64_t)q[b] << (8 * b);
+    const uint32_t t = i / g.nw, j = i - t * g.nw;
+    const uint32_t valid = min(64u, g.area - 64 * j);
+    if (valid < 64 && (m >> valid)) return false;
+    const int32_t lt = (int32_t)t + d;
+    if (lt < 0) {
+      got += __popcll(m);
+      continue;
+    }
+    int16_t* word = coef + lt * (int32_t)g.area + 64 * j;
+    while (m) {
+      const uint32_t b = __ffsll((unsigned long long)m) - 1;
+      m &= m - 1;
+      if (got >= count) return false;  // more mask bits than levels: nothing is read past the chunk
+      word[b] = (int16_t)((uint32_t)lv[2 * got] | ((uint32_t)lv[2 * got + 1] << 8));
+      ++got;
+    }
+  }
+  return !to_end || got == count;
+}
+
+// One workgroup per (tile row, group in the row) of a frame, the grid of decode_levels_kernel<N>.  Walk: per plane and per chunk that
+// overlaps the group one lane (walker w = lane * 4 + wave: the encoder's three sit in three waves); the first kStageSlots walkers read
+// their payload from LDS, staged by all threads with coalesced loads, a payload above a slot is read in place.  Then the arithmetic of
+// decode_levels_kernel in its order from the dense coefficients, so d_rec has the bits of the two calls.  The payload stage and the
+// f64 row slab are never live together and share their bytes.
+template <int N>
+__global__ __launch_bounds__(256) void decode_entropy_kernel(FusedArgs a) {
+  constexpr uint32_t kRows = kChunkCoeffs / N;
+  constexpr uint32_t kRowBytes = kRows * (N + 1) * 8, kStageBytes = kStageSlots * kStageWords * 4;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[kCoefBytes + (kRowBytes > kStageBytes ? kRowBytes : kStageBytes)];
+  int16_t* coef = reinterpret_cast<int16_t*>(smem);
+  uint32_t* stage = reinterpret_cast<uint32_t*>(smem + kCoefBytes);
+  double* rows = reinterpret_cast<double*>(smem + kCoefBytes);  // pitch N + 1, as decode_levels_kernel
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.y, tid = threadIdx.x;
+  if (a.ws.status[f] != kStOk) return;  // the finish kernel zeroes the frame
+  const uint32_t row = blockIdx.x / g.cx, gt0 = (blockIdx.x - row * g.cx) * g.ct, gnt = min(g.ct, g.tx - gt0);
+  const uint8_t* frame = a.in + a.in_off[f];
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t fwords = hdr[kHBytes] / 4;
+  const uint32_t* index = hdr + (kHeaderBytes + hdr[kETypesBytes]) / 4;
+  const uint32_t* coff = a.ws.coff + (size_t)f * g.max_chunks;
+  const uint32_t ct = a.ws.chunks[f], cx = ct >= g.tx ? 1u : (g.tx + ct - 1) / ct;
+  const uint32_t c_first = cx == 1 ? 0u : gt0 / ct, c_last = cx == 1 ? 0u : (gt0 + gnt - 1) / ct;
+  const uint32_t nwalk = c_last - c_first + 1;  // per plane: at most the group's tiles
+
+  for (uint32_t i = tid; i < kCoefBytes / 16; i += kThreads) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0, 0, 0, 0);
+  for (uint32_t s = 0; s < kStageSlots && s < 3 * nwalk; ++s) {
+    const uint32_t c = ((s / nwalk) * g.ty + row) * cx + c_first + s % nwalk;
+    const uint32_t start = coff[c], size = index[c] & 0xFFFFu;
+    const uint32_t w0 = start >> 2, nwords = ((start & 3u) + size + 3) >> 2;
+    if (size == 0 || nwords > kStageWords) continue;
+    for (uint32_t i = tid; i < nwords; i += kThreads) stage[s * kStageWords + i] = w0 + i < fwords ? hdr[w0 + i] : 0u;
+  }
+  __syncthreads();
+
+  const uint32_t w = (tid & 63u) * 4 + (tid >> 6);
+  if (w < 3 * nwalk) {
+    const uint32_t c = ((w / nwalk) * g.ty + row) * cx + c_first + w % nwalk;
+    const uint32_t entry = index[c], size = entry & 0xFFFFu, count = entry >> 16, start = coff[c];
+    uint32_t crow, t0, nt;
+    chunk_tiles(g, ct, cx, c, &crow, &t0, &nt);
+    const uint32_t t_end = min(nt, gt0 + gnt - t0);
+    const bool to_end = t_end == nt;
+    const int32_t d = (int32_t)t0 - (int32_t)gt0;
+    int16_t* plane = coef + (w / nwalk) * kChunkCoeffs;
+    const bool staged = w < kStageSlots && ((start & 3u) + size + 3) >> 2 <= kStageWords;
+    bool ok = size != 0;
+    if (ok && (frame[start] & 1u)) {
+      const uint8_t* s = staged ? reinterpret_cast<const uint8_t*>(stage + w * kStageWords) + (start & 3u) : frame + start;
+      ok = walk_raw(s, size, count, nt, t_end, to_end, d, g, plane);
+    } else if (ok && staged) {
+      ok = walk_coded(BitReader{stage + w * kStageWords, ((start & 3u) + size + 3) >> 2, 0, 0, 0, 0}, start & 3u, size, count, t_end, to_end, d,
+                      g.area, plane);
+    } else if (ok) {
+      ok = walk_coded(BitReader{hdr, fwords, 0, 0, 0, 0}, start, size, count, t_end, to_end, d, g.area, plane);
+    }
+    if (!ok) atomicOr(&a.ws.fail[f], 1u);
+  }
+  __syncthreads();
+
+  const uint32_t t = tid / N, j = tid - t * N;
+  const bool active = t < gnt;
+  const uint32_t x0 = (gt0 + t) * N, y0 = row * N;
+  float enc = 0.f, dec = 1.f;
+  if (active) {
+    // only type == 0 or not matters to the steps: the bitmap's bit, or the raw id
+    const uint32_t* sec = hdr + kHeaderBytes / 4;
+    const uint32_t b = (y0 / g.mvbh) * (g.w / g.mvbw) + x0 / g.mvbw;
+    const bool bgnd = sec[0] == 1 ? sec[1 + b] == 0 : ((sec[1 + (b >> 5)] >> (b & 31u)) & 1u) == 0;
+    const bool in_gaze = gazed(a.gaze, f, x0, y0);
+    enc = (float)(bgnd ? hdr[kHBgStep] : hdr[kHFgStep]);
+    dec = in_gaze ? 1.f : (bgnd ? a.bg : a.fg);
+  }
+  float out[3][N];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (active) {
+      const int16_t* lev = coef + c * kChunkCoeffs + t * (N * N) + j * N;
+      double y[N], r[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) y[i] = (double)requant((float)lev[i] * enc, dec);
+      idct1d<N>(y, r);
+      double* rw = rows + (t * N + j) * (N + 1);
+#pragma unroll
+      for (int i = 0; i < N; ++i) rw[i] = r[i];
+    }
+    __syncthreads();
+    if (active) {
+      double cc[N], xx[N];
+#pragma unroll
+      for (int v = 0; v < N; ++v) cc[v] = rows[(t * N + v) * (N + 1) + j];
+      idct1d<N>(cc, xx);
+#pragma unroll
+      for (int y = 0; y < N; ++y) out[c][y] = (float)xx[y];
+    }
+    __syncthreads();  // the next plane reuses rows
+  }
+  if (!active) return;
+  store_bgr_column<N>(a.rec + (((size_t)f * g.h + y0) * g.w + x0 + j) * 3, g.w, out);
+}
+
+// after the fused kernel: the frame's status; a frame that failed (its checks, or a chunk, known only after other groups stored
+// their pixels) is zeros in d_rec.  A good frame's workgroups leave at once.
+__global__ __launch_bounds__(256) void decode_entropy_finish_kernel(FusedArgs a) {
+  const Geom& g = a.g;
+  const uint32_t f = blockIdx.y;
+  uint32_t st = a.ws.status[f];
+  if (st == kStOk && a.ws.fail[f]) st = kStChunk;
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.d_status[f] = st;
+  if (st == kStOk) return;
+  const size_t n = (size_t)g.h * g.w * 3;
+  float* r = a.rec + (size_t)f * n;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) r[i] = 0.f;
+}
+
 // geometry, then the limits with SVCE's worst case (make_geom divides by the tile area: only for a tile within the limit)
 int validate(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
   const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
@@ -839,6 +1066,13 @@ int validate(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, 
 }
 
 uint64_t ws_bytes(uint32_t n, const Geom& g) { return n ? std::max(enc_ws_bytes(n, g), dec_ws_bytes(n, g)) : 0; }
+
+// the fused decode's geometry (what the reconstruction takes), then the limits with SVCE's worst case
+int validate_fused(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const int rc = validate_decode_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  return validate_limits(what, n, w, h, bw, bh, svce_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)));
+}
 
 }  // namespace
 }  // namespace svc
@@ -938,6 +1172,50 @@ int svc_hip_entropy_drain(const uint8_t* d_frames, const uint64_t* d_frame_offse
   const uint64_t worst = svce_max_bytes(make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
   if ((rc = validate_limits("entropy_max_bytes", n_frames, frame_w, frame_h, block_w, block_h, worst)) && n_frames != 0) return rc;
   return drain_to_host("entropy_drain", d_frames, d_frame_offsets, n_frames, host_dst, capacity, n_frames * worst, stream);
+}
+
+uint64_t svc_hip_decode_entropy_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                                uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_fused("decode_entropy_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
+  return n_frames ? dec_ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) : 0;
+}
+
+// Checked in the order of svc_hip_decode_levels_frames, for any n_frames: geometry, steps, display size, limits, workspace, pointers.
+int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, const uint64_t* d_offsets, uint32_t n_frames,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                  uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint32_t* d_gaze, uint8_t* d_workspace,
+                                  uint64_t workspace_bytes, float* d_rec, uint8_t* d_display, uint32_t display_w, uint32_t display_h,
+                                  uint32_t* d_status, void* stream) {
+  int rc = validate_decode_geom("decode_entropy", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_entropy: quant steps must be positive (libs/decoder.cpp:35-47)");
+  const bool display = display_w != 0 || display_h != 0;
+  if ((rc = validate_display("decode_entropy", display_w, display_h, frame_w, frame_h))) return rc;
+  if ((rc = validate_fused("decode_entropy", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  const uint64_t need = n_frames ? dec_ws_bytes(n_frames, g) : 0;
+  SVC_REQUIRE(workspace_bytes >= need, "decode_entropy: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_svce && d_offsets && d_workspace && d_rec && d_status, "decode_entropy: null pointer");
+  SVC_REQUIRE(display == (d_display != nullptr), "decode_entropy: a display buffer goes with a display size, and only with one");
+  SVC_REQUIRE(aligned(d_svce, 16) && aligned(d_workspace, 16) && aligned(d_offsets, 8) && aligned(d_rec, 4) && aligned(d_status, 4) &&
+                  aligned(d_gaze, 4),
+              "decode_entropy: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
+  const DecWs ws = carve_dec(d_workspace, n_frames, g);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the header, types and index checks and the index scan of svc_hip_entropy_decode_frames (it writes no output)
+  const DecArgs c{g, d_svce, svce_bytes, d_offsets, nullptr, nullptr, nullptr, ws, n_frames};
+  hipLaunchKernelGGL(dec_check_kernel, dim3(n_frames), dim3(kThreads), 0, s, c);
+  if ((rc = check_launch("decode_entropy check"))) return rc;
+  const FusedArgs a{g, d_svce, d_offsets, d_gaze, d_rec, d_status, ws, (float)fg_step, (float)bg_step};
+  const dim3 grid(g.ty * g.cx, n_frames);
+  if (block_w == 8) hipLaunchKernelGGL(decode_entropy_kernel<8>, grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL(decode_entropy_kernel<16>, grid, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("decode_entropy reconstruction"))) return rc;
+  hipLaunchKernelGGL(decode_entropy_finish_kernel, dim3(32, n_frames), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("decode_entropy finish")) || !display) return rc;
+  return launch_display("decode_entropy", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 }  // extern "C"

@@ -573,18 +573,6 @@ int validate_limits(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32
   return svc::validate_limits(what, n, w, h, bw, bh, frame_layout(w, h, bw, bh, mvbw, mvbh).max_bytes);
 }
 
-// decode: what the reconstruction kernels take (square 8x8 or 16x16 transform blocks and a width of whole 16-pixel segments, as
-// svc_hip_decode_frames; sides up to 32768 for the display pass's u32 coordinates), after the format's own geometry
-int validate_decode_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
-  const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
-  if (rc) return rc;
-  if (bw != bh || (bw != 8 && bw != 16))
-    return fail(SVC_ERR_UNSUPPORTED, "%s: transform block %ux%u (supported: 8x8, 16x16)", what, bw, bh);
-  if (w % 16 != 0) return fail(SVC_ERR_UNSUPPORTED, "%s: frame width %u is not a multiple of 16", what, w);
-  if (w > 32768 || h > 32768) return fail(SVC_ERR_UNSUPPORTED, "%s: frame %ux%u above 32768 on a side", what, w, h);
-  return SVC_OK;
-}
-
 // the pack's launches, with a.fg / a.bg or the budgeted pack's per-frame steps
 int enqueue_pack(const char* what, const PackArgs& a, hipStream_t s) {
   const Geom& g = a.g;

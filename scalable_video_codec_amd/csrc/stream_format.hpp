@@ -81,6 +81,18 @@ inline int validate_limits(const char* what, uint32_t n, uint32_t w, uint32_t h,
   return SVC_OK;
 }
 
+// decode: what the reconstruction kernels take (square 8x8 or 16x16 transform blocks and a width of whole 16-pixel segments, as
+// svc_hip_decode_frames; sides up to 32768 for the display pass's u32 coordinates), after the format's own geometry
+inline int validate_decode_geom(const char* what, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  if (bw != bh || (bw != 8 && bw != 16))
+    return fail(SVC_ERR_UNSUPPORTED, "%s: transform block %ux%u (supported: 8x8, 16x16)", what, bw, bh);
+  if (w % 16 != 0) return fail(SVC_ERR_UNSUPPORTED, "%s: frame width %u is not a multiple of 16", what, w);
+  if (w > 32768 || h > 32768) return fail(SVC_ERR_UNSUPPORTED, "%s: frame %ux%u above 32768 on a side", what, w, h);
+  return SVC_OK;
+}
+
 // The drain of a batch of frames to pinned host memory (levels.hip), after the caller's geometry checks: capacity against `need`,
 // then pointers, the destination's memory, and the launch.
 int drain_to_host(const char* what, const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, void* host_dst,

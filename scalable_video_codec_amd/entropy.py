@@ -185,12 +185,16 @@ def _decode_types(sec: np.ndarray, mvb: int) -> np.ndarray:
 
 # ---- encode ---------------------------------------------------------------------------------------------------------------------
 
-def encode_frame(svcq, chunk_tiles=None) -> bytes:
+def encode_frame(svcq, chunk_tiles=None, force_k=None) -> bytes:
     """One SVCQ frame (at the start of svcq; bytes-like or u8 array) -> its SVCE frame.  chunk_tiles: None = what the GPU encoder
     writes (chunk_tiles_for); any other value from 1 to 2^32 - 1 makes a frame every decoder must read, or a ValueError when a chunk
-    of that many tiles does not fit the index's u16 fields."""
+    of that many tiles does not fit the index's u16 fields.  force_k: None = the encoder's choice (per chunk the k_dc and k_ac of the
+    fewest bits, raw when that is smaller); (k_dc, k_ac), each 0 .. 7, codes every chunk with these parameters, and raw only where a
+    set mask bit holds level 0 -- a legal stream every decoder must read, with chunks that may be larger than their raw form."""
     if chunk_tiles is not None and not 1 <= int(chunk_tiles) <= 0xFFFFFFFF:
         raise ValueError(f"chunk_tiles {chunk_tiles} is not in 1 .. 2^32 - 1")
+    if force_k is not None and not (len(force_k) == 2 and all(0 <= int(k) <= 7 for k in force_k)):
+        raise ValueError(f"force_k {force_k} is not a pair of parameters in 0 .. 7")
     b = _u8(svcq)
     words, g, masks, bits, lev = _svcq_sections(b, chunk_tiles)
     C, ct, area = g.chunks, g.ct, g.area
@@ -222,11 +226,13 @@ def encode_frame(svcq, chunk_tiles=None) -> bytes:
     ac_bits = np.stack([np.bincount(ac_chunk, weights=_eg_len(uac, k), minlength=C) for k in ks], 1)
     k_dc = np.argmin(dc_bits, axis=1)  # ties: the smallest k
     k_ac = np.argmin(ac_bits, axis=1)
+    if force_k is not None:
+        k_dc, k_ac = np.full(C, int(force_k[0]), np.int64), np.full(C, int(force_k[1]), np.int64)
     fixed = 7 + np.bincount(chunk, weights=_eg_len(nac, 0), minlength=C) + np.bincount(ac_chunk, weights=_eg_len(run, 0), minlength=C)
     coded_bits = (fixed + dc_bits[np.arange(C), k_dc] + ac_bits[np.arange(C), k_ac]).astype(np.int64)
     coded_bytes = (coded_bits + 7) // 8
     raw_bytes = 1 + 8 * g.nw * g.chunk_nt + 2 * cnt
-    raw = forced | (raw_bytes < coded_bytes)
+    raw = forced | ((raw_bytes < coded_bytes) & (force_k is None))
     sizes = np.where(raw, raw_bytes, coded_bytes)
     if sizes.max(initial=0) > 0xFFFF or cnt.max(initial=0) > 0xFFFF:
         raise ValueError(f"a chunk of {ct} tiles holds {int(sizes.max())} bytes or {int(cnt.max())} levels: above the index's u16 fields")
@@ -514,9 +520,9 @@ def iter_frames(buf, offsets) -> Iterator[bytes]:
         yield decode_frame(fr)
 
 
-def encode_frames(buf, offsets, chunk_tiles=None) -> Tuple[bytes, np.ndarray]:
-    """An SVCQ batch -> (SVCE bytes, offsets (n + 1,) u64)."""
-    return _join([encode_frame(fr, chunk_tiles) for _, _, fr in _frames(buf, offsets, "SVCQ")])
+def encode_frames(buf, offsets, chunk_tiles=None, force_k=None) -> Tuple[bytes, np.ndarray]:
+    """An SVCQ batch -> (SVCE bytes, offsets (n + 1,) u64).  chunk_tiles and force_k as encode_frame."""
+    return _join([encode_frame(fr, chunk_tiles, force_k) for _, _, fr in _frames(buf, offsets, "SVCQ")])
 
 
 def decode_frames(buf, offsets) -> Tuple[bytes, np.ndarray]:

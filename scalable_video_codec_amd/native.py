@@ -142,6 +142,8 @@ SIGNATURES = {
     # its decoder (csrc/levels.hip) and the gaze rule
     "svc_hip_decode_levels_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_decode_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "svc_hip_decode_entropy_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_decode_entropy_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     "svc_hip_gaze_rect": (C.c_int, [_u32] * 8 + [C.POINTER(_u32)]),
     # the wire stream's decoder (csrc/records.hip) and its reading of a whole stream
     "svc_hip_decode_records_frames": (C.c_int, [_vp, _u64] + [_u32] * 7 + [_vp, _vp, _vp, _u32, _u32, _vp]),
@@ -970,6 +972,39 @@ def decode_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h:
                                                _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
                                                None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
                                                _dev(status, torch.int32), _stream()))
+    return rec, out_display, status
+
+
+def decode_entropy_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_decode_entropy_workspace_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def decode_entropy_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, fg_step: int = 1,
+                          bg_step: int = 640, gaze=None, display: Optional[Tuple[int, int]] = None,
+                          rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """decode_levels_frames straight from an SVCE stream (no SVCQ frames in between): the same arguments and outputs, bit for bit
+    those of entropy_decode_frames followed by decode_levels_frames; status (frames,) i32 with the entropy decoder's codes."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    if rec is None:
+        rec = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    dw, dh = display if display is not None else (0, 0)
+    if display is not None and out_display is None:
+        out_display = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(decode_entropy_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    g = None
+    if gaze is not None:
+        g = torch.as_tensor(gaze, dtype=torch.int32).reshape(n, 4).to(dev).contiguous()
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_decode_entropy_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, w, h, bw, bh,
+                                                mbw, mbh, fg_step, bg_step, None if g is None else _dev(g, torch.int32),
+                                                _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
+                                                None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
+                                                _dev(status, torch.int32), _stream()))
     return rec, out_display, status
 
 

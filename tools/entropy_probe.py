@@ -4,6 +4,10 @@
                                                 the pack, then the SVCE encode, decode and drain 5 times each; run under
                                                 `rocprofv3 --kernel-trace --stats -- python ...`.  Prints the sizes and checks the
                                                 round trip.
+  python tools/entropy_probe.py decode-fused FG BG   the same batch's SVCE frames to display frames, 5 times by the two calls
+                                                (svc_hip_entropy_decode_frames, then svc_hip_decode_levels_frames) and 5 times by
+                                                svc_hip_decode_entropy_frames, in one process; run under `rocprofv3 --kernel-trace
+                                                --stats -- python ...`.  Checks that both give the same reconstruction and display.
   python tools/entropy_probe.py rate            HostStreamEncoder(compact=True) beside HostStreamEncoder(compact=True, entropy=True)
                                                 on the same 65-frame clip: frames per second and bytes per frame
   python tools/entropy_probe.py cpp             the C++ drivers on a 65-frame C3 clip made on the CPU (this process never opens the
@@ -59,6 +63,48 @@ def kernels(fg: int, bg: int) -> None:
         sys.exit(1)
 
 
+def decode_fused(fg: int, bg: int) -> None:
+    import torch
+    from scalable_video_codec_amd import native, pipeline
+    cfg = dataclasses.replace(configs.C3, fg_step=fg, bg_step=bg)
+    dev = torch.device("cuda")
+    n = 17
+    clip = synth.SynthClip(cfg.width, cfg.height, n, cfg.seed, device=dev)
+    pw, ph = cfg.padded
+    enc = pipeline.ClipEncoder(cfg, n, dev)
+    enc.load_frames([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(n)])
+    enc.step()
+    b, mb = cfg.dct_block, cfg.mv_block
+    svcq, offs = native.pack_levels_frames(enc.coeffs[:n - 1], enc.types[:n - 1], b, mb, fg, bg)
+    e, eo, st = native.entropy_encode_frames(svcq, offs, pw, ph, b, mb)
+    display = (cfg.width, cfg.height)
+    gaze = [native.gaze_rect(100 + 110 * i, 60 + 60 * i, 64, 64, cfg.width, cfg.height, pw, ph) for i in range(n - 1)]
+    gaze = torch.tensor(gaze, dtype=torch.int32, device=dev)
+    back, bo = torch.empty_like(svcq), torch.empty_like(offs)
+    ews = torch.empty(native.entropy_workspace_bytes(n - 1, pw, ph, b, mb), dtype=torch.uint8, device=dev)
+    lws = torch.empty(native.decode_levels_workspace_bytes(n - 1, pw, ph, b), dtype=torch.uint8, device=dev)
+    fws = torch.empty(native.decode_entropy_workspace_bytes(n - 1, pw, ph, b, mb), dtype=torch.uint8, device=dev)
+    rec = [torch.empty((n - 1, ph, pw, 3), dtype=torch.float32, device=dev) for _ in range(2)]
+    disp = [torch.empty((n - 1, display[1], display[0], 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+    torch.cuda.synchronize()
+    for _ in range(5):
+        _, _, es = native.entropy_decode_frames(e, eo, pw, ph, b, mb, out=back, out_offsets=bo, workspace=ews)
+        _, _, ls = native.decode_levels_frames(back, bo, pw, ph, b, mb, 1, 640, gaze=gaze, display=display, rec=rec[0],
+                                               out_display=disp[0], workspace=lws)
+    torch.cuda.synchronize()
+    for _ in range(5):
+        _, _, fs = native.decode_entropy_frames(e, eo, pw, ph, b, mb, 1, 640, gaze=gaze, display=display, rec=rec[1],
+                                                out_display=disp[1], workspace=fws)
+    torch.cuda.synchronize()
+    zeros = [0] * (n - 1)
+    ok = st.cpu().tolist() == zeros and es.cpu().tolist() == zeros and ls.cpu().tolist() == zeros and fs.cpu().tolist() == zeros and \
+        torch.equal(rec[0], rec[1]) and torch.equal(disp[0], disp[1]) and bool(disp[1].any())
+    print(f"C3 batch of {n - 1}, steps ({fg}, {bg}): SVCE {int(eo[-1]) / (n - 1) / 1e6:.4f} MB per frame; the two calls and the fused "
+          f"call {'agree' if ok else 'DISAGREE'}", flush=True)
+    if not ok:
+        sys.exit(1)
+
+
 def rate() -> None:
     import torch
     from scalable_video_codec_amd import stream
@@ -107,4 +153,5 @@ def cpp() -> None:
 
 
 if __name__ == "__main__":
-    {"kernels": lambda: kernels(int(sys.argv[2]), int(sys.argv[3])), "rate": rate, "cpp": cpp}[sys.argv[1]]()
+    {"kernels": lambda: kernels(int(sys.argv[2]), int(sys.argv[3])), "decode-fused": lambda: decode_fused(int(sys.argv[2]), int(sys.argv[3])),
+     "rate": rate, "cpp": cpp}[sys.argv[1]]()
