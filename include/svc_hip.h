@@ -641,10 +641,11 @@ int svc_hip_dct_pack_levels_budget_frames(const uint8_t* d_bgr, uint64_t frame_s
  * rectangle contains the tile origin (x <= tx < x + w && y <= ty < y + h; w or h == 0 holds
  * nothing); requantise, f64 inverse DCT.  d_rec [n][H][W][3] f32 B,G,R at the padded size is
  * bit-identical to svc_hip_unpack_levels_frames followed by svc_hip_decode_frames with that
- * frame's rectangle.  Gaze can only keep what the encoder's steps kept: a stream encoded with
- * bg_step 640 has already lost the background detail, and decoding at step 1 inside the
- * rectangle cannot restore it.  Gaze-scalable streams are encoded with small steps and
- * quantised by the decoder, as the reference's are (its wire records are raw coefficients).
+ * frame's rectangle.  In ONE stream gaze can only keep what the encoder's steps kept (a stream
+ * encoded with bg_step 640 has lost the background detail, and step 1 inside the rectangle does
+ * not restore it): a gaze-scalable compact stream is a base stream plus an enhancement stream,
+ * "Two layers" below.  The reference's own stream scales because its wire records are raw
+ * coefficients, quantised by the decoder.
  *
  * Display (d_display != NULL, display size not 0 x 0): the reference's upscaled_frame /= 255,
  * cv::resize(INTER_LINEAR) to the source size and imshow's float -> u8, stated here (parity with
@@ -711,6 +712,86 @@ int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
 int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w,
                       uint32_t frame_h, uint32_t padded_w, uint32_t padded_h,
                       uint32_t out_xywh[4]);
+
+/* ------------------------------------------------------------------------- *
+ * Two layers: a base stream at coarse steps plus an enhancement stream that lifts tiles to a fine
+ * step, taken by the decoder only where the gaze is.  Both are SVCQ streams (the drains, the
+ * entropy coder and the host reader apply unchanged); scalable_video_codec_amd/layers.py is the
+ * numpy statement of what follows.
+ *
+ * Steps fg_step, bg_step (base) and enh_step, with fg_step % enh_step == 0 and
+ * bg_step % enh_step == 0.  For a tile of class c (background when the MV block holding its
+ * origin has type 0), sb = c's base step and ratio = sb / enh_step.  For a coefficient coef:
+ *   Lb = level(coef, sb)        the level svc_hip_dct_pack_levels_frames writes
+ *   Lf = level(coef, enh_step)  the same quantiser at enh_step
+ *   d  = Lf - Lb * ratio        in int32, stored as int16; 0 for a tile whose origin the frame's
+ *                               window does not contain
+ * Base frame: byte for byte the frame svc_hip_dct_pack_levels_frames writes with (fg_step,
+ * bg_step).  Enhancement frame: an SVCQ frame, version 1, of the same geometry and region ids,
+ * fg_step = bg_step = enh_step in its header, masks = (d != 0), levels = d, inexact 0, reserved
+ * words 0, padded to 16.  A tile with sb == enh_step has every d == 0 and costs its mask bits.
+ * Window: d_window [n_frames][4] u32 x, y, w, h in padded coordinates with the containment rule
+ * of the gaze (x <= tx < x + w && y <= ty < y + h on the tile origin; w or h == 0 holds nothing),
+ * or NULL: every tile is enhanced.
+ *
+ * Decoder, per tile: not gazed -- exactly svc_hip_decode_levels_frames on the base frame.  Gazed
+ * -- level = Lb * ratio + d (d = 0 where the enhancement mask bit is clear), c = (float)level *
+ * (float)enh_step, requantised at step 1, the same inverse transform.  Lb * ratio * enh_step ==
+ * Lb * sb, so a gazed tile outside the window has the bits the base stream decodes to under that
+ * gaze, and a gazed tile inside it the bits of a stream encoded at (enh_step, enh_step).
+ * ------------------------------------------------------------------------- */
+
+/* Both streams from one pass over the B,G,R bytes: the transform kernel of
+ * svc_hip_dct_pack_levels_frames quantises every coefficient twice and packs twice; the scan and
+ * the assemble pass run once per layer.  Geometry, stride and alignment as that call (block 8 or
+ * 16, frame_w a multiple of 16; the query returns 0 where the call refuses); d_window 4-byte
+ * aligned.  Checked for any n_frames and before any pointer: geometry, stride, steps (a step of
+ * 0, or fg_step / bg_step not a multiple of enh_step -- which covers enh_step above either -- is
+ * SVC_ERR_INVALID_ARG), the int16 bounds (255 * block / enh_step > 32767, or max(fg_step,
+ * bg_step) / enh_step > 32766: SVC_ERR_UNSUPPORTED), limits, workspace, base_capacity then
+ * enh_capacity against svc_hip_levels_max_bytes; n_frames == 0 then returns SVC_OK; then
+ * pointers.  Only enqueues. */
+uint64_t svc_hip_dct_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w,
+                                                 uint32_t frame_h, uint32_t block,
+                                                 uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_dct_pack_layers_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes,
+                                   uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                   uint32_t block, const uint32_t* d_block_types,
+                                   uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                   uint32_t bg_step, uint32_t enh_step,
+                                   const uint32_t* d_window /* [n_frames][4] x, y, w, h (padded); NULL = every tile */,
+                                   uint8_t* d_workspace, uint64_t workspace_bytes,
+                                   uint8_t* d_base_out, uint64_t base_capacity,
+                                   uint64_t* d_base_offsets /* [n_frames + 1] */,
+                                   uint8_t* d_enh_out, uint64_t enh_capacity,
+                                   uint64_t* d_enh_offsets /* [n_frames + 1] */, void* stream);
+
+/* svc_hip_decode_levels_frames on a base and an enhancement stream: fg_step / bg_step are the
+ * decoder's steps for the tiles outside the gaze, d_rec, d_display and the display size as there.
+ * With d_gaze == NULL no tile takes the enhancement: the enhancement stream is neither checked
+ * nor read (d_enh may be NULL with 0 bytes) and the call is svc_hip_decode_levels_frames on the
+ * base.  d_status [n_frames] u32: the base frame's code of svc_hip_unpack_levels_frames if it is
+ * not 0; else 0x100 | code when the enhancement frame fails those same checks; else 0x100 | 11
+ * when the enhancement frame is not one of this base frame (its header's fg_step != bg_step, or
+ * a base step that is no multiple of it).  A frame with a non-zero status is zeros in d_rec and
+ * d_display and leaves its neighbours as they would be.  Geometry, check order and alignment as
+ * svc_hip_decode_levels_frames (both streams 16-byte aligned, both offset arrays 8-byte); the
+ * workspace is twice that call's.  Only enqueues. */
+uint64_t svc_hip_decode_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w,
+                                               uint32_t frame_h, uint32_t block_w,
+                                               uint32_t block_h);
+int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes,
+                                 const uint64_t* d_base_offsets, const uint8_t* d_enh,
+                                 uint64_t enh_bytes, const uint64_t* d_enh_offsets,
+                                 uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                 uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                 uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                                 const uint32_t* d_gaze /* [n_frames][4] x, y, w, h (padded); NULL = none */,
+                                 uint8_t* d_workspace, uint64_t workspace_bytes,
+                                 float* d_rec /* [n][H][W][3] f32 B,G,R, padded */,
+                                 uint8_t* d_display /* [n][display_h][display_w][3] u8 B,G,R, or NULL */,
+                                 uint32_t display_w, uint32_t display_h, uint32_t* d_status,
+                                 void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes

@@ -31,6 +31,12 @@
 //                             planes route's counts: profiles/levels_budget_c3.txt);
 //   dct_pack_select_kernel    one workgroup per frame: the sum of the parts, nz_k as its suffix sum, bytes_k, the choice
 //                             (budget_core.hpp) and the frame's steps, which dct_pack_kernel and the assemble pass then read per frame.
+//
+// Two layers (svc_hip_dct_pack_layers_frames; include/svc_hip.h states them, scalable_video_codec_amd/layers.py in numpy): a base
+// stream at (fg_step, bg_step) and an enhancement stream of residuals d = level(c, enh_step) - level(c, base step) * ratio, from ONE
+// transform.  dct_pack_layers_kernel<N> is the third form of the body: each lane quantises its coefficients twice, the wave stages
+// and walks the base levels, then stages d into the same images and walks again into a second workspace; the scan and the assemble
+// pass then run once per layer.
 #include <algorithm>
 #include <type_traits>
 
@@ -138,6 +144,14 @@ struct CountArgs {
   uint32_t* rows;
 };
 struct NoCountArgs {};
+// what the two-layer form takes besides: the enhancement's step, each class's base step / enh_step, the frames' windows, and the
+// second workspace (a.ws is the base layer's)
+struct LayerArgs {
+  float enh_step, enh_inv;
+  uint32_t fg_ratio, bg_ratio;
+  const uint32_t* window;  // [n][4] x, y, w, h in padded coordinates, or null: every tile is enhanced
+  DctPackWs enh;
+};
 constexpr uint32_t kTauTable = 2 * kMaxLadder;  // a class's thresholds, padded with +inf to what 7 probes can reach
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
@@ -148,12 +162,28 @@ __device__ __forceinline__ uint32_t pack2(f32x2 q) {  // two levels as int16, th
   return ((uint32_t)(int32_t)q.x & 0xFFFFu) | ((uint32_t)(int32_t)q.y << 16);
 }
 
+// the workspace a layer's walk fills: the base's (the only one of the one-layer forms), or the enhancement's
+template <typename K>
+__device__ __forceinline__ const DctPackWs& layer_ws(const DctPackArgs& a, const K& k, int layer) {
+  if constexpr (std::is_same_v<K, LayerArgs>) return layer == 0 ? a.ws : k.enh;
+  else return a.ws;
+}
+
+// two residuals of the enhancement layer, packed like pack2: fine level - base level * ratio in int32, kept as int16 (|d| <= ratio / 2 + 1)
+__device__ __forceinline__ uint32_t residual2(f32x2 fine, f32x2 base, int32_t ratio) {
+  const int32_t dx = (int32_t)fine.x - (int32_t)base.x * ratio, dy = (int32_t)fine.y - (int32_t)base.y * ratio;
+  return ((uint32_t)dx & 0xFFFFu) | ((uint32_t)dy << 16);
+}
+
 // COUNT = false: the fused pack.  COUNT = true: the same transform, stopped at the column pass's f32 coefficients, which are counted per
 // ladder entry instead of quantised: k, and the counting kernel's LDS -- both classes' thresholds, tau_tab[c][i] = tau[c][i] (+inf from
-// the ladder's end on), and a histogram per wave (null for the pack).
-template <int N, bool COUNT>
-__device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::conditional_t<COUNT, CountArgs, NoCountArgs>& k,
+// the ladder's end on), and a histogram per wave (null for the pack).  LAYERS = true (with COUNT = false): the fused pack of two layers,
+// the base into a.ws and the residuals of the tiles inside the frame's window into k.enh.
+template <int N, bool COUNT, bool LAYERS = false>
+__device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
+                                              const std::conditional_t<COUNT, CountArgs, std::conditional_t<LAYERS, LayerArgs, NoCountArgs>>& k,
                                               float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
+  static_assert(!(COUNT && LAYERS), "the counting form has no layers");
   constexpr uint32_t kCols = 64 / N;        // segment columns of a wave
   constexpr uint32_t kColWords = N / 4;     // mask words of a segment column: two 8x8 tiles of one word, or one 16x16 tile of four
   constexpr int kSlab = N == 8 ? kSlab8 : kSlab16;
@@ -203,6 +233,17 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::c
     inv_step = t == 0 ? fs.bg_inv : fs.fg_inv;
   }
   uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
+  int32_t ratio = 0;      // LAYERS: the lane's tile's base step / enh_step, and whether the frame's window holds the tile's origin
+  bool enhanced = false;  // (the containment rule of the decoders' gaze: w or h of 0 holds nothing)
+  if constexpr (LAYERS) {
+    ratio = (int32_t)(t == 0 ? k.bg_ratio : k.fg_ratio);
+    enhanced = true;
+    if (k.window) {
+      const uint32_t* r = k.window + 4ull * frame;
+      const uint32_t tx = N == 8 ? x_pix + 8 * (j >> 2) : x_pix;
+      enhanced = tx >= r[0] && tx - r[0] < r[2] && y_pix >= r[1] && y_pix - r[1] < r[3];
+    }
+  }
 
   uint8_t* slab = lds + sc_local * kSlab;
   const uint8_t* wave_slabs = lds + (sc_local - g) * kSlab;
@@ -227,6 +268,7 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::c
     wave_lds_sync();
 
     uint32_t lv[8];  // this lane's levels of the channel, two int16 each
+    uint32_t dv[8];  // LAYERS: its residuals, likewise
     float m[16];     // COUNT: |c| of its 16 coefficients instead
     if (N == 8) {
       // lane j takes columns 2j, 2j+1 of the 16-wide slab (tile j >> 2): lv[v] = row v
@@ -244,6 +286,10 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::c
         if constexpr (COUNT) {
           m[2 * v] = fabsf((float)ya[v]);
           m[2 * v + 1] = fabsf((float)yb[v]);
+        } else if constexpr (LAYERS) {
+          const f32x2 cf{(float)ya[v], (float)yb[v]}, qb = quant2_level(cf, step, inv_step);
+          lv[v] = pack2(qb);
+          dv[v] = enhanced ? residual2(quant2_level(cf, k.enh_step, k.enh_inv), qb, ratio) : 0u;
         } else {
           lv[v] = pack2(quant2_level(f32x2{(float)ya[v], (float)yb[v]}, step, inv_step));
         }
@@ -259,6 +305,10 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::c
         if constexpr (COUNT) {
           m[v] = fabsf((float)yy[v]);
           m[v + 1] = fabsf((float)yy[v + 1]);
+        } else if constexpr (LAYERS) {
+          const f32x2 cf{(float)yy[v], (float)yy[v + 1]}, qb = quant2_level(cf, step, inv_step);
+          lv[v / 2] = pack2(qb);
+          dv[v / 2] = enhanced ? residual2(quant2_level(cf, k.enh_step, k.enh_inv), qb, ratio) : 0u;
         } else {
           lv[v / 2] = pack2(quant2_level(f32x2{(float)yy[v], (float)yy[v + 1]}, step, inv_step));
         }
@@ -289,44 +339,51 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::c
       continue;  // (the slabs are free for the next channel: the sync above)
     }
 
-    if (N == 8) {
-      uint8_t* img = slab + image_at(g, j >> 2) + (j & 3u) * 4;  // coefficient (v, 2 (j & 3)) of tile j >> 2: 2 * (v * 8 + 2 (j & 3)) bytes in
+    // a layer of this channel: the lane's levels q to the column's tile images, then the wave's walk into the layer's workspace.  The
+    // second layer's images replace the first's once the walk has read them (the sync that ends a layer)
 #pragma unroll
-      for (int v = 0; v < 8; ++v) *reinterpret_cast<uint32_t*>(img + v * 16) = lv[v];
-    } else {
-      uint8_t* img = slab + image_at(g, 0) + j * 2;  // coefficient (v, j): 2 * (v * 16 + j) bytes in
+    for (int layer = 0; layer < (LAYERS ? 2 : 1); ++layer) {
+      const uint32_t* q = layer == 0 ? lv : dv;
+      const DctPackWs& ws = layer_ws(a, k, layer);
+      if (N == 8) {
+        uint8_t* img = slab + image_at(g, j >> 2) + (j & 3u) * 4;  // coefficient (v, 2 (j & 3)) of tile j >> 2: 2 * (v * 8 + 2 (j & 3)) bytes in
 #pragma unroll
-      for (int v = 0; v < 16; v += 2) {
-        *reinterpret_cast<uint16_t*>(img + v * 32) = (uint16_t)lv[v / 2];
-        *reinterpret_cast<uint16_t*>(img + (v + 1) * 32) = (uint16_t)(lv[v / 2] >> 16);
+        for (int v = 0; v < 8; ++v) *reinterpret_cast<uint32_t*>(img + v * 16) = q[v];
+      } else {
+        uint8_t* img = slab + image_at(g, 0) + j * 2;  // coefficient (v, j): 2 * (v * 16 + j) bytes in
+#pragma unroll
+        for (int v = 0; v < 16; v += 2) {
+          *reinterpret_cast<uint16_t*>(img + v * 32) = (uint16_t)q[v / 2];
+          *reinterpret_cast<uint16_t*>(img + (v + 1) * 32) = (uint16_t)(q[v / 2] >> 16);
+        }
       }
-    }
-    wave_lds_sync();
+      wave_lds_sync();
 
-    // the piece of this channel
-    const size_t piece = ((size_t)frame * 3 + c) * gm.l.tiles_y * gm.waves_per_row + (size_t)band * gm.waves_per_row + wr;
-    int16_t* slot = a.ws.slots + piece * kPieceLevels;
-    // all 16 words of the wave, idle columns included (their images hold the levels of zero pixels: zeros, so their masks are 0 and
-    // nothing of them is stored): no trip count, so the reads go out together and the walk is straight-line code
-    constexpr uint32_t kWaveWords = kCols * kColWords;
-    int16_t l16[kWaveWords];
+      // the piece of this channel
+      const size_t piece = ((size_t)frame * 3 + c) * gm.l.tiles_y * gm.waves_per_row + (size_t)band * gm.waves_per_row + wr;
+      int16_t* slot = ws.slots + piece * kPieceLevels;
+      // all 16 words of the wave, idle columns included (their images hold the levels of zero pixels: zeros, so their masks are 0 and
+      // nothing of them is stored): no trip count, so the reads go out together and the walk is straight-line code
+      constexpr uint32_t kWaveWords = kCols * kColWords;
+      int16_t l16[kWaveWords];
 #pragma unroll
-    for (uint32_t w = 0; w < kWaveWords; ++w)
-      l16[w] = *reinterpret_cast<const int16_t*>(wave_slabs + (w / kColWords) * kSlab + image_at(w / kColWords, w % kColWords) + lane * 2);
-    uint32_t base = 0;  // levels of the words before this one: wave-uniform
-    uint64_t mine = 0;  // lane w keeps word w's mask: one store of the piece's masks at the end
+      for (uint32_t w = 0; w < kWaveWords; ++w)
+        l16[w] = *reinterpret_cast<const int16_t*>(wave_slabs + (w / kColWords) * kSlab + image_at(w / kColWords, w % kColWords) + lane * 2);
+      uint32_t base = 0;  // levels of the words before this one: wave-uniform
+      uint64_t mine = 0;  // lane w keeps word w's mask: one store of the piece's masks at the end
 #pragma unroll
-    for (uint32_t w = 0; w < kWaveWords; ++w) {
-      const uint64_t mask = __ballot(l16[w] != 0);
-      if (l16[w] != 0) slot[base + lane_rank(mask)] = l16[w];
-      if (lane == w) mine = mask;
-      base += (uint32_t)__popcll(mask);
+      for (uint32_t w = 0; w < kWaveWords; ++w) {
+        const uint64_t mask = __ballot(l16[w] != 0);
+        if (l16[w] != 0) slot[base + lane_rank(mask)] = l16[w];
+        if (lane == w) mine = mask;
+        base += (uint32_t)__popcll(mask);
+      }
+      uint32_t* masks = ws.masks + (size_t)frame * (up16(4ull * gm.mask_dwords) / 4) +
+                        2 * ((((size_t)c * gm.l.tiles_y + band) * gm.l.tiles_x) * gm.l.words + word0);
+      if (lane < nwords) store_mask(masks + 2 * lane, mine);
+      if (lane == 0) ws.counts[piece] = base;
+      wave_lds_sync();  // the slabs are rewritten: by the next layer's images, or by the next channel
     }
-    uint32_t* masks = a.ws.masks + (size_t)frame * (up16(4ull * gm.mask_dwords) / 4) +
-                      2 * ((((size_t)c * gm.l.tiles_y + band) * gm.l.tiles_x) * gm.l.words + word0);
-    if (lane < nwords) store_mask(masks + 2 * lane, mine);
-    if (lane == 0) a.ws.counts[piece] = base;
-    wave_lds_sync();  // the slabs are rewritten by the next channel
   }
   if constexpr (COUNT) {  // the wave's row: bins 0 .. len - 2 as they are, bin len - 1 = the lanes' full counts
     uint32_t* hist = hist_all[tid >> 6];
@@ -339,6 +396,11 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a, const std::c
 template <int N>
 __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
   dct_pack_body<N, false>(a, NoCountArgs{}, nullptr, nullptr);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void dct_pack_layers_kernel(DctPackArgs a, LayerArgs k) {
+  dct_pack_body<N, false, true>(a, k, nullptr, nullptr);
 }
 
 template <int N>
@@ -509,22 +571,31 @@ int validate_pack_limits(const char* what, uint32_t n, const PackGeom& g) {
   return SVC_OK;
 }
 
-// the fused pack's three launches, with a.fg_step / a.bg_step (fg, bg in the headers) or each frame's own steps
-int enqueue_dct_pack(const char* what, DctPackArgs& a, uint32_t n_frames, uint32_t fg, uint32_t bg, uint8_t* d_out, uint64_t* d_frame_offsets,
-                     hipStream_t s) {
+// what follows the transform, for the layer whose pieces are in ws: the scan and the assemble pass, with fg / bg in the headers or
+// each frame's own steps
+int enqueue_assemble(const char* what, const DctPackArgs& a, const DctPackWs& ws, uint32_t n_frames, uint32_t fg, uint32_t bg, uint8_t* d_out,
+                     uint64_t* d_frame_offsets, hipStream_t s) {
   const PackGeom& g = a.g;
-  int rc;
-  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
-  if (g.n_block == 8) hipLaunchKernelGGL(dct_pack_kernel<8>, grid, blk, 0, s, a);
-  else hipLaunchKernelGGL(dct_pack_kernel<16>, grid, blk, 0, s, a);
-  if ((rc = check_launch(what, "transform"))) return rc;
-  hipLaunchKernelGGL(dct_pack_scan_kernel, dim3(n_frames), blk, 0, s, g.pieces, g.l.levels_off, a.ws);
-  if ((rc = check_launch(what, "scan"))) return rc;
-  const AssembleArgs as{g, fg, bg, a.steps, a.types, a.ws, d_out, d_frame_offsets};
+  const dim3 blk(kThreads);
+  hipLaunchKernelGGL(dct_pack_scan_kernel, dim3(n_frames), blk, 0, s, g.pieces, g.l.levels_off, ws);
+  const int rc = check_launch(what, "scan");
+  if (rc) return rc;
+  const AssembleArgs as{g, fg, bg, a.steps, a.types, ws, d_out, d_frame_offsets};
   // a wave per piece and trip; enough workgroups per frame to keep a single 4K frame busy, few enough that a batch is not all launch
   const uint32_t per_frame = std::min<uint32_t>(std::max<uint32_t>(div_up(g.pieces, 32), 1), 256);
   hipLaunchKernelGGL(dct_pack_assemble_kernel, dim3(per_frame, n_frames), blk, 0, s, as);
   return check_launch(what, "assemble");
+}
+
+// the fused pack's three launches, with a.fg_step / a.bg_step (fg, bg in the headers) or each frame's own steps
+int enqueue_dct_pack(const char* what, DctPackArgs& a, uint32_t n_frames, uint32_t fg, uint32_t bg, uint8_t* d_out, uint64_t* d_frame_offsets,
+                     hipStream_t s) {
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (a.g.n_block == 8) hipLaunchKernelGGL(dct_pack_kernel<8>, grid, blk, 0, s, a);
+  else hipLaunchKernelGGL(dct_pack_kernel<16>, grid, blk, 0, s, a);
+  const int rc = check_launch(what, "transform");
+  if (rc) return rc;
+  return enqueue_assemble(what, a, a.ws, n_frames, fg, bg, d_out, d_frame_offsets, s);
 }
 
 }  // namespace
@@ -579,6 +650,78 @@ int svc_hip_dct_pack_levels_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
   a.bg_inv = 1.0f / a.bg_step;
   a.ws = carve(d_workspace, n_frames, g);
   return enqueue_dct_pack("dct_pack_levels", a, n_frames, fg_step, bg_step, d_out, d_frame_offsets, s);
+}
+
+uint64_t svc_hip_dct_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,
+                                                 uint32_t mv_block_h) {
+  if (validate_pack_geom("dct_pack_layers_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits("dct_pack_layers_workspace_bytes", n_frames, g)) return 0;
+  return 2 * pack_ws_bytes(n_frames, g);  // a layer's workspace is a multiple of 16 B: the second starts aligned
+}
+
+// Checked in the order of svc_hip_dct_pack_levels_frames: geometry, stride, steps, the int16 bounds, limits, workspace, both capacities;
+// n_frames == 0 then returns SVC_OK; then pointers.
+int svc_hip_dct_pack_layers_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                   uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                   uint32_t bg_step, uint32_t enh_step, const uint32_t* d_window, uint8_t* d_workspace,
+                                   uint64_t workspace_bytes, uint8_t* d_base_out, uint64_t base_capacity, uint64_t* d_base_offsets,
+                                   uint8_t* d_enh_out, uint64_t enh_capacity, uint64_t* d_enh_offsets, void* stream) {
+  int rc = validate_pack_geom("dct_pack_layers", frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "dct_pack_layers: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", (unsigned long long)frame_stride_bytes,
+              3ull * frame_w * frame_h);
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0 && enh_step > 0, "dct_pack_layers: quant steps must be positive");
+  // (a step that divides is not above: this also refuses enh_step > min(fg_step, bg_step))
+  SVC_REQUIRE(fg_step % enh_step == 0 && bg_step % enh_step == 0, "dct_pack_layers: fg_step %u and bg_step %u must each be a multiple of enh_step %u",
+              fg_step, bg_step, enh_step);
+  // the pack's int16 bound (Parseval) on the fine levels; the residuals are within ratio / 2 + 1 of zero
+  if (255.0 * block / enh_step > 32767.0)
+    return fail(SVC_ERR_UNSUPPORTED, "dct_pack_layers: levels of a %ux%u tile at step %u could exceed int16", block, block, enh_step);
+  if (std::max(fg_step, bg_step) / enh_step > 32766)
+    return fail(SVC_ERR_UNSUPPORTED, "dct_pack_layers: a base step of %u is more than 32766 times enh_step %u: a residual could exceed int16",
+                std::max(fg_step, bg_step), enh_step);
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits("dct_pack_layers", n_frames, g))) return rc;
+  const uint64_t ws_layer = pack_ws_bytes(n_frames, g), ws_need = 2 * ws_layer;
+  SVC_REQUIRE(workspace_bytes >= ws_need, "dct_pack_layers: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
+  const uint64_t need = n_frames * g.l.max_bytes;
+  SVC_REQUIRE(base_capacity >= need, "dct_pack_layers: base output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)base_capacity, (unsigned long long)need);
+  SVC_REQUIRE(enh_capacity >= need, "dct_pack_layers: enhancement output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)enh_capacity, (unsigned long long)need);
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_base_out && d_base_offsets && d_enh_out && d_enh_offsets, "dct_pack_layers: null pointer");
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_base_out, 16) && aligned(d_enh_out, 16) && aligned(d_workspace, 16) && aligned(d_base_offsets, 8) &&
+                  aligned(d_enh_offsets, 8) && aligned(d_block_types, 4) && aligned(d_window, 4),
+              "dct_pack_layers: frames, outputs and workspace must be 16-byte aligned, offsets 8-byte, types and window 4-byte");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.total_waves = n_frames * g.l.tiles_y * g.waves_per_row;
+  a.types = d_block_types;
+  a.fg_step = (float)fg_step;
+  a.bg_step = (float)bg_step;
+  a.fg_inv = 1.0f / a.fg_step;
+  a.bg_inv = 1.0f / a.bg_step;
+  a.ws = carve(d_workspace, n_frames, g);
+  LayerArgs k{};
+  k.enh_step = (float)enh_step;
+  k.enh_inv = 1.0f / k.enh_step;
+  k.fg_ratio = fg_step / enh_step;
+  k.bg_ratio = bg_step / enh_step;
+  k.window = d_window;
+  k.enh = carve(d_workspace + ws_layer, n_frames, g);
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (block == 8) hipLaunchKernelGGL(dct_pack_layers_kernel<8>, grid, blk, 0, s, a, k);
+  else hipLaunchKernelGGL(dct_pack_layers_kernel<16>, grid, blk, 0, s, a, k);
+  if ((rc = check_launch("dct_pack_layers", "transform"))) return rc;
+  if ((rc = enqueue_assemble("dct_pack_layers base", a, a.ws, n_frames, fg_step, bg_step, d_base_out, d_base_offsets, s))) return rc;
+  return enqueue_assemble("dct_pack_layers enhancement", a, k.enh, n_frames, enh_step, enh_step, d_enh_out, d_enh_offsets, s);
 }
 
 uint64_t svc_hip_dct_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,

@@ -18,6 +18,9 @@
 // decode: unpack's count and scan, then one kernel from the stream straight to the decoder's reconstruction (DecodeBlock with a
 // gaze rectangle per frame, the arithmetic of idct_core.hpp), and optionally the display pass of display_core.hpp (/ 255, bilinear
 // resize, to u8).
+//
+// decode of two layers (svc_hip_decode_layers_frames; include/svc_hip.h states them): the count and scan of each stream, a per-frame
+// merge of the two statuses, then the decode kernel's sibling, which inside the gaze adds the enhancement frame's residuals.
 #include "budget_core.hpp"
 #include "display_core.hpp"
 #include "idct_core.hpp"
@@ -555,6 +558,130 @@ __global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
   store_bgr_column<N>(a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3, g.w, out);
 }
 
+// ---- decode of two layers ------------------------------------------------------------------------------------------------------
+
+struct DecodeLayersArgs {
+  DecodeArgs base;              // in / offsets / ws: the base stream's; base.gaze is not null
+  const uint8_t* enh;
+  const uint64_t* enh_offsets;
+  Ws enh_ws;
+};
+
+// One thread per frame, after both scans: the frame's status -- the base frame's code, else kStEnhancement | the enhancement frame's,
+// else kStEnhancement | kStLayer for an enhancement frame that is not one of this base frame (two steps in its header, or a base step
+// that is no multiple of its step) -- to d_status and to the base workspace, where the reconstruction reads it.
+__global__ __launch_bounds__(256) void layers_status_kernel(DecodeLayersArgs a, uint32_t n, uint32_t* d_status) {
+  const uint32_t f = blockIdx.x * kThreads + threadIdx.x;
+  if (f >= n) return;
+  uint32_t st = a.base.ws.status[f];
+  if (st == kStOk && a.enh_ws.status[f] != kStOk) st = kStEnhancement | a.enh_ws.status[f];
+  if (st == kStOk) {  // both passed their checks: their headers are inside their streams, and no step is 0
+    const uint32_t* hb = reinterpret_cast<const uint32_t*>(a.base.in + a.base.offsets[f]);
+    const uint32_t* he = reinterpret_cast<const uint32_t*>(a.enh + a.enh_offsets[f]);
+    const uint32_t e = he[kHFgStep];
+    if (he[kHBgStep] != e || hb[kHFgStep] % e != 0 || hb[kHBgStep] % e != 0) st = kStEnhancement | kStLayer;
+  }
+  a.base.ws.status[f] = st;
+  d_status[f] = st;
+}
+
+// decode_levels_kernel<N> with the enhancement: the same workgroups, threads and arithmetic.  A workgroup whose group holds a gazed
+// tile also loads the enhancement frame's mask words of its jobs and scans them; a thread of a gazed tile gathers the residual d by
+// rank beside the base level Lb and decodes (Lb * ratio + d) at the enhancement's step, ratio = the tile's base step / that step.
+// Lb * ratio * enh_step == Lb * base step, so a gazed tile without residuals has the bits decode_levels_kernel gives it; every other
+// tile takes that kernel's path.
+template <int N>
+__global__ __launch_bounds__(256) void decode_layers_kernel(DecodeLayersArgs la) {
+  constexpr uint32_t kRows = kGroupCoeffs / N;
+  __shared__ uint64_t job_mask[kMaxJobs], enh_mask[kMaxJobs];
+  __shared__ uint32_t job_base[kMaxJobs], enh_base[kMaxJobs];
+  __shared__ uint32_t red[kThreads / 64];
+  __shared__ double rows[kRows * (N + 1)];
+  const DecodeArgs& a = la.base;
+  const Geom& g = a.g;
+  const uint32_t gi0 = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  const Group gr = group_of(g, gi0);
+  const uint32_t st = a.ws.status[f];  // the merged status: 0 = both frames may be read
+  const uint8_t* frame = a.in + a.offsets[f];
+  const uint8_t* eframe = la.enh + (st == kStOk ? la.enh_offsets[f] : 0);
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t t = tid / N, j = tid - t * N;
+  const bool active = t < gr.nt;
+  float enc = 0.f, dec = 1.f;
+  bool in_gaze = false;
+  uint32_t ratio = 0;
+  float enh_step = 0.f;
+  if (st == kStOk && active) {
+    const uint32_t type = tile_type(g, reinterpret_cast<const uint32_t*>(frame + kHeaderBytes), gr, t);
+    in_gaze = gazed(a.gaze, f, gr.x0 + t * N, gr.y0);
+    const uint32_t enc_step = type == 0 ? hdr[kHBgStep] : hdr[kHFgStep];
+    enc = (float)enc_step;
+    dec = in_gaze ? 1.f : (type == 0 ? a.bg : a.fg);
+    if (in_gaze) {
+      const uint32_t e = reinterpret_cast<const uint32_t*>(eframe)[kHFgStep];
+      ratio = enc_step / e;
+      enh_step = (float)e;
+    }
+  }
+  const bool any_gazed = __syncthreads_or(in_gaze) != 0;  // the same in every thread: the barriers below depend on it
+  const uint32_t jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
+  float out[3][N];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const size_t word0 = 2 * ((((size_t)c * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+    const uint32_t* masks = st != kStOk ? nullptr : reinterpret_cast<const uint32_t*>(frame + g.masks_off) + word0;
+    const uint64_t m = (masks && tid < jobs) ? load_mask(masks + 2 * tid) : 0ull;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
+    if (tid < jobs) { job_mask[tid] = m; job_base[tid] = ex; }
+    if (any_gazed) {  // (then st == kStOk)
+      const uint64_t me = tid < jobs ? load_mask(reinterpret_cast<const uint32_t*>(eframe + g.masks_off) + word0 + 2 * tid) : 0ull;
+      const uint32_t exe = block_exclusive_scan((uint32_t)__popcll(me), red, &total);
+      if (tid < jobs) { enh_mask[tid] = me; enh_base[tid] = exe; }
+    }
+    __syncthreads();
+    if (active) {
+      const size_t gi = (size_t)f * g.groups + c * per_plane + gi0;
+      const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) + (st == kStOk ? a.ws.cnt[gi] : 0u);
+      const int16_t* resid = reinterpret_cast<const int16_t*>(eframe + g.levels_off) + (in_gaze ? la.enh_ws.cnt[gi] : 0u);
+      double y[N], r[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const uint32_t k = j * N + i, w = t * g.words + (k >> 6), b = k & 63u;
+        const uint64_t mask = job_mask[w], below = (1ull << b) - 1;
+        float v = 0.f;
+        if (in_gaze) {
+          const uint64_t emask = enh_mask[w];
+          // unsigned: a stream that breaks the format's bound on a level wraps instead of overflowing
+          uint32_t lv = 0;
+          if ((mask >> b) & 1u) lv = (uint32_t)(int32_t)levels[job_base[w] + (uint32_t)__popcll(mask & below)] * ratio;
+          if ((emask >> b) & 1u) lv += (uint32_t)(int32_t)resid[enh_base[w] + (uint32_t)__popcll(emask & below)];
+          v = (float)(int32_t)lv * enh_step;
+        } else if ((mask >> b) & 1u) {
+          v = (float)levels[job_base[w] + (uint32_t)__popcll(mask & below)] * enc;
+        }
+        y[i] = (double)requant(v, dec);
+      }
+      idct1d<N>(y, r);
+      double* row = rows + (t * N + j) * (N + 1);
+#pragma unroll
+      for (int i = 0; i < N; ++i) row[i] = r[i];
+    }
+    __syncthreads();
+    if (active) {
+      double cc[N], xx[N];
+#pragma unroll
+      for (int v = 0; v < N; ++v) cc[v] = rows[(t * N + v) * (N + 1) + j];
+      idct1d<N>(cc, xx);
+#pragma unroll
+      for (int y = 0; y < N; ++y) out[c][y] = (float)xx[y];
+    }
+    __syncthreads();  // the next plane reuses rows and the job arrays
+  }
+  if (!active) return;
+  store_bgr_column<N>(a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3, g.w, out);
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -811,6 +938,55 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   else hipLaunchKernelGGL(decode_levels_kernel<16>, grid, dim3(kThreads), 0, s, a);
   if ((rc = check_launch("decode_levels reconstruction")) || !display) return rc;
   return launch_display("decode_levels", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+}
+
+uint64_t svc_hip_decode_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                               uint32_t block_h) {
+  if (validate_decode_geom("decode_layers_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
+      validate_limits("decode_layers_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
+    return 0;
+  return 2 * ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);  // a stream's half is a multiple of 16 B
+}
+
+// Checked in the order of svc_hip_decode_levels_frames.  Without a gaze no tile takes the enhancement: the call is that one on the base.
+int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, const uint64_t* d_base_offsets, const uint8_t* d_enh,
+                                 uint64_t enh_bytes, const uint64_t* d_enh_offsets, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                 uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                 uint32_t bg_step, const uint32_t* d_gaze, uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec,
+                                 uint8_t* d_display, uint32_t display_w, uint32_t display_h, uint32_t* d_status, void* stream) {
+  int rc = validate_decode_geom("decode_layers", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_layers: quant steps must be positive (libs/decoder.cpp:35-47)");
+  const bool display = display_w != 0 || display_h != 0;
+  if ((rc = validate_display("decode_layers", display_w, display_h, frame_w, frame_h))) return rc;
+  if ((rc = validate_limits("decode_layers", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  const uint64_t ws_stream = ws_bytes(n_frames, g.groups);
+  SVC_REQUIRE(workspace_bytes >= 2 * ws_stream, "decode_layers: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)(2 * ws_stream));
+  if (n_frames == 0) return SVC_OK;
+  if (!d_gaze)
+    return svc_hip_decode_levels_frames(d_base, base_bytes, d_base_offsets, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w,
+                                        mv_block_h, fg_step, bg_step, nullptr, d_workspace, workspace_bytes, d_rec, d_display, display_w,
+                                        display_h, d_status, stream);
+  SVC_REQUIRE(d_base && d_base_offsets && d_enh && d_enh_offsets && d_workspace && d_rec && d_status, "decode_layers: null pointer");
+  SVC_REQUIRE(display == (d_display != nullptr), "decode_layers: a display buffer goes with a display size, and only with one");
+  SVC_REQUIRE(aligned(d_base, 16) && aligned(d_enh, 16) && aligned(d_workspace, 16) && aligned(d_base_offsets, 8) && aligned(d_enh_offsets, 8) &&
+                  aligned(d_rec, 4) && aligned(d_status, 4) && aligned(d_gaze, 4),
+              "decode_layers: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
+  const UnpackArgs ub{g, d_base, base_bytes, d_base_offsets, nullptr, nullptr, carve(d_workspace, n_frames, g.groups)};
+  const UnpackArgs ue{g, d_enh, enh_bytes, d_enh_offsets, nullptr, nullptr, carve(d_workspace + ws_stream, n_frames, g.groups)};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = enqueue_unpack_scan("decode_layers base", ub, n_frames, d_status, s))) return rc;
+  if ((rc = enqueue_unpack_scan("decode_layers enhancement", ue, n_frames, ue.ws.status, s))) return rc;  // its codes stay in its workspace
+  const DecodeLayersArgs a{{g, d_base, d_base_offsets, d_gaze, d_rec, ub.ws, (float)fg_step, (float)bg_step}, d_enh, d_enh_offsets, ue.ws};
+  hipLaunchKernelGGL(layers_status_kernel, dim3(div_up(n_frames, kThreads)), dim3(kThreads), 0, s, a, n_frames, d_status);
+  if ((rc = check_launch("decode_layers status"))) return rc;
+  const dim3 grid(g.tiles_y * g.gx, n_frames);
+  if (block_w == 8) hipLaunchKernelGGL(decode_layers_kernel<8>, grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL(decode_layers_kernel<16>, grid, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("decode_layers reconstruction")) || !display) return rc;
+  return launch_display("decode_layers", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w, uint32_t frame_h, uint32_t padded_w,

@@ -1,0 +1,127 @@
+"""The two layers of a gaze-scalable compact stream (include/svc_hip.h, "Two layers"), stated in numpy on top of the host reader of
+SVCQ frames (levels.parse_frame): what svc_hip_dct_pack_layers_frames writes as its enhancement stream, given the base stream and the
+stream encoded at (enh_step, enh_step), and the levels and steps svc_hip_decode_layers_frames dequantises.  A consumer needs neither a
+GPU nor the native library.
+
+For a tile of class c (background when the MV block holding its origin has type 0), sb = c's base step and ratio = sb / enh_step (the
+steps divide).  Per coefficient, with Lb its level in the base frame and Lf its level at enh_step:
+    d = Lf - Lb * ratio     inside the frame's window, 0 outside it
+and an enhancement frame is an SVCQ frame whose levels are d, with fg_step = bg_step = enh_step in its header.  Inside the gaze the
+decoder dequantises (Lb * ratio + d) * enh_step, elsewhere Lb * sb."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import levels
+
+GEOMETRY = ("frame_w", "frame_h", "block_w", "block_h", "mv_block_w", "mv_block_h")
+
+
+def _tile_maps(hdr: Dict[str, int], types: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Per tile (tiles_y, tiles_x): is it background, and its origin's x and y."""
+    tx, ty = hdr["frame_w"] // hdr["block_w"], hdr["frame_h"] // hdr["block_h"]
+    ox, oy = np.arange(tx) * hdr["block_w"], np.arange(ty) * hdr["block_h"]
+    background = types[(oy // hdr["mv_block_h"])[:, None], (ox // hdr["mv_block_w"])[None, :]] == 0
+    return background, np.broadcast_to(ox[None, :], (ty, tx)), np.broadcast_to(oy[:, None], (ty, tx))
+
+
+def _per_pixel(hdr: Dict[str, int], per_tile: np.ndarray) -> np.ndarray:
+    return np.repeat(np.repeat(per_tile, hdr["block_h"], 0), hdr["block_w"], 1)
+
+
+def _contains(rect, ox: np.ndarray, oy: np.ndarray) -> np.ndarray:
+    """The containment rule of the gaze and of the window: the rectangle x, y, w, h holds the tile origin; w or h of 0 holds nothing."""
+    x, y, w, h = (int(v) for v in rect)
+    return (ox >= x) & (ox - x < w) & (oy >= y) & (oy - y < h)
+
+
+def _levels_of(hdr: Dict[str, int], types: np.ndarray, planes: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """parse_frame's planes (level * step, rounded to f32) back to the integer levels (3, H, W) i64, and the step of each tile.  The
+    f32 rounding moves level * step by at most 2^-24 of itself, that is the quotient by less than 2^-9: rint gives the level back."""
+    background, _, _ = _tile_maps(hdr, types)
+    step = np.where(background, hdr["bg_step"], hdr["fg_step"]).astype(np.int64)
+    lv = np.rint(planes.astype(np.float64) / _per_pixel(hdr, step)[None]).astype(np.int64)
+    return lv, step
+
+
+def write_frame(hdr: Dict[str, int], types: np.ndarray, lv: np.ndarray, fg_step: int, bg_step: int) -> bytes:
+    """An SVCQ frame of hdr's geometry with the region ids `types` and the integer levels lv (3, H, W), inexact 0."""
+    w, h, bw, bh = hdr["frame_w"], hdr["frame_h"], hdr["block_w"], hdr["block_h"]
+    tx, ty, area = w // bw, h // bh, bw * bh
+    nw = (area + 63) // 64
+    if lv.min(initial=0) < -32768 or lv.max(initial=0) > 32767:
+        raise ValueError("a level outside int16")
+    tiles = lv.reshape(3, ty, bh, tx, bw).transpose(0, 1, 3, 2, 4).reshape(3, ty, tx, area)
+    nz = tiles != 0
+    bits = np.zeros((3, ty, tx, nw * 64), bool)
+    bits[..., :area] = nz
+    masks = np.packbits(bits, axis=-1, bitorder="little")
+    body = np.ascontiguousarray(types, "<u4").tobytes() + masks.tobytes() + tiles[nz].astype("<i2").tobytes()
+    size = (levels.HEADER_BYTES + len(body) + 15) // 16 * 16
+    head = np.array([levels.MAGIC, levels.VERSION, w, h, bw, bh, hdr["mv_block_w"], hdr["mv_block_h"], fg_step, bg_step,
+                     int(nz.sum()), 0, size, 0, 0, 0], "<u4").tobytes()
+    return head + body + bytes(size - levels.HEADER_BYTES - len(body))
+
+
+def _belongs(hb: Dict[str, int], he: Dict[str, int]) -> bool:
+    """Is `he` the header of an enhancement (or fine) frame of the base frame `hb`: one step, which divides both base steps?"""
+    e = he["fg_step"]
+    return e != 0 and he["bg_step"] == e and hb["fg_step"] % e == 0 and hb["bg_step"] % e == 0
+
+
+def enhancement_frame(base_frame, fine_frame, enh_step: int, window=None) -> bytes:
+    """One enhancement frame from the base frame and the frame encoded at (enh_step, enh_step); window: x, y, w, h or None."""
+    hb, types, pb = levels.parse_frame(base_frame)
+    hf, types_f, pf = levels.parse_frame(fine_frame)
+    if any(hb[k] != hf[k] for k in GEOMETRY) or not np.array_equal(types, types_f):
+        raise ValueError("the base and the fine frame differ in geometry or region ids")
+    if hf["fg_step"] != enh_step or not _belongs(hb, hf):
+        raise ValueError(f"the fine frame's steps ({hf['fg_step']}, {hf['bg_step']}) are not ({enh_step}, {enh_step}), or enh_step does "
+                         f"not divide the base steps ({hb['fg_step']}, {hb['bg_step']})")
+    lb, step = _levels_of(hb, types, pb)
+    lf, _ = _levels_of(hf, types, pf)
+    d = lf - lb * _per_pixel(hb, step // enh_step)[None]
+    if window is not None:
+        _, ox, oy = _tile_maps(hb, types)
+        d = np.where(_per_pixel(hb, _contains(window, ox, oy))[None], d, 0)
+    return write_frame(hb, types, d, enh_step, enh_step)
+
+
+def enhancement_frames(base, base_offsets, fine, fine_offsets, enh_step: int, window=None) -> Tuple[bytes, np.ndarray]:
+    """The enhancement stream of a batch -> (bytes, offsets (n + 1,) u64): frame f from base frame f and fine frame f (the stream
+    encoded at (enh_step, enh_step)); window: None (every tile is enhanced) or per frame x, y, w, h in padded coordinates (n, 4)."""
+    b = np.frombuffer(base, np.uint8) if not isinstance(base, np.ndarray) else base.reshape(-1).view(np.uint8)
+    f = np.frombuffer(fine, np.uint8) if not isinstance(fine, np.ndarray) else fine.reshape(-1).view(np.uint8)
+    bo = [int(o) for o in np.asarray(base_offsets).reshape(-1)]
+    fo = [int(o) for o in np.asarray(fine_offsets).reshape(-1)]
+    if len(bo) != len(fo):
+        raise ValueError("the two streams hold different numbers of frames")
+    n = len(bo) - 1
+    win = None if window is None else np.asarray(window).reshape(n, 4)
+    frames = [enhancement_frame(b[bo[i]:bo[i + 1]], f[fo[i]:fo[i + 1]], enh_step, None if win is None else win[i]) for i in range(n)]
+    offs = np.concatenate([[0], np.cumsum([len(fr) for fr in frames])]).astype(np.uint64)
+    return b"".join(frames), offs
+
+
+def merge_levels(base_frame, enh_frame, gaze: Optional[Sequence[int]] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """What the decoder dequantises -> (levels (3, H, W) i64, steps (tiles_y, tiles_x) i64): for a tile whose origin the gaze rectangle
+    (x, y, w, h, or None) contains, Lb * ratio + d at the enhancement's step; for every other tile the base frame's levels and step.
+    Raises for an enhancement frame that does not belong to the base frame (the decoder's status 0x100 | 11)."""
+    hb, types, pb = levels.parse_frame(base_frame)
+    lb, step = _levels_of(hb, types, pb)
+    if gaze is None:
+        return lb, step
+    he, _, pe = levels.parse_frame(enh_frame)
+    if any(hb[k] != he[k] for k in GEOMETRY):
+        raise ValueError("the base and the enhancement frame differ in geometry")
+    if not _belongs(hb, he):
+        raise ValueError(f"an enhancement frame with steps ({he['fg_step']}, {he['bg_step']}) is not a layer of a base frame with "
+                         f"({hb['fg_step']}, {hb['bg_step']})")
+    e = he["fg_step"]
+    d = np.rint(pe.astype(np.float64) / e).astype(np.int64)  # one step for every tile, whatever the region ids
+    _, ox, oy = _tile_maps(hb, types)
+    gazed = _contains(gaze, ox, oy)
+    merged = np.where(_per_pixel(hb, gazed)[None], lb * _per_pixel(hb, step // e)[None] + d, lb)
+    return merged, np.where(gazed, e, step)

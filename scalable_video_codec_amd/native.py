@@ -145,6 +145,12 @@ SIGNATURES = {
     "svc_hip_decode_entropy_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_decode_entropy_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     "svc_hip_gaze_rect": (C.c_int, [_u32] * 8 + [C.POINTER(_u32)]),
+    # two layers: a base and an enhancement stream from one transform, and their decode under a gaze (host statement: layers.py)
+    "svc_hip_dct_pack_layers_workspace_bytes": (_u64, [_u32] * 6),
+    "svc_hip_dct_pack_layers_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 5 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp,
+                                                _vp]),
+    "svc_hip_decode_layers_workspace_bytes": (_u64, [_u32] * 5),
+    "svc_hip_decode_layers_frames": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     # the wire stream's decoder (csrc/records.hip) and its reading of a whole stream
     "svc_hip_decode_records_frames": (C.c_int, [_vp, _u64] + [_u32] * 7 + [_vp, _vp, _vp, _u32, _u32, _vp]),
     "svc_hip_wire_layout": (C.c_int, [C.POINTER(WireHeader), _u64, C.POINTER(_u32), C.POINTER(_u64)]),
@@ -1005,6 +1011,85 @@ def decode_entropy_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h
                                                 _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
                                                 None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
                                                 _dev(status, torch.int32), _stream()))
+    return rec, out_display, status
+
+
+# ---- two layers (include/svc_hip.h, "Two layers"; host statement: layers.py) ----
+
+def _rects(rects, n: int, dev) -> Optional[torch.Tensor]:
+    """None, or per frame x, y, w, h ((frames, 4) ints, a tensor or a list) -> (frames, 4) i32 on the device."""
+    if rects is None:
+        return None
+    return torch.as_tensor(rects, dtype=torch.int32).reshape(n, 4).to(dev).contiguous()
+
+
+def dct_pack_layers_workspace_bytes(n: int, w: int, h: int, block: int, mv_block) -> int:
+    """Scratch of dct_pack_layers_frames; 0 for a geometry it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_layers_workspace_bytes(n, w, h, block, mbw, mbh))
+
+
+def dct_pack_layers_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, fg_step: int, bg_step: int,
+                           enh_step: int, window=None, base_out: Optional[torch.Tensor] = None,
+                           enh_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
+                           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """B,G,R frames (frames, H, W, 3) u8 + region ids -> the base stream of dct_pack_levels_frames at (fg_step, bg_step) and the
+    enhancement stream that lifts the tiles whose origin is inside the frame's window to enh_step (include/svc_hip.h), from one
+    transform.  window: None (every tile), or per frame x, y, w, h in padded coordinates.  -> (base u8, base offsets (frames + 1,)
+    i64, enhancement u8, enhancement offsets), each stream of the worst-case size, on the device."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    dev = bgr.device
+    cap = max(levels_max_bytes(n, w, h, block, mv_block), 16)
+    if base_out is None:
+        base_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if enh_out is None:
+        enh_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_layers_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    base_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    enh_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    win = _rects(window, n, dev)
+    _check(load().svc_hip_dct_pack_layers_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block, _dev(block_types, torch.int32),
+                                                 mbw, mbh, fg_step, bg_step, enh_step, None if win is None else _dev(win, torch.int32),
+                                                 _dev(workspace, torch.uint8), workspace.numel(), _dev(base_out, torch.uint8),
+                                                 base_out.numel(), _dev(base_offsets, torch.int64), _dev(enh_out, torch.uint8),
+                                                 enh_out.numel(), _dev(enh_offsets, torch.int64), _stream()))
+    return base_out, base_offsets, enh_out, enh_offsets
+
+
+def decode_layers_workspace_bytes(n: int, w: int, h: int, block) -> int:
+    bw, bh = _bwbh(block)
+    return int(load().svc_hip_decode_layers_workspace_bytes(n, w, h, bw, bh))
+
+
+def decode_layers_frames(base: torch.Tensor, base_offsets: torch.Tensor, enh: Optional[torch.Tensor],
+                         enh_offsets: Optional[torch.Tensor], w: int, h: int, block, mv_block, fg_step: int = 1, bg_step: int = 640,
+                         gaze=None, display: Optional[Tuple[int, int]] = None, rec: Optional[torch.Tensor] = None,
+                         out_display: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
+                         ) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """decode_levels_frames on a base and an enhancement stream: inside the gaze a tile decodes at the enhancement's step, elsewhere
+    as decode_levels_frames decodes the base.  enh / enh_offsets may be None when gaze is None (the enhancement is then not read).
+    status (frames,) i32: the base frame's code, else 0x100 | the enhancement frame's, else 0x100 | 11 (not this base's layer)."""
+    n = base_offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = base.device
+    if rec is None:
+        rec = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    dw, dh = display if display is not None else (0, 0)
+    if display is not None and out_display is None:
+        out_display = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(decode_layers_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=dev)
+    g = _rects(gaze, n, dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_decode_layers_frames(_dev(base, torch.uint8), base.numel(), _dev(base_offsets, torch.int64),
+                                               None if enh is None else _dev(enh, torch.uint8), 0 if enh is None else enh.numel(),
+                                               None if enh_offsets is None else _dev(enh_offsets, torch.int64), n, w, h, bw, bh,
+                                               mbw, mbh, fg_step, bg_step, None if g is None else _dev(g, torch.int32),
+                                               _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
+                                               None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
+                                               _dev(status, torch.int32), _stream()))
     return rec, out_display, status
 
 

@@ -17,6 +17,12 @@
   python tools/dct_pack_probe.py budget_step [C3|C5] [frames]
                                                    svc::ClipEncoder with compact: the step at the fixed steps against the step under that
                                                    budget (SetCompactBudget), serial and pipelined; wall time per step
+  python tools/dct_pack_probe.py layers [C3|C5]    two layers, the same batch of 16: (a) svc_hip_dct_pack_layers_frames at (1, 640, 1) and
+                                                   (16, 16, 1) against svc_hip_dct_pack_levels_frames twice (base pair, then fine pair);
+                                                   (b) svc_hip_decode_layers_frames against svc_hip_decode_levels_frames on the fine stream,
+                                                   gaze 64 x 64 and the whole frame; (c) bytes per frame of the base, the enhancement (window
+                                                   256 x 256, and none) and the single stream at (1, 1), raw and entropy-coded.  Wall time
+                                                   per call over back-to-back calls, as `step`; the outputs are compared
 """
 import os
 import sys
@@ -151,6 +157,76 @@ def _per_step(fn, sync, warm=2, reps=3, steps=4):
     return min(ts), max(ts)
 
 
+def layers(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    base, fine, lbase, lenh = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(4))
+    offs_b, offs_f = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    ws1 = torch.empty(native.dct_pack_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws2 = torch.empty(native.dct_pack_layers_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    sync = torch.cuda.synchronize
+
+    def one(fg, bg, out, offs):
+        return native.dct_pack_levels_frames(bgr, block, types, mv, fg, bg, out=out, offsets=offs, workspace=ws1)
+
+    def two(fg, bg, enh, window=None):
+        return native.dct_pack_layers_frames(bgr, block, types, mv, fg, bg, enh, window=window, base_out=lbase, enh_out=lenh, workspace=ws2)
+
+    def fmt(t):
+        return f"{t[0]:.3f} .. {t[1]:.3f}"
+
+    print(f"{cfg.name} batch of {n}, ms per call (best .. worst of 3 runs of 4 back-to-back calls)", flush=True)
+    for fg, bg, enh in ((1, 640, 1), (16, 16, 1)):  # (a)
+        t_base = _per_step(lambda: one(fg, bg, base, offs_b), sync)
+        t_fine = _per_step(lambda: one(enh, enh, fine, offs_f), sync)
+        t_two = _per_step(lambda: two(fg, bg, enh), sync)
+        _, lo_b, _, _ = two(fg, bg, enh)
+        sync()
+        used = int(offs_b[-1])
+        assert torch.equal(lo_b, offs_b) and torch.equal(lbase[:used], base[:used]), "the base layer differs from the one-layer call's stream"
+        print(f"(a) encode ({fg}, {bg}, {enh}): one layer at ({fg}, {bg}) {fmt(t_base)} + at ({enh}, {enh}) {fmt(t_fine)} = "
+              f"{t_base[0] + t_fine[0]:.3f} .. {t_base[1] + t_fine[1]:.3f}; two layers {fmt(t_two)} "
+              f"({t_two[0] / (t_base[0] + t_fine[0]):.2f} of the sum); same base bytes", flush=True)
+
+    # (b), (c): the streams at (1, 640, 1)
+    one(1, 640, base, offs_b)
+    one(1, 1, fine, offs_f)
+    _, _, _, offs_e = two(1, 640, 1)
+    sync()
+    ub, uf, ue = int(offs_b[-1]), int(offs_f[-1]), int(offs_e[-1])
+    rec_f, rec_l = (torch.empty((n, ph, pw, 3), dtype=torch.float32, device=dev) for _ in range(2))
+    wsd1 = torch.empty(native.decode_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    wsd2 = torch.empty(native.decode_layers_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    small = native.gaze_rect(cfg.width // 2, cfg.height // 2, 64, 64, cfg.width, cfg.height, pw, ph)
+    for name, rect in (("64 x 64", small), ("the whole frame", (0, 0, pw, ph))):
+        gaze = torch.tensor([rect] * n, dtype=torch.int32, device=dev)
+        t_f = _per_step(lambda: native.decode_levels_frames(fine[:uf], offs_f, pw, ph, block, mv, 1, 640, gaze=gaze, rec=rec_f, workspace=wsd1), sync)
+        t_l = _per_step(lambda: native.decode_layers_frames(lbase[:ub], offs_b, lenh[:ue], offs_e, pw, ph, block, mv, 1, 640, gaze=gaze,
+                                                            rec=rec_l, workspace=wsd2), sync)
+        same = "" if rect[2] != pw else ("; same d_rec" if torch.equal(rec_f.view(torch.int32), rec_l.view(torch.int32)) else "; d_rec DIFFERS")
+        print(f"(b) decode, gaze {name} {tuple(rect)}: fine stream {fmt(t_f)}; two layers {fmt(t_l)} ({t_l[0] / t_f[0]:.2f}x){same}", flush=True)
+
+    def coded(stream, offs, used):
+        _, co, st = native.entropy_encode_frames(stream[:used], offs, pw, ph, block, mv)
+        sync()
+        assert not st.any()
+        return int(co[-1])
+
+    rows = [("base (1, 640)", ub, coded(base, offs_b, ub)), ("single stream (1, 1)", uf, coded(fine, offs_f, uf)),
+            ("enhancement, no window", ue, coded(lenh, offs_e, ue))]
+    wx, wy = (pw - 256) // 2 // 16 * 16, (ph - 256) // 2 // 16 * 16
+    _, _, _, offs_w = two(1, 640, 1, window=[(wx, wy, 256, 256)] * n)
+    sync()
+    uw = int(offs_w[-1])
+    rows.append((f"enhancement, window 256 x 256 at ({wx}, {wy})", uw, coded(lenh, offs_w, uw)))
+    for name, raw, ent in rows:
+        print(f"(c) {name}: {raw / n / 1e6:.3f} MB per frame raw, {ent / n / 1e6:.3f} MB entropy-coded", flush=True)
+
+
 def step(cfg, frames_n) -> None:
     dev = torch.device("cuda")
     clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=dev)
@@ -196,5 +272,7 @@ if __name__ == "__main__":
         budget_step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
     elif mode == "budget":
         budget(_cfg(sys.argv, 2))
+    elif mode == "layers":
+        layers(_cfg(sys.argv, 2))
     else:
         kernels(_cfg(sys.argv, 2), fused_only=mode == "fused")
