@@ -794,6 +794,57 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes,
                                  void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * A stored SVCQ stream restricted to a window per output frame, stream to stream: encode the
+ * every-tile enhancement once (d_window == NULL above), then serve any gaze without the pixels.
+ * scalable_video_codec_amd/layers.py (window_frame, window_frames) is the numpy statement.
+ *
+ * Output frame i is input frame s = d_src ? d_src[i] : i, restricted to the tiles whose origin
+ * d_window[i] contains (the containment rule of the gaze and of the encoder's window; w or h == 0
+ * holds nothing; d_window == NULL keeps every tile):
+ *   header   words 0 .. 9 and 11 copied, word 10 = the kept levels, word 12 = the output frame's
+ *            bytes = up16(levels offset + 2 * kept), words 13 .. 15 zero
+ *   types    copied
+ *   masks    a kept tile's words as they are, every other tile's words zero
+ *   levels   the kept tiles' int16 levels, in the input's order
+ *   padding  zero, to 16 bytes
+ * and d_out_offsets [n_out + 1] as the pack writes them; nothing is written past
+ * d_out_offsets[n_out].  The definition is on the masks, not on the levels' values: a set bit whose
+ * level is 0 stays set.  On the every-tile enhancement stream of svc_hip_dct_pack_layers_frames the
+ * result is byte for byte the enhancement stream that call writes with the same windows; on a base
+ * (or any other SVCQ) stream it is a region-of-interest stream.  The input may carry slack after
+ * its levels, as svc_hip_unpack_levels_frames accepts it; the output never does.
+ *
+ * d_status [n_out] u32: the code of svc_hip_unpack_levels_frames for the input frame (the level
+ * count and the stray-bit check cover the whole input frame, not only the kept tiles); 1 for
+ * d_src[i] >= n_in.  A frame that fails is 64 zero bytes, as the entropy encoder writes it, and
+ * leaves its neighbours as they would be.  Every read stays inside [d_frames, d_frames +
+ * stream_bytes).
+ *
+ * Geometry: whatever the SVCQ format takes (tiles up to 4096 coefficients, any MV block that is a
+ * multiple of the tile and divides the frame).  Checked in the order of the SVCQ entry points, for
+ * any frame counts and before any launch: geometry, limits (n_out and n_in <= 65535, the u32 frame
+ * size), d_src == NULL with n_out != n_in (SVC_ERR_INVALID_ARG), workspace, out_capacity against
+ * svc_hip_levels_max_bytes(n_out, ...); n_out == 0 then returns SVC_OK; then pointers (streams and
+ * workspace 16-byte aligned, offsets 8-byte, d_src, d_window and d_status 4-byte).  The query
+ * returns 0 where the call refuses.  d_out must not overlap the input stream: this is NOT checked.
+ * Two calls write the same bytes.  Only enqueues work.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_window_levels_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h,
+                                               uint32_t block_w, uint32_t block_h,
+                                               uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_window_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                 const uint64_t* d_frame_offsets, uint32_t n_in,
+                                 const uint32_t* d_src /* [n_out] index of the input frame; NULL = identity, then n_out must equal n_in */,
+                                 uint32_t n_out,
+                                 uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                 uint32_t mv_block_w, uint32_t mv_block_h,
+                                 const uint32_t* d_window /* [n_out][4] x, y, w, h (padded); NULL = every tile */,
+                                 uint8_t* d_workspace, uint64_t workspace_bytes,
+                                 uint8_t* d_out, uint64_t out_capacity,
+                                 uint64_t* d_out_offsets /* [n_out + 1] */,
+                                 uint32_t* d_status /* [n_out] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes
  * of svc_hip_serialize_frames / svc_hip_dct_records_frames and of the reference's encoder): the
  * reference's Decoder::operator() (libs/decoder.cpp:168-210) without the GUI.  Its records hold

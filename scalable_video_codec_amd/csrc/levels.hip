@@ -21,6 +21,9 @@
 //
 // decode of two layers (svc_hip_decode_layers_frames; include/svc_hip.h states them): the count and scan of each stream, a per-frame
 // merge of the two statuses, then the decode kernel's sibling, which inside the gaze adds the enhancement frame's residuals.
+//
+// window (svc_hip_window_levels_frames): a stored stream restricted to a window per output frame, without the pixels -- count, scan,
+// frame offsets, then one pass that writes every output frame in aligned 16-byte vectors (stated at its kernels).
 #include "budget_core.hpp"
 #include "display_core.hpp"
 #include "idct_core.hpp"
@@ -682,6 +685,260 @@ __global__ __launch_bounds__(256) void decode_layers_kernel(DecodeLayersArgs la)
   store_bgr_column<N>(a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3, g.w, out);
 }
 
+// ---- window: SVCQ frames restricted to the tiles of a window, stream to stream ---------------------------------------------------
+//
+// Output frame i = input frame s (d_src[i], or i) with the masks of the tiles outside window i cleared and their levels left out.  The
+// levels of a group's kept tiles (the window is a rectangle: adjacent tiles) are one run in the input and one in the output, so per
+// output frame
+//   count    one wave per group: its levels, its kept levels, its levels before the first kept tile, its stray bits
+//   scan     one workgroup per frame: D[group] = kept levels before the group, S[group] = the input index of its run's first level,
+//            the frame's status and size
+//   offsets  one workgroup: the frame offsets
+//   write    one thread per aligned 16 bytes of the output frame, whatever they hold.  Header, types and masks lie at the same byte
+//            offsets in both frames: an aligned 16-byte load, patched.  Eight levels inside one run are 4 (even input index) or 5 (odd:
+//            funnel-shifted by 16 bits) aligned dwords of the input; vectors that hold a section's or a run's edge, or the padding, are put
+//            together level by level.  Every output byte is stored once, by one thread: two calls write the same bytes.
+
+struct WinWs {
+  uint32_t *tot, *before, *stray;  // [n][groups]; `before` becomes S
+  uint32_t* kept;                  // [n][groups + 1]: becomes D, entry `groups` = the frame's kept levels
+  uint32_t *frame_bytes, *status;  // [n]
+};
+uint64_t win_ws_bytes(uint32_t n, uint32_t groups) {
+  return 3 * up16(4ull * n * groups) + up16(4ull * n * (groups + 1)) + 2 * up16(4ull * n);
+}
+WinWs carve_window(uint8_t* p, uint32_t n, uint32_t groups) {
+  WinWs s;
+  const uint64_t a = up16(4ull * n * groups), b = up16(4ull * n * (groups + 1)), c = up16(4ull * n);
+  s.tot = reinterpret_cast<uint32_t*>(p);
+  s.before = reinterpret_cast<uint32_t*>(p + a);
+  s.stray = reinterpret_cast<uint32_t*>(p + 2 * a);
+  s.kept = reinterpret_cast<uint32_t*>(p + 3 * a);
+  s.frame_bytes = reinterpret_cast<uint32_t*>(p + 3 * a + b);
+  s.status = reinterpret_cast<uint32_t*>(p + 3 * a + b + c);
+  return s;
+}
+
+struct WindowArgs {
+  Geom g;
+  const uint8_t* in;
+  uint64_t stream_bytes;
+  const uint64_t* offsets;  // [n_in + 1]
+  uint32_t n_in;
+  const uint32_t* src;      // [n_out] input frame of each output frame, or null: its own index
+  const uint32_t* window;   // [n_out][4] x, y, w, h in padded coordinates, or null: every tile is kept
+  uint8_t* out;
+  uint64_t* out_offsets;    // [n_out + 1]
+  uint32_t* d_status;       // [n_out]
+  WinWs ws;
+};
+
+// output frame i's input frame, checked as the unpack checks it before its masks (a frame index past the stream: kStRange)
+__device__ __forceinline__ uint32_t window_source(const WindowArgs& a, uint32_t i, uint64_t* off, const uint32_t** hdr) {
+  const uint32_t s = a.src ? a.src[i] : i;
+  if (s >= a.n_in) return kStRange;
+  return check_svcq<false>(a.g, a.in, a.stream_bytes, a.offsets, s, off, hdr);
+}
+
+__device__ __forceinline__ bool in_window(const uint32_t* window, uint32_t i, uint32_t ox, uint32_t oy) {
+  return !window || gazed(window, i, ox, oy);
+}
+
+__global__ __launch_bounds__(256) void window_count_kernel(WindowArgs a) {
+  const Geom& g = a.g;
+  const uint32_t lane = threadIdx.x & 63u, gi = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), i = blockIdx.y;
+  if (gi >= g.groups) return;  // (the whole wave)
+  const Group gr = group_of(g, gi);
+  uint64_t off = 0;
+  const uint32_t* hdr = nullptr;
+  uint32_t tot = 0, kept = 0, before = 0, stray = 0;  // a frame that fails its checks counts nothing: its masks are not read
+  if (window_source(a, i, &off, &hdr) == kStOk) {
+    const uint32_t* masks = reinterpret_cast<const uint32_t*>(a.in + off + g.masks_off) +
+                            2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+    const uint32_t jobs = gr.nt * g.words, area = g.bw * g.bh;
+    const uint32_t wx = a.window ? a.window[4ull * i] : 0u;
+    for (uint32_t j = lane; j < jobs; j += 64) {
+      const uint64_t m = load_mask(masks + 2 * j);
+      const uint32_t t = j / g.words, pc = (uint32_t)__popcll(m), ox = gr.x0 + t * g.bw;
+      const uint32_t valid = area - (j - t * g.words) * 64;
+      tot += pc;
+      if (in_window(a.window, i, ox, gr.y0)) kept += pc;
+      else if (ox < wx) before += pc;  // left of the window: ahead of the run, if this group has one
+      if (valid < 64) stray += (uint32_t)__popcll(m >> valid);
+    }
+  }
+  tot = wave_sum(tot);
+  kept = wave_sum(kept);
+  before = wave_sum(before);
+  stray = wave_sum(stray);
+  if (lane == 0) {
+    a.ws.tot[(size_t)i * g.groups + gi] = tot;
+    a.ws.kept[(size_t)i * (g.groups + 1) + gi] = kept;
+    a.ws.before[(size_t)i * g.groups + gi] = before;
+    a.ws.stray[(size_t)i * g.groups + gi] = stray;
+  }
+}
+
+__global__ __launch_bounds__(256) void window_scan_kernel(WindowArgs a) {
+  __shared__ uint32_t red[kThreads / 64];
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.x;
+  const uint32_t* tot = a.ws.tot + (size_t)i * g.groups;
+  const uint32_t* strays = a.ws.stray + (size_t)i * g.groups;
+  uint32_t* kept = a.ws.kept + (size_t)i * (g.groups + 1);
+  uint32_t* run = a.ws.before + (size_t)i * g.groups;
+  uint32_t carry_tot = 0, carry_kept = 0, stray = 0;
+  for (uint32_t base = 0; base < g.groups; base += kThreads) {
+    const uint32_t k = base + threadIdx.x;
+    const bool live = k < g.groups;
+    if (live) stray += strays[k];
+    uint32_t sum_tot, sum_kept;
+    const uint32_t ex_tot = block_exclusive_scan(live ? tot[k] : 0u, red, &sum_tot);
+    const uint32_t ex_kept = block_exclusive_scan(live ? kept[k] : 0u, red, &sum_kept);
+    if (live) {
+      run[k] += carry_tot + ex_tot;  // S: the levels before the group, then those of its tiles left of the window
+      kept[k] = carry_kept + ex_kept;
+    }
+    carry_tot += sum_tot;
+    carry_kept += sum_kept;
+  }
+  uint32_t stray_bits;
+  (void)block_exclusive_scan(stray, red, &stray_bits);
+  if (threadIdx.x == 0) {
+    kept[g.groups] = carry_kept;
+    uint64_t off = 0;
+    const uint32_t* hdr = nullptr;
+    uint32_t st = window_source(a, i, &off, &hdr);
+    if (st == kStOk && stray_bits != 0) st = kStStrayBits;
+    if (st == kStOk && hdr[kHLevels] != carry_tot) st = kStLevels;
+    a.ws.status[i] = st;
+    a.d_status[i] = st;
+    a.ws.frame_bytes[i] = st == kStOk ? (uint32_t)up16(g.levels_off + 2ull * carry_kept) : kHeaderBytes;
+  }
+}
+
+// one workgroup: offsets[0 .. n] from the frames' sizes
+__global__ __launch_bounds__(256) void window_offsets_kernel(const uint32_t* __restrict__ bytes, uint32_t n, uint64_t* __restrict__ offsets) {
+  __shared__ uint64_t red[kThreads / 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint64_t carry = 0;
+  for (uint32_t base = 0; base < n; base += kThreads) {
+    const uint32_t k = base + threadIdx.x;
+    uint64_t x = k < n ? bytes[k] : 0u;
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+      const uint64_t y = __shfl_up(x, off, 64);
+      if (lane >= off) x += y;
+    }
+    if (lane == 63) red[wave] = x;
+    __syncthreads();
+    uint64_t before = 0, sum = 0;
+    for (uint32_t w = 0; w < kThreads / 64; ++w) {
+      if (w < wave) before += red[w];
+      sum += red[w];
+    }
+    __syncthreads();
+    if (k < n) offsets[k + 1] = carry + before + x;
+    carry += sum;
+  }
+  if (threadIdx.x == 0) offsets[0] = 0;
+}
+
+// the run that holds kept level e: the last r in [lo, groups) with D[r] <= e (D[lo] <= e < D[groups])
+__device__ __forceinline__ uint32_t run_of(const uint32_t* __restrict__ D, uint32_t lo, uint32_t groups, uint32_t e) {
+  uint32_t hi = groups;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (D[mid] <= e) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// dword wb (< levels_off / 4) of output frame i, from the input frame's dword v at the same place
+__device__ __forceinline__ uint32_t window_word(const WindowArgs& a, uint32_t i, uint32_t wb, uint32_t v, uint32_t kept, uint32_t fbytes) {
+  const Geom& g = a.g;
+  if (wb < kHeaderWords) return wb == kHLevels ? kept : wb == kHBytes ? fbytes : wb >= kQReserved ? 0u : v;
+  const uint32_t mw = (uint32_t)(g.masks_off / 4);
+  if (wb < mw || !a.window) return v;
+  const uint32_t tile = (wb - mw) / (2 * g.words), row = tile / g.tiles_x;  // row = plane * tiles_y + tile row
+  return gazed(a.window, i, (tile - row * g.tiles_x) * g.bw, (row % g.tiles_y) * g.bh) ? v : 0u;
+}
+
+__global__ __launch_bounds__(256) void window_write_kernel(WindowArgs a) {
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.y, fbytes = a.ws.frame_bytes[i], nvec = fbytes / 16, stride = gridDim.x * kThreads;
+  uint4* dst = reinterpret_cast<uint4*>(a.out + a.out_offsets[i]);
+  uint32_t v = blockIdx.x * kThreads + threadIdx.x;
+  if (a.ws.status[i] != kStOk) {  // 64 zero bytes; the input frame is not read
+    for (; v < nvec; v += stride) dst[v] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  const uint8_t* frame = a.in + a.offsets[a.src ? a.src[i] : i];
+  const uint32_t* src32 = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t src_bytes = src32[kHBytes];
+  const uint32_t lw = (uint32_t)(g.levels_off / 4);  // the levels' first dword
+  const uint32_t* lv32 = src32 + lw;
+  const uint16_t* lv16 = reinterpret_cast<const uint16_t*>(lv32);
+  const uint32_t* D = a.ws.kept + (size_t)i * (g.groups + 1);
+  const uint32_t* S = a.ws.before + (size_t)i * g.groups;
+  const uint32_t kept = D[g.groups];
+  for (; v < nvec; v += stride) {
+    const uint32_t w0 = 4 * v;
+    uint32_t o[4];
+    if (w0 + 4 <= lw) {  // header, types, masks
+      const uint4 x = *reinterpret_cast<const uint4*>(frame + 16ull * v);
+      o[0] = window_word(a, i, w0, x.x, kept, fbytes);
+      o[1] = window_word(a, i, w0 + 1, x.y, kept, fbytes);
+      o[2] = window_word(a, i, w0 + 2, x.z, kept, fbytes);
+      o[3] = window_word(a, i, w0 + 3, x.w, kept, fbytes);
+    } else {
+      const uint32_t e0 = w0 >= lw ? 2 * (w0 - lw) : 0u;  // the vector's first level
+      uint32_t r = 0, rend = 0;                           // a run and its end: D[r] <= e < rend for the levels e taken from it
+      if (e0 < kept) {
+        r = run_of(D, 0, g.groups, e0);
+        rend = D[r + 1];
+      }
+      bool done = false;
+      if (w0 >= lw && e0 + 8 <= rend) {  // eight levels of one run
+        const uint32_t s = S[r] + (e0 - D[r]), q = s >> 1;
+        if (!(s & 1u)) {
+          o[0] = lv32[q]; o[1] = lv32[q + 1]; o[2] = lv32[q + 2]; o[3] = lv32[q + 3];
+          done = true;
+        } else if (g.levels_off + 4ull * (q + 5) <= src_bytes) {  // the fifth dword ends inside the input frame
+          const uint32_t x0 = lv32[q], x1 = lv32[q + 1], x2 = lv32[q + 2], x3 = lv32[q + 3], x4 = lv32[q + 4];
+          o[0] = (x0 >> 16) | (x1 << 16); o[1] = (x1 >> 16) | (x2 << 16); o[2] = (x2 >> 16) | (x3 << 16); o[3] = (x3 >> 16) | (x4 << 16);
+          done = true;
+        }
+      }
+      if (!done) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+          const uint32_t wb = w0 + k;
+          if (wb < lw) {
+            o[k] = window_word(a, i, wb, src32[wb], kept, fbytes);
+            continue;
+          }
+          uint32_t half[2];
+#pragma unroll
+          for (uint32_t b = 0; b < 2; ++b) {
+            const uint32_t e = 2 * (wb - lw) + b;
+            half[b] = 0;  // the padding
+            if (e < kept) {
+              if (e >= rend) {
+                r = run_of(D, r, g.groups, e);
+                rend = D[r + 1];
+              }
+              half[b] = lv16[S[r] + (e - D[r])];
+            }
+          }
+          o[k] = half[0] | (half[1] << 16);
+        }
+      }
+    }
+    dst[v] = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -987,6 +1244,53 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, con
   else hipLaunchKernelGGL(decode_layers_kernel<16>, grid, dim3(kThreads), 0, s, a);
   if ((rc = check_launch("decode_layers reconstruction")) || !display) return rc;
   return launch_display("decode_layers", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+}
+
+uint64_t svc_hip_window_levels_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                               uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("window_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("window_levels_workspace_bytes", n_out, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  return win_ws_bytes(n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups);
+}
+
+// Checked in the order of the SVCQ entry points, whatever the frame counts: geometry, limits, the d_src rule, workspace, output
+// capacity; n_out == 0 then returns SVC_OK; then pointers.
+int svc_hip_window_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_in,
+                                 const uint32_t* d_src, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                 uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, const uint32_t* d_window,
+                                 uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                 uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("window_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (!rc) rc = validate_limits("window_levels", std::max(n_out, n_in), frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(d_src || n_out == n_in, "window_levels: without d_src output frame i is input frame i, but n_out is %u and n_in %u", n_out,
+              n_in);
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  SVC_REQUIRE(workspace_bytes >= win_ws_bytes(n_out, g.groups), "window_levels: workspace of %llu B is smaller than the %llu B needed",
+              (unsigned long long)workspace_bytes, (unsigned long long)win_ws_bytes(n_out, g.groups));
+  const uint64_t max_bytes = frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
+  SVC_REQUIRE(out_capacity >= n_out * max_bytes, "window_levels: output of %llu B is below the batch's worst case of %llu B",
+              (unsigned long long)out_capacity, (unsigned long long)(n_out * max_bytes));
+  if (n_out == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_out && d_out_offsets && d_status, "window_levels: null pointer");
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_out_offsets, 8) && aligned(d_src, 4) && aligned(d_window, 4) && aligned(d_status, 4),
+              "window_levels: streams and workspace must be 16-byte aligned, offsets 8-byte, source indices, windows and status 4-byte");
+  const WindowArgs a{g, d_frames, stream_bytes, d_frame_offsets, n_in, d_src, d_window, d_out, d_out_offsets, d_status,
+                     carve_window(d_workspace, n_out, g.groups)};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(window_count_kernel, dim3(div_up(g.groups, kThreads / 64), n_out), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("window_levels", "count"))) return rc;
+  hipLaunchKernelGGL(window_scan_kernel, dim3(n_out), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("window_levels", "scan"))) return rc;
+  hipLaunchKernelGGL(window_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.frame_bytes, n_out, d_out_offsets);
+  if ((rc = check_launch("window_levels", "offsets"))) return rc;
+  // a workgroup's pass is 4 KB of an output frame; the grid holds twice the header, types and masks (a window's levels are fewer
+  // bytes than its frame's masks), and a frame that keeps more is walked in further passes
+  const uint32_t fixed = div_up((uint32_t)(up16(g.levels_off) / 16), kThreads), most = div_up((uint32_t)(max_bytes / 16), kThreads);
+  hipLaunchKernelGGL(window_write_kernel, dim3(std::min(2 * fixed, most), n_out), dim3(kThreads), 0, s, a);
+  return check_launch("window_levels", "write");
 }
 
 int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w, uint32_t frame_h, uint32_t padded_w,

@@ -7,7 +7,9 @@ For a tile of class c (background when the MV block holding its origin has type 
 steps divide).  Per coefficient, with Lb its level in the base frame and Lf its level at enh_step:
     d = Lf - Lb * ratio     inside the frame's window, 0 outside it
 and an enhancement frame is an SVCQ frame whose levels are d, with fg_step = bg_step = enh_step in its header.  Inside the gaze the
-decoder dequantises (Lb * ratio + d) * enh_step, elsewhere Lb * sb."""
+decoder dequantises (Lb * ratio + d) * enh_step, elsewhere Lb * sb.
+
+window_frame / window_frames state svc_hip_window_levels_frames: a stored frame restricted to the tiles of a window, on its masks."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple
@@ -46,6 +48,15 @@ def _levels_of(hdr: Dict[str, int], types: np.ndarray, planes: np.ndarray) -> Tu
     return lv, step
 
 
+def _assemble(head, inexact: int, types: np.ndarray, masks: np.ndarray, lv: np.ndarray) -> bytes:
+    """An SVCQ frame from its header words 0 .. 9, the region ids, the mask section's bytes and the levels in stream order: word 10 is
+    their number, word 12 the frame's bytes, the reserved words and the padding zero."""
+    body = np.ascontiguousarray(types, "<u4").tobytes() + np.ascontiguousarray(masks, np.uint8).tobytes() + np.asarray(lv).astype("<i2").tobytes()
+    size = (levels.HEADER_BYTES + len(body) + 15) // 16 * 16
+    words = np.array([int(v) for v in head[:10]] + [len(lv), inexact, size, 0, 0, 0], "<u4").tobytes()
+    return words + body + bytes(size - levels.HEADER_BYTES - len(body))
+
+
 def write_frame(hdr: Dict[str, int], types: np.ndarray, lv: np.ndarray, fg_step: int, bg_step: int) -> bytes:
     """An SVCQ frame of hdr's geometry with the region ids `types` and the integer levels lv (3, H, W), inexact 0."""
     w, h, bw, bh = hdr["frame_w"], hdr["frame_h"], hdr["block_w"], hdr["block_h"]
@@ -58,11 +69,8 @@ def write_frame(hdr: Dict[str, int], types: np.ndarray, lv: np.ndarray, fg_step:
     bits = np.zeros((3, ty, tx, nw * 64), bool)
     bits[..., :area] = nz
     masks = np.packbits(bits, axis=-1, bitorder="little")
-    body = np.ascontiguousarray(types, "<u4").tobytes() + masks.tobytes() + tiles[nz].astype("<i2").tobytes()
-    size = (levels.HEADER_BYTES + len(body) + 15) // 16 * 16
-    head = np.array([levels.MAGIC, levels.VERSION, w, h, bw, bh, hdr["mv_block_w"], hdr["mv_block_h"], fg_step, bg_step,
-                     int(nz.sum()), 0, size, 0, 0, 0], "<u4").tobytes()
-    return head + body + bytes(size - levels.HEADER_BYTES - len(body))
+    head = [levels.MAGIC, levels.VERSION, w, h, bw, bh, hdr["mv_block_w"], hdr["mv_block_h"], fg_step, bg_step]
+    return _assemble(head, 0, types, masks, tiles[nz])
 
 
 def _belongs(hb: Dict[str, int], he: Dict[str, int]) -> bool:
@@ -125,3 +133,57 @@ def merge_levels(base_frame, enh_frame, gaze: Optional[Sequence[int]] = None) ->
     gazed = _contains(gaze, ox, oy)
     merged = np.where(_per_pixel(hb, gazed)[None], lb * _per_pixel(hb, step // e)[None] + d, lb)
     return merged, np.where(gazed, e, step)
+
+
+# ---- a stored stream restricted to a window (include/svc_hip.h: svc_hip_window_levels_frames) -----------------------------------------
+
+def _window_frame(frame, window) -> Tuple[bytes, Dict[str, int]]:
+    b = np.frombuffer(frame, np.uint8) if not isinstance(frame, np.ndarray) else frame.reshape(-1).view(np.uint8)
+    hdr, types, _ = levels.parse_frame(b)  # raises for a frame the reader rejects: the masks and the level count below are sound
+    tx, ty = hdr["frame_w"] // hdr["block_w"], hdr["frame_h"] // hdr["block_h"]
+    nw = (hdr["block_w"] * hdr["block_h"] + 63) // 64
+    masks_off = levels.HEADER_BYTES + 4 * types.size
+    levels_off = masks_off + 8 * 3 * ty * tx * nw
+    masks = b[masks_off:levels_off].reshape(3, ty, tx, nw * 8)
+    lv = b[levels_off:levels_off + 2 * hdr["level_count"]].view("<i2")
+    keep = np.ones((ty, tx), bool)
+    if window is not None:
+        _, ox, oy = _tile_maps(hdr, types)
+        keep = _contains(window, ox, oy)
+    bits = np.unpackbits(masks, axis=-1, bitorder="little").astype(bool)  # the levels follow the set bits in this (C) order
+    kept_bits = bits & keep[None, :, :, None]
+    out_masks = np.where(keep[None, :, :, None], masks, 0)
+    return _assemble(b[:40].view("<u4"), hdr["inexact"], types, out_masks, lv[kept_bits[bits]]), hdr
+
+
+def window_frame(frame, window) -> bytes:
+    """One SVCQ frame restricted to the tiles whose origin the window (x, y, w, h in padded coordinates, or None: every tile) contains:
+    header words 0 .. 9 and 11 and the types as they are, a kept tile's mask words as they are and every other tile's zero, the kept
+    tiles' levels in the frame's order, word 10 their number, word 12 the new size, zero padding.  Stated on the masks, not on the levels'
+    values: a set bit whose level is 0 stays a set bit and keeps its level.  On enhancement_frame(base, fine, e, None) this gives
+    enhancement_frame(base, fine, e, window).  Raises ValueError for a frame levels.parse_frame rejects."""
+    return _window_frame(frame, window)[0]
+
+
+def window_frames(stream, offsets, windows, src=None) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_window_levels_frames writes for frames that pass their checks -> (bytes, offsets (n_out + 1,) u64): output frame i
+    is window_frame of input frame src[i] (src None: frame i) and windows[i]; windows: None (every tile of every frame) or per output
+    frame x, y, w, h (n_out, 4); src: indices into the input frames, repeats and any order allowed."""
+    b = np.frombuffer(stream, np.uint8) if not isinstance(stream, np.ndarray) else stream.reshape(-1).view(np.uint8)
+    offs = [int(o) for o in np.asarray(offsets).reshape(-1)]
+    n_in = len(offs) - 1
+    idx = list(range(n_in)) if src is None else [int(i) for i in np.asarray(src).reshape(-1)]
+    win = None if windows is None else np.asarray(windows).reshape(len(idx), 4)
+    frames = []
+    for i, f in enumerate(idx):
+        if not 0 <= f < n_in:
+            raise ValueError(f"output frame {i} names input frame {f} of {n_in}")
+        lo, hi = offs[f], offs[f + 1]
+        if lo % 16 or hi < lo or hi > b.size:
+            raise ValueError(f"SVCQ frame offsets out of order, misaligned or past the stream: {lo}, {hi}")
+        out, hdr = _window_frame(b[lo:hi], None if win is None else win[i])
+        if hdr["frame_bytes"] != hi - lo:
+            raise ValueError(f"SVCQ frame at {lo} has frame_bytes {hdr['frame_bytes']}, its offsets {hi - lo}")
+        frames.append(out)
+    out_offs = np.concatenate([[0], np.cumsum([len(fr) for fr in frames])]).astype(np.uint64)
+    return b"".join(frames), out_offs

@@ -151,6 +151,9 @@ SIGNATURES = {
                                                 _vp]),
     "svc_hip_decode_layers_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_decode_layers_frames": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
+    # a stored SVCQ stream restricted to a window per output frame (csrc/levels.hip; host statement: layers.window_frames)
+    "svc_hip_window_levels_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_window_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     # the wire stream's decoder (csrc/records.hip) and its reading of a whole stream
     "svc_hip_decode_records_frames": (C.c_int, [_vp, _u64] + [_u32] * 7 + [_vp, _vp, _vp, _u32, _u32, _vp]),
     "svc_hip_wire_layout": (C.c_int, [C.POINTER(WireHeader), _u64, C.POINTER(_u32), C.POINTER(_u64)]),
@@ -1091,6 +1094,44 @@ def decode_layers_frames(base: torch.Tensor, base_offsets: torch.Tensor, enh: Op
                                                None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
                                                _dev(status, torch.int32), _stream()))
     return rec, out_display, status
+
+
+def window_levels_workspace_bytes(n_out: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of window_levels_frames for n_out output frames; 0 for a geometry it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_window_levels_workspace_bytes(n_out, w, h, bw, bh, mbw, mbh))
+
+
+def window_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, window=None, src=None,
+                         out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """An SVCQ stream (u8 on the device) + its offsets, restricted to a window per output frame (include/svc_hip.h; the numpy statement is
+    layers.window_frames): output frame i is input frame src[i] (src None: frame i) with only the tiles whose origin window[i] contains.
+    window: None (every tile), or per output frame x, y, w, h in padded coordinates; src: None, or the input frame of each output frame
+    ((n_out,) ints, a tensor or a list; repeats and any order).  -> (stream u8 of the worst-case size, offsets (n_out + 1,) i64, status
+    (n_out,) i32 with unpack's codes for the input frame, 1 for an index past the input; a frame that fails is 64 zero bytes).  `out`
+    must not overlap `frames`."""
+    n_in = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    s = None if src is None else torch.as_tensor(src, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    n_out = n_in if s is None else s.numel()
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n_out, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(window_levels_workspace_bytes(n_out, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(max(n_out, 1), dtype=torch.int32, device=dev)[:n_out]
+    win = _rects(window, n_out, dev)
+    _check(load().svc_hip_window_levels_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n_in,
+                                               None if s is None else _dev(s, torch.int32), n_out, w, h, bw, bh, mbw, mbh,
+                                               None if win is None else _dev(win, torch.int32), _dev(workspace, torch.uint8),
+                                               workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
+                                               _dev(status, torch.int32), _stream()))
+    return out, out_offsets, status
 
 
 def gaze_rect(cx: int, cy: int, max_w: int, max_h: int, frame_w: int, frame_h: int, padded_w: int, padded_h: int

@@ -23,6 +23,11 @@
                                                    gaze 64 x 64 and the whole frame; (c) bytes per frame of the base, the enhancement (window
                                                    256 x 256, and none) and the single stream at (1, 1), raw and entropy-coded.  Wall time
                                                    per call over back-to-back calls, as `step`; the outputs are compared
+  python tools/dct_pack_probe.py window [C3|C5]    a stored enhancement served under a gaze, the same batch of 16 at (1, 640, 1) with a
+                                                   256 x 256 window per frame: svc_hip_window_levels_frames on the every-tile enhancement
+                                                   stream against svc_hip_dct_pack_layers_frames with those windows (the other way to these
+                                                   bytes), then 4 viewers (n_out = 64 from the 16 stored frames through d_src) against 4 such
+                                                   encodes; wall time per call over 20 back-to-back calls; the bytes are compared
 """
 import os
 import sys
@@ -227,6 +232,90 @@ def layers(cfg) -> None:
         print(f"(c) {name}: {raw / n / 1e6:.3f} MB per frame raw, {ent / n / 1e6:.3f} MB entropy-coded", flush=True)
 
 
+def window(cfg) -> None:
+    dev = torch.device("cuda")
+    n, viewers = 16, 4
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    lbase, whole, enc = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(3))
+    ws2 = torch.empty(native.dct_pack_layers_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    sync = torch.cuda.synchronize
+
+    def encode(out, win):
+        return native.dct_pack_layers_frames(bgr, block, types, mv, 1, 640, 1, window=win, base_out=lbase, enh_out=out, workspace=ws2)
+
+    def fmt(t):
+        return f"{t[0]:.3f} .. {t[1]:.3f}"
+
+    def rects(viewer):
+        """A 256 x 256 window per frame, on the MV grid, drifting with the frame and different for each viewer."""
+        out = []
+        for f in range(n):
+            x = (pw - 256) // 2 + 32 * ((f + 3 * viewer) % 7 - 3) + 64 * (viewer - 1)
+            y = (ph - 256) // 2 + 16 * ((f + viewer) % 5 - 2)
+            out.append((x // 16 * 16, y // 16 * 16, 256, 256))
+        return out
+
+    _, _, _, offs_e = encode(whole, None)
+    sync()
+    offs_e = offs_e.clone()
+    ue = int(offs_e[-1])
+    stored = whole[:ue]
+    win = torch.tensor(rects(0), dtype=torch.int32, device=dev)
+    out1 = torch.empty(cap, dtype=torch.uint8, device=dev)
+    ws1 = torch.empty(native.window_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    st1 = torch.empty(n, dtype=torch.int32, device=dev)
+    oo1 = torch.empty(n + 1, dtype=torch.int64, device=dev)
+
+    def serve():
+        return native.window_levels_frames(stored, offs_e, pw, ph, block, mv, window=win, out=out1, out_offsets=oo1, workspace=ws1, status=st1)
+
+    print(f"{cfg.name} batch of {n}, enhancement at (1, 640, 1), ms per call (best .. worst of 3 runs of 20 back-to-back calls)", flush=True)
+    t_enc = _per_step(lambda: encode(enc, win), sync, steps=20)
+    t_win = _per_step(serve, sync, steps=20)
+    t_enc2 = _per_step(lambda: encode(enc, win), sync, steps=20)  # the encode again, after: the spread of the same call in this run
+    _, _, _, offs_w = encode(enc, win)
+    serve()
+    sync()
+    uw = int(offs_w[-1])
+    assert not st1.any() and torch.equal(oo1, offs_w) and torch.equal(out1[:uw], enc[:uw]), "the windowed stream differs from the encoder's"
+    print(f"(a) one viewer, 256 x 256 per frame: encode with the window {fmt(t_enc)} (again {fmt(t_enc2)}); window the stored stream "
+          f"{fmt(t_win)} ({t_win[0] / min(t_enc[0], t_enc2[0]):.3f} of the encode); same bytes; stored {ue / n / 1e6:.3f} MB per frame, "
+          f"served {uw / n / 1e6:.3f} MB per frame, workspace {ws1.numel() / n / 1e6:.3f} MB per frame", flush=True)
+
+    # 4 viewers of the same 16 stored frames
+    n_out = viewers * n
+    src = torch.tensor([f for _ in range(viewers) for f in range(n)], dtype=torch.int32, device=dev)
+    win4 = torch.tensor([r for v in range(viewers) for r in rects(v)], dtype=torch.int32, device=dev)
+    out4 = torch.empty(native.levels_max_bytes(n_out, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws4 = torch.empty(native.window_levels_workspace_bytes(n_out, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    st4 = torch.empty(n_out, dtype=torch.int32, device=dev)
+    oo4 = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+
+    def serve4():
+        return native.window_levels_frames(stored, offs_e, pw, ph, block, mv, window=win4, src=src, out=out4, out_offsets=oo4, workspace=ws4,
+                                           status=st4)
+
+    def encode4():
+        for v in range(viewers):
+            encode(enc, win4[v * n:(v + 1) * n])
+
+    t_enc4 = _per_step(encode4, sync, steps=20)
+    t_win4 = _per_step(serve4, sync, steps=20)
+    serve4()
+    sync()
+    assert not st4.any()
+    for v in range(viewers):
+        _, _, _, offs_v = encode(enc, win4[v * n:(v + 1) * n])
+        sync()
+        lo, hi = int(oo4[v * n]), int(oo4[(v + 1) * n])
+        assert torch.equal(oo4[v * n:(v + 1) * n + 1] - lo, offs_v) and torch.equal(out4[lo:hi], enc[:hi - lo]), f"viewer {v} differs"
+    print(f"(b) {viewers} viewers, n_out = {n_out} through d_src: {viewers} encodes {fmt(t_enc4)}; one window call {fmt(t_win4)} "
+          f"({t_win4[0] / t_enc4[0]:.3f} of the encodes); same bytes; served {int(oo4[-1]) / n_out / 1e6:.3f} MB per frame", flush=True)
+
+
 def step(cfg, frames_n) -> None:
     dev = torch.device("cuda")
     clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=dev)
@@ -274,5 +363,7 @@ if __name__ == "__main__":
         budget(_cfg(sys.argv, 2))
     elif mode == "layers":
         layers(_cfg(sys.argv, 2))
+    elif mode == "window":
+        window(_cfg(sys.argv, 2))
     else:
         kernels(_cfg(sys.argv, 2), fused_only=mode == "fused")
