@@ -45,15 +45,28 @@ __global__ __launch_bounds__(256) void display_kernel(const float* __restrict__ 
   }
 }
 
-// a decoder's display size: 0 x 0 = no display pass, else within the padded frame (the pass only shrinks)
-inline int validate_display(const char* what, uint32_t dw, uint32_t dh, uint32_t w, uint32_t h) {
-  SVC_REQUIRE((dw == 0 && dh == 0) || (dw >= 1 && dw <= w && dh >= 1 && dh <= h),
-              "%s: display %ux%u must lie within 1x1 .. %ux%u (the padded frame)", what, dw, dh, w, h);
+// The checks and the closing that every decoder with a display pass shares, each with the entry point's name in its message.
+// A decoder's steps, then its display size: 0 x 0 = no display pass (*display = false), else within the padded frame (the pass only
+// shrinks).
+inline int validate_steps_display(const char* what, uint32_t fg_step, uint32_t bg_step, uint32_t dw, uint32_t dh, uint32_t w, uint32_t h,
+                                  bool* display) {
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "%s: quant steps must be positive (libs/decoder.cpp:35-47)", what);
+  *display = dw != 0 || dh != 0;
+  SVC_REQUIRE(!*display || (dw >= 1 && dw <= w && dh >= 1 && dh <= h), "%s: display %ux%u must lie within 1x1 .. %ux%u (the padded frame)",
+              what, dw, dh, w, h);
   return SVC_OK;
 }
 
-inline int launch_display(const char* what, const float* d_rec, uint8_t* d_display, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t dw,
-                          uint32_t dh, hipStream_t s) {
+inline int validate_display_buffer(const char* what, bool display, const uint8_t* d_display) {
+  SVC_REQUIRE(display == (d_display != nullptr), "%s: a display buffer goes with a display size, and only with one", what);
+  return SVC_OK;
+}
+
+// after the launch of a decoder's last pass before the picture: its check, then the display pass if there is one
+inline int finish_with_display(const char* what, const char* pass, bool display, const float* d_rec, uint8_t* d_display, uint32_t n_frames,
+                               uint32_t w, uint32_t h, uint32_t dw, uint32_t dh, hipStream_t s) {
+  const int rc = check_launch(what, pass);
+  if (rc || !display) return rc;
   hipLaunchKernelGGL(display_kernel, dim3(div_up(dw, kDisplayThreads), dh, n_frames), dim3(kDisplayThreads), 0, s, d_rec, d_display, w, h,
                      dw, dh);
   return check_launch(what, "display");

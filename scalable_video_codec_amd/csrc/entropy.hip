@@ -837,7 +837,7 @@ __global__ __launch_bounds__(256) void dec_frame_kernel(DecArgs a) {
 
 // ---- fused decode: SVCE frames straight to the decoder's reconstruction ---------------------------------------------------------
 //
-// The encoder's chunk (g.ct tiles) is the group of tiles one workgroup of levels.hip's decode_levels_kernel reconstructs, so a
+// The encoder's chunk (g.ct tiles) is the group of tiles one workgroup of levels.hip's decode_body reconstructs, so a
 // workgroup decodes the chunks that cover its group (one per plane in the encoder's layout) into dense int16 coefficients in LDS and
 // inverts them from there: the SVCQ masks and levels never exist.  Any other chunk_tiles is honoured: a chunk that overlaps the group
 // is walked from its first tile to the group's last one, and the group that holds a chunk's last tile walks it to its end and makes
@@ -941,11 +941,12 @@ __device__ __forceinline__ bool walk_raw(const uint8_t* s, uint32_t size, uint32
   return !to_end || got == count;
 }
 
-// One workgroup per (tile row, group in the row) of a frame, the grid of decode_levels_kernel<N>.  Walk: per plane and per chunk that
+// One workgroup per (tile row, group in the row) of a frame, the grid of levels.hip's decode_body<N>.  Walk: per plane and per chunk that
 // overlaps the group one lane (walker w = lane * 4 + wave: the encoder's three sit in three waves); the first kStageSlots walkers read
-// their payload from LDS, staged by all threads with coalesced loads, a payload above a slot is read in place.  Then the arithmetic of
-// decode_levels_kernel in its order from the dense coefficients, so d_rec has the bits of the two calls.  The payload stage and the
-// f64 row slab are never live together and share their bytes.
+// their payload from LDS, staged by all threads with coalesced loads, a payload above a slot is read in place.  Then thread (t, j)
+// dequantises row j of tile t from the dense coefficients and takes it through the row and column passes as idct_core.hpp states
+// them, so d_rec has the bits of the two calls.  The payload stage and the f64 row slab are never live together and share their bytes.
+// (The passes are written out here: with invert_row / invert_column the 8x8 kernel measured 2.6 % slower, profiles/decode_body_refactor.txt.)
 template <int N>
 __global__ __launch_bounds__(256) void decode_entropy_kernel(FusedArgs a) {
   constexpr uint32_t kRows = kChunkCoeffs / N;
@@ -953,7 +954,7 @@ __global__ __launch_bounds__(256) void decode_entropy_kernel(FusedArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[kCoefBytes + (kRowBytes > kStageBytes ? kRowBytes : kStageBytes)];
   int16_t* coef = reinterpret_cast<int16_t*>(smem);
   uint32_t* stage = reinterpret_cast<uint32_t*>(smem + kCoefBytes);
-  double* rows = reinterpret_cast<double*>(smem + kCoefBytes);  // pitch N + 1, as decode_levels_kernel
+  double* rows = reinterpret_cast<double*>(smem + kCoefBytes);  // pitch N + 1, the slab of idct_core.hpp's passes
   const Geom& g = a.g;
   const uint32_t f = blockIdx.y, tid = threadIdx.x;
   if (a.ws.status[f] != kStOk) return;  // the finish kernel zeroes the frame
@@ -1188,9 +1189,8 @@ int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
                                   uint32_t* d_status, void* stream) {
   int rc = validate_decode_geom("decode_entropy", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
-  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_entropy: quant steps must be positive (libs/decoder.cpp:35-47)");
-  const bool display = display_w != 0 || display_h != 0;
-  if ((rc = validate_display("decode_entropy", display_w, display_h, frame_w, frame_h))) return rc;
+  bool display;
+  if ((rc = validate_steps_display("decode_entropy", fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   if ((rc = validate_fused("decode_entropy", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   const uint64_t need = n_frames ? dec_ws_bytes(n_frames, g) : 0;
@@ -1198,7 +1198,7 @@ int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
               (unsigned long long)workspace_bytes, (unsigned long long)need);
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_svce && d_offsets && d_workspace && d_rec && d_status, "decode_entropy: null pointer");
-  SVC_REQUIRE(display == (d_display != nullptr), "decode_entropy: a display buffer goes with a display size, and only with one");
+  if ((rc = validate_display_buffer("decode_entropy", display, d_display))) return rc;
   SVC_REQUIRE(aligned(d_svce, 16) && aligned(d_workspace, 16) && aligned(d_offsets, 8) && aligned(d_rec, 4) && aligned(d_status, 4) &&
                   aligned(d_gaze, 4),
               "decode_entropy: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
@@ -1214,8 +1214,7 @@ int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
   else hipLaunchKernelGGL(decode_entropy_kernel<16>, grid, dim3(kThreads), 0, s, a);
   if ((rc = check_launch("decode_entropy reconstruction"))) return rc;
   hipLaunchKernelGGL(decode_entropy_finish_kernel, dim3(32, n_frames), dim3(kThreads), 0, s, a);
-  if ((rc = check_launch("decode_entropy finish")) || !display) return rc;
-  return launch_display("decode_entropy", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+  return finish_with_display("decode_entropy", "finish", display, d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 }  // extern "C"

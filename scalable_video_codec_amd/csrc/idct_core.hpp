@@ -1,7 +1,8 @@
 // idct_core.hpp -- the decoder's per-coefficient arithmetic, shared by every kernel that reconstructs tiles (idct.hip from f32
-// planes, levels.hip straight from the compact stream, records.hip from the wire records): the f64 inverse DCT basis, the 1-D
-// inverse transform and the quantise-round-dequantise of DecodeBlock; and the edges the two stream decoders share, the gaze test
-// of a tile and the store of a thread's pixel column.  One definition, so that all paths produce the same bits.
+// planes, levels.hip straight from the compact stream, entropy.hip from the entropy-coded one, records.hip from the wire records):
+// the f64 inverse DCT basis, the 1-D inverse transform and the quantise-round-dequantise of DecodeBlock; and what the stream
+// decoders share, the gaze test of a tile, the row and column passes of a tile plane and the store of a thread's pixel column.
+// One definition, so that all paths produce the same bits.
 #pragma once
 
 #include "svc_common.hpp"
@@ -42,6 +43,34 @@ __device__ __forceinline__ float requant(float c, float step) {  // libs/decoder
   float q = c / step;
   q = roundf(q);
   return q * step;
+}
+
+// The reconstruction of one plane of a tile in the stream decoders.  Thread (t, j) of a workgroup owns row j and then column j of
+// the workgroup's tile t; `slab` is the workgroup's f64 LDS slab, one row per (tile, coefficient row) at pitch N + 1 (the column
+// reads of a wave then spread over the banks).  invert_row: the tile's dequantised coefficient row `coef` is requantised with the
+// decoder's step, inverted and written to the slab.  After a workgroup barrier, invert_column: column j is read back, inverted and
+// rounded once to f32.  A second barrier before the slab is written again.  Rows and columns go through idct1d exactly as in
+// idct_kernel, so a plane has the bits of svc_hip_decode_frames on the same coefficients.
+// (decode_entropy_kernel keeps this text written out: entropy.hip says why.)
+template <int N>
+__device__ __forceinline__ void invert_row(const float* coef, float step, double* slab, uint32_t t, uint32_t j) {
+  double y[N], r[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) y[i] = (double)requant(coef[i], step);
+  idct1d<N>(y, r);
+  double* row = slab + (t * N + j) * (N + 1);
+#pragma unroll
+  for (int i = 0; i < N; ++i) row[i] = r[i];
+}
+
+template <int N>
+__device__ __forceinline__ void invert_column(const double* slab, uint32_t t, uint32_t j, float (&out)[N]) {
+  double cc[N], xx[N];
+#pragma unroll
+  for (int v = 0; v < N; ++v) cc[v] = slab[(t * N + v) * (N + 1) + j];
+  idct1d<N>(cc, xx);
+#pragma unroll
+  for (int y = 0; y < N; ++y) out[y] = (float)xx[y];
 }
 
 // is the tile at (tx, ty) inside frame f's gaze rectangle?  gaze = [n][4] x, y, w, h in padded coordinates, or null (no gaze):

@@ -20,7 +20,8 @@
 // resize, to u8).
 //
 // decode of two layers (svc_hip_decode_layers_frames; include/svc_hip.h states them): the count and scan of each stream, a per-frame
-// merge of the two statuses, then the decode kernel's sibling, which inside the gaze adds the enhancement frame's residuals.
+// merge of the two statuses, then the same reconstruction with its enhancement compiled in, which inside the gaze adds the enhancement
+// frame's residuals.
 //
 // window (svc_hip_window_levels_frames): a stored stream restricted to a window per output frame, without the pixels -- count, scan,
 // frame offsets, then one pass that writes every output frame in aligned 16-byte vectors (stated at its kernels).
@@ -31,6 +32,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace svc {
 namespace {
@@ -478,7 +480,7 @@ __global__ __launch_bounds__(256) void unpack_kernel(UnpackArgs a) {
   }
 }
 
-// ---- decode ------------------------------------------------------------------------------------------------------------------
+// ---- decode: one stream, or a base stream and its enhancement -------------------------------------------------------------------
 
 struct DecodeArgs {
   Geom g;
@@ -489,79 +491,6 @@ struct DecodeArgs {
   Ws ws;
   float fg, bg;          // the decoder's steps
 };
-
-// One workgroup per (tile row, group in the row) of a frame: the same tiles in all three planes.  Thread (t, j) owns row j of the
-// group's tile t: it gathers that coefficient row by rank (the group's level prefix + the popcounts of the earlier mask words + the
-// set bits below it in its own word), dequantises with the encoder's step, requantises with the decoder's and inverts the row; the
-// same thread then inverts column j of tile t from LDS and, after the third plane, stores that column's interleaved B,G,R pixels.
-// Rows and columns go through idct1d exactly as in idct_kernel, so d_rec has the bits of unpack + svc_hip_decode_frames.
-template <int N>
-__global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
-  constexpr uint32_t kRows = kGroupCoeffs / N;  // coefficient rows of a group: tpg * N <= 2048 / N
-  __shared__ uint64_t job_mask[kMaxJobs];
-  __shared__ uint32_t job_base[kMaxJobs];
-  __shared__ uint32_t red[kThreads / 64];
-  __shared__ double rows[kRows * (N + 1)];  // pitch N + 1: the column reads of a wave spread over the banks
-  const Geom& g = a.g;
-  const uint32_t gi0 = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
-  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
-  const uint32_t st = a.ws.status[f];
-  const uint8_t* frame = a.in + a.offsets[f];  // dereferenced only for a frame that passed its checks
-  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
-  const uint32_t t = tid / N, j = tid - t * N;
-  const bool active = t < gr.nt;
-  float enc = 0.f, dec = 1.f;
-  if (st == kStOk && active) {
-    const uint32_t type = tile_type(g, reinterpret_cast<const uint32_t*>(frame + kHeaderBytes), gr, t);
-    const bool in_gaze = gazed(a.gaze, f, gr.x0 + t * N, gr.y0);  // ahead of the header's steps: in this order the code is the measured one
-    enc = (float)(type == 0 ? hdr[kHBgStep] : hdr[kHFgStep]);
-    dec = in_gaze ? 1.f : (type == 0 ? a.bg : a.fg);
-  }
-  const uint32_t jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
-  float out[3][N];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const uint32_t* masks = st != kStOk ? nullptr :
-        reinterpret_cast<const uint32_t*>(frame + g.masks_off) + 2 * ((((size_t)c * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
-    const uint64_t m = (masks && tid < jobs) ? load_mask(masks + 2 * tid) : 0ull;
-    uint32_t total;
-    const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
-    if (tid < jobs) { job_mask[tid] = m; job_base[tid] = ex; }
-    __syncthreads();
-    if (active) {
-      const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) +
-                              (st == kStOk ? a.ws.cnt[(size_t)f * g.groups + c * per_plane + gi0] : 0u);
-      double y[N], r[N];
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        const uint32_t k = j * N + i, w = t * g.words + (k >> 6), b = k & 63u;
-        const uint64_t mask = job_mask[w];  // 0 for a frame that failed: no level is read
-        float v = 0.f;
-        if ((mask >> b) & 1u) v = (float)levels[job_base[w] + (uint32_t)__popcll(mask & ((1ull << b) - 1))] * enc;
-        y[i] = (double)requant(v, dec);
-      }
-      idct1d<N>(y, r);
-      double* row = rows + (t * N + j) * (N + 1);
-#pragma unroll
-      for (int i = 0; i < N; ++i) row[i] = r[i];
-    }
-    __syncthreads();
-    if (active) {
-      double cc[N], xx[N];
-#pragma unroll
-      for (int v = 0; v < N; ++v) cc[v] = rows[(t * N + v) * (N + 1) + j];
-      idct1d<N>(cc, xx);
-#pragma unroll
-      for (int y = 0; y < N; ++y) out[c][y] = (float)xx[y];
-    }
-    __syncthreads();  // the next plane reuses rows and the job arrays
-  }
-  if (!active) return;
-  // a wave stores 64 adjacent pixels per row
-  store_bgr_column<N>(a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3, g.w, out);
-}
-
-// ---- decode of two layers ------------------------------------------------------------------------------------------------------
 
 struct DecodeLayersArgs {
   DecodeArgs base;              // in / offsets / ws: the base stream's; base.gaze is not null
@@ -588,45 +517,59 @@ __global__ __launch_bounds__(256) void layers_status_kernel(DecodeLayersArgs a, 
   d_status[f] = st;
 }
 
-// decode_levels_kernel<N> with the enhancement: the same workgroups, threads and arithmetic.  A workgroup whose group holds a gazed
-// tile also loads the enhancement frame's mask words of its jobs and scans them; a thread of a gazed tile gathers the residual d by
-// rank beside the base level Lb and decodes (Lb * ratio + d) at the enhancement's step, ratio = the tile's base step / that step.
-// Lb * ratio * enh_step == Lb * base step, so a gazed tile without residuals has the bits decode_levels_kernel gives it; every other
-// tile takes that kernel's path.
-template <int N>
-__global__ __launch_bounds__(256) void decode_layers_kernel(DecodeLayersArgs la) {
-  constexpr uint32_t kRows = kGroupCoeffs / N;
-  __shared__ uint64_t job_mask[kMaxJobs], enh_mask[kMaxJobs];
-  __shared__ uint32_t job_base[kMaxJobs], enh_base[kMaxJobs];
+__device__ __forceinline__ const DecodeArgs& base_of(const DecodeArgs& a) { return a; }
+__device__ __forceinline__ const DecodeArgs& base_of(const DecodeLayersArgs& a) { return a.base; }
+
+// The reconstruction of both decodes; decode_levels_kernel and decode_layers_kernel are its two forms.  One workgroup per (tile row,
+// group in the row) of a frame: the same tiles in all three planes.  Thread (t, j) owns row j of the group's tile t: it gathers that
+// coefficient row by rank (the group's level prefix + the popcounts of the earlier mask words + the set bits below it in its own word)
+// and dequantises it with the encoder's step; the row and column passes are idct_core.hpp's, with the decoder's step; after the third
+// plane the thread stores its column's interleaved B,G,R pixels.  d_rec has the bits of unpack + svc_hip_decode_frames.
+//
+// ENH, the enhancement (the status read is then the merged one: 0 = both frames may be read): a workgroup whose group holds a gazed
+// tile also loads the enhancement frame's mask words of its jobs and scans them, into the caller's enh_mask / enh_base; a thread of a
+// gazed tile gathers the residual d by rank beside the base level Lb and decodes (Lb * ratio + d) at the enhancement's step, ratio =
+// the tile's base step / that step.  Lb * ratio * enh_step == Lb * base step, so a gazed tile without residuals has the bits of the
+// form without ENH; every other tile takes that form's path.  Without ENH none of this is compiled, and the two arrays are null.
+//
+// (args by value: by reference the compiler spends more instructions on both forms, profiles/decode_body_refactor.txt)
+template <int N, bool ENH>
+__device__ __forceinline__ void decode_body(const std::conditional_t<ENH, DecodeLayersArgs, DecodeArgs> args, uint64_t* enh_mask,
+                                            uint32_t* enh_base) {
+  constexpr uint32_t kRows = kGroupCoeffs / N;  // coefficient rows of a group: tpg * N <= 2048 / N
+  __shared__ uint64_t job_mask[kMaxJobs];
+  __shared__ uint32_t job_base[kMaxJobs];
   __shared__ uint32_t red[kThreads / 64];
-  __shared__ double rows[kRows * (N + 1)];
-  const DecodeArgs& a = la.base;
+  __shared__ double rows[kRows * (N + 1)];  // pitch N + 1: the column reads of a wave spread over the banks
+  const DecodeArgs& a = base_of(args);
   const Geom& g = a.g;
   const uint32_t gi0 = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
-  const Group gr = group_of(g, gi0);
-  const uint32_t st = a.ws.status[f];  // the merged status: 0 = both frames may be read
-  const uint8_t* frame = a.in + a.offsets[f];
-  const uint8_t* eframe = la.enh + (st == kStOk ? la.enh_offsets[f] : 0);
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t st = a.ws.status[f];
+  const uint8_t* frame = a.in + a.offsets[f];  // dereferenced only for a frame that passed its checks
+  const uint8_t* eframe = nullptr;
+  if constexpr (ENH) eframe = args.enh + (st == kStOk ? args.enh_offsets[f] : 0);
   const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
   const uint32_t t = tid / N, j = tid - t * N;
   const bool active = t < gr.nt;
-  float enc = 0.f, dec = 1.f;
-  bool in_gaze = false;
+  float enc = 0.f, dec = 1.f, enh_step = 0.f;
+  bool enhanced = false;  // a gazed tile of the form with ENH
   uint32_t ratio = 0;
-  float enh_step = 0.f;
   if (st == kStOk && active) {
     const uint32_t type = tile_type(g, reinterpret_cast<const uint32_t*>(frame + kHeaderBytes), gr, t);
-    in_gaze = gazed(a.gaze, f, gr.x0 + t * N, gr.y0);
+    const bool in_gaze = gazed(a.gaze, f, gr.x0 + t * N, gr.y0);  // ahead of the header's steps: in this order the code is the measured one
     const uint32_t enc_step = type == 0 ? hdr[kHBgStep] : hdr[kHFgStep];
     enc = (float)enc_step;
     dec = in_gaze ? 1.f : (type == 0 ? a.bg : a.fg);
-    if (in_gaze) {
+    if (ENH && in_gaze) {
       const uint32_t e = reinterpret_cast<const uint32_t*>(eframe)[kHFgStep];
       ratio = enc_step / e;
       enh_step = (float)e;
+      enhanced = true;
     }
   }
-  const bool any_gazed = __syncthreads_or(in_gaze) != 0;  // the same in every thread: the barriers below depend on it
+  bool any_enhanced = false;  // the same in every thread: the barriers below depend on it
+  if constexpr (ENH) any_enhanced = __syncthreads_or(enhanced) != 0;
   const uint32_t jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
   float out[3][N];
 #pragma unroll
@@ -637,7 +580,7 @@ __global__ __launch_bounds__(256) void decode_layers_kernel(DecodeLayersArgs la)
     uint32_t total;
     const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
     if (tid < jobs) { job_mask[tid] = m; job_base[tid] = ex; }
-    if (any_gazed) {  // (then st == kStOk)
+    if (any_enhanced) {  // (then st == kStOk)
       const uint64_t me = tid < jobs ? load_mask(reinterpret_cast<const uint32_t*>(eframe + g.masks_off) + word0 + 2 * tid) : 0ull;
       const uint32_t exe = block_exclusive_scan((uint32_t)__popcll(me), red, &total);
       if (tid < jobs) { enh_mask[tid] = me; enh_base[tid] = exe; }
@@ -646,43 +589,46 @@ __global__ __launch_bounds__(256) void decode_layers_kernel(DecodeLayersArgs la)
     if (active) {
       const size_t gi = (size_t)f * g.groups + c * per_plane + gi0;
       const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) + (st == kStOk ? a.ws.cnt[gi] : 0u);
-      const int16_t* resid = reinterpret_cast<const int16_t*>(eframe + g.levels_off) + (in_gaze ? la.enh_ws.cnt[gi] : 0u);
-      double y[N], r[N];
+      const int16_t* resid = nullptr;
+      if constexpr (ENH) resid = reinterpret_cast<const int16_t*>(eframe + g.levels_off) + (enhanced ? args.enh_ws.cnt[gi] : 0u);
+      float v[N];
 #pragma unroll
       for (int i = 0; i < N; ++i) {
         const uint32_t k = j * N + i, w = t * g.words + (k >> 6), b = k & 63u;
-        const uint64_t mask = job_mask[w], below = (1ull << b) - 1;
-        float v = 0.f;
-        if (in_gaze) {
+        const uint64_t mask = job_mask[w], below = (1ull << b) - 1;  // mask: 0 for a frame that failed, no level is read
+        v[i] = 0.f;
+        if (enhanced) {
           const uint64_t emask = enh_mask[w];
           // unsigned: a stream that breaks the format's bound on a level wraps instead of overflowing
           uint32_t lv = 0;
           if ((mask >> b) & 1u) lv = (uint32_t)(int32_t)levels[job_base[w] + (uint32_t)__popcll(mask & below)] * ratio;
           if ((emask >> b) & 1u) lv += (uint32_t)(int32_t)resid[enh_base[w] + (uint32_t)__popcll(emask & below)];
-          v = (float)(int32_t)lv * enh_step;
+          v[i] = (float)(int32_t)lv * enh_step;
         } else if ((mask >> b) & 1u) {
-          v = (float)levels[job_base[w] + (uint32_t)__popcll(mask & below)] * enc;
+          v[i] = (float)levels[job_base[w] + (uint32_t)__popcll(mask & below)] * enc;
         }
-        y[i] = (double)requant(v, dec);
       }
-      idct1d<N>(y, r);
-      double* row = rows + (t * N + j) * (N + 1);
-#pragma unroll
-      for (int i = 0; i < N; ++i) row[i] = r[i];
+      invert_row<N>(v, dec, rows, t, j);
     }
     __syncthreads();
-    if (active) {
-      double cc[N], xx[N];
-#pragma unroll
-      for (int v = 0; v < N; ++v) cc[v] = rows[(t * N + v) * (N + 1) + j];
-      idct1d<N>(cc, xx);
-#pragma unroll
-      for (int y = 0; y < N; ++y) out[c][y] = (float)xx[y];
-    }
+    if (active) invert_column<N>(rows, t, j, out[c]);
     __syncthreads();  // the next plane reuses rows and the job arrays
   }
   if (!active) return;
+  // a wave stores 64 adjacent pixels per row
   store_bgr_column<N>(a.rec + (((size_t)f * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3, g.w, out);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void decode_levels_kernel(DecodeArgs a) {
+  decode_body<N, false>(a, nullptr, nullptr);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void decode_layers_kernel(DecodeLayersArgs a) {
+  __shared__ uint64_t enh_mask[kMaxJobs];
+  __shared__ uint32_t enh_base[kMaxJobs];
+  decode_body<N, true>(a, enh_mask, enh_base);
 }
 
 // ---- window: SVCQ frames restricted to the tiles of a window, stream to stream ---------------------------------------------------
@@ -1172,16 +1118,15 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                                  uint32_t* d_status, void* stream) {
   int rc = validate_decode_geom("decode_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
-  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_levels: quant steps must be positive (libs/decoder.cpp:35-47)");
-  const bool display = display_w != 0 || display_h != 0;
-  if ((rc = validate_display("decode_levels", display_w, display_h, frame_w, frame_h))) return rc;
+  bool display;
+  if ((rc = validate_steps_display("decode_levels", fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   if ((rc = validate_limits("decode_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "decode_levels: workspace of %llu B is smaller than the %llu B needed",
               (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_rec && d_status, "decode_levels: null pointer");
-  SVC_REQUIRE(display == (d_display != nullptr), "decode_levels: a display buffer goes with a display size, and only with one");
+  if ((rc = validate_display_buffer("decode_levels", display, d_display))) return rc;
   SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_rec, 4) &&
                   aligned(d_status, 4) && aligned(d_gaze, 4),
               "decode_levels: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
@@ -1193,8 +1138,7 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   const dim3 grid(g.tiles_y * g.gx, n_frames);
   if (block_w == 8) hipLaunchKernelGGL(decode_levels_kernel<8>, grid, dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(decode_levels_kernel<16>, grid, dim3(kThreads), 0, s, a);
-  if ((rc = check_launch("decode_levels reconstruction")) || !display) return rc;
-  return launch_display("decode_levels", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+  return finish_with_display("decode_levels", "reconstruction", display, d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 uint64_t svc_hip_decode_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
@@ -1213,9 +1157,8 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, con
                                  uint8_t* d_display, uint32_t display_w, uint32_t display_h, uint32_t* d_status, void* stream) {
   int rc = validate_decode_geom("decode_layers", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
-  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_layers: quant steps must be positive (libs/decoder.cpp:35-47)");
-  const bool display = display_w != 0 || display_h != 0;
-  if ((rc = validate_display("decode_layers", display_w, display_h, frame_w, frame_h))) return rc;
+  bool display;
+  if ((rc = validate_steps_display("decode_layers", fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   if ((rc = validate_limits("decode_layers", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   const uint64_t ws_stream = ws_bytes(n_frames, g.groups);
@@ -1227,7 +1170,7 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, con
                                         mv_block_h, fg_step, bg_step, nullptr, d_workspace, workspace_bytes, d_rec, d_display, display_w,
                                         display_h, d_status, stream);
   SVC_REQUIRE(d_base && d_base_offsets && d_enh && d_enh_offsets && d_workspace && d_rec && d_status, "decode_layers: null pointer");
-  SVC_REQUIRE(display == (d_display != nullptr), "decode_layers: a display buffer goes with a display size, and only with one");
+  if ((rc = validate_display_buffer("decode_layers", display, d_display))) return rc;
   SVC_REQUIRE(aligned(d_base, 16) && aligned(d_enh, 16) && aligned(d_workspace, 16) && aligned(d_base_offsets, 8) && aligned(d_enh_offsets, 8) &&
                   aligned(d_rec, 4) && aligned(d_status, 4) && aligned(d_gaze, 4),
               "decode_layers: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
@@ -1242,8 +1185,7 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, con
   const dim3 grid(g.tiles_y * g.gx, n_frames);
   if (block_w == 8) hipLaunchKernelGGL(decode_layers_kernel<8>, grid, dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(decode_layers_kernel<16>, grid, dim3(kThreads), 0, s, a);
-  if ((rc = check_launch("decode_layers reconstruction")) || !display) return rc;
-  return launch_display("decode_layers", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+  return finish_with_display("decode_layers", "reconstruction", display, d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 uint64_t svc_hip_window_levels_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,

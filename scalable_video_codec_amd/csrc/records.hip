@@ -8,9 +8,9 @@
 // Work split: a workgroup owns a STRETCH = up to kTiles adjacent tiles of one tile row of one frame (2048 coefficients per plane, the
 // group size of levels.hip).  A tile row is one contiguous byte range of records, so the stretch is too: it is staged into LDS with
 // coalesced dword loads (records are only 4-byte aligned: 772 B per 8x8 record, 3 076 B per 16x16), then thread (t, j) takes row j
-// of tile t's coefficients from LDS, requantises it with the tile's step and inverts it; the same thread inverts column j from LDS
-// and, after the third plane, stores that column's interleaved B,G,R pixels.  Rows and columns go through idct1d exactly as in
-// idct_kernel, so d_rec has the bits of parsing the records into planes + svc_hip_decode_frames with mv_block = block.
+// of tile t's coefficients from LDS through the row and column passes of idct_core.hpp with the tile's step and, after the third
+// plane, stores its column's interleaved B,G,R pixels.  d_rec has the bits of parsing the records into planes +
+// svc_hip_decode_frames with mv_block = block.
 #include "display_core.hpp"
 #include "idct_core.hpp"
 
@@ -41,7 +41,7 @@ template <int N>
 __global__ __launch_bounds__(RecGeom<N>::kThreads) void decode_records_kernel(RecordsArgs a) {
   using G = RecGeom<N>;
   __shared__ __attribute__((aligned(16))) uint32_t stage[G::kTiles * G::kRecDw];    // 24.1 KiB at 8x8, 24.0 KiB at 16x16
-  __shared__ __attribute__((aligned(16))) double rows[G::kTiles * N * (N + 1)];    // pitch N + 1, as decode_levels_kernel
+  __shared__ __attribute__((aligned(16))) double rows[G::kTiles * N * (N + 1)];    // the slab of idct_core.hpp's passes
   const uint32_t s = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
   const uint32_t ty = s / a.gx, t0 = (s - ty * a.gx) * G::kTiles;
   const uint32_t nt = min(G::kTiles, a.tiles_x - t0);
@@ -68,23 +68,10 @@ __global__ __launch_bounds__(RecGeom<N>::kThreads) void decode_records_kernel(Re
   for (int c = 0; c < 3; ++c) {
     if (active) {
       const float* coef = reinterpret_cast<const float*>(stage + t * G::kRecDw + 1 + c * N * N + j * N);
-      double y[N], r[N];
-#pragma unroll
-      for (int i = 0; i < N; ++i) y[i] = (double)requant(coef[i], dec);
-      idct1d<N>(y, r);
-      double* row = rows + (t * N + j) * (N + 1);
-#pragma unroll
-      for (int i = 0; i < N; ++i) row[i] = r[i];
+      invert_row<N>(coef, dec, rows, t, j);
     }
     __syncthreads();
-    if (active) {
-      double cc[N], xx[N];
-#pragma unroll
-      for (int v = 0; v < N; ++v) cc[v] = rows[(t * N + v) * (N + 1) + j];
-      idct1d<N>(cc, xx);
-#pragma unroll
-      for (int y = 0; y < N; ++y) out[c][y] = (float)xx[y];
-    }
+    if (active) invert_column<N>(rows, t, j, out[c]);
     __syncthreads();  // the next plane reuses rows
   }
   if (!active) return;
@@ -123,9 +110,8 @@ int svc_hip_decode_records_frames(const uint8_t* d_records, uint64_t records_str
                                   void* stream) {
   int rc = validate_records_geom(frame_w, frame_h, block, emit_frame_h);
   if (rc) return rc;
-  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "decode_records: quant steps must be positive (libs/decoder.cpp:35-47)");
-  const bool display = display_w != 0 || display_h != 0;
-  if ((rc = validate_display("decode_records", display_w, display_h, frame_w, frame_h))) return rc;
+  bool display;
+  if ((rc = validate_steps_display("decode_records", fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   const uint64_t per = svc_hip_serialized_frame_bytes(frame_w, emit_frame_h, block, block);
   SVC_REQUIRE(records_stride_bytes % 4 == 0 && records_stride_bytes >= per,
               "decode_records: records stride %llu must be a multiple of 4 and at least one frame's %llu B",
@@ -133,7 +119,7 @@ int svc_hip_decode_records_frames(const uint8_t* d_records, uint64_t records_str
   if (n_frames > 65535) return fail(SVC_ERR_UNSUPPORTED, "decode_records: more than 65535 frames in one call");
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_records && d_rec, "decode_records: null pointer");
-  SVC_REQUIRE(display == (d_display != nullptr), "decode_records: a display buffer goes with a display size, and only with one");
+  if ((rc = validate_display_buffer("decode_records", display, d_display))) return rc;
   SVC_REQUIRE(aligned(d_records, 4) && aligned(d_rec, 4) && aligned(d_gaze, 4), "decode_records: records, output and gaze must be 4-byte aligned");
   RecordsArgs a;
   a.records = d_records; a.stride = records_stride_bytes; a.gaze = d_gaze; a.rec = d_rec;
@@ -147,8 +133,7 @@ int svc_hip_decode_records_frames(const uint8_t* d_records, uint64_t records_str
     a.gx = div_up(a.tiles_x, RecGeom<16>::kTiles);
     hipLaunchKernelGGL(decode_records_kernel<16>, dim3(a.gx * (frame_h / 16), n_frames), dim3(RecGeom<16>::kThreads), 0, s, a);
   }
-  if ((rc = check_launch("decode_records reconstruction")) || !display) return rc;
-  return launch_display("decode_records", d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+  return finish_with_display("decode_records", "reconstruction", display, d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
 }
 
 int svc_hip_wire_layout(const svc_wire_header* hdr, uint64_t stream_bytes, uint32_t* emit_frame_h, uint64_t* frame_bytes) {
