@@ -845,6 +845,116 @@ int svc_hip_window_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                                  uint32_t* d_status /* [n_out] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * A stored fine SVCQ stream split into a base stream at any steps plus its enhancement stream,
+ * stream to stream: encode once at (fine_step, fine_step), then serve any multiple of it without
+ * the pixels.  scalable_video_codec_amd/layers.py (split_frame, split_frames,
+ * split_budget_frames) is the numpy statement.
+ *
+ * fine_step = e, base steps fg_step, bg_step with fg_step % e == 0 and bg_step % e == 0.  Input
+ * frame s = d_src ? d_src[i] : i must be an SVCQ frame whose header says fg_step == bg_step == e.
+ * For a tile of class c (background when the MV block holding its origin has type 0), sb = c's
+ * base step and r = sb / e.  Per coefficient, Lf = its level in the input frame (0 where the mask
+ * bit is clear):
+ *   Lb = sign(Lf) * ((2 * |Lf| + r) / (2 * r))   integer division: Lf / r rounded half away from
+ *                                                zero, std::round's rule
+ *   d  = Lf - Lb * r                             inside d_window[i] (the containment rule of the
+ *                                                gaze; NULL = every tile); 0 for a tile whose
+ *                                                origin the window does not contain
+ * Base frame i: header words 0 .. 7 and 11 of the input, words 8 and 9 = fg_step and bg_step,
+ * word 10 its level count, word 12 its bytes, words 13 .. 15 zero; types copied; masks (Lb != 0);
+ * levels = the non-zero Lb in stream order; zero padding to 16.  Enhancement frame i: the same
+ * with words 8 and 9 = e, masks (d != 0) and levels d -- the frame svc_hip_dct_pack_layers_frames
+ * defines.  Both are defined on the levels' VALUES (unlike the window call, which is defined on
+ * the masks): a set input bit whose level is 0 is a zero, so the outputs are always canonical.
+ * |Lb| <= |Lf| and |d| <= r / 2: nothing leaves int16 when max(fg_step, bg_step) / e <= 32766,
+ * the bound svc_hip_dct_pack_layers_frames applies.
+ *
+ * What follows from the definition:
+ *   1. Exact inside the gaze, for ANY ratio: Lb * r + d == Lf, so svc_hip_decode_layers_frames
+ *      on the two outputs gives, for a gazed tile inside the window, the bits of the fine stream
+ *      decoded under that gaze.
+ *   2. The encoder's bytes, for ODD ratios: when fg_step / e and bg_step / e are both odd, every
+ *      rounding boundary of coef / sb lies on a rounding boundary of coef / e, Lb is the level a
+ *      direct quantisation at sb gives, the base is byte for byte svc_hip_dct_pack_levels_frames
+ *      at (fg_step, bg_step) and the enhancement byte for byte what
+ *      svc_hip_dct_pack_layers_frames writes with the same windows.
+ *   3. NOT the encoder's bytes, for EVEN ratios: Lf = r / 2 (mod r) is a tie that the coefficient
+ *      itself would have resolved either way; the split always rounds it away from zero.  The
+ *      base then differs from a direct encode in some levels (on Gaussian coefficients about a
+ *      quarter of them at r = 2, 3 % at r = 16, 0.08 % at r = 640), and its reconstruction error
+ *      stays within sb / 2 + e / 2 instead of sb / 2.  Consequence 1 holds all the same.
+ *
+ * d_status [n_out] u32: the code of svc_hip_unpack_levels_frames for the whole input frame, as
+ * svc_hip_window_levels_frames reports it; 1 for d_src[i] >= n_in; 11 for a frame that passes
+ * those checks but whose header's fg_step or bg_step is not fine_step.  A frame that fails is 64
+ * zero bytes in both outputs and leaves its neighbours as they would be.  Every read stays inside
+ * [d_frames, d_frames + stream_bytes); the input may carry slack after its levels, the outputs
+ * never do; d_base_offsets and d_enh_offsets [n_out + 1] as the pack writes them, and nothing is
+ * written past offsets[n_out] of either output.  Two calls write the same bytes.  The outputs
+ * must not overlap the input stream: this is NOT checked.  With d_enh_out == NULL the enhancement
+ * is not made, and d_window, d_enh_offsets and enh_capacity are not used.
+ *
+ * Geometry: whatever the SVCQ format takes, as for the window call.  Checked in the order of the
+ * SVCQ entry points, for any frame counts and before any launch: geometry; steps (a step of 0,
+ * or a base step that is not a multiple of fine_step: SVC_ERR_INVALID_ARG; a ratio above 32766:
+ * SVC_ERR_UNSUPPORTED); limits (n_in, n_out <= 65535); d_src == NULL with n_out != n_in;
+ * workspace; base_capacity, then (with d_enh_out) enh_capacity, against
+ * svc_hip_levels_max_bytes(n_out, ...); n_out == 0 then returns SVC_OK; then pointers (streams
+ * and workspace 16-byte aligned, offsets 8-byte, the rest 4-byte).  The queries return 0 where
+ * the calls refuse.  Only enqueues work: the input frames' level offsets and status (two
+ * launches), then a count, a per-frame scan, the frame offsets and one write pass, each serving
+ * both layers.
+ *
+ * The budgeted call picks the base steps per output frame from a ladder (the rules of
+ * svc_hip_pack_levels_budget_frames; in addition every step a multiple of fine_step, and the
+ * ratio bound on the last entry) and d_budget [n_out] u32 bytes.  For output frame i and entry k,
+ * nz_k = the coefficients with 2 * |Lf| >= r_k(class), which is exactly Lb != 0 at entry k, and
+ * bytes_k = up16(levels offset + 2 * nz_k): the BASE frame's SVCQ bytes, like the two budgets
+ * above (not entropy-coded bytes, and not the enhancement's).  d_choice[i] = the smallest k with
+ * bytes_k <= d_budget[i], else ladder_len - 1 with bit 31 set; 0 for a frame whose status is not
+ * 0.  Frame i of both outputs is byte for byte the fixed call's frame with pair
+ * choice[i] & 0x7FFFFFFF.  One more count (per ladder entry) and a selection run before the
+ * fixed call's passes.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w,
+                                              uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                              uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_split_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                const uint64_t* d_frame_offsets, uint32_t n_in,
+                                const uint32_t* d_src /* [n_out] index of the input frame; NULL = identity, then n_out must equal n_in */,
+                                uint32_t n_out,
+                                uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                uint32_t mv_block_w, uint32_t mv_block_h,
+                                uint32_t fine_step, uint32_t fg_step, uint32_t bg_step,
+                                const uint32_t* d_window /* [n_out][4] x, y, w, h (padded); NULL = every tile */,
+                                uint8_t* d_workspace, uint64_t workspace_bytes,
+                                uint8_t* d_base_out, uint64_t base_capacity,
+                                uint64_t* d_base_offsets /* [n_out + 1] */,
+                                uint8_t* d_enh_out /* NULL: base only */, uint64_t enh_capacity,
+                                uint64_t* d_enh_offsets /* [n_out + 1]; NULL with d_enh_out */,
+                                uint32_t* d_status /* [n_out] */, void* stream);
+
+uint64_t svc_hip_split_levels_budget_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w,
+                                                     uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                                     uint32_t mv_block_w, uint32_t mv_block_h,
+                                                     uint32_t ladder_len);
+int svc_hip_split_levels_budget_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                       const uint64_t* d_frame_offsets, uint32_t n_in,
+                                       const uint32_t* d_src, uint32_t n_out,
+                                       uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                       uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fine_step,
+                                       const svc_step_pair* ladder /* host, ladder_len entries */, uint32_t ladder_len,
+                                       const uint32_t* d_budget /* [n_out] bytes */,
+                                       const uint32_t* d_window /* [n_out][4] or NULL */,
+                                       uint8_t* d_workspace, uint64_t workspace_bytes,
+                                       uint8_t* d_base_out, uint64_t base_capacity,
+                                       uint64_t* d_base_offsets /* [n_out + 1] */,
+                                       uint8_t* d_enh_out /* NULL: base only */, uint64_t enh_capacity,
+                                       uint64_t* d_enh_offsets /* [n_out + 1]; NULL with d_enh_out */,
+                                       uint32_t* d_choice /* [n_out] */, uint32_t* d_status /* [n_out] */,
+                                       void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes
  * of svc_hip_serialize_frames / svc_hip_dct_records_frames and of the reference's encoder): the
  * reference's Decoder::operator() (libs/decoder.cpp:168-210) without the GUI.  Its records hold

@@ -25,6 +25,10 @@
 //
 // window (svc_hip_window_levels_frames): a stored stream restricted to a window per output frame, without the pixels -- count, scan,
 // frame offsets, then one pass that writes every output frame in aligned 16-byte vectors (stated at its kernels).
+//
+// split (svc_hip_split_levels_frames, svc_hip_split_levels_budget_frames): a stored fine stream -> a base stream at any steps plus its
+// enhancement, in integers on the levels -- the window call's count and scan for the input, then count, scan, frame offsets and one
+// write pass, each serving both layers (stated at its kernels).
 #include "budget_core.hpp"
 #include "display_core.hpp"
 #include "idct_core.hpp"
@@ -680,7 +684,8 @@ struct WindowArgs {
 };
 
 // output frame i's input frame, checked as the unpack checks it before its masks (a frame index past the stream: kStRange)
-__device__ __forceinline__ uint32_t window_source(const WindowArgs& a, uint32_t i, uint64_t* off, const uint32_t** hdr) {
+template <typename A>  // WindowArgs, or the split's SplitArgs
+__device__ __forceinline__ uint32_t window_source(const A& a, uint32_t i, uint64_t* off, const uint32_t** hdr) {
   const uint32_t s = a.src ? a.src[i] : i;
   if (s >= a.n_in) return kStRange;
   return check_svcq<false>(a.g, a.in, a.stream_bytes, a.offsets, s, off, hdr);
@@ -763,9 +768,12 @@ __global__ __launch_bounds__(256) void window_scan_kernel(WindowArgs a) {
   }
 }
 
-// one workgroup: offsets[0 .. n] from the frames' sizes
-__global__ __launch_bounds__(256) void window_offsets_kernel(const uint32_t* __restrict__ bytes, uint32_t n, uint64_t* __restrict__ offsets) {
+// one workgroup per stream (the window call has one, the split its two layers): offsets[0 .. n] from the frames' sizes
+__global__ __launch_bounds__(256) void window_offsets_kernel(const uint32_t* __restrict__ bytes0, uint64_t* __restrict__ offsets0,
+                                                             const uint32_t* __restrict__ bytes1, uint64_t* __restrict__ offsets1, uint32_t n) {
   __shared__ uint64_t red[kThreads / 64];
+  const uint32_t* __restrict__ bytes = blockIdx.x ? bytes1 : bytes0;
+  uint64_t* __restrict__ offsets = blockIdx.x ? offsets1 : offsets0;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint64_t carry = 0;
   for (uint32_t base = 0; base < n; base += kThreads) {
@@ -885,6 +893,343 @@ __global__ __launch_bounds__(256) void window_write_kernel(WindowArgs a) {
   }
 }
 
+// ---- split: a stored fine stream -> a base stream at any steps and its enhancement (svc_hip_split_levels_frames) ---------------------
+//
+// Input frame s holds the levels Lf at (e, e).  For a tile of class c, r = the class's base step / e, Lb = Lf / r rounded half away
+// from zero and d = Lf - Lb * r inside output frame i's window: integers only, per coefficient, so a wave owns a group (a plane, a
+// tile row, up to tpg tiles) and walks its mask words with one lane per coefficient.  The lane's Lf is found by rank (mbcnt) from the
+// input index S of the group's first level plus the popcounts of the group's earlier words; the new masks are the ballots of Lb != 0
+// and d != 0.  Per output frame
+//   input    window_count_kernel and window_scan_kernel with no window: S per group and the input frame's status (unpack's code)
+//   count    one wave per group: the non-zero levels of both layers
+//   scan     one workgroup per frame: both layers' prefixes, level counts and sizes, the final status (kStLayer for a header step that
+//            is not e)
+//   offsets  window_offsets_kernel, a workgroup per layer
+//   write    one wave per group: both layers' mask words (a lane per word, 8 bytes each) and levels.  The levels are compacted in LDS
+//            and stored as aligned dwords; a run that starts or ends at an odd level shares that dword with its neighbour's run and
+//            stores its half of it as 16 bits.  The first workgroup of a frame also writes both headers, types and paddings.  Every
+//            output byte is stored once: two calls write the same bytes.
+// The budgeted form counts, between `input` and `count`, the coefficients every ladder entry keeps (2 |Lf| >= r: an integer compare)
+// and picks each frame's pair; the passes after it take the steps per frame.
+
+struct SplitWs {
+  WinWs in;                // the input pass: in.before = S, in.status = unpack's code
+  uint32_t *nzb, *nze;     // [n][groups] non-zero levels of the base / the enhancement, then their exclusive prefixes
+  uint32_t *frame_bytes;   // [2][n] base, enhancement
+  uint32_t *frame_levels;  // [2][n]
+  uint32_t* steps;         // [n][2] fg, bg of each frame (the budgeted form)
+  uint32_t* nz;            // [n][len][groups] (the budgeted form)
+};
+uint64_t split_ws_bytes(uint32_t n, uint32_t groups, uint32_t len) {
+  return win_ws_bytes(n, groups) + 2 * up16(4ull * n * groups) + 3 * up16(8ull * n) + up16(4ull * n * len * groups);
+}
+SplitWs carve_split(uint8_t* p, uint32_t n, uint32_t groups) {
+  SplitWs s;
+  s.in = carve_window(p, n, groups);
+  p += win_ws_bytes(n, groups);
+  const uint64_t a = up16(4ull * n * groups), b = up16(8ull * n);
+  s.nzb = reinterpret_cast<uint32_t*>(p);
+  s.nze = reinterpret_cast<uint32_t*>(p + a);
+  s.frame_bytes = reinterpret_cast<uint32_t*>(p + 2 * a);
+  s.frame_levels = reinterpret_cast<uint32_t*>(p + 2 * a + b);
+  s.steps = reinterpret_cast<uint32_t*>(p + 2 * a + 2 * b);
+  s.nz = reinterpret_cast<uint32_t*>(p + 2 * a + 3 * b);
+  return s;
+}
+
+struct SplitArgs {
+  Geom g;
+  const uint8_t* in;
+  uint64_t stream_bytes;
+  const uint64_t* offsets;  // [n_in + 1]
+  uint32_t n_in;
+  const uint32_t* src;      // [n_out] or null
+  const uint32_t* window;   // [n_out][4] or null: every tile is enhanced
+  uint32_t n_out, e, fg, bg;
+  const uint32_t* steps;    // [n_out][2] fg, bg per frame (the budgeted form), or null: fg / bg for every frame
+  uint8_t *base, *enh;      // enh null: the base only
+  uint64_t *base_offsets, *enh_offsets;
+  uint32_t* d_status;
+  SplitWs ws;
+};
+
+// output frame i's input frame; only for a frame whose input pass reported kStOk (its source index and offsets are then in range)
+__device__ __forceinline__ const uint8_t* split_frame_ptr(const SplitArgs& a, uint32_t i) {
+  return a.in + a.offsets[a.src ? a.src[i] : i];
+}
+
+// the frame's status: unpack's code from the input pass, then kStLayer for a frame whose header does not say (e, e)
+__device__ __forceinline__ uint32_t split_status(const SplitArgs& a, uint32_t i, const uint8_t** frame) {
+  const uint32_t st = a.ws.in.status[i];
+  if (st != kStOk) return st;
+  *frame = split_frame_ptr(a, i);
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(*frame);
+  return hdr[kHFgStep] == a.e && hdr[kHBgStep] == a.e ? kStOk : kStLayer;
+}
+
+// floor(num / den) for num < 2^18 and den < 2^16 with rcp = 1.f / den: the f32 product is within 1 of the quotient
+__device__ __forceinline__ uint32_t div_by(uint32_t num, uint32_t den, float rcp) {
+  uint32_t q = (uint32_t)((float)num * rcp);
+  q -= q * den > num;
+  q += (q + 1) * den <= num;
+  return q;
+}
+
+// Lb = lf / r rounded half away from zero, d = lf - Lb * r; rcp = 1.f / (2 r)
+__device__ __forceinline__ void split_level(int32_t lf, uint32_t r, float rcp, int32_t* lb, int32_t* d) {
+  const uint32_t q = div_by(2u * (uint32_t)abs(lf) + r, 2u * r, rcp);
+  *lb = lf < 0 ? -(int32_t)q : (int32_t)q;
+  *d = lf - *lb * (int32_t)r;
+}
+
+// The wave's walk over its group's mask words, 64 of them at a time: lane l loads word l's mask and its tile's class and window
+// bits, a wave scan of the popcounts gives every word the index of its first level, and the words are then walked with a lane per
+// coefficient -- fn(j, fg, win, lf): j the word, fg / win whether its tile is foreground / inside output frame i's window, lf this
+// lane's input level (0 where the mask bit is clear).  No load of the walk depends on an earlier one.  s = the input index of the
+// group's first level.
+template <typename F>
+__device__ __forceinline__ void split_walk(const SplitArgs& a, uint32_t i, const Group& gr, const uint8_t* frame, uint32_t s, F&& fn) {
+  const Geom& g = a.g;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t* masks = reinterpret_cast<const uint32_t*>(frame + g.masks_off) +
+                          2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+  const uint32_t* types = reinterpret_cast<const uint32_t*>(frame + kHeaderBytes);
+  const int16_t* lv = reinterpret_cast<const int16_t*>(frame + g.levels_off) + s;
+  const uint32_t jobs = gr.nt * g.words;
+  for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {
+    const uint32_t j = j0 + lane, cnt = min(64u, jobs - j0);
+    uint64_t m = 0;
+    bool fg = false, win = false;
+    if (j < jobs) {
+      const uint32_t t = j / g.words;
+      m = load_mask(masks + 2 * j);
+      fg = tile_type(g, types, gr, t) != 0;
+      win = a.enh && in_window(a.window, i, gr.x0 + t * g.bw, gr.y0);
+    }
+    const uint32_t pc = (uint32_t)__popcll(m), first = wave_exclusive_scan(pc);
+    const uint64_t fg_words = __ballot(fg), win_words = __ballot(win);
+#pragma unroll 4
+    for (uint32_t k = 0; k < cnt; ++k) {
+      const uint64_t mk = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)m, k) |
+                          ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(m >> 32), k) << 32);
+      const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)first, k);
+      const int32_t lf = (mk >> lane) & 1u ? (int32_t)lv[at + lane_rank(mk)] : 0;
+      fn(j0 + k, (uint32_t)(fg_words >> k) & 1u, (win_words >> k) & 1u, lf);
+    }
+    lv += (uint32_t)__builtin_amdgcn_readlane((int)(first + pc), 63);
+  }
+}
+
+// a frame's steps as ratios of e: class 0 = background
+struct SplitRatios {
+  uint32_t fg, bg, r[2];
+  float rcp[2];
+};
+__device__ __forceinline__ SplitRatios split_ratios(const SplitArgs& a, uint32_t i) {
+  SplitRatios s;
+  s.fg = a.steps ? a.steps[2 * i] : a.fg;
+  s.bg = a.steps ? a.steps[2 * i + 1] : a.bg;
+  s.r[0] = s.bg / a.e;
+  s.r[1] = s.fg / a.e;
+  s.rcp[0] = 1.f / (float)(2 * s.r[0]);
+  s.rcp[1] = 1.f / (float)(2 * s.r[1]);
+  return s;
+}
+
+__global__ __launch_bounds__(256) void split_count_kernel(SplitArgs a) {
+  const Geom& g = a.g;
+  const uint32_t lane = threadIdx.x & 63u, gi = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), i = blockIdx.y;
+  if (gi >= g.groups) return;  // (the whole wave)
+  const uint8_t* frame = nullptr;
+  uint32_t nzb = 0, nze = 0;  // a frame that fails counts nothing
+  if (split_status(a, i, &frame) == kStOk) {
+    const Group gr = group_of(g, gi);
+    const SplitRatios sr = split_ratios(a, i);
+    split_walk(a, i, gr, frame, a.ws.in.before[(size_t)i * g.groups + gi], [&](uint32_t, uint32_t c, bool win, int32_t lf) {
+      int32_t lb, d;
+      split_level(lf, sr.r[c], sr.rcp[c], &lb, &d);
+      nzb += (uint32_t)__popcll(__ballot(lb != 0));
+      if (win) nze += (uint32_t)__popcll(__ballot(d != 0));
+    });
+  }
+  if (lane == 0) {
+    a.ws.nzb[(size_t)i * g.groups + gi] = nzb;
+    a.ws.nze[(size_t)i * g.groups + gi] = nze;
+  }
+}
+
+__global__ __launch_bounds__(256) void split_scan_kernel(SplitArgs a) {
+  __shared__ uint32_t red[kThreads / 64];
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.x;
+  uint32_t* nzb = a.ws.nzb + (size_t)i * g.groups;
+  uint32_t* nze = a.ws.nze + (size_t)i * g.groups;
+  uint32_t carry_b = 0, carry_e = 0;
+  for (uint32_t base = 0; base < g.groups; base += kThreads) {
+    const uint32_t k = base + threadIdx.x;
+    const bool live = k < g.groups;
+    uint32_t sum_b, sum_e;
+    const uint32_t ex_b = block_exclusive_scan(live ? nzb[k] : 0u, red, &sum_b);
+    const uint32_t ex_e = block_exclusive_scan(live ? nze[k] : 0u, red, &sum_e);
+    if (live) {
+      nzb[k] = carry_b + ex_b;
+      nze[k] = carry_e + ex_e;
+    }
+    carry_b += sum_b;
+    carry_e += sum_e;
+  }
+  if (threadIdx.x == 0) {
+    const uint8_t* frame = nullptr;
+    const uint32_t st = split_status(a, i, &frame);
+    a.d_status[i] = st;
+    a.ws.in.status[i] = st;  // the write pass reads the final code
+    a.ws.frame_levels[i] = carry_b;
+    a.ws.frame_levels[a.n_out + i] = carry_e;
+    a.ws.frame_bytes[i] = st == kStOk ? (uint32_t)up16(g.levels_off + 2ull * carry_b) : kHeaderBytes;
+    a.ws.frame_bytes[a.n_out + i] = st == kStOk ? (uint32_t)up16(g.levels_off + 2ull * carry_e) : kHeaderBytes;
+  }
+}
+
+// the wave's cnt levels from LDS to dst, a 2-byte aligned place in the output: aligned dwords, and 16 bits at an odd end
+__device__ __forceinline__ void split_store_levels(const uint16_t* buf, uint32_t cnt, uint16_t* dst) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t head = cnt != 0 && (reinterpret_cast<uintptr_t>(dst) & 2u) ? 1u : 0u, body = (cnt - head) / 2;
+  if (head && lane == 0) dst[0] = buf[0];
+  uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + head);
+  for (uint32_t k = lane; k < body; k += 64) d32[k] = (uint32_t)buf[head + 2 * k] | ((uint32_t)buf[head + 2 * k + 1] << 16);
+  if (((cnt - head) & 1u) && lane == 0) dst[cnt - 1] = buf[cnt - 1];
+}
+
+// what the first workgroup of output frame i writes of one layer: the header (words 0 .. 7 and 11 of the input's), the types, the padding
+__device__ __forceinline__ void split_frame_edges(const Geom& g, const uint8_t* frame, uint8_t* out, uint32_t fg, uint32_t bg,
+                                                  uint32_t level_count, uint32_t fbytes) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(frame);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(out);
+  const uint32_t head = kHeaderWords + g.mvb;
+  for (uint32_t k = threadIdx.x; k < head; k += blockDim.x) {
+    const uint32_t v = src[k];
+    dst[k] = k == kHFgStep ? fg : k == kHBgStep ? bg : k == kHLevels ? level_count : k == kHBytes ? fbytes :
+             (k >= kQReserved && k < kHeaderWords) ? 0u : v;
+  }
+  uint16_t* pad = reinterpret_cast<uint16_t*>(out + g.levels_off) + level_count;
+  const uint32_t npad = (uint32_t)(fbytes - (g.levels_off + 2ull * level_count)) / 2;  // at most 7: the levels end at an even byte
+  if (threadIdx.x < npad) pad[threadIdx.x] = 0;
+}
+
+// The write pass's waves per workgroup and its dynamic LDS: per wave the group's coefficients as u16, twice (base, enhancement).  A
+// group is tiles of at most kGroupCoeffs coefficients together, or one larger tile of at most kMaxTileCoeffs: 32 KB either way,
+// which the assertion below keeps should either constant move.
+constexpr uint32_t split_write_waves(uint32_t cap) { return cap > kGroupCoeffs ? 2 : kThreads / 64; }
+constexpr uint32_t split_write_lds(uint32_t cap) { return split_write_waves(cap) * 2 * cap * (uint32_t)sizeof(uint16_t); }
+static_assert(split_write_lds(kGroupCoeffs) <= 32768 && split_write_lds(kMaxTileCoeffs) <= 32768,
+              "the split's write pass stages at most 32 KB per workgroup");
+
+// blockDim.x / 64 waves, a group each; dynamic LDS: split_write_lds(cap), cap = the coefficients of a full group
+__global__ __launch_bounds__(256) void split_write_kernel(SplitArgs a, uint32_t cap) {
+  extern __shared__ uint16_t stage[];
+  const Geom& g = a.g;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, gi = blockIdx.x * (blockDim.x >> 6) + wave, i = blockIdx.y;
+  uint8_t* base = a.base + a.base_offsets[i];
+  uint8_t* enh = a.enh ? a.enh + a.enh_offsets[i] : nullptr;
+  if (a.ws.in.status[i] != kStOk) {  // (the final code) 64 zero bytes in each layer; the input frame is not read
+    if (blockIdx.x == 0 && threadIdx.x < kHeaderWords) {
+      reinterpret_cast<uint32_t*>(base)[threadIdx.x] = 0;
+      if (enh) reinterpret_cast<uint32_t*>(enh)[threadIdx.x] = 0;
+    }
+    return;
+  }
+  const uint8_t* frame = split_frame_ptr(a, i);
+  const SplitRatios sr = split_ratios(a, i);
+  const bool live = gi < g.groups;  // no early return: the barrier below is the workgroup's
+  uint16_t* buf_b = stage + (size_t)wave * 2 * cap;
+  uint16_t* buf_e = buf_b + cap;
+  uint32_t cnt_b = 0, cnt_e = 0;
+  if (live) {
+    const Group gr = group_of(g, gi);
+    const size_t word0 = 2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+    uint32_t* masks_b = reinterpret_cast<uint32_t*>(base + g.masks_off) + word0;
+    uint32_t* masks_e = enh ? reinterpret_cast<uint32_t*>(enh + g.masks_off) + word0 : nullptr;
+    const uint32_t jobs = gr.nt * g.words;
+    uint64_t keep_b = 0, keep_e = 0;  // lane l: the new masks of word (j & ~63) + l, stored 64 words at a time
+    split_walk(a, i, gr, frame, a.ws.in.before[(size_t)i * g.groups + gi], [&](uint32_t j, uint32_t c, bool win, int32_t lf) {
+      int32_t lb, d;
+      split_level(lf, sr.r[c], sr.rcp[c], &lb, &d);
+      const uint64_t mb = __ballot(lb != 0);
+      if (lb != 0) buf_b[cnt_b + lane_rank(mb)] = (uint16_t)lb;
+      cnt_b += (uint32_t)__popcll(mb);
+      uint64_t me = 0;
+      if (win) {
+        me = __ballot(d != 0);
+        if (d != 0) buf_e[cnt_e + lane_rank(me)] = (uint16_t)d;
+        cnt_e += (uint32_t)__popcll(me);
+      }
+      if (lane == (j & 63u)) keep_b = mb, keep_e = me;
+      if ((j & 63u) == 63u || j + 1 == jobs) {
+        const uint32_t k = (j & ~63u) + lane;
+        if (k <= j) {
+          store_mask(masks_b + 2 * k, keep_b);
+          if (enh) store_mask(masks_e + 2 * k, keep_e);
+        }
+      }
+    });
+  }
+  __syncthreads();
+  if (live) {
+    split_store_levels(buf_b, cnt_b, reinterpret_cast<uint16_t*>(base + g.levels_off) + a.ws.nzb[(size_t)i * g.groups + gi]);
+    if (enh) split_store_levels(buf_e, cnt_e, reinterpret_cast<uint16_t*>(enh + g.levels_off) + a.ws.nze[(size_t)i * g.groups + gi]);
+  }
+  if (blockIdx.x != 0) return;
+  split_frame_edges(g, frame, base, sr.fg, sr.bg, a.ws.frame_levels[i], a.ws.frame_bytes[i]);
+  if (enh) split_frame_edges(g, frame, enh, a.e, a.e, a.ws.frame_levels[a.n_out + i], a.ws.frame_bytes[a.n_out + i]);
+}
+
+// The budgeted form's count, one wave per group: entry k keeps a coefficient when 2 |Lf| >= r_k of the tile's class (exactly Lb != 0
+// there).  r is non-decreasing along the ladder, so a word's ballots shrink and the loop stops at the first empty one.  Lane k holds
+// r_k of both classes and sums entry k's popcounts, as budget_count_kernel does with its thresholds.
+__global__ __launch_bounds__(256) void split_budget_count_kernel(SplitArgs a, Ladder lad) {
+  const Geom& g = a.g;
+  const uint32_t lane = threadIdx.x & 63u, gi = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), i = blockIdx.y;
+  if (gi >= g.groups) return;  // (the whole wave)
+  const uint8_t* frame = nullptr;
+  uint32_t acc = 0;  // lane k: the group's non-zero base levels at entry k; a frame that fails counts nothing
+  if (split_status(a, i, &frame) == kStOk) {
+    const Group gr = group_of(g, gi);
+    const uint32_t r_bg = lane < lad.len ? lad.step[0][lane] / a.e : 0xFFFFFFFFu, r_fg = lane < lad.len ? lad.step[1][lane] / a.e : 0xFFFFFFFFu;
+    split_walk(a, i, gr, frame, a.ws.in.before[(size_t)i * g.groups + gi], [&](uint32_t, uint32_t c, bool, int32_t lf) {
+      const uint32_t r = c ? r_fg : r_bg, m2 = 2u * (uint32_t)abs(lf);
+      for (uint32_t k = 0; k < lad.len; ++k) {
+        const uint64_t mask = __ballot(m2 >= (uint32_t)__builtin_amdgcn_readlane((int)r, k));
+        if (mask == 0) break;
+        acc += lane == k ? (uint32_t)__popcll(mask) : 0u;
+      }
+    });
+  }
+  if (lane < lad.len) a.ws.nz[((size_t)i * lad.len + lane) * g.groups + gi] = acc;
+}
+
+// One workgroup per frame: bytes_k = up16(levels offset + 2 * the sum of entry k's counts), then the choice (0 for a frame that fails)
+// and that entry's steps for the passes after it.
+__global__ __launch_bounds__(256) void split_select_kernel(SplitArgs a, Ladder lad, const uint32_t* __restrict__ budget,
+                                                           uint32_t* __restrict__ choice) {
+  __shared__ uint32_t red[kThreads / 64];
+  __shared__ uint64_t bytes[kMaxLadder];
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.x;
+  for (uint32_t k = 0; k < lad.len; ++k) {
+    const uint32_t* p = a.ws.nz + ((size_t)i * lad.len + k) * g.groups;
+    uint32_t s = 0, total;
+    for (uint32_t j = threadIdx.x; j < g.groups; j += kThreads) s += p[j];
+    (void)block_exclusive_scan(s, red, &total);
+    if (threadIdx.x == 0) bytes[k] = up16(g.levels_off + 2ull * total);
+  }
+  if (threadIdx.x != 0) return;
+  const uint8_t* frame = nullptr;
+  const uint32_t ch = split_status(a, i, &frame) == kStOk ? budget_choice(bytes, lad.len, budget[i]) : 0u, pick = ch & 0x7FFFFFFFu;
+  choice[i] = ch;
+  a.ws.steps[2 * i] = lad.step[1][pick];
+  a.ws.steps[2 * i + 1] = lad.step[0][pick];
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -923,6 +1268,91 @@ int enqueue_unpack_scan(const char* what, const UnpackArgs& u, uint32_t n, uint3
   if (rc) return rc;
   hipLaunchKernelGGL(scan_kernel<true>, dim3(n), dim3(kThreads), 0, s, u.g, u.ws, u.in, u.stream_bytes, u.offsets, d_status);
   return check_launch(what, "scan");
+}
+
+
+// ---- the split's checks after its steps, and its launches
+
+// a base step pair against the fine step: multiples of it, and ratios whose residuals fit int16
+int validate_split_steps(const char* what, uint32_t fine_step, uint32_t fg_step, uint32_t bg_step) {
+  SVC_REQUIRE(fg_step % fine_step == 0 && bg_step % fine_step == 0, "%s: the base steps (%u, %u) must be multiples of fine_step %u", what,
+              fg_step, bg_step, fine_step);
+  if (std::max(fg_step, bg_step) / fine_step > 32766)
+    return fail(SVC_ERR_UNSUPPORTED, "%s: residuals of base step %u over fine_step %u could exceed int16", what, std::max(fg_step, bg_step),
+                fine_step);
+  return SVC_OK;
+}
+
+// Both calls after their steps or ladder, in the order of the SVCQ entry points: limits, the d_src rule, workspace, capacities;
+// n_out == 0 returns SVC_OK; then pointers; then the launches.  ladder null: the fixed call with a.fg / a.bg.
+int split_levels(const char* what, SplitArgs a, const svc_step_pair* ladder, uint32_t ladder_len, const uint32_t* d_budget,
+                 uint32_t* d_choice, uint8_t* d_workspace, uint64_t workspace_bytes, uint64_t base_capacity, uint64_t enh_capacity,
+                 void* stream) {
+  const Geom& g = a.g;
+  int rc = validate_limits(what, std::max(a.n_out, a.n_in), g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh);
+  if (rc) return rc;
+  SVC_REQUIRE(a.src || a.n_out == a.n_in, "%s: without d_src output frame i is input frame i, but n_out is %u and n_in %u", what, a.n_out,
+              a.n_in);
+  a.g = make_geom(g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh);
+  const uint64_t ws_need = split_ws_bytes(a.n_out, g.groups, ladder ? ladder_len : 0);
+  SVC_REQUIRE(workspace_bytes >= ws_need, "%s: workspace of %llu B is smaller than the %llu B needed", what,
+              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
+  const uint64_t max_bytes = frame_layout(g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh).max_bytes;
+  SVC_REQUIRE(base_capacity >= a.n_out * max_bytes, "%s: base output of %llu B is below the batch's worst case of %llu B", what,
+              (unsigned long long)base_capacity, (unsigned long long)(a.n_out * max_bytes));
+  SVC_REQUIRE(!a.enh || enh_capacity >= a.n_out * max_bytes,
+              "%s: enhancement output of %llu B is below the batch's worst case of %llu B", what, (unsigned long long)enh_capacity,
+              (unsigned long long)(a.n_out * max_bytes));
+  if (a.n_out == 0) return SVC_OK;
+  SVC_REQUIRE(a.in && a.offsets && d_workspace && a.base && a.base_offsets && a.d_status && (!a.enh || a.enh_offsets) &&
+                  (!ladder || (d_budget && d_choice)),
+              "%s: null pointer", what);
+  SVC_REQUIRE(aligned(a.in, 16) && aligned(a.base, 16) && aligned(a.enh, 16) && aligned(d_workspace, 16) && aligned(a.offsets, 8) &&
+                  aligned(a.base_offsets, 8) && aligned(a.enh_offsets, 8) && aligned(a.src, 4) && aligned(a.window, 4) &&
+                  aligned(a.d_status, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
+              "%s: streams and workspace must be 16-byte aligned, offsets 8-byte, source indices, windows, budget, choice and status 4-byte",
+              what);
+  a.ws = carve_split(d_workspace, a.n_out, g.groups);
+  if (!a.enh) a.enh_offsets = nullptr, a.window = nullptr;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 waves(div_up(g.groups, kThreads / 64), a.n_out);
+  // the input pass: the window call's count and scan with every tile kept
+  const WindowArgs in{g, a.in, a.stream_bytes, a.offsets, a.n_in, a.src, nullptr, nullptr, nullptr, a.d_status, a.ws.in};
+  hipLaunchKernelGGL(window_count_kernel, waves, dim3(kThreads), 0, s, in);
+  if ((rc = check_launch(what, "input count"))) return rc;
+  hipLaunchKernelGGL(window_scan_kernel, dim3(a.n_out), dim3(kThreads), 0, s, in);
+  if ((rc = check_launch(what, "input scan"))) return rc;
+  if (ladder) {
+    const Ladder lad = make_ladder(ladder, ladder_len);
+    hipLaunchKernelGGL(split_budget_count_kernel, waves, dim3(kThreads), 0, s, a, lad);
+    if ((rc = check_launch(what, "count per entry"))) return rc;
+    hipLaunchKernelGGL(split_select_kernel, dim3(a.n_out), dim3(kThreads), 0, s, a, lad, d_budget, d_choice);
+    if ((rc = check_launch(what, "select"))) return rc;
+    a.steps = a.ws.steps;
+  }
+  hipLaunchKernelGGL(split_count_kernel, waves, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch(what, "count"))) return rc;
+  hipLaunchKernelGGL(split_scan_kernel, dim3(a.n_out), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch(what, "scan"))) return rc;
+  hipLaunchKernelGGL(window_offsets_kernel, dim3(a.enh ? 2 : 1), dim3(kThreads), 0, s, a.ws.frame_bytes, a.base_offsets,
+                     a.ws.frame_bytes + a.n_out, a.enh_offsets, a.n_out);
+  if ((rc = check_launch(what, "offsets"))) return rc;
+  // a wave stages its group's levels of both layers in LDS: two waves per workgroup where a group is a tile above 2048 coefficients
+  const uint32_t cap = g.tpg * g.bw * g.bh, wpb = split_write_waves(cap);
+  hipLaunchKernelGGL(split_write_kernel, dim3(div_up(g.groups, wpb), a.n_out), dim3(64 * wpb), split_write_lds(cap), s, a, cap);
+  return check_launch(what, "write");
+}
+
+SplitArgs split_args(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_in, const uint32_t* d_src,
+                     uint32_t n_out, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh, uint32_t fine_step,
+                     const uint32_t* d_window, uint8_t* d_base_out, uint64_t* d_base_offsets, uint8_t* d_enh_out, uint64_t* d_enh_offsets,
+                     uint32_t* d_status) {
+  SplitArgs a{};
+  a.g.w = w; a.g.h = h; a.g.bw = bw; a.g.bh = bh; a.g.mvbw = mvbw; a.g.mvbh = mvbh;  // the rest of g once the limits have passed
+  a.in = d_frames; a.stream_bytes = stream_bytes; a.offsets = d_frame_offsets; a.n_in = n_in; a.src = d_src; a.window = d_window;
+  a.n_out = n_out; a.e = fine_step;
+  a.base = d_base_out; a.enh = d_enh_out; a.base_offsets = d_base_offsets; a.enh_offsets = d_enh_offsets; a.d_status = d_status;
+  return a;
 }
 
 }  // namespace
@@ -1226,13 +1656,77 @@ int svc_hip_window_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   if ((rc = check_launch("window_levels", "count"))) return rc;
   hipLaunchKernelGGL(window_scan_kernel, dim3(n_out), dim3(kThreads), 0, s, a);
   if ((rc = check_launch("window_levels", "scan"))) return rc;
-  hipLaunchKernelGGL(window_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.frame_bytes, n_out, d_out_offsets);
+  hipLaunchKernelGGL(window_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.frame_bytes, d_out_offsets, nullptr, nullptr, n_out);
   if ((rc = check_launch("window_levels", "offsets"))) return rc;
   // a workgroup's pass is 4 KB of an output frame; the grid holds twice the header, types and masks (a window's levels are fewer
   // bytes than its frame's masks), and a frame that keeps more is walked in further passes
   const uint32_t fixed = div_up((uint32_t)(up16(g.levels_off) / 16), kThreads), most = div_up((uint32_t)(max_bytes / 16), kThreads);
   hipLaunchKernelGGL(window_write_kernel, dim3(std::min(2 * fixed, most), n_out), dim3(kThreads), 0, s, a);
   return check_launch("window_levels", "write");
+}
+
+uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                              uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("split_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("split_levels_workspace_bytes", std::max(n_in, n_out), frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  return split_ws_bytes(n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups, 0);
+}
+
+uint64_t svc_hip_split_levels_budget_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                     uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t ladder_len) {
+  if (validate_geom("split_levels_budget_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("split_levels_budget_workspace_bytes", std::max(n_in, n_out), frame_w, frame_h, block_w, block_h, mv_block_w,
+                      mv_block_h))
+    return 0;
+  if (ladder_len == 0 || ladder_len > kMaxLadder) {
+    (void)fail(SVC_ERR_INVALID_ARG, "split_levels_budget_workspace_bytes: a ladder of %u entries (1 .. %u)", ladder_len, kMaxLadder);
+    return 0;
+  }
+  return split_ws_bytes(n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups, ladder_len);
+}
+
+// Checked in the order of the SVCQ entry points, whatever the frame counts: geometry, steps, limits, the d_src rule, workspace, the two
+// capacities; n_out == 0 then returns SVC_OK; then pointers.
+int svc_hip_split_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_in,
+                                const uint32_t* d_src, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fine_step, uint32_t fg_step,
+                                uint32_t bg_step, const uint32_t* d_window, uint8_t* d_workspace, uint64_t workspace_bytes,
+                                uint8_t* d_base_out, uint64_t base_capacity, uint64_t* d_base_offsets, uint8_t* d_enh_out,
+                                uint64_t enh_capacity, uint64_t* d_enh_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("split_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fine_step > 0 && fg_step > 0 && bg_step > 0, "split_levels: quant steps must be positive");
+  if ((rc = validate_split_steps("split_levels", fine_step, fg_step, bg_step))) return rc;
+  SplitArgs a = split_args(d_frames, stream_bytes, d_frame_offsets, n_in, d_src, n_out, frame_w, frame_h, block_w, block_h, mv_block_w,
+                           mv_block_h, fine_step, d_window, d_base_out, d_base_offsets, d_enh_out, d_enh_offsets, d_status);
+  a.fg = fg_step;
+  a.bg = bg_step;
+  return split_levels("split_levels", a, nullptr, 0, nullptr, nullptr, d_workspace, workspace_bytes, base_capacity, enh_capacity, stream);
+}
+
+// The same order, the ladder in place of the steps: its own rules, every step a multiple of fine_step, the int16 bound on its last
+// (coarsest) entry.
+int svc_hip_split_levels_budget_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_in,
+                                       const uint32_t* d_src, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                       uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fine_step,
+                                       const svc_step_pair* ladder, uint32_t ladder_len, const uint32_t* d_budget,
+                                       const uint32_t* d_window, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_base_out,
+                                       uint64_t base_capacity, uint64_t* d_base_offsets, uint8_t* d_enh_out, uint64_t enh_capacity,
+                                       uint64_t* d_enh_offsets, uint32_t* d_choice, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("split_levels_budget", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fine_step > 0, "split_levels_budget: quant steps must be positive");
+  if ((rc = validate_ladder("split_levels_budget", ladder, ladder_len))) return rc;
+  for (uint32_t k = 0; k < ladder_len; ++k)
+    SVC_REQUIRE(ladder[k].fg_step % fine_step == 0 && ladder[k].bg_step % fine_step == 0,
+                "split_levels_budget: ladder entry %u (%u, %u) must be multiples of fine_step %u", k, ladder[k].fg_step, ladder[k].bg_step,
+                fine_step);
+  if ((rc = validate_split_steps("split_levels_budget", fine_step, ladder[ladder_len - 1].fg_step, ladder[ladder_len - 1].bg_step))) return rc;
+  const SplitArgs a = split_args(d_frames, stream_bytes, d_frame_offsets, n_in, d_src, n_out, frame_w, frame_h, block_w, block_h,
+                                 mv_block_w, mv_block_h, fine_step, d_window, d_base_out, d_base_offsets, d_enh_out, d_enh_offsets, d_status);
+  return split_levels("split_levels_budget", a, ladder, ladder_len, d_budget, d_choice, d_workspace, workspace_bytes, base_capacity,
+                      enh_capacity, stream);
 }
 
 int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w, uint32_t frame_h, uint32_t padded_w,

@@ -9,7 +9,16 @@ steps divide).  Per coefficient, with Lb its level in the base frame and Lf its 
 and an enhancement frame is an SVCQ frame whose levels are d, with fg_step = bg_step = enh_step in its header.  Inside the gaze the
 decoder dequantises (Lb * ratio + d) * enh_step, elsewhere Lb * sb.
 
-window_frame / window_frames state svc_hip_window_levels_frames: a stored frame restricted to the tiles of a window, on its masks."""
+window_frame / window_frames state svc_hip_window_levels_frames: a stored frame restricted to the tiles of a window, on its masks.
+
+split_frame / split_frames / split_budget_frames state svc_hip_split_levels_frames and its budgeted form: the stream stored at
+(fine_step, fine_step) alone determines a base frame at any multiples of fine_step and the enhancement frame that lifts it back, in
+integers on the levels' values:
+    Lb = sign(Lf) * ((2 |Lf| + r) // (2 r))     Lf / r rounded half away from zero, r = sb / fine_step
+    d  = Lf - Lb * r                            inside the window, 0 outside it
+Lb * r + d == Lf for any r.  For odd r (both classes) Lb is the level a direct quantisation at sb gives, so the two frames are the
+encoder's own; for even r a level that is an odd multiple of r / 2 is a tie the coefficient would have resolved either way, and the base
+differs from a direct encode there."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple
@@ -57,8 +66,8 @@ def _assemble(head, inexact: int, types: np.ndarray, masks: np.ndarray, lv: np.n
     return words + body + bytes(size - levels.HEADER_BYTES - len(body))
 
 
-def write_frame(hdr: Dict[str, int], types: np.ndarray, lv: np.ndarray, fg_step: int, bg_step: int) -> bytes:
-    """An SVCQ frame of hdr's geometry with the region ids `types` and the integer levels lv (3, H, W), inexact 0."""
+def write_frame(hdr: Dict[str, int], types: np.ndarray, lv: np.ndarray, fg_step: int, bg_step: int, inexact: int = 0) -> bytes:
+    """An SVCQ frame of hdr's geometry with the region ids `types` and the integer levels lv (3, H, W); header word 11 = inexact."""
     w, h, bw, bh = hdr["frame_w"], hdr["frame_h"], hdr["block_w"], hdr["block_h"]
     tx, ty, area = w // bw, h // bh, bw * bh
     nw = (area + 63) // 64
@@ -70,7 +79,7 @@ def write_frame(hdr: Dict[str, int], types: np.ndarray, lv: np.ndarray, fg_step:
     bits[..., :area] = nz
     masks = np.packbits(bits, axis=-1, bitorder="little")
     head = [levels.MAGIC, levels.VERSION, w, h, bw, bh, hdr["mv_block_w"], hdr["mv_block_h"], fg_step, bg_step]
-    return _assemble(head, 0, types, masks, tiles[nz])
+    return _assemble(head, inexact, types, masks, tiles[nz])
 
 
 def _belongs(hb: Dict[str, int], he: Dict[str, int]) -> bool:
@@ -187,3 +196,121 @@ def window_frames(stream, offsets, windows, src=None) -> Tuple[bytes, np.ndarray
         frames.append(out)
     out_offs = np.concatenate([[0], np.cumsum([len(fr) for fr in frames])]).astype(np.uint64)
     return b"".join(frames), out_offs
+
+
+# ---- a stored fine stream split into a base at any steps and its enhancement (include/svc_hip.h: svc_hip_split_levels_frames) ---------
+
+MAX_RATIO = 32766  # of a base step to the fine step: |d| <= ratio / 2 stays an int16
+
+
+def _check_split_steps(fine_step: int, fg_step: int, bg_step: int) -> None:
+    if min(fine_step, fg_step, bg_step) <= 0:
+        raise ValueError("quant steps must be positive")
+    if fg_step % fine_step or bg_step % fine_step:
+        raise ValueError(f"the base steps ({fg_step}, {bg_step}) must be multiples of fine_step {fine_step}")
+    if max(fg_step, bg_step) // fine_step > MAX_RATIO:
+        raise ValueError(f"residuals of base step {max(fg_step, bg_step)} over fine_step {fine_step} could exceed int16")
+
+
+def _fine_levels(fine_frame, fine_step: int):
+    hdr, types, planes = levels.parse_frame(fine_frame)  # raises for a frame the reader rejects (the device's status 2 .. 7)
+    if hdr["fg_step"] != fine_step or hdr["bg_step"] != fine_step:
+        raise ValueError(f"the frame's steps ({hdr['fg_step']}, {hdr['bg_step']}) are not ({fine_step}, {fine_step})")  # status 11
+    lf, _ = _levels_of(hdr, types, planes)
+    return hdr, types, lf
+
+
+def _base_levels(lf: np.ndarray, ratio: np.ndarray) -> np.ndarray:
+    """lf / ratio rounded half away from zero, in integers (ratio per pixel, broadcast over the planes)."""
+    return np.sign(lf) * ((2 * np.abs(lf) + ratio) // (2 * ratio))
+
+
+def split_frame(fine_frame, fine_step: int, fg_step: int, bg_step: int, window=None) -> Tuple[bytes, bytes]:
+    """The frame stored at (fine_step, fine_step) -> (base frame at (fg_step, bg_step), enhancement frame): header words 0 .. 7 and 11
+    and the types of the input, the base's levels Lb and the enhancement's d (zero outside the window x, y, w, h; None: every tile).
+    Stated on the levels' values: a set mask bit whose level is 0 is a zero.  Raises ValueError where the device reports a status."""
+    _check_split_steps(fine_step, fg_step, bg_step)
+    hdr, types, lf = _fine_levels(fine_frame, fine_step)
+    background, ox, oy = _tile_maps(hdr, types)
+    ratio = _per_pixel(hdr, np.where(background, bg_step, fg_step).astype(np.int64) // fine_step)[None]
+    lb = _base_levels(lf, ratio)
+    d = lf - lb * ratio
+    if window is not None:
+        d = np.where(_per_pixel(hdr, _contains(window, ox, oy))[None], d, 0)
+    return (write_frame(hdr, types, lb, fg_step, bg_step, hdr["inexact"]),
+            write_frame(hdr, types, d, fine_step, fine_step, hdr["inexact"]))
+
+
+def _source_frames(stream, offsets, src):
+    """The input frame of every output frame, checked as window_frames checks it -> a list of u8 views."""
+    b = np.frombuffer(stream, np.uint8) if not isinstance(stream, np.ndarray) else stream.reshape(-1).view(np.uint8)
+    offs = [int(o) for o in np.asarray(offsets).reshape(-1)]
+    n_in = len(offs) - 1
+    idx = list(range(n_in)) if src is None else [int(i) for i in np.asarray(src).reshape(-1)]
+    out = []
+    for i, f in enumerate(idx):
+        if not 0 <= f < n_in:
+            raise ValueError(f"output frame {i} names input frame {f} of {n_in}")
+        lo, hi = offs[f], offs[f + 1]
+        if lo % 16 or hi < lo or hi > b.size:
+            raise ValueError(f"SVCQ frame offsets out of order, misaligned or past the stream: {lo}, {hi}")
+        if hi - lo >= levels.HEADER_BYTES and int(b[lo + 48:lo + 52].view("<u4")[0]) != hi - lo:
+            raise ValueError(f"SVCQ frame at {lo} has frame_bytes {int(b[lo + 48:lo + 52].view('<u4')[0])}, its offsets {hi - lo}")
+        out.append(b[lo:hi])
+    return out
+
+
+def _join(frames) -> Tuple[bytes, np.ndarray]:
+    return b"".join(frames), np.concatenate([[0], np.cumsum([len(fr) for fr in frames])]).astype(np.uint64)
+
+
+def split_frames(stream, offsets, fine_step: int, fg_step: int, bg_step: int, windows=None, src=None
+                 ) -> Tuple[bytes, np.ndarray, bytes, np.ndarray]:
+    """What svc_hip_split_levels_frames writes for frames that pass their checks -> (base bytes, base offsets (n_out + 1,) u64,
+    enhancement bytes, its offsets): output frame i is split_frame of input frame src[i] (src None: frame i) and windows[i]."""
+    _check_split_steps(fine_step, fg_step, bg_step)
+    frames = _source_frames(stream, offsets, src)
+    win = None if windows is None else np.asarray(windows).reshape(len(frames), 4)
+    pairs = [split_frame(fr, fine_step, fg_step, bg_step, None if win is None else win[i]) for i, fr in enumerate(frames)]
+    return _join([p[0] for p in pairs]) + _join([p[1] for p in pairs])
+
+
+def split_budget_frames(stream, offsets, fine_step: int, ladder, budgets, windows=None, src=None
+                        ) -> Tuple[bytes, np.ndarray, bytes, np.ndarray, np.ndarray]:
+    """What svc_hip_split_levels_budget_frames writes -> (base bytes, base offsets, enhancement bytes, its offsets, choice (n_out,)
+    u32).  ladder: (fg_step, bg_step) pairs, finest first, non-decreasing, multiples of fine_step; budgets: one u32 byte count for
+    every output frame, or one each.  For entry k, bytes_k = up16(levels offset + 2 nz_k) with nz_k the coefficients whose
+    2 |Lf| >= r_k of their class (exactly Lb != 0): the base frame's size.  choice = the smallest k with bytes_k <= budget, else the
+    last entry with bit 31 set; the frame is split_frame at that pair."""
+    lad = [(int(fg), int(bg)) for fg, bg in ladder]
+    if not 1 <= len(lad) <= 64:
+        raise ValueError(f"a ladder of {len(lad)} entries (1 .. 64)")
+    for k, (fg, bg) in enumerate(lad):
+        if fine_step <= 0 or fg <= 0 or bg <= 0:
+            raise ValueError("quant steps must be positive")
+        if k and (fg < lad[k - 1][0] or bg < lad[k - 1][1]):
+            raise ValueError(f"ladder entry {k} is below entry {k - 1}: the ladder must be non-decreasing")
+        if fg % fine_step or bg % fine_step:
+            raise ValueError(f"ladder entry {k} ({fg}, {bg}) must be multiples of fine_step {fine_step}")
+    _check_split_steps(fine_step, *lad[-1])
+    frames = _source_frames(stream, offsets, src)
+    n = len(frames)
+    win = None if windows is None else np.asarray(windows).reshape(n, 4)
+    budget = np.broadcast_to(np.asarray(budgets, np.int64), (n,))
+    base, enh, choice = [], [], np.zeros(n, np.uint32)
+    for i, fr in enumerate(frames):
+        hdr, types, lf = _fine_levels(fr, fine_step)
+        background = _per_pixel(hdr, _tile_maps(hdr, types)[0])[None]
+        tiles = (hdr["frame_w"] // hdr["block_w"]) * (hdr["frame_h"] // hdr["block_h"])
+        levels_off = levels.HEADER_BYTES + 4 * types.size + 8 * 3 * tiles * ((hdr["block_w"] * hdr["block_h"] + 63) // 64)
+        pick = None
+        for k, (fg, bg) in enumerate(lad):
+            nz = int((2 * np.abs(lf) >= np.where(background, bg, fg) // fine_step).sum())
+            if (levels_off + 2 * nz + 15) // 16 * 16 <= int(budget[i]):
+                pick = k
+                break
+        choice[i] = pick if pick is not None else (len(lad) - 1) | 0x80000000
+        b, e = split_frame(fr, fine_step, *lad[int(choice[i]) & 0x7FFFFFFF], None if win is None else win[i])
+        base.append(b)
+        enh.append(e)
+    return _join(base) + _join(enh) + (choice,)

@@ -154,6 +154,12 @@ SIGNATURES = {
     # a stored SVCQ stream restricted to a window per output frame (csrc/levels.hip; host statement: layers.window_frames)
     "svc_hip_window_levels_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_window_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    # a stored fine SVCQ stream split into a base at any steps plus its enhancement (csrc/levels.hip; host statement: layers.split_frames)
+    "svc_hip_split_levels_workspace_bytes": (_u64, [_u32] * 8),
+    "svc_hip_split_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 10 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "svc_hip_split_levels_budget_workspace_bytes": (_u64, [_u32] * 9),
+    "svc_hip_split_levels_budget_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 8 + [C.POINTER(StepPair), _u32, _vp, _vp, _vp, _u64,
+                                                     _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     # the wire stream's decoder (csrc/records.hip) and its reading of a whole stream
     "svc_hip_decode_records_frames": (C.c_int, [_vp, _u64] + [_u32] * 7 + [_vp, _vp, _vp, _u32, _u32, _vp]),
     "svc_hip_wire_layout": (C.c_int, [C.POINTER(WireHeader), _u64, C.POINTER(_u32), C.POINTER(_u64)]),
@@ -1132,6 +1138,95 @@ def window_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h:
                                                workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
                                                _dev(status, torch.int32), _stream()))
     return out, out_offsets, status
+
+
+def split_levels_workspace_bytes(n_in: int, n_out: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of split_levels_frames for n_out output frames; 0 for a geometry or a frame count it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_split_levels_workspace_bytes(n_in, n_out, w, h, bw, bh, mbw, mbh))
+
+
+def split_levels_budget_workspace_bytes(n_in: int, n_out: int, w: int, h: int, block, mv_block, ladder_len: int) -> int:
+    """Scratch of split_levels_budget_frames; 0 for a geometry, a frame count or a ladder length it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_split_levels_budget_workspace_bytes(n_in, n_out, w, h, bw, bh, mbw, mbh, ladder_len))
+
+
+def _split_buffers(frames, offsets, w, h, block, mv_block, src, window, enhancement, base_out, base_offsets, enh_out, enh_offsets, status):
+    """The arguments both split calls share -> (n_in, n_out, src, window, base_out, base_offsets, enh_out, enh_offsets, status)."""
+    n_in = offsets.numel() - 1
+    dev = frames.device
+    s = None if src is None else torch.as_tensor(src, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    n_out = n_in if s is None else s.numel()
+    cap = max(levels_max_bytes(n_out, w, h, block, mv_block), 16)
+    if base_out is None:
+        base_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if base_offsets is None:
+        base_offsets = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+    if enhancement:
+        if enh_out is None:
+            enh_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        if enh_offsets is None:
+            enh_offsets = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(max(n_out, 1), dtype=torch.int32, device=dev)[:n_out]
+    return n_in, n_out, s, _rects(window, n_out, dev), base_out, base_offsets, enh_out, enh_offsets, status
+
+
+def split_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, fine_step: int, fg_step: int,
+                        bg_step: int, window=None, src=None, enhancement: bool = True, base_out: Optional[torch.Tensor] = None,
+                        base_offsets: Optional[torch.Tensor] = None, enh_out: Optional[torch.Tensor] = None,
+                        enh_offsets: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                        status: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], torch.Tensor]:
+    """A stored SVCQ stream encoded at (fine_step, fine_step) + its offsets -> a base stream at (fg_step, bg_step), multiples of
+    fine_step, and the enhancement stream that lifts the tiles inside window[i] back to fine_step (include/svc_hip.h; the numpy statement
+    is layers.split_frames).  window, src as window_levels_frames takes them.  enhancement=False: the base only; enh_out is then neither
+    written nor checked and comes back as it was passed.  -> (base u8 of the worst-case size, base offsets (n_out + 1,) i64, enhancement,
+    its offsets, status (n_out,) i32: unpack's code for the input frame, 1 for an index past the input, 11 for a frame that is not at
+    fine_step; a frame that fails is 64 zero bytes in both outputs).  The outputs must not overlap `frames`."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    n_in, n_out, s, win, base_out, base_offsets, enh_out, enh_offsets, status = _split_buffers(
+        frames, offsets, w, h, block, mv_block, src, window, enhancement, base_out, base_offsets, enh_out, enh_offsets, status)
+    if workspace is None:
+        workspace = torch.empty(max(split_levels_workspace_bytes(n_in, n_out, w, h, block, mv_block), 16), dtype=torch.uint8, device=frames.device)
+    _check(load().svc_hip_split_levels_frames(
+        _dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n_in, None if s is None else _dev(s, torch.int32), n_out,
+        w, h, bw, bh, mbw, mbh, fine_step, fg_step, bg_step, None if win is None else _dev(win, torch.int32),
+        _dev(workspace, torch.uint8), workspace.numel(), _dev(base_out, torch.uint8), base_out.numel(), _dev(base_offsets, torch.int64),
+        _dev(enh_out, torch.uint8) if enhancement else None, enh_out.numel() if enhancement else 0,
+        _dev(enh_offsets, torch.int64) if enhancement else None, _dev(status, torch.int32), _stream()))
+    return base_out, base_offsets, enh_out, enh_offsets, status
+
+
+def split_levels_budget_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, fine_step: int, ladder,
+                               budget, window=None, src=None, enhancement: bool = True, base_out: Optional[torch.Tensor] = None,
+                               base_offsets: Optional[torch.Tensor] = None, enh_out: Optional[torch.Tensor] = None,
+                               enh_offsets: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                               status: Optional[torch.Tensor] = None, choice: Optional[torch.Tensor] = None
+                               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """split_levels_frames with the base steps picked per output frame: the finest ladder entry (fg_step, bg_step) whose BASE frame fits
+    its byte budget (ladder and budget as pack_levels_budget_frames takes them; every step a multiple of fine_step).  -> (base, base
+    offsets, enhancement, its offsets, status, choice (n_out,) i32: the entry's index, with bit 31 set (a negative int32) when even the
+    last entry is over budget; 0 for a frame that fails)."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    arr, k = _ladder(ladder)
+    dev = frames.device
+    n_in, n_out, s, win, base_out, base_offsets, enh_out, enh_offsets, status = _split_buffers(
+        frames, offsets, w, h, block, mv_block, src, window, enhancement, base_out, base_offsets, enh_out, enh_offsets, status)
+    if workspace is None:
+        workspace = torch.empty(max(split_levels_budget_workspace_bytes(n_in, n_out, w, h, block, mv_block, k), 16), dtype=torch.uint8, device=dev)
+    if choice is None:
+        choice = torch.empty(max(n_out, 1), dtype=torch.int32, device=dev)[:n_out]
+    if not (isinstance(budget, torch.Tensor) and budget.is_cuda):
+        budget = budget_tensor(budget, n_out, dev)
+    _check(load().svc_hip_split_levels_budget_frames(
+        _dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n_in, None if s is None else _dev(s, torch.int32), n_out,
+        w, h, bw, bh, mbw, mbh, fine_step, arr, k, _dev(budget, torch.int32), None if win is None else _dev(win, torch.int32),
+        _dev(workspace, torch.uint8), workspace.numel(), _dev(base_out, torch.uint8), base_out.numel(), _dev(base_offsets, torch.int64),
+        _dev(enh_out, torch.uint8) if enhancement else None, enh_out.numel() if enhancement else 0,
+        _dev(enh_offsets, torch.int64) if enhancement else None, _dev(choice, torch.int32), _dev(status, torch.int32), _stream()))
+    return base_out, base_offsets, enh_out, enh_offsets, status, choice
 
 
 def gaze_rect(cx: int, cy: int, max_w: int, max_h: int, frame_w: int, frame_h: int, padded_w: int, padded_h: int

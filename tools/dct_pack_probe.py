@@ -28,6 +28,14 @@
                                                    stream against svc_hip_dct_pack_layers_frames with those windows (the other way to these
                                                    bytes), then 4 viewers (n_out = 64 from the 16 stored frames through d_src) against 4 such
                                                    encodes; wall time per call over 20 back-to-back calls; the bytes are compared
+  python tools/dct_pack_probe.py split [C3|C5]     a stored fine stream served at other base steps, the same batch of 16 at (fg, bg, e) =
+                                                   (1, 640, 1) with a 256 x 256 window per frame: svc_hip_split_levels_frames and
+                                                   svc_hip_split_levels_budget_frames (the 32-entry ladder and the budget of `budget`) on the
+                                                   stream stored at (1, 1), against svc_hip_dct_pack_layers_frames from the pixels with the same
+                                                   steps and windows (the call it replaces) and svc_hip_window_levels_frames on the stored
+                                                   enhancement (the call it sits beside); wall time per call over 20 back-to-back calls, the
+                                                   bytes each call reads and writes and their fraction of the HBM peak, and the split's base
+                                                   against the encoder's base at (1, 640) (an even ratio: they differ)
 """
 import os
 import sys
@@ -316,6 +324,101 @@ def window(cfg) -> None:
           f"({t_win4[0] / t_enc4[0]:.3f} of the encodes); same bytes; served {int(oo4[-1]) / n_out / 1e6:.3f} MB per frame", flush=True)
 
 
+HBM_PEAK = 8.0e12  # bytes per second, the MI355X's HBM3E
+
+
+def split(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    fg, bg, e = 1, 640, 1
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    fine, whole, ebase, eenh, sbase, senh, wout = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(7))
+    sync = torch.cuda.synchronize
+    ws1 = torch.empty(native.dct_pack_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws2 = torch.empty(native.dct_pack_layers_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    win = torch.tensor([((pw - 256) // 2 // 16 * 16 + 32 * (f % 7 - 3), (ph - 256) // 2 // 16 * 16 + 16 * (f % 5 - 2), 256, 256) for f in range(n)],
+                       dtype=torch.int32, device=dev)
+
+    def fmt(t):
+        return f"{t[0]:.3f} .. {t[1]:.3f}"
+
+    def hbm(nbytes, t):
+        return f"{nbytes / 1e6:.2f} MB moved, {nbytes / (t[0] * 1e-3) / HBM_PEAK * 100:.1f} % of the HBM peak"
+
+    # what is stored: the stream at (e, e), and the every-tile enhancement over the base at (fg, bg)
+    _, offs_f = native.dct_pack_levels_frames(bgr, block, types, mv, e, e, out=fine, workspace=ws1)
+    _, _, _, offs_w = native.dct_pack_layers_frames(bgr, block, types, mv, fg, bg, e, base_out=ebase, enh_out=whole, workspace=ws2)
+    sync()
+    offs_f, offs_w = offs_f.clone(), offs_w.clone()
+    uf, uw = int(offs_f[-1]), int(offs_w[-1])
+    stored, stored_enh = fine[:uf], whole[:uw]
+
+    def encode():
+        return native.dct_pack_layers_frames(bgr, block, types, mv, fg, bg, e, window=win, base_out=ebase, enh_out=eenh, workspace=ws2)
+
+    wsw = torch.empty(native.window_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    wst, woo = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev)
+
+    def serve():
+        return native.window_levels_frames(stored_enh, offs_w, pw, ph, block, mv, window=win, out=wout, out_offsets=woo, workspace=wsw, status=wst)
+
+    wss = torch.empty(native.split_levels_workspace_bytes(n, n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    sbo, seo = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    sst = torch.empty(n, dtype=torch.int32, device=dev)
+
+    def fixed():
+        return native.split_levels_frames(stored, offs_f, pw, ph, block, mv, e, fg, bg, window=win, base_out=sbase, base_offsets=sbo,
+                                          enh_out=senh, enh_offsets=seo, workspace=wss, status=sst)
+
+    lad, per_frame = _budget(cfg)
+    budget_t = native.budget_tensor(per_frame, n, dev)
+    wsb = torch.empty(native.split_levels_budget_workspace_bytes(n, n, pw, ph, block, mv, len(lad)), dtype=torch.uint8, device=dev)
+    choice = torch.empty(n, dtype=torch.int32, device=dev)
+
+    def budgeted():
+        return native.split_levels_budget_frames(stored, offs_f, pw, ph, block, mv, e, lad, budget_t, window=win, base_out=sbase,
+                                                 base_offsets=sbo, enh_out=senh, enh_offsets=seo, workspace=wsb, status=sst, choice=choice)
+
+    print(f"{cfg.name} batch of {n} at ({fg}, {bg}, {e}), a 256 x 256 window per frame, ms per call (best .. worst of 3 runs of 20 back-to-back "
+          f"calls); stored fine stream {uf / n / 1e6:.3f} MB per frame", flush=True)
+    t_enc = _per_step(encode, sync, steps=20)
+    t_fix = _per_step(fixed, sync, steps=20)
+    t_bud = _per_step(budgeted, sync, steps=20)
+    t_win = _per_step(serve, sync, steps=20)
+    t_enc2 = _per_step(encode, sync, steps=20)  # the encode again, after: the spread of the same call in this run
+    _, offs_eb, _, offs_ee = encode()
+    fixed()
+    sync()
+    assert not sst.any()
+    ub, ue, sb, se = int(offs_eb[-1]), int(offs_ee[-1]), int(sbo[-1]), int(seo[-1])
+    pixels = bgr.numel()
+    masks = n * 8 * 3 * (pw // block) * (ph // block) * (block * block // 64)  # the mask section of the n frames
+    print(f"(a) encode both layers from the pixels {fmt(t_enc)} (again {fmt(t_enc2)}): {hbm(pixels + ub + ue, t_enc)}", flush=True)
+    print(f"(b) split the stored fine stream {fmt(t_fix)} ({t_fix[0] / min(t_enc[0], t_enc2[0]):.3f} of the encode): "
+          f"{hbm(2 * uf + masks + sb + se, t_fix)} (the input pass reads the masks, the count and the write pass the frames), workspace "
+          f"{wss.numel() / n / 1e6:.3f} MB per frame", flush=True)
+    # the ratio 640 is even: the bases differ in the levels the split rounds from a tie; by how much
+    same_size = torch.equal(sbo, offs_eb)
+    print(f"    base from the split {sb / n / 1e6:.4f} MB per frame, from the encoder {ub / n / 1e6:.4f} MB ({(sb - ub) / ub * 100:+.3f} %); "
+          f"offsets {'equal' if same_size else 'differ'}; enhancement {se / n / 1e6:.4f} MB per "
+          f"frame against {ue / n / 1e6:.4f} MB", flush=True)
+    budgeted()
+    sync()
+    assert not sst.any()
+    ch = choice.cpu().numpy().view("uint32")
+    bb, be = int(sbo[-1]), int(seo[-1])
+    print(f"(c) split under a budget of {per_frame} B per frame, {len(lad)} entries {fmt(t_bud)} ({t_bud[0] / t_fix[0]:.2f}x the fixed split): "
+          f"{hbm(3 * uf + masks + bb + be, t_bud)}; choices {[int(c) & 0x7FFFFFFF for c in ch]}, over budget {int((ch >> 31).sum())}, base "
+          f"{bb / n / 1e6:.3f} MB per frame, workspace {wsb.numel() / n / 1e6:.3f} MB per frame", flush=True)
+    serve()
+    sync()
+    print(f"(d) window the stored enhancement {fmt(t_win)}: {hbm(masks + 2 * int(woo[-1]), t_win)} (the masks, the kept levels in and out); stored {uw / n / 1e6:.3f} MB per frame, served "
+          f"{int(woo[-1]) / n / 1e6:.3f} MB per frame", flush=True)
+
+
 def step(cfg, frames_n) -> None:
     dev = torch.device("cuda")
     clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=dev)
@@ -365,5 +468,7 @@ if __name__ == "__main__":
         layers(_cfg(sys.argv, 2))
     elif mode == "window":
         window(_cfg(sys.argv, 2))
+    elif mode == "split":
+        split(_cfg(sys.argv, 2))
     else:
         kernels(_cfg(sys.argv, 2), fused_only=mode == "fused")
