@@ -18,8 +18,9 @@
 // of the worst-case capacity (1024 levels) with the compacted levels and their count -- only the lines touched cost traffic -- and per
 // frame the mask words in the format's own order.  Then
 //   dct_pack_scan_kernel      one workgroup per frame: piece counts -> exclusive prefixes, the frame's level count and size;
-//   dct_pack_assemble_kernel  the frame's offset (the sizes of the frames before it, as the pack's scatter sums them), header, types,
-//                             masks, every piece's levels to levels_off + 2 * prefix, the zero pad, offsets[f + 1].
+//   dct_pack_assemble_kernel  the frame's offset (the sizes of the frames before it: frame_offset_to_lds, which the pack's scatter calls
+//                             too), masks, every piece's levels to levels_off + 2 * prefix (store_level_run), and the frame's edges
+//                             (write_frame_edges: header, types, the zero pad, offsets[f + 1]).
 //
 // Rate control (svc_hip_dct_pack_levels_budget_frames): the rule of the budgeted pack of levels.hip -- per frame the finest pair of a
 // ladder whose frame fits a byte budget -- without its planes.  Two launches in front of the three above:
@@ -65,9 +66,10 @@ struct FrameSteps {
   float fg_inv, bg_inv;
 };
 
-// the budgeted call's part of the workspace, behind the pack's own
+// the budgeted call's workspace: the pack's own, then
 constexpr uint32_t kSumParts = 32;  // workgroups that share the sum of a frame's rows
 struct BudgetWs {
+  DctPackWs pack;
   uint32_t* rows;     // [n][waves of a frame][kMaxLadder]: a wave's coefficients that exactly k + 1 entries keep (the last entry: all)
   uint32_t* parts;    // [n][kSumParts][kMaxLadder]: the rows of a frame summed part by part
   FrameSteps* steps;  // [n]
@@ -93,36 +95,26 @@ PackGeom make_pack_geom(uint32_t w, uint32_t h, uint32_t block, uint32_t mvbw, u
   return g;
 }
 
-uint64_t pack_ws_bytes(uint32_t n, const PackGeom& g) {
-  return 2ull * kPieceLevels * n * g.pieces + (uint64_t)n * up16(4ull * g.mask_dwords) + up16(4ull * n * g.pieces) + 2 * up16(4ull * n);
-}
+// a frame's mask section in the workspace: its dwords, rounded up so that every frame's section starts 16-byte aligned
+__host__ __device__ inline uint64_t ws_mask_pitch(const PackGeom& g) { return up16(4ull * g.mask_dwords) / 4; }
 
-uint64_t budget_ws_bytes(uint32_t n, const PackGeom& g) {
-  return pack_ws_bytes(n, g) + 4ull * kMaxLadder * n * (g.l.tiles_y * g.waves_per_row + kSumParts) + up16(sizeof(FrameSteps) * (uint64_t)n);
-}
-
-BudgetWs carve_budget(uint8_t* p, uint32_t n, const PackGeom& g) {
-  BudgetWs s;
-  p += pack_ws_bytes(n, g);
-  s.rows = reinterpret_cast<uint32_t*>(p);
-  p += 4ull * kMaxLadder * n * g.l.tiles_y * g.waves_per_row;
-  s.parts = reinterpret_cast<uint32_t*>(p);
-  p += 4ull * kMaxLadder * n * kSumParts;
-  s.steps = reinterpret_cast<FrameSteps*>(p);
+// (slots, masks, rows and parts are whole multiples of 16 B as they are: taken without rounding)
+DctPackWs pack_ws(Carver& c, uint32_t n, const PackGeom& g) {
+  DctPackWs s;
+  s.slots = c.take<int16_t>((uint64_t)kPieceLevels * n * g.pieces, false);
+  s.masks = c.take<uint32_t>(n * ws_mask_pitch(g), false);
+  s.counts = c.take<uint32_t>((uint64_t)n * g.pieces);
+  s.frame_bytes = c.take<uint32_t>(n);
+  s.frame_levels = c.take<uint32_t>(n);
   return s;
 }
 
-DctPackWs carve(uint8_t* p, uint32_t n, const PackGeom& g) {
-  DctPackWs s;
-  s.slots = reinterpret_cast<int16_t*>(p);
-  p += 2ull * kPieceLevels * n * g.pieces;
-  s.masks = reinterpret_cast<uint32_t*>(p);
-  p += (uint64_t)n * up16(4ull * g.mask_dwords);
-  s.counts = reinterpret_cast<uint32_t*>(p);
-  p += up16(4ull * n * g.pieces);
-  s.frame_bytes = reinterpret_cast<uint32_t*>(p);
-  p += up16(4ull * n);
-  s.frame_levels = reinterpret_cast<uint32_t*>(p);
+BudgetWs budget_ws(Carver& c, uint32_t n, const PackGeom& g) {
+  BudgetWs s;
+  s.pack = pack_ws(c, n, g);
+  s.rows = c.take<uint32_t>((uint64_t)kMaxLadder * n * g.l.tiles_y * g.waves_per_row, false);
+  s.parts = c.take<uint32_t>((uint64_t)kMaxLadder * n * kSumParts, false);
+  s.steps = c.take<FrameSteps>(n);
   return s;
 }
 
@@ -378,7 +370,7 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
         if (lane == w) mine = mask;
         base += (uint32_t)__popcll(mask);
       }
-      uint32_t* masks = ws.masks + (size_t)frame * (up16(4ull * gm.mask_dwords) / 4) +
+      uint32_t* masks = ws.masks + (size_t)frame * ws_mask_pitch(gm) +
                         2 * ((((size_t)c * gm.l.tiles_y + band) * gm.l.tiles_x) * gm.l.words + word0);
       if (lane < nwords) store_mask(masks + 2 * lane, mine);
       if (lane == 0) ws.counts[piece] = base;
@@ -467,15 +459,7 @@ __global__ __launch_bounds__(256) void dct_pack_scan_kernel(uint32_t pieces, uin
   __shared__ uint32_t red[kThreads / 64];
   const uint32_t f = blockIdx.x;
   uint32_t* cnt = ws.counts + (size_t)f * pieces;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < pieces; base += kThreads) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < pieces ? cnt[i] : 0u;
-    uint32_t total;
-    const uint32_t ex = block_exclusive_scan(v, red, &total);
-    if (i < pieces) cnt[i] = carry + ex;
-    carry += total;
-  }
+  const uint32_t carry = scan_counts(cnt, cnt, pieces, 0, red);
   if (threadIdx.x == 0) {
     ws.frame_levels[f] = carry;
     ws.frame_bytes[f] = (uint32_t)up16(levels_off + 2ull * carry);
@@ -497,57 +481,30 @@ struct AssembleArgs {
 __global__ __launch_bounds__(256) void dct_pack_assemble_kernel(AssembleArgs a) {
   __shared__ uint64_t frame_off;
   const PackGeom& g = a.g;
-  const uint32_t f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (wave == 0) {  // this frame's offset: the sizes of the frames before it
-    uint64_t s = 0;
-    for (uint32_t i = lane; i < f; i += 64) s += a.ws.frame_bytes[i];
-    for (uint32_t off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (lane == 0) frame_off = s;
-  }
+  const uint32_t f = blockIdx.y, wave = threadIdx.x >> 6;
+  frame_offset_to_lds(a.ws.frame_bytes, f, &frame_off);
   __syncthreads();
   uint8_t* frame = a.out + frame_off;
-  const uint32_t level_count = a.ws.frame_levels[f], fbytes = a.ws.frame_bytes[f];
+  const uint32_t level_count = a.ws.frame_levels[f];
 
   // masks: u32 copies (the section is only 4-byte aligned when the MV block count is odd)
-  const uint32_t* msrc = a.ws.masks + (size_t)f * (up16(4ull * g.mask_dwords) / 4);
+  const uint32_t* msrc = a.ws.masks + (size_t)f * ws_mask_pitch(g);
   uint32_t* mdst = reinterpret_cast<uint32_t*>(frame + g.l.masks_off);
   for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < g.mask_dwords; i += gridDim.x * kThreads) mdst[i] = msrc[i];
 
-  // levels: a wave per piece.  The destination is 2-byte aligned (the prefix is any number), so the copy goes by the DESTINATION's
-  // dwords; a dword that two pieces share is written as halves, each piece its own
+  // levels: a wave per piece, a run at a 2-byte aligned place (the prefix is any number)
   const uint32_t* cnt = a.ws.counts + (size_t)f * g.pieces;
   uint16_t* ldst = reinterpret_cast<uint16_t*>(frame + g.l.levels_off);
   for (uint32_t p = blockIdx.x * (kThreads / 64) + wave; p < g.pieces; p += gridDim.x * (kThreads / 64)) {
     const uint32_t prefix = cnt[p], end = p + 1 < g.pieces ? cnt[p + 1] : level_count;
-    if (end == prefix) continue;
-    const uint16_t* src = reinterpret_cast<const uint16_t*>(a.ws.slots + ((size_t)f * g.pieces + p) * kPieceLevels);
-    for (uint32_t d = prefix / 2 + lane; 2 * d < end; d += 64) {
-      const uint32_t e0 = 2 * d, e1 = e0 + 1;  // the dword's two levels, as indices into the frame's levels
-      const bool has0 = e0 >= prefix, has1 = e1 < end;
-      if (has0 && has1) *reinterpret_cast<uint32_t*>(ldst + e0) = (uint32_t)src[e0 - prefix] | ((uint32_t)src[e1 - prefix] << 16);
-      else if (has0) ldst[e0] = src[e0 - prefix];
-      else if (has1) ldst[e1] = src[e1 - prefix];
-    }
+    store_level_run(reinterpret_cast<const uint16_t*>(a.ws.slots + ((size_t)f * g.pieces + p) * kPieceLevels), end - prefix, ldst + prefix);
   }
 
   if (blockIdx.x != 0) return;
   // header (inexact = 0: every level reproduces its quantised coefficient), types, pad, offsets
-  uint32_t* hdr = reinterpret_cast<uint32_t*>(frame);
-  if (threadIdx.x < kHeaderWords) {
-    const uint32_t fg = a.steps ? a.steps[f].fg : a.fg, bg = a.steps ? a.steps[f].bg : a.bg;
-    const uint32_t v[kHeaderWords] = {kMagicQ, kVersion, g.w, g.h, g.n_block, g.n_block, g.mvbw, g.mvbh, fg, bg, level_count, 0,
-                                      fbytes, 0, 0, 0};
-    hdr[threadIdx.x] = v[threadIdx.x];
-  }
-  const uint32_t* types = a.types + (size_t)f * g.l.mvb;
-  uint32_t* tdst = reinterpret_cast<uint32_t*>(frame + kHeaderBytes);
-  for (uint32_t i = threadIdx.x; i < g.l.mvb; i += kThreads) tdst[i] = types[i];
-  const uint64_t used = g.l.levels_off + 2ull * level_count;
-  for (uint64_t i = used + threadIdx.x; i < fbytes; i += kThreads) frame[i] = 0;
-  if (threadIdx.x == 0) {
-    a.offsets[f + 1] = frame_off + fbytes;
-    if (f == 0) a.offsets[0] = 0;
-  }
+  const uint32_t fg = a.steps ? a.steps[f].fg : a.fg, bg = a.steps ? a.steps[f].bg : a.bg;
+  write_frame_edges(frame, FrameHead{g.w, g.h, g.n_block, g.n_block, g.mvbw, g.mvbh, fg, bg, level_count, 0, a.ws.frame_bytes[f]},
+                    a.types + (size_t)f * g.l.mvb, g.l.mvb, g.l.levels_off, kThreads, a.offsets, f, frame_off);
 }
 
 // the format's geometry, then what the fused kernels take: the tuned transform's blocks on whole 16-pixel segments
@@ -610,7 +567,7 @@ uint64_t svc_hip_dct_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t fra
   if (validate_pack_geom("dct_pack_levels_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
   if (validate_pack_limits("dct_pack_levels_workspace_bytes", n_frames, g)) return 0;
-  return pack_ws_bytes(n_frames, g);
+  return layout_bytes(pack_ws, n_frames, g);
 }
 
 // Checked in the order of the SVCQ entry points, whatever n_frames: geometry, steps, limits, sizes, then pointers.
@@ -627,12 +584,8 @@ int svc_hip_dct_pack_levels_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
   // (the pack's int16 bound, 255 * sqrt(tile area) / step <= 32767, holds for every step at 8x8 and 16x16: at most 4080)
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
   if ((rc = validate_pack_limits("dct_pack_levels", n_frames, g))) return rc;
-  const uint64_t ws_need = pack_ws_bytes(n_frames, g);
-  SVC_REQUIRE(workspace_bytes >= ws_need, "dct_pack_levels: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
-  const uint64_t need = n_frames * g.l.max_bytes;
-  SVC_REQUIRE(out_capacity >= need, "dct_pack_levels: output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)out_capacity, (unsigned long long)need);
+  if ((rc = require_workspace("dct_pack_levels", workspace_bytes, layout_bytes(pack_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity("dct_pack_levels", "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
   if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
   SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets, "dct_pack_levels: null pointer");
   SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_block_types, 4),
@@ -648,7 +601,7 @@ int svc_hip_dct_pack_levels_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
   a.bg_step = (float)bg_step;
   a.fg_inv = 1.0f / a.fg_step;
   a.bg_inv = 1.0f / a.bg_step;
-  a.ws = carve(d_workspace, n_frames, g);
+  a.ws = carve(d_workspace, pack_ws, n_frames, g);
   return enqueue_dct_pack("dct_pack_levels", a, n_frames, fg_step, bg_step, d_out, d_frame_offsets, s);
 }
 
@@ -657,7 +610,7 @@ uint64_t svc_hip_dct_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t fra
   if (validate_pack_geom("dct_pack_layers_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
   if (validate_pack_limits("dct_pack_layers_workspace_bytes", n_frames, g)) return 0;
-  return 2 * pack_ws_bytes(n_frames, g);  // a layer's workspace is a multiple of 16 B: the second starts aligned
+  return 2 * layout_bytes(pack_ws, n_frames, g);  // a layer's workspace is a multiple of 16 B: the second starts aligned
 }
 
 // Checked in the order of svc_hip_dct_pack_levels_frames: geometry, stride, steps, the int16 bounds, limits, workspace, both capacities;
@@ -684,14 +637,10 @@ int svc_hip_dct_pack_layers_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
                 std::max(fg_step, bg_step), enh_step);
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
   if ((rc = validate_pack_limits("dct_pack_layers", n_frames, g))) return rc;
-  const uint64_t ws_layer = pack_ws_bytes(n_frames, g), ws_need = 2 * ws_layer;
-  SVC_REQUIRE(workspace_bytes >= ws_need, "dct_pack_layers: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
-  const uint64_t need = n_frames * g.l.max_bytes;
-  SVC_REQUIRE(base_capacity >= need, "dct_pack_layers: base output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)base_capacity, (unsigned long long)need);
-  SVC_REQUIRE(enh_capacity >= need, "dct_pack_layers: enhancement output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)enh_capacity, (unsigned long long)need);
+  const uint64_t ws_layer = layout_bytes(pack_ws, n_frames, g);
+  if ((rc = require_workspace("dct_pack_layers", workspace_bytes, 2 * ws_layer))) return rc;
+  if ((rc = require_capacity("dct_pack_layers", "base output", base_capacity, n_frames * g.l.max_bytes))) return rc;
+  if ((rc = require_capacity("dct_pack_layers", "enhancement output", enh_capacity, n_frames * g.l.max_bytes))) return rc;
   if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
   SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_base_out && d_base_offsets && d_enh_out && d_enh_offsets, "dct_pack_layers: null pointer");
   SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_base_out, 16) && aligned(d_enh_out, 16) && aligned(d_workspace, 16) && aligned(d_base_offsets, 8) &&
@@ -708,14 +657,14 @@ int svc_hip_dct_pack_layers_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
   a.bg_step = (float)bg_step;
   a.fg_inv = 1.0f / a.fg_step;
   a.bg_inv = 1.0f / a.bg_step;
-  a.ws = carve(d_workspace, n_frames, g);
+  a.ws = carve(d_workspace, pack_ws, n_frames, g);
   LayerArgs k{};
   k.enh_step = (float)enh_step;
   k.enh_inv = 1.0f / k.enh_step;
   k.fg_ratio = fg_step / enh_step;
   k.bg_ratio = bg_step / enh_step;
   k.window = d_window;
-  k.enh = carve(d_workspace + ws_layer, n_frames, g);
+  k.enh = carve(d_workspace + ws_layer, pack_ws, n_frames, g);
   const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
   if (block == 8) hipLaunchKernelGGL(dct_pack_layers_kernel<8>, grid, blk, 0, s, a, k);
   else hipLaunchKernelGGL(dct_pack_layers_kernel<16>, grid, blk, 0, s, a, k);
@@ -734,7 +683,7 @@ uint64_t svc_hip_dct_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint3
   }
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
   if (validate_pack_limits(what, n_frames, g)) return 0;
-  return budget_ws_bytes(n_frames, g);
+  return layout_bytes(budget_ws, n_frames, g);
 }
 
 // Checked in the order of svc_hip_dct_pack_levels_frames, the ladder in place of the steps: geometry, stride, ladder, limits, sizes;
@@ -753,12 +702,8 @@ int svc_hip_dct_pack_levels_budget_frames(const uint8_t* d_bgr, uint64_t frame_s
   // (the pack's int16 bound holds for every step at 8x8 and 16x16, as in svc_hip_dct_pack_levels_frames)
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
   if ((rc = validate_pack_limits("dct_pack_levels_budget", n_frames, g))) return rc;
-  const uint64_t ws_need = budget_ws_bytes(n_frames, g);
-  SVC_REQUIRE(workspace_bytes >= ws_need, "dct_pack_levels_budget: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
-  const uint64_t need = n_frames * g.l.max_bytes;
-  SVC_REQUIRE(out_capacity >= need, "dct_pack_levels_budget: output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)out_capacity, (unsigned long long)need);
+  if ((rc = require_workspace("dct_pack_levels_budget", workspace_bytes, layout_bytes(budget_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity("dct_pack_levels_budget", "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
   if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
   SVC_REQUIRE(d_bgr && d_block_types && d_budget && d_workspace && d_out && d_frame_offsets && d_choice,
               "dct_pack_levels_budget: null pointer");
@@ -766,7 +711,7 @@ int svc_hip_dct_pack_levels_budget_frames(const uint8_t* d_bgr, uint64_t frame_s
                   aligned(d_block_types, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
               "dct_pack_levels_budget: frames, output and workspace must be 16-byte aligned, offsets 8-byte, types, budget and choice 4-byte");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const BudgetWs bws = carve_budget(d_workspace, n_frames, g);
+  const BudgetWs bws = carve(d_workspace, budget_ws, n_frames, g);
   DctPackArgs a{};
   a.bgr = d_bgr;
   a.frame_stride = frame_stride_bytes;
@@ -774,7 +719,7 @@ int svc_hip_dct_pack_levels_budget_frames(const uint8_t* d_bgr, uint64_t frame_s
   a.total_waves = n_frames * g.l.tiles_y * g.waves_per_row;
   a.types = d_block_types;
   a.steps = bws.steps;
-  a.ws = carve(d_workspace, n_frames, g);
+  a.ws = bws.pack;
   CountArgs k{make_ladder(ladder, ladder_len), 0, bws.rows};
   while ((ladder_len >> k.probes) != 0) ++k.probes;
   LadderInv li{};

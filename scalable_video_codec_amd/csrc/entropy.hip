@@ -10,12 +10,12 @@
 //   count    one wave per chunk: the popcount of its masks (and mask bits past the tile)
 //   scan     one workgroup per frame: the SVCQ frame's checks -> status; chunk level offsets; the types section's size
 //   lengths  one wave per chunk, one lane per tile: the code lengths for every k, the choice of k and of raw
-//   layout   one workgroup per frame: chunk byte offsets, the frame's size; then one workgroup for the frame offsets
+//   layout   one workgroup per frame: chunk byte offsets, the frame's size; then the frame offsets (levels.hip: enqueue_frame_offsets)
 //   scatter  one wave per chunk: codewords ORed into LDS words, then written out bytewise (coalesced); raw chunks copied
 //   frame    one workgroup per frame: header, types section, index, padding (a failed frame: 64 zero bytes)
 // decode:
 //   check    one workgroup per frame: header and index against each other -> status; chunk byte and level offsets
-//   offsets  one workgroup: SVCQ frame offsets
+//   offsets  one workgroup: SVCQ frame offsets (the same kernel)
 //   chunks   one lane per chunk: serial Exp-Golomb decoding (a chunk is serial by design), every read clamped to the frame
 //   frame    one workgroup per frame: SVCQ header, types, padding, or zeros for a frame that failed
 // fused decode (svc_hip_decode_entropy_frames), without the SVCQ frames:
@@ -75,17 +75,16 @@ struct EncWs {
   uint32_t* fbytes; // [n] SVCE frame bytes
   uint64_t* foff;   // [n + 1] frame offsets
 };
-uint64_t enc_ws_bytes(uint32_t n, const Geom& g) { return 3 * up16(4ull * n * g.chunks) + 4 * up16(4ull * n) + up16(8ull * (n + 1)); }
-EncWs carve_enc(uint8_t* p, uint32_t n, const Geom& g) {
+EncWs enc_ws(Carver& c, uint32_t n, const Geom& g) {
   EncWs s;
-  const uint64_t a = up16(4ull * n * g.chunks), b = up16(4ull * n);
-  s.cnt = reinterpret_cast<uint32_t*>(p);
-  s.info = reinterpret_cast<uint32_t*>(p + a);
-  s.coff = reinterpret_cast<uint32_t*>(p + 2 * a);
-  s.status = reinterpret_cast<uint32_t*>(p + 3 * a);
-  s.types = reinterpret_cast<uint32_t*>(p + 3 * a + b);
-  s.fbytes = reinterpret_cast<uint32_t*>(p + 3 * a + 3 * b);
-  s.foff = reinterpret_cast<uint64_t*>(p + 3 * a + 4 * b);
+  s.cnt = c.take<uint32_t>((uint64_t)n * g.chunks);
+  s.info = c.take<uint32_t>((uint64_t)n * g.chunks);
+  s.coff = c.take<uint32_t>((uint64_t)n * g.chunks);
+  s.status = c.take<uint32_t>(n);
+  s.types = c.take<uint32_t>(n);  // [n][2] in the room of two arrays of n, each rounded up
+  (void)c.take<uint32_t>(n);
+  s.fbytes = c.take<uint32_t>(n);
+  s.foff = c.take<uint64_t>((uint64_t)n + 1);
   return s;
 }
 
@@ -98,19 +97,20 @@ struct DecWs {
   uint32_t* qbytes; // [n] SVCQ frame bytes written (the header's, or 64 for a frame that failed its checks)
   uint64_t* qoff;   // [n + 1]
 };
-uint64_t dec_ws_bytes(uint32_t n, const Geom& g) { return 2 * up16(4ull * n * g.max_chunks) + 4 * up16(4ull * n) + up16(8ull * (n + 1)); }
-DecWs carve_dec(uint8_t* p, uint32_t n, const Geom& g) {
+DecWs dec_ws(Carver& c, uint32_t n, const Geom& g) {
   DecWs s;
-  const uint64_t a = up16(4ull * n * g.max_chunks), b = up16(4ull * n);
-  s.coff = reinterpret_cast<uint32_t*>(p);
-  s.loff = reinterpret_cast<uint32_t*>(p + a);
-  s.status = reinterpret_cast<uint32_t*>(p + 2 * a);
-  s.fail = reinterpret_cast<uint32_t*>(p + 2 * a + b);
-  s.chunks = reinterpret_cast<uint32_t*>(p + 2 * a + 2 * b);
-  s.qbytes = reinterpret_cast<uint32_t*>(p + 2 * a + 3 * b);
-  s.qoff = reinterpret_cast<uint64_t*>(p + 2 * a + 4 * b);
+  s.coff = c.take<uint32_t>((uint64_t)n * g.max_chunks);
+  s.loff = c.take<uint32_t>((uint64_t)n * g.max_chunks);
+  s.status = c.take<uint32_t>(n);
+  s.fail = c.take<uint32_t>(n);
+  s.chunks = c.take<uint32_t>(n);
+  s.qbytes = c.take<uint32_t>(n);
+  s.qoff = c.take<uint64_t>((uint64_t)n + 1);
   return s;
 }
+// what svc_hip_entropy_workspace_bytes reports for both directions, and the fused decode's own: nothing for an empty batch
+uint64_t fused_ws_need(uint32_t n, const Geom& g) { return n ? layout_bytes(dec_ws, n, g) : 0; }
+uint64_t coder_ws_need(uint32_t n, const Geom& g) { return n ? std::max(layout_bytes(enc_ws, n, g), layout_bytes(dec_ws, n, g)) : 0; }
 
 // ---- device helpers -----------------------------------------------------------------------------------------------------------
 
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void enc_count_kernel(EncArgs a) {
     uint32_t row, t0, nt;
     chunk_tiles(g, g.ct, g.cx, c, &row, &t0, &nt);
     if (lane < nt) {
-      const uint8_t* m = a.in + a.in_off[f] + g.masks_off + 8ull * (((uint64_t)row * g.tx + t0 + lane) * g.nw);
+      const uint8_t* m = mask_words(a.in + a.in_off[f] + g.masks_off, row, g.tx, (uint64_t)t0 + lane, g.nw);
       for (uint32_t j = 0; j < g.nw; ++j) {
         const uint64_t w = load_mask(m + 8 * j);
         const uint32_t valid = min(64u, g.area - 64 * j);
@@ -184,6 +184,8 @@ __global__ __launch_bounds__(256) void enc_scan_kernel(EncArgs a) {
   const Geom& g = a.g;
   const uint32_t f = blockIdx.x;
   uint32_t* cnt = a.ws.cnt + (size_t)f * g.chunks;
+  // (scan_counts' loop in its own text, bit 31 masked on the way: through the function this kernel measured 2 % slower,
+  // profiles/stream_blocks_refactor.txt)
   uint32_t carry = 0, stray = 0;
   for (uint32_t base = 0; base < g.chunks; base += kThreads) {
     const uint32_t i = base + threadIdx.x;
@@ -257,6 +259,7 @@ __device__ __forceinline__ TileCtx tile_ctx(const EncArgs& a, uint32_t f, uint32
   TileCtx t;
   chunk_tiles(g, g.ct, g.cx, c, &t.row, &t.t0, &t.nt);
   const uint8_t* frame = a.in + a.in_off[f];
+  // (mask_words' address, written out here and in the scatter's raw copy: through it the two heaviest encoder kernels compile to other code)
   t.masks = frame + g.masks_off + 8ull * (((uint64_t)t.row * g.tx + t.t0 + min(lane, t.nt - 1)) * g.nw);
   const uint32_t mine = lane < t.nt ? tile_levels(g, t.masks) : 0u;
   const uint32_t first = a.ws.cnt[(size_t)f * g.chunks + c] + wave_exclusive_scan(mine);
@@ -319,7 +322,7 @@ __global__ __launch_bounds__(256) void enc_layout_kernel(EncArgs a) {
     return;
   }
   const uint32_t payload = kHeaderBytes + a.ws.types[2 * f] + 4 * g.chunks;
-  uint32_t carry = payload;
+  uint32_t carry = payload;  // (scan_counts' loop in its own text, as in enc_scan_kernel: through the function it measured 1.5 % slower)
   for (uint32_t base = 0; base < g.chunks; base += kThreads) {
     const uint32_t i = base + threadIdx.x;
     const uint32_t v = i < g.chunks ? a.ws.info[(size_t)f * g.chunks + i] & 0xFFFFu : 0u;
@@ -329,40 +332,6 @@ __global__ __launch_bounds__(256) void enc_layout_kernel(EncArgs a) {
     carry += total;
   }
   if (threadIdx.x == 0) a.ws.fbytes[f] = (uint32_t)up16(carry);
-}
-
-// frame offsets of a batch: one workgroup
-__global__ __launch_bounds__(256) void frame_offsets_kernel(const uint32_t* __restrict__ bytes, uint32_t n, uint64_t* __restrict__ ws_off,
-                                                            uint64_t* __restrict__ out_off) {
-  __shared__ uint64_t red[kWaves];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < n; base += kThreads) {
-    const uint32_t i = base + threadIdx.x;
-    const uint64_t v = i < n ? bytes[i] : 0u;
-    uint64_t x = v;
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-      const uint64_t y = __shfl_up(x, off, 64);
-      if (lane >= off) x += y;
-    }
-    if (lane == 63) red[wave] = x;
-    __syncthreads();
-    uint64_t before = 0, sum = 0;
-    for (uint32_t w = 0; w < kWaves; ++w) {
-      if (w < wave) before += red[w];
-      sum += red[w];
-    }
-    __syncthreads();
-    if (i < n) {
-      ws_off[i + 1] = carry + before + x;
-      out_off[i + 1] = carry + before + x;
-    }
-    carry += sum;
-  }
-  if (threadIdx.x == 0) {
-    ws_off[0] = 0;
-    out_off[0] = 0;
-  }
 }
 
 // LDS bit writer: the field's `bits` low bits of v at bit `pos` of the chunk's words (fields never overlap: OR)
@@ -702,7 +671,7 @@ __global__ __launch_bounds__(256) void dec_chunks_kernel(DecArgs a) {
   uint32_t row, t0, nt;
   chunk_tiles(g, ct, cx, c, &row, &t0, &nt);
   uint8_t* q = a.out + a.ws.qoff[f];
-  uint8_t* masks = q + g.masks_off + 8ull * ((uint64_t)row * g.tx + t0) * g.nw;
+  uint8_t* masks = mask_words(q + g.masks_off, row, g.tx, t0, g.nw);
   int16_t* lev = reinterpret_cast<int16_t*>(q + g.levels_off) + lev0;
   bool ok = size != 0;
   if (ok && (frame[start] & 1u)) {  // raw: mask words and levels verbatim
@@ -1066,8 +1035,6 @@ int validate(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, 
   return validate_limits(what, n, w, h, bw, bh, tile_ok ? svce_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)) : 0);
 }
 
-uint64_t ws_bytes(uint32_t n, const Geom& g) { return n ? std::max(enc_ws_bytes(n, g), dec_ws_bytes(n, g)) : 0; }
-
 // the fused decode's geometry (what the reconstruction takes), then the limits with SVCE's worst case
 int validate_fused(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
   const int rc = validate_decode_geom(what, w, h, bw, bh, mvbw, mvbh);
@@ -1091,7 +1058,7 @@ uint64_t svc_hip_entropy_max_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t
 uint64_t svc_hip_entropy_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
                                          uint32_t mv_block_w, uint32_t mv_block_h) {
   if (validate("entropy_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
-  return ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
+  return coder_ws_need(n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
 }
 
 // Checked in the order of the SVCQ entry points, for any n_frames: geometry, limits, sizes, then pointers.
@@ -1102,17 +1069,14 @@ int svc_hip_entropy_encode_frames(const uint8_t* d_svcq, uint64_t svcq_bytes, co
   int rc = validate("entropy_encode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g), "entropy_encode: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g));
-  const uint64_t need = n_frames * svce_max_bytes(g);
-  SVC_REQUIRE(out_capacity >= need, "entropy_encode: output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)out_capacity, (unsigned long long)need);
+  if ((rc = require_workspace("entropy_encode", workspace_bytes, coder_ws_need(n_frames, g)))) return rc;
+  if ((rc = require_capacity("entropy_encode", "output", out_capacity, n_frames * svce_max_bytes(g)))) return rc;
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_svcq && d_svcq_offsets && d_workspace && d_out && d_out_offsets && d_status, "entropy_encode: null pointer");
   SVC_REQUIRE(aligned(d_svcq, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_svcq_offsets, 8) &&
                   aligned(d_out_offsets, 8) && aligned(d_status, 4),
               "entropy_encode: frames, output and workspace must be 16-byte aligned, offsets 8-byte, status 4-byte");
-  const EncArgs a{g, d_svcq, svcq_bytes, d_svcq_offsets, d_out, d_out_offsets, d_status, carve_enc(d_workspace, n_frames, g), n_frames};
+  const EncArgs a{g, d_svcq, svcq_bytes, d_svcq_offsets, d_out, d_out_offsets, d_status, carve(d_workspace, enc_ws, n_frames, g), n_frames};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 chunk_grid(div_up(g.chunks, kWaves), n_frames);
   hipLaunchKernelGGL(enc_count_kernel, chunk_grid, dim3(kThreads), 0, s, a);
@@ -1123,8 +1087,7 @@ int svc_hip_entropy_encode_frames(const uint8_t* d_svcq, uint64_t svcq_bytes, co
   if ((rc = check_launch("entropy_encode lengths"))) return rc;
   hipLaunchKernelGGL(enc_layout_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
   if ((rc = check_launch("entropy_encode layout"))) return rc;
-  hipLaunchKernelGGL(frame_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.fbytes, n_frames, a.ws.foff, d_out_offsets);
-  if ((rc = check_launch("entropy_encode offsets"))) return rc;
+  if ((rc = enqueue_frame_offsets("entropy_encode", 1, OffsetsJob{a.ws.fbytes, a.ws.foff, d_out_offsets}, OffsetsJob{}, n_frames, stream))) return rc;
   const uint32_t lds_words = div_up(g.max_chunk_bytes, 4) + 2;
   hipLaunchKernelGGL(enc_scatter_kernel, chunk_grid, dim3(kThreads), kWaves * lds_words * 4, s, a, lds_words);
   if ((rc = check_launch("entropy_encode scatter"))) return rc;
@@ -1139,8 +1102,7 @@ int svc_hip_entropy_decode_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
   int rc = validate("entropy_decode", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g), "entropy_decode: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g));
+  if ((rc = require_workspace("entropy_decode", workspace_bytes, coder_ws_need(n_frames, g)))) return rc;
   const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
   SVC_REQUIRE(capacity >= need, "entropy_decode: output of %llu B is below the batch's SVCQ worst case of %llu B",
               (unsigned long long)capacity, (unsigned long long)need);
@@ -1149,12 +1111,11 @@ int svc_hip_entropy_decode_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
   SVC_REQUIRE(aligned(d_svce, 16) && aligned(d_svcq_out, 16) && aligned(d_workspace, 16) && aligned(d_offsets, 8) &&
                   aligned(d_svcq_offsets, 8) && aligned(d_status, 4),
               "entropy_decode: frames, output and workspace must be 16-byte aligned, offsets 8-byte, status 4-byte");
-  const DecArgs a{g, d_svce, svce_bytes, d_offsets, d_svcq_out, d_svcq_offsets, d_status, carve_dec(d_workspace, n_frames, g), n_frames};
+  const DecArgs a{g, d_svce, svce_bytes, d_offsets, d_svcq_out, d_svcq_offsets, d_status, carve(d_workspace, dec_ws, n_frames, g), n_frames};
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(dec_check_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
   if ((rc = check_launch("entropy_decode check"))) return rc;
-  hipLaunchKernelGGL(frame_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.qbytes, n_frames, a.ws.qoff, d_svcq_offsets);
-  if ((rc = check_launch("entropy_decode offsets"))) return rc;
+  if ((rc = enqueue_frame_offsets("entropy_decode", 1, OffsetsJob{a.ws.qbytes, a.ws.qoff, d_svcq_offsets}, OffsetsJob{}, n_frames, stream))) return rc;
   hipLaunchKernelGGL(dec_chunks_kernel, dim3(div_up(g.max_chunks, kThreads), n_frames), dim3(kThreads), 0, s, a);
   if ((rc = check_launch("entropy_decode chunks"))) return rc;
   hipLaunchKernelGGL(dec_frame_kernel, dim3(n_frames), dim3(kThreads), 0, s, a);
@@ -1178,7 +1139,7 @@ int svc_hip_entropy_drain(const uint8_t* d_frames, const uint64_t* d_frame_offse
 uint64_t svc_hip_decode_entropy_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
                                                 uint32_t mv_block_w, uint32_t mv_block_h) {
   if (validate_fused("decode_entropy_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
-  return n_frames ? dec_ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) : 0;
+  return fused_ws_need(n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
 }
 
 // Checked in the order of svc_hip_decode_levels_frames, for any n_frames: geometry, steps, display size, limits, workspace, pointers.
@@ -1193,16 +1154,14 @@ int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
   if ((rc = validate_steps_display("decode_entropy", fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   if ((rc = validate_fused("decode_entropy", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  const uint64_t need = n_frames ? dec_ws_bytes(n_frames, g) : 0;
-  SVC_REQUIRE(workspace_bytes >= need, "decode_entropy: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)need);
+  if ((rc = require_workspace("decode_entropy", workspace_bytes, fused_ws_need(n_frames, g)))) return rc;
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_svce && d_offsets && d_workspace && d_rec && d_status, "decode_entropy: null pointer");
   if ((rc = validate_display_buffer("decode_entropy", display, d_display))) return rc;
   SVC_REQUIRE(aligned(d_svce, 16) && aligned(d_workspace, 16) && aligned(d_offsets, 8) && aligned(d_rec, 4) && aligned(d_status, 4) &&
                   aligned(d_gaze, 4),
               "decode_entropy: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
-  const DecWs ws = carve_dec(d_workspace, n_frames, g);
+  const DecWs ws = carve(d_workspace, dec_ws, n_frames, g);
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the header, types and index checks and the index scan of svc_hip_entropy_decode_frames (it writes no output)
   const DecArgs c{g, d_svce, svce_bytes, d_offsets, nullptr, nullptr, nullptr, ws, n_frames};

@@ -2,15 +2,18 @@
 //
 // Quantised planes are almost all zeros (a C3 background tile-channel holds about one non-zero level), so a frame is sent as
 // a significance mask per tile plus the non-zero levels as int16 -- about 1 MB instead of the 25 MB of f32 planes at 1080p.
-// stream_format.hpp states the frame's layout, its header and the check of a frame; include/svc_hip.h has the table.
+// stream_format.hpp states the frame's layout, its header and the check of a frame, and the steps this file shares with dct_pack.hip and
+// entropy.hip: a workspace as one layout function (Carver), scan_counts, frame_offset_to_lds, write_frame_edges, store_level_run,
+// mask_words.  include/svc_hip.h has the table.
 //
 // Work split, pack and unpack alike: a workgroup owns a GROUP = one plane, one tile row, up to `tpg` adjacent tiles (about 2048
 // coefficients).  It stages the group's rows in LDS with 16-byte loads (the planes are row-major: one 8x8 tile per wave would
 // read 32-byte pieces), then one wave per 64-coefficient mask word: the word is a __ballot, a lane's rank among the non-zero
 // levels is mbcnt + the popcounts of the earlier words.  The only variable-size section is the levels, so each direction is
 //   count   (per group: non-zero levels)  ->  scan (per frame: exclusive scan of the group sums, frame size)  ->  scatter.
-// The frame offsets are not scanned by a kernel of their own: the scatter's workgroup sums the frame sizes before its own
-// frame (a batch is a few dozen frames).  Group order = (plane, tile row, group in the row) = the order of the levels.
+// The pack's frame offsets are not scanned by a kernel of their own: the scatter's workgroup sums the frame sizes before its own
+// frame (a batch is a few dozen frames).  The window call, the split and entropy.hip, whose frame sizes come from a kernel of their own,
+// share frame_offsets_kernel (enqueue_frame_offsets).  Group order = (plane, tile row, group in the row) = the order of the levels.
 //
 // budgeted pack (rate control): a count per ladder entry, a per-frame choice of steps from a byte budget, then the pack's count,
 // scan and scatter with each frame's chosen steps.
@@ -81,18 +84,14 @@ uint32_t lds_bytes(const Geom& g) {
 struct Ws {
   uint32_t *cnt, *inexact, *frame_bytes, *frame_levels, *frame_inexact, *status;
 };
-uint64_t ws_bytes(uint32_t n, uint32_t groups) {
-  return 2 * up16(4ull * n * groups) + 4 * up16(4ull * n);
-}
-Ws carve(uint8_t* p, uint32_t n, uint32_t groups) {
+Ws stream_ws(Carver& c, uint32_t n, uint32_t groups) {
   Ws s;
-  const uint64_t a = up16(4ull * n * groups), b = up16(4ull * n);
-  s.cnt = reinterpret_cast<uint32_t*>(p);
-  s.inexact = reinterpret_cast<uint32_t*>(p + a);
-  s.frame_bytes = reinterpret_cast<uint32_t*>(p + 2 * a);
-  s.frame_levels = reinterpret_cast<uint32_t*>(p + 2 * a + b);
-  s.frame_inexact = reinterpret_cast<uint32_t*>(p + 2 * a + 2 * b);
-  s.status = reinterpret_cast<uint32_t*>(p + 2 * a + 3 * b);
+  s.cnt = c.take<uint32_t>((uint64_t)n * groups);
+  s.inexact = c.take<uint32_t>((uint64_t)n * groups);
+  s.frame_bytes = c.take<uint32_t>(n);
+  s.frame_levels = c.take<uint32_t>(n);
+  s.frame_inexact = c.take<uint32_t>(n);
+  s.status = c.take<uint32_t>(n);
   return s;
 }
 
@@ -115,6 +114,19 @@ __device__ __forceinline__ Group group_of(const Geom& g, uint32_t gi) {
   r.cols = r.nt * g.bw;
   r.pitch = r.cols + ((g.pitch_pad - r.cols) & 63u);
   return r;
+}
+
+// the group's first mask word in `plane` (the group's own, or the same tiles of another) of the frame at `frame`, as dwords; a group's
+// words are contiguous: [plane][ty][t0 .. t0 + nt)[words]
+template <typename B>  // uint8_t or const uint8_t
+__device__ __forceinline__ auto group_masks(const Geom& g, B* frame, uint32_t plane, const Group& gr) {
+  using W = std::conditional_t<std::is_const_v<B>, const uint32_t, uint32_t>;
+  return mask_words(reinterpret_cast<W*>(frame + g.masks_off), (uint64_t)plane * g.tiles_y + gr.ty, g.tiles_x, gr.t0, g.words);
+}
+
+// the header of a frame of geometry g
+__device__ __forceinline__ FrameHead head_of(const Geom& g, uint32_t fg, uint32_t bg, uint32_t levels, uint32_t inexact, uint32_t bytes) {
+  return FrameHead{g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh, fg, bg, levels, inexact, bytes};
 }
 
 // the group's bh rows x cols floats of plane p -> LDS (row pitch gr.pitch)
@@ -203,12 +215,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   const uint32_t* types = a.types + (size_t)f * g.mvb;
   const uint32_t fg = a.steps ? a.steps[2 * f] : a.fg, bg = a.steps ? a.steps[2 * f + 1] : a.bg;
   stage_rows(g, gr, a.planes + ((size_t)f * 3 + gr.plane) * g.h * g.w, lds);
-  if (SCATTER && wave == 0) {  // this frame's offset: the sizes of the frames before it
-    uint64_t s = 0;
-    for (uint32_t i = lane; i < f; i += 64) s += a.ws.frame_bytes[i];
-    for (uint32_t off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (lane == 0) frame_off = s;
-  }
+  if (SCATTER) frame_offset_to_lds(a.ws.frame_bytes, f, &frame_off);
   __syncthreads();
 
   const uint32_t area = g.bw * g.bh, jobs = gr.nt * g.words;
@@ -251,9 +258,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   __syncthreads();
   uint8_t* frame = a.out + frame_off;
   int16_t* levels = reinterpret_cast<int16_t*>(frame + g.levels_off) + a.ws.cnt[(size_t)f * g.groups + gi];
-  // the mask words of the group are contiguous: [plane][ty][t0 .. t0 + nt)[words]
-  uint32_t* masks = reinterpret_cast<uint32_t*>(frame + g.masks_off) +
-                    2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+  uint32_t* masks = group_masks(g, frame, gr.plane, gr);
   for (uint32_t j = threadIdx.x; j < jobs; j += kThreads) {  // two u32 stores: the masks are 4-byte aligned when mvb is odd
     masks[2 * j] = (uint32_t)job_mask[j];
     masks[2 * j + 1] = (uint32_t)(job_mask[j] >> 32);
@@ -267,21 +272,8 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   }
   if (gi != 0) return;
   // group 0: header, types, pad, offsets
-  const uint32_t level_count = a.ws.frame_levels[f], fbytes = a.ws.frame_bytes[f];
-  uint32_t* hdr = reinterpret_cast<uint32_t*>(frame);
-  if (threadIdx.x < 16) {
-    const uint32_t v[kHeaderWords] = {kMagicQ, kVersion, g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh, fg, bg, level_count, a.ws.frame_inexact[f],
-                            fbytes, 0, 0, 0};
-    hdr[threadIdx.x] = v[threadIdx.x];
-  }
-  uint32_t* tdst = reinterpret_cast<uint32_t*>(frame + kHeaderBytes);
-  for (uint32_t i = threadIdx.x; i < g.mvb; i += kThreads) tdst[i] = types[i];
-  const uint64_t used = g.levels_off + 2ull * level_count;
-  for (uint64_t i = used + threadIdx.x; i < fbytes; i += kThreads) frame[i] = 0;
-  if (threadIdx.x == 0) {
-    a.offsets[f + 1] = frame_off + fbytes;
-    if (f == 0) a.offsets[0] = 0;
-  }
+  write_frame_edges(frame, head_of(g, fg, bg, a.ws.frame_levels[f], a.ws.frame_inexact[f], a.ws.frame_bytes[f]), types, g.mvb, g.levels_off,
+                    kThreads, a.offsets, f, frame_off);
 }
 
 // one workgroup per frame: group counts -> exclusive prefixes (in place), the frame's level count, inexact count and size.
@@ -292,17 +284,9 @@ __global__ __launch_bounds__(256) void scan_kernel(Geom g, Ws ws, const uint8_t*
   __shared__ uint32_t red[kThreads / 64];
   const uint32_t f = blockIdx.x;
   uint32_t* cnt = ws.cnt + (size_t)f * g.groups;
-  uint32_t carry = 0, inexact = 0;
-  for (uint32_t base = 0; base < g.groups; base += kThreads) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < g.groups ? cnt[i] : 0u;
-    if (i < g.groups) inexact += ws.inexact[(size_t)f * g.groups + i];
-    uint32_t total;
-    const uint32_t ex = block_exclusive_scan(v, red, &total);
-    if (i < g.groups) cnt[i] = carry + ex;
-    carry += total;
-  }
-  uint32_t t;
+  uint32_t inexact = 0, t;  // summed on the scan's way: its loads go out with the counts'
+  const uint32_t carry = scan_counts(g.groups, 0, red, [&](uint32_t i) { inexact += ws.inexact[(size_t)f * g.groups + i]; return cnt[i]; },
+                                     [&](uint32_t i, uint32_t v) { cnt[i] = v; });
   (void)block_exclusive_scan(inexact, red, &t);  // pack: inexact coefficients; unpack: mask bits past the tile area
   if (!UNPACK) {
     if (threadIdx.x == 0) {
@@ -334,18 +318,12 @@ struct BudgetWs {
   uint32_t *nz, *steps;
   uint64_t* bytes;
 };
-uint64_t budget_ws_bytes(uint32_t n, uint32_t groups, uint32_t len) {
-  return ws_bytes(n, groups) + up16(4ull * n * len * groups) + up16(8ull * n * len) + up16(8ull * n);
-}
-BudgetWs carve_budget(uint8_t* p, uint32_t n, uint32_t groups, uint32_t len) {
+BudgetWs budget_ws(Carver& c, uint32_t n, uint32_t groups, uint32_t len) {
   BudgetWs s;
-  s.pack = carve(p, n, groups);
-  uint8_t* q = p + ws_bytes(n, groups);
-  s.nz = reinterpret_cast<uint32_t*>(q);
-  q += up16(4ull * n * len * groups);
-  s.bytes = reinterpret_cast<uint64_t*>(q);
-  q += up16(8ull * n * len);
-  s.steps = reinterpret_cast<uint32_t*>(q);
+  s.pack = stream_ws(c, n, groups);
+  s.nz = c.take<uint32_t>((uint64_t)n * len * groups);
+  s.bytes = c.take<uint64_t>((uint64_t)n * len);
+  s.steps = c.take<uint32_t>(2ull * n);
   return s;
 }
 
@@ -442,8 +420,7 @@ __global__ __launch_bounds__(256) void unpack_kernel(UnpackArgs a) {
   if (SCATTER) off = a.offsets[f], hdr = reinterpret_cast<const uint32_t*>(a.in + off);
   const uint8_t* frame = a.in + off;
   const uint32_t jobs = gr.nt * g.words;
-  const uint32_t* masks = st != kStOk ? nullptr :
-      reinterpret_cast<const uint32_t*>(frame + g.masks_off) + 2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+  const uint32_t* masks = st != kStOk ? nullptr : group_masks(g, frame, gr.plane, gr);
   const uint32_t j = threadIdx.x;
   const uint64_t m = (masks && j < jobs) ? load_mask(masks + 2 * j) : 0ull;
   const uint32_t area = g.bw * g.bh;
@@ -578,6 +555,7 @@ __device__ __forceinline__ void decode_body(const std::conditional_t<ENH, Decode
   float out[3][N];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
+    // (the index, for both frames: with two calls of group_masks the layered form compiles to other code, profiles/stream_blocks_refactor.txt)
     const size_t word0 = 2 * ((((size_t)c * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
     const uint32_t* masks = st != kStOk ? nullptr : reinterpret_cast<const uint32_t*>(frame + g.masks_off) + word0;
     const uint64_t m = (masks && tid < jobs) ? load_mask(masks + 2 * tid) : 0ull;
@@ -654,18 +632,14 @@ struct WinWs {
   uint32_t* kept;                  // [n][groups + 1]: becomes D, entry `groups` = the frame's kept levels
   uint32_t *frame_bytes, *status;  // [n]
 };
-uint64_t win_ws_bytes(uint32_t n, uint32_t groups) {
-  return 3 * up16(4ull * n * groups) + up16(4ull * n * (groups + 1)) + 2 * up16(4ull * n);
-}
-WinWs carve_window(uint8_t* p, uint32_t n, uint32_t groups) {
+WinWs window_ws(Carver& c, uint32_t n, uint32_t groups) {
   WinWs s;
-  const uint64_t a = up16(4ull * n * groups), b = up16(4ull * n * (groups + 1)), c = up16(4ull * n);
-  s.tot = reinterpret_cast<uint32_t*>(p);
-  s.before = reinterpret_cast<uint32_t*>(p + a);
-  s.stray = reinterpret_cast<uint32_t*>(p + 2 * a);
-  s.kept = reinterpret_cast<uint32_t*>(p + 3 * a);
-  s.frame_bytes = reinterpret_cast<uint32_t*>(p + 3 * a + b);
-  s.status = reinterpret_cast<uint32_t*>(p + 3 * a + b + c);
+  s.tot = c.take<uint32_t>((uint64_t)n * groups);
+  s.before = c.take<uint32_t>((uint64_t)n * groups);
+  s.stray = c.take<uint32_t>((uint64_t)n * groups);
+  s.kept = c.take<uint32_t>((uint64_t)n * (groups + 1));
+  s.frame_bytes = c.take<uint32_t>(n);
+  s.status = c.take<uint32_t>(n);
   return s;
 }
 
@@ -704,8 +678,7 @@ __global__ __launch_bounds__(256) void window_count_kernel(WindowArgs a) {
   const uint32_t* hdr = nullptr;
   uint32_t tot = 0, kept = 0, before = 0, stray = 0;  // a frame that fails its checks counts nothing: its masks are not read
   if (window_source(a, i, &off, &hdr) == kStOk) {
-    const uint32_t* masks = reinterpret_cast<const uint32_t*>(a.in + off + g.masks_off) +
-                            2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+    const uint32_t* masks = group_masks(g, a.in + off, gr.plane, gr);
     const uint32_t jobs = gr.nt * g.words, area = g.bw * g.bh;
     const uint32_t wx = a.window ? a.window[4ull * i] : 0u;
     for (uint32_t j = lane; j < jobs; j += 64) {
@@ -738,22 +711,11 @@ __global__ __launch_bounds__(256) void window_scan_kernel(WindowArgs a) {
   const uint32_t* strays = a.ws.stray + (size_t)i * g.groups;
   uint32_t* kept = a.ws.kept + (size_t)i * (g.groups + 1);
   uint32_t* run = a.ws.before + (size_t)i * g.groups;
-  uint32_t carry_tot = 0, carry_kept = 0, stray = 0;
-  for (uint32_t base = 0; base < g.groups; base += kThreads) {
-    const uint32_t k = base + threadIdx.x;
-    const bool live = k < g.groups;
-    if (live) stray += strays[k];
-    uint32_t sum_tot, sum_kept;
-    const uint32_t ex_tot = block_exclusive_scan(live ? tot[k] : 0u, red, &sum_tot);
-    const uint32_t ex_kept = block_exclusive_scan(live ? kept[k] : 0u, red, &sum_kept);
-    if (live) {
-      run[k] += carry_tot + ex_tot;  // S: the levels before the group, then those of its tiles left of the window
-      kept[k] = carry_kept + ex_kept;
-    }
-    carry_tot += sum_tot;
-    carry_kept += sum_kept;
-  }
-  uint32_t stray_bits;
+  // S: the levels before the group, then those of its tiles left of the window
+  uint32_t stray = 0, stray_bits;  // summed on the first scan's way
+  const uint32_t carry_tot = scan_counts(g.groups, 0, red, [&](uint32_t k) { stray += strays[k]; return tot[k]; },
+                                         [&](uint32_t k, uint32_t v) { run[k] += v; });
+  const uint32_t carry_kept = scan_counts(kept, kept, g.groups, 0, red);
   (void)block_exclusive_scan(stray, red, &stray_bits);
   if (threadIdx.x == 0) {
     kept[g.groups] = carry_kept;
@@ -768,12 +730,14 @@ __global__ __launch_bounds__(256) void window_scan_kernel(WindowArgs a) {
   }
 }
 
-// one workgroup per stream (the window call has one, the split its two layers): offsets[0 .. n] from the frames' sizes
-__global__ __launch_bounds__(256) void window_offsets_kernel(const uint32_t* __restrict__ bytes0, uint64_t* __restrict__ offsets0,
-                                                             const uint32_t* __restrict__ bytes1, uint64_t* __restrict__ offsets1, uint32_t n) {
+// The batch's frame offsets, for every call whose frames' sizes come from a kernel of their own (enqueue_frame_offsets: the window
+// call and the entropy coder have one job, the split a job per layer).  One workgroup per job: a 64-bit inclusive scan of bytes[0 .. n).
+__global__ __launch_bounds__(256) void frame_offsets_kernel(OffsetsJob job0, OffsetsJob job1, uint32_t n) {
   __shared__ uint64_t red[kThreads / 64];
-  const uint32_t* __restrict__ bytes = blockIdx.x ? bytes1 : bytes0;
-  uint64_t* __restrict__ offsets = blockIdx.x ? offsets1 : offsets0;
+  const OffsetsJob& job = blockIdx.x ? job1 : job0;
+  const uint32_t* __restrict__ bytes = job.bytes;
+  uint64_t* __restrict__ offsets = job.offsets;
+  uint64_t* __restrict__ copy = job.copy;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint64_t carry = 0;
   for (uint32_t base = 0; base < n; base += kThreads) {
@@ -791,10 +755,16 @@ __global__ __launch_bounds__(256) void window_offsets_kernel(const uint32_t* __r
       sum += red[w];
     }
     __syncthreads();
-    if (k < n) offsets[k + 1] = carry + before + x;
+    if (k < n) {
+      offsets[k + 1] = carry + before + x;
+      if (copy) copy[k + 1] = carry + before + x;
+    }
     carry += sum;
   }
-  if (threadIdx.x == 0) offsets[0] = 0;
+  if (threadIdx.x == 0) {
+    offsets[0] = 0;
+    if (copy) copy[0] = 0;
+  }
 }
 
 // the run that holds kept level e: the last r in [lo, groups) with D[r] <= e (D[lo] <= e < D[groups])
@@ -809,9 +779,11 @@ __device__ __forceinline__ uint32_t run_of(const uint32_t* __restrict__ D, uint3
 }
 
 // dword wb (< levels_off / 4) of output frame i, from the input frame's dword v at the same place
-__device__ __forceinline__ uint32_t window_word(const WindowArgs& a, uint32_t i, uint32_t wb, uint32_t v, uint32_t kept, uint32_t fbytes) {
+__device__ __forceinline__ uint32_t window_word(const WindowArgs& a, uint32_t i, const uint32_t* src, uint32_t wb, uint32_t v,
+                                                uint32_t kept, uint32_t fbytes) {
   const Geom& g = a.g;
-  if (wb < kHeaderWords) return wb == kHLevels ? kept : wb == kHBytes ? fbytes : wb >= kQReserved ? 0u : v;
+  // the header of a frame with the input's steps and inexact count (its geometry is g: the input frame passed check_svcq with it)
+  if (wb < kHeaderWords) return header_word(head_of(g, src[kHFgStep], src[kHBgStep], kept, src[kHInexact], fbytes), wb);
   const uint32_t mw = (uint32_t)(g.masks_off / 4);
   if (wb < mw || !a.window) return v;
   const uint32_t tile = (wb - mw) / (2 * g.words), row = tile / g.tiles_x;  // row = plane * tiles_y + tile row
@@ -841,10 +813,10 @@ __global__ __launch_bounds__(256) void window_write_kernel(WindowArgs a) {
     uint32_t o[4];
     if (w0 + 4 <= lw) {  // header, types, masks
       const uint4 x = *reinterpret_cast<const uint4*>(frame + 16ull * v);
-      o[0] = window_word(a, i, w0, x.x, kept, fbytes);
-      o[1] = window_word(a, i, w0 + 1, x.y, kept, fbytes);
-      o[2] = window_word(a, i, w0 + 2, x.z, kept, fbytes);
-      o[3] = window_word(a, i, w0 + 3, x.w, kept, fbytes);
+      o[0] = window_word(a, i, src32, w0, x.x, kept, fbytes);
+      o[1] = window_word(a, i, src32, w0 + 1, x.y, kept, fbytes);
+      o[2] = window_word(a, i, src32, w0 + 2, x.z, kept, fbytes);
+      o[3] = window_word(a, i, src32, w0 + 3, x.w, kept, fbytes);
     } else {
       const uint32_t e0 = w0 >= lw ? 2 * (w0 - lw) : 0u;  // the vector's first level
       uint32_t r = 0, rend = 0;                           // a run and its end: D[r] <= e < rend for the levels e taken from it
@@ -869,7 +841,7 @@ __global__ __launch_bounds__(256) void window_write_kernel(WindowArgs a) {
         for (uint32_t k = 0; k < 4; ++k) {
           const uint32_t wb = w0 + k;
           if (wb < lw) {
-            o[k] = window_word(a, i, wb, src32[wb], kept, fbytes);
+            o[k] = window_word(a, i, src32, wb, src32[wb], kept, fbytes);
             continue;
           }
           uint32_t half[2];
@@ -904,7 +876,7 @@ __global__ __launch_bounds__(256) void window_write_kernel(WindowArgs a) {
 //   count    one wave per group: the non-zero levels of both layers
 //   scan     one workgroup per frame: both layers' prefixes, level counts and sizes, the final status (kStLayer for a header step that
 //            is not e)
-//   offsets  window_offsets_kernel, a workgroup per layer
+//   offsets  frame_offsets_kernel, a workgroup per layer
 //   write    one wave per group: both layers' mask words (a lane per word, 8 bytes each) and levels.  The levels are compacted in LDS
 //            and stored as aligned dwords; a run that starts or ends at an odd level shares that dword with its neighbour's run and
 //            stores its half of it as 16 bits.  The first workgroup of a frame also writes both headers, types and paddings.  Every
@@ -920,20 +892,15 @@ struct SplitWs {
   uint32_t* steps;         // [n][2] fg, bg of each frame (the budgeted form)
   uint32_t* nz;            // [n][len][groups] (the budgeted form)
 };
-uint64_t split_ws_bytes(uint32_t n, uint32_t groups, uint32_t len) {
-  return win_ws_bytes(n, groups) + 2 * up16(4ull * n * groups) + 3 * up16(8ull * n) + up16(4ull * n * len * groups);
-}
-SplitWs carve_split(uint8_t* p, uint32_t n, uint32_t groups) {
+SplitWs split_ws(Carver& c, uint32_t n, uint32_t groups, uint32_t len) {  // len = 0: the fixed call, no nz
   SplitWs s;
-  s.in = carve_window(p, n, groups);
-  p += win_ws_bytes(n, groups);
-  const uint64_t a = up16(4ull * n * groups), b = up16(8ull * n);
-  s.nzb = reinterpret_cast<uint32_t*>(p);
-  s.nze = reinterpret_cast<uint32_t*>(p + a);
-  s.frame_bytes = reinterpret_cast<uint32_t*>(p + 2 * a);
-  s.frame_levels = reinterpret_cast<uint32_t*>(p + 2 * a + b);
-  s.steps = reinterpret_cast<uint32_t*>(p + 2 * a + 2 * b);
-  s.nz = reinterpret_cast<uint32_t*>(p + 2 * a + 3 * b);
+  s.in = window_ws(c, n, groups);
+  s.nzb = c.take<uint32_t>((uint64_t)n * groups);
+  s.nze = c.take<uint32_t>((uint64_t)n * groups);
+  s.frame_bytes = c.take<uint32_t>(2ull * n);
+  s.frame_levels = c.take<uint32_t>(2ull * n);
+  s.steps = c.take<uint32_t>(2ull * n);
+  s.nz = c.take<uint32_t>((uint64_t)n * len * groups);
   return s;
 }
 
@@ -991,8 +958,7 @@ template <typename F>
 __device__ __forceinline__ void split_walk(const SplitArgs& a, uint32_t i, const Group& gr, const uint8_t* frame, uint32_t s, F&& fn) {
   const Geom& g = a.g;
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t* masks = reinterpret_cast<const uint32_t*>(frame + g.masks_off) +
-                          2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
+  const uint32_t* masks = group_masks(g, frame, gr.plane, gr);
   const uint32_t* types = reinterpret_cast<const uint32_t*>(frame + kHeaderBytes);
   const int16_t* lv = reinterpret_cast<const int16_t*>(frame + g.levels_off) + s;
   const uint32_t jobs = gr.nt * g.words;
@@ -1064,6 +1030,8 @@ __global__ __launch_bounds__(256) void split_scan_kernel(SplitArgs a) {
   const uint32_t i = blockIdx.x;
   uint32_t* nzb = a.ws.nzb + (size_t)i * g.groups;
   uint32_t* nze = a.ws.nze + (size_t)i * g.groups;
+  // (scan_counts' loop in its own text, both layers in one trip: as two calls this kernel measured 2.3 % slower,
+  // profiles/stream_blocks_refactor.txt)
   uint32_t carry_b = 0, carry_e = 0;
   for (uint32_t base = 0; base < g.groups; base += kThreads) {
     const uint32_t k = base + threadIdx.x;
@@ -1090,30 +1058,13 @@ __global__ __launch_bounds__(256) void split_scan_kernel(SplitArgs a) {
   }
 }
 
-// the wave's cnt levels from LDS to dst, a 2-byte aligned place in the output: aligned dwords, and 16 bits at an odd end
-__device__ __forceinline__ void split_store_levels(const uint16_t* buf, uint32_t cnt, uint16_t* dst) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t head = cnt != 0 && (reinterpret_cast<uintptr_t>(dst) & 2u) ? 1u : 0u, body = (cnt - head) / 2;
-  if (head && lane == 0) dst[0] = buf[0];
-  uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + head);
-  for (uint32_t k = lane; k < body; k += 64) d32[k] = (uint32_t)buf[head + 2 * k] | ((uint32_t)buf[head + 2 * k + 1] << 16);
-  if (((cnt - head) & 1u) && lane == 0) dst[cnt - 1] = buf[cnt - 1];
-}
-
-// what the first workgroup of output frame i writes of one layer: the header (words 0 .. 7 and 11 of the input's), the types, the padding
+// what the first workgroup of output frame i writes of one layer: the header (the geometry is the input frame's: it passed check_svcq
+// with g; the inexact count is the input's too), the input's types, the padding.  The frame offsets are the offsets kernel's.
 __device__ __forceinline__ void split_frame_edges(const Geom& g, const uint8_t* frame, uint8_t* out, uint32_t fg, uint32_t bg,
                                                   uint32_t level_count, uint32_t fbytes) {
   const uint32_t* src = reinterpret_cast<const uint32_t*>(frame);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(out);
-  const uint32_t head = kHeaderWords + g.mvb;
-  for (uint32_t k = threadIdx.x; k < head; k += blockDim.x) {
-    const uint32_t v = src[k];
-    dst[k] = k == kHFgStep ? fg : k == kHBgStep ? bg : k == kHLevels ? level_count : k == kHBytes ? fbytes :
-             (k >= kQReserved && k < kHeaderWords) ? 0u : v;
-  }
-  uint16_t* pad = reinterpret_cast<uint16_t*>(out + g.levels_off) + level_count;
-  const uint32_t npad = (uint32_t)(fbytes - (g.levels_off + 2ull * level_count)) / 2;  // at most 7: the levels end at an even byte
-  if (threadIdx.x < npad) pad[threadIdx.x] = 0;
+  write_frame_edges(out, head_of(g, fg, bg, level_count, src[kHInexact], fbytes), src + kHeaderWords, g.mvb, g.levels_off, blockDim.x,
+                    nullptr, 0, 0);
 }
 
 // The write pass's waves per workgroup and its dynamic LDS: per wave the group's coefficients as u16, twice (base, enhancement).  A
@@ -1146,9 +1097,8 @@ __global__ __launch_bounds__(256) void split_write_kernel(SplitArgs a, uint32_t 
   uint32_t cnt_b = 0, cnt_e = 0;
   if (live) {
     const Group gr = group_of(g, gi);
-    const size_t word0 = 2 * ((((size_t)gr.plane * g.tiles_y + gr.ty) * g.tiles_x + gr.t0) * g.words);
-    uint32_t* masks_b = reinterpret_cast<uint32_t*>(base + g.masks_off) + word0;
-    uint32_t* masks_e = enh ? reinterpret_cast<uint32_t*>(enh + g.masks_off) + word0 : nullptr;
+    uint32_t* masks_b = group_masks(g, base, gr.plane, gr);
+    uint32_t* masks_e = enh ? group_masks(g, enh, gr.plane, gr) : nullptr;
     const uint32_t jobs = gr.nt * g.words;
     uint64_t keep_b = 0, keep_e = 0;  // lane l: the new masks of word (j & ~63) + l, stored 64 words at a time
     split_walk(a, i, gr, frame, a.ws.in.before[(size_t)i * g.groups + gi], [&](uint32_t j, uint32_t c, bool win, int32_t lf) {
@@ -1175,8 +1125,8 @@ __global__ __launch_bounds__(256) void split_write_kernel(SplitArgs a, uint32_t 
   }
   __syncthreads();
   if (live) {
-    split_store_levels(buf_b, cnt_b, reinterpret_cast<uint16_t*>(base + g.levels_off) + a.ws.nzb[(size_t)i * g.groups + gi]);
-    if (enh) split_store_levels(buf_e, cnt_e, reinterpret_cast<uint16_t*>(enh + g.levels_off) + a.ws.nze[(size_t)i * g.groups + gi]);
+    store_level_run(buf_b, cnt_b, reinterpret_cast<uint16_t*>(base + g.levels_off) + a.ws.nzb[(size_t)i * g.groups + gi]);
+    if (enh) store_level_run(buf_e, cnt_e, reinterpret_cast<uint16_t*>(enh + g.levels_off) + a.ws.nze[(size_t)i * g.groups + gi]);
   }
   if (blockIdx.x != 0) return;
   split_frame_edges(g, frame, base, sr.fg, sr.bg, a.ws.frame_levels[i], a.ws.frame_bytes[i]);
@@ -1294,15 +1244,11 @@ int split_levels(const char* what, SplitArgs a, const svc_step_pair* ladder, uin
   SVC_REQUIRE(a.src || a.n_out == a.n_in, "%s: without d_src output frame i is input frame i, but n_out is %u and n_in %u", what, a.n_out,
               a.n_in);
   a.g = make_geom(g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh);
-  const uint64_t ws_need = split_ws_bytes(a.n_out, g.groups, ladder ? ladder_len : 0);
-  SVC_REQUIRE(workspace_bytes >= ws_need, "%s: workspace of %llu B is smaller than the %llu B needed", what,
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
+  const uint32_t len = ladder ? ladder_len : 0;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(split_ws, a.n_out, g.groups, len)))) return rc;
   const uint64_t max_bytes = frame_layout(g.w, g.h, g.bw, g.bh, g.mvbw, g.mvbh).max_bytes;
-  SVC_REQUIRE(base_capacity >= a.n_out * max_bytes, "%s: base output of %llu B is below the batch's worst case of %llu B", what,
-              (unsigned long long)base_capacity, (unsigned long long)(a.n_out * max_bytes));
-  SVC_REQUIRE(!a.enh || enh_capacity >= a.n_out * max_bytes,
-              "%s: enhancement output of %llu B is below the batch's worst case of %llu B", what, (unsigned long long)enh_capacity,
-              (unsigned long long)(a.n_out * max_bytes));
+  if ((rc = require_capacity(what, "base output", base_capacity, a.n_out * max_bytes))) return rc;
+  if (a.enh && (rc = require_capacity(what, "enhancement output", enh_capacity, a.n_out * max_bytes))) return rc;
   if (a.n_out == 0) return SVC_OK;
   SVC_REQUIRE(a.in && a.offsets && d_workspace && a.base && a.base_offsets && a.d_status && (!a.enh || a.enh_offsets) &&
                   (!ladder || (d_budget && d_choice)),
@@ -1312,7 +1258,7 @@ int split_levels(const char* what, SplitArgs a, const svc_step_pair* ladder, uin
                   aligned(a.d_status, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
               "%s: streams and workspace must be 16-byte aligned, offsets 8-byte, source indices, windows, budget, choice and status 4-byte",
               what);
-  a.ws = carve_split(d_workspace, a.n_out, g.groups);
+  a.ws = carve(d_workspace, split_ws, a.n_out, g.groups, len);
   if (!a.enh) a.enh_offsets = nullptr, a.window = nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 waves(div_up(g.groups, kThreads / 64), a.n_out);
@@ -1334,9 +1280,9 @@ int split_levels(const char* what, SplitArgs a, const svc_step_pair* ladder, uin
   if ((rc = check_launch(what, "count"))) return rc;
   hipLaunchKernelGGL(split_scan_kernel, dim3(a.n_out), dim3(kThreads), 0, s, a);
   if ((rc = check_launch(what, "scan"))) return rc;
-  hipLaunchKernelGGL(window_offsets_kernel, dim3(a.enh ? 2 : 1), dim3(kThreads), 0, s, a.ws.frame_bytes, a.base_offsets,
-                     a.ws.frame_bytes + a.n_out, a.enh_offsets, a.n_out);
-  if ((rc = check_launch(what, "offsets"))) return rc;
+  if ((rc = enqueue_frame_offsets(what, a.enh ? 2 : 1, OffsetsJob{a.ws.frame_bytes, a.base_offsets, nullptr},
+                                  OffsetsJob{a.ws.frame_bytes + a.n_out, a.enh_offsets, nullptr}, a.n_out, stream)))
+    return rc;
   // a wave stages its group's levels of both layers in LDS: two waves per workgroup where a group is a tile above 2048 coefficients
   const uint32_t cap = g.tpg * g.bw * g.bh, wpb = split_write_waves(cap);
   hipLaunchKernelGGL(split_write_kernel, dim3(div_up(g.groups, wpb), a.n_out), dim3(64 * wpb), split_write_lds(cap), s, a, cap);
@@ -1357,11 +1303,15 @@ SplitArgs split_args(const uint8_t* d_frames, uint64_t stream_bytes, const uint6
 
 }  // namespace
 
+int enqueue_frame_offsets(const char* what, uint32_t jobs, OffsetsJob job0, OffsetsJob job1, uint32_t n, void* stream) {
+  hipLaunchKernelGGL(frame_offsets_kernel, dim3(jobs), dim3(kThreads), 0, static_cast<hipStream_t>(stream), job0, job1, n);
+  return check_launch(what, "offsets");
+}
+
 int drain_to_host(const char* what, const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, void* host_dst,
                   uint64_t capacity, uint64_t need, void* stream) {
-  SVC_REQUIRE(capacity >= need, "%s: destination of %llu B is below the batch's worst case of %llu B", what,
-              (unsigned long long)capacity, (unsigned long long)need);
-  if (n_frames == 0) return SVC_OK;
+  const int rc = require_capacity(what, "destination", capacity, need);
+  if (rc || n_frames == 0) return rc;
   SVC_REQUIRE(d_frames && d_frame_offsets && host_dst, "%s: null pointer", what);
   SVC_REQUIRE(aligned(d_frames, 16) && aligned(host_dst, 16) && aligned(d_frame_offsets, 8),
               "%s: frames and destination must be 16-byte aligned, offsets 8-byte", what);
@@ -1414,7 +1364,7 @@ uint64_t svc_hip_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w
   if (validate_geom("pack_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
       validate_limits("pack_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
     return 0;
-  return ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
+  return layout_bytes(stream_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
 }
 
 // Every argument is checked in this order, whatever n_frames: geometry, steps, limits, sizes, then pointers (null, alignment,
@@ -1432,18 +1382,16 @@ int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_ty
                 std::min(fg_step, bg_step));
   if ((rc = validate_limits("pack_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "pack_levels: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
+  if ((rc = require_workspace("pack_levels", workspace_bytes, layout_bytes(stream_ws, n_frames, g.groups)))) return rc;
   const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
-  SVC_REQUIRE(out_capacity >= need, "pack_levels: output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)out_capacity, (unsigned long long)need);
+  if ((rc = require_capacity("pack_levels", "output", out_capacity, need))) return rc;
   if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
   SVC_REQUIRE(d_planes && d_block_types && d_workspace && d_out && d_frame_offsets, "pack_levels: null pointer");
   SVC_REQUIRE(aligned(d_planes, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4),
               "pack_levels: planes, output and workspace must be 16-byte aligned, offsets 8-byte");
-  const PackArgs a{g, d_planes, d_block_types, d_out, d_frame_offsets, carve(d_workspace, n_frames, g.groups), n_frames, fg_step, bg_step,
-                   nullptr};
+  const PackArgs a{g, d_planes, d_block_types, d_out, d_frame_offsets, carve(d_workspace, stream_ws, n_frames, g.groups), n_frames, fg_step,
+                   bg_step, nullptr};
   return enqueue_pack("pack_levels", a, static_cast<hipStream_t>(stream));
 }
 
@@ -1456,7 +1404,7 @@ uint64_t svc_hip_pack_levels_budget_workspace_bytes(uint32_t n_frames, uint32_t 
     (void)fail(SVC_ERR_INVALID_ARG, "pack_levels_budget_workspace_bytes: a ladder of %u entries (1 .. %u)", ladder_len, kMaxLadder);
     return 0;
   }
-  return budget_ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups, ladder_len);
+  return layout_bytes(budget_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups, ladder_len);
 }
 
 // Checked in the order of svc_hip_pack_levels_frames, the ladder in place of the steps: geometry, ladder, int16 bound on entry 0,
@@ -1475,19 +1423,16 @@ int svc_hip_pack_levels_budget_frames(const float* d_planes, const uint32_t* d_b
     return fail(SVC_ERR_UNSUPPORTED, "pack_levels_budget: levels of a %ux%u tile at step %u could exceed int16", block_w, block_h, smin);
   if ((rc = validate_limits("pack_levels_budget", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  const uint64_t ws_need = budget_ws_bytes(n_frames, g.groups, ladder_len);
-  SVC_REQUIRE(workspace_bytes >= ws_need, "pack_levels_budget: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_need);
+  if ((rc = require_workspace("pack_levels_budget", workspace_bytes, layout_bytes(budget_ws, n_frames, g.groups, ladder_len)))) return rc;
   const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
-  SVC_REQUIRE(out_capacity >= need, "pack_levels_budget: output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)out_capacity, (unsigned long long)need);
+  if ((rc = require_capacity("pack_levels_budget", "output", out_capacity, need))) return rc;
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_planes && d_block_types && d_budget && d_workspace && d_out && d_frame_offsets && d_choice, "pack_levels_budget: null pointer");
   SVC_REQUIRE(aligned(d_planes, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
               "pack_levels_budget: planes, output and workspace must be 16-byte aligned, offsets 8-byte, types, budget and choice 4-byte");
   const Ladder lad = make_ladder(ladder, ladder_len);
-  const BudgetWs bws = carve_budget(d_workspace, n_frames, g.groups, ladder_len);
+  const BudgetWs bws = carve(d_workspace, budget_ws, n_frames, g.groups, ladder_len);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(g.groups, n_frames);
   hipLaunchKernelGGL(budget_count_kernel, grid, dim3(kThreads), lds_bytes(g), s, g, d_planes, d_block_types, lad, bws.nz);
@@ -1509,14 +1454,13 @@ int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   if (!rc) rc = validate_limits("unpack_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "unpack_levels: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
+  if ((rc = require_workspace("unpack_levels", workspace_bytes, layout_bytes(stream_ws, n_frames, g.groups)))) return rc;
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_planes && d_block_types && d_status, "unpack_levels: null pointer");
   SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_planes, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4) && aligned(d_status, 4),
               "unpack_levels: frames, planes and workspace must be 16-byte aligned, offsets 8-byte");
-  const UnpackArgs a{g, d_frames, stream_bytes, d_frame_offsets, d_planes, d_block_types, carve(d_workspace, n_frames, g.groups)};
+  const UnpackArgs a{g, d_frames, stream_bytes, d_frame_offsets, d_planes, d_block_types, carve(d_workspace, stream_ws, n_frames, g.groups)};
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((rc = enqueue_unpack_scan("unpack_levels", a, n_frames, d_status, s))) return rc;
   hipLaunchKernelGGL(unpack_kernel<true>, dim3(g.groups, n_frames), dim3(kThreads), lds_bytes(g), s, a);
@@ -1538,7 +1482,7 @@ uint64_t svc_hip_decode_levels_workspace_bytes(uint32_t n_frames, uint32_t frame
   if (validate_decode_geom("decode_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
       validate_limits("decode_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
     return 0;
-  return ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
+  return layout_bytes(stream_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
 }
 
 int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
@@ -1552,8 +1496,7 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   if ((rc = validate_steps_display("decode_levels", fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   if ((rc = validate_limits("decode_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  SVC_REQUIRE(workspace_bytes >= ws_bytes(n_frames, g.groups), "decode_levels: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_frames, g.groups));
+  if ((rc = require_workspace("decode_levels", workspace_bytes, layout_bytes(stream_ws, n_frames, g.groups)))) return rc;
   if (n_frames == 0) return SVC_OK;
   SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_rec && d_status, "decode_levels: null pointer");
   if ((rc = validate_display_buffer("decode_levels", display, d_display))) return rc;
@@ -1561,7 +1504,7 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                   aligned(d_status, 4) && aligned(d_gaze, 4),
               "decode_levels: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
   // planes and types null: the count pass writes neither
-  const UnpackArgs u{g, d_frames, stream_bytes, d_frame_offsets, nullptr, nullptr, carve(d_workspace, n_frames, g.groups)};
+  const UnpackArgs u{g, d_frames, stream_bytes, d_frame_offsets, nullptr, nullptr, carve(d_workspace, stream_ws, n_frames, g.groups)};
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((rc = enqueue_unpack_scan("decode_levels", u, n_frames, d_status, s))) return rc;
   const DecodeArgs a{g, d_frames, d_frame_offsets, d_gaze, d_rec, u.ws, (float)fg_step, (float)bg_step};
@@ -1576,7 +1519,8 @@ uint64_t svc_hip_decode_layers_workspace_bytes(uint32_t n_frames, uint32_t frame
   if (validate_decode_geom("decode_layers_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
       validate_limits("decode_layers_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
     return 0;
-  return 2 * ws_bytes(n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);  // a stream's half is a multiple of 16 B
+  // two streams' workspaces back to back: a stream's half is a multiple of 16 B
+  return 2 * layout_bytes(stream_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
 }
 
 // Checked in the order of svc_hip_decode_levels_frames.  Without a gaze no tile takes the enhancement: the call is that one on the base.
@@ -1591,9 +1535,8 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, con
   if ((rc = validate_steps_display("decode_layers", fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   if ((rc = validate_limits("decode_layers", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  const uint64_t ws_stream = ws_bytes(n_frames, g.groups);
-  SVC_REQUIRE(workspace_bytes >= 2 * ws_stream, "decode_layers: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)(2 * ws_stream));
+  const uint64_t ws_stream = layout_bytes(stream_ws, n_frames, g.groups);
+  if ((rc = require_workspace("decode_layers", workspace_bytes, 2 * ws_stream))) return rc;
   if (n_frames == 0) return SVC_OK;
   if (!d_gaze)
     return svc_hip_decode_levels_frames(d_base, base_bytes, d_base_offsets, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w,
@@ -1604,8 +1547,8 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, con
   SVC_REQUIRE(aligned(d_base, 16) && aligned(d_enh, 16) && aligned(d_workspace, 16) && aligned(d_base_offsets, 8) && aligned(d_enh_offsets, 8) &&
                   aligned(d_rec, 4) && aligned(d_status, 4) && aligned(d_gaze, 4),
               "decode_layers: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte");
-  const UnpackArgs ub{g, d_base, base_bytes, d_base_offsets, nullptr, nullptr, carve(d_workspace, n_frames, g.groups)};
-  const UnpackArgs ue{g, d_enh, enh_bytes, d_enh_offsets, nullptr, nullptr, carve(d_workspace + ws_stream, n_frames, g.groups)};
+  const UnpackArgs ub{g, d_base, base_bytes, d_base_offsets, nullptr, nullptr, carve(d_workspace, stream_ws, n_frames, g.groups)};
+  const UnpackArgs ue{g, d_enh, enh_bytes, d_enh_offsets, nullptr, nullptr, carve(d_workspace + ws_stream, stream_ws, n_frames, g.groups)};
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((rc = enqueue_unpack_scan("decode_layers base", ub, n_frames, d_status, s))) return rc;
   if ((rc = enqueue_unpack_scan("decode_layers enhancement", ue, n_frames, ue.ws.status, s))) return rc;  // its codes stay in its workspace
@@ -1623,7 +1566,7 @@ uint64_t svc_hip_window_levels_workspace_bytes(uint32_t n_out, uint32_t frame_w,
   if (validate_geom("window_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
       validate_limits("window_levels_workspace_bytes", n_out, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
     return 0;
-  return win_ws_bytes(n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups);
+  return layout_bytes(window_ws, n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups);
 }
 
 // Checked in the order of the SVCQ entry points, whatever the frame counts: geometry, limits, the d_src rule, workspace, output
@@ -1639,25 +1582,23 @@ int svc_hip_window_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   SVC_REQUIRE(d_src || n_out == n_in, "window_levels: without d_src output frame i is input frame i, but n_out is %u and n_in %u", n_out,
               n_in);
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
-  SVC_REQUIRE(workspace_bytes >= win_ws_bytes(n_out, g.groups), "window_levels: workspace of %llu B is smaller than the %llu B needed",
-              (unsigned long long)workspace_bytes, (unsigned long long)win_ws_bytes(n_out, g.groups));
+  if ((rc = require_workspace("window_levels", workspace_bytes, layout_bytes(window_ws, n_out, g.groups)))) return rc;
   const uint64_t max_bytes = frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
-  SVC_REQUIRE(out_capacity >= n_out * max_bytes, "window_levels: output of %llu B is below the batch's worst case of %llu B",
-              (unsigned long long)out_capacity, (unsigned long long)(n_out * max_bytes));
+  if ((rc = require_capacity("window_levels", "output", out_capacity, n_out * max_bytes))) return rc;
   if (n_out == 0) return SVC_OK;
   SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_out && d_out_offsets && d_status, "window_levels: null pointer");
   SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_out_offsets, 8) && aligned(d_src, 4) && aligned(d_window, 4) && aligned(d_status, 4),
               "window_levels: streams and workspace must be 16-byte aligned, offsets 8-byte, source indices, windows and status 4-byte");
   const WindowArgs a{g, d_frames, stream_bytes, d_frame_offsets, n_in, d_src, d_window, d_out, d_out_offsets, d_status,
-                     carve_window(d_workspace, n_out, g.groups)};
+                     carve(d_workspace, window_ws, n_out, g.groups)};
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(window_count_kernel, dim3(div_up(g.groups, kThreads / 64), n_out), dim3(kThreads), 0, s, a);
   if ((rc = check_launch("window_levels", "count"))) return rc;
   hipLaunchKernelGGL(window_scan_kernel, dim3(n_out), dim3(kThreads), 0, s, a);
   if ((rc = check_launch("window_levels", "scan"))) return rc;
-  hipLaunchKernelGGL(window_offsets_kernel, dim3(1), dim3(kThreads), 0, s, a.ws.frame_bytes, d_out_offsets, nullptr, nullptr, n_out);
-  if ((rc = check_launch("window_levels", "offsets"))) return rc;
+  if ((rc = enqueue_frame_offsets("window_levels", 1, OffsetsJob{a.ws.frame_bytes, d_out_offsets, nullptr}, OffsetsJob{}, n_out, stream)))
+    return rc;
   // a workgroup's pass is 4 KB of an output frame; the grid holds twice the header, types and masks (a window's levels are fewer
   // bytes than its frame's masks), and a frame that keeps more is walked in further passes
   const uint32_t fixed = div_up((uint32_t)(up16(g.levels_off) / 16), kThreads), most = div_up((uint32_t)(max_bytes / 16), kThreads);
@@ -1670,7 +1611,7 @@ uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uin
   if (validate_geom("split_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
       validate_limits("split_levels_workspace_bytes", std::max(n_in, n_out), frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
     return 0;
-  return split_ws_bytes(n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups, 0);
+  return layout_bytes(split_ws, n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups, 0u);
 }
 
 uint64_t svc_hip_split_levels_budget_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
@@ -1683,7 +1624,7 @@ uint64_t svc_hip_split_levels_budget_workspace_bytes(uint32_t n_in, uint32_t n_o
     (void)fail(SVC_ERR_INVALID_ARG, "split_levels_budget_workspace_bytes: a ladder of %u entries (1 .. %u)", ladder_len, kMaxLadder);
     return 0;
   }
-  return split_ws_bytes(n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups, ladder_len);
+  return layout_bytes(split_ws, n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups, ladder_len);
 }
 
 // Checked in the order of the SVCQ entry points, whatever the frame counts: geometry, steps, limits, the d_src rule, workspace, the two

@@ -3,8 +3,9 @@
 // and entropy.py are the independent Python statements the tests compare the kernels against.
 //
 // The first part is plain C++ (host/stream_decoder.cpp reads the headers it is handed with it).  The second is for the kernel files,
-// which include svc_common.hpp first: the checks of an SVCQ frame and of the entry points' arguments, and the wave / workgroup
-// primitives both files use.
+// which include svc_common.hpp first: the checks of an SVCQ frame and of the entry points' arguments, the one statement of a
+// workspace (Carver), and the steps every producer and consumer of the stream takes -- the scan of a frame's counts, a frame's offset in
+// its batch, a frame's fixed part (header, types, padding), the store of a run of levels, the address of a mask word.
 #pragma once
 
 #include <cstdint>
@@ -94,10 +95,56 @@ inline int validate_decode_geom(const char* what, uint32_t w, uint32_t h, uint32
   return SVC_OK;
 }
 
+// the two size checks every entry point makes after its limits; which = "output", "base output", "enhancement output", "destination"
+inline int require_workspace(const char* what, uint64_t have, uint64_t need) {
+  SVC_REQUIRE(have >= need, "%s: workspace of %llu B is smaller than the %llu B needed", what, (unsigned long long)have,
+              (unsigned long long)need);
+  return SVC_OK;
+}
+inline int require_capacity(const char* what, const char* which, uint64_t have, uint64_t need) {
+  SVC_REQUIRE(have >= need, "%s: %s of %llu B is below the batch's worst case of %llu B", what, which, (unsigned long long)have,
+              (unsigned long long)need);
+  return SVC_OK;
+}
+
+// ---- workspaces ---------------------------------------------------------------------------------------------------------------------
+//
+// A workspace is stated once, as a function `layout(Carver&, sizes...)` that takes its arrays in order and returns the struct of their
+// pointers.  carve() runs it on the caller's d_workspace, layout_bytes() on a null base, where the cursor's end is the size: the size
+// an entry point reports and the pointers its kernels store through cannot disagree.
+struct Carver {
+  uintptr_t at;
+  template <typename T>
+  T* take(uint64_t count, bool align16 = true) {  // the next `count` T's; the cursor then moves on to a multiple of 16 B, or not
+    T* const p = reinterpret_cast<T*>(at);
+    at += align16 ? up16(sizeof(T) * count) : sizeof(T) * count;
+    return p;
+  }
+};
+template <typename F, typename... A>
+auto carve(uint8_t* base, F layout, const A&... sizes) {
+  Carver c{reinterpret_cast<uintptr_t>(base)};
+  return layout(c, sizes...);
+}
+template <typename F, typename... A>
+uint64_t layout_bytes(F layout, const A&... sizes) {
+  Carver c{0};
+  (void)layout(c, sizes...);
+  return c.at;
+}
+
 // The drain of a batch of frames to pinned host memory (levels.hip), after the caller's geometry checks: capacity against `need`,
 // then pointers, the destination's memory, and the launch.
 int drain_to_host(const char* what, const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, void* host_dst,
                   uint64_t capacity, uint64_t need, void* stream);
+
+// The frame offsets of a batch from its frames' sizes (levels.hip): one launch, a workgroup per job -- offsets[0 .. n] = the running
+// sum of bytes[0 .. n), also stored to `copy` where that is not null.  Checked as the launch `what` "offsets".
+struct OffsetsJob {
+  const uint32_t* bytes;
+  uint64_t *offsets, *copy;
+};
+int enqueue_frame_offsets(const char* what, uint32_t jobs, OffsetsJob job0, OffsetsJob job1, uint32_t n, void* stream);
 
 // ---- device: wave and workgroup primitives ------------------------------------------------------------------------------------------
 
@@ -142,6 +189,76 @@ __device__ __forceinline__ void store_mask(void* p, uint64_t m) {
   uint32_t* q = static_cast<uint32_t*>(p);
   q[0] = (uint32_t)m;
   q[1] = (uint32_t)(m >> 32);
+}
+
+// the first mask word of tile t of tile row `row` = plane * tiles_y + tile row, in the mask section at `section` (as bytes or dwords: a
+// mask word is 8 B).  The pointer, not an index: from an index the compiler orders the multiplies of the kernels' address differently.
+template <typename P>
+__device__ __forceinline__ P* mask_words(P* section, uint64_t row, uint32_t tiles_x, uint64_t t, uint32_t words) {
+  return section + (8 / sizeof(P)) * ((row * tiles_x + t) * words);
+}
+
+// The scan of count -> scan -> scatter, by a workgroup in trips of kThreads: store(i, carry + the sum of load(j) over j < i) for every
+// i < count; returns carry + the sum of all.  The plain form reads src[i] and writes dst[i] (the same array: in place).
+template <typename Load, typename Store>
+__device__ __forceinline__ uint32_t scan_counts(uint32_t count, uint32_t carry, uint32_t* lds4, Load load, Store store) {
+  for (uint32_t base = 0; base < count; base += kThreads) {
+    const uint32_t i = base + threadIdx.x;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(i < count ? load(i) : 0u, lds4, &total);
+    if (i < count) store(i, carry + ex);
+    carry += total;
+  }
+  return carry;
+}
+__device__ __forceinline__ uint32_t scan_counts(const uint32_t* src, uint32_t* dst, uint32_t count, uint32_t carry, uint32_t* lds4) {
+  return scan_counts(count, carry, lds4, [&](uint32_t i) { return src[i]; }, [&](uint32_t i, uint32_t v) { dst[i] = v; });
+}
+
+// Frame f's offset in its batch = the sizes of the frames before it (a batch is a few dozen frames: no kernel of its own).  Wave 0 sums
+// them into *lds; the caller's next barrier hands the value to the workgroup.
+__device__ __forceinline__ void frame_offset_to_lds(const uint32_t* frame_bytes, uint32_t f, uint64_t* lds) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (wave != 0) return;
+  uint64_t s = 0;
+  for (uint32_t i = lane; i < f; i += 64) s += frame_bytes[i];
+  for (uint32_t off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (lane == 0) *lds = s;
+}
+
+// A frame's header words 2 .. 12, in the header's order; word k of the header they make
+struct FrameHead {
+  uint32_t w, h, bw, bh, mvbw, mvbh, fg, bg, levels, inexact, bytes;
+};
+__device__ __forceinline__ uint32_t header_word(const FrameHead& h, uint32_t k) {
+  const uint32_t v[kHeaderWords] = {kMagicQ, kVersion, h.w, h.h, h.bw, h.bh, h.mvbw, h.mvbh, h.fg, h.bg, h.levels, h.inexact, h.bytes, 0, 0, 0};
+  return v[k];
+}
+
+// A frame's fixed part, by a workgroup of `threads`: the header, the types, the zero pad behind the levels and, where `offsets` is not
+// null (a frame whose offset its own workgroup summed), offsets[f + 1].
+__device__ __forceinline__ void write_frame_edges(uint8_t* frame, const FrameHead& h, const uint32_t* types, uint32_t mvb,
+                                                  uint64_t levels_off, uint32_t threads, uint64_t* offsets, uint32_t f, uint64_t frame_off) {
+  if (threadIdx.x < kHeaderWords) reinterpret_cast<uint32_t*>(frame)[threadIdx.x] = header_word(h, threadIdx.x);
+  uint32_t* tdst = reinterpret_cast<uint32_t*>(frame + kHeaderBytes);
+  for (uint32_t i = threadIdx.x; i < mvb; i += threads) tdst[i] = types[i];
+  const uint64_t used = levels_off + 2ull * h.levels;
+  for (uint64_t i = used + threadIdx.x; i < h.bytes; i += threads) frame[i] = 0;
+  if (offsets && threadIdx.x == 0) {
+    offsets[f + 1] = frame_off + h.bytes;
+    if (f == 0) offsets[0] = 0;
+  }
+}
+
+// A wave stores a run of cnt int16 levels to dst, a 2-byte aligned place in a frame: aligned dwords, and 16 bits at an odd end, where
+// the dword belongs half to the neighbouring run (whose wave stores its own half)
+__device__ __forceinline__ void store_level_run(const uint16_t* src, uint32_t cnt, uint16_t* dst) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t head = cnt != 0 && (reinterpret_cast<uintptr_t>(dst) & 2u) ? 1u : 0u, body = (cnt - head) / 2;
+  if (head && lane == 0) dst[0] = src[0];
+  uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + head);
+  for (uint32_t k = lane; k < body; k += 64) d32[k] = (uint32_t)src[head + 2 * k] | ((uint32_t)src[head + 2 * k + 1] << 16);
+  if (((cnt - head) & 1u) && lane == 0) dst[cnt - 1] = src[cnt - 1];
 }
 
 // ---- device: is SVCQ frame f well formed for geometry g inside a stream of stream_bytes? ----------------------------------------------
