@@ -845,6 +845,69 @@ int svc_hip_window_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                                  uint32_t* d_status /* [n_out] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The same on a stored SVCE stream, on its coded bytes: what a server holds and sends.  No SVCQ
+ * frame is written or read.  scalable_video_codec_amd/entropy.py (window_frame, window_frames) is
+ * the numpy statement: for a stream this project's encoder wrote, output frame i is byte for byte
+ * svc_hip_entropy_encode_frames of svc_hip_window_levels_frames of svc_hip_entropy_decode_frames of
+ * input frame s = d_src ? d_src[i] : i, with the input's chunk_tiles.
+ *
+ * An SVCE chunk is adjacent tiles of one row and a window is a rectangle of tiles, so per chunk:
+ *   kept whole     (every tile's origin inside d_window[i]) payload bytes and index entry as they
+ *                  are, canonical or not
+ *   dropped whole  (no tile inside) the canonical empty chunk: coded, k_dc = k_ac = 0, per tile the
+ *                  two bits "DC difference 0, no AC levels": ceil((7 + 2 nt) / 8) bytes, count 0
+ *   cut            (a vertical window edge inside it; at most two per tile row and plane) what
+ *                  the encoder writes for the chunk with the dropped tiles all zero: the kept
+ *                  tiles' masks and levels, the DC chain running through the dropped tiles as
+ *                  zeros, the per-chunk minimum k, raw when strictly smaller, raw when a kept set
+ *                  mask bit holds level 0
+ *   header   words 0 .. 9, 11, 14 and 15 copied, word 10 = the output chunks' levels, word 13 =
+ *            up16(levels offset + 2 * word 10), word 12 = the output frame's bytes
+ *   types    the section copied; index: one entry per chunk of the input's chunk grid
+ *   padding  zero, to 16 bytes
+ *
+ * d_status [n_out] u32: the codes 1, 2, 3, 4, 5, 8, 10 of svc_hip_entropy_decode_frames' frame
+ * check, made on the input frame; 1 also for d_src[i] >= n_in; 4 also for a chunk_tiles whose raw
+ * chunk, 1 + (8 words + 2 area) * min(chunk_tiles, tiles_x) bytes, is above 65535 (a cut chunk
+ * could not always be written into the index's u16), whatever the window; 5 also for a frame whose
+ * output would exceed svc_hip_window_entropy_max_bytes(1, ...) (kept chunks of a non-canonical
+ * input may be larger than their raw form), decided before anything of it is written; 9 for a cut
+ * chunk whose walked part is malformed (empty, a prefix above 24 zeros, a read past its size, a
+ * count, run or level outside the tile or int16, more levels than its index entry, a raw chunk
+ * whose size does not match its tiles and count or with stray mask bits).
+ * A cut chunk is walked from its first tile to its last KEPT tile only, and kept and dropped chunks
+ * are not walked at all: the decoder's end-of-chunk checks are NOT made here.  A malformation
+ * outside the walked part passes through (copied, or dropped), and the decoder of the output
+ * flags it.  A frame that fails is 64 zero bytes and leaves its neighbours as they would be.  Every
+ * read is clamped to the frame; nothing is written past d_out_offsets[n_out].
+ *
+ * svc_hip_window_entropy_max_bytes: n_out times the worst canonical frame at chunk_tiles 1
+ * (svc_hip_entropy_max_bytes' formula with a chunk per tile).  Geometry and limits: the entropy
+ * coder's.  Checked in the order of svc_hip_window_levels_frames: geometry, limits, d_src == NULL
+ * with n_out != n_in, workspace, out_capacity against the max_bytes above; n_out == 0 then returns
+ * SVC_OK; then pointers and their alignment (as above).  The queries return 0 where the call
+ * refuses.  d_out must not overlap the input stream: NOT checked.  Two calls write the same bytes.
+ * Only enqueues work.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_window_entropy_max_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h,
+                                          uint32_t block_w, uint32_t block_h,
+                                          uint32_t mv_block_w, uint32_t mv_block_h);
+uint64_t svc_hip_window_entropy_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h,
+                                                uint32_t block_w, uint32_t block_h,
+                                                uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_window_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes,
+                                  const uint64_t* d_offsets, uint32_t n_in,
+                                  const uint32_t* d_src /* [n_out] index of the input frame; NULL = identity, then n_out must equal n_in */,
+                                  uint32_t n_out,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                  uint32_t mv_block_w, uint32_t mv_block_h,
+                                  const uint32_t* d_window /* [n_out][4] x, y, w, h (padded); NULL = every tile */,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes,
+                                  uint8_t* d_out, uint64_t out_capacity,
+                                  uint64_t* d_out_offsets /* [n_out + 1] */,
+                                  uint32_t* d_status /* [n_out] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * A stored fine SVCQ stream split into a base stream at any steps plus its enhancement stream,
  * stream to stream: encode once at (fine_step, fine_step), then serve any multiple of it without
  * the pixels.  scalable_video_codec_amd/layers.py (split_frame, split_frames,

@@ -22,6 +22,8 @@
 //   check    as above
 //   decode   one workgroup per group of tiles of levels.hip's decoder: its chunks into LDS, one lane per chunk, then the reconstruction
 //   finish   status; zeros for a frame that failed
+// window (svc_hip_window_entropy_frames): an SVCE stream restricted to a window per output frame on its coded bytes -- kept chunks
+// copied, dropped chunks a constant, only the chunks a window edge cuts walked and coded again; its kernels are listed at their section
 #include "display_core.hpp"
 #include "idct_core.hpp"
 #include "stream_format.hpp"
@@ -501,23 +503,25 @@ struct DecArgs {
   uint32_t n;
 };
 
-// frame check and index scan: one workgroup per frame
-__global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
-  __shared__ uint32_t red[kWaves];
-  __shared__ uint32_t s_st;
+// frame check and index scan, by one workgroup: input frame f (f_ok: it is one of the batch's; else kStRange) into the workspace's entry
+// `slot`.  recodable: also refuse (kStGeometry) a chunk_tiles whose raw chunk, 1 + (8 nw + 2 area) min(chunk_tiles, tiles_x) bytes, is
+// above the index's u16 -- what the window call must be able to write for any chunk it cuts.
+__device__ __forceinline__ void dec_check_frame(const DecArgs& a, uint32_t f, bool f_ok, uint32_t slot, bool recodable, uint32_t* red,
+                                                uint32_t* s_st_p) {
+  uint32_t& s_st = *s_st_p;
   const Geom& g = a.g;
-  const uint32_t f = blockIdx.x;
-  const uint64_t o = a.in_off[f], e = a.in_off[f + 1];
+  const uint64_t o = f_ok ? a.in_off[f] : 0, e = f_ok ? a.in_off[f + 1] : 0;
   uint32_t st = kStOk, ct = 0, cx = 0, chunks = 0;
   const uint32_t* h = nullptr;
   uint64_t payload = 0;
-  if (o % 16 != 0 || o > e || e > a.in_bytes || e - o < kHeaderBytes) st = kStRange;
+  if (!f_ok || o % 16 != 0 || o > e || e > a.in_bytes || e - o < kHeaderBytes) st = kStRange;
   if (st == kStOk) {
     h = reinterpret_cast<const uint32_t*>(a.in + o);
     if (h[kHMagic] != kMagicE) st = kStMagic;
     else if (h[kHVersion] != kVersion) st = kStVersion;
     else if (h[kHWidth] != g.w || h[kHHeight] != g.h || h[kHTileW] != g.bw || h[kHTileH] != g.bh || h[kHMvW] != g.mvbw ||
-             h[kHMvH] != g.mvbh || h[kHFgStep] == 0 || h[kHBgStep] == 0 || h[kEChunkTiles] == 0)
+             h[kHMvH] != g.mvbh || h[kHFgStep] == 0 || h[kHBgStep] == 0 || h[kEChunkTiles] == 0 ||
+             (recodable && 1ull + (8ull * g.nw + 2ull * g.area) * min(h[kEChunkTiles], g.tx) > 0xFFFFull))
       st = kStGeometry;
     else if (h[kHBytes] % 16 != 0 || h[kHBytes] != e - o) st = kStSize;
     else if (h[kHLevels] > 3ull * g.w * g.h || h[kESvcqBytes] != up16(g.levels_off + 2ull * h[kHLevels])) st = kStSvcqBytes;
@@ -541,8 +545,8 @@ __global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
       const uint32_t eb = block_exclusive_scan(v & 0xFFFFu, red, &tb);
       const uint32_t el = block_exclusive_scan(v >> 16, red, &tl);
       if (i < chunks) {
-        a.ws.coff[(size_t)f * g.max_chunks + i] = (uint32_t)payload + bcarry + eb;
-        a.ws.loff[(size_t)f * g.max_chunks + i] = lcarry + el;
+        a.ws.coff[(size_t)slot * g.max_chunks + i] = (uint32_t)payload + bcarry + eb;
+        a.ws.loff[(size_t)slot * g.max_chunks + i] = lcarry + el;
       }
       bcarry += tb;
       lcarry += tl;
@@ -588,11 +592,17 @@ __global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
   if (threadIdx.x == 0) s_st = st;
   __syncthreads();
   if (threadIdx.x == 0) {
-    a.ws.status[f] = s_st;
-    a.ws.fail[f] = 0;
-    a.ws.chunks[f] = s_st == kStOk ? ct : 0u;
-    a.ws.qbytes[f] = s_st == kStOk ? h[kESvcqBytes] : kHeaderBytes;
+    a.ws.status[slot] = s_st;
+    a.ws.fail[slot] = 0;
+    a.ws.chunks[slot] = s_st == kStOk ? ct : 0u;
+    a.ws.qbytes[slot] = s_st == kStOk ? h[kESvcqBytes] : kHeaderBytes;
   }
+}
+
+__global__ __launch_bounds__(256) void dec_check_kernel(DecArgs a) {
+  __shared__ uint32_t red[kWaves];
+  __shared__ uint32_t s_st;
+  dec_check_frame(a, blockIdx.x, true, blockIdx.x, false, red, &s_st);
 }
 
 // a bit reader over one frame: aligned u32 loads, nothing read at or past the frame's end (zeros there).  The bits from the read
@@ -1027,6 +1037,503 @@ __global__ __launch_bounds__(256) void decode_entropy_finish_kernel(FusedArgs a)
   for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) r[i] = 0.f;
 }
 
+// ---- window: SVCE frames restricted to the tiles of a window, on their coded bytes (svc_hip_window_entropy_frames) -------------------
+//
+// Output frame i = input frame s (d_src[i], or i) as svc_hip_entropy_encode_frames would write its SVCQ frame restricted to window i,
+// on the input's own chunk grid.  A window is a rectangle of tiles, so a chunk (adjacent tiles of one row) is
+//   kept     every tile inside: its payload bytes and index entry as they are, never read as codewords
+//   dropped  no tile inside: the empty coded chunk, ceil((7 + 2 nt) / 8) bytes of a fixed pattern, the input never read
+//   cut      a vertical window edge runs through it: at most two per tile row and plane, each with a SLOT (2 * row + side)
+// Only a cut chunk is walked, once, from its first tile to its last KEPT tile: the end-of-chunk checks of the decoder are not made, and
+// kept and dropped chunks are not walked at all, so a malformation outside the walked part passes through (copied, or dropped) and the
+// decoder of the output flags it.
+//   check    one workgroup per frame: the decoder's check of the input frame (dec_check_frame)
+//   size     one lane per chunk: the index entries of the kept and the dropped chunks
+//   recode   one lane per slot (a chunk is serial by design; the slots of the rows a window crosses are adjacent lanes): the cut
+//            chunk's kept tiles decoded once into the slot's slab (mask words, then levels)
+//   lengths  one wave per slot, a lane per tile: from the slab the code lengths for every k, the choice of k and of raw as the
+//            encoder makes it -> the chunk's index entry
+//   layout   one workgroup per frame: chunk byte offsets, the frame's size, levels and final status (over-size: kStSize)
+//   offsets  the frame offsets (levels.hip)
+//   write    one wave per chunk: kept payloads copied (bytes to the first aligned dword of the destination, then dwords funnelled
+//            from the source's two, then bytes: no byte of a neighbouring chunk is touched), the dropped pattern, raw cut chunks
+//   place    one wave per slot, a lane per tile: a coded cut chunk's codewords from the slab into LDS words, stored bytewise
+//   frame    one workgroup per frame: header, types section, index, padding, or 64 zero bytes for a frame that failed
+// Every output byte is stored once, by one thread, from the input and the window alone: two calls write the same bytes.
+
+struct WinWs {
+  DecWs in;          // the check's view of output frame i's input frame: chunk byte offsets, status, fail, chunk_tiles
+  uint32_t* ent;     // [n][max_chunks] the output chunk's index entry: bytes | levels << 16
+  uint32_t* ooff;    // [n][max_chunks] its payload's byte offset inside the output frame
+  uint32_t* cut;     // [n][slots] a cut chunk's kept levels (kCutFailed: it failed its walk), then its k_dc | k_ac << 3 | raw << 6
+  uint32_t* fbytes;  // [n] output frame bytes
+  uint32_t* levels;  // [n] output header word 10
+  uint64_t* foff;    // [n + 1] frame offsets
+  uint8_t* slab;     // [n][slots][slot_bytes] a cut chunk's kept tiles: their mask words, then their levels
+};
+// two cut chunks per plane and tile row; a slot holds the kept tiles of the largest chunk the call accepts (raw form within the u16)
+uint32_t win_slots(const Geom& g) { return 6 * g.ty; }
+uint32_t win_slot_bytes(const Geom& g) { return (uint32_t)up16(std::min<uint64_t>(0xFFFEull, (8ull * g.nw + 2ull * g.area) * g.tx)); }
+WinWs win_ws(Carver& c, uint32_t n, const Geom& g) {
+  WinWs s;
+  s.in = dec_ws(c, n, g);
+  s.ent = c.take<uint32_t>((uint64_t)n * g.max_chunks);
+  s.ooff = c.take<uint32_t>((uint64_t)n * g.max_chunks);
+  s.cut = c.take<uint32_t>((uint64_t)n * win_slots(g));
+  s.fbytes = c.take<uint32_t>(n);
+  s.levels = c.take<uint32_t>(n);
+  s.foff = c.take<uint64_t>((uint64_t)n + 1);
+  s.slab = c.take<uint8_t>((uint64_t)n * win_slots(g) * win_slot_bytes(g));
+  return s;
+}
+// the worst canonical frame at chunk_tiles 1 (svce_max_bytes with a chunk per tile): what one output frame may take
+uint64_t win_max_bytes(const Geom& g) { return up16(g.levels_off + 6ull * g.w * g.h + 4 + 5ull * g.max_chunks); }
+
+struct WinArgs {
+  Geom g;
+  const uint8_t* in;
+  const uint64_t* in_off;
+  const uint32_t* src;     // [n_out] input frame of each output frame, or null: its own index
+  const uint32_t* window;  // [n_out][4] x, y, w, h in padded coordinates, or null: every tile is kept
+  uint8_t* out;
+  uint32_t* d_status;
+  WinWs ws;
+  uint32_t slots, slot_bytes;
+  uint64_t worst;          // win_max_bytes
+};
+
+__global__ __launch_bounds__(256) void win_check_kernel(DecArgs a, const uint32_t* src, uint32_t n_in) {
+  __shared__ uint32_t red[kWaves];
+  __shared__ uint32_t s_st;
+  const uint32_t i = blockIdx.x, s = src ? src[i] : i;
+  dec_check_frame(a, s, s < n_in, i, true, red, &s_st);
+}
+
+// an output frame that passed its check: the input frame and what the kernels read of it
+struct WinFrame {
+  const uint8_t* frame;
+  const uint32_t* hdr;
+  const uint32_t* index;
+  const uint32_t* coff;  // the input chunks' byte offsets
+  uint32_t fwords, ct, cx, chunks;
+};
+__device__ __forceinline__ WinFrame win_frame(const WinArgs& a, uint32_t i) {
+  WinFrame w;
+  w.frame = a.in + a.in_off[a.src ? a.src[i] : i];
+  w.hdr = reinterpret_cast<const uint32_t*>(w.frame);
+  w.index = w.hdr + (kHeaderBytes + w.hdr[kETypesBytes]) / 4;
+  w.coff = a.ws.in.coff + (size_t)i * a.g.max_chunks;
+  w.fwords = w.hdr[kHBytes] / 4;
+  w.ct = a.ws.in.chunks[i];
+  w.cx = w.ct >= a.g.tx ? 1u : (a.g.tx + w.ct - 1) / w.ct;
+  w.chunks = 3 * a.g.ty * w.cx;
+  return w;
+}
+
+// the tiles of tile row `row` (plane * ty + tile row) whose origin window i contains: [*first, *last) (the rule of gazed())
+__device__ __forceinline__ void kept_span(const WinArgs& a, uint32_t i, uint32_t row, uint32_t* first, uint32_t* last) {
+  const Geom& g = a.g;
+  *first = 0;
+  *last = g.tx;
+  if (!a.window) return;
+  const uint32_t* r = a.window + 4ull * i;
+  const uint32_t oy = (row % g.ty) * g.bh;
+  if (!(oy >= r[1] && oy - r[1] < r[3])) {
+    *last = 0;
+    return;
+  }
+  const uint64_t f = ((uint64_t)r[0] + g.bw - 1) / g.bw, l = ((uint64_t)r[0] + r[2] + g.bw - 1) / g.bw;  // r[2] == 0: l == f
+  *first = f < g.tx ? (uint32_t)f : g.tx;
+  *last = l < g.tx ? (uint32_t)l : g.tx;
+}
+// ... and those of a chunk of nt tiles from tile t0, as chunk tiles [*lo, *hi): kept whole when that is [0, nt), dropped when empty
+__device__ __forceinline__ void kept_tiles(uint32_t first, uint32_t last, uint32_t t0, uint32_t nt, uint32_t* lo, uint32_t* hi) {
+  const uint32_t a = max(first, t0), b = min(last, t0 + nt);
+  *lo = a < b ? a - t0 : 0u;
+  *hi = a < b ? b - t0 : 0u;
+}
+// the slot of a cut chunk: side 0 for the chunk that holds the row's first kept tile, side 1 for the other one (it holds the last)
+__device__ __forceinline__ uint32_t slot_of(uint32_t row, uint32_t first, uint32_t t0, uint32_t nt) {
+  return 2 * row + (first >= t0 && first < t0 + nt ? 0u : 1u);
+}
+
+// size: one lane per chunk
+__global__ __launch_bounds__(256) void win_size_kernel(WinArgs a) {
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.y, c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= g.max_chunks || a.ws.in.status[i] != kStOk) return;
+  const WinFrame w = win_frame(a, i);
+  if (c >= w.chunks) return;
+  uint32_t row, t0, nt, first, last, lo, hi;
+  chunk_tiles(g, w.ct, w.cx, c, &row, &t0, &nt);
+  kept_span(a, i, row, &first, &last);
+  kept_tiles(first, last, t0, nt, &lo, &hi);
+  if (hi - lo == nt) a.ws.ent[(size_t)i * g.max_chunks + c] = w.index[c];
+  else if (hi == lo) a.ws.ent[(size_t)i * g.max_chunks + c] = (7 + 2 * nt + 7) / 8;
+}
+
+// a slot's cut chunk, if it has one
+struct CutChunk {
+  uint32_t c, t0, nt, lo, hi;
+};
+__device__ __forceinline__ bool cut_chunk(const WinArgs& a, const WinFrame& w, uint32_t i, uint32_t sl, CutChunk* k) {
+  const Geom& g = a.g;
+  const uint32_t row = sl >> 1, side = sl & 1u;
+  uint32_t first, last;
+  kept_span(a, i, row, &first, &last);
+  if (first >= last) return false;
+  const uint32_t c0 = w.cx == 1 ? 0u : first / w.ct, c1 = w.cx == 1 ? 0u : (last - 1) / w.ct;
+  if (side && c1 == c0) return false;
+  uint32_t r;
+  k->c = row * w.cx + (side ? c1 : c0);
+  chunk_tiles(g, w.ct, w.cx, k->c, &r, &k->t0, &k->nt);
+  kept_tiles(first, last, k->t0, k->nt, &k->lo, &k->hi);
+  return k->hi - k->lo != k->nt;
+}
+
+constexpr uint32_t kCutFailed = 0xFFFFFFFFu;  // in WinWs::cut after the walk: the slot's chunk did not pass it (else: its kept levels)
+
+// recode: one lane per slot
+__global__ __launch_bounds__(256) void win_recode_kernel(WinArgs a) {
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.y, sl = blockIdx.x * kThreads + threadIdx.x;
+  if (sl >= a.slots || a.ws.in.status[i] != kStOk) return;
+  const WinFrame w = win_frame(a, i);
+  CutChunk k;
+  if (!cut_chunk(a, w, i, sl, &k)) return;
+  const uint32_t entry = w.index[k.c], size = entry & 0xFFFFu, count = entry >> 16, start = w.coff[k.c];
+  const uint8_t* frame = w.frame;
+  uint8_t* masks = a.ws.slab + ((size_t)i * a.slots + sl) * a.slot_bytes;
+  int16_t* lev = reinterpret_cast<int16_t*>(masks + 8ull * g.nw * (k.hi - k.lo));
+  uint32_t kept = 0;  // levels in the slab
+  bool ok = size != 0;
+  if (ok && (frame[start] & 1u)) {  // raw: the kept tiles' mask words and levels as they are
+    const uint32_t mbytes = 8 * g.nw * k.nt;
+    ok = (uint64_t)size == 1ull + mbytes + 2ull * count;
+    const uint8_t* lv = frame + start + 1 + mbytes;
+    uint32_t got = 0;
+    for (uint32_t x = 0; ok && x < k.hi * g.nw; ++x) {
+      const uint8_t* s = frame + start + 1 + 8 * x;
+      uint64_t m = 0;
+      for (uint32_t b = 0; b < 8; ++b) m |= (uint64_t)s[b] << (8 * b);
+      const uint32_t j = x % g.nw;
+      const uint32_t valid = min(64u, g.area - 64 * j);
+      if (valid < 64 && (m >> valid)) ok = false;
+      const uint32_t pc = (uint32_t)__popcll(m);
+      if (ok && got + pc > count) ok = false;  // more mask bits than levels: nothing is read past the chunk
+      if (!ok) break;
+      if (x >= k.lo * g.nw) {
+        store_mask(masks + 8 * (x - k.lo * g.nw), m);
+        for (uint32_t e = 0; e < pc; ++e) lev[kept++] = (int16_t)((uint32_t)lv[2 * (got + e)] | ((uint32_t)lv[2 * (got + e) + 1] << 8));
+      }
+      got += pc;
+    }
+  } else if (ok) {
+    BitReader r{w.hdr, w.fwords, 0, 0, 0, 0};
+    const uint64_t end = 8ull * (start + size);
+    uint64_t pos = 8ull * start;
+    const uint32_t head = (uint32_t)r.peek(pos);
+    const uint32_t kd = (head >> 1) & 7u, ka = (head >> 4) & 7u;
+    pos += 7;
+    r.seek(pos);
+    uint32_t written = 0;
+    int32_t dcp = 0;
+    for (uint32_t t = 0; ok && t < k.hi; ++t) {
+      const bool keep = t >= k.lo;
+      uint8_t* tm = masks + 8ull * (keep ? t - k.lo : 0u) * g.nw;
+      uint32_t u;
+      ok = get_eg(r, &pos, end, kd, &u);
+      if (!ok) break;
+      const int32_t dc = dcp + unsgn(u);
+      dcp = dc;
+      ok = dc >= -32768 && dc <= 32767;
+      uint64_t cur = 0;  // the mask word being filled, word cj of the tile
+      uint32_t cj = 0;
+      if (ok && dc != 0) {
+        ok = written < count;
+        if (ok) {
+          ++written;
+          if (keep) lev[kept++] = (int16_t)dc;
+        }
+        cur = 1;
+      }
+      uint32_t nac = 0;
+      ok = ok && get_eg(r, &pos, end, 0, &nac) && nac <= g.area - 1;
+      uint32_t p = 0;
+      for (uint32_t x = 0; ok && x < nac; ++x) {
+        uint32_t run, lu;
+        ok = get_eg(r, &pos, end, 0, &run) && (uint64_t)p + run + 1 <= g.area - 1;
+        if (!ok) break;
+        p += run + 1;
+        ok = get_eg(r, &pos, end, ka, &lu);
+        if (!ok) break;
+        const int32_t v = unsgn(lu);
+        ok = v >= -32768 && v <= 32767 && written < count;
+        if (!ok) break;
+        ++written;
+        if (!keep) continue;
+        lev[kept++] = (int16_t)v;
+        for (; cj < (p >> 6); ++cj) {
+          store_mask(tm + 8 * cj, cur);
+          cur = 0;
+        }
+        cur |= 1ull << (p & 63u);
+      }
+      if (!ok || !keep) continue;
+      for (; cj < g.nw; ++cj) {
+        store_mask(tm + 8 * cj, cur);
+        cur = 0;
+      }
+    }
+  }
+  if (!ok) {
+    atomicOr(&a.ws.in.fail[i], 1u);
+    a.ws.cut[(size_t)i * a.slots + sl] = kCutFailed;
+    return;
+  }
+  a.ws.cut[(size_t)i * a.slots + sl] = kept;
+}
+
+// the wave's trip over a cut chunk's tiles, 64 at a time, a lane per tile: fn(t, keep, masks, lev) with the tile's mask words and first
+// level in the slab for a tile inside the window (keep), nothing to read for one outside it.  Every lane of the wave calls fn.
+template <typename Fn>
+__device__ __forceinline__ void for_each_cut_tile(const Geom& g, const CutChunk& k, const uint8_t* slab, uint32_t lane, Fn fn) {
+  const int16_t* lev = reinterpret_cast<const int16_t*>(slab + 8ull * g.nw * (k.hi - k.lo));
+  uint32_t before = 0;  // levels of the tiles of earlier trips
+  for (uint32_t base = 0; base < k.nt; base += 64) {
+    const uint32_t t = base + lane;
+    const bool keep = t >= k.lo && t < k.hi;
+    const uint8_t* tm = slab + 8ull * g.nw * (keep ? t - k.lo : 0u);
+    const uint32_t mine = keep ? tile_levels(g, tm) : 0u;
+    const uint32_t first = before + wave_exclusive_scan(mine);
+    before += wave_sum(mine);
+    fn(t, keep, tm, lev + first);
+  }
+}
+
+// lengths: one wave per slot, a lane per tile -> the cut chunk's k_dc, k_ac, raw and index entry, as enc_lengths_kernel chooses them for
+// the chunk with every tile outside the window all zero
+__global__ __launch_bounds__(64) void win_lengths_kernel(WinArgs a) {
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.y, sl = blockIdx.x, lane = threadIdx.x;
+  if (a.ws.in.status[i] != kStOk) return;
+  const WinFrame w = win_frame(a, i);
+  CutChunk k;
+  if (!cut_chunk(a, w, i, sl, &k)) return;
+  const uint32_t kept = a.ws.cut[(size_t)i * a.slots + sl];
+  if (kept == kCutFailed) return;
+  const uint8_t* slab = a.ws.slab + ((size_t)i * a.slots + sl) * a.slot_bytes;
+  uint32_t dc_bits[8] = {}, ac_bits[8] = {};
+  uint32_t fixed = 0, forced = 0;
+  int32_t dc_before = 0;  // the DC of the last tile of the trip before
+  for_each_cut_tile(g, k, slab, lane, [&](uint32_t t, bool keep, const uint8_t* tm, const int16_t* lev) {
+    int32_t dc = 0;
+    uint32_t prev = 0, nac = 0;
+    if (keep)
+      for_each_level(g, tm, lev, [&](uint32_t p, int32_t v) {
+        forced |= v == 0;
+        if (p == 0) { dc = v; return; }
+        ++nac;
+        fixed += eg_len(p - prev - 1, 0);
+        prev = p;
+        const uint32_t u = sgn(v);
+        for (uint32_t q = 0; q < 8; ++q) ac_bits[q] += eg_len(u, q);
+      });
+    const int32_t left = __shfl_up(dc, 1, 64);
+    if (t < k.nt) {
+      fixed += eg_len(nac, 0);
+      const uint32_t u = sgn(dc - (lane == 0 ? dc_before : left));
+      for (uint32_t q = 0; q < 8; ++q) dc_bits[q] += eg_len(u, q);
+    }
+    dc_before = __shfl(dc, 63, 64);
+  });
+  fixed = wave_sum(fixed);
+  forced = wave_sum(forced);
+  uint32_t best_dc = 0, best_ac = 0, kd = 0, ka = 0;
+  for (uint32_t q = 0; q < 8; ++q) {
+    const uint32_t d = wave_sum(dc_bits[q]), s = wave_sum(ac_bits[q]);
+    if (q == 0 || d < best_dc) { best_dc = d; kd = q; }
+    if (q == 0 || s < best_ac) { best_ac = s; ka = q; }
+  }
+  if (lane == 0) {
+    const uint32_t coded = (7 + fixed + best_dc + best_ac + 7) / 8;
+    const uint32_t raw = 1 + 8 * g.nw * k.nt + 2 * kept;
+    const bool use_raw = forced || raw < coded;
+    a.ws.ent[(size_t)i * g.max_chunks + k.c] = (use_raw ? raw : coded) | (kept << 16);
+    a.ws.cut[(size_t)i * a.slots + sl] = kd | (ka << 3) | ((use_raw ? 1u : 0u) << 6);
+  }
+}
+
+// layout: one workgroup per frame -> chunk byte offsets, the frame's bytes and levels, its final status
+__global__ __launch_bounds__(256) void win_layout_kernel(WinArgs a) {
+  __shared__ uint32_t red[kWaves];
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.x;
+  uint32_t st = a.ws.in.status[i];
+  if (st == kStOk && a.ws.in.fail[i]) st = kStChunk;
+  uint64_t bytes = kHeaderBytes;
+  uint32_t lev = 0;
+  if (st == kStOk) {
+    const WinFrame w = win_frame(a, i);
+    const uint32_t* ent = a.ws.ent + (size_t)i * g.max_chunks;
+    bytes = kHeaderBytes + (uint64_t)w.hdr[kETypesBytes] + 4ull * w.chunks;  // (64 bits: kept chunks may be of any size)
+    for (uint32_t base = 0; base < w.chunks; base += kThreads) {
+      const uint32_t c = base + threadIdx.x;
+      const uint32_t v = c < w.chunks ? ent[c] : 0u;
+      uint32_t tb, tl;
+      const uint32_t eb = block_exclusive_scan(v & 0xFFFFu, red, &tb);
+      (void)block_exclusive_scan(v >> 16, red, &tl);
+      if (c < w.chunks) a.ws.ooff[(size_t)i * g.max_chunks + c] = (uint32_t)(bytes + eb);  // read only for a frame within a.worst
+      bytes += tb;
+      lev += tl;
+    }
+    bytes = up16(bytes);
+    if (bytes > a.worst) {  // kept chunks above their raw form: nothing of this frame is written
+      st = kStSize;
+      bytes = kHeaderBytes;
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.ws.in.status[i] = st;
+    a.d_status[i] = st;
+    a.ws.fbytes[i] = (uint32_t)bytes;
+    a.ws.levels[i] = lev;
+  }
+}
+
+// a wave copies `size` bytes from byte sb of the frame's dwords to dst, whatever the two byte phases: single bytes up to dst's first
+// aligned dword, then dwords funnelled from the source's two, then single bytes
+__device__ __forceinline__ void copy_payload(const WinFrame& w, uint32_t sb, uint32_t size, uint8_t* dst, uint32_t lane) {
+  const uint8_t* src = w.frame + sb;
+  const uint32_t head = min(size, (4u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u), body = (size - head) / 4;
+  if (lane < head) dst[lane] = src[lane];
+  uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + head);
+  const uint32_t s0 = (sb + head) >> 2, sh = 8 * ((sb + head) & 3u);
+  for (uint32_t x = lane; x < body; x += 64) {
+    const uint64_t two = (uint64_t)w.hdr[s0 + x] | (sh && s0 + x + 1 < w.fwords ? (uint64_t)w.hdr[s0 + x + 1] << 32 : 0ull);
+    d32[x] = (uint32_t)(two >> sh);
+  }
+  const uint32_t done = head + 4 * body;
+  if (lane < size - done) dst[done + lane] = src[done + lane];
+}
+
+// write: one wave per chunk
+__global__ __launch_bounds__(256) void win_write_kernel(WinArgs a) {
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.y, c = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (c >= g.max_chunks || a.ws.in.status[i] != kStOk) return;
+  const WinFrame w = win_frame(a, i);
+  if (c >= w.chunks) return;
+  uint32_t row, t0, nt, first, last, lo, hi;
+  chunk_tiles(g, w.ct, w.cx, c, &row, &t0, &nt);
+  kept_span(a, i, row, &first, &last);
+  kept_tiles(first, last, t0, nt, &lo, &hi);
+  const uint32_t size = a.ws.ent[(size_t)i * g.max_chunks + c] & 0xFFFFu;
+  uint8_t* dst = a.out + a.ws.foff[i] + a.ws.ooff[(size_t)i * g.max_chunks + c];
+  if (hi - lo == nt) {
+    copy_payload(w, w.coff[c], size, dst, lane);
+  } else if (hi == lo) {  // coded, k_dc = k_ac = 0, then two 1 bits per tile: bits [7, 7 + 2 nt) set
+    for (uint32_t b = lane; b < size; b += 64) {
+      const uint32_t from = b == 0 ? 7u : 0u, to = min(8u, 7 + 2 * nt - 8 * b);
+      dst[b] = (uint8_t)(((1u << to) - 1u) & ~((1u << from) - 1u));
+    }
+  } else {
+    const uint32_t sl = slot_of(row, first, t0, nt);
+    if (!(a.ws.cut[(size_t)i * a.slots + sl] >> 6)) return;  // coded: the place kernel's
+    // raw: the mode byte, the chunk's mask words (zero outside the window), the kept levels
+    const uint8_t* slab = a.ws.slab + ((size_t)i * a.slots + sl) * a.slot_bytes;
+    const uint32_t tb = 8 * g.nw, mbytes = tb * nt, kb = tb * (hi - lo);
+    for (uint32_t b = lane; b < size; b += 64) {
+      uint8_t v = 1;
+      if (b > mbytes) v = slab[kb + (b - 1 - mbytes)];
+      else if (b > 0) v = b - 1 >= tb * lo && b - 1 < tb * hi ? slab[b - 1 - tb * lo] : (uint8_t)0;
+      dst[b] = v;
+    }
+  }
+}
+
+// place: one wave per slot, a lane per tile -> a coded cut chunk's codewords ORed into the wave's LDS words as enc_scatter_kernel
+// places them, then stored bytewise (the chunk shares its first and last dword with its neighbours)
+__global__ __launch_bounds__(64) void win_place_kernel(WinArgs a) {
+  extern __shared__ uint32_t lds[];
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.y, sl = blockIdx.x, lane = threadIdx.x;
+  if (a.ws.in.status[i] != kStOk) return;
+  const WinFrame w = win_frame(a, i);
+  CutChunk k;
+  if (!cut_chunk(a, w, i, sl, &k)) return;
+  const uint32_t info = a.ws.cut[(size_t)i * a.slots + sl], kd = info & 7u, ka = (info >> 3) & 7u;
+  if (info >> 6) return;  // raw: the write kernel's
+  const uint32_t size = a.ws.ent[(size_t)i * g.max_chunks + k.c] & 0xFFFFu;
+  const uint8_t* slab = a.ws.slab + ((size_t)i * a.slots + sl) * a.slot_bytes;
+  for (uint32_t x = lane; x < size / 4 + 1; x += 64) lds[x] = 0;
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  if (lane == 0) put_bits(lds, 0, (kd << 1) | (ka << 4));
+  uint32_t bits_before = 7;
+  int32_t dc_before = 0;
+  for_each_cut_tile(g, k, slab, lane, [&](uint32_t t, bool keep, const uint8_t* tm, const int16_t* lev) {
+    int32_t dc = 0;
+    uint32_t len = 0, nac = 0, prev = 0;
+    if (keep)
+      for_each_level(g, tm, lev, [&](uint32_t p, int32_t v) {
+        if (p == 0) { dc = v; return; }
+        ++nac;
+        len += eg_len(p - prev - 1, 0) + eg_len(sgn(v), ka);
+        prev = p;
+      });
+    const int32_t left = __shfl_up(dc, 1, 64);
+    const uint32_t udc = sgn(dc - (lane == 0 ? dc_before : left));
+    dc_before = __shfl(dc, 63, 64);
+    len = t < k.nt ? len + eg_len(nac, 0) + eg_len(udc, kd) : 0u;
+    uint32_t pos = bits_before + wave_exclusive_scan(len);
+    bits_before += wave_sum(len);
+    if (t >= k.nt) return;
+    pos += put_eg(lds, pos, udc, kd);
+    pos += put_eg(lds, pos, nac, 0);
+    if (!keep) return;
+    prev = 0;
+    for_each_level(g, tm, lev, [&](uint32_t p, int32_t v) {
+      if (p == 0) return;
+      pos += put_eg(lds, pos, p - prev - 1, 0);
+      pos += put_eg(lds, pos, sgn(v), ka);
+      prev = p;
+    });
+  });
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  uint8_t* dst = a.out + a.ws.foff[i] + a.ws.ooff[(size_t)i * g.max_chunks + k.c];
+  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(lds);
+  for (uint32_t x = lane; x < size; x += 64) dst[x] = bytes[x];
+}
+
+// frame: one workgroup per frame -> header, types section, index, padding, or 64 zero bytes for a frame that failed
+__global__ __launch_bounds__(256) void win_frame_kernel(WinArgs a) {
+  const Geom& g = a.g;
+  const uint32_t i = blockIdx.x;
+  uint8_t* frame = a.out + a.ws.foff[i];
+  uint32_t* fw = reinterpret_cast<uint32_t*>(frame);
+  if (a.ws.in.status[i] != kStOk) {
+    if (threadIdx.x < kHeaderWords) fw[threadIdx.x] = 0;
+    return;
+  }
+  const WinFrame w = win_frame(a, i);
+  const uint32_t fbytes = a.ws.fbytes[i], lev = a.ws.levels[i], twords = w.hdr[kETypesBytes] / 4;
+  if (threadIdx.x < kHeaderWords) {
+    uint32_t v = w.hdr[threadIdx.x];
+    if (threadIdx.x == kHLevels) v = lev;
+    if (threadIdx.x == kHBytes) v = fbytes;
+    if (threadIdx.x == kESvcqBytes) v = (uint32_t)up16(g.levels_off + 2ull * lev);
+    fw[threadIdx.x] = v;
+  }
+  for (uint32_t x = threadIdx.x; x < twords; x += kThreads) fw[kHeaderWords + x] = w.hdr[kHeaderWords + x];
+  const uint32_t* ent = a.ws.ent + (size_t)i * g.max_chunks;
+  for (uint32_t c = threadIdx.x; c < w.chunks; c += kThreads) fw[kHeaderWords + twords + c] = ent[c];
+  const uint32_t last = w.chunks - 1;
+  const uint32_t used = a.ws.ooff[(size_t)i * g.max_chunks + last] + (ent[last] & 0xFFFFu);
+  for (uint32_t b = used + threadIdx.x; b < fbytes; b += kThreads) frame[b] = 0;
+}
+
 // geometry, then the limits with SVCE's worst case (make_geom divides by the tile area: only for a tile within the limit)
 int validate(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
   const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
@@ -1040,6 +1547,14 @@ int validate_fused(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_
   const int rc = validate_decode_geom(what, w, h, bw, bh, mvbw, mvbh);
   if (rc) return rc;
   return validate_limits(what, n, w, h, bw, bh, svce_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)));
+}
+
+// the window call's limits: the entropy coder's, with the window call's own worst frame
+int validate_window(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh) {
+  const int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  const bool tile_ok = (uint64_t)bw * bh <= kMaxTileCoeffs;
+  return validate_limits(what, n, w, h, bw, bh, tile_ok ? win_max_bytes(make_geom(w, h, bw, bh, mvbw, mvbh)) : 0);
 }
 
 }  // namespace
@@ -1174,6 +1689,62 @@ int svc_hip_decode_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, co
   if ((rc = check_launch("decode_entropy reconstruction"))) return rc;
   hipLaunchKernelGGL(decode_entropy_finish_kernel, dim3(32, n_frames), dim3(kThreads), 0, s, a);
   return finish_with_display("decode_entropy", "finish", display, d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+}
+
+uint64_t svc_hip_window_entropy_max_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                          uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_window("window_entropy_max_bytes", n_out, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
+  return n_out * win_max_bytes(make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h));
+}
+
+uint64_t svc_hip_window_entropy_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                                uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_window("window_entropy_workspace_bytes", n_out, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) return 0;
+  return n_out ? layout_bytes(win_ws, n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h)) : 0;
+}
+
+// Checked in the order of svc_hip_window_levels_frames, for any frame counts: geometry, limits, the d_src rule, sizes, then pointers.
+int svc_hip_window_entropy_frames(const uint8_t* d_svce, uint64_t svce_bytes, const uint64_t* d_offsets, uint32_t n_in,
+                                  const uint32_t* d_src, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                  uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, const uint32_t* d_window,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                  uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_window("window_entropy", std::max(n_out, n_in), frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(d_src || n_out == n_in, "window_entropy: without d_src output frame i is input frame i, but n_out is %u and n_in %u", n_out,
+              n_in);
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if ((rc = require_workspace("window_entropy", workspace_bytes, n_out ? layout_bytes(win_ws, n_out, g) : 0))) return rc;
+  if ((rc = require_capacity("window_entropy", "output", out_capacity, n_out * win_max_bytes(g)))) return rc;
+  if (n_out == 0) return SVC_OK;
+  SVC_REQUIRE(d_svce && d_offsets && d_workspace && d_out && d_out_offsets && d_status, "window_entropy: null pointer");
+  SVC_REQUIRE(aligned(d_svce, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_offsets, 8) && aligned(d_out_offsets, 8) &&
+                  aligned(d_src, 4) && aligned(d_window, 4) && aligned(d_status, 4),
+              "window_entropy: streams and workspace must be 16-byte aligned, offsets 8-byte, source indices, windows and status 4-byte");
+  const WinWs ws = carve(d_workspace, win_ws, n_out, g);
+  const DecArgs c{g, d_svce, svce_bytes, d_offsets, nullptr, nullptr, nullptr, ws.in, n_out};
+  const WinArgs a{g, d_svce, d_offsets, d_src, d_window, d_out, d_status, ws, win_slots(g), win_slot_bytes(g), win_max_bytes(g)};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 lanes(div_up(g.max_chunks, kThreads), n_out), slots(div_up(a.slots, kThreads), n_out);
+  hipLaunchKernelGGL(win_check_kernel, dim3(n_out), dim3(kThreads), 0, s, c, d_src, n_in);
+  if ((rc = check_launch("window_entropy check"))) return rc;
+  hipLaunchKernelGGL(win_size_kernel, lanes, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("window_entropy size"))) return rc;
+  hipLaunchKernelGGL(win_recode_kernel, slots, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("window_entropy recode"))) return rc;
+  hipLaunchKernelGGL(win_lengths_kernel, dim3(a.slots, n_out), dim3(64), 0, s, a);
+  if ((rc = check_launch("window_entropy lengths"))) return rc;
+  hipLaunchKernelGGL(win_layout_kernel, dim3(n_out), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("window_entropy layout"))) return rc;
+  if ((rc = enqueue_frame_offsets("window_entropy", 1, OffsetsJob{ws.fbytes, ws.foff, d_out_offsets}, OffsetsJob{}, n_out, stream))) return rc;
+  hipLaunchKernelGGL(win_write_kernel, dim3(div_up(g.max_chunks, kWaves), n_out), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("window_entropy write"))) return rc;
+  // the wave's LDS holds the largest coded chunk of this geometry: at most its raw form, at most the index's u16
+  const uint32_t place_lds = (uint32_t)std::min<uint64_t>(65536, (1 + (8ull * g.nw + 2ull * g.area) * g.tx) / 4 * 4 + 8);
+  hipLaunchKernelGGL(win_place_kernel, dim3(a.slots, n_out), dim3(64), place_lds, s, a);
+  if ((rc = check_launch("window_entropy place"))) return rc;
+  hipLaunchKernelGGL(win_frame_kernel, dim3(n_out), dim3(kThreads), 0, s, a);
+  return check_launch("window_entropy frame");
 }
 
 }  // extern "C"

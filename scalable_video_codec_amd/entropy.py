@@ -528,3 +528,216 @@ def encode_frames(buf, offsets, chunk_tiles=None, force_k=None) -> Tuple[bytes, 
 def decode_frames(buf, offsets) -> Tuple[bytes, np.ndarray]:
     """An SVCE batch -> (SVCQ bytes, offsets (n + 1,) u64)."""
     return _join(list(iter_frames(buf, offsets)))
+
+
+# ---- a stored SVCE stream restricted to a window, on its coded bytes (include/svc_hip.h: svc_hip_window_entropy_frames) ---------------
+
+def _walk_chunk(payload: np.ndarray, count: int, nt: int, upto: int, g: _Geom, c: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Tiles [0, upto) of a chunk of nt tiles, read as the device call reads a cut chunk: from its first tile to its last kept one and
+    no further, so the end-of-chunk checks of decode_frame are not made -> (bits (upto, area) bool, values (upto, area) i64)."""
+    area, nw = g.area, g.nw
+    bits = np.zeros((upto, area), bool)
+    vals = np.zeros((upto, area), np.int64)
+
+    def bad(why):
+        raise ValueError(f"SVCE chunk {c}: {why}")
+
+    size = payload.size
+    if size == 0:
+        bad("empty")
+    if payload[0] & 1:
+        if size != 1 + 8 * nw * nt + 2 * count:
+            bad(f"raw chunk of {size} B for {nt} tiles and {count} levels")
+        mb = np.unpackbits(payload[1:1 + 8 * nw * upto], bitorder="little").reshape(upto, nw * 64).astype(bool)
+        if mb[:, area:].any():
+            bad("raw mask bits set past the tile")
+        if int(mb.sum()) > count:
+            bad("raw masks hold more levels than the index says")
+        bits[:] = mb[:, :area]
+        lv = payload[1 + 8 * nw * nt:].view("<i2").astype(np.int64)
+        vals[bits] = lv[:int(mb.sum())]
+        return bits, vals
+    v = int.from_bytes(payload.tobytes(), "little")
+    end = 8 * size
+    kd, ka = (v >> 1) & 7, (v >> 4) & 7
+    pos = 7
+
+    def eg(k):
+        nonlocal pos
+        rest = v >> pos
+        z = (rest & -rest).bit_length() - 1 if rest else 64
+        if z > MAX_PREFIX:
+            bad("an Exp-Golomb prefix of more than 24 zeros")
+        n = z + k
+        if pos + z + 1 + n > end:
+            bad("decodes past its size")
+        w = (1 << n) | ((rest >> (z + 1)) & ((1 << n) - 1))
+        pos += z + 1 + n
+        return w - (1 << k)
+
+    def unsgn(u):
+        return (u + 1) >> 1 if u & 1 else -(u >> 1)
+
+    written, dcp = 0, 0
+    for t in range(upto):
+        dcp += unsgn(eg(kd))
+        if not -32768 <= dcp <= 32767:
+            bad("a DC level outside int16")
+        if dcp:
+            written += 1
+            vals[t, 0], bits[t, 0] = dcp, True
+        nac = eg(0)
+        if nac > area - 1:
+            bad("an AC count outside the tile")
+        p = 0
+        for _ in range(nac):
+            p += eg(0) + 1
+            if p > area - 1:
+                bad("a run past the tile")
+            lvl = unsgn(eg(ka))
+            if not -32768 <= lvl <= 32767:
+                bad("an AC level outside int16")
+            written += 1
+            vals[t, p], bits[t, p] = lvl, True
+        if written > count:
+            bad(f"decodes to more than the {count} levels of its index entry")
+    return bits, vals
+
+
+def _encode_chunk(bits: np.ndarray, vals: np.ndarray, nw: int) -> Tuple[bytes, int]:
+    """One chunk (bits, values (nt, area)) as encode_frame codes it -> (payload, levels): the k_dc and k_ac of the fewest bits (ties: the
+    smallest), raw when strictly smaller or when a set mask bit holds level 0."""
+    nt, area = bits.shape
+    cnt = int(bits.sum())
+    dc = vals[:, 0]
+    udc = _sgn(dc - np.concatenate([[0], dc[:-1]]))
+    ac_t, ac_p = np.nonzero(bits[:, 1:])
+    ac_p = ac_p + 1
+    nac = np.bincount(ac_t, minlength=nt).astype(np.int64)
+    new_tile = np.concatenate([[True], ac_t[1:] != ac_t[:-1]]) if ac_t.size else np.zeros(0, bool)
+    run = ac_p - np.where(new_tile, 0, np.concatenate([[0], ac_p[:-1]])) - 1
+    uac = _sgn(vals[ac_t, ac_p])
+    dc_bits = [int(_eg_len(udc, k).sum()) for k in range(8)]
+    ac_bits = [int(_eg_len(uac, k).sum()) for k in range(8)]
+    kd, ka = int(np.argmin(dc_bits)), int(np.argmin(ac_bits))
+    coded_bytes = (7 + int(_eg_len(nac, 0).sum()) + int(_eg_len(run, 0).sum()) + dc_bits[kd] + ac_bits[ka] + 7) // 8
+    raw_bytes = 1 + 8 * nw * nt + 2 * cnt
+    if bool((bits & (vals == 0)).any()) or raw_bytes < coded_bytes:
+        pad = np.zeros((nt, nw * 64), bool)
+        pad[:, :area] = bits
+        return b"\x01" + np.packbits(pad, axis=-1, bitorder="little").tobytes() + vals[bits].astype("<i2").tobytes(), cnt
+    acc, pos = kd << 1 | ka << 4, 7
+
+    def put(u, k):
+        nonlocal acc, pos
+        w = int(u) + (1 << k)
+        n = w.bit_length() - 1
+        pos += n - k
+        acc |= (1 | (w & ((1 << n) - 1)) << 1) << pos
+        pos += n + 1
+
+    j = 0
+    for t in range(nt):
+        put(udc[t], kd)
+        put(nac[t], 0)
+        for _ in range(int(nac[t])):
+            put(run[j], 0)
+            put(uac[j], ka)
+            j += 1
+    assert (pos + 7) // 8 == coded_bytes
+    return acc.to_bytes(coded_bytes, "little"), cnt
+
+
+def chunk_classes(svce, window) -> np.ndarray:
+    """Per chunk of a well-formed SVCE frame: 0 kept whole, 1 dropped whole, 2 cut by a vertical edge of the window (None: all kept)."""
+    return _window_frame(svce, window)[1]
+
+
+def _window_frame(svce, window) -> Tuple[bytes, np.ndarray]:
+    from . import layers
+    b = _u8(svce)
+    hdr, sizes, counts = parse_frame(b)
+    g = _Geom(hdr["frame_w"], hdr["frame_h"], hdr["block_w"], hdr["block_h"], hdr["mv_block_w"], hdr["mv_block_h"], hdr["chunk_tiles"])
+    types = _decode_types(b[HEADER_BYTES:HEADER_BYTES + hdr["types_bytes"]], g.mvb)
+    if 1 + (8 * g.nw + 2 * g.area) * min(g.ct, g.tx) > 0xFFFF:
+        raise ValueError(f"SVCE chunk_tiles {g.ct}: a raw chunk of {min(g.ct, g.tx)} tiles is above the index's u16, so a cut chunk could not "
+                         "always be written")
+    keep = np.ones((g.ty, g.tx), bool)
+    if window is not None:
+        lh = {k: hdr[k] for k in layers.GEOMETRY}
+        _, ox, oy = layers._tile_maps(lh, types.reshape(g.mfh, g.mfw))
+        keep = layers._contains(window, ox, oy)
+    C = g.chunks
+    payload_off = HEADER_BYTES + hdr["types_bytes"] + 4 * C
+    start = payload_off + np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    cls = np.zeros(C, np.int64)
+    out_payload, out_count, empty = [], [], {}
+    for c in range(C):
+        row, t0 = divmod(c, g.cx)
+        t0 *= g.ct
+        nt = int(g.chunk_nt[c])
+        k = keep[row % g.ty, t0:t0 + nt]
+        if k.all():
+            out_payload.append(b[start[c]:start[c] + sizes[c]].tobytes())
+            out_count.append(int(counts[c]))
+        elif not k.any():
+            cls[c] = 1
+            if nt not in empty:
+                empty[nt] = _encode_chunk(np.zeros((nt, g.area), bool), np.zeros((nt, g.area), np.int64), g.nw)[0]
+            out_payload.append(empty[nt])
+            out_count.append(0)
+        else:
+            cls[c] = 2
+            hi = int(np.flatnonzero(k)[-1]) + 1
+            bits = np.zeros((nt, g.area), bool)
+            vals = np.zeros((nt, g.area), np.int64)
+            bits[:hi], vals[:hi] = _walk_chunk(b[start[c]:start[c] + sizes[c]], int(counts[c]), nt, hi, g, c)
+            bits[~k], vals[~k] = False, 0
+            pay, cnt = _encode_chunk(bits, vals, g.nw)
+            out_payload.append(pay)
+            out_count.append(cnt)
+    out_sizes = np.array([len(p) for p in out_payload], np.int64)
+    level_count = int(sum(out_count))
+    frame_bytes = _up(payload_off + int(out_sizes.sum()), 16)
+    if frame_bytes > _up(g.levels_off + 6 * g.w * g.h + 4 + 5 * 3 * g.ty * g.tx, 16):
+        raise ValueError(f"the windowed frame of {frame_bytes} B is above the worst canonical frame: kept chunks larger than their raw form")
+    words = b[:HEADER_BYTES].view("<u4").copy()
+    words[10], words[12], words[13] = level_count, frame_bytes, g.svcq_bytes(level_count)
+    index = (out_sizes | (np.array(out_count, np.int64) << 16)).astype("<u4")
+    body = words.tobytes() + b[HEADER_BYTES:HEADER_BYTES + hdr["types_bytes"]].tobytes() + index.tobytes() + b"".join(out_payload)
+    return body + bytes(frame_bytes - len(body)), cls
+
+
+def window_frame(svce, window) -> bytes:
+    """One SVCE frame restricted to the tiles whose origin the window (x, y, w, h in padded coordinates, or None: every tile) contains,
+    on its coded bytes and its own chunk grid: what svc_hip_window_entropy_frames writes.  A chunk whose tiles are all kept keeps its
+    payload and index entry, canonical or not; a chunk with no kept tile becomes the empty coded chunk (ceil((7 + 2 nt) / 8) bytes, no
+    levels); a chunk a vertical window edge cuts is read up to its last kept tile and coded again as encode_frame codes it, with the
+    tiles outside the window all zero.  Header words 0 .. 9, 11, 14, 15 and the types section as they are; word 10 the output chunks'
+    levels, word 13 the SVCQ frame's bytes for them, word 12 this frame's.  For a frame this module's encoder wrote the result is
+    encode_frame(layers.window_frame(decode_frame(svce), window), chunk_tiles=the frame's).  ValueError where the device call flags the
+    frame: parse_frame's checks, a types section decode_frame rejects, a chunk_tiles whose raw chunk is above 65535 B, a cut chunk whose
+    read part is malformed, an output above the worst canonical frame.  What lies outside the read part of a cut chunk, or inside a
+    kept or a dropped chunk, is not read: it passes through or is dropped, as on the device."""
+    return _window_frame(svce, window)[0]
+
+
+def window_frames(stream, offsets, windows, src=None) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_window_entropy_frames writes for frames that pass their checks -> (bytes, offsets (n_out + 1,) u64); windows and src
+    as layers.window_frames takes them."""
+    b = _u8(stream)
+    offs = [int(o) for o in np.asarray(offsets).reshape(-1)]
+    n_in = len(offs) - 1
+    idx = list(range(n_in)) if src is None else [int(i) for i in np.asarray(src).reshape(-1)]
+    win = None if windows is None else np.asarray(windows).reshape(len(idx), 4)
+    frames = []
+    for i, f in enumerate(idx):
+        if not 0 <= f < n_in:
+            raise ValueError(f"output frame {i} names input frame {f} of {n_in}")
+        lo, hi = offs[f], offs[f + 1]
+        if lo % 16 or hi < lo or hi > b.size:
+            raise ValueError(f"SVCE frame offsets out of order, misaligned or past the stream: {lo}, {hi}")
+        if parse_frame(b[lo:hi])[0]["frame_bytes"] != hi - lo:
+            raise ValueError(f"SVCE frame at {lo} has a frame_bytes other than its offsets' {hi - lo}")
+        frames.append(window_frame(b[lo:hi], None if win is None else win[i]))
+    return _join(frames)

@@ -154,6 +154,10 @@ SIGNATURES = {
     # a stored SVCQ stream restricted to a window per output frame (csrc/levels.hip; host statement: layers.window_frames)
     "svc_hip_window_levels_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_window_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    # a stored SVCE stream restricted to a window per output frame, on its coded bytes (csrc/entropy.hip; host statement: entropy.window_frames)
+    "svc_hip_window_entropy_max_bytes": (_u64, [_u32] * 7),
+    "svc_hip_window_entropy_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_window_entropy_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     # a stored fine SVCQ stream split into a base at any steps plus its enhancement (csrc/levels.hip; host statement: layers.split_frames)
     "svc_hip_split_levels_workspace_bytes": (_u64, [_u32] * 8),
     "svc_hip_split_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 10 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
@@ -1137,6 +1141,49 @@ def window_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h:
                                                None if win is None else _dev(win, torch.int32), _dev(workspace, torch.uint8),
                                                workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
                                                _dev(status, torch.int32), _stream()))
+    return out, out_offsets, status
+
+
+def window_entropy_max_bytes(n_out: int, w: int, h: int, block, mv_block) -> int:
+    """Worst-case bytes of n_out frames of window_entropy_frames (a canonical frame with a chunk per tile); 0 where it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_window_entropy_max_bytes(n_out, w, h, bw, bh, mbw, mbh))
+
+
+def window_entropy_workspace_bytes(n_out: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of window_entropy_frames for n_out output frames; 0 for a geometry it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_window_entropy_workspace_bytes(n_out, w, h, bw, bh, mbw, mbh))
+
+
+def window_entropy_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, window=None, src=None,
+                          out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """window_levels_frames on an SVCE stream, on its coded bytes (include/svc_hip.h; the numpy statement is entropy.window_frames):
+    chunks inside the window are copied, chunks outside it become the empty chunk, and only the chunks a window edge cuts are re-coded.
+    window, src as window_levels_frames takes them.  -> (SVCE stream u8 of the worst-case size, offsets (n_out + 1,) i64, status (n_out,)
+    i32 with the entropy decoder's frame-check codes, 9 for a malformed cut chunk; a frame that fails is 64 zero bytes).  `out` must not
+    overlap `frames`."""
+    n_in = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    s = None if src is None else torch.as_tensor(src, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    n_out = n_in if s is None else s.numel()
+    if out is None:
+        out = torch.empty(max(window_entropy_max_bytes(n_out, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(window_entropy_workspace_bytes(n_out, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(max(n_out, 1), dtype=torch.int32, device=dev)[:n_out]
+    win = _rects(window, n_out, dev)
+    _check(load().svc_hip_window_entropy_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n_in,
+                                                None if s is None else _dev(s, torch.int32), n_out, w, h, bw, bh, mbw, mbh,
+                                                None if win is None else _dev(win, torch.int32), _dev(workspace, torch.uint8),
+                                                workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
+                                                _dev(status, torch.int32), _stream()))
     return out, out_offsets, status
 
 

@@ -36,6 +36,14 @@
                                                    enhancement (the call it sits beside); wall time per call over 20 back-to-back calls, the
                                                    bytes each call reads and writes and their fraction of the HBM peak, and the split's base
                                                    against the encoder's base at (1, 640) (an even ratio: they differ)
+  python tools/dct_pack_probe.py window-entropy [C3|C5]
+                                                   a stored entropy-coded enhancement served under a gaze, the same batch of 16 at
+                                                   (1, 640, 1) with a 256 x 256 window per frame: svc_hip_window_entropy_frames on the stored
+                                                   SVCE stream against the three-call route on the same stream (svc_hip_entropy_decode_frames,
+                                                   svc_hip_window_levels_frames, svc_hip_entropy_encode_frames), then 4 viewers (n_out = 64
+                                                   through d_src; the three-call route decodes the 16 stored frames once); wall time per call
+                                                   over 20 back-to-back calls, the two routes interleaved, bytes in and out and the share of
+                                                   chunks in each class; the bytes are compared
 """
 import os
 import sys
@@ -324,6 +332,103 @@ def window(cfg) -> None:
           f"({t_win4[0] / t_enc4[0]:.3f} of the encodes); same bytes; served {int(oo4[-1]) / n_out / 1e6:.3f} MB per frame", flush=True)
 
 
+def window_entropy(cfg) -> None:
+    import numpy as np
+    from scalable_video_codec_amd import entropy
+    dev = torch.device("cuda")
+    n, viewers = 16, 4
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    lbase, whole = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2))
+    ws2 = torch.empty(native.dct_pack_layers_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    sync = torch.cuda.synchronize
+
+    def fmt(t):
+        return f"{t[0]:.3f} .. {t[1]:.3f}"
+
+    def rects(viewer):  # the windows of `window`
+        out = []
+        for f in range(n):
+            x = (pw - 256) // 2 + 32 * ((f + 3 * viewer) % 7 - 3) + 64 * (viewer - 1)
+            y = (ph - 256) // 2 + 16 * ((f + viewer) % 5 - 2)
+            out.append((x // 16 * 16, y // 16 * 16, 256, 256))
+        return out
+
+    # what the server holds: the every-tile enhancement, entropy-coded
+    _, _, _, offs_q = native.dct_pack_layers_frames(bgr, block, types, mv, 1, 640, 1, window=None, base_out=lbase, enh_out=whole, workspace=ws2)
+    sync()
+    uq = int(offs_q[-1])
+    stored, offs_s, st = native.entropy_encode_frames(whole[:uq], offs_q.clone(), pw, ph, block, mv)
+    sync()
+    assert not st.any()
+    us = int(offs_s[-1])
+    stored, offs_s = stored[:us].clone(), offs_s.clone()
+    del lbase, whole, ws2, bgr
+    torch.cuda.empty_cache()
+    wse = torch.empty(native.entropy_workspace_bytes(viewers * n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+
+    for name, n_out, src, win_rects in (("(a) one viewer", n, None, rects(0)),
+                                        (f"(b) {viewers} viewers, n_out = {viewers * n} through d_src", viewers * n,
+                                         [f for _ in range(viewers) for f in range(n)], [r for v in range(viewers) for r in rects(v)])):
+        win = torch.tensor(win_rects, dtype=torch.int32, device=dev)
+        srct = None if src is None else torch.tensor(src, dtype=torch.int32, device=dev)
+        out = torch.empty(native.window_entropy_max_bytes(n_out, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+        ws = torch.empty(native.window_entropy_workspace_bytes(n_out, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+        oo, stw = torch.empty(n_out + 1, dtype=torch.int64, device=dev), torch.empty(n_out, dtype=torch.int32, device=dev)
+        # the three-call route's buffers
+        q = torch.empty(cap, dtype=torch.uint8, device=dev)
+        qo = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        wq = torch.empty(native.levels_max_bytes(n_out, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+        wo, wst = torch.empty(n_out + 1, dtype=torch.int64, device=dev), torch.empty(n_out, dtype=torch.int32, device=dev)
+        wsw = torch.empty(native.window_levels_workspace_bytes(n_out, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+        e = torch.empty(native.entropy_max_bytes(n_out, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+        eo, est = torch.empty(n_out + 1, dtype=torch.int64, device=dev), torch.empty(n_out, dtype=torch.int32, device=dev)
+
+        def serve():
+            return native.window_entropy_frames(stored, offs_s, pw, ph, block, mv, window=win, src=srct, out=out, out_offsets=oo,
+                                                workspace=ws, status=stw)
+
+        def three():
+            native.entropy_decode_frames(stored, offs_s, pw, ph, block, mv, out=q, out_offsets=qo, workspace=wse)
+            native.window_levels_frames(q, qo, pw, ph, block, mv, window=win, src=srct, out=wq, out_offsets=wo, workspace=wsw, status=wst)
+            # (the encoder reads the stream's bytes through its offsets: the whole worst-case buffer is handed over, as a server would)
+            native.entropy_encode_frames(wq, wo, pw, ph, block, mv, out=e, out_offsets=eo, workspace=wse, status=est)
+
+        if src is None:
+            print(f"{cfg.name} batch of {n}, stored SVCE enhancement at (1, 640, 1), a 256 x 256 window per frame, ms per call (best .. worst of 3 "
+                  f"runs of 20 back-to-back calls; the routes interleaved: three, one, three, one)", flush=True)
+        t3a = _per_step(three, sync, steps=20)
+        t1a = _per_step(serve, sync, steps=20)
+        t3b = _per_step(three, sync, steps=20)
+        t1b = _per_step(serve, sync, steps=20)
+        serve()
+        three()
+        sync()
+        used = int(oo[-1])
+        assert not stw.any() and not est.any() and not wst.any()
+        assert torch.equal(oo, eo) and torch.equal(out[:used], e[:used]), "the windowed SVCE stream differs from the three-call route's"
+        # the share of chunks in each class, from the statement's classification of the first frames (a frame each of the first viewer's)
+        host, ho = stored.cpu().numpy(), offs_s.cpu().tolist()
+        cls = np.zeros(3, np.int64)
+        for i in range(2):
+            f = i if src is None else src[i]
+            cls += np.bincount(entropy.chunk_classes(host[ho[f]:ho[f + 1]], win_rects[i]), minlength=3)
+        t3, t1 = (min(t3a[0], t3b[0]), max(t3a[1], t3b[1])), (min(t1a[0], t1b[0]), max(t1a[1], t1b[1]))
+        uq_out = int(wo[-1])
+        print(f"{name}: three calls {fmt(t3a)}, again {fmt(t3b)}; one call {fmt(t1a)}, again {fmt(t1b)} "
+              f"({t3[0] / t1[0]:.2f}x by the best of each, {t3[1] / t1[1]:.2f}x by the worst); same bytes and offsets", flush=True)
+        print(f"    one call: reads {us / n / 1e6:.3f} MB per stored frame (only kept and cut payloads, the header, types and index of it), writes "
+              f"{used / n_out / 1e6:.3f} MB per served frame; workspace {ws.numel() / n_out / 1e6:.3f} MB per served frame", flush=True)
+        print(f"    three calls: SVCE in {us / n / 1e6:.3f} MB, SVCQ out {uq / n / 1e6:.3f} MB per stored frame; windowed SVCQ "
+              f"{uq_out / n_out / 1e6:.3f} MB per served frame written and read again; SVCE out {used / n_out / 1e6:.3f} MB", flush=True)
+        print(f"    chunks per frame (two frames): kept {cls[0] / cls.sum() * 100:.1f} %, dropped {cls[1] / cls.sum() * 100:.1f} %, cut "
+              f"{cls[2] / cls.sum() * 100:.1f} % ({cls[2] // 2} cut chunks walked per frame of {cls.sum() // 2})", flush=True)
+        del out, ws, q, wq, wsw, e
+        torch.cuda.empty_cache()
+
+
 HBM_PEAK = 8.0e12  # bytes per second, the MI355X's HBM3E
 
 
@@ -468,6 +573,8 @@ if __name__ == "__main__":
         layers(_cfg(sys.argv, 2))
     elif mode == "window":
         window(_cfg(sys.argv, 2))
+    elif mode == "window-entropy":
+        window_entropy(_cfg(sys.argv, 2))
     elif mode == "split":
         split(_cfg(sys.argv, 2))
     else:
