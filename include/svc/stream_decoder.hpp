@@ -43,7 +43,8 @@ struct DecodedBatch {
   uint32_t width = 0, height = 0;  // of a display frame
   const uint8_t* bgr = nullptr;    // [count][height][width][3] u8 B,G,R
   const uint32_t* status = nullptr;  // [count]: 0, or svc_hip_unpack_levels_frames's code (the frame is then all zeros); an SVCE
-                                    // frame the entropy decoder refuses: svc_hip_entropy_decode_frames's code; DecodeWire: 0
+                                    // frame the entropy decoder refuses: svc_hip_entropy_decode_frames's code; DecodeWire: 0;
+                                    // DecodeLayers: stated there
 };
 
 // Where the time of one Decode() / DecodeWire() went: wall time of the calling thread; per-stream device times summed over the batches (the
@@ -73,6 +74,17 @@ class StreamDecoder {
   // (else std::runtime_error); any later frame that does not match is reported in DecodedBatch::status, not thrown.  gaze may be
   // empty (no gaze).  sink is called once per batch, in stream order, from this thread.
   void Decode(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const Gaze& gaze, const Sink& sink);
+
+  // Two layers (include/svc_hip.h, "Two layers"): a base stream and its enhancement stream, n_frames frames each, the shape of
+  // EncodedBatch::compact / enhancement.  Each stream is SVCQ or SVCE by its own first frame's magic (an SVCE stream goes through
+  // svc_hip_entropy_decode_frames first); the geometry comes from the base's first header, and the enhancement's first header must parse
+  // and name the same geometry (else std::runtime_error).  Schedule, gaze rectangles, display size and statistics as Decode; the device
+  // call is svc_hip_decode_layers_frames: inside the gaze a tile decodes at the enhancement's step.  With an empty `gaze` the
+  // enhancement is not read (it may be null) and the call is Decode on the base; a frame whose callback returns false decodes as the
+  // base alone.  DecodedBatch::status: the entropy decoder's code for the base frame if it is not 0, else 0x100 | its code for the
+  // enhancement frame, else the code of svc_hip_decode_layers_frames.  One decoder serves Decode, DecodeWire and DecodeLayers in any order.
+  void DecodeLayers(const uint8_t* base, const uint64_t* base_offsets, const uint8_t* enh, const uint64_t* enh_offsets, uint32_t n_frames,
+                    const Gaze& gaze, const Sink& sink);
 
   // stream: a whole wire stream of `bytes` bytes in host memory, the 32-byte Header (libs/codec.hpp:8-17) first, then frame_count
   // frames of records.  svc_hip_wire_layout decides how it is read (the decoder's padded tile grid, or the reference encoder's

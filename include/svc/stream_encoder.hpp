@@ -57,6 +57,18 @@ struct StreamEncoderConfig {
   bool entropy = false;            // with `compact`, not with a budget: every packed frame is coded losslessly on the device ("SVCE",
                                    // svc_hip_entropy_encode_frames) and EncodedBatch::compact carries the SVCE frames; d2h_bytes counts
                                    // the coded bytes.  A budget counts SVCQ bytes, so entropy with compact_budget throws at construction
+  uint32_t enh_step = 0;           // with `compact`: two layers (include/svc_hip.h, "Two layers").  EncodedBatch::compact carries the base
+                                   // at (fg_step, bg_step), EncodedBatch::enhancement the stream that lifts tiles to enh_step, which
+                                   // must divide both.  For every geometry the route is svc_hip_dct_frames (raw planes) then
+                                   // svc_hip_pack_layers_frames; with `entropy` both streams are coded.  0 = one layer.  Not with
+                                   // `wire`, and not with compact_budget (the budget counts one stream): both throw at construction, as
+                                   // do steps the C ABI refuses, with its message
+  std::function<bool(uint32_t frame, uint32_t xywh[4])> enh_window;  // with enh_step: the window of each encoded frame.  Empty: every
+                                   // tile is enhanced (the store-once case: svc_hip_window_levels_frames serves any viewer later).
+                                   // Otherwise called on the thread that calls Encode(), while a batch is staged, once per encoded
+                                   // frame in clip order; `frame` is the clip index EncodedBatch::first_frame counts in; it fills x, y,
+                                   // w, h in padded coordinates (the containment rule of the gaze, on the tile origin); false = an
+                                   // empty window
 };
 
 // One finished batch; the pointers are pinned host memory owned by the encoder and stay valid
@@ -80,6 +92,9 @@ struct EncodedBatch {
   uint64_t compact_bytes = 0;                 // = compact_offsets[count]
   const uint32_t* compact_choice = nullptr;   // compact_budget != 0: [count] the ladder entry each frame was packed with, bit 31 set
                                               // when even the last entry is over that frame's budget
+  const uint8_t* enhancement = nullptr;           // enh_step != 0: `count` frames of the enhancement stream (SVCQ, or SVCE with entropy),
+  const uint64_t* enhancement_offsets = nullptr;  // [count + 1], and
+  uint64_t enhancement_bytes = 0;                 // = enhancement_offsets[count]; compact* is then the base.  Lifetime as compact
 };
 
 // Where the time of one Encode() went (round 6: the PCIe-inclusive rate explains itself).  Host clocks are wall time of the CALLING thread;
@@ -95,7 +110,7 @@ struct EncodeStats {
   double deliver_wait_ms = 0;  // host: waiting for a batch's results before handing it to the sink
   double sink_ms = 0;          // host: inside the caller's sink
   double h2d_ms = 0, kernels_ms = 0, d2h_ms = 0;  // device, per stream
-  uint64_t h2d_bytes = 0, d2h_bytes = 0;  // bytes actually moved (compact: the used bytes of the stream)
+  uint64_t h2d_bytes = 0, d2h_bytes = 0;  // bytes actually moved (compact: the used bytes of the stream; two layers: of both)
   uint32_t over_budget_frames = 0;        // compact_budget != 0: frames that no ladder entry fit into (compact_choice bit 31)
 };
 

@@ -766,6 +766,37 @@ int svc_hip_dct_pack_layers_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
                                    uint8_t* d_enh_out, uint64_t enh_capacity,
                                    uint64_t* d_enh_offsets /* [n_frames + 1] */, void* stream);
 
+/* The planes route of the same pair, for any geometry the SVCQ pack takes (tiles up to 4096
+ * coefficients, non-square, any MV block the format admits): d_planes [n][3][H][W] f32 are RAW
+ * coefficient planes as svc_hip_dct_frames writes them.  Base: byte for byte what
+ * svc_hip_pack_levels_frames writes for these planes at (fg_step, bg_step), header word 11
+ * (inexact, not 0 for raw planes) included.  Enhancement: as stated above, Lb and Lf both from
+ * the same f32 coefficient through that pack's quantiser (roundf(c / step) clamped to int16), d
+ * in int32 stored as its low 16 bits, inexact 0.  So the base is the direct quantisation for any
+ * ratio (svc_hip_split_levels_frames on a stored fine stream is not, at the ties of an even one).
+ * Checked for any n_frames and before any pointer, in the order of
+ * svc_hip_dct_pack_layers_frames: geometry, steps, the int16 bounds (255 * sqrt(block_w *
+ * block_h) / enh_step > 32767, or max(fg_step, bg_step) / enh_step > 32766:
+ * SVC_ERR_UNSUPPORTED), limits, workspace, base_capacity then enh_capacity against
+ * svc_hip_levels_max_bytes; n_frames == 0 then returns SVC_OK; then pointers (planes, outputs
+ * and workspace 16-byte aligned, offsets 8-byte, types and window 4-byte).  The query returns 0
+ * where the call refuses.  Only enqueues; every output byte is stored once (two calls write the
+ * same bytes), nothing is written past offsets[n_frames], and the workspace may hold anything
+ * on entry. */
+uint64_t svc_hip_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w,
+                                             uint32_t frame_h, uint32_t block_w, uint32_t block_h);
+int svc_hip_pack_layers_frames(const float* d_planes, const uint32_t* d_block_types,
+                               uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                               uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                               uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                               uint32_t enh_step,
+                               const uint32_t* d_window /* [n_frames][4] x, y, w, h (padded); NULL = every tile */,
+                               uint8_t* d_workspace, uint64_t workspace_bytes,
+                               uint8_t* d_base_out, uint64_t base_capacity,
+                               uint64_t* d_base_offsets /* [n_frames + 1] */,
+                               uint8_t* d_enh_out, uint64_t enh_capacity,
+                               uint64_t* d_enh_offsets /* [n_frames + 1] */, void* stream);
+
 /* svc_hip_decode_levels_frames on a base and an enhancement stream: fg_step / bg_step are the
  * decoder's steps for the tiles outside the gaze, d_rec, d_display and the display size as there.
  * With d_gaze == NULL no tile takes the enhancement: the enhancement stream is neither checked

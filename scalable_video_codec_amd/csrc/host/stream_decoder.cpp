@@ -30,16 +30,59 @@ struct Slot {
   DevBuf<uint64_t> off;
   DevBuf<uint32_t> gaze, status, estatus;  // estatus: svc_hip_entropy_decode_frames's codes (SVCE)
   PinBuf<uint32_t> pin_estatus;
+  // DecodeLayers: the enhancement stream's batch beside the base's, and the entropy decoder's codes for it
+  PinBuf<uint8_t> pin_enh;
+  DevBuf<uint8_t> enh;
+  PinBuf<uint64_t> pin_enh_off;
+  DevBuf<uint64_t> enh_off;
+  DevBuf<uint32_t> enh_estatus;
+  PinBuf<uint32_t> pin_enh_estatus;
   uint32_t first = 0, count = 0;
 };
 
+// The bytes of frames first .. first + cnt of a stream in host memory -> the slot's pinned buffer, their offsets relative to it:
+// from the batch's lowest offset (rounded down to 16: frames stay aligned) to its highest, inside the stream; an offset outside it
+// becomes one the kernels refuse (status 1), so a malformed frame is reported, never read past the copy.  -> the bytes staged
+uint64_t StageFrames(CopyCrew& crew, const uint8_t* stream, const uint64_t* offsets, uint64_t total, uint32_t first, uint32_t cnt,
+                     PinBuf<uint8_t>& pin, DevBuf<uint8_t>& dev, uint64_t* pin_off) {
+  uint64_t lo = total, hi = 0;
+  for (uint32_t i = first; i <= first + cnt; ++i) {
+    const uint64_t o = std::min(offsets[i], total);
+    lo = std::min(lo, o); hi = std::max(hi, o);
+  }
+  lo &= ~(uint64_t)15;
+  const uint64_t bytes = hi - lo;
+  if (pin.n < std::max<uint64_t>(bytes, 16)) {  // grown on demand: a batch of 1080p frames is about 17 MB
+    const size_t cap = (size_t)(bytes + bytes / 4 + 4095) & ~(size_t)4095;
+    pin.Alloc(kWho, cap); dev.Alloc(kWho, cap);
+  }
+  crew.Copy(pin.p, stream + lo, bytes);
+  for (uint32_t i = 0; i <= cnt; ++i) {
+    const uint64_t o = offsets[first + i];
+    pin_off[i] = o <= total ? o - lo : ~(uint64_t)15;
+  }
+  return bytes;
+}
+
+// the first frame's header of a stream of n_frames >= 1 frames, which must open an SVCQ v1 or SVCE v1 frame
+void FirstHeader(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const char* which, uint32_t hdr[kHeaderWords]) {
+  const uint64_t total = offsets[n_frames];  // the stream's bytes, from offsets[0] on
+  if (offsets[0] % 16 || offsets[0] > total || total - offsets[0] < kHeaderBytes || offsets[1] < offsets[0] + kHeaderBytes)
+    throw std::runtime_error(std::string("svc::StreamDecoder: the ") + which + "first frame's header is out of range");
+  std::memcpy(hdr, stream + offsets[0], kHeaderWords * sizeof(uint32_t));
+  if ((hdr[kHMagic] != kMagicQ && hdr[kHMagic] != kMagicE) || hdr[kHVersion] != kVersion)
+    throw std::runtime_error(std::string("svc::StreamDecoder: the ") + which + "stream does not open with an SVCQ v1 or SVCE v1 header");
+}
+
 // A batch that has landed goes to the sink.  svce_status: a frame the entropy decoder refused is zeros to the SVCQ decoder (status 2),
 // so the entropy decoder's code is reported instead.
-void Deliver(Slot& s, uint32_t dw, uint32_t dh, bool svce_status, DecodeStats& st, const StreamDecoder::Sink& sink) {
+// enh_svce_status (DecodeLayers): likewise for the enhancement frame, as kStEnhancement | its code, where the base frame's is 0.
+void Deliver(Slot& s, uint32_t dw, uint32_t dh, bool svce_status, bool enh_svce_status, DecodeStats& st, const StreamDecoder::Sink& sink) {
   st.frames += s.count;
-  if (svce_status)
-    for (uint32_t i = 0; i < s.count; ++i)
-      if (s.pin_estatus.p[i]) s.pin_status.p[i] = s.pin_estatus.p[i];
+  for (uint32_t i = 0; i < s.count; ++i) {
+    if (svce_status && s.pin_estatus.p[i]) s.pin_status.p[i] = s.pin_estatus.p[i];
+    else if (enh_svce_status && s.pin_enh_estatus.p[i]) s.pin_status.p[i] = kStEnhancement | s.pin_enh_estatus.p[i];
+  }
   DecodedBatch b;
   b.first_frame = s.first; b.count = s.count; b.width = dw; b.height = dh;
   b.bgr = s.pin_disp.p; b.status = s.pin_status.p;
@@ -55,8 +98,12 @@ struct StreamDecoder::Impl {
   uint64_t disp_bytes = 0, ws_bytes = 0;
   bool wire = false;        // the buffers are sized for DecodeWire
   bool svce = false;        // Decode: the stream is SVCE, decoded to SVCQ in q first
+  bool layered = false;     // the buffers are sized for DecodeLayers
+  bool enh_svce = false;    // DecodeLayers: the enhancement stream is SVCE, decoded to SVCQ in eq first
   DevBuf<uint8_t> q, ews;   // SVCE: the batch's SVCQ frames and the coder's workspace (the kernels' stream only)
   DevBuf<uint64_t> qoff;
+  DevBuf<uint8_t> eq;       // the same for the enhancement stream (one workspace: the two calls follow each other)
+  DevBuf<uint64_t> eqoff;
   uint64_t q_bytes = 0, ews_bytes = 0;
   uint64_t frame_bytes = 0; // DecodeWire: bytes of one frame's records
   DevBuf<float> rec;        // the kernels' stream only: one for all slots
@@ -66,22 +113,28 @@ struct StreamDecoder::Impl {
   std::unique_ptr<BatchPipe> pipe;  // (after the buffers: its streams synchronise before those go)
   DecodeStats stats;
 
-  void Size(const uint32_t* hdr, bool entropy) {
+  // layers: for DecodeLayers (the workspace of svc_hip_decode_layers_frames; enh_entropy = the enhancement stream is SVCE)
+  void Size(const uint32_t* hdr, bool entropy, bool layers = false, bool enh_entropy = false) {
     const uint32_t w = hdr[kHWidth], h = hdr[kHHeight], tw = hdr[kHTileW], th = hdr[kHTileH], mw = hdr[kHMvW], mh = hdr[kHMvH];
     const uint32_t want_dw = c.display_w ? c.display_w : w, want_dh = c.display_h ? c.display_h : h;
-    if (!wire && entropy == svce && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
+    if (!wire && entropy == svce && layers == layered && enh_entropy == enh_svce && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
       return;
     pipe->SyncStreams();
-    const uint64_t need_ws = svc_hip_decode_levels_workspace_bytes(c.batch, w, h, tw, th);
+    const uint64_t need_ws = layers ? svc_hip_decode_layers_workspace_bytes(c.batch, w, h, tw, th)
+                                    : svc_hip_decode_levels_workspace_bytes(c.batch, w, h, tw, th);
     if (!need_ws) Abi(SVC_ERR_UNSUPPORTED, "no decoder for the first frame's geometry");
     if (want_dw > w || want_dh > h) throw std::runtime_error("svc::StreamDecoder: the display size exceeds the padded frame");
-    if (entropy) {
+    if (entropy || enh_entropy) {
       q_bytes = svc_hip_levels_max_bytes(c.batch, w, h, tw, th, mw, mh);
       ews_bytes = svc_hip_entropy_workspace_bytes(c.batch, w, h, tw, th, mw, mh);
       if (!q_bytes || !ews_bytes) Abi(SVC_ERR_UNSUPPORTED, "no entropy decoder for the first frame's geometry");
-      q.Alloc(kWho, q_bytes); ews.Alloc(kWho, ews_bytes); qoff.Alloc(kWho, c.batch + 1);
+      ews.Alloc(kWho, ews_bytes);
+      if (entropy) { q.Alloc(kWho, q_bytes); qoff.Alloc(kWho, c.batch + 1); }
+      if (enh_entropy) { eq.Alloc(kWho, q_bytes); eqoff.Alloc(kWho, c.batch + 1); }
     }
     svce = entropy;
+    layered = layers;
+    enh_svce = enh_entropy;
     wire = false;
     pw = w; ph = h; bw = tw; bh = th; mbw = mw; mbh = mh; dw = want_dw; dh = want_dh;
     disp_bytes = (uint64_t)dw * dh * 3;
@@ -145,6 +198,8 @@ StreamDecoder::StreamDecoder(const StreamDecoderConfig& config) : p_(new Impl) {
     s->pin_gaze.Alloc(kWho, 4 * B); s->gaze.Alloc(kWho, 4 * B);
     s->pin_status.Alloc(kWho, B); s->status.Alloc(kWho, B);
     s->pin_estatus.Alloc(kWho, B); s->estatus.Alloc(kWho, B);
+    s->pin_enh_off.Alloc(kWho, B + 1); s->enh_off.Alloc(kWho, B + 1);
+    s->pin_enh_estatus.Alloc(kWho, B); s->enh_estatus.Alloc(kWho, B);
     m.slots.push_back(std::move(s));
   }
 }
@@ -158,39 +213,18 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
   if (n_frames == 0) { m.stats = DecodeStats{}; return; }
   if (!stream || !offsets) throw std::runtime_error("svc::StreamDecoder: null stream");
   const uint64_t total = offsets[n_frames];  // the stream's bytes, from offsets[0] on
-  if (offsets[0] % 16 || offsets[0] > total || total - offsets[0] < kHeaderBytes || offsets[1] < offsets[0] + kHeaderBytes)
-    throw std::runtime_error("svc::StreamDecoder: the first frame's header is out of range");
   uint32_t hdr[kHeaderWords];
-  std::memcpy(hdr, stream + offsets[0], sizeof(hdr));
-  if ((hdr[kHMagic] != kMagicQ && hdr[kHMagic] != kMagicE) || hdr[kHVersion] != kVersion)
-    throw std::runtime_error("svc::StreamDecoder: the stream does not open with an SVCQ v1 or SVCE v1 header");
+  FirstHeader(stream, offsets, n_frames, "", hdr);
   m.Size(hdr, hdr[kHMagic] == kMagicE);
   const uint32_t B = c.batch;
 
   DecodeStats st;
-  m.pipe->Begin([&](uint32_t slot) { Deliver(*m.slots[slot], m.dw, m.dh, m.svce, st, sink); });
+  m.pipe->Begin([&](uint32_t slot) { Deliver(*m.slots[slot], m.dw, m.dh, m.svce, false, st, sink); });
   for (uint32_t first = 0; first < n_frames;) {
     const uint32_t cnt = std::min(B, n_frames - first);
     const uint32_t slot = m.pipe->Acquire();
     Slot& s = *m.slots[slot];
-    // the batch's bytes: from its lowest offset (rounded down to 16: frames stay aligned) to its highest, inside the stream; an
-    // offset outside it becomes one the kernels refuse (status 1), so a malformed frame is reported, never read past the copy
-    uint64_t lo = total, hi = 0;
-    for (uint32_t i = first; i <= first + cnt; ++i) {
-      const uint64_t o = std::min(offsets[i], total);
-      lo = std::min(lo, o); hi = std::max(hi, o);
-    }
-    lo &= ~(uint64_t)15;
-    const uint64_t bytes = hi - lo;
-    if (s.pin_in.n < std::max<uint64_t>(bytes, 16)) {  // grown on demand: a batch of 1080p frames is about 17 MB
-      const size_t cap = (size_t)(bytes + bytes / 4 + 4095) & ~(size_t)4095;
-      s.pin_in.Alloc(kWho, cap); s.in.Alloc(kWho, cap);
-    }
-    m.crew.Copy(s.pin_in.p, stream + lo, bytes);
-    for (uint32_t i = 0; i <= cnt; ++i) {
-      const uint64_t o = offsets[first + i];
-      s.pin_off.p[i] = o <= total ? o - lo : ~(uint64_t)15;
-    }
+    const uint64_t bytes = StageFrames(m.crew, stream, offsets, total, first, cnt, s.pin_in, s.in, s.pin_off.p);
     m.StageGaze(s, gaze, first, cnt);
     s.first = first; s.count = cnt;
     m.pipe->Submit(
@@ -227,6 +261,78 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
   m.Finish(st);
 }
 
+void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offsets, const uint8_t* enh, const uint64_t* enh_offsets,
+                                 uint32_t n_frames, const Gaze& gaze, const Sink& sink) {
+  if (!gaze) return Decode(base, base_offsets, n_frames, gaze, sink);  // no tile takes the enhancement: it is not read
+  Impl& m = *p_;
+  const StreamDecoderConfig& c = m.c;
+  if (n_frames == 0) { m.stats = DecodeStats{}; return; }
+  if (!base || !base_offsets || !enh || !enh_offsets) throw std::runtime_error("svc::StreamDecoder: null stream");
+  const uint64_t total = base_offsets[n_frames], enh_total = enh_offsets[n_frames];
+  uint32_t hdr[kHeaderWords], ehdr[kHeaderWords];
+  FirstHeader(base, base_offsets, n_frames, "base's ", hdr);
+  FirstHeader(enh, enh_offsets, n_frames, "enhancement's ", ehdr);
+  for (uint32_t k = kHWidth; k <= kHMvH; ++k)
+    if (hdr[k] != ehdr[k]) throw std::runtime_error("svc::StreamDecoder: the enhancement stream's geometry is not the base stream's");
+  m.Size(hdr, hdr[kHMagic] == kMagicE, true, ehdr[kHMagic] == kMagicE);
+  const uint32_t B = c.batch;
+
+  DecodeStats st;
+  m.pipe->Begin([&](uint32_t slot) { Deliver(*m.slots[slot], m.dw, m.dh, m.svce, m.enh_svce, st, sink); });
+  for (uint32_t first = 0; first < n_frames;) {
+    const uint32_t cnt = std::min(B, n_frames - first);
+    const uint32_t slot = m.pipe->Acquire();
+    Slot& s = *m.slots[slot];
+    const uint64_t bytes = StageFrames(m.crew, base, base_offsets, total, first, cnt, s.pin_in, s.in, s.pin_off.p);
+    const uint64_t ebytes = StageFrames(m.crew, enh, enh_offsets, enh_total, first, cnt, s.pin_enh, s.enh, s.pin_enh_off.p);
+    m.StageGaze(s, gaze, first, cnt);
+    s.first = first; s.count = cnt;
+    m.pipe->Submit(
+        slot,
+        [&](hipStream_t si) -> uint64_t {
+          Hip(hipMemcpyAsync(s.in.p, s.pin_in.p, bytes, hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D");
+          Hip(hipMemcpyAsync(s.enh.p, s.pin_enh.p, ebytes, hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D enhancement");
+          Hip(hipMemcpyAsync(s.off.p, s.pin_off.p, (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D offsets");
+          Hip(hipMemcpyAsync(s.enh_off.p, s.pin_enh_off.p, (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, si),
+              "hipMemcpyAsync H2D enhancement offsets");
+          Hip(hipMemcpyAsync(s.gaze.p, s.pin_gaze.p, 4 * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D gaze");
+          return bytes + ebytes + 2 * (cnt + 1) * sizeof(uint64_t) + 4 * cnt * sizeof(uint32_t);
+        },
+        [&](hipStream_t sk) {
+          const uint8_t *qb = s.in.p, *qe = s.enh.p;
+          const uint64_t *qboff = s.off.p, *qeoff = s.enh_off.p;
+          uint64_t qbbytes = bytes, qebytes = ebytes;
+          if (m.svce) {  // SVCE -> SVCQ in device scratch, each stream by its own kind
+            Abi(svc_hip_entropy_decode_frames(s.in.p, bytes, s.off.p, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, m.ews.p, m.ews_bytes, m.q.p,
+                                              m.q_bytes, m.qoff.p, s.estatus.p, sk),
+                "svc_hip_entropy_decode_frames");
+            qb = m.q.p; qboff = m.qoff.p; qbbytes = m.q_bytes;
+          }
+          if (m.enh_svce) {
+            Abi(svc_hip_entropy_decode_frames(s.enh.p, ebytes, s.enh_off.p, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, m.ews.p, m.ews_bytes,
+                                              m.eq.p, m.q_bytes, m.eqoff.p, s.enh_estatus.p, sk),
+                "svc_hip_entropy_decode_frames (enhancement)");
+            qe = m.eq.p; qeoff = m.eqoff.p; qebytes = m.q_bytes;
+          }
+          Abi(svc_hip_decode_layers_frames(qb, qbbytes, qboff, qe, qebytes, qeoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step,
+                                           c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh, s.status.p, sk),
+              "svc_hip_decode_layers_frames");
+        },
+        [&](hipStream_t so) -> uint64_t {
+          Hip(hipMemcpyAsync(s.pin_disp.p, s.disp.p, cnt * m.disp_bytes, hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H display");
+          Hip(hipMemcpyAsync(s.pin_status.p, s.status.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H status");
+          if (m.svce)
+            Hip(hipMemcpyAsync(s.pin_estatus.p, s.estatus.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H status");
+          if (m.enh_svce)
+            Hip(hipMemcpyAsync(s.pin_enh_estatus.p, s.enh_estatus.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, so),
+                "hipMemcpyAsync D2H enhancement status");
+          return cnt * (m.disp_bytes + (1 + m.svce + m.enh_svce) * sizeof(uint32_t));
+        });
+    first += cnt;
+  }
+  m.Finish(st);
+}
+
 void StreamDecoder::DecodeWire(const uint8_t* stream, uint64_t bytes, const Gaze& gaze, const Sink& sink) {
   Impl& m = *p_;
   const StreamDecoderConfig& c = m.c;
@@ -244,7 +350,7 @@ void StreamDecoder::DecodeWire(const uint8_t* stream, uint64_t bytes, const Gaze
   const uint32_t B = c.wire_batch;
 
   DecodeStats st;
-  m.pipe->Begin([&](uint32_t slot) { Deliver(*m.slots[slot], m.dw, m.dh, false, st, sink); });
+  m.pipe->Begin([&](uint32_t slot) { Deliver(*m.slots[slot], m.dw, m.dh, false, false, st, sink); });
   for (uint32_t first = 0; first < n_frames;) {
     const uint32_t cnt = std::min(B, n_frames - first);
     const uint32_t slot = m.pipe->Acquire();

@@ -39,6 +39,13 @@ struct Slot {
   PinBuf<uint8_t> pin_in, pin_records;
   PinBuf<float> pin_mv, pin_gm, pin_coeffs;
   PinBuf<uint32_t> pin_types;
+  // two layers: the enhancement stream's buffers beside the base's (packed, offsets, coded ...), and the frames' windows
+  DevBuf<uint8_t> enh_packed, enh_coded;
+  DevBuf<uint64_t> enh_offsets, enh_coded_offsets;
+  DevBuf<uint32_t> enh_status, window;
+  PinBuf<uint8_t> pin_enh;
+  PinBuf<uint64_t> pin_enh_offsets;
+  PinBuf<uint32_t> pin_enh_status, pin_window;
   uint32_t frames = 0;  // source frames resident in bgr (the last one carries into the next batch)
   uint32_t encoded = 0, first = 0;
 };
@@ -53,6 +60,7 @@ struct StreamEncoder::Impl : EncodeGeometry {
   uint64_t packed_bytes = 0, pack_ws_bytes = 0;  // compact: worst case of a batch, pack workspace
   uint64_t coded_bytes = 0, entropy_ws_bytes = 0; // entropy: worst case of a coded batch, coder workspace
   bool budgeted = false;                          // compact_budget != 0: rate control
+  bool layered = false;                           // enh_step != 0: a base and an enhancement stream
   std::atomic<uint32_t> budget{0};                // bytes per frame of the next batch staged (SetCompactBudget)
   std::vector<std::unique_ptr<Slot>> slots;       // the buffers of the pipe's slots
   bool fused_records = false;  // wire: the transform kernel emits the records itself
@@ -90,6 +98,13 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (c.entropy && !c.compact) throw std::runtime_error("svc::StreamEncoder: entropy coding is a form of the compact stream");
   if (c.entropy && c.compact_budget)
     throw std::runtime_error("svc::StreamEncoder: a byte budget counts uncoded compact bytes: not with entropy");
+  m.layered = c.enh_step != 0;
+  if (m.layered && c.wire) throw std::runtime_error("svc::StreamEncoder: an enhancement layer is a form of the compact stream, not of the wire records");
+  if (m.layered && !c.compact) throw std::runtime_error("svc::StreamEncoder: an enhancement layer is a form of the compact stream");
+  if (m.layered && c.compact_budget) throw std::runtime_error("svc::StreamEncoder: a byte budget counts one stream: not with enh_step");
+  if (m.layered)  // the layered pack's checks that need neither a device pointer nor a size: geometry, the steps, the int16 bounds
+    Abi(svc_hip_pack_layers_frames(nullptr, nullptr, 0, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step, c.enh_step, nullptr, nullptr,
+                                   ~0ull, nullptr, ~0ull, nullptr, nullptr, ~0ull, nullptr, nullptr), "enh_step");
   if (c.entropy) {
     m.coded_bytes = svc_hip_entropy_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
     m.entropy_ws_bytes = svc_hip_entropy_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
@@ -98,7 +113,8 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (c.compact) {
     m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
     m.pack_ws_bytes = m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
-                                 : svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
+                      : m.layered ? svc_hip_pack_layers_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th)
+                                  : svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
     if (!m.packed_bytes || !m.pack_ws_bytes) throw std::runtime_error("svc::StreamEncoder: no compact stream for this geometry");
   }
   m.crew.reset(new CopyCrew(std::min<uint32_t>(c.copy_threads ? c.copy_threads - 1 : 0, 15)));
@@ -128,6 +144,15 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
         s->coded.Alloc(kWho, m.coded_bytes); s->entropy_ws.Alloc(kWho, m.entropy_ws_bytes); s->coded_offsets.Alloc(kWho, B + 1);
         s->entropy_status.Alloc(kWho, B); s->pin_entropy_status.Alloc(kWho, B);
       }
+    }
+    if (m.layered) {
+      s->enh_packed.Alloc(kWho, m.packed_bytes); s->enh_offsets.Alloc(kWho, B + 1);
+      s->pin_enh.Alloc(kWho, c.entropy ? m.coded_bytes : m.packed_bytes); s->pin_enh_offsets.Alloc(kWho, B + 1);
+      if (c.entropy) {
+        s->enh_coded.Alloc(kWho, m.coded_bytes); s->enh_coded_offsets.Alloc(kWho, B + 1);
+        s->enh_status.Alloc(kWho, B); s->pin_enh_status.Alloc(kWho, B);
+      }
+      if (c.enh_window) { s->window.Alloc(kWho, B * 4); s->pin_window.Alloc(kWho, B * 4); }
     }
     if (m.budgeted) { s->budget.Alloc(kWho, B); s->choice.Alloc(kWho, B); s->pin_budget.Alloc(kWho, B); s->pin_choice.Alloc(kWho, B); }
     m.slots.push_back(std::move(s));
@@ -175,11 +200,14 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
   m.pipe->Begin([&](uint32_t slot) {
     Slot& s = *m.slots[slot];
     if (c.compact) st.d2h_bytes += s.pin_offsets.p[s.encoded];  // the drain moved exactly the used bytes
+    if (m.layered) st.d2h_bytes += s.pin_enh_offsets.p[s.encoded];
     if (c.entropy)  // the input is the pack's own output: a flagged frame is a bug, not a stream to pass on
-      for (uint32_t i = 0; i < s.encoded; ++i)
-        if (s.pin_entropy_status.p[i])
+      for (uint32_t i = 0; i < s.encoded; ++i) {
+        const uint32_t code = s.pin_entropy_status.p[i] ? s.pin_entropy_status.p[i] : m.layered ? s.pin_enh_status.p[i] : 0u;
+        if (code)
           throw std::runtime_error("svc::StreamEncoder: svc_hip_entropy_encode_frames flagged frame " + std::to_string(s.first + i) +
-                                   " with status " + std::to_string(s.pin_entropy_status.p[i]));
+                                   " with status " + std::to_string(code));
+      }
     if (m.budgeted)
       for (uint32_t i = 0; i < s.encoded; ++i) st.over_budget_frames += s.pin_choice.p[i] >> 31;
     st.encoded_frames += s.encoded;
@@ -193,6 +221,9 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     if (c.compact) {
       b.compact = s.pin_packed.p; b.compact_offsets = s.pin_offsets.p; b.compact_bytes = s.pin_offsets.p[s.encoded];
       b.compact_choice = m.budgeted ? s.pin_choice.p : nullptr;
+    }
+    if (m.layered) {
+      b.enhancement = s.pin_enh.p; b.enhancement_offsets = s.pin_enh_offsets.p; b.enhancement_bytes = s.pin_enh_offsets.p[s.encoded];
     }
     b.records = c.wire ? s.pin_records.p : nullptr;
     b.record_bytes = m.record_bytes;
@@ -220,6 +251,11 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     const uint32_t encoded = carry ? n_new : (n_new ? n_new - 1 : 0);
     if (encoded == 0) break;  // the clip ended on a batch boundary (or had a single frame): nothing left to encode
     const uint32_t g0 = first - 1;  // clip-wide index of the batch's first pair
+    if (m.layered && c.enh_window)  // the frames' windows, asked for here: on the caller's thread, in clip order
+      for (uint32_t i = 0; i < encoded; ++i) {
+        uint32_t* r = s.pin_window.p + 4 * (size_t)i;
+        if (!c.enh_window(first + i, r)) r[0] = r[1] = r[2] = r[3] = 0;  // false: an empty window
+      }
 
     auto h2d = [&](hipStream_t si) -> uint64_t {
       Hip(hipMemcpyAsync(s.bgr.p + (size_t)off * m.frame_bytes, s.pin_in.p + (size_t)off * m.frame_bytes,
@@ -230,6 +266,9 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       FillRansacDraws(s.pin_samples.p, g0, encoded, m.iters, c.ransac.subset_sz, m.blocks, c.seed);
       Hip(hipMemcpyAsync(s.samples.p, s.pin_samples.p, (size_t)encoded * m.iters * c.ransac.subset_sz * sizeof(uint32_t),
                          hipMemcpyHostToDevice, si), "hipMemcpyAsync samples");
+      if (m.layered && c.enh_window)
+        Hip(hipMemcpyAsync(s.window.p, s.pin_window.p, (size_t)encoded * 4 * sizeof(uint32_t), hipMemcpyHostToDevice, si),
+            "hipMemcpyAsync windows");
       if (m.budgeted) {  // the budget as it stands now, for every frame of this batch (SetCompactBudget's rule)
         const uint32_t bytes = m.budget.load();
         std::fill(s.pin_budget.p, s.pin_budget.p + encoded, bytes);
@@ -267,6 +306,22 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
                                               (uint32_t)c.compact_ladder.size(), s.budget.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
                                               m.packed_bytes, s.offsets.p, s.choice.p, sk),
             "svc_hip_pack_levels_budget_frames");
+      } else if (m.layered) {  // raw planes; both layers quantise them themselves, whatever the geometry
+        Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, sk), "svc_hip_dct_frames");
+        Abi(svc_hip_pack_layers_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step, c.enh_step,
+                                       c.enh_window ? s.window.p : nullptr, s.pack_ws.p, m.pack_ws_bytes, s.packed.p, m.packed_bytes,
+                                       s.offsets.p, s.enh_packed.p, m.packed_bytes, s.enh_offsets.p, sk),
+            "svc_hip_pack_layers_frames");
+        if (c.entropy) {  // one workspace: the two calls follow each other on this stream
+          Abi(svc_hip_entropy_encode_frames(s.packed.p, m.packed_bytes, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
+                                            s.entropy_ws.p, m.entropy_ws_bytes, s.coded.p, m.coded_bytes, s.coded_offsets.p,
+                                            s.entropy_status.p, sk),
+              "svc_hip_entropy_encode_frames");
+          Abi(svc_hip_entropy_encode_frames(s.enh_packed.p, m.packed_bytes, s.enh_offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
+                                            s.entropy_ws.p, m.entropy_ws_bytes, s.enh_coded.p, m.coded_bytes, s.enh_coded_offsets.p,
+                                            s.enh_status.p, sk),
+              "svc_hip_entropy_encode_frames (enhancement)");
+        }
       } else {
         Abi(svc_hip_dct_quant_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.types.p, m.bw,
                                      m.bh, c.fg_step, c.bg_step, s.coeffs.p, sk), "svc_hip_dct_quant_frames");
@@ -285,6 +340,20 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       uint64_t bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : c.compact ? 0 : 3 * m.plane_elems * sizeof(float)));
       if (c.compact) bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t);  // + the stream's used bytes, known at delivery
       if (m.budgeted || c.entropy) bytes += (uint64_t)encoded * sizeof(uint32_t);  // the choices, or the coder's statuses
+      if (m.layered) {  // the enhancement stream, moved as the base is (its used bytes are added at delivery)
+        bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t) + (c.entropy ? (uint64_t)encoded * sizeof(uint32_t) : 0);
+        if (c.entropy) {
+          Abi(svc_hip_entropy_drain(s.enh_coded.p, s.enh_coded_offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_enh.p,
+                                    m.coded_bytes, so), "svc_hip_entropy_drain (enhancement)");
+          Hip(hipMemcpyAsync(s.pin_enh_status.p, s.enh_status.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, so),
+              "D2H enhancement entropy status");
+        } else {
+          Abi(svc_hip_levels_drain(s.enh_packed.p, s.enh_offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, s.pin_enh.p, m.packed_bytes,
+                                   so), "svc_hip_levels_drain (enhancement)");
+        }
+        Hip(hipMemcpyAsync(s.pin_enh_offsets.p, c.entropy ? s.enh_coded_offsets.p : s.enh_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, so), "D2H enhancement offsets");
+      }
       Hip(hipMemcpyAsync(s.pin_mv.p, s.mv.p, (size_t)encoded * m.blocks * 2 * sizeof(float), hipMemcpyDeviceToHost, so), "D2H mv");
       Hip(hipMemcpyAsync(s.pin_types.p, s.types.p, (size_t)encoded * m.blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "D2H types");
       Hip(hipMemcpyAsync(s.pin_gm.p, s.gm.p, (size_t)encoded * 2 * sizeof(float), hipMemcpyDeviceToHost, so), "D2H gm");

@@ -32,6 +32,9 @@
 // split (svc_hip_split_levels_frames, svc_hip_split_levels_budget_frames): a stored fine stream -> a base stream at any steps plus its
 // enhancement, in integers on the levels -- the window call's count and scan for the input, then count, scan, frame offsets and one
 // write pass, each serving both layers (stated at its kernels).
+//
+// pack of two layers (svc_hip_pack_layers_frames): the pack's count, scan and scatter on raw planes with two quantisations per coefficient,
+// the frame offsets from frame_offsets_kernel with a job per layer (stated at its kernels).
 #include "budget_core.hpp"
 #include "display_core.hpp"
 #include "idct_core.hpp"
@@ -1180,6 +1183,154 @@ __global__ __launch_bounds__(256) void split_select_kernel(SplitArgs a, Ladder l
   a.ws.steps[2 * i + 1] = lad.step[0][pick];
 }
 
+// ---- pack of two layers from raw planes (svc_hip_pack_layers_frames) ----------------------------------------------------------------
+//
+// The pack's work split and passes with two quantisations per coefficient: Lb = level_of(c, the tile's base step), Lf = level_of(c, e)
+// and d = Lf - Lb * ratio inside the frame's window, 0 outside it -- both from the f32 coefficient the group staged in LDS, so the base
+// is the direct quantisation at (fg, bg) for any ratio (the split of a stored fine stream is not, at the ties of an even ratio).
+//   count    pack_layers_kernel<false>: per group the non-zero levels of both layers and the base's inexact coefficients
+//   scan     one workgroup per frame: both layers' prefixes, level counts and sizes, the base's inexact count
+//   offsets  frame_offsets_kernel, a workgroup per layer
+//   scatter  pack_layers_kernel<true>: both layers' masks and levels at their final place; group 0 writes both headers, types and
+//            paddings.  Every output byte is stored once: two calls write the same bytes.
+
+struct LayersWs {
+  uint32_t *nzb, *nze, *inexact;  // [n][groups]; nzb / nze become exclusive prefixes
+  uint32_t *frame_bytes;          // [2][n] base, enhancement
+  uint32_t *frame_levels;         // [2][n]
+  uint32_t *frame_inexact;        // [n] of the base
+};
+LayersWs layers_ws(Carver& c, uint32_t n, uint32_t groups) {
+  LayersWs s;
+  s.nzb = c.take<uint32_t>((uint64_t)n * groups);
+  s.nze = c.take<uint32_t>((uint64_t)n * groups);
+  s.inexact = c.take<uint32_t>((uint64_t)n * groups);
+  s.frame_bytes = c.take<uint32_t>(2ull * n);
+  s.frame_levels = c.take<uint32_t>(2ull * n);
+  s.frame_inexact = c.take<uint32_t>(n);
+  return s;
+}
+
+struct PackLayersArgs {
+  Geom g;
+  const float* planes;     // [n][3][h][w]
+  const uint32_t* types;   // [n][mvb]
+  const uint32_t* window;  // [n][4] or null: every tile is enhanced
+  uint8_t *base, *enh;
+  uint64_t *base_offsets, *enh_offsets;  // [n + 1], the offsets kernel's
+  LayersWs ws;
+  uint32_t n, fg, bg, e;
+};
+
+// SCATTER = false: the group's counts.  SCATTER = true: both layers' masks and levels and, from group 0 of each frame, their headers,
+// types and zero pads.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void pack_layers_kernel(PackLayersArgs a) {
+  extern __shared__ float lds[];
+  __shared__ uint64_t mask_b[kMaxJobs], mask_e[kMaxJobs];
+  __shared__ uint32_t at_b[kMaxJobs], at_e[kMaxJobs];
+  __shared__ uint32_t red[kThreads / 64];
+  const Geom& g = a.g;
+  const uint32_t gi = blockIdx.x, f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const Group gr = group_of(g, gi);
+  const uint32_t* types = a.types + (size_t)f * g.mvb;
+  const float e = (float)a.e;
+  stage_rows(g, gr, a.planes + ((size_t)f * 3 + gr.plane) * g.h * g.w, lds);
+  __syncthreads();
+
+  const uint32_t area = g.bw * g.bh, jobs = gr.nt * g.words;
+  // lane's two levels of word j: the base's Lb and the enhancement's d (0 outside the window and past the tile area)
+  auto levels_of = [&](uint32_t j, int32_t* lb, int32_t* d, bool* inexact) {
+    const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
+    const uint32_t sb = tile_type(g, types, gr, t) == 0 ? a.bg : a.fg;
+    *lb = 0; *d = 0; *inexact = false;
+    if (k >= area) return;
+    const float c = lds[lds_index(g, gr, t, k)];
+    *lb = level_of(c, (float)sb);
+    *inexact = c != (float)*lb * (float)sb;
+    if (in_window(a.window, f, gr.x0 + t * g.bw, gr.y0)) *d = level_of(c, e) - *lb * (int32_t)(sb / a.e);
+  };
+  uint32_t nzb = 0, nze = 0, inexact = 0;
+  for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
+    int32_t lb, d;
+    bool ix;
+    levels_of(j, &lb, &d, &ix);
+    const uint64_t mb = __ballot(lb != 0), me = __ballot(d != 0);
+    if (!SCATTER) {
+      nzb += (uint32_t)__popcll(mb);
+      nze += (uint32_t)__popcll(me);
+      inexact += ix;
+    } else if (lane == 0) {
+      mask_b[j] = mb;
+      mask_e[j] = me;
+    }
+  }
+  if (!SCATTER) {
+    // (nzb and nze are the same in every lane of a wave: lane 0's value stands for the wave)
+    uint32_t total;
+    (void)block_exclusive_scan(lane == 0 ? nzb : 0u, red, &total);
+    if (threadIdx.x == 0) a.ws.nzb[(size_t)f * g.groups + gi] = total;
+    (void)block_exclusive_scan(lane == 0 ? nze : 0u, red, &total);
+    if (threadIdx.x == 0) a.ws.nze[(size_t)f * g.groups + gi] = total;
+    (void)block_exclusive_scan(inexact, red, &total);
+    if (threadIdx.x == 0) a.ws.inexact[(size_t)f * g.groups + gi] = total;
+    return;
+  }
+
+  // scatter: exclusive scans of the words' popcounts, in word order
+  __syncthreads();
+  uint32_t total;
+  const uint32_t ex_b = block_exclusive_scan(threadIdx.x < jobs ? (uint32_t)__popcll(mask_b[threadIdx.x]) : 0u, red, &total);
+  const uint32_t ex_e = block_exclusive_scan(threadIdx.x < jobs ? (uint32_t)__popcll(mask_e[threadIdx.x]) : 0u, red, &total);
+  if (threadIdx.x < jobs) { at_b[threadIdx.x] = ex_b; at_e[threadIdx.x] = ex_e; }
+  __syncthreads();
+  uint8_t* base = a.base + a.base_offsets[f];
+  uint8_t* enh = a.enh + a.enh_offsets[f];
+  int16_t* lv_b = reinterpret_cast<int16_t*>(base + g.levels_off) + a.ws.nzb[(size_t)f * g.groups + gi];
+  int16_t* lv_e = reinterpret_cast<int16_t*>(enh + g.levels_off) + a.ws.nze[(size_t)f * g.groups + gi];
+  uint32_t* masks_b = group_masks(g, base, gr.plane, gr);
+  uint32_t* masks_e = group_masks(g, enh, gr.plane, gr);
+  for (uint32_t j = threadIdx.x; j < jobs; j += kThreads) {  // (kMaxJobs == kThreads: one trip)
+    store_mask(masks_b + 2 * j, mask_b[j]);
+    store_mask(masks_e + 2 * j, mask_e[j]);
+  }
+  for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
+    const uint64_t mb = mask_b[j], me = mask_e[j];
+    if (!(((mb | me) >> lane) & 1u)) continue;
+    int32_t lb, d;
+    bool ix;
+    levels_of(j, &lb, &d, &ix);
+    if ((mb >> lane) & 1u) lv_b[at_b[j] + lane_rank(mb)] = (int16_t)lb;
+    if ((me >> lane) & 1u) lv_e[at_e[j] + lane_rank(me)] = (int16_t)d;
+  }
+  if (gi != 0) return;
+  write_frame_edges(base, head_of(g, a.fg, a.bg, a.ws.frame_levels[f], a.ws.frame_inexact[f], a.ws.frame_bytes[f]), types, g.mvb,
+                    g.levels_off, kThreads, nullptr, 0, 0);
+  write_frame_edges(enh, head_of(g, a.e, a.e, a.ws.frame_levels[a.n + f], 0, a.ws.frame_bytes[a.n + f]), types, g.mvb, g.levels_off,
+                    kThreads, nullptr, 0, 0);
+}
+
+// one workgroup per frame: both layers' group counts -> exclusive prefixes (in place), their level counts and sizes, the base's inexact
+// count
+__global__ __launch_bounds__(256) void pack_layers_scan_kernel(Geom g, LayersWs ws, uint32_t n) {
+  __shared__ uint32_t red[kThreads / 64];
+  const uint32_t f = blockIdx.x;
+  uint32_t* nzb = ws.nzb + (size_t)f * g.groups;
+  uint32_t* nze = ws.nze + (size_t)f * g.groups;
+  uint32_t inexact = 0, t;  // summed on the first scan's way
+  const uint32_t carry_b = scan_counts(g.groups, 0, red, [&](uint32_t i) { inexact += ws.inexact[(size_t)f * g.groups + i]; return nzb[i]; },
+                                       [&](uint32_t i, uint32_t v) { nzb[i] = v; });
+  const uint32_t carry_e = scan_counts(nze, nze, g.groups, 0, red);
+  (void)block_exclusive_scan(inexact, red, &t);
+  if (threadIdx.x == 0) {
+    ws.frame_levels[f] = carry_b;
+    ws.frame_levels[n + f] = carry_e;
+    ws.frame_inexact[f] = t;
+    ws.frame_bytes[f] = (uint32_t)up16(g.levels_off + 2ull * carry_b);
+    ws.frame_bytes[n + f] = (uint32_t)up16(g.levels_off + 2ull * carry_e);
+  }
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -1668,6 +1819,59 @@ int svc_hip_split_levels_budget_frames(const uint8_t* d_frames, uint64_t stream_
                                  mv_block_w, mv_block_h, fine_step, d_window, d_base_out, d_base_offsets, d_enh_out, d_enh_offsets, d_status);
   return split_levels("split_levels_budget", a, ladder, ladder_len, d_budget, d_choice, d_workspace, workspace_bytes, base_capacity,
                       enh_capacity, stream);
+}
+
+uint64_t svc_hip_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h) {
+  // the MV block does not enter the group split: the whole frame stands in for it
+  if (validate_geom("pack_layers_workspace_bytes", frame_w, frame_h, block_w, block_h, frame_w, frame_h) ||
+      validate_limits("pack_layers_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, frame_w, frame_h))
+    return 0;
+  return layout_bytes(layers_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, frame_w, frame_h).groups);
+}
+
+// Checked in the order of svc_hip_dct_pack_layers_frames: geometry, steps, the int16 bounds, limits, workspace, both capacities;
+// n_frames == 0 then returns SVC_OK; then pointers.
+int svc_hip_pack_layers_frames(const float* d_planes, const uint32_t* d_block_types, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                               uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                               uint32_t bg_step, uint32_t enh_step, const uint32_t* d_window, uint8_t* d_workspace,
+                               uint64_t workspace_bytes, uint8_t* d_base_out, uint64_t base_capacity, uint64_t* d_base_offsets,
+                               uint8_t* d_enh_out, uint64_t enh_capacity, uint64_t* d_enh_offsets, void* stream) {
+  int rc = validate_geom("pack_layers", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0 && enh_step > 0, "pack_layers: quant steps must be positive");
+  // (a step that divides is not above: this also refuses enh_step > min(fg_step, bg_step))
+  SVC_REQUIRE(fg_step % enh_step == 0 && bg_step % enh_step == 0, "pack_layers: fg_step %u and bg_step %u must each be a multiple of enh_step %u",
+              fg_step, bg_step, enh_step);
+  // the pack's int16 bound (Parseval) on the fine levels; the residuals are within ratio / 2 + 1 of zero
+  if (255.0 * std::sqrt((double)block_w * block_h) / enh_step > 32767.0)
+    return fail(SVC_ERR_UNSUPPORTED, "pack_layers: levels of a %ux%u tile at step %u could exceed int16", block_w, block_h, enh_step);
+  if (std::max(fg_step, bg_step) / enh_step > 32766)
+    return fail(SVC_ERR_UNSUPPORTED, "pack_layers: a base step of %u is more than 32766 times enh_step %u: a residual could exceed int16",
+                std::max(fg_step, bg_step), enh_step);
+  if ((rc = validate_limits("pack_layers", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if ((rc = require_workspace("pack_layers", workspace_bytes, layout_bytes(layers_ws, n_frames, g.groups)))) return rc;
+  const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
+  if ((rc = require_capacity("pack_layers", "base output", base_capacity, need))) return rc;
+  if ((rc = require_capacity("pack_layers", "enhancement output", enh_capacity, need))) return rc;
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_planes && d_block_types && d_workspace && d_base_out && d_base_offsets && d_enh_out && d_enh_offsets, "pack_layers: null pointer");
+  SVC_REQUIRE(aligned(d_planes, 16) && aligned(d_base_out, 16) && aligned(d_enh_out, 16) && aligned(d_workspace, 16) &&
+                  aligned(d_base_offsets, 8) && aligned(d_enh_offsets, 8) && aligned(d_block_types, 4) && aligned(d_window, 4),
+              "pack_layers: planes, outputs and workspace must be 16-byte aligned, offsets 8-byte, types and window 4-byte");
+  const PackLayersArgs a{g, d_planes, d_block_types, d_window, d_base_out, d_enh_out, d_base_offsets, d_enh_offsets,
+                         carve(d_workspace, layers_ws, n_frames, g.groups), n_frames, fg_step, bg_step, enh_step};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(g.groups, n_frames);
+  hipLaunchKernelGGL(pack_layers_kernel<false>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  if ((rc = check_launch("pack_layers", "count"))) return rc;
+  hipLaunchKernelGGL(pack_layers_scan_kernel, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws, n_frames);
+  if ((rc = check_launch("pack_layers", "scan"))) return rc;
+  if ((rc = enqueue_frame_offsets("pack_layers", 2, OffsetsJob{a.ws.frame_bytes, d_base_offsets, nullptr},
+                                  OffsetsJob{a.ws.frame_bytes + n_frames, d_enh_offsets, nullptr}, n_frames, stream)))
+    return rc;
+  hipLaunchKernelGGL(pack_layers_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
+  return check_launch("pack_layers", "scatter");
 }
 
 int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w, uint32_t frame_h, uint32_t padded_w,

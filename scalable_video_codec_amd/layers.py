@@ -18,7 +18,10 @@ integers on the levels' values:
     d  = Lf - Lb * r                            inside the window, 0 outside it
 Lb * r + d == Lf for any r.  For odd r (both classes) Lb is the level a direct quantisation at sb gives, so the two frames are the
 encoder's own; for even r a level that is an odd multiple of r / 2 is a tie the coefficient would have resolved either way, and the base
-differs from a direct encode there."""
+differs from a direct encode there.
+
+pack_layers_frames states svc_hip_pack_layers_frames: both layers from raw coefficient planes, each level quantised from the coefficient
+itself, so the base is the direct encode for any ratio."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple
@@ -314,3 +317,39 @@ def split_budget_frames(stream, offsets, fine_step: int, ladder, budgets, window
         base.append(b)
         enh.append(e)
     return _join(base) + _join(enh) + (choice,)
+
+
+# ---- both layers from raw coefficient planes (include/svc_hip.h: svc_hip_pack_layers_frames) ----------------------------------------
+
+def quantise(planes: np.ndarray, step) -> np.ndarray:
+    """The pack's quantiser on f32 coefficients -> i64 levels: the quotient c / step taken in f32, rounded half away from zero (exactly:
+    the f32 quotient plus or minus a half is exact in f64), then clamped to int16.  step: an integer, or an array that broadcasts."""
+    q = (np.asarray(planes, np.float32) / np.asarray(step).astype(np.float32)).astype(np.float64)
+    return np.clip(np.trunc(q + np.copysign(0.5, q)), -32768, 32767).astype(np.int64)
+
+
+def pack_layers_frames(planes, types, geometry: Dict[str, int], fg_step: int, bg_step: int, enh_step: int, windows=None
+                       ) -> Tuple[bytes, np.ndarray, bytes, np.ndarray, np.ndarray]:
+    """What svc_hip_pack_layers_frames writes -> (base bytes, base offsets (n + 1,) u64, enhancement bytes, its offsets, inexact (n,)
+    u32).  planes: raw coefficients (n, 3, H, W) f32; types: region ids (n, MV rows, MV columns) or (n, MV blocks); geometry: a dict
+    with the keys of GEOMETRY; windows: None (every tile is enhanced) or per frame x, y, w, h in padded coordinates (n, 4).  Per frame
+    Lb = quantise(c, the tile's base step), Lf = quantise(c, enh_step) and d = Lf - Lb * ratio inside the window, 0 outside it; the
+    base's header word 11 counts the coefficients with c != (f32)Lb * (f32)step."""
+    _check_split_steps(enh_step, fg_step, bg_step)
+    w, h = geometry["frame_w"], geometry["frame_h"]
+    planes = np.asarray(planes, np.float32).reshape(-1, 3, h, w)
+    n = planes.shape[0]
+    types = np.asarray(types).astype(np.uint32).reshape(n, h // geometry["mv_block_h"], w // geometry["mv_block_w"])
+    win = None if windows is None else np.asarray(windows).reshape(n, 4)
+    base, enh, inexact = [], [], np.zeros(n, np.uint32)
+    for f in range(n):
+        background, ox, oy = _tile_maps(geometry, types[f])
+        step = _per_pixel(geometry, np.where(background, bg_step, fg_step).astype(np.int64))[None]
+        lb = quantise(planes[f], step)
+        d = quantise(planes[f], enh_step) - lb * (step // enh_step)
+        if win is not None:
+            d = np.where(_per_pixel(geometry, _contains(win[f], ox, oy))[None], d, 0)
+        inexact[f] = int((planes[f] != lb.astype(np.float32) * step.astype(np.float32)).sum())
+        base.append(write_frame(geometry, types[f], lb, fg_step, bg_step, int(inexact[f])))
+        enh.append(write_frame(geometry, types[f], d, enh_step, enh_step))
+    return _join(base) + _join(enh) + (inexact,)

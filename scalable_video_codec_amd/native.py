@@ -149,6 +149,8 @@ SIGNATURES = {
     "svc_hip_dct_pack_layers_workspace_bytes": (_u64, [_u32] * 6),
     "svc_hip_dct_pack_layers_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 5 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp,
                                                 _vp]),
+    "svc_hip_pack_layers_workspace_bytes": (_u64, [_u32] * 5),
+    "svc_hip_pack_layers_frames": (C.c_int, [_vp, _vp] + [_u32] * 10 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "svc_hip_decode_layers_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_decode_layers_frames": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     # a stored SVCQ stream restricted to a window per output frame (csrc/levels.hip; host statement: layers.window_frames)
@@ -1068,6 +1070,44 @@ def dct_pack_layers_frames(bgr: torch.Tensor, block: int, block_types: torch.Ten
                                                  _dev(workspace, torch.uint8), workspace.numel(), _dev(base_out, torch.uint8),
                                                  base_out.numel(), _dev(base_offsets, torch.int64), _dev(enh_out, torch.uint8),
                                                  enh_out.numel(), _dev(enh_offsets, torch.int64), _stream()))
+    return base_out, base_offsets, enh_out, enh_offsets
+
+
+def pack_layers_workspace_bytes(n: int, w: int, h: int, block) -> int:
+    """Scratch of pack_layers_frames; 0 for a geometry it refuses."""
+    bw, bh = _bwbh(block)
+    return int(load().svc_hip_pack_layers_workspace_bytes(n, w, h, bw, bh))
+
+
+def pack_layers_frames(planes: torch.Tensor, block_types: torch.Tensor, block, mv_block, fg_step: int, bg_step: int, enh_step: int,
+                       window=None, base_out: Optional[torch.Tensor] = None, enh_out: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None, base_offsets: Optional[torch.Tensor] = None,
+                       enh_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Raw coefficient planes (frames, 3, H, W) f32 (dct_frames) + region ids -> the base stream pack_levels_frames writes for them at
+    (fg_step, bg_step) and the enhancement stream that lifts the tiles whose origin is inside the frame's window to enh_step
+    (include/svc_hip.h), for any geometry the pack takes.  window: None (every tile), or per frame x, y, w, h in padded coordinates.
+    -> (base u8, base offsets (frames + 1,) i64, enhancement u8, enhancement offsets), each stream of the worst-case size, on the
+    device."""
+    n, _, h, w = planes.shape
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = planes.device
+    cap = max(levels_max_bytes(n, w, h, block, mv_block), 16)
+    if base_out is None:
+        base_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if enh_out is None:
+        enh_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(pack_layers_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=dev)
+    if base_offsets is None:
+        base_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if enh_offsets is None:
+        enh_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    win = _rects(window, n, dev)
+    _check(load().svc_hip_pack_layers_frames(_dev(planes, torch.float32), _dev(block_types, torch.int32), n, w, h, bw, bh, mbw, mbh,
+                                             fg_step, bg_step, enh_step, None if win is None else _dev(win, torch.int32),
+                                             _dev(workspace, torch.uint8), workspace.numel(), _dev(base_out, torch.uint8),
+                                             base_out.numel(), _dev(base_offsets, torch.int64), _dev(enh_out, torch.uint8),
+                                             enh_out.numel(), _dev(enh_offsets, torch.int64), _stream()))
     return base_out, base_offsets, enh_out, enh_offsets
 
 

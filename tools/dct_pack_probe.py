@@ -44,6 +44,16 @@
                                                    through d_src; the three-call route decodes the 16 stored frames once); wall time per call
                                                    over 20 back-to-back calls, the two routes interleaved, bytes in and out and the share of
                                                    chunks in each class; the bytes are compared
+  python tools/dct_pack_probe.py pack-layers      both layers from raw planes, at C3 and at C5, a batch of 16 each at (fg, bg, e) =
+                                                   (1, 640, 1) with a 256 x 256 window per frame: svc_hip_pack_layers_frames on the planes
+                                                   svc_hip_dct_frames wrote, against two svc_hip_pack_levels_frames calls on the same planes
+                                                   (at (fg, bg), then at (e, e)) in the same process; wall time per call over 20 back-to-back
+                                                   calls, the two routes interleaved, and the bytes each moves; the base is compared
+  python tools/dct_pack_probe.py stream-layers    the two layers through the host drivers: a 65-frame C3 synthetic clip made on the CPU,
+                                                   batches of 16, (1, 640, 1), a 256 x 256 window and a gaze centre per frame;
+                                                   tests/dropin/stream_layers_main (plain, entropy-coded, and with every tile enhanced) beside
+                                                   stream_levels_main, stream_entropy_main and stream_decode_main on the same clip and gaze,
+                                                   the whole list twice in turn; PCIe-inclusive rates as the applications print them
 """
 import os
 import sys
@@ -524,6 +534,94 @@ def split(cfg) -> None:
           f"{int(woo[-1]) / n / 1e6:.3f} MB per frame", flush=True)
 
 
+def pack_layers(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    fg, bg, e = 1, 640, 1
+    bgr, types = _batch(cfg, n)
+    planes = native.dct_frames(bgr, block)
+    del bgr
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    base, fine, lbase, lenh = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(4))
+    offs_b, offs_f, lo_b, lo_e = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(4))
+    ws1 = torch.empty(native.pack_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    ws2 = torch.empty(native.pack_layers_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    win = torch.tensor([((pw - 256) // 2 // 16 * 16 + 32 * (f % 7 - 3), (ph - 256) // 2 // 16 * 16 + 16 * (f % 5 - 2), 256, 256) for f in range(n)],
+                       dtype=torch.int32, device=dev)
+    sync = torch.cuda.synchronize
+
+    def two_calls():
+        native.pack_levels_frames(planes, types, block, mv, fg, bg, out=base, offsets=offs_b, workspace=ws1)
+        native.pack_levels_frames(planes, types, block, mv, e, e, out=fine, offsets=offs_f, workspace=ws1)
+
+    def layered(window):
+        return lambda: native.pack_layers_frames(planes, types, block, mv, fg, bg, e, window=window, base_out=lbase, enh_out=lenh,
+                                                 workspace=ws2, base_offsets=lo_b, enh_offsets=lo_e)
+
+    def fmt(t):
+        return f"{t[0]:.3f} .. {t[1]:.3f}"
+
+    print(f"{cfg.name} batch of {n} at ({fg}, {bg}, {e}), raw planes {planes.numel() * 4 / n / 1e6:.2f} MB per frame, ms per call (best .. worst "
+          f"of 3 runs of 20 back-to-back calls; the routes interleaved: two calls, layers, two calls, layers)", flush=True)
+    for name, window in (("a 256 x 256 window per frame", win), ("no window: every tile", None)):
+        t2a = _per_step(two_calls, sync, steps=20)
+        t1a = _per_step(layered(window), sync, steps=20)
+        t2b = _per_step(two_calls, sync, steps=20)
+        t1b = _per_step(layered(window), sync, steps=20)
+        two_calls()
+        layered(window)()
+        sync()
+        ub, uf, lb, le = int(offs_b[-1]), int(offs_f[-1]), int(lo_b[-1]), int(lo_e[-1])
+        assert torch.equal(lo_b, offs_b) and torch.equal(lbase[:ub], base[:ub]), "the base layer differs from svc_hip_pack_levels_frames'"
+        t2, t1 = (min(t2a[0], t2b[0]), max(t2a[1], t2b[1])), (min(t1a[0], t1b[0]), max(t1a[1], t1b[1]))
+        read2, read1 = 2 * 2 * planes.numel() * 4, 2 * planes.numel() * 4  # every pack reads its planes twice: count, then scatter
+        print(f"{name}: pack_levels at ({fg}, {bg}) + at ({e}, {e}) {fmt(t2a)}, again {fmt(t2b)}; pack_layers {fmt(t1a)}, again {fmt(t1b)} "
+              f"({t1[0] / t2[0]:.2f} of the two calls by the best of each, {t1[1] / t2[1]:.2f} by the worst); same base bytes", flush=True)
+        print(f"    two calls: {(read2 + ub + uf) / 1e6:.1f} MB moved ({(read2 + ub + uf) / (t2[0] * 1e-3) / HBM_PEAK * 100:.1f} % of the HBM peak), "
+              f"base {ub / n / 1e6:.3f} + fine {uf / n / 1e6:.3f} MB per frame written; pack_layers: {(read1 + lb + le) / 1e6:.1f} MB moved "
+              f"({(read1 + lb + le) / (t1[0] * 1e-3) / HBM_PEAK * 100:.1f} %), base {lb / n / 1e6:.3f} + enhancement {le / n / 1e6:.3f} MB per frame; "
+              f"workspace {ws2.numel() / n / 1e6:.3f} MB per frame", flush=True)
+
+
+def stream_layers() -> None:
+    import subprocess
+    import tempfile
+    cfg = configs.C3
+    n = 65
+    clip = synth.SynthClip(cfg.width, cfg.height, n, cfg.seed, device="cpu")
+    pw, ph = cfg.padded
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    dropin = os.path.join(ROOT, "tests", "dropin")
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        raw, win, gaze, q = (os.path.join(d, f) for f in ("clip.raw", "windows.txt", "gaze.txt", "q"))
+        with open(raw, "wb") as f:
+            for t in range(n):
+                clip.frame_bgr(t).numpy().tofile(f)
+        # a 256 x 256 window on the MV grid that drifts with the frame, and the gaze centre in its middle
+        rects = [((pw - 256) // 2 // 16 * 16 + 32 * (i % 7 - 3), (ph - 256) // 2 // 16 * 16 + 16 * (i % 5 - 2), 256, 256) for i in range(n)]
+        with open(win, "w") as f:
+            f.write("".join("%d %d %d %d\n" % r for r in rects))
+        with open(gaze, "w") as f:  # one line per encoded frame: clip frame i + 1
+            f.write("".join("%d %d\n" % (min(r[0] + 128, cfg.width - 1), min(r[1] + 128, cfg.height - 1)) for r in rects[1:]))
+        common = [raw, str(cfg.width), str(cfg.height), str(n), str(cfg.levels), str(cfg.dct_block)]
+        layered = [*common, "16", "3", str(cfg.seed), "1", "640", "1"]
+        runs = [("stream_levels_main", [*common, "0", "16", str(cfg.seed), q], "writes the stream stream_decode_main reads"),
+                ("stream_levels_main", [*common, "0", "16", str(cfg.seed), "-"], "one layer at (1, 640)"),
+                ("stream_decode_main", [q, str(n - 1), "0", "0", gaze, "16", "-"], "one layer, a gaze per frame"),
+                ("stream_entropy_main", [*common, "16", str(cfg.seed), gaze, "-"], "one layer, entropy-coded, a gaze per frame"),
+                ("stream_layers_main", [*layered, "0", win, gaze, "-"], "two layers, a 256 x 256 window and a gaze per frame"),
+                ("stream_layers_main", [*layered, "1", win, gaze, "-"], "two layers, entropy-coded, the same window and gaze"),
+                ("stream_layers_main", [*layered, "0", "-", gaze, "-"], "two layers, every tile enhanced, the same gaze")]
+        for turn in range(2):
+            for name, args, what in runs[1 if turn else 0:]:
+                r = subprocess.run([os.path.join(dropin, name), *args], capture_output=True, text=True, timeout=300)
+                print(f"== turn {turn}: {name}: {what} (exit {r.returncode})\n{r.stdout.strip()}\n{r.stderr.strip()}", flush=True)
+                if r.returncode != 0:
+                    sys.exit(1)
+
+
 def step(cfg, frames_n) -> None:
     dev = torch.device("cuda")
     clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=dev)
@@ -577,5 +675,11 @@ if __name__ == "__main__":
         window_entropy(_cfg(sys.argv, 2))
     elif mode == "split":
         split(_cfg(sys.argv, 2))
+    elif mode == "stream-layers":
+        stream_layers()
+    elif mode == "pack-layers":
+        for config in (configs.C3, configs.C5):
+            pack_layers(config)
+            torch.cuda.empty_cache()
     else:
         kernels(_cfg(sys.argv, 2), fused_only=mode == "fused")
