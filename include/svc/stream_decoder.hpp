@@ -33,6 +33,11 @@ struct StreamDecoderConfig {
   // batches in flight without pinning a GB.
   uint32_t wire_batch = 8;
   uint32_t depth = 3;                     // batches in flight, >= 3 (H2D, kernels and D2H of three batches overlap)
+  // Decode at 1 / reduce of the size from each tile's low frequencies (svc_hip_decode_levels_reduced_frames): 1 = the full decoder, or
+  // 2, 4, 8.  Above 1 the picture is the padded size over reduce: a display of 0 x 0 means that size, a larger one throws
+  // std::runtime_error at the first Decode; gaze centres stay in display coordinates.  Serves Decode (SVCQ and SVCE) only:
+  // DecodeLayers and DecodeWire then throw std::runtime_error before any device work.
+  uint32_t reduce = 1;
 };
 
 // One finished batch; the pointers are pinned host memory owned by the decoder and stay valid until depth - 2 more batches have

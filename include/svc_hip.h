@@ -679,6 +679,37 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                                  uint32_t display_w, uint32_t display_h, uint32_t* d_status,
                                  void* stream);
 
+/* The same stream at reduced size, from its low frequencies: reduce r = 2, 4 or 8, N = the (square, 8
+ * or 16) transform block, K = N / r (4, 2, 1 for 8 x 8; 8, 4, 2 for 16 x 16).  The picture is
+ * (W / r) x (H / r) at the padded size; tile (tx, ty) is its K x K pixels at (tx K, ty K).  Per tile and
+ * plane, for the coefficients with row < K and column < K only: c = (float)level *
+ * (float)enc_step and q = requant(c, dec_step), with enc_step, dec_step and the gaze rule exactly
+ * those of svc_hip_decode_levels_frames (the tile origin is tested in padded FULL-SIZE coordinates;
+ * a gazed tile takes step 1); then the orthonormal K-point inverse DCT-II along rows and along
+ * columns in f64, scaled by K / N (a power of two: where it is applied cannot change a bit) and
+ * rounded once to f32.  That is the tile's own cosine series cut to its first K x K terms and
+ * sampled at the centres of K x K pixels (a_K(k) sqrt(K / N) = a_N(k)): a low-passed picture, not a
+ * point-sampled one.  K = 1 is the tile's mean, q00 / N exactly.  The coefficients outside K x K
+ * are never read; no f32 plane and no full-size picture is written.
+ * d_rec [n][H / r][W / r][3] f32 B,G,R is required; d_display [n][display_h][display_w][3] u8 is the
+ * display pass above applied to the reduced picture, 1 <= display_w <= W / r and 1 <= display_h <=
+ * H / r (a display of (W / r) x (H / r) is saturate_u8(rint(rec))).  Geometry, limits and alignment
+ * as svc_hip_decode_levels_frames; checked in its order, for any n_frames: geometry, steps, reduce
+ * (anything but 2, 4, 8 is SVC_ERR_INVALID_ARG), display size, limits, workspace (that of
+ * svc_hip_decode_levels_workspace_bytes: the same scan runs), then pointers.  d_status and failed
+ * frames as there.  Only enqueues work. */
+int svc_hip_decode_levels_reduced_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                         const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                         uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                         uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                         uint32_t fg_step, uint32_t bg_step, uint32_t reduce,
+                                         const uint32_t* d_gaze /* [n_frames][4] x, y, w, h (padded, full size); NULL = none */,
+                                         uint8_t* d_workspace, uint64_t workspace_bytes,
+                                         float* d_rec /* [n][H / reduce][W / reduce][3] f32 B,G,R */,
+                                         uint8_t* d_display /* [n][display_h][display_w][3] u8 B,G,R, or NULL */,
+                                         uint32_t display_w, uint32_t display_h, uint32_t* d_status,
+                                         void* stream);
+
 /* The same decoder straight from SVCE frames, without the SVCQ frames in between: d_rec and
  * d_display are bit-identical to svc_hip_entropy_decode_frames followed by
  * svc_hip_decode_levels_frames with the same arguments and gaze.  d_status [n_frames] u32 with the

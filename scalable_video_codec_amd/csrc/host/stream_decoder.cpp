@@ -116,14 +116,17 @@ struct StreamDecoder::Impl {
   // layers: for DecodeLayers (the workspace of svc_hip_decode_layers_frames; enh_entropy = the enhancement stream is SVCE)
   void Size(const uint32_t* hdr, bool entropy, bool layers = false, bool enh_entropy = false) {
     const uint32_t w = hdr[kHWidth], h = hdr[kHHeight], tw = hdr[kHTileW], th = hdr[kHTileH], mw = hdr[kHMvW], mh = hdr[kHMvH];
-    const uint32_t want_dw = c.display_w ? c.display_w : w, want_dh = c.display_h ? c.display_h : h;
+    const uint32_t rw = w / c.reduce, rh = h / c.reduce;  // the picture the display pass reads
+    const uint32_t want_dw = c.display_w ? c.display_w : rw, want_dh = c.display_h ? c.display_h : rh;
     if (!wire && entropy == svce && layers == layered && enh_entropy == enh_svce && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
       return;
     pipe->SyncStreams();
     const uint64_t need_ws = layers ? svc_hip_decode_layers_workspace_bytes(c.batch, w, h, tw, th)
                                     : svc_hip_decode_levels_workspace_bytes(c.batch, w, h, tw, th);
     if (!need_ws) Abi(SVC_ERR_UNSUPPORTED, "no decoder for the first frame's geometry");
-    if (want_dw > w || want_dh > h) throw std::runtime_error("svc::StreamDecoder: the display size exceeds the padded frame");
+    if (want_dw > rw || want_dh > rh)
+      throw std::runtime_error(c.reduce > 1 ? "svc::StreamDecoder: the display size exceeds the padded frame over reduce"
+                                            : "svc::StreamDecoder: the display size exceeds the padded frame");
     if (entropy || enh_entropy) {
       q_bytes = svc_hip_levels_max_bytes(c.batch, w, h, tw, th, mw, mh);
       ews_bytes = svc_hip_entropy_workspace_bytes(c.batch, w, h, tw, th, mw, mh);
@@ -140,7 +143,7 @@ struct StreamDecoder::Impl {
     disp_bytes = (uint64_t)dw * dh * 3;
     ws_bytes = need_ws;
     const size_t B = c.batch;
-    rec.Alloc(kWho, B * pw * ph * 3);
+    rec.Alloc(kWho, B * rw * rh * 3);
     ws.Alloc(kWho, ws_bytes);
     for (auto& s : slots) {
       s->disp.Alloc(kWho, B * disp_bytes); s->pin_disp.Alloc(kWho, B * disp_bytes);
@@ -188,7 +191,8 @@ StreamDecoder::StreamDecoder(const StreamDecoderConfig& config) : p_(new Impl) {
   Impl& m = *p_;
   m.c = config;
   const StreamDecoderConfig& c = m.c;
-  if (c.batch == 0 || c.wire_batch == 0 || c.depth < 3 || !c.fg_step || !c.bg_step || (c.display_w == 0) != (c.display_h == 0))
+  if (c.batch == 0 || c.wire_batch == 0 || c.depth < 3 || !c.fg_step || !c.bg_step || (c.display_w == 0) != (c.display_h == 0) ||
+      (c.reduce != 1 && c.reduce != 2 && c.reduce != 4 && c.reduce != 8))
     throw std::runtime_error("svc::StreamDecoder: invalid configuration");
   m.pipe.reset(new BatchPipe(kWho, c.depth));
   const size_t B = std::max(c.batch, c.wire_batch);  // per-frame arrays serve both paths
@@ -245,9 +249,14 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
                 "svc_hip_entropy_decode_frames");
             qin = m.q.p; qoff = m.qoff.p; qbytes = m.q_bytes;
           }
-          Abi(svc_hip_decode_levels_frames(qin, qbytes, qoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step, c.bg_step, s.gaze.p,
-                                           m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh, s.status.p, sk),
-              "svc_hip_decode_levels_frames");
+          if (c.reduce > 1)
+            Abi(svc_hip_decode_levels_reduced_frames(qin, qbytes, qoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step, c.bg_step,
+                                                     c.reduce, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh, s.status.p, sk),
+                "svc_hip_decode_levels_reduced_frames");
+          else
+            Abi(svc_hip_decode_levels_frames(qin, qbytes, qoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step, c.bg_step, s.gaze.p,
+                                             m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh, s.status.p, sk),
+                "svc_hip_decode_levels_frames");
         },
         [&](hipStream_t so) -> uint64_t {
           Hip(hipMemcpyAsync(s.pin_disp.p, s.disp.p, cnt * m.disp_bytes, hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H display");
@@ -263,6 +272,7 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
 
 void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offsets, const uint8_t* enh, const uint64_t* enh_offsets,
                                  uint32_t n_frames, const Gaze& gaze, const Sink& sink) {
+  if (p_->c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeLayers does not decode at reduced size (reduce must be 1)");
   if (!gaze) return Decode(base, base_offsets, n_frames, gaze, sink);  // no tile takes the enhancement: it is not read
   Impl& m = *p_;
   const StreamDecoderConfig& c = m.c;
@@ -336,6 +346,7 @@ void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offse
 void StreamDecoder::DecodeWire(const uint8_t* stream, uint64_t bytes, const Gaze& gaze, const Sink& sink) {
   Impl& m = *p_;
   const StreamDecoderConfig& c = m.c;
+  if (c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeWire does not decode at reduced size (reduce must be 1)");
   if (!stream || bytes < sizeof(svc_wire_header)) throw std::runtime_error("svc::StreamDecoder: a wire stream opens with a 32-byte header");
   svc_wire_header hdr;
   std::memcpy(&hdr, stream, sizeof(hdr));

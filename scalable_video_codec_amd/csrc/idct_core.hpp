@@ -20,6 +20,14 @@ template <> struct IBasis<16> {
   static __device__ __forceinline__ double even(int k, int n) { return kDctEven16[k][n]; }
   static __device__ __forceinline__ double odd(int k, int n) { return kDctOdd16[k][n]; }
 };
+template <> struct IBasis<4> {  // 4 and 2: the reduced decode's K-point transforms (K = N / reduce)
+  static __device__ __forceinline__ double even(int k, int n) { return kDctEven4[k][n]; }
+  static __device__ __forceinline__ double odd(int k, int n) { return kDctOdd4[k][n]; }
+};
+template <> struct IBasis<2> {
+  static __device__ __forceinline__ double even(int k, int n) { return kDctEven2[k][n]; }
+  static __device__ __forceinline__ double odd(int k, int n) { return kDctOdd2[k][n]; }
+};
 
 // x[n] = sum_k C[k][n] y[k]: even-k terms are symmetric, odd-k terms antisymmetric in n <-> N-1-n
 template <int N>
@@ -71,6 +79,36 @@ __device__ __forceinline__ void invert_column(const double* slab, uint32_t t, ui
   idct1d<N>(cc, xx);
 #pragma unroll
   for (int y = 0; y < N; ++y) out[y] = (float)xx[y];
+}
+
+// The reduced decode (svc_hip_decode_levels_reduced_frames): the same two passes on the first K x K coefficients of an N x N tile, with the
+// K-point transform and a slab of pitch K + 1; thread (t, j), j < K.  The 1-point transform is the identity.  The column pass scales by
+// K / N (a power of two: exact) before its one rounding to f32.
+template <int K>
+__device__ __forceinline__ void idct1d_reduced(const double* __restrict__ y, double* __restrict__ x) {
+  if constexpr (K == 1) x[0] = y[0];
+  else idct1d<K>(y, x);
+}
+
+template <int K>
+__device__ __forceinline__ void invert_row_reduced(const float* coef, float step, double* slab, uint32_t t, uint32_t j) {
+  double y[K], r[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) y[i] = (double)requant(coef[i], step);
+  idct1d_reduced<K>(y, r);
+  double* row = slab + (t * K + j) * (K + 1);
+#pragma unroll
+  for (int i = 0; i < K; ++i) row[i] = r[i];
+}
+
+template <int N, int K>
+__device__ __forceinline__ void invert_column_reduced(const double* slab, uint32_t t, uint32_t j, float (&out)[K]) {
+  double cc[K], xx[K];
+#pragma unroll
+  for (int v = 0; v < K; ++v) cc[v] = slab[(t * K + v) * (K + 1) + j];
+  idct1d_reduced<K>(cc, xx);
+#pragma unroll
+  for (int y = 0; y < K; ++y) out[y] = (float)(xx[y] * ((double)K / N));
 }
 
 // is the tile at (tx, ty) inside frame f's gaze rectangle?  gaze = [n][4] x, y, w, h in padded coordinates, or null (no gaze):

@@ -26,6 +26,9 @@
 // merge of the two statuses, then the same reconstruction with its enhancement compiled in, which inside the gaze adds the enhancement
 // frame's residuals.
 //
+// decode at reduced size (svc_hip_decode_levels_reduced_frames): the decode's count and scan, then a reconstruction from the first K x K
+// coefficients of every N x N tile to a picture of 1 / reduce the size (stated at its kernel).
+//
 // window (svc_hip_window_levels_frames): a stored stream restricted to a window per output frame, without the pixels -- count, scan,
 // frame offsets, then one pass that writes every output frame in aligned 16-byte vectors (stated at its kernels).
 //
@@ -614,6 +617,79 @@ __global__ __launch_bounds__(256) void decode_layers_kernel(DecodeLayersArgs a) 
   __shared__ uint64_t enh_mask[kMaxJobs];
   __shared__ uint32_t enh_base[kMaxJobs];
   decode_body<N, true>(a, enh_mask, enh_base);
+}
+
+// ---- decode at reduced size: the first K x K coefficients of every N x N tile ------------------------------------------------------
+//
+// svc_hip_decode_levels_reduced_frames (include/svc_hip.h states it).  The grid, the rank of a level and the steps are decode_body's;
+// the workgroup is only as large as its transform: thread (t, j < K) for the group's tiles, K * tiles threads, at least a wave (N = 8:
+// 128, 64, 64; N = 16: 64).  A group has at most 64 mask words, so wave 0 scans each plane's words in registers, and every plane has
+// job arrays and an f64 slab of its own: two barriers in all (words -> gather and row passes -> column passes) where decode_body takes
+// five per plane.  The thread gathers the K levels of coefficient row j of tile t in each plane, the passes are idct_core.hpp's reduced
+// ones on a slab of pitch K + 1, and the thread stores its column of K pixels of the (W K / N) x (H K / N) picture: tile (tx, ty) is the
+// K x K pixels at (tx K, ty K).  Only K * K of a tile's levels are read; no f32 plane and no full-size picture is written.
+constexpr uint32_t reduced_threads(uint32_t n, uint32_t k) { return std::max<uint32_t>(64, k * (kGroupCoeffs / (n * n))); }
+
+template <int N, int K>
+__global__ __launch_bounds__(reduced_threads(N, K)) void decode_reduced_kernel(DecodeArgs a) {
+  constexpr uint32_t kTiles = kGroupCoeffs / (N * N), kJobs = kTiles * ((N * N + 63) / 64);  // tiles and mask words of a group
+  static_assert(kJobs <= 64, "one wave scans a group's mask words");
+  __shared__ uint64_t job_mask[3][kJobs];
+  __shared__ uint32_t job_base[3][kJobs];
+  __shared__ double rows[3][kTiles * K * (K + 1)];
+  const Geom& g = a.g;
+  const uint32_t gi0 = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t st = a.ws.status[f];
+  const uint8_t* frame = a.in + a.offsets[f];  // dereferenced only for a frame that passed its checks
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t t = tid / K, j = tid - t * K;
+  const bool active = t < gr.nt;  // (nt <= kTiles)
+  const uint32_t jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
+  if (tid < 64) {  // wave 0: mask: 0 for a frame that failed and past the group's words, no level is read through it
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint64_t m = (st == kStOk && tid < jobs) ? load_mask(group_masks(g, frame, c, gr) + 2 * tid) : 0ull;
+      const uint32_t ex = wave_exclusive_scan((uint32_t)__popcll(m));
+      if (tid < kJobs) { job_mask[c][tid] = m; job_base[c][tid] = ex; }
+    }
+  }
+  float enc = 0.f, dec = 1.f;
+  if (st == kStOk && active) {
+    const uint32_t type = tile_type(g, reinterpret_cast<const uint32_t*>(frame + kHeaderBytes), gr, t);
+    const bool in_gaze = gazed(a.gaze, f, gr.x0 + t * N, gr.y0);  // the full-size tile origin: one rule for both decoders
+    enc = (float)(type == 0 ? hdr[kHBgStep] : hdr[kHFgStep]);
+    dec = in_gaze ? 1.f : (type == 0 ? a.bg : a.fg);
+  }
+  __syncthreads();
+  if (active) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const size_t gi = (size_t)f * g.groups + c * per_plane + gi0;
+      const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) + (st == kStOk ? a.ws.cnt[gi] : 0u);
+      float v[K];
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        const uint32_t k = j * N + i, w = t * g.words + (k >> 6), b = k & 63u;
+        const uint64_t mask = job_mask[c][w], below = (1ull << b) - 1;
+        v[i] = 0.f;
+        if ((mask >> b) & 1u) v[i] = (float)levels[job_base[c][w] + (uint32_t)__popcll(mask & below)] * enc;
+      }
+      invert_row_reduced<K>(v, dec, rows[c], t, j);
+    }
+  }
+  __syncthreads();
+  if (!active) return;
+  float out[3][K];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) invert_column_reduced<N, K>(rows[c], t, j, out[c]);
+  const uint32_t rw = g.w / N * K;  // the reduced picture's width; adjacent lanes hold adjacent pixels
+  store_bgr_column<K>(a.rec + (((size_t)f * (g.h / N * K) + gr.ty * K) * rw + (gr.t0 + t) * K + j) * 3, rw, out);
+}
+
+template <int N, int K>
+void launch_decode_reduced(dim3 grid, hipStream_t s, const DecodeArgs& a) {
+  hipLaunchKernelGGL((decode_reduced_kernel<N, K>), grid, dim3(reduced_threads(N, K)), 0, s, a);
 }
 
 // ---- window: SVCQ frames restricted to the tiles of a window, stream to stream ---------------------------------------------------
@@ -1663,6 +1739,47 @@ int svc_hip_decode_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   if (block_w == 8) hipLaunchKernelGGL(decode_levels_kernel<8>, grid, dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(decode_levels_kernel<16>, grid, dim3(kThreads), 0, s, a);
   return finish_with_display("decode_levels", "reconstruction", display, d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+}
+
+// Checked in the order of svc_hip_decode_levels_frames, `reduce` after the steps and the display size against the reduced picture.
+int svc_hip_decode_levels_reduced_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                         uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                         uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, uint32_t reduce, const uint32_t* d_gaze,
+                                         uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec, uint8_t* d_display, uint32_t display_w,
+                                         uint32_t display_h, uint32_t* d_status, void* stream) {
+  const char* what = "decode_levels_reduced";
+  int rc = validate_decode_geom(what, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "%s: quant steps must be positive (libs/decoder.cpp:35-47)", what);
+  SVC_REQUIRE(reduce == 2 || reduce == 4 || reduce == 8, "%s: reduce %u (supported: 2, 4, 8)", what, reduce);
+  const uint32_t rw = frame_w / reduce, rh = frame_h / reduce;  // whole: the sides are multiples of the block, the block of `reduce`
+  const bool display = display_w != 0 || display_h != 0;
+  SVC_REQUIRE(!display || (display_w >= 1 && display_w <= rw && display_h >= 1 && display_h <= rh),
+              "%s: display %ux%u must lie within 1x1 .. %ux%u (the padded frame over reduce)", what, display_w, display_h, rw, rh);
+  if ((rc = validate_limits(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(stream_ws, n_frames, g.groups)))) return rc;
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_rec && d_status, "%s: null pointer", what);
+  if ((rc = validate_display_buffer(what, display, d_display))) return rc;
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_rec, 4) &&
+                  aligned(d_status, 4) && aligned(d_gaze, 4),
+              "%s: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte", what);
+  const UnpackArgs u{g, d_frames, stream_bytes, d_frame_offsets, nullptr, nullptr, carve(d_workspace, stream_ws, n_frames, g.groups)};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = enqueue_unpack_scan(what, u, n_frames, d_status, s))) return rc;
+  const DecodeArgs a{g, d_frames, d_frame_offsets, d_gaze, d_rec, u.ws, (float)fg_step, (float)bg_step};
+  const dim3 grid(g.tiles_y * g.gx, n_frames);
+  if (block_w == 8) {
+    if (reduce == 2) launch_decode_reduced<8, 4>(grid, s, a);
+    else if (reduce == 4) launch_decode_reduced<8, 2>(grid, s, a);
+    else launch_decode_reduced<8, 1>(grid, s, a);
+  } else {
+    if (reduce == 2) launch_decode_reduced<16, 8>(grid, s, a);
+    else if (reduce == 4) launch_decode_reduced<16, 4>(grid, s, a);
+    else launch_decode_reduced<16, 2>(grid, s, a);
+  }
+  return finish_with_display(what, "reconstruction", display, d_rec, d_display, n_frames, rw, rh, display_w, display_h, s);
 }
 
 uint64_t svc_hip_decode_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,

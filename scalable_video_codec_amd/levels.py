@@ -1,9 +1,10 @@
 """Host reader of the compact quantised-coefficient stream ("SVCQ", format version 1; layout in include/svc_hip.h, written by
-svc_hip_pack_levels_frames), and the step ladders its rate control (svc_hip_pack_levels_budget_frames) picks from.  Pure numpy: a
-consumer of the stream needs neither a GPU nor the native library."""
+svc_hip_pack_levels_frames), the step ladders its rate control (svc_hip_pack_levels_budget_frames) picks from, and the statement of
+the decode at reduced size (svc_hip_decode_levels_reduced_frames).  Pure numpy: a consumer of the stream needs neither a GPU nor the
+native library."""
 from __future__ import annotations
 
-from typing import Dict, Iterator, Tuple
+from typing import Dict, Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -104,3 +105,64 @@ def step_ladder(fg_lo: int, fg_hi: int, bg_lo: int, bg_hi: int, n_bg: int, n_fg:
         if p != out[-1]:
             out.append(p)
     return np.array(out, np.uint32).reshape(-1, 2)
+
+
+# ---- decode at reduced size from the low frequencies (include/svc_hip.h: svc_hip_decode_levels_reduced_frames) ------------------------
+
+def _reduced_side(hdr: Dict[str, int], reduce: int) -> Tuple[int, int]:
+    n = hdr["block_w"]
+    if hdr["block_h"] != n or n not in (8, 16):
+        raise ValueError(f"transform block {hdr['block_w']}x{hdr['block_h']} (supported: 8x8, 16x16)")
+    if reduce not in (1, 2, 4, 8):
+        raise ValueError(f"reduce {reduce} (supported: 1, 2, 4, 8)")
+    return n, n // reduce
+
+
+def _reduced(frame, reduce: int, fg_step: int, bg_step: int, gaze) -> Tuple[np.ndarray, int]:
+    """reduced_coefficients and its K."""
+    if fg_step <= 0 or bg_step <= 0:
+        raise ValueError("quant steps must be positive")
+    hdr, types, planes = parse_frame(frame)  # planes: (f32)level * (f32)enc_step
+    n, k = _reduced_side(hdr, reduce)
+    w, h = hdr["frame_w"], hdr["frame_h"]
+    tx, ty = w // n, h // n
+    ox, oy = (np.arange(tx) * n)[None, :], (np.arange(ty) * n)[:, None]
+    background = types[(oy // hdr["mv_block_h"]), (ox // hdr["mv_block_w"])] == 0
+    step = np.where(background, np.float32(bg_step), np.float32(fg_step)).astype(np.float32)
+    if gaze is not None:
+        x, y, gw, gh = (int(v) for v in gaze)
+        step = np.where((ox >= x) & (ox - x < gw) & (oy >= y) & (oy - y < gh), np.float32(1), step)
+    tiles = planes.reshape(3, ty, n, tx, n)[:, :, :k, :, :k]
+    s = step[None, :, None, :, None]
+    q = (tiles / s).astype(np.float32).astype(np.float64)
+    r = np.copysign(np.floor(np.abs(q) + 0.5), q).astype(np.float32)
+    out = (r * s).astype(np.float32) * np.float32(k / n)
+    return np.ascontiguousarray(out.reshape(3, ty * k, tx * k), np.float32), k
+
+
+def reduced_coefficients(frame, reduce: int, fg_step: int, bg_step: int, gaze: Optional[Sequence[int]] = None) -> np.ndarray:
+    """What the reduced decoder inverts -> (3, H / reduce, W / reduce) f32, laid out as K x K tiles (K = N / reduce): the first K x K
+    coefficients of every N x N tile, c = (f32)level * (f32)enc_step requantised with the decoder's step (1 for a tile whose origin
+    the gaze rectangle x, y, w, h holds, else bg_step for a tile whose MV block has type 0, else fg_step), q = roundf(c / step) * step,
+    and scaled by K / N.  Every operation is one f32 operation: roundf is taken in f64 on the f32 quotient (exact there; in f32
+    floor(|q| + 0.5) is wrong for quotients above 2^23), the scaling is by a power of two.  reduce = 1: the full decoder's q."""
+    return _reduced(frame, reduce, fg_step, bg_step, gaze)[0]
+
+
+def _basis(k: int) -> np.ndarray:
+    """The orthonormal DCT-II basis C[u][m] = a_k(u) cos(pi u (2 m + 1) / 2 k), f64."""
+    u, m = np.arange(k)[:, None], np.arange(k)[None, :]
+    a = np.where(u == 0, np.sqrt(1.0 / k), np.sqrt(2.0 / k))
+    return a * np.cos(np.pi * u * (2 * m + 1) / (2 * k))
+
+
+def decode_reduced_frame(frame, reduce: int, fg_step: int, bg_step: int, gaze: Optional[Sequence[int]] = None) -> np.ndarray:
+    """The reduced decoder's picture before its rounding to f32 -> (H / reduce, W / reduce, 3) f64 B,G,R: the K-point inverse DCT-II
+    along rows and columns of every K x K tile of reduced_coefficients.  reduce = 1 is the full decoder."""
+    coef, k = _reduced(frame, reduce, fg_step, bg_step, gaze)
+    coef = coef.astype(np.float64)
+    c = _basis(k)
+    _, rh, rw = coef.shape
+    t = coef.reshape(3, rh // k, k, rw // k, k)
+    x = np.einsum("vy,pavbu,ux->paybx", c, t, c)  # x[y][x] = sum_v sum_u C[v][y] q[v][u] C[u][x]
+    return np.ascontiguousarray(x.reshape(3, rh, rw).transpose(1, 2, 0))

@@ -142,6 +142,7 @@ SIGNATURES = {
     # its decoder (csrc/levels.hip) and the gaze rule
     "svc_hip_decode_levels_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_decode_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "svc_hip_decode_levels_reduced_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 10 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     "svc_hip_decode_entropy_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_decode_entropy_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     "svc_hip_gaze_rect": (C.c_int, [_u32] * 8 + [C.POINTER(_u32)]),
@@ -993,6 +994,34 @@ def decode_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h:
                                                _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
                                                None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
                                                _dev(status, torch.int32), _stream()))
+    return rec, out_display, status
+
+
+def decode_levels_reduced_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, fg_step: int = 1,
+                                 bg_step: int = 640, reduce: int = 2, gaze=None, display: Optional[Tuple[int, int]] = None,
+                                 rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None,
+                                 workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """decode_levels_frames at 1 / reduce of the size (reduce 2, 4 or 8), from the first K x K coefficients of every tile, K = block /
+    reduce -> (rec (frames, H / reduce, W / reduce, 3) f32 B,G,R, display (frames, display_h, display_w, 3) u8 or None, status).  w, h
+    and the gaze rectangles are the padded full size's; display: (w, h) within (W / reduce, H / reduce).  Host statement:
+    levels.reduced_coefficients / levels.decode_reduced_frame."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    if rec is None:
+        rec = torch.empty((n, h // max(reduce, 1), w // max(reduce, 1), 3), dtype=torch.float32, device=dev)
+    dw, dh = display if display is not None else (0, 0)
+    if display is not None and out_display is None:
+        out_display = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(decode_levels_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=dev)
+    g = _rects(gaze, n, dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_decode_levels_reduced_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, w, h, bw,
+                                                       bh, mbw, mbh, fg_step, bg_step, reduce, None if g is None else _dev(g, torch.int32),
+                                                       _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
+                                                       None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
+                                                       _dev(status, torch.int32), _stream()))
     return rec, out_display, status
 
 

@@ -5,6 +5,12 @@
                                          display pass (1920x1080 u8); run under `rocprofv3 --kernel-trace --stats -- python ...`
   python tools/decode_probe.py rate      tests/dropin/stream_levels_main writes a 65-frame clip's stream, tests/dropin/stream_decode_main
                                          decodes it to 1920x1080 display frames with a moving gaze centre (PCIe included)
+  python tools/decode_probe.py reduced   one C3 batch of 16 at (1, 640), in one process: per reduce 2, 4, 8 the reduced call
+                                         (svc_hip_decode_levels_reduced_frames) with the display (W / r, H / r) against
+                                         svc_hip_decode_levels_frames with the display pass at that size, alternating, device events;
+                                         the bytes each route stores; and at steps (1, 1) the PSNR of both against the r x r box mean
+  python tools/decode_probe.py reduced-rate   the 65-frame stream of `rate` through tests/dropin/stream_reduced_main and through
+                                         stream_decode_main at the same display sizes (PCIe included)
 """
 import os
 import subprocess
@@ -55,22 +61,28 @@ def kernels() -> None:
           f"{CFG.width * CFG.height * 3 / 1e6:.2f} MB display per frame", flush=True)
 
 
+def _stored_stream(d, n):
+    """`rate`'s clip and its stream under directory d -> the stream's prefix."""
+    clip = synth.SynthClip(CFG.width, CFG.height, n, CFG.seed, device="cpu")
+    raw = os.path.join(d, "clip.raw")
+    with open(raw, "wb") as f:
+        for t in range(n):
+            clip.frame_bgr(t).numpy().tofile(f)
+    prefix = os.path.join(d, "enc")
+    enc = os.path.join(ROOT, "tests", "dropin", "stream_levels_main")
+    r = subprocess.run([enc, raw, str(CFG.width), str(CFG.height), str(n), str(CFG.levels), str(CFG.dct_block), "0", "16",
+                        str(CFG.seed), prefix], capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        print(r.stdout, r.stderr)
+        sys.exit(1)
+    return prefix
+
+
 def rate() -> None:
     n = 65
-    clip = synth.SynthClip(CFG.width, CFG.height, n, CFG.seed, device="cpu")
     tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
     with tempfile.TemporaryDirectory(dir=tmp) as d:
-        raw = os.path.join(d, "clip.raw")
-        with open(raw, "wb") as f:
-            for t in range(n):
-                clip.frame_bgr(t).numpy().tofile(f)
-        prefix = os.path.join(d, "enc")
-        enc = os.path.join(ROOT, "tests", "dropin", "stream_levels_main")
-        r = subprocess.run([enc, raw, str(CFG.width), str(CFG.height), str(n), str(CFG.levels), str(CFG.dct_block), "0", "16",
-                            str(CFG.seed), prefix], capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            print(r.stdout, r.stderr)
-            sys.exit(1)
+        prefix = _stored_stream(d, n)
         gaze = os.path.join(d, "gaze.txt")
         with open(gaze, "w") as f:
             for i in range(n - 1):
@@ -84,5 +96,106 @@ def rate() -> None:
                 sys.exit(1)
 
 
+def reduced() -> None:
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native, pipeline
+    dev = torch.device("cuda")
+    n = 17
+    clip = synth.SynthClip(CFG.width, CFG.height, n, CFG.seed, device=dev)
+    pw, ph = CFG.padded
+    frames = [synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(n)]
+    enc = pipeline.ClipEncoder(CFG, n, dev)
+    enc.load_frames(frames)
+    enc.step()
+    planes, types = enc.coeffs, enc.types
+    block, mvb = CFG.dct_block, CFG.mv_block
+    out, offs = native.pack_levels_frames(planes, types, block, mvb, CFG.fg_step, CFG.bg_step)
+    m = n - 1
+    total = int(offs[-1].item())
+    ws = torch.empty(native.decode_levels_workspace_bytes(m, pw, ph, block), dtype=torch.uint8, device=dev)
+    rec_full = torch.empty((m, ph, pw, 3), dtype=torch.float32, device=dev)
+    print(f"C3 batch of {m} at steps ({CFG.fg_step}, {CFG.bg_step}): {total / m / 1e6:.3f} MB compact per frame", flush=True)
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    for r in (2, 4, 8):
+        rw, rh = pw // r, ph // r
+        rects = [native.gaze_rect((50 + 50 * i) // r, 500 // r, 64, 64, rw, rh, pw, ph) for i in range(m)]
+        rec = torch.empty((m, rh, rw, 3), dtype=torch.float32, device=dev)
+        disp_r = torch.empty((m, rh, rw, 3), dtype=torch.uint8, device=dev)
+        disp_f = torch.empty_like(disp_r)
+
+        def red():
+            native.decode_levels_reduced_frames(out, offs, pw, ph, block, mvb, CFG.fg_step, CFG.bg_step, reduce=r, gaze=rects,
+                                                display=(rw, rh), rec=rec, out_display=disp_r, workspace=ws)
+
+        def full():
+            native.decode_levels_frames(out, offs, pw, ph, block, mvb, CFG.fg_step, CFG.bg_step, gaze=rects, display=(rw, rh),
+                                        rec=rec_full, out_display=disp_f, workspace=ws)
+
+        for _ in range(3):
+            red(), full()
+        torch.cuda.synchronize()
+        t_red, t_full = [], []
+        for _ in range(7):  # alternating windows of 20 batches each
+            t_red.append(timed(red, 20))
+            t_full.append(timed(full, 20))
+        b_red = rw * rh * 12 + rw * rh * 3
+        b_full = pw * ph * 12 + rw * rh * 3
+        print(f"reduce {r}: display {rw}x{rh}; reduced call {np.median(t_red):.3f} ms per batch (min {min(t_red):.3f}, max {max(t_red):.3f}), "
+              f"stores {b_red / 1e6:.2f} MB per frame; full call + display pass {np.median(t_full):.3f} ms per batch (min {min(t_full):.3f}, "
+              f"max {max(t_full):.3f}), stores {b_full / 1e6:.2f} MB per frame; full / reduced = {np.median(t_full) / np.median(t_red):.2f}",
+              flush=True)
+
+    # quality at steps (1, 1): both routes' display frames against the r x r box mean of the padded source
+    bgr = torch.stack(frames[1:]).contiguous()
+    planes1 = native.dct_quant_frames(bgr, block, types, mvb, 1, 1)
+    out1, offs1 = native.pack_levels_frames(planes1, types, block, mvb, 1, 1)
+
+    def psnr(a, target):
+        mse = float(((a.float() - target) ** 2).mean().item())
+        return 10 * np.log10(255.0 ** 2 / max(mse, 1e-12))
+
+    for r in (2, 4, 8):
+        rw, rh = pw // r, ph // r
+        target = bgr.float().reshape(m, rh, r, rw, r, 3).mean(dim=(2, 4))
+        _, d_red, _ = native.decode_levels_reduced_frames(out1, offs1, pw, ph, block, mvb, 1, 1, reduce=r, display=(rw, rh))
+        _, d_full, _ = native.decode_levels_frames(out1, offs1, pw, ph, block, mvb, 1, 1, display=(rw, rh), rec=rec_full)
+        torch.cuda.synchronize()
+        print(f"quality at steps (1, 1), reduce {r}, against the {r}x{r} box mean of the source: reduced decode {psnr(d_red, target):.2f} dB, "
+              f"full decode + bilinear display {psnr(d_full, target):.2f} dB", flush=True)
+
+
+def reduced_rate() -> None:
+    n = 65
+    pw, ph = CFG.padded
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    here = os.path.join(ROOT, "tests", "dropin")
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        prefix = _stored_stream(d, n)
+        for r in (2, 4, 8):
+            dw, dh = pw // r, ph // r
+            gaze = os.path.join(d, f"gaze{r}.txt")
+            with open(gaze, "w") as f:
+                for i in range(n - 1):
+                    f.write(f"{(60 + 29 * i) % dw} {(40 + 17 * i) % dh}\n")
+            for turn in range(3):  # alternating, every run printed: the spread is part of the result
+                for name, args in (("stream_reduced_main", [str(r), "0", "0"]), ("stream_decode_main", [str(dw), str(dh)])):
+                    p = subprocess.run([os.path.join(here, name), prefix, str(n - 1), *args, gaze, "16", "-"], capture_output=True,
+                                       text=True, timeout=300)
+                    print(f"== {name} display {dw}x{dh} batch 16, run {turn} (exit {p.returncode})\n{p.stdout.strip()}\n{p.stderr.strip()}",
+                          flush=True)
+                    if p.returncode != 0:
+                        sys.exit(1)
+
+
 if __name__ == "__main__":
-    {"rate": rate, "kernels": kernels}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
+    {"rate": rate, "kernels": kernels, "reduced": reduced, "reduced-rate": reduced_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
