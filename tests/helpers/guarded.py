@@ -7,6 +7,9 @@ the interior, and at least 64 KiB) lands inside the allocation, where check() fi
 the test's own.  Device-agnostic: tests/test_guarded_host.py runs all of it on CPU tensors.
 
 What this cannot see: a read outside an input that does not change the result, and an overrun larger than the guard.
+
+Exact placement: `skew` puts the interior at an address that is `skew` mod `align`, and exactly(A) is the placement "a multiple of
+A and not of 2A", the weakest one a pointer documented as A-byte aligned admits (exactly(1) is an odd address).
 """
 from __future__ import annotations
 
@@ -28,18 +31,26 @@ def _pattern(nbytes: int, seed: int) -> torch.Tensor:
     return torch.from_numpy(np.random.default_rng(seed).integers(1, 255, nbytes, dtype=np.uint8))
 
 
+def exactly(a: int) -> Dict[str, int]:
+    """Keyword arguments for Guarded / like / surround: an address that is a multiple of `a` and not of 2 * a."""
+    assert a >= 1 and a & (a - 1) == 0, a
+    return {"align": 2 * a, "skew": a}
+
+
 class Guarded:
-    """One allocation of guard + nbytes + guard bytes; `interior` is a contiguous view of exactly nbytes bytes as `dtype`, aligned to
-    `align`.  guard = max(65536, nbytes) rounded up to align, on each side (the front one takes the few bytes that align the
-    interior).  Both guards hold a seeded pattern; check() says which of their bytes changed."""
+    """One allocation of guard + nbytes + guard bytes; `interior` is a contiguous view of exactly nbytes bytes as `dtype`, at an
+    address that is `skew` mod `align` (0 <= skew < align; a multiple of the element size unless dtype is u8).  guard =
+    max(65536, nbytes) rounded up to align, on each side (the front one takes the few bytes that place the interior).  Both guards
+    hold a seeded pattern; check() says which of their bytes changed."""
 
     def __init__(self, nbytes: int, dtype: torch.dtype = torch.uint8, device="cpu", align: int = 256, seed: int = 0,
-                 shape: Optional[Tuple[int, ...]] = None):
+                 shape: Optional[Tuple[int, ...]] = None, skew: int = 0, pin: bool = False):
         item = torch.empty(0, dtype=dtype).element_size()
         assert nbytes >= 0 and nbytes % item == 0 and align % item == 0, (nbytes, dtype, align)
+        assert 0 <= skew < align and skew % item == 0, (skew, align, dtype)
         guard = _round_up(max(MIN_GUARD, nbytes), align)
-        self.raw = torch.empty(2 * guard + nbytes + align, dtype=torch.uint8, device=device)
-        self.front = guard + (-(self.raw.data_ptr() + guard)) % align
+        self.raw = torch.empty(2 * guard + nbytes + align, dtype=torch.uint8, device=device, pin_memory=pin)  # pin: page-locked host memory
+        self.front = guard + (skew - (self.raw.data_ptr() + guard)) % align
         self.nbytes = nbytes
         self.back = self.raw.numel() - self.front - nbytes
         assert self.front >= guard and self.back >= guard
@@ -47,7 +58,9 @@ class Guarded:
         self.interior = self.bytes.view(dtype)
         if shape is not None:
             self.interior = self.interior.view(shape)
-        assert self.interior.data_ptr() % align == 0 and self.interior.is_contiguous()
+        self.addr = self.raw.data_ptr() + self.front  # the interior's address (an empty view's data_ptr() need not say it)
+        assert self.addr % align == skew and self.interior.is_contiguous()
+        assert nbytes == 0 or self.interior.data_ptr() == self.addr
         assert self.interior.numel() * item == nbytes
         self._want_front = _pattern(self.front, 2 * seed + 1).to(device)
         self._want_back = _pattern(self.back, 2 * seed + 2).to(device)
@@ -68,9 +81,47 @@ class Guarded:
         return (before - self.front).tolist(), after.tolist()
 
 
-def like(t: torch.Tensor, seed: int = 0, align: int = 256) -> Guarded:
+def like(t: torch.Tensor, seed: int = 0, align: int = 256, skew: int = 0) -> Guarded:
     """A Guarded whose interior has exactly the shape and type of t (its contents are not copied)."""
-    return Guarded(t.numel() * t.element_size(), t.dtype, t.device, align, seed, tuple(t.shape))
+    return Guarded(t.numel() * t.element_size(), t.dtype, t.device, align, seed, tuple(t.shape), skew)
+
+
+class Misplaced(torch.Tensor):
+    """A typed tensor whose data_ptr() is an address torch cannot give one (an i32 array at 2 mod 4, an i64 array at 4 mod 8): shape,
+    type and contents are those of `like`; data_ptr() is the interior of a u8 Guarded of the same size (`guarded`) that holds like's
+    bytes, and stays that through as_tensor / reshape / to / contiguous where they return the same elements.  For calls that must
+    refuse the pointer before any launch; should one launch all the same, it reads and writes inside that allocation."""
+
+    @staticmethod
+    def __new__(cls, like: torch.Tensor, seed: int = 0, align: int = 256, skew: int = 0, _guarded: Optional[Guarded] = None):
+        t = like.detach().contiguous()
+        self = torch.Tensor._make_subclass(cls, t)
+        if _guarded is None:
+            _guarded = Guarded(t.numel() * t.element_size(), torch.uint8, t.device, align, seed, skew=skew)
+            _guarded.bytes.copy_(t.view(-1).view(torch.uint8))
+        self.guarded = _guarded
+        return self
+
+    def data_ptr(self) -> int:
+        return self.guarded.addr
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        with torch._C.DisableTorchFunctionSubclass():
+            out = func(*args, **(kwargs or {}))
+            src = next((a for a in args if isinstance(a, Misplaced)), None)
+            if (src is not None and isinstance(out, torch.Tensor) and not isinstance(out, Misplaced) and out.dtype == src.dtype
+                    and out.numel() == src.numel() and out.is_contiguous() and out.device == src.device
+                    and torch.Tensor.data_ptr(out) == torch.Tensor.data_ptr(src)):
+                out = Misplaced(out, _guarded=src.guarded)  # the same elements under another shape: still at the placed address
+        return out
+
+
+def placed(tensor: torch.Tensor, seed: int, a: int):
+    """surround(tensor) at exactly(a); a Misplaced where a is no multiple of the element size."""
+    if a % tensor.element_size() == 0:
+        return surround(tensor, seed, **exactly(a))
+    return Misplaced(tensor, seed, **exactly(a))
 
 
 def poisons(nbytes: int, seed: int) -> Iterator[Tuple[str, Optional[torch.Tensor]]]:
@@ -82,11 +133,11 @@ def poisons(nbytes: int, seed: int) -> Iterator[Tuple[str, Optional[torch.Tensor
     yield "dirty", None
 
 
-def surround(tensor: torch.Tensor, seed: int, align: int = 256) -> torch.Tensor:
+def surround(tensor: torch.Tensor, seed: int, align: int = 256, skew: int = 0) -> torch.Tensor:
     """A copy of `tensor` (same shape and type) that is the interior of a Guarded whose guards hold seeded noise: two seeds give the
     same input with different neighbours.  The view keeps the allocation alive."""
     t = tensor.contiguous()
-    g = like(t, seed, align)
+    g = like(t, seed, align, skew)
     g.interior.copy_(t)
     return g.interior
 

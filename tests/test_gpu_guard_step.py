@@ -42,9 +42,10 @@ class Gapped:
     """An output of n frames of `used` bytes each, `stride` apart, in a Guarded that ends with the last frame: the frames are the
     defined output, the bytes between them must come back unchanged."""
 
-    def __init__(self, n, used, stride, seed=0):
+    def __init__(self, n, used, stride, seed=0, at=None):
+        """at: None (256-byte aligned), or A: the first frame lies at gd.exactly(A)."""
         self.n, self.used, self.stride = n, used, stride
-        self.g = gd.Guarded((n - 1) * stride + used, U8, "cuda", seed=seed)
+        self.g = gd.Guarded((n - 1) * stride + used, U8, "cuda", seed=seed, **({} if at is None else gd.exactly(at)))
         idx = torch.arange(self.g.nbytes, device="cuda") % stride
         self.gap = idx >= used
         self.before = None

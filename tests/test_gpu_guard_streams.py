@@ -68,15 +68,23 @@ class Pool:
     """The buffers one case writes: first a Guarded of exactly the asked size each; then (reuse) views of the same interiors for the
     call that dirties them.  A borrowed buffer is another pool's Guarded, used through a view from the start."""
 
-    def __init__(self):
-        self.written, self.reuse, self.borrowed = {}, False, set()
+    def __init__(self, place=None):
+        """place: None (every buffer 256-byte aligned), or name -> A: the buffer lies at gd.exactly(A).  An A that is no multiple of
+        the element size (a pointer one notch below its contract) gives a gd.Misplaced: for calls that refuse it."""
+        self.written, self.reuse, self.borrowed, self.place = {}, False, set(), place
 
     def buf(self, name, shape, dtype):
         shape = (shape,) if isinstance(shape, int) else tuple(shape)
-        nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+        item = torch.empty(0, dtype=dtype).element_size()
+        nbytes = int(np.prod(shape)) * item
         if not self.reuse and name not in self.borrowed:
             assert name not in self.written
-            self.written[name] = gd.Guarded(nbytes, dtype, "cuda", seed=len(self.written), shape=shape)
+            if self.place is not None and self.place[name] % item:
+                m = gd.Misplaced(torch.empty(shape, dtype=dtype, device="cuda"), len(self.written), **gd.exactly(self.place[name]))
+                self.written[name] = m.guarded
+                return m
+            kw = {} if self.place is None else gd.exactly(self.place[name])
+            self.written[name] = gd.Guarded(nbytes, dtype, "cuda", seed=len(self.written), shape=shape, **kw)
             return self.written[name].interior
         g = self.written[name]
         assert nbytes <= g.nbytes, (name, nbytes, g.nbytes)

@@ -1,5 +1,6 @@
 """tests/helpers/guarded.py catches what it claims to (no GPU): the stand-in "kernels" are plain torch functions on CPU tensors,
 four of them faulty in the four ways the GPU tests look for, one correct.  Each faulty one must be reported with the buffer named."""
+import pytest
 import torch
 
 from tests.helpers import guarded as gd
@@ -87,6 +88,103 @@ def test_the_guards_and_the_interior_are_what_the_rule_says():
         g.raw[g.front - 1] ^= 1
         g.raw[g.front + nbytes + 5] ^= 1
         assert g.check() == ([-1], [5])
+
+
+def test_exact_placement_arithmetic():
+    """exactly(A): a multiple of A and not of 2A, for every type that fits, through Guarded, like and surround; the guards keep
+    their size and their pattern."""
+    for a in (1, 2, 4, 8, 16, 64):
+        assert gd.exactly(a) == {"align": 2 * a, "skew": a}
+        for dtype in (torch.uint8, torch.int16, torch.int32, torch.int64):
+            item = torch.empty(0, dtype=dtype).element_size()
+            if a % item:
+                continue
+            for nbytes in (0, 8 * 5, 65536 + 8 * 3):
+                g = gd.Guarded(nbytes, dtype, seed=a, **gd.exactly(a))
+                p = g.addr
+                assert p % a == 0 and p % (2 * a) == a, (a, dtype, p)
+                assert p == g.raw.data_ptr() + g.front and (nbytes == 0 or g.interior.data_ptr() == p) and g.interior.numel() * item == nbytes
+                guard = (max(65536, nbytes) + 2 * a - 1) // (2 * a) * (2 * a)
+                assert guard <= g.front < guard + 2 * a and g.back >= guard
+                assert g.check() == ([], [])
+            t = torch.arange(21, dtype=dtype).reshape(3, 7)
+            lk = gd.like(t, 1, **gd.exactly(a))
+            sr = gd.surround(t, 2, **gd.exactly(a))
+            assert lk.interior.shape == t.shape and lk.interior.dtype == dtype and lk.interior.data_ptr() % (2 * a) == a
+            assert torch.equal(sr, t) and sr.is_contiguous() and sr.data_ptr() % (2 * a) == a
+    for align, skew in [(256, 16), (256, 255), (32, 24), (2, 0)]:  # any residue, not only the shorthand's
+        assert gd.Guarded(24, align=align, skew=skew).interior.data_ptr() % align == skew
+
+
+def test_exact_placement_refuses_what_the_rule_excludes():
+    for kw in ({"align": 16, "skew": 16}, {"align": 16, "skew": -1}):
+        with pytest.raises(AssertionError):
+            gd.Guarded(16, **kw)
+    for dtype, a in [(torch.int32, 2), (torch.int32, 1), (torch.int64, 4), (torch.int16, 1)]:  # skew no multiple of the element
+        with pytest.raises(AssertionError):
+            gd.Guarded(16, dtype, **gd.exactly(a))
+    gd.Guarded(16, torch.uint8, **gd.exactly(1))
+    with pytest.raises(AssertionError):
+        gd.exactly(3)
+
+
+def test_guards_catch_one_byte_either_side_of_a_skewed_interior():
+    for a in (1, 2, 4, 8, 16, 64):
+        for nbytes in (8, 24, 65536 + 8):
+            g = gd.Guarded(nbytes, seed=5, **gd.exactly(a))
+            before, after = g.raw[g.front - 1].clone(), g.raw[g.front + nbytes].clone()
+            g.raw[g.front - 1] ^= 1
+            assert g.check() == ([-1], [])
+            g.raw[g.front - 1] = before
+            g.raw[g.front + nbytes] ^= 0x80
+            assert g.check() == ([], [0])
+            g.raw[g.front + nbytes] = after
+            g.bytes.fill_(0xA5)  # the interior's own first and last byte are not guard
+            assert g.check() == ([], [])
+    src = torch.arange(N, dtype=torch.int32)
+    inside = gd.surround(src, 0, **gd.exactly(4))
+    for fault, words in [("write_before", "wrote before buffer 'out'"), ("write_after", "wrote after buffer 'scratch'"), (None, None)]:
+        written = {"out": gd.Guarded(4, torch.int32, **gd.exactly(4)), "scratch": gd.Guarded(4 * N, torch.int32, **gd.exactly(8))}
+
+        def call():
+            _sum_kernel(inside, written["out"].interior, written["scratch"].interior, fault)
+            return {"out": written["out"].interior}
+        found = gd.check_writes("sum_kernel", written, call)
+        assert (found == []) if fault is None else (found and all(words in f for f in found)), (fault, found)
+
+
+def test_the_default_placement_is_what_it_was():
+    """skew=0, align=256: the same front, back, interior and guard bytes as an allocation placed by the rule as first written."""
+    for nbytes, dtype, seed in [(0, torch.uint8, 0), (20, torch.int32, 3), (65536 + 8, torch.float32, 1), (200000, torch.uint8, 9)]:
+        g = gd.Guarded(nbytes, dtype, seed=seed)
+        h = gd.Guarded(nbytes, dtype, seed=seed, align=256, skew=0)
+        guard = (max(65536, nbytes) + 255) // 256 * 256
+        for x in (g, h):
+            assert x.raw.numel() == 2 * guard + nbytes + 256
+            assert x.front == guard + (-(x.raw.data_ptr() + guard)) % 256
+            assert x.back == x.raw.numel() - x.front - nbytes
+            assert x.interior.data_ptr() % 256 == 0
+            assert torch.equal(x.raw[:x.front], gd._pattern(x.front, 2 * seed + 1))
+            assert torch.equal(x.raw[x.front + nbytes:], gd._pattern(x.back, 2 * seed + 2))
+    t = torch.arange(12, dtype=torch.int16)
+    assert gd.like(t).interior.data_ptr() % 256 == 0 and gd.surround(t, 1).data_ptr() % 256 == 0
+    assert gd.like(t, 0, 64).interior.data_ptr() % 64 == 0 and gd.surround(t, 1, 64).data_ptr() % 64 == 0  # positional align
+
+
+def test_a_pointer_torch_cannot_place():
+    t = torch.arange(6, dtype=torch.int32).reshape(2, 3)
+    m = gd.placed(t, 3, 2)
+    assert isinstance(m, gd.Misplaced) and m.data_ptr() % 4 == 2 and m.dtype == torch.int32 and m.shape == (2, 3) and m.numel() == 6
+    assert m.is_contiguous() and len(m) == 2 and torch.equal(m[1], t[1]) and torch.equal(m.clone(), t)
+    assert torch.equal(m.guarded.bytes, t.view(-1).view(torch.uint8)) and m.guarded.check() == ([], [])
+    r = torch.as_tensor(m, dtype=torch.int32).reshape(-1).to("cpu").contiguous()  # what the bindings do to an argument
+    assert isinstance(r, gd.Misplaced) and r.data_ptr() == m.data_ptr() and r.shape == (6,)
+    assert not isinstance(m.clone(), gd.Misplaced) and m.clone().data_ptr() % 4 == 0  # other elements: an ordinary tensor
+    o = gd.placed(torch.arange(4, dtype=torch.int64), 1, 4)
+    assert isinstance(o, gd.Misplaced) and o.data_ptr() % 8 == 4
+    s = gd.placed(t, 3, 4)
+    assert isinstance(s, torch.Tensor) and s.data_ptr() % 8 == 4 and torch.equal(s, t)
+    assert isinstance(gd.placed(torch.zeros(5, dtype=torch.uint8), 0, 1), torch.Tensor)
 
 
 def test_poisons_and_surround():
