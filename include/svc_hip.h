@@ -446,7 +446,9 @@ int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_ty
  * checked against the geometry passed here and against the offsets; d_status [n_frames] u32:
  * 0 ok, 1 offsets out of range, 2 magic, 3 version, 4 geometry or a step of 0, 5 frame size,
  * 6 level count != the masks' popcount, 7 mask bits set past block_w * block_h.  A frame that
- * fails is written as zeros. */
+ * fails is written as zeros.  (The codes of other calls: 8 .. 10 the entropy decoder's, 11 and
+ * 0x100 | code those of the calls that take two streams, 12 svc_hip_union_levels_frames' for two
+ * frames whose masks share a bit.) */
 int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                                  const uint64_t* d_frame_offsets, uint32_t n_frames,
                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
@@ -1078,6 +1080,93 @@ int svc_hip_split_levels_budget_frames(const uint8_t* d_frames, uint64_t stream_
                                        uint64_t* d_enh_offsets /* [n_out + 1]; NULL with d_enh_out */,
                                        uint32_t* d_choice /* [n_out] */, uint32_t* d_status /* [n_out] */,
                                        void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * A stored SVCQ stream restricted to a frequency band, and optionally a window, per output frame,
+ * stream to stream: store the fine stream once, serve each viewer the coefficients its display
+ * needs, and send the next band when the viewer enlarges.  scalable_video_codec_amd/layers.py
+ * (band_frame, band_frames) is the numpy statement.
+ *
+ * The arguments are those of svc_hip_window_levels_frames plus d_band; d_src (repeats and any order
+ * allowed: one call serves several viewers at different sizes) and d_window work as they do there.
+ * Coefficient (row r, column c) of a tile is kept iff d_window[i] contains the tile's origin and,
+ * with lo_w, lo_h, hi_w, hi_h = d_band[i],
+ *   r < hi_h  &&  c < hi_w  &&  !(r < lo_h && c < lo_w)
+ * -- a plain predicate on the u32 values as they are read on the device: nothing about them is
+ * validated, a hi above the tile side means the side, hi == 0 or lo >= hi keeps nothing.  The bands
+ * (0, 0, K1, K1), (K1, K1, K2, K2), (K2, K2, block_w, block_h) partition a tile.
+ *
+ * The output frame is defined on the masks, exactly as the window call's is:
+ *   header   words 0 .. 9 and 11 copied, word 10 = the kept levels, word 12 = up16(levels offset +
+ *            2 * kept), words 13 .. 15 zero
+ *   types    copied
+ *   masks    every word the input's ANDed with the band's bits, zero outside the window
+ *   levels   the kept int16 levels, in the input's order
+ *   padding  zero, to 16 bytes
+ * A set bit whose level is 0 stays set.  The mask section keeps its full size whatever the band.
+ *
+ * Consequences:
+ *   - with d_band == NULL the bytes are those of svc_hip_window_levels_frames;
+ *   - svc_hip_decode_levels_reduced_frames at reduce r decodes the band (0, 0, K, K) stream, K =
+ *     N / r, bit for bit as it decodes the full stream: it never reads a coefficient outside K x K;
+ *   - every output is an SVCQ frame: the drains, the entropy coder, the host reader, the window
+ *     call and every decoder take it unchanged.
+ *
+ * d_status, failed frames (64 zero bytes, neighbours unaffected), the reads (inside the input
+ * stream), the writes (nothing past d_out_offsets[n_out]; two calls write the same bytes), the
+ * order of checks, the limits, the alignments (d_band 4-byte), n_out == 0 and the out_capacity rule
+ * are the window call's.  The query returns 0 where the call refuses.  d_out must not overlap the
+ * input stream: this is NOT checked.  Only enqueues work.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_band_levels_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h,
+                                             uint32_t block_w, uint32_t block_h,
+                                             uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_band_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                               const uint64_t* d_frame_offsets, uint32_t n_in,
+                               const uint32_t* d_src /* [n_out] index of the input frame; NULL = identity, then n_out must equal n_in */,
+                               uint32_t n_out,
+                               uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                               uint32_t mv_block_w, uint32_t mv_block_h,
+                               const uint32_t* d_window /* [n_out][4] x, y, w, h (padded); NULL = every tile */,
+                               const uint32_t* d_band /* [n_out][4] lo_w, lo_h, hi_w, hi_h; NULL = every coefficient */,
+                               uint8_t* d_workspace, uint64_t workspace_bytes,
+                               uint8_t* d_out, uint64_t out_capacity,
+                               uint64_t* d_out_offsets /* [n_out + 1] */,
+                               uint32_t* d_status /* [n_out] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * The inverse: frame i of stream A and frame i of stream B (the same geometry, n_frames each) give
+ * one frame whose masks are A | B and whose levels are both frames' in coefficient order.  Header
+ * words 0 .. 9 and 11 and the types are A's, word 10 is the sum of the two level counts.
+ * scalable_video_codec_amd/layers.py (union_frame, union_frames) is the numpy statement.
+ *
+ * The union of the bands of a partition, joined in any order, is the original frame byte for byte
+ * (the input may carry slack after its levels; the output never does).
+ *
+ * d_status [n_frames] u32: A's code of svc_hip_unpack_levels_frames if it is not 0; else 0x100 | B's
+ * code; else 0x100 | 11 when B's header steps (words 8, 9) or its types section differ from A's;
+ * else 12 when any mask bit is set in both.  A frame that fails is 64 zero bytes and leaves its
+ * neighbours as they would be.  Every read stays inside its input stream; nothing is written past
+ * d_out_offsets[n_frames]; two calls write the same bytes.
+ *
+ * Checked in the window call's order: geometry, limits, workspace, out_capacity against
+ * svc_hip_levels_max_bytes(n_frames, ...); n_frames == 0 then returns SVC_OK; then pointers
+ * (streams and workspace 16-byte aligned, offsets 8-byte, d_status 4-byte).  The query returns 0
+ * where the call refuses.  d_out must not overlap either input: this is NOT checked.  Only
+ * enqueues work.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_union_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                              uint32_t block_w, uint32_t block_h,
+                                              uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_union_levels_frames(const uint8_t* d_a, uint64_t a_bytes, const uint64_t* d_a_offsets,
+                                const uint8_t* d_b, uint64_t b_bytes, const uint64_t* d_b_offsets,
+                                uint32_t n_frames,
+                                uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                uint32_t mv_block_w, uint32_t mv_block_h,
+                                uint8_t* d_workspace, uint64_t workspace_bytes,
+                                uint8_t* d_out, uint64_t out_capacity,
+                                uint64_t* d_out_offsets /* [n_frames + 1] */,
+                                uint32_t* d_status /* [n_frames] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes

@@ -36,6 +36,10 @@
 // enhancement, in integers on the levels -- the window call's count and scan for the input, then count, scan, frame offsets and one
 // write pass, each serving both layers (stated at its kernels).
 //
+// band and union (svc_hip_band_levels_frames, svc_hip_union_levels_frames): a stored stream restricted to a frequency band of every tile
+// (and a window), and two streams with disjoint masks joined back -- the window call's count and scan for each input, then count, scan,
+// frame offsets and a write pass of the split's shape (stated at their kernels).
+//
 // pack of two layers (svc_hip_pack_layers_frames): the pack's count, scan and scatter on raw planes with two quantisations per coefficient,
 // the frame offsets from frame_offsets_kernel with a job per layer (stated at its kernels).
 #include "budget_core.hpp"
@@ -1407,6 +1411,297 @@ __global__ __launch_bounds__(256) void pack_layers_scan_kernel(Geom g, LayersWs 
   }
 }
 
+// ---- band: a stored stream restricted to a frequency band (and a window), stream to stream (svc_hip_band_levels_frames) ---------------
+//
+// Output frame i = input frame s with, of every tile inside window i, only the coefficients (row r, column c) of band i kept:
+//   r < hi_h && c < hi_w && !(r < lo_h && c < lo_w)
+// -- a plain predicate on u32, so a band is one 64-bit word per mask word of a tile (band_words) and a new mask word is the input's ANDed
+// with it.  The selection is inside a tile, so the passes have the split's shape: a wave owns a group, a lane walks each coefficient and
+// finds its level by rank.  Per output frame
+//   input    window_count_kernel and window_scan_kernel with no window: S per group and the input frame's status (unpack's code)
+//   count    one wave per group, a lane per mask word: the kept levels
+//   scan     one workgroup per frame: the kept levels' prefixes, the frame's level count and size
+//   offsets  frame_offsets_kernel
+//   write    one wave per group: the new mask words (a lane per word) and the kept levels, compacted in LDS and stored by store_level_run.
+//            The first workgroup of a frame also writes its header, types and padding.  Every output byte is stored once: two calls
+//            write the same bytes.
+
+struct BandWs {
+  WinWs in;                // the input pass: in.before = S, in.status = unpack's code
+  uint32_t* kept;          // [n][groups] kept levels, then their exclusive prefix
+  uint32_t *frame_bytes, *frame_levels;  // [n]
+};
+BandWs band_ws(Carver& c, uint32_t n, uint32_t groups) {
+  BandWs s;
+  s.in = window_ws(c, n, groups);
+  s.kept = c.take<uint32_t>((uint64_t)n * groups);
+  s.frame_bytes = c.take<uint32_t>(n);
+  s.frame_levels = c.take<uint32_t>(n);
+  return s;
+}
+
+struct BandArgs {
+  WindowArgs w;          // the window call's arguments; w.ws = the input pass's arrays
+  const uint32_t* band;  // [n_out][4] lo_w, lo_h, hi_w, hi_h, or null: every coefficient
+  uint32_t *kept, *frame_bytes, *frame_levels;
+};
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t k) {
+  return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, k) |
+         ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), k) << 32);
+}
+
+// lane l (< g.words; the others 0): the bits of a tile's mask word l whose coefficients band i keeps
+__device__ __forceinline__ uint64_t band_words(const Geom& g, const uint32_t* __restrict__ band, uint32_t i) {
+  const uint32_t lane = threadIdx.x & 63u, area = g.bw * g.bh;
+  const uint32_t lo_w = band ? band[4ull * i] : 0u, lo_h = band ? band[4ull * i + 1] : 0u;
+  const uint32_t hi_w = band ? band[4ull * i + 2] : 0xFFFFFFFFu, hi_h = band ? band[4ull * i + 3] : 0xFFFFFFFFu;
+  uint64_t mine = 0;
+  for (uint32_t wi = 0; wi < g.words; ++wi) {
+    const uint32_t k = wi * 64 + lane, r = k / g.bw, c = k - r * g.bw;
+    const uint64_t word = __ballot(k < area && r < hi_h && c < hi_w && !(r < lo_h && c < lo_w));
+    if (lane == wi) mine = word;
+  }
+  return mine;
+}
+
+// lane's view of mask word j of a group of output frame i: the band's bits of the word's place in its tile, 0 outside the window
+__device__ __forceinline__ uint64_t band_of_word(const BandArgs& a, uint32_t i, const Group& gr, uint32_t j, uint64_t words) {
+  const Geom& g = a.w.g;
+  const uint32_t t = j / g.words, wi = j - t * g.words;
+  const uint64_t b = __shfl(words, wi, 64);
+  return in_window(a.w.window, i, gr.x0 + t * g.bw, gr.y0) ? b : 0ull;
+}
+
+__global__ __launch_bounds__(256) void band_count_kernel(BandArgs a) {
+  const Geom& g = a.w.g;
+  const uint32_t lane = threadIdx.x & 63u, gi = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), i = blockIdx.y;
+  if (gi >= g.groups) return;  // (the whole wave)
+  uint32_t kept = 0;           // a frame that fails counts nothing: its masks are not read
+  if (a.w.ws.status[i] == kStOk) {
+    const Group gr = group_of(g, gi);
+    const uint8_t* frame = a.w.in + a.w.offsets[a.w.src ? a.w.src[i] : i];
+    const uint32_t* masks = group_masks(g, frame, gr.plane, gr);
+    const uint64_t words = band_words(g, a.band, i);
+    const uint32_t jobs = gr.nt * g.words;
+    for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {  // (the shuffle inside band_of_word is the whole wave's)
+      const uint32_t j = min(j0 + lane, jobs - 1);
+      const uint64_t b = band_of_word(a, i, gr, j, words);
+      if (j0 + lane < jobs) kept += (uint32_t)__popcll(load_mask(masks + 2 * j) & b);
+    }
+  }
+  kept = wave_sum(kept);
+  if (lane == 0) a.kept[(size_t)i * g.groups + gi] = kept;
+}
+
+__global__ __launch_bounds__(256) void band_scan_kernel(BandArgs a) {
+  __shared__ uint32_t red[kThreads / 64];
+  const Geom& g = a.w.g;
+  const uint32_t i = blockIdx.x;
+  uint32_t* kept = a.kept + (size_t)i * g.groups;
+  const uint32_t carry = scan_counts(kept, kept, g.groups, 0, red);
+  if (threadIdx.x == 0) {
+    a.frame_levels[i] = carry;
+    a.frame_bytes[i] = a.w.ws.status[i] == kStOk ? (uint32_t)up16(g.levels_off + 2ull * carry) : kHeaderBytes;
+  }
+}
+
+// The write passes of the band call and the union: kThreads / 64 waves, a group each, each wave's levels staged as u16 -- at most
+// the coefficients of a full group
+constexpr uint32_t select_write_lds(uint32_t cap) { return (kThreads / 64) * cap * (uint32_t)sizeof(uint16_t); }
+static_assert(select_write_lds(kGroupCoeffs) <= 32768 && select_write_lds(kMaxTileCoeffs) <= 32768,
+              "the band's and the union's write passes stage at most 32 KB per workgroup");
+
+// dynamic LDS: select_write_lds(cap), cap = the coefficients of a full group
+__global__ __launch_bounds__(256) void band_write_kernel(BandArgs a, uint32_t cap) {
+  extern __shared__ uint16_t stage[];
+  const Geom& g = a.w.g;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, gi = blockIdx.x * (kThreads / 64) + wave, i = blockIdx.y;
+  uint8_t* out = a.w.out + a.w.out_offsets[i];
+  if (a.w.ws.status[i] != kStOk) {  // 64 zero bytes; the input frame is not read
+    if (blockIdx.x == 0 && threadIdx.x < kHeaderWords) reinterpret_cast<uint32_t*>(out)[threadIdx.x] = 0;
+    return;
+  }
+  const uint8_t* frame = a.w.in + a.w.offsets[a.w.src ? a.w.src[i] : i];
+  const bool live = gi < g.groups;  // no early return: the barrier below is the workgroup's
+  uint16_t* buf = stage + (size_t)wave * cap;
+  uint32_t cnt = 0;
+  if (live) {
+    const Group gr = group_of(g, gi);
+    const uint32_t* masks = group_masks(g, frame, gr.plane, gr);
+    uint32_t* masks_out = group_masks(g, out, gr.plane, gr);
+    const uint16_t* lv = reinterpret_cast<const uint16_t*>(frame + g.levels_off) + a.w.ws.before[(size_t)i * g.groups + gi];
+    const uint64_t words = band_words(g, a.band, i);
+    const uint32_t jobs = gr.nt * g.words;
+    for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {
+      const uint32_t j = min(j0 + lane, jobs - 1), n = min(64u, jobs - j0);
+      const uint64_t b = band_of_word(a, i, gr, j, words);
+      const uint64_t m = j0 + lane < jobs ? load_mask(masks + 2 * j) : 0ull, keep = m & b;
+      if (j0 + lane < jobs) store_mask(masks_out + 2 * j, keep);
+      const uint32_t pc = (uint32_t)__popcll(m), first = wave_exclusive_scan(pc);
+      const uint32_t pk = (uint32_t)__popcll(keep), first_k = wave_exclusive_scan(pk);
+      for (uint32_t k = 0; k < n; ++k) {
+        const uint64_t kk = readlane64(keep, k);
+        if (kk == 0) continue;  // (the whole wave)
+        const uint64_t mk = readlane64(m, k);
+        const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)first, k), to = (uint32_t)__builtin_amdgcn_readlane((int)first_k, k);
+        if ((kk >> lane) & 1u) buf[cnt + to + lane_rank(kk)] = lv[at + lane_rank(mk)];
+      }
+      lv += (uint32_t)__builtin_amdgcn_readlane((int)(first + pc), 63);
+      cnt += (uint32_t)__builtin_amdgcn_readlane((int)(first_k + pk), 63);
+    }
+  }
+  __syncthreads();
+  if (live) store_level_run(buf, cnt, reinterpret_cast<uint16_t*>(out + g.levels_off) + a.kept[(size_t)i * g.groups + gi]);
+  if (blockIdx.x != 0) return;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(frame);
+  split_frame_edges(g, frame, out, src[kHFgStep], src[kHBgStep], a.frame_levels[i], a.frame_bytes[i]);
+}
+
+// ---- union: two streams of the same frames with disjoint masks -> one (svc_hip_union_levels_frames) -----------------------------------
+//
+// Output frame i has the masks of frame i of A ORed with those of frame i of B and the levels of both in coefficient order: a lane
+// per coefficient picks its level by rank in A's or B's mask word and puts it at its rank in the union's.  Header words 0 .. 9 and 11 and the
+// types are A's.  Per frame
+//   input    window_count_kernel and window_scan_kernel with no window on each stream: S per group and the frame's unpack code
+//   count    one wave per group, a lane per mask word: the union's levels, and whether a bit is set in both
+//   scan     one workgroup per frame: the prefixes, the final status (A's code, 0x100 | B's, 0x100 | kStLayer for other steps or types,
+//            kStOverlap), the frame's level count and size
+//   offsets  frame_offsets_kernel
+//   write    as the band's, with two inputs
+
+struct UnionWs {
+  WinWs a, b;                                     // the two input passes
+  uint32_t *cnt, *overlap;                        // [n][groups] the union's levels (then their prefix); words with a bit in both
+  uint32_t *frame_bytes, *frame_levels, *status;  // [n]
+};
+UnionWs union_ws(Carver& c, uint32_t n, uint32_t groups) {
+  UnionWs s;
+  s.a = window_ws(c, n, groups);
+  s.b = window_ws(c, n, groups);
+  s.cnt = c.take<uint32_t>((uint64_t)n * groups);
+  s.overlap = c.take<uint32_t>((uint64_t)n * groups);
+  s.frame_bytes = c.take<uint32_t>(n);
+  s.frame_levels = c.take<uint32_t>(n);
+  s.status = c.take<uint32_t>(n);
+  return s;
+}
+
+struct UnionArgs {
+  WindowArgs a, b;  // the two streams as the input pass takes them (no source indices, no window); a.out, a.out_offsets, a.d_status: the call's
+  uint32_t *cnt, *overlap, *frame_bytes, *frame_levels, *status;
+};
+
+__global__ __launch_bounds__(256) void union_count_kernel(UnionArgs u) {
+  const Geom& g = u.a.g;
+  const uint32_t lane = threadIdx.x & 63u, gi = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), i = blockIdx.y;
+  if (gi >= g.groups) return;  // (the whole wave)
+  uint32_t cnt = 0, both = 0;  // a pair with a frame that fails counts nothing: no masks are read
+  if (u.a.ws.status[i] == kStOk && u.b.ws.status[i] == kStOk) {
+    const Group gr = group_of(g, gi);
+    const uint32_t* ma = group_masks(g, u.a.in + u.a.offsets[i], gr.plane, gr);
+    const uint32_t* mb = group_masks(g, u.b.in + u.b.offsets[i], gr.plane, gr);
+    const uint32_t jobs = gr.nt * g.words;
+    for (uint32_t j = lane; j < jobs; j += 64) {
+      const uint64_t x = load_mask(ma + 2 * j), y = load_mask(mb + 2 * j);
+      cnt += (uint32_t)__popcll(x | y);
+      both += (x & y) != 0;
+    }
+  }
+  cnt = wave_sum(cnt);
+  both = wave_sum(both);
+  if (lane == 0) {
+    u.cnt[(size_t)i * g.groups + gi] = cnt;
+    u.overlap[(size_t)i * g.groups + gi] = both;
+  }
+}
+
+__global__ __launch_bounds__(256) void union_scan_kernel(UnionArgs u) {
+  __shared__ uint32_t red[kThreads / 64];
+  const Geom& g = u.a.g;
+  const uint32_t i = blockIdx.x;
+  uint32_t* cnt = u.cnt + (size_t)i * g.groups;
+  const uint32_t* overlap = u.overlap + (size_t)i * g.groups;
+  uint32_t both = 0, words_both, other = 0, words_other;  // summed on the scan's way
+  const uint32_t carry = scan_counts(g.groups, 0, red, [&](uint32_t k) { both += overlap[k]; return cnt[k]; },
+                                     [&](uint32_t k, uint32_t v) { cnt[k] = v; });
+  (void)block_exclusive_scan(both, red, &words_both);
+  const uint32_t sa = u.a.ws.status[i], sb = u.b.ws.status[i];
+  if (sa == kStOk && sb == kStOk) {  // (the whole workgroup) does B belong to A: the same steps and types?
+    const uint32_t* ha = reinterpret_cast<const uint32_t*>(u.a.in + u.a.offsets[i]);
+    const uint32_t* hb = reinterpret_cast<const uint32_t*>(u.b.in + u.b.offsets[i]);
+    if (threadIdx.x == 0) other = ha[kHFgStep] != hb[kHFgStep] || ha[kHBgStep] != hb[kHBgStep];
+    for (uint32_t k = threadIdx.x; k < g.mvb; k += kThreads) other += ha[kHeaderWords + k] != hb[kHeaderWords + k];
+  }
+  (void)block_exclusive_scan(other, red, &words_other);
+  if (threadIdx.x == 0) {
+    uint32_t st = sa;
+    if (st == kStOk && sb != kStOk) st = kStEnhancement | sb;
+    if (st == kStOk && words_other != 0) st = kStEnhancement | kStLayer;
+    if (st == kStOk && words_both != 0) st = kStOverlap;
+    u.status[i] = st;
+    u.a.d_status[i] = st;
+    u.frame_levels[i] = carry;
+    u.frame_bytes[i] = st == kStOk ? (uint32_t)up16(g.levels_off + 2ull * carry) : kHeaderBytes;
+  }
+}
+
+// dynamic LDS: select_write_lds(cap), cap = the coefficients of a full group
+__global__ __launch_bounds__(256) void union_write_kernel(UnionArgs u, uint32_t cap) {
+  extern __shared__ uint16_t stage[];
+  const Geom& g = u.a.g;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, gi = blockIdx.x * (kThreads / 64) + wave, i = blockIdx.y;
+  uint8_t* out = u.a.out + u.a.out_offsets[i];
+  if (u.status[i] != kStOk) {  // 64 zero bytes; the input frames are not read
+    if (blockIdx.x == 0 && threadIdx.x < kHeaderWords) reinterpret_cast<uint32_t*>(out)[threadIdx.x] = 0;
+    return;
+  }
+  const uint8_t* fa = u.a.in + u.a.offsets[i];
+  const uint8_t* fb = u.b.in + u.b.offsets[i];
+  const bool live = gi < g.groups;  // no early return: the barrier below is the workgroup's
+  uint16_t* buf = stage + (size_t)wave * cap;
+  uint32_t cnt = 0;
+  if (live) {
+    const Group gr = group_of(g, gi);
+    const uint32_t* masks_a = group_masks(g, fa, gr.plane, gr);
+    const uint32_t* masks_b = group_masks(g, fb, gr.plane, gr);
+    uint32_t* masks_out = group_masks(g, out, gr.plane, gr);
+    const uint16_t* la = reinterpret_cast<const uint16_t*>(fa + g.levels_off) + u.a.ws.before[(size_t)i * g.groups + gi];
+    const uint16_t* lb = reinterpret_cast<const uint16_t*>(fb + g.levels_off) + u.b.ws.before[(size_t)i * g.groups + gi];
+    const uint32_t jobs = gr.nt * g.words;
+    for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {
+      const uint32_t j = j0 + lane, n = min(64u, jobs - j0);
+      uint64_t x = 0, y = 0;
+      if (j < jobs) {
+        x = load_mask(masks_a + 2 * j);
+        y = load_mask(masks_b + 2 * j);
+        store_mask(masks_out + 2 * j, x | y);
+      }
+      const uint32_t px = (uint32_t)__popcll(x), py = (uint32_t)__popcll(y);  // (disjoint: the union's popcount is their sum)
+      const uint32_t first_x = wave_exclusive_scan(px), first_y = wave_exclusive_scan(py);
+      for (uint32_t k = 0; k < n; ++k) {
+        const uint64_t xk = readlane64(x, k), yk = readlane64(y, k);
+        if ((xk | yk) == 0) continue;  // (the whole wave)
+        const uint32_t ax = (uint32_t)__builtin_amdgcn_readlane((int)first_x, k), ay = (uint32_t)__builtin_amdgcn_readlane((int)first_y, k);
+        uint16_t v = 0;
+        if ((xk >> lane) & 1u) v = la[ax + lane_rank(xk)];
+        else if ((yk >> lane) & 1u) v = lb[ay + lane_rank(yk)];
+        if (((xk | yk) >> lane) & 1u) buf[cnt + ax + ay + lane_rank(xk | yk)] = v;
+      }
+      const uint32_t tx = (uint32_t)__builtin_amdgcn_readlane((int)(first_x + px), 63);
+      const uint32_t ty = (uint32_t)__builtin_amdgcn_readlane((int)(first_y + py), 63);
+      la += tx;
+      lb += ty;
+      cnt += tx + ty;
+    }
+  }
+  __syncthreads();
+  if (live) store_level_run(buf, cnt, reinterpret_cast<uint16_t*>(out + g.levels_off) + u.cnt[(size_t)i * g.groups + gi]);
+  if (blockIdx.x != 0) return;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(fa);
+  split_frame_edges(g, fa, out, src[kHFgStep], src[kHBgStep], u.frame_levels[i], u.frame_bytes[i]);
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -1872,6 +2167,107 @@ int svc_hip_window_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
   const uint32_t fixed = div_up((uint32_t)(up16(g.levels_off) / 16), kThreads), most = div_up((uint32_t)(max_bytes / 16), kThreads);
   hipLaunchKernelGGL(window_write_kernel, dim3(std::min(2 * fixed, most), n_out), dim3(kThreads), 0, s, a);
   return check_launch("window_levels", "write");
+}
+
+uint64_t svc_hip_band_levels_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                             uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("band_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("band_levels_workspace_bytes", n_out, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  return layout_bytes(band_ws, n_out, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups);
+}
+
+// Checked as svc_hip_window_levels_frames, in its order: geometry, limits, the d_src rule, workspace, output capacity; n_out == 0 then
+// returns SVC_OK; then pointers.
+int svc_hip_band_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_in,
+                               const uint32_t* d_src, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                               uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, const uint32_t* d_window, const uint32_t* d_band,
+                               uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                               uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("band_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (!rc) rc = validate_limits("band_levels", std::max(n_out, n_in), frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(d_src || n_out == n_in, "band_levels: without d_src output frame i is input frame i, but n_out is %u and n_in %u", n_out, n_in);
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if ((rc = require_workspace("band_levels", workspace_bytes, layout_bytes(band_ws, n_out, g.groups)))) return rc;
+  const uint64_t max_bytes = frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
+  if ((rc = require_capacity("band_levels", "output", out_capacity, n_out * max_bytes))) return rc;
+  if (n_out == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_out && d_out_offsets && d_status, "band_levels: null pointer");
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_out_offsets, 8) && aligned(d_src, 4) && aligned(d_window, 4) && aligned(d_band, 4) && aligned(d_status, 4),
+              "band_levels: streams and workspace must be 16-byte aligned, offsets 8-byte, source indices, windows, bands and status 4-byte");
+  const BandWs ws = carve(d_workspace, band_ws, n_out, g.groups);
+  const BandArgs a{{g, d_frames, stream_bytes, d_frame_offsets, n_in, d_src, d_window, d_out, d_out_offsets, d_status, ws.in},
+                   d_band, ws.kept, ws.frame_bytes, ws.frame_levels};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 waves(div_up(g.groups, kThreads / 64), n_out);
+  // the input pass: the window call's count and scan with every tile kept
+  WindowArgs in = a.w;
+  in.window = nullptr;
+  hipLaunchKernelGGL(window_count_kernel, waves, dim3(kThreads), 0, s, in);
+  if ((rc = check_launch("band_levels", "input count"))) return rc;
+  hipLaunchKernelGGL(window_scan_kernel, dim3(n_out), dim3(kThreads), 0, s, in);
+  if ((rc = check_launch("band_levels", "input scan"))) return rc;
+  hipLaunchKernelGGL(band_count_kernel, waves, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("band_levels", "count"))) return rc;
+  hipLaunchKernelGGL(band_scan_kernel, dim3(n_out), dim3(kThreads), 0, s, a);
+  if ((rc = check_launch("band_levels", "scan"))) return rc;
+  if ((rc = enqueue_frame_offsets("band_levels", 1, OffsetsJob{ws.frame_bytes, d_out_offsets, nullptr}, OffsetsJob{}, n_out, stream))) return rc;
+  const uint32_t cap = g.tpg * g.bw * g.bh;
+  hipLaunchKernelGGL(band_write_kernel, waves, dim3(kThreads), select_write_lds(cap), s, a, cap);
+  return check_launch("band_levels", "write");
+}
+
+uint64_t svc_hip_union_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                              uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("union_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("union_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  return layout_bytes(union_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups);
+}
+
+// Checked in the window call's order: geometry, limits, workspace, output capacity; n_frames == 0 then returns SVC_OK; then pointers.
+int svc_hip_union_levels_frames(const uint8_t* d_a, uint64_t a_bytes, const uint64_t* d_a_offsets, const uint8_t* d_b, uint64_t b_bytes,
+                                const uint64_t* d_b_offsets, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint8_t* d_workspace, uint64_t workspace_bytes,
+                                uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_geom("union_levels", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (!rc) rc = validate_limits("union_levels", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if ((rc = require_workspace("union_levels", workspace_bytes, layout_bytes(union_ws, n_frames, g.groups)))) return rc;
+  const uint64_t max_bytes = frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes;
+  if ((rc = require_capacity("union_levels", "output", out_capacity, n_frames * max_bytes))) return rc;
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_a && d_a_offsets && d_b && d_b_offsets && d_workspace && d_out && d_out_offsets && d_status, "union_levels: null pointer");
+  SVC_REQUIRE(aligned(d_a, 16) && aligned(d_b, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_a_offsets, 8) &&
+                  aligned(d_b_offsets, 8) && aligned(d_out_offsets, 8) && aligned(d_status, 4),
+              "union_levels: streams and workspace must be 16-byte aligned, offsets 8-byte, status 4-byte");
+  const UnionWs ws = carve(d_workspace, union_ws, n_frames, g.groups);
+  const UnionArgs u{{g, d_a, a_bytes, d_a_offsets, n_frames, nullptr, nullptr, d_out, d_out_offsets, d_status, ws.a},
+                    {g, d_b, b_bytes, d_b_offsets, n_frames, nullptr, nullptr, nullptr, nullptr, d_status, ws.b},
+                    ws.cnt, ws.overlap, ws.frame_bytes, ws.frame_levels, ws.status};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 waves(div_up(g.groups, kThreads / 64), n_frames);
+  // the input pass of each stream: the window call's count and scan with every tile kept (d_status holds A's, then B's codes until the
+  // scan below writes the pair's)
+  for (const WindowArgs* in : {&u.a, &u.b}) {
+    const char* which = in == &u.a ? "input count" : "second input count";
+    hipLaunchKernelGGL(window_count_kernel, waves, dim3(kThreads), 0, s, *in);
+    if ((rc = check_launch("union_levels", which))) return rc;
+    hipLaunchKernelGGL(window_scan_kernel, dim3(n_frames), dim3(kThreads), 0, s, *in);
+    if ((rc = check_launch("union_levels", "input scan"))) return rc;
+  }
+  hipLaunchKernelGGL(union_count_kernel, waves, dim3(kThreads), 0, s, u);
+  if ((rc = check_launch("union_levels", "count"))) return rc;
+  hipLaunchKernelGGL(union_scan_kernel, dim3(n_frames), dim3(kThreads), 0, s, u);
+  if ((rc = check_launch("union_levels", "scan"))) return rc;
+  if ((rc = enqueue_frame_offsets("union_levels", 1, OffsetsJob{ws.frame_bytes, d_out_offsets, nullptr}, OffsetsJob{}, n_frames, stream)))
+    return rc;
+  const uint32_t cap = g.tpg * g.bw * g.bh;
+  hipLaunchKernelGGL(union_write_kernel, waves, dim3(kThreads), select_write_lds(cap), s, u, cap);
+  return check_launch("union_levels", "write");
 }
 
 uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,

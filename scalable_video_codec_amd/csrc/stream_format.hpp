@@ -30,10 +30,11 @@ enum : uint32_t {
 };
 
 // per-frame status of the unpack / decode (1 .. 7, also the entropy encoder's view of its SVCQ input) and of the entropy decoder; the
-// two-layer decode reports its enhancement frame's code as kStEnhancement | code, 11 for one that does not belong to its base frame
+// two-layer decode reports its enhancement frame's code as kStEnhancement | code, 11 for one that does not belong to its base frame; the
+// union reports its second stream's frame the same way, and 12 for a pair whose masks share a bit
 enum : uint32_t {
   kStOk = 0, kStRange = 1, kStMagic = 2, kStVersion = 3, kStGeometry = 4, kStSize = 5, kStLevels = 6, kStStrayBits = 7,
-  kStIndex = 8, kStChunk = 9, kStSvcqBytes = 10, kStLayer = 11, kStEnhancement = 0x100
+  kStIndex = 8, kStChunk = 9, kStSvcqBytes = 10, kStLayer = 11, kStOverlap = 12, kStEnhancement = 0x100
 };
 
 constexpr uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }  // constexpr: host and device

@@ -11,6 +11,9 @@ decoder dequantises (Lb * ratio + d) * enh_step, elsewhere Lb * sb.
 
 window_frame / window_frames state svc_hip_window_levels_frames: a stored frame restricted to the tiles of a window, on its masks.
 
+band_frame / band_frames state svc_hip_band_levels_frames: a stored frame restricted to a frequency band of every tile (and a window), on
+its masks; union_frame / union_frames state svc_hip_union_levels_frames, which joins such parts back.
+
 split_frame / split_frames / split_budget_frames state svc_hip_split_levels_frames and its budgeted form: the stream stored at
 (fine_step, fine_step) alone determines a base frame at any multiples of fine_step and the enhancement frame that lifts it back, in
 integers on the levels' values:
@@ -149,16 +152,20 @@ def merge_levels(base_frame, enh_frame, gaze: Optional[Sequence[int]] = None) ->
 
 # ---- a stored stream restricted to a window (include/svc_hip.h: svc_hip_window_levels_frames) -----------------------------------------
 
-def _window_frame(frame, window) -> Tuple[bytes, Dict[str, int]]:
+def _sections(frame):
+    """A frame levels.parse_frame accepts -> (u8 view, header dict, types, mask bytes (3, ty, tx, nw * 8), levels i16 in stream order)."""
     b = np.frombuffer(frame, np.uint8) if not isinstance(frame, np.ndarray) else frame.reshape(-1).view(np.uint8)
     hdr, types, _ = levels.parse_frame(b)  # raises for a frame the reader rejects: the masks and the level count below are sound
     tx, ty = hdr["frame_w"] // hdr["block_w"], hdr["frame_h"] // hdr["block_h"]
     nw = (hdr["block_w"] * hdr["block_h"] + 63) // 64
     masks_off = levels.HEADER_BYTES + 4 * types.size
     levels_off = masks_off + 8 * 3 * ty * tx * nw
-    masks = b[masks_off:levels_off].reshape(3, ty, tx, nw * 8)
-    lv = b[levels_off:levels_off + 2 * hdr["level_count"]].view("<i2")
-    keep = np.ones((ty, tx), bool)
+    return b, hdr, types, b[masks_off:levels_off].reshape(3, ty, tx, nw * 8), b[levels_off:levels_off + 2 * hdr["level_count"]].view("<i2")
+
+
+def _window_frame(frame, window) -> Tuple[bytes, Dict[str, int]]:
+    b, hdr, types, masks, lv = _sections(frame)
+    keep = np.ones(masks.shape[1:3], bool)
     if window is not None:
         _, ox, oy = _tile_maps(hdr, types)
         keep = _contains(window, ox, oy)
@@ -199,6 +206,80 @@ def window_frames(stream, offsets, windows, src=None) -> Tuple[bytes, np.ndarray
         frames.append(out)
     out_offs = np.concatenate([[0], np.cumsum([len(fr) for fr in frames])]).astype(np.uint64)
     return b"".join(frames), out_offs
+
+
+# ---- a stored stream restricted to a frequency band, and bands joined back (include/svc_hip.h: svc_hip_band_levels_frames,
+# svc_hip_union_levels_frames) ------------------------------------------------------------------------------------------------------------
+
+def _band_bits(hdr: Dict[str, int], band) -> np.ndarray:
+    """(nw * 64,) bool: the coefficients of a tile, in mask-bit order, that the band lo_w, lo_h, hi_w, hi_h (or None: all) keeps."""
+    bw, bh = hdr["block_w"], hdr["block_h"]
+    lo_w, lo_h, hi_w, hi_h = (0, 0, bw, bh) if band is None else (int(v) for v in band)
+    r, c = np.arange(bh)[:, None], np.arange(bw)[None, :]
+    keep = (r < hi_h) & (c < hi_w) & ~((r < lo_h) & (c < lo_w))
+    bits = np.zeros((bw * bh + 63) // 64 * 64, bool)
+    bits[:bw * bh] = keep.reshape(-1)
+    return bits
+
+
+def band_frame(frame, band, window=None) -> bytes:
+    """One SVCQ frame restricted to a frequency band and a window: coefficient (row r, column c) of a tile is kept iff the window (x, y,
+    w, h in padded coordinates, or None: every tile) contains the tile's origin and
+        r < hi_h and c < hi_w and not (r < lo_h and c < lo_w)
+    for band = (lo_w, lo_h, hi_w, hi_h) (None: every coefficient; a hi above the tile side means the side).  Header words 0 .. 9 and 11
+    and the types as they are, every mask word ANDed with the band's bits (zero outside the window), the kept levels in the frame's order,
+    word 10 their number, word 12 the new size, zero padding.  Stated on the masks, as window_frame is: a set bit whose level is 0 stays
+    set.  band_frame(f, None, window) == window_frame(f, window); the bands (0, 0, K1, K1), (K1, K1, K2, K2), (K2, K2, bw, bh) partition
+    a tile.  Raises ValueError for a frame levels.parse_frame rejects."""
+    b, hdr, types, masks, lv = _sections(frame)
+    keep = np.ones(masks.shape[1:3], bool)
+    if window is not None:
+        _, ox, oy = _tile_maps(hdr, types)
+        keep = _contains(window, ox, oy)
+    bits = np.unpackbits(masks, axis=-1, bitorder="little").astype(bool)  # the levels follow the set bits in this (C) order
+    kept_bits = bits & keep[None, :, :, None] & _band_bits(hdr, band)[None, None, None, :]
+    return _assemble(b[:40].view("<u4"), hdr["inexact"], types, np.packbits(kept_bits, axis=-1, bitorder="little"), lv[kept_bits[bits]])
+
+
+def band_frames(stream, offsets, bands, windows=None, src=None) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_band_levels_frames writes for frames that pass their checks -> (bytes, offsets (n_out + 1,) u64): output frame i is
+    band_frame of input frame src[i] (src None: frame i), bands[i] and windows[i]; bands: None (every coefficient) or per output frame
+    lo_w, lo_h, hi_w, hi_h (n_out, 4); windows, src as window_frames takes them."""
+    frames = _source_frames(stream, offsets, src)
+    band = None if bands is None else np.asarray(bands).reshape(len(frames), 4)
+    win = None if windows is None else np.asarray(windows).reshape(len(frames), 4)
+    return _join([band_frame(fr, None if band is None else band[i], None if win is None else win[i]) for i, fr in enumerate(frames)])
+
+
+def union_frame(a, b) -> bytes:
+    """Two frames of one geometry, the same steps and types and disjoint masks -> the frame whose masks are theirs ORed and whose levels
+    are both frames' in coefficient order; header words 0 .. 9 and 11 and the types are a's.  The bands of a partition of a frame, joined
+    in any order, give the frame back.  Raises ValueError for a frame levels.parse_frame rejects, for a pair that does not belong together
+    (the device's status 0x100 | 11) and for masks that share a bit (status 12)."""
+    ba, ha, types, ma, la = _sections(a)
+    _, hb, types_b, mb, lb = _sections(b)
+    if any(ha[k] != hb[k] for k in GEOMETRY):
+        raise ValueError("the two frames differ in geometry")
+    if (ha["fg_step"], ha["bg_step"]) != (hb["fg_step"], hb["bg_step"]) or not np.array_equal(types, types_b):
+        raise ValueError("the two frames differ in steps or region ids: they are not parts of one frame")
+    bits_a = np.unpackbits(ma, axis=-1, bitorder="little").astype(bool)
+    bits_b = np.unpackbits(mb, axis=-1, bitorder="little").astype(bool)
+    if (bits_a & bits_b).any():
+        raise ValueError("the two frames' masks overlap")
+    vals = np.zeros(bits_a.shape, np.int16)
+    vals[bits_a] = la
+    vals[bits_b] = lb
+    both = bits_a | bits_b
+    return _assemble(ba[:40].view("<u4"), ha["inexact"], types, ma | mb, vals[both])
+
+
+def union_frames(a, a_offsets, b, b_offsets) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_union_levels_frames writes for pairs that pass their checks -> (bytes, offsets (n + 1,) u64): frame i is union_frame
+    of frame i of each stream."""
+    fa, fb = _source_frames(a, a_offsets, None), _source_frames(b, b_offsets, None)
+    if len(fa) != len(fb):
+        raise ValueError("the two streams hold different numbers of frames")
+    return _join([union_frame(x, y) for x, y in zip(fa, fb)])
 
 
 # ---- a stored fine stream split into a base at any steps and its enhancement (include/svc_hip.h: svc_hip_split_levels_frames) ---------

@@ -157,6 +157,12 @@ SIGNATURES = {
     # a stored SVCQ stream restricted to a window per output frame (csrc/levels.hip; host statement: layers.window_frames)
     "svc_hip_window_levels_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_window_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    # a stored SVCQ stream restricted to a frequency band (and a window) per output frame, and two such streams joined back (csrc/levels.hip;
+    # host statements: layers.band_frames, layers.union_frames)
+    "svc_hip_band_levels_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_band_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "svc_hip_union_levels_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_union_levels_frames": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     # a stored SVCE stream restricted to a window per output frame, on its coded bytes (csrc/entropy.hip; host statement: entropy.window_frames)
     "svc_hip_window_entropy_max_bytes": (_u64, [_u32] * 7),
     "svc_hip_window_entropy_workspace_bytes": (_u64, [_u32] * 7),
@@ -1210,6 +1216,77 @@ def window_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h:
                                                None if win is None else _dev(win, torch.int32), _dev(workspace, torch.uint8),
                                                workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
                                                _dev(status, torch.int32), _stream()))
+    return out, out_offsets, status
+
+
+def band_levels_workspace_bytes(n_out: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of band_levels_frames for n_out output frames; 0 for a geometry it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_band_levels_workspace_bytes(n_out, w, h, bw, bh, mbw, mbh))
+
+
+def band_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, band=None, window=None, src=None,
+                       out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """An SVCQ stream (u8 on the device) + its offsets, restricted to a frequency band and a window per output frame (include/svc_hip.h;
+    the numpy statement is layers.band_frames): output frame i is input frame src[i] (src None: frame i) with, of the tiles whose origin
+    window[i] contains, only the coefficients (row r, column c) with r < hi_h, c < hi_w and not (r < lo_h and c < lo_w).  band: None (every
+    coefficient), or per output frame lo_w, lo_h, hi_w, hi_h ((n_out, 4) ints, a tensor or a list); window, src, the buffers and the
+    result as window_levels_frames takes and gives them.  `out` must not overlap `frames`."""
+    n_in = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    s = None if src is None else torch.as_tensor(src, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    n_out = n_in if s is None else s.numel()
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n_out, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(band_levels_workspace_bytes(n_out, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(max(n_out, 1), dtype=torch.int32, device=dev)[:n_out]
+    win, bnd = _rects(window, n_out, dev), _rects(band, n_out, dev)
+    _check(load().svc_hip_band_levels_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n_in,
+                                             None if s is None else _dev(s, torch.int32), n_out, w, h, bw, bh, mbw, mbh,
+                                             None if win is None else _dev(win, torch.int32), None if bnd is None else _dev(bnd, torch.int32),
+                                             _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
+                                             _dev(out_offsets, torch.int64), _dev(status, torch.int32), _stream()))
+    return out, out_offsets, status
+
+
+def union_levels_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of union_levels_frames for n frames; 0 for a geometry it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_union_levels_workspace_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def union_levels_frames(a: torch.Tensor, a_offsets: torch.Tensor, b: torch.Tensor, b_offsets: torch.Tensor, w: int, h: int, block, mv_block,
+                        out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                        workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Two SVCQ streams of the same number of frames whose masks are disjoint, such as two bands of one stream, joined frame by frame
+    (include/svc_hip.h; the numpy statement is layers.union_frames): the masks ORed, the levels of both in coefficient order, the header
+    and types of `a`.  -> (stream u8 of the worst-case size, offsets (n + 1,) i64, status (n,) i32: a's unpack code, else 0x100 | b's,
+    else 0x100 | 11 for other steps or types, else 12 for masks that share a bit; a frame that fails is 64 zero bytes).  `out` must not
+    overlap `a` or `b`."""
+    n = a_offsets.numel() - 1
+    assert b_offsets.numel() == n + 1, "the two streams hold different numbers of frames"
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = a.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(union_levels_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    _check(load().svc_hip_union_levels_frames(_dev(a, torch.uint8), a.numel(), _dev(a_offsets, torch.int64), _dev(b, torch.uint8), b.numel(),
+                                              _dev(b_offsets, torch.int64), n, w, h, bw, bh, mbw, mbh, _dev(workspace, torch.uint8),
+                                              workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
+                                              _dev(status, torch.int32), _stream()))
     return out, out_offsets, status
 
 

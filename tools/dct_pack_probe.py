@@ -36,6 +36,16 @@
                                                    enhancement (the call it sits beside); wall time per call over 20 back-to-back calls, the
                                                    bytes each call reads and writes and their fraction of the HBM peak, and the split's base
                                                    against the encoder's base at (1, 640) (an even ratio: they differ)
+  python tools/dct_pack_probe.py band [C3|C5] [frames]
+                                                   a stored stream served by frequency band, the same batch of 16 stored at (1, 640) and at
+                                                   (1, 1): (a) bytes per frame of the bands (0, 0, K, K), K = N / 2, N / 4, N / 8, and of their
+                                                   remainders, raw and entropy-coded, beside the stored stream's; (b) svc_hip_band_levels_frames
+                                                   against svc_hip_window_levels_frames with no window and svc_hip_split_levels_frames on the
+                                                   same stream; (c) svc_hip_union_levels_frames of a band and its remainder against the same
+                                                   two, its bytes compared with the stored stream's; (d) 4 viewers at four K (n_out = 64 through
+                                                   d_src) against four calls; wall time per call over 20 back-to-back calls; (e) `frames`
+                                                   (default 64) frames at (1, 640) as SVCE through tests/dropin/stream_reduced_main at reduce 2,
+                                                   4, 8: the band stream against the full stream, alternating, every run printed
   python tools/dct_pack_probe.py window-entropy [C3|C5]
                                                    a stored entropy-coded enhancement served under a gaze, the same batch of 16 at
                                                    (1, 640, 1) with a 256 x 256 window per frame: svc_hip_window_entropy_frames on the stored
@@ -534,6 +544,149 @@ def split(cfg) -> None:
           f"{int(woo[-1]) / n / 1e6:.3f} MB per frame", flush=True)
 
 
+def band(cfg, frames_n=64) -> None:
+    import subprocess
+    import tempfile
+
+    import numpy as np
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    masks = 8 * 3 * (pw // block) * (ph // block) * (block * block // 64)  # the mask section of a frame
+    ks = [block // r for r in (2, 4, 8)]
+
+    def fmt(t):
+        return f"{t[0]:.3f} .. {t[1]:.3f}"
+
+    def coded_bytes(stream, offs):
+        _, eo, st = native.entropy_encode_frames(stream, offs, pw, ph, block, mv)
+        sync()
+        assert not st.any()
+        return int(eo[-1])
+
+    def band_of(stream, offs, rows, src=None):
+        out, oo, st = native.band_levels_frames(stream, offs, pw, ph, block, mv, band=rows, src=src)
+        sync()
+        assert not st.any()
+        return out[:int(oo[-1])].clone(), oo.clone()
+
+    stored = {}
+    for steps in ((1, 640), (1, 1)):
+        out, offs = native.dct_pack_levels_frames(bgr, block, types, mv, *steps)
+        sync()
+        stored[steps] = (out[:int(offs[-1])].clone(), offs.clone())
+    # (a) bytes per frame
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}; the mask section is {masks / 1e6:.3f} MB of every frame, whatever the band", flush=True)
+    for steps, (stream, offs) in stored.items():
+        print(f"(a) stored at {steps}: {stream.numel() / n / 1e6:.4f} MB per frame, entropy-coded {coded_bytes(stream, offs) / n / 1e6:.4f} MB", flush=True)
+        for k in ks:
+            for name, row in ((f"band (0, 0, {k}, {k})", (0, 0, k, k)), (f"remainder ({k}, {k}, {block}, {block})", (k, k, block, block))):
+                b, bo = band_of(stream, offs, [row] * n)
+                print(f"      {name}: {b.numel() / n / 1e6:.4f} MB per frame, entropy-coded {coded_bytes(b, bo) / n / 1e6:.4f} MB", flush=True)
+    # (b), (c) the calls' time on the stream stored at (1, 1), which the split takes too; then the band call on the stream at (1, 640)
+    outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(3)]
+    oo = [torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(3)]
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    ws_w = torch.empty(native.window_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_s = torch.empty(native.split_levels_workspace_bytes(n, n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_b = torch.empty(native.band_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_u = torch.empty(native.union_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    for steps in ((1, 1), (1, 640)):
+        stream, offs = stored[steps]
+        print(f"(b) the stream stored at {steps} ({stream.numel() / n / 1e6:.3f} MB per frame), ms per call of {n} frames (best .. worst of 3 "
+              f"runs of 20 back-to-back calls)", flush=True)
+
+        def f_window():
+            return native.window_levels_frames(stream, offs, pw, ph, block, mv, out=outs[0], out_offsets=oo[0], workspace=ws_w, status=st)
+
+        def f_split():
+            return native.split_levels_frames(stream, offs, pw, ph, block, mv, 1, 1, 640, base_out=outs[1], base_offsets=oo[1], enh_out=outs[2],
+                                              enh_offsets=oo[2], workspace=ws_s, status=st)
+        t_win = _per_step(f_window, sync, steps=20)
+        print(f"    svc_hip_window_levels_frames, no window {fmt(t_win)}", flush=True)
+        if steps == (1, 1):
+            t_split = _per_step(f_split, sync, steps=20)
+            assert not st.any()
+            print(f"    svc_hip_split_levels_frames to (1, 640), every tile enhanced {fmt(t_split)}", flush=True)
+        for k in ks + [block]:
+            rows = torch.tensor([(0, 0, k, k)] * n, dtype=torch.int32, device=dev)
+
+            def call():
+                return native.band_levels_frames(stream, offs, pw, ph, block, mv, band=rows, out=outs[0], out_offsets=oo[0], workspace=ws_b, status=st)
+            t = _per_step(call, sync, steps=20)
+            assert not st.any()
+            print(f"    svc_hip_band_levels_frames (0, 0, {k}, {k}) {fmt(t)} ({t[0] / t_win[0]:.2f}x the window call"
+                  + (f", {t[0] / t_split[0]:.2f}x the split" if steps == (1, 1) else "") + f"), {int(oo[0][-1]) / n / 1e6:.3f} MB per frame out", flush=True)
+        t_win2 = _per_step(f_window, sync, steps=20)  # the window call again, after: the spread of the same call in this run
+        print(f"    svc_hip_window_levels_frames again {fmt(t_win2)}", flush=True)
+        k = ks[0]
+        low, lo = band_of(stream, offs, [(0, 0, k, k)] * n)
+        high, ho = band_of(stream, offs, [(k, k, block, block)] * n)
+
+        def f_union():
+            return native.union_levels_frames(low, lo, high, ho, pw, ph, block, mv, out=outs[0], out_offsets=oo[0], workspace=ws_u, status=st)
+        t_u = _per_step(f_union, sync, steps=20)
+        assert not st.any() and torch.equal(oo[0], offs) and torch.equal(outs[0][:stream.numel()], stream), "the union is not the stored stream"
+        print(f"(c) svc_hip_union_levels_frames of (0, 0, {k}, {k}) and its remainder {fmt(t_u)} ({t_u[0] / t_win[0]:.2f}x the window call"
+              + (f", {t_u[0] / t_split[0]:.2f}x the split" if steps == (1, 1) else "") + "); the bytes are the stored stream's", flush=True)
+    # (d) one call for 4 viewers at four K against four calls
+    stream, offs = stored[(1, 640)]
+    four = ks[::-1] + [block]
+    src = torch.arange(n, dtype=torch.int32, device=dev).repeat(4)
+    rows64 = torch.tensor([(0, 0, k, k) for k in four for _ in range(n)], dtype=torch.int32, device=dev)
+    rows16 = [torch.tensor([(0, 0, k, k)] * n, dtype=torch.int32, device=dev) for k in four]
+    out64 = torch.empty(4 * cap, dtype=torch.uint8, device=dev)
+    oo64, st64 = torch.empty(4 * n + 1, dtype=torch.int64, device=dev), torch.empty(4 * n, dtype=torch.int32, device=dev)
+    ws64 = torch.empty(native.band_levels_workspace_bytes(4 * n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+
+    def one_call():
+        return native.band_levels_frames(stream, offs, pw, ph, block, mv, band=rows64, src=src, out=out64, out_offsets=oo64, workspace=ws64, status=st64)
+
+    def four_calls():
+        for rows in rows16:
+            native.band_levels_frames(stream, offs, pw, ph, block, mv, band=rows, out=outs[0], out_offsets=oo[0], workspace=ws_b, status=st)
+    t1, t4 = _per_step(one_call, sync, steps=20), _per_step(four_calls, sync, steps=20)
+    t1b = _per_step(one_call, sync, steps=20)
+    assert not st64.any()
+    print(f"(d) 4 viewers at K = {four} from the stream at (1, 640): one call with n_out = {4 * n} {fmt(t1)} (again {fmt(t1b)}), four calls {fmt(t4)}",
+          flush=True)
+    # (e) through svc::StreamDecoder on SVCE input: the band stream against the full stream, PCIe included
+    here = os.path.join(ROOT, "tests", "dropin")
+    bgr, types = _batch(cfg, frames_n)
+    out, offs = native.dct_pack_levels_frames(bgr, block, types, mv, 1, 640)
+    sync()
+    full = (out[:int(offs[-1])].clone(), offs.clone())
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        def store(name, stream, so):
+            coded, eo, est = native.entropy_encode_frames(stream, so, pw, ph, block, mv)
+            sync()
+            assert not est.any()
+            coded[:int(eo[-1])].cpu().numpy().tofile(os.path.join(d, name + ".big"))
+            eo.cpu().numpy().astype(np.uint64).tofile(os.path.join(d, name + ".offsets"))
+            return int(eo[-1])
+        print(f"(e) {frames_n} frames at (1, 640) as SVCE through tests/dropin/stream_reduced_main, batch 16, display (W / r, H / r), no gaze; full "
+              f"stream {store('full', *full) / frames_n / 1e6:.4f} MB per frame coded", flush=True)
+        for r in (2, 4, 8):
+            k = block // r
+            coded = store(f"band{r}", *band_of(*full, [(0, 0, k, k)] * frames_n))
+            print(f"    reduce {r}: band (0, 0, {k}, {k}) {coded / frames_n / 1e6:.4f} MB per frame coded", flush=True)
+            for turn in range(3):  # alternating, every run printed: the spread is part of the result
+                for name in ("full", f"band{r}"):
+                    p = subprocess.run([os.path.join(here, "stream_reduced_main"), os.path.join(d, name), str(frames_n), str(r), "0", "0", "-", "16",
+                                        "-"], capture_output=True, text=True, timeout=300)
+                    lines = p.stdout.strip().splitlines() or [p.stderr.strip()]
+                    print(f"      {name}, run {turn} (exit {p.returncode}): {lines[0]}", flush=True)
+                    if turn == 0 and len(lines) > 1:  # where the time went, once per stream
+                        print(f"        {lines[1]}", flush=True)
+                    if p.returncode != 0:
+                        sys.exit(1)
+
+
 def pack_layers(cfg) -> None:
     dev = torch.device("cuda")
     n = 16
@@ -675,6 +828,8 @@ if __name__ == "__main__":
         window_entropy(_cfg(sys.argv, 2))
     elif mode == "split":
         split(_cfg(sys.argv, 2))
+    elif mode == "band":
+        band(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 64)
     elif mode == "stream-layers":
         stream_layers()
     elif mode == "pack-layers":
