@@ -447,8 +447,8 @@ int svc_hip_pack_levels_frames(const float* d_planes, const uint32_t* d_block_ty
  * 0 ok, 1 offsets out of range, 2 magic, 3 version, 4 geometry or a step of 0, 5 frame size,
  * 6 level count != the masks' popcount, 7 mask bits set past block_w * block_h.  A frame that
  * fails is written as zeros.  (The codes of other calls: 8 .. 10 the entropy decoder's, 11 and
- * 0x100 | code those of the calls that take two streams, 12 svc_hip_union_levels_frames' for two
- * frames whose masks share a bit.) */
+ * 0x100 | code those of the calls that take two streams or a frame and its predecessor, 12
+ * svc_hip_union_levels_frames' for two frames whose masks share a bit.) */
 int svc_hip_unpack_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
                                  const uint64_t* d_frame_offsets, uint32_t n_frames,
                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
@@ -1167,6 +1167,84 @@ int svc_hip_union_levels_frames(const uint8_t* d_a, uint64_t a_bytes, const uint
                                 uint8_t* d_out, uint64_t out_capacity,
                                 uint64_t* d_out_offsets /* [n_frames + 1] */,
                                 uint32_t* d_status /* [n_frames] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * A stored SVCQ stream cut by time: every frame coded against the frame before it, in levels, and
+ * the inverse.  scalable_video_codec_amd/layers.py (delta_frame, delta_frames, undelta_frame,
+ * undelta_frames) is the numpy statement.
+ *
+ * For a frame F, L_F is the int16 level of every coefficient (0 where the mask bit is clear; a set
+ * bit whose level is 0 reads as 0) and step_F(tile) is header word 9 where the MV block holding the
+ * tile's origin has type 0, else word 8.  Frame i is a KEY frame if it has no predecessor or
+ * d_key[i] != 0 (d_key NULL: no flag is set).  The predecessor of frame 0 is the one frame at d_prev
+ * (NULL: none, frame 0 is a key frame); the predecessor of frame i > 0 is, in the delta call, INPUT
+ * frame i - 1 and, in the undelta call, OUTPUT frame i - 1.  d_prev is therefore the last input frame
+ * of the delta call before, or the last output frame of the undelta call before: a stream cut into
+ * two calls at any frame gives the bytes of one call.
+ *
+ * A tile is predicted iff the frame is not a key frame and step_cur(tile) == step_prev(tile).
+ *   delta     D = L_cur - (L_prev in a predicted tile, else 0)      modulo 2^16, as int16
+ *   undelta   L = D + (L_prev_rec in a predicted tile, else 0)      modulo 2^16, as int16
+ * Nothing overflows and no frame is refused for its values.  Both outputs are SVCQ frames:
+ *   header   words 0 .. 9 and 11 copied from the input frame, word 10 = the non-zero results, word
+ *            12 = up16(levels offset + 2 * word 10), words 13 .. 15 zero
+ *   types    copied
+ *   masks    a bit is set iff the result is not 0
+ *   levels   the non-zero results, in coefficient order
+ *   padding  zero, to 16 bytes
+ * Since header and types are copied, the undelta call finds the predicted tiles from the delta
+ * stream alone; the key flags travel beside the stream, as d_choice does.  A delta frame is not
+ * marked: the caller knows what the stream holds, as it does for an enhancement stream.
+ *
+ * Consequences:
+ *   - undelta(delta(s)) is s byte for byte for every stream without set bits of level 0 (every
+ *     stream the packers write); such bits come back cleared;
+ *   - the window call and the band call, applied with one window or band to all frames, commute
+ *     with the delta call: a server may store the delta stream and window it;
+ *   - every output is an SVCQ frame: the drains, the entropy coder and the host reader take it.
+ *
+ * d_status [n_frames] u32: frame i's own code of svc_hip_unpack_levels_frames if it is not 0; else,
+ * for a frame that is not a key frame and whose predecessor's status s is not 0, 0x100 | (s & 0xFF).
+ * The predecessor's status is, in the delta call, the input frame's own code (d_prev: checked as a
+ * frame occupying [0, prev_bytes)); in the undelta call it is the output frame's status, so a
+ * failure runs down the chain to the next key frame.  A frame that fails is 64 zero bytes and leaves
+ * the frames not chained to it as they would be.  Every read stays inside its input; nothing is
+ * written past d_out_offsets[n_frames]; two calls write the same bytes.
+ *
+ * Checked in the window call's order: geometry (any the SVCQ pack takes), limits, workspace,
+ * out_capacity against svc_hip_levels_max_bytes(n_frames, ...); n_frames == 0 then returns SVC_OK;
+ * then pointers (streams, d_prev and workspace 16-byte aligned, offsets 8-byte, d_status and d_key
+ * 4-byte).  The queries return 0 where the calls refuse.  d_out must not overlap d_frames or d_prev:
+ * this is NOT checked.  Only enqueues work; the number of launches does not depend on n_frames.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_delta_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                              uint32_t block_w, uint32_t block_h,
+                                              uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                const uint8_t* d_prev /* one SVCQ frame, the predecessor of frame 0; NULL: frame 0 is a key frame */,
+                                uint64_t prev_bytes,
+                                const uint32_t* d_key /* [n_frames], != 0: key frame; NULL: none but frame 0 without d_prev */,
+                                uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                uint32_t mv_block_w, uint32_t mv_block_h,
+                                uint8_t* d_workspace, uint64_t workspace_bytes,
+                                uint8_t* d_out, uint64_t out_capacity,
+                                uint64_t* d_out_offsets /* [n_frames + 1] */,
+                                uint32_t* d_status /* [n_frames] */, void* stream);
+uint64_t svc_hip_undelta_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                uint32_t block_w, uint32_t block_h,
+                                                uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_undelta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                  const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                  const uint8_t* d_prev /* one reconstructed SVCQ frame, the predecessor of frame 0; NULL: frame 0 is a key frame */,
+                                  uint64_t prev_bytes,
+                                  const uint32_t* d_key /* [n_frames], as the delta call took it */,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                  uint32_t mv_block_w, uint32_t mv_block_h,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes,
+                                  uint8_t* d_out, uint64_t out_capacity,
+                                  uint64_t* d_out_offsets /* [n_frames + 1] */,
+                                  uint32_t* d_status /* [n_frames] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes

@@ -40,6 +40,10 @@
 // (and a window), and two streams with disjoint masks joined back -- the window call's count and scan for each input, then count, scan,
 // frame offsets and a write pass of the split's shape (stated at their kernels).
 //
+// delta and undelta (svc_hip_delta_levels_frames, svc_hip_undelta_levels_frames): frames coded against their predecessors as differences
+// of levels, and added back up -- the window call's count and scan for the input, then count, scan, frame offsets and write; the undelta's
+// waves each carry one group through all frames of the call (stated at their kernels).
+//
 // pack of two layers (svc_hip_pack_layers_frames): the pack's count, scan and scatter on raw planes with two quantisations per coefficient,
 // the frame offsets from frame_offsets_kernel with a job per layer (stated at its kernels).
 #include "budget_core.hpp"
@@ -1702,6 +1706,273 @@ __global__ __launch_bounds__(256) void union_write_kernel(UnionArgs u, uint32_t 
   split_frame_edges(g, fa, out, src[kHFgStep], src[kHBgStep], u.frame_levels[i], u.frame_bytes[i]);
 }
 
+// ---- delta and undelta: frames coded against their predecessors in levels, and back (svc_hip_delta_levels_frames,
+// svc_hip_undelta_levels_frames; include/svc_hip.h states them) ---------------------------------------------------------------------------
+//
+// D = L_cur - L_prev and L = D + L_prev_rec, modulo 2^16, in the tiles both frames code at one step (the others and key frames: D = L_cur),
+// a mask bit set iff the result is not 0.  Header and types are copied, so both directions find the predicted tiles in their input stream.
+// Both calls share
+//   input    window_count_kernel and window_scan_kernel with no window on the stream and on the one frame at d_prev (as a stream of one
+//            frame whose offsets delta_prev_kernel writes): S per group and each frame's unpack code
+//   status   one wave: every frame's final status -- its own code, else 0x100 | its predecessor's; in the undelta call the predecessor is
+//            an output frame, so the wave scans the chain (a frame with a code of its own or a key flag sets the state, any other passes it on)
+//   scan     band_scan_kernel on the counts below: the prefixes, the frame's level count and size
+//   offsets  frame_offsets_kernel
+// The delta call's count and write are delta_kernel, a wave per (group, frame) as the union's: a lane per coefficient picks both levels by
+// rank; the count reads the levels too, since it must know which differences are 0.
+// The undelta call's are undelta_kernel: frame i needs output frame i - 1, so a wave owns one group through ALL frames of the call and the
+// grid does not depend on their number.  It keeps the group's reconstructed levels dense in LDS ([tile][coefficient] u16, at most 4096)
+// with their mask words, walks the frames in order and adds each frame's run of levels (found at the input pass's S) into them; a key frame
+// and a tile whose step changed start from 0.  A word with no difference and no level held is skipped.  The write walk compacts each
+// frame's non-zero levels in LDS and stores them with store_level_run; the first workgroup also writes every frame's header, types and
+// padding.  Every output byte is stored once: two calls write the same bytes.
+
+struct DeltaWs {
+  WinWs in, prev;          // the input passes of the stream and of d_prev
+  uint64_t* prev_offsets;  // [2] 0, prev_bytes
+  uint32_t* prev_code;     // [1] d_prev's unpack code, as its input pass reports it
+  uint32_t* cnt;           // [n][groups] non-zero results, then their exclusive prefix
+  uint32_t *frame_bytes, *frame_levels, *status;  // [n]
+};
+DeltaWs delta_ws(Carver& c, uint32_t n, uint32_t groups) {
+  DeltaWs s;
+  s.in = window_ws(c, n, groups);
+  const uint32_t one = n ? 1 : 0;  // an empty batch needs no workspace
+  s.prev = window_ws(c, one, groups);
+  s.prev_offsets = c.take<uint64_t>(2 * one);
+  s.prev_code = c.take<uint32_t>(one);
+  s.cnt = c.take<uint32_t>((uint64_t)n * groups);
+  s.frame_bytes = c.take<uint32_t>(n);
+  s.frame_levels = c.take<uint32_t>(n);
+  s.status = c.take<uint32_t>(n);
+  return s;
+}
+
+struct DeltaArgs {
+  WindowArgs in;    // the stream as the input pass takes it; in.out, in.out_offsets, in.d_status: the call's
+  WindowArgs prev;  // d_prev as a stream of one frame; prev.in null: none
+  const uint32_t* key;  // [n] or null
+  uint32_t n;
+  uint32_t *cnt, *frame_bytes, *frame_levels, *status;
+};
+
+__global__ void delta_prev_kernel(uint64_t* offsets, uint64_t prev_bytes) {
+  offsets[0] = 0;
+  offsets[1] = prev_bytes;
+}
+
+__device__ __forceinline__ bool delta_key(const DeltaArgs& a, uint32_t i) {
+  return (i == 0 && !a.prev.in) || (a.key && a.key[i] != 0);
+}
+
+// the input frame before frame i: d_prev for frame 0.  Only for a frame that is not a key frame
+__device__ __forceinline__ const uint8_t* delta_before(const DeltaArgs& a, uint32_t i) {
+  return i == 0 ? a.prev.in : a.in.in + a.in.offsets[i - 1];
+}
+
+// the step of the group's tile t in `frame`: the rule of svc_hip_dct_quant_frames on the frame's own header and types
+__device__ __forceinline__ uint32_t tile_step(const Geom& g, const uint8_t* frame, const Group& gr, uint32_t t) {
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(frame);
+  return tile_type(g, h + kHeaderWords, gr, t) == 0 ? h[kHBgStep] : h[kHFgStep];
+}
+
+// One wave.  e = the low byte of a frame's final status, the state the next frame inherits unless it is a key frame or has a code of its
+// own.  CHAIN (undelta): e runs from frame to frame -- an inclusive scan in which a frame that sets the state overrides what came before it.
+// Without CHAIN (delta) the predecessor is an input frame: its own code.
+template <bool CHAIN>
+__global__ __launch_bounds__(64) void delta_status_kernel(DeltaArgs a) {
+  const uint32_t lane = threadIdx.x;
+  uint32_t carry = a.prev.in ? a.prev.ws.status[0] & 0xFFu : 0u;  // of the frame before `base`
+  for (uint32_t base = 0; base < a.n; base += 64) {
+    const uint32_t i = base + lane;
+    const bool live = i < a.n;
+    const uint32_t own = live ? a.in.ws.status[i] : 0u;
+    const bool key = live && delta_key(a, i);
+    uint32_t e;
+    if (CHAIN) {
+      uint32_t sets = own != 0 || key, val = own & 0xFFu;
+      for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint32_t s2 = __shfl_up(sets, off, 64), v2 = __shfl_up(val, off, 64);
+        if (lane >= off && !sets) sets = s2, val = v2;
+      }
+      e = sets ? val : carry;
+      carry = __shfl(e, 63, 64);
+    } else {
+      const uint32_t before = i == 0 ? carry : (live ? a.in.ws.status[i - 1] & 0xFFu : 0u);
+      e = own != 0 ? own & 0xFFu : (key ? 0u : before);
+    }
+    if (live) {
+      const uint32_t st = own != 0 ? own : (e != 0 ? kStEnhancement | e : (uint32_t)kStOk);
+      a.status[i] = st;
+      a.in.d_status[i] = st;
+    }
+  }
+}
+
+// WRITE = false: the group's non-zero differences (0 for a frame that fails).  WRITE = true: its mask words and levels and, from the first
+// workgroup of a frame, header, types and padding; dynamic LDS: select_write_lds(cap), cap = the coefficients of a full group
+template <bool WRITE>
+__global__ __launch_bounds__(256) void delta_kernel(DeltaArgs a, uint32_t cap) {
+  extern __shared__ uint16_t stage[];
+  const Geom& g = a.in.g;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, gi = blockIdx.x * (kThreads / 64) + wave, i = blockIdx.y;
+  const bool live = gi < g.groups;  // no early return: the barrier below is the workgroup's
+  uint8_t* out = WRITE ? a.in.out + a.in.out_offsets[i] : nullptr;
+  if (a.status[i] != kStOk) {  // 64 zero bytes; no frame is read
+    if (WRITE) {
+      if (blockIdx.x == 0 && threadIdx.x < kHeaderWords) reinterpret_cast<uint32_t*>(out)[threadIdx.x] = 0;
+    } else if (live && lane == 0) {
+      a.cnt[(size_t)i * g.groups + gi] = 0;
+    }
+    return;
+  }
+  const uint8_t* fc = a.in.in + a.in.offsets[i];
+  uint16_t* buf = stage + (size_t)wave * cap;
+  uint32_t cnt = 0;
+  if (live) {
+    const Group gr = group_of(g, gi);
+    const uint8_t* fp = delta_key(a, i) ? nullptr : delta_before(a, i);  // (its own status is 0: this frame's would not be)
+    const uint32_t* masks_c = group_masks(g, fc, gr.plane, gr);
+    const uint32_t* masks_p = fp ? group_masks(g, fp, gr.plane, gr) : nullptr;
+    uint32_t* masks_out = WRITE ? group_masks(g, out, gr.plane, gr) : nullptr;
+    const uint16_t* lc = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + a.in.ws.before[(size_t)i * g.groups + gi];
+    const uint16_t* lp = nullptr;
+    if (fp) lp = reinterpret_cast<const uint16_t*>(fp + g.levels_off) + (i == 0 ? a.prev.ws.before[gi] : a.in.ws.before[(size_t)(i - 1) * g.groups + gi]);
+    const uint32_t jobs = gr.nt * g.words;
+    for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {
+      const uint32_t j = j0 + lane, n = min(64u, jobs - j0);
+      uint64_t x = 0, y = 0;
+      bool predicted = false;
+      if (j < jobs) {
+        x = load_mask(masks_c + 2 * j);
+        if (fp) {
+          const uint32_t t = j / g.words;
+          y = load_mask(masks_p + 2 * j);
+          predicted = tile_step(g, fc, gr, t) == tile_step(g, fp, gr, t);
+        }
+      }
+      const uint32_t px = (uint32_t)__popcll(x), py = (uint32_t)__popcll(y);
+      const uint32_t first_x = wave_exclusive_scan(px), first_y = wave_exclusive_scan(py);
+      const uint64_t yp = predicted ? y : 0ull;  // the predecessor's levels of any other tile are passed over
+      uint64_t keep = 0;                         // lane l: the new mask of word j0 + l
+      for (uint32_t k = 0; k < n; ++k) {
+        const uint64_t xk = readlane64(x, k), yk = readlane64(yp, k);
+        if ((xk | yk) == 0) continue;  // (the whole wave)
+        const uint32_t ax = (uint32_t)__builtin_amdgcn_readlane((int)first_x, k), ay = (uint32_t)__builtin_amdgcn_readlane((int)first_y, k);
+        const uint16_t c = (xk >> lane) & 1u ? lc[ax + lane_rank(xk)] : (uint16_t)0;
+        const uint16_t p = (yk >> lane) & 1u ? lp[ay + lane_rank(yk)] : (uint16_t)0;
+        const uint16_t d = (uint16_t)(c - p);
+        const uint64_t mk = __ballot(d != 0);
+        if (WRITE) {
+          if (d != 0) buf[cnt + lane_rank(mk)] = d;
+          if (lane == k) keep = mk;
+        }
+        cnt += (uint32_t)__popcll(mk);
+      }
+      if (WRITE && j < jobs) store_mask(masks_out + 2 * j, keep);
+      lc += (uint32_t)__builtin_amdgcn_readlane((int)(first_x + px), 63);
+      if (fp) lp += (uint32_t)__builtin_amdgcn_readlane((int)(first_y + py), 63);
+    }
+  }
+  if (!WRITE) {
+    if (live && lane == 0) a.cnt[(size_t)i * g.groups + gi] = cnt;
+    return;
+  }
+  __syncthreads();
+  if (live) store_level_run(buf, cnt, reinterpret_cast<uint16_t*>(out + g.levels_off) + a.cnt[(size_t)i * g.groups + gi]);
+  if (blockIdx.x != 0) return;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(fc);
+  split_frame_edges(g, fc, out, src[kHFgStep], src[kHBgStep], a.frame_levels[i], a.frame_bytes[i]);
+}
+
+// WRITE = false: every frame's count of the group's non-zero levels.  WRITE = true: their mask words and levels and, from the first
+// workgroup, every frame's header, types and padding.  blockDim.x / 64 waves, a group each through all frames; waves per workgroup and
+// dynamic LDS are the split's write pass's (split_write_waves, split_write_lds(cap), cap = the coefficients of a full group): per wave the
+// group's coefficients as u16, twice -- the levels held, and the frame's non-zero ones in order; the held levels' mask words are static
+template <bool WRITE>
+__global__ __launch_bounds__(256) void undelta_kernel(DeltaArgs a, uint32_t cap) {
+  extern __shared__ uint16_t stage[];
+  __shared__ uint64_t held_masks[kThreads / 64][kMaxJobs];
+  const Geom& g = a.in.g;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, gi = blockIdx.x * (blockDim.x >> 6) + wave;
+  const bool live = gi < g.groups;  // no early return: the barriers below are the workgroup's
+  const Group gr = group_of(g, live ? gi : 0u);
+  const uint32_t jobs = gr.nt * g.words, area = g.bw * g.bh;
+  uint16_t* held = stage + (size_t)wave * 2 * cap;  // [tile][coefficient]: != 0 exactly where its bit of held_mask is set
+  uint16_t* buf = held + cap;
+  uint64_t* held_mask = held_masks[wave];
+  for (uint32_t k = lane; k < cap; k += 64) held[k] = 0;
+  for (uint32_t j = lane; j < jobs; j += 64) held_mask[j] = 0;
+  // frame -1 is d_prev: it is added like a key frame and nothing is written for it.  Every condition on a frame is the workgroup's.
+  for (int32_t i = a.prev.in && a.prev.ws.status[0] == kStOk ? -1 : 0; i < (int32_t)a.n; ++i) {
+    const bool seed = i < 0;
+    uint8_t* out = WRITE && !seed ? a.in.out + a.in.out_offsets[i] : nullptr;
+    if (!seed && a.status[i] != kStOk) {  // 64 zero bytes; the frame is not read, and the next frame that passes is a key frame
+      if (WRITE) {
+        if (blockIdx.x == 0 && threadIdx.x < kHeaderWords) reinterpret_cast<uint32_t*>(out)[threadIdx.x] = 0;
+      } else if (live && lane == 0) {
+        a.cnt[(size_t)i * g.groups + gi] = 0;
+      }
+      continue;
+    }
+    const uint8_t* fc = seed ? a.prev.in : a.in.in + a.in.offsets[i];
+    uint32_t cnt = 0;
+    if (live) {
+      const uint8_t* fp = seed || delta_key(a, (uint32_t)i) ? nullptr : delta_before(a, (uint32_t)i);
+      const uint32_t* masks_c = group_masks(g, fc, gr.plane, gr);
+      uint32_t* masks_out = out ? group_masks(g, out, gr.plane, gr) : nullptr;
+      const uint16_t* lc = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + (seed ? a.prev.ws.before[gi] : a.in.ws.before[(size_t)i * g.groups + gi]);
+      for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {
+        const uint32_t j = j0 + lane, n = min(64u, jobs - j0);
+        uint64_t x = 0, was = 0;
+        uint32_t slot0 = 0;  // of the word's first coefficient
+        bool predicted = false;
+        if (j < jobs) {
+          const uint32_t t = j / g.words;
+          x = load_mask(masks_c + 2 * j);
+          was = held_mask[j];
+          slot0 = t * area + (j - t * g.words) * 64;
+          if (fp) predicted = tile_step(g, fc, gr, t) == tile_step(g, fp, gr, t);
+        }
+        const uint32_t px = (uint32_t)__popcll(x), first_x = wave_exclusive_scan(px);
+        const uint64_t predicted_words = __ballot(predicted);
+        uint64_t keep = 0;  // lane l: the new mask of word j0 + l
+        for (uint32_t k = 0; k < n; ++k) {
+          const uint64_t xk = readlane64(x, k), wk = readlane64(was, k);
+          if ((xk | wk) == 0) continue;  // (the whole wave) nothing to add and nothing held: the word stays 0
+          const uint32_t ax = (uint32_t)__builtin_amdgcn_readlane((int)first_x, k);
+          const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)slot0, k) + lane;
+          const uint16_t d = (xk >> lane) & 1u ? lc[ax + lane_rank(xk)] : (uint16_t)0;
+          const uint16_t p = ((predicted_words >> k) & 1u) && ((wk >> lane) & 1u) ? held[slot] : (uint16_t)0;
+          const uint16_t lv = (uint16_t)(d + p);
+          if (((xk | wk) >> lane) & 1u) held[slot] = lv;  // (no bit is set past the tile's area: such a frame fails)
+          const uint64_t mk = __ballot(lv != 0);
+          if (lane == k) keep = mk;
+          if (WRITE && out && lv != 0) buf[cnt + lane_rank(mk)] = lv;
+          cnt += (uint32_t)__popcll(mk);
+        }
+        if (j < jobs) {
+          held_mask[j] = keep;
+          if (masks_out) store_mask(masks_out + 2 * j, keep);
+        }
+        lc += (uint32_t)__builtin_amdgcn_readlane((int)(first_x + px), 63);
+      }
+    }
+    if (seed) continue;
+    if (!WRITE) {
+      if (live && lane == 0) a.cnt[(size_t)i * g.groups + gi] = cnt;
+      continue;
+    }
+    __syncthreads();
+    if (live) store_level_run(buf, cnt, reinterpret_cast<uint16_t*>(out + g.levels_off) + a.cnt[(size_t)i * g.groups + gi]);
+    if (blockIdx.x == 0) {
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(fc);
+      split_frame_edges(g, fc, out, src[kHFgStep], src[kHBgStep], a.frame_levels[i], a.frame_bytes[i]);
+    }
+    __syncthreads();  // the next frame's levels go to buf again
+  }
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -1808,6 +2079,63 @@ int split_levels(const char* what, SplitArgs a, const svc_step_pair* ladder, uin
   // a wave stages its group's levels of both layers in LDS: two waves per workgroup where a group is a tile above 2048 coefficients
   const uint32_t cap = g.tpg * g.bw * g.bh, wpb = split_write_waves(cap);
   hipLaunchKernelGGL(split_write_kernel, dim3(div_up(g.groups, wpb), a.n_out), dim3(64 * wpb), split_write_lds(cap), s, a, cap);
+  return check_launch(what, "write");
+}
+
+// Both directions of the delta, checked in the window call's order: geometry, limits, workspace, output capacity; n_frames == 0 then
+// returns SVC_OK; then pointers.  Ten launches, whatever n_frames (seven without d_prev).
+int delta_levels(const char* what, bool undo, const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n,
+                 const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh,
+                 uint32_t mvbw, uint32_t mvbh, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                 uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
+  int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (!rc) rc = validate_limits(what, n, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  const Geom g = make_geom(w, h, bw, bh, mvbw, mvbh);
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(delta_ws, n, g.groups)))) return rc;
+  const uint64_t max_bytes = frame_layout(w, h, bw, bh, mvbw, mvbh).max_bytes;
+  if ((rc = require_capacity(what, "output", out_capacity, n * max_bytes))) return rc;
+  if (n == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_out && d_out_offsets && d_status, "%s: null pointer", what);
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_prev, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_out_offsets, 8) && aligned(d_key, 4) && aligned(d_status, 4),
+              "%s: streams, the frame before and workspace must be 16-byte aligned, offsets 8-byte, key flags and status 4-byte", what);
+  const DeltaWs ws = carve(d_workspace, delta_ws, n, g.groups);
+  const DeltaArgs a{{g, d_frames, stream_bytes, d_frame_offsets, n, nullptr, nullptr, d_out, d_out_offsets, d_status, ws.in},
+                    {g, d_prev, prev_bytes, ws.prev_offsets, 1, nullptr, nullptr, nullptr, nullptr, ws.prev_code, ws.prev},
+                    d_key, n, ws.cnt, ws.frame_bytes, ws.frame_levels, ws.status};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint32_t wave_blocks = div_up(g.groups, kThreads / 64);
+  // the input pass of the stream and of the frame before it: the window call's count and scan with every tile kept (d_status holds the
+  // frames' own codes until the status kernel writes the final ones)
+  if (d_prev) {
+    hipLaunchKernelGGL(delta_prev_kernel, dim3(1), dim3(1), 0, s, ws.prev_offsets, prev_bytes);
+    if ((rc = check_launch(what, "offsets of the frame before"))) return rc;
+  }
+  for (const WindowArgs* in : {&a.prev, &a.in}) {
+    if (!in->in) continue;
+    hipLaunchKernelGGL(window_count_kernel, dim3(wave_blocks, in->n_in), dim3(kThreads), 0, s, *in);
+    if ((rc = check_launch(what, in == &a.in ? "input count" : "input count of the frame before"))) return rc;
+    hipLaunchKernelGGL(window_scan_kernel, dim3(in->n_in), dim3(kThreads), 0, s, *in);
+    if ((rc = check_launch(what, "input scan"))) return rc;
+  }
+  if (undo) hipLaunchKernelGGL(delta_status_kernel<true>, dim3(1), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(delta_status_kernel<false>, dim3(1), dim3(64), 0, s, a);
+  if ((rc = check_launch(what, "status"))) return rc;
+  // the scan of the band call on this call's counts and final statuses
+  WindowArgs counted = a.in;
+  counted.ws.status = ws.status;
+  const BandArgs scan{counted, nullptr, ws.cnt, ws.frame_bytes, ws.frame_levels};
+  const uint32_t cap = g.tpg * g.bw * g.bh, wpb = split_write_waves(cap);
+  const dim3 chains(div_up(g.groups, wpb)), pairs(wave_blocks, n);
+  if (undo) hipLaunchKernelGGL(undelta_kernel<false>, chains, dim3(64 * wpb), split_write_lds(cap), s, a, cap);
+  else hipLaunchKernelGGL(delta_kernel<false>, pairs, dim3(kThreads), 0, s, a, cap);
+  if ((rc = check_launch(what, "count"))) return rc;
+  hipLaunchKernelGGL(band_scan_kernel, dim3(n), dim3(kThreads), 0, s, scan);
+  if ((rc = check_launch(what, "scan"))) return rc;
+  if ((rc = enqueue_frame_offsets(what, 1, OffsetsJob{ws.frame_bytes, d_out_offsets, nullptr}, OffsetsJob{}, n, stream))) return rc;
+  if (undo) hipLaunchKernelGGL(undelta_kernel<true>, chains, dim3(64 * wpb), split_write_lds(cap), s, a, cap);
+  else hipLaunchKernelGGL(delta_kernel<true>, pairs, dim3(kThreads), select_write_lds(cap), s, a, cap);
   return check_launch(what, "write");
 }
 
@@ -2268,6 +2596,41 @@ int svc_hip_union_levels_frames(const uint8_t* d_a, uint64_t a_bytes, const uint
   const uint32_t cap = g.tpg * g.bw * g.bh;
   hipLaunchKernelGGL(union_write_kernel, waves, dim3(kThreads), select_write_lds(cap), s, u, cap);
   return check_launch("union_levels", "write");
+}
+
+uint64_t svc_hip_delta_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                              uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("delta_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("delta_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  return layout_bytes(delta_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups);
+}
+
+int svc_hip_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t frame_w, uint32_t frame_h,
+                                uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint8_t* d_workspace,
+                                uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status,
+                                void* stream) {
+  return delta_levels("delta_levels", false, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w, frame_h,
+                      block_w, block_h, mv_block_w, mv_block_h, d_workspace, workspace_bytes, d_out, out_capacity, d_out_offsets, d_status, stream);
+}
+
+// (the two directions share one workspace layout)
+uint64_t svc_hip_undelta_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                                uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("undelta_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("undelta_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  return layout_bytes(delta_ws, n_frames, make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).groups);
+}
+
+int svc_hip_undelta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                  const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t frame_w, uint32_t frame_h,
+                                  uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint8_t* d_workspace,
+                                  uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status,
+                                  void* stream) {
+  return delta_levels("undelta_levels", true, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w, frame_h,
+                      block_w, block_h, mv_block_w, mv_block_h, d_workspace, workspace_bytes, d_out, out_capacity, d_out_offsets, d_status, stream);
 }
 
 uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,

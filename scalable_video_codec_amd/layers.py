@@ -14,6 +14,9 @@ window_frame / window_frames state svc_hip_window_levels_frames: a stored frame 
 band_frame / band_frames state svc_hip_band_levels_frames: a stored frame restricted to a frequency band of every tile (and a window), on
 its masks; union_frame / union_frames state svc_hip_union_levels_frames, which joins such parts back.
 
+delta_frame / delta_frames state svc_hip_delta_levels_frames: a frame coded against the frame before it, as the difference of their levels
+in the tiles both code at one step; undelta_frame / undelta_frames state svc_hip_undelta_levels_frames, which adds the frames back up.
+
 split_frame / split_frames / split_budget_frames state svc_hip_split_levels_frames and its budgeted form: the stream stored at
 (fine_step, fine_step) alone determines a base frame at any multiples of fine_step and the enhancement frame that lifts it back, in
 integers on the levels' values:
@@ -280,6 +283,82 @@ def union_frames(a, a_offsets, b, b_offsets) -> Tuple[bytes, np.ndarray]:
     if len(fa) != len(fb):
         raise ValueError("the two streams hold different numbers of frames")
     return _join([union_frame(x, y) for x, y in zip(fa, fb)])
+
+
+# ---- frames coded against their predecessors in levels, and back (include/svc_hip.h: svc_hip_delta_levels_frames,
+# svc_hip_undelta_levels_frames) ------------------------------------------------------------------------------------------------------------
+
+def _dense(frame):
+    """_sections with the levels at their coefficients -> (u8 view, header dict, types, levels (3, ty, tx, nw * 64) i16, step of each tile
+    (ty, tx) i64).  A level is 0 where the mask bit is clear; a set bit whose level is 0 reads as 0."""
+    b, hdr, types, masks, lv = _sections(frame)
+    bits = np.unpackbits(masks, axis=-1, bitorder="little").astype(bool)  # the levels follow the set bits in this (C) order
+    vals = np.zeros(bits.shape, np.int16)
+    vals[bits] = lv
+    background, _, _ = _tile_maps(hdr, types)
+    return b, hdr, types, vals, np.where(background, hdr["bg_step"], hdr["fg_step"]).astype(np.int64)
+
+
+def _chained(cur, prev, sign: int) -> bytes:
+    """cur's levels plus sign * prev's in the tiles both frames code at one step, modulo 2^16, as an SVCQ frame with cur's header words
+    0 .. 9 and 11 and types; prev None: cur's levels."""
+    b, hdr, types, vals, step = _dense(cur)
+    if prev is not None:
+        _, hp, _, pvals, pstep = _dense(prev)
+        if any(hdr[k] != hp[k] for k in GEOMETRY):
+            raise ValueError("the frame and its predecessor differ in geometry")
+        predicted = (step == pstep)[None, :, :, None]
+        vals = (vals.astype(np.int64) + sign * np.where(predicted, pvals, 0)).astype(np.uint16).view(np.int16)  # two's complement wrap-around
+    nz = vals != 0
+    return _assemble(b[:40].view("<u4"), hdr["inexact"], types, np.packbits(nz, axis=-1, bitorder="little"), vals[nz])
+
+
+def delta_frame(cur, prev=None) -> bytes:
+    """One SVCQ frame coded against its predecessor, in levels.  With L_F the int16 level of every coefficient of frame F (0 where the
+    mask bit is clear; a set bit whose level is 0 reads as 0) and step_F(tile) F's bg_step where the MV block holding the tile's origin
+    has type 0, else its fg_step, a tile is predicted iff prev is given and step_cur(tile) == step_prev(tile), and
+        D = L_cur - (L_prev in a predicted tile, else 0)     modulo 2^16, as int16
+    Nothing overflows and no frame is refused for its values.  The result is again an SVCQ frame: header words 0 .. 9 and 11 and the types
+    are cur's, a mask bit is set iff D != 0, the levels are D in coefficient order, word 10 their number, word 12 the size, words 13 .. 15
+    and the padding zero.  Nothing in it says that it holds differences: the caller knows, as for an enhancement frame.  prev None: a key
+    frame, D = L_cur.  window_frame and band_frame, applied with one window or band to cur and prev, commute with delta_frame.  Raises
+    ValueError for a frame levels.parse_frame rejects and for two frames of different geometry."""
+    return _chained(cur, prev, -1)
+
+
+def undelta_frame(diff, prev_rec=None) -> bytes:
+    """delta_frame undone: L = D + (L_prev_rec in a predicted tile, else 0), modulo 2^16, written the same way (a mask bit set iff
+    L != 0).  Which tiles are predicted follows from diff's header and types and prev_rec's, which are cur's and prev's because both calls
+    copy them: undelta_frame(delta_frame(cur, prev), prev) is cur with the set bits of level 0 cleared, byte for byte cur for a frame
+    without such bits -- every frame the packers and write_frame write.  prev_rec None: a key frame."""
+    return _chained(diff, prev_rec, +1)
+
+
+def _keys(keys, n: int):
+    return np.zeros(n, bool) if keys is None else np.asarray(keys).reshape(n) != 0
+
+
+def delta_frames(stream, offsets, keys=None, prev=None) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_delta_levels_frames writes for frames that pass their checks -> (bytes, offsets (n + 1,) u64): frame i is a key
+    frame if it has no predecessor or keys[i] != 0 (keys None: no flag is set); otherwise it is delta_frame of input frame i and its
+    predecessor, input frame i - 1, for frame 0 the frame `prev` (None: frame 0 is a key frame).  A stream cut into two calls at any
+    frame, the second with prev = the first's last input frame, gives the bytes of one call."""
+    frames = _source_frames(stream, offsets, None)
+    key = _keys(keys, len(frames))
+    return _join([delta_frame(fr, None if key[i] else (frames[i - 1] if i else prev)) for i, fr in enumerate(frames)])
+
+
+def undelta_frames(stream, offsets, keys=None, prev=None) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_undelta_levels_frames writes for frames that pass their checks -> (bytes, offsets (n + 1,) u64): delta_frames undone
+    with the same keys.  The predecessor of frame i is OUTPUT frame i - 1, for frame 0 the reconstructed frame `prev`:
+    undelta_frames(*delta_frames(s, o, keys), keys) gives s back for a stream without set bits of level 0.  A stream cut into two calls,
+    the second with prev = the first's last output frame, gives the bytes of one call."""
+    frames = _source_frames(stream, offsets, None)
+    key = _keys(keys, len(frames))
+    out = []
+    for i, fr in enumerate(frames):
+        out.append(undelta_frame(fr, None if key[i] else (out[i - 1] if i else prev)))
+    return _join(out)
 
 
 # ---- a stored fine stream split into a base at any steps and its enhancement (include/svc_hip.h: svc_hip_split_levels_frames) ---------

@@ -163,6 +163,12 @@ SIGNATURES = {
     "svc_hip_band_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "svc_hip_union_levels_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_union_levels_frames": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    # an SVCQ stream coded frame against frame in levels, and back (csrc/levels.hip; host statements: layers.delta_frames,
+    # layers.undelta_frames)
+    "svc_hip_delta_levels_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_delta_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 6 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "svc_hip_undelta_levels_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_undelta_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 6 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     # a stored SVCE stream restricted to a window per output frame, on its coded bytes (csrc/entropy.hip; host statement: entropy.window_frames)
     "svc_hip_window_entropy_max_bytes": (_u64, [_u32] * 7),
     "svc_hip_window_entropy_workspace_bytes": (_u64, [_u32] * 7),
@@ -1288,6 +1294,63 @@ def union_levels_frames(a: torch.Tensor, a_offsets: torch.Tensor, b: torch.Tenso
                                               workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
                                               _dev(status, torch.int32), _stream()))
     return out, out_offsets, status
+
+
+def delta_levels_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of delta_levels_frames for n frames; 0 for a geometry it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_delta_levels_workspace_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def undelta_levels_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of undelta_levels_frames for n frames; 0 for a geometry it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_undelta_levels_workspace_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def _delta_call(undo: bool, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status):
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    k = None if key is None else torch.as_tensor(key, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    assert k is None or k.numel() == n, "one key flag per frame"
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        query = undelta_levels_workspace_bytes if undo else delta_levels_workspace_bytes
+        workspace = torch.empty(max(query(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    fn = load().svc_hip_undelta_levels_frames if undo else load().svc_hip_delta_levels_frames
+    _check(fn(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, None if prev is None else _dev(prev, torch.uint8),
+              0 if prev is None else prev.numel(), None if k is None else _dev(k, torch.int32), w, h, bw, bh, mbw, mbh,
+              _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
+              _dev(status, torch.int32), _stream()))
+    return out, out_offsets, status
+
+
+def delta_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, prev: Optional[torch.Tensor] = None,
+                        key=None, out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                        workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """An SVCQ stream (u8 on the device) + its offsets, every frame coded against the frame before it (include/svc_hip.h; the numpy
+    statement is layers.delta_frames): in the tiles both frames code at one step the levels' difference modulo 2^16, elsewhere and in a key
+    frame the levels.  prev: None (frame 0 is a key frame) or the one input frame before frame 0, exactly its bytes; key: None, or per frame
+    != 0 for a key frame ((n,) ints, a tensor or a list).  -> (stream u8 of the worst-case size, offsets (n + 1,) i64, status (n,) i32: the
+    frame's unpack code, else 0x100 | its predecessor's; a frame that fails is 64 zero bytes).  `out` must not overlap `frames` or `prev`."""
+    return _delta_call(False, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status)
+
+
+def undelta_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, prev: Optional[torch.Tensor] = None,
+                          key=None, out: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """delta_levels_frames undone (include/svc_hip.h; the numpy statement is layers.undelta_frames): frame i is the delta stream's frame i
+    plus OUTPUT frame i - 1, with the key flags the delta call took.  prev: None, or the reconstructed frame before frame 0 (the last
+    output frame of the call before).  The result as delta_levels_frames gives it; a failure runs down the chain to the next key frame."""
+    return _delta_call(True, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status)
 
 
 def window_entropy_max_bytes(n_out: int, w: int, h: int, block, mv_block) -> int:

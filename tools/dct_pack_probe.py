@@ -46,6 +46,14 @@
                                                    d_src) against four calls; wall time per call over 20 back-to-back calls; (e) `frames`
                                                    (default 64) frames at (1, 640) as SVCE through tests/dropin/stream_reduced_main at reduce 2,
                                                    4, 8: the band stream against the full stream, alternating, every run printed
+  python tools/dct_pack_probe.py delta [C3|C5]     a stream coded frame against frame in levels, the same batch of 16 with frame 0 the key
+                                                   frame, stored at (1, 640), at (1, 1) and as the every-tile enhancement at (1, 640, 1):
+                                                   (a) bytes per frame of the delta stream beside the intra stream, raw and entropy-coded, and
+                                                   undelta(delta) compared with the stored stream; (b) svc_hip_delta_levels_frames and
+                                                   svc_hip_undelta_levels_frames against svc_hip_union_levels_frames on two bands of the same
+                                                   stream and svc_hip_window_levels_frames with no window, then svc_hip_undelta_levels_frames
+                                                   followed by svc_hip_decode_levels_frames against the decode alone; wall time per call over
+                                                   20 back-to-back calls
   python tools/dct_pack_probe.py window-entropy [C3|C5]
                                                    a stored entropy-coded enhancement served under a gaze, the same batch of 16 at
                                                    (1, 640, 1) with a 256 x 256 window per frame: svc_hip_window_entropy_frames on the stored
@@ -687,6 +695,103 @@ def band(cfg, frames_n=64) -> None:
                         sys.exit(1)
 
 
+def delta(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+
+    def fmt(t):
+        return f"{t[0]:.3f} .. {t[1]:.3f}"
+
+    def coded_bytes(stream, offs):
+        _, eo, st = native.entropy_encode_frames(stream, offs, pw, ph, block, mv)
+        sync()
+        assert not st.any()
+        return int(eo[-1])
+
+    def used(out, offs):
+        sync()
+        return out[:int(offs[-1])].clone(), offs.clone()
+
+    stored = {}
+    for steps in ((1, 640), (1, 1)):
+        stored[f"{steps}"] = used(*native.dct_pack_levels_frames(bgr, block, types, mv, *steps))
+    _, _, enh, enh_offs = native.dct_pack_layers_frames(bgr, block, types, mv, 1, 640, 1)
+    stored["(1, 640, 1) enhancement, every tile"] = used(enh, enh_offs)
+    # (a) bytes: a key frame every 16, so frame 0 of the batch is the key frame and 15 frames are differences
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}, frame 0 a key frame; MB per frame, raw / entropy-coded", flush=True)
+    diffs = {}
+    for name, (stream, offs) in stored.items():
+        out, oo, st = native.delta_levels_frames(stream, offs, pw, ph, block, mv)
+        assert not st.any()
+        diffs[name] = d, do = used(out, oo)
+        back, bo, st = native.undelta_levels_frames(d, do, pw, ph, block, mv)
+        sync()
+        assert not st.any() and torch.equal(bo, offs) and torch.equal(back[:stream.numel()], stream), "undelta(delta) is not the stored stream"
+        raw, craw = stream.numel(), coded_bytes(stream, offs)
+        draw, dcoded = d.numel(), coded_bytes(d, do)
+        key = int(offs[1])
+        print(f"(a) {name}: intra {raw / n / 1e6:.4f} / {craw / n / 1e6:.4f}, delta {draw / n / 1e6:.4f} / {dcoded / n / 1e6:.4f} "
+              f"({draw / raw:.3f}x / {dcoded / craw:.3f}x); the 15 difference frames alone {(draw - key) / 15 / 1e6:.4f} raw against "
+              f"{(raw - key) / 15 / 1e6:.4f}; undelta(delta) is the stored stream", flush=True)
+    # (b) the calls' time beside the two-input merge on streams of the same bytes and the plain copy
+    outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+    oo = [torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(2)]
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    ws_w = torch.empty(native.window_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_u = torch.empty(native.union_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_d = torch.empty(native.delta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_x = torch.empty(native.decode_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    rec = torch.empty((n, ph, pw, 3), dtype=torch.float32, device=dev)
+    k = block // 2
+    for name in ("(1, 1)", "(1, 640)"):
+        stream, offs = stored[name]
+        d, do = diffs[name]
+        low, lo = used(*native.band_levels_frames(stream, offs, pw, ph, block, mv, band=[(0, 0, k, k)] * n)[:2])
+        high, ho = used(*native.band_levels_frames(stream, offs, pw, ph, block, mv, band=[(k, k, block, block)] * n)[:2])
+        print(f"(b) the stream stored at {name} ({stream.numel() / n / 1e6:.3f} MB per frame, its delta stream {d.numel() / n / 1e6:.3f}), ms per "
+              f"call of {n} frames (best .. worst of 3 runs of 20 back-to-back calls)", flush=True)
+
+        def f_window():
+            return native.window_levels_frames(stream, offs, pw, ph, block, mv, out=outs[0], out_offsets=oo[0], workspace=ws_w, status=st)
+
+        def f_union():
+            return native.union_levels_frames(low, lo, high, ho, pw, ph, block, mv, out=outs[0], out_offsets=oo[0], workspace=ws_u, status=st)
+
+        def f_delta():
+            return native.delta_levels_frames(stream, offs, pw, ph, block, mv, out=outs[0], out_offsets=oo[0], workspace=ws_d, status=st)
+
+        def f_undelta():
+            return native.undelta_levels_frames(d, do, pw, ph, block, mv, out=outs[1], out_offsets=oo[1], workspace=ws_d, status=st)
+
+        def f_decode():
+            return native.decode_levels_frames(stream, offs, pw, ph, block, mv, 1, 640, rec=rec, workspace=ws_x)
+
+        def f_undelta_decode():
+            f_undelta()
+            return native.decode_levels_frames(outs[1], oo[1], pw, ph, block, mv, 1, 640, rec=rec, workspace=ws_x)
+        t_win = _per_step(f_window, sync, steps=20)
+        t_uni = _per_step(f_union, sync, steps=20)
+        t_del = _per_step(f_delta, sync, steps=20)
+        t_und = _per_step(f_undelta, sync, steps=20)
+        assert not st.any() and torch.equal(oo[1], offs) and torch.equal(outs[1][:stream.numel()], stream)
+        t_win2 = _per_step(f_window, sync, steps=20)  # the window call again, after: the spread of the same call in this run
+        print(f"    svc_hip_window_levels_frames, no window {fmt(t_win)} (again {fmt(t_win2)})", flush=True)
+        print(f"    svc_hip_union_levels_frames of (0, 0, {k}, {k}) and its remainder {fmt(t_uni)}", flush=True)
+        print(f"    svc_hip_delta_levels_frames {fmt(t_del)} ({t_del[0] / t_uni[0]:.2f}x the union, {t_del[0] / t_win[0]:.2f}x the window call)", flush=True)
+        print(f"    svc_hip_undelta_levels_frames {fmt(t_und)} ({t_und[0] / t_uni[0]:.2f}x the union, {t_und[0] / t_win[0]:.2f}x the window call), "
+              f"{(d.numel() + stream.numel()) / t_und[0] / 1e6:.1f} GB/s of input plus output", flush=True)
+        t_dec = _per_step(f_decode, sync, steps=20)
+        t_both = _per_step(f_undelta_decode, sync, steps=20)
+        t_dec2 = _per_step(f_decode, sync, steps=20)
+        print(f"    svc_hip_decode_levels_frames {fmt(t_dec)} (again {fmt(t_dec2)}); undelta then decode {fmt(t_both)} ({t_both[0] / t_dec[0]:.2f}x)",
+              flush=True)
+
+
 def pack_layers(cfg) -> None:
     dev = torch.device("cuda")
     n = 16
@@ -830,6 +935,8 @@ if __name__ == "__main__":
         split(_cfg(sys.argv, 2))
     elif mode == "band":
         band(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 64)
+    elif mode == "delta":
+        delta(_cfg(sys.argv, 2))
     elif mode == "stream-layers":
         stream_layers()
     elif mode == "pack-layers":
