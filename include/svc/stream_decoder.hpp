@@ -33,10 +33,11 @@ struct StreamDecoderConfig {
   // batches in flight without pinning a GB.
   uint32_t wire_batch = 8;
   uint32_t depth = 3;                     // batches in flight, >= 3 (H2D, kernels and D2H of three batches overlap)
-  // Decode at 1 / reduce of the size from each tile's low frequencies (svc_hip_decode_levels_reduced_frames): 1 = the full decoder, or
-  // 2, 4, 8.  Above 1 the picture is the padded size over reduce: a display of 0 x 0 means that size, a larger one throws
-  // std::runtime_error at the first Decode; gaze centres stay in display coordinates.  Serves Decode (SVCQ and SVCE) only:
-  // DecodeLayers and DecodeWire then throw std::runtime_error before any device work.
+  // Decode at 1 / reduce of the size from each tile's low frequencies (svc_hip_decode_levels_reduced_frames, for DecodeLayers
+  // svc_hip_decode_layers_reduced_frames): 1 = the full decoder, or 2, 4, 8.  Above 1 the picture is the padded size over reduce: a
+  // display of 0 x 0 means that size, a larger one throws std::runtime_error at the first Decode or DecodeLayers; gaze centres stay in
+  // display coordinates.  Serves Decode and DecodeLayers (SVCQ and SVCE): only DecodeWire then throws std::runtime_error before any
+  // device work.
   uint32_t reduce = 1;
 };
 
@@ -84,10 +85,11 @@ class StreamDecoder {
   // EncodedBatch::compact / enhancement.  Each stream is SVCQ or SVCE by its own first frame's magic (an SVCE stream goes through
   // svc_hip_entropy_decode_frames first); the geometry comes from the base's first header, and the enhancement's first header must parse
   // and name the same geometry (else std::runtime_error).  Schedule, gaze rectangles, display size and statistics as Decode; the device
-  // call is svc_hip_decode_layers_frames: inside the gaze a tile decodes at the enhancement's step.  With an empty `gaze` the
-  // enhancement is not read (it may be null) and the call is Decode on the base; a frame whose callback returns false decodes as the
-  // base alone.  DecodedBatch::status: the entropy decoder's code for the base frame if it is not 0, else 0x100 | its code for the
-  // enhancement frame, else the code of svc_hip_decode_layers_frames.  One decoder serves Decode, DecodeWire and DecodeLayers in any order.
+  // call is svc_hip_decode_layers_frames, with config.reduce above 1 svc_hip_decode_layers_reduced_frames: inside the gaze a tile decodes
+  // at the enhancement's step.  With an empty `gaze` the enhancement is not read (it may be null) and the call is Decode on the base
+  // (at that reduce); a frame whose callback returns false decodes as the base alone.  DecodedBatch::status: the entropy decoder's code
+  // for the base frame if it is not 0, else 0x100 | its code for the enhancement frame, else the code of svc_hip_decode_layers_frames.
+  // One decoder serves Decode, DecodeWire and DecodeLayers in any order.
   void DecodeLayers(const uint8_t* base, const uint64_t* base_offsets, const uint8_t* enh, const uint64_t* enh_offsets, uint32_t n_frames,
                     const Gaze& gaze, const Sink& sink);
 

@@ -857,6 +857,38 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes,
                                  uint32_t display_w, uint32_t display_h, uint32_t* d_status,
                                  void* stream);
 
+/* The two layers at reduced size: the union of svc_hip_decode_levels_reduced_frames and
+ * svc_hip_decode_layers_frames.  reduce, K, the picture, d_rec, d_display and the display size are
+ * those of svc_hip_decode_levels_reduced_frames; per tile, for the coefficients with row < K and
+ * column < K only: not gazed -- exactly that call on the base frame; gazed (the tile origin tested
+ * in padded FULL-SIZE coordinates) -- the level Lb * ratio + d and the step of
+ * svc_hip_decode_layers_frames, requantised at step 1, then the K-point inverse and the scaling of
+ * the reduced call.  The residuals outside K x K are never read: the band (0, 0, K, K) of both
+ * layers (svc_hip_band_levels_frames) decodes to the same bits.  Geometry, limits, alignment and
+ * check order as svc_hip_decode_levels_reduced_frames (both streams 16-byte aligned, both offset
+ * arrays 8-byte): geometry, steps, reduce, display size, limits, workspace, then pointers.  The
+ * workspace (twice the one-stream one), d_status and failed frames as svc_hip_decode_layers_frames.
+ * With d_gaze == NULL the enhancement stream is neither checked nor read (d_enh may be NULL with 0
+ * bytes) and the call is svc_hip_decode_levels_reduced_frames on the base, bit for bit.
+ * scalable_video_codec_amd/layers.py (reduced_coefficients, decode_layers_reduced_frame) is the
+ * numpy statement.  Only enqueues. */
+uint64_t svc_hip_decode_layers_reduced_workspace_bytes(uint32_t n_frames, uint32_t frame_w,
+                                                       uint32_t frame_h, uint32_t block_w,
+                                                       uint32_t block_h);
+int svc_hip_decode_layers_reduced_frames(const uint8_t* d_base, uint64_t base_bytes,
+                                         const uint64_t* d_base_offsets, const uint8_t* d_enh,
+                                         uint64_t enh_bytes, const uint64_t* d_enh_offsets,
+                                         uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                         uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                         uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                                         uint32_t reduce,
+                                         const uint32_t* d_gaze /* [n_frames][4] x, y, w, h (padded, full size); NULL = none */,
+                                         uint8_t* d_workspace, uint64_t workspace_bytes,
+                                         float* d_rec /* [n][H / reduce][W / reduce][3] f32 B,G,R */,
+                                         uint8_t* d_display /* [n][display_h][display_w][3] u8 B,G,R, or NULL */,
+                                         uint32_t display_w, uint32_t display_h, uint32_t* d_status,
+                                         void* stream);
+
 /* ------------------------------------------------------------------------- *
  * A stored SVCQ stream restricted to a window per output frame, stream to stream: encode the
  * every-tile enhancement once (d_window == NULL above), then serve any gaze without the pixels.

@@ -129,6 +129,7 @@ DROPIN_APPS = [
     "stream_decode_main",   # svc::StreamDecoder: stream_levels_main's output -> display frames, tests/test_gpu_decode_levels.py
     "stream_reduced_main",  # svc::StreamDecoder with StreamDecoderConfig::reduce: display frames at 1/2, 1/4, 1/8 size, tests/test_gpu_decode_reduced.py
     "stream_layers_main",   # two layers: compact + enh_step, and svc::StreamDecoder::DecodeLayers on them: tests/test_gpu_stream_layers.py
+    "stream_layers_reduced_main",  # DecodeLayers with StreamDecoderConfig::reduce on stream_layers_main's files: tests/test_gpu_decode_layers_reduced.py
     "wire_decode_main",     # svc::StreamDecoder::DecodeWire: a reference stream on stdin -> display frames, tests/test_gpu_decode_records.py
     "stream_fuzz",          # the encoder at random against itself (batch sizes, depths, entry points, reuse): tests/test_gpu_stream.py
 ]

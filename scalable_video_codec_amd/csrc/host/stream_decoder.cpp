@@ -113,7 +113,8 @@ struct StreamDecoder::Impl {
   std::unique_ptr<BatchPipe> pipe;  // (after the buffers: its streams synchronise before those go)
   DecodeStats stats;
 
-  // layers: for DecodeLayers (the workspace of svc_hip_decode_layers_frames; enh_entropy = the enhancement stream is SVCE)
+  // layers: for DecodeLayers (the workspace of svc_hip_decode_layers_frames, which the reduced call shares; enh_entropy = the enhancement
+  // stream is SVCE)
   void Size(const uint32_t* hdr, bool entropy, bool layers = false, bool enh_entropy = false) {
     const uint32_t w = hdr[kHWidth], h = hdr[kHHeight], tw = hdr[kHTileW], th = hdr[kHTileH], mw = hdr[kHMvW], mh = hdr[kHMvH];
     const uint32_t rw = w / c.reduce, rh = h / c.reduce;  // the picture the display pass reads
@@ -272,7 +273,6 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
 
 void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offsets, const uint8_t* enh, const uint64_t* enh_offsets,
                                  uint32_t n_frames, const Gaze& gaze, const Sink& sink) {
-  if (p_->c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeLayers does not decode at reduced size (reduce must be 1)");
   if (!gaze) return Decode(base, base_offsets, n_frames, gaze, sink);  // no tile takes the enhancement: it is not read
   Impl& m = *p_;
   const StreamDecoderConfig& c = m.c;
@@ -324,9 +324,15 @@ void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offse
                 "svc_hip_entropy_decode_frames (enhancement)");
             qe = m.eq.p; qeoff = m.eqoff.p; qebytes = m.q_bytes;
           }
-          Abi(svc_hip_decode_layers_frames(qb, qbbytes, qboff, qe, qebytes, qeoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step,
-                                           c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh, s.status.p, sk),
-              "svc_hip_decode_layers_frames");
+          if (c.reduce > 1)
+            Abi(svc_hip_decode_layers_reduced_frames(qb, qbbytes, qboff, qe, qebytes, qeoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh,
+                                                     c.fg_step, c.bg_step, c.reduce, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw,
+                                                     m.dh, s.status.p, sk),
+                "svc_hip_decode_layers_reduced_frames");
+          else
+            Abi(svc_hip_decode_layers_frames(qb, qbbytes, qboff, qe, qebytes, qeoff, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, c.fg_step,
+                                             c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh, s.status.p, sk),
+                "svc_hip_decode_layers_frames");
         },
         [&](hipStream_t so) -> uint64_t {
           Hip(hipMemcpyAsync(s.pin_disp.p, s.disp.p, cnt * m.disp_bytes, hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H display");

@@ -29,6 +29,9 @@
 // decode at reduced size (svc_hip_decode_levels_reduced_frames): the decode's count and scan, then a reconstruction from the first K x K
 // coefficients of every N x N tile to a picture of 1 / reduce the size (stated at its kernel).
 //
+// decode of two layers at reduced size (svc_hip_decode_layers_reduced_frames): the two-layer decode's counts, scans and status merge, then
+// the reduced reconstruction with the enhancement inside the gaze, a kernel of its own (stated there).
+//
 // window (svc_hip_window_levels_frames): a stored stream restricted to a window per output frame, without the pixels -- count, scan,
 // frame offsets, then one pass that writes every output frame in aligned 16-byte vectors (stated at its kernels).
 //
@@ -698,6 +701,115 @@ __global__ __launch_bounds__(reduced_threads(N, K)) void decode_reduced_kernel(D
 template <int N, int K>
 void launch_decode_reduced(dim3 grid, hipStream_t s, const DecodeArgs& a) {
   hipLaunchKernelGGL((decode_reduced_kernel<N, K>), grid, dim3(reduced_threads(N, K)), 0, s, a);
+}
+
+// svc_hip_decode_layers_reduced_frames: decode_reduced_kernel with decode_body's enhancement, a kernel of its own so that the one-stream
+// form keeps its code.  The status read is the merged one (0 = both frames may be read).  Whether the group holds a gazed tile is
+// decided in wave 0 itself (lane l tests tile l, one ballot: the group has at most 32 tiles), which then also scans the enhancement
+// frame's words of the three planes into job arrays of their own (3 x 64 x 12 B at most); no barrier depends on it.  A thread of a gazed
+// tile gathers the residual d by rank beside the base level Lb, for its K coefficients only, and dequantises (Lb * ratio + d) at the
+// enhancement's step; every other thread takes decode_reduced_kernel's path and has its bits.
+template <int N, int K>
+__global__ __launch_bounds__(reduced_threads(N, K)) void decode_layers_reduced_kernel(DecodeLayersArgs args) {
+  constexpr uint32_t kTiles = kGroupCoeffs / (N * N), kJobs = kTiles * ((N * N + 63) / 64);  // tiles and mask words of a group
+  static_assert(kJobs <= 64, "one wave scans a group's mask words");
+  __shared__ uint64_t job_mask[3][kJobs], enh_mask[3][kJobs];
+  __shared__ uint32_t job_base[3][kJobs], enh_base[3][kJobs];
+  __shared__ double rows[3][kTiles * K * (K + 1)];
+  const DecodeArgs& a = args.base;
+  const Geom& g = a.g;
+  const uint32_t gi0 = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t st = a.ws.status[f];
+  const uint8_t* frame = a.in + a.offsets[f];  // both dereferenced only for a frame whose merged status is 0
+  const uint8_t* eframe = args.enh + (st == kStOk ? args.enh_offsets[f] : 0);
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t t = tid / K, j = tid - t * K;
+  const bool active = t < gr.nt;  // (nt <= kTiles)
+  const uint32_t jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
+  if (tid < 64) {  // wave 0: mask: 0 for a frame that failed and past the group's words, no level is read through it
+    const bool any_gazed = __ballot(st == kStOk && tid < gr.nt && gazed(a.gaze, f, gr.x0 + tid * N, gr.y0)) != 0;  // the same in every lane
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint64_t m = (st == kStOk && tid < jobs) ? load_mask(group_masks(g, frame, c, gr) + 2 * tid) : 0ull;
+      const uint32_t ex = wave_exclusive_scan((uint32_t)__popcll(m));
+      if (tid < kJobs) { job_mask[c][tid] = m; job_base[c][tid] = ex; }
+      if (any_gazed) {
+        const uint64_t me = tid < jobs ? load_mask(group_masks(g, eframe, c, gr) + 2 * tid) : 0ull;
+        const uint32_t exe = wave_exclusive_scan((uint32_t)__popcll(me));
+        if (tid < kJobs) { enh_mask[c][tid] = me; enh_base[c][tid] = exe; }
+      }
+    }
+  }
+  float enc = 0.f, dec = 1.f, enh_step = 0.f;
+  bool enhanced = false;  // a gazed tile: its group's enhancement words are in LDS
+  uint32_t ratio = 0;
+  if (st == kStOk && active) {
+    const uint32_t type = tile_type(g, reinterpret_cast<const uint32_t*>(frame + kHeaderBytes), gr, t);
+    const bool in_gaze = gazed(a.gaze, f, gr.x0 + t * N, gr.y0);  // the full-size tile origin: one rule for both decoders
+    const uint32_t enc_step = type == 0 ? hdr[kHBgStep] : hdr[kHFgStep];
+    enc = (float)enc_step;
+    dec = in_gaze ? 1.f : (type == 0 ? a.bg : a.fg);
+    if (in_gaze) {
+      const uint32_t e = reinterpret_cast<const uint32_t*>(eframe)[kHFgStep];
+      ratio = enc_step / e;
+      enh_step = (float)e;
+      enhanced = true;
+    }
+  }
+  __syncthreads();
+  if (active) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const size_t gi = (size_t)f * g.groups + c * per_plane + gi0;
+      const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) + (st == kStOk ? a.ws.cnt[gi] : 0u);
+      const int16_t* resid = reinterpret_cast<const int16_t*>(eframe + g.levels_off) + (enhanced ? args.enh_ws.cnt[gi] : 0u);
+      float v[K];
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        const uint32_t k = j * N + i, w = t * g.words + (k >> 6), b = k & 63u;
+        const uint64_t mask = job_mask[c][w], below = (1ull << b) - 1;
+        v[i] = 0.f;
+        if (enhanced) {
+          const uint64_t emask = enh_mask[c][w];
+          // unsigned: a stream that breaks the format's bound on a level wraps instead of overflowing
+          uint32_t lv = 0;
+          if ((mask >> b) & 1u) lv = (uint32_t)(int32_t)levels[job_base[c][w] + (uint32_t)__popcll(mask & below)] * ratio;
+          if ((emask >> b) & 1u) lv += (uint32_t)(int32_t)resid[enh_base[c][w] + (uint32_t)__popcll(emask & below)];
+          v[i] = (float)(int32_t)lv * enh_step;
+        } else if ((mask >> b) & 1u) {
+          v[i] = (float)levels[job_base[c][w] + (uint32_t)__popcll(mask & below)] * enc;
+        }
+      }
+      invert_row_reduced<K>(v, dec, rows[c], t, j);
+    }
+  }
+  __syncthreads();
+  if (!active) return;
+  float out[3][K];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) invert_column_reduced<N, K>(rows[c], t, j, out[c]);
+  const uint32_t rw = g.w / N * K;  // the reduced picture's width; adjacent lanes hold adjacent pixels
+  store_bgr_column<K>(a.rec + (((size_t)f * (g.h / N * K) + gr.ty * K) * rw + (gr.t0 + t) * K + j) * 3, rw, out);
+}
+
+template <int N, int K>
+void launch_decode_reduced(dim3 grid, hipStream_t s, const DecodeLayersArgs& a) {
+  hipLaunchKernelGGL((decode_layers_reduced_kernel<N, K>), grid, dim3(reduced_threads(N, K)), 0, s, a);
+}
+
+// the instantiation for a block of 8 or 16 and a reduce of 2, 4 or 8 (both checked by the caller), of either form
+template <typename A>  // DecodeArgs or DecodeLayersArgs
+void launch_decode_reduced(uint32_t block, uint32_t reduce, dim3 grid, hipStream_t s, const A& a) {
+  if (block == 8) {
+    if (reduce == 2) launch_decode_reduced<8, 4>(grid, s, a);
+    else if (reduce == 4) launch_decode_reduced<8, 2>(grid, s, a);
+    else launch_decode_reduced<8, 1>(grid, s, a);
+  } else {
+    if (reduce == 2) launch_decode_reduced<16, 8>(grid, s, a);
+    else if (reduce == 4) launch_decode_reduced<16, 4>(grid, s, a);
+    else launch_decode_reduced<16, 2>(grid, s, a);
+  }
 }
 
 // ---- window: SVCQ frames restricted to the tiles of a window, stream to stream ---------------------------------------------------
@@ -1991,6 +2103,19 @@ int validate_limits(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32
   return svc::validate_limits(what, n, w, h, bw, bh, frame_layout(w, h, bw, bh, mvbw, mvbh).max_bytes);
 }
 
+// What the two decodes at reduced size check first, in this order: geometry, steps, reduce, the display size against the reduced picture,
+// limits.
+int validate_reduced(const char* what, uint32_t n, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t mvbw, uint32_t mvbh, uint32_t fg,
+                     uint32_t bg, uint32_t reduce, uint32_t display_w, uint32_t display_h) {
+  const int rc = validate_decode_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (rc) return rc;
+  SVC_REQUIRE(fg > 0 && bg > 0, "%s: quant steps must be positive (libs/decoder.cpp:35-47)", what);
+  SVC_REQUIRE(reduce == 2 || reduce == 4 || reduce == 8, "%s: reduce %u (supported: 2, 4, 8)", what, reduce);
+  SVC_REQUIRE((display_w == 0 && display_h == 0) || (display_w >= 1 && display_w <= w / reduce && display_h >= 1 && display_h <= h / reduce),
+              "%s: display %ux%u must lie within 1x1 .. %ux%u (the padded frame over reduce)", what, display_w, display_h, w / reduce, h / reduce);
+  return validate_limits(what, n, w, h, bw, bh, mvbw, mvbh);
+}
+
 // the pack's launches, with a.fg / a.bg or the budgeted pack's per-frame steps
 int enqueue_pack(const char* what, const PackArgs& a, hipStream_t s) {
   const Geom& g = a.g;
@@ -2371,15 +2496,11 @@ int svc_hip_decode_levels_reduced_frames(const uint8_t* d_frames, uint64_t strea
                                          uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec, uint8_t* d_display, uint32_t display_w,
                                          uint32_t display_h, uint32_t* d_status, void* stream) {
   const char* what = "decode_levels_reduced";
-  int rc = validate_decode_geom(what, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  int rc = validate_reduced(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, reduce, display_w,
+                            display_h);
   if (rc) return rc;
-  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "%s: quant steps must be positive (libs/decoder.cpp:35-47)", what);
-  SVC_REQUIRE(reduce == 2 || reduce == 4 || reduce == 8, "%s: reduce %u (supported: 2, 4, 8)", what, reduce);
   const uint32_t rw = frame_w / reduce, rh = frame_h / reduce;  // whole: the sides are multiples of the block, the block of `reduce`
   const bool display = display_w != 0 || display_h != 0;
-  SVC_REQUIRE(!display || (display_w >= 1 && display_w <= rw && display_h >= 1 && display_h <= rh),
-              "%s: display %ux%u must lie within 1x1 .. %ux%u (the padded frame over reduce)", what, display_w, display_h, rw, rh);
-  if ((rc = validate_limits(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if ((rc = require_workspace(what, workspace_bytes, layout_bytes(stream_ws, n_frames, g.groups)))) return rc;
   if (n_frames == 0) return SVC_OK;
@@ -2393,15 +2514,7 @@ int svc_hip_decode_levels_reduced_frames(const uint8_t* d_frames, uint64_t strea
   if ((rc = enqueue_unpack_scan(what, u, n_frames, d_status, s))) return rc;
   const DecodeArgs a{g, d_frames, d_frame_offsets, d_gaze, d_rec, u.ws, (float)fg_step, (float)bg_step};
   const dim3 grid(g.tiles_y * g.gx, n_frames);
-  if (block_w == 8) {
-    if (reduce == 2) launch_decode_reduced<8, 4>(grid, s, a);
-    else if (reduce == 4) launch_decode_reduced<8, 2>(grid, s, a);
-    else launch_decode_reduced<8, 1>(grid, s, a);
-  } else {
-    if (reduce == 2) launch_decode_reduced<16, 8>(grid, s, a);
-    else if (reduce == 4) launch_decode_reduced<16, 4>(grid, s, a);
-    else launch_decode_reduced<16, 2>(grid, s, a);
-  }
+  launch_decode_reduced(block_w, reduce, grid, s, a);
   return finish_with_display(what, "reconstruction", display, d_rec, d_display, n_frames, rw, rh, display_w, display_h, s);
 }
 
@@ -2450,6 +2563,51 @@ int svc_hip_decode_layers_frames(const uint8_t* d_base, uint64_t base_bytes, con
   if (block_w == 8) hipLaunchKernelGGL(decode_layers_kernel<8>, grid, dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(decode_layers_kernel<16>, grid, dim3(kThreads), 0, s, a);
   return finish_with_display("decode_layers", "reconstruction", display, d_rec, d_display, n_frames, frame_w, frame_h, display_w, display_h, s);
+}
+
+uint64_t svc_hip_decode_layers_reduced_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                       uint32_t block_h) {
+  return svc_hip_decode_layers_workspace_bytes(n_frames, frame_w, frame_h, block_w, block_h);
+}
+
+// Checked in the order of svc_hip_decode_levels_reduced_frames, with the workspace of svc_hip_decode_layers_frames.  Without a gaze no
+// tile takes the enhancement: the call is svc_hip_decode_levels_reduced_frames on the base.
+int svc_hip_decode_layers_reduced_frames(const uint8_t* d_base, uint64_t base_bytes, const uint64_t* d_base_offsets, const uint8_t* d_enh,
+                                         uint64_t enh_bytes, const uint64_t* d_enh_offsets, uint32_t n_frames, uint32_t frame_w,
+                                         uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                         uint32_t fg_step, uint32_t bg_step, uint32_t reduce, const uint32_t* d_gaze, uint8_t* d_workspace,
+                                         uint64_t workspace_bytes, float* d_rec, uint8_t* d_display, uint32_t display_w, uint32_t display_h,
+                                         uint32_t* d_status, void* stream) {
+  const char* what = "decode_layers_reduced";
+  int rc = validate_reduced(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, reduce, display_w,
+                            display_h);
+  if (rc) return rc;
+  const uint32_t rw = frame_w / reduce, rh = frame_h / reduce;  // whole: the sides are multiples of the block, the block of `reduce`
+  const bool display = display_w != 0 || display_h != 0;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  const uint64_t ws_stream = layout_bytes(stream_ws, n_frames, g.groups);
+  if ((rc = require_workspace(what, workspace_bytes, 2 * ws_stream))) return rc;
+  if (n_frames == 0) return SVC_OK;
+  if (!d_gaze)
+    return svc_hip_decode_levels_reduced_frames(d_base, base_bytes, d_base_offsets, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w,
+                                                mv_block_h, fg_step, bg_step, reduce, nullptr, d_workspace, workspace_bytes, d_rec, d_display,
+                                                display_w, display_h, d_status, stream);
+  SVC_REQUIRE(d_base && d_base_offsets && d_enh && d_enh_offsets && d_workspace && d_rec && d_status, "%s: null pointer", what);
+  if ((rc = validate_display_buffer(what, display, d_display))) return rc;
+  SVC_REQUIRE(aligned(d_base, 16) && aligned(d_enh, 16) && aligned(d_workspace, 16) && aligned(d_base_offsets, 8) && aligned(d_enh_offsets, 8) &&
+                  aligned(d_rec, 4) && aligned(d_status, 4) && aligned(d_gaze, 4),
+              "%s: frames and workspace must be 16-byte aligned, offsets 8-byte, output, gaze and status 4-byte", what);
+  const UnpackArgs ub{g, d_base, base_bytes, d_base_offsets, nullptr, nullptr, carve(d_workspace, stream_ws, n_frames, g.groups)};
+  const UnpackArgs ue{g, d_enh, enh_bytes, d_enh_offsets, nullptr, nullptr, carve(d_workspace + ws_stream, stream_ws, n_frames, g.groups)};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = enqueue_unpack_scan("decode_layers_reduced base", ub, n_frames, d_status, s))) return rc;
+  if ((rc = enqueue_unpack_scan("decode_layers_reduced enhancement", ue, n_frames, ue.ws.status, s))) return rc;  // its codes stay in its workspace
+  const DecodeLayersArgs a{{g, d_base, d_base_offsets, d_gaze, d_rec, ub.ws, (float)fg_step, (float)bg_step}, d_enh, d_enh_offsets, ue.ws};
+  hipLaunchKernelGGL(layers_status_kernel, dim3(div_up(n_frames, kThreads)), dim3(kThreads), 0, s, a, n_frames, d_status);
+  if ((rc = check_launch("decode_layers_reduced status"))) return rc;
+  const dim3 grid(g.tiles_y * g.gx, n_frames);
+  launch_decode_reduced(block_w, reduce, grid, s, a);
+  return finish_with_display(what, "reconstruction", display, d_rec, d_display, n_frames, rw, rh, display_w, display_h, s);
 }
 
 uint64_t svc_hip_window_levels_workspace_bytes(uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,

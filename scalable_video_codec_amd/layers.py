@@ -9,6 +9,9 @@ steps divide).  Per coefficient, with Lb its level in the base frame and Lf its 
 and an enhancement frame is an SVCQ frame whose levels are d, with fg_step = bg_step = enh_step in its header.  Inside the gaze the
 decoder dequantises (Lb * ratio + d) * enh_step, elsewhere Lb * sb.
 
+reduced_coefficients / decode_layers_reduced_frame state svc_hip_decode_layers_reduced_frames: the same two layers decoded at 1 / reduce of
+the size from the first K x K coefficients of every tile, on top of levels.reduced_coefficients.
+
 window_frame / window_frames state svc_hip_window_levels_frames: a stored frame restricted to the tiles of a window, on its masks.
 
 band_frame / band_frames state svc_hip_band_levels_frames: a stored frame restricted to a frequency band of every tile (and a window), on
@@ -151,6 +154,53 @@ def merge_levels(base_frame, enh_frame, gaze: Optional[Sequence[int]] = None) ->
     gazed = _contains(gaze, ox, oy)
     merged = np.where(_per_pixel(hb, gazed)[None], lb * _per_pixel(hb, step // e)[None] + d, lb)
     return merged, np.where(gazed, e, step)
+
+
+# ---- the two layers decoded at reduced size (include/svc_hip.h: svc_hip_decode_layers_reduced_frames) --------------------------------
+
+def _reduced(base_frame, enh_frame, reduce: int, fg_step: int, bg_step: int, gaze) -> Tuple[np.ndarray, int]:
+    """reduced_coefficients and its K."""
+    out, k = levels._reduced(base_frame, reduce, fg_step, bg_step, None)  # every tile as a tile outside the gaze
+    if gaze is None:
+        return out, k
+    merged, step = merge_levels(base_frame, enh_frame, gaze)  # raises for an enhancement frame that is not this base frame's
+    hb, types, _ = levels.parse_frame(base_frame)
+    n = hb["block_w"]
+    _, ox, oy = _tile_maps(hb, types)
+    gazed = _contains(gaze, ox, oy)
+    ty, tx = gazed.shape
+    c = merged.astype(np.float32) * _per_pixel(hb, step)[None].astype(np.float32)  # a gazed tile: (f32)(Lb * ratio + d) * (f32)enh_step
+    tiles = c.reshape(3, ty, n, tx, n)[:, :, :k, :, :k]
+    q = (tiles / np.float32(1)).astype(np.float32).astype(np.float64)
+    r = np.copysign(np.floor(np.abs(q) + 0.5), q).astype(np.float32)
+    lifted = (r * np.float32(1)).astype(np.float32) * np.float32(k / n)
+    out = np.where(gazed[None, :, None, :, None], lifted, out.reshape(3, ty, k, tx, k))
+    return np.ascontiguousarray(out.reshape(3, ty * k, tx * k), np.float32), k
+
+
+def reduced_coefficients(base_frame, enh_frame, reduce: int, fg_step: int, bg_step: int, gaze: Optional[Sequence[int]] = None
+                         ) -> np.ndarray:
+    """What the reduced decoder of two layers inverts -> (3, H / reduce, W / reduce) f32, laid out as levels.reduced_coefficients lays
+    it out: the first K x K coefficients of every N x N tile, K = N / reduce.  A tile whose origin (in full-size padded coordinates) the
+    gaze rectangle x, y, w, h does not contain, and every tile for gaze None: exactly levels.reduced_coefficients on the base frame.  A
+    gazed tile: level = Lb * ratio + d of merge_levels (d = 0 where the enhancement's mask bit is clear, ratio = the tile's base step /
+    the enhancement's step), c = (f32)level * (f32)enh_step, requantised at step 1 and scaled by K / N, every operation one f32
+    operation as there (roundf in f64 on the f32 quotient).  reduce = 1: the full layered decoder's requantised coefficients.  enh_frame
+    is not read for gaze None; otherwise raises ValueError where merge_levels raises."""
+    return _reduced(base_frame, enh_frame, reduce, fg_step, bg_step, gaze)[0]
+
+
+def decode_layers_reduced_frame(base_frame, enh_frame, reduce: int, fg_step: int, bg_step: int,
+                                gaze: Optional[Sequence[int]] = None) -> np.ndarray:
+    """The reduced decoder's picture of two layers before its rounding to f32 -> (H / reduce, W / reduce, 3) f64 B,G,R: the K-point
+    inverse DCT-II along rows and columns of every K x K tile of reduced_coefficients, as levels.decode_reduced_frame takes it."""
+    coef, k = _reduced(base_frame, enh_frame, reduce, fg_step, bg_step, gaze)
+    coef = coef.astype(np.float64)
+    c = levels._basis(k)
+    _, rh, rw = coef.shape
+    t = coef.reshape(3, rh // k, k, rw // k, k)
+    x = np.einsum("vy,pavbu,ux->paybx", c, t, c)
+    return np.ascontiguousarray(x.reshape(3, rh, rw).transpose(1, 2, 0))
 
 
 # ---- a stored stream restricted to a window (include/svc_hip.h: svc_hip_window_levels_frames) -----------------------------------------

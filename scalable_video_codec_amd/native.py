@@ -154,6 +154,9 @@ SIGNATURES = {
     "svc_hip_pack_layers_frames": (C.c_int, [_vp, _vp] + [_u32] * 10 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "svc_hip_decode_layers_workspace_bytes": (_u64, [_u32] * 5),
     "svc_hip_decode_layers_frames": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp] + [_u32] * 9 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "svc_hip_decode_layers_reduced_workspace_bytes": (_u64, [_u32] * 5),
+    "svc_hip_decode_layers_reduced_frames": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp] + [_u32] * 10
+                                             + [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
     # a stored SVCQ stream restricted to a window per output frame (csrc/levels.hip; host statement: layers.window_frames)
     "svc_hip_window_levels_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_window_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp] + [_u32] * 7 + [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
@@ -1184,6 +1187,44 @@ def decode_layers_frames(base: torch.Tensor, base_offsets: torch.Tensor, enh: Op
                                                _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
                                                None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
                                                _dev(status, torch.int32), _stream()))
+    return rec, out_display, status
+
+
+def decode_layers_reduced_workspace_bytes(n: int, w: int, h: int, block) -> int:
+    bw, bh = _bwbh(block)
+    return int(load().svc_hip_decode_layers_reduced_workspace_bytes(n, w, h, bw, bh))
+
+
+def decode_layers_reduced_frames(base: torch.Tensor, base_offsets: torch.Tensor, enh: Optional[torch.Tensor],
+                                 enh_offsets: Optional[torch.Tensor], w: int, h: int, block, mv_block, fg_step: int = 1,
+                                 bg_step: int = 640, reduce: int = 2, gaze=None, display: Optional[Tuple[int, int]] = None,
+                                 rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None,
+                                 workspace: Optional[torch.Tensor] = None
+                                 ) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """decode_layers_frames at 1 / reduce of the size (reduce 2, 4 or 8), from the first K x K coefficients of every tile of both
+    layers, K = block / reduce -> (rec (frames, H / reduce, W / reduce, 3) f32 B,G,R, display (frames, display_h, display_w, 3) u8 or
+    None, status as decode_layers_frames).  w, h and the gaze rectangles are the padded full size's; display: (w, h) within (W / reduce,
+    H / reduce).  enh / enh_offsets may be None when gaze is None: the call is then decode_levels_reduced_frames on the base.  Host
+    statement: layers.reduced_coefficients / layers.decode_layers_reduced_frame."""
+    n = base_offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = base.device
+    if rec is None:
+        rec = torch.empty((n, h // max(reduce, 1), w // max(reduce, 1), 3), dtype=torch.float32, device=dev)
+    dw, dh = display if display is not None else (0, 0)
+    if display is not None and out_display is None:
+        out_display = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(decode_layers_reduced_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=dev)
+    g = _rects(gaze, n, dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_decode_layers_reduced_frames(_dev(base, torch.uint8), base.numel(), _dev(base_offsets, torch.int64),
+                                                       None if enh is None else _dev(enh, torch.uint8), 0 if enh is None else enh.numel(),
+                                                       None if enh_offsets is None else _dev(enh_offsets, torch.int64), n, w, h, bw, bh,
+                                                       mbw, mbh, fg_step, bg_step, reduce, None if g is None else _dev(g, torch.int32),
+                                                       _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
+                                                       None if out_display is None else _dev(out_display, torch.uint8), dw, dh,
+                                                       _dev(status, torch.int32), _stream()))
     return rec, out_display, status
 
 

@@ -11,6 +11,13 @@
                                          the bytes each route stores; and at steps (1, 1) the PSNR of both against the r x r box mean
   python tools/decode_probe.py reduced-rate   the 65-frame stream of `rate` through tests/dropin/stream_reduced_main and through
                                          stream_decode_main at the same display sizes (PCIe included)
+  python tools/decode_probe.py layers-reduced   one C3 batch of 16 as two layers at (1, 640, 1), in one process: per reduce 2, 4, 8 and for a
+                                         64 x 64 gaze and the whole frame gazed, svc_hip_decode_layers_reduced_frames with the display
+                                         (W / r, H / r) against svc_hip_decode_layers_frames with the display pass at that size and against
+                                         svc_hip_decode_levels_reduced_frames on the base alone, alternating, device events
+  python tools/decode_probe.py layers-reduced-rate   tests/dropin/stream_layers_main writes the 65-frame clip as two layers, plain and
+                                         entropy-coded; tests/dropin/stream_layers_reduced_main decodes them at reduce r and, as the full
+                                         route, at reduce 1 with the display (W / r, H / r) (PCIe included)
 """
 import os
 import subprocess
@@ -197,5 +204,114 @@ def reduced_rate() -> None:
                         sys.exit(1)
 
 
+def layers_reduced() -> None:
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native, pipeline
+    dev = torch.device("cuda")
+    m = 16
+    clip = synth.SynthClip(CFG.width, CFG.height, m + 1, CFG.seed, device=dev)
+    pw, ph = CFG.padded
+    frames = [synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(m + 1)]
+    enc = pipeline.ClipEncoder(CFG, m + 1, dev)  # `reduced`'s batch: the region ids are the encoder's
+    enc.load_frames(frames)
+    enc.step()
+    types = enc.types
+    bgr = torch.stack(frames[1:]).contiguous()
+    block, mvb = CFG.dct_block, CFG.mv_block
+    fg, bg, e = CFG.fg_step, CFG.bg_step, 1
+    base, bo, enh, eo = native.dct_pack_layers_frames(bgr, block, types, mvb, fg, bg, e)
+    torch.cuda.synchronize()
+    ub, ue = int(bo[-1]), int(eo[-1])
+    base, enh = base[:ub].clone(), enh[:ue].clone()
+    ws = torch.empty(native.decode_layers_reduced_workspace_bytes(m, pw, ph, block), dtype=torch.uint8, device=dev)
+    rec_full = torch.empty((m, ph, pw, 3), dtype=torch.float32, device=dev)
+    print(f"C3 batch of {m} as two layers at ({fg}, {bg}, {e}): {ub / m / 1e6:.3f} MB of base and {ue / m / 1e6:.3f} MB of enhancement per frame",
+          flush=True)
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def fmt(t):
+        return f"{np.median(t):.3f} ms per batch (min {min(t):.3f}, max {max(t):.3f})"
+
+    for r in (2, 4, 8):
+        rw, rh = pw // r, ph // r
+        small = [native.gaze_rect((50 + 50 * i) // r, 500 // r, 64, 64, rw, rh, pw, ph) for i in range(m)]
+        rec = torch.empty((m, rh, rw, 3), dtype=torch.float32, device=dev)
+        disp_r, disp_f, disp_b = (torch.empty((m, rh, rw, 3), dtype=torch.uint8, device=dev) for _ in range(3))
+        for name, rects in (("64 x 64", small), ("the whole frame", [(0, 0, pw, ph)] * m)):
+            gaze = torch.tensor(rects, dtype=torch.int32, device=dev)
+
+            def red():
+                native.decode_layers_reduced_frames(base, bo, enh, eo, pw, ph, block, mvb, fg, bg, reduce=r, gaze=gaze, display=(rw, rh),
+                                                    rec=rec, out_display=disp_r, workspace=ws)
+
+            def full():
+                native.decode_layers_frames(base, bo, enh, eo, pw, ph, block, mvb, fg, bg, gaze=gaze, display=(rw, rh), rec=rec_full,
+                                            out_display=disp_f, workspace=ws)
+
+            def one():
+                native.decode_levels_reduced_frames(base, bo, pw, ph, block, mvb, fg, bg, reduce=r, gaze=gaze, display=(rw, rh), rec=rec,
+                                                    out_display=disp_b, workspace=ws)
+
+            for _ in range(3):
+                red(), full(), one()
+            torch.cuda.synchronize()
+            t_red, t_full, t_one = [], [], []
+            for _ in range(7):  # alternating windows of 20 batches each
+                t_red.append(timed(red, 20))
+                t_full.append(timed(full, 20))
+                t_one.append(timed(one, 20))
+            print(f"reduce {r}, gaze {name}: display {rw}x{rh}; layered reduced call {fmt(t_red)}; full layered call + display pass {fmt(t_full)}, "
+                  f"full / reduced = {np.median(t_full) / np.median(t_red):.2f}; one-stream reduced call on the base {fmt(t_one)}, "
+                  f"layered / one-stream = {np.median(t_red) / np.median(t_one):.2f}", flush=True)
+
+
+def layers_reduced_rate() -> None:
+    n = 65
+    pw, ph = CFG.padded
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    here = os.path.join(ROOT, "tests", "dropin")
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        clip = synth.SynthClip(CFG.width, CFG.height, n, CFG.seed, device="cpu")
+        raw = os.path.join(d, "clip.raw")
+        with open(raw, "wb") as f:
+            for t in range(n):
+                clip.frame_bgr(t).numpy().tofile(f)
+        prefixes = {}
+        for coded in (0, 1):
+            prefixes[coded] = os.path.join(d, f"layers{coded}")
+            p = subprocess.run([os.path.join(here, "stream_layers_main"), raw, str(CFG.width), str(CFG.height), str(n), str(CFG.levels),
+                                str(CFG.dct_block), "16", "3", str(CFG.seed), str(CFG.fg_step), str(CFG.bg_step), "1", str(coded), "-", "-",
+                                prefixes[coded]], capture_output=True, text=True, timeout=600)
+            print(f"== stream_layers_main entropy {coded} (exit {p.returncode})\n{p.stdout.strip()}\n{p.stderr.strip()}", flush=True)
+            if p.returncode != 0:
+                sys.exit(1)
+            os.remove(prefixes[coded] + ".display")
+        exe = os.path.join(here, "stream_layers_reduced_main")
+        for r in (2, 4, 8):
+            dw, dh = pw // r, ph // r
+            gaze = os.path.join(d, f"gaze{r}.txt")
+            with open(gaze, "w") as f:
+                for i in range(n - 1):
+                    f.write(f"{(60 + 29 * i) % dw} {(40 + 17 * i) % dh}\n")
+            for coded in (0, 1):
+                for turn in range(3):  # alternating, every run printed: the spread is part of the result
+                    for name, args in (("reduced", [str(r), "0", "0"]), ("full", ["1", str(dw), str(dh)])):
+                        p = subprocess.run([exe, prefixes[coded], str(n - 1), *args, gaze, "16", "-"], capture_output=True, text=True, timeout=300)
+                        print(f"== stream_layers_reduced_main {name} ({'SVCE' if coded else 'SVCQ'}) display {dw}x{dh} batch 16, run {turn} "
+                              f"(exit {p.returncode})\n{p.stdout.strip()}\n{p.stderr.strip()}", flush=True)
+                        if p.returncode != 0:
+                            sys.exit(1)
+
+
 if __name__ == "__main__":
-    {"rate": rate, "kernels": kernels, "reduced": reduced, "reduced-rate": reduced_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
+    {"rate": rate, "kernels": kernels, "reduced": reduced, "reduced-rate": reduced_rate, "layers-reduced": layers_reduced,
+     "layers-reduced-rate": layers_reduced_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
