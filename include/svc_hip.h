@@ -1326,6 +1326,63 @@ int svc_hip_wire_layout(const svc_wire_header* hdr, uint64_t stream_bytes, uint3
                         uint64_t* frame_bytes);
 
 /* ------------------------------------------------------------------------- *
+ * Transcoding between the two streams on the device, stream to stream: the reference's wire
+ * records <-> the compact stream ("SVCQ"), with no f32 planes in between.  A clip stored by the
+ * reference's encoder becomes a compact stream (and with svc_hip_entropy_encode_frames an
+ * entropy-coded one) without its pixels; a compact stream becomes records the reference's
+ * unchanged decoder plays.
+ *
+ * svc_hip_records_pack_levels_frames: records -> SVCQ at (fg_step, bg_step).  The records are
+ * read as svc_hip_decode_records_frames reads them: frame_w x frame_h is the PADDED size, the grid
+ * frame_w / block columns by ceil(emit_frame_h / block) rows, frame f at d_records + f *
+ * records_stride_bytes; tile rows the stream does not hold are zero coefficients.  The wire
+ * header carries no MV block: the caller chooses one (a multiple of the tile that divides the
+ * frame; mv_block = block always works).  The types section holds, for each MV block, the type
+ * word of the record of the tile at that block's origin (the rule of svc_hip_dct_quant_frames read
+ * backwards; 0 where that tile's row is not held).  Header with its inexact word, types, masks,
+ * levels, padding and offsets are, byte for byte and on any input bits, what
+ * svc_hip_pack_levels_frames writes for the planes and per-MV-block types parsed from the
+ * records.  d_status [n_frames] u32: 4 for a frame in which a held record's type word differs
+ * from its MV block's type (the frame still comes out by the origin rule), else 0.
+ *
+ * Any square tile with block * block <= 4096.  Checked in this order, for any n_frames, before any
+ * pointer and without a device: geometry (as svc_hip_pack_levels_frames; 1 <= emit_frame_h <=
+ * frame_h), steps (0 is SVC_ERR_INVALID_ARG), the int16 bound of svc_hip_pack_levels_frames
+ * (SVC_ERR_UNSUPPORTED), limits, the stride (a multiple of 4, at least
+ * svc_hip_serialized_frame_bytes(frame_w, emit_frame_h, block, block)), workspace, out_capacity
+ * against svc_hip_levels_max_bytes; n_frames == 0 then returns SVC_OK; then pointers (records and
+ * status 4-byte aligned, output and workspace 16, offsets 8).  Only enqueues work: three launches.
+ *
+ * svc_hip_levels_records_frames: SVCQ -> records, byte for byte those of
+ * svc_hip_unpack_levels_frames followed by svc_hip_serialize_frames(frame_w, emit_frame_h, ...) on
+ * its planes and types: the type word is the MV block's id, a coefficient (float)level *
+ * (float)step where a mask bit is set and +0.0 elsewhere.  d_status [n_frames] u32 with the codes
+ * of svc_hip_unpack_levels_frames; a frame that fails is all-zero records.  Bytes of a frame's
+ * stride past its records are left as they are.  Square tiles only (else SVC_ERR_UNSUPPORTED).
+ * Checked in this order: geometry, the square tile, emit_frame_h, limits, stride, workspace;
+ * n_frames == 0 then returns SVC_OK; then pointers.  Only enqueues work: three launches.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_records_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                     uint32_t block, uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_records_pack_levels_frames(const uint8_t* d_records, uint64_t records_stride_bytes, uint32_t n_frames,
+                                       uint32_t frame_w, uint32_t frame_h /* padded */, uint32_t block,
+                                       uint32_t emit_frame_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                       uint32_t fg_step, uint32_t bg_step,
+                                       uint8_t* d_workspace, uint64_t workspace_bytes,
+                                       uint8_t* d_out, uint64_t out_capacity,
+                                       uint64_t* d_frame_offsets /* [n_frames + 1] */,
+                                       uint32_t* d_status /* [n_frames] */, void* stream);
+uint64_t svc_hip_levels_records_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                uint32_t block_w, uint32_t block_h);
+int svc_hip_levels_records_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                  const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                  uint32_t mv_block_w, uint32_t mv_block_h, uint32_t emit_frame_h,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes,
+                                  uint8_t* d_records, uint64_t records_stride_bytes,
+                                  uint32_t* d_status /* [n_frames] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Pre-step: luma + pyramid on the device, so the pyramid never
  * crosses PCIe.  Stands in for cv::cvtColor(BGR2YUV) + cv::extractChannel +
  * cv::buildPyramid (libs/encoder.cpp:468-470) with this repo's fixed-point

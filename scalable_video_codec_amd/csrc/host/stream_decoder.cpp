@@ -5,6 +5,7 @@
 #include "../stream_format.hpp"
 #include "batch_pipe.hpp"
 #include "copy_crew.hpp"
+#include "stage_frames.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -39,30 +40,6 @@ struct Slot {
   PinBuf<uint32_t> pin_enh_estatus;
   uint32_t first = 0, count = 0;
 };
-
-// The bytes of frames first .. first + cnt of a stream in host memory -> the slot's pinned buffer, their offsets relative to it:
-// from the batch's lowest offset (rounded down to 16: frames stay aligned) to its highest, inside the stream; an offset outside it
-// becomes one the kernels refuse (status 1), so a malformed frame is reported, never read past the copy.  -> the bytes staged
-uint64_t StageFrames(CopyCrew& crew, const uint8_t* stream, const uint64_t* offsets, uint64_t total, uint32_t first, uint32_t cnt,
-                     PinBuf<uint8_t>& pin, DevBuf<uint8_t>& dev, uint64_t* pin_off) {
-  uint64_t lo = total, hi = 0;
-  for (uint32_t i = first; i <= first + cnt; ++i) {
-    const uint64_t o = std::min(offsets[i], total);
-    lo = std::min(lo, o); hi = std::max(hi, o);
-  }
-  lo &= ~(uint64_t)15;
-  const uint64_t bytes = hi - lo;
-  if (pin.n < std::max<uint64_t>(bytes, 16)) {  // grown on demand: a batch of 1080p frames is about 17 MB
-    const size_t cap = (size_t)(bytes + bytes / 4 + 4095) & ~(size_t)4095;
-    pin.Alloc(kWho, cap); dev.Alloc(kWho, cap);
-  }
-  crew.Copy(pin.p, stream + lo, bytes);
-  for (uint32_t i = 0; i <= cnt; ++i) {
-    const uint64_t o = offsets[first + i];
-    pin_off[i] = o <= total ? o - lo : ~(uint64_t)15;
-  }
-  return bytes;
-}
 
 // the first frame's header of a stream of n_frames >= 1 frames, which must open an SVCQ v1 or SVCE v1 frame
 void FirstHeader(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const char* which, uint32_t hdr[kHeaderWords]) {
@@ -229,7 +206,7 @@ void StreamDecoder::Decode(const uint8_t* stream, const uint64_t* offsets, uint3
     const uint32_t cnt = std::min(B, n_frames - first);
     const uint32_t slot = m.pipe->Acquire();
     Slot& s = *m.slots[slot];
-    const uint64_t bytes = StageFrames(m.crew, stream, offsets, total, first, cnt, s.pin_in, s.in, s.pin_off.p);
+    const uint64_t bytes = StageFrames(kWho, m.crew, stream, offsets, total, first, cnt, s.pin_in, s.in, s.pin_off.p);
     m.StageGaze(s, gaze, first, cnt);
     s.first = first; s.count = cnt;
     m.pipe->Submit(
@@ -293,8 +270,8 @@ void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offse
     const uint32_t cnt = std::min(B, n_frames - first);
     const uint32_t slot = m.pipe->Acquire();
     Slot& s = *m.slots[slot];
-    const uint64_t bytes = StageFrames(m.crew, base, base_offsets, total, first, cnt, s.pin_in, s.in, s.pin_off.p);
-    const uint64_t ebytes = StageFrames(m.crew, enh, enh_offsets, enh_total, first, cnt, s.pin_enh, s.enh, s.pin_enh_off.p);
+    const uint64_t bytes = StageFrames(kWho, m.crew, base, base_offsets, total, first, cnt, s.pin_in, s.in, s.pin_off.p);
+    const uint64_t ebytes = StageFrames(kWho, m.crew, enh, enh_offsets, enh_total, first, cnt, s.pin_enh, s.enh, s.pin_enh_off.p);
     m.StageGaze(s, gaze, first, cnt);
     s.first = first; s.count = cnt;
     m.pipe->Submit(

@@ -49,6 +49,9 @@
 //
 // pack of two layers (svc_hip_pack_layers_frames): the pack's count, scan and scatter on raw planes with two quantisations per coefficient,
 // the frame offsets from frame_offsets_kernel with a job per layer (stated at its kernels).
+//
+// wire records <-> SVCQ (svc_hip_records_pack_levels_frames, svc_hip_levels_records_frames): the pack's and the unpack's count, scan and
+// scatter with the reference's wire records in place of the planes, stream to stream (stated at their kernels).
 #include "budget_core.hpp"
 #include "display_core.hpp"
 #include "idct_core.hpp"
@@ -2096,6 +2099,191 @@ __global__ __launch_bounds__(256) void drain_kernel(const uint4* __restrict__ sr
   for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
 }
 
+// ---- the reference's wire records <-> SVCQ, stream to stream (svc_hip_records_pack_levels_frames, svc_hip_levels_records_frames) --------
+//
+// A wire frame is one record per tile in tile order, each a u32 type word and 3 x N x N f32 coefficients (wire.hip, records.hip), so
+// plane p of a tile is N x N CONTIGUOUS floats at dword 1 + p N N of its record: a 64-coefficient mask word is one coalesced dword load
+// (records are only 4-byte aligned: 772 B at 8 x 8) and a __ballot, with no staging of rows.  Both directions keep the pack's and the
+// unpack's groups, their order, their counts and their scans, so the bytes are those of the routes through planes.
+
+// the workspace of the pack from records: the pack's own, then per frame the MV blocks' types as the records give them, and per
+// (frame, group of plane 0) whether a held record disagrees with its MV block
+struct RecordsPackWs {
+  Ws pack;
+  uint32_t *types, *mismatch;
+};
+RecordsPackWs records_pack_ws(Carver& c, uint32_t n, uint32_t groups, uint32_t mvb) {
+  RecordsPackWs s;
+  s.pack = stream_ws(c, n, groups);
+  s.types = c.take<uint32_t>((uint64_t)n * mvb);
+  s.mismatch = c.take<uint32_t>((uint64_t)n * (groups / 3));
+  return s;
+}
+
+struct RecordsPackArgs {
+  Geom g;
+  const uint8_t* records;  // frame f at records + f * stride
+  uint64_t stride;
+  uint32_t emit_rows, rec_dw;  // tile rows the stream holds; dwords per record
+  uint8_t* out;
+  uint64_t* offsets;       // [n + 1]
+  uint32_t* d_status;      // [n]
+  RecordsPackWs ws;
+  uint32_t fg, bg;
+};
+
+// the type word of the record at the origin of the MV block that holds tile (ty, tx) of a held tile row (the origin's row is then held too)
+__device__ __forceinline__ uint32_t origin_type(const RecordsPackArgs& a, const uint32_t* __restrict__ frame_rec, uint32_t ty, uint32_t tx) {
+  const Geom& g = a.g;
+  const uint32_t oy = (ty * g.bh / g.mvbh) * (g.mvbh / g.bh), ox = (tx * g.bw / g.mvbw) * (g.mvbw / g.bw);
+  return frame_rec[((size_t)oy * g.tiles_x + ox) * a.rec_dw];
+}
+
+// pack_kernel with the records as its source.  SCATTER = false: the group's non-zero count and inexact count and, from the groups of
+// plane 0, the MV blocks' types (the type word of the record at each block's origin; 0 in a tile row the stream does not hold) and
+// whether a held record's type word differs from its block's.  SCATTER = true: masks and levels at their final place -- the levels
+// compacted in LDS in stream order and stored as one run per wave -- and, from group 0 of each frame, the header, the types, the zero
+// pad, offsets[f + 1] and the frame's status.  A tile row the stream does not hold is zero coefficients.
+// Dynamic LDS (SCATTER): 2 x cap u16, cap = the group's coefficients, even.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void records_pack_kernel(RecordsPackArgs a) {
+  extern __shared__ uint16_t lds16[];
+  __shared__ uint64_t job_mask[kMaxJobs];
+  __shared__ uint32_t job_base[kMaxJobs];
+  __shared__ uint32_t red[kThreads / 64];
+  __shared__ uint64_t frame_off;
+  const Geom& g = a.g;
+  const uint32_t gi = blockIdx.x, f = blockIdx.y, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const Group gr = group_of(g, gi);
+  const bool held = gr.ty < a.emit_rows;  // the same in every thread
+  const uint32_t* frame_rec = reinterpret_cast<const uint32_t*>(a.records + f * a.stride);
+  const uint32_t* row_rec = frame_rec + ((size_t)gr.ty * g.tiles_x + gr.t0) * a.rec_dw;  // the group's first record; read only if held
+  const uint32_t area = g.bw * g.bh, jobs = gr.nt * g.words, cap = (g.tpg * area + 1) & ~1u;
+  uint16_t *raw = lds16, *run = lds16 + cap;
+  if (SCATTER) frame_offset_to_lds(a.ws.pack.frame_bytes, f, &frame_off);
+
+  uint32_t nz_count = 0, inexact = 0;
+  for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
+    const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
+    int32_t lv = 0;
+    if (held && k < area) {
+      const float step = origin_type(a, frame_rec, gr.ty, gr.t0 + t) == 0 ? (float)a.bg : (float)a.fg;
+      const float c = __uint_as_float(row_rec[(size_t)t * a.rec_dw + 1 + gr.plane * area + k]);
+      lv = level_of(c, step);
+      if (!SCATTER) inexact += c != (float)lv * step;
+    }
+    if (SCATTER && k < area) raw[t * area + k] = (uint16_t)lv;
+    const uint64_t mask = __ballot(lv != 0);
+    if (!SCATTER) nz_count += __popcll(mask);
+    else if (lane == 0) job_mask[j] = mask;
+  }
+  if (!SCATTER) {
+    inexact = wave_sum(inexact);
+    if (lane == 0) red[wave] = inexact;
+    __syncthreads();
+    if (threadIdx.x == 0) a.ws.pack.inexact[(size_t)f * g.groups + gi] = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    if (lane == 0) red[wave] = nz_count;
+    __syncthreads();
+    if (threadIdx.x == 0) a.ws.pack.cnt[(size_t)f * g.groups + gi] = red[0] + red[1] + red[2] + red[3];
+    if (gr.plane != 0) return;
+    // plane 0: thread t looks at the type word of the group's tile t (a group has at most kMaxJobs = kThreads tiles)
+    bool differs = false;
+    if (threadIdx.x < gr.nt) {
+      const uint32_t tx = gr.t0 + threadIdx.x, x = tx * g.bw;
+      const uint32_t own = held ? row_rec[(size_t)threadIdx.x * a.rec_dw] : 0u;
+      differs = held && own != origin_type(a, frame_rec, gr.ty, tx);
+      if (x % g.mvbw == 0 && gr.y0 % g.mvbh == 0) a.ws.types[(size_t)f * g.mvb + (gr.y0 / g.mvbh) * g.mfw + x / g.mvbw] = own;
+    }
+    const int any = __syncthreads_or(differs);
+    if (threadIdx.x == 0) a.ws.mismatch[(size_t)f * (g.groups / 3) + gi] = any != 0;
+    return;
+  }
+
+  // scatter: exclusive scan of the words' popcounts, in word order; the levels to their ranks in LDS
+  __syncthreads();
+  uint32_t total;
+  const uint32_t pc = threadIdx.x < jobs ? (uint32_t)__popcll(job_mask[threadIdx.x]) : 0u;
+  const uint32_t ex = block_exclusive_scan(pc, red, &total);
+  if (threadIdx.x < jobs) job_base[threadIdx.x] = ex;
+  __syncthreads();
+  for (uint32_t j = wave; j < jobs; j += kThreads / 64) {
+    const uint64_t mask = job_mask[j];
+    if (!((mask >> lane) & 1u)) continue;
+    const uint32_t t = j / g.words, k = (j - t * g.words) * 64 + lane;
+    run[job_base[j] + lane_rank(mask)] = raw[t * area + k];
+  }
+  __syncthreads();
+  uint8_t* frame = a.out + frame_off;
+  uint16_t* levels = reinterpret_cast<uint16_t*>(frame + g.levels_off) + a.ws.pack.cnt[(size_t)f * g.groups + gi];
+  uint32_t* masks = group_masks(g, frame, gr.plane, gr);
+  for (uint32_t j = threadIdx.x; j < jobs; j += kThreads) {  // two u32 stores: the masks are 4-byte aligned when mvb is odd
+    masks[2 * j] = (uint32_t)job_mask[j];
+    masks[2 * j + 1] = (uint32_t)(job_mask[j] >> 32);
+  }
+  // a wave stores a quarter of the group's run, from an even level on
+  const uint32_t piece = 2 * div_up(total, 2 * (kThreads / 64)), first = wave * piece;
+  if (first < total) store_level_run(run + first, min(piece, total - first), levels + first);
+  if (gi != 0) return;
+  // group 0: header, types, pad, offsets, status
+  const uint32_t* types = a.ws.types + (size_t)f * g.mvb;
+  write_frame_edges(frame, head_of(g, a.fg, a.bg, a.ws.pack.frame_levels[f], a.ws.pack.frame_inexact[f], a.ws.pack.frame_bytes[f]), types, g.mvb,
+                    g.levels_off, kThreads, a.offsets, f, frame_off);
+  bool differs = false;
+  for (uint32_t i = threadIdx.x; i < g.groups / 3; i += kThreads) differs |= a.ws.mismatch[(size_t)f * (g.groups / 3) + i] != 0;
+  const int any = __syncthreads_or(differs);
+  if (threadIdx.x == 0) a.d_status[f] = any ? kStGeometry : kStOk;
+}
+
+struct LevelsRecordsArgs {
+  UnpackArgs u;      // planes and types are null: none are written
+  uint8_t* records;  // frame f at records + f * stride
+  uint64_t stride;
+  uint32_t rec_dw;   // dwords per record
+};
+
+// After the unpack's count and scan.  Grid (groups of plane 0 in the tile rows the stream holds, frames): a workgroup writes the whole
+// records of its group's tiles -- the type word (the MV block's id) from thread t for tile t, then plane by plane the unpack's scatter
+// with the record as its destination: a wave per mask word, 64 adjacent dwords per store.  A frame that failed its checks is zeros.
+__global__ __launch_bounds__(256) void levels_records_kernel(LevelsRecordsArgs a) {
+  __shared__ uint32_t red[kThreads / 64];
+  __shared__ uint32_t job_base[kMaxJobs];
+  __shared__ uint64_t job_mask[kMaxJobs];
+  const Geom& g = a.u.g;
+  const uint32_t gi0 = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t st = a.u.ws.status[f];
+  const uint8_t* frame = a.u.in + (st == kStOk ? a.u.offsets[f] : 0);  // dereferenced only for a frame that passed its checks
+  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(frame);
+  const uint32_t* types = reinterpret_cast<const uint32_t*>(frame + kHeaderBytes);
+  const float fg = st == kStOk ? (float)hdr[kHFgStep] : 0.f, bg = st == kStOk ? (float)hdr[kHBgStep] : 0.f;
+  uint32_t* out = reinterpret_cast<uint32_t*>(a.records + f * a.stride) + ((size_t)gr.ty * g.tiles_x + gr.t0) * a.rec_dw;
+  const uint32_t area = g.bw * g.bh, jobs = gr.nt * g.words, per_plane = g.tiles_y * g.gx;
+  if (tid < gr.nt) out[(size_t)tid * a.rec_dw] = st == kStOk ? tile_type(g, types, gr, tid) : 0u;
+  for (uint32_t c = 0; c < 3; ++c) {
+    const uint32_t* masks = st != kStOk ? nullptr : group_masks(g, frame, c, gr);
+    const uint64_t m = (masks && tid < jobs) ? load_mask(masks + 2 * tid) : 0ull;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan((uint32_t)__popcll(m), red, &total);
+    if (tid < jobs) { job_mask[tid] = m; job_base[tid] = ex; }
+    __syncthreads();
+    const int16_t* levels = reinterpret_cast<const int16_t*>(frame + g.levels_off) +
+                            (st == kStOk ? a.u.ws.cnt[(size_t)f * g.groups + c * per_plane + gi0] : 0u);
+    for (uint32_t jj = wave; jj < jobs; jj += kThreads / 64) {
+      const uint64_t mask = job_mask[jj];
+      const uint32_t t = jj / g.words, k = (jj - t * g.words) * 64 + lane;
+      if (k >= area) continue;
+      float v = 0.f;
+      if ((mask >> lane) & 1u) {
+        const float step = tile_type(g, types, gr, t) == 0 ? bg : fg;
+        v = (float)levels[job_base[jj] + lane_rank(mask)] * step;
+      }
+      out[(size_t)t * a.rec_dw + 1 + c * area + k] = __float_as_uint(v);
+    }
+    __syncthreads();  // the next plane reuses the job arrays
+  }
+}
+
 // ---- the entry points' checks and launch sequences -----------------------------------------------------------------------------------
 
 // the limits with SVCQ's worst case
@@ -2906,6 +3094,94 @@ int svc_hip_pack_layers_frames(const float* d_planes, const uint32_t* d_block_ty
     return rc;
   hipLaunchKernelGGL(pack_layers_kernel<true>, grid, dim3(kThreads), lds_bytes(g), s, a);
   return check_launch("pack_layers", "scatter");
+}
+
+uint64_t svc_hip_records_pack_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                                     uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_geom("records_pack_levels_workspace_bytes", frame_w, frame_h, block, block, mv_block_w, mv_block_h) ||
+      validate_limits("records_pack_levels_workspace_bytes", n_frames, frame_w, frame_h, block, block, mv_block_w, mv_block_h))
+    return 0;
+  const Geom g = make_geom(frame_w, frame_h, block, block, mv_block_w, mv_block_h);
+  return layout_bytes(records_pack_ws, n_frames, g.groups, g.mvb);
+}
+
+// Checked in the order of svc_hip_pack_levels_frames, for any n_frames: geometry (with emit_frame_h), steps, the int16 bound, limits,
+// then the records' stride, workspace, output capacity; n_frames == 0 then returns SVC_OK; then pointers.  Three launches.
+int svc_hip_records_pack_levels_frames(const uint8_t* d_records, uint64_t records_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                       uint32_t frame_h, uint32_t block, uint32_t emit_frame_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                       uint32_t fg_step, uint32_t bg_step, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
+                                       uint64_t out_capacity, uint64_t* d_frame_offsets, uint32_t* d_status, void* stream) {
+  const char* what = "records_pack_levels";
+  int rc = validate_geom(what, frame_w, frame_h, block, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(emit_frame_h >= 1 && emit_frame_h <= frame_h, "%s: emit_frame_h %u outside [1, %u]", what, emit_frame_h, frame_h);
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "%s: quant steps must be positive", what);
+  // the pack's bound (Parseval on an orthonormal DCT of u8 samples): a stream of such coefficients then never clamps
+  if (255.0 * block / std::min(fg_step, bg_step) > 32767.0)
+    return fail(SVC_ERR_UNSUPPORTED, "%s: levels of a %ux%u tile at step %u could exceed int16", what, block, block, std::min(fg_step, bg_step));
+  if ((rc = validate_limits(what, n_frames, frame_w, frame_h, block, block, mv_block_w, mv_block_h))) return rc;
+  const uint64_t per = svc_hip_serialized_frame_bytes(frame_w, emit_frame_h, block, block);
+  SVC_REQUIRE(records_stride_bytes % 4 == 0 && records_stride_bytes >= per,
+              "%s: records stride %llu must be a multiple of 4 and at least one frame's %llu B", what,
+              (unsigned long long)records_stride_bytes, (unsigned long long)per);
+  const Geom g = make_geom(frame_w, frame_h, block, block, mv_block_w, mv_block_h);
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(records_pack_ws, n_frames, g.groups, g.mvb)))) return rc;
+  const uint64_t need = n_frames * frame_layout(frame_w, frame_h, block, block, mv_block_w, mv_block_h).max_bytes;
+  if ((rc = require_capacity(what, "output", out_capacity, need))) return rc;
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_records && d_workspace && d_out && d_frame_offsets && d_status, "%s: null pointer", what);
+  SVC_REQUIRE(aligned(d_records, 4) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_status, 4),
+              "%s: output and workspace must be 16-byte aligned, offsets 8-byte, records and status 4-byte", what);
+  RecordsPackArgs a{};
+  a.g = g; a.records = d_records; a.stride = records_stride_bytes;
+  a.emit_rows = div_up(emit_frame_h, block); a.rec_dw = 1 + 3 * block * block;
+  a.out = d_out; a.offsets = d_frame_offsets; a.d_status = d_status;
+  a.ws = carve(d_workspace, records_pack_ws, n_frames, g.groups, g.mvb);
+  a.fg = fg_step; a.bg = bg_step;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(g.groups, n_frames);
+  const uint32_t cap = (g.tpg * block * block + 1) & ~1u;  // the group's coefficients, as the kernel splits its LDS
+  hipLaunchKernelGGL(records_pack_kernel<false>, grid, dim3(kThreads), 0, s, a);
+  if ((rc = check_launch(what, "count"))) return rc;
+  hipLaunchKernelGGL(scan_kernel<false>, dim3(n_frames), dim3(kThreads), 0, s, g, a.ws.pack, nullptr, 0, nullptr, nullptr);
+  if ((rc = check_launch(what, "scan"))) return rc;
+  hipLaunchKernelGGL(records_pack_kernel<true>, grid, dim3(kThreads), 2 * cap * sizeof(uint16_t), s, a);
+  return check_launch(what, "scatter");
+}
+
+uint64_t svc_hip_levels_records_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h) {
+  return svc_hip_pack_levels_workspace_bytes(n_frames, frame_w, frame_h, block_w, block_h);  // the unpack's count and scan
+}
+
+// Checked in the order of svc_hip_unpack_levels_frames, for any n_frames: geometry (with the square tile and emit_frame_h), limits,
+// then the records' stride, workspace; n_frames == 0 then returns SVC_OK; then pointers.  Three launches.
+int svc_hip_levels_records_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                  uint32_t mv_block_h, uint32_t emit_frame_h, uint8_t* d_workspace, uint64_t workspace_bytes,
+                                  uint8_t* d_records, uint64_t records_stride_bytes, uint32_t* d_status, void* stream) {
+  const char* what = "levels_records";
+  int rc = validate_geom(what, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  if (block_w != block_h)
+    return fail(SVC_ERR_UNSUPPORTED, "%s: non-square tiles %ux%u (a record's rows and columns are those of a square tile)", what, block_w, block_h);
+  SVC_REQUIRE(emit_frame_h >= 1 && emit_frame_h <= frame_h, "%s: emit_frame_h %u outside [1, %u]", what, emit_frame_h, frame_h);
+  if ((rc = validate_limits(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const uint64_t per = svc_hip_serialized_frame_bytes(frame_w, emit_frame_h, block_w, block_h);
+  SVC_REQUIRE(records_stride_bytes % 4 == 0 && records_stride_bytes >= per,
+              "%s: records stride %llu must be a multiple of 4 and at least one frame's %llu B", what,
+              (unsigned long long)records_stride_bytes, (unsigned long long)per);
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(stream_ws, n_frames, g.groups)))) return rc;
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_records && d_status, "%s: null pointer", what);
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_records, 4) && aligned(d_status, 4),
+              "%s: frames and workspace must be 16-byte aligned, offsets 8-byte, records and status 4-byte", what);
+  const LevelsRecordsArgs a{{g, d_frames, stream_bytes, d_frame_offsets, nullptr, nullptr, carve(d_workspace, stream_ws, n_frames, g.groups)},
+                            d_records, records_stride_bytes, 1 + 3 * block_w * block_h};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = enqueue_unpack_scan(what, a.u, n_frames, d_status, s))) return rc;
+  hipLaunchKernelGGL(levels_records_kernel, dim3(div_up(emit_frame_h, block_h) * g.gx, n_frames), dim3(kThreads), 0, s, a);
+  return check_launch(what, "records");
 }
 
 int svc_hip_gaze_rect(uint32_t cx, uint32_t cy, uint32_t max_w, uint32_t max_h, uint32_t frame_w, uint32_t frame_h, uint32_t padded_w,

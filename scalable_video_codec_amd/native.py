@@ -185,6 +185,11 @@ SIGNATURES = {
     # the wire stream's decoder (csrc/records.hip) and its reading of a whole stream
     "svc_hip_decode_records_frames": (C.c_int, [_vp, _u64] + [_u32] * 7 + [_vp, _vp, _vp, _u32, _u32, _vp]),
     "svc_hip_wire_layout": (C.c_int, [C.POINTER(WireHeader), _u64, C.POINTER(_u32), C.POINTER(_u64)]),
+    # wire records <-> the compact stream, stream to stream (csrc/levels.hip; numpy statement: wire.py)
+    "svc_hip_records_pack_levels_workspace_bytes": (_u64, [_u32] * 6),
+    "svc_hip_records_pack_levels_frames": (C.c_int, [_vp, _u64] + [_u32] * 9 + [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "svc_hip_levels_records_workspace_bytes": (_u64, [_u32] * 5),
+    "svc_hip_levels_records_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 8 + [_vp, _u64, _vp, _u64, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1566,3 +1571,65 @@ def wire_layout(header: bytes, stream_bytes: int) -> Tuple[int, int]:
     emit, per = _u32(), _u64()
     _check(load().svc_hip_wire_layout(C.byref(hdr), stream_bytes, C.byref(emit), C.byref(per)))
     return int(emit.value), int(per.value)
+
+
+# ---- wire records <-> the compact stream, stream to stream (include/svc_hip.h; numpy statement: wire.py) ----
+
+def records_pack_levels_workspace_bytes(n: int, w: int, h: int, block: int, mv_block) -> int:
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_records_pack_levels_workspace_bytes(n, w, h, block, mbw, mbh))
+
+
+def records_pack_levels_frames(records: torch.Tensor, w: int, h: int, block: int, mv_block, fg_step: int, bg_step: int,
+                               emit_h: Optional[int] = None, out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                               workspace: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None
+                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Wire records (frames, bytes) u8 on the device, frame f's records in row f, read at the padded size w x h (emit_h: the height
+    they were emitted for, default h) -> what pack_levels_frames writes for their planes and per-MV-block types at (fg_step, bg_step),
+    without the planes: (stream u8 of the worst-case size, offsets (frames + 1,) i64, status (frames,) i32: 4 = a record's type word
+    differs from its MV block's)."""
+    n = records.shape[0]
+    emit_h = h if emit_h is None else emit_h
+    mbw, mbh = _bwbh(mv_block)
+    dev = records.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(records_pack_levels_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_records_pack_levels_frames(_dev(records, torch.uint8), records.stride(0) if n else 4 * (1 + 3 * block * block),
+                                                     n, w, h, block, emit_h, mbw, mbh, fg_step, bg_step,
+                                                     _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
+                                                     _dev(offsets, torch.int64), _dev(status, torch.int32), _stream()))
+    return out, offsets, status
+
+
+def levels_records_workspace_bytes(n: int, w: int, h: int, block) -> int:
+    bw, bh = _bwbh(block)
+    return int(load().svc_hip_levels_records_workspace_bytes(n, w, h, bw, bh))
+
+
+def levels_records_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, emit_h: Optional[int] = None,
+                          records: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                          status: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A packed stream (u8 on the device) + its offsets -> (wire records (frames, bytes) u8, the bytes of unpack_levels_frames +
+    serialize_frames(w, emit_h) without the planes; status (frames,) i32 with unpack_levels_frames' codes, a failed frame is zeros).
+    records: a (frames, stride) u8 tensor to write into (bytes of a row past its records are left alone)."""
+    n = offsets.numel() - 1
+    emit_h = h if emit_h is None else emit_h
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    if records is None:
+        records = torch.empty((n, serialized_frame_bytes(w, emit_h, bw, bh)), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(levels_records_workspace_bytes(n, w, h, block), 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(load().svc_hip_levels_records_frames(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, w, h, bw, bh,
+                                                mbw, mbh, emit_h, _dev(workspace, torch.uint8), workspace.numel(),
+                                                _dev(records, torch.uint8), records.stride(0) if n else 4 * (1 + 3 * bw * bh),
+                                                _dev(status, torch.int32), _stream()))
+    return records, status

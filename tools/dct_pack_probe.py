@@ -72,6 +72,14 @@
                                                    tests/dropin/stream_layers_main (plain, entropy-coded, and with every tile enhanced) beside
                                                    stream_levels_main, stream_entropy_main and stream_decode_main on the same clip and gaze,
                                                    the whole list twice in turn; PCIe-inclusive rates as the applications print them
+  python tools/dct_pack_probe.py transcode [C3|C5] the wire stream <-> the compact stream without planes, a batch of 8 (the drivers' wire
+                                                   batch) of raw-coefficient records with the pipeline's region ids, at (1, 640) and (1, 1):
+                                                   svc_hip_records_pack_levels_frames against svc_hip_pack_levels_frames on the same
+                                                   coefficients as planes, and svc_hip_levels_records_frames against
+                                                   svc_hip_unpack_levels_frames + svc_hip_serialize_frames; wall time per call over 20
+                                                   back-to-back calls, the routes alternating, the median of three runs each; the bytes are
+                                                   compared.  Then tests/dropin/wire_transcode_main --rate on 24 such frames, to-compact (plain
+                                                   and --entropy) and to-wire, beside wire_decode_main on the same stream, the list twice
 """
 import os
 import sys
@@ -843,6 +851,97 @@ def pack_layers(cfg) -> None:
               f"workspace {ws2.numel() / n / 1e6:.3f} MB per frame", flush=True)
 
 
+def _median_ms(fn, sync, runs=3, steps=20):
+    """Wall ms per call over `steps` back-to-back calls: every run, and the median."""
+    ts = sorted(_per_step(fn, sync, warm=1, reps=1, steps=steps)[0] for _ in range(runs))
+    return ts[len(ts) // 2], ts
+
+
+def transcode(cfg) -> None:
+    import subprocess
+    dev = torch.device("cuda")
+    n = 8
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    bgr, types = _batch(cfg, n)
+    planes = native.dct_frames(bgr, block)
+    records = native.serialize_frames(planes, types, pw, ph, block, block, pw // mv, ph // mv, mv)
+    del bgr
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out_r, out_p = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2))
+    offs_r, offs_p = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    ws_r = torch.empty(native.records_pack_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_p = torch.empty(native.pack_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    rec_out = torch.empty_like(records)
+    planes_out, types_out, rec_via = torch.empty_like(planes), torch.empty_like(types), torch.empty_like(records)
+    sync = torch.cuda.synchronize
+    rec_mb = records.numel() / 1e6
+    print(f"{cfg.name} batch of {n}: records {rec_mb / n:.2f} MB per frame; ms per call = the median of 3 runs of 20 back-to-back calls, "
+          f"the routes alternating (every run in brackets)", flush=True)
+    for fg, bg in ((1, 640), (1, 1)):
+        def from_records():
+            native.records_pack_levels_frames(records, pw, ph, block, mv, fg, bg, out=out_r, offsets=offs_r, workspace=ws_r, status=status)
+
+        def from_planes():
+            native.pack_levels_frames(planes, types, block, mv, fg, bg, out=out_p, offsets=offs_p, workspace=ws_p)
+
+        tr, tp = [], []
+        for _ in range(3):
+            tp += _median_ms(from_planes, sync, runs=1)[1]
+            tr += _median_ms(from_records, sync, runs=1)[1]
+        used = int(offs_r[-1])
+        assert torch.equal(offs_r, offs_p) and torch.equal(out_r[:used], out_p[:used]) and not status.any(), "records_pack differs from the pack"
+        mr, mp = sorted(tr)[1], sorted(tp)[1]
+        moved = 2 * records.numel() + used  # count and scatter each read the coefficients
+        print(f"({fg}, {bg}) forward: pack_levels on planes {mp:.3f} {[round(t, 3) for t in tp]}, records_pack_levels {mr:.3f} "
+              f"{[round(t, 3) for t in tr]} ({mr / mp:.2f} of the planes route); {used / n / 1e6:.3f} MB per frame out, {moved / 1e6:.1f} MB moved, "
+              f"{moved / (mr * 1e-3) / HBM_PEAK * 100:.1f} % of the HBM peak; same bytes", flush=True)
+        stream = out_r[:used].clone()
+
+        def to_records():
+            native.levels_records_frames(stream, offs_r, pw, ph, block, mv, records=rec_out, workspace=ws_p, status=status)
+
+        def via_planes():
+            native.unpack_levels_frames(stream, offs_r, pw, ph, block, mv, planes=planes_out, block_types=types_out, workspace=ws_p)
+            native.serialize_frames(planes_out, types_out, pw, ph, block, block, pw // mv, ph // mv, mv, out=rec_via)
+
+        tr, tp = [], []
+        for _ in range(3):
+            tp += _median_ms(via_planes, sync, runs=1)[1]
+            tr += _median_ms(to_records, sync, runs=1)[1]
+        assert torch.equal(rec_out, rec_via), "levels_records differs from unpack + serialize"
+        mr, mp = sorted(tr)[1], sorted(tp)[1]
+        print(f"({fg}, {bg}) reverse: unpack_levels + serialize {mp:.3f} {[round(t, 3) for t in tp]}, levels_records {mr:.3f} "
+              f"{[round(t, 3) for t in tr]} ({mr / mp:.2f} of the planes route); {(used + records.numel()) / 1e6:.1f} MB moved, "
+              f"{(used + records.numel()) / (mr * 1e-3) / HBM_PEAK * 100:.1f} % of the HBM peak; same bytes", flush=True)
+    # the drivers, PCIe-inclusive: 24 frames (3 batches of 8) = the batch three times over
+    import tempfile
+    dropin = os.path.join(ROOT, "tests", "dropin")
+    hdr = native.wire_header(3 * n + 1, cfg.width, cfg.height, mv, cfg.levels, block)
+    body = records.cpu().numpy().tobytes()
+    del planes, planes_out, rec_via, rec_out, out_p
+    torch.cuda.empty_cache()
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        wire_path, compact_path = os.path.join(d, "clip.wire"), os.path.join(d, "clip.svcq")
+        with open(wire_path, "wb") as f:
+            f.write(hdr + body * 3)
+        with open(wire_path, "rb") as fin, open(compact_path, "wb") as fout:
+            subprocess.run([os.path.join(dropin, "wire_transcode_main"), "to-compact", "--mv-block", str(mv)], stdin=fin, stdout=fout, check=True,
+                           timeout=300)
+        runs = [("wire_decode_main", [], wire_path), ("wire_transcode_main", ["to-compact", "--mv-block", str(mv), "--rate"], wire_path),
+                ("wire_transcode_main", ["to-compact", "--mv-block", str(mv), "--entropy", "--rate"], wire_path),
+                ("wire_transcode_main", ["to-wire", "--rate"], compact_path)]
+        for turn in range(2):
+            for name, args, path in runs:
+                with open(path, "rb") as fin:
+                    r = subprocess.run([os.path.join(dropin, name), *args], stdin=fin, capture_output=True, text=True, timeout=300)
+                print(f"== turn {turn}: {name} {' '.join(args)} (exit {r.returncode})\n{r.stdout.strip()}\n{r.stderr.strip()}", flush=True)
+                if r.returncode != 0:
+                    sys.exit(1)
+
+
 def stream_layers() -> None:
     import subprocess
     import tempfile
@@ -939,6 +1038,8 @@ if __name__ == "__main__":
         delta(_cfg(sys.argv, 2))
     elif mode == "stream-layers":
         stream_layers()
+    elif mode == "transcode":
+        transcode(_cfg(sys.argv, 2))
     elif mode == "pack-layers":
         for config in (configs.C3, configs.C5):
             pack_layers(config)
