@@ -36,8 +36,8 @@ struct StreamDecoderConfig {
   // Decode at 1 / reduce of the size from each tile's low frequencies (svc_hip_decode_levels_reduced_frames, for DecodeLayers
   // svc_hip_decode_layers_reduced_frames): 1 = the full decoder, or 2, 4, 8.  Above 1 the picture is the padded size over reduce: a
   // display of 0 x 0 means that size, a larger one throws std::runtime_error at the first Decode or DecodeLayers; gaze centres stay in
-  // display coordinates.  Serves Decode and DecodeLayers (SVCQ and SVCE): only DecodeWire then throws std::runtime_error before any
-  // device work.
+  // display coordinates.  Serves Decode and DecodeLayers (SVCQ and SVCE): DecodeWire and DecodeDelta then throw std::runtime_error before
+  // any device work.
   uint32_t reduce = 1;
 };
 
@@ -92,6 +92,20 @@ class StreamDecoder {
   // One decoder serves Decode, DecodeWire and DecodeLayers in any order.
   void DecodeLayers(const uint8_t* base, const uint64_t* base_offsets, const uint8_t* enh, const uint64_t* enh_offsets, uint32_t n_frames,
                     const Gaze& gaze, const Sink& sink);
+
+  // A delta stream (include/svc_hip.h, "A stored SVCQ stream cut by time"): n_frames frames coded against their predecessors by
+  // svc_hip_delta_levels_frames, as ONE chain -- frame 0 has no predecessor, frame i > 0 hangs on reconstructed frame i - 1 unless
+  // key[i] != 0 (key: n_frames host flags as the delta call took them, or null: only frame 0 is a key frame).  SVCQ or SVCE by the first
+  // frame's magic (SVCE goes through svc_hip_entropy_decode_frames first, as in Decode).  Schedule, gaze rectangles, display size and
+  // statistics are Decode's.  The device call is svc_hip_decode_delta_levels_frames -- the undelta and the decode in one kernel, which
+  // measures faster than the two calls at both densities (README, profiles/decode_delta_c3.txt) -- and two one-frame device buffers carry
+  // its d_last of batch b into the d_prev of batch b + 1 on the kernel stream, so the display frames do not depend on the batch size or
+  // the depth.  The next batch's call needs the carried frame's length on the host: 8 bytes come back on the kernel stream, and the host
+  // waits for batch b's kernels before it enqueues batch b + 1's (its H2D copy is in flight by then).  DecodedBatch::status: the entropy
+  // decoder's code if it is not 0, else svc_hip_undelta_levels_frames's (a failure runs down the chain to the next key frame).
+  // config.reduce above 1 throws std::runtime_error before any device work.  One decoder serves all four methods in any order.
+  void DecodeDelta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, const Gaze& gaze,
+                   const Sink& sink);
 
   // stream: a whole wire stream of `bytes` bytes in host memory, the 32-byte Header (libs/codec.hpp:8-17) first, then frame_count
   // frames of records.  svc_hip_wire_layout decides how it is read (the decoder's padded tile grid, or the reference encoder's

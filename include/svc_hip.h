@@ -1279,6 +1279,58 @@ int svc_hip_undelta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes
                                   uint32_t* d_status /* [n_frames] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * A delta stream straight to display frames: svc_hip_undelta_levels_frames and
+ * svc_hip_decode_levels_frames in one call, without the reconstructed stream in between.
+ *
+ * d_rec (and d_display, if a display size is given) are bit-identical, for every frame, to
+ * svc_hip_undelta_levels_frames with the same d_prev and d_key followed by
+ * svc_hip_decode_levels_frames on its output with the same steps, gaze and display size: the int16
+ * level of every coefficient is the same number in both routes and feeds the same arithmetic.  A
+ * frame that fails is zeros.  fg_step / bg_step are the DECODER's steps and d_gaze [n_frames][4] (or
+ * NULL) the gaze rectangles, as svc_hip_decode_levels_frames states them.
+ *
+ * d_status [n_frames] u32 is the UNDELTA call's status (the frame's own unpack code, else 0x100 |
+ * its predecessor's, down to the next key frame), which says more than the decode call's view of a
+ * failed frame's 64 zero bytes.
+ *
+ * Chaining: d_last (NULL with last_capacity 0 and d_last_bytes NULL: not wanted) receives the
+ * reconstructed SVCQ frame of frame n_frames - 1, byte for byte output frame n_frames - 1 of the
+ * undelta call (64 zero bytes if that frame failed; a set bit of level 0 is cleared), and
+ * *d_last_bytes its length.  last_capacity must be at least svc_hip_levels_max_bytes(1, ...).  The next
+ * call takes it as d_prev, so a player ping-pongs two one-frame buffers, and a chain may move freely
+ * between this call and the undelta call.  d_last must not overlap d_prev or d_frames: this is NOT
+ * checked.  Nothing is written past *d_last_bytes.
+ *
+ * Geometry: square 8x8 or 16x16 tiles and a width of whole 16-pixel segments, as
+ * svc_hip_decode_levels_frames (else SVC_ERR_UNSUPPORTED and a workspace of 0).  Checked in that
+ * call's order, for any n_frames: geometry, steps (0: SVC_ERR_INVALID_ARG), display size, limits,
+ * workspace, then last_capacity where d_last is given; n_frames == 0 then returns SVC_OK and leaves
+ * d_last untouched; then pointers (streams, d_prev, d_last and workspace 16-byte aligned, offsets and
+ * d_last_bytes 8-byte, the rest 4-byte).  Only enqueues work; the number of launches does not depend
+ * on n_frames: one workgroup carries a group of tiles through all frames of the call.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_decode_delta_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                     uint32_t block_w, uint32_t block_h,
+                                                     uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                       const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                       const uint8_t* d_prev /* one reconstructed SVCQ frame, the predecessor of frame 0; NULL: frame 0 is a key frame */,
+                                       uint64_t prev_bytes,
+                                       const uint32_t* d_key /* [n_frames], as the delta call took it */,
+                                       uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                       uint32_t mv_block_w, uint32_t mv_block_h,
+                                       uint32_t fg_step, uint32_t bg_step,
+                                       const uint32_t* d_gaze /* [n_frames][4] or NULL */,
+                                       uint8_t* d_workspace, uint64_t workspace_bytes,
+                                       float* d_rec /* [n_frames][frame_h][frame_w][3] */,
+                                       uint8_t* d_display /* [n_frames][display_h][display_w][3] or NULL */,
+                                       uint32_t display_w, uint32_t display_h,
+                                       uint8_t* d_last /* the last frame, reconstructed; NULL: not wanted */,
+                                       uint64_t last_capacity,
+                                       uint64_t* d_last_bytes /* [1] */,
+                                       uint32_t* d_status /* [n_frames] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes
  * of svc_hip_serialize_frames / svc_hip_dct_records_frames and of the reference's encoder): the
  * reference's Decoder::operator() (libs/decoder.cpp:168-210) without the GUI.  Its records hold

@@ -38,6 +38,9 @@ struct Slot {
   DevBuf<uint64_t> enh_off;
   DevBuf<uint32_t> enh_estatus;
   PinBuf<uint32_t> pin_enh_estatus;
+  // DecodeDelta: the batch's key flags
+  PinBuf<uint32_t> pin_key;
+  DevBuf<uint32_t> key;
   uint32_t first = 0, count = 0;
 };
 
@@ -77,6 +80,11 @@ struct StreamDecoder::Impl {
   bool svce = false;        // Decode: the stream is SVCE, decoded to SVCQ in q first
   bool layered = false;     // the buffers are sized for DecodeLayers
   bool enh_svce = false;    // DecodeLayers: the enhancement stream is SVCE, decoded to SVCQ in eq first
+  bool delta = false;       // the buffers are sized for DecodeDelta
+  DevBuf<uint8_t> chain[2]; // DecodeDelta: the last reconstructed frame of a batch, the next batch's frame before (the kernels' stream only)
+  DevBuf<uint64_t> chain_len;     // its length, as the device call writes it ...
+  PinBuf<uint64_t> pin_chain_len; // ... and where the host reads it
+  uint64_t chain_bytes = 0;
   DevBuf<uint8_t> q, ews;   // SVCE: the batch's SVCQ frames and the coder's workspace (the kernels' stream only)
   DevBuf<uint64_t> qoff;
   DevBuf<uint8_t> eq;       // the same for the enhancement stream (one workspace: the two calls follow each other)
@@ -92,15 +100,17 @@ struct StreamDecoder::Impl {
 
   // layers: for DecodeLayers (the workspace of svc_hip_decode_layers_frames, which the reduced call shares; enh_entropy = the enhancement
   // stream is SVCE)
-  void Size(const uint32_t* hdr, bool entropy, bool layers = false, bool enh_entropy = false) {
+  // chained: for DecodeDelta (the workspace of svc_hip_decode_delta_levels_frames and the two frames of the chain)
+  void Size(const uint32_t* hdr, bool entropy, bool layers = false, bool enh_entropy = false, bool chained = false) {
     const uint32_t w = hdr[kHWidth], h = hdr[kHHeight], tw = hdr[kHTileW], th = hdr[kHTileH], mw = hdr[kHMvW], mh = hdr[kHMvH];
     const uint32_t rw = w / c.reduce, rh = h / c.reduce;  // the picture the display pass reads
     const uint32_t want_dw = c.display_w ? c.display_w : rw, want_dh = c.display_h ? c.display_h : rh;
-    if (!wire && entropy == svce && layers == layered && enh_entropy == enh_svce && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
+    if (!wire && entropy == svce && layers == layered && enh_entropy == enh_svce && chained == delta && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
       return;
     pipe->SyncStreams();
-    const uint64_t need_ws = layers ? svc_hip_decode_layers_workspace_bytes(c.batch, w, h, tw, th)
-                                    : svc_hip_decode_levels_workspace_bytes(c.batch, w, h, tw, th);
+    const uint64_t need_ws = chained  ? svc_hip_decode_delta_levels_workspace_bytes(c.batch, w, h, tw, th, mw, mh)
+                             : layers ? svc_hip_decode_layers_workspace_bytes(c.batch, w, h, tw, th)
+                                      : svc_hip_decode_levels_workspace_bytes(c.batch, w, h, tw, th);
     if (!need_ws) Abi(SVC_ERR_UNSUPPORTED, "no decoder for the first frame's geometry");
     if (want_dw > rw || want_dh > rh)
       throw std::runtime_error(c.reduce > 1 ? "svc::StreamDecoder: the display size exceeds the padded frame over reduce"
@@ -116,6 +126,12 @@ struct StreamDecoder::Impl {
     svce = entropy;
     layered = layers;
     enh_svce = enh_entropy;
+    delta = chained;
+    if (chained) {
+      chain_bytes = svc_hip_levels_max_bytes(1, w, h, tw, th, mw, mh);
+      for (auto& b : chain) b.Alloc(kWho, chain_bytes);
+      chain_len.Alloc(kWho, 1); pin_chain_len.Alloc(kWho, 1);
+    }
     wire = false;
     pw = w; ph = h; bw = tw; bh = th; mbw = mw; mbh = mh; dw = want_dw; dh = want_dh;
     disp_bytes = (uint64_t)dw * dh * 3;
@@ -182,6 +198,7 @@ StreamDecoder::StreamDecoder(const StreamDecoderConfig& config) : p_(new Impl) {
     s->pin_estatus.Alloc(kWho, B); s->estatus.Alloc(kWho, B);
     s->pin_enh_off.Alloc(kWho, B + 1); s->enh_off.Alloc(kWho, B + 1);
     s->pin_enh_estatus.Alloc(kWho, B); s->enh_estatus.Alloc(kWho, B);
+    s->pin_key.Alloc(kWho, B); s->key.Alloc(kWho, B);
     m.slots.push_back(std::move(s));
   }
 }
@@ -320,6 +337,76 @@ void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offse
             Hip(hipMemcpyAsync(s.pin_enh_estatus.p, s.enh_estatus.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, so),
                 "hipMemcpyAsync D2H enhancement status");
           return cnt * (m.disp_bytes + (1 + m.svce + m.enh_svce) * sizeof(uint32_t));
+        });
+    first += cnt;
+  }
+  m.Finish(st);
+}
+
+void StreamDecoder::DecodeDelta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, const Gaze& gaze,
+                                const Sink& sink) {
+  Impl& m = *p_;
+  const StreamDecoderConfig& c = m.c;
+  if (c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeDelta does not decode at reduced size (reduce must be 1)");
+  if (n_frames == 0) { m.stats = DecodeStats{}; return; }
+  if (!stream || !offsets) throw std::runtime_error("svc::StreamDecoder: null stream");
+  const uint64_t total = offsets[n_frames];  // the stream's bytes, from offsets[0] on
+  uint32_t hdr[kHeaderWords];
+  FirstHeader(stream, offsets, n_frames, "", hdr);
+  m.Size(hdr, hdr[kHMagic] == kMagicE, false, false, true);
+  const uint32_t B = c.batch;
+
+  DecodeStats st;
+  m.pipe->Begin([&](uint32_t slot) { Deliver(*m.slots[slot], m.dw, m.dh, m.svce, false, st, sink); });
+  uint32_t batch = 0;
+  for (uint32_t first = 0; first < n_frames; ++batch) {
+    const uint32_t cnt = std::min(B, n_frames - first);
+    const uint32_t slot = m.pipe->Acquire();
+    Slot& s = *m.slots[slot];
+    const uint64_t bytes = StageFrames(kWho, m.crew, stream, offsets, total, first, cnt, s.pin_in, s.in, s.pin_off.p);
+    m.StageGaze(s, gaze, first, cnt);
+    for (uint32_t i = 0; i < cnt; ++i) s.pin_key.p[i] = key ? key[first + i] : 0u;  // (frame 0 has no frame before it: a key frame)
+    s.first = first; s.count = cnt;
+    m.pipe->Submit(
+        slot,
+        [&](hipStream_t si) -> uint64_t {
+          Hip(hipMemcpyAsync(s.in.p, s.pin_in.p, bytes, hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D");
+          Hip(hipMemcpyAsync(s.off.p, s.pin_off.p, (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D offsets");
+          Hip(hipMemcpyAsync(s.gaze.p, s.pin_gaze.p, 4 * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D gaze");
+          Hip(hipMemcpyAsync(s.key.p, s.pin_key.p, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, si), "hipMemcpyAsync H2D key flags");
+          return bytes + (cnt + 1) * sizeof(uint64_t) + 5 * cnt * sizeof(uint32_t);
+        },
+        [&](hipStream_t sk) {
+          const uint8_t* qin = s.in.p;
+          const uint64_t* qoff = s.off.p;
+          uint64_t qbytes = bytes;
+          if (m.svce) {  // SVCE -> SVCQ in device scratch, then the SVCQ route unchanged
+            Abi(svc_hip_entropy_decode_frames(s.in.p, bytes, s.off.p, cnt, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh, m.ews.p, m.ews_bytes, m.q.p,
+                                              m.q_bytes, m.qoff.p, s.estatus.p, sk),
+                "svc_hip_entropy_decode_frames");
+            qin = m.q.p; qoff = m.qoff.p; qbytes = m.q_bytes;
+          }
+          // the frame before this batch: the batch before left it in chain[(batch - 1) % 2], and its length is on its way to the host
+          const uint8_t* prev = nullptr;
+          uint64_t prev_bytes = 0;
+          if (batch > 0) {
+            Hip(hipStreamSynchronize(sk), "hipStreamSynchronize");
+            prev = m.chain[(batch - 1) % 2].p;
+            prev_bytes = m.pin_chain_len.p[0];
+          }
+          Abi(svc_hip_decode_delta_levels_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh,
+                                                 c.fg_step, c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh,
+                                                 m.chain[batch % 2].p, m.chain_bytes, m.chain_len.p, s.status.p, sk),
+              "svc_hip_decode_delta_levels_frames");
+          if (first + cnt < n_frames)
+            Hip(hipMemcpyAsync(m.pin_chain_len.p, m.chain_len.p, sizeof(uint64_t), hipMemcpyDeviceToHost, sk), "hipMemcpyAsync D2H chain length");
+        },
+        [&](hipStream_t so) -> uint64_t {
+          Hip(hipMemcpyAsync(s.pin_disp.p, s.disp.p, cnt * m.disp_bytes, hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H display");
+          Hip(hipMemcpyAsync(s.pin_status.p, s.status.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H status");
+          if (m.svce)
+            Hip(hipMemcpyAsync(s.pin_estatus.p, s.estatus.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "hipMemcpyAsync D2H status");
+          return cnt * (m.disp_bytes + (m.svce ? 2 : 1) * sizeof(uint32_t));
         });
     first += cnt;
   }

@@ -47,6 +47,10 @@
 // of levels, and added back up -- the window call's count and scan for the input, then count, scan, frame offsets and write; the undelta's
 // waves each carry one group through all frames of the call (stated at their kernels).
 //
+// decode of a delta stream (svc_hip_decode_delta_levels_frames): the undelta's input and status passes, then one kernel whose workgroups
+// each carry a group of tiles in three planes through all frames -- the undelta's add into levels held in LDS and the decode's passes on
+// them -- and, for the chain's last frame as an SVCQ frame, a scan and a write pass (stated at its kernels).
+//
 // pack of two layers (svc_hip_pack_layers_frames): the pack's count, scan and scatter on raw planes with two quantisations per coefficient,
 // the frame offsets from frame_offsets_kernel with a job per layer (stated at its kernels).
 //
@@ -2088,6 +2092,199 @@ __global__ __launch_bounds__(256) void undelta_kernel(DeltaArgs a, uint32_t cap)
   }
 }
 
+// ---- decode of a delta stream: the undelta and the reconstruction in one kernel (svc_hip_decode_delta_levels_frames; include/svc_hip.h
+// states it) ------------------------------------------------------------------------------------------------------------------------------
+//
+// The passes in front are the undelta's (input, status); its count, scan, offsets and write fall away, since no reconstructed stream is
+// written.  One workgroup of decode_body's shape -- the same tiles in all three planes, thread (t, j) owns coefficient row j of tile t --
+// carries its group through ALL frames of the call.  It holds the three planes' reconstructed levels dense in LDS ([plane][tile][coefficient]
+// u16) with their mask words.  Per frame, every wave reads the plane's mask words of the delta frame (a lane per word) and scans their
+// popcounts itself, so the add needs no barrier: wave w adds words w, w + 4, .. exactly as undelta_kernel does, a lane per coefficient by
+// rank.  After one barrier thread (t, j) reads its row from the held levels -- a plain LDS read where decode_body gathers by rank -- and
+// the passes are idct_core.hpp's.  The int16 level of every coefficient is the one decode_body would gather from the undelta's output, so
+// d_rec has the bits of svc_hip_undelta_levels_frames + svc_hip_decode_levels_frames.
+//
+// d_last, the reconstructed SVCQ frame of the call's last frame: the workgroup stores its mask words at their place, its count per plane
+// and its non-zero levels as one run per (plane, group) at the group's worst-case place in the workspace; decode_delta_last_scan_kernel
+// gives each run its place and the frame its size, decode_delta_last_write_kernel moves the runs (a wave each, store_level_run) and writes
+// header, types and padding.  A last frame that failed is 64 zero bytes.  Every output byte is stored once.
+
+struct DecodeDeltaWs {
+  WinWs in, prev;          // the input passes of the stream and of d_prev
+  uint64_t* prev_offsets;  // [2] 0, prev_bytes
+  uint32_t* prev_code;     // [1] d_prev's unpack code, as its input pass reports it
+  uint32_t* status;        // [n] the final statuses
+  uint32_t *last_cnt, *last_first;  // [groups] the last frame's non-zero levels per group, and their exclusive prefix
+  uint32_t* last_head;     // [2] the last frame's level count and size
+  uint16_t* last_runs;     // [groups][tpg * bw * bh]
+};
+DecodeDeltaWs decode_delta_ws(Carver& c, uint32_t n, uint32_t groups, uint32_t cap) {
+  DecodeDeltaWs s;
+  s.in = window_ws(c, n, groups);
+  const uint32_t one = n ? 1 : 0;  // an empty batch needs no workspace
+  s.prev = window_ws(c, one, groups);
+  s.prev_offsets = c.take<uint64_t>(2 * one);
+  s.prev_code = c.take<uint32_t>(one);
+  s.status = c.take<uint32_t>(n);
+  s.last_cnt = c.take<uint32_t>((uint64_t)one * groups);
+  s.last_first = c.take<uint32_t>((uint64_t)one * groups);
+  s.last_head = c.take<uint32_t>(2 * one);
+  s.last_runs = c.take<uint16_t>((uint64_t)one * groups * cap);
+  return s;
+}
+
+struct DecodeDeltaArgs {
+  DeltaArgs d;           // d.in.out, d.in.out_offsets, d.cnt, d.frame_bytes, d.frame_levels are null: no stream is written
+  const uint32_t* gaze;  // [n][4] or null
+  float* rec;            // [n][h][w][3]
+  float fg, bg;          // the decoder's steps
+  uint8_t* last;         // or null: not wanted
+  uint64_t* last_bytes;
+  uint32_t *last_cnt, *last_first, *last_head;
+  uint16_t* last_runs;
+  uint32_t cap;          // coefficients of a full group: the pitch of last_runs
+};
+
+__device__ __forceinline__ bool bit_of(uint64_t m, uint32_t b) { return (m >> b) & 1u; }
+
+template <int N>
+__global__ __launch_bounds__(256) void decode_delta_kernel(DecodeDeltaArgs args) {
+  constexpr uint32_t kArea = N * N, kWords = kArea / 64, kJobs = kGroupCoeffs / 64;  // a mask word is 64 adjacent held levels
+  constexpr uint32_t kRows = kGroupCoeffs / N;
+  constexpr uint32_t kWaves = kThreads / 64;
+  __shared__ uint16_t held[3][kGroupCoeffs];  // [plane][tile][coefficient]: != 0 exactly where its bit of held_mask is set
+  __shared__ uint64_t held_mask[3][kJobs];
+  __shared__ double rows[kRows * (N + 1)];
+  const DeltaArgs& a = args.d;
+  const Geom& g = a.in.g;
+  const uint32_t gi0 = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t jobs = gr.nt * kWords, per_plane = g.tiles_y * g.gx;
+  const uint32_t t = tid / N, j = tid - t * N;
+  const bool active = t < gr.nt;  // an idle thread stays in every barrier below
+  for (uint32_t k = tid; k < 3 * kGroupCoeffs; k += kThreads) (&held[0][0])[k] = 0;
+  for (uint32_t k = tid; k < 3 * kJobs; k += kThreads) (&held_mask[0][0])[k] = 0;
+  __syncthreads();
+  // frame -1 is d_prev: it is added like a key frame and nothing is decoded for it.  Every condition on a frame is the workgroup's.
+  for (int32_t i = a.prev.in && a.prev.ws.status[0] == kStOk ? -1 : 0; i < (int32_t)a.n; ++i) {
+    const bool seed = i < 0;
+    float* dst = seed ? nullptr : args.rec + (((size_t)i * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3;
+    if (!seed && a.status[i] != kStOk) {  // zeros; the frame is not read, and the next frame that passes is a key frame
+      if (active) {
+#pragma unroll
+        for (int y = 0; y < N; ++y) {
+          float* p = dst + (size_t)y * g.w * 3;
+          p[0] = 0.f; p[1] = 0.f; p[2] = 0.f;
+        }
+      }
+      continue;
+    }
+    const uint8_t* fc = seed ? a.prev.in : a.in.in + a.in.offsets[i];
+    const uint8_t* fp = seed || delta_key(a, (uint32_t)i) ? nullptr : delta_before(a, (uint32_t)i);
+    const bool same_step = fp && lane < gr.nt && tile_step(g, fc, gr, lane) == tile_step(g, fp, gr, lane);
+    const uint64_t predicted_tiles = __ballot(same_step);  // (a group has at most 32 tiles)
+    const uint32_t* first_level = seed ? a.prev.ws.before : a.in.ws.before + (size_t)i * g.groups;
+#pragma unroll
+    for (uint32_t c = 0; c < 3; ++c) {
+      const uint32_t* masks = group_masks(g, fc, c, gr);
+      const uint16_t* lc = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + first_level[c * per_plane + gi0];
+      const uint64_t x = lane < jobs ? load_mask(masks + 2 * lane) : 0ull;
+      const uint32_t first_x = wave_exclusive_scan((uint32_t)__popcll(x));
+      for (uint32_t k = wave; k < jobs; k += kWaves) {
+        const uint64_t xk = readlane64(x, k), wk = readlane64(held_mask[c][k], 0);
+        if ((xk | wk) == 0) continue;  // (the whole wave) nothing to add and nothing held: the word stays 0
+        const uint32_t ax = (uint32_t)__builtin_amdgcn_readlane((int)first_x, k), slot = k * 64 + lane;
+        const uint16_t d = bit_of(xk, lane) ? lc[ax + lane_rank(xk)] : (uint16_t)0;
+        const uint16_t p = bit_of(predicted_tiles, k / kWords) && bit_of(wk, lane) ? held[c][slot] : (uint16_t)0;
+        const uint16_t lv = (uint16_t)(d + p);
+        if (bit_of(xk | wk, lane)) held[c][slot] = lv;  // (no bit is set past the tile's area: such a frame fails)
+        const uint64_t mk = __ballot(lv != 0);
+        if (lane == 0) held_mask[c][k] = mk;
+      }
+    }
+    __syncthreads();
+    if (seed) continue;
+    float enc = 0.f, dec = 1.f;
+    if (active) {
+      const uint32_t* hdr = reinterpret_cast<const uint32_t*>(fc);
+      const uint32_t type = tile_type(g, hdr + kHeaderWords, gr, t);
+      const bool in_gaze = gazed(args.gaze, (uint32_t)i, gr.x0 + t * N, gr.y0);
+      enc = (float)(type == 0 ? hdr[kHBgStep] : hdr[kHFgStep]);
+      dec = in_gaze ? 1.f : (type == 0 ? args.bg : args.fg);
+    }
+    float out[3][N];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (active) {
+        const uint16_t* row = &held[c][t * kArea + j * N];
+        float v[N];
+#pragma unroll
+        for (int q = 0; q < N; ++q) v[q] = (float)(int16_t)row[q] * enc;
+        invert_row<N>(v, dec, rows, t, j);
+      }
+      __syncthreads();
+      if (active) invert_column<N>(rows, t, j, out[c]);
+      if (c < 2) __syncthreads();  // the next plane reuses rows; the next frame writes them only after its own barrier
+    }
+    if (active) store_bgr_column<N>(dst, g.w, out);
+  }
+  if (!args.last || a.status[a.n - 1] != kStOk) return;  // (the whole workgroup)
+  __syncthreads();
+#pragma unroll
+  for (uint32_t c = 0; c < 3; ++c) {
+    const uint32_t gi = c * per_plane + gi0;
+    const uint64_t m = lane < jobs ? held_mask[c][lane] : 0ull;
+    const uint32_t pc = (uint32_t)__popcll(m), first = wave_exclusive_scan(pc);
+    uint16_t* run = args.last_runs + (size_t)gi * args.cap;
+    for (uint32_t k = wave; k < jobs; k += kWaves) {
+      const uint64_t mk = readlane64(m, k);
+      const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)first, k);
+      if (bit_of(mk, lane)) run[at + lane_rank(mk)] = held[c][k * 64 + lane];
+    }
+    if (wave == 0) {
+      uint32_t* masks_out = group_masks(g, args.last, c, gr);
+      if (lane < jobs) store_mask(masks_out + 2 * lane, m);
+      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)(first + pc), 63);
+      if (lane == 0) args.last_cnt[gi] = total;
+    }
+  }
+}
+
+// one workgroup: the last frame's runs get their places, the frame its level count and size; a failed frame is 64 zero bytes
+__global__ __launch_bounds__(256) void decode_delta_last_scan_kernel(DecodeDeltaArgs args) {
+  __shared__ uint32_t red[kThreads / 64];
+  const DeltaArgs& a = args.d;
+  const Geom& g = a.in.g;
+  if (a.status[a.n - 1] != kStOk) {  // (the whole workgroup)
+    if (threadIdx.x < kHeaderWords) reinterpret_cast<uint32_t*>(args.last)[threadIdx.x] = 0;
+    if (threadIdx.x == 0) *args.last_bytes = kHeaderBytes;
+    return;
+  }
+  const uint32_t carry = scan_counts(args.last_cnt, args.last_first, g.groups, 0, red);
+  if (threadIdx.x == 0) {
+    const uint32_t bytes = (uint32_t)up16(g.levels_off + 2ull * carry);
+    args.last_head[0] = carry;
+    args.last_head[1] = bytes;
+    *args.last_bytes = bytes;
+  }
+}
+
+// a wave per group: its run of levels to its place in d_last; the first workgroup also writes header, types and padding
+__global__ __launch_bounds__(256) void decode_delta_last_write_kernel(DecodeDeltaArgs args) {
+  const DeltaArgs& a = args.d;
+  const Geom& g = a.in.g;
+  if (a.status[a.n - 1] != kStOk) return;
+  const uint32_t gi = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (gi < g.groups)
+    store_level_run(args.last_runs + (size_t)gi * args.cap, args.last_cnt[gi],
+                    reinterpret_cast<uint16_t*>(args.last + g.levels_off) + args.last_first[gi]);
+  if (blockIdx.x != 0) return;
+  const uint8_t* fc = a.in.in + a.in.offsets[a.n - 1];
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(fc);
+  split_frame_edges(g, fc, args.last, src[kHFgStep], src[kHBgStep], args.last_head[0], args.last_head[1]);
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -2395,6 +2592,29 @@ int split_levels(const char* what, SplitArgs a, const svc_step_pair* ladder, uin
   return check_launch(what, "write");
 }
 
+// What the delta call, the undelta call and the decode of a delta stream begin with: the input pass of the stream and of the frame before
+// it -- the window call's count and scan with every tile kept (d_status holds the frames' own codes until the status kernel writes the
+// final ones) -- then the status kernel, chained for the two calls whose predecessor is a reconstructed frame.  Six launches, three
+// without d_prev.
+int enqueue_delta_input(const char* what, const DeltaArgs& a, bool chain, uint64_t prev_bytes, hipStream_t s) {
+  int rc;
+  const uint32_t wave_blocks = div_up(a.in.g.groups, kThreads / 64);
+  if (a.prev.in) {
+    hipLaunchKernelGGL(delta_prev_kernel, dim3(1), dim3(1), 0, s, const_cast<uint64_t*>(a.prev.offsets), prev_bytes);
+    if ((rc = check_launch(what, "offsets of the frame before"))) return rc;
+  }
+  for (const WindowArgs* in : {&a.prev, &a.in}) {
+    if (!in->in) continue;
+    hipLaunchKernelGGL(window_count_kernel, dim3(wave_blocks, in->n_in), dim3(kThreads), 0, s, *in);
+    if ((rc = check_launch(what, in == &a.in ? "input count" : "input count of the frame before"))) return rc;
+    hipLaunchKernelGGL(window_scan_kernel, dim3(in->n_in), dim3(kThreads), 0, s, *in);
+    if ((rc = check_launch(what, "input scan"))) return rc;
+  }
+  if (chain) hipLaunchKernelGGL(delta_status_kernel<true>, dim3(1), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(delta_status_kernel<false>, dim3(1), dim3(64), 0, s, a);
+  return check_launch(what, "status");
+}
+
 // Both directions of the delta, checked in the window call's order: geometry, limits, workspace, output capacity; n_frames == 0 then
 // returns SVC_OK; then pointers.  Ten launches, whatever n_frames (seven without d_prev).
 int delta_levels(const char* what, bool undo, const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n,
@@ -2419,22 +2639,7 @@ int delta_levels(const char* what, bool undo, const uint8_t* d_frames, uint64_t 
                     d_key, n, ws.cnt, ws.frame_bytes, ws.frame_levels, ws.status};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t wave_blocks = div_up(g.groups, kThreads / 64);
-  // the input pass of the stream and of the frame before it: the window call's count and scan with every tile kept (d_status holds the
-  // frames' own codes until the status kernel writes the final ones)
-  if (d_prev) {
-    hipLaunchKernelGGL(delta_prev_kernel, dim3(1), dim3(1), 0, s, ws.prev_offsets, prev_bytes);
-    if ((rc = check_launch(what, "offsets of the frame before"))) return rc;
-  }
-  for (const WindowArgs* in : {&a.prev, &a.in}) {
-    if (!in->in) continue;
-    hipLaunchKernelGGL(window_count_kernel, dim3(wave_blocks, in->n_in), dim3(kThreads), 0, s, *in);
-    if ((rc = check_launch(what, in == &a.in ? "input count" : "input count of the frame before"))) return rc;
-    hipLaunchKernelGGL(window_scan_kernel, dim3(in->n_in), dim3(kThreads), 0, s, *in);
-    if ((rc = check_launch(what, "input scan"))) return rc;
-  }
-  if (undo) hipLaunchKernelGGL(delta_status_kernel<true>, dim3(1), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(delta_status_kernel<false>, dim3(1), dim3(64), 0, s, a);
-  if ((rc = check_launch(what, "status"))) return rc;
+  if ((rc = enqueue_delta_input(what, a, undo, prev_bytes, s))) return rc;
   // the scan of the band call on this call's counts and final statuses
   WindowArgs counted = a.in;
   counted.ws.status = ws.status;
@@ -2977,6 +3182,65 @@ int svc_hip_undelta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes
                                   void* stream) {
   return delta_levels("undelta_levels", true, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w, frame_h,
                       block_w, block_h, mv_block_w, mv_block_h, d_workspace, workspace_bytes, d_out, out_capacity, d_out_offsets, d_status, stream);
+}
+
+uint64_t svc_hip_decode_delta_levels_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                     uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_decode_geom("decode_delta_levels_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("decode_delta_levels_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  return layout_bytes(decode_delta_ws, n_frames, g.groups, g.tpg * block_w * block_h);
+}
+
+// Checked in the order of svc_hip_decode_levels_frames, then last_capacity; n_frames == 0 then returns SVC_OK; then pointers.  Four launches
+// without d_prev, d_last and display, ten with all three, whatever n_frames.
+int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                       const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t frame_w, uint32_t frame_h,
+                                       uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                       uint32_t bg_step, const uint32_t* d_gaze, uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec,
+                                       uint8_t* d_display, uint32_t display_w, uint32_t display_h, uint8_t* d_last, uint64_t last_capacity,
+                                       uint64_t* d_last_bytes, uint32_t* d_status, void* stream) {
+  const char* what = "decode_delta_levels";
+  int rc = validate_decode_geom(what, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  bool display;
+  if ((rc = validate_steps_display(what, fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
+  if ((rc = validate_limits(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  const uint32_t cap = g.tpg * block_w * block_h;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(decode_delta_ws, n_frames, g.groups, cap)))) return rc;
+  if (d_last && (rc = require_capacity(what, "last frame", last_capacity,
+                                       frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes)))
+    return rc;
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_rec && d_status, "%s: null pointer", what);
+  SVC_REQUIRE((d_last != nullptr) == (d_last_bytes != nullptr), "%s: the last frame and its length go together", what);
+  if ((rc = validate_display_buffer(what, display, d_display))) return rc;
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_prev, 16) && aligned(d_last, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_last_bytes, 8) && aligned(d_key, 4) && aligned(d_gaze, 4) && aligned(d_rec, 4) && aligned(d_status, 4),
+              "%s: streams, the frame before, the last frame and workspace must be 16-byte aligned, offsets and the last frame's length "
+              "8-byte, key flags, gaze, output and status 4-byte",
+              what);
+  const DecodeDeltaWs ws = carve(d_workspace, decode_delta_ws, n_frames, g.groups, cap);
+  const DecodeDeltaArgs a{{{g, d_frames, stream_bytes, d_frame_offsets, n_frames, nullptr, nullptr, nullptr, nullptr, d_status, ws.in},
+                           {g, d_prev, prev_bytes, ws.prev_offsets, 1, nullptr, nullptr, nullptr, nullptr, ws.prev_code, ws.prev},
+                           d_key, n_frames, nullptr, nullptr, nullptr, ws.status},
+                          d_gaze, d_rec, (float)fg_step, (float)bg_step, d_last, d_last_bytes, ws.last_cnt, ws.last_first, ws.last_head,
+                          ws.last_runs, cap};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = enqueue_delta_input(what, a.d, true, prev_bytes, s))) return rc;
+  const dim3 chains(g.tiles_y * g.gx);
+  if (block_w == 8) hipLaunchKernelGGL(decode_delta_kernel<8>, chains, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL(decode_delta_kernel<16>, chains, dim3(kThreads), 0, s, a);
+  if (d_last) {
+    if ((rc = check_launch(what, "reconstruction"))) return rc;
+    hipLaunchKernelGGL(decode_delta_last_scan_kernel, dim3(1), dim3(kThreads), 0, s, a);
+    if ((rc = check_launch(what, "scan of the last frame"))) return rc;
+    hipLaunchKernelGGL(decode_delta_last_write_kernel, dim3(div_up(g.groups, kThreads / 64)), dim3(kThreads), 0, s, a);
+  }
+  return finish_with_display(what, d_last ? "write of the last frame" : "reconstruction", display, d_rec, d_display, n_frames, frame_w,
+                             frame_h, display_w, display_h, s);
 }
 
 uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,

@@ -18,6 +18,14 @@
   python tools/decode_probe.py layers-reduced-rate   tests/dropin/stream_layers_main writes the 65-frame clip as two layers, plain and
                                          entropy-coded; tests/dropin/stream_layers_reduced_main decodes them at reduce r and, as the full
                                          route, at reduce 1 with the display (W / r, H / r) (PCIe included)
+  python tools/decode_probe.py delta [C3|C5]   one batch of 16 stored at (1, 1) and at (1, 640) and coded frame against frame, with a key
+                                         frame every 16 and with none (the frame before the batch given), in one process: the fused
+                                         svc_hip_decode_delta_levels_frames against svc_hip_undelta_levels_frames +
+                                         svc_hip_decode_levels_frames, against the decode alone on the undelta'd stream, and with and without
+                                         d_last, alternating, device events, the median of three windows; the routes' rec compared
+  python tools/decode_probe.py delta-rate   `rate`'s stream and its delta stream (a key frame every 16) through
+                                         tests/dropin/stream_decode_main (Decode) and tests/dropin/stream_delta_main (DecodeDelta), PCIe
+                                         included, alternating
 """
 import os
 import subprocess
@@ -312,6 +320,127 @@ def layers_reduced_rate() -> None:
                             sys.exit(1)
 
 
+def delta() -> None:
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native, pipeline
+    cfg = {"C3": configs.C3, "C5": configs.C5}[sys.argv[2] if len(sys.argv) > 2 else "C3"]
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    clip = synth.SynthClip(cfg.width, cfg.height, n + 2, cfg.seed, device=dev)
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(n + 2)]).contiguous()
+    enc = pipeline.ClipEncoder(cfg, n + 2, dev)
+    enc.load_frames(list(frames))
+    enc.step()
+    torch.cuda.synchronize()
+    bgr, types = frames[1:].contiguous(), enc.types.clone()  # n + 1 encoded frames: the frame before the batch, then the batch
+
+    def timed(fn, reps=20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def fmt(t):
+        return f"{np.median(t):.3f} (min {min(t):.3f}, max {max(t):.3f})"
+
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    back, bo = torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ws_u = torch.empty(native.undelta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_x = torch.empty(native.decode_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    ws_f = torch.empty(native.decode_delta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    rec, rec2 = (torch.empty((n, ph, pw, 3), dtype=torch.float32, device=dev) for _ in range(2))
+    last = torch.empty(native.levels_max_bytes(1, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    st, st2 = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}; ms per call of {n} frames, device events over 20 back-to-back calls, the median of "
+          f"three such windows per route, the routes alternating; workspace of the fused call {ws_f.numel() / 1e6:.1f} MB", flush=True)
+    for steps in ((1, 1), (1, 640)):
+        out, offs = native.dct_pack_levels_frames(bgr, block, types, mv, *steps)
+        torch.cuda.synchronize()
+        o = offs.cpu().tolist()
+        prev, stream, so = out[:o[1]].clone(), out[o[1]:o[-1]].clone(), (offs[1:] - offs[1]).contiguous()
+        for name, keys, before in (("a key frame every 16", [1] + [0] * (n - 1), None), ("no key frame", None, prev)):
+            d, do, dst = native.delta_levels_frames(stream, so, pw, ph, block, mv, prev=before, key=keys)
+            torch.cuda.synchronize()
+            assert not dst.any()
+            d = d[:int(do[-1])].clone()
+
+            def two():
+                native.undelta_levels_frames(d, do, pw, ph, block, mv, prev=before, key=keys, out=back, out_offsets=bo, workspace=ws_u, status=st2)
+                native.decode_levels_frames(back, bo, pw, ph, block, mv, 1, 640, rec=rec2, workspace=ws_x)
+
+            def decode_alone():  # on the stream the undelta left in `back`
+                native.decode_levels_frames(back, bo, pw, ph, block, mv, 1, 640, rec=rec2, workspace=ws_x)
+
+            def fused():
+                native.decode_delta_levels_frames(d, do, pw, ph, block, mv, 1, 640, prev=before, key=keys, rec=rec, last=last, workspace=ws_f,
+                                                  status=st)
+
+            def fused_no_last():
+                native.decode_delta_levels_frames(d, do, pw, ph, block, mv, 1, 640, prev=before, key=keys, rec=rec, workspace=ws_f, status=st)
+
+            for _ in range(2):
+                two(), fused(), fused_no_last(), decode_alone()
+            torch.cuda.synchronize()
+            assert not st.any() and not st2.any() and torch.equal(rec.view(torch.int32), rec2.view(torch.int32)), "the routes differ"
+            assert torch.equal(back[:stream.numel()], stream)
+            t = {k: [] for k in ("two", "fused", "no_last", "alone")}
+            for _ in range(3):
+                t["two"].append(timed(two))
+                t["fused"].append(timed(fused))
+                t["alone"].append(timed(decode_alone))
+                t["no_last"].append(timed(fused_no_last))
+            m = {k: float(np.median(v)) for k, v in t.items()}
+            print(f"stored at {steps}, {name} ({d.numel() / n / 1e6:.3f} MB per delta frame): undelta + decode {fmt(t['two'])}; "
+                  f"svc_hip_decode_delta_levels_frames {fmt(t['fused'])} = {m['fused'] / m['two']:.2f}x of the two calls, "
+                  f"{m['fused'] / m['alone']:.2f}x of the decode alone {fmt(t['alone'])}; without d_last {fmt(t['no_last'])}", flush=True)
+
+
+def delta_rate() -> None:
+    """DecodeDelta against Decode on the same clip's plain stream, PCIe included: `rate`'s 64 frames, their delta stream made on the device."""
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native
+    n = 65
+    m = n - 1
+    pw, ph = CFG.padded
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    here = os.path.join(ROOT, "tests", "dropin")
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        prefix = _stored_stream(d, n)
+        big = torch.from_numpy(np.fromfile(prefix + ".big", np.uint8)).cuda()
+        offs = torch.from_numpy(np.fromfile(prefix + ".offsets", np.uint64).astype(np.int64)).cuda()
+        keys = [int(i % 16 == 0) for i in range(m)]
+        diff, do, st = native.delta_levels_frames(big, offs, pw, ph, CFG.dct_block, CFG.mv_block, key=keys)
+        torch.cuda.synchronize()
+        assert not st.any()
+        dprefix = os.path.join(d, "delta")
+        diff[:int(do[-1])].cpu().numpy().tofile(dprefix + ".big")
+        do.cpu().numpy().astype(np.uint64).tofile(dprefix + ".offsets")
+        print(f"{m} frames: plain stream {big.numel() / m / 1e6:.3f} MB per frame, delta stream (a key frame every 16) {int(do[-1]) / m / 1e6:.3f}",
+              flush=True)
+        del big, diff
+        key_file, gaze = os.path.join(d, "key.txt"), os.path.join(d, "gaze.txt")
+        with open(key_file, "w") as f:
+            f.write("".join(f"{k}\n" for k in keys))
+        with open(gaze, "w") as f:
+            for i in range(m):
+                f.write(f"{(60 + 29 * i) % CFG.width} {(40 + 17 * i) % CFG.height}\n")
+        size = [str(CFG.width), str(CFG.height)]
+        for turn in range(3):  # alternating, every run printed: the spread is part of the result
+            for name, args in (("stream_decode_main", [prefix, str(m), *size, gaze, "16", "-"]),
+                               ("stream_delta_main", [dprefix, str(m), *size, gaze, key_file, "16", "3", "1", "-"])):
+                p = subprocess.run([os.path.join(here, name), *args], capture_output=True, text=True, timeout=300)
+                print(f"== {name} batch 16, run {turn} (exit {p.returncode})\n{p.stdout.strip()}\n{p.stderr.strip()}", flush=True)
+                if p.returncode != 0:
+                    sys.exit(1)
+
+
 if __name__ == "__main__":
     {"rate": rate, "kernels": kernels, "reduced": reduced, "reduced-rate": reduced_rate, "layers-reduced": layers_reduced,
-     "layers-reduced-rate": layers_reduced_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
+     "layers-reduced-rate": layers_reduced_rate, "delta": delta, "delta-rate": delta_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
