@@ -1,0 +1,663 @@
+"""Every stream entry point once on a batch whose frame offsets pass 2^32 and whose frame count is some seventy trips of 256 frames.
+
+The other files pin each kernel at the smallest geometry where its work split changes; none of them gives a stream call a byte offset
+of 2^32 or more, and only tests/test_gpu_stream_offsets.py takes three of the calls past one 256-frame trip.  A `uint32_t` offset or
+product in one of the stream kernels would give right bytes in all of them and wrong bytes for a stored clip.  Here:
+
+ * the geometry is 256 x 256 with 16 x 16 MV blocks and 8 x 8 tiles (G8); the decoders and the forms that transform B,G,R frames, whose
+   kernels are instantiated per tile size, also run with 16 x 16 tiles (G16).  These are the smallest geometries at which n <= 65535
+   frames reach 2^32 bytes and the numpy statements stay cheap;
+ * the input is a cycle of k = 4 frames of layers.write_frame at steps (1, 1) -- two different frames with every level set, one at
+   density 0.3, one without a level -- repeated on the device (tests/helpers/periodic.py); n is chosen per case so that, on the input and,
+   wherever the output gets there, on the output, the offsets alone show a frame that straddles 2^32, two whole cycles above it and
+   n > 256: asserted before the call;
+ * every byte output is compared exactly with the call's numpy statement (layers.py, entropy.py, wire.py) on the 2k-frame prefix, whose
+   frames [k, 2k) are the period: all n + 1 offsets on the host, the stream on the device, cycle against cycle; status and choice whole.
+   Float outputs (rec, planes) and display are bit for bit the same call's output on the 2k-frame prefix, extended periodically -- what
+   that short call computes is pinned by tests/test_gpu_transform_exact.py and the decoders' own files.  The forms that transform B,G,R
+   frames have no numpy statement: their period is the numpy writer's (tests/test_levels_host.py) on the planes the transform kernels
+   give for the prefix;
+ * the window, band and split calls and the SVCE window call also run as a viewer is served: n_out = 16 frames named by d_src -- stored
+   frame 0, the frame that straddles 2^32, its neighbours, the last cycle, the last frame -- compared with the numpy statement on those
+   frames copied back.  svc_hip_window_entropy_frames runs only so: its workspace for n_out = n is 14 GiB.
+
+Reduced, for memory: svc_hip_pack_layers_frames and svc_hip_pack_levels_budget_frames, which pack raw planes, cross 2^32 on the input
+side only (f * plane stride) -- for their streams to cross as well they would need 20 GB of planes and 11 GB of capacity per output;
+svc_hip_dct_pack_layers_frames runs past four trips of 256 frames only -- at the frame count where anything of it crosses 2^32 its
+workspace is 11 GiB beside two outputs of 5.6 GiB capacity.  Not here: the two drains (svc_hip_levels_drain, svc_hip_entropy_drain)
+would need 4 GiB of page-locked host memory; and flat indices past 2^32 COEFFICIENTS, which would need 8.6 GB of levels.
+
+Nothing large goes to the host.  An output's capacity must be the worst case of n frames and the cycle's frames are three fifths of that on
+average, so a case holds more than its streams: the peak is 21 GiB (svc_hip_decode_layers_frames: two streams and rec).
+
+Every case prints a line `LARGE <case> seconds=... peak_GiB=... n=... in_max=... out_max=...` (pytest -rP shows it)."""
+import time
+
+import numpy as np
+import pytest
+import torch
+
+from scalable_video_codec_amd import entropy, layers, wire
+from scalable_video_codec_amd import native as nat
+from tests.helpers import periodic as pd
+from tests.test_gpu_dct_pack import _content, _types
+from tests.test_gpu_decode_levels import _rects
+from tests.test_levels_budget_host import frame_bytes, select
+from tests.test_levels_host import write_frame, write_frames
+from tests.test_pack_layers_host import random_planes
+from tests.test_window_levels_host import geom_dict, random_levels, random_types
+
+pytestmark = pytest.mark.gpu
+
+W = H = 256
+MV = (16, 16)
+K = 4
+G8 = (W, H, (8, 8), MV)
+G16 = (W, H, (16, 16), MV)
+GEOMS = [G8, G16]
+DEC = (3, 17)       # the decoders' steps
+DISPLAY = (64, 64)
+COARSE = (255, 257)  # base steps over the fine step 1: the base keeps all but the levels below 128, the residual all but one in 255
+# by cycle position: whole-frame and partial windows alternate; the bands partition nothing, they only differ
+WINDOWS = [(0, 0, W, H), (8, 16, 232, 224), (0, 0, W, H), (16, 8, 104, 200)]
+BANDS = [(0, 0, 8, 8), (2, 2, 8, 8), (0, 0, 8, 4), (0, 0, 4, 8)]
+GAZE = [_rects(6, W, H)[i] for i in (1, 2, 3, 0)]  # the frame, a rectangle, one that runs past the frame, none
+FIG = {}
+DEV = "cuda"
+
+
+def _gid(g):
+    return f"tile{g[2][0]}"
+
+
+def _rows(rows, reps=2):
+    return np.array(list(rows) * reps, np.uint32)
+
+
+def _cycle(geom):
+    rng = np.random.default_rng(2 ** 32 % 1009 + geom[2][0])
+    w, h, tile, mv = geom
+    return [layers.write_frame(geom_dict(*geom), random_types(rng, w, h, mv), random_levels(rng, w, h, d), 1, 1) for d in (1.0, 1.0, 0.3, 0.0)]
+
+
+class Source:
+    """A periodic stream given by its 2k-frame prefix; its n-frame form is made on the device and held until release()."""
+
+    def __init__(self, data, offs):
+        self.data = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
+        self.offs = np.asarray(offs).astype(np.int64)
+        assert self.offs.size == 2 * K + 1 and self.offs[-1] == self.data.size
+        self.cycle_bytes = int(self.offs[2 * K] - self.offs[K])
+        self.held = None
+
+    def prefix(self):
+        return self.data, self.offs.astype(np.uint64)
+
+    def prefix_dev(self):
+        return torch.from_numpy(self.data.copy()).to(DEV), torch.from_numpy(self.offs).to(DEV)
+
+    def take(self, n, restarts=(0,)):
+        """-> (stream u8 of exactly offsets[n] bytes, offsets (n + 1,) i64 on the device, the offsets on the host)."""
+        exp = pd.Periodic(self.data, self.offs, K, n, restarts)
+        restarts = tuple(restarts)
+        if self.held is None or self.held[1] != restarts or (self.held[0] < n if restarts == (0,) else self.held[0] != n):
+            self.release()
+            self.held = (n, restarts, exp.materialize(DEV))
+        return self.held[2][:int(exp.offsets[-1])], torch.from_numpy(exp.offsets).to(DEV), exp.offsets
+
+    def release(self):
+        self.held = None
+        torch.cuda.empty_cache()
+
+
+class Sources:
+    """The module's big inputs, each built once per geometry: the SVCQ cycle and what the numpy statements make of its prefix.  The SVCQ
+    stream of one geometry stays on the device from case to case; everything else goes after the case that asked for it."""
+
+    def __init__(self):
+        self.made = {}
+
+    def get(self, kind, geom):
+        if (kind, geom) not in self.made:
+            self.made[kind, geom] = self._make(kind, geom)
+        for (k, g), s in self.made.items():
+            if k == "svcq" and g != geom:
+                s.release()
+        return self.made[kind, geom]
+
+    def _make(self, kind, geom):
+        if kind == "svcq":
+            frames = _cycle(geom)
+            return Source(*layers._join(frames * 2))
+        q = self.get("svcq", geom).prefix()
+        if kind == "svce":
+            return Source(*entropy.encode_frames(*q))
+        if kind == "delta":
+            return Source(*layers.delta_frames(*q))
+        if kind in ("base", "enh"):
+            made = layers.split_frames(*q, 1, *COARSE)
+            return Source(*(made[:2] if kind == "base" else made[2:]))
+        if kind in ("low", "high"):  # a partition of every tile: its upper and its lower four rows
+            return Source(*layers.band_frames(*q, _rows([(0, 0, 8, 4) if kind == "low" else (8, 4, 8, 8)], 2 * K)))
+        if kind == "records":  # fixed-size frames: the wire records without the stream's header
+            rec = np.frombuffer(wire.write_stream(*q), np.uint8)[wire.HEADER_BYTES:]
+            return Source(rec, np.arange(2 * K + 1) * (rec.size // (2 * K)))
+        raise KeyError(kind)
+
+    def release(self, keep=("svcq",)):
+        for (k, g), s in self.made.items():
+            if k not in keep:
+                s.release()
+
+
+@pytest.fixture(scope="module")
+def big(native):
+    s = Sources()
+    yield s
+    s.release(keep=())
+
+
+@pytest.fixture(autouse=True)
+def _figures(request, native, big):
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    FIG.clear()
+    t0 = time.perf_counter()
+    yield
+    torch.cuda.synchronize()
+    print(f"LARGE {request.node.name} seconds={time.perf_counter() - t0:.2f} peak_GiB={torch.cuda.max_memory_allocated() / 2 ** 30:.2f} "
+          + " ".join(f"{k}={v}" for k, v in FIG.items()))
+    big.release()
+
+
+def _crossed(side, offs):
+    """The case's preconditions on one side, before the call; the highest offset goes into the case's line."""
+    s = pd.crossing(offs, K)
+    FIG[f"{side}_max"] = int(np.asarray(offs)[-1])
+    return s
+
+
+def _frames_for(*cycle_bytes):
+    n = pd.frames_to_cross(min(cycle_bytes), K)
+    assert 256 < n <= 65535
+    FIG["n"] = n
+    return n
+
+
+def _key_frame(n, *offsets):
+    """The start of the last whole cycle: above 2^32 in all the given offsets."""
+    r = (n // K - 1) * K
+    assert all(o[r] > pd.WRAP for o in offsets)
+    keys = torch.zeros(n, dtype=torch.int32, device=DEV)
+    keys[0] = keys[r] = 1
+    return r, keys
+
+
+def _finish(what, out, got_offs, exp, status=None):
+    torch.cuda.synchronize()
+    if status is not None:
+        assert status.numel() == exp.n and int(torch.count_nonzero(status)) == 0, f"{what}: statuses {torch.unique(status).tolist()}"
+    report = pd.mismatch(out, got_offs, exp)
+    assert report is None, f"{what}: {report}"
+
+
+def _one_stream(src, statement, call, what, key=False):
+    """A call from one periodic stream to one stream: statement(prefix bytes, offsets) -> (bytes, offsets); call(stream, offsets, n, keys)
+    -> (out, out offsets, status)."""
+    ref = statement(*src.prefix())[:2]
+    n = _frames_for(src.cycle_bytes, int(ref[1][2 * K]) - int(ref[1][K]))
+    restarts = (0, (n // K - 1) * K) if key else (0,)
+    exp = pd.Periodic(*ref, K, n, restarts)
+    stream, offs, offs_np = src.take(n, restarts if key == "both" else (0,))
+    _crossed("in", offs_np)
+    _crossed("out", exp.offsets)
+    keys = _key_frame(n, offs_np, exp.offsets)[1] if key else None
+    out, got, status = call(stream, offs, n, keys)
+    _finish(what, out, got, exp, status)
+
+
+# ---- SVCQ / SVCE in, one stream out --------------------------------------------------------------------------------------------------------
+
+def test_window_levels_whole_batch(big):
+    w, h, tile, mv = G8
+    _one_stream(big.get("svcq", G8), lambda d, o: layers.window_frames(d, o, _rows(WINDOWS)),
+                lambda s, o, n, _: nat.window_levels_frames(s, o, w, h, tile, mv, window=pd.repeat_rows(WINDOWS, n, DEV)), "window_levels")
+
+
+def test_band_levels_whole_batch(big):
+    w, h, tile, mv = G8
+    _one_stream(big.get("svcq", G8), lambda d, o: layers.band_frames(d, o, _rows(BANDS), _rows(WINDOWS)),
+                lambda s, o, n, _: nat.band_levels_frames(s, o, w, h, tile, mv, band=pd.repeat_rows(BANDS, n, DEV),
+                                                          window=pd.repeat_rows(WINDOWS, n, DEV)), "band_levels")
+
+
+def test_entropy_encode(big):
+    """White noise gives raw chunks, the 0.3 frame coded ones."""
+    w, h, tile, mv = G8
+    _one_stream(big.get("svcq", G8), entropy.encode_frames, lambda s, o, n, _: nat.entropy_encode_frames(s, o, w, h, tile, mv),
+                "entropy_encode")
+
+
+def test_entropy_decode(big):
+    w, h, tile, mv = G8
+    _one_stream(big.get("svce", G8), entropy.decode_frames, lambda s, o, n, _: nat.entropy_decode_frames(s, o, w, h, tile, mv),
+                "entropy_decode")
+
+
+def test_delta_levels(big):
+    """Key flags at frame 0 and at the start of the last whole cycle, above 2^32 on both sides."""
+    w, h, tile, mv = G8
+    _one_stream(big.get("svcq", G8), layers.delta_frames, lambda s, o, n, keys: nat.delta_levels_frames(s, o, w, h, tile, mv, key=keys),
+                "delta_levels", key=True)
+
+
+def test_undelta_levels(big):
+    """The chain runs through every frame of the batch but for the two key frames."""
+    w, h, tile, mv = G8
+    _one_stream(big.get("delta", G8), layers.undelta_frames,
+                lambda s, o, n, keys: nat.undelta_levels_frames(s, o, w, h, tile, mv, key=keys), "undelta_levels", key="both")
+
+
+def test_union_levels(big):
+    """Both inputs from the band statement on a partition; the union is the stored stream again."""
+    w, h, tile, mv = G8
+    a, b, q = big.get("low", G8), big.get("high", G8), big.get("svcq", G8)
+    ref = layers.union_frames(*a.prefix(), *b.prefix())
+    assert bytes(ref[0]) == q.data.tobytes()
+    n = _frames_for(a.cycle_bytes, b.cycle_bytes, q.cycle_bytes)
+    exp = pd.Periodic(*ref, K, n)
+    q.release()  # the expected stream is compared cycle by cycle: the stored one need not lie on the device
+    sa, oa, oa_np = a.take(n)
+    sb, ob, ob_np = b.take(n)
+    _crossed("in", oa_np)
+    _crossed("in_b", ob_np)
+    _crossed("out", exp.offsets)
+    out, got, status = nat.union_levels_frames(sa, oa, sb, ob, w, h, tile, mv)
+    _finish("union_levels", out, got, exp, status)
+
+
+# ---- the split calls: two streams out ----------------------------------------------------------------------------------------------------------
+
+def _split_case(big, statement, call, what, enh_crosses):
+    src = big.get("svcq", G8)
+    ref = statement(*src.prefix())
+    cycles = [int(o[2 * K]) - int(o[K]) for o in (ref[1], ref[3])]
+    n = _frames_for(src.cycle_bytes, *(cycles if enh_crosses else cycles[:1]))
+    base, enh = pd.Periodic(ref[0], ref[1], K, n), pd.Periodic(ref[2], ref[3], K, n)
+    stream, offs, offs_np = src.take(n)
+    _crossed("in", offs_np)
+    _crossed("out", base.offsets)
+    if enh_crosses:
+        _crossed("out_enh", enh.offsets)
+    got = call(stream, offs, n)
+    _finish(what + " base", got[0], got[1], base, got[4])
+    _finish(what + " enhancement", got[2], got[3], enh)
+    return ref, got
+
+
+def test_split_levels_whole_batch(big):
+    w, h, tile, mv = G8
+    _split_case(big, lambda d, o: layers.split_frames(d, o, 1, *COARSE, _rows(WINDOWS)),
+                lambda s, o, n: nat.split_levels_frames(s, o, w, h, tile, mv, 1, *COARSE, window=pd.repeat_rows(WINDOWS, n, DEV)),
+                "split_levels", enh_crosses=True)
+
+
+def test_split_levels_budget(big):
+    """A ladder whose first entry is (1, 1): three frames of the cycle have room for it (their base is the stored frame, their residual
+    nothing); the first dense frame gets exactly its size at the second entry.  The enhancement stays below 2^32."""
+    w, h, tile, mv = G8
+    ladder = [(1, 1), COARSE]
+    frames = pd.split_frames(*big.get("svcq", G8).prefix())
+    tight = len(layers.split_frame(frames[0], 1, *COARSE)[0])
+    assert tight < len(frames[0])
+    budgets = [tight, 1 << 20, 1 << 20, 1 << 20]
+    ref, got = _split_case(big, lambda d, o: layers.split_budget_frames(d, o, 1, ladder, budgets * 2, _rows(WINDOWS)),
+                           lambda s, o, n: nat.split_levels_budget_frames(s, o, w, h, tile, mv, 1, ladder, pd.repeat_rows([[b] for b in budgets],
+                                                                          n, DEV).reshape(-1), window=pd.repeat_rows(WINDOWS, n, DEV)),
+                           "split_levels_budget", enh_crosses=False)
+    assert ref[4].tolist() == [1, 0, 0, 0] * 2
+    n = got[5].numel()
+    assert torch.equal(got[5], pd.repeat_rows([[c] for c in ref[4][:K]], n, DEV).reshape(-1)), "choice"
+
+
+# ---- the serving form: n_out = 16 frames of a stored stream past 2^32 ---------------------------------------------------------------------
+
+def _serving(src, statement, call, what, pairs=1):
+    """statement(small stream, its offsets, src indices into it) and call(stream, offsets, d_src) -> (bytes, offsets) * pairs [+ status]."""
+    n = _frames_for(src.cycle_bytes)
+    stream, offs, offs_np = src.take(n)
+    s = _crossed("in", offs_np)
+    pick = ([0, s, s - 1, s + 1] + list(range((n // K - 1) * K, n)) + [n - 1, s, 0, s + 1, s + 2, 1])[:16]
+    assert len(pick) == 16 and offs_np[pick[4]] > pd.WRAP
+    distinct = sorted(set(pick))
+    small = torch.cat([stream[int(offs_np[f]):int(offs_np[f + 1])] for f in distinct]).cpu().numpy()
+    small_offs = np.concatenate([[0], np.cumsum([offs_np[f + 1] - offs_np[f] for f in distinct])]).astype(np.uint64)
+    want = statement(small, small_offs, [distinct.index(f) for f in pick])
+    got = call(stream, offs, torch.tensor(pick, dtype=torch.int32, device=DEV))
+    torch.cuda.synchronize()
+    assert got[2 * pairs].cpu().tolist() == [0] * 16, f"{what}: status"
+    for p in range(pairs):
+        o = got[2 * p + 1].cpu().tolist()
+        assert o == [int(v) for v in want[2 * p + 1]], f"{what}: offsets of output {p}"
+        assert got[2 * p][:o[-1]].cpu().numpy().tobytes() == bytes(want[2 * p]), f"{what}: bytes of output {p}"
+
+
+WINDOWS16 = [WINDOWS[(i + 1) % K] for i in range(16)]
+
+
+def test_window_levels_serving(big):
+    w, h, tile, mv = G8
+    _serving(big.get("svcq", G8), lambda d, o, src: layers.window_frames(d, o, _rows(WINDOWS16, 1), src),
+             lambda s, o, src: nat.window_levels_frames(s, o, w, h, tile, mv, window=pd.repeat_rows(WINDOWS16, 16, DEV), src=src), "window_levels")
+
+
+def test_band_levels_serving(big):
+    w, h, tile, mv = G8
+    bands = [BANDS[i % K] for i in range(16)]
+    _serving(big.get("svcq", G8), lambda d, o, src: layers.band_frames(d, o, _rows(bands, 1), _rows(WINDOWS16, 1), src),
+             lambda s, o, src: nat.band_levels_frames(s, o, w, h, tile, mv, band=pd.repeat_rows(bands, 16, DEV),
+                                                      window=pd.repeat_rows(WINDOWS16, 16, DEV), src=src), "band_levels")
+
+
+def test_split_levels_serving(big):
+    w, h, tile, mv = G8
+    _serving(big.get("svcq", G8), lambda d, o, src: layers.split_frames(d, o, 1, 3, 5, _rows(WINDOWS16, 1), src),
+             lambda s, o, src: nat.split_levels_frames(s, o, w, h, tile, mv, 1, 3, 5, window=pd.repeat_rows(WINDOWS16, 16, DEV), src=src),
+             "split_levels", pairs=2)
+
+
+def test_window_entropy_serving(big):
+    """The only form of this call here: its workspace for n_out = n is 14 GiB."""
+    w, h, tile, mv = G8
+    _serving(big.get("svce", G8), lambda d, o, src: entropy.window_frames(d, o, _rows(WINDOWS16, 1), src),
+             lambda s, o, src: nat.window_entropy_frames(s, o, w, h, tile, mv, window=pd.repeat_rows(WINDOWS16, 16, DEV), src=src),
+             "window_entropy")
+
+
+# ---- planes and records -------------------------------------------------------------------------------------------------------------------------
+
+def _rows_case(what, n, ref_rows, got_rows, restarts=(0,)):
+    torch.cuda.synchronize()
+    for name, ref, got in zip(what, ref_rows, got_rows):
+        assert got.shape[0] == n
+        report = pd.row_mismatch(got, ref, K, restarts, name)
+        assert report is None, report
+
+
+def _fixed(n, row_bytes, side):
+    """The offsets of n fixed-size rows: f * stride is what passes 2^32 there."""
+    return _crossed(side, np.arange(n + 1, dtype=np.int64) * row_bytes)
+
+
+def _tiled(ref, n):
+    """(2k, ...) rows of a prefix whose two halves are alike -> (n, ...): the period repeated."""
+    assert torch.equal(ref[:K], ref[K:])
+    return ref[K:].repeat(-(-n // K), *([1] * (ref.dim() - 1)))[:n].contiguous()
+
+
+def test_unpack_levels(big):
+    w, h, tile, mv = G8
+    src = big.get("svcq", G8)
+    ref = nat.unpack_levels_frames(*src.prefix_dev(), w, h, tile, mv)
+    n = _frames_for(src.cycle_bytes)
+    stream, offs, offs_np = src.take(n)
+    _crossed("in", offs_np)
+    _fixed(n, 3 * h * w * 4, "out")
+    planes, types, status = nat.unpack_levels_frames(stream, offs, w, h, tile, mv)
+    _rows_case(("plane", "type", "status"), n, ref, (planes, types, status))
+    assert int(torch.count_nonzero(status)) == 0
+
+
+def test_pack_levels(big):
+    """The planes the unpack gives for the host-built frames, repeated: their pack is those frames again (tests/test_gpu_levels.py), so the
+    period is the stored cycle, layers.write_frame's."""
+    w, h, tile, mv = G8
+    src = big.get("svcq", G8)
+    planes, types, status = nat.unpack_levels_frames(*src.prefix_dev(), w, h, tile, mv)
+    assert status.tolist() == [0] * (2 * K)
+    n = _frames_for(src.cycle_bytes)
+    exp = pd.Periodic(*src.prefix(), K, n)
+    src.release()
+    _fixed(n, 3 * h * w * 4, "in")
+    _crossed("out", exp.offsets)
+    out, got = nat.pack_levels_frames(_tiled(planes, n), _tiled(types, n), tile, mv, 1, 1)
+    _finish("pack_levels", out, got, exp)
+
+
+def test_pack_layers(big):
+    """Raw coefficient planes (random_planes of tests/test_pack_layers_host.py at the cycle's densities) at steps (4, 16), every tile
+    enhanced at step 2.  Input side only: f * plane stride passes 2^32 near frame 5 461.  For the enhancement to pass it as well the batch
+    would need some 26 000 frames: 20 GB of planes and two outputs of 11 GB capacity each."""
+    w, h, tile, mv = G8
+    rng = np.random.default_rng(77)
+    planes = np.concatenate([random_planes(rng, 1, w, h, tile, d) for d in (1.0, 1.0, 0.3, 0.0)] * 2)
+    types = np.stack([random_types(rng, w, h, mv) for _ in range(K)] * 2)
+    ref = layers.pack_layers_frames(planes, types, geom_dict(*G8), 4, 16, 2)
+    n = _frames_for(K * 3 * h * w * 4)
+    base, enh = pd.Periodic(ref[0], ref[1], K, n), pd.Periodic(ref[2], ref[3], K, n)
+    big.get("svcq", G8).release()
+    _fixed(n, 3 * h * w * 4, "in")
+    FIG["out_max"], FIG["out_enh_max"] = int(base.offsets[-1]), int(enh.offsets[-1])
+    p = _tiled(torch.from_numpy(planes).to(DEV), n)
+    t = _tiled(torch.from_numpy(types.view(np.int32).reshape(2 * K, -1)).to(DEV), n)
+    got = nat.pack_layers_frames(p, t, tile, mv, 4, 16, 2)
+    _finish("pack_layers base", got[0], got[1], base)
+    _finish("pack_layers enhancement", got[2], got[3], enh)
+
+
+def test_levels_records(big):
+    w, h, tile, mv = G8
+    src, rec = big.get("svcq", G8), big.get("records", G8)
+    stride = rec.cycle_bytes // K
+    assert stride == nat.serialized_frame_bytes(w, h, *tile)
+    n = _frames_for(src.cycle_bytes)
+    stream, offs, offs_np = src.take(n)
+    _crossed("in", offs_np)
+    _fixed(n, stride, "out")
+    records, status = nat.levels_records_frames(stream, offs, w, h, tile, mv)
+    _rows_case(("record",), n, (torch.from_numpy(rec.data.reshape(2 * K, stride).copy()).to(DEV),), (records,))
+    assert int(torch.count_nonzero(status)) == 0
+
+
+def test_records_pack_levels(big):
+    """The records of the cycle (wire.write_stream), packed at steps (1, 3)."""
+    w, h, tile, mv = G8
+    rec = big.get("records", G8)
+    stride = rec.cycle_bytes // K
+    rows = rec.data.reshape(2 * K, stride)
+    ref = wire.pack_records(rows, w, h, tile[0], *mv, 1, 3)
+    assert ref[2].tolist() == [0] * (2 * K)
+    n = _frames_for(int(ref[1][2 * K]) - int(ref[1][K]))
+    exp = pd.Periodic(ref[0], ref[1], K, n)
+    big.get("svcq", G8).release()
+    _fixed(n, stride, "in")
+    _crossed("out", exp.offsets)
+    out, got, status = nat.records_pack_levels_frames(_tiled(torch.from_numpy(rows.copy()).to(DEV), n), w, h, tile[0], mv, 1, 3)
+    _finish("records_pack_levels", out, got, exp, status)
+
+
+# ---- the decoders: a gaze rectangle per frame, rec and a 64 x 64 display -------------------------------------------------------------------
+
+def _decode_case(what, n, ref, got, reduce=1, restarts=(0,)):
+    """ref, got: (rec, display, status) of the prefix and of the batch."""
+    if reduce == 1:
+        _fixed(n, H * W * 3 * 4, "out")
+    _rows_case((f"{what} rec", f"{what} display", f"{what} status"), n, ref[:3], got[:3], restarts)
+    assert int(torch.count_nonzero(got[2])) == 0
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+@pytest.mark.parametrize("reduce", [1, 2])
+def test_decode_levels(big, geom, reduce):
+    w, h, tile, mv = geom
+    src = big.get("svcq", geom)
+    fn = nat.decode_levels_frames if reduce == 1 else (lambda *a, **kw: nat.decode_levels_reduced_frames(*a, reduce=reduce, **kw))
+    ref = fn(*src.prefix_dev(), w, h, tile, mv, *DEC, gaze=_rows(GAZE).astype(np.int32), display=DISPLAY)
+    n = _frames_for(src.cycle_bytes)
+    stream, offs, offs_np = src.take(n)
+    _crossed("in", offs_np)
+    got = fn(stream, offs, w, h, tile, mv, *DEC, gaze=pd.repeat_rows(GAZE, n, DEV), display=DISPLAY)
+    _decode_case("decode_levels", n, ref, got, reduce)
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+def test_decode_entropy(big, geom):
+    w, h, tile, mv = geom
+    src = big.get("svce", geom)
+    ref = nat.decode_entropy_frames(*src.prefix_dev(), w, h, tile, mv, *DEC, gaze=_rows(GAZE).astype(np.int32), display=DISPLAY)
+    n = _frames_for(src.cycle_bytes)
+    big.get("svcq", geom).release()
+    stream, offs, offs_np = src.take(n)
+    _crossed("in", offs_np)
+    got = nat.decode_entropy_frames(stream, offs, w, h, tile, mv, *DEC, gaze=pd.repeat_rows(GAZE, n, DEV), display=DISPLAY)
+    _decode_case("decode_entropy", n, ref, got)
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+def test_decode_delta_levels(big, geom):
+    """Key flags at frame 0 and at the start of the last whole cycle, above 2^32 in the stream and in rec."""
+    w, h, tile, mv = geom
+    src = big.get("delta", geom)
+    ref = nat.decode_delta_levels_frames(*src.prefix_dev(), w, h, tile, mv, *DEC, gaze=_rows(GAZE).astype(np.int32), display=DISPLAY)
+    n = _frames_for(src.cycle_bytes)
+    restarts = (0, (n // K - 1) * K)
+    big.get("svcq", geom).release()
+    stream, offs, offs_np = src.take(n, restarts)
+    _crossed("in", offs_np)
+    _, keys = _key_frame(n, offs_np, np.arange(n + 1, dtype=np.int64) * (h * w * 12))
+    got = nat.decode_delta_levels_frames(stream, offs, w, h, tile, mv, *DEC, key=keys, gaze=pd.repeat_rows(GAZE, n, DEV), display=DISPLAY)
+    _decode_case("decode_delta_levels", n, ref, got, restarts=restarts)
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+@pytest.mark.parametrize("reduce", [1, 2])
+def test_decode_layers(big, geom, reduce):
+    """A base at steps (255, 257) and its enhancement in every tile, from the split statement: both streams pass 2^32."""
+    w, h, tile, mv = geom
+    base, enh = big.get("base", geom), big.get("enh", geom)
+    fn = nat.decode_layers_frames if reduce == 1 else (lambda *a, **kw: nat.decode_layers_reduced_frames(*a, reduce=reduce, **kw))
+    ref = fn(*base.prefix_dev(), *enh.prefix_dev(), w, h, tile, mv, *COARSE, gaze=_rows(GAZE).astype(np.int32), display=DISPLAY)
+    n = _frames_for(base.cycle_bytes, enh.cycle_bytes)
+    big.get("svcq", geom).release()
+    sb, ob, ob_np = base.take(n)
+    se, oe, oe_np = enh.take(n)
+    _crossed("in", ob_np)
+    _crossed("in_enh", oe_np)
+    got = fn(sb, ob, se, oe, w, h, tile, mv, *COARSE, gaze=pd.repeat_rows(GAZE, n, DEV), display=DISPLAY)
+    _decode_case("decode_layers", n, ref, got, reduce)
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+def test_decode_records(big, geom):
+    """f * stride passes 2^32 in the records and in rec."""
+    w, h, tile, mv = geom
+    rec = big.get("records", geom)
+    stride = rec.cycle_bytes // K
+    rows = torch.from_numpy(rec.data.reshape(2 * K, stride).copy()).to(DEV)
+    ref = nat.decode_records_frames(rows, w, h, tile[0], *DEC, gaze=_rows(GAZE).astype(np.int32), display=DISPLAY)
+    n = _frames_for(rec.cycle_bytes, K * h * w * 12)
+    big.get("svcq", geom).release()
+    _fixed(n, stride, "in")
+    _fixed(n, h * w * 12, "out")
+    got = nat.decode_records_frames(_tiled(rows, n), w, h, tile[0], *DEC, gaze=pd.repeat_rows(GAZE, n, DEV), display=DISPLAY)
+    _rows_case(("decode_records rec", "decode_records display"), n, ref, got)
+
+
+# ---- raw planes and B,G,R frames in ------------------------------------------------------------------------------------------------------------
+
+LADDER = [(1, 1), (4, 16)]  # the first entry is (1, 1); one frame a cycle has to step down
+
+
+def test_pack_levels_budget(big):
+    """random_planes at the cycle's densities; the first frame's budget is its size at the second entry, the others have room for the
+    first.  Input side only (see the file's docstring)."""
+    w, h, tile, mv = G8
+    rng = np.random.default_rng(78)
+    planes = np.concatenate([random_planes(rng, 1, w, h, tile, d, steps=(1, 4, 16)) for d in (1.0, 1.0, 0.3, 0.0)] * 2)
+    types = np.stack([random_types(rng, w, h, mv).reshape(-1) for _ in range(K)] * 2)
+    sizes = frame_bytes(planes[0], types[0], *tile, *mv, LADDER)
+    assert sizes[1] < sizes[0]
+    budgets = [int(sizes[1]), 1 << 20, 1 << 20, 1 << 20]
+    choice = select(planes, types, *tile, *mv, LADDER, budgets * 2)
+    assert choice.tolist() == [1, 0, 0, 0] * 2
+    frames = [write_frame(planes[f], types[f], *tile, *mv, *LADDER[int(choice[f])]) for f in range(2 * K)]
+    n = _frames_for(K * 3 * h * w * 4)
+    exp = pd.Periodic(*layers._join(frames), K, n)
+    big.get("svcq", G8).release()
+    _fixed(n, 3 * h * w * 4, "in")
+    FIG["out_max"] = int(exp.offsets[-1])
+    out, got, got_choice = nat.pack_levels_budget_frames(_tiled(torch.from_numpy(planes).to(DEV), n),
+                                                         _tiled(torch.from_numpy(types.view(np.int32)).to(DEV), n), tile, mv, LADDER,
+                                                         pd.repeat_rows([[b] for b in budgets], n, DEV).reshape(-1))
+    _finish("pack_levels_budget", out, got, exp)
+    assert torch.equal(got_choice, pd.repeat_rows([[c] for c in choice[:K]], n, DEV).reshape(-1)), "choice"
+
+
+def _bgr_cycle(geom, seed):
+    """Two frames of random bytes (every level set at step 1), a synthetic frame, a zero frame (no level) -> (2k frames, their types)."""
+    w, h, tile, mv = geom
+    bgr = torch.cat([_content("random", 1, w, h, seed), _content("random", 1, w, h, seed + 1), _content("synth", 1, w, h, seed + 2),
+                     _content("zero", 1, w, h, 0)])
+    return bgr.repeat(2, 1, 1, 1).contiguous(), _types("random", K, w, h, mv, seed).repeat(2, 1).contiguous()
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+def test_dct_pack_levels(big, geom):
+    """Output side: the frames are 196 608 bytes each and stay below 2^32."""
+    w, h, tile, mv = geom
+    bgr, types = _bgr_cycle(geom, 11)
+    q = nat.dct_quant_frames(bgr, tile[0], types, mv[0], 1, 1)
+    ref = write_frames(q.cpu().numpy(), types.cpu().numpy().view(np.uint32), *tile, *mv, 1, 1)
+    n = _frames_for(int(ref[1][2 * K]) - int(ref[1][K]))
+    exp = pd.Periodic(*ref, K, n)
+    big.get("svcq", geom).release()
+    FIG["in_max"] = n * h * w * 3
+    _crossed("out", exp.offsets)
+    out, got = nat.dct_pack_levels_frames(_tiled(bgr, n), tile[0], _tiled(types, n), mv, 1, 1)
+    _finish("dct_pack_levels", out, got, exp)
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+def test_dct_pack_levels_budget(big, geom):
+    """The first random frame's budget is its size at the second entry, the others have room for (1, 1).  Output side."""
+    w, h, tile, mv = geom
+    bgr, types = _bgr_cycle(geom, 12)
+    raw, t = nat.dct_frames(bgr, tile[0]).cpu().numpy(), types.cpu().numpy().view(np.uint32)
+    sizes = frame_bytes(raw[0], t[0], *tile, *mv, LADDER)
+    assert sizes[1] < sizes[0]
+    budgets = [int(sizes[1]), 1 << 20, 1 << 20, 1 << 20]
+    choice = select(raw, t, *tile, *mv, LADDER, budgets * 2)
+    assert choice.tolist() == [1, 0, 0, 0] * 2
+    frames = [bytearray(write_frame(raw[f], t[f], *tile, *mv, *LADDER[int(choice[f])])) for f in range(2 * K)]
+    for fr in frames:  # header word 11 counts the raw coefficients that are not level * step; the fused calls are handed no planes and
+        fr[44:48] = bytes(4)  # write 0 (tests/test_gpu_dct_pack_budget.py)
+    ref = layers._join([bytes(fr) for fr in frames])
+    n = _frames_for(int(ref[1][2 * K]) - int(ref[1][K]))
+    exp = pd.Periodic(*ref, K, n)
+    big.get("svcq", geom).release()
+    FIG["in_max"] = n * h * w * 3
+    _crossed("out", exp.offsets)
+    out, got, got_choice = nat.dct_pack_levels_budget_frames(_tiled(bgr, n), tile[0], _tiled(types, n), mv, LADDER,
+                                                             pd.repeat_rows([[b] for b in budgets], n, DEV).reshape(-1))
+    _finish("dct_pack_levels_budget", out, got, exp)
+    assert torch.equal(got_choice, pd.repeat_rows([[c] for c in choice[:K]], n, DEV).reshape(-1)), "choice"
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=_gid)
+def test_dct_pack_layers_past_four_trips(big, geom):
+    """1027 frames: the trips of 256 frames and their carry, not 2^32 (see the file's docstring).  The base is the numpy writer's on the
+    transform's quantised planes; the enhancement in every tile is the split statement's on the planes quantised at the enhancement's step."""
+    w, h, tile, mv = geom
+    bgr, types = _bgr_cycle(geom, 13)
+    t = types.cpu().numpy().view(np.uint32)
+    base = write_frames(nat.dct_quant_frames(bgr, tile[0], types, mv[0], 4, 16).cpu().numpy(), t, *tile, *mv, 4, 16)
+    fine = write_frames(nat.dct_quant_frames(bgr, tile[0], types, mv[0], 2, 2).cpu().numpy(), t, *tile, *mv, 2, 2)
+    enh = layers.enhancement_frames(*base, *fine, 2)
+    n = 4 * 256 + 3
+    FIG["n"] = n
+    assert n > 256
+    eb, ee = pd.Periodic(*base, K, n), pd.Periodic(*enh, K, n)
+    FIG["in_max"], FIG["out_max"], FIG["out_enh_max"] = n * h * w * 3, int(eb.offsets[-1]), int(ee.offsets[-1])
+    got = nat.dct_pack_layers_frames(_tiled(bgr, n), tile[0], _tiled(types, n), mv, 4, 16, 2)
+    _finish("dct_pack_layers base", got[0], got[1], eb)
+    _finish("dct_pack_layers enhancement", got[2], got[3], ee)

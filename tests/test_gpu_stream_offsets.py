@@ -5,7 +5,7 @@ call, the split's two layers and the entropy coder's two directions).
 svc_hip_window_levels_frames (a window per frame, some empty), svc_hip_split_levels_frames at (1, 3, 1) and svc_hip_entropy_encode_frames,
 and back through svc_hip_entropy_decode_frames.  Every call's n + 1 offsets and its stream are compared byte for byte with the numpy
 statements: layers.window_frames, layers.split_frames, entropy.encode_frames.  (A frame's group scan past 256 groups is the 16 x 704 case
-of tests/test_gpu_window_levels.py.)"""
+of tests/test_gpu_window_levels.py.  Some seventy trips, with the offsets themselves past 2^32, for every stream call: tests/test_gpu_large_streams.py.)"""
 import numpy as np
 import pytest
 
