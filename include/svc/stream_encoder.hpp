@@ -63,6 +63,15 @@ struct StreamEncoderConfig {
                                    // svc_hip_pack_layers_frames; with `entropy` both streams are coded.  0 = one layer.  Not with
                                    // `wire`, and not with compact_budget (the budget counts one stream): both throw at construction, as
                                    // do steps the C ABI refuses, with its message
+  bool delta = false;              // with `compact`: the DELTA stream (include/svc_hip.h, svc_hip_dct_pack_delta_frames): every frame coded
+                                   // against the frame before it in levels, straight from the pixels; EncodedBatch::compact carries it
+                                   // (with `entropy`: its SVCE frames) and EncodedBatch::compact_key the key flags.
+                                   // svc::StreamDecoder::DecodeDelta plays it.  The chain runs across batches, so the stream does not
+                                   // depend on batch or depth; every Encode() starts with a key frame.  Square 8x8 or 16x16 transform
+                                   // blocks only; not with `wire`, compact_budget or enh_step: each throws at construction, as does a
+                                   // geometry the C ABI refuses, with its message
+  uint32_t key_interval = 0;       // with `delta`: the encoded frame with clip index f (as EncodedBatch::first_frame counts: the first
+                                   // is 1) is a key frame iff f == 1, or key_interval != 0 and (f - 1) % key_interval == 0
   std::function<bool(uint32_t frame, uint32_t xywh[4])> enh_window;  // with enh_step: the window of each encoded frame.  Empty: every
                                    // tile is enhanced (the store-once case: svc_hip_window_levels_frames serves any viewer later).
                                    // Otherwise called on the thread that calls Encode(), while a batch is staged, once per encoded
@@ -92,6 +101,8 @@ struct EncodedBatch {
   uint64_t compact_bytes = 0;                 // = compact_offsets[count]
   const uint32_t* compact_choice = nullptr;   // compact_budget != 0: [count] the ladder entry each frame was packed with, bit 31 set
                                               // when even the last entry is over that frame's budget
+  const uint32_t* compact_key = nullptr;      // delta == true: [count] != 0 for a key frame, as svc::StreamDecoder::DecodeDelta and
+                                              // svc_hip_undelta_levels_frames take them
   const uint8_t* enhancement = nullptr;           // enh_step != 0: `count` frames of the enhancement stream (SVCQ, or SVCE with entropy),
   const uint64_t* enhancement_offsets = nullptr;  // [count + 1], and
   uint64_t enhancement_bytes = 0;                 // = enhancement_offsets[count]; compact* is then the base.  Lifetime as compact

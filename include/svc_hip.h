@@ -1331,6 +1331,52 @@ int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_
                                        uint32_t* d_status /* [n_frames] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * A delta stream straight from pixels: svc_hip_dct_pack_levels_frames and
+ * svc_hip_delta_levels_frames in one call, without the plain stream in between.
+ *
+ * d_out and d_frame_offsets are byte for byte what svc_hip_dct_pack_levels_frames on the same
+ * frames, followed by svc_hip_delta_levels_frames on its output with the same d_key and with
+ * d_prev = svc_hip_dct_pack_levels_frames of (d_prev_bgr, d_prev_types) at the same steps, leave:
+ *   header   words 0 .. 9 and 11 as the fused pack writes them (inexact = 0), word 10 = the non-zero
+ *            differences, word 12 = the frame's size
+ *   types    d_block_types of the frame
+ *   masks    of the differences;  levels  the non-zero differences;  padding  zero
+ * The predecessor of frame i > 0 is INPUT frame i - 1; that of frame 0 is the frame at d_prev_bgr
+ * with the region ids at d_prev_types (both NULL: none, frame 0 is a key frame).  A tile is predicted
+ * iff the frame is not a key frame (d_key as svc_hip_delta_levels_frames takes it) and
+ * step(type now) == step(type before), step(t) = bg_step for t == 0, else fg_step: with
+ * fg_step == bg_step every tile of a frame that is not a key frame is predicted.  The difference is
+ * modulo 2^16.  A batch cut into two calls at any frame, the second given the first's last input
+ * frame and types, writes the bytes of one call; d_prev_bgr may be the frame immediately in front of
+ * d_bgr.  svc_hip_undelta_levels_frames and svc_hip_decode_delta_levels_frames take the output.
+ *
+ * The predecessor's levels are a function of its pixels, its types and the steps, so a wave carries
+ * its piece of the frame through a run of 8 consecutive frames with the frame before in registers:
+ * 9 transforms for 8 frames (runs of 1, 2, 4 and 8 measured: profiles/dct_pack_delta_c3.txt).
+ * Measured there per C3 batch of 16 at (1, 640): 0.152 ms against 0.132 for
+ * svc_hip_dct_pack_levels_frames alone and 0.413 for it + svc_hip_delta_levels_frames.
+ *
+ * Geometry, the order of the checks, alignment and the stride rule are those of
+ * svc_hip_dct_pack_levels_frames: geometry, stride, steps, limits, workspace, out_capacity;
+ * n_frames == 0 then returns SVC_OK; then pointers (a d_prev_bgr without d_prev_types, or the
+ * reverse: SVC_ERR_INVALID_ARG; d_prev_bgr 16-byte aligned, d_prev_types and d_key 4-byte).  The
+ * workspace query returns 0 where the call refuses.  No status array: pixels cannot be malformed.
+ * Only enqueues work; the number of launches (three) does not depend on n_frames.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_dct_pack_delta_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                uint32_t block, uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_dct_pack_delta_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames,
+                                  uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                  const uint32_t* d_block_types /* [n_frames][mv blocks] */,
+                                  uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                                  const uint8_t* d_prev_bgr     /* one frame, the predecessor of frame 0; NULL: frame 0 is a key frame */,
+                                  const uint32_t* d_prev_types  /* [mv blocks] of that frame; NULL exactly when d_prev_bgr is */,
+                                  const uint32_t* d_key         /* [n_frames] or NULL, as svc_hip_delta_levels_frames takes it */,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes,
+                                  uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets /* [n_frames + 1] */,
+                                  void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes
  * of svc_hip_serialize_frames / svc_hip_dct_records_frames and of the reference's encoder): the
  * reference's Decoder::operator() (libs/decoder.cpp:168-210) without the GUI.  Its records hold

@@ -38,6 +38,16 @@
 // transform.  dct_pack_layers_kernel<N> is the third form of the body: each lane quantises its coefficients twice, the wave stages
 // and walks the base levels, then stages d into the same images and walks again into a second workspace; the scan and the assemble
 // pass then run once per layer.
+//
+// The delta stream from pixels (svc_hip_dct_pack_delta_frames; include/svc_hip.h states it): the bytes of svc_hip_dct_pack_levels_frames
+// followed by svc_hip_delta_levels_frames, without the plain stream in between.  The predecessor of frame i is INPUT frame i - 1, whose
+// levels are a function of its pixels, its region ids and the steps alone, so the difference is taken in the transform's registers.
+// dct_pack_delta_kernel<N> is the fourth form of the body: a wave owns its piece through a RUN of kDeltaRun consecutive frames.  It
+// transforms the frame in front of the run (not where the run starts at a key frame) and keeps that frame's packed levels -- 3 channels
+// x 8 dwords -- in registers; then, frame by frame, it transforms, subtracts the kept levels in the two int16 halves of every dword
+// where the lane's tile is predicted (a lane's 16 coefficients lie in one tile: a predicate per lane from two type reads), keeps the
+// undifferenced levels for the next frame, and stages and walks the differences exactly as the one-layer form does its levels.  A run
+// of R frames costs R + 1 transforms and the grid is that of n / R frames; the scan and the assemble pass are the fused pack's.
 #include <algorithm>
 #include <type_traits>
 
@@ -144,6 +154,21 @@ struct LayerArgs {
   const uint32_t* window;  // [n][4] x, y, w, h in padded coordinates, or null: every tile is enhanced
   DctPackWs enh;
 };
+// what the delta form takes besides: the frame in front of frame 0 (null: none), the key flags, and how the frames fall into runs
+struct DeltaRunArgs {
+  const uint8_t* prev_bgr;     // one frame, or null: frame 0 is a key frame
+  const uint32_t* prev_types;  // [mv blocks] of that frame
+  const uint32_t* key;         // [n] or null
+  uint32_t n_frames, run;      // a wave carries frames [r * run, min((r + 1) * run, n_frames))
+  uint32_t one_step;           // fg_step == bg_step: every tile of a frame that is not a key frame is predicted
+};
+// Frames of a run.  {1, 2, 4, 8} measured at C3 and C5, batches of 16 (profiles/dct_pack_delta_c3.txt has all four): 8 is the fastest
+// or tied in every row -- at C3 / (1, 640) 0.194, 0.163, 0.152, 0.152 ms; at C5 1.065, 0.897, 0.820, 0.790.
+#ifndef SVC_DCT_PACK_DELTA_RUN  // (the probe that measured them builds this file once per value: tools/dct_pack_probe.py delta-encode)
+#define SVC_DCT_PACK_DELTA_RUN 8
+#endif
+constexpr uint32_t kDeltaRun = SVC_DCT_PACK_DELTA_RUN;
+static_assert(kDeltaRun >= 1, "a run holds a frame");
 constexpr uint32_t kTauTable = 2 * kMaxLadder;  // a class's thresholds, padded with +inf to what 7 probes can reach
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
@@ -152,6 +177,12 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
 
 __device__ __forceinline__ uint32_t pack2(f32x2 q) {  // two levels as int16, the first in the low half
   return ((uint32_t)(int32_t)q.x & 0xFFFFu) | ((uint32_t)(int32_t)q.y << 16);
+}
+
+template <typename K>
+__device__ __forceinline__ bool k_one_step(const K& k) {
+  if constexpr (std::is_same_v<K, DeltaRunArgs>) return k.one_step != 0;
+  else return false;
 }
 
 // the workspace a layer's walk fills: the base's (the only one of the one-layer forms), or the enhancement's
@@ -167,15 +198,24 @@ __device__ __forceinline__ uint32_t residual2(f32x2 fine, f32x2 base, int32_t ra
   return ((uint32_t)dx & 0xFFFFu) | ((uint32_t)dy << 16);
 }
 
+// a - b in each int16 half, modulo 2^16: one packed subtract
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t sub2(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)));
+}
+
 // COUNT = false: the fused pack.  COUNT = true: the same transform, stopped at the column pass's f32 coefficients, which are counted per
 // ladder entry instead of quantised: k, and the counting kernel's LDS -- both classes' thresholds, tau_tab[c][i] = tau[c][i] (+inf from
 // the ladder's end on), and a histogram per wave (null for the pack).  LAYERS = true (with COUNT = false): the fused pack of two layers,
-// the base into a.ws and the residuals of the tiles inside the frame's window into k.enh.
-template <int N, bool COUNT, bool LAYERS = false>
-__device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
-                                              const std::conditional_t<COUNT, CountArgs, std::conditional_t<LAYERS, LayerArgs, NoCountArgs>>& k,
-                                              float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
+// the base into a.ws and the residuals of the tiles inside the frame's window into k.enh.  DELTA = true (alone): the fused pack of
+// differences; a.total_waves counts runs where the other forms count frames, and the wave goes through its run's frames in turn.
+template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false>
+__device__ __forceinline__ void dct_pack_body(
+    const DctPackArgs& a,
+    const std::conditional_t<COUNT, CountArgs, std::conditional_t<LAYERS, LayerArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>& k,
+    float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
   static_assert(!(COUNT && LAYERS), "the counting form has no layers");
+  static_assert(!(DELTA && (COUNT || LAYERS)), "the delta form is one layer at fixed steps");
   constexpr uint32_t kCols = 64 / N;        // segment columns of a wave
   constexpr uint32_t kColWords = N / 4;     // mask words of a segment column: two 8x8 tiles of one word, or one 16x16 tile of four
   constexpr int kSlab = N == 8 ? kSlab8 : kSlab16;
@@ -199,24 +239,51 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
   }
   if (wv >= a.total_waves) return;
   const uint32_t row_g = wv / gm.waves_per_row, wr = wv - row_g * gm.waves_per_row;
-  const uint32_t frame = row_g / gm.l.tiles_y, band = row_g - frame * gm.l.tiles_y;
+  const uint32_t frame0 = row_g / gm.l.tiles_y, band = row_g - frame0 * gm.l.tiles_y;  // DELTA: frame0 is the run
   const uint32_t seg0 = wr * kCols, seg = seg0 + g;
   const uint32_t ncols = min(kCols, gm.segs_per_band - seg0);  // the last wave of a row may hold fewer
   const bool active = g < ncols;  // an idle column runs on zeros and is not packed
   const uint32_t y_pix = band * N, x_pix = seg * 16;
 
+  // DELTA: the run's frames in turn, it = -1 for the frame in front of the run, of which only the levels are kept.  The other forms:
+  // one trip, it = 0 -- the loop's condition is a constant false there, so their code is what it was without the loop (their symbols'
+  // sizes are compared in profiles/dct_pack_delta_c3.txt).  Everything that tells the trips apart is the same in every lane of the wave.
+  uint32_t run_first = 0, run_len = 1;
+  uint32_t before[3][8] = {};  // DELTA: the undifferenced levels of the frame before, as lv below, and that frame's type of the lane's tile
+  uint32_t t_before = 0;
+  uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
+  if constexpr (DELTA) {
+    run_first = frame0 * k.run;
+    run_len = min(k.run, k.n_frames - run_first);
+  }
+  int it = DELTA ? -1 : 0;
+  do {  // (a trip's statements keep the indentation they have had as the only trip)
+  const uint32_t frame = DELTA ? run_first + (uint32_t)it : frame0;
+  bool key = false;  // DELTA: a key frame is not predicted, and the frame in front of it is not read
+  const uint8_t* frame_bgr = nullptr;  // DELTA: the trip's frame and its types
+  const uint32_t* frame_types = nullptr;
+  if constexpr (DELTA) {
+    const uint32_t f = run_first + (uint32_t)max(it, 0);  // the frame whose flag decides this trip
+    key = (f == 0 && !k.prev_bgr) || (k.key && k.key[f] != 0);
+    if (it < 0 && key) continue;  // (`before` is not read)
+    const bool outside = it < 0 && run_first == 0;  // the frame in front of frame 0
+    frame_bgr = outside ? k.prev_bgr : a.bgr + (size_t)frame * a.frame_stride;
+    frame_types = outside ? k.prev_types : a.types + (size_t)frame * gm.l.mvb;
+  }
+
   // 16 BGR pixels of row j of this segment column
   uint32_t wds[12] = {};
   uint32_t t = 0;
   if (active) {
-    const uint4* p = reinterpret_cast<const uint4*>(a.bgr + (size_t)frame * a.frame_stride + ((size_t)(y_pix + j) * gm.w + x_pix) * 3);
+    const uint4* p = reinterpret_cast<const uint4*>((DELTA ? frame_bgr : a.bgr + (size_t)frame * a.frame_stride) + ((size_t)(y_pix + j) * gm.w + x_pix) * 3);
     const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
     wds[0] = v0.x; wds[1] = v0.y; wds[2] = v0.z; wds[3] = v0.w;
     wds[4] = v1.x; wds[5] = v1.y; wds[6] = v1.z; wds[7] = v1.w;
     wds[8] = v2.x; wds[9] = v2.y; wds[10] = v2.z; wds[11] = v2.w;
     // tile type = type of the MV block that holds it; background (0) takes bg_step: the rule of dct_kernel
     const uint32_t col = N == 8 ? x_pix + 2 * j : x_pix + j;
-    t = a.types[(size_t)frame * gm.l.mvb + (y_pix / gm.mvbh) * gm.l.mfw + col / gm.mvbw];
+    if constexpr (DELTA) t = frame_types[(y_pix / gm.mvbh) * gm.l.mfw + col / gm.mvbw];
+    else t = a.types[(size_t)frame * gm.l.mvb + (y_pix / gm.mvbh) * gm.l.mfw + col / gm.mvbw];
   }
   float step = t == 0 ? a.bg_step : a.fg_step, inv_step = t == 0 ? a.bg_inv : a.fg_inv;
   if (!COUNT && a.steps) {  // the wave's own frame's pair: one workgroup's four waves can belong to four frames
@@ -224,7 +291,6 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
     step = (float)(t == 0 ? fs.bg : fs.fg);  // libs/decoder.cpp:141 divides a float by an unsigned
     inv_step = t == 0 ? fs.bg_inv : fs.fg_inv;
   }
-  uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
   int32_t ratio = 0;      // LAYERS: the lane's tile's base step / enh_step, and whether the frame's window holds the tile's origin
   bool enhanced = false;  // (the containment rule of the decoders' gaze: w or h of 0 holds nothing)
   if constexpr (LAYERS) {
@@ -241,6 +307,8 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
   const uint8_t* wave_slabs = lds + (sc_local - g) * kSlab;
   const uint32_t nwords = ncols * kColWords;                           // mask words of the piece, in the format's order
   const uint32_t word0 = (seg0 * (16 / N)) * gm.l.words;               // the piece's first word within its tile row
+  // DELTA: the lane's tile is predicted where both frames code it at one step
+  const bool predicted = DELTA && !key && (k_one_step(k) || (t == 0) == (t_before == 0));
 
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -330,6 +398,15 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
       }
       continue;  // (the slabs are free for the next channel: the sync above)
     }
+    if constexpr (DELTA) {  // the levels stay for the next frame; what is staged and walked is their difference to the frame before
+#pragma unroll
+      for (int v = 0; v < 8; ++v) {
+        const uint32_t cur = lv[v];
+        if (predicted) lv[v] = sub2(cur, before[c][v]);
+        before[c][v] = cur;
+      }
+      if (it < 0) continue;  // the frame in front of the run is not packed
+    }
 
     // a layer of this channel: the lane's levels q to the column's tile images, then the wave's walk into the layer's workspace.  The
     // second layer's images replace the first's once the walk has read them (the sync that ends a layer)
@@ -377,6 +454,8 @@ __device__ __forceinline__ void dct_pack_body(const DctPackArgs& a,
       wave_lds_sync();  // the slabs are rewritten: by the next layer's images, or by the next channel
     }
   }
+  t_before = t;
+  } while (DELTA && ++it < (int)run_len);
   if constexpr (COUNT) {  // the wave's row: bins 0 .. len - 2 as they are, bin len - 1 = the lanes' full counts
     uint32_t* hist = hist_all[tid >> 6];
     if (full) atomicAdd(&hist[k.lad.len - 1], full);
@@ -393,6 +472,11 @@ __global__ __launch_bounds__(256) void dct_pack_kernel(DctPackArgs a) {
 template <int N>
 __global__ __launch_bounds__(256) void dct_pack_layers_kernel(DctPackArgs a, LayerArgs k) {
   dct_pack_body<N, false, true>(a, k, nullptr, nullptr);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void dct_pack_delta_kernel(DctPackArgs a, DeltaRunArgs k) {
+  dct_pack_body<N, false, false, true>(a, k, nullptr, nullptr);
 }
 
 template <int N>
@@ -603,6 +687,59 @@ int svc_hip_dct_pack_levels_frames(const uint8_t* d_bgr, uint64_t frame_stride_b
   a.bg_inv = 1.0f / a.bg_step;
   a.ws = carve(d_workspace, pack_ws, n_frames, g);
   return enqueue_dct_pack("dct_pack_levels", a, n_frames, fg_step, bg_step, d_out, d_frame_offsets, s);
+}
+
+uint64_t svc_hip_dct_pack_delta_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,
+                                                uint32_t mv_block_h) {
+  if (validate_pack_geom("dct_pack_delta_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits("dct_pack_delta_workspace_bytes", n_frames, g)) return 0;
+  return layout_bytes(pack_ws, n_frames, g);  // the fused pack's: the frame before lives in registers
+}
+
+// Checked in the order of svc_hip_dct_pack_levels_frames: geometry, stride, steps, limits, sizes; n_frames == 0 then returns SVC_OK; then
+// pointers, the pairing of d_prev_bgr and d_prev_types among them.
+int svc_hip_dct_pack_delta_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                  uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                  uint32_t bg_step, const uint8_t* d_prev_bgr, const uint32_t* d_prev_types, const uint32_t* d_key,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                  uint64_t* d_frame_offsets, void* stream) {
+  int rc = validate_pack_geom("dct_pack_delta", frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "dct_pack_delta: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", (unsigned long long)frame_stride_bytes,
+              3ull * frame_w * frame_h);
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "dct_pack_delta: quant steps must be positive");
+  // (the pack's int16 bound holds for every step at 8x8 and 16x16, as in svc_hip_dct_pack_levels_frames; a difference wraps by definition)
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits("dct_pack_delta", n_frames, g))) return rc;
+  if ((rc = require_workspace("dct_pack_delta", workspace_bytes, layout_bytes(pack_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity("dct_pack_delta", "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets, "dct_pack_delta: null pointer");
+  SVC_REQUIRE((d_prev_bgr == nullptr) == (d_prev_types == nullptr),
+              "dct_pack_delta: the frame before frame 0 is its pixels and its types: d_prev_bgr and d_prev_types are given together or not at all");
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_prev_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_block_types, 4) && aligned(d_prev_types, 4) && aligned(d_key, 4),
+              "dct_pack_delta: frames, d_prev_bgr, output and workspace must be 16-byte aligned, offsets 8-byte, types and key flags 4-byte");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.types = d_block_types;
+  a.fg_step = (float)fg_step;
+  a.bg_step = (float)bg_step;
+  a.fg_inv = 1.0f / a.fg_step;
+  a.bg_inv = 1.0f / a.bg_step;
+  a.ws = carve(d_workspace, pack_ws, n_frames, g);
+  const DeltaRunArgs k{d_prev_bgr, d_prev_types, d_key, n_frames, kDeltaRun, fg_step == bg_step ? 1u : 0u};
+  a.total_waves = div_up(n_frames, kDeltaRun) * g.l.tiles_y * g.waves_per_row;  // a wave per piece and RUN
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (block == 8) hipLaunchKernelGGL(dct_pack_delta_kernel<8>, grid, blk, 0, s, a, k);
+  else hipLaunchKernelGGL(dct_pack_delta_kernel<16>, grid, blk, 0, s, a, k);
+  if ((rc = check_launch("dct_pack_delta", "transform"))) return rc;
+  return enqueue_assemble("dct_pack_delta", a, a.ws, n_frames, fg_step, bg_step, d_out, d_frame_offsets, s);
 }
 
 uint64_t svc_hip_dct_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,

@@ -46,6 +46,9 @@ struct Slot {
   PinBuf<uint8_t> pin_enh;
   PinBuf<uint64_t> pin_enh_offsets;
   PinBuf<uint32_t> pin_enh_status, pin_window;
+  // delta: the frames' key flags
+  DevBuf<uint32_t> key;
+  PinBuf<uint32_t> pin_key;
   uint32_t frames = 0;  // source frames resident in bgr (the last one carries into the next batch)
   uint32_t encoded = 0, first = 0;
 };
@@ -78,6 +81,11 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   m.bw = c.mv_block; m.bh = c.mv_block_h ? c.mv_block_h : c.mv_block;
   m.tw = c.dct_block; m.th = c.dct_block_h ? c.dct_block_h : c.dct_block;
   if (!m.tw || !m.th) throw std::runtime_error("svc::StreamEncoder: invalid configuration");
+  if (c.delta && c.wire) throw std::runtime_error("svc::StreamEncoder: the delta stream is a form of the compact stream, not of the wire records");
+  if (c.delta && !c.compact) throw std::runtime_error("svc::StreamEncoder: the delta stream is a form of the compact stream");
+  if (c.delta && c.compact_budget)
+    throw std::runtime_error("svc::StreamEncoder: a byte budget picks each frame's steps, a difference needs the steps of the frame before: not with delta");
+  if (c.delta && c.enh_step) throw std::runtime_error("svc::StreamEncoder: the delta stream has one layer: not with enh_step");
   if (c.compact && c.wire) throw std::runtime_error("svc::StreamEncoder: compact is a form of the quantised planes, not of the wire records");
   static_cast<EncodeGeometry&>(m) = EncodeGeometry(c.width, c.height, c.levels, m.bw, m.bh);
   // reference_stream: SerializeEncodedFrame over the UNPADDED size (libs/encoder.cpp:647-650); the transform kernel emits that
@@ -105,6 +113,13 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (m.layered)  // the layered pack's checks that need neither a device pointer nor a size: geometry, the steps, the int16 bounds
     Abi(svc_hip_pack_layers_frames(nullptr, nullptr, 0, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step, c.enh_step, nullptr, nullptr,
                                    ~0ull, nullptr, ~0ull, nullptr, nullptr, ~0ull, nullptr, nullptr), "enh_step");
+  if (c.delta) {  // the call's checks that need neither a device pointer nor a size: geometry (square 8x8 / 16x16 tiles, whole segments), the steps
+    if (m.tw != m.th)
+      throw std::runtime_error("svc::StreamEncoder: the delta stream takes square transform blocks (8x8, 16x16), not " + std::to_string(m.tw) + "x" +
+                               std::to_string(m.th));
+    Abi(svc_hip_dct_pack_delta_frames(nullptr, m.frame_bytes, 0, m.pw, m.ph, m.tw, nullptr, m.bw, m.bh, c.fg_step, c.bg_step, nullptr, nullptr,
+                                      nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr, nullptr), "delta");
+  }
   if (c.entropy) {
     m.coded_bytes = svc_hip_entropy_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
     m.entropy_ws_bytes = svc_hip_entropy_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
@@ -114,6 +129,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
     m.pack_ws_bytes = m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
                       : m.layered ? svc_hip_pack_layers_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th)
+                      : c.delta   ? svc_hip_dct_pack_delta_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh)
                                   : svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
     if (!m.packed_bytes || !m.pack_ws_bytes) throw std::runtime_error("svc::StreamEncoder: no compact stream for this geometry");
   }
@@ -135,7 +151,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     s->samples.Alloc(kWho, B * m.iters * c.ransac.subset_sz); s->pin_samples.Alloc(kWho, B * m.iters * c.ransac.subset_sz);
     Hip(hipMemset(s->samples.p, 0, std::max<size_t>(B * m.iters * c.ransac.subset_sz, 1) * sizeof(uint32_t)), "hipMemset");
     if (c.wire) { s->records.Alloc(kWho, B * m.record_bytes); s->pin_records.Alloc(kWho, B * m.record_bytes); }
-    if (!c.wire || !m.fused_records) s->coeffs.Alloc(kWho, B * 3 * m.plane_elems);
+    if ((!c.wire || !m.fused_records) && !c.delta) s->coeffs.Alloc(kWho, B * 3 * m.plane_elems);  // (the delta route has no planes)
     if (!c.wire && !c.compact) s->pin_coeffs.Alloc(kWho, B * 3 * m.plane_elems);
     if (c.compact) {
       s->packed.Alloc(kWho, m.packed_bytes); s->pack_ws.Alloc(kWho, m.pack_ws_bytes); s->offsets.Alloc(kWho, B + 1);
@@ -154,6 +170,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
       }
       if (c.enh_window) { s->window.Alloc(kWho, B * 4); s->pin_window.Alloc(kWho, B * 4); }
     }
+    if (c.delta) { s->key.Alloc(kWho, B); s->pin_key.Alloc(kWho, B); }
     if (m.budgeted) { s->budget.Alloc(kWho, B); s->choice.Alloc(kWho, B); s->pin_budget.Alloc(kWho, B); s->pin_choice.Alloc(kWho, B); }
     m.slots.push_back(std::move(s));
   }
@@ -221,6 +238,7 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     if (c.compact) {
       b.compact = s.pin_packed.p; b.compact_offsets = s.pin_offsets.p; b.compact_bytes = s.pin_offsets.p[s.encoded];
       b.compact_choice = m.budgeted ? s.pin_choice.p : nullptr;
+      b.compact_key = c.delta ? s.pin_key.p : nullptr;
     }
     if (m.layered) {
       b.enhancement = s.pin_enh.p; b.enhancement_offsets = s.pin_enh_offsets.p; b.enhancement_bytes = s.pin_enh_offsets.p[s.encoded];
@@ -269,6 +287,13 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       if (m.layered && c.enh_window)
         Hip(hipMemcpyAsync(s.window.p, s.pin_window.p, (size_t)encoded * 4 * sizeof(uint32_t), hipMemcpyHostToDevice, si),
             "hipMemcpyAsync windows");
+      if (c.delta) {  // the key flags: a function of the clip index alone, so the stream does not depend on how it falls into batches
+        for (uint32_t i = 0; i < encoded; ++i) {
+          const uint32_t f = first + i;
+          s.pin_key.p[i] = (f == 1 || (c.key_interval != 0 && (f - 1) % c.key_interval == 0)) ? 1u : 0u;
+        }
+        Hip(hipMemcpyAsync(s.key.p, s.pin_key.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyHostToDevice, si), "hipMemcpyAsync key flags");
+      }
       if (m.budgeted) {  // the budget as it stands now, for every frame of this batch (SetCompactBudget's rule)
         const uint32_t bytes = m.budget.load();
         std::fill(s.pin_budget.p, s.pin_budget.p + encoded, bytes);
@@ -306,6 +331,21 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
                                               (uint32_t)c.compact_ladder.size(), s.budget.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
                                               m.packed_bytes, s.offsets.p, s.choice.p, sk),
             "svc_hip_pack_levels_budget_frames");
+      } else if (c.delta) {
+        // The frame before this batch's first encoded frame: its pixels are the slot's frame 0 (the previous batch's last frame, copied on
+        // the device), its types the previous slot's last encoded row.  That buffer is written by the previous batch's segmentation and
+        // next by the batch that takes the slot again, depth - 1 >= 2 batches on -- both on this one stream (batch_pipe.hpp), so the
+        // read below lies between them.  The first batch of an Encode() has no frame before: its first frame is a key frame.
+        const uint32_t* prev_types = carry ? prev->types.p + (size_t)(prev->encoded - 1) * m.blocks : nullptr;
+        Abi(svc_hip_dct_pack_delta_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.fg_step, c.bg_step,
+                                          carry ? s.bgr.p : nullptr, prev_types, s.key.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
+                                          m.packed_bytes, s.offsets.p, sk),
+            "svc_hip_dct_pack_delta_frames");
+        if (c.entropy)
+          Abi(svc_hip_entropy_encode_frames(s.packed.p, m.packed_bytes, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
+                                            s.entropy_ws.p, m.entropy_ws_bytes, s.coded.p, m.coded_bytes, s.coded_offsets.p,
+                                            s.entropy_status.p, sk),
+              "svc_hip_entropy_encode_frames");
       } else if (m.layered) {  // raw planes; both layers quantise them themselves, whatever the geometry
         Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, sk), "svc_hip_dct_frames");
         Abi(svc_hip_pack_layers_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.fg_step, c.bg_step, c.enh_step,

@@ -124,6 +124,8 @@ SIGNATURES = {
     "svc_hip_unpack_levels_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 7 + [_vp, _u64, _vp, _vp, _vp, _vp]),
     "svc_hip_dct_pack_levels_workspace_bytes": (_u64, [_u32] * 6),
     "svc_hip_dct_pack_levels_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 + [_vp, _u64, _vp, _u64, _vp, _vp]),
+    "svc_hip_dct_pack_delta_workspace_bytes": (_u64, [_u32] * 6),
+    "svc_hip_dct_pack_delta_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 + [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "svc_hip_levels_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
     # its lossless entropy coding, "SVCE" (csrc/entropy.hip; the drain in csrc/levels.hip)
     "svc_hip_entropy_max_bytes": (_u64, [_u32] * 7),
@@ -804,6 +806,43 @@ def dct_pack_levels_frames(bgr: torch.Tensor, block: int, block_types: torch.Ten
                                                  _dev(block_types, torch.int32), mbw, mbh, fg_step, bg_step,
                                                  _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
                                                  _dev(offsets, torch.int64), _stream()))
+    return out, offsets
+
+
+def dct_pack_delta_workspace_bytes(n: int, w: int, h: int, block: int, mv_block) -> int:
+    """Scratch of dct_pack_delta_frames; 0 for a geometry it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_delta_workspace_bytes(n, w, h, block, mbw, mbh))
+
+
+def dct_pack_delta_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, fg_step: int, bg_step: int,
+                          prev_bgr: Optional[torch.Tensor] = None, prev_types: Optional[torch.Tensor] = None, key=None,
+                          out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """B,G,R frames (frames, H, W, 3) u8 + region ids (frames, blocks) i32 -> the DELTA stream of those frames, byte for byte
+    delta_levels_frames of dct_pack_levels_frames' stream, without that stream (include/svc_hip.h): (stream u8 of the worst-case
+    size, offsets (frames + 1,) i64 on the device).  The numpy statement is layers.delta_frames applied to the frames of
+    dct_pack_levels_frames: there is no other.  prev_bgr (H, W, 3) u8 with prev_types (blocks,) i32: the frame before frame 0 (the
+    last input frame of the call before) -- both or neither; neither: frame 0 is a key frame.  key: None, or per frame != 0 for a
+    key frame ((frames,) ints, a tensor or a list).  Geometry as dct_pack_levels_frames."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    dev = bgr.device
+    k = None if key is None else torch.as_tensor(key, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    assert k is None or k.numel() == n, "one key flag per frame"
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_delta_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    _check(load().svc_hip_dct_pack_delta_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                _dev(block_types, torch.int32), mbw, mbh, fg_step, bg_step,
+                                                None if prev_bgr is None else _dev(prev_bgr, torch.uint8),
+                                                None if prev_types is None else _dev(prev_types, torch.int32),
+                                                None if k is None else _dev(k, torch.int32),
+                                                _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
+                                                _dev(offsets, torch.int64), _stream()))
     return out, offsets
 
 

@@ -54,6 +54,17 @@
                                                    stream and svc_hip_window_levels_frames with no window, then svc_hip_undelta_levels_frames
                                                    followed by svc_hip_decode_levels_frames against the decode alone; wall time per call over
                                                    20 back-to-back calls
+  python tools/dct_pack_probe.py delta-encode      the delta stream straight from the pixels (svc_hip_dct_pack_delta_frames), at C3 and at C5, a batch of 16 at
+                                                   (1, 640) and (1, 1), with frame 0 the key frame (a key frame every 16) and with the frame before
+                                                   given and no key frame: the call with runs of 1, 2, 4 and 8 frames (csrc/dct_pack.hip built once per
+                                                   value into tools/_bin, -DSVC_DCT_PACK_DELTA_RUN), svc_hip_dct_pack_levels_frames alone, that call
+                                                   + svc_hip_delta_levels_frames, and the planes route (svc_hip_dct_quant_frames,
+                                                   svc_hip_pack_levels_frames) + svc_hip_delta_levels_frames; wall time per call over 20 back-to-back
+                                                   calls, the routes alternating in one process, the median of three; the bytes are compared.  Then
+                                                   delta bytes against plain bytes, raw and entropy-coded, for the synthetic clip and for a static
+                                                   background (the first synthetic frame repeated) under a moving 128 x 128 patch of the clip, region
+                                                   ids foreground under the patch.  Then tests/dropin/stream_delta_encode_main on a 33-frame 1080p
+                                                   clip, with delta and without, plain and entropy-coded, the list twice
   python tools/dct_pack_probe.py window-entropy [C3|C5]
                                                    a stored entropy-coded enhancement served under a gaze, the same batch of 16 at
                                                    (1, 640, 1) with a 256 x 256 window per frame: svc_hip_window_entropy_frames on the stored
@@ -366,6 +377,190 @@ def window(cfg) -> None:
         assert torch.equal(oo4[v * n:(v + 1) * n + 1] - lo, offs_v) and torch.equal(out4[lo:hi], enc[:hi - lo]), f"viewer {v} differs"
     print(f"(b) {viewers} viewers, n_out = {n_out} through d_src: {viewers} encodes {fmt(t_enc4)}; one window call {fmt(t_win4)} "
           f"({t_win4[0] / t_enc4[0]:.3f} of the encodes); same bytes; served {int(oo4[-1]) / n_out / 1e6:.3f} MB per frame", flush=True)
+
+
+DELTA_RUNS = (1, 2, 4, 8)
+
+
+def _delta_run_lib(run):
+    """csrc/dct_pack.hip built with runs of `run` frames, as a small library of its own beside libsvc_hip.so (whose other symbols it
+    uses); built once, into tools/_bin (git-ignored)."""
+    import ctypes
+    import subprocess
+    from scalable_video_codec_amd import build
+    out = os.path.join(ROOT, "tools", "_bin", f"libsvc_dct_pack_delta_run{run}.so")
+    if not os.path.exists(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call([build._hipcc(), *build.HIPCC_FLAGS, f"-DSVC_DCT_PACK_DELTA_RUN={run}", "-shared", "-o", out,
+                               os.path.join(build.CSRC, "dct_pack.hip"), f"-L{build.PKG}", "-lsvc_hip", f"-Wl,-rpath,{build.PKG}"])
+    native.load()  # (first: the variant resolves the shared helpers in it)
+    lib = ctypes.CDLL(out)
+    fn = lib.svc_hip_dct_pack_delta_frames
+    fn.restype, fn.argtypes = native.SIGNATURES["svc_hip_dct_pack_delta_frames"]
+    return fn
+
+
+def _median3(fns, sync, steps=20):
+    """Wall ms per call of each fn over `steps` back-to-back calls and one sync: three rounds over the whole list in turn, the median
+    of each fn's three."""
+    for fn in fns:
+        fn()
+    sync()
+    ts = [[] for _ in fns]
+    for _ in range(3):
+        for i, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            sync()
+            ts[i].append((time.perf_counter() - t0) * 1e3 / steps)
+    return [sorted(t)[1] for t in ts]
+
+
+def delta_encode_kernels(cfg, runs) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    mbw, mbh = native._bwbh(mv)
+    sync = torch.cuda.synchronize
+    all_bgr, all_types = _batch(cfg, n + 1)  # the frame before, and the 16 of the batch
+    bgr, types = all_bgr[1:], all_types[1:]
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out, plain, ref = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(3))
+    offs, plain_offs, ref_offs = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(3))
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(native.dct_pack_delta_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_d = torch.empty(native.delta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_p = torch.empty(native.pack_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    planes = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=dev)
+    key16 = torch.zeros(n, dtype=torch.int32, device=dev)
+    key16[0] = 1
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}, ms per call (20 back-to-back calls, the routes in turn, the median of three rounds)",
+          flush=True)
+    for fg, bg in ((1, 640), (1, 1)):
+        prev_q, prev_qo = native.dct_pack_levels_frames(all_bgr[:1], block, all_types[:1], mv, fg, bg)
+        sync()
+        prev_q = prev_q[:int(prev_qo[-1])].clone()
+        for name, prev_bgr, prev_types, prev_svcq, key in (("a key frame every 16", None, None, None, key16),
+                                                          ("the frame before given, no key frame", all_bgr[0], all_types[0], prev_q, None)):
+            def new(fn):
+                def call():
+                    native._check(fn(bgr.data_ptr(), pw * ph * 3, n, pw, ph, block, types.data_ptr(), mbw, mbh, fg, bg,
+                                     None if prev_bgr is None else prev_bgr.data_ptr(), None if prev_types is None else prev_types.data_ptr(),
+                                     None if key is None else key.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(),
+                                     offs.data_ptr(), native._stream()))
+                return call
+
+            def fused():
+                native.dct_pack_levels_frames(bgr, block, types, mv, fg, bg, out=plain, offsets=plain_offs, workspace=ws)
+
+            def delta_call():
+                native.delta_levels_frames(plain, plain_offs, pw, ph, block, mv, prev=prev_svcq, key=key, out=ref, out_offsets=ref_offs,
+                                           workspace=ws_d, status=st)
+
+            def fused_delta():
+                fused()
+                delta_call()
+
+            def planes_delta():
+                native.dct_quant_frames(bgr, block, types, mv, fg, bg, out=planes)
+                native.pack_levels_frames(planes, types, block, mv, fg, bg, out=plain, offsets=plain_offs, workspace=ws_p)
+                delta_call()
+
+            fused_delta()
+            sync()
+            used = int(ref_offs[-1])
+            assert not st.any()
+            for r, fn in runs.items():
+                out.fill_(0xA5)
+                new(fn)()
+                sync()
+                assert torch.equal(offs, ref_offs) and torch.equal(out[:used], ref[:used]), f"runs of {r}: the bytes differ from the two calls'"
+            t = _median3([new(fn) for fn in runs.values()] + [fused, fused_delta, planes_delta], sync)
+            t_runs, (t_fused, t_two, t_planes) = dict(zip(runs, t)), t[len(runs):]
+            best = min(t_runs, key=t_runs.get)
+            print(f"  ({fg}, {bg}), {name}: svc_hip_dct_pack_delta_frames with runs of "
+                  + ", ".join(f"{r}: {t_runs[r]:.3f}" for r in runs) + f" (the fastest: {best}); svc_hip_dct_pack_levels_frames alone {t_fused:.3f}; "
+                  f"+ svc_hip_delta_levels_frames {t_two:.3f}; the planes route + svc_hip_delta_levels_frames {t_planes:.3f}; "
+                  f"delta stream {used / n / 1e6:.4f} MB per frame, plain {int(plain_offs[-1]) / n / 1e6:.4f}; same bytes at every run length",
+                  flush=True)
+
+
+def delta_encode_sizes(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    mbw, mbh = native._bwbh(mv)
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    # a static background (the first frame, repeated) under a moving 128 x 128 patch of the clip; foreground under the patch
+    still = bgr[:1].expand(n, ph, pw, 3).clone()
+    still_types = torch.zeros_like(types).view(n, ph // mbh, pw // mbw)
+    for f in range(n):
+        x, y = 256 + 48 * f, 192 + 16 * f  # (on the MV grid at both sizes)
+        still[f, y:y + 128, x:x + 128] = bgr[f, y:y + 128, x:x + 128]
+        still_types[f, y // mbh:(y + 128) // mbh, x // mbw:(x + 128) // mbw] = 1
+    still_types = still_types.reshape(n, -1).contiguous()
+    key = [1] + [0] * (n - 1)
+
+    def coded_bytes(stream, so):
+        _, eo, est = native.entropy_encode_frames(stream, so, pw, ph, block, mv)
+        sync()
+        assert not est.any()
+        return int(eo[-1])
+
+    print(f"{cfg.name} batch of {n}, frame 0 the key frame; MB per frame raw / entropy-coded", flush=True)
+    for clip_name, frames, ty in (("the synthetic clip (fresh noise every frame)", bgr, types),
+                                  ("a static background under a moving 128 x 128 patch", still, still_types)):
+        for fg, bg in ((1, 640), (1, 1)):
+            p, po = native.dct_pack_levels_frames(frames, block, ty, mv, fg, bg)
+            d, do = native.dct_pack_delta_frames(frames, block, ty, mv, fg, bg, key=key)
+            sync()
+            p, d = p[:int(po[-1])], d[:int(do[-1])]
+            raw, craw, draw, dcoded = p.numel(), coded_bytes(p, po), d.numel(), coded_bytes(d, do)
+            k0 = int(po[1])
+            print(f"  {clip_name} at ({fg}, {bg}): plain {raw / n / 1e6:.4f} / {craw / n / 1e6:.4f}, delta {draw / n / 1e6:.4f} / "
+                  f"{dcoded / n / 1e6:.4f} ({draw / raw:.3f}x / {dcoded / craw:.3f}x); the 15 difference frames alone "
+                  f"{(draw - k0) / 15 / 1e6:.4f} raw against {(raw - k0) / 15 / 1e6:.4f}", flush=True)
+
+
+def delta_encode_stream(frames_n=33) -> None:
+    import subprocess
+    import tempfile
+    cfg = configs.C3
+    exe = os.path.join(ROOT, "tests", "dropin", "stream_delta_encode_main")
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=torch.device("cuda"))
+        raw = os.path.join(d, "clip.raw")
+        with open(raw, "wb") as f:
+            for t in range(frames_n):
+                f.write(clip.frame_bgr(t).cpu().numpy().tobytes())
+        del clip
+        torch.cuda.empty_cache()
+        print(f"{cfg.name}, {frames_n} frames from host memory through svc::StreamEncoder (tests/dropin/stream_delta_encode_main), batch 16, depth 3, "
+              f"key_interval 16; every run printed", flush=True)
+        for turn in range(2):
+            for entropy_coded in (0, 1):
+                for delta_on in (1, 0):
+                    p = subprocess.run([exe, raw, str(cfg.width), str(cfg.height), str(frames_n), str(cfg.levels), str(cfg.dct_block), "16", "3",
+                                        str(cfg.seed), str(delta_on), "16", str(entropy_coded), "-"], capture_output=True, text=True, timeout=300)
+                    print(f"  run {turn} (exit {p.returncode}): {(p.stdout.strip() or p.stderr.strip())}", flush=True)
+                    if p.returncode != 0:
+                        sys.exit(1)
+
+
+def delta_encode() -> None:
+    runs = {r: _delta_run_lib(r) for r in DELTA_RUNS}
+    for config in (configs.C3, configs.C5):
+        delta_encode_kernels(config, runs)
+        torch.cuda.empty_cache()
+    for config in (configs.C3, configs.C5):
+        delta_encode_sizes(config)
+        torch.cuda.empty_cache()
+    delta_encode_stream()
 
 
 def window_entropy(cfg) -> None:
@@ -1036,6 +1231,8 @@ if __name__ == "__main__":
         band(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 64)
     elif mode == "delta":
         delta(_cfg(sys.argv, 2))
+    elif mode == "delta-encode":
+        delta_encode()
     elif mode == "stream-layers":
         stream_layers()
     elif mode == "transcode":
