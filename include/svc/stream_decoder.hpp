@@ -37,7 +37,7 @@ struct StreamDecoderConfig {
   // svc_hip_decode_layers_reduced_frames): 1 = the full decoder, or 2, 4, 8.  Above 1 the picture is the padded size over reduce: a
   // display of 0 x 0 means that size, a larger one throws std::runtime_error at the first Decode or DecodeLayers; gaze centres stay in
   // display coordinates.  Serves Decode and DecodeLayers (SVCQ and SVCE): DecodeWire and DecodeDelta then throw std::runtime_error before
-  // any device work.
+  // any device work, and DecodeDeltaReduced takes only this reduce.
   uint32_t reduce = 1;
 };
 
@@ -103,9 +103,21 @@ class StreamDecoder {
   // the depth.  The next batch's call needs the carried frame's length on the host: 8 bytes come back on the kernel stream, and the host
   // waits for batch b's kernels before it enqueues batch b + 1's (its H2D copy is in flight by then).  DecodedBatch::status: the entropy
   // decoder's code if it is not 0, else svc_hip_undelta_levels_frames's (a failure runs down the chain to the next key frame).
-  // config.reduce above 1 throws std::runtime_error before any device work.  One decoder serves all four methods in any order.
+  // config.reduce above 1 throws std::runtime_error before any device work (DecodeDeltaReduced is the method for that).  One decoder
+  // serves all methods in any order.
   void DecodeDelta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, const Gaze& gaze,
                    const Sink& sink);
+
+  // DecodeDelta at 1 / reduce of the size: the device call is svc_hip_decode_delta_levels_reduced_frames, which carries only the first
+  // K x K levels of every tile through time (K = tile side / reduce).  reduce is 2, 4 or 8; the size belongs to the chain, so it is an
+  // argument: config.reduce must be 1 or equal to it, and the configured display (0 x 0: the padded frame over reduce) must fit the padded
+  // frame over reduce, else std::runtime_error before any device work.  Gaze centres stay in display coordinates, as in Decode under
+  // config.reduce.  `stream` is the full delta stream or its band (0, 0, K, K) (svc_hip_band_levels_frames: what a server sends a small
+  // viewer), SVCQ or SVCE by the first frame's magic; the display frames are the same for both.  The two chain buffers hold band frames
+  // here -- this is the only route that carries a band-sized chain, so the driver uses the fused call whatever it measures against the
+  // two calls (README).  Everything else -- key flags, schedule, statuses, statistics -- is DecodeDelta's.
+  void DecodeDeltaReduced(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce,
+                          const Gaze& gaze, const Sink& sink);
 
   // stream: a whole wire stream of `bytes` bytes in host memory, the 32-byte Header (libs/codec.hpp:8-17) first, then frame_count
   // frames of records.  svc_hip_wire_layout decides how it is read (the decoder's padded tile grid, or the reference encoder's

@@ -1331,6 +1331,68 @@ int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_
                                        uint32_t* d_status /* [n_frames] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * A delta stream straight to display frames at reduced size: svc_hip_undelta_levels_frames and
+ * svc_hip_decode_levels_reduced_frames in one call.  The delta chain is per coefficient, so with
+ * K = block / reduce only the first K x K levels of every tile are carried through time.
+ *
+ * Pictures: d_rec [n_frames][frame_h / reduce][frame_w / reduce][3] (and d_display, if a display size
+ * is given) are bit-identical, for every frame, to svc_hip_undelta_levels_frames with the same d_prev
+ * and d_key followed by svc_hip_decode_levels_reduced_frames on its output with the same steps, reduce,
+ * gaze and display size.  A frame that fails is zeros.  The gaze rule is the reduced decoder's:
+ * full-size padded tile origins.
+ *
+ * d_status [n_frames] u32 is the UNDELTA call's: the frame's own unpack code, else 0x100 | its
+ * predecessor's, down to the next key frame.
+ *
+ * Reads: no level outside the first K x K coefficients of a tile is read, in the frames or in d_prev
+ * (headers, types and mask words are read whole).  So
+ *   - on the band (0, 0, K, K) of the delta stream (svc_hip_band_levels_frames, one band for all
+ *     frames, no window) every output has the bits it has on the full delta stream: a server stores
+ *     the delta stream and sends a 1 / reduce viewer that band of it;
+ *   - d_prev may be the full reconstructed frame (an undelta output, or d_last of
+ *     svc_hip_decode_delta_levels_frames) or its band (0, 0, K, K).
+ *
+ * Chaining: d_last (NULL with last_capacity 0 and d_last_bytes NULL: not wanted) receives the band
+ * (0, 0, K, K) of the reconstructed frame n_frames - 1: byte for byte svc_hip_band_levels_frames with
+ * that band and no window on output frame n_frames - 1 of the undelta call -- the header, the types,
+ * the full-size mask section (bits only inside K x K) and the padding follow the band call's rules; 64
+ * zero bytes if that frame failed; a set bit of level 0 is cleared.  *d_last_bytes is its length, and
+ * nothing is written past it.  last_capacity must be at least svc_hip_levels_max_bytes(1, ...), the
+ * rule of svc_hip_decode_delta_levels_frames, so a player's two ping-pong buffers serve both calls.  A
+ * call cut in two at any frame, the second given the first's d_last, writes the pictures of one call.
+ * A band-sized chain holds nothing outside K x K: it CANNOT move to a larger K (a smaller reduce, or
+ * the full-size calls) without a key frame or a full-size d_prev.  d_last must not overlap d_prev or
+ * d_frames: this is NOT checked.
+ *
+ * Geometry, limits and alignments are those of svc_hip_decode_delta_levels_frames; reduce is 2, 4 or
+ * 8.  Checked, for any n_frames, in this order: geometry, steps (0: SVC_ERR_INVALID_ARG), reduce
+ * (anything else: SVC_ERR_INVALID_ARG), display size (0 x 0, or 1 .. the padded size / reduce),
+ * limits, workspace, then last_capacity where d_last is given; n_frames == 0 then returns SVC_OK and
+ * leaves d_last untouched; then pointers.  The query returns 0 where the call refuses.  Only enqueues
+ * work; the number of launches does not depend on n_frames.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_decode_delta_levels_reduced_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                             uint32_t block_w, uint32_t block_h,
+                                                             uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_decode_delta_levels_reduced_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                               const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                               const uint8_t* d_prev /* one reconstructed SVCQ frame or its band (0, 0, K, K); NULL: frame 0 is a key frame */,
+                                               uint64_t prev_bytes,
+                                               const uint32_t* d_key /* [n_frames], as the delta call took it */,
+                                               uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                               uint32_t mv_block_w, uint32_t mv_block_h,
+                                               uint32_t fg_step, uint32_t bg_step, uint32_t reduce,
+                                               const uint32_t* d_gaze /* [n_frames][4] or NULL */,
+                                               uint8_t* d_workspace, uint64_t workspace_bytes,
+                                               float* d_rec /* [n_frames][frame_h / reduce][frame_w / reduce][3] */,
+                                               uint8_t* d_display /* [n_frames][display_h][display_w][3] or NULL */,
+                                               uint32_t display_w, uint32_t display_h,
+                                               uint8_t* d_last /* the band (0, 0, K, K) of the last frame, reconstructed; NULL: not wanted */,
+                                               uint64_t last_capacity,
+                                               uint64_t* d_last_bytes /* [1] */,
+                                               uint32_t* d_status /* [n_frames] */, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * A delta stream straight from pixels: svc_hip_dct_pack_levels_frames and
  * svc_hip_delta_levels_frames in one call, without the plain stream in between.
  *

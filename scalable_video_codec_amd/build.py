@@ -131,6 +131,7 @@ DROPIN_APPS = [
     "stream_layers_main",   # two layers: compact + enh_step, and svc::StreamDecoder::DecodeLayers on them: tests/test_gpu_stream_layers.py
     "stream_layers_reduced_main",  # DecodeLayers with StreamDecoderConfig::reduce on stream_layers_main's files: tests/test_gpu_decode_layers_reduced.py
     "stream_delta_main",    # svc::StreamDecoder::DecodeDelta: a delta stream (SVCQ or SVCE) -> display frames, tests/test_gpu_stream_delta.py
+    "stream_delta_reduced_main",  # svc::StreamDecoder::DecodeDeltaReduced: a delta stream or its band -> display frames at 1/2, 1/4, 1/8 size, tests/test_gpu_stream_delta_reduced.py
     "stream_delta_encode_main",  # StreamEncoderConfig::delta: a raw clip -> the delta stream and its key flags, tests/test_gpu_stream_delta_encode.py
     "wire_decode_main",     # svc::StreamDecoder::DecodeWire: a reference stream on stdin -> display frames, tests/test_gpu_decode_records.py
     "wire_transcode_main",  # svc::WireTranscoder: a reference stream on stdin -> the compact stream, and back: tests/test_gpu_wire_transcode.py

@@ -80,8 +80,9 @@ struct StreamDecoder::Impl {
   bool svce = false;        // Decode: the stream is SVCE, decoded to SVCQ in q first
   bool layered = false;     // the buffers are sized for DecodeLayers
   bool enh_svce = false;    // DecodeLayers: the enhancement stream is SVCE, decoded to SVCQ in eq first
-  bool delta = false;       // the buffers are sized for DecodeDelta
-  DevBuf<uint8_t> chain[2]; // DecodeDelta: the last reconstructed frame of a batch, the next batch's frame before (the kernels' stream only)
+  bool delta = false;       // the buffers are sized for DecodeDelta or DecodeDeltaReduced
+  uint32_t red = 0;         // the reduce the buffers are sized for (0 = none yet)
+  DevBuf<uint8_t> chain[2]; // DecodeDelta: the last reconstructed frame of a batch (DecodeDeltaReduced: its band), the next batch's frame before
   DevBuf<uint64_t> chain_len;     // its length, as the device call writes it ...
   PinBuf<uint64_t> pin_chain_len; // ... and where the host reads it
   uint64_t chain_bytes = 0;
@@ -100,12 +101,14 @@ struct StreamDecoder::Impl {
 
   // layers: for DecodeLayers (the workspace of svc_hip_decode_layers_frames, which the reduced call shares; enh_entropy = the enhancement
   // stream is SVCE)
-  // chained: for DecodeDelta (the workspace of svc_hip_decode_delta_levels_frames and the two frames of the chain)
-  void Size(const uint32_t* hdr, bool entropy, bool layers = false, bool enh_entropy = false, bool chained = false) {
+  // chained: for DecodeDelta and DecodeDeltaReduced (the workspace of svc_hip_decode_delta_levels_frames, which the reduced call shares,
+  // and the two frames of the chain); reduce: 0 = the configured one, else DecodeDeltaReduced's argument
+  void Size(const uint32_t* hdr, bool entropy, bool layers = false, bool enh_entropy = false, bool chained = false, uint32_t reduce = 0) {
+    if (!reduce) reduce = c.reduce;
     const uint32_t w = hdr[kHWidth], h = hdr[kHHeight], tw = hdr[kHTileW], th = hdr[kHTileH], mw = hdr[kHMvW], mh = hdr[kHMvH];
-    const uint32_t rw = w / c.reduce, rh = h / c.reduce;  // the picture the display pass reads
+    const uint32_t rw = w / reduce, rh = h / reduce;  // the picture the display pass reads
     const uint32_t want_dw = c.display_w ? c.display_w : rw, want_dh = c.display_h ? c.display_h : rh;
-    if (!wire && entropy == svce && layers == layered && enh_entropy == enh_svce && chained == delta && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
+    if (!wire && entropy == svce && layers == layered && enh_entropy == enh_svce && chained == delta && reduce == red && w == pw && h == ph && tw == bw && th == bh && mw == mbw && mh == mbh && want_dw == dw && want_dh == dh)
       return;
     pipe->SyncStreams();
     const uint64_t need_ws = chained  ? svc_hip_decode_delta_levels_workspace_bytes(c.batch, w, h, tw, th, mw, mh)
@@ -113,8 +116,8 @@ struct StreamDecoder::Impl {
                                       : svc_hip_decode_levels_workspace_bytes(c.batch, w, h, tw, th);
     if (!need_ws) Abi(SVC_ERR_UNSUPPORTED, "no decoder for the first frame's geometry");
     if (want_dw > rw || want_dh > rh)
-      throw std::runtime_error(c.reduce > 1 ? "svc::StreamDecoder: the display size exceeds the padded frame over reduce"
-                                            : "svc::StreamDecoder: the display size exceeds the padded frame");
+      throw std::runtime_error(reduce > 1 ? "svc::StreamDecoder: the display size exceeds the padded frame over reduce"
+                                          : "svc::StreamDecoder: the display size exceeds the padded frame");
     if (entropy || enh_entropy) {
       q_bytes = svc_hip_levels_max_bytes(c.batch, w, h, tw, th, mw, mh);
       ews_bytes = svc_hip_entropy_workspace_bytes(c.batch, w, h, tw, th, mw, mh);
@@ -127,6 +130,7 @@ struct StreamDecoder::Impl {
     layered = layers;
     enh_svce = enh_entropy;
     delta = chained;
+    red = reduce;
     if (chained) {
       chain_bytes = svc_hip_levels_max_bytes(1, w, h, tw, th, mw, mh);
       for (auto& b : chain) b.Alloc(kWho, chain_bytes);
@@ -171,6 +175,9 @@ struct StreamDecoder::Impl {
         r[0] = r[1] = r[2] = r[3] = 0;
     }
   }
+
+  void Delta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce, const Gaze& gaze,
+             const Sink& sink);
 
   void Finish(DecodeStats& st) {
     const BatchPipe::Totals& t = pipe->Finish();
@@ -345,15 +352,29 @@ void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offse
 
 void StreamDecoder::DecodeDelta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, const Gaze& gaze,
                                 const Sink& sink) {
-  Impl& m = *p_;
-  const StreamDecoderConfig& c = m.c;
-  if (c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeDelta does not decode at reduced size (reduce must be 1)");
+  if (p_->c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeDelta does not decode at reduced size (reduce must be 1)");
+  p_->Delta(stream, offsets, n_frames, key, 1, gaze, sink);
+}
+
+void StreamDecoder::DecodeDeltaReduced(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce,
+                                       const Gaze& gaze, const Sink& sink) {
+  if (reduce != 2 && reduce != 4 && reduce != 8) throw std::runtime_error("svc::StreamDecoder: DecodeDeltaReduced takes a reduce of 2, 4 or 8");
+  if (p_->c.reduce != 1 && p_->c.reduce != reduce)
+    throw std::runtime_error("svc::StreamDecoder: DecodeDeltaReduced's reduce is not the configured one (config.reduce must be 1 or the argument)");
+  p_->Delta(stream, offsets, n_frames, key, reduce, gaze, sink);
+}
+
+// DecodeDelta (reduce 1) and DecodeDeltaReduced: one chain through the batches, carried in the two chain buffers -- whole reconstructed
+// frames at reduce 1, their bands (0, 0, K, K) above
+void StreamDecoder::Impl::Delta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce,
+                                const Gaze& gaze, const Sink& sink) {
+  Impl& m = *this;
   if (n_frames == 0) { m.stats = DecodeStats{}; return; }
   if (!stream || !offsets) throw std::runtime_error("svc::StreamDecoder: null stream");
   const uint64_t total = offsets[n_frames];  // the stream's bytes, from offsets[0] on
   uint32_t hdr[kHeaderWords];
   FirstHeader(stream, offsets, n_frames, "", hdr);
-  m.Size(hdr, hdr[kHMagic] == kMagicE, false, false, true);
+  m.Size(hdr, hdr[kHMagic] == kMagicE, false, false, true, reduce);
   const uint32_t B = c.batch;
 
   DecodeStats st;
@@ -394,10 +415,17 @@ void StreamDecoder::DecodeDelta(const uint8_t* stream, const uint64_t* offsets, 
             prev = m.chain[(batch - 1) % 2].p;
             prev_bytes = m.pin_chain_len.p[0];
           }
-          Abi(svc_hip_decode_delta_levels_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh,
-                                                 c.fg_step, c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh,
-                                                 m.chain[batch % 2].p, m.chain_bytes, m.chain_len.p, s.status.p, sk),
-              "svc_hip_decode_delta_levels_frames");
+          if (reduce > 1)
+            Abi(svc_hip_decode_delta_levels_reduced_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh, m.mbw,
+                                                           m.mbh, c.fg_step, c.bg_step, reduce, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p,
+                                                           s.disp.p, m.dw, m.dh, m.chain[batch % 2].p, m.chain_bytes, m.chain_len.p,
+                                                           s.status.p, sk),
+                "svc_hip_decode_delta_levels_reduced_frames");
+          else
+            Abi(svc_hip_decode_delta_levels_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh,
+                                                   c.fg_step, c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh,
+                                                   m.chain[batch % 2].p, m.chain_bytes, m.chain_len.p, s.status.p, sk),
+                "svc_hip_decode_delta_levels_frames");
           if (first + cnt < n_frames)
             Hip(hipMemcpyAsync(m.pin_chain_len.p, m.chain_len.p, sizeof(uint64_t), hipMemcpyDeviceToHost, sk), "hipMemcpyAsync D2H chain length");
         },

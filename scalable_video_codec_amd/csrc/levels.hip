@@ -51,6 +51,9 @@
 // each carry a group of tiles in three planes through all frames -- the undelta's add into levels held in LDS and the decode's passes on
 // them -- and, for the chain's last frame as an SVCQ frame, a scan and a write pass (stated at its kernels).
 //
+// decode of a delta stream at reduced size (svc_hip_decode_delta_levels_reduced_frames): the same passes around a kernel of the reduced
+// decode's shape that carries only the first K x K levels of every tile through the frames, in registers (stated at its kernel).
+//
 // pack of two layers (svc_hip_pack_layers_frames): the pack's count, scan and scatter on raw planes with two quantisations per coefficient,
 // the frame offsets from frame_offsets_kernel with a job per layer (stated at its kernels).
 //
@@ -2285,6 +2288,172 @@ __global__ __launch_bounds__(256) void decode_delta_last_write_kernel(DecodeDelt
   split_frame_edges(g, fc, args.last, src[kHFgStep], src[kHBgStep], args.last_head[0], args.last_head[1]);
 }
 
+// ---- decode of a delta stream at reduced size (svc_hip_decode_delta_levels_reduced_frames; include/svc_hip.h states it) ------------------
+//
+// The delta chain is per coefficient, so a decoder of the first K x K coefficients carries only those through time.  The passes in front
+// and the workspace are decode_delta_kernel's; the workgroup is decode_reduced_kernel's: thread (t, j < K) for the group's tiles in all
+// three planes, and like decode_delta_kernel's it walks ALL frames of the call.  A thread owns the same K coefficients -- row j of tile t
+// -- of each plane in every frame, so the held levels are 3 K registers per thread: no level is held in LDS, and no other thread ever
+// needs them.  Per frame, wave 0 loads and scans the delta frame's mask words of the three planes (decode_reduced_kernel's first step);
+// after a barrier the thread gathers its K differences by rank, adds them modulo 2^16 to what it holds if its own tile is predicted (else
+// to 0: a key frame, d_prev, a tile whose step changed), dequantises and runs idct_core.hpp's reduced row pass; after a second barrier,
+// the column pass and the store.  Those two barriers also order the job arrays and the slab between frames: wave 0 writes frame i + 1's
+// words only after every wave has passed frame i's second barrier, behind its gather.  The held int16 is the level decode_reduced_kernel
+// would gather from the undelta's output, so d_rec has the bits of svc_hip_undelta_levels_frames + svc_hip_decode_levels_reduced_frames.
+// Levels outside K x K are never read: the frames and d_prev may be their band (0, 0, K, K).
+//
+// d_last, the band (0, 0, K, K) of the call's last frame as an SVCQ frame, goes through decode_delta_kernel's scan and write passes: the
+// threads put their rows' non-zero bits to LDS, wave 0 makes the group's full-size mask words of them (bits only inside K x K), stores
+// them and their count, and every thread puts its non-zero levels at their rank in the group's run in the workspace.
+// (args.rec: [n][h K / N][w K / N][3])
+template <int N, int K>
+__global__ __launch_bounds__(reduced_threads(N, K)) void decode_delta_reduced_kernel(DecodeDeltaArgs args) {
+  constexpr uint32_t kTiles = kGroupCoeffs / (N * N), kWords = N * N / 64, kJobs = kTiles * kWords;  // tiles and mask words of a group
+  constexpr uint32_t kRowsPerWord = 64 / N;  // coefficient rows of a tile in one mask word
+  static_assert(kJobs <= 64, "one wave scans a group's mask words");
+  __shared__ uint64_t job_mask[3][kJobs];
+  __shared__ uint32_t job_base[3][kJobs];
+  __shared__ uint32_t row_bits[3][kTiles * K];  // the last frame's non-zero levels of a thread's row, bit i = coefficient i
+  __shared__ double rows[3][kTiles * K * (K + 1)];
+  const DeltaArgs& a = args.d;
+  const Geom& g = a.in.g;
+  const uint32_t gi0 = blockIdx.x, tid = threadIdx.x;
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t jobs = gr.nt * kWords, per_plane = g.tiles_y * g.gx;
+  const uint32_t t = tid / K, j = tid - t * K;
+  const bool active = t < gr.nt;  // (nt <= kTiles) an idle thread stays in every barrier below
+  const uint32_t rw = g.w / N * K, rh = g.h / N * K;  // the reduced picture; adjacent lanes hold adjacent pixels
+  uint32_t held[3][K];  // the thread's reconstructed levels, as u16
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int q = 0; q < K; ++q) held[c][q] = 0;
+  // frame -1 is d_prev: it is added like a key frame and nothing is decoded for it.  Every condition on a frame is the workgroup's.
+  for (int32_t i = a.prev.in && a.prev.ws.status[0] == kStOk ? -1 : 0; i < (int32_t)a.n; ++i) {
+    const bool seed = i < 0;
+    float* dst = seed ? nullptr : args.rec + (((size_t)i * rh + gr.ty * K) * rw + (gr.t0 + t) * K + j) * 3;
+    if (!seed && a.status[i] != kStOk) {  // zeros; the frame is not read, and the next frame that passes is a key frame
+      if (active) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) {
+          float* p = dst + (size_t)y * rw * 3;
+          p[0] = 0.f; p[1] = 0.f; p[2] = 0.f;
+        }
+      }
+      continue;
+    }
+    const uint8_t* fc = seed ? a.prev.in : a.in.in + a.in.offsets[i];
+    const uint8_t* fp = seed || delta_key(a, (uint32_t)i) ? nullptr : delta_before(a, (uint32_t)i);
+    const uint32_t* first_level = seed ? a.prev.ws.before : a.in.ws.before + (size_t)i * g.groups;
+    if (tid < 64) {  // wave 0: mask 0 past the group's words, no level is read through it
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint64_t m = tid < jobs ? load_mask(group_masks(g, fc, c, gr) + 2 * tid) : 0ull;
+        const uint32_t ex = wave_exclusive_scan((uint32_t)__popcll(m));
+        if (tid < kJobs) { job_mask[c][tid] = m; job_base[c][tid] = ex; }
+      }
+    }
+    bool predicted = false;  // the thread's own tile
+    float enc = 0.f, dec = 1.f;
+    if (active) {
+      const uint32_t* hdr = reinterpret_cast<const uint32_t*>(fc);
+      const uint32_t type = tile_type(g, hdr + kHeaderWords, gr, t);
+      const uint32_t enc_step = type == 0 ? hdr[kHBgStep] : hdr[kHFgStep];
+      predicted = fp && enc_step == tile_step(g, fp, gr, t);
+      if (!seed) {
+        const bool in_gaze = gazed(args.gaze, (uint32_t)i, gr.x0 + t * N, gr.y0);  // the full-size tile origin: one rule for both decoders
+        enc = (float)enc_step;
+        dec = in_gaze ? 1.f : (type == 0 ? args.bg : args.fg);
+      }
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint16_t* levels = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + first_level[c * per_plane + gi0];
+        float v[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+          const uint32_t k = j * N + q, w = t * kWords + (k >> 6), b = k & 63u;
+          const uint64_t mask = job_mask[c][w], below = (1ull << b) - 1;
+          uint32_t lv = predicted ? held[c][q] : 0u;
+          if ((mask >> b) & 1u) lv += levels[job_base[c][w] + (uint32_t)__popcll(mask & below)];
+          lv &= 0xFFFFu;
+          held[c][q] = lv;
+          v[q] = (float)(int16_t)lv * enc;
+        }
+        if (!seed) invert_row_reduced<K>(v, dec, rows[c], t, j);
+      }
+    }
+    __syncthreads();  // (the next frame's words are written behind it; its row passes behind that frame's own first barrier)
+    if (seed || !active) continue;
+    float out[3][K];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) invert_column_reduced<N, K>(rows[c], t, j, out[c]);
+    store_bgr_column<K>(dst, rw, out);
+  }
+  if (!args.last || a.status[a.n - 1] != kStOk) return;  // (the whole workgroup)
+  if (active) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      uint32_t bits = 0;
+#pragma unroll
+      for (int q = 0; q < K; ++q) bits |= (held[c][q] != 0 ? 1u : 0u) << q;
+      row_bits[c][t * K + j] = bits;
+    }
+  }
+  __syncthreads();  // (also: every wave is past the last frame's gather, the job arrays are free)
+  if (tid < 64) {   // wave 0, lane = mask word: the rows of its tile that lie in the word and inside K x K
+    const uint32_t wt = tid / kWords, wi = tid - wt * kWords;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      uint64_t m = 0;
+      if (tid < jobs) {
+#pragma unroll
+        for (uint32_t r = 0; r < kRowsPerWord; ++r) {
+          const uint32_t row = wi * kRowsPerWord + r;
+          if (row < K) m |= (uint64_t)row_bits[c][wt * K + row] << (r * N);
+        }
+      }
+      const uint32_t pc = (uint32_t)__popcll(m), ex = wave_exclusive_scan(pc);
+      if (tid < kJobs) { job_mask[c][tid] = m; job_base[c][tid] = ex; }
+      if (tid < jobs) store_mask(group_masks(g, args.last, c, gr) + 2 * tid, m);
+      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)(ex + pc), 63);
+      if (tid == 0) args.last_cnt[c * per_plane + gi0] = total;
+    }
+  }
+  __syncthreads();
+  if (!active) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    uint16_t* run = args.last_runs + (size_t)(c * per_plane + gi0) * args.cap;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      const uint32_t k = j * N + q, w = t * kWords + (k >> 6), b = k & 63u;
+      const uint64_t mask = job_mask[c][w], below = (1ull << b) - 1;
+      if (held[c][q] != 0) run[job_base[c][w] + (uint32_t)__popcll(mask & below)] = (uint16_t)held[c][q];
+    }
+  }
+}
+
+template <int N, int K>
+void launch_decode_delta_reduced(dim3 grid, hipStream_t s, const DecodeDeltaArgs& a) {
+  hipLaunchKernelGGL((decode_delta_reduced_kernel<N, K>), grid, dim3(reduced_threads(N, K)), 0, s, a);
+}
+
+// the instantiation for a block of 8 or 16 and a reduce of 2, 4 or 8 (both checked by the caller)
+void launch_decode_delta_reduced(uint32_t block, uint32_t reduce, dim3 grid, hipStream_t s, const DecodeDeltaArgs& a) {
+  if (block == 8) {
+    if (reduce == 2) launch_decode_delta_reduced<8, 4>(grid, s, a);
+    else if (reduce == 4) launch_decode_delta_reduced<8, 2>(grid, s, a);
+    else launch_decode_delta_reduced<8, 1>(grid, s, a);
+  } else {
+    if (reduce == 2) launch_decode_delta_reduced<16, 8>(grid, s, a);
+    else if (reduce == 4) launch_decode_delta_reduced<16, 4>(grid, s, a);
+    else launch_decode_delta_reduced<16, 2>(grid, s, a);
+  }
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -3241,6 +3410,65 @@ int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_
   }
   return finish_with_display(what, d_last ? "write of the last frame" : "reconstruction", display, d_rec, d_display, n_frames, frame_w,
                              frame_h, display_w, display_h, s);
+}
+
+// (the workspace of svc_hip_decode_delta_levels_frames: a group's run of the last frame is placed at its full-size worst case)
+uint64_t svc_hip_decode_delta_levels_reduced_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                             uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h) {
+  if (validate_decode_geom("decode_delta_levels_reduced_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_limits("decode_delta_levels_reduced_workspace_bytes", n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))
+    return 0;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  return layout_bytes(decode_delta_ws, n_frames, g.groups, g.tpg * block_w * block_h);
+}
+
+// Checked in the order of svc_hip_decode_levels_reduced_frames, then last_capacity; n_frames == 0 then returns SVC_OK; then pointers.  The
+// launches are those of svc_hip_decode_delta_levels_frames.
+int svc_hip_decode_delta_levels_reduced_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets,
+                                               uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key,
+                                               uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                               uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, uint32_t reduce, const uint32_t* d_gaze,
+                                               uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec, uint8_t* d_display,
+                                               uint32_t display_w, uint32_t display_h, uint8_t* d_last, uint64_t last_capacity,
+                                               uint64_t* d_last_bytes, uint32_t* d_status, void* stream) {
+  const char* what = "decode_delta_levels_reduced";
+  int rc = validate_reduced(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, reduce, display_w,
+                            display_h);
+  if (rc) return rc;
+  const uint32_t rw = frame_w / reduce, rh = frame_h / reduce;  // whole: the sides are multiples of the block, the block of `reduce`
+  const bool display = display_w != 0 || display_h != 0;
+  const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+  const uint32_t cap = g.tpg * block_w * block_h;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(decode_delta_ws, n_frames, g.groups, cap)))) return rc;
+  if (d_last && (rc = require_capacity(what, "last frame", last_capacity,
+                                       frame_layout(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h).max_bytes)))
+    return rc;
+  if (n_frames == 0) return SVC_OK;
+  SVC_REQUIRE(d_frames && d_frame_offsets && d_workspace && d_rec && d_status, "%s: null pointer", what);
+  SVC_REQUIRE((d_last != nullptr) == (d_last_bytes != nullptr), "%s: the last frame and its length go together", what);
+  if ((rc = validate_display_buffer(what, display, d_display))) return rc;
+  SVC_REQUIRE(aligned(d_frames, 16) && aligned(d_prev, 16) && aligned(d_last, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_last_bytes, 8) && aligned(d_key, 4) && aligned(d_gaze, 4) && aligned(d_rec, 4) && aligned(d_status, 4),
+              "%s: streams, the frame before, the last frame and workspace must be 16-byte aligned, offsets and the last frame's length "
+              "8-byte, key flags, gaze, output and status 4-byte",
+              what);
+  const DecodeDeltaWs ws = carve(d_workspace, decode_delta_ws, n_frames, g.groups, cap);
+  const DecodeDeltaArgs a{{{g, d_frames, stream_bytes, d_frame_offsets, n_frames, nullptr, nullptr, nullptr, nullptr, d_status, ws.in},
+                           {g, d_prev, prev_bytes, ws.prev_offsets, 1, nullptr, nullptr, nullptr, nullptr, ws.prev_code, ws.prev},
+                           d_key, n_frames, nullptr, nullptr, nullptr, ws.status},
+                          d_gaze, d_rec, (float)fg_step, (float)bg_step, d_last, d_last_bytes, ws.last_cnt, ws.last_first, ws.last_head,
+                          ws.last_runs, cap};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = enqueue_delta_input(what, a.d, true, prev_bytes, s))) return rc;
+  launch_decode_delta_reduced(block_w, reduce, dim3(g.tiles_y * g.gx), s, a);
+  if (d_last) {
+    if ((rc = check_launch(what, "reconstruction"))) return rc;
+    hipLaunchKernelGGL(decode_delta_last_scan_kernel, dim3(1), dim3(kThreads), 0, s, a);
+    if ((rc = check_launch(what, "scan of the last frame"))) return rc;
+    hipLaunchKernelGGL(decode_delta_last_write_kernel, dim3(div_up(g.groups, kThreads / 64)), dim3(kThreads), 0, s, a);
+  }
+  return finish_with_display(what, d_last ? "write of the last frame" : "reconstruction", display, d_rec, d_display, n_frames, rw, rh,
+                             display_w, display_h, s);
 }
 
 uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,

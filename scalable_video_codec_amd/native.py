@@ -178,6 +178,10 @@ SIGNATURES = {
     "svc_hip_decode_delta_levels_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_decode_delta_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 8 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32,
                                                      _vp, _u64, _vp, _vp, _vp]),
+    # ... at reduced size: the undelta and the reduced decode in one call, on the first K x K levels of every tile (csrc/levels.hip)
+    "svc_hip_decode_delta_levels_reduced_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_decode_delta_levels_reduced_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 9 +
+                                                   [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     # a stored SVCE stream restricted to a window per output frame, on its coded bytes (csrc/entropy.hip; host statement: entropy.window_frames)
     "svc_hip_window_entropy_max_bytes": (_u64, [_u32] * 7),
     "svc_hip_window_entropy_workspace_bytes": (_u64, [_u32] * 7),
@@ -1484,6 +1488,56 @@ def decode_delta_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: i
     _check(load().svc_hip_decode_delta_levels_frames(
         _dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, None if prev is None else _dev(prev, torch.uint8),
         0 if prev is None else prev.numel(), None if k is None else _dev(k, torch.int32), w, h, bw, bh, mbw, mbh, fg_step, bg_step,
+        None if g is None else _dev(g, torch.int32), _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
+        None if out_display is None else _dev(out_display, torch.uint8), dw, dh, None if last is None else _dev(last, torch.uint8),
+        0 if last is None else last.numel(), None if last is None else _dev(last_bytes, torch.int64), _dev(status, torch.int32), _stream()))
+    return rec, out_display, status, last, last_bytes
+
+
+def decode_delta_levels_reduced_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:
+    """Scratch of decode_delta_levels_reduced_frames for n frames, at any reduce; 0 for a geometry it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_decode_delta_levels_reduced_workspace_bytes(n, w, h, bw, bh, mbw, mbh))
+
+
+def decode_delta_levels_reduced_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, fg_step: int = 1,
+                                       bg_step: int = 640, reduce: int = 2, prev: Optional[torch.Tensor] = None, key=None, gaze=None,
+                                       display: Optional[Tuple[int, int]] = None, want_last: bool = False,
+                                       rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None,
+                                       last: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                       status: Optional[torch.Tensor] = None
+                                       ) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """A packed delta stream (u8 on the device), or its band (0, 0, K, K) with K = block / reduce, + its offsets -> (rec, display or None,
+    status, last or None, last_bytes or None): undelta_levels_frames and decode_levels_reduced_frames in one call (include/svc_hip.h; the
+    numpy statement is layers.undelta_frames + levels.decode_reduced_frame + layers.band_frames).  rec (frames, H / reduce, W / reduce, 3)
+    f32 B,G,R and display (frames, display_h, display_w, 3) u8 have the bits of those two calls; status (frames,) i32 is the undelta call's.
+    reduce: 2, 4 or 8.  fg_step / bg_step, key, gaze (full-size padded coordinates) and display as decode_delta_levels_frames takes them.
+    prev: None (frame 0 is a key frame), or the reconstructed frame before frame 0 or its band (0, 0, K, K), exactly its bytes.
+    want_last (or a `last` buffer of at least levels_max_bytes(1, ...)): the band (0, 0, K, K) of the reconstructed last frame, the next
+    call's prev once cut to last_bytes (a (1,) i64 tensor on the device).  `last` must not overlap `frames` or `prev`."""
+    n = offsets.numel() - 1
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    dev = frames.device
+    k = None if key is None else torch.as_tensor(key, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    assert k is None or k.numel() == n, "one key flag per frame"
+    if rec is None:
+        rec = torch.empty((n, h // max(reduce, 1), w // max(reduce, 1), 3), dtype=torch.float32, device=dev)
+    dw, dh = display if display is not None else (0, 0)
+    if display is not None and out_display is None:
+        out_display = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=dev)
+    if want_last and last is None:
+        last = torch.empty(max(levels_max_bytes(1, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    last_bytes = None if last is None else torch.zeros(1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(decode_delta_levels_reduced_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    g = None
+    if gaze is not None:
+        g = torch.as_tensor(gaze, dtype=torch.int32).reshape(n, 4).to(dev).contiguous()
+    if status is None:
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    _check(load().svc_hip_decode_delta_levels_reduced_frames(
+        _dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, None if prev is None else _dev(prev, torch.uint8),
+        0 if prev is None else prev.numel(), None if k is None else _dev(k, torch.int32), w, h, bw, bh, mbw, mbh, fg_step, bg_step, reduce,
         None if g is None else _dev(g, torch.int32), _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
         None if out_display is None else _dev(out_display, torch.uint8), dw, dh, None if last is None else _dev(last, torch.uint8),
         0 if last is None else last.numel(), None if last is None else _dev(last_bytes, torch.int64), _dev(status, torch.int32), _stream()))

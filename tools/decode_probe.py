@@ -26,6 +26,15 @@
   python tools/decode_probe.py delta-rate   `rate`'s stream and its delta stream (a key frame every 16) through
                                          tests/dropin/stream_decode_main (Decode) and tests/dropin/stream_delta_main (DecodeDelta), PCIe
                                          included, alternating
+  python tools/decode_probe.py delta-reduced [C3|C5]   `delta`'s streams; per reduce 2, 4, 8, with the display pass (W / r, H / r): the fused
+                                         svc_hip_decode_delta_levels_reduced_frames with and without d_last and on the band (0, 0, K, K) of
+                                         the delta stream, against svc_hip_undelta_levels_frames + svc_hip_decode_levels_reduced_frames,
+                                         against svc_hip_decode_delta_levels_frames with the display pass at that size, and against the
+                                         reduced decode of the plain stream, alternating, device events, the median of three windows; the
+                                         routes' rec and display compared
+  python tools/decode_probe.py delta-reduced-rate   `delta-rate`'s delta stream; per reduce, tests/dropin/stream_delta_reduced_main
+                                         (DecodeDeltaReduced) on the entropy-coded band (0, 0, K, K) and on the full SVCQ delta stream against
+                                         stream_delta_main (DecodeDelta) at full size with the display (W / r, H / r), PCIe included, alternating
 """
 import os
 import subprocess
@@ -441,6 +450,178 @@ def delta_rate() -> None:
                     sys.exit(1)
 
 
+def delta_reduced() -> None:
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native, pipeline
+    cfg = {"C3": configs.C3, "C5": configs.C5}[sys.argv[2] if len(sys.argv) > 2 else "C3"]
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    clip = synth.SynthClip(cfg.width, cfg.height, n + 2, cfg.seed, device=dev)
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(n + 2)]).contiguous()
+    enc = pipeline.ClipEncoder(cfg, n + 2, dev)
+    enc.load_frames(list(frames))
+    enc.step()
+    torch.cuda.synchronize()
+    bgr, types = frames[1:].contiguous(), enc.types.clone()  # n + 1 encoded frames: the frame before the batch, then the batch
+
+    def timed(fn, reps=20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def fmt(t):
+        return f"{np.median(t):.3f} (min {min(t):.3f}, max {max(t):.3f})"
+
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    back, bo = torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ws_u = torch.empty(native.undelta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_x = torch.empty(native.decode_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    ws_f = torch.empty(native.decode_delta_levels_reduced_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    rec_full = torch.empty((n, ph, pw, 3), dtype=torch.float32, device=dev)
+    last = torch.empty(native.levels_max_bytes(1, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    st, st2 = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}; ms per call of {n} frames with the display pass (W / r, H / r), device events over 20 "
+          f"back-to-back calls, the median of three such windows per route, the routes alternating; workspace of the fused call "
+          f"{ws_f.numel() / 1e6:.1f} MB", flush=True)
+    for steps in ((1, 1), (1, 640)):
+        out, offs = native.dct_pack_levels_frames(bgr, block, types, mv, *steps)
+        torch.cuda.synchronize()
+        o = offs.cpu().tolist()
+        prev, stream, so = out[:o[1]].clone(), out[o[1]:o[-1]].clone(), (offs[1:] - offs[1]).contiguous()
+        for name, keys, before in (("a key frame every 16", [1] + [0] * (n - 1), None), ("no key frame", None, prev)):
+            d, do, dst = native.delta_levels_frames(stream, so, pw, ph, block, mv, prev=before, key=keys)
+            torch.cuda.synchronize()
+            assert not dst.any()
+            d = d[:int(do[-1])].clone()
+            for r in (2, 4, 8):
+                k = block // r
+                rw, rh = pw // r, ph // r
+                rec, rec2 = (torch.empty((n, rh, rw, 3), dtype=torch.float32, device=dev) for _ in range(2))
+                disp, disp2 = (torch.empty((n, rh, rw, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+                b, b_offs, bst = native.band_levels_frames(d, do, pw, ph, block, mv, band=[(0, 0, k, k)] * n)  # what a server sends
+                torch.cuda.synchronize()
+                assert not bst.any()
+                b = b[:int(b_offs[-1])].clone()
+                b_prev = None
+                if before is not None:
+                    p, p_offs, _ = native.band_levels_frames(before, torch.tensor([0, before.numel()], dtype=torch.int64, device=dev), pw, ph,
+                                                             block, mv, band=[(0, 0, k, k)])
+                    b_prev = p[:int(p_offs[1])].clone()
+                kw = dict(gaze=None, display=(rw, rh))
+
+                def two():  # the route the fused call replaces
+                    native.undelta_levels_frames(d, do, pw, ph, block, mv, prev=before, key=keys, out=back, out_offsets=bo, workspace=ws_u,
+                                                 status=st2)
+                    native.decode_levels_reduced_frames(back, bo, pw, ph, block, mv, 1, 640, r, rec=rec2, out_display=disp2, workspace=ws_x, **kw)
+
+                def plain():  # the reduced decode on the plain stream the undelta left in `back`: the price of the chain
+                    native.decode_levels_reduced_frames(back, bo, pw, ph, block, mv, 1, 640, r, rec=rec2, out_display=disp2, workspace=ws_x, **kw)
+
+                def full():  # what a small viewer pays today: the full-size fused decode with the display pass at the reduced size
+                    native.decode_delta_levels_frames(d, do, pw, ph, block, mv, 1, 640, prev=before, key=keys, rec=rec_full, out_display=disp2,
+                                                      workspace=ws_f, status=st2, **kw)
+
+                def fused():
+                    native.decode_delta_levels_reduced_frames(d, do, pw, ph, block, mv, 1, 640, r, prev=before, key=keys, rec=rec,
+                                                              out_display=disp, last=last, workspace=ws_f, status=st, **kw)
+
+                def fused_no_last():
+                    native.decode_delta_levels_reduced_frames(d, do, pw, ph, block, mv, 1, 640, r, prev=before, key=keys, rec=rec,
+                                                              out_display=disp, workspace=ws_f, status=st, **kw)
+
+                def on_band():
+                    native.decode_delta_levels_reduced_frames(b, b_offs, pw, ph, block, mv, 1, 640, r, prev=b_prev, key=keys, rec=rec,
+                                                              out_display=disp, workspace=ws_f, status=st, **kw)
+
+                routes = {"two": two, "plain": plain, "full": full, "fused": fused, "no_last": fused_no_last, "band": on_band}
+                for _ in range(2):
+                    for fn in routes.values():
+                        fn()
+                torch.cuda.synchronize()
+                two(), on_band()
+                torch.cuda.synchronize()
+                assert not st.any() and not st2.any() and torch.equal(rec.view(torch.int32), rec2.view(torch.int32)), "the routes differ"
+                assert torch.equal(disp, disp2)
+                t = {name_: [] for name_ in routes}
+                for _ in range(3):
+                    for name_, fn in routes.items():
+                        t[name_].append(timed(fn))
+                m = {k_: float(np.median(v)) for k_, v in t.items()}
+                print(f"stored at {steps}, {name}, reduce {r} ({d.numel() / n / 1e6:.3f} MB per delta frame, {b.numel() / n / 1e6:.3f} in its band): "
+                      f"fused without d_last {fmt(t['no_last'])}; with d_last {fmt(t['fused'])}; on the band stream {fmt(t['band'])}; "
+                      f"undelta + reduced decode {fmt(t['two'])}, fused / two = {m['no_last'] / m['two']:.2f}; full-size fused decode + display "
+                      f"{fmt(t['full'])}, fused / full = {m['no_last'] / m['full']:.2f}; reduced decode of the plain stream {fmt(t['plain'])}, "
+                      f"fused / plain = {m['no_last'] / m['plain']:.2f}", flush=True)
+
+
+def delta_reduced_rate() -> None:
+    """DecodeDeltaReduced on the band SVCE stream and on the full SVCQ stream against DecodeDelta at full size on the same clip, PCIe
+    included: `rate`'s 64 frames, their delta stream (a key frame every 16), its bands and their entropy coding made on the device."""
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native
+    n = 65
+    m = n - 1
+    pw, ph = CFG.padded
+    block, mv = CFG.dct_block, CFG.mv_block
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    here = os.path.join(ROOT, "tests", "dropin")
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        prefix = _stored_stream(d, n)
+        big = torch.from_numpy(np.fromfile(prefix + ".big", np.uint8)).cuda()
+        offs = torch.from_numpy(np.fromfile(prefix + ".offsets", np.uint64).astype(np.int64)).cuda()
+        keys = [int(i % 16 == 0) for i in range(m)]
+        diff, do, st = native.delta_levels_frames(big, offs, pw, ph, block, mv, key=keys)
+        torch.cuda.synchronize()
+        assert not st.any()
+        diff = diff[:int(do[-1])].clone()
+
+        def store(name, data, data_offs):
+            p = os.path.join(d, name)
+            data[:int(data_offs[-1])].cpu().numpy().tofile(p + ".big")
+            data_offs.cpu().numpy().astype(np.uint64).tofile(p + ".offsets")
+            return p, int(data_offs[-1]) / m / 1e6
+
+        dprefix, mb_full = store("delta", diff, do)
+        key_file = os.path.join(d, "key.txt")
+        with open(key_file, "w") as f:
+            f.write("".join(f"{k}\n" for k in keys))
+        print(f"{m} frames: plain stream {big.numel() / m / 1e6:.3f} MB per frame, delta stream (a key frame every 16) {mb_full:.3f}", flush=True)
+        del big
+        for r in (2, 4, 8):
+            k = block // r
+            dw, dh = pw // r, ph // r
+            band, bo, bst = native.band_levels_frames(diff, do, pw, ph, block, mv, band=[(0, 0, k, k)] * m)
+            coded, co, est = native.entropy_encode_frames(band[:int(bo[-1])].clone(), bo, pw, ph, block, mv)
+            torch.cuda.synchronize()
+            assert not bst.any() and not est.any()
+            bprefix, mb_band = store(f"band{r}", coded, co)
+            print(f"reduce {r}: the band (0, 0, {k}, {k}) of the delta stream {int(bo[-1]) / m / 1e6:.3f} MB per frame, entropy-coded {mb_band:.3f}",
+                  flush=True)
+            gaze = os.path.join(d, f"gaze{r}.txt")
+            with open(gaze, "w") as f:
+                for i in range(m):
+                    f.write(f"{(60 + 29 * i) % dw} {(40 + 17 * i) % dh}\n")
+            tail = [gaze, key_file, "16", "3"]
+            for turn in range(3):  # alternating, every run printed: the spread is part of the result
+                for what, name, args in (("band SVCE", "stream_delta_reduced_main", [bprefix, str(m), "0", "0", *tail, str(r), "-"]),
+                                         ("full SVCQ", "stream_delta_reduced_main", [dprefix, str(m), "0", "0", *tail, str(r), "-"]),
+                                         ("full size", "stream_delta_main", [dprefix, str(m), str(dw), str(dh), *tail, "1", "-"])):
+                    p = subprocess.run([os.path.join(here, name), *args], capture_output=True, text=True, timeout=300)
+                    print(f"== {name} ({what}) display {dw}x{dh} batch 16, run {turn} (exit {p.returncode})\n{p.stdout.strip()}\n{p.stderr.strip()}",
+                          flush=True)
+                    if p.returncode != 0:
+                        sys.exit(1)
+
+
 if __name__ == "__main__":
     {"rate": rate, "kernels": kernels, "reduced": reduced, "reduced-rate": reduced_rate, "layers-reduced": layers_reduced,
-     "layers-reduced-rate": layers_reduced_rate, "delta": delta, "delta-rate": delta_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
+     "layers-reduced-rate": layers_reduced_rate, "delta": delta, "delta-rate": delta_rate, "delta-reduced": delta_reduced,
+     "delta-reduced-rate": delta_reduced_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
