@@ -72,6 +72,13 @@ struct StreamEncoderConfig {
                                    // geometry the C ABI refuses, with its message
   uint32_t key_interval = 0;       // with `delta`: the encoded frame with clip index f (as EncodedBatch::first_frame counts: the first
                                    // is 1) is a key frame iff f == 1, or key_interval != 0 and (f - 1) % key_interval == 0
+  bool auto_key = false;           // with `delta` (without it the constructor throws): the key frames are chosen by size on the device
+                                   // (svc_hip_dct_pack_delta_auto_frames): a frame is a key frame iff the rule above forces it, or its
+                                   // difference to the frame before holds at least as many levels as the frame itself -- frame by
+                                   // frame the stream is never larger than `compact` alone or `delta` without key frames.
+                                   // EncodedBatch::compact_key carries the CHOSEN flags, compact_level_counts what they were chosen
+                                   // by.  A frame's choice depends on it and the frame before alone: stream and flags do not
+                                   // depend on batch or depth.  With `entropy` the chosen frames are coded unchanged
   std::function<bool(uint32_t frame, uint32_t xywh[4])> enh_window;  // with enh_step: the window of each encoded frame.  Empty: every
                                    // tile is enhanced (the store-once case: svc_hip_window_levels_frames serves any viewer later).
                                    // Otherwise called on the thread that calls Encode(), while a batch is staged, once per encoded
@@ -103,6 +110,8 @@ struct EncodedBatch {
                                               // when even the last entry is over that frame's budget
   const uint32_t* compact_key = nullptr;      // delta == true: [count] != 0 for a key frame, as svc::StreamDecoder::DecodeDelta and
                                               // svc_hip_undelta_levels_frames take them
+  const uint32_t* compact_level_counts = nullptr;  // auto_key == true: [count][2] the levels of the frame as a key frame and as a
+                                              // difference (equal for a frame without predecessor): svc_hip_dct_pack_delta_auto_frames
   const uint8_t* enhancement = nullptr;           // enh_step != 0: `count` frames of the enhancement stream (SVCQ, or SVCE with entropy),
   const uint64_t* enhancement_offsets = nullptr;  // [count + 1], and
   uint64_t enhancement_bytes = 0;                 // = enhancement_offsets[count]; compact* is then the base.  Lifetime as compact

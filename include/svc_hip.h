@@ -1439,6 +1439,52 @@ int svc_hip_dct_pack_delta_frames(const uint8_t* d_bgr, uint64_t frame_stride_by
                                   void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The delta stream from pixels with the key frames chosen by size.
+ *
+ * svc_hip_dct_pack_delta_frames with the flags it computes itself: frame f is a key frame iff it
+ * has no predecessor (f == 0 and d_prev_bgr NULL), or d_forced[f] != 0, or its difference to the
+ * frame before holds AT LEAST as many non-zero levels as the frame itself.  The mask section of an
+ * SVCQ frame has a fixed size, so the level count decides the frame's size: frame by frame the
+ * output is never larger than svc_hip_dct_pack_levels_frames' nor than this stream with no key
+ * frame.  A tie gives a key frame: the same bytes, and a point of random access.  The levels of the
+ * frame before are a function of its pixels alone, not of how it was coded, so the choice for a
+ * frame does not depend on the choice for any other and a batch cut into two calls at any frame
+ * (d_prev_bgr / d_prev_types as in svc_hip_dct_pack_delta_frames) gives the bytes, flags and counts
+ * of one call.
+ *   d_out, d_frame_offsets   byte for byte svc_hip_dct_pack_delta_frames with d_key = d_key_out
+ *   d_key_out [n]            0 / 1: layers.auto_keys of
+ *   d_level_counts [n][2]    layers.delta_level_counts of svc_hip_dct_pack_levels_frames' stream:
+ *                            [f][0] the frame's levels, [f][1] its difference's (== [f][0] for a
+ *                            frame without predecessor); d_forced does not enter them.  May be NULL
+ * The flags travel beside the stream, as before: every decoder of the delta stream takes them.
+ *
+ * Three steps on the stream: dct_delta_count_kernel<N> walks the delta form's runs, reads no flag,
+ * stops after quantising and stores both counts of a wave's piece per frame to the workspace (no
+ * atomics: a batch's 32 counters share a cache line); a workgroup per frame sums them (u32: any
+ * order gives the same counts) and applies the rule; then svc_hip_dct_pack_delta_frames' own three
+ * launches.  Two transforms per frame where that call has one; measured in
+ * profiles/dct_pack_delta_auto_c3.txt.
+ *
+ * Geometry, limits, the order of the checks, alignments and the pairing of d_prev_bgr and
+ * d_prev_types are those of svc_hip_dct_pack_delta_frames; d_key_out is required, and d_forced,
+ * d_key_out and d_level_counts are 4-byte aligned, checked where that call checks d_key.  The
+ * workspace query returns 0 where the call refuses.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_dct_pack_delta_auto_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                     uint32_t block, uint32_t mv_block_w, uint32_t mv_block_h);
+int svc_hip_dct_pack_delta_auto_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames,
+                                       uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                       const uint32_t* d_block_types /* [n_frames][mv blocks] */,
+                                       uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                                       const uint8_t* d_prev_bgr     /* one frame, the predecessor of frame 0, or NULL */,
+                                       const uint32_t* d_prev_types  /* [mv blocks] of that frame; NULL exactly when d_prev_bgr is */,
+                                       const uint32_t* d_forced      /* [n_frames] != 0: a key frame whatever its size; or NULL */,
+                                       uint8_t* d_workspace, uint64_t workspace_bytes,
+                                       uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets /* [n_frames + 1] */,
+                                       uint32_t* d_key_out /* [n_frames] 0 / 1 */,
+                                       uint32_t* d_level_counts /* [n_frames][2], or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Headless decoder of the reference's own wire stream (Header + one record per tile, the bytes
  * of svc_hip_serialize_frames / svc_hip_dct_records_frames and of the reference's encoder): the
  * reference's Decoder::operator() (libs/decoder.cpp:168-210) without the GUI.  Its records hold

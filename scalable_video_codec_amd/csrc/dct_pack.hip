@@ -48,6 +48,12 @@
 // where the lane's tile is predicted (a lane's 16 coefficients lie in one tile: a predicate per lane from two type reads), keeps the
 // undifferenced levels for the next frame, and stages and walks the differences exactly as the one-layer form does its levels.  A run
 // of R frames costs R + 1 transforms and the grid is that of n / R frames; the scan and the assemble pass are the fused pack's.
+//
+// The same with the key frames chosen by size (svc_hip_dct_pack_delta_auto_frames): a frame is a key frame where its difference holds
+// at least as many levels as the frame itself.  dct_delta_count_kernel<N> is the fifth form of the body, TALLY beside DELTA: the delta
+// form's runs without its flags (both counts of a frame are a function of two input frames), stopped after quantising; a wave stores the
+// two counts of its piece per frame, dct_delta_select_kernel sums them per frame and writes the flags, and the delta form's three
+// launches follow with those flags.
 #include <algorithm>
 #include <type_traits>
 
@@ -162,6 +168,10 @@ struct DeltaRunArgs {
   uint32_t n_frames, run;      // a wave carries frames [r * run, min((r + 1) * run, n_frames))
   uint32_t one_step;           // fg_step == bg_step: every tile of a frame that is not a key frame is predicted
 };
+// what the delta form's counting takes: the same runs (key is not read), and where a wave leaves the two level counts of its piece
+struct DeltaTallyArgs : DeltaRunArgs {
+  uint32_t* tally;  // [runs][waves of a frame][run][2] levels of the piece, levels of its difference to the frame before
+};
 // Frames of a run.  {1, 2, 4, 8} measured at C3 and C5, batches of 16 (profiles/dct_pack_delta_c3.txt has all four): 8 is the fastest
 // or tied in every row -- at C3 / (1, 640) 0.194, 0.163, 0.152, 0.152 ms; at C5 1.065, 0.897, 0.820, 0.790.
 #ifndef SVC_DCT_PACK_DELTA_RUN  // (the probe that measured them builds this file once per value: tools/dct_pack_probe.py delta-encode)
@@ -181,7 +191,7 @@ __device__ __forceinline__ uint32_t pack2(f32x2 q) {  // two levels as int16, th
 
 template <typename K>
 __device__ __forceinline__ bool k_one_step(const K& k) {
-  if constexpr (std::is_same_v<K, DeltaRunArgs>) return k.one_step != 0;
+  if constexpr (std::is_base_of_v<DeltaRunArgs, K>) return k.one_step != 0;
   else return false;
 }
 
@@ -209,13 +219,19 @@ __device__ __forceinline__ uint32_t sub2(uint32_t a, uint32_t b) {
 // the ladder's end on), and a histogram per wave (null for the pack).  LAYERS = true (with COUNT = false): the fused pack of two layers,
 // the base into a.ws and the residuals of the tiles inside the frame's window into k.enh.  DELTA = true (alone): the fused pack of
 // differences; a.total_waves counts runs where the other forms count frames, and the wave goes through its run's frames in turn.
-template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false>
+// TALLY = true (with DELTA): the delta form's runs, stopped after quantising: no flag is read, nothing is staged or walked; per frame
+// the wave stores the non-zero levels and the non-zero differences of its piece to its own place in k.tally
+// (svc_hip_dct_pack_delta_auto_frames sums and chooses by them).
+template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false>
 __device__ __forceinline__ void dct_pack_body(
     const DctPackArgs& a,
-    const std::conditional_t<COUNT, CountArgs, std::conditional_t<LAYERS, LayerArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>& k,
+    const std::conditional_t<COUNT, CountArgs,
+                             std::conditional_t<LAYERS, LayerArgs,
+                                                std::conditional_t<TALLY, DeltaTallyArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>>& k,
     float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
   static_assert(!(COUNT && LAYERS), "the counting form has no layers");
   static_assert(!(DELTA && (COUNT || LAYERS)), "the delta form is one layer at fixed steps");
+  static_assert(!TALLY || DELTA, "the tally walks the delta form's runs");
   constexpr uint32_t kCols = 64 / N;        // segment columns of a wave
   constexpr uint32_t kColWords = N / 4;     // mask words of a segment column: two 8x8 tiles of one word, or one 16x16 tile of four
   constexpr int kSlab = N == 8 ? kSlab8 : kSlab16;
@@ -264,7 +280,8 @@ __device__ __forceinline__ void dct_pack_body(
   const uint32_t* frame_types = nullptr;
   if constexpr (DELTA) {
     const uint32_t f = run_first + (uint32_t)max(it, 0);  // the frame whose flag decides this trip
-    key = (f == 0 && !k.prev_bgr) || (k.key && k.key[f] != 0);
+    if constexpr (TALLY) key = f == 0 && !k.prev_bgr;  // no flag is read: the frame in front of a run is always transformed
+    else key = (f == 0 && !k.prev_bgr) || (k.key && k.key[f] != 0);
     if (it < 0 && key) continue;  // (`before` is not read)
     const bool outside = it < 0 && run_first == 0;  // the frame in front of frame 0
     frame_bgr = outside ? k.prev_bgr : a.bgr + (size_t)frame * a.frame_stride;
@@ -309,6 +326,7 @@ __device__ __forceinline__ void dct_pack_body(
   const uint32_t word0 = (seg0 * (16 / N)) * gm.l.words;               // the piece's first word within its tile row
   // DELTA: the lane's tile is predicted where both frames code it at one step
   const bool predicted = DELTA && !key && (k_one_step(k) || (t == 0) == (t_before == 0));
+  uint32_t tally = 0;  // TALLY: this lane's non-zero levels of the frame (at most 48) in the low half, non-zero differences in the high
 
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -406,6 +424,14 @@ __device__ __forceinline__ void dct_pack_body(
         before[c][v] = cur;
       }
       if (it < 0) continue;  // the frame in front of the run is not packed
+      if constexpr (TALLY) {  // (before[c] holds the frame's levels, lv their differences where predicted: the int16 halves that are not 0)
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+          const uint32_t cur = before[c][v], d = lv[v];
+          tally += ((cur & 0xFFFFu) != 0) + ((cur >> 16) != 0) + ((((d & 0xFFFFu) != 0) + ((d >> 16) != 0)) << 16);
+        }
+        continue;  // (the slabs are free for the next channel: the sync above)
+      }
     }
 
     // a layer of this channel: the lane's levels q to the column's tile images, then the wave's walk into the layer's workspace.  The
@@ -454,6 +480,14 @@ __device__ __forceinline__ void dct_pack_body(
       wave_lds_sync();  // the slabs are rewritten: by the next layer's images, or by the next channel
     }
   }
+  if constexpr (TALLY) {  // a wave's 64 x 48 coefficients: both sums fit their halves.  A place per wave and frame, no atomics: with
+    // 65 280 adds into the one cache line that holds a batch's 32 counters the call took 0.709 ms at C3 (1, 640), with the stores 0.238
+    // (profiles/dct_pack_delta_auto_c3.txt)
+    if (it >= 0) {
+      const uint32_t sum = wave_sum(tally);
+      if (lane == 0) *reinterpret_cast<uint2*>(k.tally + ((size_t)wv * k.run + (uint32_t)it) * 2) = make_uint2(sum & 0xFFFFu, sum >> 16);
+    }
+  }
   t_before = t;
   } while (DELTA && ++it < (int)run_len);
   if constexpr (COUNT) {  // the wave's row: bins 0 .. len - 2 as they are, bin len - 1 = the lanes' full counts
@@ -477,6 +511,48 @@ __global__ __launch_bounds__(256) void dct_pack_layers_kernel(DctPackArgs a, Lay
 template <int N>
 __global__ __launch_bounds__(256) void dct_pack_delta_kernel(DctPackArgs a, DeltaRunArgs k) {
   dct_pack_body<N, false, false, true>(a, k, nullptr, nullptr);
+}
+
+// the delta form's runs with both level counts of every frame instead of the pack
+template <int N>
+__global__ __launch_bounds__(256) void dct_delta_count_kernel(DctPackArgs a, DeltaTallyArgs k) {
+  dct_pack_body<N, false, false, true, true>(a, k, nullptr, nullptr);
+}
+
+// One workgroup per frame: the waves' counts summed (u32 sums: any order gives the same counts), then the key frame by size,
+// key[f] = forced[f] != 0 or (f == 0 and no frame before) or diff >= plain -- a tie is a key frame; the counts to the caller where asked.
+struct DeltaSelectArgs {
+  const uint32_t* tally;   // as DeltaTallyArgs::tally
+  const uint32_t* forced;  // [n] or null
+  uint32_t* key;           // [n]
+  uint32_t* counts;        // [n][2] or null
+  uint32_t waves_per_frame, run, has_prev;
+};
+__global__ __launch_bounds__(256) void dct_delta_select_kernel(DeltaSelectArgs a) {
+  __shared__ uint32_t part[kThreads / 64][2];
+  const uint32_t f = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t* mine = a.tally + (((size_t)(f / a.run) * a.waves_per_frame) * a.run + f % a.run) * 2;  // wave 0 of the frame's run, this frame
+  uint32_t plain = 0, diff = 0;
+  for (uint32_t w = threadIdx.x; w < a.waves_per_frame; w += kThreads) {
+    const uint2 v = *reinterpret_cast<const uint2*>(mine + (size_t)w * a.run * 2);
+    plain += v.x;
+    diff += v.y;
+  }
+  plain = wave_sum(plain);
+  diff = wave_sum(diff);
+  if (lane == 0) {
+    part[wave][0] = plain;
+    part[wave][1] = diff;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  plain = part[0][0] + part[1][0] + part[2][0] + part[3][0];
+  diff = part[0][1] + part[1][1] + part[2][1] + part[3][1];
+  a.key[f] = ((a.forced && a.forced[f] != 0) || (f == 0 && !a.has_prev) || diff >= plain) ? 1u : 0u;
+  if (a.counts) {
+    a.counts[2 * (size_t)f] = plain;
+    a.counts[2 * (size_t)f + 1] = diff;
+  }
 }
 
 template <int N>
@@ -639,6 +715,30 @@ int enqueue_dct_pack(const char* what, DctPackArgs& a, uint32_t n_frames, uint32
   return enqueue_assemble(what, a, a.ws, n_frames, fg, bg, d_out, d_frame_offsets, s);
 }
 
+// the delta form's three launches: a wave per piece and RUN of k.n_frames frames, then the fused pack's scan and assemble
+int enqueue_dct_pack_delta(const char* what, DctPackArgs& a, const DeltaRunArgs& k, uint32_t fg, uint32_t bg, uint8_t* d_out,
+                           uint64_t* d_frame_offsets, hipStream_t s) {
+  a.total_waves = div_up(k.n_frames, kDeltaRun) * a.g.l.tiles_y * a.g.waves_per_row;
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (a.g.n_block == 8) hipLaunchKernelGGL(dct_pack_delta_kernel<8>, grid, blk, 0, s, a, k);
+  else hipLaunchKernelGGL(dct_pack_delta_kernel<16>, grid, blk, 0, s, a, k);
+  const int rc = check_launch(what, "transform");
+  if (rc) return rc;
+  return enqueue_assemble(what, a, a.ws, k.n_frames, fg, bg, d_out, d_frame_offsets, s);
+}
+
+// the auto call's workspace: the delta call's, then both level counts of every wave's piece of every frame, whole runs
+struct DeltaAutoWs {
+  DctPackWs pack;
+  uint32_t* tally;  // [runs][waves of a frame][kDeltaRun][2]
+};
+DeltaAutoWs delta_auto_ws(Carver& c, uint32_t n, const PackGeom& g) {
+  DeltaAutoWs s;
+  s.pack = pack_ws(c, n, g);
+  s.tally = c.take<uint32_t>(2ull * kDeltaRun * div_up(n, kDeltaRun) * g.l.tiles_y * g.waves_per_row);
+  return s;
+}
+
 }  // namespace
 }  // namespace svc
 
@@ -734,12 +834,70 @@ int svc_hip_dct_pack_delta_frames(const uint8_t* d_bgr, uint64_t frame_stride_by
   a.bg_inv = 1.0f / a.bg_step;
   a.ws = carve(d_workspace, pack_ws, n_frames, g);
   const DeltaRunArgs k{d_prev_bgr, d_prev_types, d_key, n_frames, kDeltaRun, fg_step == bg_step ? 1u : 0u};
-  a.total_waves = div_up(n_frames, kDeltaRun) * g.l.tiles_y * g.waves_per_row;  // a wave per piece and RUN
+  return enqueue_dct_pack_delta("dct_pack_delta", a, k, fg_step, bg_step, d_out, d_frame_offsets, s);
+}
+
+uint64_t svc_hip_dct_pack_delta_auto_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,
+                                                     uint32_t mv_block_h) {
+  if (validate_pack_geom("dct_pack_delta_auto_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits("dct_pack_delta_auto_workspace_bytes", n_frames, g)) return 0;
+  return layout_bytes(delta_auto_ws, n_frames, g);
+}
+
+// Checked as svc_hip_dct_pack_delta_frames, the new pointers where it checks d_key.  Five launches whatever n_frames: the counting
+// kernel, the selection, then that call's own three with d_key_out as their flags.
+int svc_hip_dct_pack_delta_auto_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                       uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                       uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint8_t* d_prev_bgr,
+                                       const uint32_t* d_prev_types, const uint32_t* d_forced, uint8_t* d_workspace, uint64_t workspace_bytes,
+                                       uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets, uint32_t* d_key_out,
+                                       uint32_t* d_level_counts, void* stream) {
+  int rc = validate_pack_geom("dct_pack_delta_auto", frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "dct_pack_delta_auto: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)",
+              (unsigned long long)frame_stride_bytes, 3ull * frame_w * frame_h);
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "dct_pack_delta_auto: quant steps must be positive");
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits("dct_pack_delta_auto", n_frames, g))) return rc;
+  if ((rc = require_workspace("dct_pack_delta_auto", workspace_bytes, layout_bytes(delta_auto_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity("dct_pack_delta_auto", "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets && d_key_out, "dct_pack_delta_auto: null pointer");
+  SVC_REQUIRE((d_prev_bgr == nullptr) == (d_prev_types == nullptr),
+              "dct_pack_delta_auto: the frame before frame 0 is its pixels and its types: d_prev_bgr and d_prev_types are given together or "
+              "not at all");
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_prev_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
+                  aligned(d_block_types, 4) && aligned(d_prev_types, 4) && aligned(d_forced, 4) && aligned(d_key_out, 4) &&
+                  aligned(d_level_counts, 4),
+              "dct_pack_delta_auto: frames, d_prev_bgr, output and workspace must be 16-byte aligned, offsets 8-byte, types, forced flags, key "
+              "flags and level counts 4-byte");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.types = d_block_types;
+  a.fg_step = (float)fg_step;
+  a.bg_step = (float)bg_step;
+  a.fg_inv = 1.0f / a.fg_step;
+  a.bg_inv = 1.0f / a.bg_step;
+  const DeltaAutoWs ws = carve(d_workspace, delta_auto_ws, n_frames, g);
+  a.ws = ws.pack;
+  a.total_waves = div_up(n_frames, kDeltaRun) * g.l.tiles_y * g.waves_per_row;  // a wave per piece and RUN, as the pack below
+  DeltaTallyArgs t{};
+  static_cast<DeltaRunArgs&>(t) = DeltaRunArgs{d_prev_bgr, d_prev_types, nullptr, n_frames, kDeltaRun, fg_step == bg_step ? 1u : 0u};
+  t.tally = ws.tally;
   const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
-  if (block == 8) hipLaunchKernelGGL(dct_pack_delta_kernel<8>, grid, blk, 0, s, a, k);
-  else hipLaunchKernelGGL(dct_pack_delta_kernel<16>, grid, blk, 0, s, a, k);
-  if ((rc = check_launch("dct_pack_delta", "transform"))) return rc;
-  return enqueue_assemble("dct_pack_delta", a, a.ws, n_frames, fg_step, bg_step, d_out, d_frame_offsets, s);
+  if (block == 8) hipLaunchKernelGGL(dct_delta_count_kernel<8>, grid, blk, 0, s, a, t);
+  else hipLaunchKernelGGL(dct_delta_count_kernel<16>, grid, blk, 0, s, a, t);
+  if ((rc = check_launch("dct_pack_delta_auto", "count"))) return rc;
+  const DeltaSelectArgs sel{ws.tally, d_forced, d_key_out, d_level_counts, g.l.tiles_y * g.waves_per_row, kDeltaRun, d_prev_bgr ? 1u : 0u};
+  hipLaunchKernelGGL(dct_delta_select_kernel, dim3(n_frames), blk, 0, s, sel);
+  if ((rc = check_launch("dct_pack_delta_auto", "select"))) return rc;
+  const DeltaRunArgs k{d_prev_bgr, d_prev_types, d_key_out, n_frames, kDeltaRun, fg_step == bg_step ? 1u : 0u};
+  return enqueue_dct_pack_delta("dct_pack_delta_auto", a, k, fg_step, bg_step, d_out, d_frame_offsets, s);
 }
 
 uint64_t svc_hip_dct_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,

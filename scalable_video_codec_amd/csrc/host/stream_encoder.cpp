@@ -49,6 +49,9 @@ struct Slot {
   // delta: the frames' key flags
   DevBuf<uint32_t> key;
   PinBuf<uint32_t> pin_key;
+  // auto_key: the flags the caller's rule forces (key then holds the device's choice), and both level counts of every frame
+  DevBuf<uint32_t> forced, level_counts;
+  PinBuf<uint32_t> pin_forced, pin_level_counts;
   uint32_t frames = 0;  // source frames resident in bgr (the last one carries into the next batch)
   uint32_t encoded = 0, first = 0;
 };
@@ -85,6 +88,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (c.delta && !c.compact) throw std::runtime_error("svc::StreamEncoder: the delta stream is a form of the compact stream");
   if (c.delta && c.compact_budget)
     throw std::runtime_error("svc::StreamEncoder: a byte budget picks each frame's steps, a difference needs the steps of the frame before: not with delta");
+  if (c.auto_key && !c.delta) throw std::runtime_error("svc::StreamEncoder: auto_key chooses the key frames of the delta stream: not without delta");
   if (c.delta && c.enh_step) throw std::runtime_error("svc::StreamEncoder: the delta stream has one layer: not with enh_step");
   if (c.compact && c.wire) throw std::runtime_error("svc::StreamEncoder: compact is a form of the quantised planes, not of the wire records");
   static_cast<EncodeGeometry&>(m) = EncodeGeometry(c.width, c.height, c.levels, m.bw, m.bh);
@@ -129,6 +133,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
     m.pack_ws_bytes = m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
                       : m.layered ? svc_hip_pack_layers_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th)
+                      : c.auto_key ? svc_hip_dct_pack_delta_auto_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh)
                       : c.delta   ? svc_hip_dct_pack_delta_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh)
                                   : svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
     if (!m.packed_bytes || !m.pack_ws_bytes) throw std::runtime_error("svc::StreamEncoder: no compact stream for this geometry");
@@ -171,6 +176,10 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
       if (c.enh_window) { s->window.Alloc(kWho, B * 4); s->pin_window.Alloc(kWho, B * 4); }
     }
     if (c.delta) { s->key.Alloc(kWho, B); s->pin_key.Alloc(kWho, B); }
+    if (c.auto_key) {
+      s->forced.Alloc(kWho, B); s->pin_forced.Alloc(kWho, B);
+      s->level_counts.Alloc(kWho, 2 * B); s->pin_level_counts.Alloc(kWho, 2 * B);
+    }
     if (m.budgeted) { s->budget.Alloc(kWho, B); s->choice.Alloc(kWho, B); s->pin_budget.Alloc(kWho, B); s->pin_choice.Alloc(kWho, B); }
     m.slots.push_back(std::move(s));
   }
@@ -239,6 +248,7 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       b.compact = s.pin_packed.p; b.compact_offsets = s.pin_offsets.p; b.compact_bytes = s.pin_offsets.p[s.encoded];
       b.compact_choice = m.budgeted ? s.pin_choice.p : nullptr;
       b.compact_key = c.delta ? s.pin_key.p : nullptr;
+      b.compact_level_counts = c.auto_key ? s.pin_level_counts.p : nullptr;
     }
     if (m.layered) {
       b.enhancement = s.pin_enh.p; b.enhancement_offsets = s.pin_enh_offsets.p; b.enhancement_bytes = s.pin_enh_offsets.p[s.encoded];
@@ -288,11 +298,14 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         Hip(hipMemcpyAsync(s.window.p, s.pin_window.p, (size_t)encoded * 4 * sizeof(uint32_t), hipMemcpyHostToDevice, si),
             "hipMemcpyAsync windows");
       if (c.delta) {  // the key flags: a function of the clip index alone, so the stream does not depend on how it falls into batches
+        // (auto_key: the flags this rule forces; the device adds its own, a function of a frame and the frame before alone)
+        uint32_t* flags = c.auto_key ? s.pin_forced.p : s.pin_key.p;
         for (uint32_t i = 0; i < encoded; ++i) {
           const uint32_t f = first + i;
-          s.pin_key.p[i] = (f == 1 || (c.key_interval != 0 && (f - 1) % c.key_interval == 0)) ? 1u : 0u;
+          flags[i] = (f == 1 || (c.key_interval != 0 && (f - 1) % c.key_interval == 0)) ? 1u : 0u;
         }
-        Hip(hipMemcpyAsync(s.key.p, s.pin_key.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyHostToDevice, si), "hipMemcpyAsync key flags");
+        Hip(hipMemcpyAsync(c.auto_key ? s.forced.p : s.key.p, flags, (size_t)encoded * sizeof(uint32_t), hipMemcpyHostToDevice, si),
+            "hipMemcpyAsync key flags");
       }
       if (m.budgeted) {  // the budget as it stands now, for every frame of this batch (SetCompactBudget's rule)
         const uint32_t bytes = m.budget.load();
@@ -337,10 +350,16 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         // next by the batch that takes the slot again, depth - 1 >= 2 batches on -- both on this one stream (batch_pipe.hpp), so the
         // read below lies between them.  The first batch of an Encode() has no frame before: its first frame is a key frame.
         const uint32_t* prev_types = carry ? prev->types.p + (size_t)(prev->encoded - 1) * m.blocks : nullptr;
-        Abi(svc_hip_dct_pack_delta_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.fg_step, c.bg_step,
-                                          carry ? s.bgr.p : nullptr, prev_types, s.key.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
-                                          m.packed_bytes, s.offsets.p, sk),
-            "svc_hip_dct_pack_delta_frames");
+        if (c.auto_key)
+          Abi(svc_hip_dct_pack_delta_auto_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.fg_step, c.bg_step,
+                                                 carry ? s.bgr.p : nullptr, prev_types, s.forced.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
+                                                 m.packed_bytes, s.offsets.p, s.key.p, s.level_counts.p, sk),
+              "svc_hip_dct_pack_delta_auto_frames");
+        else
+          Abi(svc_hip_dct_pack_delta_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.fg_step, c.bg_step,
+                                            carry ? s.bgr.p : nullptr, prev_types, s.key.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
+                                            m.packed_bytes, s.offsets.p, sk),
+              "svc_hip_dct_pack_delta_frames");
         if (c.entropy)
           Abi(svc_hip_entropy_encode_frames(s.packed.p, m.packed_bytes, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
                                             s.entropy_ws.p, m.entropy_ws_bytes, s.coded.p, m.coded_bytes, s.coded_offsets.p,
@@ -393,6 +412,12 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         }
         Hip(hipMemcpyAsync(s.pin_enh_offsets.p, c.entropy ? s.enh_coded_offsets.p : s.enh_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, so), "D2H enhancement offsets");
+      }
+      if (c.auto_key) {  // the chosen flags and the counts they were chosen by
+        bytes += (uint64_t)encoded * 3 * sizeof(uint32_t);
+        Hip(hipMemcpyAsync(s.pin_key.p, s.key.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "D2H key flags");
+        Hip(hipMemcpyAsync(s.pin_level_counts.p, s.level_counts.p, (size_t)encoded * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, so),
+            "D2H level counts");
       }
       Hip(hipMemcpyAsync(s.pin_mv.p, s.mv.p, (size_t)encoded * m.blocks * 2 * sizeof(float), hipMemcpyDeviceToHost, so), "D2H mv");
       Hip(hipMemcpyAsync(s.pin_types.p, s.types.p, (size_t)encoded * m.blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "D2H types");

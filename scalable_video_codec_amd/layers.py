@@ -19,6 +19,7 @@ its masks; union_frame / union_frames state svc_hip_union_levels_frames, which j
 
 delta_frame / delta_frames state svc_hip_delta_levels_frames: a frame coded against the frame before it, as the difference of their levels
 in the tiles both code at one step; undelta_frame / undelta_frames state svc_hip_undelta_levels_frames, which adds the frames back up.
+delta_level_counts / auto_keys / delta_auto_frames state the key frames svc_hip_dct_pack_delta_auto_frames chooses by the frame's size.
 
 split_frame / split_frames / split_budget_frames state svc_hip_split_levels_frames and its budgeted form: the stream stored at
 (fine_step, fine_step) alone determines a base frame at any multiples of fine_step and the enhancement frame that lifts it back, in
@@ -409,6 +410,54 @@ def undelta_frames(stream, offsets, keys=None, prev=None) -> Tuple[bytes, np.nda
     for i, fr in enumerate(frames):
         out.append(undelta_frame(fr, None if key[i] else (out[i - 1] if i else prev)))
     return _join(out)
+
+
+# ---- key frames chosen by the SVCQ frame's size (include/svc_hip.h: svc_hip_dct_pack_delta_auto_frames) ------------------------------------
+
+def _level_count(frame: bytes) -> int:
+    return int(np.frombuffer(frame, "<u4", 16)[10])
+
+
+def delta_level_counts(stream, offsets, prev=None) -> np.ndarray:
+    """-> (n, 2) u32: per frame, column 0 the level count of the frame written as a key frame, delta_frame(frame), and column 1 that of
+    delta_frame(frame, predecessor) -- header word 10 of the written frame, so a set mask bit over level 0 counts in neither.  The
+    predecessor of frame i is input frame i - 1, for frame 0 the frame `prev`; a frame without one (frame 0, prev None) has column 1
+    equal to column 0.  No key flag enters the counts: the levels of the frame before are its own, however it is coded, so a row is a
+    function of its frame and that frame's predecessor alone, and a stream cut in two at any frame, the second call with prev = the
+    first's last input frame, gives the rows of one call."""
+    frames = _source_frames(stream, offsets, None)
+    counts = np.zeros((len(frames), 2), np.uint32)
+    for i, fr in enumerate(frames):
+        before = frames[i - 1] if i else prev
+        counts[i, 0] = _level_count(delta_frame(fr))
+        counts[i, 1] = counts[i, 0] if before is None else _level_count(delta_frame(fr, before))
+    return counts
+
+
+def auto_keys(counts, forced=None, has_prev: bool = True) -> np.ndarray:
+    """The key frames chosen by size -> (n,) bool: key[f] = forced[f] != 0 or (f == 0 and not has_prev) or counts[f, 1] >= counts[f, 0],
+    counts as delta_level_counts gives them (forced None: no frame is forced).  The mask section of an SVCQ frame has a fixed size, so
+    the level count decides the frame's size: a frame is differenced exactly where that makes it smaller.  A tie gives a key frame --
+    the same bytes, and a point of random access."""
+    counts = np.asarray(counts).reshape(-1, 2)
+    key = _keys(forced, len(counts)) | (counts[:, 1] >= counts[:, 0])
+    if len(key) and not has_prev:
+        key[0] = True
+    return key
+
+
+def delta_auto_frames(stream, offsets, forced=None, prev=None) -> Tuple[bytes, np.ndarray, np.ndarray, np.ndarray]:
+    """What svc_hip_dct_pack_delta_auto_frames writes, given the stream svc_hip_dct_pack_levels_frames writes from the same frames ->
+    (bytes, offsets (n + 1,) u64, keys (n,) bool, counts (n, 2) u32): delta_frames with the keys auto_keys chose from
+    delta_level_counts.  With forced None every output frame holds min(counts[f]) levels, so frame by frame it is never larger than
+    the plain stream's frame nor than the frame delta_frames writes without key flags; a forced frame is the plain stream's.  The
+    choice for a frame does not depend on the choice for any other, so a stream cut into two calls at any frame, the second with
+    prev = the first's last input frame and its share of `forced`, gives the bytes, keys and counts of one call.
+    undelta_frames(bytes, offsets, keys, prev's reconstruction) gives the stream back."""
+    counts = delta_level_counts(stream, offsets, prev)
+    keys = auto_keys(counts, forced, prev is not None)
+    out, offs = delta_frames(stream, offsets, keys, prev)
+    return out, offs, keys, counts
 
 
 # ---- a stored fine stream split into a base at any steps and its enhancement (include/svc_hip.h: svc_hip_split_levels_frames) ---------

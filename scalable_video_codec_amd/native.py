@@ -126,6 +126,9 @@ SIGNATURES = {
     "svc_hip_dct_pack_levels_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 + [_vp, _u64, _vp, _u64, _vp, _vp]),
     "svc_hip_dct_pack_delta_workspace_bytes": (_u64, [_u32] * 6),
     "svc_hip_dct_pack_delta_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 + [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "svc_hip_dct_pack_delta_auto_workspace_bytes": (_u64, [_u32] * 6),
+    "svc_hip_dct_pack_delta_auto_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 +
+                                           [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "svc_hip_levels_drain": (C.c_int, [_vp, _vp] + [_u32] * 7 + [_vp, _u64, _vp]),
     # its lossless entropy coding, "SVCE" (csrc/entropy.hip; the drain in csrc/levels.hip)
     "svc_hip_entropy_max_bytes": (_u64, [_u32] * 7),
@@ -848,6 +851,50 @@ def dct_pack_delta_frames(bgr: torch.Tensor, block: int, block_types: torch.Tens
                                                 _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
                                                 _dev(offsets, torch.int64), _stream()))
     return out, offsets
+
+
+def dct_pack_delta_auto_workspace_bytes(n: int, w: int, h: int, block: int, mv_block) -> int:
+    """Scratch of dct_pack_delta_auto_frames; 0 for a geometry it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_delta_auto_workspace_bytes(n, w, h, block, mbw, mbh))
+
+
+def dct_pack_delta_auto_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, fg_step: int, bg_step: int,
+                               prev_bgr: Optional[torch.Tensor] = None, prev_types: Optional[torch.Tensor] = None, forced=None,
+                               out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                               keys: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                               workspace: Optional[torch.Tensor] = None
+                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """dct_pack_delta_frames with the key frames chosen by size (include/svc_hip.h, svc_hip_dct_pack_delta_auto_frames): a frame is a
+    key frame iff it has no predecessor, forced[f] != 0, or its difference holds at least as many levels as the frame itself ->
+    (stream u8 of the worst-case size, offsets (frames + 1,) i64, keys (frames,) i32 0 / 1, counts (frames, 2) i32: the frame's levels
+    and its difference's), all on the device.  Stream and offsets are dct_pack_delta_frames' with key = keys; keys and counts are
+    layers.auto_keys and layers.delta_level_counts of dct_pack_levels_frames' stream.  forced: None, or per frame != 0 ((frames,) ints,
+    a tensor or a list).  prev_bgr / prev_types and the geometry as dct_pack_delta_frames."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    dev = bgr.device
+    k = None if forced is None else torch.as_tensor(forced, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    assert k is None or k.numel() == n, "one forced flag per frame"
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if keys is None:
+        keys = torch.empty(n, dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_delta_auto_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    _check(load().svc_hip_dct_pack_delta_auto_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                     _dev(block_types, torch.int32), mbw, mbh, fg_step, bg_step,
+                                                     None if prev_bgr is None else _dev(prev_bgr, torch.uint8),
+                                                     None if prev_types is None else _dev(prev_types, torch.int32),
+                                                     None if k is None else _dev(k, torch.int32),
+                                                     _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
+                                                     _dev(offsets, torch.int64), _dev(keys, torch.int32), _dev(counts, torch.int32),
+                                                     _stream()))
+    return out, offsets, keys, counts
 
 
 def _ladder(ladder) -> Tuple[C.Array, int]:

@@ -65,6 +65,18 @@
                                                    background (the first synthetic frame repeated) under a moving 128 x 128 patch of the clip, region
                                                    ids foreground under the patch.  Then tests/dropin/stream_delta_encode_main on a 33-frame 1080p
                                                    clip, with delta and without, plain and entropy-coded, the list twice
+  python tools/dct_pack_probe.py delta-auto        the delta stream with its key frames chosen by size (svc_hip_dct_pack_delta_auto_frames), at C3 and at C5, a
+                                                   batch of 16 at (1, 640) and (1, 1): the call against svc_hip_dct_pack_delta_frames with fixed
+                                                   flags (a key frame every 16) and against the route a caller has without it --
+                                                   svc_hip_dct_pack_levels_frames + svc_hip_dct_pack_delta_frames with no key frame and the choice
+                                                   per frame from the two offset arrays (the chosen frames are NOT copied together); wall time
+                                                   per call over 20 back-to-back calls, the routes in turn, the median of three; flags and bytes
+                                                   are compared.  Then, on the synthetic clip, on the static background under a moving patch and
+                                                   on 8 frames of the one followed by 8 of the other turned upside down (a cut), raw and
+                                                   entropy-coded bytes per frame of the plain stream, of delta with a key frame every 16 and of
+                                                   delta with the chosen flags, and the frames at which the level-count choice is not the
+                                                   smaller CODED frame with the bytes that costs.  Then tests/dropin/stream_delta_auto_main on a
+                                                   33-frame 1080p clip with auto_key and with delta alone, plain and entropy-coded, the list twice
   python tools/dct_pack_probe.py window-entropy [C3|C5]
                                                    a stored entropy-coded enhancement served under a gaze, the same batch of 16 at
                                                    (1, 640, 1) with a 256 x 256 window per frame: svc_hip_window_entropy_frames on the stored
@@ -561,6 +573,139 @@ def delta_encode() -> None:
         delta_encode_sizes(config)
         torch.cuda.empty_cache()
     delta_encode_stream()
+
+
+def delta_auto_kernels(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out, plain, never, fixed = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(4))
+    offs, plain_offs, never_offs, fixed_offs = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(4))
+    keys = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    ws = torch.empty(native.dct_pack_delta_auto_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    key16 = torch.zeros(n, dtype=torch.int32, device=dev)
+    key16[0] = 1
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}, ms per call (20 back-to-back calls, the routes in turn, the median of three rounds)",
+          flush=True)
+    for fg, bg in ((1, 640), (1, 1)):
+        def auto():
+            native.dct_pack_delta_auto_frames(bgr, block, types, mv, fg, bg, out=out, offsets=offs, keys=keys, counts=counts, workspace=ws)
+
+        def fixed_flags():
+            native.dct_pack_delta_frames(bgr, block, types, mv, fg, bg, key=key16, out=fixed, offsets=fixed_offs, workspace=ws)
+
+        def both_and_choose():
+            native.dct_pack_levels_frames(bgr, block, types, mv, fg, bg, out=plain, offsets=plain_offs, workspace=ws)
+            native.dct_pack_delta_frames(bgr, block, types, mv, fg, bg, out=never, offsets=never_offs, workspace=ws)
+            return (never_offs[1:] - never_offs[:-1]) >= (plain_offs[1:] - plain_offs[:-1])
+
+        auto()
+        fixed_flags()
+        chosen = both_and_choose()
+        sync()
+        k = keys.bool()
+        # a frame's size is its level count rounded up to 16 bytes: where the sizes differ the two choices agree
+        differ = (never_offs[1:] - never_offs[:-1]) != (plain_offs[1:] - plain_offs[:-1])
+        assert torch.equal(k[differ], chosen[differ]) and bool(k[0])
+        want, want_offs = native.dct_pack_delta_frames(bgr, block, types, mv, fg, bg, key=keys)
+        sync()
+        assert torch.equal(offs, want_offs) and torch.equal(out[:int(offs[-1])], want[:int(offs[-1])]), "the bytes differ from the delta call's"
+        t_auto, t_fixed, t_both = _median3([auto, fixed_flags, both_and_choose], sync)
+        print(f"  ({fg}, {bg}): svc_hip_dct_pack_delta_auto_frames {t_auto:.3f}; svc_hip_dct_pack_delta_frames with a key frame every 16 "
+              f"{t_fixed:.3f} ({t_auto / t_fixed:.2f}x); svc_hip_dct_pack_levels_frames + svc_hip_dct_pack_delta_frames + the choice from "
+              f"the offsets {t_both:.3f} ({t_auto / t_both:.2f}x); key frames chosen {int(k.sum())} of {n}; MB per frame auto "
+              f"{int(offs[-1]) / n / 1e6:.4f}, key every 16 {int(fixed_offs[-1]) / n / 1e6:.4f}, plain {int(plain_offs[-1]) / n / 1e6:.4f}",
+              flush=True)
+
+
+def delta_auto_sizes(cfg) -> None:
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    mbw, mbh = native._bwbh(mv)
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    # delta_encode_sizes' static background (the first frame, repeated) under a moving 128 x 128 patch of the clip
+    still = bgr[:1].expand(n, ph, pw, 3).clone()
+    still_types = torch.zeros_like(types).view(n, ph // mbh, pw // mbw)
+    for f in range(n):
+        x, y = 256 + 48 * f, 192 + 16 * f
+        still[f, y:y + 128, x:x + 128] = bgr[f, y:y + 128, x:x + 128]
+        still_types[f, y // mbh:(y + 128) // mbh, x // mbw:(x + 128) // mbw] = 1
+    # a cut: 8 frames of the static clip, then 8 of the synthetic clip turned upside down -- two unrelated pictures at frame 8
+    cut = torch.cat([still[:8], bgr[8:].flip(1)]).contiguous()
+    cut_types = torch.cat([still_types[:8], types.view(n, ph // mbh, pw // mbw)[8:].flip(1)]).reshape(n, -1).contiguous()
+    still_types = still_types.reshape(n, -1).contiguous()
+    key16 = [1] + [0] * (n - 1)
+
+    def coded_sizes(stream, so):
+        _, eo, est = native.entropy_encode_frames(stream, so, pw, ph, block, mv)
+        sync()
+        assert not est.any()
+        return (eo[1:] - eo[:-1]).cpu()
+
+    print(f"{cfg.name} batch of {n}; MB per frame raw / entropy-coded", flush=True)
+    for clip_name, frames, ty in (("the synthetic clip (fresh noise every frame)", bgr, types),
+                                  ("a static background under a moving 128 x 128 patch", still, still_types),
+                                  ("8 static frames, then 8 synthetic ones upside down (a cut)", cut, cut_types)):
+        for fg, bg in ((1, 640), (1, 1)):
+            p, po = native.dct_pack_levels_frames(frames, block, ty, mv, fg, bg)
+            d, do = native.dct_pack_delta_frames(frames, block, ty, mv, fg, bg, key=key16)
+            a, ao, keys, counts = native.dct_pack_delta_auto_frames(frames, block, ty, mv, fg, bg)
+            sync()
+            raw = [int(o[-1]) for o in (po, do, ao)]
+            cp, cd, ca = coded_sizes(p[:raw[0]], po), coded_sizes(d[:raw[1]], do), coded_sizes(a[:raw[2]], ao)
+            k = keys.bool().cpu()
+            assert torch.equal(torch.where(k, cp, cd)[1:], ca[1:])  # (frame 0 is a key frame in all three)
+            best = torch.minimum(cp, cd)
+            wrong = ca > best
+            lost = int((ca - best).sum())
+            print(f"  {clip_name} at ({fg}, {bg}): plain {raw[0] / n / 1e6:.4f} / {int(cp.sum()) / n / 1e6:.4f}, delta with a key frame every 16 "
+                  f"{raw[1] / n / 1e6:.4f} / {int(cd.sum()) / n / 1e6:.4f}, delta with the chosen key frames {raw[2] / n / 1e6:.4f} / "
+                  f"{int(ca.sum()) / n / 1e6:.4f} ({int(k.sum())} key frames: {''.join('K' if v else '.' for v in k.tolist())}); the level-count "
+                  f"choice is not the smaller coded frame at {int(wrong.sum())} of {n} frames, {lost} B in all "
+                  f"({100.0 * lost / max(int(best.sum()), 1):.3f} % of the best coded stream)", flush=True)
+
+
+def delta_auto_stream(frames_n=33) -> None:
+    import subprocess
+    import tempfile
+    cfg = configs.C3
+    exe = os.path.join(ROOT, "tests", "dropin", "stream_delta_auto_main")
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=torch.device("cuda"))
+        raw = os.path.join(d, "clip.raw")
+        with open(raw, "wb") as f:
+            for t in range(frames_n):
+                f.write(clip.frame_bgr(t).cpu().numpy().tobytes())
+        del clip
+        torch.cuda.empty_cache()
+        print(f"{cfg.name}, {frames_n} frames from host memory through svc::StreamEncoder (tests/dropin/stream_delta_auto_main), batch 16, depth 3, "
+              f"key_interval 16; every run printed", flush=True)
+        for turn in range(2):
+            for entropy_coded in (0, 1):
+                for auto_on in (1, 0):
+                    p = subprocess.run([exe, raw, str(cfg.width), str(cfg.height), str(frames_n), str(cfg.levels), str(cfg.dct_block), "16", "3",
+                                        str(cfg.seed), str(auto_on), "16", str(entropy_coded), "-"], capture_output=True, text=True, timeout=300)
+                    print(f"  run {turn} (exit {p.returncode}): {(p.stdout.strip() or p.stderr.strip())}", flush=True)
+                    if p.returncode != 0:
+                        sys.exit(1)
+
+
+def delta_auto() -> None:
+    for config in (configs.C3, configs.C5):
+        delta_auto_kernels(config)
+        torch.cuda.empty_cache()
+    for config in (configs.C3, configs.C5):
+        delta_auto_sizes(config)
+        torch.cuda.empty_cache()
+    delta_auto_stream()
 
 
 def window_entropy(cfg) -> None:
@@ -1233,6 +1378,8 @@ if __name__ == "__main__":
         delta(_cfg(sys.argv, 2))
     elif mode == "delta-encode":
         delta_encode()
+    elif mode == "delta-auto":
+        delta_auto()
     elif mode == "stream-layers":
         stream_layers()
     elif mode == "transcode":
