@@ -119,6 +119,16 @@ class StreamDecoder {
   void DecodeDeltaReduced(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce,
                           const Gaze& gaze, const Sink& sink);
 
+  // DecodeDelta for a delta stream with temporal layers (include/svc_hip.h, "Temporal layers"; svc::StreamEncoderConfig::temporal_period
+  // writes one): frame i hangs on reconstructed frame i - min(lowbit(i), period), period 1, 2 or 4.  The device call is
+  // svc_hip_decode_delta_levels_temporal_frames, the undelta and the decode in one kernel (against the two calls: README,
+  // profiles/temporal_delta_c3.txt); its d_last, frame period * ((n - 1) / period) of a batch, is the next batch's d_prev, so
+  // config.batch must be a multiple of period (else std::runtime_error before any device work, as for another period).  The stream
+  // thinned to every 2^s-th frame (frames and key flags copied) plays with period >> s; period 1 forwards to DecodeDelta.  Everything
+  // else -- SVCQ or SVCE by magic, key flags, schedule, statistics -- is DecodeDelta's; a failure runs down the tree of references.
+  void DecodeDeltaTemporal(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t period,
+                           const Gaze& gaze, const Sink& sink);
+
   // stream: a whole wire stream of `bytes` bytes in host memory, the 32-byte Header (libs/codec.hpp:8-17) first, then frame_count
   // frames of records.  svc_hip_wire_layout decides how it is read (the decoder's padded tile grid, or the reference encoder's
   // unpadded loops); a stream it refuses throws std::runtime_error with its message.  Batches of config.wire_batch frames, the

@@ -1331,6 +1331,97 @@ int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_
                                        uint32_t* d_status /* [n_frames] */, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Temporal layers: a delta stream that can be thinned to 1/2 or 1/4 of its frame rate by dropping
+ * frames.  The three calls above with one more argument, period = 1, 2 or 4 (= 2^T), which changes
+ * only WHICH earlier frame a frame is coded against.  scalable_video_codec_amd/layers.py
+ * (temporal_ref, delta_temporal_frames, undelta_temporal_frames, thin_frames) is the numpy statement.
+ *
+ * Reference frame.  Frame i of a stream is coded against
+ *     ref(i) = i - min(lowbit(i), period)     for i > 0        (lowbit(i) = i & -i)
+ *     ref(0) = the frame at d_prev                              (NULL: none, frame 0 is a key frame)
+ * Frame i has layer 0 if i % period == 0, and else layer T - log2(lowbit(i)); odd frames have layer T
+ * and no frame refers to them.  The frames with i % 2^s == 0 (s <= T) refer only to each other: they
+ * are, byte for byte, the stream of period (period >> s) of the clip thinned to every 2^s-th frame,
+ * with the key flags thinned alike, and where period >> s == 1 the three plain calls take them
+ * unchanged.  A server stores one stream and thins it with svc_hip_window_levels_frames (d_src, no
+ * window); the window and band calls still commute with the delta call.
+ *
+ * Frame i of a CALL must have a stream index that is i modulo period: every call of a stream but the
+ * last holds a multiple of period frames.  The calls cannot check this.  d_prev is the frame at index
+ * -period, the last layer-0 frame of the call before: an input frame for the delta call, a
+ * reconstructed frame for the undelta and decode calls.
+ *
+ * Per frame everything is as the plain calls state it, with "predecessor" read as ref(i): key flags
+ * d_key[i] at any position, the rule for a predicted tile, D and L modulo 2^16, header and types
+ * copied, a set bit of level 0 read as 0.
+ *
+ * d_status [n_frames] u32: the frame's own unpack code if it is not 0; else, for a frame that is not a
+ * key frame and whose reference's status s is not 0, 0x100 | (s & 0xFF).  The reference is an input
+ * frame in the delta call (its own code) and an output frame in the undelta and decode calls (its
+ * final status).  A failure therefore runs down a tree, not a chain: a damaged odd frame harms no
+ * other frame, and a damaged layer-0 frame harms every frame up to the next key frame of layer 0
+ * except those behind a key flag of their own.  Holds for every n_frames the limits admit.
+ *
+ * svc_hip_decode_delta_levels_temporal_frames: d_rec, d_display and d_status are bit for bit
+ * svc_hip_undelta_levels_temporal_frames followed by svc_hip_decode_levels_frames.  d_last receives
+ * the reconstructed frame period * ((n_frames - 1) / period) -- the next call's d_prev -- byte for
+ * byte that output frame of the undelta call (64 zero bytes if it failed).
+ *
+ * period == 1 gives exactly the plain calls' bytes, statuses and pictures (it runs them).  Any other
+ * period than 1, 2, 4: SVC_ERR_INVALID_ARG, checked right after the geometry; the rest of the check
+ * order, the alignments and the workspaces are the plain siblings'.  The queries return 0 where the
+ * calls refuse.  Only enqueues work; the number of launches does not depend on n_frames.
+ * ------------------------------------------------------------------------- */
+uint64_t svc_hip_delta_levels_temporal_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                       uint32_t block_w, uint32_t block_h,
+                                                       uint32_t mv_block_w, uint32_t mv_block_h, uint32_t period);
+int svc_hip_delta_levels_temporal_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                         const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                         const uint8_t* d_prev /* the input frame at index -period; NULL: frame 0 is a key frame */,
+                                         uint64_t prev_bytes,
+                                         const uint32_t* d_key /* [n_frames] or NULL */,
+                                         uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                         uint32_t mv_block_w, uint32_t mv_block_h,
+                                         uint8_t* d_workspace, uint64_t workspace_bytes,
+                                         uint8_t* d_out, uint64_t out_capacity,
+                                         uint64_t* d_out_offsets /* [n_frames + 1] */,
+                                         uint32_t* d_status /* [n_frames] */, void* stream, uint32_t period);
+uint64_t svc_hip_undelta_levels_temporal_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                         uint32_t block_w, uint32_t block_h,
+                                                         uint32_t mv_block_w, uint32_t mv_block_h, uint32_t period);
+int svc_hip_undelta_levels_temporal_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                           const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                           const uint8_t* d_prev /* the reconstructed frame at index -period; NULL: frame 0 is a key frame */,
+                                           uint64_t prev_bytes,
+                                           const uint32_t* d_key /* [n_frames], as the delta call took it */,
+                                           uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                           uint32_t mv_block_w, uint32_t mv_block_h,
+                                           uint8_t* d_workspace, uint64_t workspace_bytes,
+                                           uint8_t* d_out, uint64_t out_capacity,
+                                           uint64_t* d_out_offsets /* [n_frames + 1] */,
+                                           uint32_t* d_status /* [n_frames] */, void* stream, uint32_t period);
+uint64_t svc_hip_decode_delta_levels_temporal_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                                              uint32_t block_w, uint32_t block_h,
+                                                              uint32_t mv_block_w, uint32_t mv_block_h, uint32_t period);
+int svc_hip_decode_delta_levels_temporal_frames(const uint8_t* d_frames, uint64_t stream_bytes,
+                                                const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                                const uint8_t* d_prev /* the reconstructed frame at index -period; NULL: frame 0 is a key frame */,
+                                                uint64_t prev_bytes,
+                                                const uint32_t* d_key /* [n_frames], as the delta call took it */,
+                                                uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                                uint32_t mv_block_w, uint32_t mv_block_h,
+                                                uint32_t fg_step, uint32_t bg_step,
+                                                const uint32_t* d_gaze /* [n_frames][4] or NULL */,
+                                                uint8_t* d_workspace, uint64_t workspace_bytes,
+                                                float* d_rec /* [n_frames][frame_h][frame_w][3] */,
+                                                uint8_t* d_display /* [n_frames][display_h][display_w][3] or NULL */,
+                                                uint32_t display_w, uint32_t display_h,
+                                                uint8_t* d_last /* frame period * ((n_frames - 1) / period), reconstructed; NULL: not wanted */,
+                                                uint64_t last_capacity,
+                                                uint64_t* d_last_bytes /* [1] */,
+                                                uint32_t* d_status /* [n_frames] */, void* stream, uint32_t period);
+
+/* ------------------------------------------------------------------------- *
  * A delta stream straight to display frames at reduced size: svc_hip_undelta_levels_frames and
  * svc_hip_decode_levels_reduced_frames in one call.  The delta chain is per coefficient, so with
  * K = block / reduce only the first K x K levels of every tile are carried through time.

@@ -176,7 +176,7 @@ struct StreamDecoder::Impl {
     }
   }
 
-  void Delta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce, const Gaze& gaze,
+  void Delta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce, uint32_t period, const Gaze& gaze,
              const Sink& sink);
 
   void Finish(DecodeStats& st) {
@@ -353,7 +353,16 @@ void StreamDecoder::DecodeLayers(const uint8_t* base, const uint64_t* base_offse
 void StreamDecoder::DecodeDelta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, const Gaze& gaze,
                                 const Sink& sink) {
   if (p_->c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeDelta does not decode at reduced size (reduce must be 1)");
-  p_->Delta(stream, offsets, n_frames, key, 1, gaze, sink);
+  p_->Delta(stream, offsets, n_frames, key, 1, 1, gaze, sink);
+}
+
+void StreamDecoder::DecodeDeltaTemporal(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t period,
+                                        const Gaze& gaze, const Sink& sink) {
+  if (period != 1 && period != 2 && period != 4) throw std::runtime_error("svc::StreamDecoder: DecodeDeltaTemporal takes a period of 1, 2 or 4");
+  if (p_->c.reduce != 1) throw std::runtime_error("svc::StreamDecoder: DecodeDeltaTemporal does not decode at reduced size (reduce must be 1)");
+  if (p_->c.batch % period != 0)
+    throw std::runtime_error("svc::StreamDecoder: DecodeDeltaTemporal carries the frame at index -period from batch to batch: config.batch must be a multiple of the period");
+  p_->Delta(stream, offsets, n_frames, key, 1, period, gaze, sink);
 }
 
 void StreamDecoder::DecodeDeltaReduced(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce,
@@ -361,13 +370,14 @@ void StreamDecoder::DecodeDeltaReduced(const uint8_t* stream, const uint64_t* of
   if (reduce != 2 && reduce != 4 && reduce != 8) throw std::runtime_error("svc::StreamDecoder: DecodeDeltaReduced takes a reduce of 2, 4 or 8");
   if (p_->c.reduce != 1 && p_->c.reduce != reduce)
     throw std::runtime_error("svc::StreamDecoder: DecodeDeltaReduced's reduce is not the configured one (config.reduce must be 1 or the argument)");
-  p_->Delta(stream, offsets, n_frames, key, reduce, gaze, sink);
+  p_->Delta(stream, offsets, n_frames, key, reduce, 1, gaze, sink);
 }
 
-// DecodeDelta (reduce 1) and DecodeDeltaReduced: one chain through the batches, carried in the two chain buffers -- whole reconstructed
-// frames at reduce 1, their bands (0, 0, K, K) above
+// DecodeDelta (reduce 1), DecodeDeltaTemporal (reduce 1, a period above 1) and DecodeDeltaReduced: one chain through the batches, carried
+// in the two chain buffers -- whole reconstructed frames at reduce 1, their bands (0, 0, K, K) above; with a period the carried frame is
+// the batch's last of layer 0
 void StreamDecoder::Impl::Delta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce,
-                                const Gaze& gaze, const Sink& sink) {
+                                uint32_t period, const Gaze& gaze, const Sink& sink) {
   Impl& m = *this;
   if (n_frames == 0) { m.stats = DecodeStats{}; return; }
   if (!stream || !offsets) throw std::runtime_error("svc::StreamDecoder: null stream");
@@ -421,6 +431,11 @@ void StreamDecoder::Impl::Delta(const uint8_t* stream, const uint64_t* offsets, 
                                                            s.disp.p, m.dw, m.dh, m.chain[batch % 2].p, m.chain_bytes, m.chain_len.p,
                                                            s.status.p, sk),
                 "svc_hip_decode_delta_levels_reduced_frames");
+          else if (period > 1)
+            Abi(svc_hip_decode_delta_levels_temporal_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh, m.mbw,
+                                                            m.mbh, c.fg_step, c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw,
+                                                            m.dh, m.chain[batch % 2].p, m.chain_bytes, m.chain_len.p, s.status.p, sk, period),
+                "svc_hip_decode_delta_levels_temporal_frames");
           else
             Abi(svc_hip_decode_delta_levels_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh, m.mbw, m.mbh,
                                                    c.fg_step, c.bg_step, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p, s.disp.p, m.dw, m.dh,

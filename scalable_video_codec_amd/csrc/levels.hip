@@ -51,6 +51,10 @@
 // each carry a group of tiles in three planes through all frames -- the undelta's add into levels held in LDS and the decode's passes on
 // them -- and, for the chain's last frame as an SVCQ frame, a scan and a write pass (stated at its kernels).
 //
+// temporal layers (svc_hip_delta_levels_temporal_frames, svc_hip_undelta_levels_temporal_frames, svc_hip_decode_delta_levels_temporal_frames):
+// the three calls above with frame i coded against frame i - min(lowbit(i), period) -- the delta's body with another frame before, and the two
+// kernels that rebuild with one held state per temporal layer; the statuses run down a tree.
+//
 // decode of a delta stream at reduced size (svc_hip_decode_delta_levels_reduced_frames): the same passes around a kernel of the reduced
 // decode's shape that carries only the first K x K levels of every tile through the frames, in registers (stated at its kernel).
 //
@@ -1887,9 +1891,15 @@ __device__ __forceinline__ bool delta_key(const DeltaArgs& a, uint32_t i) {
   return (i == 0 && !a.prev.in) || (a.key && a.key[i] != 0);
 }
 
+// The frame that frame i > 0 of a call is coded against (include/svc_hip.h, "Temporal layers"): i - min(lowbit(i), period); period 1,
+// the plain delta stream: i - 1.
+__device__ __forceinline__ uint32_t temporal_ref(uint32_t i, uint32_t period) {
+  return period == 1 ? i - 1 : i - min(i & (0u - i), period);
+}
+
 // the input frame before frame i: d_prev for frame 0.  Only for a frame that is not a key frame
-__device__ __forceinline__ const uint8_t* delta_before(const DeltaArgs& a, uint32_t i) {
-  return i == 0 ? a.prev.in : a.in.in + a.in.offsets[i - 1];
+__device__ __forceinline__ const uint8_t* delta_before(const DeltaArgs& a, uint32_t i, uint32_t period = 1) {
+  return i == 0 ? a.prev.in : a.in.in + a.in.offsets[temporal_ref(i, period)];
 }
 
 // the step of the group's tile t in `frame`: the rule of svc_hip_dct_quant_frames on the frame's own header and types
@@ -1933,8 +1943,9 @@ __global__ __launch_bounds__(64) void delta_status_kernel(DeltaArgs a) {
 
 // WRITE = false: the group's non-zero differences (0 for a frame that fails).  WRITE = true: its mask words and levels and, from the first
 // workgroup of a frame, header, types and padding; dynamic LDS: select_write_lds(cap), cap = the coefficients of a full group
+// `period`: 1 for svc_hip_delta_levels_frames (a constant there), else the temporal call's: the frame before is frame temporal_ref(i).
 template <bool WRITE>
-__global__ __launch_bounds__(256) void delta_kernel(DeltaArgs a, uint32_t cap) {
+__device__ __forceinline__ void delta_body(const DeltaArgs& a, uint32_t cap, uint32_t period) {
   extern __shared__ uint16_t stage[];
   const Geom& g = a.in.g;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, gi = blockIdx.x * (kThreads / 64) + wave, i = blockIdx.y;
@@ -1953,13 +1964,13 @@ __global__ __launch_bounds__(256) void delta_kernel(DeltaArgs a, uint32_t cap) {
   uint32_t cnt = 0;
   if (live) {
     const Group gr = group_of(g, gi);
-    const uint8_t* fp = delta_key(a, i) ? nullptr : delta_before(a, i);  // (its own status is 0: this frame's would not be)
+    const uint8_t* fp = delta_key(a, i) ? nullptr : delta_before(a, i, period);  // (its own status is 0: this frame's would not be)
     const uint32_t* masks_c = group_masks(g, fc, gr.plane, gr);
     const uint32_t* masks_p = fp ? group_masks(g, fp, gr.plane, gr) : nullptr;
     uint32_t* masks_out = WRITE ? group_masks(g, out, gr.plane, gr) : nullptr;
     const uint16_t* lc = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + a.in.ws.before[(size_t)i * g.groups + gi];
     const uint16_t* lp = nullptr;
-    if (fp) lp = reinterpret_cast<const uint16_t*>(fp + g.levels_off) + (i == 0 ? a.prev.ws.before[gi] : a.in.ws.before[(size_t)(i - 1) * g.groups + gi]);
+    if (fp) lp = reinterpret_cast<const uint16_t*>(fp + g.levels_off) + (i == 0 ? a.prev.ws.before[gi] : a.in.ws.before[(size_t)temporal_ref(i, period) * g.groups + gi]);
     const uint32_t jobs = gr.nt * g.words;
     for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {
       const uint32_t j = j0 + lane, n = min(64u, jobs - j0);
@@ -2005,6 +2016,16 @@ __global__ __launch_bounds__(256) void delta_kernel(DeltaArgs a, uint32_t cap) {
   if (blockIdx.x != 0) return;
   const uint32_t* src = reinterpret_cast<const uint32_t*>(fc);
   split_frame_edges(g, fc, out, src[kHFgStep], src[kHBgStep], a.frame_levels[i], a.frame_bytes[i]);
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void delta_kernel(DeltaArgs a, uint32_t cap) {
+  delta_body<WRITE>(a, cap, 1);
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void delta_temporal_kernel(DeltaArgs a, uint32_t cap, uint32_t period) {
+  delta_body<WRITE>(a, cap, period);
 }
 
 // WRITE = false: every frame's count of the group's non-zero levels.  WRITE = true: their mask words and levels and, from the first
@@ -2090,6 +2111,169 @@ __global__ __launch_bounds__(256) void undelta_kernel(DeltaArgs a, uint32_t cap)
     if (blockIdx.x == 0) {
       const uint32_t* src = reinterpret_cast<const uint32_t*>(fc);
       split_frame_edges(g, fc, out, src[kHFgStep], src[kHBgStep], a.frame_levels[i], a.frame_bytes[i]);
+    }
+    __syncthreads();  // the next frame's levels go to buf again
+  }
+}
+
+// ---- temporal layers of the delta stream (svc_hip_delta_levels_temporal_frames, svc_hip_undelta_levels_temporal_frames,
+// svc_hip_decode_delta_levels_temporal_frames; include/svc_hip.h states them) ------------------------------------------------------------
+//
+// Frame i is coded against frame temporal_ref(i) = i - min(lowbit(i), period), period 2 or 4 = 2^T (period 1 takes the calls above).  The
+// frames of layer 0 (i % period == 0) form a chain of their own, those of layer l hang on a frame of a lower layer, and the odd frames
+// (layer T) are referenced by none.  The delta call is delta_kernel's body with that frame before.  The kernels that rebuild keep one
+// state per layer below T: a frame of layer l < T is rebuilt INTO state l from the state of its reference's layer, an odd frame from it
+// into nothing that lasts.  (State l therefore holds the latest frame of layer l, not the latest multiple of 2^(T - l): a frame reads the
+// state of the layer its reference has, which is the same frame, and no frame is stored twice.)  Rebuilt into another state than it reads,
+// a coefficient is written wherever the difference, the reference's mask or the destination's old mask has a bit -- else a level of the
+// frame overwritten would survive.
+
+__device__ __forceinline__ uint32_t temporal_src_state(uint32_t i, uint32_t period) { return period == 4 && (i & 3u) == 3u ? 1u : 0u; }
+// the state frame i is rebuilt into; `none` for an odd frame
+__device__ __forceinline__ uint32_t temporal_dst_state(uint32_t i, uint32_t period, uint32_t none) {
+  const uint32_t r = i & (period - 1);
+  return r == 0 ? 0u : (r == 2 ? 1u : none);
+}
+
+// delta_status_kernel for a period of 2 or 4.  One wave.  Without CHAIN (delta) the frame before is an input frame: its own code.  CHAIN
+// (undelta, decode): the frames of layer 0 are scanned as delta_status_kernel scans all frames; then, layer by layer, every other frame
+// takes the state of its reference, whose final status is in a.status by then -- T steps of independent frames, whatever n.
+template <bool CHAIN>
+__global__ __launch_bounds__(64) void delta_temporal_status_kernel(DeltaArgs a, uint32_t period) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t carry0 = a.prev.in ? a.prev.ws.status[0] & 0xFFu : 0u;
+  auto finish = [&](uint32_t i, uint32_t own, uint32_t e) {
+    const uint32_t st = own != 0 ? own : (e != 0 ? kStEnhancement | e : (uint32_t)kStOk);
+    a.status[i] = st;
+    a.in.d_status[i] = st;
+  };
+  if (!CHAIN) {
+    for (uint32_t i = lane; i < a.n; i += 64) {
+      const uint32_t own = a.in.ws.status[i];
+      const uint32_t before = i == 0 ? carry0 : a.in.ws.status[temporal_ref(i, period)] & 0xFFu;
+      finish(i, own, own != 0 ? own & 0xFFu : (delta_key(a, i) ? 0u : before));
+    }
+    return;
+  }
+  uint32_t carry = carry0;  // of the layer-0 frame before `base`
+  const uint32_t n0 = (a.n + period - 1) / period;
+  for (uint32_t base = 0; base < n0; base += 64) {
+    const uint32_t i = (base + lane) * period;
+    const bool live = base + lane < n0;
+    const uint32_t own = live ? a.in.ws.status[i] : 0u;
+    uint32_t sets = own != 0 || (live && delta_key(a, i)), val = own & 0xFFu;
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+      const uint32_t s2 = __shfl_up(sets, off, 64), v2 = __shfl_up(val, off, 64);
+      if (lane >= off && !sets) sets = s2, val = v2;
+    }
+    const uint32_t e = sets ? val : carry;
+    carry = __shfl(e, 63, 64);
+    if (live) finish(i, own, e);
+  }
+  for (uint32_t stride = period >> 1; stride >= 1; stride >>= 1) {
+    __threadfence();  // the layer below is in a.status
+    __syncthreads();
+    for (uint32_t i = (2 * lane + 1) * stride; i < a.n; i += 128 * stride) {  // lowbit(i) == stride: its reference is i - stride
+      const uint32_t own = a.in.ws.status[i];
+      finish(i, own, own != 0 ? own & 0xFFu : (delta_key(a, i) ? 0u : a.status[i - stride] & 0xFFu));
+    }
+  }
+}
+
+// two waves per workgroup, one where a group is a tile above 2048 coefficients; per wave two states and the frame's run of levels
+constexpr uint32_t temporal_waves(uint32_t cap) { return cap > kGroupCoeffs ? 1 : 2; }
+constexpr uint32_t temporal_lds(uint32_t cap) { return temporal_waves(cap) * 3 * cap * (uint32_t)sizeof(uint16_t); }
+static_assert(temporal_lds(kGroupCoeffs) <= 24576 && temporal_lds(kMaxTileCoeffs) <= 24576,
+              "the temporal undelta holds at most 24 KB of levels per workgroup, and 8 KB of mask words");
+
+// undelta_kernel for a period of 2 or 4: blockDim.x / 64 waves (temporal_waves), a group each through all frames; dynamic LDS
+// temporal_lds(cap): per wave states 0 and 1, [tile][coefficient] u16, then the frame's non-zero levels in order.  Period 2 uses state 0 only.
+template <bool WRITE>
+__global__ __launch_bounds__(128) void undelta_temporal_kernel(DeltaArgs a, uint32_t cap, uint32_t period) {
+  extern __shared__ uint16_t stage[];
+  __shared__ uint64_t state_masks[2][2][kMaxJobs];  // [wave][state][word]
+  constexpr uint32_t kNone = 2;
+  const Geom& g = a.in.g;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, gi = blockIdx.x * (blockDim.x >> 6) + wave;
+  const bool live = gi < g.groups;  // no early return: the barriers below are the workgroup's
+  const Group gr = group_of(g, live ? gi : 0u);
+  const uint32_t jobs = gr.nt * g.words, area = g.bw * g.bh;
+  uint16_t* states = stage + (size_t)wave * 3 * cap;  // a level != 0 exactly where its bit of the state's mask is set
+  uint16_t* buf = states + 2 * cap;
+  for (uint32_t k = lane; k < 2 * cap; k += 64) states[k] = 0;
+  for (uint32_t j = lane; j < jobs; j += 64) state_masks[wave][0][j] = 0, state_masks[wave][1][j] = 0;
+  // frame -1 is d_prev, the frame at index -period: it goes into state 0 like a key frame and nothing is written for it
+  for (int32_t i = a.prev.in && a.prev.ws.status[0] == kStOk ? -1 : 0; i < (int32_t)a.n; ++i) {
+    const bool seed = i < 0;
+    uint8_t* out = WRITE && !seed ? a.in.out + a.in.out_offsets[i] : nullptr;
+    if (!seed && a.status[i] != kStOk) {  // 64 zero bytes; the frame is not read, and no frame that passes hangs on it
+      if (WRITE) {
+        if (blockIdx.x == 0 && threadIdx.x < kHeaderWords) reinterpret_cast<uint32_t*>(out)[threadIdx.x] = 0;
+      } else if (live && lane == 0) {
+        a.cnt[(size_t)i * g.groups + gi] = 0;
+      }
+      continue;
+    }
+    const uint8_t* fc = seed ? a.prev.in : a.in.in + a.in.offsets[i];
+    const uint32_t src = seed ? 0u : temporal_src_state((uint32_t)i, period);
+    const uint32_t dst = seed ? 0u : temporal_dst_state((uint32_t)i, period, kNone);
+    uint32_t cnt = 0;
+    if (live) {
+      const uint8_t* fp = seed || delta_key(a, (uint32_t)i) ? nullptr : delta_before(a, (uint32_t)i, period);
+      const uint32_t* masks_c = group_masks(g, fc, gr.plane, gr);
+      uint32_t* masks_out = out ? group_masks(g, out, gr.plane, gr) : nullptr;
+      const uint16_t* lc = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + (seed ? a.prev.ws.before[gi] : a.in.ws.before[(size_t)i * g.groups + gi]);
+      const uint16_t* from = states + src * cap;
+      uint16_t* into = dst == kNone ? nullptr : states + dst * cap;
+      const uint64_t* from_mask = state_masks[wave][src];
+      uint64_t* into_mask = dst == kNone ? nullptr : state_masks[wave][dst];
+      for (uint32_t j0 = 0; j0 < jobs; j0 += 64) {
+        const uint32_t j = j0 + lane, n = min(64u, jobs - j0);
+        uint64_t x = 0, ref = 0, old = 0;
+        uint32_t slot0 = 0;  // of the word's first coefficient
+        bool predicted = false;
+        if (j < jobs) {
+          const uint32_t t = j / g.words;
+          x = load_mask(masks_c + 2 * j);
+          ref = from_mask[j];
+          if (into_mask) old = into_mask[j];
+          slot0 = t * area + (j - t * g.words) * 64;
+          if (fp) predicted = tile_step(g, fc, gr, t) == tile_step(g, fp, gr, t);
+        }
+        const uint32_t px = (uint32_t)__popcll(x), first_x = wave_exclusive_scan(px);
+        const uint64_t predicted_words = __ballot(predicted);
+        uint64_t keep = 0;  // lane l: the new mask of word j0 + l
+        for (uint32_t k = 0; k < n; ++k) {
+          const uint64_t xk = readlane64(x, k), rk = readlane64(ref, k), any = xk | rk | readlane64(old, k);
+          if (any == 0) continue;  // (the whole wave) nothing to add, nothing to add to and nothing to overwrite: the word stays 0
+          const uint32_t ax = (uint32_t)__builtin_amdgcn_readlane((int)first_x, k);
+          const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)slot0, k) + lane;
+          const uint16_t d = (xk >> lane) & 1u ? lc[ax + lane_rank(xk)] : (uint16_t)0;
+          const uint16_t p = ((predicted_words >> k) & 1u) && ((rk >> lane) & 1u) ? from[slot] : (uint16_t)0;
+          const uint16_t lv = (uint16_t)(d + p);
+          if (into && ((any >> lane) & 1u)) into[slot] = lv;  // (no bit is set past the tile's area: such a frame fails)
+          const uint64_t mk = __ballot(lv != 0);
+          if (lane == k) keep = mk;
+          if (WRITE && out && lv != 0) buf[cnt + lane_rank(mk)] = lv;
+          cnt += (uint32_t)__popcll(mk);
+        }
+        if (j < jobs) {
+          if (into_mask) into_mask[j] = keep;
+          if (masks_out) store_mask(masks_out + 2 * j, keep);
+        }
+        lc += (uint32_t)__builtin_amdgcn_readlane((int)(first_x + px), 63);
+      }
+    }
+    if (seed) continue;
+    if (!WRITE) {
+      if (live && lane == 0) a.cnt[(size_t)i * g.groups + gi] = cnt;
+      continue;
+    }
+    __syncthreads();
+    if (live) store_level_run(buf, cnt, reinterpret_cast<uint16_t*>(out + g.levels_off) + a.cnt[(size_t)i * g.groups + gi]);
+    if (blockIdx.x == 0) {
+      const uint32_t* hdr = reinterpret_cast<const uint32_t*>(fc);
+      split_frame_edges(g, fc, out, hdr[kHFgStep], hdr[kHBgStep], a.frame_levels[i], a.frame_bytes[i]);
     }
     __syncthreads();  // the next frame's levels go to buf again
   }
@@ -2286,6 +2470,125 @@ __global__ __launch_bounds__(256) void decode_delta_last_write_kernel(DecodeDelt
   const uint8_t* fc = a.in.in + a.in.offsets[a.n - 1];
   const uint32_t* src = reinterpret_cast<const uint32_t*>(fc);
   split_frame_edges(g, fc, args.last, src[kHFgStep], src[kHBgStep], args.last_head[0], args.last_head[1]);
+}
+
+// ---- decode of a delta stream with temporal layers (svc_hip_decode_delta_levels_temporal_frames) ----------------------------------------
+//
+// decode_delta_kernel's workgroup with T + 1 dense states in LDS where that kernel has one: states 0 .. T - 1 are the temporal undelta's
+// (the latest rebuilt frame of each layer below T), state T receives the odd frames, which no frame refers to.  Every frame is rebuilt
+// from the state of its reference INTO the state of its own layer -- no copy: the add reads one buffer and writes the other, wherever the
+// difference, the reference's mask or the destination's old mask has a bit -- and the rows are read from the state just written.
+// Static LDS, period 2: 2 x 12.75 KB of states + 18 KB of rows = 43.5 KB, three workgroups (12 waves) per CU; period 4: 3 x 12.75 + 18 =
+// 56.25 KB, two workgroups (8 waves) per CU, where decode_delta_kernel's 30.75 KB admits five.
+//
+// d_last is the frame the next call refers to, period * ((n - 1) / period): state 0 after the last frame.  It goes through
+// decode_delta_last_scan_kernel and decode_delta_last_write_kernel, which are handed that frame as the call's last.
+template <int N, int T>
+__global__ __launch_bounds__(256) void decode_delta_temporal_kernel(DecodeDeltaArgs args, uint32_t last_frame) {
+  constexpr uint32_t kArea = N * N, kWords = kArea / 64, kJobs = kGroupCoeffs / 64;  // a mask word is 64 adjacent levels of a state
+  constexpr uint32_t kRows = kGroupCoeffs / N;
+  constexpr uint32_t kWaves = kThreads / 64;
+  constexpr uint32_t kStates = T + 1, kPeriod = 1u << T;
+  __shared__ uint16_t state[kStates][3][kGroupCoeffs];  // [state][plane][tile][coefficient]: != 0 exactly where its bit of state_mask is set
+  __shared__ uint64_t state_mask[kStates][3][kJobs];
+  __shared__ double rows[kRows * (N + 1)];
+  const DeltaArgs& a = args.d;
+  const Geom& g = a.in.g;
+  const uint32_t gi0 = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t jobs = gr.nt * kWords, per_plane = g.tiles_y * g.gx;
+  const uint32_t t = tid / N, j = tid - t * N;
+  const bool active = t < gr.nt;  // an idle thread stays in every barrier below
+  for (uint32_t k = tid; k < kStates * 3 * kGroupCoeffs; k += kThreads) (&state[0][0][0])[k] = 0;
+  for (uint32_t k = tid; k < kStates * 3 * kJobs; k += kThreads) (&state_mask[0][0][0])[k] = 0;
+  __syncthreads();
+  // frame -1 is d_prev, the frame at index -period: it goes into state 0 like a key frame and nothing is decoded for it
+  for (int32_t i = a.prev.in && a.prev.ws.status[0] == kStOk ? -1 : 0; i < (int32_t)a.n; ++i) {
+    const bool seed = i < 0;
+    float* dst = seed ? nullptr : args.rec + (((size_t)i * g.h + gr.y0) * g.w + gr.x0 + t * N + j) * 3;
+    if (!seed && a.status[i] != kStOk) {  // zeros; the frame is not read, and no frame that passes hangs on it
+      if (active) {
+#pragma unroll
+        for (int y = 0; y < N; ++y) {
+          float* p = dst + (size_t)y * g.w * 3;
+          p[0] = 0.f; p[1] = 0.f; p[2] = 0.f;
+        }
+      }
+      continue;
+    }
+    const uint8_t* fc = seed ? a.prev.in : a.in.in + a.in.offsets[i];
+    const uint8_t* fp = seed || delta_key(a, (uint32_t)i) ? nullptr : delta_before(a, (uint32_t)i, kPeriod);
+    const uint32_t from = seed ? 0u : temporal_src_state((uint32_t)i, kPeriod);
+    const uint32_t into = seed ? 0u : temporal_dst_state((uint32_t)i, kPeriod, (uint32_t)T);
+    const bool same_step = fp && lane < gr.nt && tile_step(g, fc, gr, lane) == tile_step(g, fp, gr, lane);
+    const uint64_t predicted_tiles = __ballot(same_step);  // (a group has at most 32 tiles)
+    const uint32_t* first_level = seed ? a.prev.ws.before : a.in.ws.before + (size_t)i * g.groups;
+#pragma unroll
+    for (uint32_t c = 0; c < 3; ++c) {
+      const uint32_t* masks = group_masks(g, fc, c, gr);
+      const uint16_t* lc = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + first_level[c * per_plane + gi0];
+      const uint64_t x = lane < jobs ? load_mask(masks + 2 * lane) : 0ull;
+      const uint32_t first_x = wave_exclusive_scan((uint32_t)__popcll(x));
+      for (uint32_t k = wave; k < jobs; k += kWaves) {
+        const uint64_t xk = readlane64(x, k), rk = readlane64(state_mask[from][c][k], 0);
+        const uint64_t any = xk | rk | readlane64(state_mask[into][c][k], 0);
+        if (any == 0) continue;  // (the whole wave) nothing to add, nothing to add to and nothing to overwrite: the word stays 0
+        const uint32_t ax = (uint32_t)__builtin_amdgcn_readlane((int)first_x, k), slot = k * 64 + lane;
+        const uint16_t d = bit_of(xk, lane) ? lc[ax + lane_rank(xk)] : (uint16_t)0;
+        const uint16_t p = bit_of(predicted_tiles, k / kWords) && bit_of(rk, lane) ? state[from][c][slot] : (uint16_t)0;
+        const uint16_t lv = (uint16_t)(d + p);
+        if (bit_of(any, lane)) state[into][c][slot] = lv;  // (no bit is set past the tile's area: such a frame fails)
+        const uint64_t mk = __ballot(lv != 0);
+        if (lane == 0) state_mask[into][c][k] = mk;
+      }
+    }
+    __syncthreads();
+    if (seed) continue;
+    float enc = 0.f, dec = 1.f;
+    if (active) {
+      const uint32_t* hdr = reinterpret_cast<const uint32_t*>(fc);
+      const uint32_t type = tile_type(g, hdr + kHeaderWords, gr, t);
+      const bool in_gaze = gazed(args.gaze, (uint32_t)i, gr.x0 + t * N, gr.y0);
+      enc = (float)(type == 0 ? hdr[kHBgStep] : hdr[kHFgStep]);
+      dec = in_gaze ? 1.f : (type == 0 ? args.bg : args.fg);
+    }
+    float out[3][N];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (active) {
+        const uint16_t* row = &state[into][c][t * kArea + j * N];
+        float v[N];
+#pragma unroll
+        for (int q = 0; q < N; ++q) v[q] = (float)(int16_t)row[q] * enc;
+        invert_row<N>(v, dec, rows, t, j);
+      }
+      __syncthreads();
+      if (active) invert_column<N>(rows, t, j, out[c]);
+      if (c < 2) __syncthreads();  // the next plane reuses rows; the next frame writes them only after its own barrier
+    }
+    if (active) store_bgr_column<N>(dst, g.w, out);
+  }
+  if (!args.last || a.status[last_frame] != kStOk) return;  // (the whole workgroup)
+  __syncthreads();
+#pragma unroll
+  for (uint32_t c = 0; c < 3; ++c) {
+    const uint32_t gi = c * per_plane + gi0;
+    const uint64_t m = lane < jobs ? state_mask[0][c][lane] : 0ull;
+    const uint32_t pc = (uint32_t)__popcll(m), first = wave_exclusive_scan(pc);
+    uint16_t* run = args.last_runs + (size_t)gi * args.cap;
+    for (uint32_t k = wave; k < jobs; k += kWaves) {
+      const uint64_t mk = readlane64(m, k);
+      const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)first, k);
+      if (bit_of(mk, lane)) run[at + lane_rank(mk)] = state[0][c][k * 64 + lane];
+    }
+    if (wave == 0) {
+      uint32_t* masks_out = group_masks(g, args.last, c, gr);
+      if (lane < jobs) store_mask(masks_out + 2 * lane, m);
+      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)(first + pc), 63);
+      if (lane == 0) args.last_cnt[gi] = total;
+    }
+  }
 }
 
 // ---- decode of a delta stream at reduced size (svc_hip_decode_delta_levels_reduced_frames; include/svc_hip.h states it) ------------------
@@ -2765,7 +3068,7 @@ int split_levels(const char* what, SplitArgs a, const svc_step_pair* ladder, uin
 // it -- the window call's count and scan with every tile kept (d_status holds the frames' own codes until the status kernel writes the
 // final ones) -- then the status kernel, chained for the two calls whose predecessor is a reconstructed frame.  Six launches, three
 // without d_prev.
-int enqueue_delta_input(const char* what, const DeltaArgs& a, bool chain, uint64_t prev_bytes, hipStream_t s) {
+int enqueue_delta_input(const char* what, const DeltaArgs& a, bool chain, uint64_t prev_bytes, hipStream_t s, uint32_t period = 1) {
   int rc;
   const uint32_t wave_blocks = div_up(a.in.g.groups, kThreads / 64);
   if (a.prev.in) {
@@ -2779,18 +3082,32 @@ int enqueue_delta_input(const char* what, const DeltaArgs& a, bool chain, uint64
     hipLaunchKernelGGL(window_scan_kernel, dim3(in->n_in), dim3(kThreads), 0, s, *in);
     if ((rc = check_launch(what, "input scan"))) return rc;
   }
-  if (chain) hipLaunchKernelGGL(delta_status_kernel<true>, dim3(1), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(delta_status_kernel<false>, dim3(1), dim3(64), 0, s, a);
+  if (period != 1) {  // the temporal calls: a tree of statuses, not a chain
+    if (chain) hipLaunchKernelGGL(delta_temporal_status_kernel<true>, dim3(1), dim3(64), 0, s, a, period);
+    else hipLaunchKernelGGL(delta_temporal_status_kernel<false>, dim3(1), dim3(64), 0, s, a, period);
+  } else if (chain) {
+    hipLaunchKernelGGL(delta_status_kernel<true>, dim3(1), dim3(64), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(delta_status_kernel<false>, dim3(1), dim3(64), 0, s, a);
+  }
   return check_launch(what, "status");
 }
 
+// the period of the temporal calls, checked right after the geometry
+int validate_period(const char* what, uint32_t period) {
+  SVC_REQUIRE(period == 1 || period == 2 || period == 4, "%s: period %u (supported: 1, 2, 4)", what, period);
+  return SVC_OK;
+}
+
 // Both directions of the delta, checked in the window call's order: geometry, limits, workspace, output capacity; n_frames == 0 then
-// returns SVC_OK; then pointers.  Ten launches, whatever n_frames (seven without d_prev).
-int delta_levels(const char* what, bool undo, const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n,
+// returns SVC_OK; then pointers.  Ten launches, whatever n_frames (seven without d_prev).  period 1: the plain calls; 2 or 4: the temporal
+// calls, which differ in the status kernel and in the count and write kernels alone.
+int delta_levels(const char* what, bool undo, uint32_t period, const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n,
                  const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t w, uint32_t h, uint32_t bw, uint32_t bh,
                  uint32_t mvbw, uint32_t mvbh, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
                  uint64_t* d_out_offsets, uint32_t* d_status, void* stream) {
   int rc = validate_geom(what, w, h, bw, bh, mvbw, mvbh);
+  if (!rc) rc = validate_period(what, period);
   if (!rc) rc = validate_limits(what, n, w, h, bw, bh, mvbw, mvbh);
   if (rc) return rc;
   const Geom g = make_geom(w, h, bw, bh, mvbw, mvbh);
@@ -2808,20 +3125,26 @@ int delta_levels(const char* what, bool undo, const uint8_t* d_frames, uint64_t 
                     d_key, n, ws.cnt, ws.frame_bytes, ws.frame_levels, ws.status};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t wave_blocks = div_up(g.groups, kThreads / 64);
-  if ((rc = enqueue_delta_input(what, a, undo, prev_bytes, s))) return rc;
+  if ((rc = enqueue_delta_input(what, a, undo, prev_bytes, s, period))) return rc;
   // the scan of the band call on this call's counts and final statuses
   WindowArgs counted = a.in;
   counted.ws.status = ws.status;
   const BandArgs scan{counted, nullptr, ws.cnt, ws.frame_bytes, ws.frame_levels};
   const uint32_t cap = g.tpg * g.bw * g.bh, wpb = split_write_waves(cap);
   const dim3 chains(div_up(g.groups, wpb)), pairs(wave_blocks, n);
-  if (undo) hipLaunchKernelGGL(undelta_kernel<false>, chains, dim3(64 * wpb), split_write_lds(cap), s, a, cap);
+  const uint32_t twpb = temporal_waves(cap);
+  const dim3 trees(div_up(g.groups, twpb));
+  if (period != 1 && undo) hipLaunchKernelGGL(undelta_temporal_kernel<false>, trees, dim3(64 * twpb), temporal_lds(cap), s, a, cap, period);
+  else if (period != 1) hipLaunchKernelGGL(delta_temporal_kernel<false>, pairs, dim3(kThreads), 0, s, a, cap, period);
+  else if (undo) hipLaunchKernelGGL(undelta_kernel<false>, chains, dim3(64 * wpb), split_write_lds(cap), s, a, cap);
   else hipLaunchKernelGGL(delta_kernel<false>, pairs, dim3(kThreads), 0, s, a, cap);
   if ((rc = check_launch(what, "count"))) return rc;
   hipLaunchKernelGGL(band_scan_kernel, dim3(n), dim3(kThreads), 0, s, scan);
   if ((rc = check_launch(what, "scan"))) return rc;
   if ((rc = enqueue_frame_offsets(what, 1, OffsetsJob{ws.frame_bytes, d_out_offsets, nullptr}, OffsetsJob{}, n, stream))) return rc;
-  if (undo) hipLaunchKernelGGL(undelta_kernel<true>, chains, dim3(64 * wpb), split_write_lds(cap), s, a, cap);
+  if (period != 1 && undo) hipLaunchKernelGGL(undelta_temporal_kernel<true>, trees, dim3(64 * twpb), temporal_lds(cap), s, a, cap, period);
+  else if (period != 1) hipLaunchKernelGGL(delta_temporal_kernel<true>, pairs, dim3(kThreads), select_write_lds(cap), s, a, cap, period);
+  else if (undo) hipLaunchKernelGGL(undelta_kernel<true>, chains, dim3(64 * wpb), split_write_lds(cap), s, a, cap);
   else hipLaunchKernelGGL(delta_kernel<true>, pairs, dim3(kThreads), select_write_lds(cap), s, a, cap);
   return check_launch(what, "write");
 }
@@ -3331,7 +3654,7 @@ int svc_hip_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, 
                                 uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint8_t* d_workspace,
                                 uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status,
                                 void* stream) {
-  return delta_levels("delta_levels", false, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w, frame_h,
+  return delta_levels("delta_levels", false, 1, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w, frame_h,
                       block_w, block_h, mv_block_w, mv_block_h, d_workspace, workspace_bytes, d_out, out_capacity, d_out_offsets, d_status, stream);
 }
 
@@ -3349,7 +3672,7 @@ int svc_hip_undelta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes
                                   uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint8_t* d_workspace,
                                   uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status,
                                   void* stream) {
-  return delta_levels("undelta_levels", true, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w, frame_h,
+  return delta_levels("undelta_levels", true, 1, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w, frame_h,
                       block_w, block_h, mv_block_w, mv_block_h, d_workspace, workspace_bytes, d_out, out_capacity, d_out_offsets, d_status, stream);
 }
 
@@ -3363,16 +3686,18 @@ uint64_t svc_hip_decode_delta_levels_workspace_bytes(uint32_t n_frames, uint32_t
 }
 
 // Checked in the order of svc_hip_decode_levels_frames, then last_capacity; n_frames == 0 then returns SVC_OK; then pointers.  Four launches
-// without d_prev, d_last and display, ten with all three, whatever n_frames.
-int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
-                                       const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t frame_w, uint32_t frame_h,
-                                       uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
-                                       uint32_t bg_step, const uint32_t* d_gaze, uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec,
-                                       uint8_t* d_display, uint32_t display_w, uint32_t display_h, uint8_t* d_last, uint64_t last_capacity,
-                                       uint64_t* d_last_bytes, uint32_t* d_status, void* stream) {
-  const char* what = "decode_delta_levels";
+// without d_prev, d_last and display, ten with all three, whatever n_frames.  period 1: svc_hip_decode_delta_levels_frames; 2 or 4: the
+// temporal call, which differs in the status kernel, in the reconstruction kernel and in the frame d_last holds.
+static int decode_delta_levels(const char* what, uint32_t period, const uint8_t* d_frames, uint64_t stream_bytes,
+                               const uint64_t* d_frame_offsets, uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes,
+                               const uint32_t* d_key, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                               uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint32_t* d_gaze,
+                               uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec, uint8_t* d_display, uint32_t display_w,
+                               uint32_t display_h, uint8_t* d_last, uint64_t last_capacity, uint64_t* d_last_bytes, uint32_t* d_status,
+                               void* stream) {
   int rc = validate_decode_geom(what, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
+  if ((rc = validate_period(what, period))) return rc;
   bool display;
   if ((rc = validate_steps_display(what, fg_step, bg_step, display_w, display_h, frame_w, frame_h, &display))) return rc;
   if ((rc = validate_limits(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h))) return rc;
@@ -3398,18 +3723,101 @@ int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_
                           d_gaze, d_rec, (float)fg_step, (float)bg_step, d_last, d_last_bytes, ws.last_cnt, ws.last_first, ws.last_head,
                           ws.last_runs, cap};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((rc = enqueue_delta_input(what, a.d, true, prev_bytes, s))) return rc;
+  if ((rc = enqueue_delta_input(what, a.d, true, prev_bytes, s, period))) return rc;
   const dim3 chains(g.tiles_y * g.gx);
-  if (block_w == 8) hipLaunchKernelGGL(decode_delta_kernel<8>, chains, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL(decode_delta_kernel<16>, chains, dim3(kThreads), 0, s, a);
+  const uint32_t last_frame = (n_frames - 1) / period * period;  // the frame the next call's frame 0 refers to
+  if (period == 1) {
+    if (block_w == 8) hipLaunchKernelGGL(decode_delta_kernel<8>, chains, dim3(kThreads), 0, s, a);
+    else hipLaunchKernelGGL(decode_delta_kernel<16>, chains, dim3(kThreads), 0, s, a);
+  } else if (period == 2) {
+    if (block_w == 8) hipLaunchKernelGGL((decode_delta_temporal_kernel<8, 1>), chains, dim3(kThreads), 0, s, a, last_frame);
+    else hipLaunchKernelGGL((decode_delta_temporal_kernel<16, 1>), chains, dim3(kThreads), 0, s, a, last_frame);
+  } else {
+    if (block_w == 8) hipLaunchKernelGGL((decode_delta_temporal_kernel<8, 2>), chains, dim3(kThreads), 0, s, a, last_frame);
+    else hipLaunchKernelGGL((decode_delta_temporal_kernel<16, 2>), chains, dim3(kThreads), 0, s, a, last_frame);
+  }
   if (d_last) {
     if ((rc = check_launch(what, "reconstruction"))) return rc;
-    hipLaunchKernelGGL(decode_delta_last_scan_kernel, dim3(1), dim3(kThreads), 0, s, a);
+    DecodeDeltaArgs last = a;  // the two kernels take the call's last frame for the one d_last holds
+    last.d.n = last_frame + 1;
+    hipLaunchKernelGGL(decode_delta_last_scan_kernel, dim3(1), dim3(kThreads), 0, s, last);
     if ((rc = check_launch(what, "scan of the last frame"))) return rc;
-    hipLaunchKernelGGL(decode_delta_last_write_kernel, dim3(div_up(g.groups, kThreads / 64)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(decode_delta_last_write_kernel, dim3(div_up(g.groups, kThreads / 64)), dim3(kThreads), 0, s, last);
   }
   return finish_with_display(what, d_last ? "write of the last frame" : "reconstruction", display, d_rec, d_display, n_frames, frame_w,
                              frame_h, display_w, display_h, s);
+}
+
+int svc_hip_decode_delta_levels_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                       const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t frame_w, uint32_t frame_h,
+                                       uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                       uint32_t bg_step, const uint32_t* d_gaze, uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec,
+                                       uint8_t* d_display, uint32_t display_w, uint32_t display_h, uint8_t* d_last, uint64_t last_capacity,
+                                       uint64_t* d_last_bytes, uint32_t* d_status, void* stream) {
+  return decode_delta_levels("decode_delta_levels", 1, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key, frame_w,
+                             frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, d_gaze, d_workspace, workspace_bytes, d_rec,
+                             d_display, display_w, display_h, d_last, last_capacity, d_last_bytes, d_status, stream);
+}
+
+// ---- temporal layers: the three calls above with a period (the workspaces are their siblings')
+
+uint64_t svc_hip_delta_levels_temporal_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                       uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t period) {
+  if (validate_geom("delta_levels_temporal_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_period("delta_levels_temporal_workspace_bytes", period))
+    return 0;
+  return svc_hip_delta_levels_workspace_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+}
+
+int svc_hip_delta_levels_temporal_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets, uint32_t n_frames,
+                                         const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key, uint32_t frame_w,
+                                         uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                         uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                         uint64_t* d_out_offsets, uint32_t* d_status, void* stream, uint32_t period) {
+  return delta_levels("delta_levels_temporal", false, period, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key,
+                      frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, d_workspace, workspace_bytes, d_out, out_capacity,
+                      d_out_offsets, d_status, stream);
+}
+
+uint64_t svc_hip_undelta_levels_temporal_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                         uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t period) {
+  if (validate_geom("undelta_levels_temporal_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_period("undelta_levels_temporal_workspace_bytes", period))
+    return 0;
+  return svc_hip_undelta_levels_workspace_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+}
+
+int svc_hip_undelta_levels_temporal_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets,
+                                           uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key,
+                                           uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                           uint32_t mv_block_h, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
+                                           uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_status, void* stream,
+                                           uint32_t period) {
+  return delta_levels("undelta_levels_temporal", true, period, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes, d_key,
+                      frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, d_workspace, workspace_bytes, d_out, out_capacity,
+                      d_out_offsets, d_status, stream);
+}
+
+uint64_t svc_hip_decode_delta_levels_temporal_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                              uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                                              uint32_t period) {
+  if (validate_decode_geom("decode_delta_levels_temporal_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_period("decode_delta_levels_temporal_workspace_bytes", period))
+    return 0;
+  return svc_hip_decode_delta_levels_workspace_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+}
+
+int svc_hip_decode_delta_levels_temporal_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets,
+                                                uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key,
+                                                uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                                uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                                                const uint32_t* d_gaze, uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec,
+                                                uint8_t* d_display, uint32_t display_w, uint32_t display_h, uint8_t* d_last,
+                                                uint64_t last_capacity, uint64_t* d_last_bytes, uint32_t* d_status, void* stream,
+                                                uint32_t period) {
+  return decode_delta_levels("decode_delta_levels_temporal", period, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes,
+                             d_key, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, d_gaze, d_workspace,
+                             workspace_bytes, d_rec, d_display, display_w, display_h, d_last, last_capacity, d_last_bytes, d_status, stream);
 }
 
 // (the workspace of svc_hip_decode_delta_levels_frames: a group's run of the last frame is placed at its full-size worst case)

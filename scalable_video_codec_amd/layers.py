@@ -20,6 +20,9 @@ its masks; union_frame / union_frames state svc_hip_union_levels_frames, which j
 delta_frame / delta_frames state svc_hip_delta_levels_frames: a frame coded against the frame before it, as the difference of their levels
 in the tiles both code at one step; undelta_frame / undelta_frames state svc_hip_undelta_levels_frames, which adds the frames back up.
 delta_level_counts / auto_keys / delta_auto_frames state the key frames svc_hip_dct_pack_delta_auto_frames chooses by the frame's size.
+temporal_ref / delta_temporal_frames / undelta_temporal_frames / thin_frames / temporal_statuses state the temporal layers of the delta
+stream (svc_hip_delta_levels_temporal_frames, svc_hip_undelta_levels_temporal_frames): frame i coded against frame i - min(lowbit(i), period),
+so that every 2^s-th frame is the stream of period >> s of the thinned clip.
 
 split_frame / split_frames / split_budget_frames state svc_hip_split_levels_frames and its budgeted form: the stream stored at
 (fine_step, fine_step) alone determines a base frame at any multiples of fine_step and the enhancement frame that lifts it back, in
@@ -410,6 +413,76 @@ def undelta_frames(stream, offsets, keys=None, prev=None) -> Tuple[bytes, np.nda
     for i, fr in enumerate(frames):
         out.append(undelta_frame(fr, None if key[i] else (out[i - 1] if i else prev)))
     return _join(out)
+
+
+# ---- temporal layers of the delta stream (include/svc_hip.h: svc_hip_delta_levels_temporal_frames,
+# svc_hip_undelta_levels_temporal_frames) ---------------------------------------------------------------------------------------------------
+
+PERIODS = (1, 2, 4)
+
+
+def temporal_ref(i: int, period: int) -> int:
+    """The frame that frame i > 0 of a stream of period 1, 2 or 4 is coded against: i - min(lowbit(i), period), lowbit(i) = i & -i.
+    Frame 0 is coded against the frame handed in as `prev` (-period, the last frame of layer 0 before the call).  The frames with
+    i % 2^s == 0 (2^s <= period) refer only to each other, and temporal_ref(i, period) // 2^s == temporal_ref(i // 2^s, period >> s)."""
+    if period not in PERIODS:
+        raise ValueError(f"period {period} (supported: 1, 2, 4)")
+    if i <= 0:
+        raise ValueError("frame 0 refers to the frame before the call")
+    return i - min(i & -i, period)
+
+
+def delta_temporal_frames(stream, offsets, period: int, keys=None, prev=None) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_delta_levels_temporal_frames writes for frames that pass their checks -> (bytes, offsets (n + 1,) u64): delta_frames
+    with the predecessor of frame i read as INPUT frame temporal_ref(i, period), for frame 0 the frame `prev`, the input frame at index
+    -period.  Period 1 is delta_frames.  A stream cut into two calls at a multiple of period, the second with prev = input frame
+    cut - period, gives the bytes of one call."""
+    frames = _source_frames(stream, offsets, None)
+    key = _keys(keys, len(frames))
+    return _join([delta_frame(fr, None if key[i] else (frames[temporal_ref(i, period)] if i else prev)) for i, fr in enumerate(frames)])
+
+
+def undelta_temporal_frames(stream, offsets, period: int, keys=None, prev=None) -> Tuple[bytes, np.ndarray]:
+    """What svc_hip_undelta_levels_temporal_frames writes for frames that pass their checks -> (bytes, offsets (n + 1,) u64):
+    delta_temporal_frames undone with the same keys; the predecessor of frame i is OUTPUT frame temporal_ref(i, period), for frame 0 the
+    reconstructed frame `prev` at index -period.  Period 1 is undelta_frames."""
+    frames = _source_frames(stream, offsets, None)
+    key = _keys(keys, len(frames))
+    out = []
+    for i, fr in enumerate(frames):
+        out.append(undelta_frame(fr, None if key[i] else (out[temporal_ref(i, period)] if i else prev)))
+    return _join(out)
+
+
+def temporal_statuses(own, period: int, keys=None, prev: Optional[int] = None, chain: bool = True) -> np.ndarray:
+    """d_status of the temporal calls from every frame's own unpack code -> (n,) u32: the own code if it is not 0; else 0 for a key frame
+    (keys[i] != 0, or frame 0 with prev None); else 0x100 | (s & 0xFF) where the status s of the frame it refers to is not 0.  prev: the
+    own code of the frame handed in as d_prev, None where there is none.  chain (the undelta and decode calls): s is the FINAL status of
+    output frame temporal_ref(i, period), so a failure runs down the tree of references; not chain (the delta call): s is the input
+    frame's own code.  Period 1 is the status of the plain calls."""
+    own = [int(c) for c in np.asarray(own).reshape(-1)]
+    key = _keys(keys, len(own))
+    st = []
+    for i, code in enumerate(own):
+        if code or key[i] or (i == 0 and prev is None):
+            st.append(code)
+            continue
+        s = int(prev) if i == 0 else (st if chain else own)[temporal_ref(i, period)]
+        st.append(0x100 | (s & 0xFF) if s else 0)
+    return np.asarray(st, np.uint32)
+
+
+def thin_frames(stream, offsets, keys, every: int) -> Tuple[bytes, np.ndarray, Optional[np.ndarray]]:
+    """Every `every`-th frame of a stream, from frame 0, with its key flag -> (bytes, offsets, keys or None): what a server sends a viewer
+    of 1 / every of the frame rate (svc_hip_window_levels_frames with d_src = 0, every, 2 * every, .. and no window writes the same
+    bytes).  For every = 2^s <= period, thin_frames of delta_temporal_frames(clip, period, keys) is delta_temporal_frames of the thinned
+    clip at period >> s with the thinned keys: at period >> s == 1 the plain delta stream, which every decoder of it takes."""
+    if every < 1:
+        raise ValueError("every must be at least 1")
+    frames = _source_frames(stream, offsets, None)
+    kept = range(0, len(frames), every)
+    out, offs = _join([bytes(frames[i]) for i in kept])
+    return out, offs, None if keys is None else _keys(keys, len(frames))[list(kept)]
 
 
 # ---- key frames chosen by the SVCQ frame's size (include/svc_hip.h: svc_hip_dct_pack_delta_auto_frames) ------------------------------------

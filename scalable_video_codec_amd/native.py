@@ -181,6 +181,17 @@ SIGNATURES = {
     "svc_hip_decode_delta_levels_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_decode_delta_levels_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 8 + [_vp, _vp, _u64, _vp, _vp, _u32, _u32,
                                                      _vp, _u64, _vp, _vp, _vp]),
+    # the three calls above with temporal layers: frame i coded against frame i - min(lowbit(i), period) (csrc/levels.hip; host
+    # statements: layers.delta_temporal_frames, layers.undelta_temporal_frames)
+    "svc_hip_delta_levels_temporal_workspace_bytes": (_u64, [_u32] * 8),
+    "svc_hip_delta_levels_temporal_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 6 +
+                                             [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _u32]),
+    "svc_hip_undelta_levels_temporal_workspace_bytes": (_u64, [_u32] * 8),
+    "svc_hip_undelta_levels_temporal_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 6 +
+                                               [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _u32]),
+    "svc_hip_decode_delta_levels_temporal_workspace_bytes": (_u64, [_u32] * 8),
+    "svc_hip_decode_delta_levels_temporal_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 8 +
+                                                    [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _u32]),
     # ... at reduced size: the undelta and the reduced decode in one call, on the first K x K levels of every tile (csrc/levels.hip)
     "svc_hip_decode_delta_levels_reduced_workspace_bytes": (_u64, [_u32] * 7),
     "svc_hip_decode_delta_levels_reduced_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 9 +
@@ -1448,7 +1459,7 @@ def undelta_levels_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> i
     return int(load().svc_hip_undelta_levels_workspace_bytes(n, w, h, bw, bh, mbw, mbh))
 
 
-def _delta_call(undo: bool, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status):
+def _delta_call(undo: bool, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status, period=None):
     n = offsets.numel() - 1
     (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
     dev = frames.device
@@ -1459,15 +1470,23 @@ def _delta_call(undo: bool, frames, offsets, w, h, block, mv_block, prev, key, o
     if out_offsets is None:
         out_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     if workspace is None:
-        query = undelta_levels_workspace_bytes if undo else delta_levels_workspace_bytes
-        workspace = torch.empty(max(query(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+        if period is None:
+            query = undelta_levels_workspace_bytes if undo else delta_levels_workspace_bytes
+            need = query(n, w, h, block, mv_block)
+        else:
+            query = undelta_levels_temporal_workspace_bytes if undo else delta_levels_temporal_workspace_bytes
+            need = query(n, w, h, block, mv_block, period)
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     if status is None:
         status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
-    fn = load().svc_hip_undelta_levels_frames if undo else load().svc_hip_delta_levels_frames
+    if period is None:
+        fn = load().svc_hip_undelta_levels_frames if undo else load().svc_hip_delta_levels_frames
+    else:
+        fn = load().svc_hip_undelta_levels_temporal_frames if undo else load().svc_hip_delta_levels_temporal_frames
     _check(fn(_dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, None if prev is None else _dev(prev, torch.uint8),
               0 if prev is None else prev.numel(), None if k is None else _dev(k, torch.int32), w, h, bw, bh, mbw, mbh,
               _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(), _dev(out_offsets, torch.int64),
-              _dev(status, torch.int32), _stream()))
+              _dev(status, torch.int32), _stream(), *(() if period is None else (period,))))
     return out, out_offsets, status
 
 
@@ -1493,6 +1512,39 @@ def undelta_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h
     return _delta_call(True, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status)
 
 
+def delta_levels_temporal_workspace_bytes(n: int, w: int, h: int, block, mv_block, period: int) -> int:
+    """Scratch of delta_levels_temporal_frames for n frames; 0 for a geometry or a period it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_delta_levels_temporal_workspace_bytes(n, w, h, bw, bh, mbw, mbh, period))
+
+
+def undelta_levels_temporal_workspace_bytes(n: int, w: int, h: int, block, mv_block, period: int) -> int:
+    """Scratch of undelta_levels_temporal_frames for n frames; 0 for a geometry or a period it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_undelta_levels_temporal_workspace_bytes(n, w, h, bw, bh, mbw, mbh, period))
+
+
+def delta_levels_temporal_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, period: int,
+                                 prev: Optional[torch.Tensor] = None, key=None, out: Optional[torch.Tensor] = None,
+                                 out_offsets: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                 status: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """delta_levels_frames with temporal layers (include/svc_hip.h, "Temporal layers"; the numpy statement is
+    layers.delta_temporal_frames): frame i is coded against INPUT frame i - min(lowbit(i), period), period 1, 2 or 4, so the frames with
+    i % 2^s == 0 are the stream of period >> s of the thinned clip.  prev: None, or the input frame at index -period.  Frame i of the call
+    must have a stream index that is i modulo period.  The rest as delta_levels_frames; a frame's status hangs on its reference's."""
+    return _delta_call(False, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status, period)
+
+
+def undelta_levels_temporal_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, period: int,
+                                   prev: Optional[torch.Tensor] = None, key=None, out: Optional[torch.Tensor] = None,
+                                   out_offsets: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                   status: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """delta_levels_temporal_frames undone (the numpy statement is layers.undelta_temporal_frames): frame i is the delta stream's frame i
+    plus OUTPUT frame i - min(lowbit(i), period).  prev: None, or the reconstructed frame at index -period.  A failure runs down the tree
+    of references: a damaged odd frame harms no other."""
+    return _delta_call(True, frames, offsets, w, h, block, mv_block, prev, key, out, out_offsets, workspace, status, period)
+
+
 def decode_delta_levels_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:
     """Scratch of decode_delta_levels_frames for n frames; 0 for a geometry it refuses."""
     (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
@@ -1512,6 +1564,13 @@ def decode_delta_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: i
     bytes; key: None, or per frame != 0 for a key frame; gaze: None, or per frame x, y, w, h in padded coordinates; display: (w, h).
     want_last (or a `last` buffer of at least levels_max_bytes(1, ...)): the reconstructed SVCQ frame of the last frame, the next call's
     prev once cut to last_bytes (a (1,) i64 tensor on the device).  `last` must not overlap `frames` or `prev`."""
+    return _decode_delta_call(None, frames, offsets, w, h, block, mv_block, fg_step, bg_step, prev, key, gaze, display, want_last, rec,
+                              out_display, last, workspace, status)
+
+
+def _decode_delta_call(_period, frames, offsets, w, h, block, mv_block, fg_step, bg_step, prev, key, gaze, display, want_last, rec, out_display,
+                       last, workspace, status):
+    """decode_delta_levels_frames (_period None) or decode_delta_levels_temporal_frames."""
     n = offsets.numel() - 1
     (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
     dev = frames.device
@@ -1526,19 +1585,43 @@ def decode_delta_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: i
         last = torch.empty(max(levels_max_bytes(1, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
     last_bytes = None if last is None else torch.zeros(1, dtype=torch.int64, device=dev)
     if workspace is None:
-        workspace = torch.empty(max(decode_delta_levels_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+        need = (decode_delta_levels_workspace_bytes(n, w, h, block, mv_block) if _period is None else
+                decode_delta_levels_temporal_workspace_bytes(n, w, h, block, mv_block, _period))
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     g = None
     if gaze is not None:
         g = torch.as_tensor(gaze, dtype=torch.int32).reshape(n, 4).to(dev).contiguous()
     if status is None:
         status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
-    _check(load().svc_hip_decode_delta_levels_frames(
+    fn = load().svc_hip_decode_delta_levels_frames if _period is None else load().svc_hip_decode_delta_levels_temporal_frames
+    _check(fn(
         _dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, None if prev is None else _dev(prev, torch.uint8),
         0 if prev is None else prev.numel(), None if k is None else _dev(k, torch.int32), w, h, bw, bh, mbw, mbh, fg_step, bg_step,
         None if g is None else _dev(g, torch.int32), _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
         None if out_display is None else _dev(out_display, torch.uint8), dw, dh, None if last is None else _dev(last, torch.uint8),
-        0 if last is None else last.numel(), None if last is None else _dev(last_bytes, torch.int64), _dev(status, torch.int32), _stream()))
+        0 if last is None else last.numel(), None if last is None else _dev(last_bytes, torch.int64), _dev(status, torch.int32), _stream(),
+        *(() if _period is None else (_period,))))
     return rec, out_display, status, last, last_bytes
+
+
+def decode_delta_levels_temporal_workspace_bytes(n: int, w: int, h: int, block, mv_block, period: int) -> int:
+    """Scratch of decode_delta_levels_temporal_frames for n frames; 0 for a geometry or a period it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_decode_delta_levels_temporal_workspace_bytes(n, w, h, bw, bh, mbw, mbh, period))
+
+
+def decode_delta_levels_temporal_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, period: int,
+                                        fg_step: int = 1, bg_step: int = 640, prev: Optional[torch.Tensor] = None, key=None, gaze=None,
+                                        display: Optional[Tuple[int, int]] = None, want_last: bool = False,
+                                        rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None,
+                                        last: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                        status: Optional[torch.Tensor] = None
+                                        ) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """decode_delta_levels_frames with temporal layers (include/svc_hip.h, "Temporal layers"): undelta_levels_temporal_frames and
+    decode_levels_frames in one call, with that function's arguments and results.  period: 1, 2 or 4; prev: the reconstructed frame at
+    index -period; `last` is reconstructed frame period * ((n - 1) // period), the next call's prev."""
+    return _decode_delta_call(period, frames, offsets, w, h, block, mv_block, fg_step, bg_step, prev, key, gaze, display, want_last, rec,
+                              out_display, last, workspace, status)
 
 
 def decode_delta_levels_reduced_workspace_bytes(n: int, w: int, h: int, block, mv_block) -> int:

@@ -77,6 +77,15 @@
                                                    delta with the chosen flags, and the frames at which the level-count choice is not the
                                                    smaller CODED frame with the bytes that costs.  Then tests/dropin/stream_delta_auto_main on a
                                                    33-frame 1080p clip with auto_key and with delta alone, plain and entropy-coded, the list twice
+  python tools/dct_pack_probe.py delta-temporal    temporal layers of the delta stream, at C3 and one line at C5, a batch of 16 at (1, 640) and (1, 1) with
+                                                   frame 0 the key frame: svc_hip_delta_levels_temporal_frames at periods 2 and 4 against
+                                                   svc_hip_delta_levels_frames on the same plain stream, and the encoder's two-call route
+                                                   (svc_hip_dct_pack_levels_frames + the temporal call at period 4) against
+                                                   svc_hip_dct_pack_delta_frames; wall time per call over 20 back-to-back calls, the routes in turn,
+                                                   the median of three.  Then, at C3, raw and entropy-coded bytes per frame at periods 1, 2 and 4
+                                                   for delta-auto's three clips, and what a half-rate and a quarter-rate viewer is sent from the
+                                                   period-4 stream.  Then tests/dropin/stream_temporal_main on a 33-frame 1080p clip at periods 4
+                                                   and 1 (`delta` alone), encode and play, the list twice
   python tools/dct_pack_probe.py window-entropy [C3|C5]
                                                    a stored entropy-coded enhancement served under a gaze, the same batch of 16 at
                                                    (1, 640, 1) with a 256 x 256 window per frame: svc_hip_window_entropy_frames on the stored
@@ -670,6 +679,147 @@ def delta_auto_sizes(cfg) -> None:
                   f"{int(ca.sum()) / n / 1e6:.4f} ({int(k.sum())} key frames: {''.join('K' if v else '.' for v in k.tolist())}); the level-count "
                   f"choice is not the smaller coded frame at {int(wrong.sum())} of {n} frames, {lost} B in all "
                   f"({100.0 * lost / max(int(best.sum()), 1):.3f} % of the best coded stream)", flush=True)
+
+
+def delta_temporal_kernels(cfg, both_steps=True) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out, plain, ref = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(3))
+    offs, plain_offs, ref_offs = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(3))
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(native.dct_pack_delta_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_d = torch.empty(native.delta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    key = torch.zeros(n, dtype=torch.int32, device=dev)
+    key[0] = 1
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}, frame 0 the key frame; ms per call (20 back-to-back calls, the routes in turn, the "
+          f"median of three rounds)", flush=True)
+    for fg, bg in ((1, 640), (1, 1)) if both_steps else ((1, 640),):
+        def pack():
+            native.dct_pack_levels_frames(bgr, block, types, mv, fg, bg, out=plain, offsets=plain_offs, workspace=ws)
+
+        def delta_at(period):
+            def call():
+                if period == 1:
+                    native.delta_levels_frames(plain, plain_offs, pw, ph, block, mv, key=key, out=ref, out_offsets=ref_offs, workspace=ws_d,
+                                               status=st)
+                else:
+                    native.delta_levels_temporal_frames(plain, plain_offs, pw, ph, block, mv, period, key=key, out=ref, out_offsets=ref_offs,
+                                                        workspace=ws_d, status=st)
+            return call
+
+        def fused():
+            native.dct_pack_delta_frames(bgr, block, types, mv, fg, bg, key=key, out=out, offsets=offs, workspace=ws)
+
+        def two_calls():
+            pack()
+            delta_at(4)()
+
+        pack()
+        sizes = {}
+        for period in (1, 2, 4):
+            delta_at(period)()
+            sync()
+            assert not st.any()
+            sizes[period] = int(ref_offs[-1]) / n / 1e6
+        t = _median3([delta_at(1), delta_at(2), delta_at(4), fused, two_calls, pack], sync)
+        print(f"  ({fg}, {bg}): svc_hip_delta_levels_frames {t[0]:.3f}; svc_hip_delta_levels_temporal_frames at period 2 {t[1]:.3f} "
+              f"({t[1] / t[0]:.2f}x), at period 4 {t[2]:.3f} ({t[2] / t[0]:.2f}x); svc_hip_dct_pack_delta_frames (period 1, fused) {t[3]:.3f}; "
+              f"svc_hip_dct_pack_levels_frames + the temporal call at period 4 {t[4]:.3f} ({t[4] / t[3]:.2f}x of the fused call; the pack alone "
+              f"{t[5]:.3f}); MB per frame at periods 1, 2, 4: " + ", ".join(f"{sizes[p]:.4f}" for p in (1, 2, 4)), flush=True)
+
+
+def delta_temporal_sizes(cfg) -> None:
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    mbw, mbh = native._bwbh(mv)
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    # delta_auto_sizes' clips: the static background under a moving 128 x 128 patch, and 8 frames of it followed by 8 synthetic ones
+    # upside down
+    still = bgr[:1].expand(n, ph, pw, 3).clone()
+    still_types = torch.zeros_like(types).view(n, ph // mbh, pw // mbw)
+    for f in range(n):
+        x, y = 256 + 48 * f, 192 + 16 * f
+        still[f, y:y + 128, x:x + 128] = bgr[f, y:y + 128, x:x + 128]
+        still_types[f, y // mbh:(y + 128) // mbh, x // mbw:(x + 128) // mbw] = 1
+    cut = torch.cat([still[:8], bgr[8:].flip(1)]).contiguous()
+    cut_types = torch.cat([still_types[:8], types.view(n, ph // mbh, pw // mbw)[8:].flip(1)]).reshape(n, -1).contiguous()
+    still_types = still_types.reshape(n, -1).contiguous()
+    key16 = [1] + [0] * (n - 1)
+
+    def coded_sizes(stream, so):
+        _, eo, est = native.entropy_encode_frames(stream, so, pw, ph, block, mv)
+        sync()
+        assert not est.any()
+        return (eo[1:] - eo[:-1]).cpu()
+
+    print(f"{cfg.name} batch of {n}, frame 0 the key frame; MB per frame raw / entropy-coded", flush=True)
+    for clip_name, frames, ty in (("the synthetic clip (fresh noise every frame)", bgr, types),
+                                  ("a static background under a moving 128 x 128 patch", still, still_types),
+                                  ("8 static frames, then 8 synthetic ones upside down (a cut)", cut, cut_types)):
+        for fg, bg in ((1, 640), (1, 1)):
+            p, po = native.dct_pack_levels_frames(frames, block, ty, mv, fg, bg)
+            sync()
+            p = p[:int(po[-1])].clone()
+            row, per_frame = [], {}
+            for period in (1, 2, 4):
+                if period == 1:
+                    d, do, st = native.delta_levels_frames(p, po, pw, ph, block, mv, key=key16)
+                else:
+                    d, do, st = native.delta_levels_temporal_frames(p, po, pw, ph, block, mv, period, key=key16)
+                sync()
+                assert not st.any()
+                raw = (do[1:] - do[:-1]).cpu()
+                coded = coded_sizes(d[:int(do[-1])].clone(), do)
+                per_frame[period] = (raw, coded)
+                row.append(f"period {period} {int(raw.sum()) / n / 1e6:.4f} / {int(coded.sum()) / n / 1e6:.4f}")
+            r1, c1 = (int(v.sum()) for v in per_frame[1])
+            grow = ", ".join(f"period {q}: {int(per_frame[q][0].sum()) / r1:.3f}x / {int(per_frame[q][1].sum()) / c1:.3f}x" for q in (2, 4))
+            raw4, coded4 = per_frame[4]
+            sent = ", ".join(f"{name} {int(raw4[::e].sum()) / int(raw4.sum()):.3f} / {int(coded4[::e].sum()) / int(coded4.sum()):.3f} of the "
+                             f"stream's bytes for {len(raw4[::e])} of {n} frames" for name, e in (("half rate", 2), ("quarter rate", 4)))
+            print(f"  {clip_name} at ({fg}, {bg}): " + "; ".join(row) + f" (against period 1, {grow}); from the period-4 stream {sent}", flush=True)
+
+
+def delta_temporal_stream(frames_n=33) -> None:
+    import subprocess
+    import tempfile
+    cfg = configs.C3
+    exe = os.path.join(ROOT, "tests", "dropin", "stream_temporal_main")
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=torch.device("cuda"))
+        raw = os.path.join(d, "clip.raw")
+        with open(raw, "wb") as f:
+            for t in range(frames_n):
+                f.write(clip.frame_bgr(t).cpu().numpy().tobytes())
+        del clip
+        torch.cuda.empty_cache()
+        print(f"{cfg.name}, {frames_n} frames from host memory through svc::StreamEncoder and svc::StreamDecoder (tests/dropin/stream_temporal_main), "
+              f"batch 16, depth 3, key_interval 16; every run printed", flush=True)
+        for turn in range(2):
+            for period in (4, 1):
+                p = subprocess.run([exe, raw, str(cfg.width), str(cfg.height), str(frames_n), str(cfg.levels), str(cfg.dct_block), "16", "3",
+                                    str(cfg.seed), str(period), "16", "0", "-"], capture_output=True, text=True, timeout=300)
+                print(f"  run {turn}, temporal_period {period} (exit {p.returncode}): {(p.stdout.strip() or p.stderr.strip())}", flush=True)
+                if p.returncode != 0:
+                    sys.exit(1)
+
+
+def delta_temporal() -> None:
+    delta_temporal_kernels(configs.C3)
+    torch.cuda.empty_cache()
+    delta_temporal_kernels(configs.C5, both_steps=False)
+    torch.cuda.empty_cache()
+    delta_temporal_sizes(configs.C3)
+    torch.cuda.empty_cache()
+    delta_temporal_stream()
 
 
 def delta_auto_stream(frames_n=33) -> None:
@@ -1380,6 +1530,8 @@ if __name__ == "__main__":
         delta_encode()
     elif mode == "delta-auto":
         delta_auto()
+    elif mode == "delta-temporal":
+        delta_temporal()
     elif mode == "stream-layers":
         stream_layers()
     elif mode == "transcode":

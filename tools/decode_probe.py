@@ -23,6 +23,12 @@
                                          svc_hip_decode_delta_levels_frames against svc_hip_undelta_levels_frames +
                                          svc_hip_decode_levels_frames, against the decode alone on the undelta'd stream, and with and without
                                          d_last, alternating, device events, the median of three windows; the routes' rec compared
+  python tools/decode_probe.py temporal [C3|C5]   `delta`'s batch stored at (1, 640) and at (1, 1) with frame 0 the key frame, coded at periods 1, 2
+                                         and 4 (include/svc_hip.h, "Temporal layers"), in one process: svc_hip_undelta_levels_temporal_frames
+                                         against svc_hip_undelta_levels_frames, svc_hip_decode_delta_levels_temporal_frames against
+                                         svc_hip_decode_delta_levels_frames, and the fused temporal decode against the temporal undelta +
+                                         svc_hip_decode_levels_frames, alternating, device events, the median of three windows; the
+                                         routes' rec compared
   python tools/decode_probe.py delta-rate   `rate`'s stream and its delta stream (a key frame every 16) through
                                          tests/dropin/stream_decode_main (Decode) and tests/dropin/stream_delta_main (DecodeDelta), PCIe
                                          included, alternating
@@ -410,6 +416,93 @@ def delta() -> None:
                   f"{m['fused'] / m['alone']:.2f}x of the decode alone {fmt(t['alone'])}; without d_last {fmt(t['no_last'])}", flush=True)
 
 
+def temporal() -> None:
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native, pipeline
+    cfg = {"C3": configs.C3, "C5": configs.C5}[sys.argv[2] if len(sys.argv) > 2 else "C3"]
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    clip = synth.SynthClip(cfg.width, cfg.height, n + 1, cfg.seed, device=dev)
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(n + 1)]).contiguous()
+    enc = pipeline.ClipEncoder(cfg, n + 1, dev)
+    enc.load_frames(list(frames))
+    enc.step()
+    torch.cuda.synchronize()
+    bgr, types = frames[1:].contiguous(), enc.types.clone()
+
+    def timed(fn, reps=20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    back, bo = torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ws_u = torch.empty(native.undelta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_x = torch.empty(native.decode_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    ws_f = torch.empty(native.decode_delta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    rec, rec2 = (torch.empty((n, ph, pw, 3), dtype=torch.float32, device=dev) for _ in range(2))
+    last = torch.empty(native.levels_max_bytes(1, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    st, st2 = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    keys = [1] + [0] * (n - 1)
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}, frame 0 the key frame; ms per call of {n} frames, device events over 20 back-to-back "
+          f"calls, the median of three such windows per route, the routes alternating", flush=True)
+    for steps in ((1, 640), (1, 1)):
+        out, offs = native.dct_pack_levels_frames(bgr, block, types, mv, *steps)
+        torch.cuda.synchronize()
+        stream = out[:int(offs[-1])].clone()
+        routes, sizes = {}, {}
+        for period in (1, 2, 4):
+            if period == 1:
+                d, do, dst = native.delta_levels_frames(stream, offs, pw, ph, block, mv, key=keys)
+            else:
+                d, do, dst = native.delta_levels_temporal_frames(stream, offs, pw, ph, block, mv, period, key=keys)
+            torch.cuda.synchronize()
+            assert not dst.any()
+            d = d[:int(do[-1])].clone()
+            sizes[period] = d.numel() / n / 1e6
+
+            def undelta(d=d, do=do, period=period):
+                if period == 1:
+                    native.undelta_levels_frames(d, do, pw, ph, block, mv, key=keys, out=back, out_offsets=bo, workspace=ws_u, status=st2)
+                else:
+                    native.undelta_levels_temporal_frames(d, do, pw, ph, block, mv, period, key=keys, out=back, out_offsets=bo, workspace=ws_u,
+                                                          status=st2)
+
+            def two(undelta=undelta):
+                undelta()
+                native.decode_levels_frames(back, bo, pw, ph, block, mv, 1, 640, rec=rec2, workspace=ws_x)
+
+            def fused(d=d, do=do, period=period):
+                if period == 1:
+                    native.decode_delta_levels_frames(d, do, pw, ph, block, mv, 1, 640, key=keys, rec=rec, last=last, workspace=ws_f, status=st)
+                else:
+                    native.decode_delta_levels_temporal_frames(d, do, pw, ph, block, mv, period, fg_step=1, bg_step=640, key=keys, rec=rec,
+                                                               last=last, workspace=ws_f, status=st)
+
+            two(), fused()
+            torch.cuda.synchronize()
+            assert not st.any() and not st2.any() and torch.equal(rec.view(torch.int32), rec2.view(torch.int32)), "the routes differ"
+            assert torch.equal(back[:stream.numel()], stream)
+            routes[period] = (undelta, two, fused)
+        t = {(p, k): [] for p in routes for k in range(3)}
+        for _ in range(3):
+            for p, fns in routes.items():
+                for k, fn in enumerate(fns):
+                    t[p, k].append(timed(fn))
+        m = {key: float(np.median(v)) for key, v in t.items()}
+        for p in (1, 2, 4):
+            print(f"stored at {steps}, period {p} ({sizes[p]:.3f} MB per delta frame): undelta {m[p, 0]:.3f} ({m[p, 0] / m[1, 0]:.2f}x of period 1); "
+                  f"undelta + decode {m[p, 1]:.3f}; fused decode {m[p, 2]:.3f} = {m[p, 2] / m[p, 1]:.2f}x of the two calls, "
+                  f"{m[p, 2] / m[1, 2]:.2f}x of period 1's fused decode (min {min(t[p, 2]):.3f}, max {max(t[p, 2]):.3f})", flush=True)
+
+
 def delta_rate() -> None:
     """DecodeDelta against Decode on the same clip's plain stream, PCIe included: `rate`'s 64 frames, their delta stream made on the device."""
     import numpy as np
@@ -624,4 +717,4 @@ def delta_reduced_rate() -> None:
 if __name__ == "__main__":
     {"rate": rate, "kernels": kernels, "reduced": reduced, "reduced-rate": reduced_rate, "layers-reduced": layers_reduced,
      "layers-reduced-rate": layers_reduced_rate, "delta": delta, "delta-rate": delta_rate, "delta-reduced": delta_reduced,
-     "delta-reduced-rate": delta_reduced_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
+     "delta-reduced-rate": delta_reduced_rate, "temporal": temporal}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
