@@ -21,7 +21,9 @@
 // xGMI) and the transform of the step four back -- while RANSAC + segmentation (latency-bound: one workgroup per frame) of an earlier step
 // start beside them on a stream of their own (forked at the start of the iteration, in front of the luma launch) and have two iterations to
 // finish, consecutive steps alternating between two such streams.  The small per-frame outputs exist in four sets, pyramids in two; Flush()
-// drains the pipeline.
+// drains the pipeline.  Co-run: at one rank, on fields up to 8 192 MV blocks (no deferred RMSE kernel on that stream), a step that reads the clip once (below) runs transform(s) | motion search(s - 1) on the main stream
+// and the pyramid levels(s) on the communication stream, forked behind the transform, beside that search (VALU-paced beside a kernel that
+// leaves the VALU idle: - 1.8 % per step at C3, profiles/ab_pyramid_beside_search.txt); pyramid_on_main keeps them on the main stream.
 //
 // Chunks (round 6).  With ClipEncoderConfig::chunk_pairs a pipelined step at one rank is cut into chunks of that many frame pairs and the
 // pipeline runs over the CHUNKS: every stage launch covers one chunk, RANSAC + segmentation of chunk c run beside the motion search of chunk
@@ -118,6 +120,8 @@ struct ClipEncoderConfig {
   bool mixed_steps = false;         // a step into an empty pipeline that knows nothing about the clip: first half two passes, second half one
                                     // pass, blind (A/B: - 2 % at 0.5 % foreground, + 5-8 % at 13 %; profiles/r06_ab_mixed_step.txt)
   bool search_after_transform = false;  // one rank: the motion search, not a pyramid pass, right behind the transform kernel (A/B)
+  bool pyramid_on_main = false;     // one rank: never the co-run order (Schedule, above): the pyramid levels of a one-pass micro-step stay on
+                                    // the main stream, in front of the same micro-step's search (A/B, tests)
 };
 
 enum class Stage : uint32_t { kLumaPyramid = 0, kHalo, kHbma, kRansac, kSegment, kTransform, kTypePatch, kCount };

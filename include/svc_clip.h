@@ -53,6 +53,9 @@ typedef struct svc_clip svc_clip;
 #define SVC_CLIP_TUNE_SEARCH_AFTER_TRANSFORM 256u /* one rank: the motion search, not a pyramid pass, runs right behind the transform kernel (A/B) */
 #define SVC_CLIP_TUNE_WHOLE_SHARD_STEPS 128u /* never the idle-pipeline rule (a step that finds the pipeline empty runs in two chunks on big
                                                 shards in the two-pass order: clip_encoder.hpp); A/B */
+#define SVC_CLIP_TUNE_PYRAMID_ON_MAIN 16384u /* one rank, pipelined: the pyramid levels of a micro-step that reads its frames once stay on the main
+                                                stream (transform | pyramid levels | search of the SAME micro-step) instead of running on the
+                                                communication stream beside the previous micro-step's motion search (the default up to 8 192 MV blocks, clip_encoder.hpp); A/B, tests */
 
 typedef struct svc_clip_config {
   uint32_t struct_size;   /* sizeof(svc_clip_config) of the caller's build: svc_clip_create refuses any other value, so a

@@ -26,6 +26,7 @@ TUNE_RANDOM_POLICY = 2048  # tests: the speculation policy answers yes / no by a
 TUNE_MIXED_STEPS = 1024  # a step into an empty pipeline that knows nothing about the clip takes the mixed form (A/B, off by default)
 TUNE_SEARCH_AFTER_TRANSFORM = 256  # one rank: the motion search right behind the transform kernel (A/B)
 TUNE_WHOLE_SHARD_STEPS = 128  # never the idle-pipeline rule (A/B)
+TUNE_PYRAMID_ON_MAIN = 16384  # one rank: a one-pass micro-step's pyramid levels stay on the main stream, not beside the previous search (A/B, tests)
 OUTPUT_COMPACT = 8192  # same field, a statement about the output: the compact stream (SVCQ) straight from the transform instead of planes
 KEEP_FOREGROUND_PRIOR = 64  # same field: the clips loaded are consecutive pieces of one stream (the policy keeps its prior across load_frames)
 STAGES = ("luma_pyramid", "halo_exchange", "hbma", "ransac", "segment", "dct_quant", "type_patch")

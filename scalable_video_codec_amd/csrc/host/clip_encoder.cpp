@@ -61,7 +61,8 @@ struct ClipEncoder::Impl : EncodeGeometry {
   // mixed form of a step into an empty pipeline)
   // frames: the shard's B,G,R frames this micro-step's step encodes -- the resident buffer (LoadFrames) or the caller's own device buffer
   // (StepFrames: a stream of clips, each encoded once, without a copy and without draining the pipeline between them)
-  struct Micro { uint32_t step = 0, p0 = 0, pn = 0; bool first = true; uint8_t order = 0; const uint8_t* frames = nullptr; };
+  // idle: a half of a step cut by the idle-pipeline rule (Step()); such a micro-step keeps the order it always had, whatever it decides
+  struct Micro { uint32_t step = 0, p0 = 0, pn = 0; bool first = true; uint8_t order = 0; const uint8_t* frames = nullptr; bool idle = false; };
   static constexpr int kRing = 8;  // > depth + 2 micro-steps in flight
   Micro ring[kRing], next_micro;
   uint32_t n_steps = 0;
@@ -93,6 +94,17 @@ struct ClipEncoder::Impl : EncodeGeometry {
   DevBuf<uint32_t> compact_budget, compact_choice;
   Event e_pyr[2], e_halo[2], e_fork, e_join[kSets], e_rfork, e_rmse[kSets];
   bool halo_recorded[2] = {false, false}, join_pending[kSets] = {}, rmse_pending[kSets] = {};
+  // Co-run (one rank, pipelined; off with pyramid_on_main): the pyramid levels of a micro-step that reads its frames once run on the
+  // communication stream, forked behind the micro-step's transform (e_front), beside the PREVIOUS micro-step's motion search on the main
+  // stream; the micro-step's own search follows one iteration later and waits for them.  e_pyr[m & 1] is recorded behind the levels of
+  // micro-step m and pyr_wait[m & 1] = m + 1 says so until search(m) has waited: a search never skips a recorded event and never waits on
+  // one that was not recorded for it, whatever order the micro-steps around it take.  (m & 1, not the step's parity: the chunks of one step
+  // would share an event and search(m - 1) would wait for the levels of m.  Two are enough: search(m) is enqueued in iteration m + 1 at the
+  // latest, the levels of m + 2 in iteration m + 2.  The halo, the other user of e_pyr, exists only on a multi-rank run.)
+  bool co_run = false;
+  Event e_front;
+  uint64_t pyr_wait[2] = {0, 0};
+  bool CoRun(const Micro& mi, bool speculates) const { return co_run && mi.pn && !mi.idle && (one_bgr_pass || (spec_quant && speculates)); }
   bool defer_rmse = false;  // pipelined, large fields: RANSAC leaves its in-order RMSE sum to a later kernel (nothing downstream
                             // needs it): on sC beside the segmentation at world 1, on the latency stream behind it on a multi-rank run
   uint64_t iter = 0, fork_iter[kSets] = {};
@@ -268,7 +280,7 @@ struct ClipEncoder::Impl : EncodeGeometry {
       --n_spec;
     }
   }
-  template <typename Between> void Luma(uint64_t m, hipStream_t st, bool timing, Between&& between) {
+  template <typename Between> void Luma(uint64_t m, hipStream_t st, bool timing, bool side, Between&& between) {
     cur_pairs = Pn(m);
     const int b = Par(m);
     const uint32_t p0 = P0(m), pn = Pn(m), skip = Skip();
@@ -285,14 +297,33 @@ struct ClipEncoder::Impl : EncodeGeometry {
           Abi(svc_hip_dct_records_luma_frames(enc, frame_bytes, pn, pw, ph, c.dct_block_w, ph,
                                               Records(m).p + (uint64_t)p0 * record_bytes, record_bytes, slots, pyr_stride, st), "svc_hip_dct_records_luma_frames");
       });
-      between();  // (search_after_transform: the motion search of the previous micro-step goes here, right behind the transform)
+      // Co-run: the levels go to the communication stream, behind this transform only.  What they write -- levels >= 1 of this chunk's slots of
+      // pyr[b], and slot 1 on a shard's first chunk -- was last read by a search of the step two back, at the latest search(m - 2): that one is
+      // on the main stream in front of this transform, so the event orders the levels behind it.  search(m - 1), which runs beside them, reads
+      // the other parity's pyramids or (a chunk of the same step) slots up to this chunk's tracked frame, one below the first slot written here.
+      // The next writer of these slots (a luma or transform launch of step + 2) follows search(m) on the main stream, and search(m) waits for
+      // e_pyr (Hbma).  The tracked-only frame is read from the step's frames: the step's last transform, behind which e_step says the frames
+      // are free, is enqueued iterations after search(m) on the main stream.
+      hipStream_t ps = st;
+      if (side) {
+        Hip(hipEventRecord(e_front, st), "hipEventRecord");
+        Hip(hipStreamWaitEvent(sC, e_front, 0), "hipStreamWaitEvent");
+        ps = sC;
+      } else {
+        between();  // (search_after_transform: the motion search of the previous micro-step goes here, right behind the transform)
+      }
       cur_pairs = pn;
-      Run(Stage::kLumaPyramid, st, timing, [&] {
+      Run(Stage::kLumaPyramid, ps, timing, [&] {
         if (skip && first_chunk)  // the tracked-only first frame of the clip has no records: its pyramid the usual way
-          Abi(svc_hip_luma_pyramid_frames(At(m).frames, frame_bytes, 1, pw, ph, c.levels, pyr[b].p + pyr_stride, pyr_stride, st),
+          Abi(svc_hip_luma_pyramid_frames(At(m).frames, frame_bytes, 1, pw, ph, c.levels, pyr[b].p + pyr_stride, pyr_stride, ps),
               "svc_hip_luma_pyramid_frames");
-        Abi(svc_hip_pyramid_levels_frames(slots, pyr_stride, pn, pw, ph, c.levels, st), "svc_hip_pyramid_levels_frames");
+        Abi(svc_hip_pyramid_levels_frames(slots, pyr_stride, pn, pw, ph, c.levels, ps), "svc_hip_pyramid_levels_frames");
       });
+      if (side) {
+        Hip(hipEventRecord(e_pyr[m & 1], sC), "hipEventRecord");
+        pyr_wait[m & 1] = m + 1;
+        between();  // the motion search of the previous micro-step, on the main stream beside the levels
+      }
       return;
     }
     // the chunk's own frames (the first chunk of a shard without a halo also holds the clip's tracked-only frame 0)
@@ -329,6 +360,10 @@ struct ClipEncoder::Impl : EncodeGeometry {
     if (rmse_pending[k]) {  // a deferred RMSE kernel may still read the motion field this rewrites: the slot's newest one is later on its
       Hip(hipStreamWaitEvent(st, e_rmse[k], 0), "hipStreamWaitEvent");  // stream than the one of this chunk's previous step
       rmse_pending[k] = false;
+    }
+    if (pyr_wait[m & 1] == m + 1) {  // co-run: this micro-step's pyramid levels ran on the communication stream (Luma)
+      Hip(hipStreamWaitEvent(st, e_pyr[m & 1], 0), "hipStreamWaitEvent");
+      pyr_wait[m & 1] = 0;
     }
     Run(Stage::kHbma, st, timing, [&] {
       Abi(svc_hip_hbma_pairs(pyr[b].p + t0 * pyr_stride, pyr[b].p + (t0 + 1) * pyr_stride, pyr_stride, pn, c.levels, pw, ph,
@@ -473,8 +508,12 @@ struct ClipEncoder::Impl : EncodeGeometry {
   // One iteration of the software pipeline over micro-steps.  Multi-rank (a halo to wait for): luma + pyramid of m, motion search of
   // m - 1, fork of RANSAC + segmentation of m - 2, transform of m - 2 - depth.  One rank: the motion search of m follows its own pyramids
   // in the same iteration (nothing to wait for), so RANSAC + segmentation of m - 1 fork at the start of the next one and the transform
-  // of m - 1 - depth joins them.  Buffer hazards (a micro-step's events live in slot m % (depth + 2), its data at its chunk's offset
-  // in set step % (depth + 2)):
+  // of m - 1 - depth joins them.  One rank, a micro-step that reads its frames once (the co-run order, unless pyramid_on_main): main stream
+  // transform(m) | search(m - 1) | transform(m + 1) | search(m) ..., the pyramid levels of m on the communication stream behind transform(m),
+  // beside search(m - 1); search(m) waits for them, so RANSAC + segmentation of m fork one iteration later than in the other orders (as
+  // with search_after_transform, whose main-stream order this is).  A two-pass micro-step, a half cut by the idle-pipeline rule and a drain
+  // keep their order and enqueue the search still owed in front of their own.  Hazards of the side-stream levels: Luma.
+  // Buffer hazards (a micro-step's events live in slot m % (depth + 2), its data at its chunk's offset in set step % (depth + 2)):
   //   lat(l) reads mv[l], writes mask / types[l] on stream l % depth, and must be done before transform(l) reads types[l]:
   //     joined there, `depth` iterations after its fork;
   //   hbma(h) writes its chunk of mv[set]: the last reader of that range, lat of the same chunk nsets steps earlier, was joined long before;
@@ -499,6 +538,11 @@ struct ClipEncoder::Impl : EncodeGeometry {
     // pass: a one-pass micro-step runs transform(m) | search(m - 1) | pyramid levels(m) (the search one micro-step behind, as on a
     // multi-rank run), a two-pass one luma(m) | transform(m - 3) | search(m).
     const bool reorder = c.search_after_transform && c.world == 1;
+    // Co-run (one rank; the default order of a micro-step that reads its frames once, pyramid_on_main restores the parent's): the same
+    // main-stream order, transform(m) | search(m - 1), with the pyramid levels of m on the communication stream beside that search (Luma);
+    // search(m) follows transform(m + 1), or whatever this micro-step's successor puts in front of its own search, and waits for the levels
+    // there (Hbma).  Every other micro-step keeps its order and only finds a search more to enqueue in front of its own.
+    const bool side = new_step && CoRun(next_micro, decided);
     bool hbma_done = false;
     auto pending_searches = [&](uint64_t upto) {
       while (n_hbma < upto) { Hbma(n_hbma, sM, timing); ++n_hbma; }
@@ -508,9 +552,9 @@ struct ClipEncoder::Impl : EncodeGeometry {
       const int b = Par(m);
       if (c.world > 1 && halo_recorded[b])  // the send out of pyr[b] two steps ago must have left
         Hip(hipStreamWaitEvent(sM, e_halo[b], 0), "hipStreamWaitEvent");
-      Luma(m, sM, timing, [&] {
+      Luma(m, sM, timing, side, [&] {
         if (do_lat && fork_late) ForkLat(l, timing);
-        if (reorder) { pending_searches(lumas_before); hbma_done = true; }
+        if (reorder || side) { pending_searches(lumas_before); hbma_done = true; }
       });
       if (c.world > 1) Halo(m, timing);
       ++n_luma;
@@ -524,16 +568,21 @@ struct ClipEncoder::Impl : EncodeGeometry {
     }
     // one rank: the search of the micro-step whose pyramids were just enqueued; multi-rank: the previous one's, whose halo has had a
     // whole iteration to arrive
-    const bool do_hbma = (c.world > 1 && new_step) ? n_hbma < lumas_before : n_hbma < n_luma;
-    const uint64_t h = n_hbma;
-    if (do_hbma && c.world > 1) Hip(hipStreamWaitEvent(sM, e_halo[Par(h)], 0), "hipStreamWaitEvent");
-    if (do_hbma) Hbma(h, sM, timing);
+    if (c.world == 1) {
+      if (!hbma_done) pending_searches(n_luma);  // (more than one only behind a co-run micro-step, whose own search is still owed)
+    } else {
+      const bool do_hbma = new_step ? n_hbma < lumas_before : n_hbma < n_luma;
+      const uint64_t h = n_hbma;
+      if (do_hbma) Hip(hipStreamWaitEvent(sM, e_halo[Par(h)], 0), "hipStreamWaitEvent");
+      if (do_hbma) Hbma(h, sM, timing);
+      n_hbma += do_hbma;
+    }
     if (do_dct) {
       JoinLat(d);
       Transform(d, sM, timing);
       MarkStepDone(d);
     }
-    n_hbma += do_hbma; n_lat += do_lat; n_dct += do_dct;
+    n_lat += do_lat; n_dct += do_dct;
     ++iter;
   }
 
@@ -544,7 +593,7 @@ struct ClipEncoder::Impl : EncodeGeometry {
     Decide(s);
     const int b = Par(s);
     if (c.world > 1 && halo_recorded[b]) Hip(hipStreamWaitEvent(sM, e_halo[b], 0), "hipStreamWaitEvent");
-    Luma(s, sM, timing, [] {});
+    Luma(s, sM, timing, false, [] {});
     if (c.world > 1) {
       Halo(s, timing);
       Hip(hipStreamWaitEvent(sM, e_halo[b], 0), "hipStreamWaitEvent");
@@ -629,7 +678,11 @@ ClipEncoder::ClipEncoder(const ClipEncoderConfig& config) : p_(new Impl) {
     for (int b = 0; b < m.nsets; ++b) m.e_rmse[b] = Event(kWho);
   }
   for (int k = 0; k < m.depth; ++k) m.sL[k] = Stream(kWho);
-  for (Event* e : {&m.e_pyr[0], &m.e_pyr[1], &m.e_halo[0], &m.e_halo[1], &m.e_fork}) *e = Event(kWho);
+  for (Event* e : {&m.e_pyr[0], &m.e_pyr[1], &m.e_halo[0], &m.e_halo[1], &m.e_fork, &m.e_front}) *e = Event(kWho);
+  // Only where the communication stream carries nothing else: with the deferred RMSE kernel on it (fields above 8 192 blocks) the levels queue
+  // behind that kernel, which waits for a RANSAC that waits for the latency stream's previous chain -- at 4K they then run inside the NEXT
+  // transform, not beside the search, and the step loses 1.3 % (C5 --wire 2.208 -> 2.236 ms, profiles/ab_pyramid_beside_search.txt, section 5)
+  m.co_run = pipelined && c.world == 1 && !c.pyramid_on_main && !m.defer_rmse;
   for (int b = 0; b < m.nsets; ++b) m.e_join[b] = Event(kWho);
   for (Event& e : m.e_step) e = Event(kWho);
   m.bgr.Alloc(kWho, (size_t)N * m.frame_bytes);
@@ -769,13 +822,14 @@ void ClipEncoder::StepOn(const uint8_t* frames, bool timed) {
   uint8_t order[2] = {0, 0};
   const bool idle = !m.c.chunk_pairs && !m.c.compact && m.c.world == 1 && !m.c.whole_shard_steps && m.n_dct == m.n_luma && P >= 2 &&
                     (m.c.idle_rule_any_size || (uint64_t)P * m.pw * m.ph >= Impl::kIdleRuleMinPixels);
+  bool cut = false;
   if (idle && !m.WouldReadOnce()) {  // (polls the newest foreground measurement)
-    n = 2; cp = (P + 1) / 2;
+    n = 2; cp = (P + 1) / 2; cut = true;
     if (m.spec_quant && !m.c.two_bgr_passes && m.c.mixed_steps && m.fg_share < 0.0) { order[0] = 1; order[1] = 2; }  // nothing known: mixed
   }
   for (uint32_t k = 0; k < n; ++k) {
     const uint32_t p0 = std::min(P, k * cp);
-    m.next_micro = Impl::Micro{m.n_steps, p0, std::min(cp, P - p0), k == 0, n == 2 ? order[k] : (uint8_t)0, frames};
+    m.next_micro = Impl::Micro{m.n_steps, p0, std::min(cp, P - p0), k == 0, n == 2 ? order[k] : (uint8_t)0, frames, cut};
     if (k + 1 == n) m.step_last_micro[m.n_steps % Impl::kRing] = m.n_luma;  // the micro-step this Iterate enters
     m.Iterate(true, timed);
   }
@@ -927,7 +981,8 @@ int svc_clip_create(const svc_clip_config* k, svc_clip** out) {
     constexpr uint32_t kTuneBits = SVC_CLIP_TUNE_STANDALONE_SHAPES | SVC_CLIP_TUNE_SEGMENT_FORK | SVC_CLIP_TUNE_NARROW_ATTEMPTS | SVC_CLIP_TUNE_INLINE_RMSE |
                                    SVC_CLIP_TUNE_TWO_BGR_PASSES | SVC_CLIP_TUNE_ALWAYS_SPECULATE | SVC_CLIP_KEEP_FOREGROUND_PRIOR |
                                    SVC_CLIP_TUNE_WHOLE_SHARD_STEPS | SVC_CLIP_TUNE_SEARCH_AFTER_TRANSFORM | SVC_CLIP_TUNE_IDLE_RULE_ANY_SIZE |
-                                   SVC_CLIP_TUNE_MIXED_STEPS | SVC_CLIP_TUNE_RANDOM_POLICY | SVC_CLIP_TUNE_FORK_BEHIND_FRONT | SVC_CLIP_OUTPUT_COMPACT;
+                                   SVC_CLIP_TUNE_MIXED_STEPS | SVC_CLIP_TUNE_RANDOM_POLICY | SVC_CLIP_TUNE_FORK_BEHIND_FRONT | SVC_CLIP_OUTPUT_COMPACT |
+                                   SVC_CLIP_TUNE_PYRAMID_ON_MAIN;
     if (k->hbma_flags & ~kHbmaBits) throw std::runtime_error("svc_clip_create: unknown hbma_flags bits");
     if (k->tuning & ~kTuneBits) throw std::runtime_error("svc_clip_create: unknown tuning bits");
     if (k->lat_depth > 3) throw std::runtime_error("svc_clip_create: lat_depth must be 0..3");
@@ -953,6 +1008,7 @@ int svc_clip_create(const svc_clip_config* k, svc_clip** out) {
     c.mixed_steps = (k->tuning & SVC_CLIP_TUNE_MIXED_STEPS) != 0;
     c.random_policy = (k->tuning & SVC_CLIP_TUNE_RANDOM_POLICY) != 0;
     c.fork_behind_front = (k->tuning & SVC_CLIP_TUNE_FORK_BEHIND_FRONT) != 0;
+    c.pyramid_on_main = (k->tuning & SVC_CLIP_TUNE_PYRAMID_ON_MAIN) != 0;
     c.compact = (k->tuning & SVC_CLIP_OUTPUT_COMPACT) != 0;
     c.chunk_pairs = k->chunk_pairs;
     std::unique_ptr<svc_clip> h(new svc_clip);
