@@ -82,10 +82,10 @@ struct StreamEncoderConfig {
   uint32_t temporal_period = 1;    // with `delta`: temporal layers (include/svc_hip.h, "Temporal layers").  1, 2 or 4: the encoded frame
                                    // with clip index f has stream index i = f - 1 and is coded against frame i - min(lowbit(i), period), so
                                    // a server thins the stream to 1/2 or 1/4 of the frame rate by dropping frames and their key flags,
-                                   // and svc::StreamDecoder::DecodeDeltaTemporal plays it and every thinning.  Above 1 the route is two
-                                   // calls, svc_hip_dct_pack_levels_frames into a device buffer, then
-                                   // svc_hip_delta_levels_temporal_frames; the plain frame at index -period is carried across batches on
-                                   // the kernel stream, so the stream does not depend on batch or depth.  1 takes the fused route above.
+                                   // and svc::StreamDecoder::DecodeDeltaTemporal plays it and every thinning.  Above 1 the route is one
+                                   // call, svc_hip_dct_pack_delta_temporal_frames (include/svc_hip_temporal.h), straight from the
+                                   // pixels as at period 1; the input frame at index -period and its region ids are carried across
+                                   // batches on the device, so the stream does not depend on batch or depth.
                                    // The constructor throws for another period, for a period above 1 without `delta` or with auto_key,
                                    // and for a `batch` the period does not divide.  With `entropy` the frames are coded unchanged
   std::function<bool(uint32_t frame, uint32_t xywh[4])> enh_window;  // with enh_step: the window of each encoded frame.  Empty: every

@@ -54,6 +54,13 @@
 // form's runs without its flags (both counts of a frame are a function of two input frames), stopped after quantising; a wave stores the
 // two counts of its piece per frame, dct_delta_select_kernel sums them per frame and writes the flags, and the delta form's three
 // launches follow with those flags.
+//
+// Both with temporal layers (svc_hip_dct_pack_delta_temporal_frames, svc_hip_dct_pack_delta_temporal_auto_frames;
+// include/svc_hip_temporal.h states them): frame i against INPUT frame i - min(lowbit(i), period), period 2 or 4, the bytes of
+// svc_hip_dct_pack_levels_frames followed by svc_hip_delta_levels_temporal_frames.  A run of 8 starts at a frame of layer 0, so every
+// reference but that of the run's first frame lies in the run: PERIOD is a template parameter of the DELTA and TALLY forms, the trip in
+// front of the run transforms frame run_first - PERIOD, and the kept levels are replaced only at a frame a later one refers to.  The
+// other five forms' device code is instruction for instruction what it was (profiles/dct_pack_delta_temporal_c3.txt).
 #include <algorithm>
 #include <type_traits>
 
@@ -62,6 +69,7 @@
 #include "quant_core.hpp"
 #include "stream_format.hpp"
 #include "svc_common.hpp"
+#include "svc_hip_temporal.h"
 
 namespace svc {
 namespace {
@@ -179,6 +187,17 @@ struct DeltaTallyArgs : DeltaRunArgs {
 #endif
 constexpr uint32_t kDeltaRun = SVC_DCT_PACK_DELTA_RUN;
 static_assert(kDeltaRun >= 1, "a run holds a frame");
+// Temporal layers: a run starts at a frame of layer 0, so it holds whole periods (a build that probes another kDeltaRun keeps 8 here).
+constexpr uint32_t kTemporalRun = kDeltaRun % 4 == 0 ? kDeltaRun : 8;
+// Period 4 needs the levels of frame 4k (for 4k + 1, 4k + 2 and 4k + 4) and of 4k + 2 (for 4k + 3).  0: both are kept, 48 dwords, and the
+// kernel has 139 / 147 VGPRs: three workgroups a CU where the delta form has four.  1: one set is kept -- frame 4k + 2's levels replace
+// frame 4k's, and frame 4k is transformed a second time in front of frame 4k + 4 (not where that is a key frame): 10 transforms for
+// 8 frames at period 2's registers.  Both measured in profiles/dct_pack_delta_temporal_c3.txt (tools/dct_pack_probe.py
+// delta-temporal-encode builds this file once per value).
+#ifndef SVC_DCT_PACK_TEMPORAL_REDO
+#define SVC_DCT_PACK_TEMPORAL_REDO 0
+#endif
+constexpr bool kTemporalRedo = SVC_DCT_PACK_TEMPORAL_REDO != 0;
 constexpr uint32_t kTauTable = 2 * kMaxLadder;  // a class's thresholds, padded with +inf to what 7 probes can reach
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
@@ -222,7 +241,12 @@ __device__ __forceinline__ uint32_t sub2(uint32_t a, uint32_t b) {
 // TALLY = true (with DELTA): the delta form's runs, stopped after quantising: no flag is read, nothing is staged or walked; per frame
 // the wave stores the non-zero levels and the non-zero differences of its piece to its own place in k.tally
 // (svc_hip_dct_pack_delta_auto_frames sums and chooses by them).
-template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false>
+// PERIOD = 2 or 4 (with DELTA, alone or with TALLY): the delta form with temporal layers, frame i against frame i - min(lowbit(i), PERIOD).
+// kTemporalRun is a multiple of 4, so a run starts at a frame of layer 0 and every reference but its first frame's lies in the run: the trip
+// in front of the run transforms frame run_first - PERIOD, `before` keeps the last frame of layer 0 (2k or 4k: it is replaced only there)
+// and, PERIOD = 4, `mid` keeps frame 4k + 2 for frame 4k + 3.  A run still costs R + 1 transforms.  REDO (PERIOD = 4): no `mid`; `before`
+// takes frame 4k + 2's levels as well, and a trip in front of frame 4k + 4 puts frame 4k's back (kTemporalRedo above).
+template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false, int PERIOD = 1, bool REDO = false>
 __device__ __forceinline__ void dct_pack_body(
     const DctPackArgs& a,
     const std::conditional_t<COUNT, CountArgs,
@@ -232,6 +256,9 @@ __device__ __forceinline__ void dct_pack_body(
   static_assert(!(COUNT && LAYERS), "the counting form has no layers");
   static_assert(!(DELTA && (COUNT || LAYERS)), "the delta form is one layer at fixed steps");
   static_assert(!TALLY || DELTA, "the tally walks the delta form's runs");
+  static_assert(PERIOD == 1 || (DELTA && (PERIOD == 2 || PERIOD == 4) && kTemporalRun % PERIOD == 0), "temporal layers: the delta form, whole periods a run");
+  static_assert(!REDO || PERIOD == 4, "only period 4 has a second kept frame to trade for a transform");
+  constexpr bool kMid = PERIOD == 4 && !REDO;  // frame 4k + 2 is kept in `mid`
   constexpr uint32_t kCols = 64 / N;        // segment columns of a wave
   constexpr uint32_t kColWords = N / 4;     // mask words of a segment column: two 8x8 tiles of one word, or one 16x16 tile of four
   constexpr int kSlab = N == 8 ? kSlab8 : kSlab16;
@@ -267,6 +294,9 @@ __device__ __forceinline__ void dct_pack_body(
   uint32_t run_first = 0, run_len = 1;
   uint32_t before[3][8] = {};  // DELTA: the undifferenced levels of the frame before, as lv below, and that frame's type of the lane's tile
   uint32_t t_before = 0;
+  uint32_t mid[3][8] = {};  // kMid: the same of frame 4k + 2, from there to frame 4k + 3
+  bool redo = false;        // REDO: this trip transforms frame 4k again, in front of frame 4k + 4 (`it` stays at 4k + 3)
+  uint32_t t_mid = 0;
   uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
   if constexpr (DELTA) {
     run_first = frame0 * k.run;
@@ -274,7 +304,11 @@ __device__ __forceinline__ void dct_pack_body(
   }
   int it = DELTA ? -1 : 0;
   do {  // (a trip's statements keep the indentation they have had as the only trip)
-  const uint32_t frame = DELTA ? run_first + (uint32_t)it : frame0;
+  const uint32_t frame = !DELTA ? frame0 : PERIOD > 1 && it < 0 ? run_first - (uint32_t)PERIOD
+                                         : REDO && redo     ? run_first + (uint32_t)it - 3u : run_first + (uint32_t)it;
+  const bool use_mid = kMid && (it & 3) == 3;  // (it = -1 too: nothing is subtracted in that trip)
+  // PERIOD > 1: a trip whose frame is only kept, for the frame after it (asked only in that form's own statements: the others' code stays)
+  auto front = [&] { return it < 0 || (REDO && redo); };
   bool key = false;  // DELTA: a key frame is not predicted, and the frame in front of it is not read
   const uint8_t* frame_bgr = nullptr;  // DELTA: the trip's frame and its types
   const uint32_t* frame_types = nullptr;
@@ -325,7 +359,7 @@ __device__ __forceinline__ void dct_pack_body(
   const uint32_t nwords = ncols * kColWords;                           // mask words of the piece, in the format's order
   const uint32_t word0 = (seg0 * (16 / N)) * gm.l.words;               // the piece's first word within its tile row
   // DELTA: the lane's tile is predicted where both frames code it at one step
-  const bool predicted = DELTA && !key && (k_one_step(k) || (t == 0) == (t_before == 0));
+  const bool predicted = DELTA && !key && (k_one_step(k) || (t == 0) == ((kMid && use_mid ? t_mid : t_before) == 0));
   uint32_t tally = 0;  // TALLY: this lane's non-zero levels of the frame (at most 48) in the low half, non-zero differences in the high
 
 #pragma unroll
@@ -416,7 +450,22 @@ __device__ __forceinline__ void dct_pack_body(
       }
       continue;  // (the slabs are free for the next channel: the sync above)
     }
-    if constexpr (DELTA) {  // the levels stay for the next frame; what is staged and walked is their difference to the frame before
+    if constexpr (DELTA && PERIOD > 1) {  // the same against the kept frame of the trip's layer; the levels stay where a later frame refers to them
+      // (the same in every lane)  REDO: every even frame is kept, frame 4k + 2 in frame 4k's place
+      const bool keep = front() || (it & (REDO ? 1 : PERIOD - 1)) == 0, keep_mid = kMid && (it & 3) == 2;
+#pragma unroll
+      for (int v = 0; v < 8; ++v) {
+        const uint32_t cur = lv[v];
+        if (predicted) lv[v] = sub2(cur, kMid && use_mid ? mid[c][v] : before[c][v]);
+        if constexpr (TALLY) {
+          const uint32_t d = lv[v];
+          tally += ((cur & 0xFFFFu) != 0) + ((cur >> 16) != 0) + ((((d & 0xFFFFu) != 0) + ((d >> 16) != 0)) << 16);
+        }
+        if (keep) before[c][v] = cur;
+        if (kMid && keep_mid) mid[c][v] = cur;
+      }
+      if (front() || TALLY) continue;  // a frame that is only kept is not packed (its tally is not stored); the tally packs nothing
+    } else if constexpr (DELTA) {  // the levels stay for the next frame; what is staged and walked is their difference to the frame before
 #pragma unroll
       for (int v = 0; v < 8; ++v) {
         const uint32_t cur = lv[v];
@@ -483,13 +532,23 @@ __device__ __forceinline__ void dct_pack_body(
   if constexpr (TALLY) {  // a wave's 64 x 48 coefficients: both sums fit their halves.  A place per wave and frame, no atomics: with
     // 65 280 adds into the one cache line that holds a batch's 32 counters the call took 0.709 ms at C3 (1, 640), with the stores 0.238
     // (profiles/dct_pack_delta_auto_c3.txt)
-    if (it >= 0) {
+    if (it >= 0 && !(REDO && redo)) {
       const uint32_t sum = wave_sum(tally);
       if (lane == 0) *reinterpret_cast<uint2*>(k.tally + ((size_t)wv * k.run + (uint32_t)it) * 2) = make_uint2(sum & 0xFFFFu, sum >> 16);
     }
   }
-  t_before = t;
-  } while (DELTA && ++it < (int)run_len);
+  if constexpr (PERIOD > 1) {
+    if (front() || (it & (REDO ? 1 : PERIOD - 1)) == 0) t_before = t;
+    if (kMid && (it & 3) == 2) t_mid = t;
+  } else {
+    t_before = t;
+  }
+  if constexpr (REDO) {  // after frame 4k + 3, where frame 4k + 4 is in the run and predicted: frame 4k once more, then on
+    bool again = !redo && (it & 3) == 3 && it + 1 < (int)run_len;
+    if constexpr (!TALLY) again = again && !(k.key && k.key[run_first + (uint32_t)it + 1u] != 0);
+    redo = again;
+  }
+  } while (DELTA && ((REDO && redo) || ++it < (int)run_len));
   if constexpr (COUNT) {  // the wave's row: bins 0 .. len - 2 as they are, bin len - 1 = the lanes' full counts
     uint32_t* hist = hist_all[tid >> 6];
     if (full) atomicAdd(&hist[k.lad.len - 1], full);
@@ -517,6 +576,17 @@ __global__ __launch_bounds__(256) void dct_pack_delta_kernel(DctPackArgs a, Delt
 template <int N>
 __global__ __launch_bounds__(256) void dct_delta_count_kernel(DctPackArgs a, DeltaTallyArgs k) {
   dct_pack_body<N, false, false, true, true>(a, k, nullptr, nullptr);
+}
+
+// both with temporal layers: a frame against frame i - min(lowbit(i), PERIOD)
+template <int N, int PERIOD>
+__global__ __launch_bounds__(256) void dct_pack_delta_temporal_kernel(DctPackArgs a, DeltaRunArgs k) {
+  dct_pack_body<N, false, false, true, false, PERIOD, PERIOD == 4 && kTemporalRedo>(a, k, nullptr, nullptr);
+}
+
+template <int N, int PERIOD>
+__global__ __launch_bounds__(256) void dct_delta_temporal_count_kernel(DctPackArgs a, DeltaTallyArgs k) {
+  dct_pack_body<N, false, false, true, true, PERIOD, PERIOD == 4 && kTemporalRedo>(a, k, nullptr, nullptr);
 }
 
 // One workgroup per frame: the waves' counts summed (u32 sums: any order gives the same counts), then the key frame by size,
@@ -680,6 +750,12 @@ int validate_pack_geom(const char* what, uint32_t w, uint32_t h, uint32_t block,
   return SVC_OK;
 }
 
+// the period of the temporal calls, checked right after the geometry (the rule of the temporal calls on streams, csrc/levels.hip)
+int validate_pack_period(const char* what, uint32_t period) {
+  SVC_REQUIRE(period == 1 || period == 2 || period == 4, "%s: period %u (supported: 1, 2, 4)", what, period);
+  return SVC_OK;
+}
+
 // the formats' limits with SVCQ's worst case, and one launch's worth of waves
 int validate_pack_limits(const char* what, uint32_t n, const PackGeom& g) {
   const int rc = validate_limits(what, n, g.w, g.h, g.n_block, g.n_block, g.l.max_bytes);
@@ -715,13 +791,37 @@ int enqueue_dct_pack(const char* what, DctPackArgs& a, uint32_t n_frames, uint32
   return enqueue_assemble(what, a, a.ws, n_frames, fg, bg, d_out, d_frame_offsets, s);
 }
 
+// the delta form's kernel (period 1) or the temporal form's, for a block of 8 or 16 and a period of 1, 2 or 4: the pack, and its counting
+void launch_delta_pack(uint32_t block, uint32_t period, dim3 grid, hipStream_t s, const DctPackArgs& a, const DeltaRunArgs& k) {
+  const dim3 blk(kThreads);
+  if (block == 8) {
+    if (period == 1) hipLaunchKernelGGL(dct_pack_delta_kernel<8>, grid, blk, 0, s, a, k);
+    else if (period == 2) hipLaunchKernelGGL((dct_pack_delta_temporal_kernel<8, 2>), grid, blk, 0, s, a, k);
+    else hipLaunchKernelGGL((dct_pack_delta_temporal_kernel<8, 4>), grid, blk, 0, s, a, k);
+  } else {
+    if (period == 1) hipLaunchKernelGGL(dct_pack_delta_kernel<16>, grid, blk, 0, s, a, k);
+    else if (period == 2) hipLaunchKernelGGL((dct_pack_delta_temporal_kernel<16, 2>), grid, blk, 0, s, a, k);
+    else hipLaunchKernelGGL((dct_pack_delta_temporal_kernel<16, 4>), grid, blk, 0, s, a, k);
+  }
+}
+void launch_delta_count(uint32_t block, uint32_t period, dim3 grid, hipStream_t s, const DctPackArgs& a, const DeltaTallyArgs& k) {
+  const dim3 blk(kThreads);
+  if (block == 8) {
+    if (period == 1) hipLaunchKernelGGL(dct_delta_count_kernel<8>, grid, blk, 0, s, a, k);
+    else if (period == 2) hipLaunchKernelGGL((dct_delta_temporal_count_kernel<8, 2>), grid, blk, 0, s, a, k);
+    else hipLaunchKernelGGL((dct_delta_temporal_count_kernel<8, 4>), grid, blk, 0, s, a, k);
+  } else {
+    if (period == 1) hipLaunchKernelGGL(dct_delta_count_kernel<16>, grid, blk, 0, s, a, k);
+    else if (period == 2) hipLaunchKernelGGL((dct_delta_temporal_count_kernel<16, 2>), grid, blk, 0, s, a, k);
+    else hipLaunchKernelGGL((dct_delta_temporal_count_kernel<16, 4>), grid, blk, 0, s, a, k);
+  }
+}
+
 // the delta form's three launches: a wave per piece and RUN of k.n_frames frames, then the fused pack's scan and assemble
 int enqueue_dct_pack_delta(const char* what, DctPackArgs& a, const DeltaRunArgs& k, uint32_t fg, uint32_t bg, uint8_t* d_out,
-                           uint64_t* d_frame_offsets, hipStream_t s) {
-  a.total_waves = div_up(k.n_frames, kDeltaRun) * a.g.l.tiles_y * a.g.waves_per_row;
-  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
-  if (a.g.n_block == 8) hipLaunchKernelGGL(dct_pack_delta_kernel<8>, grid, blk, 0, s, a, k);
-  else hipLaunchKernelGGL(dct_pack_delta_kernel<16>, grid, blk, 0, s, a, k);
+                           uint64_t* d_frame_offsets, hipStream_t s, uint32_t period = 1) {
+  a.total_waves = div_up(k.n_frames, k.run) * a.g.l.tiles_y * a.g.waves_per_row;
+  launch_delta_pack(a.g.n_block, period, dim3(div_up(a.total_waves, 4)), s, a, k);
   const int rc = check_launch(what, "transform");
   if (rc) return rc;
   return enqueue_assemble(what, a, a.ws, k.n_frames, fg, bg, d_out, d_frame_offsets, s);
@@ -730,12 +830,13 @@ int enqueue_dct_pack_delta(const char* what, DctPackArgs& a, const DeltaRunArgs&
 // the auto call's workspace: the delta call's, then both level counts of every wave's piece of every frame, whole runs
 struct DeltaAutoWs {
   DctPackWs pack;
-  uint32_t* tally;  // [runs][waves of a frame][kDeltaRun][2]
+  uint32_t* tally;  // [runs][waves of a frame][run][2], run = kDeltaRun or kTemporalRun
 };
 DeltaAutoWs delta_auto_ws(Carver& c, uint32_t n, const PackGeom& g) {
   DeltaAutoWs s;
   s.pack = pack_ws(c, n, g);
-  s.tally = c.take<uint32_t>(2ull * kDeltaRun * div_up(n, kDeltaRun) * g.l.tiles_y * g.waves_per_row);
+  // (whole runs of either length: the two are one number unless a probe build sets another kDeltaRun)
+  s.tally = c.take<uint32_t>(2ull * std::max(kDeltaRun * div_up(n, kDeltaRun), kTemporalRun * div_up(n, kTemporalRun)) * g.l.tiles_y * g.waves_per_row);
   return s;
 }
 
@@ -799,29 +900,31 @@ uint64_t svc_hip_dct_pack_delta_workspace_bytes(uint32_t n_frames, uint32_t fram
 
 // Checked in the order of svc_hip_dct_pack_levels_frames: geometry, stride, steps, limits, sizes; n_frames == 0 then returns SVC_OK; then
 // pointers, the pairing of d_prev_bgr and d_prev_types among them.
-int svc_hip_dct_pack_delta_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+// `period`: 1 for svc_hip_dct_pack_delta_frames, else the temporal call's, checked right after the geometry.
+static int dct_pack_delta(const char* what, uint32_t period, const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
                                   uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
                                   uint32_t bg_step, const uint8_t* d_prev_bgr, const uint32_t* d_prev_types, const uint32_t* d_key,
                                   uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
                                   uint64_t* d_frame_offsets, void* stream) {
-  int rc = validate_pack_geom("dct_pack_delta", frame_w, frame_h, block, mv_block_w, mv_block_h);
+  int rc = validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h);
   if (rc) return rc;
+  if ((rc = validate_pack_period(what, period))) return rc;
   SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
-              "dct_pack_delta: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", (unsigned long long)frame_stride_bytes,
+              "%s: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", what, (unsigned long long)frame_stride_bytes,
               3ull * frame_w * frame_h);
-  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "dct_pack_delta: quant steps must be positive");
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "%s: quant steps must be positive", what);
   // (the pack's int16 bound holds for every step at 8x8 and 16x16, as in svc_hip_dct_pack_levels_frames; a difference wraps by definition)
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
-  if ((rc = validate_pack_limits("dct_pack_delta", n_frames, g))) return rc;
-  if ((rc = require_workspace("dct_pack_delta", workspace_bytes, layout_bytes(pack_ws, n_frames, g)))) return rc;
-  if ((rc = require_capacity("dct_pack_delta", "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
+  if ((rc = validate_pack_limits(what, n_frames, g))) return rc;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(pack_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity(what, "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
   if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
-  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets, "dct_pack_delta: null pointer");
+  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets, "%s: null pointer", what);
   SVC_REQUIRE((d_prev_bgr == nullptr) == (d_prev_types == nullptr),
-              "dct_pack_delta: the frame before frame 0 is its pixels and its types: d_prev_bgr and d_prev_types are given together or not at all");
+              "%s: the frame before frame 0 is its pixels and its types: d_prev_bgr and d_prev_types are given together or not at all", what);
   SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_prev_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4) && aligned(d_prev_types, 4) && aligned(d_key, 4),
-              "dct_pack_delta: frames, d_prev_bgr, output and workspace must be 16-byte aligned, offsets 8-byte, types and key flags 4-byte");
+              "%s: frames, d_prev_bgr, output and workspace must be 16-byte aligned, offsets 8-byte, types and key flags 4-byte", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
   DctPackArgs a{};
   a.bgr = d_bgr;
@@ -833,8 +936,18 @@ int svc_hip_dct_pack_delta_frames(const uint8_t* d_bgr, uint64_t frame_stride_by
   a.fg_inv = 1.0f / a.fg_step;
   a.bg_inv = 1.0f / a.bg_step;
   a.ws = carve(d_workspace, pack_ws, n_frames, g);
-  const DeltaRunArgs k{d_prev_bgr, d_prev_types, d_key, n_frames, kDeltaRun, fg_step == bg_step ? 1u : 0u};
-  return enqueue_dct_pack_delta("dct_pack_delta", a, k, fg_step, bg_step, d_out, d_frame_offsets, s);
+  const DeltaRunArgs k{d_prev_bgr, d_prev_types, d_key, n_frames, period == 1 ? kDeltaRun : kTemporalRun, fg_step == bg_step ? 1u : 0u};
+  return enqueue_dct_pack_delta(what, a, k, fg_step, bg_step, d_out, d_frame_offsets, s, period);
+}
+
+int svc_hip_dct_pack_delta_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w, uint32_t frame_h,
+                                  uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step,
+                                  uint32_t bg_step, const uint8_t* d_prev_bgr, const uint32_t* d_prev_types, const uint32_t* d_key,
+                                  uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                  uint64_t* d_frame_offsets, void* stream) {
+  return dct_pack_delta("dct_pack_delta", 1, d_bgr, frame_stride_bytes, n_frames, frame_w, frame_h, block, d_block_types, mv_block_w, mv_block_h,
+                        fg_step, bg_step, d_prev_bgr, d_prev_types, d_key, d_workspace, workspace_bytes, d_out, out_capacity, d_frame_offsets,
+                        stream);
 }
 
 uint64_t svc_hip_dct_pack_delta_auto_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,
@@ -847,32 +960,34 @@ uint64_t svc_hip_dct_pack_delta_auto_workspace_bytes(uint32_t n_frames, uint32_t
 
 // Checked as svc_hip_dct_pack_delta_frames, the new pointers where it checks d_key.  Five launches whatever n_frames: the counting
 // kernel, the selection, then that call's own three with d_key_out as their flags.
-int svc_hip_dct_pack_delta_auto_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+// `period` as in dct_pack_delta.
+static int dct_pack_delta_auto(const char* what, uint32_t period, const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
                                        uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
                                        uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint8_t* d_prev_bgr,
                                        const uint32_t* d_prev_types, const uint32_t* d_forced, uint8_t* d_workspace, uint64_t workspace_bytes,
                                        uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets, uint32_t* d_key_out,
                                        uint32_t* d_level_counts, void* stream) {
-  int rc = validate_pack_geom("dct_pack_delta_auto", frame_w, frame_h, block, mv_block_w, mv_block_h);
+  int rc = validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h);
   if (rc) return rc;
+  if ((rc = validate_pack_period(what, period))) return rc;
   SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
-              "dct_pack_delta_auto: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)",
+              "%s: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", what,
               (unsigned long long)frame_stride_bytes, 3ull * frame_w * frame_h);
-  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "dct_pack_delta_auto: quant steps must be positive");
+  SVC_REQUIRE(fg_step > 0 && bg_step > 0, "%s: quant steps must be positive", what);
   const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
-  if ((rc = validate_pack_limits("dct_pack_delta_auto", n_frames, g))) return rc;
-  if ((rc = require_workspace("dct_pack_delta_auto", workspace_bytes, layout_bytes(delta_auto_ws, n_frames, g)))) return rc;
-  if ((rc = require_capacity("dct_pack_delta_auto", "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
+  if ((rc = validate_pack_limits(what, n_frames, g))) return rc;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(delta_auto_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity(what, "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
   if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
-  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets && d_key_out, "dct_pack_delta_auto: null pointer");
+  SVC_REQUIRE(d_bgr && d_block_types && d_workspace && d_out && d_frame_offsets && d_key_out, "%s: null pointer", what);
   SVC_REQUIRE((d_prev_bgr == nullptr) == (d_prev_types == nullptr),
-              "dct_pack_delta_auto: the frame before frame 0 is its pixels and its types: d_prev_bgr and d_prev_types are given together or "
-              "not at all");
+              "%s: the frame before frame 0 is its pixels and its types: d_prev_bgr and d_prev_types are given together or "
+              "not at all", what);
   SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_prev_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) &&
                   aligned(d_block_types, 4) && aligned(d_prev_types, 4) && aligned(d_forced, 4) && aligned(d_key_out, 4) &&
                   aligned(d_level_counts, 4),
-              "dct_pack_delta_auto: frames, d_prev_bgr, output and workspace must be 16-byte aligned, offsets 8-byte, types, forced flags, key "
-              "flags and level counts 4-byte");
+              "%s: frames, d_prev_bgr, output and workspace must be 16-byte aligned, offsets 8-byte, types, forced flags, key "
+              "flags and level counts 4-byte", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
   DctPackArgs a{};
   a.bgr = d_bgr;
@@ -885,19 +1000,68 @@ int svc_hip_dct_pack_delta_auto_frames(const uint8_t* d_bgr, uint64_t frame_stri
   a.bg_inv = 1.0f / a.bg_step;
   const DeltaAutoWs ws = carve(d_workspace, delta_auto_ws, n_frames, g);
   a.ws = ws.pack;
-  a.total_waves = div_up(n_frames, kDeltaRun) * g.l.tiles_y * g.waves_per_row;  // a wave per piece and RUN, as the pack below
+  const uint32_t run = period == 1 ? kDeltaRun : kTemporalRun;
+  a.total_waves = div_up(n_frames, run) * g.l.tiles_y * g.waves_per_row;  // a wave per piece and RUN, as the pack below
   DeltaTallyArgs t{};
-  static_cast<DeltaRunArgs&>(t) = DeltaRunArgs{d_prev_bgr, d_prev_types, nullptr, n_frames, kDeltaRun, fg_step == bg_step ? 1u : 0u};
+  static_cast<DeltaRunArgs&>(t) = DeltaRunArgs{d_prev_bgr, d_prev_types, nullptr, n_frames, run, fg_step == bg_step ? 1u : 0u};
   t.tally = ws.tally;
-  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
-  if (block == 8) hipLaunchKernelGGL(dct_delta_count_kernel<8>, grid, blk, 0, s, a, t);
-  else hipLaunchKernelGGL(dct_delta_count_kernel<16>, grid, blk, 0, s, a, t);
-  if ((rc = check_launch("dct_pack_delta_auto", "count"))) return rc;
-  const DeltaSelectArgs sel{ws.tally, d_forced, d_key_out, d_level_counts, g.l.tiles_y * g.waves_per_row, kDeltaRun, d_prev_bgr ? 1u : 0u};
-  hipLaunchKernelGGL(dct_delta_select_kernel, dim3(n_frames), blk, 0, s, sel);
-  if ((rc = check_launch("dct_pack_delta_auto", "select"))) return rc;
-  const DeltaRunArgs k{d_prev_bgr, d_prev_types, d_key_out, n_frames, kDeltaRun, fg_step == bg_step ? 1u : 0u};
-  return enqueue_dct_pack_delta("dct_pack_delta_auto", a, k, fg_step, bg_step, d_out, d_frame_offsets, s);
+  launch_delta_count(block, period, dim3(div_up(a.total_waves, 4)), s, a, t);
+  if ((rc = check_launch(what, "count"))) return rc;
+  const DeltaSelectArgs sel{ws.tally, d_forced, d_key_out, d_level_counts, g.l.tiles_y * g.waves_per_row, run, d_prev_bgr ? 1u : 0u};
+  hipLaunchKernelGGL(dct_delta_select_kernel, dim3(n_frames), dim3(kThreads), 0, s, sel);
+  if ((rc = check_launch(what, "select"))) return rc;
+  const DeltaRunArgs k{d_prev_bgr, d_prev_types, d_key_out, n_frames, run, fg_step == bg_step ? 1u : 0u};
+  return enqueue_dct_pack_delta(what, a, k, fg_step, bg_step, d_out, d_frame_offsets, s, period);
+}
+
+int svc_hip_dct_pack_delta_auto_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                       uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                       uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint8_t* d_prev_bgr,
+                                       const uint32_t* d_prev_types, const uint32_t* d_forced, uint8_t* d_workspace, uint64_t workspace_bytes,
+                                       uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets, uint32_t* d_key_out,
+                                       uint32_t* d_level_counts, void* stream) {
+  return dct_pack_delta_auto("dct_pack_delta_auto", 1, d_bgr, frame_stride_bytes, n_frames, frame_w, frame_h, block, d_block_types, mv_block_w,
+                             mv_block_h, fg_step, bg_step, d_prev_bgr, d_prev_types, d_forced, d_workspace, workspace_bytes, d_out,
+                             out_capacity, d_frame_offsets, d_key_out, d_level_counts, stream);
+}
+
+// ---- temporal layers: the two calls above with a period (include/svc_hip_temporal.h; the workspaces are their siblings')
+
+uint64_t svc_hip_dct_pack_delta_temporal_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                                         uint32_t mv_block_w, uint32_t mv_block_h, uint32_t period) {
+  if (validate_pack_geom("dct_pack_delta_temporal_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h) ||
+      validate_pack_period("dct_pack_delta_temporal_workspace_bytes", period))
+    return 0;
+  return svc_hip_dct_pack_delta_workspace_bytes(n_frames, frame_w, frame_h, block, mv_block_w, mv_block_h);
+}
+
+int svc_hip_dct_pack_delta_temporal_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                           uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                           uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint8_t* d_prev_bgr,
+                                           const uint32_t* d_prev_types, const uint32_t* d_key, uint8_t* d_workspace, uint64_t workspace_bytes,
+                                           uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets, void* stream, uint32_t period) {
+  return dct_pack_delta("dct_pack_delta_temporal", period, d_bgr, frame_stride_bytes, n_frames, frame_w, frame_h, block, d_block_types,
+                        mv_block_w, mv_block_h, fg_step, bg_step, d_prev_bgr, d_prev_types, d_key, d_workspace, workspace_bytes, d_out,
+                        out_capacity, d_frame_offsets, stream);
+}
+
+uint64_t svc_hip_dct_pack_delta_temporal_auto_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                                              uint32_t mv_block_w, uint32_t mv_block_h, uint32_t period) {
+  if (validate_pack_geom("dct_pack_delta_temporal_auto_workspace_bytes", frame_w, frame_h, block, mv_block_w, mv_block_h) ||
+      validate_pack_period("dct_pack_delta_temporal_auto_workspace_bytes", period))
+    return 0;
+  return svc_hip_dct_pack_delta_auto_workspace_bytes(n_frames, frame_w, frame_h, block, mv_block_w, mv_block_h);
+}
+
+int svc_hip_dct_pack_delta_temporal_auto_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                                uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                                uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, const uint8_t* d_prev_bgr,
+                                                const uint32_t* d_prev_types, const uint32_t* d_forced, uint8_t* d_workspace,
+                                                uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets,
+                                                uint32_t* d_key_out, uint32_t* d_level_counts, void* stream, uint32_t period) {
+  return dct_pack_delta_auto("dct_pack_delta_temporal_auto", period, d_bgr, frame_stride_bytes, n_frames, frame_w, frame_h, block,
+                             d_block_types, mv_block_w, mv_block_h, fg_step, bg_step, d_prev_bgr, d_prev_types, d_forced, d_workspace,
+                             workspace_bytes, d_out, out_capacity, d_frame_offsets, d_key_out, d_level_counts, stream);
 }
 
 uint64_t svc_hip_dct_pack_layers_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block, uint32_t mv_block_w,

@@ -5,6 +5,7 @@
 #include "batch_pipe.hpp"
 #include "copy_crew.hpp"
 #include "encode_geometry.hpp"
+#include "svc_hip_temporal.h"
 
 #include <sched.h>
 
@@ -52,13 +53,8 @@ struct Slot {
   // auto_key: the flags the caller's rule forces (key then holds the device's choice), and both level counts of every frame
   DevBuf<uint32_t> forced, level_counts;
   PinBuf<uint32_t> pin_forced, pin_level_counts;
-  // temporal_period > 1: the batch's plain SVCQ stream, which the temporal delta call reads, and that call's statuses
-  DevBuf<uint8_t> plain;
-  DevBuf<uint64_t> plain_offsets;
-  DevBuf<uint32_t> delta_status;
-  PinBuf<uint64_t> pin_plain_offsets;
-  PinBuf<uint32_t> pin_delta_status;
-  Event plain_offsets_done;  // the plain stream's offsets are in pin_plain_offsets
+  // temporal_period > 1: the input frame at index -period of the batch's first encoded frame, copied on the device from the slot before
+  DevBuf<uint8_t> before_bgr;
   uint32_t frames = 0;  // source frames resident in bgr (the last one carries into the next batch)
   uint32_t encoded = 0, first = 0;
 };
@@ -74,8 +70,7 @@ struct StreamEncoder::Impl : EncodeGeometry {
   uint64_t coded_bytes = 0, entropy_ws_bytes = 0; // entropy: worst case of a coded batch, coder workspace
   bool budgeted = false;                          // compact_budget != 0: rate control
   bool layered = false;                           // enh_step != 0: a base and an enhancement stream
-  bool temporal = false;                          // delta with temporal_period > 1: the plain pack, then the temporal delta call
-  uint64_t plain_ws_bytes = 0;                    // temporal: the plain pack's workspace (pack_ws_bytes: the delta call's)
+  bool temporal = false;                          // delta with temporal_period > 1: svc_hip_dct_pack_delta_temporal_frames
   std::atomic<uint32_t> budget{0};                // bytes per frame of the next batch staged (SetCompactBudget)
   std::vector<std::unique_ptr<Slot>> slots;       // the buffers of the pipe's slots
   bool fused_records = false;  // wire: the transform kernel emits the records itself
@@ -153,11 +148,10 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     m.pack_ws_bytes = m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
                       : m.layered ? svc_hip_pack_layers_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th)
                       : c.auto_key ? svc_hip_dct_pack_delta_auto_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh)
-                      : m.temporal ? svc_hip_delta_levels_temporal_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.temporal_period)
+                      : m.temporal ? svc_hip_dct_pack_delta_temporal_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh, c.temporal_period)
                       : c.delta   ? svc_hip_dct_pack_delta_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh)
                                   : svc_hip_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th);
-    if (m.temporal) m.plain_ws_bytes = svc_hip_dct_pack_levels_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh);
-    if (!m.packed_bytes || !m.pack_ws_bytes || (m.temporal && !m.plain_ws_bytes))
+    if (!m.packed_bytes || !m.pack_ws_bytes)
       throw std::runtime_error("svc::StreamEncoder: no compact stream for this geometry");
   }
   m.crew.reset(new CopyCrew(std::min<uint32_t>(c.copy_threads ? c.copy_threads - 1 : 0, 15)));
@@ -181,7 +175,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
     if ((!c.wire || !m.fused_records) && !c.delta) s->coeffs.Alloc(kWho, B * 3 * m.plane_elems);  // (the delta route has no planes)
     if (!c.wire && !c.compact) s->pin_coeffs.Alloc(kWho, B * 3 * m.plane_elems);
     if (c.compact) {
-      s->packed.Alloc(kWho, m.packed_bytes); s->pack_ws.Alloc(kWho, std::max(m.pack_ws_bytes, m.plain_ws_bytes)); s->offsets.Alloc(kWho, B + 1);
+      s->packed.Alloc(kWho, m.packed_bytes); s->pack_ws.Alloc(kWho, m.pack_ws_bytes); s->offsets.Alloc(kWho, B + 1);
       s->pin_packed.Alloc(kWho, c.entropy ? m.coded_bytes : m.packed_bytes); s->pin_offsets.Alloc(kWho, B + 1);
       if (c.entropy) {
         s->coded.Alloc(kWho, m.coded_bytes); s->entropy_ws.Alloc(kWho, m.entropy_ws_bytes); s->coded_offsets.Alloc(kWho, B + 1);
@@ -198,11 +192,7 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
       if (c.enh_window) { s->window.Alloc(kWho, B * 4); s->pin_window.Alloc(kWho, B * 4); }
     }
     if (c.delta) { s->key.Alloc(kWho, B); s->pin_key.Alloc(kWho, B); }
-    if (m.temporal) {
-      s->plain.Alloc(kWho, m.packed_bytes); s->plain_offsets.Alloc(kWho, B + 1); s->pin_plain_offsets.Alloc(kWho, B + 1);
-      s->delta_status.Alloc(kWho, B); s->pin_delta_status.Alloc(kWho, B);
-      s->plain_offsets_done = Event(kWho);
-    }
+    if (m.temporal) s->before_bgr.Alloc(kWho, m.frame_bytes);
     if (c.auto_key) {
       s->forced.Alloc(kWho, B); s->pin_forced.Alloc(kWho, B);
       s->level_counts.Alloc(kWho, 2 * B); s->pin_level_counts.Alloc(kWho, 2 * B);
@@ -261,11 +251,6 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
           throw std::runtime_error("svc::StreamEncoder: svc_hip_entropy_encode_frames flagged frame " + std::to_string(s.first + i) +
                                    " with status " + std::to_string(code));
       }
-    if (m.temporal)  // the input is the pack's own output, as above
-      for (uint32_t i = 0; i < s.encoded; ++i)
-        if (s.pin_delta_status.p[i])
-          throw std::runtime_error("svc::StreamEncoder: svc_hip_delta_levels_temporal_frames flagged frame " + std::to_string(s.first + i) +
-                                   " with status " + std::to_string(s.pin_delta_status.p[i]));
     if (m.budgeted)
       for (uint32_t i = 0; i < s.encoded; ++i) st.over_budget_frames += s.pin_choice.p[i] >> 31;
     st.encoded_frames += s.encoded;
@@ -323,6 +308,9 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       if (carry)  // the previous batch's last frame is this one's first: behind that batch's H2D, which this stream carried too
         Hip(hipMemcpyAsync(s.bgr.p, prev->bgr.p + (size_t)(prev->frames - 1) * m.frame_bytes, m.frame_bytes,
                            hipMemcpyDeviceToDevice, si), "hipMemcpyAsync D2D");
+      if (carry && m.temporal)  // and the frame the batch's first encoded frame refers to, `temporal_period` frames before it, the same way
+        Hip(hipMemcpyAsync(s.before_bgr.p, prev->bgr.p + (size_t)(prev->frames - c.temporal_period) * m.frame_bytes, m.frame_bytes,
+                           hipMemcpyDeviceToDevice, si), "hipMemcpyAsync D2D (temporal reference)");
       FillRansacDraws(s.pin_samples.p, g0, encoded, m.iters, c.ransac.subset_sz, m.blocks, c.seed);
       Hip(hipMemcpyAsync(s.samples.p, s.pin_samples.p, (size_t)encoded * m.iters * c.ransac.subset_sz * sizeof(uint32_t),
                          hipMemcpyHostToDevice, si), "hipMemcpyAsync samples");
@@ -383,30 +371,16 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         // read below lies between them.  The first batch of an Encode() has no frame before: its first frame is a key frame.
         const uint32_t* prev_types = carry ? prev->types.p + (size_t)(prev->encoded - 1) * m.blocks : nullptr;
         if (m.temporal) {
-          // Two calls: the plain stream into a buffer of the slot, then the temporal delta call on it.  The stream index of the encoded
-          // frame with clip index f is f - 1, and every batch but the last holds a multiple of the period, so frame i of the batch has an
-          // index that is i modulo the period.  The frame at index -period is plain frame B - period of the batch before: it lies in that
-          // slot's buffer, which is next written depth - 1 >= 2 batches on, on this stream.  Where it lies and how long it is are on the
-          // device until that batch's offsets have come back, on this stream too: the host waits for them (for that batch's pack, not
-          // for this batch's motion kernels), as svc::StreamDecoder waits for the length of its chain's frame.
-          const uint8_t* before = nullptr;
-          uint64_t before_bytes = 0;
-          if (carry) {
-            Hip(hipEventSynchronize(prev->plain_offsets_done), "hipEventSynchronize");
-            const uint64_t* po = prev->pin_plain_offsets.p + (B - c.temporal_period);
-            before = prev->plain.p + po[0];
-            before_bytes = po[1] - po[0];
-          }
-          Abi(svc_hip_dct_pack_levels_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.fg_step, c.bg_step,
-                                             s.pack_ws.p, m.plain_ws_bytes, s.plain.p, m.packed_bytes, s.plain_offsets.p, sk),
-              "svc_hip_dct_pack_levels_frames");
-          Hip(hipMemcpyAsync(s.pin_plain_offsets.p, s.plain_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, sk),
-              "D2H plain offsets");
-          Hip(hipEventRecord(s.plain_offsets_done, sk), "hipEventRecord");
-          Abi(svc_hip_delta_levels_temporal_frames(s.plain.p, m.packed_bytes, s.plain_offsets.p, encoded, before, before_bytes, s.key.p, m.pw,
-                                                   m.ph, m.tw, m.th, m.bw, m.bh, s.pack_ws.p, m.pack_ws_bytes, s.packed.p, m.packed_bytes,
-                                                   s.offsets.p, s.delta_status.p, sk, c.temporal_period),
-              "svc_hip_delta_levels_temporal_frames");
+          // The stream index of the encoded frame with clip index f is f - 1, and every batch but the last holds a multiple of the period,
+          // so frame i of the batch has an index that is i modulo the period.  The frame at index -period is encoded frame B - period of
+          // the batch before: its pixels were copied into this slot behind that batch's H2D (above), its types are that slot's row
+          // B - period, read between the two writes named above.  Nothing comes back to the host for it: the stream does not depend on
+          // how the clip falls into batches, nor on the depth.
+          const uint32_t* before_types = carry ? prev->types.p + (size_t)(prev->encoded - c.temporal_period) * m.blocks : nullptr;
+          Abi(svc_hip_dct_pack_delta_temporal_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.fg_step,
+                                                     c.bg_step, carry ? s.before_bgr.p : nullptr, before_types, s.key.p, s.pack_ws.p,
+                                                     m.pack_ws_bytes, s.packed.p, m.packed_bytes, s.offsets.p, sk, c.temporal_period),
+              "svc_hip_dct_pack_delta_temporal_frames");
         } else if (c.auto_key)
           Abi(svc_hip_dct_pack_delta_auto_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.fg_step, c.bg_step,
                                                  carry ? s.bgr.p : nullptr, prev_types, s.forced.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
@@ -469,11 +443,6 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         }
         Hip(hipMemcpyAsync(s.pin_enh_offsets.p, c.entropy ? s.enh_coded_offsets.p : s.enh_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, so), "D2H enhancement offsets");
-      }
-      if (m.temporal) {
-        bytes += (uint64_t)encoded * sizeof(uint32_t);
-        Hip(hipMemcpyAsync(s.pin_delta_status.p, s.delta_status.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, so),
-            "D2H delta status");
       }
       if (c.auto_key) {  // the chosen flags and the counts they were chosen by
         bytes += (uint64_t)encoded * 3 * sizeof(uint32_t);

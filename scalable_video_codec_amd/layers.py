@@ -491,17 +491,21 @@ def _level_count(frame: bytes) -> int:
     return int(np.frombuffer(frame, "<u4", 16)[10])
 
 
-def delta_level_counts(stream, offsets, prev=None) -> np.ndarray:
+def delta_level_counts(stream, offsets, prev=None, period: int = 1) -> np.ndarray:
     """-> (n, 2) u32: per frame, column 0 the level count of the frame written as a key frame, delta_frame(frame), and column 1 that of
     delta_frame(frame, predecessor) -- header word 10 of the written frame, so a set mask bit over level 0 counts in neither.  The
     predecessor of frame i is input frame i - 1, for frame 0 the frame `prev`; a frame without one (frame 0, prev None) has column 1
     equal to column 0.  No key flag enters the counts: the levels of the frame before are its own, however it is coded, so a row is a
     function of its frame and that frame's predecessor alone, and a stream cut in two at any frame, the second call with prev = the
-    first's last input frame, gives the rows of one call."""
+    first's last input frame, gives the rows of one call.  period 2 or 4 (svc_hip_dct_pack_delta_temporal_auto_frames): the predecessor
+    of frame i is input frame temporal_ref(i, period), `prev` the input frame at index -period; a cut then falls on a multiple of period,
+    and every 2^s-th row (2^s <= period) is the row of the thinned clip at period >> s."""
+    if period not in PERIODS:
+        raise ValueError(f"period {period} (supported: 1, 2, 4)")
     frames = _source_frames(stream, offsets, None)
     counts = np.zeros((len(frames), 2), np.uint32)
     for i, fr in enumerate(frames):
-        before = frames[i - 1] if i else prev
+        before = frames[temporal_ref(i, period)] if i else prev
         counts[i, 0] = _level_count(delta_frame(fr))
         counts[i, 1] = counts[i, 0] if before is None else _level_count(delta_frame(fr, before))
     return counts
@@ -519,17 +523,20 @@ def auto_keys(counts, forced=None, has_prev: bool = True) -> np.ndarray:
     return key
 
 
-def delta_auto_frames(stream, offsets, forced=None, prev=None) -> Tuple[bytes, np.ndarray, np.ndarray, np.ndarray]:
+def delta_auto_frames(stream, offsets, forced=None, prev=None, period: int = 1) -> Tuple[bytes, np.ndarray, np.ndarray, np.ndarray]:
     """What svc_hip_dct_pack_delta_auto_frames writes, given the stream svc_hip_dct_pack_levels_frames writes from the same frames ->
     (bytes, offsets (n + 1,) u64, keys (n,) bool, counts (n, 2) u32): delta_frames with the keys auto_keys chose from
     delta_level_counts.  With forced None every output frame holds min(counts[f]) levels, so frame by frame it is never larger than
     the plain stream's frame nor than the frame delta_frames writes without key flags; a forced frame is the plain stream's.  The
     choice for a frame does not depend on the choice for any other, so a stream cut into two calls at any frame, the second with
     prev = the first's last input frame and its share of `forced`, gives the bytes, keys and counts of one call.
-    undelta_frames(bytes, offsets, keys, prev's reconstruction) gives the stream back."""
-    counts = delta_level_counts(stream, offsets, prev)
+    undelta_frames(bytes, offsets, keys, prev's reconstruction) gives the stream back.  period 2 or 4: what
+    svc_hip_dct_pack_delta_temporal_auto_frames writes -- delta_temporal_frames with the keys auto_keys chose from
+    delta_level_counts(.., period), `prev` the input frame at index -period; thin_frames of it at 2^s <= period, with the thinned keys
+    and counts, is this function on the thinned clip at period >> s."""
+    counts = delta_level_counts(stream, offsets, prev, period)
     keys = auto_keys(counts, forced, prev is not None)
-    out, offs = delta_frames(stream, offsets, keys, prev)
+    out, offs = delta_temporal_frames(stream, offsets, period, keys, prev)
     return out, offs, keys, counts
 
 

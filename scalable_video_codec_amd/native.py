@@ -216,6 +216,19 @@ SIGNATURES = {
     "svc_hip_levels_records_frames": (C.c_int, [_vp, _u64, _vp] + [_u32] * 8 + [_vp, _u64, _vp, _u64, _vp, _vp]),
 }
 
+# The calls of include/svc_hip_temporal.h: a table of its own because SIGNATURES is tied one to one to the declarations of include/svc_hip.h
+# (tests/test_abi.py); load() applies both.
+SIGNATURES_TEMPORAL = {
+    # the temporal-layer delta stream straight from the transform (csrc/dct_pack.hip; host statement: layers.delta_temporal_frames of the
+    # fused pack's frames), and the same with the key frames chosen by size (layers.delta_auto_frames with period)
+    "svc_hip_dct_pack_delta_temporal_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_dct_pack_delta_temporal_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 + [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp,
+                                                        _vp, _u32]),
+    "svc_hip_dct_pack_delta_temporal_auto_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_dct_pack_delta_temporal_auto_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 4 + [_vp, _vp, _vp, _vp, _u64, _vp, _u64,
+                                                             _vp, _vp, _vp, _vp, _u32]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -228,7 +241,7 @@ def load() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m scalable_video_codec_amd.build` "
                 "(or __graft_entry__.build()); the MI355X path has no CPU fallback")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TEMPORAL.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -905,6 +918,85 @@ def dct_pack_delta_auto_frames(bgr: torch.Tensor, block: int, block_types: torch
                                                      _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
                                                      _dev(offsets, torch.int64), _dev(keys, torch.int32), _dev(counts, torch.int32),
                                                      _stream()))
+    return out, offsets, keys, counts
+
+
+def dct_pack_delta_temporal_workspace_bytes(n: int, w: int, h: int, block: int, mv_block, period: int) -> int:
+    """Scratch of dct_pack_delta_temporal_frames; 0 for a geometry or a period it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_delta_temporal_workspace_bytes(n, w, h, block, mbw, mbh, period))
+
+
+def dct_pack_delta_temporal_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, fg_step: int, bg_step: int, period: int,
+                                   prev_bgr: Optional[torch.Tensor] = None, prev_types: Optional[torch.Tensor] = None, key=None,
+                                   out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                                   workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dct_pack_delta_frames with temporal layers (include/svc_hip_temporal.h): byte for byte delta_levels_temporal_frames of
+    dct_pack_levels_frames' stream, without that stream; the numpy statement is layers.delta_temporal_frames applied to the frames of
+    dct_pack_levels_frames.  Frame i is coded against input frame i - min(lowbit(i), period), period 1, 2 or 4; prev_bgr / prev_types:
+    the input frame at index -period (both or neither; neither: frame 0 is a key frame).  Everything else as dct_pack_delta_frames."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    dev = bgr.device
+    k = None if key is None else torch.as_tensor(key, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    assert k is None or k.numel() == n, "one key flag per frame"
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_delta_temporal_workspace_bytes(n, w, h, block, mv_block, period), 16), dtype=torch.uint8,
+                                device=dev)
+    _check(load().svc_hip_dct_pack_delta_temporal_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                         _dev(block_types, torch.int32), mbw, mbh, fg_step, bg_step,
+                                                         None if prev_bgr is None else _dev(prev_bgr, torch.uint8),
+                                                         None if prev_types is None else _dev(prev_types, torch.int32),
+                                                         None if k is None else _dev(k, torch.int32),
+                                                         _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8), out.numel(),
+                                                         _dev(offsets, torch.int64), _stream(), period))
+    return out, offsets
+
+
+def dct_pack_delta_temporal_auto_workspace_bytes(n: int, w: int, h: int, block: int, mv_block, period: int) -> int:
+    """Scratch of dct_pack_delta_temporal_auto_frames; 0 for a geometry or a period it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_delta_temporal_auto_workspace_bytes(n, w, h, block, mbw, mbh, period))
+
+
+def dct_pack_delta_temporal_auto_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, fg_step: int, bg_step: int,
+                                        period: int, prev_bgr: Optional[torch.Tensor] = None, prev_types: Optional[torch.Tensor] = None,
+                                        forced=None, out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+                                        keys: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                                        workspace: Optional[torch.Tensor] = None
+                                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """dct_pack_delta_auto_frames with temporal layers (include/svc_hip_temporal.h): a frame is a key frame iff it has no reference,
+    forced[f] != 0, or its difference to input frame f - min(lowbit(f), period) holds at least as many levels as the frame itself ->
+    (stream, offsets, keys, counts) as dct_pack_delta_auto_frames.  Stream and offsets are dct_pack_delta_temporal_frames' with
+    key = keys; keys and counts are layers.auto_keys and layers.delta_level_counts(.., period=period) of dct_pack_levels_frames' stream."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    dev = bgr.device
+    k = None if forced is None else torch.as_tensor(forced, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+    assert k is None or k.numel() == n, "one forced flag per frame"
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if keys is None:
+        keys = torch.empty(n, dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_delta_temporal_auto_workspace_bytes(n, w, h, block, mv_block, period), 16), dtype=torch.uint8,
+                                device=dev)
+    _check(load().svc_hip_dct_pack_delta_temporal_auto_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                              _dev(block_types, torch.int32), mbw, mbh, fg_step, bg_step,
+                                                              None if prev_bgr is None else _dev(prev_bgr, torch.uint8),
+                                                              None if prev_types is None else _dev(prev_types, torch.int32),
+                                                              None if k is None else _dev(k, torch.int32),
+                                                              _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8),
+                                                              out.numel(), _dev(offsets, torch.int64), _dev(keys, torch.int32),
+                                                              _dev(counts, torch.int32), _stream(), period))
     return out, offsets, keys, counts
 
 

@@ -99,6 +99,13 @@
                                                    svc_hip_dct_frames wrote, against two svc_hip_pack_levels_frames calls on the same planes
                                                    (at (fg, bg), then at (e, e)) in the same process; wall time per call over 20 back-to-back
                                                    calls, the two routes interleaved, and the bytes each moves; the base is compared
+  python tools/dct_pack_probe.py delta-temporal-encode
+                                                   the temporal-layer delta stream from pixels: svc_hip_dct_pack_delta_temporal_frames at
+                                                   periods 2 and 4, at C3 and C5, steps (1, 640) and (1, 1), against the two calls it replaces
+                                                   (bytes compared), svc_hip_dct_pack_delta_frames (period 1) and
+                                                   svc_hip_dct_pack_levels_frames alone, and svc_hip_dct_pack_delta_temporal_auto_frames
+                                                   against it; one process, the routes in turn, the median of three rounds.  Then
+                                                   delta-temporal's host-driver runs (tests/dropin/stream_temporal_main, periods 4 and 1)
   python tools/dct_pack_probe.py stream-layers    the two layers through the host drivers: a 65-frame C3 synthetic clip made on the CPU,
                                                    batches of 16, (1, 640, 1), a 256 x 256 window and a gaze centre per frame;
                                                    tests/dropin/stream_layers_main (plain, entropy-coded, and with every tile enhanced) beside
@@ -822,6 +829,104 @@ def delta_temporal() -> None:
     delta_temporal_stream()
 
 
+def _temporal_variant_lib(redo):
+    """csrc/dct_pack.hip built with the other form of period 4 (SVC_DCT_PACK_TEMPORAL_REDO), as _delta_run_lib builds its runs."""
+    import ctypes
+    import subprocess
+    from scalable_video_codec_amd import build
+    out = os.path.join(ROOT, "tools", "_bin", f"libsvc_dct_pack_temporal_redo{redo}.so")
+    if not os.path.exists(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call([build._hipcc(), *build.HIPCC_FLAGS, f"-DSVC_DCT_PACK_TEMPORAL_REDO={redo}", "-shared", "-o", out,
+                               os.path.join(build.CSRC, "dct_pack.hip"), f"-L{build.PKG}", "-lsvc_hip", f"-Wl,-rpath,{build.PKG}"])
+    fn = ctypes.CDLL(out).svc_hip_dct_pack_delta_temporal_frames
+    fn.restype, fn.argtypes = native.SIGNATURES_TEMPORAL["svc_hip_dct_pack_delta_temporal_frames"]
+    return fn
+
+
+def delta_temporal_encode_kernels(cfg) -> None:
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out, plain, ref = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(3))
+    offs, plain_offs, ref_offs = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(3))
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    keys, counts = torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev)
+    ws = torch.empty(native.dct_pack_delta_temporal_auto_workspace_bytes(n, pw, ph, block, mv, 4), dtype=torch.uint8, device=dev)
+    ws_d = torch.empty(native.delta_levels_temporal_workspace_bytes(n, pw, ph, block, mv, 4), dtype=torch.uint8, device=dev)
+    key = torch.zeros(n, dtype=torch.int32, device=dev)
+    key[0] = 1
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}, frame 0 the key frame; ms per call (20 back-to-back calls, the routes in turn, the "
+          f"median of three rounds)", flush=True)
+    for fg, bg in ((1, 640), (1, 1)):
+        def pack():
+            native.dct_pack_levels_frames(bgr, block, types, mv, fg, bg, out=plain, offsets=plain_offs, workspace=ws)
+
+        def two_calls(period):
+            def call():
+                pack()
+                native.delta_levels_temporal_frames(plain, plain_offs, pw, ph, block, mv, period, key=key, out=ref, out_offsets=ref_offs,
+                                                    workspace=ws_d, status=st)
+            return call
+
+        def fused(period):
+            def call():
+                native.dct_pack_delta_temporal_frames(bgr, block, types, mv, fg, bg, period, key=key, out=out, offsets=offs, workspace=ws)
+            return call
+
+        def auto(period):
+            def call():
+                native.dct_pack_delta_temporal_auto_frames(bgr, block, types, mv, fg, bg, period, forced=key, out=out, offsets=offs, keys=keys,
+                                                           counts=counts, workspace=ws)
+            return call
+
+        def period1():
+            native.dct_pack_delta_frames(bgr, block, types, mv, fg, bg, key=key, out=out, offsets=offs, workspace=ws)
+
+        def variant(redo):  # period 4 in the form built with SVC_DCT_PACK_TEMPORAL_REDO = redo
+            fn = _temporal_variant_lib(redo)
+            mbw, mbh = native._bwbh(mv)
+
+            def call():
+                native._check(fn(bgr.data_ptr(), ph * pw * 3, n, pw, ph, block, types.data_ptr(), mbw, mbh, fg, bg, None, None, key.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(), offs.data_ptr(), native._stream(), 4))
+            return call
+
+        two_calls(4)()
+        for redo in (0, 1):
+            variant(redo)()
+            sync()
+            assert torch.equal(offs, ref_offs) and torch.equal(out[:int(offs[-1])], ref[:int(offs[-1])])
+        tv = _median3([variant(0), variant(1)], sync)
+        print(f"  ({fg}, {bg}): period 4, both sets kept (9 transforms for 8 frames) {tv[0]:.3f}; one set kept, frame 4k transformed again in "
+              f"front of frame 4k + 4 (10) {tv[1]:.3f}", flush=True)
+        for period in (2, 4):  # the bytes first: the fused call against the two it replaces
+            two_calls(period)()
+            fused(period)()
+            sync()
+            assert not st.any() and torch.equal(offs, ref_offs) and torch.equal(out[:int(offs[-1])], ref[:int(offs[-1])])
+        t = _median3([fused(2), fused(4), two_calls(2), two_calls(4), period1, pack, auto(2), auto(4)], sync)
+        worst = max(t[0] / t[2], t[1] / t[3])
+        print(f"  ({fg}, {bg}): svc_hip_dct_pack_delta_temporal_frames at period 2 {t[0]:.3f}, at period 4 {t[1]:.3f}; "
+              f"svc_hip_dct_pack_levels_frames + svc_hip_delta_levels_temporal_frames {t[2]:.3f} ({t[2] / t[0]:.2f}x), {t[3]:.3f} "
+              f"({t[3] / t[1]:.2f}x); svc_hip_dct_pack_delta_frames (period 1) {t[4]:.3f} (the fused call {t[0] / t[4]:.2f}x, {t[1] / t[4]:.2f}x "
+              f"of it); svc_hip_dct_pack_levels_frames alone {t[5]:.3f}; svc_hip_dct_pack_delta_temporal_auto_frames {t[6]:.3f} "
+              f"({t[6] / t[0]:.2f}x of the fixed-flag call), {t[7]:.3f} ({t[7] / t[1]:.2f}x); bytes == the two calls'; the fused call is "
+              f"{'faster' if worst < 1 else 'NOT faster'} than the two calls at both periods", flush=True)
+
+
+def delta_temporal_encode() -> None:
+    delta_temporal_encode_kernels(configs.C3)
+    torch.cuda.empty_cache()
+    delta_temporal_encode_kernels(configs.C5)
+    torch.cuda.empty_cache()
+    delta_temporal_stream()
+
+
 def delta_auto_stream(frames_n=33) -> None:
     import subprocess
     import tempfile
@@ -1532,6 +1637,8 @@ if __name__ == "__main__":
         delta_auto()
     elif mode == "delta-temporal":
         delta_temporal()
+    elif mode == "delta-temporal-encode":
+        delta_temporal_encode()
     elif mode == "stream-layers":
         stream_layers()
     elif mode == "transcode":
