@@ -129,6 +129,19 @@ class StreamDecoder {
   void DecodeDeltaTemporal(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t period,
                            const Gaze& gaze, const Sink& sink);
 
+  // DecodeDeltaTemporal at 1 / reduce of the size: a temporal-layer delta stream, or its band (0, 0, K, K) (K = tile side / reduce), played
+  // small.  The device call is svc_hip_decode_delta_levels_temporal_reduced_frames (include/svc_hip_temporal_decode.h), which carries the first
+  // K x K levels of every tile in one set of registers per temporal layer; the two chain buffers hold the band of frame
+  // period * ((n - 1) / period) of a batch, the next batch's d_prev.  It is the only route whose chain runs on band-sized frames, so the
+  // driver takes it whatever it measures against the undelta and the reduced decode as two calls (README,
+  // profiles/decode_delta_temporal_reduced_c3.txt).  Thrown as std::runtime_error before any device work: a period other than 1, 2 or 4;
+  // a reduce other than 2, 4 or 8; config.reduce neither 1 nor `reduce`; config.batch not a multiple of period.  period 1 forwards to
+  // DecodeDeltaReduced.  The stream thinned to every 2^s-th frame plays with period >> s.  Everything else -- SVCQ or SVCE by magic,
+  // key flags, gaze in display coordinates, display size, schedule, statuses, statistics -- is DecodeDeltaReduced's and
+  // DecodeDeltaTemporal's.
+  void DecodeDeltaTemporalReduced(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t period,
+                                  uint32_t reduce, const Gaze& gaze, const Sink& sink);
+
   // stream: a whole wire stream of `bytes` bytes in host memory, the 32-byte Header (libs/codec.hpp:8-17) first, then frame_count
   // frames of records.  svc_hip_wire_layout decides how it is read (the decoder's padded tile grid, or the reference encoder's
   // unpadded loops); a stream it refuses throws std::runtime_error with its message.  Batches of config.wire_batch frames, the

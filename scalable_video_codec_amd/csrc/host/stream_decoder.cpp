@@ -2,6 +2,8 @@
 // the other way.  No arithmetic of the hot path lives here; the gaze rule and the decode are calls into the C ABI.
 #include "svc/stream_decoder.hpp"
 
+#include "svc_hip_temporal_decode.h"
+
 #include "../stream_format.hpp"
 #include "batch_pipe.hpp"
 #include "copy_crew.hpp"
@@ -373,7 +375,22 @@ void StreamDecoder::DecodeDeltaReduced(const uint8_t* stream, const uint64_t* of
   p_->Delta(stream, offsets, n_frames, key, reduce, 1, gaze, sink);
 }
 
-// DecodeDelta (reduce 1), DecodeDeltaTemporal (reduce 1, a period above 1) and DecodeDeltaReduced: one chain through the batches, carried
+void StreamDecoder::DecodeDeltaTemporalReduced(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key,
+                                               uint32_t period, uint32_t reduce, const Gaze& gaze, const Sink& sink) {
+  if (period != 1 && period != 2 && period != 4)
+    throw std::runtime_error("svc::StreamDecoder: DecodeDeltaTemporalReduced takes a period of 1, 2 or 4");
+  if (reduce != 2 && reduce != 4 && reduce != 8)
+    throw std::runtime_error("svc::StreamDecoder: DecodeDeltaTemporalReduced takes a reduce of 2, 4 or 8");
+  if (p_->c.reduce != 1 && p_->c.reduce != reduce)
+    throw std::runtime_error("svc::StreamDecoder: DecodeDeltaTemporalReduced's reduce is not the configured one (config.reduce must be 1 or the argument)");
+  if (p_->c.batch % period != 0)
+    throw std::runtime_error("svc::StreamDecoder: DecodeDeltaTemporalReduced carries the frame at index -period from batch to batch: config.batch must be a multiple of the period");
+  if (period == 1) return DecodeDeltaReduced(stream, offsets, n_frames, key, reduce, gaze, sink);
+  p_->Delta(stream, offsets, n_frames, key, reduce, period, gaze, sink);
+}
+
+// DecodeDelta (reduce 1), DecodeDeltaTemporal (reduce 1, a period above 1), DecodeDeltaReduced and DecodeDeltaTemporalReduced (a reduce
+// and a period above 1): one chain through the batches, carried
 // in the two chain buffers -- whole reconstructed frames at reduce 1, their bands (0, 0, K, K) above; with a period the carried frame is
 // the batch's last of layer 0
 void StreamDecoder::Impl::Delta(const uint8_t* stream, const uint64_t* offsets, uint32_t n_frames, const uint32_t* key, uint32_t reduce,
@@ -425,7 +442,13 @@ void StreamDecoder::Impl::Delta(const uint8_t* stream, const uint64_t* offsets, 
             prev = m.chain[(batch - 1) % 2].p;
             prev_bytes = m.pin_chain_len.p[0];
           }
-          if (reduce > 1)
+          if (reduce > 1 && period > 1)
+            Abi(svc_hip_decode_delta_levels_temporal_reduced_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh,
+                                                                    m.mbw, m.mbh, c.fg_step, c.bg_step, reduce, s.gaze.p, m.ws.p, m.ws_bytes,
+                                                                    m.rec.p, s.disp.p, m.dw, m.dh, m.chain[batch % 2].p, m.chain_bytes,
+                                                                    m.chain_len.p, s.status.p, sk, period),
+                "svc_hip_decode_delta_levels_temporal_reduced_frames");
+          else if (reduce > 1)
             Abi(svc_hip_decode_delta_levels_reduced_frames(qin, qbytes, qoff, cnt, prev, prev_bytes, s.key.p, m.pw, m.ph, m.bw, m.bh, m.mbw,
                                                            m.mbh, c.fg_step, c.bg_step, reduce, s.gaze.p, m.ws.p, m.ws_bytes, m.rec.p,
                                                            s.disp.p, m.dw, m.dh, m.chain[batch % 2].p, m.chain_bytes, m.chain_len.p,

@@ -58,6 +58,9 @@
 // decode of a delta stream at reduced size (svc_hip_decode_delta_levels_reduced_frames): the same passes around a kernel of the reduced
 // decode's shape that carries only the first K x K levels of every tile through the frames, in registers (stated at its kernel).
 //
+// decode of a temporal-layer delta stream at reduced size (svc_hip_decode_delta_levels_temporal_reduced_frames, include/svc_hip_temporal_decode.h):
+// that kernel with one set of held levels per temporal layer below the odd frames, all in registers (stated at its kernel).
+//
 // pack of two layers (svc_hip_pack_layers_frames): the pack's count, scan and scatter on raw planes with two quantisations per coefficient,
 // the frame offsets from frame_offsets_kernel with a job per layer (stated at its kernels).
 //
@@ -67,6 +70,7 @@
 #include "display_core.hpp"
 #include "idct_core.hpp"
 #include "stream_format.hpp"
+#include "svc_hip_temporal_decode.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2757,6 +2761,190 @@ void launch_decode_delta_reduced(uint32_t block, uint32_t reduce, dim3 grid, hip
   }
 }
 
+// ---- decode of a delta stream with temporal layers at reduced size (svc_hip_decode_delta_levels_temporal_reduced_frames;
+// include/svc_hip_temporal_decode.h states it) --------------------------------------------------------------------------------------------------
+//
+// decode_delta_reduced_kernel's workgroup, passes and two barriers per frame, with the temporal undelta's states where that kernel has
+// one set of held levels: the thread holds T sets of 3 K levels in registers, set 0 the latest frame of layer 0 and, at period 4 (T = 2),
+// set 1 frame 4k + 2.  A frame is rebuilt from the set of its reference (temporal_src_state) and kept in the set of its own layer
+// (temporal_dst_state); an odd frame, which no frame refers to, is rebuilt into the temporaries of the row pass alone.  The two sets are
+// two named arrays and every index into them is a constant: which one a frame reads and which it writes are conditions on the frame
+// number, the same for the whole wave, so each held level costs one v_cndmask to read and one to keep and nothing goes to scratch.  No LDS
+// is added to decode_delta_reduced_kernel's.  The tile-predicted predicate reads the reference's header and types as the full-size
+// temporal kernel does, and levels outside K x K are never read, so the frames and d_prev may be their band (0, 0, K, K).
+//
+// d_last is the band (0, 0, K, K) of frame `last_frame` = period * ((n - 1) / period), the frame the next call's frame 0 refers to: set 0
+// after the last frame, through decode_delta_reduced_kernel's row_bits -> mask words -> ranked store path and the scan and write kernels,
+// which are handed that frame as the call's last.
+// (args.rec: [n][h K / N][w K / N][3])
+template <int N, int K, int T>
+__global__ __launch_bounds__(reduced_threads(N, K)) void decode_delta_temporal_reduced_kernel(DecodeDeltaArgs args, uint32_t last_frame) {
+  constexpr uint32_t kTiles = kGroupCoeffs / (N * N), kWords = N * N / 64, kJobs = kTiles * kWords;  // tiles and mask words of a group
+  constexpr uint32_t kRowsPerWord = 64 / N;  // coefficient rows of a tile in one mask word
+  constexpr uint32_t kPeriod = 1u << T;
+  static_assert(T == 1 || T == 2, "period 2 or 4");
+  static_assert(kJobs <= 64, "one wave scans a group's mask words");
+  __shared__ uint64_t job_mask[3][kJobs];
+  __shared__ uint32_t job_base[3][kJobs];
+  __shared__ uint32_t row_bits[3][kTiles * K];  // frame last_frame's non-zero levels of a thread's row, bit i = coefficient i
+  __shared__ double rows[3][kTiles * K * (K + 1)];
+  const DeltaArgs& a = args.d;
+  const Geom& g = a.in.g;
+  const uint32_t gi0 = blockIdx.x, tid = threadIdx.x;
+  const Group gr = group_of(g, gi0);  // plane 0's group; planes 1 and 2 hold the same tiles
+  const uint32_t jobs = gr.nt * kWords, per_plane = g.tiles_y * g.gx;
+  const uint32_t t = tid / K, j = tid - t * K;
+  const bool active = t < gr.nt;  // (nt <= kTiles) an idle thread stays in every barrier below
+  const uint32_t rw = g.w / N * K, rh = g.h / N * K;  // the reduced picture; adjacent lanes hold adjacent pixels
+  // The thread's levels of layer 0's latest frame, as u16, and (T = 2) of frame 4k + 2.  At K = 8 the second set is packed two levels to
+  // a dword: unpacked, the 16 x 16, K = 8, T = 2 instantiation needs 169 VGPRs, one more than three waves per SIMD admit.
+  constexpr bool kPacked = K == 8;
+  constexpr int kHeld1 = kPacked ? K / 2 : K;
+  uint32_t held0[3][K], held1[3][kHeld1];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int q = 0; q < K; ++q) held0[c][q] = 0;
+#pragma unroll
+    for (int q = 0; q < kHeld1; ++q) held1[c][q] = 0;
+  }
+  // frame -1 is d_prev, the frame at index -period: it goes into set 0 like a key frame and nothing is decoded for it.  Every condition
+  // on a frame is the workgroup's.
+  for (int32_t i = a.prev.in && a.prev.ws.status[0] == kStOk ? -1 : 0; i < (int32_t)a.n; ++i) {
+    const bool seed = i < 0;
+    float* dst = seed ? nullptr : args.rec + (((size_t)i * rh + gr.ty * K) * rw + (gr.t0 + t) * K + j) * 3;
+    if (!seed && a.status[i] != kStOk) {  // zeros; the frame is not read, and no frame that passes hangs on it
+      if (active) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) {
+          float* p = dst + (size_t)y * rw * 3;
+          p[0] = 0.f; p[1] = 0.f; p[2] = 0.f;
+        }
+      }
+      continue;
+    }
+    const uint8_t* fc = seed ? a.prev.in : a.in.in + a.in.offsets[i];
+    const uint8_t* fp = seed || delta_key(a, (uint32_t)i) ? nullptr : delta_before(a, (uint32_t)i, kPeriod);
+    const uint32_t from = seed ? 0u : temporal_src_state((uint32_t)i, kPeriod);
+    const uint32_t into = seed ? 0u : temporal_dst_state((uint32_t)i, kPeriod, (uint32_t)T);  // T: an odd frame, kept nowhere
+    const bool from1 = T == 2 && from == 1u, into0 = into == 0u, into1 = T == 2 && into == 1u;  // (the whole wave)
+    const uint32_t* first_level = seed ? a.prev.ws.before : a.in.ws.before + (size_t)i * g.groups;
+    if (tid < 64) {  // wave 0: mask 0 past the group's words, no level is read through it
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint64_t m = tid < jobs ? load_mask(group_masks(g, fc, c, gr) + 2 * tid) : 0ull;
+        const uint32_t ex = wave_exclusive_scan((uint32_t)__popcll(m));
+        if (tid < kJobs) { job_mask[c][tid] = m; job_base[c][tid] = ex; }
+      }
+    }
+    bool predicted = false;  // the thread's own tile
+    float enc = 0.f, dec = 1.f;
+    if (active) {
+      const uint32_t* hdr = reinterpret_cast<const uint32_t*>(fc);
+      const uint32_t type = tile_type(g, hdr + kHeaderWords, gr, t);
+      const uint32_t enc_step = type == 0 ? hdr[kHBgStep] : hdr[kHFgStep];
+      predicted = fp && enc_step == tile_step(g, fp, gr, t);
+      if (!seed) {
+        const bool in_gaze = gazed(args.gaze, (uint32_t)i, gr.x0 + t * N, gr.y0);  // the full-size tile origin: one rule for both decoders
+        enc = (float)enc_step;
+        dec = in_gaze ? 1.f : (type == 0 ? args.bg : args.fg);
+      }
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint16_t* levels = reinterpret_cast<const uint16_t*>(fc + g.levels_off) + first_level[c * per_plane + gi0];
+        float v[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+          const uint32_t k = j * N + q, w = t * kWords + (k >> 6), b = k & 63u;
+          const uint64_t mask = job_mask[c][w], below = (1ull << b) - 1;
+          const uint32_t set1 = kPacked ? (held1[c][q / 2] >> (16 * (q & 1))) & 0xFFFFu : held1[c][q % kHeld1];
+          uint32_t lv = predicted ? (from1 ? set1 : held0[c][q]) : 0u;
+          if ((mask >> b) & 1u) lv += levels[job_base[c][w] + (uint32_t)__popcll(mask & below)];
+          lv &= 0xFFFFu;
+          if (into0) held0[c][q] = lv;
+          if (into1) {
+            if (kPacked) held1[c][q / 2] = q & 1 ? (held1[c][q / 2] & 0xFFFFu) | (lv << 16) : (held1[c][q / 2] & 0xFFFF0000u) | lv;
+            else held1[c][q % kHeld1] = lv;
+          }
+          v[q] = (float)(int16_t)lv * enc;
+        }
+        if (!seed) invert_row_reduced<K>(v, dec, rows[c], t, j);
+      }
+    }
+    __syncthreads();  // (the next frame's words are written behind it; its row passes behind that frame's own first barrier)
+    if (seed || !active) continue;
+    float out[3][K];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) invert_column_reduced<N, K>(rows[c], t, j, out[c]);
+    store_bgr_column<K>(dst, rw, out);
+  }
+  if (!args.last || a.status[last_frame] != kStOk) return;  // (the whole workgroup)
+  if (active) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      uint32_t bits = 0;
+#pragma unroll
+      for (int q = 0; q < K; ++q) bits |= (held0[c][q] != 0 ? 1u : 0u) << q;
+      row_bits[c][t * K + j] = bits;
+    }
+  }
+  __syncthreads();  // (also: every wave is past the last frame's gather, the job arrays are free)
+  if (tid < 64) {   // wave 0, lane = mask word: the rows of its tile that lie in the word and inside K x K
+    const uint32_t wt = tid / kWords, wi = tid - wt * kWords;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      uint64_t m = 0;
+      if (tid < jobs) {
+#pragma unroll
+        for (uint32_t r = 0; r < kRowsPerWord; ++r) {
+          const uint32_t row = wi * kRowsPerWord + r;
+          if (row < K) m |= (uint64_t)row_bits[c][wt * K + row] << (r * N);
+        }
+      }
+      const uint32_t pc = (uint32_t)__popcll(m), ex = wave_exclusive_scan(pc);
+      if (tid < kJobs) { job_mask[c][tid] = m; job_base[c][tid] = ex; }
+      if (tid < jobs) store_mask(group_masks(g, args.last, c, gr) + 2 * tid, m);
+      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)(ex + pc), 63);
+      if (tid == 0) args.last_cnt[c * per_plane + gi0] = total;
+    }
+  }
+  __syncthreads();
+  if (!active) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    uint16_t* run = args.last_runs + (size_t)(c * per_plane + gi0) * args.cap;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      const uint32_t k = j * N + q, w = t * kWords + (k >> 6), b = k & 63u;
+      const uint64_t mask = job_mask[c][w], below = (1ull << b) - 1;
+      if (held0[c][q] != 0) run[job_base[c][w] + (uint32_t)__popcll(mask & below)] = (uint16_t)held0[c][q];
+    }
+  }
+}
+
+template <int N, int K>
+void launch_decode_delta_temporal_reduced(uint32_t period, dim3 grid, hipStream_t s, const DecodeDeltaArgs& a, uint32_t last_frame) {
+  if (period == 2) hipLaunchKernelGGL((decode_delta_temporal_reduced_kernel<N, K, 1>), grid, dim3(reduced_threads(N, K)), 0, s, a, last_frame);
+  else hipLaunchKernelGGL((decode_delta_temporal_reduced_kernel<N, K, 2>), grid, dim3(reduced_threads(N, K)), 0, s, a, last_frame);
+}
+
+// the instantiation for a block of 8 or 16, a reduce of 2, 4 or 8 and a period of 2 or 4 (all checked by the caller)
+void launch_decode_delta_temporal_reduced(uint32_t block, uint32_t reduce, uint32_t period, dim3 grid, hipStream_t s,
+                                          const DecodeDeltaArgs& a, uint32_t last_frame) {
+  if (block == 8) {
+    if (reduce == 2) launch_decode_delta_temporal_reduced<8, 4>(period, grid, s, a, last_frame);
+    else if (reduce == 4) launch_decode_delta_temporal_reduced<8, 2>(period, grid, s, a, last_frame);
+    else launch_decode_delta_temporal_reduced<8, 1>(period, grid, s, a, last_frame);
+  } else {
+    if (reduce == 2) launch_decode_delta_temporal_reduced<16, 8>(period, grid, s, a, last_frame);
+    else if (reduce == 4) launch_decode_delta_temporal_reduced<16, 4>(period, grid, s, a, last_frame);
+    else launch_decode_delta_temporal_reduced<16, 2>(period, grid, s, a, last_frame);
+  }
+}
+
 // ---- drain -------------------------------------------------------------------------------------------------------------------
 
 // offsets[n] bytes (a multiple of 16: every frame is padded to 16) from HBM to pinned host memory, 16 B per lane per store
@@ -3830,19 +4018,23 @@ uint64_t svc_hip_decode_delta_levels_reduced_workspace_bytes(uint32_t n_frames, 
   return layout_bytes(decode_delta_ws, n_frames, g.groups, g.tpg * block_w * block_h);
 }
 
-// Checked in the order of svc_hip_decode_levels_reduced_frames, then last_capacity; n_frames == 0 then returns SVC_OK; then pointers.  The
-// launches are those of svc_hip_decode_delta_levels_frames.
-int svc_hip_decode_delta_levels_reduced_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets,
-                                               uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key,
-                                               uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
-                                               uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, uint32_t reduce, const uint32_t* d_gaze,
-                                               uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec, uint8_t* d_display,
-                                               uint32_t display_w, uint32_t display_h, uint8_t* d_last, uint64_t last_capacity,
-                                               uint64_t* d_last_bytes, uint32_t* d_status, void* stream) {
-  const char* what = "decode_delta_levels_reduced";
-  int rc = validate_reduced(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, reduce, display_w,
-                            display_h);
+// Checked in the order of svc_hip_decode_levels_reduced_frames (the period right after the geometry), then last_capacity; n_frames == 0
+// then returns SVC_OK; then pointers.  The launches are those of svc_hip_decode_delta_levels_frames.  period 1:
+// svc_hip_decode_delta_levels_reduced_frames; 2 or 4: the temporal call, which differs in the status kernel, in the reconstruction kernel
+// and in the frame d_last holds.
+static int decode_delta_levels_reduced(const char* what, uint32_t period, const uint8_t* d_frames, uint64_t stream_bytes,
+                                       const uint64_t* d_frame_offsets, uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes,
+                                       const uint32_t* d_key, uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                       uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, uint32_t reduce,
+                                       const uint32_t* d_gaze, uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec,
+                                       uint8_t* d_display, uint32_t display_w, uint32_t display_h, uint8_t* d_last, uint64_t last_capacity,
+                                       uint64_t* d_last_bytes, uint32_t* d_status, void* stream) {
+  int rc = validate_decode_geom(what, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
   if (rc) return rc;
+  if ((rc = validate_period(what, period))) return rc;
+  if ((rc = validate_reduced(what, n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, reduce, display_w,
+                             display_h)))
+    return rc;
   const uint32_t rw = frame_w / reduce, rh = frame_h / reduce;  // whole: the sides are multiples of the block, the block of `reduce`
   const bool display = display_w != 0 || display_h != 0;
   const Geom g = make_geom(frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
@@ -3867,16 +4059,57 @@ int svc_hip_decode_delta_levels_reduced_frames(const uint8_t* d_frames, uint64_t
                           d_gaze, d_rec, (float)fg_step, (float)bg_step, d_last, d_last_bytes, ws.last_cnt, ws.last_first, ws.last_head,
                           ws.last_runs, cap};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((rc = enqueue_delta_input(what, a.d, true, prev_bytes, s))) return rc;
-  launch_decode_delta_reduced(block_w, reduce, dim3(g.tiles_y * g.gx), s, a);
+  if ((rc = enqueue_delta_input(what, a.d, true, prev_bytes, s, period))) return rc;
+  const uint32_t last_frame = (n_frames - 1) / period * period;  // the frame the next call's frame 0 refers to
+  if (period == 1) launch_decode_delta_reduced(block_w, reduce, dim3(g.tiles_y * g.gx), s, a);
+  else launch_decode_delta_temporal_reduced(block_w, reduce, period, dim3(g.tiles_y * g.gx), s, a, last_frame);
   if (d_last) {
     if ((rc = check_launch(what, "reconstruction"))) return rc;
-    hipLaunchKernelGGL(decode_delta_last_scan_kernel, dim3(1), dim3(kThreads), 0, s, a);
+    DecodeDeltaArgs last = a;  // the two kernels take the call's last frame for the one d_last holds
+    last.d.n = last_frame + 1;
+    hipLaunchKernelGGL(decode_delta_last_scan_kernel, dim3(1), dim3(kThreads), 0, s, last);
     if ((rc = check_launch(what, "scan of the last frame"))) return rc;
-    hipLaunchKernelGGL(decode_delta_last_write_kernel, dim3(div_up(g.groups, kThreads / 64)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(decode_delta_last_write_kernel, dim3(div_up(g.groups, kThreads / 64)), dim3(kThreads), 0, s, last);
   }
   return finish_with_display(what, d_last ? "write of the last frame" : "reconstruction", display, d_rec, d_display, n_frames, rw, rh,
                              display_w, display_h, s);
+}
+
+int svc_hip_decode_delta_levels_reduced_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets,
+                                               uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key,
+                                               uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h, uint32_t mv_block_w,
+                                               uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step, uint32_t reduce, const uint32_t* d_gaze,
+                                               uint8_t* d_workspace, uint64_t workspace_bytes, float* d_rec, uint8_t* d_display,
+                                               uint32_t display_w, uint32_t display_h, uint8_t* d_last, uint64_t last_capacity,
+                                               uint64_t* d_last_bytes, uint32_t* d_status, void* stream) {
+  return decode_delta_levels_reduced("decode_delta_levels_reduced", 1, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev, prev_bytes,
+                                     d_key, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, reduce, d_gaze,
+                                     d_workspace, workspace_bytes, d_rec, d_display, display_w, display_h, d_last, last_capacity, d_last_bytes,
+                                     d_status, stream);
+}
+
+// (include/svc_hip_temporal_decode.h) the workspace is the reduced call's
+uint64_t svc_hip_decode_delta_levels_temporal_reduced_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,
+                                                                      uint32_t block_h, uint32_t mv_block_w, uint32_t mv_block_h,
+                                                                      uint32_t period) {
+  if (validate_decode_geom("decode_delta_levels_temporal_reduced_workspace_bytes", frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h) ||
+      validate_period("decode_delta_levels_temporal_reduced_workspace_bytes", period))
+    return 0;
+  return svc_hip_decode_delta_levels_reduced_workspace_bytes(n_frames, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h);
+}
+
+int svc_hip_decode_delta_levels_temporal_reduced_frames(const uint8_t* d_frames, uint64_t stream_bytes, const uint64_t* d_frame_offsets,
+                                                        uint32_t n_frames, const uint8_t* d_prev, uint64_t prev_bytes, const uint32_t* d_key,
+                                                        uint32_t frame_w, uint32_t frame_h, uint32_t block_w, uint32_t block_h,
+                                                        uint32_t mv_block_w, uint32_t mv_block_h, uint32_t fg_step, uint32_t bg_step,
+                                                        uint32_t reduce, const uint32_t* d_gaze, uint8_t* d_workspace,
+                                                        uint64_t workspace_bytes, float* d_rec, uint8_t* d_display, uint32_t display_w,
+                                                        uint32_t display_h, uint8_t* d_last, uint64_t last_capacity, uint64_t* d_last_bytes,
+                                                        uint32_t* d_status, void* stream, uint32_t period) {
+  return decode_delta_levels_reduced("decode_delta_levels_temporal_reduced", period, d_frames, stream_bytes, d_frame_offsets, n_frames, d_prev,
+                                     prev_bytes, d_key, frame_w, frame_h, block_w, block_h, mv_block_w, mv_block_h, fg_step, bg_step, reduce,
+                                     d_gaze, d_workspace, workspace_bytes, d_rec, d_display, display_w, display_h, d_last, last_capacity,
+                                     d_last_bytes, d_status, stream);
 }
 
 uint64_t svc_hip_split_levels_workspace_bytes(uint32_t n_in, uint32_t n_out, uint32_t frame_w, uint32_t frame_h, uint32_t block_w,

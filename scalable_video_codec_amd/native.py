@@ -229,6 +229,16 @@ SIGNATURES_TEMPORAL = {
                                                              _vp, _vp, _vp, _vp, _u32]),
 }
 
+# The calls of include/svc_hip_temporal_decode.h: a table of its own for the same reason (SIGNATURES_TEMPORAL is tied one to one to
+# include/svc_hip_temporal.h by tests/test_dct_pack_delta_temporal_host.py); load() applies all three.
+SIGNATURES_TEMPORAL_DECODE = {
+    # the temporal-layer delta stream straight to display frames at reduced size (csrc/levels.hip; host statement:
+    # layers.undelta_temporal_frames + levels.decode_reduced_frame)
+    "svc_hip_decode_delta_levels_temporal_reduced_workspace_bytes": (_u64, [_u32] * 8),
+    "svc_hip_decode_delta_levels_temporal_reduced_frames": (C.c_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp] + [_u32] * 9 +
+                                                            [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _u32]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -241,7 +251,7 @@ def load() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m scalable_video_codec_amd.build` "
                 "(or __graft_entry__.build()); the MI355X path has no CPU fallback")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TEMPORAL.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TEMPORAL.items()) + list(SIGNATURES_TEMPORAL_DECODE.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -1737,6 +1747,13 @@ def decode_delta_levels_reduced_frames(frames: torch.Tensor, offsets: torch.Tens
     prev: None (frame 0 is a key frame), or the reconstructed frame before frame 0 or its band (0, 0, K, K), exactly its bytes.
     want_last (or a `last` buffer of at least levels_max_bytes(1, ...)): the band (0, 0, K, K) of the reconstructed last frame, the next
     call's prev once cut to last_bytes (a (1,) i64 tensor on the device).  `last` must not overlap `frames` or `prev`."""
+    return _decode_delta_reduced_call(None, frames, offsets, w, h, block, mv_block, fg_step, bg_step, reduce, prev, key, gaze, display,
+                                      want_last, rec, out_display, last, workspace, status)
+
+
+def _decode_delta_reduced_call(_period, frames, offsets, w, h, block, mv_block, fg_step, bg_step, reduce, prev, key, gaze, display, want_last,
+                               rec, out_display, last, workspace, status):
+    """decode_delta_levels_reduced_frames (_period None) or decode_delta_levels_temporal_reduced_frames."""
     n = offsets.numel() - 1
     (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
     dev = frames.device
@@ -1751,19 +1768,47 @@ def decode_delta_levels_reduced_frames(frames: torch.Tensor, offsets: torch.Tens
         last = torch.empty(max(levels_max_bytes(1, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
     last_bytes = None if last is None else torch.zeros(1, dtype=torch.int64, device=dev)
     if workspace is None:
-        workspace = torch.empty(max(decode_delta_levels_reduced_workspace_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+        need = (decode_delta_levels_reduced_workspace_bytes(n, w, h, block, mv_block) if _period is None else
+                decode_delta_levels_temporal_reduced_workspace_bytes(n, w, h, block, mv_block, _period))
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     g = None
     if gaze is not None:
         g = torch.as_tensor(gaze, dtype=torch.int32).reshape(n, 4).to(dev).contiguous()
     if status is None:
         status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
-    _check(load().svc_hip_decode_delta_levels_reduced_frames(
+    fn = load().svc_hip_decode_delta_levels_reduced_frames if _period is None else load().svc_hip_decode_delta_levels_temporal_reduced_frames
+    _check(fn(
         _dev(frames, torch.uint8), frames.numel(), _dev(offsets, torch.int64), n, None if prev is None else _dev(prev, torch.uint8),
         0 if prev is None else prev.numel(), None if k is None else _dev(k, torch.int32), w, h, bw, bh, mbw, mbh, fg_step, bg_step, reduce,
         None if g is None else _dev(g, torch.int32), _dev(workspace, torch.uint8), workspace.numel(), _dev(rec, torch.float32),
         None if out_display is None else _dev(out_display, torch.uint8), dw, dh, None if last is None else _dev(last, torch.uint8),
-        0 if last is None else last.numel(), None if last is None else _dev(last_bytes, torch.int64), _dev(status, torch.int32), _stream()))
+        0 if last is None else last.numel(), None if last is None else _dev(last_bytes, torch.int64), _dev(status, torch.int32), _stream(),
+        *(() if _period is None else (_period,))))
     return rec, out_display, status, last, last_bytes
+
+
+def decode_delta_levels_temporal_reduced_workspace_bytes(n: int, w: int, h: int, block, mv_block, period: int) -> int:
+    """Scratch of decode_delta_levels_temporal_reduced_frames for n frames, at any reduce; 0 for a geometry or a period it refuses."""
+    (bw, bh), (mbw, mbh) = _bwbh(block), _bwbh(mv_block)
+    return int(load().svc_hip_decode_delta_levels_temporal_reduced_workspace_bytes(n, w, h, bw, bh, mbw, mbh, period))
+
+
+def decode_delta_levels_temporal_reduced_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block, period: int,
+                                                fg_step: int = 1, bg_step: int = 640, reduce: int = 2,
+                                                prev: Optional[torch.Tensor] = None, key=None, gaze=None,
+                                                display: Optional[Tuple[int, int]] = None, want_last: bool = False,
+                                                rec: Optional[torch.Tensor] = None, out_display: Optional[torch.Tensor] = None,
+                                                last: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                                status: Optional[torch.Tensor] = None
+                                                ) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """decode_delta_levels_reduced_frames with temporal layers (include/svc_hip_temporal_decode.h): undelta_levels_temporal_frames and
+    decode_levels_reduced_frames in one call, with that function's arguments and results plus period (1, 2 or 4).  There is no numpy
+    statement of its own: it is layers.undelta_temporal_frames + levels.decode_reduced_frame, and for the streams it takes
+    layers.band_frames / layers.thin_frames.  The stream may be the temporal delta stream or its band (0, 0, K, K), K = block / reduce;
+    prev: the reconstructed frame at index -period or that band of it; `last` is the band (0, 0, K, K) of reconstructed frame
+    period * ((n - 1) // period), the next call's prev."""
+    return _decode_delta_reduced_call(period, frames, offsets, w, h, block, mv_block, fg_step, bg_step, reduce, prev, key, gaze, display,
+                                      want_last, rec, out_display, last, workspace, status)
 
 
 def window_entropy_max_bytes(n_out: int, w: int, h: int, block, mv_block) -> int:

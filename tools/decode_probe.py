@@ -41,6 +41,18 @@
   python tools/decode_probe.py delta-reduced-rate   `delta-rate`'s delta stream; per reduce, tests/dropin/stream_delta_reduced_main
                                          (DecodeDeltaReduced) on the entropy-coded band (0, 0, K, K) and on the full SVCQ delta stream against
                                          stream_delta_main (DecodeDelta) at full size with the display (W / r, H / r), PCIe included, alternating
+  python tools/decode_probe.py temporal-reduced [C3|C5]   `temporal`'s batch stored at (1, 640) and at (1, 1), frame 0 the key frame, coded at
+                                         periods 2 and 4; per reduce 2, 4, 8, with the display pass (W / r, H / r): the fused
+                                         svc_hip_decode_delta_levels_temporal_reduced_frames (include/svc_hip_temporal_decode.h) with and without
+                                         d_last, on the full stream and on its band (0, 0, K, K), against (a)
+                                         svc_hip_undelta_levels_temporal_frames + svc_hip_decode_levels_reduced_frames, (b)
+                                         svc_hip_decode_delta_levels_temporal_frames with the display pass at that size and (c)
+                                         svc_hip_decode_delta_levels_reduced_frames on the period-1 stream of the same clip (the price of the
+                                         layers), alternating, device events, the median of three windows; the routes' rec and display compared
+  python tools/decode_probe.py temporal-reduced-rate   `rate`'s stream coded at periods 2 and 4 (a key frame every 16); per reduce 2 and 8,
+                                         tests/dropin/stream_temporal_reduced_main (DecodeDeltaTemporalReduced) on the entropy-coded band
+                                         (0, 0, K, K) and on the full SVCQ stream against its reduce-0 mode (DecodeDeltaTemporal at full size with
+                                         the display (W / r, H / r)), PCIe included, alternating
 """
 import os
 import subprocess
@@ -714,7 +726,176 @@ def delta_reduced_rate() -> None:
                         sys.exit(1)
 
 
+def temporal_reduced() -> None:
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native, pipeline
+    cfg = {"C3": configs.C3, "C5": configs.C5}[sys.argv[2] if len(sys.argv) > 2 else "C3"]
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    clip = synth.SynthClip(cfg.width, cfg.height, n + 1, cfg.seed, device=dev)
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(n + 1)]).contiguous()
+    enc = pipeline.ClipEncoder(cfg, n + 1, dev)
+    enc.load_frames(list(frames))
+    enc.step()
+    torch.cuda.synchronize()
+    bgr, types = frames[1:].contiguous(), enc.types.clone()
+
+    def timed(fn, reps=20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def fmt(t):
+        return f"{np.median(t):.3f} (min {min(t):.3f}, max {max(t):.3f})"
+
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    back, bo = torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ws_u = torch.empty(native.undelta_levels_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    ws_x = torch.empty(native.decode_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    ws_f = torch.empty(native.decode_delta_levels_temporal_reduced_workspace_bytes(n, pw, ph, block, mv, 4), dtype=torch.uint8, device=dev)
+    rec_full = torch.empty((n, ph, pw, 3), dtype=torch.float32, device=dev)
+    last = torch.empty(native.levels_max_bytes(1, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    st, st2 = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    keys = [1] + [0] * (n - 1)
+    print(f"{cfg.name} batch of {n}, tiles {block} x {block}, frame 0 the key frame; ms per call of {n} frames with the display pass (W / r, H / r), "
+          f"device events over 20 back-to-back calls, the median of three such windows per route, the routes alternating", flush=True)
+    for steps in ((1, 640), (1, 1)):
+        out, offs = native.dct_pack_levels_frames(bgr, block, types, mv, *steps)
+        torch.cuda.synchronize()
+        stream = out[:int(offs[-1])].clone()
+        d1, d1o, dst = native.delta_levels_frames(stream, offs, pw, ph, block, mv, key=keys)  # the period-1 stream of the same clip
+        torch.cuda.synchronize()
+        assert not dst.any()
+        d1 = d1[:int(d1o[-1])].clone()
+        for period in (2, 4):
+            d, do, dst = native.delta_levels_temporal_frames(stream, offs, pw, ph, block, mv, period, key=keys)
+            torch.cuda.synchronize()
+            assert not dst.any()
+            d = d[:int(do[-1])].clone()
+            for r in (2, 4, 8):
+                k = block // r
+                rw, rh = pw // r, ph // r
+                rec, rec2 = (torch.empty((n, rh, rw, 3), dtype=torch.float32, device=dev) for _ in range(2))
+                disp, disp2 = (torch.empty((n, rh, rw, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+                b, b_offs, bst = native.band_levels_frames(d, do, pw, ph, block, mv, band=[(0, 0, k, k)] * n)  # what a server sends
+                torch.cuda.synchronize()
+                assert not bst.any()
+                b = b[:int(b_offs[-1])].clone()
+                kw = dict(gaze=None, display=(rw, rh))
+
+                def two():  # (a) the route the fused call replaces
+                    native.undelta_levels_temporal_frames(d, do, pw, ph, block, mv, period, key=keys, out=back, out_offsets=bo, workspace=ws_u,
+                                                          status=st2)
+                    native.decode_levels_reduced_frames(back, bo, pw, ph, block, mv, 1, 640, r, rec=rec2, out_display=disp2, workspace=ws_x, **kw)
+
+                def full():  # (b) the full-size temporal decode with the display pass at the reduced size
+                    native.decode_delta_levels_temporal_frames(d, do, pw, ph, block, mv, period, fg_step=1, bg_step=640, key=keys, rec=rec_full,
+                                                               out_display=disp2, workspace=ws_f, status=st2, **kw)
+
+                def plain():  # (c) the reduced decode of the period-1 delta stream: the price of the layers
+                    native.decode_delta_levels_reduced_frames(d1, d1o, pw, ph, block, mv, 1, 640, r, key=keys, rec=rec2, out_display=disp2,
+                                                              workspace=ws_f, status=st2, **kw)
+
+                def fused(data=d, data_offs=do, want_last=None):
+                    native.decode_delta_levels_temporal_reduced_frames(data, data_offs, pw, ph, block, mv, period, 1, 640, r, key=keys, rec=rec,
+                                                                       out_display=disp, last=want_last, workspace=ws_f, status=st, **kw)
+
+                routes = {"two": two, "full": full, "plain": plain, "no_last": fused, "fused": lambda: fused(want_last=last),
+                          "band": lambda: fused(b, b_offs), "band_last": lambda: fused(b, b_offs, last)}
+                for _ in range(2):
+                    for fn in routes.values():
+                        fn()
+                torch.cuda.synchronize()
+                for fn in (routes["fused"], routes["band_last"]):  # both streams against the two calls, bit for bit
+                    rec.zero_(), disp.zero_()
+                    two(), fn()
+                    torch.cuda.synchronize()
+                    assert not st.any() and not st2.any() and torch.equal(rec.view(torch.int32), rec2.view(torch.int32)), "the routes differ"
+                    assert torch.equal(disp, disp2)
+                t = {name_: [] for name_ in routes}
+                for _ in range(3):
+                    for name_, fn in routes.items():
+                        t[name_].append(timed(fn))
+                m = {k_: float(np.median(v)) for k_, v in t.items()}
+                print(f"stored at {steps}, period {period}, reduce {r} ({d.numel() / n / 1e6:.3f} MB per delta frame, {b.numel() / n / 1e6:.3f} in its "
+                      f"band): fused without d_last {fmt(t['no_last'])}; with d_last {fmt(t['fused'])}; on the band stream {fmt(t['band'])}; on the "
+                      f"band with d_last {fmt(t['band_last'])}; (a) temporal undelta + reduced decode {fmt(t['two'])}, fused / a = "
+                      f"{m['no_last'] / m['two']:.2f}; (b) full-size temporal decode + display {fmt(t['full'])}, fused / b = "
+                      f"{m['no_last'] / m['full']:.2f}; (c) period-1 reduced delta decode {fmt(t['plain'])}, fused / c = "
+                      f"{m['no_last'] / m['plain']:.2f}", flush=True)
+
+
+def temporal_reduced_rate() -> None:
+    """DecodeDeltaTemporalReduced on the band SVCE stream and on the full SVCQ stream against DecodeDeltaTemporal at full size with the
+    display at the reduced size, PCIe included: `rate`'s 64 frames coded at periods 2 and 4 with a key frame every 16, the bands and their
+    entropy coding made on the device."""
+    import numpy as np
+    import torch
+    from scalable_video_codec_amd import native
+    n = 65
+    m = n - 1
+    pw, ph = CFG.padded
+    block, mv = CFG.dct_block, CFG.mv_block
+    tmp = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
+    exe = os.path.join(ROOT, "tests", "dropin", "stream_temporal_reduced_main")
+    with tempfile.TemporaryDirectory(dir=tmp) as d:
+        prefix = _stored_stream(d, n)
+        big = torch.from_numpy(np.fromfile(prefix + ".big", np.uint8)).cuda()
+        offs = torch.from_numpy(np.fromfile(prefix + ".offsets", np.uint64).astype(np.int64)).cuda()
+        keys = [int(i % 16 == 0) for i in range(m)]
+        key_file = os.path.join(d, "key.txt")
+        with open(key_file, "w") as f:
+            f.write("".join(f"{k}\n" for k in keys))
+
+        def store(name, data, data_offs):
+            p = os.path.join(d, name)
+            data[:int(data_offs[-1])].cpu().numpy().tofile(p + ".big")
+            data_offs.cpu().numpy().astype(np.uint64).tofile(p + ".offsets")
+            return p, int(data_offs[-1]) / m / 1e6
+
+        for period in (2, 4):
+            diff, do, st = native.delta_levels_temporal_frames(big, offs, pw, ph, block, mv, period, key=keys)
+            torch.cuda.synchronize()
+            assert not st.any()
+            diff = diff[:int(do[-1])].clone()
+            dprefix, mb_full = store(f"delta{period}", diff, do)
+            print(f"{m} frames, period {period}: plain stream {big.numel() / m / 1e6:.3f} MB per frame, temporal delta stream (a key frame every 16) "
+                  f"{mb_full:.3f}", flush=True)
+            for r in (2, 8):
+                k = block // r
+                dw, dh = pw // r, ph // r
+                band, bo, bst = native.band_levels_frames(diff, do, pw, ph, block, mv, band=[(0, 0, k, k)] * m)
+                coded, co, est = native.entropy_encode_frames(band[:int(bo[-1])].clone(), bo, pw, ph, block, mv)
+                torch.cuda.synchronize()
+                assert not bst.any() and not est.any()
+                bprefix, mb_band = store(f"band{period}_{r}", coded, co)
+                print(f"period {period}, reduce {r}: the band (0, 0, {k}, {k}) {int(bo[-1]) / m / 1e6:.3f} MB per frame, entropy-coded {mb_band:.3f}",
+                      flush=True)
+                gaze = os.path.join(d, f"gaze{r}.txt")
+                with open(gaze, "w") as f:
+                    for i in range(m):
+                        f.write(f"{(60 + 29 * i) % dw} {(40 + 17 * i) % dh}\n")
+                tail = [gaze, key_file, "16", "3"]
+                for turn in range(3):  # alternating, every run printed: the spread is part of the result
+                    for what, args in (("band SVCE", [bprefix, str(m), "0", "0", *tail, str(r), str(period), "-"]),
+                                       ("full SVCQ", [dprefix, str(m), "0", "0", *tail, str(r), str(period), "-"]),
+                                       ("full size, DecodeDeltaTemporal", [dprefix, str(m), str(dw), str(dh), *tail, "0", str(period), "-"])):
+                        p = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300)
+                        print(f"== stream_temporal_reduced_main ({what}) period {period} display {dw}x{dh} batch 16, run {turn} (exit {p.returncode})\n"
+                              f"{p.stdout.strip()}\n{p.stderr.strip()}", flush=True)
+                        if p.returncode != 0:
+                            sys.exit(1)
+
+
 if __name__ == "__main__":
     {"rate": rate, "kernels": kernels, "reduced": reduced, "reduced-rate": reduced_rate, "layers-reduced": layers_reduced,
      "layers-reduced-rate": layers_reduced_rate, "delta": delta, "delta-rate": delta_rate, "delta-reduced": delta_reduced,
-     "delta-reduced-rate": delta_reduced_rate, "temporal": temporal}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
+     "delta-reduced-rate": delta_reduced_rate, "temporal": temporal, "temporal-reduced": temporal_reduced,
+     "temporal-reduced-rate": temporal_reduced_rate}[sys.argv[1] if len(sys.argv) > 1 else "kernels"]()
