@@ -128,7 +128,10 @@ enum class Stage : uint32_t { kLumaPyramid = 0, kHalo, kHbma, kRansac, kSegment,
 enum class Buffer : uint32_t { kMv = 0, kMinMad, kGlobalMotion, kRmse, kInlierMask, kInlierCount, kBlockTypes,
                                kCoeffs, kRecords, kPyramids, kBgr,
                                kCompact /* offsets[pairs] bytes of SVCQ frames, back to back */, kCompactOffsets /* [pairs + 1] u64 */,
-                               kCompactChoice /* SetCompactBudget: [pairs] u32, the ladder entry of each frame; empty without a budget */, kCount };
+                               kCompactChoice /* SetCompactBudget: [pairs] u32, the ladder entry of each frame; empty without a budget or a target */,
+                               kCompactDistortion /* SetCompactQuality: [pairs] u64, the squared error of each frame's entry; empty without a target
+                                                     and until a step under the current target has finished */,
+                               kCount };
 
 class ClipEncoder {
  public:
@@ -178,6 +181,16 @@ class ClipEncoder {
   // the ladder is checked by the C ABI's pointer-free checks (std::runtime_error with its message).  ladder_len == 0 returns to the fixed
   // fg_step / bg_step.  The first call allocates the larger workspace, a budget and a choice per pair.
   void SetCompactBudget(const svc_step_pair* ladder, uint32_t ladder_len, uint32_t bytes_per_frame);
+  // The same by quality: every step submitted after this call packs each frame with the coarsest pair of `ladder` (the rules above) whose
+  // squared error D still meets `target`, in the units of include/svc_hip_quality.h (scalable_video_codec_amd.layers.distortion_target
+  // gives it for a PSNR), and not finer than the finest pair whose frame fits bytes_cap SVCQ bytes (0: no cap) --
+  // svc_hip_dct_pack_levels_quality_frames in place of svc_hip_dct_pack_levels_frames, still without planes.  Buffer::kCompactChoice then
+  // holds each frame's ladder entry, bit 31 set where even the last one is over the cap and bit 30 where the target is not met, and
+  // Buffer::kCompactDistortion each frame's D at its entry, once a step submitted after this call has finished (empty until then: what an
+  // earlier setting's step left is not this ladder's).  Sync()s first; the ladder is checked by the C ABI's pointer-free checks.
+  // ladder_len == 0 returns to the fixed fg_step / bg_step.  A budget and a target exclude each other: the later call replaces the earlier.
+  // The first call allocates the larger workspace, a target, a table row and a chosen distortion per pair.
+  void SetCompactQuality(const svc_step_pair* ladder, uint32_t ladder_len, uint64_t target, uint32_t bytes_cap /* 0: none */);
   void Flush();  // pipelined schedule: enqueues what is left of the steps in flight
   void Sync();   // Flush() + waits for every stream
 

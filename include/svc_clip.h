@@ -101,7 +101,10 @@ enum { SVC_STAGE_LUMA_PYRAMID = 0, SVC_STAGE_HALO, SVC_STAGE_HBMA, SVC_STAGE_RAN
 enum { SVC_BUF_MV = 0, SVC_BUF_MIN_MAD, SVC_BUF_GLOBAL_MOTION, SVC_BUF_RMSE, SVC_BUF_INLIER_MASK,
        SVC_BUF_INLIER_COUNT, SVC_BUF_BLOCK_TYPES, SVC_BUF_COEFFS, SVC_BUF_RECORDS, SVC_BUF_PYRAMIDS,
        SVC_BUF_BGR, SVC_BUF_COMPACT /* bytes = offsets[pairs] of the newest step */, SVC_BUF_COMPACT_OFFSETS,
-       SVC_BUF_COMPACT_CHOICE /* svc_clip_set_compact_budget: pairs x u32, each frame's ladder entry; empty without a budget */, SVC_BUF_COUNT };
+       SVC_BUF_COMPACT_CHOICE /* svc_clip_set_compact_budget: pairs x u32, each frame's ladder entry; empty without a budget or a target */,
+       SVC_BUF_COMPACT_DISTORTION /* svc_clip_set_compact_quality: pairs x u64, each frame's squared error at its entry; empty without a target
+                                     and until a step under the current target has finished */,
+       SVC_BUF_COUNT };
 
 /* Halo transport override: must enqueue on `stream` the send of `bytes` from d_send to rank + 1
  * (if any) and the receive into d_recv from rank - 1 (if any). */
@@ -138,6 +141,11 @@ int svc_clip_wait_step(svc_clip* clip, uint32_t step); /* returns once nothing r
    gives) whose frame fits bytes_per_frame SVCQ bytes, and SVC_BUF_COMPACT_CHOICE holds the entries chosen (bit 31: over budget).
    ladder_len == 0 returns to the fixed fg_step / bg_step.  A call and not a config field: svc_clip_config keeps its layout. */
 int svc_clip_set_compact_budget(svc_clip* clip, const svc_step_pair* ladder, uint32_t ladder_len, uint32_t bytes_per_frame);
+/* The same by quality (svc::ClipEncoder::SetCompactQuality): syncs, then every later step packs each frame with the coarsest of `ladder`'s pairs
+   whose squared error still meets `target` (the units of include/svc_hip_quality.h), not finer than bytes_cap SVCQ bytes allow (0: no cap);
+   SVC_BUF_COMPACT_CHOICE holds the entries chosen (bit 31: over the cap, bit 30: target not met), SVC_BUF_COMPACT_DISTORTION each frame's squared
+   error at its entry.  ladder_len == 0 returns to the fixed steps.  A budget and a target exclude each other: the later call replaces the earlier. */
+int svc_clip_set_compact_quality(svc_clip* clip, const svc_step_pair* ladder, uint32_t ladder_len, uint64_t target, uint32_t bytes_cap);
 int svc_clip_flush(svc_clip* clip);           /* enqueue what the pipeline still holds */
 int svc_clip_sync(svc_clip* clip);            /* flush + wait for the GPU */
 

@@ -34,7 +34,7 @@ BUFFERS = {"mv": (0, torch.float32), "min_mad": (1, torch.float32), "global_moti
            "rmse": (3, torch.float32), "inlier_mask": (4, torch.uint8), "inlier_count": (5, torch.int32),
            "block_types": (6, torch.int32), "coeffs": (7, torch.float32), "records": (8, torch.uint8),
            "pyramids": (9, torch.uint8), "bgr": (10, torch.uint8), "compact": (11, torch.uint8), "compact_offsets": (12, torch.int64),
-           "compact_choice": (13, torch.int32)}
+           "compact_choice": (13, torch.int32), "compact_distortion": (14, torch.int64)}
 COMM_ID_BYTES = 128
 
 
@@ -68,6 +68,7 @@ SIGNATURES = {
     "svc_clip_step_frames": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_u32)]),
     "svc_clip_wait_step": (C.c_int, [_vp, _u32]),
     "svc_clip_set_compact_budget": (C.c_int, [_vp, C.POINTER(native.StepPair), _u32, _u32]),
+    "svc_clip_set_compact_quality": (C.c_int, [_vp, C.POINTER(native.StepPair), _u32, _u64, _u32]),
     "svc_clip_flush": (C.c_int, [_vp]),
     "svc_clip_sync": (C.c_int, [_vp]),
     "svc_clip_stage_time": (C.c_int, [_vp, _u32, C.POINTER(C.c_double), C.POINTER(_u32)]),
@@ -249,6 +250,22 @@ class Clip:
         Syncs first."""
         arr, k = native._ladder(ladder)
         _check(load().svc_clip_set_compact_budget(self._h, arr, k, bytes_per_frame))
+
+    def set_compact_quality(self, ladder, psnr_db=None, target=None, bytes_cap: int = 0) -> None:
+        """Constant quality for a clip made with compact=True: every later step packs each frame with the coarsest (fg_step, bg_step) of
+        `ladder` whose squared error still meets the target -- psnr_db in dB (layers.distortion_target at the padded size), or `target` in the
+        units of include/svc_hip_quality.h -- and not finer than bytes_cap SVCQ bytes allow (0: no cap)
+        (svc_hip_dct_pack_levels_quality_frames).  read("compact_choice") then gives each frame's entry (bit 31: over the cap, bit 30:
+        target not met) and read("compact_distortion") its squared error there (u64 values in an int64 tensor; empty until a step under this
+        setting has finished).  An empty ladder returns to
+        the configuration's steps; a budget and a target replace each other.  Syncs first."""
+        arr, k = native._ladder(ladder)
+        if k and (psnr_db is None) == (target is None):
+            raise ValueError("give psnr_db or target")
+        if k and target is None:
+            from . import layers
+            target = layers.distortion_target(psnr_db, self.info.padded_w, self.info.padded_h)
+        _check(load().svc_clip_set_compact_quality(self._h, arr, k, int(target or 0), bytes_cap))
 
     def flush(self) -> None:
         _check(load().svc_clip_flush(self._h))

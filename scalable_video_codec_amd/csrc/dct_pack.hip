@@ -61,6 +61,14 @@
 // reference but that of the run's first frame lies in the run: PERIOD is a template parameter of the DELTA and TALLY forms, the trip in
 // front of the run transforms frame run_first - PERIOD, and the kept levels are replaced only at a frame a later one refers to.  The
 // other five forms' device code is instruction for instruction what it was (profiles/dct_pack_delta_temporal_c3.txt).
+//
+// A quality target (svc_hip_dct_pack_levels_quality_frames; include/svc_hip_quality.h states it, layers.distortion_table in numpy): per frame
+// the coarsest pair of the ladder whose squared error D_k still meets a target, optionally not finer than the byte budget allows.
+// dct_measure_kernel<N> is the sixth form of the body, MEASURE beside COUNT: the counting form, which also keeps |c| of the lane's 48
+// coefficients and, per ladder entry, sums e^2, e = rint(256 (|c| - q s)) -- exact integers, so any order gives the same u64.  A wave stores
+// its 64 sums as a row beside its row of counts; dct_measure_sum_kernel adds both kinds of rows in kSumParts parts,
+// dct_quality_select_kernel chooses and writes the frame's steps (and its row of the table), and the fused pack's three launches follow.
+// The other forms' device code is instruction for instruction what it was (profiles/dct_pack_quality_c3.txt).
 #include <algorithm>
 #include <type_traits>
 
@@ -69,6 +77,7 @@
 #include "quant_core.hpp"
 #include "stream_format.hpp"
 #include "svc_common.hpp"
+#include "svc_hip_quality.h"
 #include "svc_hip_temporal.h"
 
 namespace svc {
@@ -142,6 +151,20 @@ BudgetWs budget_ws(Carver& c, uint32_t n, const PackGeom& g) {
   return s;
 }
 
+// the quality call's workspace: the budgeted call's (so the fixed and the budgeted call run on it too), then the squared errors
+struct QualityWs {
+  BudgetWs budget;
+  uint64_t* drows;   // [n][waves of a frame][kMaxLadder]: a wave's sum of e^2 per ladder entry (0 from the ladder's end on)
+  uint64_t* dparts;  // [n][kSumParts][kMaxLadder]: the rows of a frame summed part by part
+};
+QualityWs quality_ws(Carver& c, uint32_t n, const PackGeom& g) {
+  QualityWs s;
+  s.budget = budget_ws(c, n, g);
+  s.drows = c.take<uint64_t>((uint64_t)kMaxLadder * n * g.l.tiles_y * g.waves_per_row, false);
+  s.dparts = c.take<uint64_t>((uint64_t)kMaxLadder * n * kSumParts, false);
+  return s;
+}
+
 struct DctPackArgs {
   const uint8_t* bgr;
   uint64_t frame_stride;
@@ -160,6 +183,14 @@ struct CountArgs {
   uint32_t* rows;
 };
 struct NoCountArgs {};
+struct LadderInv {
+  float inv[2][kMaxLadder];  // RN(1 / step), computed on the host as the fixed call computes it
+};
+// what the measuring form takes besides: each entry's RN(1 / step) for the quantiser, and where the waves' rows of squared errors go
+struct MeasureArgs : CountArgs {
+  LadderInv li;
+  uint64_t* drows;
+};
 // what the two-layer form takes besides: the enhancement's step, each class's base step / enh_step, the frames' windows, and the
 // second workspace (a.ws is the base layer's)
 struct LayerArgs {
@@ -198,6 +229,13 @@ constexpr uint32_t kTemporalRun = kDeltaRun % 4 == 0 ? kDeltaRun : 8;
 #define SVC_DCT_PACK_TEMPORAL_REDO 0
 #endif
 constexpr bool kTemporalRedo = SVC_DCT_PACK_TEMPORAL_REDO != 0;
+// The measuring form takes an entry's sum from the entry before where no lane of the wave has another step there.  1: it does; 0: every
+// entry is computed.  Both measured in profiles/dct_pack_quality_c3.txt (tools/dct_pack_probe.py quality-variants builds this file once
+// per value).
+#ifndef SVC_DCT_PACK_MEASURE_SHARE
+#define SVC_DCT_PACK_MEASURE_SHARE 1
+#endif
+constexpr bool kMeasureShare = SVC_DCT_PACK_MEASURE_SHARE != 0;
 constexpr uint32_t kTauTable = 2 * kMaxLadder;  // a class's thresholds, padded with +inf to what 7 probes can reach
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
@@ -246,13 +284,21 @@ __device__ __forceinline__ uint32_t sub2(uint32_t a, uint32_t b) {
 // in front of the run transforms frame run_first - PERIOD, `before` keeps the last frame of layer 0 (2k or 4k: it is replaced only there)
 // and, PERIOD = 4, `mid` keeps frame 4k + 2 for frame 4k + 3.  A run still costs R + 1 transforms.  REDO (PERIOD = 4): no `mid`; `before`
 // takes frame 4k + 2's levels as well, and a trip in front of frame 4k + 4 puts frame 4k's back (kTemporalRedo above).
-template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false, int PERIOD = 1, bool REDO = false>
+// MEASURE = true (with COUNT): the counting form, and per ladder entry k the wave's sum of e^2, e = rint(256 (|c| - q_k s_k)) with q_k the
+// level entry k's step of the lane's class gives (include/svc_hip_quality.h states it, layers.distortion_table in numpy).  The lane keeps
+// |c| of all three channels and, after the last, goes through the ladder once: 48 quantisations per entry, the lanes' u64 sums added over
+// the wave, the total kept by lane k and stored with the wave's row of counts.  An entry at which no lane's step differs from the entry
+// before (a ladder of levels.step_ladder moves one class at a time) takes the sum before it: nothing is computed.  The entry is the same
+// in every lane, so both classes' step and RN(1 / step) are uniform loads from the arguments and the lane selects by its class: no table.
+template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false, int PERIOD = 1, bool REDO = false, bool MEASURE = false>
 __device__ __forceinline__ void dct_pack_body(
     const DctPackArgs& a,
-    const std::conditional_t<COUNT, CountArgs,
+    const std::conditional_t<MEASURE, MeasureArgs,
+    std::conditional_t<COUNT, CountArgs,
                              std::conditional_t<LAYERS, LayerArgs,
-                                                std::conditional_t<TALLY, DeltaTallyArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>>& k,
+                                                std::conditional_t<TALLY, DeltaTallyArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>>>& k,
     float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
+  static_assert(!MEASURE || COUNT, "the measuring form is the counting form with the squared errors");
   static_assert(!(COUNT && LAYERS), "the counting form has no layers");
   static_assert(!(DELTA && (COUNT || LAYERS)), "the delta form is one layer at fixed steps");
   static_assert(!TALLY || DELTA, "the tally walks the delta form's runs");
@@ -298,6 +344,8 @@ __device__ __forceinline__ void dct_pack_body(
   bool redo = false;        // REDO: this trip transforms frame 4k again, in front of frame 4k + 4 (`it` stays at 4k + 3)
   uint32_t t_mid = 0;
   uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
+  float kept[MEASURE ? 3 : 1][16];  // MEASURE: |c| of the lane's coefficients, all three channels, and the lane's class
+  uint32_t cls = 0;
   if constexpr (DELTA) {
     run_first = frame0 * k.run;
     run_len = min(k.run, k.n_frames - run_first);
@@ -448,6 +496,11 @@ __device__ __forceinline__ void dct_pack_body(
         full += e[i] == k.lad.len ? 1u : 0u;
         if (e[i] != 0 && e[i] != k.lad.len) atomicAdd(&hist[e[i] - 1], 1u);
       }
+      if constexpr (MEASURE) {
+        cls = t == 0 ? 0u : 1u;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) kept[c][i] = m[i];
+      }
       continue;  // (the slabs are free for the next channel: the sync above)
     }
     if constexpr (DELTA && PERIOD > 1) {  // the same against the kept frame of the trip's layer; the levels stay where a later frame refers to them
@@ -549,6 +602,34 @@ __device__ __forceinline__ void dct_pack_body(
     redo = again;
   }
   } while (DELTA && ((REDO && redo) || ++it < (int)run_len));
+  if constexpr (MEASURE) {
+    // x = |c| - q s is exact in one fma and 256 x is exact (the header argues both), so e is an integer below 2^21 whatever the order:
+    // e^2 < 2^41, a lane's 48 below 2^47, a wave's below 2^53
+    uint64_t mine = 0, total = 0;  // lane k keeps entry k's total
+    float prev_step = 0.f;         // (no step is 0: the first entry is always computed)
+    for (uint32_t kk = 0; kk < k.lad.len; ++kk) {
+      const float2 si = cls ? make_float2((float)k.lad.step[1][kk], k.li.inv[1][kk]) : make_float2((float)k.lad.step[0][kk], k.li.inv[0][kk]);
+      if (!kMeasureShare || __ballot(si.x != prev_step) != 0) {  // the same in every lane; a lane whose step stayed computes the sum it had
+        uint64_t s = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+          for (int i = 0; i < 16; i += 2) {
+            const f32x2 cf{kept[c][i], kept[c][i + 1]}, q = quant2_level(cf, si.x, si.y);
+            const uint32_t e0 = (uint32_t)fabsf(rintf(256.f * __builtin_fmaf(-q.x, si.x, cf.x)));
+            const uint32_t e1 = (uint32_t)fabsf(rintf(256.f * __builtin_fmaf(-q.y, si.x, cf.y)));
+            s += (uint64_t)e0 * e0;
+            s += (uint64_t)e1 * e1;
+          }
+        }
+        for (uint32_t off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+        total = s;
+      }
+      prev_step = si.x;
+      if (lane == kk) mine = total;
+    }
+    k.drows[(size_t)wv * kMaxLadder + lane] = mine;
+  }
   if constexpr (COUNT) {  // the wave's row: bins 0 .. len - 2 as they are, bin len - 1 = the lanes' full counts
     uint32_t* hist = hist_all[tid >> 6];
     if (full) atomicAdd(&hist[k.lad.len - 1], full);
@@ -632,12 +713,20 @@ __global__ __launch_bounds__(256) void dct_count_kernel(DctPackArgs a, CountArgs
   dct_pack_body<N, true>(a, k, tau_tab, hist_all);
 }
 
+// the counting form with every ladder entry's squared error beside the counts
+template <int N>
+__global__ __launch_bounds__(256) void dct_measure_kernel(DctPackArgs a, MeasureArgs k) {
+  __shared__ float tau_tab[2][kTauTable];
+  __shared__ uint32_t hist_all[kThreads / 64][kMaxLadder];
+  dct_pack_body<N, true, false, false, false, 1, false, true>(a, k, tau_tab, hist_all);
+}
+
 // Column `lane` of rows first, first + step, ... below count, summed over the workgroup's four waves: every thread gets its column's sum
 // (unsigned sums: any order gives the same bytes).
-__device__ __forceinline__ uint32_t sum_rows(const uint32_t* __restrict__ rows, uint32_t first, uint32_t step, uint32_t count,
-                                             uint32_t (*part)[kMaxLadder]) {
+template <typename T>  // u32 counts, u64 squared errors
+__device__ __forceinline__ T sum_rows(const T* __restrict__ rows, uint32_t first, uint32_t step, uint32_t count, T (*part)[kMaxLadder]) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t s = 0;
+  T s = 0;
 #pragma unroll 4
   for (uint32_t r = first + wave * step; r < count; r += (kThreads / 64) * step) s += rows[(size_t)r * kMaxLadder + lane];
   part[wave][lane] = s;
@@ -662,9 +751,6 @@ struct SelectArgs {
   FrameSteps* steps;
   uint32_t* choice;
 };
-struct LadderInv {
-  float inv[2][kMaxLadder];  // RN(1 / step), computed on the host as the fixed call computes it
-};
 
 __global__ __launch_bounds__(256) void dct_pack_select_kernel(Ladder lad, LadderInv li, SelectArgs a) {
   __shared__ uint32_t part[kThreads / 64][kMaxLadder];
@@ -681,6 +767,61 @@ __global__ __launch_bounds__(256) void dct_pack_select_kernel(Ladder lad, Ladder
   if (lane != 0) return;
   const uint32_t ch = budget_choice(bytes, lad.len, a.budget[f]), pick = ch & 0x7FFFFFFFu;
   a.choice[f] = ch;
+  a.steps[f] = FrameSteps{lad.step[1][pick], lad.step[0][pick], li.inv[1][pick], li.inv[0][pick]};
+}
+
+// The quality call's sum: dct_count_sum_kernel on the counts and, in the same launch, on the squared errors.
+__global__ __launch_bounds__(256) void dct_measure_sum_kernel(uint32_t rows_per_frame, const uint32_t* __restrict__ rows, uint32_t* __restrict__ parts,
+                                                              const uint64_t* __restrict__ drows, uint64_t* __restrict__ dparts) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  __shared__ uint64_t dpart[kThreads / 64][kMaxLadder];
+  const uint32_t f = blockIdx.y;
+  const uint32_t v = sum_rows(rows + (size_t)f * rows_per_frame * kMaxLadder, blockIdx.x, kSumParts, rows_per_frame, part);
+  const uint64_t d = sum_rows(drows + (size_t)f * rows_per_frame * kMaxLadder, blockIdx.x, kSumParts, rows_per_frame, dpart);
+  if (threadIdx.x < kMaxLadder) {
+    parts[((size_t)f * kSumParts + blockIdx.x) * kMaxLadder + threadIdx.x] = v;
+    dparts[((size_t)f * kSumParts + blockIdx.x) * kMaxLadder + threadIdx.x] = d;
+  }
+}
+
+// One workgroup per frame: bytes_k as dct_pack_select_kernel has them and D_k = the summed squared errors of entry k; then
+//   kq = the largest k with D_k <= target, 0 where there is none (D is not monotone along a ladder);
+//   kb = budget_choice on bytes_k, 0 without a budget;
+//   choice = max(kq, kb), bit 31 as kb has it, bit 30 where D[choice] > target;
+// the chosen pair's steps, and the frame's row of the table where asked.
+struct QualitySelectArgs {
+  uint64_t levels_off;
+  const uint32_t* parts;
+  const uint64_t* dparts;
+  const uint64_t* target;
+  const uint32_t* budget;  // or null
+  FrameSteps* steps;
+  uint32_t* choice;
+  uint64_t* distortion;    // [n][len] or null
+};
+__global__ __launch_bounds__(256) void dct_quality_select_kernel(Ladder lad, LadderInv li, QualitySelectArgs a) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  __shared__ uint64_t dpart[kThreads / 64][kMaxLadder];
+  __shared__ uint64_t bytes[kMaxLadder], dist[kMaxLadder];
+  const uint32_t f = blockIdx.x, lane = threadIdx.x & 63u;
+  uint32_t nz = sum_rows(a.parts + (size_t)f * kSumParts * kMaxLadder, 0, 1, kSumParts, part);
+  const uint64_t d = sum_rows(a.dparts + (size_t)f * kSumParts * kMaxLadder, 0, 1, kSumParts, dpart);
+  if (threadIdx.x >= 64) return;
+  for (uint32_t off = 1; off < 64; off <<= 1) {  // inclusive suffix sum over the lanes
+    const uint32_t up = __shfl_down(nz, off, 64);
+    if (lane + off < 64) nz += up;
+  }
+  bytes[lane] = up16(a.levels_off + 2ull * nz);
+  dist[lane] = d;
+  if (a.distortion && lane < lad.len) a.distortion[(size_t)f * lad.len + lane] = d;
+  wave_lds_sync();
+  if (lane != 0) return;
+  const uint64_t target = a.target[f];
+  const uint32_t kb = a.budget ? budget_choice(bytes, lad.len, a.budget[f]) : 0u;
+  uint32_t kq = 0;
+  for (uint32_t i = 0; i < lad.len; ++i) kq = dist[i] <= target ? i : kq;
+  const uint32_t pick = max(kq, kb & 0x7FFFFFFFu);
+  a.choice[f] = pick | (kb & 0x80000000u) | (dist[pick] > target ? 0x40000000u : 0u);
   a.steps[f] = FrameSteps{lad.step[1][pick], lad.step[0][pick], li.inv[1][pick], li.inv[0][pick]};
 }
 
@@ -1196,6 +1337,78 @@ int svc_hip_dct_pack_levels_budget_frames(const uint8_t* d_bgr, uint64_t frame_s
   hipLaunchKernelGGL(dct_pack_select_kernel, dim3(n_frames), blk, 0, s, k.lad, li, sel);
   if ((rc = check_launch("dct_pack_levels_budget", "select"))) return rc;
   return enqueue_dct_pack("dct_pack_levels_budget", a, n_frames, 0, 0, d_out, d_frame_offsets, s);
+}
+
+// ---- a quality target in place of the byte budget, or beside it (include/svc_hip_quality.h)
+
+uint64_t svc_hip_dct_pack_levels_quality_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                                         uint32_t mv_block_w, uint32_t mv_block_h, uint32_t ladder_len) {
+  const char* what = "dct_pack_levels_quality_workspace_bytes";
+  if (validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  if (ladder_len == 0 || ladder_len > kMaxLadder) {
+    (void)fail(SVC_ERR_INVALID_ARG, "%s: a ladder of %u entries (1 .. %u)", what, ladder_len, kMaxLadder);
+    return 0;
+  }
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits(what, n_frames, g)) return 0;
+  return layout_bytes(quality_ws, n_frames, g);
+}
+
+// Checked in the order of svc_hip_dct_pack_levels_budget_frames: geometry, stride, ladder, limits (which bound a frame's coefficients
+// below 2^31: the u64 sums cannot overflow), sizes; n_frames == 0 then returns SVC_OK; then pointers.  Six launches whatever n_frames.
+int svc_hip_dct_pack_levels_quality_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                           uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                           uint32_t mv_block_h, const svc_step_pair* ladder, uint32_t ladder_len, const uint64_t* d_target,
+                                           const uint32_t* d_budget, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
+                                           uint64_t out_capacity, uint64_t* d_frame_offsets, uint32_t* d_choice, uint64_t* d_distortion,
+                                           void* stream) {
+  const char* what = "dct_pack_levels_quality";
+  int rc = validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "%s: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", what, (unsigned long long)frame_stride_bytes,
+              3ull * frame_w * frame_h);
+  if ((rc = validate_ladder(what, ladder, ladder_len))) return rc;
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits(what, n_frames, g))) return rc;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(quality_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity(what, "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_target && d_workspace && d_out && d_frame_offsets && d_choice, "%s: null pointer", what);
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_target, 8) &&
+                  aligned(d_distortion, 8) && aligned(d_block_types, 4) && aligned(d_budget, 4) && aligned(d_choice, 4),
+              "%s: frames, output and workspace must be 16-byte aligned, offsets, target and distortion 8-byte, types, budget and choice 4-byte",
+              what);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const QualityWs qws = carve(d_workspace, quality_ws, n_frames, g);
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.total_waves = n_frames * g.l.tiles_y * g.waves_per_row;
+  a.types = d_block_types;
+  a.steps = qws.budget.steps;
+  a.ws = qws.budget.pack;
+  MeasureArgs k{};
+  k.lad = make_ladder(ladder, ladder_len);
+  while ((ladder_len >> k.probes) != 0) ++k.probes;
+  k.rows = qws.budget.rows;
+  for (uint32_t i = 0; i < ladder_len; ++i) {
+    k.li.inv[0][i] = 1.0f / (float)ladder[i].bg_step;
+    k.li.inv[1][i] = 1.0f / (float)ladder[i].fg_step;
+  }
+  k.drows = qws.drows;
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (block == 8) hipLaunchKernelGGL(dct_measure_kernel<8>, grid, blk, 0, s, a, k);
+  else hipLaunchKernelGGL(dct_measure_kernel<16>, grid, blk, 0, s, a, k);
+  if ((rc = check_launch(what, "measure"))) return rc;
+  hipLaunchKernelGGL(dct_measure_sum_kernel, dim3(kSumParts, n_frames), blk, 0, s, g.l.tiles_y * g.waves_per_row, qws.budget.rows,
+                     qws.budget.parts, qws.drows, qws.dparts);
+  if ((rc = check_launch(what, "sum"))) return rc;
+  const QualitySelectArgs sel{g.l.levels_off, qws.budget.parts, qws.dparts, d_target, d_budget, qws.budget.steps, d_choice, d_distortion};
+  hipLaunchKernelGGL(dct_quality_select_kernel, dim3(n_frames), blk, 0, s, k.lad, k.li, sel);
+  if ((rc = check_launch(what, "select"))) return rc;
+  return enqueue_dct_pack(what, a, n_frames, 0, 0, d_out, d_frame_offsets, s);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "encode_geometry.hpp"
 #include "hip_raii.hpp"
 #include "svc_clip.h"
+#include "svc_hip_quality.h"
 
 namespace svc {
 namespace {
@@ -92,6 +93,14 @@ struct ClipEncoder::Impl : EncodeGeometry {
   // then the budgeted call's workspace, which holds the fixed call's
   std::vector<svc_step_pair> budget_ladder;
   DevBuf<uint32_t> compact_budget, compact_choice;
+  // SetCompactQuality: the ladder is budget_ladder and `quality` says that a target chooses (the two settings exclude each other);
+  // every frame's target, the newest step's table [pairs][ladder entries] and, gathered when read, each frame's chosen entry of it;
+  // compact_ws is then the quality call's workspace, which holds the budgeted call's.  quality_cap: compact_budget holds a byte cap.
+  // table_steps: steps submitted under the current target (0: compact_table and compact_choice are an earlier setting's, of another ladder
+  // length, and nothing is read from them); dist_of: table_steps when compact_dist was last gathered (a read gathers once per step)
+  bool quality = false, quality_cap = false;
+  uint64_t table_steps = 0, dist_of = 0;
+  DevBuf<uint64_t> compact_target, compact_table, compact_dist;
   Event e_pyr[2], e_halo[2], e_fork, e_join[kSets], e_rfork, e_rmse[kSets];
   bool halo_recorded[2] = {false, false}, join_pending[kSets] = {}, rmse_pending[kSets] = {};
   // Co-run (one rank, pipelined; off with pyramid_on_main): the pyramid levels of a micro-step that reads its frames once run on the
@@ -455,7 +464,14 @@ struct ClipEncoder::Impl : EncodeGeometry {
     Run(Stage::kTransform, st, timing, [&] {
       // records carry RAW coefficients, as the reference's encoder serialises them (libs/encoder.cpp:638-650:
       // the decoder picks the step per tile, libs/decoder.cpp:130-135); planes carry the quantised ones
-      if (c.compact && !budget_ladder.empty())  // ... with each frame's steps from its byte budget (SetCompactBudget)
+      if (c.compact && !budget_ladder.empty() && quality) {  // ... with each frame's steps from its distortion target (SetCompactQuality)
+        ++table_steps;
+        Abi(svc_hip_dct_pack_levels_quality_frames(enc, frame_bytes, pn, pw, ph, c.dct_block_w, types_c, c.mv_block, c.mv_block,
+                                                   budget_ladder.data(), (uint32_t)budget_ladder.size(), compact_target.p,
+                                                   quality_cap ? compact_budget.p : nullptr, compact_ws.p, compact_ws.bytes(), compact.p,
+                                                   compact.bytes(), compact_off.p, compact_choice.p, compact_table.p, st),
+            "svc_hip_dct_pack_levels_quality_frames");
+      } else if (c.compact && !budget_ladder.empty())  // ... with each frame's steps from its byte budget (SetCompactBudget)
         Abi(svc_hip_dct_pack_levels_budget_frames(enc, frame_bytes, pn, pw, ph, c.dct_block_w, types_c, c.mv_block, c.mv_block,
                                                   budget_ladder.data(), (uint32_t)budget_ladder.size(), compact_budget.p, compact_ws.p,
                                                   compact_ws.bytes(), compact.p, compact.bytes(), compact_off.p, compact_choice.p, st),
@@ -841,7 +857,7 @@ void ClipEncoder::SetCompactBudget(const svc_step_pair* ladder, uint32_t ladder_
   Impl& m = *p_;
   const ClipEncoderConfig& c = m.c;
   if (!c.compact) throw std::runtime_error("svc::ClipEncoder: a byte budget is a setting of the compact stream (compact)");
-  if (ladder_len == 0) { m.budget_ladder.clear(); return; }
+  if (ladder_len == 0) { m.budget_ladder.clear(); m.quality = false; m.table_steps = m.dist_of = 0; return; }
   const uint32_t P = m.sh.pairs;
   // the budgeted call's checks that need neither a device pointer nor a size: geometry, stride, the ladder, limits
   Abi(svc_hip_dct_pack_levels_budget_frames(nullptr, m.frame_bytes, 0, m.pw, m.ph, c.dct_block_w, nullptr, c.mv_block, c.mv_block, ladder, ladder_len,
@@ -856,6 +872,41 @@ void ClipEncoder::SetCompactBudget(const svc_step_pair* ladder, uint32_t ladder_
   const std::vector<uint32_t> b(std::max(P, 1u), bytes_per_frame);
   Hip(hipMemcpy(m.compact_budget.p, b.data(), b.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy");
   m.budget_ladder.assign(ladder, ladder + ladder_len);
+  m.quality = false;  // a budget replaces a target
+  m.table_steps = m.dist_of = 0;
+}
+
+void ClipEncoder::SetCompactQuality(const svc_step_pair* ladder, uint32_t ladder_len, uint64_t target, uint32_t bytes_cap) {
+  Sync();  // the steps in flight keep the steps they were submitted with
+  Impl& m = *p_;
+  const ClipEncoderConfig& c = m.c;
+  if (!c.compact) throw std::runtime_error("svc::ClipEncoder: a quality target is a setting of the compact stream (compact)");
+  if (ladder_len == 0) { m.budget_ladder.clear(); m.quality = false; m.table_steps = m.dist_of = 0; return; }
+  const uint32_t P = m.sh.pairs;
+  // the quality call's checks that need neither a device pointer nor a size: geometry, stride, the ladder, limits
+  Abi(svc_hip_dct_pack_levels_quality_frames(nullptr, m.frame_bytes, 0, m.pw, m.ph, c.dct_block_w, nullptr, c.mv_block, c.mv_block, ladder, ladder_len,
+                                             nullptr, nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr, nullptr, nullptr, nullptr),
+      "svc_hip_dct_pack_levels_quality_frames");
+  if (!m.compact_target.p) {  // once: the larger workspace, a target, a cap, a choice, a row of the table and a chosen distortion per pair
+    m.compact_ws.Alloc(kWho, svc_hip_dct_pack_levels_quality_workspace_bytes(P, m.pw, m.ph, c.dct_block_w, c.mv_block, c.mv_block, 64));
+    m.compact_target.Alloc(kWho, std::max(P, 1u));
+    m.compact_table.Alloc(kWho, 64 * (size_t)std::max(P, 1u));
+    m.compact_dist.Alloc(kWho, std::max(P, 1u));
+    if (!m.compact_budget.p) {
+      m.compact_budget.Alloc(kWho, std::max(P, 1u));
+      m.compact_choice.Alloc(kWho, std::max(P, 1u));
+      Hip(hipMemset(m.compact_choice.p, 0, m.compact_choice.bytes()), "hipMemset");
+    }
+    Hip(hipMemset(m.compact_table.p, 0, m.compact_table.bytes()), "hipMemset");
+  }
+  const std::vector<uint64_t> t(std::max(P, 1u), target);
+  Hip(hipMemcpy(m.compact_target.p, t.data(), t.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy");
+  const std::vector<uint32_t> b(std::max(P, 1u), bytes_cap);
+  Hip(hipMemcpy(m.compact_budget.p, b.data(), b.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy");
+  m.budget_ladder.assign(ladder, ladder + ladder_len);
+  m.quality = true;  // a target replaces a budget
+  m.table_steps = m.dist_of = 0;  // what the table and the choices hold is another setting's until a step under this one has run
+  m.quality_cap = bytes_cap != 0;
 }
 
 void ClipEncoder::Flush() {
@@ -923,6 +974,22 @@ void* ClipEncoder::Output(Buffer b, uint64_t* bytes) {
       ptr = m.compact_choice.p;
       n = m.budget_ladder.empty() ? 0 : (uint64_t)m.sh.pairs * sizeof(uint32_t);
       break;
+    case Buffer::kCompactDistortion: {  // nothing until a step under the current target has finished; then each frame's entry of that
+      // step's table, gathered once per step (table and choices were written with this ladder's length: table_steps is not 0)
+      ptr = m.compact_dist.p;
+      n = m.quality && !m.budget_ladder.empty() && m.table_steps ? (uint64_t)m.sh.pairs * sizeof(uint64_t) : 0;
+      if (n && m.dist_of != m.table_steps) {
+        const uint32_t P = m.sh.pairs, K = (uint32_t)m.budget_ladder.size();
+        std::vector<uint64_t> table((size_t)P * K), dist(P);
+        std::vector<uint32_t> choice(P);
+        Hip(hipMemcpy(table.data(), m.compact_table.p, table.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+        Hip(hipMemcpy(choice.data(), m.compact_choice.p, P * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy");
+        for (uint32_t f = 0; f < P; ++f) dist[f] = table[(size_t)f * K + std::min(choice[f] & 0x3FFFFFFFu, K - 1)];
+        Hip(hipMemcpy(m.compact_dist.p, dist.data(), P * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy");
+        m.dist_of = m.table_steps;
+      }
+      break;
+    }
     default: throw std::runtime_error("svc::ClipEncoder: unknown buffer");
   }
   if (bytes) *bytes = n;
@@ -1065,6 +1132,10 @@ int svc_clip_step_frames(svc_clip* clip, const uint8_t* device_frames, int timed
 int svc_clip_wait_step(svc_clip* clip, uint32_t step) { return Guard([&] { clip->enc->WaitStep(step); }); }
 int svc_clip_set_compact_budget(svc_clip* clip, const svc_step_pair* ladder, uint32_t ladder_len, uint32_t bytes_per_frame) {
   return Guard([&] { clip->enc->SetCompactBudget(ladder, ladder_len, bytes_per_frame); });
+}
+
+int svc_clip_set_compact_quality(svc_clip* clip, const svc_step_pair* ladder, uint32_t ladder_len, uint64_t target, uint32_t bytes_cap) {
+  return Guard([&] { clip->enc->SetCompactQuality(ladder, ladder_len, target, bytes_cap); });
 }
 int svc_clip_flush(svc_clip* clip) { return Guard([&] { clip->enc->Flush(); }); }
 int svc_clip_sync(svc_clip* clip) { return Guard([&] { clip->enc->Sync(); }); }

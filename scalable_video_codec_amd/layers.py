@@ -34,7 +34,10 @@ encoder's own; for even r a level that is an odd multiple of r / 2 is a tie the 
 differs from a direct encode there.
 
 pack_layers_frames states svc_hip_pack_layers_frames: both layers from raw coefficient planes, each level quantised from the coefficient
-itself, so the base is the direct encode for any ratio."""
+itself, so the base is the direct encode for any ratio.
+
+distortion_table / quality_choice / distortion_target / distortion_psnr state svc_hip_dct_pack_levels_quality_frames
+(include/svc_hip_quality.h): the squared error every ladder entry would leave, in integers, and the per-frame choice by it."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple
@@ -665,6 +668,81 @@ def quantise(planes: np.ndarray, step) -> np.ndarray:
     the f32 quotient plus or minus a half is exact in f64), then clamped to int16.  step: an integer, or an array that broadcasts."""
     q = (np.asarray(planes, np.float32) / np.asarray(step).astype(np.float32)).astype(np.float64)
     return np.clip(np.trunc(q + np.copysign(0.5, q)), -32768, 32767).astype(np.int64)
+
+
+# ---- a quality target for the fused pack (include/svc_hip_quality.h: svc_hip_dct_pack_levels_quality_frames) -------------------------
+
+def quantisation_error(planes: np.ndarray, step) -> np.ndarray:
+    """x = c - quantise(c, step) * step per coefficient, in f64: c is an f32 and the product an integer below 2^24, so the difference is
+    exact there.  (It is representable in f32 as well -- q == 0 gives c itself, otherwise x is a multiple of ulp(c) no larger than about
+    step / 2 <= |c| -- which is why the kernel's one f32 fma gives the same number; tests/test_quality_host.py checks it.)"""
+    c = np.asarray(planes, np.float32).astype(np.float64)
+    return c - (quantise(planes, step) * np.asarray(step).astype(np.int64)).astype(np.float64)
+
+
+def distortion_table(planes, types, geometry: Dict[str, int], ladder) -> np.ndarray:
+    """D (n, K) u64 of svc_hip_dct_pack_levels_quality_frames.  planes: raw coefficients (n, 3, H, W) f32, what svc_hip_dct_frames writes;
+    types: region ids (n, MV rows, MV columns) or (n, MV blocks); geometry: a dict with the keys of GEOMETRY; ladder: K pairs
+    (fg_step, bg_step).  Per coefficient c and entry k, with s the step of c's tile (bg_step where the MV block holding the tile has type
+    0): e = rint(256 * (c - quantise(c, s) * s)), half to even, an integer; D[f][k] = the sum of e * e over the frame's three planes.
+    D / 65536 is the squared error of the dequantised coefficients and, the transform being orthonormal, of the unclipped picture."""
+    w, h = geometry["frame_w"], geometry["frame_h"]
+    planes = np.asarray(planes, np.float32).reshape(-1, 3, h, w)
+    n = planes.shape[0]
+    types = np.asarray(types).astype(np.uint32).reshape(n, h // geometry["mv_block_h"], w // geometry["mv_block_w"])
+    lad = [(int(fg), int(bg)) for fg, bg in ladder]
+    table = np.zeros((n, len(lad)), np.uint64)
+    for f in range(n):
+        background = _per_pixel(geometry, _tile_maps(geometry, types[f])[0])[None]
+        for k, (fg, bg) in enumerate(lad):
+            e = np.rint(256.0 * quantisation_error(planes[f], np.where(background, bg, fg))).astype(np.int64)
+            table[f, k] = int((e * e).sum(dtype=np.int64))  # < 2^32 per coefficient on average: below 2^63 for any frame the call takes
+    return table
+
+
+def quality_choice(table, sizes, targets, budgets=None) -> np.ndarray:
+    """choice (n,) u32 of svc_hip_dct_pack_levels_quality_frames.  table: D (n, K); sizes: bytes_k (n, K), the SVCQ frame's size at every
+    entry; targets: one u64 for every frame, or one each; budgets: None (no cap), or u32 bytes likewise.
+      kq = the largest k with D[k] <= target, 0 where no entry meets it (D is not monotone along a ladder);
+      kb = the budgeted calls' choice -- the smallest k with bytes_k <= budget, else K - 1 with bit 31 set; 0 without budgets;
+      choice = max(kq, kb & 0x7FFFFFFF), bit 31 as kb has it, bit 30 set exactly when D[choice] > target."""
+    table = np.asarray(table, np.uint64)
+    n, K = table.shape
+    sizes = np.asarray(sizes).reshape(n, K)
+    target = np.broadcast_to(np.asarray(targets, np.uint64), (n,))
+    budget = None if budgets is None else np.broadcast_to(np.asarray(budgets, np.int64), (n,))
+    choice = np.zeros(n, np.uint32)
+    for f in range(n):
+        met = [k for k in range(K) if int(table[f, k]) <= int(target[f])]
+        kq = met[-1] if met else 0
+        kb, over = 0, 0
+        if budget is not None:
+            fits = [k for k in range(K) if int(sizes[f, k]) <= int(budget[f])]
+            kb, over = (fits[0], 0) if fits else (K - 1, 0x80000000)
+        pick = max(kq, kb)
+        choice[f] = pick | over | (0x40000000 if int(table[f, pick]) > int(target[f]) else 0)
+    return choice
+
+
+def _psnr_scale(w: int, h: int) -> int:
+    return 255 * 255 * 3 * int(w) * int(h) * 65536
+
+
+def distortion_target(psnr_db, w: int, h: int) -> int:
+    """The largest D that still reaches psnr_db on a w x h frame: floor(255^2 * 3 w h * 65536 / 10^(psnr_db / 10)), in decimal
+    arithmetic of 60 digits (an f64 quotient is off by thousands of units at these magnitudes), capped at 2^64 - 1."""
+    import decimal
+    with decimal.localcontext() as ctx:
+        ctx.prec = 60
+        d = decimal.Decimal(_psnr_scale(w, h)) / (decimal.Decimal(10) ** (decimal.Decimal(psnr_db) / 10))
+        return min(int(d.to_integral_value(rounding=decimal.ROUND_FLOOR)), 2 ** 64 - 1)
+
+
+def distortion_psnr(d, w: int, h: int) -> float:
+    """The PSNR in dB a distortion D stands for on a w x h frame, 10 log10(255^2 * 3 w h * 65536 / D); inf for D = 0."""
+    import math
+    d = int(d)
+    return math.inf if d == 0 else 10.0 * math.log10(_psnr_scale(w, h) / d)
 
 
 def pack_layers_frames(planes, types, geometry: Dict[str, int], fg_step: int, bg_step: int, enh_step: int, windows=None

@@ -239,6 +239,15 @@ SIGNATURES_TEMPORAL_DECODE = {
                                                             [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _u32]),
 }
 
+# The calls of include/svc_hip_quality.h: a table of its own for the same reason; load() applies all four.
+SIGNATURES_QUALITY = {
+    # the fused pack with a distortion target per frame, optionally capped by a byte budget (csrc/dct_pack.hip; host statements:
+    # layers.distortion_table, layers.quality_choice)
+    "svc_hip_dct_pack_levels_quality_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_dct_pack_levels_quality_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 2 + [C.POINTER(StepPair), _u32, _vp, _vp, _vp,
+                                                         _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -251,7 +260,8 @@ def load() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m scalable_video_codec_amd.build` "
                 "(or __graft_entry__.build()); the MI355X path has no CPU fallback")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TEMPORAL.items()) + list(SIGNATURES_TEMPORAL_DECODE.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_TEMPORAL.items()) + list(SIGNATURES_TEMPORAL_DECODE.items()) +
+                                  list(SIGNATURES_QUALITY.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -1090,6 +1100,54 @@ def dct_pack_levels_budget_frames(bgr: torch.Tensor, block: int, block_types: to
                                                         _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8),
                                                         out.numel(), _dev(offsets, torch.int64), _dev(choice, torch.int32), _stream()))
     return out, offsets, choice
+
+
+def dct_pack_levels_quality_workspace_bytes(n: int, w: int, h: int, block: int, mv_block, ladder_len: int) -> int:
+    """Scratch of dct_pack_levels_quality_frames; 0 for a geometry or a ladder length it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_levels_quality_workspace_bytes(n, w, h, block, mbw, mbh, ladder_len))
+
+
+def target_tensor(target, n: int, device) -> torch.Tensor:
+    """A distortion target (one int for every frame, or one per frame; layers.distortion_target gives it for a PSNR) -> (n,) i64 on the
+    device holding the u64 values."""
+    import numpy as np
+    t = [int(v) for v in np.broadcast_to(np.asarray(target, object), (n,))]
+    if any(v < 0 or v > 0xFFFFFFFFFFFFFFFF for v in t):
+        raise ValueError("a distortion target is a u64")
+    return torch.from_numpy(np.array(t, np.uint64).view(np.int64).copy()).to(device)
+
+
+def dct_pack_levels_quality_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, ladder, target, budget=None,
+                                   out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, distortion: bool = False):
+    """B,G,R frames (frames, H, W, 3) u8 + region ids -> each frame packed with the coarsest ladder entry whose squared error still meets
+    its distortion target, not finer than its byte budget allows (include/svc_hip_quality.h; layers.distortion_table and
+    layers.quality_choice state it).  target: an int, one per frame, or an (frames,) i64 device tensor of u64 values; budget: None (no
+    cap), or as dct_pack_levels_budget_frames takes it.  -> (stream u8 of the worst-case size, offsets (frames + 1,) i64, choice
+    (frames,) i32 on the device: the entry's index, bit 31 over budget, bit 30 target not met[, the table (frames, K) i64 holding u64
+    values, with distortion=True])."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    arr, k = _ladder(ladder)
+    dev = bgr.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_levels_quality_workspace_bytes(n, w, h, block, mv_block, k), 16), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    choice = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    table = torch.empty((max(n, 1), max(k, 1)), dtype=torch.int64, device=dev)[:n] if distortion else None
+    if not (isinstance(target, torch.Tensor) and target.is_cuda):
+        target = target_tensor(target, n, dev)
+    if budget is not None and not (isinstance(budget, torch.Tensor) and budget.is_cuda):
+        budget = budget_tensor(budget, n, dev)
+    _check(load().svc_hip_dct_pack_levels_quality_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                         _dev(block_types, torch.int32), mbw, mbh, arr, k, _dev(target, torch.int64),
+                                                         None if budget is None else _dev(budget, torch.int32),
+                                                         _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8),
+                                                         out.numel(), _dev(offsets, torch.int64), _dev(choice, torch.int32),
+                                                         None if table is None else _dev(table, torch.int64), _stream()))
+    return (out, offsets, choice, table) if distortion else (out, offsets, choice)
 
 
 def unpack_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block,

@@ -14,6 +14,18 @@
                                                    1.1 MB per 1080p frame (scaled by the pixels at C5); the planes route (svc_hip_dct_frames +
                                                    svc_hip_pack_levels_budget_frames) 5 times, then svc_hip_dct_pack_levels_budget_frames 5
                                                    times; stream, offsets and choices are compared.  Run under rocprofv3 as `kernels`
+  python tools/dct_pack_probe.py quality [C3|C5]   constant quality: the same batch and ladder, svc_hip_dct_pack_levels_quality_frames at a 40 dB
+                                                   and a 30 dB target against (a) svc_hip_dct_pack_levels_budget_frames and (b) per entry the
+                                                   fixed fused pack + svc_hip_decode_levels_frames + a torch squared error; one process, the
+                                                   routes in turn, the median of three rounds; then entries, PSNR and bytes (raw and
+                                                   entropy-coded) at both targets on the synthetic clip and on a static background
+  python tools/dct_pack_probe.py quality-kernels [C3|C5]
+                                                   the quality call and the budgeted call five times each and nothing else: for a kernel trace
+  python tools/dct_pack_probe.py quality-variants [C3|C5]
+                                                   the quality call against a build of csrc/dct_pack.hip that computes every ladder entry
+                                                   (SVC_DCT_PACK_MEASURE_SHARE=0), on the 32-entry ladder and on one whose every entry moves both steps
+  python tools/dct_pack_probe.py quality_step [C3|C5] [frames]
+                                                   svc::ClipEncoder compact steps: fixed, under the budget, at a 40 dB target (SetCompactQuality)
   python tools/dct_pack_probe.py budget_step [C3|C5] [frames]
                                                    svc::ClipEncoder with compact: the step at the fixed steps against the step under that
                                                    budget (SetCompactBudget), serial and pipelined; wall time per step
@@ -236,6 +248,186 @@ def budget_step(cfg, frames_n) -> None:
               f"{fixed_ms[0]:.3f} .. {fixed_ms[1]:.3f}; under a budget of {per_frame} B per frame {budget_ms[0]:.3f} .. {budget_ms[1]:.3f} "
               f"({budget_ms[0] / fixed_ms[0]:.2f}x; entries {int((ch & 0x7FFFFFFF).min())} .. {int((ch & 0x7FFFFFFF).max())}, over budget "
               f"{int((ch >> 31).sum())}); fixed again {again_ms[0]:.3f} .. {again_ms[1]:.3f}", flush=True)
+
+
+def _still(bgr, types, pw, ph, mv):
+    """delta_encode_sizes' static background (the first frame, repeated) under a moving 128 x 128 patch of the clip, foreground under it."""
+    n = bgr.shape[0]
+    mbw, mbh = native._bwbh(mv)
+    still = bgr[:1].expand(n, ph, pw, 3).clone()
+    still_types = torch.zeros_like(types).view(n, ph // mbh, pw // mbw)
+    for f in range(n):
+        x, y = 256 + 48 * f, 192 + 16 * f
+        still[f, y:y + 128, x:x + 128] = bgr[f, y:y + 128, x:x + 128]
+        still_types[f, y // mbh:(y + 128) // mbh, x // mbw:(x + 128) // mbw] = 1
+    return still, still_types.reshape(n, -1).contiguous()
+
+
+def quality(cfg, kernels_only=False) -> None:
+    """The quality call at 40 dB and 30 dB against (a) the budgeted call with the same ladder and (b) the route a caller had before it: per
+    entry the fixed fused pack, svc_hip_decode_levels_frames and a torch squared error.  One process, the routes in turn, the median of
+    three rounds.  Then what the targets give on the synthetic clip and on the static background.  kernels_only: each call five times and
+    nothing else, for a kernel trace."""
+    from scalable_video_codec_amd import layers as lay
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    lad, per_frame = _budget(cfg)
+    t40, t30 = (native.target_tensor(lay.distortion_target(db, pw, ph), n, dev) for db in (40.0, 30.0))
+    b = native.budget_tensor(per_frame, n, dev)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out, out2 = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2))
+    wsq = torch.empty(native.dct_pack_levels_quality_workspace_bytes(n, pw, ph, block, mv, len(lad)), dtype=torch.uint8, device=dev)
+    wsb = torch.empty(native.dct_pack_levels_budget_workspace_bytes(n, pw, ph, block, mv, len(lad)), dtype=torch.uint8, device=dev)
+    wsd = torch.empty(native.decode_levels_workspace_bytes(n, pw, ph, block), dtype=torch.uint8, device=dev)
+    rec = torch.empty((n, ph, pw, 3), dtype=torch.float32, device=dev)
+    src = bgr.float()
+
+    def q40():
+        return native.dct_pack_levels_quality_frames(bgr, block, types, mv, lad, t40, out=out, workspace=wsq)
+
+    def q30():
+        return native.dct_pack_levels_quality_frames(bgr, block, types, mv, lad, t30, out=out, workspace=wsq)
+
+    def q40_cap_table():
+        return native.dct_pack_levels_quality_frames(bgr, block, types, mv, lad, t40, b, out=out, workspace=wsq, distortion=True)
+
+    def budgeted():
+        return native.dct_pack_levels_budget_frames(bgr, block, types, mv, lad, b, out=out, workspace=wsb)
+
+    def before():  # per entry: encode, decode, compare pixels -> the table a caller had to make by hand (its units: squared pixel error)
+        sse = []
+        for fg, bg in lad:
+            s, so = native.dct_pack_levels_frames(bgr, block, types, mv, int(fg), int(bg), out=out2, workspace=wsb)
+            native.decode_levels_frames(s, so, pw, ph, block, mv, int(fg), int(bg), rec=rec, workspace=wsd)
+            sse.append(((rec - src) ** 2).sum(dim=(1, 2, 3)))
+        return torch.stack(sse, 1)
+
+    if kernels_only:
+        for fn in (q40, budgeted):
+            for _ in range(5):
+                fn()
+        sync()
+        return
+    ms = _median3([q40, q30, q40_cap_table, budgeted], sync, steps=20)
+    ms_before = _median3([before], sync, steps=2)[0]
+    print(f"{cfg.name} batch of {n}, {len(lad)} entries, ms per call (median of 3 rounds of 20 back-to-back calls, the routes in turn): quality "
+          f"call at 40 dB {ms[0]:.3f}, at 30 dB {ms[1]:.3f}, at 40 dB with a cap of {per_frame} B and the table {ms[2]:.3f}; (a) the budgeted call "
+          f"{ms[3]:.3f} ({ms[0] / ms[3]:.2f}x: the price of measuring instead of counting); (b) {len(lad)} x (fixed fused pack + decode + torch "
+          f"squared error) {ms_before:.3f} ({ms_before / ms[0]:.1f}x the quality call; 2 calls a round); quality workspace "
+          f"{wsq.numel() / n / 1e6:.2f} MB per frame against {wsb.numel() / n / 1e6:.2f}", flush=True)
+    # the table against route (b)'s, the scale check at full size
+    _, _, _, table = q40_cap_table()
+    by_hand = before()
+    sync()
+    d = table.cpu().numpy().view("uint64").astype("float64") / 65536.0
+    rel = abs(d - by_hand.double().cpu().numpy()) / by_hand.double().cpu().numpy().clip(min=1.0)
+    print(f"  the call's table / 65536 against route (b)'s squared pixel errors (f32 sums of the clipped-free f32 reconstruction): worst relative "
+          f"difference {rel.max():.2e}", flush=True)
+
+    def coded_bytes(stream, so):
+        _, eo, est = native.entropy_encode_frames(stream, so, pw, ph, block, mv)
+        sync()
+        assert not est.any()
+        return int(eo[-1])
+
+    still, still_types = _still(bgr, types, pw, ph, mv)
+    for clip_name, frames, ty in (("the synthetic clip", bgr, types), ("a static background under a moving 128 x 128 patch", still, still_types)):
+        for db, t in ((40.0, t40), (30.0, t30)):
+            s, so, ch, tab = native.dct_pack_levels_quality_frames(frames, block, ty, mv, lad, t, distortion=True)
+            sync()
+            ch, tab = ch.cpu().numpy().view("uint32"), tab.cpu().numpy().view("uint64")
+            picks = [int(c) & 0x3FFFFFFF for c in ch]
+            psnr = [lay.distortion_psnr(tab[f, k], pw, ph) for f, k in enumerate(picks)]
+            raw = int(so[-1])
+            print(f"  {clip_name} at {db:g} dB: entries {min(picks)} .. {max(picks)} (steps {tuple(int(v) for v in lad[min(picks)])} .. "
+                  f"{tuple(int(v) for v in lad[max(picks)])}), target not met in {int(((ch >> 30) & 1).sum())} frames, PSNR reached "
+                  f"{min(psnr):.2f} .. {max(psnr):.2f} dB, {raw / n / 1e6:.4f} MB per frame raw, {coded_bytes(s[:raw], so) / n / 1e6:.4f} "
+                  f"entropy-coded", flush=True)
+
+
+def _measure_variant_lib(share):
+    """csrc/dct_pack.hip built with the other form of the measuring loop (SVC_DCT_PACK_MEASURE_SHARE), as _delta_run_lib builds its runs."""
+    import ctypes
+    import subprocess
+    from scalable_video_codec_amd import build
+    out = os.path.join(ROOT, "tools", "_bin", f"libsvc_dct_pack_measure_share{share}.so")
+    if not os.path.exists(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call([build._hipcc(), *build.HIPCC_FLAGS, f"-DSVC_DCT_PACK_MEASURE_SHARE={share}", "-shared", "-o", out,
+                               os.path.join(build.CSRC, "dct_pack.hip"), f"-L{build.PKG}", "-lsvc_hip", f"-Wl,-rpath,{build.PKG}"])
+    native.load()  # (first: the variant resolves the shared helpers in it)
+    fn = ctypes.CDLL(out).svc_hip_dct_pack_levels_quality_frames
+    fn.restype, fn.argtypes = native.SIGNATURES_QUALITY["svc_hip_dct_pack_levels_quality_frames"]
+    return fn
+
+
+def quality_variants(cfg) -> None:
+    """The quality call as built against the build that computes every ladder entry, with the 32-entry ladder (11 background steps, then 21
+    foreground steps) and with 32 entries that all differ in both classes; same tables and bytes."""
+    from scalable_video_codec_amd import layers as lay
+    dev = torch.device("cuda")
+    n = 16
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    mbw, mbh = native._bwbh(mv)
+    bgr, types = _batch(cfg, n)
+    every = _measure_variant_lib(0)
+    t40 = native.target_tensor(lay.distortion_target(40.0, pw, ph), n, dev)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    ladders = (("levels.step_ladder(1, 256, 4, 640, 10, 24)", _budget(cfg)[0]), ("32 entries, both steps rising at each", [(k + 1, 4 + 20 * k) for k in range(32)]))
+    for name, lad in ladders:
+        arr, k = native._ladder(lad)
+        ws = torch.empty(native.dct_pack_levels_quality_workspace_bytes(n, pw, ph, block, mv, k), dtype=torch.uint8, device=dev)
+        res = []
+        for _ in range(2):
+            res.append((torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev),
+                        torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, k), dtype=torch.int64, device=dev)))
+
+        def call(fn, r):
+            out, offs, ch, tab = r
+            native._check(fn(bgr.data_ptr(), pw * ph * 3, n, pw, ph, block, types.data_ptr(), mbw, mbh, arr, k, t40.data_ptr(), None, ws.data_ptr(),
+                             ws.numel(), out.data_ptr(), out.numel(), offs.data_ptr(), ch.data_ptr(), tab.data_ptr(), native._stream()))
+        ms = _median3([lambda: call(native.load().svc_hip_dct_pack_levels_quality_frames, res[0]), lambda: call(every, res[1])],
+                      torch.cuda.synchronize)
+        used = int(res[0][1][-1])
+        same = all(torch.equal(a, b) for a, b in zip(res[0][1:], res[1][1:])) and torch.equal(res[0][0][:used], res[1][0][:used])
+        print(f"{cfg.name} batch of {n}, {name}: the call as built {ms[0]:.3f} ms, every entry computed {ms[1]:.3f} ms ({ms[1] / ms[0]:.2f}x); "
+              f"tables, choices, offsets and bytes {'equal' if same else 'DIFFER'}", flush=True)
+
+
+def quality_step(cfg, frames_n) -> None:
+    from scalable_video_codec_amd import layers as lay
+    dev = torch.device("cuda")
+    clip = synth.SynthClip(cfg.width, cfg.height, frames_n, cfg.seed, device=dev)
+    pw, ph = cfg.padded
+    frames = torch.stack([synth.pad_frame(clip.frame_bgr(t), pw, ph) for t in range(frames_n)]).contiguous()
+    lad, per_frame = _budget(cfg)
+    for schedule, name in ((clipmod.SERIAL, "serial"), (clipmod.PIPELINED, "pipelined")):
+        enc = clipmod.Clip(cfg, frames_n, schedule=schedule, compact=True)
+        enc.load_frames(frames)
+        fixed_ms = _per_step(enc.step, enc.sync)
+        enc.set_compact_budget(lad, per_frame)
+        budget_ms = _per_step(enc.step, enc.sync)
+        enc.set_compact_quality(lad, psnr_db=40.0)
+        quality_ms = _per_step(enc.step, enc.sync)
+        ch = enc.read("compact_choice").numpy().view("uint32")
+        dist = enc.read("compact_distortion").numpy().view("uint64")
+        enc.set_compact_quality([], target=0)
+        again_ms = _per_step(enc.step, enc.sync)
+        i = enc.info
+        enc.close()
+        del enc
+        torch.cuda.empty_cache()
+        psnr = [lay.distortion_psnr(v, pw, ph) for v in dist]
+        print(f"{cfg.name} {name}, {i.pairs} pairs, ms per step (best .. worst of 3 runs of 4 back-to-back steps): fixed compact step "
+              f"{fixed_ms[0]:.3f} .. {fixed_ms[1]:.3f}; under a budget of {per_frame} B per frame {budget_ms[0]:.3f} .. {budget_ms[1]:.3f}; at a "
+              f"40 dB target {quality_ms[0]:.3f} .. {quality_ms[1]:.3f} ({quality_ms[0] / fixed_ms[0]:.2f}x the fixed step, "
+              f"{quality_ms[0] / budget_ms[0]:.2f}x the budgeted; entries {int((ch & 0x3FFFFFFF).min())} .. {int((ch & 0x3FFFFFFF).max())}, "
+              f"{min(psnr):.2f} .. {max(psnr):.2f} dB); fixed again {again_ms[0]:.3f} .. {again_ms[1]:.3f}", flush=True)
 
 
 def _per_step(fn, sync, warm=2, reps=3, steps=4):
@@ -1619,6 +1811,12 @@ if __name__ == "__main__":
         budget_step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
     elif mode == "budget":
         budget(_cfg(sys.argv, 2))
+    elif mode in ("quality", "quality-kernels"):
+        quality(_cfg(sys.argv, 2), kernels_only=mode == "quality-kernels")
+    elif mode == "quality-variants":
+        quality_variants(_cfg(sys.argv, 2))
+    elif mode == "quality_step":
+        quality_step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
     elif mode == "layers":
         layers(_cfg(sys.argv, 2))
     elif mode == "window":
