@@ -52,7 +52,8 @@ struct StreamEncoderConfig {
                                    // EncodedBatch::compact instead of coeffs.  Not with `wire`
   uint32_t compact_budget = 0;     // with `compact`: bytes per frame.  Each frame is packed with the finest entry of compact_ladder whose
                                    // frame fits (svc_hip_pack_levels_budget_frames; the transform then leaves RAW planes).  0 = the
-                                   // fixed fg_step / bg_step.  SetCompactBudget changes it for a live stream
+                                   // fixed fg_step / bg_step.  SetCompactBudget changes it for a live stream.  With `delta`: a
+                                   // group's budget is the sum over its frames (see there)
   std::vector<svc_step_pair> compact_ladder;  // required with a budget: 1 .. 64 (fg_step, bg_step), finest first, non-decreasing
   bool entropy = false;            // with `compact`, not with a budget: every packed frame is coded losslessly on the device ("SVCE",
                                    // svc_hip_entropy_encode_frames) and EncodedBatch::compact carries the SVCE frames; d2h_bytes counts
@@ -68,8 +69,14 @@ struct StreamEncoderConfig {
                                    // (with `entropy`: its SVCE frames) and EncodedBatch::compact_key the key flags.
                                    // svc::StreamDecoder::DecodeDelta plays it.  The chain runs across batches, so the stream does not
                                    // depend on batch or depth; every Encode() starts with a key frame.  Square 8x8 or 16x16 transform
-                                   // blocks only; not with `wire`, compact_budget or enh_step: each throws at construction, as does a
-                                   // geometry the C ABI refuses, with its message
+                                   // blocks only; not with `wire` or enh_step: each throws at construction, as does a
+                                   // geometry the C ABI refuses, with its message.
+                                   // With compact_budget and compact_ladder: a byte budget per GROUP of frames, from a key frame up to
+                                   // the next (svc_hip_dct_pack_delta_budget_frames, include/svc_hip_delta_budget.h): the group's frames
+                                   // together fit the sum of their budgets at one pair of the ladder, and EncodedBatch::compact_choice
+                                   // carries it for every frame.  Accepted exactly when key_interval != 0, batch % key_interval == 0,
+                                   // !auto_key, temporal_period == 1 and !entropy -- every batch then holds whole groups and nothing
+                                   // is carried across batches; any other combination throws at construction
   uint32_t key_interval = 0;       // with `delta`: the encoded frame with clip index f (as EncodedBatch::first_frame counts: the first
                                    // is 1) is a key frame iff f == 1, or key_interval != 0 and (f - 1) % key_interval == 0
   bool auto_key = false;           // with `delta` (without it the constructor throws): the key frames are chosen by size on the device

@@ -69,6 +69,14 @@
 // its 64 sums as a row beside its row of counts; dct_measure_sum_kernel adds both kinds of rows in kSumParts parts,
 // dct_quality_select_kernel chooses and writes the frame's steps (and its row of the table), and the fused pack's three launches follow.
 // The other forms' device code is instruction for instruction what it was (profiles/dct_pack_quality_c3.txt).
+//
+// A byte budget per group of frames (svc_hip_dct_pack_delta_budget_frames; include/svc_hip_delta_budget.h states it,
+// layers.delta_ladder_counts / delta_budget_choice in numpy): the delta stream with one pair of a ladder per group, from a key frame up
+// to the next.  dct_delta_ladder_kernel<N> is GROUP + TALLY of the body: the delta form's runs with the f32 coefficients of the frame
+// before in registers and, per frame and ladder entry, the count of differences that entry would leave -- a row per wave and frame.
+// dct_delta_ladder_sum_kernel adds the rows in kSumParts parts, dct_delta_group_select_kernel sums a group's bytes per entry, chooses over
+// all entries and writes every frame's steps; dct_pack_delta_group_kernel<N> (GROUP alone) is the delta form with those steps, and the
+// fused pack's scan and assemble follow.  The other forms' device code is what it was (profiles/dct_pack_delta_budget_c3.txt).
 #include <algorithm>
 #include <type_traits>
 
@@ -77,6 +85,7 @@
 #include "quant_core.hpp"
 #include "stream_format.hpp"
 #include "svc_common.hpp"
+#include "svc_hip_delta_budget.h"
 #include "svc_hip_quality.h"
 #include "svc_hip_temporal.h"
 
@@ -211,6 +220,13 @@ struct DeltaRunArgs {
 struct DeltaTallyArgs : DeltaRunArgs {
   uint32_t* tally;  // [runs][waves of a frame][run][2] levels of the piece, levels of its difference to the frame before
 };
+// what the delta form's ladder tally takes: the same runs (key IS read), the ladder with each entry's RN(1 / step) for the quantiser, and
+// where a wave leaves its row of counts per frame
+struct DeltaLadderArgs : DeltaRunArgs {
+  Ladder lad;
+  LadderInv li;
+  uint32_t* rows;  // [runs][waves of a frame][run][kMaxLadder]: the wave's non-zero differences of the frame at entry k (0 from the ladder's end on)
+};
 // Frames of a run.  {1, 2, 4, 8} measured at C3 and C5, batches of 16 (profiles/dct_pack_delta_c3.txt has all four): 8 is the fastest
 // or tied in every row -- at C3 / (1, 640) 0.194, 0.163, 0.152, 0.152 ms; at C5 1.065, 0.897, 0.820, 0.790.
 #ifndef SVC_DCT_PACK_DELTA_RUN  // (the probe that measured them builds this file once per value: tools/dct_pack_probe.py delta-encode)
@@ -290,14 +306,28 @@ __device__ __forceinline__ uint32_t sub2(uint32_t a, uint32_t b) {
 // the wave, the total kept by lane k and stored with the wave's row of counts.  An entry at which no lane's step differs from the entry
 // before (a ladder of levels.step_ladder moves one class at a time) takes the sum before it: nothing is computed.  The entry is the same
 // in every lane, so both classes' step and RN(1 / step) are uniform loads from the arguments and the lane selects by its class: no table.
-template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false, int PERIOD = 1, bool REDO = false, bool MEASURE = false>
+// GROUP = true (with DELTA, PERIOD 1): the forms of svc_hip_dct_pack_delta_budget_frames (include/svc_hip_delta_budget.h states it,
+// layers.delta_ladder_counts in numpy), one pair of steps per group of frames.  Alone: the delta form with each frame's own pair from
+// a.steps -- the predicate's fg == bg is then the frame's, not the call's.  With TALLY: the delta form's runs WITH its flags, stopped at
+// the column pass's f32 coefficients.  The lane keeps the coefficients of the frame before (48 f32, not levels: a level belongs to one
+// step) and, channel by channel, goes through the ladder with the channel's 16 against the kept 16: per entry both are quantised at the
+// entry's step of the lane's tile and the levels that differ are counted -- against 0 where the tile is not predicted at that entry, that
+// is in a key frame or where the entry gives the tile another step in the frame before (fg_k == bg_k changes along a ladder).  Integer
+// counts, so any order of summing gives the same u32.  As in the measuring form, an entry at which no lane's step and no lane's
+// predicate differ from the entry before takes that entry's sum.  Lane k keeps entry k's sum over the three channels; the wave stores
+// that row per frame to a place of its own (no atomics, as the TALLY form).
+template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false, int PERIOD = 1, bool REDO = false, bool MEASURE = false,
+          bool GROUP = false>
 __device__ __forceinline__ void dct_pack_body(
     const DctPackArgs& a,
     const std::conditional_t<MEASURE, MeasureArgs,
     std::conditional_t<COUNT, CountArgs,
                              std::conditional_t<LAYERS, LayerArgs,
-                                                std::conditional_t<TALLY, DeltaTallyArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>>>& k,
+                                                std::conditional_t<TALLY && GROUP, DeltaLadderArgs,
+                                                std::conditional_t<TALLY, DeltaTallyArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>>>>& k,
     float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
+  static_assert(!GROUP || (DELTA && PERIOD == 1), "a group's steps: the delta form without temporal layers");
+  constexpr bool kLadderTally = GROUP && TALLY;  // the counts of every ladder entry instead of the pack
   static_assert(!MEASURE || COUNT, "the measuring form is the counting form with the squared errors");
   static_assert(!(COUNT && LAYERS), "the counting form has no layers");
   static_assert(!(DELTA && (COUNT || LAYERS)), "the delta form is one layer at fixed steps");
@@ -346,6 +376,9 @@ __device__ __forceinline__ void dct_pack_body(
   uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
   float kept[MEASURE ? 3 : 1][16];  // MEASURE: |c| of the lane's coefficients, all three channels, and the lane's class
   uint32_t cls = 0;
+  float prior[kLadderTally ? 3 : 1][16] = {};  // kLadderTally: the f32 coefficients of the frame before, all three channels
+  uint32_t tally_row = 0;                      // and, in lane k, the frame's count at ladder entry k
+  bool frame_one_step = false;                 // GROUP: the trip's frame has fg == bg
   if constexpr (DELTA) {
     run_first = frame0 * k.run;
     run_len = min(k.run, k.n_frames - run_first);
@@ -362,7 +395,7 @@ __device__ __forceinline__ void dct_pack_body(
   const uint32_t* frame_types = nullptr;
   if constexpr (DELTA) {
     const uint32_t f = run_first + (uint32_t)max(it, 0);  // the frame whose flag decides this trip
-    if constexpr (TALLY) key = f == 0 && !k.prev_bgr;  // no flag is read: the frame in front of a run is always transformed
+    if constexpr (TALLY && !GROUP) key = f == 0 && !k.prev_bgr;  // no flag is read: the frame in front of a run is always transformed
     else key = (f == 0 && !k.prev_bgr) || (k.key && k.key[f] != 0);
     if (it < 0 && key) continue;  // (`before` is not read)
     const bool outside = it < 0 && run_first == 0;  // the frame in front of frame 0
@@ -389,6 +422,7 @@ __device__ __forceinline__ void dct_pack_body(
     const FrameSteps fs = a.steps[frame];
     step = (float)(t == 0 ? fs.bg : fs.fg);  // libs/decoder.cpp:141 divides a float by an unsigned
     inv_step = t == 0 ? fs.bg_inv : fs.fg_inv;
+    if constexpr (GROUP) frame_one_step = fs.fg == fs.bg;  // (the frame in front of a run: its group's pair, the next frame's unless that is a key frame)
   }
   int32_t ratio = 0;      // LAYERS: the lane's tile's base step / enh_step, and whether the frame's window holds the tile's origin
   bool enhanced = false;  // (the containment rule of the decoders' gaze: w or h of 0 holds nothing)
@@ -407,7 +441,7 @@ __device__ __forceinline__ void dct_pack_body(
   const uint32_t nwords = ncols * kColWords;                           // mask words of the piece, in the format's order
   const uint32_t word0 = (seg0 * (16 / N)) * gm.l.words;               // the piece's first word within its tile row
   // DELTA: the lane's tile is predicted where both frames code it at one step
-  const bool predicted = DELTA && !key && (k_one_step(k) || (t == 0) == ((kMid && use_mid ? t_mid : t_before) == 0));
+  const bool predicted = DELTA && !key && ((GROUP ? frame_one_step : k_one_step(k)) || (t == 0) == ((kMid && use_mid ? t_mid : t_before) == 0));
   uint32_t tally = 0;  // TALLY: this lane's non-zero levels of the frame (at most 48) in the low half, non-zero differences in the high
 
 #pragma unroll
@@ -429,7 +463,7 @@ __device__ __forceinline__ void dct_pack_body(
 
     uint32_t lv[8];  // this lane's levels of the channel, two int16 each
     uint32_t dv[8];  // LAYERS: its residuals, likewise
-    float m[16];     // COUNT: |c| of its 16 coefficients instead
+    float m[16];     // COUNT: |c| of its 16 coefficients instead; kLadderTally: the coefficients themselves
     if (N == 8) {
       // lane j takes columns 2j, 2j+1 of the 16-wide slab (tile j >> 2): lv[v] = row v
       double ca[8], cb[8], ya[8], yb[8];
@@ -446,6 +480,9 @@ __device__ __forceinline__ void dct_pack_body(
         if constexpr (COUNT) {
           m[2 * v] = fabsf((float)ya[v]);
           m[2 * v + 1] = fabsf((float)yb[v]);
+        } else if constexpr (kLadderTally) {
+          m[2 * v] = (float)ya[v];
+          m[2 * v + 1] = (float)yb[v];
         } else if constexpr (LAYERS) {
           const f32x2 cf{(float)ya[v], (float)yb[v]}, qb = quant2_level(cf, step, inv_step);
           lv[v] = pack2(qb);
@@ -465,6 +502,9 @@ __device__ __forceinline__ void dct_pack_body(
         if constexpr (COUNT) {
           m[v] = fabsf((float)yy[v]);
           m[v + 1] = fabsf((float)yy[v + 1]);
+        } else if constexpr (kLadderTally) {
+          m[v] = (float)yy[v];
+          m[v + 1] = (float)yy[v + 1];
         } else if constexpr (LAYERS) {
           const f32x2 cf{(float)yy[v], (float)yy[v + 1]}, qb = quant2_level(cf, step, inv_step);
           lv[v / 2] = pack2(qb);
@@ -501,6 +541,38 @@ __device__ __forceinline__ void dct_pack_body(
 #pragma unroll
         for (int i = 0; i < 16; ++i) kept[c][i] = m[i];
       }
+      continue;  // (the slabs are free for the next channel: the sync above)
+    }
+    if constexpr (kLadderTally) {
+      // Entry kk's steps are uniform loads from the arguments (the measuring form's way: no table); the lane selects by its tile's class
+      // now and in the frame before.  Where the two steps differ the tile is not predicted at that entry -- the pack's predicate, per entry.
+      if (it >= 0) {
+        uint32_t total = 0, prev_step = 0;  // (no step is 0: the first entry is always computed)
+        bool prev_pred = false;
+        for (uint32_t kk = 0; kk < k.lad.len; ++kk) {
+          const uint32_t s_bg = k.lad.step[0][kk], s_fg = k.lad.step[1][kk];
+          const uint32_t s_now = t == 0 ? s_bg : s_fg, s_before = t_before == 0 ? s_bg : s_fg;
+          const float inv = t == 0 ? k.li.inv[0][kk] : k.li.inv[1][kk];
+          const bool pred = !key && s_now == s_before;
+          if (__ballot(s_now != prev_step || pred != prev_pred) != 0) {  // the same in every lane; a lane for which nothing moved computes the count it had
+            const float s = (float)s_now;
+            uint32_t cnt = 0;
+#pragma unroll
+            for (int i = 0; i < 16; i += 2) {
+              const f32x2 q = quant2_level(f32x2{m[i], m[i + 1]}, s, inv);
+              f32x2 qb = {0.f, 0.f};
+              if (pred) qb = quant2_level(f32x2{prior[c][i], prior[c][i + 1]}, s, inv);
+              cnt += (q.x != qb.x ? 1u : 0u) + (q.y != qb.y ? 1u : 0u);  // (integers in f32; -0.0 == 0.0, as both pack to level 0)
+            }
+            total = wave_sum(cnt);
+          }
+          prev_step = s_now;
+          prev_pred = pred;
+          if (lane == kk) tally_row += total;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) prior[c][i] = m[i];
       continue;  // (the slabs are free for the next channel: the sync above)
     }
     if constexpr (DELTA && PERIOD > 1) {  // the same against the kept frame of the trip's layer; the levels stay where a later frame refers to them
@@ -582,7 +654,10 @@ __device__ __forceinline__ void dct_pack_body(
       wave_lds_sync();  // the slabs are rewritten: by the next layer's images, or by the next channel
     }
   }
-  if constexpr (TALLY) {  // a wave's 64 x 48 coefficients: both sums fit their halves.  A place per wave and frame, no atomics: with
+  if constexpr (kLadderTally) {  // a place per wave and frame: a row of kMaxLadder counts, each at most 64 x 48
+    if (it >= 0) k.rows[((size_t)wv * k.run + (uint32_t)it) * kMaxLadder + lane] = tally_row;
+    tally_row = 0;
+  } else if constexpr (TALLY) {  // a wave's 64 x 48 coefficients: both sums fit their halves.  A place per wave and frame, no atomics: with
     // 65 280 adds into the one cache line that holds a batch's 32 counters the call took 0.709 ms at C3 (1, 640), with the stores 0.238
     // (profiles/dct_pack_delta_auto_c3.txt)
     if (it >= 0 && !(REDO && redo)) {
@@ -657,6 +732,17 @@ __global__ __launch_bounds__(256) void dct_pack_delta_kernel(DctPackArgs a, Delt
 template <int N>
 __global__ __launch_bounds__(256) void dct_delta_count_kernel(DctPackArgs a, DeltaTallyArgs k) {
   dct_pack_body<N, false, false, true, true>(a, k, nullptr, nullptr);
+}
+
+// the delta form with each frame's own pair of steps (a.steps), and the delta form's runs with the counts of every ladder entry
+template <int N>
+__global__ __launch_bounds__(256) void dct_pack_delta_group_kernel(DctPackArgs a, DeltaRunArgs k) {
+  dct_pack_body<N, false, false, true, false, 1, false, false, true>(a, k, nullptr, nullptr);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void dct_delta_ladder_kernel(DctPackArgs a, DeltaLadderArgs k) {
+  dct_pack_body<N, false, false, true, true, 1, false, false, true>(a, k, nullptr, nullptr);
 }
 
 // both with temporal layers: a frame against frame i - min(lowbit(i), PERIOD)
@@ -825,6 +911,55 @@ __global__ __launch_bounds__(256) void dct_quality_select_kernel(Ladder lad, Lad
   a.steps[f] = FrameSteps{lad.step[1][pick], lad.step[0][pick], li.inv[1][pick], li.inv[0][pick]};
 }
 
+// The ladder tally's sum.  grid (kSumParts, frames): part p of frame f = the sum of its waves' rows p, p + kSumParts, ...  A wave's rows
+// of the frames of its run lie side by side, so the rows of one frame are `run` rows apart.
+__global__ __launch_bounds__(256) void dct_delta_ladder_sum_kernel(uint32_t waves_per_frame, uint32_t run, const uint32_t* __restrict__ rows,
+                                                                   uint32_t* __restrict__ parts) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  const uint32_t f = blockIdx.y;
+  const uint32_t* mine = rows + (((size_t)(f / run) * waves_per_frame) * run + f % run) * kMaxLadder;  // wave 0 of the frame's run, this frame
+  const uint32_t v = sum_rows(mine, blockIdx.x * run, kSumParts * run, waves_per_frame * run, part);
+  if (threadIdx.x < kMaxLadder) parts[((size_t)f * kSumParts + blockIdx.x) * kMaxLadder + threadIdx.x] = v;
+}
+
+// One workgroup per frame; the one of a frame that starts a group (frame 0, or a set flag) works, the others leave.  Frame by frame up
+// to the next start: the parts' sum = count[g][k] in lane k (to the caller's table where asked), bytes_k(g) = up16(levels_off + 2 count)
+// and the budget, both summed in 64 bits.  The choice is the first lane whose sum fits, from a ballot over ALL entries: the counts of
+// differences are not monotone along a ladder, so nothing of the counting form's suffix sums carries over and no entry is skipped.
+// None fits: the last entry, bit 31 set.  Every frame of the group gets the value and the pair's steps.
+struct GroupSelectArgs {
+  uint64_t levels_off;
+  const uint32_t* parts;
+  const uint32_t* key;     // [n] or null: one group
+  const uint32_t* budget;  // [n]
+  FrameSteps* steps;
+  uint32_t* choice;
+  uint32_t* counts;        // [n][len] or null
+  uint32_t n_frames;
+};
+__global__ __launch_bounds__(256) void dct_delta_group_select_kernel(Ladder lad, LadderInv li, GroupSelectArgs a) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  const uint32_t first = blockIdx.x, lane = threadIdx.x & 63u;
+  if (first != 0 && !(a.key && a.key[first] != 0)) return;  // (the same in every thread, as the loop's trips below)
+  uint64_t bytes = 0, allowed = 0;
+  uint32_t end = first;
+  do {
+    const uint32_t nz = sum_rows(a.parts + (size_t)end * kSumParts * kMaxLadder, 0, 1, kSumParts, part);
+    bytes += up16(a.levels_off + 2ull * nz);
+    allowed += a.budget[end];
+    if (a.counts && threadIdx.x < lad.len) a.counts[(size_t)end * lad.len + threadIdx.x] = nz;
+    __syncthreads();  // part is rewritten by the next frame's sum
+    ++end;
+  } while (end < a.n_frames && !(a.key && a.key[end] != 0));
+  const uint64_t fits = __ballot(lane < lad.len && bytes <= allowed);  // every wave holds all entries: lane k has entry k
+  const uint32_t ch = fits ? (uint32_t)__builtin_ctzll(fits) : ((lad.len - 1) | 0x80000000u), pick = ch & 0x7FFFFFFFu;
+  const FrameSteps fs{lad.step[1][pick], lad.step[0][pick], li.inv[1][pick], li.inv[0][pick]};
+  for (uint32_t g = first + threadIdx.x; g < end; g += kThreads) {
+    a.choice[g] = ch;
+    a.steps[g] = fs;
+  }
+}
+
 // one workgroup per frame: piece counts -> exclusive prefixes (in place), the frame's level count and size
 __global__ __launch_bounds__(256) void dct_pack_scan_kernel(uint32_t pieces, uint64_t levels_off, DctPackWs ws) {
   __shared__ uint32_t red[kThreads / 64];
@@ -978,6 +1113,22 @@ DeltaAutoWs delta_auto_ws(Carver& c, uint32_t n, const PackGeom& g) {
   s.pack = pack_ws(c, n, g);
   // (whole runs of either length: the two are one number unless a probe build sets another kDeltaRun)
   s.tally = c.take<uint32_t>(2ull * std::max(kDeltaRun * div_up(n, kDeltaRun), kTemporalRun * div_up(n, kTemporalRun)) * g.l.tiles_y * g.waves_per_row);
+  return s;
+}
+
+// the group-budget call's workspace: the delta call's, then every wave's row of counts per frame (whole runs), their parts and the steps
+struct DeltaBudgetWs {
+  DctPackWs pack;
+  uint32_t* rows;     // as DeltaLadderArgs::rows
+  uint32_t* parts;    // [n][kSumParts][kMaxLadder]
+  FrameSteps* steps;  // [n]
+};
+DeltaBudgetWs delta_budget_ws(Carver& c, uint32_t n, const PackGeom& g) {
+  DeltaBudgetWs s;
+  s.pack = pack_ws(c, n, g);
+  s.rows = c.take<uint32_t>((uint64_t)kMaxLadder * kDeltaRun * div_up(n, kDeltaRun) * g.l.tiles_y * g.waves_per_row, false);
+  s.parts = c.take<uint32_t>((uint64_t)kMaxLadder * n * kSumParts, false);
+  s.steps = c.take<FrameSteps>(n);
   return s;
 }
 
@@ -1409,6 +1560,82 @@ int svc_hip_dct_pack_levels_quality_frames(const uint8_t* d_bgr, uint64_t frame_
   hipLaunchKernelGGL(dct_quality_select_kernel, dim3(n_frames), blk, 0, s, k.lad, k.li, sel);
   if ((rc = check_launch(what, "select"))) return rc;
   return enqueue_dct_pack(what, a, n_frames, 0, 0, d_out, d_frame_offsets, s);
+}
+
+// ---- the delta stream with one pair of steps per group of frames, by a byte budget on the group (include/svc_hip_delta_budget.h)
+
+uint64_t svc_hip_dct_pack_delta_budget_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                                       uint32_t mv_block_w, uint32_t mv_block_h, uint32_t ladder_len) {
+  const char* what = "dct_pack_delta_budget_workspace_bytes";
+  if (validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  if (ladder_len == 0 || ladder_len > kMaxLadder) {
+    (void)fail(SVC_ERR_INVALID_ARG, "%s: a ladder of %u entries (1 .. %u)", what, ladder_len, kMaxLadder);
+    return 0;
+  }
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits(what, n_frames, g)) return 0;
+  return layout_bytes(delta_budget_ws, n_frames, g);
+}
+
+// Checked in the order of svc_hip_dct_pack_levels_budget_frames: geometry, stride, ladder, limits, sizes; n_frames == 0 then returns
+// SVC_OK; then pointers.  Six launches whatever n_frames: the ladder tally, its sum, the groups' selection, then the delta form's three
+// with each frame's own steps.
+int svc_hip_dct_pack_delta_budget_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                         uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                         uint32_t mv_block_h, const svc_step_pair* ladder, uint32_t ladder_len, const uint32_t* d_key,
+                                         const uint32_t* d_budget, uint8_t* d_workspace, uint64_t workspace_bytes, uint8_t* d_out,
+                                         uint64_t out_capacity, uint64_t* d_frame_offsets, uint32_t* d_choice, uint32_t* d_level_counts,
+                                         void* stream) {
+  const char* what = "dct_pack_delta_budget";
+  int rc = validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "%s: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", what, (unsigned long long)frame_stride_bytes,
+              3ull * frame_w * frame_h);
+  if ((rc = validate_ladder(what, ladder, ladder_len))) return rc;
+  // (the pack's int16 bound holds for every step at 8x8 and 16x16, as in svc_hip_dct_pack_levels_frames; a difference wraps by definition)
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits(what, n_frames, g))) return rc;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(delta_budget_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity(what, "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_budget && d_workspace && d_out && d_frame_offsets && d_choice, "%s: null pointer", what);
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_block_types, 4) &&
+                  aligned(d_key, 4) && aligned(d_budget, 4) && aligned(d_choice, 4) && aligned(d_level_counts, 4),
+              "%s: frames, output and workspace must be 16-byte aligned, offsets 8-byte, types, key flags, budget, choice and level counts 4-byte",
+              what);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const DeltaBudgetWs ws = carve(d_workspace, delta_budget_ws, n_frames, g);
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.types = d_block_types;
+  a.ws = ws.pack;
+  a.total_waves = div_up(n_frames, kDeltaRun) * g.l.tiles_y * g.waves_per_row;  // a wave per piece and RUN, as the pack below
+  const DeltaRunArgs run{nullptr, nullptr, d_key, n_frames, kDeltaRun, 0u};  // (one_step is each frame's own, from its steps)
+  DeltaLadderArgs t{};
+  static_cast<DeltaRunArgs&>(t) = run;
+  t.lad = make_ladder(ladder, ladder_len);
+  for (uint32_t i = 0; i < ladder_len; ++i) {
+    t.li.inv[0][i] = 1.0f / (float)ladder[i].bg_step;
+    t.li.inv[1][i] = 1.0f / (float)ladder[i].fg_step;
+  }
+  t.rows = ws.rows;
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if (block == 8) hipLaunchKernelGGL(dct_delta_ladder_kernel<8>, grid, blk, 0, s, a, t);
+  else hipLaunchKernelGGL(dct_delta_ladder_kernel<16>, grid, blk, 0, s, a, t);
+  if ((rc = check_launch(what, "tally"))) return rc;
+  hipLaunchKernelGGL(dct_delta_ladder_sum_kernel, dim3(kSumParts, n_frames), blk, 0, s, g.l.tiles_y * g.waves_per_row, kDeltaRun, ws.rows, ws.parts);
+  if ((rc = check_launch(what, "sum"))) return rc;
+  const GroupSelectArgs sel{g.l.levels_off, ws.parts, d_key, d_budget, ws.steps, d_choice, d_level_counts, n_frames};
+  hipLaunchKernelGGL(dct_delta_group_select_kernel, dim3(n_frames), blk, 0, s, t.lad, t.li, sel);
+  if ((rc = check_launch(what, "select"))) return rc;
+  a.steps = ws.steps;
+  if (block == 8) hipLaunchKernelGGL(dct_pack_delta_group_kernel<8>, grid, blk, 0, s, a, run);
+  else hipLaunchKernelGGL(dct_pack_delta_group_kernel<16>, grid, blk, 0, s, a, run);
+  if ((rc = check_launch(what, "transform"))) return rc;
+  return enqueue_assemble(what, a, a.ws, n_frames, 0, 0, d_out, d_frame_offsets, s);
 }
 
 }  // extern "C"

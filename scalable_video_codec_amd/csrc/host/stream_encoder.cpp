@@ -5,6 +5,7 @@
 #include "batch_pipe.hpp"
 #include "copy_crew.hpp"
 #include "encode_geometry.hpp"
+#include "svc_hip_delta_budget.h"
 #include "svc_hip_temporal.h"
 
 #include <sched.h>
@@ -69,6 +70,7 @@ struct StreamEncoder::Impl : EncodeGeometry {
   uint64_t packed_bytes = 0, pack_ws_bytes = 0;  // compact: worst case of a batch, pack workspace
   uint64_t coded_bytes = 0, entropy_ws_bytes = 0; // entropy: worst case of a coded batch, coder workspace
   bool budgeted = false;                          // compact_budget != 0: rate control
+  bool group_budget = false;                      // ... of the delta stream: a budget per group of frames, svc_hip_dct_pack_delta_budget_frames
   bool layered = false;                           // enh_step != 0: a base and an enhancement stream
   bool temporal = false;                          // delta with temporal_period > 1: svc_hip_dct_pack_delta_temporal_frames
   std::atomic<uint32_t> budget{0};                // bytes per frame of the next batch staged (SetCompactBudget)
@@ -90,8 +92,13 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (!m.tw || !m.th) throw std::runtime_error("svc::StreamEncoder: invalid configuration");
   if (c.delta && c.wire) throw std::runtime_error("svc::StreamEncoder: the delta stream is a form of the compact stream, not of the wire records");
   if (c.delta && !c.compact) throw std::runtime_error("svc::StreamEncoder: the delta stream is a form of the compact stream");
-  if (c.delta && c.compact_budget)
-    throw std::runtime_error("svc::StreamEncoder: a byte budget picks each frame's steps, a difference needs the steps of the frame before: not with delta");
+  // a byte budget with delta: one pair of steps per group of frames, and a batch must hold whole groups (svc_hip_dct_pack_delta_budget_frames
+  // takes no frame before frame 0) -- key frames at a fixed interval that divides the batch, nothing chosen or referred to across them
+  if (c.delta && c.compact_budget &&
+      !(c.key_interval != 0 && c.batch % c.key_interval == 0 && !c.auto_key && c.temporal_period == 1 && !c.entropy))
+    throw std::runtime_error("svc::StreamEncoder: a byte budget picks one pair of steps per group of frames, from a key frame up to the next, and "
+                             "a difference needs the steps of the frame before: not with delta unless every batch holds whole groups "
+                             "(key_interval != 0 that divides batch, no auto_key, temporal_period 1, no entropy)");
   if (c.auto_key && !c.delta) throw std::runtime_error("svc::StreamEncoder: auto_key chooses the key frames of the delta stream: not without delta");
   if (c.delta && c.enh_step) throw std::runtime_error("svc::StreamEncoder: the delta stream has one layer: not with enh_step");
   if (c.temporal_period != 1 && c.temporal_period != 2 && c.temporal_period != 4)
@@ -117,7 +124,15 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (c.compact_budget && !c.compact) throw std::runtime_error("svc::StreamEncoder: a byte budget is a setting of the compact stream");
   m.budgeted = c.compact_budget != 0;
   m.budget.store(c.compact_budget);
-  if (m.budgeted)  // the budgeted pack's checks that need neither a device pointer nor a size: geometry, the ladder, the int16 bound
+  m.group_budget = m.budgeted && c.delta;
+  if (m.group_budget) {  // the call's checks that need neither a device pointer nor a size: geometry, the ladder
+    if (m.tw != m.th)
+      throw std::runtime_error("svc::StreamEncoder: the delta stream takes square transform blocks (8x8, 16x16), not " + std::to_string(m.tw) + "x" +
+                               std::to_string(m.th));
+    Abi(svc_hip_dct_pack_delta_budget_frames(nullptr, m.frame_bytes, 0, m.pw, m.ph, m.tw, nullptr, m.bw, m.bh, c.compact_ladder.data(),
+                                             (uint32_t)c.compact_ladder.size(), nullptr, nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr, nullptr,
+                                             nullptr, nullptr), "compact_ladder");
+  } else if (m.budgeted)  // the budgeted pack's checks that need neither a device pointer nor a size: geometry, the ladder, the int16 bound
     Abi(svc_hip_pack_levels_budget_frames(nullptr, nullptr, 0, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.compact_ladder.data(),
                                           (uint32_t)c.compact_ladder.size(), nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr, nullptr,
                                           nullptr), "compact_ladder");
@@ -145,7 +160,8 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   }
   if (c.compact) {
     m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
-    m.pack_ws_bytes = m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
+    m.pack_ws_bytes = m.group_budget ? svc_hip_dct_pack_delta_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh, (uint32_t)c.compact_ladder.size())
+                      : m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
                       : m.layered ? svc_hip_pack_layers_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th)
                       : c.auto_key ? svc_hip_dct_pack_delta_auto_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh)
                       : m.temporal ? svc_hip_dct_pack_delta_temporal_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh, c.temporal_period)
@@ -358,6 +374,11 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         const uint32_t sw = c.reference_stream ? c.width : m.pw, sh = c.reference_stream ? c.height : m.ph;
         Abi(svc_hip_serialize_frames(s.coeffs.p, m.plane_elems, B, s.types.p, sw, sh, m.tw, m.th, m.mfw, m.mfh,
                                      m.bw, m.bh, s.records.p, m.record_bytes, sk), "svc_hip_serialize_frames");
+      } else if (m.group_budget) {  // every batch starts at a key frame and holds whole groups: no frame before, nothing carried
+        Abi(svc_hip_dct_pack_delta_budget_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.compact_ladder.data(),
+                                                 (uint32_t)c.compact_ladder.size(), s.key.p, s.budget.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
+                                                 m.packed_bytes, s.offsets.p, s.choice.p, nullptr, sk),
+            "svc_hip_dct_pack_delta_budget_frames");
       } else if (m.budgeted) {  // raw planes; the pack picks each frame's steps from its budget
         Abi(svc_hip_dct_frames(enc_bgr, m.frame_bytes, B, m.pw, m.ph, m.tw, m.th, s.coeffs.p, sk), "svc_hip_dct_frames");
         Abi(svc_hip_pack_levels_budget_frames(s.coeffs.p, s.types.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh, c.compact_ladder.data(),

@@ -20,6 +20,8 @@ its masks; union_frame / union_frames state svc_hip_union_levels_frames, which j
 delta_frame / delta_frames state svc_hip_delta_levels_frames: a frame coded against the frame before it, as the difference of their levels
 in the tiles both code at one step; undelta_frame / undelta_frames state svc_hip_undelta_levels_frames, which adds the frames back up.
 delta_level_counts / auto_keys / delta_auto_frames state the key frames svc_hip_dct_pack_delta_auto_frames chooses by the frame's size.
+delta_groups / delta_ladder_counts / delta_budget_choice / delta_budget_frames state svc_hip_dct_pack_delta_budget_frames
+(include/svc_hip_delta_budget.h): one pair of steps per group of frames, from a key frame up to the next, by a byte budget on the group.
 temporal_ref / delta_temporal_frames / undelta_temporal_frames / thin_frames / temporal_statuses state the temporal layers of the delta
 stream (svc_hip_delta_levels_temporal_frames, svc_hip_undelta_levels_temporal_frames): frame i coded against frame i - min(lowbit(i), period),
 so that every 2^s-th frame is the stream of period >> s of the thinned clip.
@@ -541,6 +543,65 @@ def delta_auto_frames(stream, offsets, forced=None, prev=None, period: int = 1) 
     keys = auto_keys(counts, forced, prev is not None)
     out, offs = delta_temporal_frames(stream, offsets, period, keys, prev)
     return out, offs, keys, counts
+
+
+# ---- a byte budget per group of frames for the delta stream (include/svc_hip_delta_budget.h: svc_hip_dct_pack_delta_budget_frames) ---------
+
+def delta_groups(keys, n: int):
+    """The groups of a delta stream of n frames -> a list of (first, end): a group starts at frame 0 and at every frame f with
+    keys[f] != 0, and runs up to the next start (keys None: one group).  Frame 0 starts a group whatever its flag."""
+    key = _keys(keys, n)
+    starts = [f for f in range(n) if f == 0 or key[f]]
+    return [(s, e) for s, e in zip(starts, starts[1:] + [n])]
+
+
+def delta_ladder_counts(streams, keys=None) -> np.ndarray:
+    """-> (n, L) u32: column k is header word 10 of every frame of delta_frames(*streams[k], keys), streams[k] = (bytes, offsets) of
+    the plain SVCQ stream of the same frames at ladder entry k (what svc_hip_dct_pack_levels_frames writes with that pair).  Frame 0
+    has no predecessor: it is a key frame at every entry.  A frame's tiles are predicted where the frame and its predecessor code
+    them at one step, which differs from entry to entry where an entry's fg_step equals its bg_step; and a difference is 0 where two
+    levels agree, which a coarser step does not make likelier in every coefficient: a column is NOT monotone in k."""
+    cols = []
+    for stream, offsets in streams:
+        out, offs = delta_frames(stream, offsets, keys)
+        cols.append([_level_count(fr) for fr in _source_frames(out, offs, None)])
+    return np.asarray(cols, np.uint32).T.reshape(len(cols[0]) if cols else 0, len(cols))
+
+
+def delta_budget_choice(counts, geometry: Dict[str, int], keys, budgets) -> np.ndarray:
+    """choice (n,) u32 of svc_hip_dct_pack_delta_budget_frames.  counts: (n, L) as delta_ladder_counts gives them; geometry: a dict with
+    the keys of GEOMETRY; budgets: one u32 byte count for every frame, or one each.  bytes_k(f) = up16(levels offset + 2 counts[f, k]),
+    the SVCQ frame's size.  Per group G of delta_groups the choice is the smallest k with sum_G bytes_k <= sum_G budgets (sums of 64
+    bits), found by looking at EVERY entry: bytes_k is not monotone in k, so an entry may fit behind one that does not.  If none fits:
+    L - 1 with bit 31 set.  Every frame of a group carries its group's value."""
+    counts = np.asarray(counts, np.uint32)
+    n, L = counts.shape
+    tiles = (geometry["frame_w"] // geometry["block_w"]) * (geometry["frame_h"] // geometry["block_h"])
+    mvb = (geometry["frame_w"] // geometry["mv_block_w"]) * (geometry["frame_h"] // geometry["mv_block_h"])
+    levels_off = levels.HEADER_BYTES + 4 * mvb + 8 * 3 * tiles * ((geometry["block_w"] * geometry["block_h"] + 63) // 64)
+    size = (levels_off + 2 * counts.astype(np.int64) + 15) // 16 * 16
+    budget = np.broadcast_to(np.asarray(budgets, np.int64), (n,))
+    choice = np.zeros(n, np.uint32)
+    for first, end in delta_groups(keys, n):
+        total, allowed = size[first:end].sum(axis=0), int(budget[first:end].sum())
+        fits = [k for k in range(L) if int(total[k]) <= allowed]
+        choice[first:end] = fits[0] if fits else (L - 1) | 0x80000000
+    return choice
+
+
+def delta_budget_frames(streams, keys, budgets) -> Tuple[bytes, np.ndarray, np.ndarray, np.ndarray]:
+    """What svc_hip_dct_pack_delta_budget_frames writes, given the plain streams of the same frames at every ladder entry ->
+    (bytes, offsets (n + 1,) u64, choice (n,) u32, counts (n, L) u32): frame f is frame f of
+    delta_frames(*streams[choice[f] & 0x7FFFFFFF], keys).  A group starts at a key frame, so no frame is predicted across a change of
+    steps: the result is delta_frames of the plain stream in which every frame is packed at its own chosen pair, and
+    undelta_frames(bytes, offsets, keys) gives that stream back."""
+    counts = delta_ladder_counts(streams, keys)
+    first = _source_frames(*streams[0], None)[0]
+    hdr = {k: int(v) for k, v in zip(levels.FIELDS, np.frombuffer(bytes(first[:levels.HEADER_BYTES]), "<u4"))}
+    choice = delta_budget_choice(counts, {k: hdr[k] for k in GEOMETRY}, keys, budgets)
+    coded = [_source_frames(*delta_frames(s, o, keys), None) for s, o in streams]
+    out, offs = _join([bytes(coded[int(c) & 0x7FFFFFFF][f]) for f, c in enumerate(choice)])
+    return out, offs, choice, counts
 
 
 # ---- a stored fine stream split into a base at any steps and its enhancement (include/svc_hip.h: svc_hip_split_levels_frames) ---------

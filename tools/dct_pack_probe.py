@@ -24,6 +24,14 @@
   python tools/dct_pack_probe.py quality-variants [C3|C5]
                                                    the quality call against a build of csrc/dct_pack.hip that computes every ladder entry
                                                    (SVC_DCT_PACK_MEASURE_SHARE=0), on the 32-entry ladder and on one whose every entry moves both steps
+  python tools/dct_pack_probe.py delta-budget [C3|C5]
+                                                   rate control of the delta stream: svc_hip_dct_pack_delta_budget_frames on the same batch and
+                                                   ladder with a key frame every 8, against (a) per entry svc_hip_dct_pack_delta_frames for the
+                                                   sizes plus one more encode, (b) that call at fixed steps and (c)
+                                                   svc_hip_dct_pack_levels_budget_frames; then entries, bytes and PSNR of this call and of the
+                                                   per-frame budgeted plain stream at the same budgets, on the synthetic clip and on a static
+                                                   background.  delta-budget-kernels: this call and the quality call five times each, for a
+                                                   kernel trace
   python tools/dct_pack_probe.py quality_step [C3|C5] [frames]
                                                    svc::ClipEncoder compact steps: fixed, under the budget, at a 40 dB target (SetCompactQuality)
   python tools/dct_pack_probe.py budget_step [C3|C5] [frames]
@@ -347,6 +355,93 @@ def quality(cfg, kernels_only=False) -> None:
                   f"{tuple(int(v) for v in lad[max(picks)])}), target not met in {int(((ch >> 30) & 1).sum())} frames, PSNR reached "
                   f"{min(psnr):.2f} .. {max(psnr):.2f} dB, {raw / n / 1e6:.4f} MB per frame raw, {coded_bytes(s[:raw], so) / n / 1e6:.4f} "
                   f"entropy-coded", flush=True)
+
+
+def delta_budget(cfg, kernels_only=False) -> None:
+    """svc_hip_dct_pack_delta_budget_frames, a batch of 16 with a key frame every 8 and the 32-entry ladder, against (a) the route a caller
+    had before it -- per entry svc_hip_dct_pack_delta_frames to read the sizes (all offsets fetched in one copy), then one more at the
+    chosen steps --, (b) svc_hip_dct_pack_delta_frames at fixed steps and (c) svc_hip_dct_pack_levels_budget_frames.  One process, the
+    routes in turn, the median of three rounds.  Then what it buys: entries, bytes and PSNR (the quality call's table) of this call and
+    of the per-frame budgeted plain stream at the same budgets, on the synthetic clip and on the static background.  kernels_only: this
+    call and the quality call five times each and nothing else, for a kernel trace."""
+    import numpy as np
+    from scalable_video_codec_amd import layers as lay
+    dev = torch.device("cuda")
+    n, interval = 16, 8
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    lad, per_frame = _budget(cfg)
+    key = torch.tensor([int(f % interval == 0) for f in range(n)], dtype=torch.int32, device=dev)
+    b = native.budget_tensor(per_frame, n, dev)
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out, out2 = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2))
+    wsg = torch.empty(native.dct_pack_delta_budget_workspace_bytes(n, pw, ph, block, mv, len(lad)), dtype=torch.uint8, device=dev)
+    wsd = torch.empty(native.dct_pack_delta_workspace_bytes(n, pw, ph, block, mv), dtype=torch.uint8, device=dev)
+    wsb = torch.empty(native.dct_pack_levels_budget_workspace_bytes(n, pw, ph, block, mv, len(lad)), dtype=torch.uint8, device=dev)
+    wsq = torch.empty(native.dct_pack_levels_quality_workspace_bytes(n, pw, ph, block, mv, len(lad)), dtype=torch.uint8, device=dev)
+    all_offs = torch.empty((len(lad), n + 1), dtype=torch.int64, device=dev)
+    top = native.target_tensor(2 ** 64 - 1, n, dev)
+
+    def group_call(frames=bgr, ty=types, budget=b, counts=False):
+        return native.dct_pack_delta_budget_frames(frames, block, ty, mv, lad, budget, key=key, out=out, workspace=wsg, counts=counts)
+
+    def by_hand():  # (a): every entry's delta stream for its sizes, the choice on the host, one more encode
+        for k, (fg, bg) in enumerate(lad):
+            native.dct_pack_delta_frames(bgr, block, types, mv, int(fg), int(bg), key=key, out=out2, offsets=all_offs[k], workspace=wsd)
+        sizes = np.diff(all_offs.cpu().numpy(), axis=1)  # (entries, frames)
+        for g in range(0, n, interval):
+            fits = [k for k in range(len(lad)) if sizes[k, g:g + interval].sum() <= per_frame * interval]
+            fg, bg = (int(v) for v in lad[fits[0] if fits else len(lad) - 1])
+            native.dct_pack_delta_frames(bgr[g:g + interval], block, types[g:g + interval], mv, fg, bg, out=out2, workspace=wsd)
+
+    def fixed():
+        return native.dct_pack_delta_frames(bgr, block, types, mv, cfg.fg_step, cfg.bg_step, key=key, out=out2, workspace=wsd)
+
+    def plain_budgeted(frames=bgr, ty=types, budget=b):
+        return native.dct_pack_levels_budget_frames(frames, block, ty, mv, lad, budget, out=out2, workspace=wsb)
+
+    def quality_call():
+        return native.dct_pack_levels_quality_frames(bgr, block, types, mv, lad, top, out=out2, workspace=wsq)
+
+    if kernels_only:
+        for fn in (group_call, quality_call):
+            for _ in range(5):
+                fn()
+        sync()
+        return
+    ms = _median3([group_call, fixed, plain_budgeted, quality_call], sync, steps=20)
+    ms_hand = _median3([by_hand], sync, steps=2)[0]
+    print(f"{cfg.name} batch of {n}, a key frame every {interval}, {len(lad)} entries, {per_frame} B per frame; ms per call (median of 3 rounds of "
+          f"20 back-to-back calls, the routes in turn): the group-budget call {ms[0]:.3f}; (a) {len(lad)} x svc_hip_dct_pack_delta_frames + one "
+          f"copy of the offsets + one more encode per group {ms_hand:.3f} ({ms_hand / ms[0]:.1f}x; 2 calls a round); (b) "
+          f"svc_hip_dct_pack_delta_frames at ({cfg.fg_step}, {cfg.bg_step}) {ms[1]:.3f} (the price of choosing: {ms[0] / ms[1]:.2f}x); (c) "
+          f"svc_hip_dct_pack_levels_budget_frames {ms[2]:.3f} ({ms[0] / ms[2]:.2f}x); the quality call {ms[3]:.3f}; workspace "
+          f"{wsg.numel() / n / 1e6:.2f} MB per frame against {wsd.numel() / n / 1e6:.2f} (delta) and {wsb.numel() / n / 1e6:.2f} (budgeted)", flush=True)
+
+    still, still_types = _still(bgr, types, pw, ph, mv)
+    for clip_name, frames, ty in (("the synthetic clip", bgr, types), ("a static background under a moving 128 x 128 patch", still, still_types)):
+        _, _, _, dist = native.dct_pack_levels_quality_frames(frames, block, ty, mv, lad, top, workspace=wsq, distortion=True)
+        sync()
+        dist = dist.cpu().numpy().view("uint64")
+        for percent in (100, 92, 85):  # (the masks alone are 74 % of the C3 budget: a frame has a floor no step gets under)
+            budget = native.budget_tensor(per_frame * percent // 100 // 16 * 16, n, dev)
+            _, so, ch = group_call(frames, ty, budget)
+            sync()
+            ch, total = ch.cpu().numpy().view("uint32"), int(so[-1])
+            picks = [int(c) & 0x7FFFFFFF for c in ch]
+            psnr = [lay.distortion_psnr(dist[f, k], pw, ph) for f, k in enumerate(picks)]
+            _, po, pch = plain_budgeted(frames, ty, budget)
+            sync()
+            pch, ptotal = pch.cpu().numpy().view("uint32"), int(po[-1])
+            ppicks = [int(c) & 0x7FFFFFFF for c in pch]
+            ppsnr = [lay.distortion_psnr(dist[f, k], pw, ph) for f, k in enumerate(ppicks)]
+            print(f"  {clip_name}, {per_frame * percent // 100 // 16 * 16} B per frame: this call entries {[picks[g] for g in range(0, n, interval)]} per group "
+                  f"(steps {[tuple(int(v) for v in lad[picks[g]]) for g in range(0, n, interval)]}), over budget {int((ch >> 31).sum())} frames, "
+                  f"{total / n / 1e6:.4f} MB per frame, PSNR {min(psnr):.2f} .. {max(psnr):.2f} dB (mean {sum(psnr) / n:.2f}); the per-frame budgeted "
+                  f"plain stream entries {min(ppicks)} .. {max(ppicks)}, over budget {int((pch >> 31).sum())} frames, {ptotal / n / 1e6:.4f} MB per "
+                  f"frame, PSNR {min(ppsnr):.2f} .. {max(ppsnr):.2f} dB (mean {sum(ppsnr) / n:.2f})", flush=True)
 
 
 def _measure_variant_lib(share):
@@ -1815,6 +1910,8 @@ if __name__ == "__main__":
         quality(_cfg(sys.argv, 2), kernels_only=mode == "quality-kernels")
     elif mode == "quality-variants":
         quality_variants(_cfg(sys.argv, 2))
+    elif mode in ("delta-budget", "delta-budget-kernels"):
+        delta_budget(_cfg(sys.argv, 2), kernels_only=mode == "delta-budget-kernels")
     elif mode == "quality_step":
         quality_step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
     elif mode == "layers":
