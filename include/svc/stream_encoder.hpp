@@ -77,6 +77,17 @@ struct StreamEncoderConfig {
                                    // carries it for every frame.  Accepted exactly when key_interval != 0, batch % key_interval == 0,
                                    // !auto_key, temporal_period == 1 and !entropy -- every batch then holds whole groups and nothing
                                    // is carried across batches; any other combination throws at construction
+  double compact_quality = 0;      // with `delta` and compact_ladder: a PSNR in dB that every frame holds, 0 = off
+                                   // (svc_hip_dct_pack_delta_quality_frames, include/svc_hip_delta_quality.h).  Per GROUP of frames, from a
+                                   // key frame up to the next, the coarsest pair of the ladder at which every frame of the group still
+                                   // reaches it; the bytes fall where the content is still.  The target in the units of D is
+                                   // floor(255^2 * 3 * padded_w * padded_h * 65536 / 10^(dB / 10)), at most 2^64 - 1.  With compact_budget
+                                   // also set the group's budget is a cap, under the rules `delta` states for it.
+                                   // EncodedBatch::compact_choice carries each frame's entry (bit 30: the target is not met, bit 31: over
+                                   // the cap), compact_distortion its D there.  SetCompactQuality changes it for a live stream.
+                                   // Accepted exactly with delta, key_interval != 0, batch % key_interval == 0, !auto_key,
+                                   // temporal_period == 1 and no enh_step -- every batch then holds whole groups; `entropy` is allowed (the
+                                   // frames are coded unchanged).  Any other combination throws at construction, naming the pair
   uint32_t key_interval = 0;       // with `delta`: the encoded frame with clip index f (as EncodedBatch::first_frame counts: the first
                                    // is 1) is a key frame iff f == 1, or key_interval != 0 and (f - 1) % key_interval == 0
   bool auto_key = false;           // with `delta` (without it the constructor throws): the key frames are chosen by size on the device
@@ -123,7 +134,11 @@ struct EncodedBatch {
   const uint64_t* compact_offsets = nullptr;  // [count + 1]: frame i in [offsets[i], offsets[i + 1])
   uint64_t compact_bytes = 0;                 // = compact_offsets[count]
   const uint32_t* compact_choice = nullptr;   // compact_budget != 0: [count] the ladder entry each frame was packed with, bit 31 set
-                                              // when even the last entry is over that frame's budget
+                                              // when even the last entry is over that frame's budget.  compact_quality != 0: the entry of
+                                              // the frame's group in bits 0 .. 29, bit 30 set when the group misses the target there, bit
+                                              // 31 when no entry fits the cap
+  const uint64_t* compact_distortion = nullptr;  // compact_quality != 0: [count] each frame's D at its chosen entry (include/svc_hip_quality.h;
+                                              // PSNR = 10 log10(255^2 * 3 * padded_w * padded_h * 65536 / D))
   const uint32_t* compact_key = nullptr;      // delta == true: [count] != 0 for a key frame, as svc::StreamDecoder::DecodeDelta and
                                               // svc_hip_undelta_levels_frames take them
   const uint32_t* compact_level_counts = nullptr;  // auto_key == true: [count][2] the levels of the frame as a key frame and as a
@@ -148,6 +163,7 @@ struct EncodeStats {
   double h2d_ms = 0, kernels_ms = 0, d2h_ms = 0;  // device, per stream
   uint64_t h2d_bytes = 0, d2h_bytes = 0;  // bytes actually moved (compact: the used bytes of the stream; two layers: of both)
   uint32_t over_budget_frames = 0;        // compact_budget != 0: frames that no ladder entry fit into (compact_choice bit 31)
+  uint32_t below_quality_frames = 0;      // compact_quality != 0: frames of groups that miss the target at their entry (compact_choice bit 30)
 };
 
 class StreamEncoder {
@@ -178,6 +194,10 @@ class StreamEncoder {
   // applies to the whole next clip.  Safe from any thread.  Throws std::logic_error on an encoder built without a budget, and
   // std::invalid_argument for 0.
   void SetCompactBudget(uint32_t bytes);
+
+  // The same for the quality target, a PSNR in dB: every frame of each batch STAGED after this returns.  Throws std::logic_error on an
+  // encoder built without compact_quality, and std::invalid_argument for a value that is not positive and finite.
+  void SetCompactQuality(double psnr_db);
 
   uint32_t padded_width() const;
   uint32_t padded_height() const;

@@ -135,6 +135,7 @@ DROPIN_APPS = [
     "stream_delta_encode_main",  # StreamEncoderConfig::delta: a raw clip -> the delta stream and its key flags, tests/test_gpu_stream_delta_encode.py
     "stream_delta_auto_main",  # StreamEncoderConfig::auto_key: a raw clip -> the delta stream with its key frames chosen by size, played by DecodeDelta: tests/test_gpu_stream_delta_auto.py
     "stream_delta_budget_main",  # StreamEncoderConfig::delta with compact_budget: a raw clip -> the delta stream with one ladder entry per group of frames, tests/test_gpu_stream_delta_budget.py
+    "stream_delta_quality_main",  # StreamEncoderConfig::delta with compact_quality: a raw clip -> the delta stream at a PSNR held per group of frames, tests/test_gpu_stream_delta_quality.py
     "stream_temporal_main",  # StreamEncoderConfig::temporal_period: a raw clip -> the delta stream with temporal layers, thinned and played by DecodeDeltaTemporal: tests/test_gpu_stream_temporal.py
     "stream_temporal_reduced_main",  # svc::StreamDecoder::DecodeDeltaTemporalReduced: a temporal-layer delta stream or its band -> display frames at 1/2, 1/4, 1/8 size, tests/test_gpu_stream_temporal_reduced.py
     "wire_decode_main",     # svc::StreamDecoder::DecodeWire: a reference stream on stdin -> display frames, tests/test_gpu_decode_records.py

@@ -77,6 +77,14 @@
 // dct_delta_ladder_sum_kernel adds the rows in kSumParts parts, dct_delta_group_select_kernel sums a group's bytes per entry, chooses over
 // all entries and writes every frame's steps; dct_pack_delta_group_kernel<N> (GROUP alone) is the delta form with those steps, and the
 // fused pack's scan and assemble follow.  The other forms' device code is what it was (profiles/dct_pack_delta_budget_c3.txt).
+//
+// A distortion target per group of frames (svc_hip_dct_pack_delta_quality_frames; include/svc_hip_delta_quality.h states it,
+// layers.delta_quality_choice in numpy): the same stream with the coarsest pair at which every frame of the group meets its target, under
+// the group's byte budget where there is one.  dct_delta_measure_kernel<N> is GROUP + TALLY + MEASURE of the body: the ladder tally, which
+// adds the measuring form's e^2 from the levels it already has and stores a second row per wave and frame -- both tables from one pass
+// over the pixels.  dct_delta_measure_sum_kernel adds both kinds of rows, dct_delta_quality_select_kernel chooses per group over all
+// entries and writes every frame's steps; the group form of the pack, scan and assemble follow.  The other forms' device code is what it
+// was, and the call built on the two older passes is slower (profiles/dct_pack_delta_quality_c3.txt).
 #include <algorithm>
 #include <type_traits>
 
@@ -86,6 +94,7 @@
 #include "stream_format.hpp"
 #include "svc_common.hpp"
 #include "svc_hip_delta_budget.h"
+#include "svc_hip_delta_quality.h"
 #include "svc_hip_quality.h"
 #include "svc_hip_temporal.h"
 
@@ -227,6 +236,10 @@ struct DeltaLadderArgs : DeltaRunArgs {
   LadderInv li;
   uint32_t* rows;  // [runs][waves of a frame][run][kMaxLadder]: the wave's non-zero differences of the frame at entry k (0 from the ladder's end on)
 };
+// what the delta form's measuring tally takes besides: where a wave leaves its row of squared errors per frame
+struct DeltaMeasureArgs : DeltaLadderArgs {
+  uint64_t* drows;  // [runs][waves of a frame][run][kMaxLadder]: the wave's sum of e^2 of the frame at entry k, beside rows
+};
 // Frames of a run.  {1, 2, 4, 8} measured at C3 and C5, batches of 16 (profiles/dct_pack_delta_c3.txt has all four): 8 is the fastest
 // or tied in every row -- at C3 / (1, 640) 0.194, 0.163, 0.152, 0.152 ms; at C5 1.065, 0.897, 0.820, 0.790.
 #ifndef SVC_DCT_PACK_DELTA_RUN  // (the probe that measured them builds this file once per value: tools/dct_pack_probe.py delta-encode)
@@ -252,6 +265,13 @@ constexpr bool kTemporalRedo = SVC_DCT_PACK_TEMPORAL_REDO != 0;
 #define SVC_DCT_PACK_MEASURE_SHARE 1
 #endif
 constexpr bool kMeasureShare = SVC_DCT_PACK_MEASURE_SHARE != 0;
+// svc_hip_dct_pack_delta_quality_frames takes both tables from one pass over the pixels (dct_delta_measure_kernel).  1: from two, the
+// measuring form then the ladder tally, with the same launches after them: the form the fused one was measured against in
+// profiles/dct_pack_delta_quality_c3.txt (tools/dct_pack_probe.py delta-quality builds this file once per value).
+#ifndef SVC_DCT_PACK_DELTA_QUALITY_TWO_PASS
+#define SVC_DCT_PACK_DELTA_QUALITY_TWO_PASS 0
+#endif
+constexpr bool kDeltaQualityTwoPass = SVC_DCT_PACK_DELTA_QUALITY_TWO_PASS != 0;
 constexpr uint32_t kTauTable = 2 * kMaxLadder;  // a class's thresholds, padded with +inf to what 7 probes can reach
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
@@ -316,19 +336,26 @@ __device__ __forceinline__ uint32_t sub2(uint32_t a, uint32_t b) {
 // counts, so any order of summing gives the same u32.  As in the measuring form, an entry at which no lane's step and no lane's
 // predicate differ from the entry before takes that entry's sum.  Lane k keeps entry k's sum over the three channels; the wave stores
 // that row per frame to a place of its own (no atomics, as the TALLY form).
+// MEASURE = true (with GROUP + TALLY): the form of svc_hip_dct_pack_delta_quality_frames (include/svc_hip_delta_quality.h), the ladder
+// tally with the measuring form's squared errors.  From the level q the tally already has of the channel's 16 coefficients at entry k the
+// lane adds e^2, e = rint(256 fma(-q, s, c)); the lane's u64 sum and its count go through ONE wave reduction (the count in the bits the
+// sum cannot reach), and lane k keeps entry k's two sums over the three channels: a second row per wave and frame, of u64.  The skip rule
+// is the union of both parents' -- the tally's already is: an entry is computed where any lane's step or predicate moved.
 template <int N, bool COUNT, bool LAYERS = false, bool DELTA = false, bool TALLY = false, int PERIOD = 1, bool REDO = false, bool MEASURE = false,
           bool GROUP = false>
 __device__ __forceinline__ void dct_pack_body(
     const DctPackArgs& a,
-    const std::conditional_t<MEASURE, MeasureArgs,
+    const std::conditional_t<MEASURE && TALLY && GROUP, DeltaMeasureArgs,
+    std::conditional_t<MEASURE, MeasureArgs,
     std::conditional_t<COUNT, CountArgs,
                              std::conditional_t<LAYERS, LayerArgs,
                                                 std::conditional_t<TALLY && GROUP, DeltaLadderArgs,
-                                                std::conditional_t<TALLY, DeltaTallyArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>>>>& k,
+                                                std::conditional_t<TALLY, DeltaTallyArgs, std::conditional_t<DELTA, DeltaRunArgs, NoCountArgs>>>>>>>& k,
     float (*tau_tab)[kTauTable], uint32_t (*hist_all)[kMaxLadder]) {
   static_assert(!GROUP || (DELTA && PERIOD == 1), "a group's steps: the delta form without temporal layers");
   constexpr bool kLadderTally = GROUP && TALLY;  // the counts of every ladder entry instead of the pack
-  static_assert(!MEASURE || COUNT, "the measuring form is the counting form with the squared errors");
+  static_assert(!MEASURE || COUNT || kLadderTally, "the measuring form is the counting form, or the ladder tally, with the squared errors");
+  constexpr bool kTallyMeasure = kLadderTally && MEASURE;  // the ladder tally with every entry's squared error beside its count
   static_assert(!(COUNT && LAYERS), "the counting form has no layers");
   static_assert(!(DELTA && (COUNT || LAYERS)), "the delta form is one layer at fixed steps");
   static_assert(!TALLY || DELTA, "the tally walks the delta form's runs");
@@ -374,10 +401,11 @@ __device__ __forceinline__ void dct_pack_body(
   bool redo = false;        // REDO: this trip transforms frame 4k again, in front of frame 4k + 4 (`it` stays at 4k + 3)
   uint32_t t_mid = 0;
   uint32_t full = 0;  // COUNT: this lane's coefficients that the whole ladder keeps
-  float kept[MEASURE ? 3 : 1][16];  // MEASURE: |c| of the lane's coefficients, all three channels, and the lane's class
+  float kept[MEASURE && COUNT ? 3 : 1][16];  // MEASURE: |c| of the lane's coefficients, all three channels, and the lane's class
   uint32_t cls = 0;
   float prior[kLadderTally ? 3 : 1][16] = {};  // kLadderTally: the f32 coefficients of the frame before, all three channels
   uint32_t tally_row = 0;                      // and, in lane k, the frame's count at ladder entry k
+  uint64_t measure_row = 0;                    // kTallyMeasure: and the frame's sum of e^2 at that entry
   bool frame_one_step = false;                 // GROUP: the trip's frame has fg == bg
   if constexpr (DELTA) {
     run_first = frame0 * k.run;
@@ -536,7 +564,7 @@ __device__ __forceinline__ void dct_pack_body(
         full += e[i] == k.lad.len ? 1u : 0u;
         if (e[i] != 0 && e[i] != k.lad.len) atomicAdd(&hist[e[i] - 1], 1u);
       }
-      if constexpr (MEASURE) {
+      if constexpr (MEASURE) {  // (COUNT: the measuring form)
         cls = t == 0 ? 0u : 1u;
 #pragma unroll
         for (int i = 0; i < 16; ++i) kept[c][i] = m[i];
@@ -548,6 +576,7 @@ __device__ __forceinline__ void dct_pack_body(
       // now and in the frame before.  Where the two steps differ the tile is not predicted at that entry -- the pack's predicate, per entry.
       if (it >= 0) {
         uint32_t total = 0, prev_step = 0;  // (no step is 0: the first entry is always computed)
+        uint64_t total_d = 0;               // kTallyMeasure: the entry's sum of e^2 over the wave, this channel
         bool prev_pred = false;
         for (uint32_t kk = 0; kk < k.lad.len; ++kk) {
           const uint32_t s_bg = k.lad.step[0][kk], s_fg = k.lad.step[1][kk];
@@ -557,18 +586,37 @@ __device__ __forceinline__ void dct_pack_body(
           if (__ballot(s_now != prev_step || pred != prev_pred) != 0) {  // the same in every lane; a lane for which nothing moved computes the count it had
             const float s = (float)s_now;
             uint32_t cnt = 0;
+            uint64_t sq = 0;
 #pragma unroll
             for (int i = 0; i < 16; i += 2) {
               const f32x2 q = quant2_level(f32x2{m[i], m[i + 1]}, s, inv);
               f32x2 qb = {0.f, 0.f};
               if (pred) qb = quant2_level(f32x2{prior[c][i], prior[c][i + 1]}, s, inv);
               cnt += (q.x != qb.x ? 1u : 0u) + (q.y != qb.y ? 1u : 0u);  // (integers in f32; -0.0 == 0.0, as both pack to level 0)
+              if constexpr (kTallyMeasure) {  // the measuring form's e from the same level: the quantiser is odd, so c's sign only flips e's
+                const uint32_t e0 = (uint32_t)fabsf(rintf(256.f * __builtin_fmaf(-q.x, s, m[i])));
+                const uint32_t e1 = (uint32_t)fabsf(rintf(256.f * __builtin_fmaf(-q.y, s, m[i + 1])));
+                sq += (uint64_t)e0 * e0;
+                sq += (uint64_t)e1 * e1;
+              }
             }
-            total = wave_sum(cnt);
+            if constexpr (kTallyMeasure) {
+              // One reduction for both: e^2 < 2^41 (the header's bound), a lane's 16 below 2^45 and the wave's below 2^51; the wave's
+              // count is at most 64 x 16 = 2^10.  The count rides in bits 52 .. 62 of the same u64.
+              uint64_t both = sq | ((uint64_t)cnt << 52);
+              for (uint32_t off = 32; off >= 1; off >>= 1) both += __shfl_xor(both, off, 64);
+              total = (uint32_t)(both >> 52);
+              total_d = both & ((1ull << 52) - 1);
+            } else {
+              total = wave_sum(cnt);
+            }
           }
           prev_step = s_now;
           prev_pred = pred;
           if (lane == kk) tally_row += total;
+          if constexpr (kTallyMeasure) {
+            if (lane == kk) measure_row += total_d;
+          }
         }
       }
 #pragma unroll
@@ -657,6 +705,10 @@ __device__ __forceinline__ void dct_pack_body(
   if constexpr (kLadderTally) {  // a place per wave and frame: a row of kMaxLadder counts, each at most 64 x 48
     if (it >= 0) k.rows[((size_t)wv * k.run + (uint32_t)it) * kMaxLadder + lane] = tally_row;
     tally_row = 0;
+    if constexpr (kTallyMeasure) {
+      if (it >= 0) k.drows[((size_t)wv * k.run + (uint32_t)it) * kMaxLadder + lane] = measure_row;
+      measure_row = 0;
+    }
   } else if constexpr (TALLY) {  // a wave's 64 x 48 coefficients: both sums fit their halves.  A place per wave and frame, no atomics: with
     // 65 280 adds into the one cache line that holds a batch's 32 counters the call took 0.709 ms at C3 (1, 640), with the stores 0.238
     // (profiles/dct_pack_delta_auto_c3.txt)
@@ -677,7 +729,7 @@ __device__ __forceinline__ void dct_pack_body(
     redo = again;
   }
   } while (DELTA && ((REDO && redo) || ++it < (int)run_len));
-  if constexpr (MEASURE) {
+  if constexpr (MEASURE && COUNT) {
     // x = |c| - q s is exact in one fma and 256 x is exact (the header argues both), so e is an integer below 2^21 whatever the order:
     // e^2 < 2^41, a lane's 48 below 2^47, a wave's below 2^53
     uint64_t mine = 0, total = 0;  // lane k keeps entry k's total
@@ -743,6 +795,12 @@ __global__ __launch_bounds__(256) void dct_pack_delta_group_kernel(DctPackArgs a
 template <int N>
 __global__ __launch_bounds__(256) void dct_delta_ladder_kernel(DctPackArgs a, DeltaLadderArgs k) {
   dct_pack_body<N, false, false, true, true, 1, false, false, true>(a, k, nullptr, nullptr);
+}
+
+// the ladder tally with every entry's squared error beside its count
+template <int N>
+__global__ __launch_bounds__(256) void dct_delta_measure_kernel(DctPackArgs a, DeltaMeasureArgs k) {
+  dct_pack_body<N, false, false, true, true, 1, false, true, true>(a, k, nullptr, nullptr);
 }
 
 // both with temporal layers: a frame against frame i - min(lowbit(i), PERIOD)
@@ -960,6 +1018,77 @@ __global__ __launch_bounds__(256) void dct_delta_group_select_kernel(Ladder lad,
   }
 }
 
+// The measuring tally's sum: dct_delta_ladder_sum_kernel on the counts and, in the same launch, on the squared errors, whose rows lie
+// the same way (drun == run; the two-pass build's measuring form leaves them frame by frame: drun == 1).
+__global__ __launch_bounds__(256) void dct_delta_measure_sum_kernel(uint32_t waves_per_frame, uint32_t run, const uint32_t* __restrict__ rows,
+                                                                    uint32_t* __restrict__ parts, uint32_t drun, const uint64_t* __restrict__ drows,
+                                                                    uint64_t* __restrict__ dparts) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  __shared__ uint64_t dpart[kThreads / 64][kMaxLadder];
+  const uint32_t f = blockIdx.y;
+  const size_t mine = (((size_t)(f / run) * waves_per_frame) * run + f % run) * kMaxLadder;  // wave 0 of the frame's run, this frame
+  const uint32_t v = sum_rows(rows + mine, blockIdx.x * run, kSumParts * run, waves_per_frame * run, part);
+  const size_t dmine = (((size_t)(f / drun) * waves_per_frame) * drun + f % drun) * kMaxLadder;
+  const uint64_t d = sum_rows(drows + dmine, blockIdx.x * drun, kSumParts * drun, waves_per_frame * drun, dpart);
+  if (threadIdx.x < kMaxLadder) {
+    parts[((size_t)f * kSumParts + blockIdx.x) * kMaxLadder + threadIdx.x] = v;
+    dparts[((size_t)f * kSumParts + blockIdx.x) * kMaxLadder + threadIdx.x] = d;
+  }
+}
+
+// One workgroup per frame; the one of a frame that starts a group works, as in dct_delta_group_select_kernel.  Frame by frame: count and
+// D of entry k in lane k (to the caller's tables where asked), the group's bytes and budget summed in 64 bits, and whether every frame so
+// far meets its own target at the entry.  Two ballots over ALL entries -- Q, the entries every frame meets its target at, and F, those
+// whose bytes fit (every entry without a budget) -- and the choice include/svc_hip_delta_quality.h states: max(Q & F); else min(F), bit 30;
+// else the last entry, bit 31, and bit 30 where it is not in Q.  Every frame of the group gets the value and the pair's steps.
+struct GroupQualitySelectArgs {
+  uint64_t levels_off;
+  const uint32_t* parts;
+  const uint64_t* dparts;
+  const uint32_t* key;      // [n] or null: one group
+  const uint64_t* target;   // [n]
+  const uint32_t* budget;   // [n] or null: no cap
+  FrameSteps* steps;
+  uint32_t* choice;
+  uint32_t* counts;         // [n][len] or null
+  uint64_t* distortion;     // [n][len] or null
+  uint32_t n_frames;
+};
+__global__ __launch_bounds__(256) void dct_delta_quality_select_kernel(Ladder lad, LadderInv li, GroupQualitySelectArgs a) {
+  __shared__ uint32_t part[kThreads / 64][kMaxLadder];
+  __shared__ uint64_t dpart[kThreads / 64][kMaxLadder];
+  const uint32_t first = blockIdx.x, lane = threadIdx.x & 63u;
+  if (first != 0 && !(a.key && a.key[first] != 0)) return;  // (the same in every thread, as the loop's trips below)
+  uint64_t bytes = 0, allowed = 0;
+  bool met = true;
+  uint32_t end = first;
+  do {
+    const uint32_t nz = sum_rows(a.parts + (size_t)end * kSumParts * kMaxLadder, 0, 1, kSumParts, part);
+    const uint64_t d = sum_rows(a.dparts + (size_t)end * kSumParts * kMaxLadder, 0, 1, kSumParts, dpart);
+    bytes += up16(a.levels_off + 2ull * nz);
+    if (a.budget) allowed += a.budget[end];
+    met = met && d <= a.target[end];
+    if (threadIdx.x < lad.len) {
+      if (a.counts) a.counts[(size_t)end * lad.len + threadIdx.x] = nz;
+      if (a.distortion) a.distortion[(size_t)end * lad.len + threadIdx.x] = d;
+    }
+    __syncthreads();  // part and dpart are rewritten by the next frame's sums
+    ++end;
+  } while (end < a.n_frames && !(a.key && a.key[end] != 0));
+  // every wave holds all entries: lane k has entry k
+  const uint64_t q = __ballot(lane < lad.len && met), f = __ballot(lane < lad.len && (!a.budget || bytes <= allowed));
+  uint32_t ch;
+  if (q & f) ch = 63u - (uint32_t)__builtin_clzll(q & f);
+  else if (f) ch = (uint32_t)__builtin_ctzll(f) | 0x40000000u;
+  else ch = (lad.len - 1) | 0x80000000u | ((q >> (lad.len - 1)) & 1ull ? 0u : 0x40000000u);
+  const uint32_t pick = ch & 0x3FFFFFFFu;
+  const FrameSteps fs{lad.step[1][pick], lad.step[0][pick], li.inv[1][pick], li.inv[0][pick]};
+  for (uint32_t g = first + threadIdx.x; g < end; g += kThreads) {
+    a.choice[g] = ch;
+    a.steps[g] = fs;
+  }
+}
+
 // one workgroup per frame: piece counts -> exclusive prefixes (in place), the frame's level count and size
 __global__ __launch_bounds__(256) void dct_pack_scan_kernel(uint32_t pieces, uint64_t levels_off, DctPackWs ws) {
   __shared__ uint32_t red[kThreads / 64];
@@ -1129,6 +1258,23 @@ DeltaBudgetWs delta_budget_ws(Carver& c, uint32_t n, const PackGeom& g) {
   s.rows = c.take<uint32_t>((uint64_t)kMaxLadder * kDeltaRun * div_up(n, kDeltaRun) * g.l.tiles_y * g.waves_per_row, false);
   s.parts = c.take<uint32_t>((uint64_t)kMaxLadder * n * kSumParts, false);
   s.steps = c.take<FrameSteps>(n);
+  return s;
+}
+
+// the group-quality call's workspace: the group-budget call's (so that call and the fixed delta call run on it too), then every wave's
+// row of squared errors per frame, laid out as the counts' rows, and their parts
+struct DeltaQualityWs {
+  DeltaBudgetWs budget;
+  uint64_t* drows;   // as DeltaMeasureArgs::drows
+  uint64_t* dparts;  // [n][kSumParts][kMaxLadder]
+  uint32_t* crows;   // kDeltaQualityTwoPass: [n][waves of a frame][kMaxLadder], the measuring form's rows of counts, which nothing reads
+};
+DeltaQualityWs delta_quality_ws(Carver& c, uint32_t n, const PackGeom& g) {
+  DeltaQualityWs s;
+  s.budget = delta_budget_ws(c, n, g);
+  s.drows = c.take<uint64_t>((uint64_t)kMaxLadder * kDeltaRun * div_up(n, kDeltaRun) * g.l.tiles_y * g.waves_per_row, false);
+  s.dparts = c.take<uint64_t>((uint64_t)kMaxLadder * n * kSumParts, false);
+  s.crows = kDeltaQualityTwoPass ? c.take<uint32_t>((uint64_t)kMaxLadder * n * g.l.tiles_y * g.waves_per_row, false) : nullptr;
   return s;
 }
 
@@ -1632,6 +1778,103 @@ int svc_hip_dct_pack_delta_budget_frames(const uint8_t* d_bgr, uint64_t frame_st
   hipLaunchKernelGGL(dct_delta_group_select_kernel, dim3(n_frames), blk, 0, s, t.lad, t.li, sel);
   if ((rc = check_launch(what, "select"))) return rc;
   a.steps = ws.steps;
+  if (block == 8) hipLaunchKernelGGL(dct_pack_delta_group_kernel<8>, grid, blk, 0, s, a, run);
+  else hipLaunchKernelGGL(dct_pack_delta_group_kernel<16>, grid, blk, 0, s, a, run);
+  if ((rc = check_launch(what, "transform"))) return rc;
+  return enqueue_assemble(what, a, a.ws, n_frames, 0, 0, d_out, d_frame_offsets, s);
+}
+
+// ---- the same with a distortion target per group, and the byte budget as an optional cap (include/svc_hip_delta_quality.h)
+
+uint64_t svc_hip_dct_pack_delta_quality_workspace_bytes(uint32_t n_frames, uint32_t frame_w, uint32_t frame_h, uint32_t block,
+                                                        uint32_t mv_block_w, uint32_t mv_block_h, uint32_t ladder_len) {
+  const char* what = "dct_pack_delta_quality_workspace_bytes";
+  if (validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h)) return 0;
+  if (ladder_len == 0 || ladder_len > kMaxLadder) {
+    (void)fail(SVC_ERR_INVALID_ARG, "%s: a ladder of %u entries (1 .. %u)", what, ladder_len, kMaxLadder);
+    return 0;
+  }
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (validate_pack_limits(what, n_frames, g)) return 0;
+  return layout_bytes(delta_quality_ws, n_frames, g);
+}
+
+// Checked in the order of svc_hip_dct_pack_delta_budget_frames: geometry, stride, ladder, limits (which bound a frame's coefficients below
+// 2^31: the u64 sums cannot overflow), sizes; n_frames == 0 then returns SVC_OK; then pointers.  Six launches whatever n_frames: the
+// measuring tally, its sum, the groups' selection, then the delta form's three with each frame's own steps.
+int svc_hip_dct_pack_delta_quality_frames(const uint8_t* d_bgr, uint64_t frame_stride_bytes, uint32_t n_frames, uint32_t frame_w,
+                                          uint32_t frame_h, uint32_t block, const uint32_t* d_block_types, uint32_t mv_block_w,
+                                          uint32_t mv_block_h, const svc_step_pair* ladder, uint32_t ladder_len, const uint32_t* d_key,
+                                          const uint64_t* d_target, const uint32_t* d_budget, uint8_t* d_workspace, uint64_t workspace_bytes,
+                                          uint8_t* d_out, uint64_t out_capacity, uint64_t* d_frame_offsets, uint32_t* d_choice,
+                                          uint32_t* d_level_counts, uint64_t* d_distortion, void* stream) {
+  const char* what = "dct_pack_delta_quality";
+  int rc = validate_pack_geom(what, frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if (rc) return rc;
+  SVC_REQUIRE(frame_stride_bytes >= 3ull * frame_w * frame_h && frame_stride_bytes % 16 == 0,
+              "%s: a frame stride of %llu B (at least the frame's %llu B, a multiple of 16)", what, (unsigned long long)frame_stride_bytes,
+              3ull * frame_w * frame_h);
+  if ((rc = validate_ladder(what, ladder, ladder_len))) return rc;
+  const PackGeom g = make_pack_geom(frame_w, frame_h, block, mv_block_w, mv_block_h);
+  if ((rc = validate_pack_limits(what, n_frames, g))) return rc;
+  if ((rc = require_workspace(what, workspace_bytes, layout_bytes(delta_quality_ws, n_frames, g)))) return rc;
+  if ((rc = require_capacity(what, "output", out_capacity, n_frames * g.l.max_bytes))) return rc;
+  if (n_frames == 0) return SVC_OK;  // empty batch: nothing to enqueue
+  SVC_REQUIRE(d_bgr && d_block_types && d_target && d_workspace && d_out && d_frame_offsets && d_choice, "%s: null pointer", what);
+  SVC_REQUIRE(aligned(d_bgr, 16) && aligned(d_out, 16) && aligned(d_workspace, 16) && aligned(d_frame_offsets, 8) && aligned(d_target, 8) &&
+                  aligned(d_distortion, 8) && aligned(d_block_types, 4) && aligned(d_key, 4) && aligned(d_budget, 4) && aligned(d_choice, 4) &&
+                  aligned(d_level_counts, 4),
+              "%s: frames, output and workspace must be 16-byte aligned, offsets, target and distortion 8-byte, types, key flags, budget, "
+              "choice and level counts 4-byte", what);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const DeltaQualityWs ws = carve(d_workspace, delta_quality_ws, n_frames, g);
+  const uint32_t waves_per_frame = g.l.tiles_y * g.waves_per_row;
+  DctPackArgs a{};
+  a.bgr = d_bgr;
+  a.frame_stride = frame_stride_bytes;
+  a.g = g;
+  a.types = d_block_types;
+  a.ws = ws.budget.pack;
+  a.total_waves = div_up(n_frames, kDeltaRun) * waves_per_frame;  // a wave per piece and RUN, as the pack below
+  const DeltaRunArgs run{nullptr, nullptr, d_key, n_frames, kDeltaRun, 0u};  // (one_step is each frame's own, from its steps)
+  DeltaMeasureArgs t{};
+  static_cast<DeltaRunArgs&>(t) = run;
+  t.lad = make_ladder(ladder, ladder_len);
+  for (uint32_t i = 0; i < ladder_len; ++i) {
+    t.li.inv[0][i] = 1.0f / (float)ladder[i].bg_step;
+    t.li.inv[1][i] = 1.0f / (float)ladder[i].fg_step;
+  }
+  t.rows = ws.budget.rows;
+  t.drows = ws.drows;
+  const dim3 grid(div_up(a.total_waves, 4)), blk(kThreads);
+  if constexpr (kDeltaQualityTwoPass) {  // the measuring form for D, a frame per wave, then the ladder tally for the counts
+    DctPackArgs m = a;
+    m.total_waves = n_frames * waves_per_frame;
+    MeasureArgs k{};
+    k.lad = t.lad;
+    while ((ladder_len >> k.probes) != 0) ++k.probes;
+    k.rows = ws.crows;
+    k.li = t.li;
+    k.drows = ws.drows;
+    const dim3 mgrid(div_up(m.total_waves, 4));
+    if (block == 8) hipLaunchKernelGGL(dct_measure_kernel<8>, mgrid, blk, 0, s, m, k);
+    else hipLaunchKernelGGL(dct_measure_kernel<16>, mgrid, blk, 0, s, m, k);
+    if ((rc = check_launch(what, "measure"))) return rc;
+    if (block == 8) hipLaunchKernelGGL(dct_delta_ladder_kernel<8>, grid, blk, 0, s, a, static_cast<const DeltaLadderArgs&>(t));
+    else hipLaunchKernelGGL(dct_delta_ladder_kernel<16>, grid, blk, 0, s, a, static_cast<const DeltaLadderArgs&>(t));
+  } else {
+    if (block == 8) hipLaunchKernelGGL(dct_delta_measure_kernel<8>, grid, blk, 0, s, a, t);
+    else hipLaunchKernelGGL(dct_delta_measure_kernel<16>, grid, blk, 0, s, a, t);
+  }
+  if ((rc = check_launch(what, "tally"))) return rc;
+  hipLaunchKernelGGL(dct_delta_measure_sum_kernel, dim3(kSumParts, n_frames), blk, 0, s, waves_per_frame, kDeltaRun, ws.budget.rows, ws.budget.parts,
+                     kDeltaQualityTwoPass ? 1u : kDeltaRun, ws.drows, ws.dparts);
+  if ((rc = check_launch(what, "sum"))) return rc;
+  const GroupQualitySelectArgs sel{g.l.levels_off, ws.budget.parts, ws.dparts, d_key, d_target, d_budget, ws.budget.steps, d_choice,
+                                   d_level_counts, d_distortion, n_frames};
+  hipLaunchKernelGGL(dct_delta_quality_select_kernel, dim3(n_frames), blk, 0, s, t.lad, t.li, sel);
+  if ((rc = check_launch(what, "select"))) return rc;
+  a.steps = ws.budget.steps;
   if (block == 8) hipLaunchKernelGGL(dct_pack_delta_group_kernel<8>, grid, blk, 0, s, a, run);
   else hipLaunchKernelGGL(dct_pack_delta_group_kernel<16>, grid, blk, 0, s, a, run);
   if ((rc = check_launch(what, "transform"))) return rc;

@@ -6,6 +6,7 @@
 #include "copy_crew.hpp"
 #include "encode_geometry.hpp"
 #include "svc_hip_delta_budget.h"
+#include "svc_hip_delta_quality.h"
 #include "svc_hip_temporal.h"
 
 #include <sched.h>
@@ -13,6 +14,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -56,9 +58,20 @@ struct Slot {
   PinBuf<uint32_t> pin_forced, pin_level_counts;
   // temporal_period > 1: the input frame at index -period of the batch's first encoded frame, copied on the device from the slot before
   DevBuf<uint8_t> before_bgr;
+  // compact_quality: the frames' targets, the table D[frame][entry] of the batch and, gathered at delivery, each frame's D at its entry
+  DevBuf<uint64_t> target, dist_table;
+  PinBuf<uint64_t> pin_target, pin_dist_table, pin_distortion;
   uint32_t frames = 0;  // source frames resident in bgr (the last one carries into the next batch)
   uint32_t encoded = 0, first = 0;
 };
+
+// layers.distortion_target: the largest D that still reaches psnr_db on a w x h frame, floor(255^2 * 3 w h * 65536 / 10^(dB / 10)), at most
+// 2^64 - 1.  In long double: exact wherever 10^(dB / 10) is an integer (the scale of a frame the stream calls take is below 2^64).
+uint64_t DistortionTarget(double psnr_db, uint32_t w, uint32_t h) {
+  const long double scale = 65025.0L * 3.0L * (long double)w * (long double)h * 65536.0L;
+  const long double d = std::floor(scale / std::pow(10.0L, (long double)psnr_db / 10.0L));
+  return d >= 18446744073709551615.0L ? ~0ull : (uint64_t)d;
+}
 
 }  // namespace
 
@@ -74,6 +87,8 @@ struct StreamEncoder::Impl : EncodeGeometry {
   bool layered = false;                           // enh_step != 0: a base and an enhancement stream
   bool temporal = false;                          // delta with temporal_period > 1: svc_hip_dct_pack_delta_temporal_frames
   std::atomic<uint32_t> budget{0};                // bytes per frame of the next batch staged (SetCompactBudget)
+  bool quality = false;                           // compact_quality != 0: a distortion target per group of frames, svc_hip_dct_pack_delta_quality_frames
+  std::atomic<uint64_t> target{0};                // in the units of D, for every frame of the next batch staged (SetCompactQuality)
   std::vector<std::unique_ptr<Slot>> slots;       // the buffers of the pipe's slots
   bool fused_records = false;  // wire: the transform kernel emits the records itself
   std::unique_ptr<CopyCrew> crew;
@@ -92,6 +107,18 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (!m.tw || !m.th) throw std::runtime_error("svc::StreamEncoder: invalid configuration");
   if (c.delta && c.wire) throw std::runtime_error("svc::StreamEncoder: the delta stream is a form of the compact stream, not of the wire records");
   if (c.delta && !c.compact) throw std::runtime_error("svc::StreamEncoder: the delta stream is a form of the compact stream");
+  // a quality target: the delta stream's, one pair of steps per group of frames, and a batch must hold whole groups as under a budget
+  if (c.compact_quality != 0) {
+    auto refuse = [](const std::string& why) { throw std::runtime_error("svc::StreamEncoder: compact_quality " + why); };
+    if (!(c.compact_quality > 0) || !std::isfinite(c.compact_quality)) refuse("is a PSNR in dB: positive and finite, or 0 for off");
+    if (!c.delta) refuse("holds every frame of the delta stream at a PSNR: not without delta");
+    if (c.enh_step) refuse("measures one layer: not with enh_step");
+    if (c.temporal_period > 1) refuse("picks one pair of steps per group of consecutive frames: not with temporal_period " + std::to_string(c.temporal_period));
+    if (c.auto_key) refuse("needs the groups before it chooses, auto_key the steps before it cuts them: not with auto_key");
+    if (c.key_interval == 0 || c.batch % c.key_interval != 0)
+      refuse("picks one pair of steps per group of frames, from a key frame up to the next: every batch must hold whole groups (key_interval " +
+             std::to_string(c.key_interval) + " must be positive and divide batch " + std::to_string(c.batch) + ")");
+  }
   // a byte budget with delta: one pair of steps per group of frames, and a batch must hold whole groups (svc_hip_dct_pack_delta_budget_frames
   // takes no frame before frame 0) -- key frames at a fixed interval that divides the batch, nothing chosen or referred to across them
   if (c.delta && c.compact_budget &&
@@ -124,8 +151,17 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   if (c.compact_budget && !c.compact) throw std::runtime_error("svc::StreamEncoder: a byte budget is a setting of the compact stream");
   m.budgeted = c.compact_budget != 0;
   m.budget.store(c.compact_budget);
-  m.group_budget = m.budgeted && c.delta;
-  if (m.group_budget) {  // the call's checks that need neither a device pointer nor a size: geometry, the ladder
+  m.quality = c.compact_quality != 0;
+  m.group_budget = m.budgeted && c.delta && !m.quality;
+  if (m.quality) {  // the call's checks that need neither a device pointer nor a size: geometry, the ladder
+    if (m.tw != m.th)
+      throw std::runtime_error("svc::StreamEncoder: the delta stream takes square transform blocks (8x8, 16x16), not " + std::to_string(m.tw) + "x" +
+                               std::to_string(m.th));
+    Abi(svc_hip_dct_pack_delta_quality_frames(nullptr, m.frame_bytes, 0, m.pw, m.ph, m.tw, nullptr, m.bw, m.bh, c.compact_ladder.data(),
+                                              (uint32_t)c.compact_ladder.size(), nullptr, nullptr, nullptr, nullptr, ~0ull, nullptr, ~0ull, nullptr,
+                                              nullptr, nullptr, nullptr, nullptr), "compact_ladder");
+    m.target.store(DistortionTarget(c.compact_quality, m.pw, m.ph));
+  } else if (m.group_budget) {  // the call's checks that need neither a device pointer nor a size: geometry, the ladder
     if (m.tw != m.th)
       throw std::runtime_error("svc::StreamEncoder: the delta stream takes square transform blocks (8x8, 16x16), not " + std::to_string(m.tw) + "x" +
                                std::to_string(m.th));
@@ -160,7 +196,8 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
   }
   if (c.compact) {
     m.packed_bytes = svc_hip_levels_max_bytes(c.batch, m.pw, m.ph, m.tw, m.th, m.bw, m.bh);
-    m.pack_ws_bytes = m.group_budget ? svc_hip_dct_pack_delta_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh, (uint32_t)c.compact_ladder.size())
+    m.pack_ws_bytes = m.quality ? svc_hip_dct_pack_delta_quality_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh, (uint32_t)c.compact_ladder.size())
+                      : m.group_budget ? svc_hip_dct_pack_delta_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh, (uint32_t)c.compact_ladder.size())
                       : m.budgeted ? svc_hip_pack_levels_budget_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th, (uint32_t)c.compact_ladder.size())
                       : m.layered ? svc_hip_pack_layers_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.th)
                       : c.auto_key ? svc_hip_dct_pack_delta_auto_workspace_bytes(c.batch, m.pw, m.ph, m.tw, m.bw, m.bh)
@@ -213,7 +250,13 @@ StreamEncoder::StreamEncoder(const StreamEncoderConfig& config) : p_(new Impl) {
       s->forced.Alloc(kWho, B); s->pin_forced.Alloc(kWho, B);
       s->level_counts.Alloc(kWho, 2 * B); s->pin_level_counts.Alloc(kWho, 2 * B);
     }
-    if (m.budgeted) { s->budget.Alloc(kWho, B); s->choice.Alloc(kWho, B); s->pin_budget.Alloc(kWho, B); s->pin_choice.Alloc(kWho, B); }
+    if (m.budgeted) { s->budget.Alloc(kWho, B); s->pin_budget.Alloc(kWho, B); }
+    if (m.budgeted || m.quality) { s->choice.Alloc(kWho, B); s->pin_choice.Alloc(kWho, B); }
+    if (m.quality) {
+      const size_t L = c.compact_ladder.size();
+      s->target.Alloc(kWho, B); s->pin_target.Alloc(kWho, B);
+      s->dist_table.Alloc(kWho, B * L); s->pin_dist_table.Alloc(kWho, B * L); s->pin_distortion.Alloc(kWho, B);
+    }
     m.slots.push_back(std::move(s));
   }
 }
@@ -227,6 +270,12 @@ void StreamEncoder::SetCompactBudget(uint32_t bytes) {
   if (!p_->budgeted) throw std::logic_error("svc::StreamEncoder: SetCompactBudget on an encoder built without compact_budget");
   if (bytes == 0) throw std::invalid_argument("svc::StreamEncoder: a byte budget of 0");
   p_->budget.store(bytes);
+}
+
+void StreamEncoder::SetCompactQuality(double psnr_db) {
+  if (!p_->quality) throw std::logic_error("svc::StreamEncoder: SetCompactQuality on an encoder built without compact_quality");
+  if (!(psnr_db > 0) || !std::isfinite(psnr_db)) throw std::invalid_argument("svc::StreamEncoder: a quality target is a PSNR in dB, positive and finite");
+  p_->target.store(DistortionTarget(psnr_db, p_->pw, p_->ph));
 }
 
 void StreamEncoder::Encode(const uint8_t* bgr, uint32_t n_frames, const Sink& sink) {
@@ -269,6 +318,11 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
       }
     if (m.budgeted)
       for (uint32_t i = 0; i < s.encoded; ++i) st.over_budget_frames += s.pin_choice.p[i] >> 31;
+    if (m.quality)  // each frame's D at its group's entry, out of the batch's table
+      for (uint32_t i = 0; i < s.encoded; ++i) {
+        st.below_quality_frames += (s.pin_choice.p[i] >> 30) & 1u;
+        s.pin_distortion.p[i] = s.pin_dist_table.p[(size_t)i * c.compact_ladder.size() + (s.pin_choice.p[i] & 0x3FFFFFFFu)];
+      }
     st.encoded_frames += s.encoded;
     const Clock::time_point t0 = Clock::now();
     EncodedBatch b;
@@ -279,7 +333,8 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     b.coeffs = c.wire || c.compact ? nullptr : s.pin_coeffs.p;
     if (c.compact) {
       b.compact = s.pin_packed.p; b.compact_offsets = s.pin_offsets.p; b.compact_bytes = s.pin_offsets.p[s.encoded];
-      b.compact_choice = m.budgeted ? s.pin_choice.p : nullptr;
+      b.compact_choice = m.budgeted || m.quality ? s.pin_choice.p : nullptr;
+      b.compact_distortion = m.quality ? s.pin_distortion.p : nullptr;
       b.compact_key = c.delta ? s.pin_key.p : nullptr;
       b.compact_level_counts = c.auto_key ? s.pin_level_counts.p : nullptr;
     }
@@ -349,6 +404,12 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         Hip(hipMemcpyAsync(s.budget.p, s.pin_budget.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyHostToDevice, si),
             "hipMemcpyAsync budget");
       }
+      if (m.quality) {  // the target as it stands now, for every frame of this batch (SetCompactQuality's rule)
+        const uint64_t d = m.target.load();
+        std::fill(s.pin_target.p, s.pin_target.p + encoded, d);
+        Hip(hipMemcpyAsync(s.target.p, s.pin_target.p, (size_t)encoded * sizeof(uint64_t), hipMemcpyHostToDevice, si),
+            "hipMemcpyAsync target");
+      }
       st.staging_ms += ms_since(t_stage);
       return (uint64_t)n_new * m.frame_bytes;
     };
@@ -374,6 +435,17 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         const uint32_t sw = c.reference_stream ? c.width : m.pw, sh = c.reference_stream ? c.height : m.ph;
         Abi(svc_hip_serialize_frames(s.coeffs.p, m.plane_elems, B, s.types.p, sw, sh, m.tw, m.th, m.mfw, m.mfh,
                                      m.bw, m.bh, s.records.p, m.record_bytes, sk), "svc_hip_serialize_frames");
+      } else if (m.quality) {  // every batch starts at a key frame and holds whole groups: no frame before, nothing carried
+        Abi(svc_hip_dct_pack_delta_quality_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.compact_ladder.data(),
+                                                  (uint32_t)c.compact_ladder.size(), s.key.p, s.target.p, m.budgeted ? s.budget.p : nullptr,
+                                                  s.pack_ws.p, m.pack_ws_bytes, s.packed.p, m.packed_bytes, s.offsets.p, s.choice.p, nullptr,
+                                                  s.dist_table.p, sk),
+            "svc_hip_dct_pack_delta_quality_frames");
+        if (c.entropy)
+          Abi(svc_hip_entropy_encode_frames(s.packed.p, m.packed_bytes, s.offsets.p, encoded, m.pw, m.ph, m.tw, m.th, m.bw, m.bh,
+                                            s.entropy_ws.p, m.entropy_ws_bytes, s.coded.p, m.coded_bytes, s.coded_offsets.p,
+                                            s.entropy_status.p, sk),
+              "svc_hip_entropy_encode_frames");
       } else if (m.group_budget) {  // every batch starts at a key frame and holds whole groups: no frame before, nothing carried
         Abi(svc_hip_dct_pack_delta_budget_frames(enc_bgr, m.frame_bytes, encoded, m.pw, m.ph, m.tw, s.types.p, m.bw, m.bh, c.compact_ladder.data(),
                                                  (uint32_t)c.compact_ladder.size(), s.key.p, s.budget.p, s.pack_ws.p, m.pack_ws_bytes, s.packed.p,
@@ -450,7 +522,7 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
     auto d2h = [&](hipStream_t so) -> uint64_t {
       uint64_t bytes = (uint64_t)encoded * ((uint64_t)m.blocks * 12 + 8 + (c.wire ? m.record_bytes : c.compact ? 0 : 3 * m.plane_elems * sizeof(float)));
       if (c.compact) bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t);  // + the stream's used bytes, known at delivery
-      if (m.budgeted || c.entropy) bytes += (uint64_t)encoded * sizeof(uint32_t);  // the choices, or the coder's statuses
+      if ((m.budgeted && !m.quality) || c.entropy) bytes += (uint64_t)encoded * sizeof(uint32_t);  // the choices, or the coder's statuses
       if (m.layered) {  // the enhancement stream, moved as the base is (its used bytes are added at delivery)
         bytes += (uint64_t)(encoded + 1) * sizeof(uint64_t) + (c.entropy ? (uint64_t)encoded * sizeof(uint32_t) : 0);
         if (c.entropy) {
@@ -464,6 +536,12 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
         }
         Hip(hipMemcpyAsync(s.pin_enh_offsets.p, c.entropy ? s.enh_coded_offsets.p : s.enh_offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, so), "D2H enhancement offsets");
+      }
+      if (m.quality) {  // the choices and the batch's table of distortions
+        const size_t L = c.compact_ladder.size();
+        bytes += (uint64_t)encoded * (sizeof(uint32_t) + L * sizeof(uint64_t));
+        Hip(hipMemcpyAsync(s.pin_choice.p, s.choice.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "D2H choice");
+        Hip(hipMemcpyAsync(s.pin_dist_table.p, s.dist_table.p, (size_t)encoded * L * sizeof(uint64_t), hipMemcpyDeviceToHost, so), "D2H distortion");
       }
       if (c.auto_key) {  // the chosen flags and the counts they were chosen by
         bytes += (uint64_t)encoded * 3 * sizeof(uint32_t);
@@ -488,7 +566,7 @@ void StreamEncoder::Encode(const Source& next, uint32_t header_frame_count, cons
                                  so), "svc_hip_levels_drain");
         Hip(hipMemcpyAsync(s.pin_offsets.p, s.offsets.p, (size_t)(encoded + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, so),
             "D2H offsets");
-        if (m.budgeted)
+        if (m.budgeted && !m.quality)
           Hip(hipMemcpyAsync(s.pin_choice.p, s.choice.p, (size_t)encoded * sizeof(uint32_t), hipMemcpyDeviceToHost, so), "D2H choice");
       } else
         Hip(hipMemcpyAsync(s.pin_coeffs.p, s.coeffs.p, (size_t)encoded * 3 * m.plane_elems * sizeof(float), hipMemcpyDeviceToHost, so), "D2H coeffs");

@@ -604,6 +604,60 @@ def delta_budget_frames(streams, keys, budgets) -> Tuple[bytes, np.ndarray, np.n
     return out, offs, choice, counts
 
 
+# ---- a distortion target per group of frames for the delta stream (include/svc_hip_delta_quality.h: svc_hip_dct_pack_delta_quality_frames)
+
+def delta_quality_choice(counts, table, geometry: Dict[str, int], keys, targets, budgets=None) -> np.ndarray:
+    """choice (n,) u32 of svc_hip_dct_pack_delta_quality_frames.  counts: (n, L) as delta_ladder_counts gives them; table: D (n, L) as
+    distortion_table gives it (the delta is lossless in levels: a frame's D does not depend on its flags); geometry: a dict with the keys
+    of GEOMETRY; targets: one u64 for every frame, or one each; budgets: None (no cap), or u32 bytes likewise.  Per group G of
+    delta_groups, looking at EVERY entry (neither table is monotone along a ladder):
+      Q = the entries k with D[f, k] <= targets[f] for every frame f of G (per frame, not a sum);
+      F = the entries k with sum_G bytes_k <= sum_G budgets (sums of 64 bits, bytes_k as in delta_budget_choice); every entry without budgets;
+      choice = max(Q & F) where that is not empty: the coarsest entry that meets the quality and fits;
+               else min(F) with bit 30 set where F is not empty: the finest entry that fits, quality not met;
+               else L - 1 with bit 31 set, and bit 30 set where L - 1 is not in Q.
+    Every frame of a group carries its group's value."""
+    counts = np.asarray(counts, np.uint32)
+    n, L = counts.shape
+    table = np.asarray(table, np.uint64).reshape(n, L)
+    tiles = (geometry["frame_w"] // geometry["block_w"]) * (geometry["frame_h"] // geometry["block_h"])
+    mvb = (geometry["frame_w"] // geometry["mv_block_w"]) * (geometry["frame_h"] // geometry["mv_block_h"])
+    levels_off = levels.HEADER_BYTES + 4 * mvb + 8 * 3 * tiles * ((geometry["block_w"] * geometry["block_h"] + 63) // 64)
+    size = (levels_off + 2 * counts.astype(np.int64) + 15) // 16 * 16
+    target = np.broadcast_to(np.asarray(targets, np.uint64), (n,))
+    budget = None if budgets is None else np.broadcast_to(np.asarray(budgets, np.int64), (n,))
+    choice = np.zeros(n, np.uint32)
+    for first, end in delta_groups(keys, n):
+        met = [k for k in range(L) if all(int(table[f, k]) <= int(target[f]) for f in range(first, end))]
+        fits = list(range(L))
+        if budget is not None:
+            total, allowed = size[first:end].sum(axis=0), int(budget[first:end].sum())
+            fits = [k for k in range(L) if int(total[k]) <= allowed]
+        both = [k for k in met if k in fits]
+        if both:
+            value = both[-1]
+        elif fits:
+            value = fits[0] | 0x40000000
+        else:
+            value = (L - 1) | 0x80000000 | (0 if L - 1 in met else 0x40000000)
+        choice[first:end] = value
+    return choice
+
+
+def delta_quality_frames(streams, table, keys, targets, budgets=None) -> Tuple[bytes, np.ndarray, np.ndarray, np.ndarray]:
+    """What svc_hip_dct_pack_delta_quality_frames writes, given the plain streams of the same frames at every ladder entry and their
+    distortion table -> (bytes, offsets (n + 1,) u64, choice (n,) u32, counts (n, L) u32): frame f is frame f of
+    delta_frames(*streams[choice[f] & 0x3FFFFFFF], keys).  As in delta_budget_frames a group starts at a key frame, so
+    undelta_frames(bytes, offsets, keys) gives back the plain stream in which every frame is packed at its own chosen pair."""
+    counts = delta_ladder_counts(streams, keys)
+    first = _source_frames(*streams[0], None)[0]
+    hdr = {k: int(v) for k, v in zip(levels.FIELDS, np.frombuffer(bytes(first[:levels.HEADER_BYTES]), "<u4"))}
+    choice = delta_quality_choice(counts, table, {k: hdr[k] for k in GEOMETRY}, keys, targets, budgets)
+    coded = [_source_frames(*delta_frames(s, o, keys), None) for s, o in streams]
+    out, offs = _join([bytes(coded[int(c) & 0x3FFFFFFF][f]) for f, c in enumerate(choice)])
+    return out, offs, choice, counts
+
+
 # ---- a stored fine stream split into a base at any steps and its enhancement (include/svc_hip.h: svc_hip_split_levels_frames) ---------
 
 MAX_RATIO = 32766  # of a base step to the fine step: |d| <= ratio / 2 stays an int16

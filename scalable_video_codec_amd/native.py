@@ -257,6 +257,15 @@ SIGNATURES_DELTA_BUDGET = {
                                                        _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
 }
 
+# The calls of include/svc_hip_delta_quality.h: a table of its own for the same reason; load() applies all six.
+SIGNATURES_DELTA_QUALITY = {
+    # the delta stream with one ladder entry per group of frames, by a distortion target on every frame of the group and an optional byte
+    # budget on the group (csrc/dct_pack.hip; host statements: layers.delta_quality_choice, layers.delta_quality_frames)
+    "svc_hip_dct_pack_delta_quality_workspace_bytes": (_u64, [_u32] * 7),
+    "svc_hip_dct_pack_delta_quality_frames": (C.c_int, [_vp, _u64] + [_u32] * 4 + [_vp] + [_u32] * 2 + [C.POINTER(StepPair), _u32, _vp, _vp, _vp, _vp,
+                                                        _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -270,7 +279,8 @@ def load() -> C.CDLL:
                 "(or __graft_entry__.build()); the MI355X path has no CPU fallback")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_TEMPORAL.items()) + list(SIGNATURES_TEMPORAL_DECODE.items()) +
-                                  list(SIGNATURES_QUALITY.items()) + list(SIGNATURES_DELTA_BUDGET.items())):
+                                  list(SIGNATURES_QUALITY.items()) + list(SIGNATURES_DELTA_BUDGET.items()) +
+                                  list(SIGNATURES_DELTA_QUALITY.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -1194,6 +1204,50 @@ def dct_pack_delta_budget_frames(bgr: torch.Tensor, block: int, block_types: tor
                                                        out.numel(), _dev(offsets, torch.int64), _dev(choice, torch.int32),
                                                        None if table is None else _dev(table, torch.int32), _stream()))
     return (out, offsets, choice, table) if counts else (out, offsets, choice)
+
+
+def dct_pack_delta_quality_workspace_bytes(n: int, w: int, h: int, block: int, mv_block, ladder_len: int) -> int:
+    """Scratch of dct_pack_delta_quality_frames; 0 for a geometry or a ladder length it refuses."""
+    mbw, mbh = _bwbh(mv_block)
+    return int(load().svc_hip_dct_pack_delta_quality_workspace_bytes(n, w, h, block, mbw, mbh, ladder_len))
+
+
+def dct_pack_delta_quality_frames(bgr: torch.Tensor, block: int, block_types: torch.Tensor, mv_block, ladder, target, budget=None,
+                                  key: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                                  workspace: Optional[torch.Tensor] = None, counts: bool = False, distortion: bool = False):
+    """B,G,R frames (frames, H, W, 3) u8 + region ids -> the delta stream (dct_pack_delta_frames without a frame before frame 0) with
+    one ladder entry per GROUP of frames -- from frame 0 or a frame with key[f] != 0 up to the next -- the coarsest entry at which every
+    frame of the group still meets its distortion target and the group's frames together fit the group's byte budget, if there is one
+    (include/svc_hip_delta_quality.h; layers.delta_quality_choice and layers.delta_quality_frames state it).  target as
+    dct_pack_levels_quality_frames takes it; budget: None (no cap), or as dct_pack_levels_budget_frames takes it; key: (frames,) i32 on
+    the device, or None: one group.  -> (stream u8 of the worst-case size, offsets (frames + 1,) i64, choice (frames,) i32 on the device:
+    the group's entry, bit 31 over budget, bit 30 target not met[, the counts of differences (frames, K) i32, with counts=True][, the
+    distortion table (frames, K) i64 holding u64 values, with distortion=True])."""
+    n, h, w, _ = bgr.shape
+    mbw, mbh = _bwbh(mv_block)
+    arr, k = _ladder(ladder)
+    dev = bgr.device
+    if out is None:
+        out = torch.empty(max(levels_max_bytes(n, w, h, block, mv_block), 16), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(dct_pack_delta_quality_workspace_bytes(n, w, h, block, mv_block, k), 16), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    choice = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    ctable = torch.empty((max(n, 1), max(k, 1)), dtype=torch.int32, device=dev)[:n] if counts else None
+    dtable = torch.empty((max(n, 1), max(k, 1)), dtype=torch.int64, device=dev)[:n] if distortion else None
+    if not (isinstance(target, torch.Tensor) and target.is_cuda):
+        target = target_tensor(target, n, dev)
+    if budget is not None and not (isinstance(budget, torch.Tensor) and budget.is_cuda):
+        budget = budget_tensor(budget, n, dev)
+    _check(load().svc_hip_dct_pack_delta_quality_frames(_dev(bgr, torch.uint8), h * w * 3, n, w, h, block,
+                                                        _dev(block_types, torch.int32), mbw, mbh, arr, k,
+                                                        None if key is None else _dev(key, torch.int32), _dev(target, torch.int64),
+                                                        None if budget is None else _dev(budget, torch.int32),
+                                                        _dev(workspace, torch.uint8), workspace.numel(), _dev(out, torch.uint8),
+                                                        out.numel(), _dev(offsets, torch.int64), _dev(choice, torch.int32),
+                                                        None if ctable is None else _dev(ctable, torch.int32),
+                                                        None if dtable is None else _dev(dtable, torch.int64), _stream()))
+    return (out, offsets, choice) + ((ctable,) if counts else ()) + ((dtable,) if distortion else ())
 
 
 def unpack_levels_frames(frames: torch.Tensor, offsets: torch.Tensor, w: int, h: int, block, mv_block,

@@ -32,6 +32,15 @@
                                                    per-frame budgeted plain stream at the same budgets, on the synthetic clip and on a static
                                                    background.  delta-budget-kernels: this call and the quality call five times each, for a
                                                    kernel trace
+  python tools/dct_pack_probe.py delta-quality [C3|C5]
+                                                   constant quality for the delta stream: svc_hip_dct_pack_delta_quality_frames on the same batch
+                                                   and ladder with a key frame every 8, against (a) a build of csrc/dct_pack.hip that takes the two
+                                                   tables from two passes (SVC_DCT_PACK_DELTA_QUALITY_TWO_PASS=1), (b) the route a caller had before
+                                                   it -- the quality call, the delta-budget call and one more delta-budget call standing in for the
+                                                   encode at the chosen steps -- and (c) svc_hip_dct_pack_delta_budget_frames alone; then entries,
+                                                   bytes raw and entropy-coded and PSNR at 40 dB and 30 dB, of this call and of the per-frame plain
+                                                   quality call, on the synthetic clip and on a static background.  delta-quality-kernels: this
+                                                   call five times, for a kernel trace
   python tools/dct_pack_probe.py quality_step [C3|C5] [frames]
                                                    svc::ClipEncoder compact steps: fixed, under the budget, at a 40 dB target (SetCompactQuality)
   python tools/dct_pack_probe.py budget_step [C3|C5] [frames]
@@ -442,6 +451,117 @@ def delta_budget(cfg, kernels_only=False) -> None:
                   f"{total / n / 1e6:.4f} MB per frame, PSNR {min(psnr):.2f} .. {max(psnr):.2f} dB (mean {sum(psnr) / n:.2f}); the per-frame budgeted "
                   f"plain stream entries {min(ppicks)} .. {max(ppicks)}, over budget {int((pch >> 31).sum())} frames, {ptotal / n / 1e6:.4f} MB per "
                   f"frame, PSNR {min(ppsnr):.2f} .. {max(ppsnr):.2f} dB (mean {sum(ppsnr) / n:.2f})", flush=True)
+
+
+def _delta_quality_two_pass_lib():
+    """csrc/dct_pack.hip built with both tables from two passes (SVC_DCT_PACK_DELTA_QUALITY_TWO_PASS=1), as _measure_variant_lib builds its
+    variant -> (the call, the workspace query)."""
+    import ctypes
+    import subprocess
+    from scalable_video_codec_amd import build
+    out = os.path.join(ROOT, "tools", "_bin", "libsvc_dct_pack_delta_quality_two_pass.so")
+    if not os.path.exists(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call([build._hipcc(), *build.HIPCC_FLAGS, "-DSVC_DCT_PACK_DELTA_QUALITY_TWO_PASS=1", "-shared", "-o", out,
+                               os.path.join(build.CSRC, "dct_pack.hip"), f"-L{build.PKG}", "-lsvc_hip", f"-Wl,-rpath,{build.PKG}"])
+    native.load()  # (first: the variant resolves the shared helpers in it)
+    lib = ctypes.CDLL(out)
+    for name, (res, args) in native.SIGNATURES_DELTA_QUALITY.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
+    return lib.svc_hip_dct_pack_delta_quality_frames, lib.svc_hip_dct_pack_delta_quality_workspace_bytes
+
+
+def delta_quality(cfg, kernels_only=False) -> None:
+    """svc_hip_dct_pack_delta_quality_frames, a batch of 16 with a key frame every 8 and the 32-entry ladder, at 40 dB with both tables asked
+    for, against (a) the two-pass build of the same call, (b) the route a caller had before it and (c) the delta-budget call alone.  One
+    process, the routes in turn, the median of three rounds; the two builds' outputs are compared.  Then what the targets give.
+    kernels_only: the call five times and nothing else, for a kernel trace."""
+    from scalable_video_codec_amd import layers as lay
+    dev = torch.device("cuda")
+    n, interval = 16, 8
+    pw, ph = cfg.padded
+    block, mv = cfg.dct_block, cfg.mv_block
+    mbw, mbh = native._bwbh(mv)
+    sync = torch.cuda.synchronize
+    bgr, types = _batch(cfg, n)
+    lad, per_frame = _budget(cfg)
+    arr, k = native._ladder(lad)
+    key = torch.tensor([int(f % interval == 0) for f in range(n)], dtype=torch.int32, device=dev)
+    b = native.budget_tensor(per_frame, n, dev)
+    t40, t30 = (native.target_tensor(lay.distortion_target(db, pw, ph), n, dev) for db in (40.0, 30.0))
+    cap = native.levels_max_bytes(n, pw, ph, block, mv)
+    out, out2 = (torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2))
+    ws = torch.empty(native.dct_pack_delta_quality_workspace_bytes(n, pw, ph, block, mv, k), dtype=torch.uint8, device=dev)
+    wsg = torch.empty(native.dct_pack_delta_budget_workspace_bytes(n, pw, ph, block, mv, k), dtype=torch.uint8, device=dev)
+    wsq = torch.empty(native.dct_pack_levels_quality_workspace_bytes(n, pw, ph, block, mv, k), dtype=torch.uint8, device=dev)
+
+    def call(frames=bgr, ty=types, target=t40, budget=None):
+        return native.dct_pack_delta_quality_frames(frames, block, ty, mv, lad, target, budget, key=key, out=out, workspace=ws, counts=True,
+                                                    distortion=True)
+
+    if kernels_only:
+        for _ in range(5):
+            call()
+        sync()
+        return
+    two_pass, two_pass_bytes = _delta_quality_two_pass_lib()
+    ws2 = torch.empty(two_pass_bytes(n, pw, ph, block, mbw, mbh, k), dtype=torch.uint8, device=dev)
+    res2 = (torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+            torch.empty((n, k), dtype=torch.int32, device=dev), torch.empty((n, k), dtype=torch.int64, device=dev))
+
+    def call_two_pass():
+        offs, ch, ct, dt = res2
+        native._check(two_pass(bgr.data_ptr(), pw * ph * 3, n, pw, ph, block, types.data_ptr(), mbw, mbh, arr, k, key.data_ptr(), t40.data_ptr(), None,
+                               ws2.data_ptr(), ws2.numel(), out2.data_ptr(), out2.numel(), offs.data_ptr(), ch.data_ptr(), ct.data_ptr(),
+                               dt.data_ptr(), native._stream()))
+
+    def group_budget():
+        return native.dct_pack_delta_budget_frames(bgr, block, types, mv, lad, b, key=key, out=out2, workspace=wsg, counts=True)
+
+    def before():  # (b): both tables from two calls; the host would choose here; the encode at the chosen steps costs a third call
+        native.dct_pack_levels_quality_frames(bgr, block, types, mv, lad, t40, out=out2, workspace=wsq, distortion=True)
+        group_budget()
+        group_budget()
+
+    ms = _median3([call, call_two_pass, before, group_budget], sync, steps=20)
+    call_two_pass()  # (last into out2: the routes above share it)
+    got = call()
+    sync()
+    used = int(got[1][-1])
+    same = all(torch.equal(a, r) for a, r in zip(got[1:], res2)) and torch.equal(got[0][:used], out2[:used])
+    print(f"{cfg.name} batch of {n}, a key frame every {interval}, {k} entries, 40 dB, both tables; ms per call (median of 3 rounds of 20 "
+          f"back-to-back calls, the routes in turn): the call (one pass) {ms[0]:.3f}; (a) the two-pass build {ms[1]:.3f} ({ms[1] / ms[0]:.2f}x; "
+          f"tables, choices, offsets and bytes {'equal' if same else 'DIFFER'}); (b) quality call + delta-budget call + one more delta-budget "
+          f"call {ms[2]:.3f} ({ms[2] / ms[0]:.2f}x); (c) svc_hip_dct_pack_delta_budget_frames alone {ms[3]:.3f} (the price of the second table: "
+          f"{ms[0] / ms[3]:.2f}x); workspace {ws.numel() / n / 1e6:.2f} MB per frame against {ws2.numel() / n / 1e6:.2f} (two passes) and "
+          f"{wsg.numel() / n / 1e6:.2f} (delta-budget)", flush=True)
+
+    def coded_bytes(stream, so):
+        _, eo, est = native.entropy_encode_frames(stream, so, pw, ph, block, mv)
+        sync()
+        assert not est.any()
+        return int(eo[-1])
+
+    still, still_types = _still(bgr, types, pw, ph, mv)
+    for clip_name, frames, ty in (("the synthetic clip", bgr, types), ("a static background under a moving 128 x 128 patch", still, still_types)):
+        for db, t in ((40.0, t40), (30.0, t30)):
+            s, so, ch, _, tab = call(frames, ty, t)
+            sync()
+            ch, tab, raw = ch.cpu().numpy().view("uint32"), tab.cpu().numpy().view("uint64"), int(so[-1])
+            picks = [int(c) & 0x3FFFFFFF for c in ch]
+            psnr = [lay.distortion_psnr(tab[f, kk], pw, ph) for f, kk in enumerate(picks)]
+            coded = coded_bytes(s[:raw].clone(), so.clone())
+            ps, pso, pch = native.dct_pack_levels_quality_frames(frames, block, ty, mv, lad, t, out=out2, workspace=wsq)
+            sync()
+            pch, praw = pch.cpu().numpy().view("uint32"), int(pso[-1])
+            ppicks = [int(c) & 0x3FFFFFFF for c in pch]
+            ppsnr = [lay.distortion_psnr(tab[f, kk], pw, ph) for f, kk in enumerate(ppicks)]
+            print(f"  {clip_name} at {db:g} dB: this call entries {[picks[g] for g in range(0, n, interval)]} per group (steps "
+                  f"{[tuple(int(v) for v in lad[picks[g]]) for g in range(0, n, interval)]}), target not met in {int(((ch >> 30) & 1).sum())} "
+                  f"frames, PSNR {min(psnr):.2f} .. {max(psnr):.2f} dB, {raw / n / 1e6:.4f} MB per frame raw, {coded / n / 1e6:.4f} entropy-coded; "
+                  f"the per-frame plain quality call entries {min(ppicks)} .. {max(ppicks)}, not met in {int(((pch >> 30) & 1).sum())}, PSNR "
+                  f"{min(ppsnr):.2f} .. {max(ppsnr):.2f} dB, {praw / n / 1e6:.4f} MB per frame raw, {coded_bytes(ps[:praw], pso) / n / 1e6:.4f} "
+                  f"entropy-coded ({praw / raw:.2f}x the bytes of this call)", flush=True)
 
 
 def _measure_variant_lib(share):
@@ -1912,6 +2032,8 @@ if __name__ == "__main__":
         quality_variants(_cfg(sys.argv, 2))
     elif mode in ("delta-budget", "delta-budget-kernels"):
         delta_budget(_cfg(sys.argv, 2), kernels_only=mode == "delta-budget-kernels")
+    elif mode in ("delta-quality", "delta-quality-kernels"):
+        delta_quality(_cfg(sys.argv, 2), kernels_only=mode == "delta-quality-kernels")
     elif mode == "quality_step":
         quality_step(_cfg(sys.argv, 2), int(sys.argv[3]) if len(sys.argv) > 3 else 300)
     elif mode == "layers":
