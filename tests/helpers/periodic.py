@@ -171,6 +171,43 @@ def row_mismatch(out, ref, k, restarts=(0,), what="row"):
     return f"{int(bad.sum())} of {n} {what}s differ from the prefix's, the first at frame {first}"
 
 
+def range_sums(rows, k, a, b, restarts=(0,)):
+    """The column sums of a per-frame row table over frames [a, b) of a periodic batch, as Python integers.  rows: the (2k, L) table of
+    the prefix, integers; the row of frame f is rows[f % k] in the cycles of `restarts` (frames, multiples of k) and rows[k + f % k]
+    elsewhere, as in row_mismatch.  Whole cycles x the cycle's sum + the head cycles + the remainder: no table of n rows is made and
+    nothing is held in a fixed width.  -> a list of L ints."""
+    r = [[int(v) for v in row] for row in np.asarray(rows).reshape(2 * k, -1)]
+    assert 0 <= a <= b and all(x % k == 0 for x in restarts)
+    heads = sorted(x // k for x in restarts)
+    L = len(r[0])
+    cum = [[[sum(row[j] for row in r[base:base + m]) for j in range(L)] for m in range(k + 1)] for base in (k, 0)]  # [period, head][m]
+
+    def upto(f):  # frames [0, f)
+        c, m = divmod(f, k)
+        h = sum(1 for x in heads if x < c)
+        part = cum[1 if c in heads else 0][m]
+        return [h * cum[1][k][j] + (c - h) * cum[0][k][j] + part[j] for j in range(L)]
+    return [y - x for x, y in zip(upto(a), upto(b))]
+
+
+def first_fit(fits, over=0x80000000):
+    """The budgeted calls' rule on one group: the first entry that fits, else the last with bit 31 set."""
+    return fits.index(True) if True in fits else (len(fits) - 1) | over
+
+
+def truncation_flips(totals, allowed, choose=first_fit, wrap=None):
+    """The precondition of a case on sums past `wrap`: with the group's bytes per entry (`totals`) or its budget (`allowed`) taken modulo
+    `wrap` -- either one alone -- the comparison bytes <= allowed comes out differently for some entry, and choose(fits per entry) gives
+    another value than with the whole sums.  Asserts both; -> the choice with the whole sums."""
+    wrap = WRAP if wrap is None else wrap
+    totals, allowed = [int(t) for t in totals], int(allowed)
+    whole = [t <= allowed for t in totals]
+    for what, fits in (("bytes", [t % wrap <= allowed for t in totals]), ("allowed", [t <= allowed % wrap for t in totals])):
+        assert fits != whole, f"{what} modulo {wrap}: every comparison stays {whole} (bytes {totals}, allowed {allowed})"
+        assert choose(fits) != choose(whole), f"{what} modulo {wrap}: the choice stays {choose(whole)} (bytes {totals}, allowed {allowed})"
+    return choose(whole)
+
+
 def repeat_rows(rows, n, device, dtype=torch.int32):
     """k rows of per-frame arguments (u32 values) repeated with the cycle -> (n, len(row)) i32 on `device`."""
     a = np.asarray(rows, dtype=np.uint32)

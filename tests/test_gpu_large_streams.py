@@ -25,7 +25,9 @@ Reduced, for memory: svc_hip_pack_layers_frames and svc_hip_pack_levels_budget_f
 side only (f * plane stride) -- for their streams to cross as well they would need 20 GB of planes and 11 GB of capacity per output;
 svc_hip_dct_pack_layers_frames runs past four trips of 256 frames only -- at the frame count where anything of it crosses 2^32 its
 workspace is 11 GiB beside two outputs of 5.6 GiB capacity.  Not here: the two drains (svc_hip_levels_drain, svc_hip_entropy_drain)
-would need 4 GiB of page-locked host memory; and flat indices past 2^32 COEFFICIENTS, which would need 8.6 GB of levels.
+would need 4 GiB of page-locked host memory; and flat indices past 2^32 COEFFICIENTS, which would need 8.6 GB of levels.  Elsewhere: the
+encoders that write the delta stream or choose by quality straight from pixels, and the reduced temporal decoder, on a cycle of their
+own: tests/test_gpu_large_streams_encoders.py.
 
 Nothing large goes to the host.  An output's capacity must be the worst case of n frames and the cycle's frames are three fifths of that on
 average, so a case holds more than its streams: the peak is 21 GiB (svc_hip_decode_layers_frames: two streams and rec).

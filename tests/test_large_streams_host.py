@@ -109,3 +109,46 @@ def test_offsets_taken_modulo_the_wrap_point_are_caught(call):
     report = pd.mismatch(_wrapped(exp, wrap), exp.offsets, exp, wrap)
     assert report is not None and f"frame {above}, the first to start at or above {wrap}, differs" in report, report
     assert f"{n - above} of the {n - above} frames from it on differ" in report, report
+
+
+def _entry_cycle(seed, densities):
+    """One cycle at the given level densities: the plain frames of one ladder entry (a coarser entry holds fewer levels)."""
+    rng = np.random.default_rng(seed)
+    w, h, tile, mv = GEOM
+    types = [random_types(rng, w, h, mv) for _ in densities]
+    frames = [layers.write_frame(geom_dict(*GEOM), t, random_levels(rng, w, h, d), 1, 1) for t, d in zip(types, densities)]
+    return frames, np.concatenate([[0], np.cumsum([len(f) for f in frames])]).astype(np.int64)
+
+
+def test_sums_of_a_periodic_table_and_the_truncation_precondition():
+    """pd.range_sums on the prefix's rows is the sum over the whole batch's rows, for a group that runs from frame 0 to a key frame in the
+    last whole cycle and for the group behind it; and the precondition of the long-group cases of tests/test_gpu_large_streams_encoders.py
+    -- a budget of exactly the group's bytes at entry 1 changes the choice once either sum is taken modulo the wrap point -- holds at a
+    modulus of 2^16 and fails where nothing is truncated."""
+    n = 4 * 40 + 3
+    key_at = 4 * (n // 4 - 1)
+    keys = np.zeros(n, np.int32)
+    keys[[0, key_at]] = 1
+    entries = [_entry_cycle(21, (1.0, 1.0, 0.5, 0.2)), _entry_cycle(22, (0.3, 0.3, 0.1, 0.2))]
+    floor = 64 + 4 * 1 + 8 * 3 * 4
+
+    def sizes(count, key):
+        counts = layers.delta_ladder_counts([_batch(fr, cyc, count) for fr, cyc in entries], key)
+        return (floor + 2 * counts.astype(np.int64) + 15) // 16 * 16
+    whole, rows = sizes(n, keys), sizes(2 * K, [1] + [0] * (2 * K - 1))
+    restarts = (0, key_at)
+    for a, b in ((0, key_at), (key_at, n), (0, n), (5, 4 * 9 + 2), (key_at - 1, key_at + 2), (7, 7)):
+        assert pd.range_sums(rows, K, a, b, restarts) == [int(v) for v in whole[a:b].sum(axis=0)], (a, b)
+    assert pd.range_sums(rows, K, 0, n) != pd.range_sums(rows, K, 0, n, restarts)  # the head's key frame counts where a cycle restarts
+    wrap = 1 << 16
+    totals = pd.range_sums(rows, K, 0, key_at, restarts)
+    assert totals[0] > totals[1] > wrap
+    allowed = totals[1]  # every frame its own bytes at entry 1
+    assert pd.truncation_flips(totals, allowed, wrap=wrap) == 1
+    budgets = whole[:, 1]
+    geometry = dict(zip(layers.GEOMETRY, (GEOM[0], GEOM[1], *GEOM[2], *GEOM[3])))
+    assert layers.delta_budget_choice((whole - floor) // 2, geometry, keys, budgets)[:key_at].tolist() == [1] * key_at
+    with pytest.raises(AssertionError, match="every comparison stays"):
+        pd.truncation_flips(totals, allowed, wrap=1 << 40)
+    with pytest.raises(AssertionError, match="the choice stays"):  # a rule that does not look at the comparisons
+        pd.truncation_flips(totals, allowed, choose=lambda fits: 0, wrap=wrap)
